@@ -7,7 +7,16 @@ Lattice.run_monte_carlo (reference lattice.rs:204-207) for 256 experiments at on
 already in HBM when the timed region starts; edge-list ingest, lattice recognition, the random start
 and the final energy/state read-back are outside it.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+
+A plain run sets up, pre-conditions, warms up, times the K steps and prints the result line.  Everything else the
+benchmark measures -- the cold steps, the roofline (streaming-copy ceiling, live shader clock, committed counters), the
+energy check, the binary's hashes and the CPU baseline -- runs only with --full.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what they computed, as a caller of Lattice.run_monte_carlo
+receives it: DIR/energies.npy (float64[R]) and DIR/spins_sample.npy (float32 0/1, [R, S]: the spins of S sites drawn with a
+fixed seed from every replica; the whole bool[R, 4096^2] array is 4 GiB).  Seeds, lattice and step counts are fixed by the
+arguments, so two builds given the same arguments can be compared output for output.
 
 --gpus N > 1 without WORLD_SIZE in the environment: this process starts N rank processes itself
 (torch.distributed.run, rendezvous on 127.0.0.1) BEFORE anything touches a GPU, relays their output and
@@ -15,9 +24,11 @@ exits with their code; launched under torchrun (WORLD_SIZE set) it is one of the
 shard: every rank runs its own 256 replicas (weak scaling), no data-path collective.  Rank 0 prints ONE
 JSON line.
 
-Timed region: after `--precondition-s` seconds of the same sweeps (reported as "precondition_s": the chip
+Timed region: after `--precondition-steps` of the same sweeps (their seconds reported as "precondition_s": the chip
 settles its clock a few tens of ms after the load step -- a cold 20-step run reads 20-25 % slow, see
-"cold_ms_per_step") and W warm-up steps, exactly K steps between barrier + synchronize pairs.
+"cold_ms_per_step" under --full) and W warm-up steps, exactly K steps between barrier + synchronize pairs.  The
+pre-conditioning is a fixed number of steps, not a time, so that the state entering the timed steps is the same in
+every run; the default (1250 steps) is the 0.5 s the chip needs at ~0.4 ms per step.
 """
 import argparse
 import json
@@ -37,6 +48,8 @@ SEED_GEN = 1
 BYTES_PER_ATTEMPT = 0.375  # read own + other colour plane, write own plane, bit-packed
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
 N_CU, SIMD_PER_CU = 256, 4
+DUMP_SITES = 16384         # spins per replica in --dump-outputs: 256 replicas x 16384 x 4 B = 16 MiB
+DUMP_BYTES = 32 << 20      # ... and fewer sites per replica when --replicas makes that exceed this
 
 
 def parse_args():
@@ -45,9 +58,12 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--replicas", type=int, default=REPLICAS_PER_GPU, help="replicas per GPU")
-    ap.add_argument("--precondition-s", type=float, default=0.5,
-                    help="seconds of untimed sweeps before the counted warm-up (device clock/power settle)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--precondition-steps", type=int, default=1250,
+                    help="untimed sweeps before the counted warm-up (device clock/power settle)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the cold steps, the roofline, the energy check, the hashes and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the timed steps' final energies and a spin sample as .npy")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend for --gpus > 1 (nccl = RCCL; gloo lets several ranks share one "
                          "GPU to rehearse the multi-rank path on a one-GPU box)")
@@ -177,6 +193,17 @@ def valu_bound(avg_launch_us, clock_ghz, quads_per_launch):
             "peak_source": "this run: HIP-event launch time x live shader clock"}
 
 
+def dump_outputs(states, nvars, out_dir):
+    """energies float64[R] and a fixed, seeded sample of the spins bool[R, nvars] (as float32) after the last timed step."""
+    import numpy as np
+    R = states.count
+    n = min(nvars, DUMP_SITES, DUMP_BYTES // (4 * R))
+    sites = np.sort(np.random.default_rng(SEED_GEN).choice(nvars, size=n, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "energies.npy"), states.energies())
+    np.save(os.path.join(out_dir, "spins_sample.npy"), states.states()[:, sites].astype(np.float32))
+
+
 def main():
     args = parse_args()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -221,15 +248,15 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # cold: the same K steps straight after the random start (reported, never `value`)
     barrier()
-    cold_ms = states.do_time_steps_timed(args.steps, BETA)
-    # pre-conditioning: >= precondition_s seconds of the same sweeps on the same state
+    cold_ms = 0.0
+    if args.full:  # cold: the same K steps straight after the random start (reported, never `value`)
+        cold_ms = states.do_time_steps_timed(args.steps, BETA)
+    # pre-conditioning: a fixed number of the same sweeps on the same state, 50 per call
     t0 = time.perf_counter()
-    pre_steps = 0
-    while time.perf_counter() - t0 < args.precondition_s:
-        states.do_time_steps(50, BETA)
-        pre_steps += 50
+    pre_steps = args.precondition_steps
+    for done in range(0, pre_steps, 50):
+        states.do_time_steps(min(50, pre_steps - done), BETA)
     precondition_s = time.perf_counter() - t0
     states.do_time_steps(args.warmup, BETA)
     barrier()
@@ -237,41 +264,18 @@ def main():
     device_ms = states.do_time_steps_timed(args.steps, BETA)  # blocking; HIP events on the engine's stream
     barrier()
     wall = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(states, nvars, args.dump_outputs)
 
     stats = torch.tensor([wall, device_ms, cold_ms], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
     if world > 1:
         dist.all_reduce(stats, op=dist.ReduceOp.MAX)
     wall, device_ms, cold_ms = float(stats[0]), float(stats[1]), float(stats[2])
 
-    # outside the timed region: energy per site at beta_c must be near -sqrt(2); live shader clock under the kernel
-    e_site = float(states.energies().mean()) / nvars
-    clock_ghz = states.shader_clock_ghz(60, BETA, probe_ms=10.0) if rank == 0 else None
-
     if rank == 0:
-        attempts = world * R * nvars * args.steps
-        launches = 2 * args.steps                       # one colour half-sweep of all replicas = one "launch"
-        bytes_per_launch = BYTES_PER_ATTEMPT * R * nvars / 2
-        avg_launch_us = device_ms * 1e3 / launches
-        achieved = bytes_per_launch / (avg_launch_us * 1e-6) / 1e9
-        traffic, traffic_meta = traffic_from_profile()
-        roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                    "traffic_source": "profiles/traffic_latest.json (committed rocprofv3 --pmc passes, not measured in this run; null when they "
-                                      "belong to another build)",
-                    **traffic_meta,
-                    "kernel": "lat_sweep_loop_kernel<uniformJ> (2 quads per thread; replicas in 2 stream lanes)",
-                    "algorithmic_bytes_per_launch": bytes_per_launch,
-                    "avg_launch_us": avg_launch_us,
-                    "launch": "one colour half-sweep of all replicas (2 kernel dispatches, one per lane)"}
-        copy_gbs = copy_ceiling_gbs(torch)
-        roofline["copy_ceiling"] = {"achieved": achieved, "peak": copy_gbs, "unit": "GB/s", "frac": achieved / copy_gbs,
-                                    "peak_source": "this run: 2 GiB device-to-device copy (better of the runtime copy and an elementwise kernel), read + written bytes per second"}
-        sec = valu_bound(avg_launch_us, clock_ghz, R * nvars / 2 / 128 / 64)  # wave-quads: 64 lanes x 128 spins
-        if sec:
-            roofline["secondary"] = sec
         out = {
             "metric": "spin-flip attempts/s (whole node), 4096^2 2D Ising",
-            "value": attempts / wall,
+            "value": world * R * nvars * args.steps / wall,
             "unit": "spin-flip attempts/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": wall * 1e3 / args.steps,
@@ -281,16 +285,45 @@ def main():
                                    "checkerboard Metropolis, bit-packed spins, Philox4x32-10",
                        "replicas_per_gpu": R, "lattice": [L, L], "beta": BETA, "parallelism": f"replicas x{world}"},
             "precondition_s": precondition_s, "precondition_steps": pre_steps,
-            "cold_ms_per_step": cold_ms / args.steps,
-            "roofline": roofline,
             "device_attempts_per_s": R * nvars * args.steps / (device_ms * 1e-3),
-            "shader_clock_ghz": clock_ghz,
-            "energy_per_site": e_site,
             "ingest_s": t_ingest,
-            "library_sha256": library_sha256(), "source_sha256": source_sha256(),
         }
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(ea, eb, ej, nvars)
+    if args.full:
+        # outside the timed region: energy per site at beta_c must be near -sqrt(2); live shader clock under the kernel
+        e_site = float(states.energies().mean()) / nvars
+        clock_ghz = states.shader_clock_ghz(60, BETA, probe_ms=10.0) if rank == 0 else None
+
+        if rank == 0:
+            launches = 2 * args.steps                       # one colour half-sweep of all replicas = one "launch"
+            bytes_per_launch = BYTES_PER_ATTEMPT * R * nvars / 2
+            avg_launch_us = device_ms * 1e3 / launches
+            achieved = bytes_per_launch / (avg_launch_us * 1e-6) / 1e9
+            traffic, traffic_meta = traffic_from_profile()
+            roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                        "traffic_source": "profiles/traffic_latest.json (committed rocprofv3 --pmc passes, not measured in this run; null when they "
+                                          "belong to another build)",
+                        **traffic_meta,
+                        "kernel": "lat_sweep_loop_kernel<uniformJ> (2 quads per thread; replicas in 2 stream lanes)",
+                        "algorithmic_bytes_per_launch": bytes_per_launch,
+                        "avg_launch_us": avg_launch_us,
+                        "launch": "one colour half-sweep of all replicas (2 kernel dispatches, one per lane)"}
+            copy_gbs = copy_ceiling_gbs(torch)
+            roofline["copy_ceiling"] = {"achieved": achieved, "peak": copy_gbs, "unit": "GB/s", "frac": achieved / copy_gbs,
+                                        "peak_source": "this run: 2 GiB device-to-device copy (better of the runtime copy and an elementwise kernel), read + written bytes per second"}
+            sec = valu_bound(avg_launch_us, clock_ghz, R * nvars / 2 / 128 / 64)  # wave-quads: 64 lanes x 128 spins
+            if sec:
+                roofline["secondary"] = sec
+            out.update({
+                "cold_ms_per_step": cold_ms / args.steps,
+                "roofline": roofline,
+                "shader_clock_ghz": clock_ghz,
+                "energy_per_site": e_site,
+                "library_sha256": library_sha256(), "source_sha256": source_sha256(),
+            })
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(ea, eb, ej, nvars)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

@@ -44,7 +44,7 @@ def test_bare_bench_invocation_spawns_its_ranks():
     ranks itself and rank 0 prints the one JSON line with n_gpus = 2.  gloo backend: both ranks share this box's GPU."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                          "--replicas", "8", "--precondition-s", "0.05", "--backend", "gloo"], env=env, capture_output=True,
+                          "--replicas", "8", "--precondition-steps", "50", "--backend", "gloo", "--full"], env=env, capture_output=True,
                          text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -55,12 +55,12 @@ def test_bare_bench_invocation_spawns_its_ranks():
 
 
 def test_single_gpu_bench_line_keeps_the_contract():
-    """`python bench.py --gpus 1 --steps K --warmup W` (the driver's form): ONE JSON line on stdout with the contract's keys, the
+    """`python bench.py --gpus 1 --steps K --warmup W --full`: ONE JSON line on stdout with the contract's keys, the
     `roofline` and `cpu_baseline` objects, and numbers that agree with each other (value x ms_per_step, achieved / peak = frac,
     algorithmic bytes per launch = SURVEY 8d's 0.375 B per attempt x the attempts of one colour half-sweep)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"], env=env,
-                         capture_output=True, text=True, timeout=900)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"],
+                         env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -86,6 +86,36 @@ def test_single_gpu_bench_line_keeps_the_contract():
         assert key in cpu, key
     assert cpu["kind"] == "port" and cpu["cores"] >= 1 and 1e6 < cpu["value"] < 1e10 and rec["value"] > 100 * cpu["value"]
     assert -1.6 < rec["energy_per_site"] < -1.0
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W` (the driver's form) measures the headline only: the contract's keys, none of
+    --full's.  --dump-outputs writes the final energies and a spin sample of the timed path: the same in two runs, and values
+    that a run near beta_c gives."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3",
+                              "--replicas", "16", "--precondition-steps", "120", "--dump-outputs", str(d)], env=env,
+                             capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        rec = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype"):
+            assert key in rec, key
+        for key in ("roofline", "cpu_baseline", "cold_ms_per_step", "energy_per_site", "shader_clock_ghz"):
+            assert key not in rec, key
+        assert rec["steps"] == 7 and rec["precondition_steps"] == 120
+        assert abs(rec["value"] * rec["ms_per_step"] * 1e-3 / (16 * 4096 * 4096) - 1.0) < 1e-9
+        assert sorted(os.listdir(d)) == ["energies.npy", "spins_sample.npy"]
+        dumps.append((np.load(d / "energies.npy"), np.load(d / "spins_sample.npy")))
+    (e0, s0), (e1, s1) = dumps
+    assert e0.dtype == np.float64 and e0.shape == (16,) and s0.dtype == np.float32 and s0.shape == (16, 16384)
+    assert np.array_equal(e0, e1) and np.array_equal(s0, s1)
+    assert set(np.unique(s0)) <= {0.0, 1.0} and 0.3 < s0.mean() < 0.7
+    assert np.all(-2.0 < e0 / 4096 ** 2) and np.all(e0 / 4096 ** 2 < -1.0)
 
 
 def test_sharded_c3_ladder_matches_the_in_kernel_exchange(tmp_path):

@@ -102,7 +102,9 @@ def test_python_shim_under_asan_and_ubsan(tmp_path):
     probe = subprocess.run(["python", "-c", "import py_monte_carlo, pyisingmontecarlo_amd._py_monte_carlo as m; print(m.__file__)"],
                            env=env, capture_output=True, text=True, timeout=600, cwd=str(scratch))     # cwd leads sys.path
     assert probe.returncode == 0 and str(scratch) in probe.stdout, (probe.stdout + probe.stderr)[-3000:]
-    out = subprocess.run(["python", "-m", "pytest", "-x", "-q", "-p", "no:cacheprovider", "-m", "not gpu",
+    # --rootdir: pytest would otherwise root the run at the common ancestor of the scratch cwd and the checkout (possibly "/")
+    # and collect its way down through directories this user may not be allowed to list
+    out = subprocess.run(["python", "-m", "pytest", "-x", "-q", "-p", "no:cacheprovider", "-m", "not gpu", "--rootdir", ROOT,
                           os.path.join(ROOT, "tests", "test_api_surface.py")], env=env, capture_output=True, text=True, timeout=1500,
                          cwd=str(scratch))
     assert out.returncode == 0, (out.stdout + out.stderr)[-4000:]

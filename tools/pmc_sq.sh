@@ -1,10 +1,10 @@
 #!/bin/bash
 # SQ counter passes for the sweep kernel (per-launch means printed as JSON): tools/pmc_sq.sh <tag> [<python script> [args]]
-# default command: bench.py --steps 20 --warmup 2 --no-cpu-baseline; KFILTER=<substring of the kernel name> (default lat_sweep)
+# default command: bench.py --full --steps 20 --warmup 2 --no-cpu-baseline; KFILTER=<substring of the kernel name> (default lat_sweep)
 set -uo pipefail
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/pmc_sq_$1; shift
-if [ $# -eq 0 ]; then set -- bench.py --steps 20 --warmup 2 --no-cpu-baseline; fi
+if [ $# -eq 0 ]; then set -- bench.py --full --steps 20 --warmup 2 --no-cpu-baseline; fi
 export KFILTER=${KFILTER:-lat_sweep}
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp

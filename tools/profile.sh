@@ -8,8 +8,8 @@ set -euo pipefail
 TAG=${1:-r01}; shift || true
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
-ARGS=${*:---steps 50 --warmup 5 --no-cpu-baseline}   # PMC passes: counters are per launch
-TRACE_ARGS=${TRACE_ARGS:---no-cpu-baseline}          # trace pass: the default bench (1000 steps + 100 warm-up)
+ARGS=${*:---full --steps 50 --warmup 5 --no-cpu-baseline}   # PMC passes: counters are per launch
+TRACE_ARGS=${TRACE_ARGS:---full --no-cpu-baseline}   # trace pass: the default bench (1000 steps + 100 warm-up)
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 "$ROOT/bench.py" $TRACE_ARGS > "$OUT/trace.log" 2>&1
