@@ -581,6 +581,7 @@ extern "C" int isingmc_graph_create(const uint64_t *ea, const uint64_t *eb, cons
     TRY(use_device(device));
     auto g = std::make_unique<isingmc_graph>();
     g->device = device;
+    (void)hipDeviceGetAttribute(&g->n_cu, hipDeviceAttributeMultiprocessorCount, device);
     g->nvars = nvars;
     g->n_edges = n_edges;
     g->has_bias = has_bias;

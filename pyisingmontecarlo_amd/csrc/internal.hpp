@@ -10,6 +10,7 @@
 #include <sys/mman.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -179,6 +180,7 @@ struct isingmc_graph {
     bool stable_path = false;             // ISINGMC_FLAG_STABLE_PATH: the kernel family never depends on the number of experiments
     Options opt;                          // the environment's switches when the graph was created
     std::vector<uint32_t> class_real_end; // per colour class: end of its real sites (the padding follows)
+    int n_cu = 256;                       // compute units of the device (queried once, at creation)
     std::vector<void *> dev_allocs;
 
     ~isingmc_graph()
@@ -393,3 +395,28 @@ IM_INTERNAL int strip_error(int rc);
 IM_INTERNAL bool may_use_strips(const isingmc_states *s);
 IM_INTERNAL int snapshot_take(isingmc_states *s);
 IM_INTERNAL int snapshot_restore(isingmc_states *s);
+
+// counter pairs of a measurement (measure_enqueue): one per (group, bit) slot of a packed container, one per replica otherwise
+static inline size_t counter_slots(const isingmc_states *s) { return s->packed ? s->pk_slots() : s->R; }
+static inline size_t counter_slot(const isingmc_states *s, size_t r) { return s->packed ? r + s->pk_bit0 : r; }
+static inline double counters_energy(const isingmc_states *s, unsigned long long c0, unsigned long long c1)
+{
+    return s->packed ? pk_energy(s->g, s->rj, c0, c1) : lattice_energy(s->g, c0, c1);
+}
+
+// A synchronous call that may launch the strip kernel keeps the planes it started from: if a launch gives up (its workgroups
+// were not all resident: a co-tenant, a CU mask), the planes and the clock are put back and the call is repeated, on the
+// per-colour launches by then (strip_check has disabled the strip kernel of the object).
+template <typename F>
+static int with_strip_retry(isingmc_states *s, bool may_strip, F &&call)
+{
+    if (!may_strip) return strip_error(call());
+    TRY(use_device(s->g->device));
+    const uint64_t t0 = s->t;
+    TRY(snapshot_take(s));
+    const int rc = call();
+    if (rc != STRIP_TIMED_OUT) return rc;
+    TRY(snapshot_restore(s));
+    s->t = t0;
+    return strip_error(call());
+}

@@ -551,152 +551,6 @@ double pk_energy(const isingmc_graph *g, bool rj, unsigned long long c0, unsigne
     return g->jabs * (double(int64_t(g->n_directed / 2)) - double(int64_t(c0))) + g->self_energy;
 }
 
-static int pk_measure(isingmc_states *s, double *energies, int64_t *mags)
-{
-    const isingmc_graph *g = s->g;
-    const size_t R = s->R;
-    if (s->rj && energies && mags) { // the second counter of a slot holds the lo level of the energy OR the up spins
-        TRY(pk_measure(s, energies, nullptr));
-        return pk_measure(s, nullptr, mags);
-    }
-    TRY(measure_enqueue(s, s->d_meas, nullptr, nullptr, /*want_up=*/mags != nullptr));
-    s->meas_zero = false;
-    std::vector<unsigned long long> h(2 * s->pk_slots());
-    HIP_TRY(hipMemcpyAsync(h.data(), s->d_meas, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    for (size_t r = 0; r < R; r++) {
-        const size_t sl = r + s->pk_bit0;
-        if (energies) energies[r] = pk_energy(g, s->rj, h[2 * sl], h[2 * sl + 1]);
-        if (mags) mags[r] = 2 * int64_t(h[2 * sl + 1]) - int64_t(g->nvars);
-    }
-    return ISINGMC_OK;
-}
-
-static int pk_run_steps(isingmc_states *s, size_t timesteps, const double *betas, size_t beta_stride,
-                        double *energies_per_step, float *device_ms, bool sync)
-{
-    const isingmc_graph *g = s->g;
-    const size_t R = s->R, CS = s->pk_slots();
-    DeviceScratch scratch(s->stream);
-    uint32_t *d_step_tabs = nullptr;
-    RjBeta *d_rj_steps = nullptr; // real-coupling path: one acceptance scale per timestep of the chunk
-    std::vector<RjBeta> h_rj;
-    const size_t chunk = std::min<size_t>(timesteps, 2048);
-    if (!s->has_betas && s->rj) TRY(scratch.alloc(&d_rj_steps, beta_stride ? chunk : 1));
-    else if (!s->has_betas) TRY(scratch.alloc(&d_step_tabs, (beta_stride ? chunk : 1) * PK_TAB_WORDS));
-    // energies after every timestep: the measurements are enqueued behind their sweeps into one counter slot
-    // per step; the host reads a whole chunk at once
-    unsigned long long *d_step_counts = nullptr;
-    std::vector<unsigned long long> h_step_counts;
-    if (energies_per_step) {
-        TRY(scratch.alloc(&d_step_counts, chunk * CS * 2));
-        h_step_counts.resize(chunk * CS * 2);
-    }
-    std::vector<uint32_t> h_tabs;
-    // one-degree kernels: the wave-uniform halves of every timestep's Philox calls, PK_PHILOX_STEPS timesteps ahead, written by one
-    // small launch when the rows run out (s->d_pk_philox: kept across calls)
-    constexpr size_t PK_PHILOX_STEPS = 2048; // (>= chunk)
-    const size_t philox_words = !s->rj && g->pk_uni_deg && !s->opt.disable_packed_uniform ? s->groups * pk_uni_philox_table_words() : 0;
-    const auto philox_rows_ready = [&](size_t nk) {
-        return s->pk_philox_steps && s->pk_philox_groups == s->groups && s->t >= s->pk_philox_t0 &&
-               s->t + nk <= s->pk_philox_t0 + s->pk_philox_steps;
-    };
-    int rc = ISINGMC_OK;
-    if (device_ms) HIP_TRY(hipEventRecord(s->ev0, s->stream));
-    // The replica groups are independent: mid-size launches (a few waves per SIMD: the 64^3 glass x 64 replicas puts ONE wave on a
-    // SIMD per colour-class launch) leave the chip idle around every kernel boundary, so the groups go to several streams and one
-    // lane's launch gap / ramp / tail overlaps the other lanes' work (as the lattice path's replica lanes).  ISINGMC_PK_STREAMS=<n> forces.
-    size_t want_lanes = 1;
-    if (!energies_per_step && s->groups >= 2) {
-        uint64_t biggest = 0;
-        for (uint32_t c = 0; c < g->n_colours; c++) biggest = std::max<uint64_t>(biggest, g->class_base[c + 1] - g->class_base[c]);
-        const uint64_t waves_per_launch = s->groups * biggest / (s->rj ? 64 : 256); // a thread decides 1 (real) / 4 (bit-sliced) positions
-        const int forced = s->opt.pk_streams;
-        if (forced > 0) want_lanes = size_t(forced);
-        // measured (tools/pk_lanes_ab.py, profiles/r03_pk_lanes_ab.txt): two lanes +7 % (2048^2 x 256) to +43 % (512^2 x 64) from ~2 000 waves per
-        // launch on, -3..-13 % below (32^3 x 64: the launches are too short for the fork / join); four lanes: worse than two almost everywhere
-        // Short calls (the 10-timestep blocks between tempering rounds) double their launch count with lanes and run into the host's
-        // launch rate sooner: 64^3 x 64 rungs went from 24.5 to 31 us per timestep; they take lanes only for long launches
-        else if (timesteps >= 64 ? waves_per_launch >= 2048 : timesteps >= 4 && waves_per_launch >= 16384) want_lanes = 2;
-        want_lanes = std::min(want_lanes, s->groups);
-    }
-    struct LaneJoin {
-        isingmc_states *s;
-        ~LaneJoin() { if (s->n_lanes > 1) (void)lanes_join(s); }
-    } lane_join{s};
-    const size_t n_lanes = want_lanes, per_lane = (s->groups + n_lanes - 1) / n_lanes;
-    const auto launch_step = [&](size_t k) {
-        for (size_t lane = 0; lane < n_lanes; lane++) {
-            const size_t gb = lane * per_lane, ge = std::min(s->groups, gb + per_lane);
-            if (gb >= ge) continue;
-            hipStream_t st = n_lanes > 1 ? s->lanes[lane] : s->stream;
-            if (s->rj) {
-                if (s->has_betas) rj_launch_timestep(s, s->d_rj_betas, 32, gb, ge, st);
-                else rj_launch_timestep(s, d_rj_steps + (beta_stride ? k : 0), 0, gb, ge, st);
-            } else {
-                const uint32_t *rows = philox_words ? s->d_pk_philox + size_t(s->t - s->pk_philox_t0) * philox_words : nullptr; // timestep s->t's
-                if (s->has_betas) pk_launch_timestep(s, s->d_tab, PK_TAB_WORDS, rows, gb, ge, st);
-                else pk_launch_timestep(s, d_step_tabs + (beta_stride ? k * PK_TAB_WORDS : 0), 0, rows, gb, ge, st);
-            }
-        }
-    };
-    for (size_t k0 = 0; k0 < timesteps && rc == ISINGMC_OK; k0 += chunk) {
-        const size_t nk = std::min(chunk, timesteps - k0);
-        const bool new_step_tabs = !s->has_betas && (beta_stride || k0 == 0);
-        const bool new_philox_rows = philox_words && !philox_rows_ready(nk);
-        if (k0 > 0 && (new_step_tabs || new_philox_rows)) { // the chunk's tables are overwritten: every lane must have finished reading them
-            if (s->n_lanes > 1) TRY(lanes_join(s));
-            if (new_step_tabs) HIP_TRY(hipStreamSynchronize(s->stream)); // (written from the host)
-        }
-        if (!s->has_betas && s->rj && (beta_stride || k0 == 0)) {
-            h_rj.resize(beta_stride ? nk : 1);
-            for (size_t k = 0; k < h_rj.size(); k++) rj_beta(betas[(k0 + k) * beta_stride], g->rj_k, &h_rj[k].shift, &h_rj[k].mant);
-            HIP_TRY(hipMemcpy(d_rj_steps, h_rj.data(), h_rj.size() * sizeof(RjBeta), hipMemcpyHostToDevice));
-        } else if (!s->has_betas && (beta_stride || k0 == 0)) {
-            h_tabs.resize((beta_stride ? nk : 1) * PK_TAB_WORDS);
-            for (size_t k = 0; k < h_tabs.size() / PK_TAB_WORDS; k++) {
-                const double beta = betas[(k0 + k) * beta_stride];
-                pk_fill_table(h_tabs.data() + k * PK_TAB_WORDS, g->jabs, [&](uint32_t) { return beta; });
-            }
-            HIP_TRY(hipMemcpy(d_step_tabs, h_tabs.data(), h_tabs.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        }
-        if (new_philox_rows) { // (on the main stream, the lanes joined: in order with every sweep that read the old rows)
-            if (!s->d_pk_philox) TRY(dev_alloc(&s->d_pk_philox, PK_PHILOX_STEPS * philox_words));
-            HIP_TRY(pk_uni_launch_philox_table(s->stream, s->d_pk_philox, s->d_keys, uint32_t(s->groups), s->t, uint32_t(PK_PHILOX_STEPS)));
-            s->pk_philox_t0 = s->t;
-            s->pk_philox_steps = PK_PHILOX_STEPS;
-            s->pk_philox_groups = s->groups;
-        }
-        if (want_lanes > 1 && s->n_lanes <= 1) TRY(lanes_fork(s, want_lanes)); // (behind the table launch: the lanes wait for it)
-        for (size_t k = 0; k < nk && rc == ISINGMC_OK; k++) {
-            launch_step(k);
-            s->t++;
-            if (energies_per_step) rc = measure_enqueue(s, d_step_counts + k * CS * 2, nullptr, nullptr, /*want_up=*/false);
-        }
-        if (energies_per_step && rc == ISINGMC_OK) {
-            HIP_TRY(hipMemcpyAsync(h_step_counts.data(), d_step_counts, nk * CS * 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->stream));
-            HIP_TRY(hipStreamSynchronize(s->stream));
-            for (size_t k = 0; k < nk; k++)
-                for (size_t r = 0; r < R; r++)
-                    energies_per_step[r * timesteps + k0 + k] = pk_energy(g, s->rj, h_step_counts[(k * CS + r + s->pk_bit0) * 2],
-                                                                          h_step_counts[(k * CS + r + s->pk_bit0) * 2 + 1]);
-        }
-    }
-    if (s->n_lanes > 1) { const int jrc = lanes_join(s); if (rc == ISINGMC_OK) rc = jrc; }
-    if (device_ms && rc == ISINGMC_OK) {
-        hipError_t err = hipEventRecord(s->ev1, s->stream);
-        if (err == hipSuccess) err = hipEventSynchronize(s->ev1);
-        if (err == hipSuccess) err = hipEventElapsedTime(device_ms, s->ev0, s->ev1);
-        if (err != hipSuccess) rc = fail(ISINGMC_ERR_HIP, hipGetErrorString(err));
-    }
-    if (rc == ISINGMC_OK) {
-        hipError_t err = hipGetLastError();
-        if (err == hipSuccess && sync) err = hipStreamSynchronize(s->stream);
-        if (err != hipSuccess) rc = fail(ISINGMC_ERR_HIP, hipGetErrorString(err));
-    }
-    return rc; // `scratch` drains the stream before it frees the step tables
-}
-
 // packed words -> one byte per spin, replica by replica
 int pk_get_states(isingmc_states *s, uint8_t *states_out, size_t replica_stride_bytes, uint32_t *packed_out)
 {
@@ -889,50 +743,122 @@ static void launch_gen_timestep(isingmc_states *s, double beta)
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// measurements enqueued behind the sweeps (per-step energies, sampling, tempering rounds)
+// ------------------------------------------------------------------------------------------------
+int measure_enqueue(isingmc_states *s, unsigned long long *counts_slot, double *e_slot, long long *m_slot, bool want_up)
+{
+    const isingmc_graph *g = s->g;
+    const size_t R = s->R;
+    if (s->packed) { // counts_slot: [pk_slots()][2], one pair per (group, bit) -- a shard may own only some bits of a group
+        HIP_TRY(hipMemsetAsync(counts_slot, 0, 2 * s->pk_slots() * sizeof(unsigned long long), s->stream));
+        if (s->rj) {
+            const bool bip = g->n_colours == 2;
+            // all workgroups resident at once (the runtime's occupancy figure for this instantiation), every one walks its
+            // share of the blocks; a grid one round and a bit long would run its tail at a fraction of the chip
+            static std::mutex per_cu_mutex; // (the device fan-out measures from several host threads)
+            static int per_cu[6][2][2] = {};
+            int pc;
+            {
+                std::lock_guard<std::mutex> lock(per_cu_mutex);
+                int &slot = per_cu[g->rj.slots == 4 ? 0 : g->rj.slots == 7 ? 1 : g->rj.slots == 11 ? 2 : g->rj.slots == 15 ? 3 : g->rj.slots == 23 ? 4 : 5][bip][want_up];
+                if (slot == 0) slot = std::max(1, rj_measure_blocks_per_cu(g->rj.slots, bip, want_up));
+                pc = slot;
+            }
+            const size_t resident = size_t(pc) * size_t(std::max(g->n_cu, 1));
+            // two colour classes: the bonds from class 0 alone; class 1 is visited only for its bias terms or the up spins
+            const uint32_t class0_end = bip ? uint32_t(g->class_base[1]) : 0u;
+            const uint32_t scan_end = bip && !g->has_bias && !want_up ? class0_end : g->pk.n_pos;
+            const size_t scan_blocks = scan_end / rj_threads(g->rj.slots);
+            for (size_t g0 = 0; g0 < s->groups; g0 += MAX_GRID_Y) {
+                const size_t ng = std::min(MAX_GRID_Y, s->groups - g0);
+                const size_t gx = std::min(scan_blocks, std::max<size_t>(1, resident / ng));
+                // hi level (+ the up spins when wanted) into the first counter of a slot, lo level into the second
+                HIP_TRY(rj_launch_measure(dim3(unsigned(std::max<size_t>(gx, 1)), unsigned(ng)), s->stream, s->d_state + g0 * g->pk.n_pos, g->rj_hi,
+                                          g->pk.site, class0_end, scan_end, want_up, counts_slot + 2 * 32 * g0));
+                if (!want_up)
+                    HIP_TRY(rj_launch_measure(dim3(unsigned(std::max<size_t>(gx, 1)), unsigned(ng)), s->stream, s->d_state + g0 * g->pk.n_pos, g->rj_lo,
+                                              g->pk.site, class0_end, scan_end, false, counts_slot + 2 * 32 * g0 + 1));
+            }
+            return ISINGMC_OK;
+        }
+        uint32_t ppt = PK_MEASURE_POS_PER_THREAD; // halved until the launch has >= 1024 workgroups (not below 8: the transpose
+                                                  // at the end of a chunk costs as much as ~16 positions)
+        while (ppt > 8 && size_t((g->pk.n_pos + 256 * ppt - 1) / (256 * ppt)) * s->groups < 1024) ppt /= 2;
+        const unsigned blocks = unsigned(std::max<uint32_t>(1, std::min<uint32_t>(2048, (g->pk.n_pos + 256 * ppt - 1) / (256 * ppt))));
+        for (size_t g0 = 0; g0 < s->groups; g0 += MAX_GRID_Y) {
+            const size_t ng = std::min(MAX_GRID_Y, s->groups - g0);
+            hipLaunchKernelGGL(pk_measure_kernel, dim3(blocks, unsigned(ng)), dim3(256), 0, s->stream,
+                               s->d_state + g0 * g->pk.n_pos, g->pk, counts_slot + 2 * 32 * g0, uint32_t(32 * ng), ppt,
+                               g->n_colours == 2 ? uint32_t(g->class_base[1]) : g->pk.n_pos, g->n_colours == 2 ? 2u : 1u);
+        }
+    } else if (g->kind == ISINGMC_KIND_LATTICE2D) {
+        HIP_TRY(hipMemsetAsync(counts_slot, 0, 2 * R * sizeof(unsigned long long), s->stream));
+        LAT_DISPATCH(launch_lat_measure, s, counts_slot, size_t(2));
+    } else {
+        for (size_t r0 = 0; r0 < R; r0 += MAX_GRID_Y) {
+            const size_t n = std::min(MAX_GRID_Y, R - r0);
+            const dim3 grid(s->n_partials, unsigned(n));
+            if (g->w_is_float)
+                hipLaunchKernelGGL(gen_measure_kernel<float>, grid, dim3(256), 0, s->stream, s->d_state + r0 * g->state_words,
+                                   g->gdev, s->d_pe + r0 * s->n_partials, s->d_pm + r0 * s->n_partials);
+            else
+                hipLaunchKernelGGL(gen_measure_kernel<double>, grid, dim3(256), 0, s->stream, s->d_state + r0 * g->state_words,
+                                   g->gdev, s->d_pe + r0 * s->n_partials, s->d_pm + r0 * s->n_partials);
+        }
+        hipLaunchKernelGGL(gen_reduce_kernel, dim3(unsigned(R)), dim3(256), 0, s->stream, s->d_pe, s->d_pm, s->n_partials,
+                           e_slot, m_slot);
+    }
+    HIP_TRY(hipGetLastError());
+    return ISINGMC_OK;
+}
+
+void lat_measure_enqueue(isingmc_states *s, unsigned long long *out, size_t out_stride)
+{
+    LAT_DISPATCH(launch_lat_measure, s, out, out_stride);
+}
+
+// device -> host, waited for
+template <typename T>
+static int read_back(isingmc_states *s, std::vector<T> &h, const T *d, size_t n)
+{
+    h.resize(n);
+    HIP_TRY(hipMemcpyAsync(h.data(), d, n * sizeof(T), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return ISINGMC_OK;
+}
+
 // energies / magnetisations of the current configurations into host arrays (either may be NULL)
 static int measure(isingmc_states *s, double *energies, int64_t *mags)
 {
     const isingmc_graph *g = s->g;
     const size_t R = s->R;
     if (R == 0) return ISINGMC_OK;
-    if (s->packed) return pk_measure(s, energies, mags);
-    if (g->kind == ISINGMC_KIND_LATTICE2D) {
-        HIP_TRY(hipMemsetAsync(s->d_meas, 0, 2 * R * sizeof(unsigned long long), s->stream));
+    if (s->rj && energies && mags) { // the second counter of a slot holds the lo level of the energy OR the up spins
+        TRY(measure(s, energies, nullptr));
+        return measure(s, nullptr, mags);
+    }
+    if (s->packed || g->kind == ISINGMC_KIND_LATTICE2D) {
+        TRY(measure_enqueue(s, s->d_meas, nullptr, nullptr, /*want_up=*/mags != nullptr));
         s->meas_zero = false;
-        LAT_DISPATCH(launch_lat_measure, s, s->d_meas, size_t(2));
-        HIP_TRY(hipGetLastError());
-        std::vector<unsigned long long> h(2 * R);
-        HIP_TRY(hipMemcpyAsync(h.data(), s->d_meas, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipStreamSynchronize(s->stream));
+        std::vector<unsigned long long> h;
+        TRY(read_back(s, h, s->d_meas, 2 * counter_slots(s)));
         for (size_t r = 0; r < R; r++) {
-            if (energies) energies[r] = lattice_energy(g, h[2 * r], h[2 * r + 1]);
-            if (mags) mags[r] = 2 * int64_t(h[2 * r + 1]) - int64_t(g->nvars);
+            const size_t sl = counter_slot(s, r);
+            if (energies) energies[r] = counters_energy(s, h[2 * sl], h[2 * sl + 1]);
+            if (mags) mags[r] = 2 * int64_t(h[2 * sl + 1]) - int64_t(g->nvars);
         }
-    } else {
-        for (size_t r0 = 0; r0 < R; r0 += MAX_GRID_Y) {
-            const size_t n = std::min(MAX_GRID_Y, R - r0);
-            const dim3 grid(s->n_partials, unsigned(n));
-            if (g->w_is_float)
-                hipLaunchKernelGGL(gen_measure_kernel<float>, grid, dim3(256), 0, s->stream,
-                                   s->d_state + r0 * g->state_words, g->gdev, s->d_pe + r0 * s->n_partials,
-                                   s->d_pm + r0 * s->n_partials);
-            else
-                hipLaunchKernelGGL(gen_measure_kernel<double>, grid, dim3(256), 0, s->stream,
-                                   s->d_state + r0 * g->state_words, g->gdev, s->d_pe + r0 * s->n_partials,
-                                   s->d_pm + r0 * s->n_partials);
-        }
-        hipLaunchKernelGGL(gen_reduce_kernel, dim3(unsigned(R)), dim3(256), 0, s->stream, s->d_pe, s->d_pm,
-                           s->n_partials, s->d_oe, s->d_om);
-        HIP_TRY(hipGetLastError());
-        std::vector<double> he(R);
-        std::vector<long long> hm(R);
-        HIP_TRY(hipMemcpyAsync(he.data(), s->d_oe, R * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipMemcpyAsync(hm.data(), s->d_om, R * sizeof(long long), hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipStreamSynchronize(s->stream));
-        for (size_t r = 0; r < R; r++) {
-            if (energies) energies[r] = he[r] + g->self_energy;
-            if (mags) mags[r] = hm[r];
-        }
+        return ISINGMC_OK;
+    }
+    TRY(measure_enqueue(s, nullptr, s->d_oe, s->d_om));
+    std::vector<double> he(R);
+    std::vector<long long> hm(R);
+    HIP_TRY(hipMemcpyAsync(he.data(), s->d_oe, R * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(hm.data(), s->d_om, R * sizeof(long long), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    for (size_t r = 0; r < R; r++) {
+        if (energies) energies[r] = he[r] + g->self_energy;
+        if (mags) mags[r] = hm[r];
     }
     return ISINGMC_OK;
 }
@@ -972,15 +898,13 @@ StripPlan strip_plan(const isingmc_states *s, size_t timesteps, bool ladder)
     P.nw = s->opt.strip_nw == 1 ? 1 : 4; // measured on 1024^2 x 64 (round 4, with wave priorities): 8.4 (4) / 8.6 (1) us per timestep; with exchange rounds 10.4 (4) / 12.0 (1)
     const uint32_t S = 64 * uint32_t(P.nw) / qpr;
     if (g->geom.H % S != 0 || g->geom.H / S < 2) return P;
-    int dev_cus = 256;
-    (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, g->device);
     // Every workgroup of a launch must be resident at once.  Per CU: what the runtime's occupancy calculation grants this
     // instantiation with its dynamic LDS (registers, LDS, wave slots), and never more than the policy bound of
     // STRIP_MAX_WAVES_PER_CU waves (beyond it the per-colour launches are faster anyway).
     const size_t lds = (size_t(2) * (S + 2) * g->geom.wpr + 16) * sizeof(uint32_t);
     const int by_occupancy = strip_resident_blocks_per_cu(!g->uniform_sign, P.nw, ladder, lds);
     const size_t per_cu = std::min<size_t>(size_t(STRIP_MAX_WAVES_PER_CU) / size_t(P.nw), size_t(std::max(by_occupancy, 0)));
-    const size_t limit = per_cu * size_t(std::max(dev_cus, 1)); // workgroups resident at once
+    const size_t limit = per_cu * size_t(std::max(g->n_cu, 1)); // workgroups resident at once
     const size_t n_strips = g->geom.H / S, total = s->R * n_strips;
     if (limit == 0 || n_strips > limit) return P;
     // one pass only by default: with twice the replicas (1024^2 x 128) the per-colour launches are long enough to win (16.7 vs 18.6 us)
@@ -1125,22 +1049,406 @@ bool may_use_strips(const isingmc_states *s)
 int run_steps(isingmc_states *s, size_t timesteps, const double *betas, size_t beta_stride,
               double *energies_per_step, float *device_ms, bool sync, double *final_energies)
 {
-    // a synchronous call keeps the planes it started from when it may launch the strip kernel; if a launch gives up (its
-    // workgroups were not all resident: a co-tenant, a CU mask) the call is repeated with the per-colour launches
-    const bool guard = sync && timesteps >= 2 && may_use_strips(s) && strip_plan(s, timesteps).use;
-    if (!guard) {
-        const int rc = run_steps_impl(s, timesteps, betas, beta_stride, energies_per_step, device_ms, sync, final_energies);
-        return sync ? strip_error(rc) : rc;
+    const bool may_strip = sync && timesteps >= 2 && may_use_strips(s) && strip_plan(s, timesteps).use;
+    return with_strip_retry(s, may_strip, [&] {
+        return run_steps_impl(s, timesteps, betas, beta_stride, energies_per_step, device_ms, sync, final_energies);
+    });
+}
+
+// ------------------------------------------------------------------------------------------------
+// run_steps: one plan per call (kernel path, chunk of timesteps, replica lanes), one runner per path for each chunk
+// ------------------------------------------------------------------------------------------------
+enum class StepPath { Packed, LatResident, LatStrip, LatStream, McResident, McStream, GenResident, GenCsr };
+
+struct StepPlan {
+    StepPath path = StepPath::GenCsr;
+    size_t chunk = 0;      // timesteps per runner call (per-step energies are read back chunk by chunk)
+    size_t step_slots = 1; // per-step counter slots per replica: the streaming kernels measure into MEASURE_SLOTS partial counters
+    size_t lanes = 1;      // replica lanes (streams)
+    StripPlan strip;
+};
+
+// small lattices: one LDS-resident launch per chunk of timesteps instead of two launches per timestep (up to 1024 quads per
+// colour: beyond that one workgroup per replica is slower than the launches it saves); the multi-class kernels' bound too
+static bool lat_resident_fits(const isingmc_states *s)
+{
+    const isingmc_graph *g = s->g;
+    return g->state_words * sizeof(uint32_t) <= LDS_RESIDENT_MAX_BYTES && g->geom.nquads <= 1024 && !resident_disabled(s);
+}
+
+static StepPlan plan_steps(const isingmc_states *s, size_t timesteps, bool energies_per_step)
+{
+    const isingmc_graph *g = s->g;
+    const size_t R = s->R;
+    StepPlan P;
+    if (s->packed) {
+        P.path = StepPath::Packed;
+        P.chunk = std::min<size_t>(timesteps, 2048);
+        // The replica groups are independent: mid-size launches (a few waves per SIMD: the 64^3 glass x 64 replicas puts ONE wave on a
+        // SIMD per colour-class launch) leave the chip idle around every kernel boundary, so the groups go to several streams and one
+        // lane's launch gap / ramp / tail overlaps the other lanes' work (as the lattice path's replica lanes).  ISINGMC_PK_STREAMS=<n> forces.
+        if (!energies_per_step && s->groups >= 2) {
+            uint64_t biggest = 0;
+            for (uint32_t c = 0; c < g->n_colours; c++) biggest = std::max<uint64_t>(biggest, g->class_base[c + 1] - g->class_base[c]);
+            const uint64_t waves_per_launch = s->groups * biggest / (s->rj ? 64 : 256); // a thread decides 1 (real) / 4 (bit-sliced) positions
+            const int forced = s->opt.pk_streams;
+            if (forced > 0) P.lanes = size_t(forced);
+            // measured (tools/pk_lanes_ab.py, profiles/r03_pk_lanes_ab.txt): two lanes +7 % (2048^2 x 256) to +43 % (512^2 x 64) from ~2 000 waves per
+            // launch on, -3..-13 % below (32^3 x 64: the launches are too short for the fork / join); four lanes: worse than two almost everywhere
+            // Short calls (the 10-timestep blocks between tempering rounds) double their launch count with lanes and run into the host's
+            // launch rate sooner: 64^3 x 64 rungs went from 24.5 to 31 us per timestep; they take lanes only for long launches
+            else if (timesteps >= 64 ? waves_per_launch >= 2048 : timesteps >= 4 && waves_per_launch >= 16384) P.lanes = 2;
+            P.lanes = std::min(P.lanes, s->groups);
+        }
+        return P;
     }
-    TRY(use_device(s->g->device));
-    const uint64_t t0 = s->t;
-    TRY(snapshot_take(s));
-    int rc = run_steps_impl(s, timesteps, betas, beta_stride, energies_per_step, device_ms, sync, final_energies);
-    if (rc != STRIP_TIMED_OUT) return rc;
-    TRY(snapshot_restore(s));
-    s->t = t0;
-    rc = run_steps_impl(s, timesteps, betas, beta_stride, energies_per_step, device_ms, sync, final_energies); // strip_disabled now
-    return strip_error(rc);
+    if (g->kind != ISINGMC_KIND_LATTICE2D) P.path = gen_resident_fits(g, R) && !resident_disabled(s) ? StepPath::GenResident : StepPath::GenCsr;
+    // lattices with a field or open boundaries: the multi-class kernels
+    else if (g->mc_mode != MC_NONE) P.path = lat_resident_fits(s) ? StepPath::McResident : StepPath::McStream;
+    else if (lat_resident_fits(s)) P.path = StepPath::LatResident;
+    else {
+        P.strip = strip_plan(s, timesteps);
+        P.path = P.strip.use ? StepPath::LatStrip : StepPath::LatStream;
+    }
+    if (energies_per_step && P.path == StepPath::LatStream) P.step_slots = MEASURE_SLOTS;
+    // per-step counters: 16 B per (step, replica) and counter slot, at most 32 MiB per chunk on each side of the bus
+    P.chunk = energies_per_step ? std::max<size_t>(1, std::min<size_t>(timesteps, (size_t(32) << 20) / (16 * R * P.step_slots))) : timesteps;
+    if (P.path == StepPath::LatResident || P.path == StepPath::LatStrip || P.path == StepPath::McResident || P.path == StepPath::GenResident)
+        P.chunk = std::min<size_t>(P.chunk, 65536);
+    // mid-size launches (a few waves per SIMD) leave the GPU idle around every kernel boundary: run the
+    // replica blocks on several streams.  Large launches (c2) keep the chip full on one stream.
+    if ((P.path == StepPath::LatStream || P.path == StepPath::McStream) && !energies_per_step) {
+        const size_t waves_per_launch = R * ((g->geom.nquads + 255) / 256) * 4;
+        if (s->opt.streams > 0) P.lanes = size_t(s->opt.streams);
+        // < 64 waves per SIMD per launch: +17..33 % with 2 lanes (4 go host-bound); short calls lose it to fork/join.
+        // Large launches: +2.8 % (one block's drain overlaps the other's ramp); the fork/join is ~45 us per call
+        else if (waves_per_launch < 64 * 1024 ? timesteps >= 64 : timesteps >= 8) P.lanes = 2;
+        P.lanes = std::min(P.lanes, R);
+    }
+    return P;
+}
+
+// one run_steps call: its arguments, its plan and its scratch (freed on every exit path, after the stream has drained)
+struct StepRun {
+    isingmc_states *s;
+    StepPlan P;
+    const double *betas;
+    size_t beta_stride, timesteps;
+    double *energies_per_step, *final_energies;
+    DeviceScratch scratch{s->stream};
+    unsigned long long *d_counts = nullptr; // per-step counters [chunk][counter slots][step_slots][2] (lattice and packed paths)
+    double *d_energies = nullptr;           // per-step energies [chunk x R] (general paths)
+    long long *d_mags = nullptr;
+    // per-step tables: one per timestep of a chunk, or one for the call (beta_stride == 0)
+    LatThr *d_thr = nullptr;
+    double *d_betas = nullptr;
+    uint32_t *d_pk_tabs = nullptr;
+    RjBeta *d_rj = nullptr;
+    std::vector<unsigned long long> h_counts{};
+    std::vector<LatThr> h_thr{};
+    std::vector<std::array<uint32_t, PK_TAB_WORDS>> h_pk_tabs{};
+    std::vector<RjBeta> h_rj{};
+};
+
+// the host's tables of the chunk [k0, k0 + nk)
+template <typename T, typename F>
+static void fill_step_tables(const StepRun &c, size_t k0, size_t nk, std::vector<T> &h, F &&table_of)
+{
+    h.resize(c.beta_stride ? nk : 1);
+    for (size_t k = 0; k < h.size(); k++) h[k] = table_of(c.betas[(k0 + k) * c.beta_stride]);
+}
+
+static double step_beta(const StepRun &c, size_t k) { return c.s->has_betas ? 0.0 : c.betas[k * c.beta_stride]; }
+
+static int upload_lat_thresholds(StepRun &c, size_t k0, size_t nk)
+{
+    if (c.s->has_betas) return ISINGMC_OK;
+    fill_step_tables(c, k0, nk, c.h_thr, [&](double beta) { return lattice_thresholds(beta, c.s->g->jabs); });
+    HIP_TRY(hipMemcpyAsync(c.d_thr, c.h_thr.data(), c.h_thr.size() * sizeof(LatThr), hipMemcpyHostToDevice, c.s->stream));
+    return ISINGMC_OK;
+}
+
+static int run_packed(StepRun &c, size_t k0, size_t nk)
+{
+    isingmc_states *s = c.s;
+    const isingmc_graph *g = s->g;
+    // one-degree kernels: the wave-uniform halves of every timestep's Philox calls, PK_PHILOX_STEPS timesteps ahead, written by one
+    // small launch when the rows run out (s->d_pk_philox: kept across calls)
+    constexpr size_t PK_PHILOX_STEPS = 2048; // (>= chunk)
+    const size_t philox_words = !s->rj && g->pk_uni_deg && !s->opt.disable_packed_uniform ? s->groups * pk_uni_philox_table_words() : 0;
+    const bool new_step_tabs = !s->has_betas && (c.beta_stride || k0 == 0);
+    const bool new_philox_rows = philox_words && !(s->pk_philox_steps && s->pk_philox_groups == s->groups && s->t >= s->pk_philox_t0 &&
+                                                   s->t + nk <= s->pk_philox_t0 + s->pk_philox_steps);
+    if (k0 > 0 && (new_step_tabs || new_philox_rows)) { // the chunk's tables are overwritten: every lane must have finished reading them
+        if (s->n_lanes > 1) TRY(lanes_join(s));
+        if (new_step_tabs) HIP_TRY(hipStreamSynchronize(s->stream)); // (written from the host)
+    }
+    if (new_step_tabs && s->rj) { // real-coupling path: one acceptance scale per timestep
+        fill_step_tables(c, k0, nk, c.h_rj, [&](double beta) {
+            RjBeta b{};
+            rj_beta(beta, g->rj_k, &b.shift, &b.mant);
+            return b;
+        });
+        HIP_TRY(hipMemcpy(c.d_rj, c.h_rj.data(), c.h_rj.size() * sizeof(RjBeta), hipMemcpyHostToDevice));
+    } else if (new_step_tabs) {
+        fill_step_tables(c, k0, nk, c.h_pk_tabs, [&](double beta) {
+            std::array<uint32_t, PK_TAB_WORDS> tab;
+            pk_fill_table(tab.data(), g->jabs, [&](uint32_t) { return beta; });
+            return tab;
+        });
+        HIP_TRY(hipMemcpy(c.d_pk_tabs, c.h_pk_tabs.data(), c.h_pk_tabs.size() * sizeof(c.h_pk_tabs[0]), hipMemcpyHostToDevice));
+    }
+    if (new_philox_rows) { // (on the main stream, the lanes joined: in order with every sweep that read the old rows)
+        if (!s->d_pk_philox) TRY(dev_alloc(&s->d_pk_philox, PK_PHILOX_STEPS * philox_words));
+        HIP_TRY(pk_uni_launch_philox_table(s->stream, s->d_pk_philox, s->d_keys, uint32_t(s->groups), s->t, uint32_t(PK_PHILOX_STEPS)));
+        s->pk_philox_t0 = s->t;
+        s->pk_philox_steps = PK_PHILOX_STEPS;
+        s->pk_philox_groups = s->groups;
+    }
+    const size_t n_lanes = c.P.lanes, per_lane = (s->groups + n_lanes - 1) / n_lanes, CS = s->pk_slots();
+    if (n_lanes > 1 && s->n_lanes <= 1) TRY(lanes_fork(s, n_lanes)); // (behind the table launch: the lanes wait for it)
+    for (size_t k = 0; k < nk; k++) {
+        for (size_t lane = 0; lane < n_lanes; lane++) {
+            const size_t gb = lane * per_lane, ge = std::min(s->groups, gb + per_lane);
+            if (gb >= ge) continue;
+            hipStream_t st = n_lanes > 1 ? s->lanes[lane] : s->stream;
+            if (s->rj) {
+                if (s->has_betas) rj_launch_timestep(s, s->d_rj_betas, 32, gb, ge, st);
+                else rj_launch_timestep(s, c.d_rj + (c.beta_stride ? k : 0), 0, gb, ge, st);
+            } else {
+                const uint32_t *rows = philox_words ? s->d_pk_philox + size_t(s->t - s->pk_philox_t0) * philox_words : nullptr; // timestep s->t's
+                if (s->has_betas) pk_launch_timestep(s, s->d_tab, PK_TAB_WORDS, rows, gb, ge, st);
+                else pk_launch_timestep(s, c.d_pk_tabs + (c.beta_stride ? k * PK_TAB_WORDS : 0), 0, rows, gb, ge, st);
+            }
+        }
+        s->t++;
+        // energies after every timestep: the measurements are enqueued behind their sweeps into one counter slot per step
+        if (c.d_counts) TRY(measure_enqueue(s, c.d_counts + k * CS * 2, nullptr, nullptr, /*want_up=*/false));
+    }
+    return ISINGMC_OK;
+}
+
+static int run_lat_resident(StepRun &c, size_t k0, size_t nk)
+{
+    isingmc_states *s = c.s;
+    const isingmc_graph *g = s->g;
+    const size_t R = s->R;
+    TRY(upload_lat_thresholds(c, k0, nk));
+    // small lattices: eight (four, two) lanes per quad, one (two, four) Philox calls each (lat_resident_spread_kernel)
+    // ... while every replica of the call is resident at once: beyond that the one-lane-per-quad kernel's small workgroups fill
+    // the chip better (measured, tools/small_lattice_spread_ab.py: 64^2 x 2048 4.1 against 5.9 us, x 4096 10.5 against 9.1;
+    // 128^2 x 512 4.4 against 5.4, x 1024 8.7 against 5.3).  ISINGMC_RESIDENT_SPREAD=0 / 2: never / whenever the lattice allows
+    const int spread_mode = s->opt.resident_spread;
+    // eight lanes per quad only: with four or two (256 / 512 quads per colour, 1024 threads) the barriers of a 16-wave workgroup
+    // cost more than the shorter chain saves (256^2 x 64: 5.7 against 5.1 us; ISINGMC_RESIDENT_LPQ=4 / 2 for A/B runs)
+    const int lpq_forced = s->opt.resident_lpq;
+    const int lpq = lpq_forced == 4 || lpq_forced == 2 ? lpq_forced : 8;
+    bool spread = spread_mode != 0 && size_t(g->geom.nquads) * size_t(lpq) <= 1024;
+    const unsigned spread_threads = unsigned((size_t(g->geom.nquads) * size_t(lpq) + 63) / 64 * 64);
+    const size_t spread_lds = g->state_words * sizeof(uint32_t) + size_t(g->geom.nquads) * 8 * sizeof(uint4);
+    if (spread && spread_mode != 2) {
+        const int per_cu = spread_blocks_per_cu(g->vec, !g->uniform_sign, lpq, spread_threads, spread_lds);
+        spread = per_cu > 0 && R <= size_t(g->n_cu) * size_t(per_cu);
+    }
+    const unsigned threads = spread ? spread_threads : unsigned(std::min<size_t>(1024, (g->geom.nquads + 63) / 64 * 64));
+    const size_t lds = spread ? spread_lds : g->state_words * sizeof(uint32_t);
+    const auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(unsigned(R)), dim3(threads), lds, s->stream,
+                           s->d_state, g->geom, s->t, uint32_t(nk), s->d_keys, c.d_thr, uint32_t(c.beta_stride ? 1 : 0),
+                           s->has_betas ? s->d_thr : nullptr, g->d_jneg, g->jneg_uniform, c.d_counts, uint32_t(R));
+    };
+    if (spread) {
+        HIP_TRY(spread_launch(g->vec, !g->uniform_sign, lpq, unsigned(R), threads, lds, s->stream, s->d_state, g->geom, s->t, uint32_t(nk), s->d_keys,
+                              c.d_thr, uint32_t(c.beta_stride ? 1 : 0), s->has_betas ? s->d_thr : nullptr, g->d_jneg, g->jneg_uniform,
+                              c.d_counts, uint32_t(R)));
+    } else if (g->vec) { if (g->uniform_sign) launch(lat_resident_kernel<true, false>); else launch(lat_resident_kernel<true, true>); }
+    else { if (g->uniform_sign) launch(lat_resident_kernel<false, false>); else launch(lat_resident_kernel<false, true>); }
+    s->t += nk;
+    if (k0 + nk < c.timesteps && !c.d_counts) HIP_TRY(hipStreamSynchronize(s->stream)); // h_thr is reused by the next chunk
+    return ISINGMC_OK;
+}
+
+// mid-size lattices: the whole chunk of timesteps in one persistent launch per block of replicas
+static int run_lat_strip(StepRun &c, size_t k0, size_t nk)
+{
+    isingmc_states *s = c.s;
+    const size_t R = s->R;
+    TRY(upload_lat_thresholds(c, k0, nk));
+    // final_energies (device, [R]): the energies of the final configurations come with the last launch (tempering rounds)
+    const bool last = k0 + nk == c.timesteps;
+    for (size_t r0 = 0; r0 < R; r0 += c.P.strip.replicas_per_pass)
+        TRY(launch_strip(s, c.P.strip, r0, std::min(c.P.strip.replicas_per_pass, R - r0), nk, c.d_thr, uint32_t(c.beta_stride ? 1 : 0),
+                         c.d_counts ? c.d_counts + 2 * r0 : nullptr, last ? c.final_energies : nullptr));
+    s->strip_epoch += uint32_t(2 * nk);
+    s->t += nk;
+    if (c.final_energies && last) s->meas_fresh = true;
+    if (k0 + nk < c.timesteps && !c.d_counts) HIP_TRY(hipStreamSynchronize(s->stream)); // h_thr is reused by the next chunk
+    return ISINGMC_OK;
+}
+
+static int run_mc_resident(StepRun &c, size_t k0, size_t nk)
+{
+    isingmc_states *s = c.s;
+    const isingmc_graph *g = s->g;
+    const size_t R = s->R;
+    DeviceScratch thr_scratch(s->stream); // freed (after a stream sync) at the end of this chunk
+    LatThrMC *d_thr_mc_steps = nullptr;
+    if (!s->has_betas) {
+        std::vector<LatThrMC> h;
+        fill_step_tables(c, k0, nk, h, [&](double beta) { return lattice_thresholds_mc(g, beta); });
+        TRY(thr_scratch.alloc(&d_thr_mc_steps, h.size()));
+        HIP_TRY(hipMemcpy(d_thr_mc_steps, h.data(), h.size() * sizeof(LatThrMC), hipMemcpyHostToDevice));
+    }
+    // small lattices, few enough replicas to be resident at once: eight lanes per quad (lat_mc_resident_kernel SPREAD; the
+    // kernel takes the spread form when the launch's LDS holds the random words too).  ISINGMC_RESIDENT_SPREAD=0: off
+    const int mc_spread_mode = s->opt.resident_spread;
+    const size_t spread_threads = (size_t(g->geom.nquads) * 8 + 63) / 64 * 64;
+    const bool mc_spread = mc_spread_mode != 0 && spread_threads <= 1024 &&
+                           (mc_spread_mode == 2 || R <= size_t(g->n_cu) * std::max<size_t>(1, 1024 / spread_threads));
+    const unsigned threads = mc_spread ? unsigned(spread_threads) : unsigned(std::min<size_t>(1024, (g->geom.nquads + 63) / 64 * 64));
+    const size_t mc_lds = g->state_words * sizeof(uint32_t) + (mc_spread ? size_t(g->geom.nquads) * 8 * sizeof(uint4) : 0);
+    for (size_t r0 = 0; r0 < R; r0 += 65535) {
+        const size_t n = std::min<size_t>(65535, R - r0);
+        HIP_TRY(mc_launch_resident(g->mc_mode, !g->uniform_sign, unsigned(n), threads, mc_lds,
+                                   s->stream, s->d_state + r0 * g->state_words, g->geom, s->t, uint32_t(nk), s->d_keys + r0,
+                                   d_thr_mc_steps, uint32_t(c.beta_stride ? 1 : 0),
+                                   s->has_betas ? s->d_thr_mc + r0 : nullptr, g->d_jneg, g->jneg_uniform, g->open, g->d_fneg,
+                                   c.d_counts ? c.d_counts + 2 * r0 : nullptr, uint32_t(R)));
+    }
+    s->t += nk;
+    return ISINGMC_OK;
+}
+
+static int run_gen_resident(StepRun &c, size_t k0, size_t nk)
+{
+    isingmc_states *s = c.s;
+    const isingmc_graph *g = s->g;
+    const size_t R = s->R;
+    const size_t nb = c.beta_stride ? nk : 1;
+    if (!s->has_betas) HIP_TRY(hipMemcpyAsync(c.d_betas, c.betas + k0 * c.beta_stride, nb * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    unsigned threads = 64;
+    for (uint32_t col = 0; col < g->n_colours; col++)
+        threads = std::max<unsigned>(threads, unsigned(std::min<uint64_t>(1024, g->class_base[col + 1] - g->class_base[col])));
+    // the graph in LDS too (gen_resident_kernel STAGE) while every replica of the call can still be resident at once (160 KB
+    // of LDS per compute unit): small graphs, where a timestep is a chain of dependent loads.  Everything when that fits,
+    // else the topology alone (the links of the chain); ISINGMC_GEN_STAGE=0 / 1 / 2 forces none / all / topology (A/B runs)
+    const int stage_mode = s->opt.gen_stage;
+    const size_t lds_cu = 160 * 1024, lds_max = 150 * 1024; // (a few KB stay free for the kernel's static LDS)
+    size_t stage_bytes = 0;
+    int stage = 0;
+    {
+        size_t bytes[3] = {0, 0, 0}, resident[3] = {0, 0, 0};
+        for (int mode = 1; mode <= 2; mode++) {
+            bytes[mode] = size_t(gen_stage_words(g->gdev.n_pos, g->gen_edges2, g->gdev.bias != nullptr, g->w_is_float ? 4 : 8, mode)) * 4;
+            if (bytes[mode] <= lds_max) resident[mode] = std::min<size_t>(2048 / threads, lds_cu / (bytes[mode] + 1024)); // workgroups per compute unit
+        }
+        if (stage_mode == 0) stage = 0;
+        else if (stage_mode == 1 || stage_mode == 2) stage = resident[stage_mode] ? stage_mode : 0;
+        else if (resident[1] && (R <= size_t(g->n_cu) * resident[1] || threads > 512 || resident[2] <= resident[1])) stage = 1;
+        // (measured, tools/small_graph_stage_ab.py: workgroups of <= 512 threads gain from running side by side, so when
+        //  the full copy would keep some of the call's replicas waiting the smaller one wins: 32^2 x 1024 5.7 against
+        //  6.2 us, 8^3 x 1024 3.5 against 4.4; 1024-thread workgroups do not: 12^3 x 512 6.6 against 9.4)
+        else if (resident[2]) stage = 2;
+        stage_bytes = bytes[stage];
+    }
+    const auto launch = [&](auto kernel) {
+        if (stage_bytes > 64 * 1024) // beyond the default limit of dynamic LDS
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(stage_bytes));
+        hipLaunchKernelGGL(kernel, dim3(unsigned(R)), dim3(threads), stage ? stage_bytes : g->state_words * sizeof(uint32_t), s->stream,
+                           s->d_state, g->gdev, s->t, uint32_t(nk), s->d_keys, c.d_betas, uint32_t(c.beta_stride ? 1 : 0),
+                           s->has_betas ? s->d_beta : nullptr, c.d_energies, g->self_energy, g->gen_edges2);
+    };
+    if (g->w_is_float) {
+        if (stage == 1) launch(gen_resident_kernel<float, 1>); else if (stage == 2) launch(gen_resident_kernel<float, 2>); else launch(gen_resident_kernel<float, 0>);
+    } else {
+        if (stage == 1) launch(gen_resident_kernel<double, 1>); else if (stage == 2) launch(gen_resident_kernel<double, 2>); else launch(gen_resident_kernel<double, 0>);
+    }
+    s->t += nk;
+    if (!c.d_energies && k0 + nk < c.timesteps) HIP_TRY(hipStreamSynchronize(s->stream));
+    return ISINGMC_OK;
+}
+
+// lattices: two launches per timestep (the second fused with the measurement when the energies of every step are wanted)
+static int run_lat_stream(StepRun &c, size_t k0, size_t nk)
+{
+    isingmc_states *s = c.s;
+    const size_t R = s->R, SS = c.P.step_slots;
+    for (size_t k = k0; k < k0 + nk; k++) {
+        const LatThr thr = lattice_thresholds(step_beta(c, k), s->g->jabs);
+        LAT_DISPATCH(launch_lat_sweep, s, 0u, thr, s->t);
+        if (c.d_counts) LAT_DISPATCH(launch_lat_sweep_measure, s, thr, s->t, c.d_counts + (k - k0) * R * 2 * SS, 2 * SS);
+        else LAT_DISPATCH(launch_lat_sweep, s, 1u, thr, s->t);
+        s->t++;
+    }
+    return ISINGMC_OK;
+}
+
+// lattices with a field or open boundaries: one launch per colour (+ one measurement per step)
+static int run_mc_stream(StepRun &c, size_t k0, size_t nk)
+{
+    isingmc_states *s = c.s;
+    const isingmc_graph *g = s->g;
+    const size_t R = s->R;
+    for (size_t k = k0; k < k0 + nk; k++) {
+        const LatThrMC thr = lattice_thresholds_mc(g, step_beta(c, k));
+        const size_t per_lane = (R + s->n_lanes - 1) / s->n_lanes; // replica blocks on the lanes' streams, as launch_lat_sweep
+        for (uint32_t colour = 0; colour < 2; colour++)
+            for (size_t lane = 0; lane < s->n_lanes; lane++) {
+                const size_t lo = lane * per_lane, hi = std::min(R, lo + per_lane);
+                hipStream_t stream = s->n_lanes > 1 ? s->lanes[lane] : s->stream;
+                for (size_t r0 = lo; r0 < hi; r0 += MAX_GRID_Y) {
+                    const size_t n = std::min(MAX_GRID_Y, hi - r0);
+                    HIP_TRY(mc_launch_sweep(g->mc_mode, !g->uniform_sign, lat_grid(g, g->geom.nquads, n), stream,
+                                            s->d_state + r0 * g->state_words, g->geom, colour, s->t, s->d_keys + r0, thr,
+                                            s->has_betas ? s->d_thr_mc + r0 : nullptr, g->d_jneg, g->jneg_uniform, g->open, g->d_fneg));
+                }
+            }
+        s->t++;
+        // get_energy after this timestep: a measurement pass behind the sweep (as on the general path)
+        if (c.d_counts) TRY(measure_enqueue(s, c.d_counts + (k - k0) * R * 2, nullptr, nullptr));
+    }
+    return ISINGMC_OK;
+}
+
+// general graphs: one launch per colour class (+ one measurement per step)
+static int run_gen_csr(StepRun &c, size_t k0, size_t nk)
+{
+    isingmc_states *s = c.s;
+    for (size_t k = k0; k < k0 + nk; k++) {
+        launch_gen_timestep(s, step_beta(c, k));
+        s->t++;
+        if (c.d_energies) TRY(measure_enqueue(s, nullptr, c.d_energies + (k - k0) * s->R, c.d_mags));
+    }
+    return ISINGMC_OK;
+}
+
+// the per-step energies of the chunk [k0, k0 + nk) into energies_per_step[r * timesteps + k0 + k]
+static int read_step_energies(StepRun &c, size_t k0, size_t nk)
+{
+    isingmc_states *s = c.s;
+    const size_t R = s->R, T = c.timesteps;
+    double *out = c.energies_per_step + k0;
+    if (c.d_energies) { // general paths: [replica][step] from the resident kernel, [step][replica] from the reductions
+        std::vector<double> he;
+        TRY(read_back(s, he, c.d_energies, nk * R));
+        const bool resident = c.P.path == StepPath::GenResident;
+        for (size_t k = 0; k < nk; k++)
+            for (size_t r = 0; r < R; r++) out[r * T + k] = resident ? he[r * nk + k] : he[k * R + r] + s->g->self_energy;
+        return ISINGMC_OK;
+    }
+    const size_t CS = counter_slots(s), SS = c.P.step_slots;
+    TRY(read_back(s, c.h_counts, c.d_counts, nk * CS * SS * 2));
+    for (size_t k = 0; k < nk; k++)
+        for (size_t r = 0; r < R; r++) {
+            const unsigned long long *p = c.h_counts.data() + (k * CS + counter_slot(s, r)) * SS * 2;
+            unsigned long long c0 = 0, c1 = 0;
+            for (size_t sl = 0; sl < SS; sl++) {
+                c0 += p[2 * sl];
+                c1 += p[2 * sl + 1];
+            }
+            out[r * T + k] = counters_energy(s, c0, c1);
+        }
+    return ISINGMC_OK;
 }
 
 static int run_steps_impl(isingmc_states *s, size_t timesteps, const double *betas, size_t beta_stride, double *energies_per_step,
@@ -1153,276 +1461,44 @@ static int run_steps_impl(isingmc_states *s, size_t timesteps, const double *bet
             if (!std::isfinite(betas[k * beta_stride])) return fail(ISINGMC_ERR_INVALID, "beta must be finite");
     if (device_ms) *device_ms = 0.f;
     TRY(use_device(s->g->device));
-    const isingmc_graph *g = s->g;
     const size_t R = s->R;
     if (R == 0) s->t += timesteps; // time passes for an empty container too (replicas appended later start here)
     if (R == 0 || timesteps == 0) return ISINGMC_OK;
-    if (s->packed) return pk_run_steps(s, timesteps, betas, beta_stride, energies_per_step, device_ms, sync);
-    const bool lattice = g->kind == ISINGMC_KIND_LATTICE2D;
-
-    // per-step energies on the lattice path: integer counters per (step, replica), converted at the
-    // end of each chunk; on the general path one measure() per step.
-    // small lattices: one LDS-resident launch per chunk of timesteps instead of two launches per timestep
-    // (up to 1024 quads per colour: beyond that one workgroup per replica is slower than the launches it saves)
-    // lattices with a field or open boundaries: the multi-class kernels, one launch per colour (+ one measurement per step)
-    const bool mc = lattice && g->mc_mode != MC_NONE;
-    const bool resident = lattice && !mc && g->state_words * sizeof(uint32_t) <= LDS_RESIDENT_MAX_BYTES && g->geom.nquads <= 1024 &&
-                          !resident_disabled(s);
-    // per-step counters: 16 B per (step, replica) and counter slot, at most 32 MiB per chunk on each side of the bus
-    const StripPlan strip = (lattice && !resident && !mc) ? strip_plan(s, timesteps) : StripPlan{};
     s->meas_fresh = false;
-    const size_t step_slots = (energies_per_step && lattice && !resident && !strip.use && !mc) ? MEASURE_SLOTS : 1;
-    size_t chunk = energies_per_step ? std::max<size_t>(1, std::min<size_t>(timesteps, (size_t(32) << 20) / (16 * R * step_slots))) : timesteps;
-    const bool gen_resident = !lattice && gen_resident_fits(g, R) && !resident_disabled(s);
-    // the multi-class modes' LDS-resident kernel: same size bound
-    const bool mc_resident = mc && g->state_words * sizeof(uint32_t) <= LDS_RESIDENT_MAX_BYTES && g->geom.nquads <= 1024 && !resident_disabled(s);
-    if (resident || gen_resident || strip.use || mc_resident) chunk = std::min<size_t>(chunk, 65536);
-    DeviceScratch scratch(s->stream);
-    double *d_beta_steps = nullptr, *d_gen_energies = nullptr;
-    long long *d_gen_mags = nullptr;
-    if (gen_resident) {
-        if (!s->has_betas) TRY(scratch.alloc(&d_beta_steps, beta_stride ? chunk : 1));
-        if (energies_per_step) TRY(scratch.alloc(&d_gen_energies, chunk * R));
-    } else if (!lattice && energies_per_step) { // CSR path: one reduction slot per step, read back per chunk
-        TRY(scratch.alloc(&d_gen_energies, chunk * R));
-        TRY(scratch.alloc(&d_gen_mags, R));
-    }
-    unsigned long long *d_steps = nullptr;
-    LatThr *d_thr_steps = nullptr;
-    std::vector<unsigned long long> h_steps;
-    std::vector<LatThr> h_thr;
-    if (energies_per_step && lattice) {
-        // streaming kernels measure inside the colour-1 half-sweep, into MEASURE_SLOTS partial counters per replica
-        TRY(scratch.alloc(&d_steps, chunk * R * 2 * step_slots));
-        h_steps.resize(chunk * R * 2 * step_slots);
-    }
-    if ((resident || strip.use) && !s->has_betas) TRY(scratch.alloc(&d_thr_steps, beta_stride ? chunk : 1));
-    int rc = ISINGMC_OK;
+    StepRun c{s, plan_steps(s, timesteps, energies_per_step != nullptr), betas, beta_stride, timesteps, energies_per_step, final_energies};
+    const StepPlan &P = c.P;
+    const size_t n_tabs = s->has_betas ? 0 : beta_stride ? P.chunk : 1;
+    if (n_tabs && (P.path == StepPath::LatResident || P.path == StepPath::LatStrip)) TRY(c.scratch.alloc(&c.d_thr, n_tabs));
+    if (n_tabs && P.path == StepPath::GenResident) TRY(c.scratch.alloc(&c.d_betas, n_tabs));
+    if (n_tabs && P.path == StepPath::Packed && s->rj) TRY(c.scratch.alloc(&c.d_rj, n_tabs));
+    if (n_tabs && P.path == StepPath::Packed && !s->rj) TRY(c.scratch.alloc(&c.d_pk_tabs, n_tabs * PK_TAB_WORDS));
+    const bool general = P.path == StepPath::GenResident || P.path == StepPath::GenCsr;
+    if (energies_per_step && general) TRY(c.scratch.alloc(&c.d_energies, P.chunk * R));
+    if (energies_per_step && P.path == StepPath::GenCsr) TRY(c.scratch.alloc(&c.d_mags, R));
+    if (energies_per_step && !general) TRY(c.scratch.alloc(&c.d_counts, P.chunk * counter_slots(s) * P.step_slots * 2));
     if (device_ms) HIP_TRY(hipEventRecord(s->ev0, s->stream));
-    // mid-size launches (a few waves per SIMD) leave the GPU idle around every kernel boundary: run the
-    // replica blocks on several streams.  Large launches (c2) keep the chip full on one stream.
-    size_t want_lanes = 1;
-    if (lattice && !resident && !strip.use && !mc_resident && !energies_per_step) { // the multi-class kernels' launches too
-        const size_t waves_per_launch = R * ((g->geom.nquads + 255) / 256) * 4;
-        if (s->opt.streams > 0) want_lanes = size_t(s->opt.streams);
-        // < 64 waves per SIMD per launch: +17..33 % with 2 lanes (4 go host-bound); short calls lose it to fork/join.
-        // Large launches: +2.8 % (one block's drain overlaps the other's ramp); the fork/join is ~45 us per call
-        else if (waves_per_launch < 64 * 1024 ? timesteps >= 64 : timesteps >= 8) want_lanes = 2;
-        want_lanes = std::min(want_lanes, R);
-    }
     // every exit path below joins the lanes again: later calls (measure, get_states) use s->stream alone
     struct LaneJoin {
         isingmc_states *s;
         ~LaneJoin() { if (s->n_lanes > 1) (void)lanes_join(s); }
     } lane_join{s};
-    if (want_lanes > 1) TRY(lanes_fork(s, want_lanes));
-    for (size_t k0 = 0; k0 < timesteps && rc == ISINGMC_OK; k0 += chunk) {
-        const size_t nk = std::min(chunk, timesteps - k0);
-        if (d_steps) HIP_TRY(hipMemsetAsync(d_steps, 0, nk * R * 2 * step_slots * sizeof(unsigned long long), s->stream));
-        if (resident) {
-            if (!s->has_betas) {
-                h_thr.resize(beta_stride ? nk : 1);
-                for (size_t k = 0; k < h_thr.size(); k++) h_thr[k] = lattice_thresholds(betas[(k0 + k) * beta_stride], g->jabs);
-                HIP_TRY(hipMemcpyAsync(d_thr_steps, h_thr.data(), h_thr.size() * sizeof(LatThr), hipMemcpyHostToDevice, s->stream));
-            }
-            // small lattices: eight (four, two) lanes per quad, one (two, four) Philox calls each (lat_resident_spread_kernel)
-            // ... while every replica of the call is resident at once: beyond that the one-lane-per-quad kernel's small workgroups fill
-            // the chip better (measured, tools/small_lattice_spread_ab.py: 64^2 x 2048 4.1 against 5.9 us, x 4096 10.5 against 9.1;
-            // 128^2 x 512 4.4 against 5.4, x 1024 8.7 against 5.3).  ISINGMC_RESIDENT_SPREAD=0 / 2: never / whenever the lattice allows
-            const int spread_mode = s->opt.resident_spread;
-            // eight lanes per quad only: with four or two (256 / 512 quads per colour, 1024 threads) the barriers of a 16-wave workgroup
-            // cost more than the shorter chain saves (256^2 x 64: 5.7 against 5.1 us; ISINGMC_RESIDENT_LPQ=4 / 2 for A/B runs)
-            const int lpq_forced = s->opt.resident_lpq;
-            const int lpq = lpq_forced == 4 || lpq_forced == 2 ? lpq_forced : 8;
-            bool spread = spread_mode != 0 && size_t(g->geom.nquads) * size_t(lpq) <= 1024;
-            const unsigned spread_threads = unsigned((size_t(g->geom.nquads) * size_t(lpq) + 63) / 64 * 64);
-            const size_t spread_lds = g->state_words * sizeof(uint32_t) + size_t(g->geom.nquads) * 8 * sizeof(uint4);
-            if (spread && spread_mode != 2) {
-                int n_cu = 256;
-                const int per_cu = spread_blocks_per_cu(g->vec, !g->uniform_sign, lpq, spread_threads, spread_lds);
-                (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, g->device);
-                spread = per_cu > 0 && R <= size_t(n_cu) * size_t(per_cu);
-            }
-            const unsigned threads = spread ? spread_threads : unsigned(std::min<size_t>(1024, (g->geom.nquads + 63) / 64 * 64));
-            const size_t lds = spread ? spread_lds : g->state_words * sizeof(uint32_t);
-            const auto launch = [&](auto kernel) {
-                hipLaunchKernelGGL(kernel, dim3(unsigned(R)), dim3(threads), lds, s->stream,
-                                   s->d_state, g->geom, s->t, uint32_t(nk), s->d_keys, d_thr_steps, uint32_t(beta_stride ? 1 : 0),
-                                   s->has_betas ? s->d_thr : nullptr, g->d_jneg, g->jneg_uniform, d_steps, uint32_t(R));
-            };
-            if (spread) {
-                HIP_TRY(spread_launch(g->vec, !g->uniform_sign, lpq, unsigned(R), threads, lds, s->stream, s->d_state, g->geom, s->t, uint32_t(nk), s->d_keys,
-                                      d_thr_steps, uint32_t(beta_stride ? 1 : 0), s->has_betas ? s->d_thr : nullptr, g->d_jneg, g->jneg_uniform,
-                                      d_steps, uint32_t(R)));
-            } else if (g->vec) { if (g->uniform_sign) launch(lat_resident_kernel<true, false>); else launch(lat_resident_kernel<true, true>); }
-            else { if (g->uniform_sign) launch(lat_resident_kernel<false, false>); else launch(lat_resident_kernel<false, true>); }
-            s->t += nk;
-            if (k0 + nk < timesteps && !d_steps) HIP_TRY(hipStreamSynchronize(s->stream)); // h_thr is reused by the next chunk
+    if (P.lanes > 1 && P.path != StepPath::Packed) TRY(lanes_fork(s, P.lanes)); // (the packed runner forks behind its table launches)
+    int rc = ISINGMC_OK;
+    for (size_t k0 = 0; k0 < timesteps && rc == ISINGMC_OK; k0 += P.chunk) {
+        const size_t nk = std::min(P.chunk, timesteps - k0);
+        if (c.d_counts && P.path != StepPath::Packed) // (measure_enqueue clears the packed counters itself)
+            HIP_TRY(hipMemsetAsync(c.d_counts, 0, nk * R * P.step_slots * 2 * sizeof(unsigned long long), s->stream));
+        switch (P.path) {
+        case StepPath::Packed: rc = run_packed(c, k0, nk); break;
+        case StepPath::LatResident: rc = run_lat_resident(c, k0, nk); break;
+        case StepPath::LatStrip: rc = run_lat_strip(c, k0, nk); break;
+        case StepPath::LatStream: rc = run_lat_stream(c, k0, nk); break;
+        case StepPath::McResident: rc = run_mc_resident(c, k0, nk); break;
+        case StepPath::McStream: rc = run_mc_stream(c, k0, nk); break;
+        case StepPath::GenResident: rc = run_gen_resident(c, k0, nk); break;
+        case StepPath::GenCsr: rc = run_gen_csr(c, k0, nk); break;
         }
-        if (strip.use) { // mid-size lattices: the whole chunk of timesteps in one persistent launch per block of replicas
-            if (!s->has_betas) {
-                h_thr.resize(beta_stride ? nk : 1);
-                for (size_t k = 0; k < h_thr.size(); k++) h_thr[k] = lattice_thresholds(betas[(k0 + k) * beta_stride], g->jabs);
-                HIP_TRY(hipMemcpyAsync(d_thr_steps, h_thr.data(), h_thr.size() * sizeof(LatThr), hipMemcpyHostToDevice, s->stream));
-            }
-            // final_energies (device, [R]): the energies of the final configurations come with the last launch (tempering rounds)
-            const bool last = k0 + nk == timesteps;
-            for (size_t r0 = 0; r0 < R && rc == ISINGMC_OK; r0 += strip.replicas_per_pass)
-                rc = launch_strip(s, strip, r0, std::min(strip.replicas_per_pass, R - r0), nk, d_thr_steps, uint32_t(beta_stride ? 1 : 0),
-                                  d_steps ? d_steps + 2 * r0 : nullptr, last ? final_energies : nullptr);
-            if (rc != ISINGMC_OK) break;
-            s->strip_epoch += uint32_t(2 * nk);
-            s->t += nk;
-            if (final_energies && last) s->meas_fresh = true;
-            if (k0 + nk < timesteps && !d_steps) HIP_TRY(hipStreamSynchronize(s->stream)); // h_thr is reused by the next chunk
-        }
-        if (mc_resident) {
-            DeviceScratch thr_scratch(s->stream); // freed (after a stream sync) at the end of this chunk
-            LatThrMC *d_thr_mc_steps = nullptr;
-            if (!s->has_betas) {
-                std::vector<LatThrMC> h(beta_stride ? nk : 1);
-                for (size_t k = 0; k < h.size(); k++) h[k] = lattice_thresholds_mc(g, betas[(k0 + k) * beta_stride]);
-                rc = thr_scratch.alloc(&d_thr_mc_steps, h.size());
-                if (rc != ISINGMC_OK) break;
-                HIP_TRY(hipMemcpy(d_thr_mc_steps, h.data(), h.size() * sizeof(LatThrMC), hipMemcpyHostToDevice));
-            }
-            // small lattices, few enough replicas to be resident at once: eight lanes per quad (lat_mc_resident_kernel SPREAD; the
-            // kernel takes the spread form when the launch's LDS holds the random words too).  ISINGMC_RESIDENT_SPREAD=0: off
-            const int mc_spread_mode = s->opt.resident_spread;
-            int mc_n_cu = 256;
-            (void)hipDeviceGetAttribute(&mc_n_cu, hipDeviceAttributeMultiprocessorCount, g->device);
-            const size_t spread_threads = (size_t(g->geom.nquads) * 8 + 63) / 64 * 64;
-            const bool mc_spread = mc_spread_mode != 0 && spread_threads <= 1024 &&
-                                   (mc_spread_mode == 2 || R <= size_t(mc_n_cu) * std::max<size_t>(1, 1024 / spread_threads));
-            const unsigned threads = mc_spread ? unsigned(spread_threads) : unsigned(std::min<size_t>(1024, (g->geom.nquads + 63) / 64 * 64));
-            const size_t mc_lds = g->state_words * sizeof(uint32_t) + (mc_spread ? size_t(g->geom.nquads) * 8 * sizeof(uint4) : 0);
-            for (size_t r0 = 0; r0 < R && rc == ISINGMC_OK; r0 += 65535) {
-                const size_t n = std::min<size_t>(65535, R - r0);
-                const hipError_t err = mc_launch_resident(g->mc_mode, !g->uniform_sign, unsigned(n), threads, mc_lds,
-                                                          s->stream, s->d_state + r0 * g->state_words, g->geom, s->t, uint32_t(nk), s->d_keys + r0,
-                                                          d_thr_mc_steps, uint32_t(beta_stride ? 1 : 0),
-                                                          s->has_betas ? s->d_thr_mc + r0 : nullptr, g->d_jneg, g->jneg_uniform, g->open, g->d_fneg,
-                                                          d_steps ? d_steps + 2 * r0 : nullptr, uint32_t(R));
-                if (err != hipSuccess) rc = fail(ISINGMC_ERR_HIP, hipGetErrorString(err));
-            }
-            if (rc != ISINGMC_OK) break;
-            s->t += nk;
-        }
-        if (gen_resident) {
-            const size_t nb = beta_stride ? nk : 1;
-            if (!s->has_betas) HIP_TRY(hipMemcpyAsync(d_beta_steps, betas + k0 * beta_stride, nb * sizeof(double), hipMemcpyHostToDevice, s->stream));
-            unsigned threads = 64;
-            for (uint32_t c = 0; c < g->n_colours; c++)
-                threads = std::max<unsigned>(threads, unsigned(std::min<uint64_t>(1024, g->class_base[c + 1] - g->class_base[c])));
-            // the graph in LDS too (gen_resident_kernel STAGE) while every replica of the call can still be resident at once (160 KB
-            // of LDS per compute unit): small graphs, where a timestep is a chain of dependent loads.  Everything when that fits,
-            // else the topology alone (the links of the chain); ISINGMC_GEN_STAGE=0 / 1 / 2 forces none / all / topology (A/B runs)
-            const int stage_mode = s->opt.gen_stage;
-            int n_cu = 256;
-            (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, g->device);
-            const size_t lds_cu = 160 * 1024, lds_max = 150 * 1024; // (a few KB stay free for the kernel's static LDS)
-            size_t stage_bytes = 0;
-            int stage = 0;
-            {
-                size_t bytes[3] = {0, 0, 0}, resident[3] = {0, 0, 0};
-                for (int mode = 1; mode <= 2; mode++) {
-                    bytes[mode] = size_t(gen_stage_words(g->gdev.n_pos, g->gen_edges2, g->gdev.bias != nullptr, g->w_is_float ? 4 : 8, mode)) * 4;
-                    if (bytes[mode] <= lds_max) resident[mode] = std::min<size_t>(2048 / threads, lds_cu / (bytes[mode] + 1024)); // workgroups per compute unit
-                }
-                if (stage_mode == 0) stage = 0;
-                else if (stage_mode == 1 || stage_mode == 2) stage = resident[stage_mode] ? stage_mode : 0;
-                else if (resident[1] && (R <= size_t(n_cu) * resident[1] || threads > 512 || resident[2] <= resident[1])) stage = 1;
-                // (measured, tools/small_graph_stage_ab.py: workgroups of <= 512 threads gain from running side by side, so when
-                //  the full copy would keep some of the call's replicas waiting the smaller one wins: 32^2 x 1024 5.7 against
-                //  6.2 us, 8^3 x 1024 3.5 against 4.4; 1024-thread workgroups do not: 12^3 x 512 6.6 against 9.4)
-                else if (resident[2]) stage = 2;
-                stage_bytes = bytes[stage];
-            }
-            const auto launch = [&](auto kernel) {
-                if (stage_bytes > 64 * 1024) // beyond the default limit of dynamic LDS
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(stage_bytes));
-                hipLaunchKernelGGL(kernel, dim3(unsigned(R)), dim3(threads), stage ? stage_bytes : g->state_words * sizeof(uint32_t), s->stream,
-                                   s->d_state, g->gdev, s->t, uint32_t(nk), s->d_keys, d_beta_steps, uint32_t(beta_stride ? 1 : 0),
-                                   s->has_betas ? s->d_beta : nullptr, d_gen_energies, g->self_energy, g->gen_edges2);
-            };
-            if (g->w_is_float) {
-                if (stage == 1) launch(gen_resident_kernel<float, 1>); else if (stage == 2) launch(gen_resident_kernel<float, 2>); else launch(gen_resident_kernel<float, 0>);
-            } else {
-                if (stage == 1) launch(gen_resident_kernel<double, 1>); else if (stage == 2) launch(gen_resident_kernel<double, 2>); else launch(gen_resident_kernel<double, 0>);
-            }
-            s->t += nk;
-            if (d_gen_energies) {
-                std::vector<double> he(nk * R);
-                hipError_t err = hipMemcpyAsync(he.data(), d_gen_energies, he.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream);
-                if (err == hipSuccess) err = hipStreamSynchronize(s->stream);
-                if (err != hipSuccess) { rc = fail(ISINGMC_ERR_HIP, hipGetErrorString(err)); break; }
-                for (size_t r = 0; r < R; r++)
-                    for (size_t k = 0; k < nk; k++) energies_per_step[r * timesteps + k0 + k] = he[r * nk + k];
-            } else if (k0 + nk < timesteps) {
-                HIP_TRY(hipStreamSynchronize(s->stream));
-            }
-        }
-        for (size_t k = k0; k < k0 + nk && !resident && !gen_resident && !strip.use && !mc_resident; k++) {
-            const double beta = s->has_betas ? 0.0 : betas[k * beta_stride];
-            if (mc) {
-                const LatThrMC thr = lattice_thresholds_mc(g, beta);
-                const size_t per_lane = (R + s->n_lanes - 1) / s->n_lanes; // replica blocks on the lanes' streams, as launch_lat_sweep
-                for (uint32_t colour = 0; colour < 2 && rc == ISINGMC_OK; colour++)
-                    for (size_t lane = 0; lane < s->n_lanes && rc == ISINGMC_OK; lane++) {
-                        const size_t lo = lane * per_lane, hi = std::min(R, lo + per_lane);
-                        hipStream_t stream = s->n_lanes > 1 ? s->lanes[lane] : s->stream;
-                        for (size_t r0 = lo; r0 < hi; r0 += MAX_GRID_Y) {
-                            const size_t n = std::min(MAX_GRID_Y, hi - r0);
-                            const hipError_t err = mc_launch_sweep(g->mc_mode, !g->uniform_sign, lat_grid(g, g->geom.nquads, n), stream,
-                                                                   s->d_state + r0 * g->state_words, g->geom, colour, s->t, s->d_keys + r0, thr,
-                                                                   s->has_betas ? s->d_thr_mc + r0 : nullptr, g->d_jneg, g->jneg_uniform, g->open,
-                                                                   g->d_fneg);
-                            if (err != hipSuccess) { rc = fail(ISINGMC_ERR_HIP, hipGetErrorString(err)); break; }
-                        }
-                    }
-                if (rc != ISINGMC_OK) break;
-                if (d_steps) { // get_energy after this timestep: a measurement pass behind the sweep (as on the general path)
-                    s->t++;
-                    rc = measure_enqueue(s, d_steps + (k - k0) * R * 2, nullptr, nullptr);
-                    if (rc != ISINGMC_OK) break;
-                    continue;
-                }
-            } else if (lattice) {
-                const LatThr thr = lattice_thresholds(beta, g->jabs);
-                LAT_DISPATCH(launch_lat_sweep, s, 0u, thr, s->t);
-                if (d_steps) LAT_DISPATCH(launch_lat_sweep_measure, s, thr, s->t, d_steps + (k - k0) * R * 2 * step_slots, 2 * step_slots);
-                else LAT_DISPATCH(launch_lat_sweep, s, 1u, thr, s->t);
-            } else {
-                launch_gen_timestep(s, beta);
-            }
-            s->t++;
-            if (energies_per_step && !lattice) {
-                rc = measure_enqueue(s, nullptr, d_gen_energies + (k - k0) * R, d_gen_mags);
-                if (rc != ISINGMC_OK) break;
-            }
-        }
-        if (energies_per_step && !lattice && !gen_resident && rc == ISINGMC_OK) {
-            std::vector<double> he(nk * R);
-            hipError_t err = hipMemcpyAsync(he.data(), d_gen_energies, he.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream);
-            if (err == hipSuccess) err = hipStreamSynchronize(s->stream);
-            if (err != hipSuccess) { rc = fail(ISINGMC_ERR_HIP, hipGetErrorString(err)); break; }
-            for (size_t k = 0; k < nk; k++)
-                for (size_t r = 0; r < R; r++) energies_per_step[r * timesteps + k0 + k] = he[k * R + r] + g->self_energy;
-        }
-        if (d_steps && rc == ISINGMC_OK) {
-            hipError_t err = hipMemcpyAsync(h_steps.data(), d_steps, nk * R * 2 * step_slots * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->stream);
-            if (err == hipSuccess) err = hipStreamSynchronize(s->stream);
-            if (err != hipSuccess) { rc = fail(ISINGMC_ERR_HIP, hipGetErrorString(err)); break; }
-            for (size_t k = 0; k < nk; k++)
-                for (size_t r = 0; r < R; r++) {
-                    unsigned long long sat = 0, up = 0;
-                    for (size_t sl = 0; sl < step_slots; sl++) {
-                        sat += h_steps[((k * R + r) * step_slots + sl) * 2];
-                        up += h_steps[((k * R + r) * step_slots + sl) * 2 + 1];
-                    }
-                    energies_per_step[r * timesteps + k0 + k] = lattice_energy(g, sat, up);
-                }
-        }
+        if (rc == ISINGMC_OK && energies_per_step) rc = read_step_energies(c, k0, nk);
     }
     if (s->n_lanes > 1) { const int jrc = lanes_join(s); if (rc == ISINGMC_OK) rc = jrc; }
     if (device_ms && rc == ISINGMC_OK) {
@@ -1435,7 +1511,7 @@ static int run_steps_impl(isingmc_states *s, size_t timesteps, const double *bet
     HIP_TRY(hipGetLastError());
     if (sync) {
         HIP_TRY(hipStreamSynchronize(s->stream));
-        if (strip.use) TRY(strip_check(s));
+        if (P.path == StepPath::LatStrip) TRY(strip_check(s));
     }
     return ISINGMC_OK;
 }
@@ -1476,81 +1552,4 @@ extern "C" int isingmc_get_packed_states(isingmc_states *s, uint32_t *words_out)
     HIP_TRY(hipMemcpyAsync(words_out, s->d_state, s->R * s->g->state_words * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return ISINGMC_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// measurements enqueued behind the sweeps (per-step energies, sampling, tempering rounds)
-// ------------------------------------------------------------------------------------------------
-int measure_enqueue(isingmc_states *s, unsigned long long *counts_slot, double *e_slot, long long *m_slot, bool want_up)
-{
-    const isingmc_graph *g = s->g;
-    const size_t R = s->R;
-    if (s->packed) { // counts_slot: [pk_slots()][2], one pair per (group, bit) -- a shard may own only some bits of a group
-        HIP_TRY(hipMemsetAsync(counts_slot, 0, 2 * s->pk_slots() * sizeof(unsigned long long), s->stream));
-        if (s->rj) {
-            const bool bip = g->n_colours == 2;
-            int dev_cus = 256;
-            (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, g->device);
-            // all workgroups resident at once (the runtime's occupancy figure for this instantiation), every one walks its
-            // share of the blocks; a grid one round and a bit long would run its tail at a fraction of the chip
-            static std::mutex per_cu_mutex; // (the device fan-out measures from several host threads)
-            static int per_cu[6][2][2] = {};
-            int pc;
-            {
-                std::lock_guard<std::mutex> lock(per_cu_mutex);
-                int &slot = per_cu[g->rj.slots == 4 ? 0 : g->rj.slots == 7 ? 1 : g->rj.slots == 11 ? 2 : g->rj.slots == 15 ? 3 : g->rj.slots == 23 ? 4 : 5][bip][want_up];
-                if (slot == 0) slot = std::max(1, rj_measure_blocks_per_cu(g->rj.slots, bip, want_up));
-                pc = slot;
-            }
-            const size_t resident = size_t(pc) * size_t(std::max(dev_cus, 1));
-            // two colour classes: the bonds from class 0 alone; class 1 is visited only for its bias terms or the up spins
-            const uint32_t class0_end = bip ? uint32_t(g->class_base[1]) : 0u;
-            const uint32_t scan_end = bip && !g->has_bias && !want_up ? class0_end : g->pk.n_pos;
-            const size_t scan_blocks = scan_end / rj_threads(g->rj.slots);
-            for (size_t g0 = 0; g0 < s->groups; g0 += MAX_GRID_Y) {
-                const size_t ng = std::min(MAX_GRID_Y, s->groups - g0);
-                const size_t gx = std::min(scan_blocks, std::max<size_t>(1, resident / ng));
-                // hi level (+ the up spins when wanted) into the first counter of a slot, lo level into the second
-                HIP_TRY(rj_launch_measure(dim3(unsigned(std::max<size_t>(gx, 1)), unsigned(ng)), s->stream, s->d_state + g0 * g->pk.n_pos, g->rj_hi,
-                                          g->pk.site, class0_end, scan_end, want_up, counts_slot + 2 * 32 * g0));
-                if (!want_up)
-                    HIP_TRY(rj_launch_measure(dim3(unsigned(std::max<size_t>(gx, 1)), unsigned(ng)), s->stream, s->d_state + g0 * g->pk.n_pos, g->rj_lo,
-                                              g->pk.site, class0_end, scan_end, false, counts_slot + 2 * 32 * g0 + 1));
-            }
-            return ISINGMC_OK;
-        }
-        uint32_t ppt = PK_MEASURE_POS_PER_THREAD; // halved until the launch has >= 1024 workgroups (not below 8: the transpose
-                                                  // at the end of a chunk costs as much as ~16 positions)
-        while (ppt > 8 && size_t((g->pk.n_pos + 256 * ppt - 1) / (256 * ppt)) * s->groups < 1024) ppt /= 2;
-        const unsigned blocks = unsigned(std::max<uint32_t>(1, std::min<uint32_t>(2048, (g->pk.n_pos + 256 * ppt - 1) / (256 * ppt))));
-        for (size_t g0 = 0; g0 < s->groups; g0 += MAX_GRID_Y) {
-            const size_t ng = std::min(MAX_GRID_Y, s->groups - g0);
-            hipLaunchKernelGGL(pk_measure_kernel, dim3(blocks, unsigned(ng)), dim3(256), 0, s->stream,
-                               s->d_state + g0 * g->pk.n_pos, g->pk, counts_slot + 2 * 32 * g0, uint32_t(32 * ng), ppt,
-                               g->n_colours == 2 ? uint32_t(g->class_base[1]) : g->pk.n_pos, g->n_colours == 2 ? 2u : 1u);
-        }
-    } else if (g->kind == ISINGMC_KIND_LATTICE2D) {
-        HIP_TRY(hipMemsetAsync(counts_slot, 0, 2 * R * sizeof(unsigned long long), s->stream));
-        LAT_DISPATCH(launch_lat_measure, s, counts_slot, size_t(2));
-    } else {
-        for (size_t r0 = 0; r0 < R; r0 += MAX_GRID_Y) {
-            const size_t n = std::min(MAX_GRID_Y, R - r0);
-            const dim3 grid(s->n_partials, unsigned(n));
-            if (g->w_is_float)
-                hipLaunchKernelGGL(gen_measure_kernel<float>, grid, dim3(256), 0, s->stream, s->d_state + r0 * g->state_words,
-                                   g->gdev, s->d_pe + r0 * s->n_partials, s->d_pm + r0 * s->n_partials);
-            else
-                hipLaunchKernelGGL(gen_measure_kernel<double>, grid, dim3(256), 0, s->stream, s->d_state + r0 * g->state_words,
-                                   g->gdev, s->d_pe + r0 * s->n_partials, s->d_pm + r0 * s->n_partials);
-        }
-        hipLaunchKernelGGL(gen_reduce_kernel, dim3(unsigned(R)), dim3(256), 0, s->stream, s->d_pe, s->d_pm, s->n_partials,
-                           e_slot, m_slot);
-    }
-    HIP_TRY(hipGetLastError());
-    return ISINGMC_OK;
-}
-
-void lat_measure_enqueue(isingmc_states *s, unsigned long long *out, size_t out_stride)
-{
-    LAT_DISPATCH(launch_lat_measure, s, out, out_stride);
 }

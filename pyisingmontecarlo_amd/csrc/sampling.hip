@@ -106,17 +106,10 @@ extern "C" int isingmc_run_sampling(isingmc_states *s, double beta, size_t therm
                                     size_t n_samples, double *energies_out, uint8_t *states_out)
 {
     if (!s) return fail(ISINGMC_ERR_INVALID, "NULL states");
-    if (!may_use_strips(s) || !(strip_plan(s, thermalization).use || strip_plan(s, sampling_freq).use))
-        return strip_error(run_sampling_impl(s, beta, thermalization, sampling_freq, n_samples, energies_out, states_out));
-    // as run_steps: the call keeps the planes it started from and is repeated without the strip kernel if a launch gives up
-    TRY(use_device(s->g->device));
-    const uint64_t t0 = s->t;
-    TRY(snapshot_take(s));
-    int rc = run_sampling_impl(s, beta, thermalization, sampling_freq, n_samples, energies_out, states_out);
-    if (rc != STRIP_TIMED_OUT) return rc;
-    TRY(snapshot_restore(s));
-    s->t = t0;
-    return strip_error(run_sampling_impl(s, beta, thermalization, sampling_freq, n_samples, energies_out, states_out));
+    const bool may_strip = may_use_strips(s) && (strip_plan(s, thermalization).use || strip_plan(s, sampling_freq).use);
+    return with_strip_retry(s, may_strip, [&] {
+        return run_sampling_impl(s, beta, thermalization, sampling_freq, n_samples, energies_out, states_out);
+    });
 }
 
 static int run_sampling_impl(isingmc_states *s, double beta, size_t thermalization, size_t sampling_freq, size_t n_samples,
@@ -149,7 +142,7 @@ static int run_sampling_impl(isingmc_states *s, double beta, size_t thermalizati
     }
     const bool counts = s->packed || g->kind == ISINGMC_KIND_LATTICE2D;
     const size_t words = s->packed ? s->groups * size_t(g->pk.n_pos) : R * g->state_words;
-    const size_t CS = s->packed ? s->pk_slots() : R; // counter pairs per sample
+    const size_t CS = counter_slots(s); // counter pairs per sample
     // Pipeline over SLABS of samples (<= 64 MiB of packed words each), two in flight: while the host expands
     // slab j-1 from pinned memory into the caller's bool[R,S,N] array (non-temporal stores, all host threads), the device
     // runs the sweeps of slab j and a second stream copies finished slabs out.  The expansion to one byte per spin is the
@@ -168,19 +161,16 @@ static int run_sampling_impl(isingmc_states *s, double beta, size_t thermalizati
         parallel_for(nk * R, [&](size_t idx) {
             const size_t k = idx / R, r = idx % R;
             uint8_t *out = states_out + (r * S + k0 + k) * N;
-            double energy;
+            const size_t sl = counter_slot(s, r);
             if (s->packed) {
-                const size_t sl = r + s->pk_bit0;
                 const uint32_t *w = h_samples + k * words + (sl / 32) * g->pk.n_pos;
                 const uint32_t bit = uint32_t(sl % 32);
                 for (uint64_t i = 0; i < N; i++) out[i] = (w[g->pos[i]] >> bit) & 1u;
-                energy = pk_energy(g, s->rj, h_counts[(k * CS + sl) * 2], h_counts[(k * CS + sl) * 2 + 1]);
             } else {
                 unpack_state(g, h_samples + k * words + r * g->state_words, out);
-                if (counts) energy = lattice_energy(g, h_counts[(k * R + r) * 2], h_counts[(k * R + r) * 2 + 1]);
-                else energy = h_e[k * R + r] + g->self_energy;
             }
-            energies_out[r * S + k0 + k] = energy;
+            energies_out[r * S + k0 + k] = counts ? counters_energy(s, h_counts[(k * CS + sl) * 2], h_counts[(k * CS + sl) * 2 + 1])
+                                                  : h_e[k * R + r] + g->self_energy;
         }, N);
     };
     for (size_t j = 0; j < n_slabs; j++) {
