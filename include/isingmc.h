@@ -232,6 +232,20 @@ uint64_t isingmc_states_timestep(const isingmc_states *states);
  * resumes on exactly the trajectory it would have followed (the reference has no equivalent: its rng state is not exposed). */
 int isingmc_states_set_timestep(isingmc_states *states, uint64_t t);
 
+/* ---- Swendsen-Wang cluster updates (this build's own non-local move, no reference counterpart) ----
+ * With k > 0 every timestep t with t % k == k - 1 (t = isingmc_states_timestep) is a cluster step instead of a Metropolis sweep:
+ * bonds between satisfied neighbours are activated with probability 1 - exp(-2 beta |J|), every connected cluster is flipped with
+ * probability 1/2.  It counts as one timestep in every call (per-step energies, sampling, schedules, isingmc_states_set_timestep).
+ * Served: checkerboard lattice containers with fast_path == 0 (periodic, no field, one |J|) and one coupling sign, W H < 2^32 - 1,
+ * no ladder attached; everything else returns ISINGMC_ERR_INVALID and leaves k as it was.  k = 0 (the default) switches it off.
+ * The workspace of a cluster step (8.4 bytes per site and replica) is limited by the option "cluster_workspace_bytes"
+ * (isingmc_states_set_option; replicas are processed in batches that fit, at least one at a time; results do not depend on it). */
+int isingmc_states_set_cluster_every(isingmc_states *states, size_t k);
+int isingmc_states_cluster_every(const isingmc_states *states, size_t *k_out);
+/* the last cluster step of every replica: number of clusters and size of the largest one, uint64[R] each (synchronises);
+ * ISINGMC_ERR_INVALID before the first cluster step */
+int isingmc_cluster_stats(isingmc_states *states, uint64_t *n_clusters_out, uint64_t *largest_out);
+
 /* replaces the whole sampling loop of lattice.rs:271-287 / classicising.rs:144-173:
  *   thermalization x do_time_step(beta);  n_samples x { sampling_freq x do_time_step(beta);
  *   states[r][k][:] = state_ref();  energies[r][k] = get_energy() }

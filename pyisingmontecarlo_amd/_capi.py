@@ -66,6 +66,9 @@ _PROTOTYPES = {
     "isingmc_get_packed_states": (C.c_int, [_vp, _vp]),
     "isingmc_states_timestep": (C.c_uint64, [_vp]),
     "isingmc_states_set_timestep": (C.c_int, [_vp, C.c_uint64]),
+    "isingmc_states_set_cluster_every": (C.c_int, [_vp, C.c_size_t]),
+    "isingmc_states_cluster_every": (C.c_int, [_vp, C.POINTER(C.c_size_t)]),
+    "isingmc_cluster_stats": (C.c_int, [_vp, _vp, _vp]),
     "isingmc_run_sampling": (C.c_int, [_vp, C.c_double, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp]),
     "isingmc_pt_attach": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint64]),
     "isingmc_pt_can_attach": (C.c_int, [_vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_int)]),
@@ -384,6 +387,22 @@ class States:
         if b is not None and b.size != self.count:
             raise ValueError("one beta per replica expected")
         _check(lib().isingmc_states_set_betas(self._h, _p(b)))
+
+    def set_cluster_every(self, k):
+        """Every k-th timestep (t % k == k - 1) becomes a Swendsen-Wang cluster step; 0 switches it off."""
+        _check(lib().isingmc_states_set_cluster_every(self._h, int(k)))
+
+    @property
+    def cluster_every(self):
+        k = C.c_size_t()
+        _check(lib().isingmc_states_cluster_every(self._h, C.byref(k)))
+        return int(k.value)
+
+    def cluster_stats(self):
+        """(number of clusters, size of the largest cluster) of every replica's last cluster step: two uint64[R] arrays."""
+        n, largest = np.zeros(self.count, dtype=np.uint64), np.zeros(self.count, dtype=np.uint64)
+        _check(lib().isingmc_cluster_stats(self._h, _p(n), _p(largest)))
+        return n, largest
 
     def do_time_steps(self, timesteps, beta=None, per_step_energies=False):
         """beta: float (constant), sequence of length timesteps, or None when per-replica betas are set."""

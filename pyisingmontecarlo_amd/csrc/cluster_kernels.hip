@@ -1,0 +1,227 @@
+// Swendsen-Wang cluster step: five plain stream-ordered launches per batch of replicas.
+//   cl_bonds_kernel   one thread per (direction, plane, word): 8 Philox calls -> the 32 active-bond bits of the word's sites;
+//                     the tail of the grid writes the flip bits of all possible roots (one Philox call per 128 site ids)
+//   cl_tile_kernel    one workgroup per 64 x 32 tile: union-find over the tile's inner bonds in LDS, labels = global site ids
+//   cl_merge_kernel   one thread per bond that leaves a tile (both periodic wraps included): union in global memory
+//   cl_flip_kernel    one wave per 64 consecutive sites of a row: chase to the root, look the flip bit up, ballot -> the two
+//                     32-spin words of the row segment; counts the roots and the sites per root
+//   cl_max_kernel     largest cluster
+// Every union links a root to a SMALLER site id with an integer atomicMin, so the final root of a component is its smallest
+// site id whatever the order of execution, and every loop below walks strictly decreasing labels: it ends after at most
+// W H steps without waiting for any other thread.
+#include "cluster_kernels.hpp"
+
+namespace isingmc {
+
+namespace {
+
+// ---- union-find on a label array that other threads link concurrently (LDS: workgroup scope, global: agent scope) ------------
+template <int SCOPE>
+__device__ __forceinline__ uint32_t cl_load(const uint32_t *p)
+{
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, SCOPE);
+}
+
+template <int SCOPE>
+__device__ __forceinline__ uint32_t cl_find(const uint32_t *lab, uint32_t a)
+{
+    for (uint32_t p = cl_load<SCOPE>(lab + a); p != a; p = cl_load<SCOPE>(lab + a)) a = p; // p < a: strictly decreasing
+    return a;
+}
+
+template <int SCOPE>
+__device__ __forceinline__ void cl_unite(uint32_t *lab, uint32_t a, uint32_t b)
+{
+    for (;;) {
+        a = cl_find<SCOPE>(lab, a);
+        b = cl_find<SCOPE>(lab, b);
+        if (a == b) return;
+        if (a < b) { const uint32_t x = a; a = b; b = x; }
+        // a > b: hang root a below b.  If a has stopped being a root meanwhile, its label is now min(old, b) -- still a member
+        // of the same component -- and the union goes on between old (< a) and b.
+        const uint32_t old = __hip_atomic_fetch_min(lab + a, b, __ATOMIC_RELAXED, SCOPE);
+        if (old == a) return;
+        a = old;
+    }
+}
+
+// bits 0, 2, 4, ... of x, packed
+__device__ __forceinline__ uint32_t even_bits(uint64_t x)
+{
+    x &= 0x5555555555555555ull;
+    x = (x | (x >> 1)) & 0x3333333333333333ull;
+    x = (x | (x >> 2)) & 0x0F0F0F0F0F0F0F0Full;
+    x = (x | (x >> 4)) & 0x00FF00FF00FF00FFull;
+    x = (x | (x >> 8)) & 0x0000FFFF0000FFFFull;
+    x = (x | (x >> 16)) & 0x00000000FFFFFFFFull;
+    return uint32_t(x);
+}
+
+} // namespace
+
+// grid: (ceil(4.5 wpp / 256), n).  Thread gid < 4 wpp: bond word gid = (2 d + c) wpp + w; the wpp / 2 threads behind them: the
+// flip table.
+__global__ __launch_bounds__(256) void cl_bonds_kernel(const uint32_t *__restrict__ state, const LatGeom g, const uint64_t t,
+                                                       const uint2 *__restrict__ keys, const uint32_t jneg_uniform, const uint64_t thr,
+                                                       const uint64_t *__restrict__ thr_per_replica, uint32_t *__restrict__ bonds,
+                                                       uint32_t *__restrict__ fliptab)
+{
+    const uint32_t r = blockIdx.y, gid = blockIdx.x * 256 + threadIdx.x;
+    const uint2 key = keys[r];
+    const uint32_t c0 = uint32_t(t);
+    if (gid >= 4 * g.wpp) {
+        const uint32_t q = gid - 4 * g.wpp; // site ids 128 q .. 128 q + 127
+        if (q < g.wpp / 2) {
+            const uint4 v = philox4x32_10(make_uint4(c0, q, DOM_SW_FLIP, ctr2(t, 0, 0)), key);
+            *reinterpret_cast<uint4 *>(fliptab + size_t(r) * 2 * g.wpp + 4 * size_t(q)) = v;
+        }
+        return;
+    }
+    const uint32_t d = gid >= 2 * g.wpp, rem = gid - d * 2 * g.wpp, c = rem >= g.wpp, w = rem - c * g.wpp;
+    const uint32_t y = w / g.wpr, k = w - y * g.wpr;
+    const uint32_t *own = state + size_t(r) * 2 * g.wpp + size_t(c) * g.wpp, *oth = state + size_t(r) * 2 * g.wpp + size_t(1 - c) * g.wpp;
+    uint32_t nb;
+    if (d == 0) { // right neighbour: compact index i + 1 on the rows where this colour sits on odd columns, else i
+        nb = oth[w];
+        if ((y + c) & 1u) nb = (nb >> 1) | (oth[y * g.wpr + (k + 1 == g.wpr ? 0 : k + 1)] << 31);
+    } else {
+        nb = oth[(y + 1 == g.H ? 0 : y + 1) * g.wpr + k];
+    }
+    const uint32_t sat = own[w] ^ nb ^ jneg_uniform; // J s s < 0
+    const uint64_t T = thr_per_replica ? thr_per_replica[r] : thr;
+    uint32_t act = 0;
+    if (T >> 32) act = sat;
+    else if (T != 0) {
+        const uint32_t T32 = uint32_t(T);
+#pragma unroll 2
+        for (uint32_t j = 0; j < 8; j++) {
+            const uint4 u = philox4x32_10(make_uint4(c0, w, DOM_SW_BOND, ctr2(t, c, 8 * d + j)), key);
+            act |= (uint32_t(u.x < T32) | (uint32_t(u.y < T32) << 1) | (uint32_t(u.z < T32) << 2) | (uint32_t(u.w < T32) << 3)) << (4 * j);
+        }
+        act &= sat;
+    }
+    bonds[size_t(r) * 4 * g.wpp + gid] = act;
+}
+
+// grid: (W / 64, ceil(H / CL_TILE_ROWS), n)
+__global__ __launch_bounds__(256) void cl_tile_kernel(const LatGeom g, const uint32_t *__restrict__ bonds, uint32_t *__restrict__ labels,
+                                                      uint32_t *__restrict__ sizes)
+{
+    __shared__ uint32_t lab[CL_TILE_W * CL_TILE_ROWS];
+    __shared__ uint32_t sb[2][2][CL_TILE_ROWS]; // [direction][plane][row of the tile]
+    constexpr int WG = __HIP_MEMORY_SCOPE_WORKGROUP;
+    const uint32_t tx = blockIdx.x, y0 = blockIdx.y * CL_TILE_ROWS, r = blockIdx.z, tid = threadIdx.x;
+    const uint32_t rows = min(CL_TILE_ROWS, g.H - y0);
+    const uint32_t *b = bonds + size_t(r) * 4 * g.wpp;
+    if (tid < 4 * CL_TILE_ROWS) {
+        const uint32_t dc = tid / CL_TILE_ROWS, ly = tid % CL_TILE_ROWS;
+        sb[dc >> 1][dc & 1][ly] = ly < rows ? b[size_t(dc) * g.wpp + (y0 + ly) * g.wpr + tx] : 0u;
+    }
+    for (uint32_t l = tid; l < CL_TILE_W * CL_TILE_ROWS; l += 256) lab[l] = l;
+    __syncthreads();
+    for (uint32_t l = tid; l < CL_TILE_W * rows; l += 256) {
+        const uint32_t lx = l & 63u, ly = l >> 6, c = (lx + y0 + ly) & 1u, bit = lx >> 1;
+        if (lx < 63 && ((sb[0][c][ly] >> bit) & 1u)) cl_unite<WG>(lab, l, l + 1);
+        if (ly + 1 < rows && ((sb[1][c][ly] >> bit) & 1u)) cl_unite<WG>(lab, l, l + CL_TILE_W);
+    }
+    __syncthreads();
+    const size_t base = size_t(r) * g.W * g.H;
+    for (uint32_t l = tid; l < CL_TILE_W * rows; l += 256) {
+        const uint32_t root = cl_find<WG>(lab, l); // local order = global order inside a tile: the smallest site of the local component
+        const size_t site = base + size_t(y0 + (l >> 6)) * g.W + tx * CL_TILE_W + (l & 63u);
+        labels[site] = (y0 + (root >> 6)) * g.W + tx * CL_TILE_W + (root & 63u);
+        sizes[site] = 0;
+    }
+}
+
+// grid: (ceil((H W / 64 + ceil(H / CL_TILE_ROWS) W) / 256), n): the right bond of the last column of every tile, then the down
+// bond of the last row of every tile
+__global__ __launch_bounds__(256) void cl_merge_kernel(const LatGeom g, const uint32_t *__restrict__ bonds, uint32_t *__restrict__ labels)
+{
+    const uint32_t r = blockIdx.y, gid = blockIdx.x * 256 + threadIdx.x;
+    const uint32_t n_right = g.H * g.wpr, tile_rows = (g.H + CL_TILE_ROWS - 1) / CL_TILE_ROWS;
+    uint32_t x, y, d, nbr;
+    if (gid < n_right) {
+        y = gid / g.wpr;
+        x = (gid - y * g.wpr) * CL_TILE_W + CL_TILE_W - 1;
+        d = 0;
+        nbr = y * g.W + (x + 1 == g.W ? 0 : x + 1);
+    } else {
+        const uint32_t j = gid - n_right, ty = j / g.W;
+        if (ty >= tile_rows) return;
+        x = j - ty * g.W;
+        y = min(ty * CL_TILE_ROWS + CL_TILE_ROWS - 1, g.H - 1);
+        d = 1;
+        nbr = (y + 1 == g.H ? 0 : y + 1) * g.W + x;
+    }
+    const uint32_t c = (x + y) & 1u;
+    const uint32_t word = bonds[size_t(r) * 4 * g.wpp + size_t(2 * d + c) * g.wpp + y * g.wpr + (x >> 6)];
+    if ((word >> ((x >> 1) & 31u)) & 1u) cl_unite<__HIP_MEMORY_SCOPE_AGENT>(labels + size_t(r) * g.W * g.H, y * g.W + x, nbr);
+}
+
+// grid: (ceil(wpp / 4), n); wave `seg` owns sites 64 seg .. 64 seg + 63 = word seg of both planes.  Nothing writes the labels here.
+__global__ __launch_bounds__(256) void cl_flip_kernel(uint32_t *__restrict__ state, const LatGeom g, const uint32_t *__restrict__ labels,
+                                                      const uint32_t *__restrict__ fliptab, uint32_t *__restrict__ sizes,
+                                                      uint32_t *__restrict__ stats)
+{
+    const uint32_t r = blockIdx.y, seg = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (seg >= g.wpp) return; // (the whole wave)
+    const size_t N = size_t(g.W) * g.H;
+    const uint32_t *lab = labels + size_t(r) * N;
+    const uint32_t site = seg * 64 + lane;
+    uint32_t root = lab[site];
+    for (uint32_t p = lab[root]; p != root; p = lab[root]) root = p;
+    const uint32_t flip = (fliptab[size_t(r) * (N / 32) + (root >> 5)] >> (root & 31u)) & 1u;
+    const uint64_t flips = __ballot(flip != 0), roots = __ballot(root == site);
+    // sites per root: lanes with the root of the first pending lane add up in one atomic (a row segment inside a large cluster
+    // is one root); after four rounds the rest go one by one
+    uint32_t *sz = sizes + size_t(r) * N;
+    uint64_t pending = __ballot(1);
+    for (int it = 0; it < 4 && pending; it++) {
+        const int leader = __ffsll((unsigned long long)pending) - 1;
+        const uint32_t lr = __shfl(root, leader);
+        const uint64_t same = __ballot(root == lr);
+        if (int(lane) == leader) atomicAdd(sz + lr, uint32_t(__popcll(same)));
+        pending &= ~same;
+    }
+    if ((pending >> lane) & 1ull) atomicAdd(sz + root, 1u);
+    const uint32_t y = seg / g.wpr;
+    uint32_t *st = state + size_t(r) * 2 * g.wpp;
+    // even columns belong to plane y & 1, odd columns to the other one; compact index = column >> 1
+    if (lane == 0) {
+        st[size_t(y & 1u) * g.wpp + seg] ^= even_bits(flips);
+        if (roots) atomicAdd(stats + 2 * r, uint32_t(__popcll(roots)));
+    } else if (lane == 1) {
+        st[size_t((y + 1) & 1u) * g.wpp + seg] ^= even_bits(flips >> 1);
+    }
+}
+
+// grid: (ceil(N / 1024), n): four sites per thread (N is a multiple of 128)
+__global__ __launch_bounds__(256) void cl_max_kernel(const uint32_t *__restrict__ sizes, const uint32_t quads, uint32_t *__restrict__ stats)
+{
+    const uint32_t r = blockIdx.y, q = blockIdx.x * 256 + threadIdx.x;
+    uint32_t m = 0;
+    if (q < quads) {
+        const uint4 v = reinterpret_cast<const uint4 *>(sizes + size_t(r) * 4 * quads)[q];
+        m = max(max(v.x, v.y), max(v.z, v.w));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = max(m, uint32_t(__shfl_xor(m, o)));
+    if ((threadIdx.x & 63u) == 0 && m) atomicMax(stats + 2 * r + 1, m);
+}
+
+hipError_t cluster_launch_step(hipStream_t stream, uint32_t *state, const LatGeom &g, uint64_t t, const uint2 *keys, uint32_t jneg_uniform,
+                               uint64_t thr, const uint64_t *thr_per_replica, const ClusterWork &work, uint32_t n, uint32_t *stats)
+{
+    const uint32_t wpp = g.wpp, tile_rows = (g.H + CL_TILE_ROWS - 1) / CL_TILE_ROWS;
+    const uint32_t border = g.H * g.wpr + tile_rows * g.W, quads = g.W * g.H / 4;
+    hipLaunchKernelGGL(cl_bonds_kernel, dim3((4 * wpp + wpp / 2 + 255) / 256, n), dim3(256), 0, stream, state, g, t, keys, jneg_uniform, thr,
+                       thr_per_replica, work.bonds, work.fliptab);
+    hipLaunchKernelGGL(cl_tile_kernel, dim3(g.wpr, tile_rows, n), dim3(256), 0, stream, g, work.bonds, work.labels, work.sizes);
+    hipLaunchKernelGGL(cl_merge_kernel, dim3((border + 255) / 256, n), dim3(256), 0, stream, g, work.bonds, work.labels);
+    hipLaunchKernelGGL(cl_flip_kernel, dim3((wpp + 3) / 4, n), dim3(256), 0, stream, state, g, work.labels, work.fliptab, work.sizes, stats);
+    hipLaunchKernelGGL(cl_max_kernel, dim3((quads + 255) / 256, n), dim3(256), 0, stream, work.sizes, quads, stats);
+    return hipGetLastError();
+}
+
+} // namespace isingmc

@@ -1,0 +1,34 @@
+// Swendsen-Wang cluster step for periodic, field-free checkerboard lattices with one |J| and one coupling
+// sign: launch interface of cluster_kernels.hip (a translation unit of its own: nothing here is instantiated beside the
+// tuned sweep kernels).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstddef>
+#include <cstdint>
+
+#include "lattice_kernels.hpp"
+
+namespace isingmc {
+
+constexpr uint32_t DOM_SW_BOND = 0x53574244u; // "SWBD"
+constexpr uint32_t DOM_SW_FLIP = 0x5357464Cu; // "SWFL"
+
+constexpr uint32_t CL_TILE_W = 64;    // sites: the 32 spins of one word of plane 0 interleaved with the 32 of plane 1
+constexpr uint32_t CL_TILE_ROWS = 32; // rows of a tile (the last tile row of a lattice may be shorter)
+
+// workspace of one batch of n replicas (N = W H sites, wpp = N / 64 words per plane)
+struct ClusterWork {
+    uint32_t *labels;  // [n][N]       site -> a smaller site of its cluster (the root: the smallest)
+    uint32_t *sizes;   // [n][N]       sites per root
+    uint32_t *bonds;   // [n][2][2][wpp] active bonds, [direction][plane][word] in the layout of the spins
+    uint32_t *fliptab; // [n][N / 32]  flip bit of every possible root
+};
+
+constexpr size_t cluster_words_per_replica(uint64_t nvars) { return size_t(2 * nvars + nvars / 16 + nvars / 32); }
+
+// One cluster step of replicas [0, n) at timestep t: state / keys / thr_per_replica / stats point at the first replica of the
+// batch.  thr_per_replica == nullptr: every replica uses thr.  stats: [n][2] = {clusters, largest cluster}, zero on entry.
+hipError_t cluster_launch_step(hipStream_t stream, uint32_t *state, const LatGeom &g, uint64_t t, const uint2 *keys, uint32_t jneg_uniform,
+                               uint64_t thr, const uint64_t *thr_per_replica, const ClusterWork &work, uint32_t n, uint32_t *stats);
+
+} // namespace isingmc

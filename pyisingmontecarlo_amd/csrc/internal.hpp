@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/isingmc.h"
+#include "cluster_kernels.hpp"
 #include "general_kernels.hpp"
 #include "host_logic.hpp"
 #include "lattice_kernels.hpp"
@@ -86,6 +87,7 @@ struct Options {
     int sweep_iters = 0, debug_sweep_lds = 0;
     int resident_spread = 1, resident_lpq = 0, gen_stage = -1;
     int sample_slab_bytes = 64 << 20, pt_in_kernel = 1, real_target_wgs = 3072;
+    int cluster_workspace_bytes = 1 << 30; // labels, cluster sizes and bond planes of one batch of replicas
 
     static Options from_env()
     {
@@ -110,6 +112,7 @@ struct Options {
         o.sample_slab_bytes = std::max(1, env_int("ISINGMC_SAMPLE_SLAB_BYTES", 64 << 20));
         o.pt_in_kernel = env_int("ISINGMC_PT_IN_KERNEL", 1);
         o.real_target_wgs = std::max(256, env_int("ISINGMC_REAL_TARGET_WGS", 3072));
+        o.cluster_workspace_bytes = std::max(1, env_int("ISINGMC_CLUSTER_WORKSPACE_BYTES", 1 << 30));
         return o;
     }
 
@@ -125,7 +128,8 @@ struct Options {
             {"strip_nw", &strip_nw}, {"strip_max_wg", &strip_max_wg}, {"strip_test_fail_once", &strip_test_fail_once},
             {"streams", &streams}, {"pk_streams", &pk_streams}, {"sweep_iters", &sweep_iters}, {"debug_sweep_lds", &debug_sweep_lds},
             {"resident_spread", &resident_spread}, {"resident_lpq", &resident_lpq}, {"gen_stage", &gen_stage},
-            {"sample_slab_bytes", &sample_slab_bytes}, {"pt_in_kernel", &pt_in_kernel}, {"real_target_wgs", &real_target_wgs}};
+            {"sample_slab_bytes", &sample_slab_bytes}, {"pt_in_kernel", &pt_in_kernel}, {"real_target_wgs", &real_target_wgs},
+            {"cluster_workspace_bytes", &cluster_workspace_bytes}};
         for (const auto &e : table)
             if (n == e.first) { *e.second = int(value); return true; }
         return false;
@@ -259,6 +263,11 @@ struct isingmc_states {
     uint32_t *d_pt_perm = nullptr;
     unsigned long long *d_pt_counters = nullptr;
     size_t pt_per = 0, pt_world = 1;
+    // Swendsen-Wang cluster steps (cluster_kernels.hpp): timestep t is one when cluster_every > 0 and t % cluster_every == cluster_every - 1
+    size_t cluster_every = 0;
+    uint32_t *d_cl_stats = nullptr; // [cl_stats_cap][2]: clusters, largest cluster of the last cluster step
+    size_t cl_stats_cap = 0;
+    bool cl_have_stats = false;
 
     ~isingmc_states()
     {
@@ -277,6 +286,7 @@ struct isingmc_states {
         if (d_rj_betas) (void)cached_free(d_rj_betas);
         if (d_pk_slot_thr) (void)cached_free(d_pk_slot_thr);
         if (d_thr_mc) (void)cached_free(d_thr_mc);
+        if (d_cl_stats) (void)cached_free(d_cl_stats);
         for (int b = 0; b < 2; b++) {
             for (void *p : {(void *)d_samples[b], (void *)d_sample_counts[b], (void *)d_sample_e[b]})
                 if (p) (void)cached_free(p);

@@ -1148,6 +1148,11 @@ struct StepRun {
     std::vector<LatThr> h_thr{};
     std::vector<std::array<uint32_t, PK_TAB_WORDS>> h_pk_tabs{};
     std::vector<RjBeta> h_rj{};
+    // cluster steps: the workspace of one batch of replicas (allocated by the call's first cluster step), per-replica thresholds
+    ClusterWork cl{nullptr, nullptr, nullptr, nullptr};
+    size_t cl_batch = 0;
+    uint64_t *d_cl_thr = nullptr;
+    std::vector<uint64_t> h_cl_thr{};
 };
 
 // the host's tables of the chunk [k0, k0 + nk)
@@ -1422,6 +1427,111 @@ static int run_gen_csr(StepRun &c, size_t k0, size_t nk)
     return ISINGMC_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Swendsen-Wang cluster steps (cluster_kernels.hip)
+// ------------------------------------------------------------------------------------------------
+
+// why this container cannot take cluster steps ("" when it can)
+static std::string cluster_obstacle(const isingmc_states *s)
+{
+    const isingmc_graph *g = s->g;
+    if (g->kind != ISINGMC_KIND_LATTICE2D || s->packed)
+        return "cluster updates need a container on the checkerboard lattice path; this graph runs on a general-graph kernel family";
+    if (g->mc_mode == MC_FIELD || g->mc_mode == MC_FIELD_OPEN) return "cluster updates are not implemented for lattices with a field";
+    if (g->mc_mode == MC_OPEN) return "cluster updates are not implemented for open boundaries (periodic lattices only)";
+    if (g->mc_mode != MC_NONE) return "cluster updates are not implemented for anisotropic couplings (|Jx| != |Jy|)";
+    if (!g->uniform_sign) return "cluster updates are not implemented for +-J sign patterns (one coupling sign only)";
+    if (g->nvars >= 0xFFFFFFFFull) return "cluster updates label sites with 32 bits: W H must be below 2^32 - 1";
+    if (s->pt_attached) return "a tempering ladder is attached to this container (isingmc_pt_detach first)";
+    return "";
+}
+
+extern "C" int isingmc_states_set_cluster_every(isingmc_states *s, size_t k)
+{
+    if (!s) return fail(ISINGMC_ERR_INVALID, "NULL states");
+    if (k) {
+        const std::string why = cluster_obstacle(s);
+        if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
+    }
+    s->cluster_every = k;
+    return ISINGMC_OK;
+}
+
+extern "C" int isingmc_states_cluster_every(const isingmc_states *s, size_t *k_out)
+{
+    if (!s || !k_out) return fail(ISINGMC_ERR_INVALID, "NULL argument");
+    *k_out = s->cluster_every;
+    return ISINGMC_OK;
+}
+
+extern "C" int isingmc_cluster_stats(isingmc_states *s, uint64_t *n_clusters_out, uint64_t *largest_out)
+{
+    if (!s || !n_clusters_out || !largest_out) return fail(ISINGMC_ERR_INVALID, "NULL argument");
+    if (!s->cl_have_stats || s->cl_stats_cap < s->R) return fail(ISINGMC_ERR_INVALID, "no cluster step has run on these replicas yet");
+    TRY(use_device(s->g->device));
+    std::vector<uint32_t> h;
+    TRY(read_back(s, h, s->d_cl_stats, 2 * s->R));
+    for (size_t r = 0; r < s->R; r++) {
+        n_clusters_out[r] = h[2 * r];
+        largest_out[r] = h[2 * r + 1];
+    }
+    return ISINGMC_OK;
+}
+
+// T = floor((1 - exp(-2 beta |J|)) 2^32) in f64 (expm1 of glibc, as the tests' restatement); 2^32 = always, 0 = never
+static uint64_t cluster_threshold(double beta, double jabs)
+{
+    if (!(beta > 0.0)) return 0;
+    return uint64_t(std::floor(std::ldexp(-std::expm1(-2.0 * beta * jabs), 32)));
+}
+
+static bool is_cluster_step(const isingmc_states *s) { return s->cluster_every && s->t % s->cluster_every == s->cluster_every - 1; }
+
+// timestep s->t (= step k0 of the call) as a cluster step of every replica, batch by batch on the main stream
+static int run_cluster(StepRun &c, size_t k0)
+{
+    isingmc_states *s = c.s;
+    const isingmc_graph *g = s->g;
+    const size_t R = s->R;
+    if (s->n_lanes > 1) TRY(lanes_join(s)); // the Metropolis stretch before this step may have run on replica lanes
+    if (!c.cl.labels) {
+        const size_t words = cluster_words_per_replica(g->nvars);
+        c.cl_batch = std::min<size_t>({R, size_t(32768), std::max<size_t>(1, size_t(std::max(1, s->opt.cluster_workspace_bytes)) / (words * sizeof(uint32_t)))});
+        uint32_t *block = nullptr;
+        TRY(c.scratch.alloc(&block, c.cl_batch * words));
+        c.cl.labels = block;
+        c.cl.sizes = c.cl.labels + c.cl_batch * g->nvars;
+        c.cl.bonds = c.cl.sizes + c.cl_batch * g->nvars;
+        c.cl.fliptab = c.cl.bonds + c.cl_batch * (g->nvars / 16);
+    }
+    if (s->cl_stats_cap < R) {
+        HIP_TRY(stream_quiesce(s->stream)); // the old block is recycled
+        if (s->d_cl_stats) HIP_TRY(cached_free(s->d_cl_stats));
+        s->d_cl_stats = nullptr;
+        s->cl_stats_cap = 0;
+        TRY(dev_alloc(&s->d_cl_stats, 2 * s->cap));
+        s->cl_stats_cap = s->cap;
+    }
+    uint64_t thr = 0;
+    if (!s->has_betas) thr = cluster_threshold(c.betas[k0 * c.beta_stride], g->jabs);
+    else if (!c.d_cl_thr) { // per-replica betas do not change inside a call
+        c.h_cl_thr.resize(R);
+        for (size_t r = 0; r < R; r++) c.h_cl_thr[r] = cluster_threshold(s->betas[r], g->jabs);
+        TRY(c.scratch.alloc(&c.d_cl_thr, R));
+        HIP_TRY(hipMemcpyAsync(c.d_cl_thr, c.h_cl_thr.data(), R * sizeof(uint64_t), hipMemcpyHostToDevice, s->stream));
+    }
+    HIP_TRY(hipMemsetAsync(s->d_cl_stats, 0, 2 * R * sizeof(uint32_t), s->stream));
+    for (size_t r0 = 0; r0 < R; r0 += c.cl_batch) {
+        const size_t n = std::min(c.cl_batch, R - r0);
+        HIP_TRY(cluster_launch_step(s->stream, s->d_state + r0 * g->state_words, g->geom, s->t, s->d_keys + r0, g->jneg_uniform, thr,
+                                    c.d_cl_thr ? c.d_cl_thr + r0 : nullptr, c.cl, uint32_t(n), s->d_cl_stats + 2 * r0));
+    }
+    s->cl_have_stats = true;
+    s->t++;
+    if (c.d_counts) lat_measure_enqueue(s, c.d_counts, 2 * c.P.step_slots); // the energy after this timestep: counter slot 0 of step 0 of the chunk
+    return ISINGMC_OK;
+}
+
 // the per-step energies of the chunk [k0, k0 + nk) into energies_per_step[r * timesteps + k0 + k]
 static int read_step_energies(StepRun &c, size_t k0, size_t nk)
 {
@@ -1484,11 +1594,19 @@ static int run_steps_impl(isingmc_states *s, size_t timesteps, const double *bet
     } lane_join{s};
     if (P.lanes > 1 && P.path != StepPath::Packed) TRY(lanes_fork(s, P.lanes)); // (the packed runner forks behind its table launches)
     int rc = ISINGMC_OK;
-    for (size_t k0 = 0; k0 < timesteps && rc == ISINGMC_OK; k0 += P.chunk) {
-        const size_t nk = std::min(P.chunk, timesteps - k0);
+    for (size_t k0 = 0, nk = 0; k0 < timesteps && rc == ISINGMC_OK; k0 += nk) {
+        nk = std::min(P.chunk, timesteps - k0);
+        // cluster steps cut the call: a chunk is one cluster step, or a Metropolis stretch that ends before the next one
+        const bool cluster = is_cluster_step(s);
+        if (cluster) nk = 1;
+        else if (s->cluster_every) {
+            nk = std::min<size_t>(nk, s->cluster_every - 1 - s->t % s->cluster_every);
+            if (P.lanes > 1 && s->n_lanes <= 1) TRY(lanes_fork(s, P.lanes)); // (joined by the cluster step before this stretch)
+        }
         if (c.d_counts && P.path != StepPath::Packed) // (measure_enqueue clears the packed counters itself)
             HIP_TRY(hipMemsetAsync(c.d_counts, 0, nk * R * P.step_slots * 2 * sizeof(unsigned long long), s->stream));
-        switch (P.path) {
+        if (cluster) rc = run_cluster(c, k0);
+        else switch (P.path) {
         case StepPath::Packed: rc = run_packed(c, k0, nk); break;
         case StepPath::LatResident: rc = run_lat_resident(c, k0, nk); break;
         case StepPath::LatStrip: rc = run_lat_strip(c, k0, nk); break;

@@ -246,12 +246,17 @@ public:
     // it the Markov chain -- of a general graph normally follows the number of experiments of the call;
     // set_stable_path(True) fixes it from the graph alone: row k of run_monte_carlo(beta, T, R) is then the same for every R > k.
     void set_stable_path(bool v) { stable_path_ = v; graphs_.clear(); }
+    // extension: every k-th timestep of the run_* methods is a Swendsen-Wang cluster step (isingmc_states_set_cluster_every;
+    // 0 = off, the default).  Applied to every container the run_* methods create; a graph the cluster step does not serve raises
+    // ValueError there.  (Not wired to only_basic_moves: its default None would switch it on.)
+    void set_cluster_update_every(size_t k) { cluster_every_ = k; }
     py::dict engine_info(std::optional<size_t> num_experiments)
     {
         isingmc_graph_info_t info;
         check(isingmc_graph_info(graph()->g, &info));
         py::dict d;
         d["stable_path"] = bool(info.stable_path);
+        d["cluster_update_every"] = cluster_every_;
         if (num_experiments) { // the kernel family a call with that many experiments runs on
             int family = 0;
             check(isingmc_graph_family_for(graph()->g, *num_experiments, &family));
@@ -425,6 +430,7 @@ private:
         const auto run_block = [&](Block &blk) {
             isingmc_states *st = nullptr;
             blk.rc = isingmc_states_create_range(graphs_[blk.slot]->g, num_experiments, seeds.data(), blk.lo, blk.hi - blk.lo, ini, &st);
+            if (blk.rc == ISINGMC_OK && cluster_every_) blk.rc = isingmc_states_set_cluster_every(st, cluster_every_);
             if (blk.rc == ISINGMC_OK) blk.rc = body(st, blk.lo - lo);
             if (blk.rc != ISINGMC_OK) blk.msg = isingmc_last_error(); // per thread: read it where it was set
             isingmc_states_destroy(st);
@@ -466,6 +472,7 @@ private:
     bool use_allocator_ = true;
     std::vector<int> devices_;  // one block of experiments per entry (ISINGMC_DEVICES; an ordinal may repeat)
     bool force_general_ = false, stable_path_ = false;
+    size_t cluster_every_ = 0;
     std::vector<std::shared_ptr<GraphHandle>> graphs_;
 };
 
@@ -575,6 +582,9 @@ public:
         return s;
     }
     size_t get_num_graphs() const { return isingmc_states_count(st_->s); }
+    // extension: Swendsen-Wang cluster steps on the persistent replicas (see Lattice.set_cluster_update_every); the graph is known
+    // here, so one the cluster step does not serve raises ValueError at once
+    void set_cluster_update_every(size_t k) { check(isingmc_states_set_cluster_every(st_->s, k)); }
 
 private:
     // nspinupdates = single-spin attempts per timestep (classicising.rs:88-110 hands it to do_time_step; crate default:
@@ -641,6 +651,7 @@ PYBIND11_MODULE(_py_monte_carlo, m)
         .def("get_devices", &Lattice::get_devices)
         .def("set_force_general_path", &Lattice::set_force_general_path, "force"_a)
         .def("set_stable_path", &Lattice::set_stable_path, "stable"_a)
+        .def("set_cluster_update_every", &Lattice::set_cluster_update_every, "k"_a)
         .def("engine_info", &Lattice::engine_info, "num_experiments"_a = py::none())
         .def("run_monte_carlo", &Lattice::run_monte_carlo, "beta"_a, "timesteps"_a, "num_experiments"_a,
              "only_basic_moves"_a = py::none(), "edge_move_importance_sampling"_a = py::none(),
@@ -684,5 +695,6 @@ PYBIND11_MODULE(_py_monte_carlo, m)
              "only_basic_moves"_a = py::none(), "thermalization_time"_a = py::none(), "sampling_freq"_a = py::none())
         .def("get_energies", &ClassicIsing::get_energies)
         .def("get_states", &ClassicIsing::get_states)
-        .def("get_num_graphs", &ClassicIsing::get_num_graphs);
+        .def("get_num_graphs", &ClassicIsing::get_num_graphs)
+        .def("set_cluster_update_every", &ClassicIsing::set_cluster_update_every, "k"_a);
 }

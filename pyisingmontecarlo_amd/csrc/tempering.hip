@@ -43,6 +43,7 @@ static int pt_after_swap(isingmc_states *s)
 static std::string pt_attach_obstacle(const isingmc_states *s, size_t n_rungs, size_t slot_offset, size_t slots_per_rank, size_t world_size)
 {
     if (s->pt_attached) return "a ladder is already attached";
+    if (s->cluster_every) return "cluster updates are switched on for this container (isingmc_states_set_cluster_every): a tempering round has no cluster steps";
     const bool pk_ladder = s->packed && !s->rj;
     if (!s->packed && (s->g->kind != ISINGMC_KIND_LATTICE2D || s->g->mc_mode != MC_NONE))
         return "on-stream tempering is implemented for periodic, field-free lattices and for the replica-packed "
