@@ -69,6 +69,9 @@ _PROTOTYPES = {
     "isingmc_states_set_cluster_every": (C.c_int, [_vp, C.c_size_t]),
     "isingmc_states_cluster_every": (C.c_int, [_vp, C.POINTER(C.c_size_t)]),
     "isingmc_cluster_stats": (C.c_int, [_vp, _vp, _vp]),
+    "isingmc_states_set_icm_every": (C.c_int, [_vp, C.c_size_t]),
+    "isingmc_states_icm_every": (C.c_int, [_vp, C.POINTER(C.c_size_t)]),
+    "isingmc_icm_stats": (C.c_int, [_vp, _vp, _vp, _vp]),
     "isingmc_run_sampling": (C.c_int, [_vp, C.c_double, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp]),
     "isingmc_pt_attach": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint64]),
     "isingmc_pt_can_attach": (C.c_int, [_vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_int)]),
@@ -403,6 +406,24 @@ class States:
         n, largest = np.zeros(self.count, dtype=np.uint64), np.zeros(self.count, dtype=np.uint64)
         _check(lib().isingmc_cluster_stats(self._h, _p(n), _p(largest)))
         return n, largest
+
+    def set_icm_every(self, k):
+        """Every k-th timestep (t % k == k - 1) becomes an isoenergetic cluster move between the replicas (2p, 2p + 1)
+        (DESIGN.md S9); 0 switches it off."""
+        _check(lib().isingmc_states_set_icm_every(self._h, int(k)))
+
+    @property
+    def icm_every(self):
+        k = C.c_size_t()
+        _check(lib().isingmc_states_icm_every(self._h, C.byref(k)))
+        return int(k.value)
+
+    def icm_stats(self):
+        """(number of q = -1 clusters, size of the largest, number of q = -1 sites) of every pair's last isoenergetic cluster
+        move: three uint64[count // 2] arrays."""
+        out = [np.zeros(self.count // 2, dtype=np.uint64) for _ in range(3)]
+        _check(lib().isingmc_icm_stats(self._h, _p(out[0]), _p(out[1]), _p(out[2])))
+        return tuple(out)
 
     def do_time_steps(self, timesteps, beta=None, per_step_energies=False):
         """beta: float (constant), sequence of length timesteps, or None when per-replica betas are set."""

@@ -9,6 +9,7 @@
 // Every union links a root to a SMALLER site id with an integer atomicMin, so the final root of a component is its smallest
 // site id whatever the order of execution, and every loop below walks strictly decreasing labels: it ends after at most
 // W H steps without waiting for any other thread.
+// The isoenergetic cluster move of S9 reuses the tile, merge and max kernels between two kernels of its own (further down).
 #include "cluster_kernels.hpp"
 
 namespace isingmc {
@@ -210,6 +211,97 @@ __global__ __launch_bounds__(256) void cl_max_kernel(const uint32_t *__restrict_
     if ((threadIdx.x & 63u) == 0 && m) atomicMax(stats + 2 * r + 1, m);
 }
 
+// ---- isoenergetic cluster move between the replicas of a pair ------------------------------------------------
+// Four launches of their own around the unchanged labelling: icm_bonds_kernel -> cl_tile_kernel -> cl_merge_kernel ->
+// icm_flip_kernel -> cl_max_kernel, with n = number of pairs.  Pair p = replicas 2 p and 2 p + 1 of `state`; q = spins of the
+// first XOR spins of the second (a set bit: q_i = -1); a bond is active iff both ends have their q bit set.  The couplings
+// are never read.
+
+// grid: (ceil(4.5 wpp / 256), n_pairs), laid out as cl_bonds_kernel.  Thread gid < 4 wpp: bond word gid = (2 d + c) wpp + w;
+// tail thread j < wpp / 2 behind them: the flip bits of site ids 128 j .. 128 j + 127 and the q = -1 sites among those 128
+// sites (words 2 j and 2 j + 1 of both planes), summed over the wave into one atomicAdd.
+__global__ __launch_bounds__(256) void icm_bonds_kernel(const uint32_t *__restrict__ state, const LatGeom g, const uint64_t t,
+                                                        const uint2 *__restrict__ keys, uint32_t *__restrict__ bonds,
+                                                        uint32_t *__restrict__ fliptab, uint32_t *__restrict__ minus)
+{
+    const uint32_t p = blockIdx.y, gid = blockIdx.x * 256 + threadIdx.x;
+    const uint32_t *sa = state + size_t(2 * p) * 2 * g.wpp, *sb = sa + 2 * g.wpp;
+    if (gid < 4 * g.wpp) {
+        const uint32_t d = gid >= 2 * g.wpp, rem = gid - d * 2 * g.wpp, c = rem >= g.wpp, w = rem - c * g.wpp;
+        const uint32_t y = w / g.wpr, k = w - y * g.wpr;
+        const uint32_t own = size_t(c) * g.wpp, oth = size_t(1 - c) * g.wpp;
+        uint32_t nb;
+        if (d == 0) { // right neighbour: compact index i + 1 on the rows where this colour sits on odd columns, else i
+            nb = sa[oth + w] ^ sb[oth + w];
+            if ((y + c) & 1u) {
+                const uint32_t w1 = oth + y * g.wpr + (k + 1 == g.wpr ? 0 : k + 1);
+                nb = (nb >> 1) | ((sa[w1] ^ sb[w1]) << 31);
+            }
+        } else {
+            const uint32_t w1 = oth + (y + 1 == g.H ? 0 : y + 1) * g.wpr + k;
+            nb = sa[w1] ^ sb[w1];
+        }
+        bonds[size_t(p) * 4 * g.wpp + gid] = (sa[own + w] ^ sb[own + w]) & nb;
+    }
+    if ((gid | 63u) < 4 * g.wpp) return; // (the whole wave: no tail thread in it)
+    uint32_t cnt = 0;
+    const uint32_t j = gid - 4 * g.wpp; // wraps for the bond threads of a mixed wave: never below wpp / 2 then
+    if (gid >= 4 * g.wpp && j < g.wpp / 2) {
+        const uint4 v = philox4x32_10(make_uint4(uint32_t(t), j, DOM_ICM_FLIP, ctr2(t, 0, 0)), keys[2 * p]);
+        *reinterpret_cast<uint4 *>(fliptab + size_t(p) * 2 * g.wpp + 4 * size_t(j)) = v;
+        cnt = __popc(sa[2 * j] ^ sb[2 * j]) + __popc(sa[2 * j + 1] ^ sb[2 * j + 1]) + __popc(sa[g.wpp + 2 * j] ^ sb[g.wpp + 2 * j]) +
+              __popc(sa[g.wpp + 2 * j + 1] ^ sb[g.wpp + 2 * j + 1]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt += uint32_t(__shfl_xor(cnt, o));
+    if ((threadIdx.x & 63u) == 0 && cnt) atomicAdd(minus + p, cnt);
+}
+
+// grid: (ceil(wpp / 4), n_pairs); wave `seg` owns sites 64 seg .. 64 seg + 63 = word seg of both planes of both replicas.
+// A q = +1 site has no active bond: it is a singleton label that neither flips nor counts.
+__global__ __launch_bounds__(256) void icm_flip_kernel(uint32_t *__restrict__ state, const LatGeom g, const uint32_t *__restrict__ labels,
+                                                       const uint32_t *__restrict__ fliptab, uint32_t *__restrict__ sizes,
+                                                       uint32_t *__restrict__ stats)
+{
+    const uint32_t p = blockIdx.y, seg = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (seg >= g.wpp) return; // (the whole wave)
+    const size_t N = size_t(g.W) * g.H;
+    const uint32_t y = seg / g.wpr;
+    uint32_t *sa = state + size_t(2 * p) * 2 * g.wpp, *sb = sa + 2 * g.wpp;
+    // even columns belong to plane y & 1, odd columns to the other one; compact index = column >> 1
+    const size_t we = size_t(y & 1u) * g.wpp + seg, wo = size_t((y + 1) & 1u) * g.wpp + seg;
+    const uint32_t qe = sa[we] ^ sb[we], qo = sa[wo] ^ sb[wo];
+    const bool q = (((lane & 1u) ? qo : qe) >> (lane >> 1)) & 1u;
+    const uint32_t *lab = labels + size_t(p) * N;
+    const uint32_t site = seg * 64 + lane;
+    uint32_t root = site;
+    if (q) {
+        root = lab[site];
+        for (uint32_t r = lab[root]; r != root; r = lab[root]) root = r;
+    }
+    const uint32_t flip = (fliptab[size_t(p) * (N / 32) + (root >> 5)] >> (root & 31u)) & 1u;
+    const uint64_t flips = __ballot(q && flip != 0), roots = __ballot(q && root == site);
+    // sites per root, as in cl_flip_kernel, over the q = -1 lanes only
+    uint32_t *sz = sizes + size_t(p) * N;
+    uint64_t pending = __ballot(q);
+    for (int it = 0; it < 4 && pending; it++) {
+        const int leader = __ffsll((unsigned long long)pending) - 1;
+        const uint32_t lr = __shfl(root, leader);
+        const uint64_t same = __ballot(q && root == lr);
+        if (int(lane) == leader) atomicAdd(sz + lr, uint32_t(__popcll(same)));
+        pending &= ~same;
+    }
+    if ((pending >> lane) & 1ull) atomicAdd(sz + root, 1u);
+    if (!flips && !roots) return; // (the whole wave)
+    const uint32_t fe = even_bits(flips), fo = even_bits(flips >> 1);
+    if (lane == 0) {
+        sa[we] ^= fe;
+        if (roots) atomicAdd(stats + 2 * p, uint32_t(__popcll(roots)));
+    } else if (lane == 1) sa[wo] ^= fo;
+    else if (lane == 2) sb[we] ^= fe;
+    else if (lane == 3) sb[wo] ^= fo;
+}
+
 hipError_t cluster_launch_step(hipStream_t stream, uint32_t *state, const LatGeom &g, uint64_t t, const uint2 *keys, uint32_t jneg_uniform,
                                uint64_t thr, const uint64_t *thr_per_replica, const ClusterWork &work, uint32_t n, uint32_t *stats)
 {
@@ -221,6 +313,20 @@ hipError_t cluster_launch_step(hipStream_t stream, uint32_t *state, const LatGeo
     hipLaunchKernelGGL(cl_merge_kernel, dim3((border + 255) / 256, n), dim3(256), 0, stream, g, work.bonds, work.labels);
     hipLaunchKernelGGL(cl_flip_kernel, dim3((wpp + 3) / 4, n), dim3(256), 0, stream, state, g, work.labels, work.fliptab, work.sizes, stats);
     hipLaunchKernelGGL(cl_max_kernel, dim3((quads + 255) / 256, n), dim3(256), 0, stream, work.sizes, quads, stats);
+    return hipGetLastError();
+}
+
+hipError_t icm_launch_step(hipStream_t stream, uint32_t *state, const LatGeom &g, uint64_t t, const uint2 *keys, const ClusterWork &work,
+                           uint32_t n_pairs, uint32_t *stats, uint32_t *minus_sites)
+{
+    const uint32_t wpp = g.wpp, tile_rows = (g.H + CL_TILE_ROWS - 1) / CL_TILE_ROWS;
+    const uint32_t border = g.H * g.wpr + tile_rows * g.W, quads = g.W * g.H / 4;
+    hipLaunchKernelGGL(icm_bonds_kernel, dim3((4 * wpp + wpp / 2 + 255) / 256, n_pairs), dim3(256), 0, stream, state, g, t, keys, work.bonds,
+                       work.fliptab, minus_sites);
+    hipLaunchKernelGGL(cl_tile_kernel, dim3(g.wpr, tile_rows, n_pairs), dim3(256), 0, stream, g, work.bonds, work.labels, work.sizes);
+    hipLaunchKernelGGL(cl_merge_kernel, dim3((border + 255) / 256, n_pairs), dim3(256), 0, stream, g, work.bonds, work.labels);
+    hipLaunchKernelGGL(icm_flip_kernel, dim3((wpp + 3) / 4, n_pairs), dim3(256), 0, stream, state, g, work.labels, work.fliptab, work.sizes, stats);
+    hipLaunchKernelGGL(cl_max_kernel, dim3((quads + 255) / 256, n_pairs), dim3(256), 0, stream, work.sizes, quads, stats);
     return hipGetLastError();
 }
 

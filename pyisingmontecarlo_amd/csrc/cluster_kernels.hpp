@@ -1,6 +1,7 @@
 // Swendsen-Wang cluster step for periodic, field-free checkerboard lattices with one |J| and one coupling
-// sign: launch interface of cluster_kernels.hip (a translation unit of its own: nothing here is instantiated beside the
-// tuned sweep kernels).
+// sign, and the isoenergetic cluster move between replica pairs (S9, any sign pattern) on the same labelling: launch
+// interface of cluster_kernels.hip (a translation unit of its own: nothing here is instantiated beside the tuned sweep
+// kernels).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
@@ -12,6 +13,7 @@ namespace isingmc {
 
 constexpr uint32_t DOM_SW_BOND = 0x53574244u; // "SWBD"
 constexpr uint32_t DOM_SW_FLIP = 0x5357464Cu; // "SWFL"
+constexpr uint32_t DOM_ICM_FLIP = 0x4943464Cu; // "ICFL"
 
 constexpr uint32_t CL_TILE_W = 64;    // sites: the 32 spins of one word of plane 0 interleaved with the 32 of plane 1
 constexpr uint32_t CL_TILE_ROWS = 32; // rows of a tile (the last tile row of a lattice may be shorter)
@@ -30,5 +32,12 @@ constexpr size_t cluster_words_per_replica(uint64_t nvars) { return size_t(2 * n
 // batch.  thr_per_replica == nullptr: every replica uses thr.  stats: [n][2] = {clusters, largest cluster}, zero on entry.
 hipError_t cluster_launch_step(hipStream_t stream, uint32_t *state, const LatGeom &g, uint64_t t, const uint2 *keys, uint32_t jneg_uniform,
                                uint64_t thr, const uint64_t *thr_per_replica, const ClusterWork &work, uint32_t n, uint32_t *stats);
+
+// One isoenergetic cluster move of pairs [0, n_pairs) at timestep t: pair p = replicas 2 p and 2 p + 1 behind
+// `state` / `keys` (the key of replica 2 p draws the flip bits); the workspace holds n_pairs labelling problems.
+// stats: [n_pairs][2] = {q = -1 clusters, largest one} in the layout cl_max_kernel writes; minus_sites: [n_pairs] q = -1 sites;
+// both zero on entry.
+hipError_t icm_launch_step(hipStream_t stream, uint32_t *state, const LatGeom &g, uint64_t t, const uint2 *keys, const ClusterWork &work,
+                           uint32_t n_pairs, uint32_t *stats, uint32_t *minus_sites);
 
 } // namespace isingmc

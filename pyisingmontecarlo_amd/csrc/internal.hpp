@@ -268,6 +268,12 @@ struct isingmc_states {
     uint32_t *d_cl_stats = nullptr; // [cl_stats_cap][2]: clusters, largest cluster of the last cluster step
     size_t cl_stats_cap = 0;
     bool cl_have_stats = false;
+    // isoenergetic cluster moves between the replicas (2 p, 2 p + 1): timestep t is one when icm_every > 0 and
+    // t % icm_every == icm_every - 1; never on together with cluster_every
+    size_t icm_every = 0;
+    uint32_t *d_icm_stats = nullptr; // [icm_stats_cap][2] clusters, largest cluster, then [icm_stats_cap] q = -1 sites: the last ICM step of every pair
+    size_t icm_stats_cap = 0;
+    bool icm_have_stats = false;
 
     ~isingmc_states()
     {
@@ -287,6 +293,7 @@ struct isingmc_states {
         if (d_pk_slot_thr) (void)cached_free(d_pk_slot_thr);
         if (d_thr_mc) (void)cached_free(d_thr_mc);
         if (d_cl_stats) (void)cached_free(d_cl_stats);
+        if (d_icm_stats) (void)cached_free(d_icm_stats);
         for (int b = 0; b < 2; b++) {
             for (void *p : {(void *)d_samples[b], (void *)d_sample_counts[b], (void *)d_sample_e[b]})
                 if (p) (void)cached_free(p);

@@ -231,6 +231,14 @@ extern "C" int isingmc_states_set_betas(isingmc_states *s, const double *beta_pe
     return set_betas(s, beta_per_replica, false);
 }
 
+// the isoenergetic cluster move is valid between replicas at one temperature only
+static bool icm_unequal_pair_betas(const isingmc_states *s, const double *betas)
+{
+    for (size_t r = 0; r + 1 < s->R; r += 2)
+        if (betas[r] != betas[r + 1]) return true;
+    return false;
+}
+
 // all_equal: the caller passes one beta R times (run_sampling) -- then a shard that cuts a replica group is fine
 int set_betas(isingmc_states *s, const double *beta_per_replica, bool all_equal)
 {
@@ -242,6 +250,8 @@ int set_betas(isingmc_states *s, const double *beta_per_replica, bool all_equal)
     }
     for (size_t r = 0; r < s->R; r++)
         if (!std::isfinite(beta_per_replica[r])) return fail(ISINGMC_ERR_INVALID, "beta must be finite");
+    if (s->icm_every && icm_unequal_pair_betas(s, beta_per_replica))
+        return fail(ISINGMC_ERR_INVALID, "isoenergetic cluster moves are switched on: the two replicas of every pair (2 p, 2 p + 1) need equal betas");
     TRY(use_device(s->g->device));
     if (!all_equal) { // one beta R times is as good as a uniform beta: any cut of a group is fine then
         all_equal = true;
@@ -1452,6 +1462,7 @@ extern "C" int isingmc_states_set_cluster_every(isingmc_states *s, size_t k)
     if (k) {
         const std::string why = cluster_obstacle(s);
         if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
+        if (s->icm_every) return fail(ISINGMC_ERR_INVALID, "isoenergetic cluster moves are switched on for this container (isingmc_states_set_icm_every): one non-local move at a time");
     }
     s->cluster_every = k;
     return ISINGMC_OK;
@@ -1532,6 +1543,105 @@ static int run_cluster(StepRun &c, size_t k0)
     return ISINGMC_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Isoenergetic cluster moves between replica pairs (cluster_kernels.hip)
+// ------------------------------------------------------------------------------------------------
+
+// why this container cannot take isoenergetic cluster moves ("" when it can)
+static std::string icm_obstacle(const isingmc_states *s)
+{
+    const isingmc_graph *g = s->g;
+    if (g->kind != ISINGMC_KIND_LATTICE2D || s->packed)
+        return "isoenergetic cluster moves need a container on the checkerboard lattice path; this graph runs on a general-graph kernel family";
+    if (g->mc_mode == MC_FIELD || g->mc_mode == MC_FIELD_OPEN) return "isoenergetic cluster moves are not implemented for lattices with a field";
+    if (g->mc_mode == MC_OPEN) return "isoenergetic cluster moves are not implemented for open boundaries (periodic lattices only)";
+    if (g->mc_mode != MC_NONE) return "isoenergetic cluster moves are not implemented for anisotropic couplings (|Jx| != |Jy|)";
+    if (g->nvars >= 0xFFFFFFFFull) return "isoenergetic cluster moves label sites with 32 bits: W H must be below 2^32 - 1";
+    if (s->pt_attached) return "a tempering ladder is attached to this container (isingmc_pt_detach first)";
+    if (s->cluster_every) return "Swendsen-Wang cluster updates are switched on for this container (isingmc_states_set_cluster_every): one non-local move at a time";
+    // pairs are (2 p, 2 p + 1) of the GLOBAL experiment index: a shard must hold both replicas of every pair it touches
+    if (s->first % 2) return "this shard starts at an odd experiment index: its first replica's partner lives on another shard";
+    if ((s->first + s->R) % 2 && s->first + s->R < s->n_total) return "this shard ends inside a pair: its last replica's partner lives on another shard";
+    if (s->has_betas && icm_unequal_pair_betas(s, s->betas.data()))
+        return "per-replica betas differ inside a pair: the two replicas of every pair (2 p, 2 p + 1) need equal betas";
+    return "";
+}
+
+extern "C" int isingmc_states_set_icm_every(isingmc_states *s, size_t k)
+{
+    if (!s) return fail(ISINGMC_ERR_INVALID, "NULL states");
+    if (k) {
+        const std::string why = icm_obstacle(s);
+        if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
+    }
+    s->icm_every = k;
+    return ISINGMC_OK;
+}
+
+extern "C" int isingmc_states_icm_every(const isingmc_states *s, size_t *k_out)
+{
+    if (!s || !k_out) return fail(ISINGMC_ERR_INVALID, "NULL argument");
+    *k_out = s->icm_every;
+    return ISINGMC_OK;
+}
+
+extern "C" int isingmc_icm_stats(isingmc_states *s, uint64_t *n_clusters_out, uint64_t *largest_out, uint64_t *minus_sites_out)
+{
+    if (!s || !n_clusters_out || !largest_out || !minus_sites_out) return fail(ISINGMC_ERR_INVALID, "NULL argument");
+    const size_t pairs = s->R / 2;
+    if (!s->icm_have_stats || s->icm_stats_cap < pairs) return fail(ISINGMC_ERR_INVALID, "no isoenergetic cluster move has run on these replicas yet");
+    TRY(use_device(s->g->device));
+    std::vector<uint32_t> h;
+    TRY(read_back(s, h, s->d_icm_stats, 3 * s->icm_stats_cap));
+    for (size_t p = 0; p < pairs; p++) {
+        n_clusters_out[p] = h[2 * p];
+        largest_out[p] = h[2 * p + 1];
+        minus_sites_out[p] = h[2 * s->icm_stats_cap + p];
+    }
+    return ISINGMC_OK;
+}
+
+static bool is_icm_step(const isingmc_states *s) { return s->icm_every && s->t % s->icm_every == s->icm_every - 1; }
+
+// timestep s->t as an isoenergetic cluster move of every pair, batch by batch on the main stream; a last replica without a
+// partner stays as it is
+static int run_icm(StepRun &c)
+{
+    isingmc_states *s = c.s;
+    const isingmc_graph *g = s->g;
+    const size_t pairs = s->R / 2;
+    if (s->n_lanes > 1) TRY(lanes_join(s)); // the Metropolis stretch before this step may have run on replica lanes
+    if (pairs && !c.cl.labels) { // one labelling problem per PAIR
+        const size_t words = cluster_words_per_replica(g->nvars);
+        c.cl_batch = std::min<size_t>({pairs, size_t(32768), std::max<size_t>(1, size_t(std::max(1, s->opt.cluster_workspace_bytes)) / (words * sizeof(uint32_t)))});
+        uint32_t *block = nullptr;
+        TRY(c.scratch.alloc(&block, c.cl_batch * words));
+        c.cl.labels = block;
+        c.cl.sizes = c.cl.labels + c.cl_batch * g->nvars;
+        c.cl.bonds = c.cl.sizes + c.cl_batch * g->nvars;
+        c.cl.fliptab = c.cl.bonds + c.cl_batch * (g->nvars / 16);
+    }
+    if (!s->d_icm_stats || s->icm_stats_cap < pairs) {
+        HIP_TRY(stream_quiesce(s->stream)); // the old block is recycled
+        if (s->d_icm_stats) HIP_TRY(cached_free(s->d_icm_stats));
+        s->d_icm_stats = nullptr;
+        s->icm_stats_cap = 0;
+        const size_t cap = std::max<size_t>(1, s->cap / 2);
+        TRY(dev_alloc(&s->d_icm_stats, 3 * cap));
+        s->icm_stats_cap = cap;
+    }
+    HIP_TRY(hipMemsetAsync(s->d_icm_stats, 0, 3 * s->icm_stats_cap * sizeof(uint32_t), s->stream));
+    for (size_t p0 = 0; p0 < pairs; p0 += c.cl_batch) {
+        const size_t n = std::min(c.cl_batch, pairs - p0);
+        HIP_TRY(icm_launch_step(s->stream, s->d_state + 2 * p0 * g->state_words, g->geom, s->t, s->d_keys + 2 * p0, c.cl, uint32_t(n),
+                                s->d_icm_stats + 2 * p0, s->d_icm_stats + 2 * s->icm_stats_cap + p0));
+    }
+    s->icm_have_stats = true;
+    s->t++;
+    if (c.d_counts) lat_measure_enqueue(s, c.d_counts, 2 * c.P.step_slots); // the energy after this timestep: counter slot 0 of step 0 of the chunk
+    return ISINGMC_OK;
+}
+
 // the per-step energies of the chunk [k0, k0 + nk) into energies_per_step[r * timesteps + k0 + k]
 static int read_step_energies(StepRun &c, size_t k0, size_t nk)
 {
@@ -1597,15 +1707,17 @@ static int run_steps_impl(isingmc_states *s, size_t timesteps, const double *bet
     for (size_t k0 = 0, nk = 0; k0 < timesteps && rc == ISINGMC_OK; k0 += nk) {
         nk = std::min(P.chunk, timesteps - k0);
         // cluster steps cut the call: a chunk is one cluster step, or a Metropolis stretch that ends before the next one
-        const bool cluster = is_cluster_step(s);
-        if (cluster) nk = 1;
-        else if (s->cluster_every) {
-            nk = std::min<size_t>(nk, s->cluster_every - 1 - s->t % s->cluster_every);
+        // (Swendsen-Wang steps and isoenergetic cluster moves exclude each other: at most one period applies)
+        const bool cluster = is_cluster_step(s), icm = is_icm_step(s);
+        if (cluster || icm) nk = 1;
+        else if (const size_t every = s->cluster_every ? s->cluster_every : s->icm_every) {
+            nk = std::min<size_t>(nk, every - 1 - s->t % every);
             if (P.lanes > 1 && s->n_lanes <= 1) TRY(lanes_fork(s, P.lanes)); // (joined by the cluster step before this stretch)
         }
         if (c.d_counts && P.path != StepPath::Packed) // (measure_enqueue clears the packed counters itself)
             HIP_TRY(hipMemsetAsync(c.d_counts, 0, nk * R * P.step_slots * 2 * sizeof(unsigned long long), s->stream));
         if (cluster) rc = run_cluster(c, k0);
+        else if (icm) rc = run_icm(c);
         else switch (P.path) {
         case StepPath::Packed: rc = run_packed(c, k0, nk); break;
         case StepPath::LatResident: rc = run_lat_resident(c, k0, nk); break;

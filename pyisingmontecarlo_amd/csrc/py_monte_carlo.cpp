@@ -250,6 +250,10 @@ public:
     // 0 = off, the default).  Applied to every container the run_* methods create; a graph the cluster step does not serve raises
     // ValueError there.  (Not wired to only_basic_moves: its default None would switch it on.)
     void set_cluster_update_every(size_t k) { cluster_every_ = k; }
+    // extension: every k-th timestep of the run_* methods is an isoenergetic cluster move between the experiments (2 p, 2 p + 1)
+    // (isingmc_states_set_icm_every; 0 = off, the default): the non-local move for +-J glasses.  Applied to every container the
+    // run_* methods create; the device blocks then hold whole pairs.
+    void set_replica_cluster_update_every(size_t k) { icm_every_ = k; }
     py::dict engine_info(std::optional<size_t> num_experiments)
     {
         isingmc_graph_info_t info;
@@ -257,6 +261,7 @@ public:
         py::dict d;
         d["stable_path"] = bool(info.stable_path);
         d["cluster_update_every"] = cluster_every_;
+        d["replica_cluster_update_every"] = icm_every_;
         if (num_experiments) { // the kernel family a call with that many experiments runs on
             int family = 0;
             check(isingmc_graph_family_for(graph()->g, *num_experiments, &family));
@@ -419,6 +424,10 @@ private:
         const size_t n = hi - lo, D = devices_.size();
         size_t per = (n + D - 1) / std::max<size_t>(D, 1);
         if (per >= 32) per = (per + 31) / 32 * 32;
+        if (icm_every_) { // pairs are (2 p, 2 p + 1) of the global experiment index: no device cut may split one
+            if (lo % 2) throw py::value_error("replica_range must start at an even experiment with replica cluster updates on: experiments (2p, 2p + 1) form a pair");
+            per += per % 2;
+        }
         struct Block { size_t slot, lo, hi; int rc = ISINGMC_OK; std::string msg; };
         std::vector<Block> blocks;
         for (size_t d = 0; d < D; d++) {
@@ -431,6 +440,7 @@ private:
             isingmc_states *st = nullptr;
             blk.rc = isingmc_states_create_range(graphs_[blk.slot]->g, num_experiments, seeds.data(), blk.lo, blk.hi - blk.lo, ini, &st);
             if (blk.rc == ISINGMC_OK && cluster_every_) blk.rc = isingmc_states_set_cluster_every(st, cluster_every_);
+            if (blk.rc == ISINGMC_OK && icm_every_) blk.rc = isingmc_states_set_icm_every(st, icm_every_);
             if (blk.rc == ISINGMC_OK) blk.rc = body(st, blk.lo - lo);
             if (blk.rc != ISINGMC_OK) blk.msg = isingmc_last_error(); // per thread: read it where it was set
             isingmc_states_destroy(st);
@@ -472,7 +482,7 @@ private:
     bool use_allocator_ = true;
     std::vector<int> devices_;  // one block of experiments per entry (ISINGMC_DEVICES; an ordinal may repeat)
     bool force_general_ = false, stable_path_ = false;
-    size_t cluster_every_ = 0;
+    size_t cluster_every_ = 0, icm_every_ = 0;
     std::vector<std::shared_ptr<GraphHandle>> graphs_;
 };
 
@@ -585,6 +595,8 @@ public:
     // extension: Swendsen-Wang cluster steps on the persistent replicas (see Lattice.set_cluster_update_every); the graph is known
     // here, so one the cluster step does not serve raises ValueError at once
     void set_cluster_update_every(size_t k) { check(isingmc_states_set_cluster_every(st_->s, k)); }
+    // extension: isoenergetic cluster moves between the persistent replicas (2 p, 2 p + 1) (see Lattice.set_replica_cluster_update_every)
+    void set_replica_cluster_update_every(size_t k) { check(isingmc_states_set_icm_every(st_->s, k)); }
 
 private:
     // nspinupdates = single-spin attempts per timestep (classicising.rs:88-110 hands it to do_time_step; crate default:
@@ -652,6 +664,7 @@ PYBIND11_MODULE(_py_monte_carlo, m)
         .def("set_force_general_path", &Lattice::set_force_general_path, "force"_a)
         .def("set_stable_path", &Lattice::set_stable_path, "stable"_a)
         .def("set_cluster_update_every", &Lattice::set_cluster_update_every, "k"_a)
+        .def("set_replica_cluster_update_every", &Lattice::set_replica_cluster_update_every, "k"_a)
         .def("engine_info", &Lattice::engine_info, "num_experiments"_a = py::none())
         .def("run_monte_carlo", &Lattice::run_monte_carlo, "beta"_a, "timesteps"_a, "num_experiments"_a,
              "only_basic_moves"_a = py::none(), "edge_move_importance_sampling"_a = py::none(),
@@ -696,5 +709,6 @@ PYBIND11_MODULE(_py_monte_carlo, m)
         .def("get_energies", &ClassicIsing::get_energies)
         .def("get_states", &ClassicIsing::get_states)
         .def("get_num_graphs", &ClassicIsing::get_num_graphs)
-        .def("set_cluster_update_every", &ClassicIsing::set_cluster_update_every, "k"_a);
+        .def("set_cluster_update_every", &ClassicIsing::set_cluster_update_every, "k"_a)
+        .def("set_replica_cluster_update_every", &ClassicIsing::set_replica_cluster_update_every, "k"_a);
 }
