@@ -263,6 +263,27 @@ int isingmc_states_icm_every(const isingmc_states *states, size_t *k_out);
  * (overlap of the pair: 1 - 2 n / N), uint64[count / 2] each (synchronises); ISINGMC_ERR_INVALID before the first such move */
 int isingmc_icm_stats(isingmc_states *states, uint64_t *n_clusters_out, uint64_t *largest_out, uint64_t *minus_sites_out);
 
+/* The isoenergetic cluster move of S9 between TWO containers of one graph handle: pair p = replica slots_a[p] of
+ * `a` and replica slots_b[p] of `b`; the key of a's replica draws the flip bits, t = the containers' common timestep.  Both
+ * timestep counters advance by one (the move is a timestep in place of a sweep) and energies a tempering measurement had cached
+ * are dropped in both.  Enqueue only: a's stream waits for what b's stream holds so far, runs the move, and b's stream waits
+ * for it; nothing waits on the host (except when the workspace, which stays with `a` under its option
+ * "cluster_workspace_bytes", has to grow).
+ *   slots_a / slots_b: uint32[n_pairs] in host memory, every slot at most once per table; per-replica betas set with
+ *     isingmc_states_set_betas must be bitwise equal inside every pair (containers without per-replica betas: no requirement;
+ *     with a ladder attached the caller pairs equal rungs: the betas live on the device).
+ *   both NULL: both containers carry a tempering ladder of their own (isingmc_pt_attach with world size 1, slot offset 0, one
+ *     slot per rung) over bitwise equal betas, n_pairs = the number of rungs, and pair r = (a's slot at rung r, b's slot at rung
+ *     r): the kernels read the two permutations on the device.
+ * Refused with ISINGMC_ERR_INVALID and a message (both containers stay as they were): a == b, two graph handles, a graph that
+ * isingmc_states_set_icm_every would refuse (general-graph families, fields, open boundaries, anisotropic couplings, W H >=
+ * 2^32 - 1), unequal timesteps, Swendsen-Wang steps or isoenergetic cluster moves switched on inside either container, unequal
+ * pair betas, slots out of range or used twice, the NULL form without two matching ladders. */
+int isingmc_icm_between(isingmc_states *a, isingmc_states *b, const uint32_t *slots_a, const uint32_t *slots_b, size_t n_pairs);
+/* the last isingmc_icm_between call with `a` as its first container, per pair in the order of the call: as isingmc_icm_stats,
+ * uint64[n_pairs] each with n_pairs that of the call (synchronises) */
+int isingmc_icm_between_stats(isingmc_states *a, uint64_t *n_clusters_out, uint64_t *largest_out, uint64_t *minus_sites_out, size_t n_pairs);
+
 /* replaces the whole sampling loop of lattice.rs:271-287 / classicising.rs:144-173:
  *   thermalization x do_time_step(beta);  n_samples x { sampling_freq x do_time_step(beta);
  *   states[r][k][:] = state_ref();  energies[r][k] = get_energy() }

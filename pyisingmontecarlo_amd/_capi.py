@@ -72,6 +72,8 @@ _PROTOTYPES = {
     "isingmc_states_set_icm_every": (C.c_int, [_vp, C.c_size_t]),
     "isingmc_states_icm_every": (C.c_int, [_vp, C.POINTER(C.c_size_t)]),
     "isingmc_icm_stats": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "isingmc_icm_between": (C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t]),
+    "isingmc_icm_between_stats": (C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t]),
     "isingmc_run_sampling": (C.c_int, [_vp, C.c_double, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp]),
     "isingmc_pt_attach": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint64]),
     "isingmc_pt_can_attach": (C.c_int, [_vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_int)]),
@@ -423,6 +425,30 @@ class States:
         move: three uint64[count // 2] arrays."""
         out = [np.zeros(self.count // 2, dtype=np.uint64) for _ in range(3)]
         _check(lib().isingmc_icm_stats(self._h, _p(out[0]), _p(out[1]), _p(out[2])))
+        return tuple(out)
+
+    def icm_between(self, other, slots_a=None, slots_b=None):
+        """One isoenergetic cluster move between this container and `other` as timestep t of both: pair p =
+        (replica slots_a[p] of self, replica slots_b[p] of other).  Without tables both containers carry a tempering ladder over
+        the same betas and pair r = the two replicas at rung r (read on the device).  Enqueue only."""
+        if (slots_a is None) != (slots_b is None):
+            raise ValueError("give both slot tables or neither")
+        if slots_a is None:
+            sa, sb, n = None, None, self.count
+        else:
+            sa, sb = _arr(slots_a, np.uint32), _arr(slots_b, np.uint32)
+            if sa.ndim != 1 or sa.shape != sb.shape:
+                raise ValueError("the slot tables must be two one-dimensional arrays of one length")
+            n = sa.size
+        _check(lib().isingmc_icm_between(self._h, other._h, _p(sa), _p(sb), n))
+        self._icmb_pairs = n
+
+    def icm_between_stats(self):
+        """(number of q = -1 clusters, size of the largest, number of q = -1 sites) per pair of the last icm_between call made
+        on this container: three uint64[n_pairs] arrays."""
+        n = getattr(self, "_icmb_pairs", 0)
+        out = [np.zeros(n, dtype=np.uint64) for _ in range(3)]
+        _check(lib().isingmc_icm_between_stats(self._h, _p(out[0]), _p(out[1]), _p(out[2]), n))
         return tuple(out)
 
     def do_time_steps(self, timesteps, beta=None, per_step_energies=False):

@@ -9,7 +9,8 @@
 // Every union links a root to a SMALLER site id with an integer atomicMin, so the final root of a component is its smallest
 // site id whatever the order of execution, and every loop below walks strictly decreasing labels: it ends after at most
 // W H steps without waiting for any other thread.
-// The isoenergetic cluster move of S9 reuses the tile, merge and max kernels between two kernels of its own (further down).
+// The isoenergetic cluster move of S9 reuses the tile, merge and max kernels between two kernels of its own (further down); S10 is
+// the same move between two containers, paired through slot tables in device memory.
 #include "cluster_kernels.hpp"
 
 namespace isingmc {
@@ -220,12 +221,12 @@ __global__ __launch_bounds__(256) void cl_max_kernel(const uint32_t *__restrict_
 // grid: (ceil(4.5 wpp / 256), n_pairs), laid out as cl_bonds_kernel.  Thread gid < 4 wpp: bond word gid = (2 d + c) wpp + w;
 // tail thread j < wpp / 2 behind them: the flip bits of site ids 128 j .. 128 j + 127 and the q = -1 sites among those 128
 // sites (words 2 j and 2 j + 1 of both planes), summed over the wave into one atomicAdd.
-__global__ __launch_bounds__(256) void icm_bonds_kernel(const uint32_t *__restrict__ state, const LatGeom g, const uint64_t t,
-                                                        const uint2 *__restrict__ keys, uint32_t *__restrict__ bonds,
-                                                        uint32_t *__restrict__ fliptab, uint32_t *__restrict__ minus)
+// (the body of both bond kernels: sa / sb = the planes of the pair's two replicas, key = the key of the first)
+__device__ __forceinline__ void icm_bonds_body(const uint32_t *__restrict__ sa, const uint32_t *__restrict__ sb, const LatGeom &g,
+                                               const uint64_t t, const uint2 key, const uint32_t p, uint32_t *__restrict__ bonds,
+                                               uint32_t *__restrict__ fliptab, uint32_t *__restrict__ minus)
 {
-    const uint32_t p = blockIdx.y, gid = blockIdx.x * 256 + threadIdx.x;
-    const uint32_t *sa = state + size_t(2 * p) * 2 * g.wpp, *sb = sa + 2 * g.wpp;
+    const uint32_t gid = blockIdx.x * 256 + threadIdx.x;
     if (gid < 4 * g.wpp) {
         const uint32_t d = gid >= 2 * g.wpp, rem = gid - d * 2 * g.wpp, c = rem >= g.wpp, w = rem - c * g.wpp;
         const uint32_t y = w / g.wpr, k = w - y * g.wpr;
@@ -247,7 +248,7 @@ __global__ __launch_bounds__(256) void icm_bonds_kernel(const uint32_t *__restri
     uint32_t cnt = 0;
     const uint32_t j = gid - 4 * g.wpp; // wraps for the bond threads of a mixed wave: never below wpp / 2 then
     if (gid >= 4 * g.wpp && j < g.wpp / 2) {
-        const uint4 v = philox4x32_10(make_uint4(uint32_t(t), j, DOM_ICM_FLIP, ctr2(t, 0, 0)), keys[2 * p]);
+        const uint4 v = philox4x32_10(make_uint4(uint32_t(t), j, DOM_ICM_FLIP, ctr2(t, 0, 0)), key);
         *reinterpret_cast<uint4 *>(fliptab + size_t(p) * 2 * g.wpp + 4 * size_t(j)) = v;
         cnt = __popc(sa[2 * j] ^ sb[2 * j]) + __popc(sa[2 * j + 1] ^ sb[2 * j + 1]) + __popc(sa[g.wpp + 2 * j] ^ sb[g.wpp + 2 * j]) +
               __popc(sa[g.wpp + 2 * j + 1] ^ sb[g.wpp + 2 * j + 1]);
@@ -257,17 +258,38 @@ __global__ __launch_bounds__(256) void icm_bonds_kernel(const uint32_t *__restri
     if ((threadIdx.x & 63u) == 0 && cnt) atomicAdd(minus + p, cnt);
 }
 
+__global__ __launch_bounds__(256) void icm_bonds_kernel(const uint32_t *__restrict__ state, const LatGeom g, const uint64_t t,
+                                                        const uint2 *__restrict__ keys, uint32_t *__restrict__ bonds,
+                                                        uint32_t *__restrict__ fliptab, uint32_t *__restrict__ minus)
+{
+    const uint32_t p = blockIdx.y;
+    const uint32_t *sa = state + size_t(2 * p) * 2 * g.wpp;
+    icm_bonds_body(sa, sa + 2 * g.wpp, g, t, keys[2 * p], p, bonds, fliptab, minus);
+}
+
+// The same between two containers: pair p = replica slots_a[p] behind state_a and replica slots_b[p] behind
+// state_b; keys_a[slots_a[p]] draws the flip bits.  The two table reads are wave-uniform (blockIdx.y): scalar loads.
+__global__ __launch_bounds__(256) void icm_bonds_between_kernel(const uint32_t *__restrict__ state_a, const uint32_t *__restrict__ state_b,
+                                                                const uint32_t *__restrict__ slots_a, const uint32_t *__restrict__ slots_b,
+                                                                const LatGeom g, const uint64_t t, const uint2 *__restrict__ keys_a,
+                                                                uint32_t *__restrict__ bonds, uint32_t *__restrict__ fliptab,
+                                                                uint32_t *__restrict__ minus)
+{
+    const uint32_t p = blockIdx.y, ra = slots_a[p], rb = slots_b[p];
+    icm_bonds_body(state_a + size_t(ra) * 2 * g.wpp, state_b + size_t(rb) * 2 * g.wpp, g, t, keys_a[ra], p, bonds, fliptab, minus);
+}
+
 // grid: (ceil(wpp / 4), n_pairs); wave `seg` owns sites 64 seg .. 64 seg + 63 = word seg of both planes of both replicas.
 // A q = +1 site has no active bond: it is a singleton label that neither flips nor counts.
-__global__ __launch_bounds__(256) void icm_flip_kernel(uint32_t *__restrict__ state, const LatGeom g, const uint32_t *__restrict__ labels,
-                                                       const uint32_t *__restrict__ fliptab, uint32_t *__restrict__ sizes,
-                                                       uint32_t *__restrict__ stats)
+// (the body of both flip kernels)
+__device__ __forceinline__ void icm_flip_body(uint32_t *__restrict__ sa, uint32_t *__restrict__ sb, const LatGeom &g, const uint32_t p,
+                                              const uint32_t *__restrict__ labels, const uint32_t *__restrict__ fliptab,
+                                              uint32_t *__restrict__ sizes, uint32_t *__restrict__ stats)
 {
-    const uint32_t p = blockIdx.y, seg = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    const uint32_t seg = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
     if (seg >= g.wpp) return; // (the whole wave)
     const size_t N = size_t(g.W) * g.H;
     const uint32_t y = seg / g.wpr;
-    uint32_t *sa = state + size_t(2 * p) * 2 * g.wpp, *sb = sa + 2 * g.wpp;
     // even columns belong to plane y & 1, odd columns to the other one; compact index = column >> 1
     const size_t we = size_t(y & 1u) * g.wpp + seg, wo = size_t((y + 1) & 1u) * g.wpp + seg;
     const uint32_t qe = sa[we] ^ sb[we], qo = sa[wo] ^ sb[wo];
@@ -302,6 +324,25 @@ __global__ __launch_bounds__(256) void icm_flip_kernel(uint32_t *__restrict__ st
     else if (lane == 3) sb[wo] ^= fo;
 }
 
+__global__ __launch_bounds__(256) void icm_flip_kernel(uint32_t *__restrict__ state, const LatGeom g, const uint32_t *__restrict__ labels,
+                                                       const uint32_t *__restrict__ fliptab, uint32_t *__restrict__ sizes,
+                                                       uint32_t *__restrict__ stats)
+{
+    const uint32_t p = blockIdx.y;
+    uint32_t *sa = state + size_t(2 * p) * 2 * g.wpp;
+    icm_flip_body(sa, sa + 2 * g.wpp, g, p, labels, fliptab, sizes, stats);
+}
+
+__global__ __launch_bounds__(256) void icm_flip_between_kernel(uint32_t *__restrict__ state_a, uint32_t *__restrict__ state_b,
+                                                               const uint32_t *__restrict__ slots_a, const uint32_t *__restrict__ slots_b,
+                                                               const LatGeom g, const uint32_t *__restrict__ labels,
+                                                               const uint32_t *__restrict__ fliptab, uint32_t *__restrict__ sizes,
+                                                               uint32_t *__restrict__ stats)
+{
+    const uint32_t p = blockIdx.y;
+    icm_flip_body(state_a + size_t(slots_a[p]) * 2 * g.wpp, state_b + size_t(slots_b[p]) * 2 * g.wpp, g, p, labels, fliptab, sizes, stats);
+}
+
 hipError_t cluster_launch_step(hipStream_t stream, uint32_t *state, const LatGeom &g, uint64_t t, const uint2 *keys, uint32_t jneg_uniform,
                                uint64_t thr, const uint64_t *thr_per_replica, const ClusterWork &work, uint32_t n, uint32_t *stats)
 {
@@ -326,6 +367,22 @@ hipError_t icm_launch_step(hipStream_t stream, uint32_t *state, const LatGeom &g
     hipLaunchKernelGGL(cl_tile_kernel, dim3(g.wpr, tile_rows, n_pairs), dim3(256), 0, stream, g, work.bonds, work.labels, work.sizes);
     hipLaunchKernelGGL(cl_merge_kernel, dim3((border + 255) / 256, n_pairs), dim3(256), 0, stream, g, work.bonds, work.labels);
     hipLaunchKernelGGL(icm_flip_kernel, dim3((wpp + 3) / 4, n_pairs), dim3(256), 0, stream, state, g, work.labels, work.fliptab, work.sizes, stats);
+    hipLaunchKernelGGL(cl_max_kernel, dim3((quads + 255) / 256, n_pairs), dim3(256), 0, stream, work.sizes, quads, stats);
+    return hipGetLastError();
+}
+
+hipError_t icm_between_launch_step(hipStream_t stream, uint32_t *state_a, uint32_t *state_b, const uint32_t *slots_a, const uint32_t *slots_b,
+                                   const LatGeom &g, uint64_t t, const uint2 *keys_a, const ClusterWork &work, uint32_t n_pairs, uint32_t *stats,
+                                   uint32_t *minus_sites)
+{
+    const uint32_t wpp = g.wpp, tile_rows = (g.H + CL_TILE_ROWS - 1) / CL_TILE_ROWS;
+    const uint32_t border = g.H * g.wpr + tile_rows * g.W, quads = g.W * g.H / 4;
+    hipLaunchKernelGGL(icm_bonds_between_kernel, dim3((4 * wpp + wpp / 2 + 255) / 256, n_pairs), dim3(256), 0, stream, state_a, state_b, slots_a,
+                       slots_b, g, t, keys_a, work.bonds, work.fliptab, minus_sites);
+    hipLaunchKernelGGL(cl_tile_kernel, dim3(g.wpr, tile_rows, n_pairs), dim3(256), 0, stream, g, work.bonds, work.labels, work.sizes);
+    hipLaunchKernelGGL(cl_merge_kernel, dim3((border + 255) / 256, n_pairs), dim3(256), 0, stream, g, work.bonds, work.labels);
+    hipLaunchKernelGGL(icm_flip_between_kernel, dim3((wpp + 3) / 4, n_pairs), dim3(256), 0, stream, state_a, state_b, slots_a, slots_b, g,
+                       work.labels, work.fliptab, work.sizes, stats);
     hipLaunchKernelGGL(cl_max_kernel, dim3((quads + 255) / 256, n_pairs), dim3(256), 0, stream, work.sizes, quads, stats);
     return hipGetLastError();
 }

@@ -40,4 +40,11 @@ hipError_t cluster_launch_step(hipStream_t stream, uint32_t *state, const LatGeo
 hipError_t icm_launch_step(hipStream_t stream, uint32_t *state, const LatGeom &g, uint64_t t, const uint2 *keys, const ClusterWork &work,
                            uint32_t n_pairs, uint32_t *stats, uint32_t *minus_sites);
 
+// The same move between two containers: pair p = replica slots_a[p] behind state_a and replica slots_b[p] behind
+// state_b, both tables in DEVICE memory ([n_pairs], every slot at most once); keys_a: the keys of state_a's replicas from slot 0
+// on (the key of slots_a[p] draws the flip bits).  stats / minus_sites as above.
+hipError_t icm_between_launch_step(hipStream_t stream, uint32_t *state_a, uint32_t *state_b, const uint32_t *slots_a, const uint32_t *slots_b,
+                                   const LatGeom &g, uint64_t t, const uint2 *keys_a, const ClusterWork &work, uint32_t n_pairs, uint32_t *stats,
+                                   uint32_t *minus_sites);
+
 } // namespace isingmc

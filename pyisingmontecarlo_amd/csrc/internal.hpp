@@ -263,6 +263,7 @@ struct isingmc_states {
     uint32_t *d_pt_perm = nullptr;
     unsigned long long *d_pt_counters = nullptr;
     size_t pt_per = 0, pt_world = 1;
+    std::vector<double> ladder_betas; // host copy of d_pt_ladder (two ladders are compared without a device read)
     // Swendsen-Wang cluster steps (cluster_kernels.hpp): timestep t is one when cluster_every > 0 and t % cluster_every == cluster_every - 1
     size_t cluster_every = 0;
     uint32_t *d_cl_stats = nullptr; // [cl_stats_cap][2]: clusters, largest cluster of the last cluster step
@@ -274,6 +275,15 @@ struct isingmc_states {
     uint32_t *d_icm_stats = nullptr; // [icm_stats_cap][2] clusters, largest cluster, then [icm_stats_cap] q = -1 sites: the last ICM step of every pair
     size_t icm_stats_cap = 0;
     bool icm_have_stats = false;
+    // isoenergetic cluster moves between this container and another one (isingmc_icm_between): everything below
+    // belongs to the FIRST container of the call and stays with it, so that a call only enqueues
+    uint32_t *d_icmb_work = nullptr;  // labelling workspace of icmb_batch pairs (cluster_words_per_replica each)
+    size_t icmb_batch = 0;
+    uint32_t *d_icmb_slots = nullptr; // [2][icmb_cap] slot tables of the host-table form
+    uint32_t *d_icmb_stats = nullptr; // [icmb_cap][2] clusters, largest cluster, then [icmb_cap] q = -1 sites: the last call
+    size_t icmb_cap = 0, icmb_pairs = 0;
+    bool icmb_have_stats = false;
+    hipEvent_t icmb_ev[2] = {nullptr, nullptr}; // the other container's stream has arrived / this container's launches are enqueued
 
     ~isingmc_states()
     {
@@ -294,6 +304,9 @@ struct isingmc_states {
         if (d_thr_mc) (void)cached_free(d_thr_mc);
         if (d_cl_stats) (void)cached_free(d_cl_stats);
         if (d_icm_stats) (void)cached_free(d_icm_stats);
+        for (void *p : {(void *)d_icmb_work, (void *)d_icmb_slots, (void *)d_icmb_stats})
+            if (p) (void)cached_free(p);
+        for (auto ev : icmb_ev) pooled_event_destroy(ev, true);
         for (int b = 0; b < 2; b++) {
             for (void *p : {(void *)d_samples[b], (void *)d_sample_counts[b], (void *)d_sample_e[b]})
                 if (p) (void)cached_free(p);

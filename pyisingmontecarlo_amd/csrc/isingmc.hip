@@ -1642,6 +1642,148 @@ static int run_icm(StepRun &c)
     return ISINGMC_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Isoenergetic cluster moves between two containers (cluster_kernels.hip): the move of S9 with pair p =
+// (slot slots_a[p] of a, slot slots_b[p] of b) -- what two tempering ladders over the same betas need, whose rung permutations
+// live on the device
+// ------------------------------------------------------------------------------------------------
+
+// why these two containers cannot take a move between them ("" when they can): icm_obstacle without its ladder and shard clauses
+static std::string icm_between_obstacle(const isingmc_states *a, const isingmc_states *b)
+{
+    if (a == b) return "an isoenergetic cluster move between two containers needs two different containers";
+    if (a->g != b->g) return "the two containers belong to different graph handles: both must be replicas of one isingmc_graph";
+    const isingmc_graph *g = a->g; // (one graph handle: one device)
+    if (g->kind != ISINGMC_KIND_LATTICE2D || a->packed || b->packed)
+        return "isoenergetic cluster moves need containers on the checkerboard lattice path; this graph runs on a general-graph kernel family";
+    if (g->mc_mode == MC_FIELD || g->mc_mode == MC_FIELD_OPEN) return "isoenergetic cluster moves are not implemented for lattices with a field";
+    if (g->mc_mode == MC_OPEN) return "isoenergetic cluster moves are not implemented for open boundaries (periodic lattices only)";
+    if (g->mc_mode != MC_NONE) return "isoenergetic cluster moves are not implemented for anisotropic couplings (|Jx| != |Jy|)";
+    if (g->nvars >= 0xFFFFFFFFull) return "isoenergetic cluster moves label sites with 32 bits: W H must be below 2^32 - 1";
+    for (const isingmc_states *s : {a, b}) {
+        if (s->cluster_every) return "Swendsen-Wang cluster updates are switched on for one of the containers (isingmc_states_set_cluster_every): one non-local move at a time";
+        if (s->icm_every) return "isoenergetic cluster moves inside one of the containers are switched on (isingmc_states_set_icm_every): one non-local move at a time";
+    }
+    if (a->t != b->t) return "the two containers stand at unequal timesteps: the move is timestep t of both";
+    return "";
+}
+
+extern "C" int isingmc_icm_between(isingmc_states *a, isingmc_states *b, const uint32_t *slots_a, const uint32_t *slots_b, size_t n_pairs)
+{
+    if (!a || !b) return fail(ISINGMC_ERR_INVALID, "NULL states");
+    {
+        const std::string why = icm_between_obstacle(a, b);
+        if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
+    }
+    if ((slots_a == nullptr) != (slots_b == nullptr)) return fail(ISINGMC_ERR_INVALID, "give both slot tables or neither");
+    const isingmc_graph *g = a->g;
+    const bool ladders = slots_a == nullptr;
+    if (ladders) { // pair r = (a's rung r, b's rung r): the permutations are read on the device
+        if (!a->pt_attached || !b->pt_attached) return fail(ISINGMC_ERR_INVALID, "without slot tables both containers need an attached tempering ladder (isingmc_pt_attach)");
+        for (const isingmc_states *s : {a, b})
+            if (s->pt_world != 1 || s->pt.slot_offset != 0 || s->pt.n_rungs != s->R)
+                return fail(ISINGMC_ERR_INVALID, "without slot tables each ladder must live on its container alone (world size 1, one slot per rung): sharded ladders are not served");
+        if (a->pt.n_rungs != b->pt.n_rungs) return fail(ISINGMC_ERR_INVALID, "the two ladders differ in their number of rungs");
+        if (a->ladder_betas.size() != b->ladder_betas.size() ||
+            std::memcmp(a->ladder_betas.data(), b->ladder_betas.data(), a->ladder_betas.size() * sizeof(double)) != 0)
+            return fail(ISINGMC_ERR_INVALID, "the two ladders differ in their betas: the replicas of a pair need equal betas");
+        if (n_pairs != a->R) return fail(ISINGMC_ERR_INVALID, "without slot tables n_pairs must be the number of rungs");
+    } else {
+        if (n_pairs > a->R || n_pairs > b->R) return fail(ISINGMC_ERR_INVALID, "more pairs than replicas");
+        std::vector<uint8_t> seen_a(a->R, 0), seen_b(b->R, 0);
+        for (size_t p = 0; p < n_pairs; p++) {
+            if (slots_a[p] >= a->R || slots_b[p] >= b->R) return fail(ISINGMC_ERR_INVALID, "slot out of range");
+            if (seen_a[slots_a[p]]++ || seen_b[slots_b[p]]++) return fail(ISINGMC_ERR_INVALID, "a duplicate slot: every replica belongs to at most one pair");
+        }
+        // per-replica betas set by the host are known here; a ladder relabels them on the device (the caller pairs equal rungs)
+        if (a->has_betas != b->has_betas && !a->pt_attached && !b->pt_attached)
+            return fail(ISINGMC_ERR_INVALID, "per-replica betas are set on one container only: the replicas of a pair need equal betas");
+        if (a->has_betas && b->has_betas && !a->pt_attached && !b->pt_attached)
+            for (size_t p = 0; p < n_pairs; p++)
+                if (std::memcmp(&a->betas[slots_a[p]], &b->betas[slots_b[p]], sizeof(double)) != 0)
+                    return fail(ISINGMC_ERR_INVALID, "per-replica betas differ inside a pair: the two replicas of every pair need equal betas");
+    }
+    TRY(use_device(g->device));
+    if (n_pairs == 0) { // time passes all the same
+        a->t++;
+        b->t++;
+        return ISINGMC_OK;
+    }
+    for (isingmc_states *s : {a, b})
+        if (s->n_lanes > 1) TRY(lanes_join(s));
+    // workspace, tables, statistics and events stay with `a`: nothing below waits for the device unless one of them grows
+    const size_t words = cluster_words_per_replica(g->nvars);
+    const size_t batch = std::min<size_t>({n_pairs, size_t(32768), std::max<size_t>(1, size_t(std::max(1, a->opt.cluster_workspace_bytes)) / (words * sizeof(uint32_t)))});
+    if (!a->d_icmb_work || a->icmb_batch != batch) {
+        HIP_TRY(stream_quiesce(a->stream)); // the old block is recycled
+        if (a->d_icmb_work) HIP_TRY(cached_free(a->d_icmb_work));
+        a->d_icmb_work = nullptr;
+        a->icmb_batch = 0;
+        TRY(dev_alloc(&a->d_icmb_work, batch * words));
+        a->icmb_batch = batch;
+    }
+    if (a->icmb_cap < n_pairs) {
+        HIP_TRY(stream_quiesce(a->stream));
+        for (uint32_t **p : {&a->d_icmb_slots, &a->d_icmb_stats}) {
+            if (*p) HIP_TRY(cached_free(*p));
+            *p = nullptr;
+        }
+        a->icmb_cap = 0;
+        a->icmb_have_stats = false;
+        const size_t cap = std::max(n_pairs, a->cap);
+        TRY(dev_alloc(&a->d_icmb_slots, 2 * cap));
+        TRY(dev_alloc(&a->d_icmb_stats, 3 * cap));
+        a->icmb_cap = cap;
+    }
+    for (hipEvent_t &ev : a->icmb_ev)
+        if (!ev) HIP_TRY(pooled_event_create(&ev, true));
+    ClusterWork cl;
+    cl.labels = a->d_icmb_work;
+    cl.sizes = cl.labels + batch * g->nvars;
+    cl.bonds = cl.sizes + batch * g->nvars;
+    cl.fliptab = cl.bonds + batch * (g->nvars / 16);
+    const uint32_t *d_sa = a->d_pt_perm, *d_sb = b->d_pt_perm;
+    if (!ladders) {
+        HIP_TRY(hipMemcpyAsync(a->d_icmb_slots, slots_a, n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, a->stream));
+        HIP_TRY(hipMemcpyAsync(a->d_icmb_slots + a->icmb_cap, slots_b, n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, a->stream));
+        d_sa = a->d_icmb_slots;
+        d_sb = a->d_icmb_slots + a->icmb_cap;
+    }
+    HIP_TRY(hipEventRecord(a->icmb_ev[0], b->stream)); // b's sweeps and exchange rounds so far ...
+    HIP_TRY(hipStreamWaitEvent(a->stream, a->icmb_ev[0], 0)); // ... before a's stream touches b's planes and permutation
+    HIP_TRY(hipMemsetAsync(a->d_icmb_stats, 0, 3 * a->icmb_cap * sizeof(uint32_t), a->stream));
+    for (size_t p0 = 0; p0 < n_pairs; p0 += batch) {
+        const size_t n = std::min(batch, n_pairs - p0);
+        HIP_TRY(icm_between_launch_step(a->stream, a->d_state, b->d_state, d_sa + p0, d_sb + p0, g->geom, a->t, a->d_keys, cl, uint32_t(n),
+                                        a->d_icmb_stats + 2 * p0, a->d_icmb_stats + 2 * a->icmb_cap + p0));
+    }
+    HIP_TRY(hipEventRecord(a->icmb_ev[1], a->stream));
+    HIP_TRY(hipStreamWaitEvent(b->stream, a->icmb_ev[1], 0)); // b goes on with the new configurations
+    a->icmb_pairs = n_pairs;
+    a->icmb_have_stats = true;
+    for (isingmc_states *s : {a, b}) {
+        s->t++;
+        s->meas_fresh = false; // energies a strip launch left behind belong to the configurations before the move
+    }
+    return ISINGMC_OK;
+}
+
+extern "C" int isingmc_icm_between_stats(isingmc_states *a, uint64_t *n_clusters_out, uint64_t *largest_out, uint64_t *minus_sites_out, size_t n_pairs)
+{
+    if (!a || !n_clusters_out || !largest_out || !minus_sites_out) return fail(ISINGMC_ERR_INVALID, "NULL argument");
+    if (!a->icmb_have_stats) return fail(ISINGMC_ERR_INVALID, "no isoenergetic cluster move between containers has been called on this container yet");
+    if (n_pairs != a->icmb_pairs) return fail(ISINGMC_ERR_INVALID, "n_pairs differs from the number of pairs of the last move");
+    TRY(use_device(a->g->device));
+    std::vector<uint32_t> h;
+    TRY(read_back(a, h, a->d_icmb_stats, 3 * a->icmb_cap));
+    for (size_t p = 0; p < n_pairs; p++) {
+        n_clusters_out[p] = h[2 * p];
+        largest_out[p] = h[2 * p + 1];
+        minus_sites_out[p] = h[2 * a->icmb_cap + p];
+    }
+    return ISINGMC_OK;
+}
+
 // the per-step energies of the chunk [k0, k0 + nk) into energies_per_step[r * timesteps + k0 + k]
 static int read_step_energies(StepRun &c, size_t k0, size_t nk)
 {

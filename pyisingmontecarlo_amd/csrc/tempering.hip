@@ -85,6 +85,7 @@ extern "C" int isingmc_pt_detach(isingmc_states *s)
     s->pt_attached = false;
     s->has_betas = false;
     s->betas.clear();
+    s->ladder_betas.clear();
     s->meas_fresh = false;
     return ISINGMC_OK;
 }
@@ -152,6 +153,7 @@ extern "C" int isingmc_pt_attach(isingmc_states *s, const double *ladder_betas, 
                   uint32_t(slot_offset), uint32_t(s->R), uint32_t(seed), uint32_t(seed >> 32)};
     s->pt_per = slots_per_rank;
     s->pt_world = world_size;
+    s->ladder_betas.assign(ladder_betas, ladder_betas + n_rungs);
     s->betas.assign(s->R, 0.0);
     s->has_betas = true;
     s->pt_attached = true;

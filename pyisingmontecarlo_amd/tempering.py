@@ -50,12 +50,24 @@ def _split(edges):
     return ea, eb, ej
 
 
+COPY_SEED_XOR = 0x9E3779B97F4A7C15  # copy 1 of a copies=2 ladder is the ladder of seed ^ this
+
+
 class ClassicalTempering:
-    def __init__(self, edges, seed=None, *, group=None, device=None, engine_factory=None, devices=None, group_backend=0):
+    def __init__(self, edges, seed=None, *, group=None, device=None, engine_factory=None, devices=None, group_backend=0, copies=1):
         """devices: HIP ordinals of an IN-PROCESS ladder -- shard k of the slots lives on devices[k] and the exchange step runs
         through the library's RCCL group (group_backend 0: RCCL when the devices are distinct, else device copies; 1: RCCL;
-        2: copies).  Mutually exclusive with a torch.distributed `group`."""
+        2: copies).  Mutually exclusive with a torch.distributed `group`.
+
+        copies=2: two ladders over the same betas on one device, for isoenergetic cluster moves between the two
+        configurations at every rung (set_replica_cluster_update_every).  Copy 0 is the ladder copies=1 would build; copy 1 is
+        the ladder of the seed `seed ^ COPY_SEED_XOR`.  Single process, single device only."""
         self._ea, self._eb, self._ej = _split(edges)
+        if copies not in (1, 2):
+            raise ValueError("copies must be 1 or 2")
+        self._ncopies = int(copies)
+        self._icm_every = 0
+        self._pair = None
         self._devices = None if devices is None else [int(d) for d in devices]
         self._group_backend = int(group_backend)
         self._shards, self._pgroup = None, None
@@ -69,6 +81,25 @@ class ClassicalTempering:
                 raise ValueError("a seed is required when the ladder is sharded over several ranks")
             seed = int(_capi.make_seeds(None, 1)[0])
         self._seed = int(seed)
+        if self._ncopies == 2:
+            if devices is not None:
+                raise ValueError("copies=2 is a single-device ladder: not with devices=[...]")
+            if self._world > 1:
+                raise ValueError("copies=2 is a single-process ladder: not inside a torch.distributed group of several ranks")
+            # both copies share ONE engine (one graph handle: the cluster move pairs replicas of one graph); each is a plain
+            # copies=1 ladder, the second one on a seed of its own, so that nothing it draws disturbs the first one's stream
+            shared = []
+
+            def factory():
+                if not shared:
+                    shared.append((engine_factory or (lambda: HipEngine(self._ea, self._eb, self._ej, self.nvars,
+                                                                         device=self._default_device())))())
+                return shared[0]
+
+            self._pair = [ClassicalTempering((self._ea, self._eb, self._ej), s, device=device, engine_factory=factory)
+                          for s in (self._seed, self._seed ^ COPY_SEED_XOR)]
+            self._t = 0               # absolute timestep, the same on both copies
+            self._icm_stats, self._icm_pending = None, False
         self._betas = []
         self._slot_seeds = []
         self._n_drawn = 0
@@ -95,6 +126,11 @@ class ClassicalTempering:
             raise ValueError("add every rung before the first timestep")
         if not np.isfinite(beta):
             raise ValueError("beta must be finite")
+        if self._pair is not None:   # copy 0: exactly what a copies=1 ladder does; copy 1 draws from its own stream
+            self._pair[0].add_graph(beta, seed)
+            self._pair[1].add_graph(beta)
+            self._betas.append(float(beta))
+            return
         if seed is None:  # seed.unwrap_or_else(|| self.tempering.rng_mut().gen())
             self._n_drawn += 1
             seed = int(_capi.make_seeds(self._seed, self._n_drawn)[-1])
@@ -105,6 +141,8 @@ class ClassicalTempering:
         return len(self._betas)
 
     def get_total_swaps(self):  # tempering.rs:297-299
+        if self._pair is not None:
+            return sum(c.get_total_swaps() for c in self._pair)
         if self._pgroup is not None:
             return int(self._shards[0].pt_state()[2])
         if self._on_stream:
@@ -115,7 +153,9 @@ class ClassicalTempering:
         return np.array(self._betas)
 
     def get_permutation(self):
-        """rung -> replica slot currently holding that temperature."""
+        """rung -> replica slot currently holding that temperature (copies=2: uint32[2, G], one row per copy)."""
+        if self._pair is not None:
+            return np.stack([c.get_permutation() for c in self._pair])
         self._materialise()
         if self._pgroup is not None:
             self._perm = self._shards[0].pt_state()[0]
@@ -124,7 +164,159 @@ class ClassicalTempering:
         return self._perm.copy()
 
     # -------------------------------------------------------------------------------------------
+    def set_replica_cluster_update_every(self, k):
+        """copies=2 only, before the first timestep: with k > 0 ladder timestep t is an isoenergetic cluster move between the two
+        configurations at every rung iff t % k == k - 1, in place of that timestep's sweep; 0 switches it off."""
+        if self._pair is None:
+            raise ValueError("replica cluster updates need two configurations per temperature: build the ladder with copies=2")
+        if self._states is not None:
+            raise ValueError("set the replica cluster update period before the first timestep")
+        if int(k) < 0:
+            raise ValueError("k must not be negative")
+        self._icm_every = int(k)
+
+    def get_replica_cluster_update_every(self):
+        return self._icm_every
+
+    def get_replica_cluster_stats(self):
+        """The last cluster move per rung: (number of q = -1 clusters, size of the largest, number of q = -1 sites), three
+        uint64[G] arrays; None before the first move."""
+        if self._pair is None:
+            raise ValueError("replica cluster updates need copies=2")
+        if self._icm_stats is None and self._icm_pending:
+            self._icm_stats = self._pair[0]._states.icm_between_stats()
+            self._icm_pending = False
+        return self._icm_stats
+
+    # -- copies=2: the two ladders, cut at exchange rounds and at cluster moves ------------------------------------------------
+    def _materialise_pair(self):
+        if self._states is not None:
+            return
+        if not self._betas:
+            raise ValueError("no graphs: call add_graph(beta) first")
+        a, b = self._pair
+        a._materialise()
+        b._materialise()
+        if a._on_stream != b._on_stream:   # (one graph, one geometry: cannot differ)
+            raise RuntimeError("the two copies of the ladder took different exchange paths")
+        if self._icm_every and not hasattr(a._states, "icm_between"):
+            raise ValueError("this engine has no isoenergetic cluster move between containers (icm_between)")
+        self._states = a._states
+        self._on_stream = a._on_stream
+        self._icm_pending = False
+
+    def _pair_icm(self):
+        """Timestep self._t of both copies as a cluster move between the configurations at equal rungs."""
+        a, b = self._pair
+        if self._on_stream:
+            a._states.icm_between(b._states)   # the rung permutations are read on the device
+        else:
+            a._states.icm_between(b._states, a._perm, b._perm)
+        self._icm_stats, self._icm_pending = None, True
+        self._t += 1
+
+    def _pair_sweeps(self, n):
+        for c in self._pair:
+            if c._on_stream:
+                c._states.pt_time_steps(n)
+            else:
+                c._states.do_time_steps(n)
+        self._t += n
+
+    def _until_icm(self):
+        """Metropolis timesteps before the next cluster move (None: there is none)."""
+        k = self._icm_every
+        return (k - 1 - self._t % k) if k else None
+
+    def _pair_timesteps(self, t, f):
+        self._materialise_pair()
+        t, f = int(t), int(f or 0)
+        done = 0
+        while done < t:
+            m = self._until_icm()
+            if m == 0:
+                self._pair_icm()   # a timestep; a round that falls on the same boundary comes after it
+                done += 1
+                if f and done % f == 0:
+                    for c in self._pair:
+                        c._swap_step()
+                continue
+            n = t - done if m is None else min(m, t - done)
+            while n > 0:
+                if f and done % f == 0 and n >= f and self._on_stream:
+                    whole = n // f * f     # rounds inside the stretch: one library call (in-kernel rounds on strip shapes)
+                    for c in self._pair:
+                        c._states.pt_run(whole, f)
+                    self._t += whole
+                    done += whole
+                    n -= whole
+                    continue
+                b = min(n, f - done % f) if f else n
+                self._pair_sweeps(b)
+                done += b
+                n -= b
+                if f and done % f == 0:
+                    for c in self._pair:
+                        c._swap_step()
+        if self._on_stream:
+            for c in self._pair:
+                c._states.synchronize()
+
+    def _pair_timesteps_sample(self, timesteps, replica_swap_freq, sampling_freq):
+        """The countdown scheduler of timesteps_sample over both copies, cut at cluster moves as well: states bool[2, G, S, N]
+        by rung, energies float64[2, G]."""
+        self._materialise_pair()
+        sampling_freq = 1 if sampling_freq is None else int(sampling_freq)
+        replica_swap_freq = 1 if replica_swap_freq is None else int(replica_swap_freq)
+        if sampling_freq <= 0:
+            raise ValueError("sampling_freq must be positive")
+        G, N = len(self._betas), self.nvars
+        S = timesteps // sampling_freq
+        for c in self._pair:
+            if c._on_stream:
+                c._perm = c._states.pt_state()[0]
+        states = np.zeros((2, G, S, N), dtype=np.bool_)   # by slot first
+        rungs = np.zeros((2, G, S), dtype=np.int64)
+        energy_acc = np.zeros((2, G), dtype=np.float64)
+        remaining, to_swap, to_sample, k = timesteps, replica_swap_freq, sampling_freq, 0
+        while remaining > 0:
+            t = min(to_sample, remaining) if replica_swap_freq <= 0 else min(to_sample, to_swap, remaining)
+            m = self._until_icm()
+            if m == 0:
+                t = 1
+                self._pair_icm()
+                for i, c in enumerate(self._pair):   # the energy after the move counts as this timestep's energy
+                    energy_acc[i] += c._states.energies()[c._perm]
+            else:
+                t = t if m is None else min(t, m)
+                for i, c in enumerate(self._pair):
+                    energy_acc[i] += c._states.do_time_steps(t, per_step_energies=True).sum(axis=1)[c._perm]
+                self._t += t
+            to_sample -= t
+            to_swap -= t
+            remaining -= t
+            if to_swap == 0 and replica_swap_freq > 0:
+                for c in self._pair:
+                    c._swap_step(need_perm=True)
+                to_swap = replica_swap_freq
+            if to_sample == 0:
+                if k < S:
+                    for i, c in enumerate(self._pair):
+                        c._states.states(out=states[i, :, k, :])
+                        inv = np.empty(G, dtype=np.int64)
+                        inv[c._perm] = np.arange(G)
+                        rungs[i, :, k] = inv
+                k += 1
+                to_sample = sampling_freq
+        by_rung = np.empty_like(states)
+        for i in range(2):
+            for s in range(S):
+                by_rung[i, rungs[i, :, s], s, :] = states[i, :, s, :]
+        return by_rung, energy_acc / max(timesteps, 1)
+
     def _materialise(self):
+        if self._pair is not None:
+            return self._materialise_pair()
         if self._states is not None:
             return
         G = len(self._betas)
@@ -243,6 +435,10 @@ class ClassicalTempering:
     def timesteps(self, t, replica_swap_freq=None):
         """tempering.rs:150-152 (parallel_timesteps): t sweeps on every rung.  replica_swap_freq (extension):
         an exchange round after every `replica_swap_freq` sweeps, as in the loop of tempering.rs:177-194."""
+        if self._pair is not None:
+            if t > 0:
+                self._pair_timesteps(t, replica_swap_freq)
+            return
         self._materialise()
         if t <= 0:
             return
@@ -283,8 +479,11 @@ class ClassicalTempering:
         Returns (states, energies[, rungs]): energies float64[G] = time average per rung (identical on
         every rank).  Single process: states bool[G, S, N] indexed by rung.  Sharded: states
         bool[G_local, S, N] of this rank's slots plus rungs int[G_local, S] = the rung each local slot
-        held at each sample (configurations never leave their GPU).
+        held at each sample (configurations never leave their GPU).  copies=2: states bool[2, G, S, N] by rung and
+        energies float64[2, G], one row per copy.
         """
+        if self._pair is not None:
+            return self._pair_timesteps_sample(timesteps, replica_swap_freq, sampling_freq)
         self._materialise()
         if self._pgroup is not None:
             return self._timesteps_sample_in_process(timesteps, replica_swap_freq, sampling_freq)
