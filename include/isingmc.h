@@ -237,9 +237,14 @@ int isingmc_states_set_timestep(isingmc_states *states, uint64_t t);
  * bonds between satisfied neighbours are activated with probability 1 - exp(-2 beta |J|), every connected cluster is flipped with
  * probability 1/2.  It counts as one timestep in every call (per-step energies, sampling, schedules, isingmc_states_set_timestep).
  * Served: checkerboard lattice containers with fast_path == 0 (periodic, no field, one |J|) and one coupling sign, W H < 2^32 - 1,
- * no ladder attached; everything else returns ISINGMC_ERR_INVALID and leaves k as it was.  k = 0 (the default) switches it off.
- * The workspace of a cluster step (8.4 bytes per site and replica) is limited by the option "cluster_workspace_bytes"
- * (isingmc_states_set_option; replicas are processed in batches that fit, at least one at a time; results do not depend on it). */
+ * no ladder attached; and replica-packed bit-sliced containers of any general graph (one |J|, no biases, degree <= 6,
+ * any sign pattern: cubic, triangular, honeycomb, diluted lattices, random regular graphs), no ladder attached.  Everything else --
+ * a general graph on the f64 CSR family (the packed family is chosen by size, by ISINGMC_FORCE_PACKED=1 or by
+ * ISINGMC_FLAG_STABLE_PATH at creation), the real-coupling path -- returns ISINGMC_ERR_INVALID and leaves k as it was.  k = 0 (the
+ * default) switches it off.
+ * The workspace of a cluster step (8.4 bytes per site and replica; packed containers: 284 bytes per position and group of 32
+ * replicas) is limited by the option "cluster_workspace_bytes" (isingmc_states_set_option; replicas -- whole groups of a packed
+ * container -- are processed in batches that fit, at least one at a time; results do not depend on it). */
 int isingmc_states_set_cluster_every(isingmc_states *states, size_t k);
 int isingmc_states_cluster_every(const isingmc_states *states, size_t *k_out);
 /* the last cluster step of every replica: number of clusters and size of the largest one, uint64[R] each (synchronises);

@@ -12,40 +12,13 @@
 // The isoenergetic cluster move of S9 reuses the tile, merge and max kernels between two kernels of its own (further down); S10 is
 // the same move between two containers, paired through slot tables in device memory.
 #include "cluster_kernels.hpp"
+#include "cluster_union.hpp"
 
 namespace isingmc {
 
 namespace {
 
-// ---- union-find on a label array that other threads link concurrently (LDS: workgroup scope, global: agent scope) ------------
-template <int SCOPE>
-__device__ __forceinline__ uint32_t cl_load(const uint32_t *p)
-{
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, SCOPE);
-}
-
-template <int SCOPE>
-__device__ __forceinline__ uint32_t cl_find(const uint32_t *lab, uint32_t a)
-{
-    for (uint32_t p = cl_load<SCOPE>(lab + a); p != a; p = cl_load<SCOPE>(lab + a)) a = p; // p < a: strictly decreasing
-    return a;
-}
-
-template <int SCOPE>
-__device__ __forceinline__ void cl_unite(uint32_t *lab, uint32_t a, uint32_t b)
-{
-    for (;;) {
-        a = cl_find<SCOPE>(lab, a);
-        b = cl_find<SCOPE>(lab, b);
-        if (a == b) return;
-        if (a < b) { const uint32_t x = a; a = b; b = x; }
-        // a > b: hang root a below b.  If a has stopped being a root meanwhile, its label is now min(old, b) -- still a member
-        // of the same component -- and the union goes on between old (< a) and b.
-        const uint32_t old = __hip_atomic_fetch_min(lab + a, b, __ATOMIC_RELAXED, SCOPE);
-        if (old == a) return;
-        a = old;
-    }
-}
+// (union-find on a label array that other threads link concurrently: cluster_union.hpp)
 
 // bits 0, 2, 4, ... of x, packed
 __device__ __forceinline__ uint32_t even_bits(uint64_t x)

@@ -29,6 +29,7 @@
 #include "general_kernels.hpp"
 #include "host_logic.hpp"
 #include "lattice_kernels.hpp"
+#include "packed_cluster_kernels.hpp"
 #include "packed_kernels.hpp"
 #include "mc_types.hpp"
 #include "real_types.hpp"
@@ -36,6 +37,8 @@
 #include "strip_types.hpp"
 
 using namespace isingmc;
+
+static_assert(PKC_PAD_SITE == PAD_SITE, "packed_cluster_kernels.hip tests PkGraphDev::site against the general path's padding mark");
 
 
 #define IM_INTERNAL __attribute__((visibility("hidden")))
@@ -266,7 +269,7 @@ struct isingmc_states {
     std::vector<double> ladder_betas; // host copy of d_pt_ladder (two ladders are compared without a device read)
     // Swendsen-Wang cluster steps (cluster_kernels.hpp): timestep t is one when cluster_every > 0 and t % cluster_every == cluster_every - 1
     size_t cluster_every = 0;
-    uint32_t *d_cl_stats = nullptr; // [cl_stats_cap][2]: clusters, largest cluster of the last cluster step
+    uint32_t *d_cl_stats = nullptr; // [cl_stats_cap][2]: clusters, largest cluster of the last cluster step (packed: per counter slot)
     size_t cl_stats_cap = 0;
     bool cl_have_stats = false;
     // isoenergetic cluster moves between the replicas (2 p, 2 p + 1): timestep t is one when icm_every > 0 and

@@ -1160,7 +1160,9 @@ struct StepRun {
     std::vector<RjBeta> h_rj{};
     // cluster steps: the workspace of one batch of replicas (allocated by the call's first cluster step), per-replica thresholds
     ClusterWork cl{nullptr, nullptr, nullptr, nullptr};
+    PkClusterWork pk_cl{nullptr, nullptr, nullptr, nullptr}; // (packed containers: a batch of replica groups)
     size_t cl_batch = 0;
+    bool pk_tabs_written = false; // run_packed has written the call's acceptance table (a call may begin with a cluster step)
     uint64_t *d_cl_thr = nullptr;
     std::vector<uint64_t> h_cl_thr{};
 };
@@ -1191,7 +1193,9 @@ static int run_packed(StepRun &c, size_t k0, size_t nk)
     // small launch when the rows run out (s->d_pk_philox: kept across calls)
     constexpr size_t PK_PHILOX_STEPS = 2048; // (>= chunk)
     const size_t philox_words = !s->rj && g->pk_uni_deg && !s->opt.disable_packed_uniform ? s->groups * pk_uni_philox_table_words() : 0;
-    const bool new_step_tabs = !s->has_betas && (c.beta_stride || k0 == 0);
+    // one table per timestep of the chunk, or one for the call: written by the call's first Metropolis chunk, which is not
+    // chunk 0 when the call begins with a cluster step
+    const bool new_step_tabs = !s->has_betas && (c.beta_stride || !c.pk_tabs_written);
     const bool new_philox_rows = philox_words && !(s->pk_philox_steps && s->pk_philox_groups == s->groups && s->t >= s->pk_philox_t0 &&
                                                    s->t + nk <= s->pk_philox_t0 + s->pk_philox_steps);
     if (k0 > 0 && (new_step_tabs || new_philox_rows)) { // the chunk's tables are overwritten: every lane must have finished reading them
@@ -1213,6 +1217,7 @@ static int run_packed(StepRun &c, size_t k0, size_t nk)
         });
         HIP_TRY(hipMemcpy(c.d_pk_tabs, c.h_pk_tabs.data(), c.h_pk_tabs.size() * sizeof(c.h_pk_tabs[0]), hipMemcpyHostToDevice));
     }
+    if (new_step_tabs) c.pk_tabs_written = true;
     if (new_philox_rows) { // (on the main stream, the lanes joined: in order with every sweep that read the old rows)
         if (!s->d_pk_philox) TRY(dev_alloc(&s->d_pk_philox, PK_PHILOX_STEPS * philox_words));
         HIP_TRY(pk_uni_launch_philox_table(s->stream, s->d_pk_philox, s->d_keys, uint32_t(s->groups), s->t, uint32_t(PK_PHILOX_STEPS)));
@@ -1438,15 +1443,22 @@ static int run_gen_csr(StepRun &c, size_t k0, size_t nk)
 }
 
 // ------------------------------------------------------------------------------------------------
-// Swendsen-Wang cluster steps (cluster_kernels.hip)
+// Swendsen-Wang cluster steps (cluster_kernels.hip; S11 on replica-packed containers, packed_cluster_kernels.hip)
 // ------------------------------------------------------------------------------------------------
 
 // why this container cannot take cluster steps ("" when it can)
 static std::string cluster_obstacle(const isingmc_states *s)
 {
     const isingmc_graph *g = s->g;
-    if (g->kind != ISINGMC_KIND_LATTICE2D || s->packed)
-        return "cluster updates need a container on the checkerboard lattice path; this graph runs on a general-graph kernel family";
+    if (s->packed) { // S11: any graph of the bit-sliced packed path, any sign pattern
+        if (s->rj) return "cluster updates are not implemented for the replica-packed real-coupling path (couplings of one size and no biases only)";
+        if (s->pt_attached) return "a tempering ladder is attached to this container (isingmc_pt_detach first)";
+        return "";
+    }
+    if (g->kind != ISINGMC_KIND_LATTICE2D)
+        return "cluster updates need a container on the checkerboard lattice path or on the replica-packed bit-sliced path; this graph runs on "
+               "the f64 CSR general-graph kernel family (cluster updates on general graphs need the replica-packed family: chosen by size, "
+               "or by ISINGMC_FORCE_PACKED=1 / the stable-path flag at creation)";
     if (g->mc_mode == MC_FIELD || g->mc_mode == MC_FIELD_OPEN) return "cluster updates are not implemented for lattices with a field";
     if (g->mc_mode == MC_OPEN) return "cluster updates are not implemented for open boundaries (periodic lattices only)";
     if (g->mc_mode != MC_NONE) return "cluster updates are not implemented for anisotropic couplings (|Jx| != |Jy|)";
@@ -1478,13 +1490,13 @@ extern "C" int isingmc_states_cluster_every(const isingmc_states *s, size_t *k_o
 extern "C" int isingmc_cluster_stats(isingmc_states *s, uint64_t *n_clusters_out, uint64_t *largest_out)
 {
     if (!s || !n_clusters_out || !largest_out) return fail(ISINGMC_ERR_INVALID, "NULL argument");
-    if (!s->cl_have_stats || s->cl_stats_cap < s->R) return fail(ISINGMC_ERR_INVALID, "no cluster step has run on these replicas yet");
+    if (!s->cl_have_stats || s->cl_stats_cap < counter_slots(s)) return fail(ISINGMC_ERR_INVALID, "no cluster step has run on these replicas yet");
     TRY(use_device(s->g->device));
     std::vector<uint32_t> h;
-    TRY(read_back(s, h, s->d_cl_stats, 2 * s->R));
-    for (size_t r = 0; r < s->R; r++) {
-        n_clusters_out[r] = h[2 * r];
-        largest_out[r] = h[2 * r + 1];
+    TRY(read_back(s, h, s->d_cl_stats, 2 * counter_slots(s)));
+    for (size_t r = 0; r < s->R; r++) { // (packed: one pair per (group, bit) slot)
+        n_clusters_out[r] = h[2 * counter_slot(s, r)];
+        largest_out[r] = h[2 * counter_slot(s, r) + 1];
     }
     return ISINGMC_OK;
 }
@@ -1498,6 +1510,52 @@ static uint64_t cluster_threshold(double beta, double jabs)
 
 static bool is_cluster_step(const isingmc_states *s) { return s->cluster_every && s->t % s->cluster_every == s->cluster_every - 1; }
 
+// the same on a replica-packed bit-sliced container: batches of whole replica groups; every bit of a group is
+// simulated, owned or not, as by the sweeps
+static int run_cluster_packed(StepRun &c, size_t k0)
+{
+    isingmc_states *s = c.s;
+    const isingmc_graph *g = s->g;
+    const size_t groups = s->groups, slots = s->pk_slots(), n_pos = g->pk.n_pos;
+    if (!c.pk_cl.labels) {
+        const size_t words = pk_cluster_words_per_group(n_pos);
+        c.cl_batch = std::min<size_t>({groups, size_t(32768), std::max<size_t>(1, size_t(std::max(1, s->opt.cluster_workspace_bytes)) / (words * sizeof(uint32_t)))});
+        uint32_t *block = nullptr;
+        TRY(c.scratch.alloc(&block, c.cl_batch * words));
+        c.pk_cl.labels = block;
+        c.pk_cl.sizes = c.pk_cl.labels + c.cl_batch * n_pos * 32;
+        c.pk_cl.bonds = c.pk_cl.sizes + c.cl_batch * n_pos * 32;
+        c.pk_cl.fliptab = c.pk_cl.bonds + c.cl_batch * n_pos * PK_MAX_DEG;
+    }
+    if (s->cl_stats_cap < slots) { // (the groups of a packed container are fixed for its life: allocated once)
+        HIP_TRY(stream_quiesce(s->stream));
+        if (s->d_cl_stats) HIP_TRY(cached_free(s->d_cl_stats));
+        s->d_cl_stats = nullptr;
+        s->cl_stats_cap = 0;
+        TRY(dev_alloc(&s->d_cl_stats, 2 * slots));
+        s->cl_stats_cap = slots;
+    }
+    uint64_t thr = 0;
+    if (!s->has_betas) thr = cluster_threshold(c.betas[k0 * c.beta_stride], g->jabs);
+    else if (!c.d_cl_thr) { // per-replica betas do not change inside a call; bits this shard does not own take the nearest owned replica's
+        c.h_cl_thr.resize(slots);
+        for (size_t sl = 0; sl < slots; sl++)
+            c.h_cl_thr[sl] = cluster_threshold(s->betas[sl < s->pk_bit0 ? 0 : std::min(s->R - 1, sl - s->pk_bit0)], g->jabs);
+        TRY(c.scratch.alloc(&c.d_cl_thr, slots));
+        HIP_TRY(hipMemcpyAsync(c.d_cl_thr, c.h_cl_thr.data(), slots * sizeof(uint64_t), hipMemcpyHostToDevice, s->stream));
+    }
+    HIP_TRY(hipMemsetAsync(s->d_cl_stats, 0, 2 * slots * sizeof(uint32_t), s->stream));
+    for (size_t g0 = 0; g0 < groups; g0 += c.cl_batch) {
+        const size_t n = std::min(c.cl_batch, groups - g0);
+        HIP_TRY(pk_cluster_launch_step(s->stream, s->d_state + g0 * n_pos, g->pk, s->t, s->d_keys + g0, thr, c.d_cl_thr ? c.d_cl_thr + 32 * g0 : nullptr,
+                                       c.pk_cl, uint32_t(n), s->d_cl_stats + 2 * 32 * g0));
+    }
+    s->cl_have_stats = true;
+    s->t++;
+    if (c.d_counts) TRY(measure_enqueue(s, c.d_counts, nullptr, nullptr, /*want_up=*/false)); // the energy after this timestep: step 0 of the chunk
+    return ISINGMC_OK;
+}
+
 // timestep s->t (= step k0 of the call) as a cluster step of every replica, batch by batch on the main stream
 static int run_cluster(StepRun &c, size_t k0)
 {
@@ -1505,6 +1563,7 @@ static int run_cluster(StepRun &c, size_t k0)
     const isingmc_graph *g = s->g;
     const size_t R = s->R;
     if (s->n_lanes > 1) TRY(lanes_join(s)); // the Metropolis stretch before this step may have run on replica lanes
+    if (s->packed) return run_cluster_packed(c, k0);
     if (!c.cl.labels) {
         const size_t words = cluster_words_per_replica(g->nvars);
         c.cl_batch = std::min<size_t>({R, size_t(32768), std::max<size_t>(1, size_t(std::max(1, s->opt.cluster_workspace_bytes)) / (words * sizeof(uint32_t)))});
@@ -1854,7 +1913,8 @@ static int run_steps_impl(isingmc_states *s, size_t timesteps, const double *bet
         if (cluster || icm) nk = 1;
         else if (const size_t every = s->cluster_every ? s->cluster_every : s->icm_every) {
             nk = std::min<size_t>(nk, every - 1 - s->t % every);
-            if (P.lanes > 1 && s->n_lanes <= 1) TRY(lanes_fork(s, P.lanes)); // (joined by the cluster step before this stretch)
+            // (joined by the cluster step before this stretch; the packed runner forks behind its table launches)
+            if (P.lanes > 1 && s->n_lanes <= 1 && P.path != StepPath::Packed) TRY(lanes_fork(s, P.lanes));
         }
         if (c.d_counts && P.path != StepPath::Packed) // (measure_enqueue clears the packed counters itself)
             HIP_TRY(hipMemsetAsync(c.d_counts, 0, nk * R * P.step_slots * 2 * sizeof(unsigned long long), s->stream));

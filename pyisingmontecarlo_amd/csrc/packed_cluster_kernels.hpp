@@ -1,0 +1,35 @@
+// Swendsen-Wang cluster step on the replica-packed bit-sliced path: any graph the S6 path serves (one |J|, no
+// fields, degree <= 6, any sign pattern).  Launch interface of packed_cluster_kernels.hip (a translation unit of its own:
+// nothing here is instantiated beside the tuned sweep kernels).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstddef>
+#include <cstdint>
+
+#include "packed_types.hpp"
+
+namespace isingmc {
+
+constexpr uint32_t DOM_PK_CL_BOND = 0x504B4244u; // "PKBD"
+constexpr uint32_t DOM_PK_CL_FLIP = 0x504B464Cu; // "PKFL"
+// PkGraphDev::site on padding; general_kernels.hpp (PAD_SITE) is not included here because it would instantiate its kernels in
+// this translation unit: internal.hpp, which sees both, asserts that the two agree
+constexpr uint32_t PKC_PAD_SITE = 0xFFFFFFFFu;
+
+// workspace of one batch of n replica groups (n_pos positions each)
+struct PkClusterWork {
+    uint32_t *labels;  // [n][n_pos][32]         (position, replica bit) -> a smaller position of its cluster (the root: the smallest)
+    uint32_t *sizes;   // [n][n_pos][32]         positions per root
+    uint32_t *bonds;   // [n][PK_MAX_DEG][n_pos] active bonds of the 32 replicas, by (adjacency slot, owner position); 0 where not owned
+    uint32_t *fliptab; // [n][n_pos]             flip bits of the 32 replicas for every possible root
+};
+
+constexpr size_t pk_cluster_words_per_group(uint64_t n_pos) { return size_t((64 + PK_MAX_DEG + 1) * n_pos); }
+
+// One cluster step of groups [0, n) at timestep t: state / group_keys / thr_per_slot / stats point at the first group of the
+// batch.  thr_per_slot == nullptr: every replica uses thr; else thr_per_slot[32 g + b].  stats: [32 n][2] = {clusters, largest
+// cluster} per (group, replica bit), zero on entry.  n <= 32768.
+hipError_t pk_cluster_launch_step(hipStream_t stream, uint32_t *state, const PkGraphDev &G, uint64_t t, const uint2 *group_keys, uint64_t thr,
+                                  const uint64_t *thr_per_slot, const PkClusterWork &work, uint32_t n, uint32_t *stats);
+
+} // namespace isingmc
