@@ -210,6 +210,10 @@ struct isingmc_states {
     std::vector<hipEvent_t> lane_events;
     hipEvent_t fork_event = nullptr;
     size_t n_lanes = 1; // lanes in use by the current run_steps call
+    // workgroups of lat_sweep_loop_kernel<uniform J / +-J> the device holds at once with sweep_resident_lds bytes of LDS each
+    // (occupancy query x CUs, asked once; -1 = not asked yet)
+    int sweep_resident_wgs[2] = {-1, -1};
+    unsigned sweep_resident_lds = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool has_betas = false;
     std::vector<double> betas;

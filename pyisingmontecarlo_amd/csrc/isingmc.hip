@@ -588,6 +588,45 @@ int pk_get_states(isingmc_states *s, uint8_t *states_out, size_t replica_stride_
 // ------------------------------------------------------------------------------------------------
 // sweeps
 // ------------------------------------------------------------------------------------------------
+// Quads per thread of a streaming half-sweep (1 = the one-quad kernel, else lat_sweep_loop_kernel), for a dispatch of `n`
+// replicas of the container's s->R.  A looping thread walks `iters` quads nquads / iters apart: that distance must be a whole,
+// even number of rows (the kernel carries the row parity and the column across its iterations), i.e. 2 * iters divides H.
+//  - resident-sized launch: the largest power of two <= 16 at which the workgroups of ALL lanes of the half-sweep together
+//    are a whole multiple, and at least twice, of the workgroups the device holds at once (occupancy query x CUs): every
+//    wave slot is refilled by the wave's own next quad, all workgroups are equally long and the rounds are whole, so there
+//    is no tail to quantise; the second round lets the CUs that ran ahead take more than their share.  4096^2 x 256 on 256
+//    CUs: 65536 one-quad workgroups, 2048 resident => 16 quads per thread, two rounds.  Measured there, same box, against
+//    two quads per thread: 16 quads +3.0 %, 8 quads +2.7 %, 32 quads (ONE round) +1.3 %; one lane instead of two: -7 % at
+//    16, -11 % at 32 (profiles/2026-10-17_resident_sweep_ab.txt);
+//  - else two quads per thread while that leaves >= 8 workgroups per CU (measured before the rule above existed: 2 quads +4 %,
+//    4 +2.7 %, 8 +1.3 % on uniform J; +-J: 2 quads +2.6 %).  Workgroups of 128 or 64 threads: no gain.
+// ISINGMC_SWEEP_ITERS=1|2|4|8|16|32 forces the choice (measurement and tests).
+template <bool PMJ>
+static uint32_t sweep_loop_iters(isingmc_states *s, size_t n, unsigned lds_bytes)
+{
+    const LatGeom &geom = s->g->geom;
+    const auto fits = [&](uint32_t k) { return geom.nquads % (256 * k) == 0 && geom.H % (2 * k) == 0; };
+    const int forced = s->opt.sweep_iters;
+    if (forced) return forced > 1 && forced <= 32 && (forced & (forced - 1)) == 0 && fits(uint32_t(forced)) ? uint32_t(forced) : 1u;
+    if (s->sweep_resident_wgs[PMJ] < 0 || s->sweep_resident_lds != lds_bytes) {
+        int per_cu = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lat_sweep_loop_kernel<PMJ>, 256, lds_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            per_cu = 0;
+        }
+        s->sweep_resident_wgs[!PMJ] = -1; // a container runs one of the two instantiations
+        s->sweep_resident_wgs[PMJ] = per_cu * s->g->n_cu;
+        s->sweep_resident_lds = lds_bytes;
+    }
+    const size_t resident = size_t(s->sweep_resident_wgs[PMJ]);
+    for (uint32_t k = 16; resident > 0 && k > 1; k >>= 1) {
+        if (!fits(k)) continue;
+        const size_t wgs = size_t(geom.nquads / (256 * k)) * s->R;
+        if (wgs >= 2 * resident && wgs % resident == 0) return k;
+    }
+    return fits(2) && size_t(geom.nquads / 512) * n >= size_t(8) * 256 ? 2u : 1u;
+}
+
 template <bool VEC, bool PMJ>
 static void launch_lat_sweep(isingmc_states *s, uint32_t colour, const LatThr &thr, uint64_t t_arg)
 {
@@ -607,17 +646,8 @@ static void launch_lat_sweep(isingmc_states *s, uint32_t colour, const LatThr &t
                                    s->d_state + r0 * g->state_words, g->geom, colour, t_arg, s->d_keys + r0, thr,
                                    s->has_betas ? s->d_thr + r0 : nullptr, g->d_jneg, g->jneg_uniform);
             };
-            // large launches: every thread loops over two quads (measured: 2 quads +4 %, 4 +2.7 %, 8 +1.3 % on
-            // uniform J; +-J: 2 quads +2.6 %, 4 quads -2 %).  Workgroups of 128 or 64 threads: no gain.
-            // ISINGMC_SWEEP_ITERS=1|2|4|8 forces the choice (measurement only)
             uint32_t iters = 1;
-            if (VEC && g->geom.cols_log2 >= 0) {
-                const int forced = s->opt.sweep_iters;
-                const uint32_t want = forced ? uint32_t(forced) : 2u;
-                if (want > 1 && g->geom.nquads % (256 * want) == 0 &&
-                    (forced || size_t(g->geom.nquads / (256 * want)) * n >= size_t(8) * 256)) // >= 8 workgroups per CU left (c4: +2.6 %)
-                    iters = want;
-            }
+            if (VEC && g->geom.cols_log2 >= 0) iters = sweep_loop_iters<PMJ>(s, n, dbg_lds);
             if (iters > 1)
                 hipLaunchKernelGGL(lat_sweep_loop_kernel<PMJ>, dim3(g->geom.nquads / (256 * iters), unsigned(n), 1), dim3(256), dbg_lds, stream,
                                    s->d_state + r0 * g->state_words, g->geom, colour, t_arg, s->d_keys + r0, thr,

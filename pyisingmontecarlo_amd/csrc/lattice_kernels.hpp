@@ -720,26 +720,97 @@ __global__ __launch_bounds__(256) void lat_sweep_kernel(
 // 6.8 of the 8 wave slots of a SIMD were occupied (SQ_WAVE_CYCLES), and the kernel loses 9 % going from 8 to 6.
 // Here the slot is refilled by the wave's own next iteration, and the prologue (kernel arguments, key, round
 // keys, threshold bits) is paid once per `iters` quads.  Same quads, same counters: bit-identical.
+//
+// The thread -> quad map of load_quad_uni is evaluated ONCE per thread: `stride` quads are a whole, even number
+// of rows (the host launches nothing else), so from one iteration to the next every lane's quad, its row and
+// all its load offsets move by the same wave-uniform amount, the row parity and the column stay.  The lane
+// offsets of the first quad (vQ, vS) never change; the walk rides in the buffer instructions' scalar offset,
+// and the quad index (Philox counter word 1) takes one add.  The wave's first row is carried on the scalar
+// unit: the iteration in which the wave holds row H-1 wraps its rows per lane, as load_quad_uni does; so does, in all
+// its iterations, the wave that starts in row 0.
 template <bool PMJ>
 __global__ __launch_bounds__(256) void lat_sweep_loop_kernel(
     uint32_t *__restrict__ state, const LatGeom g, const uint32_t colour, const uint64_t t,
     const uint2 *__restrict__ keys, const LatThr thr_uniform, const LatThr *__restrict__ thr_replica,
     const uint32_t *__restrict__ jneg, const uint32_t jneg_uniform, const uint32_t iters)
 {
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     const uint32_t r = blockIdx.y;
-    const uint32_t stride = gridDim.x * 256; // g.nquads == iters * stride (checked by the host)
-    uint32_t gid = blockIdx.x * 256 + threadIdx.x;
+    const uint32_t stride = gridDim.x * 256; // g.nquads == iters * stride, stride >> cols_log2 even (checked by the host)
+    const uint32_t gid = blockIdx.x * 256 + threadIdx.x;
     BufPlanes mem;
     mem.rsrc = __builtin_amdgcn_make_buffer_rsrc(state + size_t(r) * 2 * g.wpp, 0, int(2 * g.wpp * sizeof(uint32_t)), 0x00020000);
     mem.own_off = colour * g.wpp * 4u;
     mem.oth_off = (1 - colour) * g.wpp * 4u;
     const uint2 key = keys[r];
     const PhiloxVKeys vk = philox_vkeys(key);
-    const LatThr thr = thr_replica ? thr_replica[r] : thr_uniform;
+    const ThrBits tb = thr_bits(thr_replica ? thr_replica[r] : thr_uniform);
     const uint32_t *jn = PMJ ? jneg + size_t(colour) * 4 * g.wpp : nullptr;
+
+    const uint32_t cl = uint32_t(g.cols_log2), rb = 16u << cl; // row bytes of a plane
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(gid >> 6), lane = gid & 63u;
+    uint32_t ys, span; // wave-uniform: the first row of the wave's quads; it holds row H-1 when ys + span >= H
+    uint32_t Q;
+    bool odd;
+    if (cl >= 6) { // a wave never leaves its row
+        ys = wave >> (cl - 6);
+        span = 1;
+        Q = gid;
+        odd = ((ys + colour) & 1u) != 0;
+    } else {
+        const uint32_t rpw = 64u >> cl;
+        ys = ((wave >> 1) << (7 - cl)) + (wave & 1u);
+        span = 2 * (rpw - 1) + 1;
+        Q = ((ys + 2 * (lane >> cl)) << cl) + (lane & ((1u << cl) - 1));
+        odd = ((wave + colour) & 1u) != 0;
+    }
+    const uint32_t vQ = Q << 4, t16 = vQ & (rb - 1);
+    const uint32_t vS = (vQ - t16) + (odd ? ((t16 + 16) & (rb - 1)) : ((t16 - 4) & (rb - 1)));
+    const uint32_t row_step = stride >> cl, byte_step = stride << 4;
+    // a lane that began in row 0 has no valid "one row up" offset relative to its first quad (the buffer's range check sees the
+    // lane offset alone, and vQ - rb is negative there): its wave, one per plane and workgroup column, keeps the per-lane form
+    const bool from_row0 = ys == 0;
+    uint32_t walked = 0; // bytes between the first quad and the current one
 #pragma unroll 1
-    for (uint32_t it = 0; it < iters; it++, gid += stride)
-        update_quad<true, PMJ, true>(mem, g, colour, t, key, vk, thr, jn, jneg_uniform, gid);
+    for (uint32_t it = 0; it < iters; it++) {
+        uint32_t vU, vD, s_ud; // up / down rows: lane offset + scalar offset
+        if (from_row0 | (ys + span >= g.H)) { // per-lane wrap: the wave holding row H-1 in that iteration, the one that began in row 0
+            const uint32_t y = Q >> cl, col = Q & ((1u << cl) - 1);
+            const uint32_t yu = (y == 0 ? g.H : y) - 1, yd = (y + 1 == g.H) ? 0 : y + 1;
+            vU = ((yu << cl) + col) << 4;
+            vD = ((yd << cl) + col) << 4;
+            s_ud = mem.oth_off;
+        } else {
+            vU = vQ - rb;
+            vD = vQ + rb;
+            s_ud = mem.oth_off + walked;
+        }
+        const u32x4 o4 = __builtin_amdgcn_raw_buffer_load_b128(mem.rsrc, vQ, mem.own_off + walked, 0);
+        const u32x4 c4 = __builtin_amdgcn_raw_buffer_load_b128(mem.rsrc, vQ, mem.oth_off + walked, 0);
+        const u32x4 u4 = __builtin_amdgcn_raw_buffer_load_b128(mem.rsrc, vU, s_ud, 0);
+        const u32x4 d4 = __builtin_amdgcn_raw_buffer_load_b128(mem.rsrc, vD, s_ud, 0);
+        const uint32_t sw = __builtin_amdgcn_raw_buffer_load_b32(mem.rsrc, vS, mem.oth_off + walked, 0);
+        uint32_t own[4] = {o4.x, o4.y, o4.z, o4.w}, acc[4];
+        QuadNbr n;
+        n.ce[0] = c4.x; n.ce[1] = c4.y; n.ce[2] = c4.z; n.ce[3] = c4.w;
+        n.up[0] = u4.x; n.up[1] = u4.y; n.up[2] = u4.z; n.up[3] = u4.w;
+        n.dn[0] = d4.x; n.dn[1] = d4.y; n.dn[2] = d4.z; n.dn[3] = d4.w;
+        n.si[0] = sw;
+        side_words(n, odd);
+        QuadSigns js;
+        load_signs<PMJ>(jn, g, Q, js);
+        const uint32_t widx[4] = {4 * Q, 4 * Q + 1, 4 * Q + 2, 4 * Q + 3};
+        QuadState st[1];
+        const uint32_t Qs[1] = {Q};
+        quad_classes<PMJ>(own, n, widx, g, tb, js, jneg_uniform, st[0]);
+        quad_planes<1>(st, Qs, colour, t, key, vk, tb);
+        quad_ties(st[0], Q, colour, t, key, vk, tb, acc);
+        __builtin_amdgcn_raw_buffer_store_b128(u32x4{own[0] ^ acc[0], own[1] ^ acc[1], own[2] ^ acc[2], own[3] ^ acc[3]}, mem.rsrc, vQ,
+                                               mem.own_off + walked, 0);
+        Q += stride;
+        ys += row_step;
+        walked += byte_step;
+    }
 }
 
 // Random initial configuration: word w of plane c = Philox(key, (0, w>>2, c<<8, "LATI"))[w&3].
