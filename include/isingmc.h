@@ -251,17 +251,21 @@ int isingmc_states_cluster_every(const isingmc_states *states, size_t *k_out);
  * ISINGMC_ERR_INVALID before the first cluster step */
 int isingmc_cluster_stats(isingmc_states *states, uint64_t *n_clusters_out, uint64_t *largest_out);
 
-/* ---- Isoenergetic cluster moves between replica pairs (DESIGN.md S9; Houdayer 2001; no reference counterpart) ----
+/* ---- Isoenergetic cluster moves between replica pairs (DESIGN.md S9, S12; Houdayer 2001; no reference counterpart) ----
  * With k > 0 every timestep t with t % k == k - 1 is an isoenergetic cluster move instead of a Metropolis sweep: the replicas with
  * GLOBAL experiment indices (2 p, 2 p + 1) form pair p; the connected clusters of the sites where the two configurations differ
  * (overlap q = -1) are each flipped, in both replicas, with probability 1/2.  The move is rejection-free, conserves the sum of the
  * two energies exactly for any couplings and does not read beta: it is valid between replicas at the same temperature only, so
  * per-replica betas must be equal inside every pair.  A last replica without a partner is left unchanged (its timestep counts).
  * Served: checkerboard lattice containers with fast_path == 0 (periodic, no field, one |J|) of ANY sign pattern (ferromagnet,
- * antiferromagnet, +-J glass), W H < 2^32 - 1, no ladder attached, Swendsen-Wang steps off, a shard that starts on an even
- * experiment index and does not end inside a pair; everything else returns ISINGMC_ERR_INVALID and leaves k as it was.  While it
- * is on, isingmc_states_set_cluster_every(k > 0), isingmc_pt_attach and unequal pair betas are refused.  k = 0 (the default)
- * switches it off.  Workspace: that of a Swendsen-Wang step per PAIR, under the same option "cluster_workspace_bytes". */
+ * antiferromagnet, +-J glass), W H < 2^32 - 1, and (S12) replica-packed containers of both families -- bit-sliced and
+ * real-coupling: any graph, couplings and biases those paths run; the two replicas swap their spins on a cluster, which
+ * conserves the sum of the two energies with fields too -- no ladder attached, Swendsen-Wang steps off, a shard that starts on an
+ * even experiment index and does not end inside a pair; everything else (containers on the f64 CSR general-graph family among
+ * it) returns ISINGMC_ERR_INVALID and leaves k as it was.  While it is on, isingmc_states_set_cluster_every(k > 0),
+ * isingmc_pt_attach and unequal pair betas are refused.  k = 0 (the default) switches it off.  Workspace: that of a
+ * Swendsen-Wang step per PAIR (packed containers: about 130 bytes per position and replica GROUP, batched by whole groups), under
+ * the same option "cluster_workspace_bytes". */
 int isingmc_states_set_icm_every(isingmc_states *states, size_t k);
 int isingmc_states_icm_every(const isingmc_states *states, size_t *k_out);
 /* the last isoenergetic cluster move of every pair: number of q = -1 clusters, size of the largest one and number of q = -1 sites n
@@ -281,7 +285,8 @@ int isingmc_icm_stats(isingmc_states *states, uint64_t *n_clusters_out, uint64_t
  *     slot per rung) over bitwise equal betas, n_pairs = the number of rungs, and pair r = (a's slot at rung r, b's slot at rung
  *     r): the kernels read the two permutations on the device.
  * Refused with ISINGMC_ERR_INVALID and a message (both containers stay as they were): a == b, two graph handles, a graph that
- * isingmc_states_set_icm_every would refuse (general-graph families, fields, open boundaries, anisotropic couplings, W H >=
+ * is not a checkerboard lattice isingmc_states_set_icm_every accepts (general-graph families, the replica-packed ones
+ * included; fields, open boundaries, anisotropic couplings, W H >=
  * 2^32 - 1), unequal timesteps, Swendsen-Wang steps or isoenergetic cluster moves switched on inside either container, unequal
  * pair betas, slots out of range or used twice, the NULL form without two matching ladders. */
 int isingmc_icm_between(isingmc_states *a, isingmc_states *b, const uint32_t *slots_a, const uint32_t *slots_b, size_t n_pairs);

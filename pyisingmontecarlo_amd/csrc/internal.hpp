@@ -30,6 +30,7 @@
 #include "host_logic.hpp"
 #include "lattice_kernels.hpp"
 #include "packed_cluster_kernels.hpp"
+#include "packed_icm_kernels.hpp"
 #include "packed_kernels.hpp"
 #include "mc_types.hpp"
 #include "real_types.hpp"

@@ -1191,6 +1191,9 @@ struct StepRun {
     // cluster steps: the workspace of one batch of replicas (allocated by the call's first cluster step), per-replica thresholds
     ClusterWork cl{nullptr, nullptr, nullptr, nullptr};
     PkClusterWork pk_cl{nullptr, nullptr, nullptr, nullptr}; // (packed containers: a batch of replica groups)
+    PkIcmWork pk_icm{nullptr, nullptr, nullptr};             // (isoenergetic moves on packed containers, S12)
+    uint32_t *d_icm_mask = nullptr;                          // the moving pairs of every group (written by the call's first move)
+    std::vector<uint32_t> h_icm_mask{};
     size_t cl_batch = 0;
     bool pk_tabs_written = false; // run_packed has written the call's acceptance table (a call may begin with a cluster step)
     uint64_t *d_cl_thr = nullptr;
@@ -1633,22 +1636,30 @@ static int run_cluster(StepRun &c, size_t k0)
 }
 
 // ------------------------------------------------------------------------------------------------
-// Isoenergetic cluster moves between replica pairs (cluster_kernels.hip)
+// Isoenergetic cluster moves between replica pairs (cluster_kernels.hip; S12 on replica-packed containers of both
+// families, packed_icm_kernels.hip)
 // ------------------------------------------------------------------------------------------------
 
 // why this container cannot take isoenergetic cluster moves ("" when it can)
 static std::string icm_obstacle(const isingmc_states *s)
 {
     const isingmc_graph *g = s->g;
-    if (g->kind != ISINGMC_KIND_LATTICE2D || s->packed)
-        return "isoenergetic cluster moves need a container on the checkerboard lattice path; this graph runs on a general-graph kernel family";
-    if (g->mc_mode == MC_FIELD || g->mc_mode == MC_FIELD_OPEN) return "isoenergetic cluster moves are not implemented for lattices with a field";
-    if (g->mc_mode == MC_OPEN) return "isoenergetic cluster moves are not implemented for open boundaries (periodic lattices only)";
-    if (g->mc_mode != MC_NONE) return "isoenergetic cluster moves are not implemented for anisotropic couplings (|Jx| != |Jy|)";
-    if (g->nvars >= 0xFFFFFFFFull) return "isoenergetic cluster moves label sites with 32 bits: W H must be below 2^32 - 1";
+    if (s->packed) { // S12: any graph of either packed family (the move reads no coupling and no bias)
+        if (s->cluster_every)
+            return "Swendsen-Wang cluster updates are switched on for this replica-packed general-graph container (isingmc_states_set_cluster_every): "
+                   "one non-local move at a time";
+    } else {
+        if (g->kind != ISINGMC_KIND_LATTICE2D)
+            return "isoenergetic cluster moves need a container on the checkerboard lattice path; this graph runs on a general-graph kernel family";
+        if (g->mc_mode == MC_FIELD || g->mc_mode == MC_FIELD_OPEN) return "isoenergetic cluster moves are not implemented for lattices with a field";
+        if (g->mc_mode == MC_OPEN) return "isoenergetic cluster moves are not implemented for open boundaries (periodic lattices only)";
+        if (g->mc_mode != MC_NONE) return "isoenergetic cluster moves are not implemented for anisotropic couplings (|Jx| != |Jy|)";
+        if (g->nvars >= 0xFFFFFFFFull) return "isoenergetic cluster moves label sites with 32 bits: W H must be below 2^32 - 1";
+    }
     if (s->pt_attached) return "a tempering ladder is attached to this container (isingmc_pt_detach first)";
     if (s->cluster_every) return "Swendsen-Wang cluster updates are switched on for this container (isingmc_states_set_cluster_every): one non-local move at a time";
     // pairs are (2 p, 2 p + 1) of the GLOBAL experiment index: a shard must hold both replicas of every pair it touches
+    // (packed: the pair is then bits (2 j, 2 j + 1) of one state word, pk_bit0 = first % 32 being even)
     if (s->first % 2) return "this shard starts at an odd experiment index: its first replica's partner lives on another shard";
     if ((s->first + s->R) % 2 && s->first + s->R < s->n_total) return "this shard ends inside a pair: its last replica's partner lives on another shard";
     if (s->has_betas && icm_unequal_pair_betas(s, s->betas.data()))
@@ -1677,20 +1688,66 @@ extern "C" int isingmc_states_icm_every(const isingmc_states *s, size_t *k_out)
 extern "C" int isingmc_icm_stats(isingmc_states *s, uint64_t *n_clusters_out, uint64_t *largest_out, uint64_t *minus_sites_out)
 {
     if (!s || !n_clusters_out || !largest_out || !minus_sites_out) return fail(ISINGMC_ERR_INVALID, "NULL argument");
-    const size_t pairs = s->R / 2;
-    if (!s->icm_have_stats || s->icm_stats_cap < pairs) return fail(ISINGMC_ERR_INVALID, "no isoenergetic cluster move has run on these replicas yet");
+    const size_t pairs = s->R / 2, slot0 = s->packed ? s->pk_bit0 / 2 : 0; // (packed: device slot 16 group + pair; pk_bit0 is even)
+    if (!s->icm_have_stats || s->icm_stats_cap < slot0 + pairs) return fail(ISINGMC_ERR_INVALID, "no isoenergetic cluster move has run on these replicas yet");
     TRY(use_device(s->g->device));
     std::vector<uint32_t> h;
     TRY(read_back(s, h, s->d_icm_stats, 3 * s->icm_stats_cap));
     for (size_t p = 0; p < pairs; p++) {
-        n_clusters_out[p] = h[2 * p];
-        largest_out[p] = h[2 * p + 1];
-        minus_sites_out[p] = h[2 * s->icm_stats_cap + p];
+        n_clusters_out[p] = h[2 * (slot0 + p)];
+        largest_out[p] = h[2 * (slot0 + p) + 1];
+        minus_sites_out[p] = h[2 * s->icm_stats_cap + slot0 + p];
     }
     return ISINGMC_OK;
 }
 
 static bool is_icm_step(const isingmc_states *s) { return s->icm_every && s->t % s->icm_every == s->icm_every - 1; }
+
+// the same on a replica-packed container of either family: batches of whole replica groups, 16 pairs each; pair j
+// of GLOBAL group G moves when both its experiments exist (32 G + 2 j + 1 < n_total), owned by this shard or not
+static int run_icm_packed(StepRun &c)
+{
+    isingmc_states *s = c.s;
+    const isingmc_graph *g = s->g;
+    const size_t groups = s->groups, pair_slots = 16 * groups, n_pos = g->pk.n_pos;
+    if (!c.pk_icm.labels) {
+        const size_t words = pk_icm_words_per_group(n_pos);
+        c.cl_batch = std::min<size_t>({groups, size_t(32768), std::max<size_t>(1, size_t(std::max(1, s->opt.cluster_workspace_bytes)) / (words * sizeof(uint32_t)))});
+        uint32_t *block = nullptr;
+        TRY(c.scratch.alloc(&block, c.cl_batch * words));
+        c.pk_icm.labels = block;
+        c.pk_icm.sizes = c.pk_icm.labels + c.cl_batch * n_pos * 16;
+        c.pk_icm.fliptab = c.pk_icm.sizes + c.cl_batch * n_pos * 16;
+        c.h_icm_mask.resize(groups);
+        const size_t G0 = s->first / 32;
+        for (size_t gi = 0; gi < groups; gi++) {
+            uint32_t m = 0;
+            for (size_t j = 0; j < 16; j++)
+                if (32 * (G0 + gi) + 2 * j + 1 < s->n_total) m |= 1u << (2 * j);
+            c.h_icm_mask[gi] = m;
+        }
+        TRY(c.scratch.alloc(&c.d_icm_mask, groups));
+        HIP_TRY(hipMemcpyAsync(c.d_icm_mask, c.h_icm_mask.data(), groups * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream)); // (h_icm_mask lives as long as the call)
+    }
+    if (s->icm_stats_cap < pair_slots) { // (the groups of a packed container are fixed for its life: allocated once)
+        HIP_TRY(stream_quiesce(s->stream));
+        if (s->d_icm_stats) HIP_TRY(cached_free(s->d_icm_stats));
+        s->d_icm_stats = nullptr;
+        s->icm_stats_cap = 0;
+        TRY(dev_alloc(&s->d_icm_stats, 3 * pair_slots));
+        s->icm_stats_cap = pair_slots;
+    }
+    HIP_TRY(hipMemsetAsync(s->d_icm_stats, 0, 3 * s->icm_stats_cap * sizeof(uint32_t), s->stream));
+    for (size_t g0 = 0; g0 < groups; g0 += c.cl_batch) {
+        const size_t n = std::min(c.cl_batch, groups - g0);
+        HIP_TRY(pk_icm_launch_step(s->stream, s->d_state + g0 * n_pos, g->pk, s->rj ? g->rj.nbr : nullptr, s->rj ? g->rj.slots : 0, s->t, s->d_keys + g0,
+                                   c.d_icm_mask + g0, c.pk_icm, uint32_t(n), s->d_icm_stats + 2 * 16 * g0, s->d_icm_stats + 2 * s->icm_stats_cap + 16 * g0));
+    }
+    s->icm_have_stats = true;
+    s->t++;
+    if (c.d_counts) TRY(measure_enqueue(s, c.d_counts, nullptr, nullptr, /*want_up=*/false)); // the energy after this timestep: step 0 of the chunk
+    return ISINGMC_OK;
+}
 
 // timestep s->t as an isoenergetic cluster move of every pair, batch by batch on the main stream; a last replica without a
 // partner stays as it is
@@ -1700,6 +1757,7 @@ static int run_icm(StepRun &c)
     const isingmc_graph *g = s->g;
     const size_t pairs = s->R / 2;
     if (s->n_lanes > 1) TRY(lanes_join(s)); // the Metropolis stretch before this step may have run on replica lanes
+    if (s->packed) return run_icm_packed(c);
     if (pairs && !c.cl.labels) { // one labelling problem per PAIR
         const size_t words = cluster_words_per_replica(g->nvars);
         c.cl_batch = std::min<size_t>({pairs, size_t(32768), std::max<size_t>(1, size_t(std::max(1, s->opt.cluster_workspace_bytes)) / (words * sizeof(uint32_t)))});
