@@ -284,10 +284,13 @@ int isingmc_icm_stats(isingmc_states *states, uint64_t *n_clusters_out, uint64_t
  *   both NULL: both containers carry a tempering ladder of their own (isingmc_pt_attach with world size 1, slot offset 0, one
  *     slot per rung) over bitwise equal betas, n_pairs = the number of rungs, and pair r = (a's slot at rung r, b's slot at rung
  *     r): the kernels read the two permutations on the device.
- * Refused with ISINGMC_ERR_INVALID and a message (both containers stay as they were): a == b, two graph handles, a graph that
- * is not a checkerboard lattice isingmc_states_set_icm_every accepts (general-graph families, the replica-packed ones
- * included; fields, open boundaries, anisotropic couplings, W H >=
- * 2^32 - 1), unequal timesteps, Swendsen-Wang steps or isoenergetic cluster moves switched on inside either container, unequal
+ * Served: two checkerboard containers (S10), or two replica-packed containers of ONE family, bit-sliced or real-coupling
+ * (DESIGN.md S13): there slot s is bit (first + s) % 32 of its replica group, the key of a's GLOBAL group and the global bit of
+ * a's slot draw the flip bits, and slots in no pair -- the bits a container does not own included -- stay as they were.
+ * Refused with ISINGMC_ERR_INVALID and a message (both containers stay as they were): a == b, two graph handles, a container
+ * on the f64 CSR general-graph family, two containers on different replica-packed families, a checkerboard lattice
+ * isingmc_states_set_icm_every does not accept (fields, open boundaries, anisotropic couplings, W H >= 2^32 - 1), unequal
+ * timesteps, Swendsen-Wang steps or isoenergetic cluster moves switched on inside either container, unequal
  * pair betas, slots out of range or used twice, the NULL form without two matching ladders. */
 int isingmc_icm_between(isingmc_states *a, isingmc_states *b, const uint32_t *slots_a, const uint32_t *slots_b, size_t n_pairs);
 /* the last isingmc_icm_between call with `a` as its first container, per pair in the order of the call: as isingmc_icm_stats,

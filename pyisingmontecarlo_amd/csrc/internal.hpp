@@ -29,6 +29,7 @@
 #include "general_kernels.hpp"
 #include "host_logic.hpp"
 #include "lattice_kernels.hpp"
+#include "packed_between_kernels.hpp"
 #include "packed_cluster_kernels.hpp"
 #include "packed_icm_kernels.hpp"
 #include "packed_kernels.hpp"
@@ -285,8 +286,10 @@ struct isingmc_states {
     bool icm_have_stats = false;
     // isoenergetic cluster moves between this container and another one (isingmc_icm_between): everything below
     // belongs to the FIRST container of the call and stays with it, so that a call only enqueues
-    uint32_t *d_icmb_work = nullptr;  // labelling workspace of icmb_batch pairs (cluster_words_per_replica each)
-    size_t icmb_batch = 0;
+    uint32_t *d_icmb_work = nullptr;  // labelling workspace of icmb_batch pairs (cluster_words_per_replica each); packed containers
+    size_t icmb_batch = 0;            // (DESIGN.md S13): of icmb_batch pair BLOCKS (pk_between_words_per_block each)
+    uint32_t *d_icmb_inv = nullptr;   // packed containers: (local group, bit) -> pair of the call, this container's groups first,
+    size_t icmb_inv_cap = 0;          // then the other one's (words)
     uint32_t *d_icmb_slots = nullptr; // [2][icmb_cap] slot tables of the host-table form
     uint32_t *d_icmb_stats = nullptr; // [icmb_cap][2] clusters, largest cluster, then [icmb_cap] q = -1 sites: the last call
     size_t icmb_cap = 0, icmb_pairs = 0;
@@ -312,7 +315,7 @@ struct isingmc_states {
         if (d_thr_mc) (void)cached_free(d_thr_mc);
         if (d_cl_stats) (void)cached_free(d_cl_stats);
         if (d_icm_stats) (void)cached_free(d_icm_stats);
-        for (void *p : {(void *)d_icmb_work, (void *)d_icmb_slots, (void *)d_icmb_stats})
+        for (void *p : {(void *)d_icmb_work, (void *)d_icmb_slots, (void *)d_icmb_stats, (void *)d_icmb_inv})
             if (p) (void)cached_free(p);
         for (auto ev : icmb_ev) pooled_event_destroy(ev, true);
         for (int b = 0; b < 2; b++) {

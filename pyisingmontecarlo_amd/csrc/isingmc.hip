@@ -1792,7 +1792,8 @@ static int run_icm(StepRun &c)
 // ------------------------------------------------------------------------------------------------
 // Isoenergetic cluster moves between two containers (cluster_kernels.hip): the move of S9 with pair p =
 // (slot slots_a[p] of a, slot slots_b[p] of b) -- what two tempering ladders over the same betas need, whose rung permutations
-// live on the device
+// live on the device.  Two replica-packed containers of one family take the same call in the form of DESIGN.md S13
+// (packed_between_kernels.hip)
 // ------------------------------------------------------------------------------------------------
 
 // why these two containers cannot take a move between them ("" when they can): icm_obstacle without its ladder and shard clauses
@@ -1801,18 +1802,101 @@ static std::string icm_between_obstacle(const isingmc_states *a, const isingmc_s
     if (a == b) return "an isoenergetic cluster move between two containers needs two different containers";
     if (a->g != b->g) return "the two containers belong to different graph handles: both must be replicas of one isingmc_graph";
     const isingmc_graph *g = a->g; // (one graph handle: one device)
-    if (g->kind != ISINGMC_KIND_LATTICE2D || a->packed || b->packed)
-        return "isoenergetic cluster moves need containers on the checkerboard lattice path; this graph runs on a general-graph kernel family";
-    if (g->mc_mode == MC_FIELD || g->mc_mode == MC_FIELD_OPEN) return "isoenergetic cluster moves are not implemented for lattices with a field";
-    if (g->mc_mode == MC_OPEN) return "isoenergetic cluster moves are not implemented for open boundaries (periodic lattices only)";
-    if (g->mc_mode != MC_NONE) return "isoenergetic cluster moves are not implemented for anisotropic couplings (|Jx| != |Jy|)";
-    if (g->nvars >= 0xFFFFFFFFull) return "isoenergetic cluster moves label sites with 32 bits: W H must be below 2^32 - 1";
+    if (a->packed && b->packed) { // S13: any graph of either packed family, both containers on the same one
+        if (a->rj != b->rj)
+            return "the two containers run on different kernel families (one on the replica-packed bit-sliced family, the other on the "
+                   "replica-packed real-coupling family): a move between containers needs both on the same family";
+    } else {
+        if (g->kind != ISINGMC_KIND_LATTICE2D || a->packed || b->packed)
+            return "isoenergetic cluster moves need containers on the checkerboard lattice path; this graph runs on a general-graph kernel family";
+        if (g->mc_mode == MC_FIELD || g->mc_mode == MC_FIELD_OPEN) return "isoenergetic cluster moves are not implemented for lattices with a field";
+        if (g->mc_mode == MC_OPEN) return "isoenergetic cluster moves are not implemented for open boundaries (periodic lattices only)";
+        if (g->mc_mode != MC_NONE) return "isoenergetic cluster moves are not implemented for anisotropic couplings (|Jx| != |Jy|)";
+        if (g->nvars >= 0xFFFFFFFFull) return "isoenergetic cluster moves label sites with 32 bits: W H must be below 2^32 - 1";
+    }
     for (const isingmc_states *s : {a, b}) {
         if (s->cluster_every) return "Swendsen-Wang cluster updates are switched on for one of the containers (isingmc_states_set_cluster_every): one non-local move at a time";
         if (s->icm_every) return "isoenergetic cluster moves inside one of the containers are switched on (isingmc_states_set_icm_every): one non-local move at a time";
     }
     if (a->t != b->t) return "the two containers stand at unequal timesteps: the move is timestep t of both";
     return "";
+}
+
+// the move between two replica-packed containers of one family (packed_between_kernels.hip) behind the checks of
+// isingmc_icm_between: batches of whole pair blocks (32 pairs each) under a's cluster_workspace_bytes.  slots_a == nullptr: the
+// two ladders' permutations on the device.
+static int icm_between_packed(isingmc_states *a, isingmc_states *b, const uint32_t *slots_a, const uint32_t *slots_b, size_t n_pairs)
+{
+    const isingmc_graph *g = a->g;
+    const size_t n_pos = g->pk.n_pos, blocks = (n_pairs + 31) / 32;
+    // workspace, tables, statistics and events stay with `a`: nothing below waits for the device unless one of them grows
+    const size_t words = pk_between_words_per_block(n_pos);
+    const size_t batch = std::min<size_t>({blocks, size_t(32768), std::max<size_t>(1, size_t(std::max(1, a->opt.cluster_workspace_bytes)) / (words * sizeof(uint32_t)))});
+    if (!a->d_icmb_work || a->icmb_batch != batch) {
+        HIP_TRY(stream_quiesce(a->stream)); // the old block is recycled
+        if (a->d_icmb_work) HIP_TRY(cached_free(a->d_icmb_work));
+        a->d_icmb_work = nullptr;
+        a->icmb_batch = 0;
+        TRY(dev_alloc(&a->d_icmb_work, batch * words));
+        a->icmb_batch = batch;
+    }
+    const size_t inv_words = 32 * (a->groups + b->groups);
+    if (a->icmb_inv_cap < inv_words) {
+        HIP_TRY(stream_quiesce(a->stream));
+        if (a->d_icmb_inv) HIP_TRY(cached_free(a->d_icmb_inv));
+        a->d_icmb_inv = nullptr;
+        a->icmb_inv_cap = 0;
+        TRY(dev_alloc(&a->d_icmb_inv, inv_words));
+        a->icmb_inv_cap = inv_words;
+    }
+    if (a->icmb_cap < n_pairs) {
+        HIP_TRY(stream_quiesce(a->stream));
+        for (uint32_t **p : {&a->d_icmb_slots, &a->d_icmb_stats}) {
+            if (*p) HIP_TRY(cached_free(*p));
+            *p = nullptr;
+        }
+        a->icmb_cap = 0;
+        a->icmb_have_stats = false;
+        const size_t cap = std::max(n_pairs, a->cap);
+        TRY(dev_alloc(&a->d_icmb_slots, 2 * cap));
+        TRY(dev_alloc(&a->d_icmb_stats, 3 * cap));
+        a->icmb_cap = cap;
+    }
+    for (hipEvent_t &ev : a->icmb_ev)
+        if (!ev) HIP_TRY(pooled_event_create(&ev, true));
+    PkBetweenWork work;
+    work.labels = a->d_icmb_work;
+    work.sizes = work.labels + batch * n_pos * 32;
+    work.d = work.sizes + batch * n_pos * 32;
+    work.f = work.d + batch * n_pos;
+    work.fliptab = work.f + batch * n_pos;
+    const uint32_t *d_sa = a->d_pt_perm, *d_sb = b->d_pt_perm;
+    if (slots_a) {
+        HIP_TRY(hipMemcpyAsync(a->d_icmb_slots, slots_a, n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, a->stream));
+        HIP_TRY(hipMemcpyAsync(a->d_icmb_slots + a->icmb_cap, slots_b, n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, a->stream));
+        d_sa = a->d_icmb_slots;
+        d_sb = a->d_icmb_slots + a->icmb_cap;
+    }
+    const PkBetweenSide A{a->d_state, d_sa, a->d_icmb_inv, uint32_t(a->pk_bit0), uint32_t(a->R), uint32_t(a->groups)};
+    const PkBetweenSide B{b->d_state, d_sb, a->d_icmb_inv + 32 * a->groups, uint32_t(b->pk_bit0), uint32_t(b->R), uint32_t(b->groups)};
+    HIP_TRY(hipEventRecord(a->icmb_ev[0], b->stream)); // b's sweeps and exchange rounds so far ...
+    HIP_TRY(hipStreamWaitEvent(a->stream, a->icmb_ev[0], 0)); // ... before a's stream touches b's words and permutation
+    HIP_TRY(hipMemsetAsync(a->d_icmb_stats, 0, 3 * a->icmb_cap * sizeof(uint32_t), a->stream));
+    HIP_TRY(pk_between_launch_tables(a->stream, A, B, uint32_t(n_pairs)));
+    for (size_t b0 = 0; b0 < blocks; b0 += batch) {
+        const size_t n = std::min(batch, blocks - b0);
+        HIP_TRY(pk_between_launch_batch(a->stream, A, B, g->pk, a->rj ? g->rj.nbr : nullptr, a->rj ? g->rj.slots : 0, a->t, a->d_keys, work, uint32_t(b0),
+                                        uint32_t(n), uint32_t(n_pairs), a->d_icmb_stats, a->d_icmb_stats + 2 * a->icmb_cap));
+    }
+    HIP_TRY(hipEventRecord(a->icmb_ev[1], a->stream));
+    HIP_TRY(hipStreamWaitEvent(b->stream, a->icmb_ev[1], 0)); // b goes on with the new configurations
+    a->icmb_pairs = n_pairs;
+    a->icmb_have_stats = true;
+    for (isingmc_states *s : {a, b}) {
+        s->t++;
+        s->meas_fresh = false; // cached ladder energies belong to the configurations before the move
+    }
+    return ISINGMC_OK;
 }
 
 extern "C" int isingmc_icm_between(isingmc_states *a, isingmc_states *b, const uint32_t *slots_a, const uint32_t *slots_b, size_t n_pairs)
@@ -1858,6 +1942,7 @@ extern "C" int isingmc_icm_between(isingmc_states *a, isingmc_states *b, const u
     }
     for (isingmc_states *s : {a, b})
         if (s->n_lanes > 1) TRY(lanes_join(s));
+    if (a->packed) return icm_between_packed(a, b, slots_a, slots_b, n_pairs);
     // workspace, tables, statistics and events stay with `a`: nothing below waits for the device unless one of them grows
     const size_t words = cluster_words_per_replica(g->nvars);
     const size_t batch = std::min<size_t>({n_pairs, size_t(32768), std::max<size_t>(1, size_t(std::max(1, a->opt.cluster_workspace_bytes)) / (words * sizeof(uint32_t)))});

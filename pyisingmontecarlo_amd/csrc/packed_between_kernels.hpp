@@ -1,0 +1,51 @@
+// Isoenergetic cluster move between two replica-packed containers of one family: pair n is slot slots_a[n] of
+// container a and slot slots_b[n] of container b -- arbitrary bits of arbitrary words of two state arrays.  The work is organised
+// in PAIR BLOCKS of 32 pairs (pair 32 B + i = bit i of block B), which gives the [block][position][32] label layout of S11.  Like
+// S12 the move reads no coupling and no bias: one set of kernels, templated on the neighbour accessor (packed_nbr.hpp), serves both
+// families.  Launch interface of packed_between_kernels.hip (a translation unit of its own: nothing here is instantiated beside the
+// tuned sweep kernels).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstddef>
+#include <cstdint>
+
+#include "packed_types.hpp"
+
+namespace isingmc {
+
+constexpr uint32_t DOM_PK_BETWEEN_FLIP = 0x504B4246u; // "PKBF"
+constexpr uint32_t PKB_NO_PAIR = 0xFFFFFFFFu;
+
+// workspace of one batch of n pair blocks (n_pos positions each)
+struct PkBetweenWork {
+    uint32_t *labels;  // [n][n_pos][32]       (position, pair lane) -> a smaller position of its cluster (the root: the smallest)
+    uint32_t *sizes;   // [n][n_pos][32]       d = 1 positions per root
+    uint32_t *d;       // [n][n_pos]           overlap words: bit i set where the two replicas of pair lane i differ
+    uint32_t *f;       // [n][n_pos]           flip words: bit i set where pair lane i swaps its two spins
+    uint32_t *fliptab; // [n][32][n_pos / 32]  one flip bit per (pair lane, possible root position)
+};
+
+constexpr size_t pk_between_words_per_block(uint64_t n_pos) { return size_t(67 * n_pos); }
+
+// one of the two containers as the kernels see it
+struct PkBetweenSide {
+    uint32_t *state;       // [groups][n_pos]
+    const uint32_t *slots; // [n_pairs] slot of every pair (a device table: the host's copy or a ladder's rung permutation)
+    uint32_t *inv;         // [groups][32] pair of every (local group, bit), PKB_NO_PAIR where none (pk_between_launch_tables)
+    uint32_t bit0;         // slot s is bit (bit0 + s) & 31 of local group (bit0 + s) >> 5
+    uint32_t n_slots;      // slots owned (a table entry at or beyond it names no pair: nothing is read or written for it)
+    uint32_t groups;
+};
+
+// the bit -> pair tables of both sides, once per move
+hipError_t pk_between_launch_tables(hipStream_t stream, const PkBetweenSide &a, const PkBetweenSide &b, uint32_t n_pairs);
+
+// Pair blocks [block0, block0 + n_blocks) of a move of n_pairs pairs at timestep t.  nbr_rj == nullptr: the neighbours of
+// G.nbr_ell (PK_MAX_DEG slots); else nbr_rj[slot][n_pos] with rj_slots slots.  a_keys: the group keys of a's local groups.
+// stats: [n_pairs][2] = {clusters, largest cluster}, minus: [n_pairs] = positions where the pair differs; zero on entry.
+// n_blocks <= 32768.
+hipError_t pk_between_launch_batch(hipStream_t stream, const PkBetweenSide &a, const PkBetweenSide &b, const PkGraphDev &G, const uint32_t *nbr_rj,
+                                   uint32_t rj_slots, uint64_t t, const uint2 *a_keys, const PkBetweenWork &work, uint32_t block0, uint32_t n_blocks,
+                                   uint32_t n_pairs, uint32_t *stats, uint32_t *minus);
+
+} // namespace isingmc

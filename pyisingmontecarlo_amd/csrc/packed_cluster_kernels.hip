@@ -166,4 +166,10 @@ hipError_t pk_cluster_launch_step(hipStream_t stream, uint32_t *state, const PkG
     return hipGetLastError();
 }
 
+hipError_t pk_cluster_launch_max(hipStream_t stream, uint32_t n_pos, const uint32_t *sizes, uint32_t n, uint32_t *stats)
+{
+    hipLaunchKernelGGL(pkc_max_kernel, dim3(std::min(n_pos / 8, 1024u), n), dim3(256), 0, stream, n_pos, sizes, stats);
+    return hipGetLastError();
+}
+
 } // namespace isingmc

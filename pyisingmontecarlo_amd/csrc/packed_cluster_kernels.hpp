@@ -32,4 +32,8 @@ constexpr size_t pk_cluster_words_per_group(uint64_t n_pos) { return size_t((64 
 hipError_t pk_cluster_launch_step(hipStream_t stream, uint32_t *state, const PkGraphDev &G, uint64_t t, const uint2 *group_keys, uint64_t thr,
                                   const uint64_t *thr_per_slot, const PkClusterWork &work, uint32_t n, uint32_t *stats);
 
+// The last launch of the step on its own, for any sizes[n][n_pos][32] (S13's pair blocks have this layout): stats[2 (32 g + b) + 1]
+// = max over p of sizes[g][p][b]; entries whose maximum is 0 are not written.
+hipError_t pk_cluster_launch_max(hipStream_t stream, uint32_t n_pos, const uint32_t *sizes, uint32_t n, uint32_t *stats);
+
 } // namespace isingmc

@@ -19,6 +19,7 @@
 
 #include "cluster_union.hpp"
 #include "packed_cluster_kernels.hpp"
+#include "packed_nbr.hpp"
 #include "philox.hpp"
 
 namespace isingmc {
@@ -27,25 +28,6 @@ namespace {
 
 constexpr uint32_t PKI_FLIP_POS = 128;         // positions per workgroup of pki_flip_kernel (n_pos is a multiple of 256)
 constexpr int AGENT = __HIP_MEMORY_SCOPE_AGENT;
-
-// neighbour accessors: position of the neighbour in adjacency slot k of position p when p owns that bond (the neighbour's
-// position is above p), else 0 (never above p)
-struct PkNbr { // bit-sliced family: PK_MAX_DEG slots, PK_NO_NBR in unused ones, the coupling's sign in bit 31
-    const uint32_t *nbr_ell;
-    uint32_t n_pos;
-    __device__ __forceinline__ uint32_t slots() const { return uint32_t(PK_MAX_DEG); }
-    __device__ __forceinline__ uint32_t operator()(uint32_t k, uint32_t p) const
-    {
-        const uint32_t x = nbr_ell[size_t(k) * n_pos + p];
-        return x == PK_NO_NBR ? 0u : x & 0x7FFFFFFFu;
-    }
-};
-struct RjNbr { // real-coupling family: n_slots slots, the own position in unused ones
-    const uint32_t *nbr;
-    uint32_t n_pos, n_slots;
-    __device__ __forceinline__ uint32_t slots() const { return n_slots; }
-    __device__ __forceinline__ uint32_t operator()(uint32_t k, uint32_t p) const { return nbr[size_t(k) * n_pos + p]; }
-};
 
 // per-pair combination of the 16 position-lanes of a workgroup (lane & 15 = pair) -> threads 0..15
 template <typename OP>

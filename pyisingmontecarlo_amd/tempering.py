@@ -61,7 +61,9 @@ class ClassicalTempering:
 
         copies=2: two ladders over the same betas on one device, for isoenergetic cluster moves between the two
         configurations at every rung (set_replica_cluster_update_every).  Copy 0 is the ladder copies=1 would build; copy 1 is
-        the ladder of the seed `seed ^ COPY_SEED_XOR`.  Single process, single device only."""
+        the ladder of the seed `seed ^ COPY_SEED_XOR`.  Single process, single device only.  Served: periodic field-free 2-D
+        lattices, and every graph whose containers run on a replica-packed family -- with ISINGMC_FORCE_PACKED=1,
+        the stable-path flag or a large enough graph that is the 3-d +-J glass and every Gaussian glass."""
         self._ea, self._eb, self._ej = _split(edges)
         if copies not in (1, 2):
             raise ValueError("copies must be 1 or 2")
@@ -166,7 +168,9 @@ class ClassicalTempering:
     # -------------------------------------------------------------------------------------------
     def set_replica_cluster_update_every(self, k):
         """copies=2 only, before the first timestep: with k > 0 ladder timestep t is an isoenergetic cluster move between the two
-        configurations at every rung iff t % k == k - 1, in place of that timestep's sweep; 0 switches it off."""
+        configurations at every rung (S13 on the replica-packed general-graph families) iff t % k == k - 1, in
+        place of that timestep's sweep; 0 switches it off.  A graph whose containers run on the f64 CSR family is refused at the
+        first move ("general-graph kernel family")."""
         if self._pair is None:
             raise ValueError("replica cluster updates need two configurations per temperature: build the ladder with copies=2")
         if self._states is not None:
