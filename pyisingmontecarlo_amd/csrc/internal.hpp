@@ -84,6 +84,14 @@ IM_INTERNAL int env_int(const char *name, int dflt);
 // the object it wants to steer.  (Measurement / A-B switches and test hooks; none of them changes a result, only which kernel
 // produces it -- except FORCE / DISABLE of a kernel FAMILY, which select another spec: DESIGN.md section 2.)
 // ------------------------------------------------------------------------------------------------
+// an option's name as the table below holds it: lower case, without the ISINGMC_ prefix
+inline std::string option_bare_name(const std::string &name)
+{
+    std::string n;
+    for (char c : name) n += char(std::tolower(static_cast<unsigned char>(c)));
+    return n.rfind("isingmc_", 0) == 0 ? n.substr(8) : n;
+}
+
 struct Options {
     int force_real = 0, disable_real = 0, force_packed = 0, disable_packed = 0; // kernel family (decided at creation)
     int disable_packed_uniform = 0, disable_resident = 0;
@@ -124,9 +132,7 @@ struct Options {
     // name: the environment variable's name without the ISINGMC_ prefix, lower or upper case
     bool set(const std::string &name_in, long value)
     {
-        std::string n;
-        for (char c : name_in) n += char(std::tolower(static_cast<unsigned char>(c)));
-        if (n.rfind("isingmc_", 0) == 0) n = n.substr(8);
+        const std::string n = option_bare_name(name_in);
         const std::pair<const char *, int *> table[] = {
             {"force_real", &force_real}, {"disable_real", &disable_real}, {"force_packed", &force_packed}, {"disable_packed", &disable_packed},
             {"disable_packed_uniform", &disable_packed_uniform}, {"disable_resident", &disable_resident}, {"strip", &strip},

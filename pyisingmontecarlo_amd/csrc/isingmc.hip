@@ -218,8 +218,9 @@ extern "C" int isingmc_states_set_option(isingmc_states *s, const char *name, lo
 {
     if (!s || !name) return fail(ISINGMC_ERR_INVALID, "NULL argument");
     const std::string n(name);
+    const std::string bare = option_bare_name(n); // as Options::set reads it
     for (const char *family : {"force_real", "disable_real", "force_packed", "disable_packed"})
-        if (n.find(family) != std::string::npos && (n.size() == std::strlen(family) || n.size() == std::strlen(family) + 8))
+        if (bare == family) // (the whole name: "disable_packed_uniform" is a switch of its own, eight characters longer)
             return fail(ISINGMC_ERR_INVALID, "the kernel family of a container is fixed when it is created (set ISINGMC_" + std::string(family) +
                                                  " in the environment before isingmc_states_create)");
     if (!s->opt.set(n, value)) return fail(ISINGMC_ERR_INVALID, "unknown option '" + n + "'");
