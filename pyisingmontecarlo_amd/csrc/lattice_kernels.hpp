@@ -249,28 +249,52 @@ __device__ __forceinline__ void load_signs(const uint32_t *__restrict__ jn, cons
     }
 }
 
-template <bool PMJ>
-__device__ __forceinline__ void quad_classes(const uint32_t own[4], const QuadNbr &n, const uint32_t widx[4], const LatGeom &g,
-                                             const ThrBits &tb, const QuadSigns &js, const uint32_t jneg_uniform,
-                                             QuadState &st)
+// class masks of one word from the pairwise sums / carries of its four bond masks a0..a3 (s01 = a0 ^ a1, c01 = a0 & a1, ...)
+__device__ __forceinline__ void class_masks(const uint32_t s01, const uint32_t c01, const uint32_t s23, const uint32_t c23,
+                                            uint32_t &eq3, uint32_t &eq4)
 {
+    eq4 = c01 & c23;
+    eq3 = __builtin_amdgcn_bitop3_b32(c01, s23, c23 & s01, 0xEA); // (c01 & s23) | (c23 & s01)
+    // pin the two class masks in registers: hipcc otherwise re-derives them from the bond masks inside
+    // every plane (7 instead of 5 instructions per word and plane)
+    asm("" : "+v"(eq3), "+v"(eq4));
+}
+
+template <bool PMJ>
+__device__ __forceinline__ void quad_classes(const uint32_t own[4], const QuadNbr &n, const ThrBits &tb, const QuadSigns &js,
+                                             const uint32_t jneg_uniform, QuadState &st)
+{
+    if constexpr (PMJ) {
 #pragma unroll
-    for (int q = 0; q < 4; q++) {
-        uint32_t a0, a1, a2, a3;
-        if constexpr (PMJ) { // jneg planes hold 1 where J < 0: satisfied = own ^ neighbour ^ jneg
-            a0 = own[q] ^ n.up[q] ^ js.w[q][0];
-            a1 = own[q] ^ n.dn[q] ^ js.w[q][1];
-            a2 = own[q] ^ n.ce[q] ^ js.w[q][2];
-            a3 = own[q] ^ n.si[q] ^ js.w[q][3];
-        } else {
-            bond_masks<false>(own[q], n, q, nullptr, g.wpp, widx[q], jneg_uniform, a0, a1, a2, a3);
+        for (int q = 0; q < 4; q++) { // jneg planes hold 1 where J < 0: satisfied = own ^ neighbour ^ jneg
+            const uint32_t a0 = own[q] ^ n.up[q] ^ js.w[q][0];
+            const uint32_t a1 = own[q] ^ n.dn[q] ^ js.w[q][1];
+            const uint32_t a2 = own[q] ^ n.ce[q] ^ js.w[q][2];
+            const uint32_t a3 = own[q] ^ n.si[q] ^ js.w[q][3];
+            class_masks(a0 ^ a1, a0 & a1, a2 ^ a3, a2 & a3, st.eq3[q], st.eq4[q]);
         }
-        const uint32_t s01 = a0 ^ a1, c01 = a0 & a1, s23 = a2 ^ a3, c23 = a2 & a3;
-        st.eq4[q] = c01 & c23;
-        st.eq3[q] = __builtin_amdgcn_bitop3_b32(c01, s23, c23 & s01, 0xEA); // (c01 & s23) | (c23 & s01)
-        // pin the two class masks in registers: hipcc otherwise re-derives them from the bond masks inside
-        // every plane (7 instead of 5 instructions per word and plane)
-        asm("" : "+v"(st.eq3[q]), "+v"(st.eq4[q]));
+    } else {
+        // One sign for the whole graph (jneg_uniform is 0 or ~0, in an SGPR): the bond masks a_i = own ^ neighbour ^ sign are
+        // never formed.  a0 ^ a1 = up ^ dn and a2 ^ a3 = ce ^ si hold neither `own` nor the sign, and a0 & a1, a2 & a3 are
+        // 3-input functions of (own, up, dn) / (own, ce, si) whose truth table the sign picks: (o ^ u) & (o ^ d) = 0x18,
+        // ~(o ^ u) & ~(o ^ d) = 0x81.  ONE scalar branch per quad selects the table -- 7 instead of 9 vector instructions per
+        // word, none of them with a scalar source.
+        uint32_t c01[4], c23[4];
+        if (jneg_uniform) {
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                c01[q] = __builtin_amdgcn_bitop3_b32(own[q], n.up[q], n.dn[q], 0x81);
+                c23[q] = __builtin_amdgcn_bitop3_b32(own[q], n.ce[q], n.si[q], 0x81);
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                c01[q] = __builtin_amdgcn_bitop3_b32(own[q], n.up[q], n.dn[q], 0x18);
+                c23[q] = __builtin_amdgcn_bitop3_b32(own[q], n.ce[q], n.si[q], 0x18);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 4; q++) class_masks(n.up[q] ^ n.dn[q], c01[q], n.ce[q] ^ n.si[q], c23[q], st.eq3[q], st.eq4[q]);
     }
     if (tb.any_all) { // threshold 2^THR_BITS (beta = 0 ...): the class flips outright, like k <= 2; scalar branch, rarely taken
 #pragma unroll
@@ -470,29 +494,29 @@ __device__ __forceinline__ void quad_ties(const QuadState &st, const uint32_t Q,
 
 // The 128 flip decisions of quad Q from its loaded words: acc[q] bit b = 1 where the spin flips.
 template <bool PMJ>
-__device__ __forceinline__ void quad_flips(const uint32_t own[4], const QuadNbr &n, const uint32_t widx[4], const LatGeom &g,
-                                           const uint32_t colour, const uint64_t t, const uint2 key, const PhiloxVKeys &vk,
+__device__ __forceinline__ void quad_flips(const uint32_t own[4], const QuadNbr &n, const uint32_t colour, const uint64_t t,
+                                           const uint2 key, const PhiloxVKeys &vk,
                                            const LatThr thr, const QuadSigns &js, const uint32_t jneg_uniform,
                                            const uint32_t Q, uint32_t acc[4])
 {
     const ThrBits tb = thr_bits(thr);
     QuadState st[1];
     const uint32_t Qs[1] = {Q};
-    quad_classes<PMJ>(own, n, widx, g, tb, js, jneg_uniform, st[0]);
+    quad_classes<PMJ>(own, n, tb, js, jneg_uniform, st[0]);
     quad_planes<1>(st, Qs, colour, t, key, vk, tb);
     quad_ties(st[0], Q, colour, t, key, vk, tb, acc);
 }
 
 // the same decisions from random words drawn earlier (quad_random)
 template <bool PMJ>
-__device__ __forceinline__ void quad_flips_pre(const uint32_t own[4], const QuadNbr &n, const uint32_t widx[4], const LatGeom &g,
-                                               const uint32_t colour, const uint64_t t, const uint2 key, const PhiloxVKeys &vk,
+__device__ __forceinline__ void quad_flips_pre(const uint32_t own[4], const QuadNbr &n, const uint32_t colour, const uint64_t t,
+                                               const uint2 key, const PhiloxVKeys &vk,
                                                const LatThr thr, const QuadSigns &js, const uint32_t jneg_uniform, const uint32_t Q,
                                                const QuadRandom &R, uint32_t acc[4])
 {
     const ThrBits tb = thr_bits(thr);
     QuadState st;
-    quad_classes<PMJ>(own, n, widx, g, tb, js, jneg_uniform, st);
+    quad_classes<PMJ>(own, n, tb, js, jneg_uniform, st);
 #pragma unroll
     for (int p = N_PLANES - 1; p >= 0; p--) plane_step(st, R.rr[p], p, tb);
     quad_ties(st, Q, colour, t, key, vk, tb, acc, &R.tie);
@@ -614,15 +638,14 @@ __device__ __forceinline__ void update_quad(const Mem &mem, const LatGeom &g, co
         QuadSigns js;
         load_quad_uni(mem, g, colour, gid, Q, vQ, own, n);
         load_signs<PMJ>(jn, g, Q, js);
-        const uint32_t widx[4] = {4 * Q, 4 * Q + 1, 4 * Q + 2, 4 * Q + 3};
-        quad_flips<PMJ>(own, n, widx, g, colour, t, key, vk, thr, js, jneg_uniform, Q, acc);
+        quad_flips<PMJ>(own, n, colour, t, key, vk, thr, js, jneg_uniform, Q, acc);
         if constexpr (MEASURE) {
             // NOT stored here: the vector store (buffer_store_dwordx4 with a register offset) reads its four data registers
             // some cycles after it issues, the compiler's hazard model inserts no wait state for that form, and the counting
             // below would overwrite them at once -- on a loaded chip a word of the quad then arrived in memory as a bit
             // count (wrong spins from ~1500 workgroups per launch on; round 3).  The kernel stores as its last instruction.
 #pragma unroll
-            for (int q = 0; q < 4; q++) { pending->w[q] = own[q] ^ acc[q]; pending->widx[q] = widx[q]; }
+            for (int q = 0; q < 4; q++) { pending->w[q] = own[q] ^ acc[q]; pending->widx[q] = 4 * Q + q; }
             quad_measure<PMJ>(pending->w, n, js, jneg_uniform, *sat, *up);
         } else {
             __builtin_amdgcn_raw_buffer_store_b128(u32x4{own[0] ^ acc[0], own[1] ^ acc[1], own[2] ^ acc[2], own[3] ^ acc[3]}, mem.rsrc,
@@ -638,7 +661,7 @@ __device__ __forceinline__ void update_quad(const Mem &mem, const LatGeom &g, co
     QuadSigns js;
     load_signs<PMJ>(jn, g, Q, js);
     load_quad<VEC, UNI>(mem, g, colour, Q, qy, qxw, own, n, widx);
-    quad_flips<PMJ>(own, n, widx, g, colour, t, key, vk, thr, js, jneg_uniform, Q, acc);
+    quad_flips<PMJ>(own, n, colour, t, key, vk, thr, js, jneg_uniform, Q, acc);
 
     if constexpr (MEASURE) { // stored by the kernel at its end, as above
 #pragma unroll
@@ -799,10 +822,9 @@ __global__ __launch_bounds__(256) void lat_sweep_loop_kernel(
         side_words(n, odd);
         QuadSigns js;
         load_signs<PMJ>(jn, g, Q, js);
-        const uint32_t widx[4] = {4 * Q, 4 * Q + 1, 4 * Q + 2, 4 * Q + 3};
         QuadState st[1];
         const uint32_t Qs[1] = {Q};
-        quad_classes<PMJ>(own, n, widx, g, tb, js, jneg_uniform, st[0]);
+        quad_classes<PMJ>(own, n, tb, js, jneg_uniform, st[0]);
         quad_planes<1>(st, Qs, colour, t, key, vk, tb);
         quad_ties(st[0], Q, colour, t, key, vk, tb, acc);
         __builtin_amdgcn_raw_buffer_store_b128(u32x4{own[0] ^ acc[0], own[1] ^ acc[1], own[2] ^ acc[2], own[3] ^ acc[3]}, mem.rsrc, vQ,

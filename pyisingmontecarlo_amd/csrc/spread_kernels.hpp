@@ -57,7 +57,7 @@ __global__ __launch_bounds__(1024) void lat_resident_spread_kernel(
                 QuadSigns js;
                 load_signs<PMJ>(PMJ ? jneg + size_t(colour) * 4 * g.wpp : nullptr, g, Q, js);
                 load_quad<VEC, false>(mem, g, colour, Q, qy, qxw, own, n, widx);
-                quad_flips_pre<PMJ>(own, n, widx, g, colour, t, key, vk, thr, js, jneg_uniform, Q, R, acc);
+                quad_flips_pre<PMJ>(own, n, colour, t, key, vk, thr, js, jneg_uniform, Q, R, acc);
                 if constexpr (VEC) {
                     mem.store4(widx[0], make_uint4(own[0] ^ acc[0], own[1] ^ acc[1], own[2] ^ acc[2], own[3] ^ acc[3]));
                 } else {

@@ -108,12 +108,11 @@ __device__ __forceinline__ void strip_update_quad(uint32_t *lds, const uint32_t 
     n.up[0] = u4.x; n.up[1] = u4.y; n.up[2] = u4.z; n.up[3] = u4.w;
     n.dn[0] = d4.x; n.dn[1] = d4.y; n.dn[2] = d4.z; n.dn[3] = d4.w;
     side_words(n, odd);
-    const uint32_t widx[4] = {0, 0, 0, 0}; // only the PMJ = false bond masks take it, and ignore it
 #ifdef ISINGMC_STRIP_NO_PRECOMPUTE // A/B build: the random words drawn after the wait, as in the streaming kernels
     (void)R;
-    quad_flips<PMJ>(own, n, widx, g, colour, t, key, vk, thr, js, jneg_uniform, Q, acc);
+    quad_flips<PMJ>(own, n, colour, t, key, vk, thr, js, jneg_uniform, Q, acc);
 #else
-    quad_flips_pre<PMJ>(own, n, widx, g, colour, t, key, vk, thr, js, jneg_uniform, Q, R, acc);
+    quad_flips_pre<PMJ>(own, n, colour, t, key, vk, thr, js, jneg_uniform, Q, R, acc);
 #endif
 #pragma unroll
     for (int q = 0; q < 4; q++) new_words[q] = own[q] ^ acc[q];
