@@ -132,6 +132,18 @@ int isingmc_host_colour_graph(const uint64_t *edge_a, const uint64_t *edge_b, si
 int isingmc_host_pt_swap_round(uint64_t seed, uint64_t round, size_t n_rungs, const double *betas,
                                const double *slot_energy, uint32_t *perm, uint64_t *swaps_out);
 
+/* The source table of one population-annealing resampling, the host twin of what isingmc_pa_resample computes
+ * on the device.  energies[n] are the replicas' energies (the f64 values of isingmc_get_energies), dbeta = beta_to - beta_from of
+ * either sign.  E_ref = min E for dbeta >= 0, else max E; x[r] = -(dbeta * (E[r] - E_ref)), three separately rounded f64
+ * operations; W[r] = floor(det_exp(x[r]) 2^32) as a 64-bit integer (the replica at E_ref has exactly 2^32); S = sum W and the
+ * inclusive prefix sums C are exact integer sums.  One Philox4x32-10 call with counter {step lo, step hi, 0, "PARS"} and the key
+ * (seed lo, seed hi) gives the 64-bit word U = (r[1] << 32) | r[0] and the offset u = the high 64 bits of U S.  New slot j takes
+ * the configuration of old replica src_out[j] = the r with n C[r-1] <= j S + u < n C[r] (128-bit compare): systematic resampling,
+ * src non-decreasing, replica r copied n_r times with |n_r - n W[r] / S| < 1.  *sum_out = S, *eref_out = E_ref (either may be
+ * NULL).  ln(S / (n 2^32)) - dbeta E_ref estimates ln Z(beta_to) - ln Z(beta_from).  n in 1 .. 2^31, everything finite. */
+int isingmc_host_pa_sources(uint64_t seed, uint64_t step, size_t n, const double *energies, double dbeta, uint32_t *src_out,
+                            uint64_t *sum_out, double *eref_out);
+
 /* Host halves of the replica-packed REAL-COUPLING path -- what the device kernels are fed with, exposed
  * so that they can be checked without a GPU.  That path serves edge lists with couplings of several sizes
  * (lattice.rs:46-50 takes any f64) and arbitrary site biases (set_individual_bias / set_global_bias, lattice.rs:104-131)
@@ -226,6 +238,11 @@ int isingmc_get_magnetisations(isingmc_states *states, int64_t *mags_out);
 int isingmc_get_states(isingmc_states *states, uint8_t *states_out, size_t replica_stride_bytes);
 /* Raw packed device words of every replica (layout: DESIGN.md S2), uint32[R][state_words]. */
 int isingmc_get_packed_states(isingmc_states *states, uint32_t *words_out);
+/* The device words exactly as they lie in memory (synchronises): checkerboard containers uint32[count][state_words], the same
+ * as isingmc_get_packed_states; replica-packed containers uint32[groups][positions] with replica s in bit s % 32 of group s / 32 --
+ * padding positions and the bits of a last group that no replica owns included.  *n_words_out (may be NULL) receives the number
+ * of words; words_out == NULL asks for that number alone. */
+int isingmc_get_raw_state(isingmc_states *states, uint32_t *words_out, size_t *n_words_out);
 /* Absolute timestep counter of the replicas (Philox counter word; persists across calls). */
 uint64_t isingmc_states_timestep(const isingmc_states *states);
 /* Sets that counter (t < 2^48): with the seeds, isingmc_states_set_state and this, a run that was stopped after t timesteps
@@ -355,6 +372,42 @@ int isingmc_pt_group_allgather(isingmc_pt_group *group);     /* enqueue only: lo
 int isingmc_pt_group_run(isingmc_pt_group *group, size_t timesteps, size_t swap_every); /* enqueue only */
 int isingmc_pt_group_synchronize(isingmc_pt_group *group);
 void isingmc_pt_group_destroy(isingmc_pt_group *group);
+
+/* ---- population annealing: resampling on the device (Hukushima and Iba 2003, Machta 2010; no reference
+ * counterpart) ----
+ * A population is one container whose replicas share one beta.  Between two temperatures the caller resamples it: new slot j
+ * takes the configuration of old replica src[j], with src from the rule of isingmc_host_pa_sources applied to the energies of
+ * the current configurations.  Resampling moves CONFIGURATIONS only: the Philox keys stay with the slots and the timestep
+ * counter does not advance, so the copies of one configuration diverge from the next sweep on.  Cluster periods
+ * (isingmc_states_set_cluster_every / _set_icm_every) may be on: all replicas share one beta, so the pairs stay valid.
+ * Memory: from the first resampling on the container keeps a second state buffer exactly as large as its state (the gathers
+ * write into it and the two are swapped), plus 28 bytes per replica of tables; both are freed with the container.
+ * Served: checkerboard containers with fast_path == 0 and both replica-packed families.  Refused with ISINGMC_ERR_INVALID and a
+ * message by every entry point of this block, the container untouched: the f64 CSR family; lattices with fields, open boundaries or anisotropic couplings (they
+ * have no device-side energy array); a tempering ladder attached; per-replica betas set; a shard of a larger set of experiments;
+ * an empty container; more than 2^31 replicas; a non-finite dbeta. */
+/* enqueue only: measure, weights, prefix sum, source table, gather.  dbeta = beta_to - beta_from; (seed, step) key the offset. */
+int isingmc_pa_resample(isingmc_states *states, double dbeta, uint64_t seed, uint64_t step);
+/* the gather alone with the caller's table src[count] in host memory: new slot j <- old replica src[j]; any table with entries
+ * below the replica count is valid (custom resampling schemes).  The families follow.  Synchronises. */
+int isingmc_pa_apply_sources(isingmc_states *states, const uint32_t *src);
+/* A whole schedule in one call: for k = 0 .. n_betas - 1 { k > 0: the resampling for betas[k] - betas[k-1] keyed by (seed, k);
+ * sweeps_per_beta timesteps at betas[k] }.  Everything is enqueued -- the acceptance tables of all betas are uploaded before the
+ * first launch, every resampling leaves its record in a device log -- and the host waits ONCE, at the end, then fills
+ * sum_out / eref_out / distinct_out / mean_energy_out[n_betas - 1] (any may be NULL) with the step records in order.  (While a
+ * cluster period is on, the cluster steps' workspace makes the host wait once per beta.)  Same results as the loop of
+ * isingmc_pa_resample and isingmc_do_time_steps. */
+int isingmc_pa_run(isingmc_states *states, const double *betas, size_t n_betas, size_t sweeps_per_beta, uint64_t seed,
+                   uint64_t *sum_out, double *eref_out, uint64_t *distinct_out, double *mean_energy_out);
+/* synchronises; the record of the last resampling (isingmc_pa_resample, or the last step of isingmc_pa_run): src_out[count]
+ * (NULL allowed; that resampling's own table -- a later isingmc_pa_apply_sources does not touch it), S, E_ref, the number of distinct sources and the population's mean energy before the resampling.
+ * ISINGMC_ERR_INVALID before the first resampling. */
+int isingmc_pa_last(isingmc_states *states, uint32_t *src_out, uint64_t *sum_out, double *eref_out, uint64_t *distinct_out,
+                    double *mean_energy_out);
+/* family_out[count]: the slot whose configuration at the last reset (or at creation) each slot's configuration descends from;
+ * synchronises.  The reset makes every slot its own family again. */
+int isingmc_pa_families(isingmc_states *states, uint32_t *family_out);
+int isingmc_pa_reset_families(isingmc_states *states);
 
 /* ---- measurement hook (bench.py; no reference counterpart) ------------------------------------------
  * Runs `timesteps` sweeps at `beta` like isingmc_do_time_steps and, beside them on a side stream, one

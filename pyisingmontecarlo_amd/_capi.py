@@ -40,6 +40,8 @@ _PROTOTYPES = {
     "isingmc_host_colour_graph": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.POINTER(C.c_uint32)]),
     "isingmc_host_pt_swap_round": (C.c_int, [C.c_uint64, C.c_uint64, C.c_size_t, _vp, _vp, _vp,
                                              C.POINTER(C.c_uint64)]),
+    "isingmc_host_pa_sources": (C.c_int, [C.c_uint64, C.c_uint64, C.c_size_t, _vp, C.c_double, _vp, C.POINTER(C.c_uint64),
+                                          C.POINTER(C.c_double)]),
     "isingmc_host_rj_quantise": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp, _vp, _vp, C.POINTER(C.c_int),
                                            C.POINTER(C.c_int)]),
     "isingmc_host_rj_energy_levels": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int)]),
@@ -64,6 +66,7 @@ _PROTOTYPES = {
     "isingmc_get_magnetisations": (C.c_int, [_vp, _vp]),
     "isingmc_get_states": (C.c_int, [_vp, _vp, C.c_size_t]),
     "isingmc_get_packed_states": (C.c_int, [_vp, _vp]),
+    "isingmc_get_raw_state": (C.c_int, [_vp, _vp, C.POINTER(C.c_size_t)]),
     "isingmc_states_timestep": (C.c_uint64, [_vp]),
     "isingmc_states_set_timestep": (C.c_int, [_vp, C.c_uint64]),
     "isingmc_states_set_cluster_every": (C.c_int, [_vp, C.c_size_t]),
@@ -90,6 +93,12 @@ _PROTOTYPES = {
     "isingmc_pt_run": (C.c_int, [_vp, C.c_size_t, C.c_size_t]),
     "isingmc_pt_swap": (C.c_int, [_vp]),
     "isingmc_pt_state": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "isingmc_pa_resample": (C.c_int, [_vp, C.c_double, C.c_uint64, C.c_uint64]),
+    "isingmc_pa_apply_sources": (C.c_int, [_vp, _vp]),
+    "isingmc_pa_run": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "isingmc_pa_last": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    "isingmc_pa_families": (C.c_int, [_vp, _vp]),
+    "isingmc_pa_reset_families": (C.c_int, [_vp]),
     "isingmc_states_stream": (C.c_int, [_vp, C.POINTER(_vp)]),
     "isingmc_synchronize": (C.c_int, [_vp]),
     "isingmc_debug_shader_clock": (C.c_int, [_vp, C.c_size_t, C.c_double, C.c_double, C.POINTER(C.c_double)]),
@@ -245,6 +254,16 @@ def pt_swap_round(seed, rnd, betas, slot_energy, perm):
     _check(lib().isingmc_host_pt_swap_round(C.c_uint64(int(seed)), C.c_uint64(int(rnd)), len(betas), _p(betas),
                                             _p(slot_energy), _p(perm), C.byref(swaps)))
     return swaps.value
+
+
+def pa_sources(seed, step, energies, dbeta):
+    """(src uint32[n], S, E_ref): the source table of one population-annealing resampling."""
+    e = _arr(energies, np.float64)
+    src = np.zeros(len(e), dtype=np.uint32)
+    total, eref = C.c_uint64(), C.c_double()
+    _check(lib().isingmc_host_pa_sources(C.c_uint64(int(seed)), C.c_uint64(int(step)), len(e), _p(e), float(dbeta), _p(src),
+                                         C.byref(total), C.byref(eref)))
+    return src, total.value, eref.value
 
 
 class PtGroup:
@@ -562,6 +581,50 @@ class States:
         rnd, swaps = C.c_uint64(), C.c_uint64()
         _check(lib().isingmc_pt_state(self._h, _p(perm), C.byref(rnd), C.byref(swaps)))
         return perm, rnd.value, swaps.value
+
+    def raw_state(self):
+        """The device words as they lie in memory, uint32 (one-dimensional): padding and unowned bits of a packed container included."""
+        n = C.c_size_t()
+        _check(lib().isingmc_get_raw_state(self._h, None, C.byref(n)))
+        out = np.zeros(n.value, dtype=np.uint32)
+        _check(lib().isingmc_get_raw_state(self._h, _p(out), None))
+        return out
+
+    # ---- population annealing (DESIGN.md S14)
+    def pa_run(self, betas, sweeps_per_beta, seed):
+        """The whole schedule with one host wait at the end: dict(sum, eref, distinct, mean_energy), one entry per resampling."""
+        b = _arr(betas, np.float64)
+        n = max(len(b) - 1, 0)
+        total, distinct = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+        eref, mean = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.float64)
+        _check(lib().isingmc_pa_run(self._h, _p(b), len(b), int(sweeps_per_beta), C.c_uint64(int(seed)), _p(total), _p(eref), _p(distinct), _p(mean)))
+        return dict(sum=total, eref=eref, distinct=distinct, mean_energy=mean)
+
+    def pa_resample(self, dbeta, seed, step):
+        """Resample the population for the step dbeta = beta_to - beta_from; enqueue only."""
+        _check(lib().isingmc_pa_resample(self._h, float(dbeta), C.c_uint64(int(seed)), C.c_uint64(int(step))))
+
+    def pa_apply_sources(self, src):
+        """new slot j <- old replica src[j] for any table with entries below the replica count."""
+        t = _arr(src, np.uint32)
+        if t.ndim != 1 or t.size != self.count:
+            raise ValueError("one source per replica expected")
+        _check(lib().isingmc_pa_apply_sources(self._h, _p(t)))
+
+    def pa_last(self):
+        """dict(src, sum, eref, distinct, mean_energy) of the last pa_resample (synchronises)."""
+        src = np.zeros(self.count, dtype=np.uint32)
+        total, eref, distinct, mean = C.c_uint64(), C.c_double(), C.c_uint64(), C.c_double()
+        _check(lib().isingmc_pa_last(self._h, _p(src), C.byref(total), C.byref(eref), C.byref(distinct), C.byref(mean)))
+        return dict(src=src, sum=total.value, eref=eref.value, distinct=distinct.value, mean_energy=mean.value)
+
+    def pa_families(self):
+        out = np.zeros(self.count, dtype=np.uint32)
+        _check(lib().isingmc_pa_families(self._h, _p(out)))
+        return out
+
+    def pa_reset_families(self):
+        _check(lib().isingmc_pa_reset_families(self._h))
 
     def synchronize(self):
         _check(lib().isingmc_synchronize(self._h))

@@ -167,6 +167,20 @@ extern "C" int isingmc_host_pt_swap_round(uint64_t seed, uint64_t round, size_t 
     return ISINGMC_OK;
 }
 
+extern "C" int isingmc_host_pa_sources(uint64_t seed, uint64_t step, size_t n, const double *energies, double dbeta, uint32_t *src_out,
+                                       uint64_t *sum_out, double *eref_out)
+{
+    if (n == 0) return fail(ISINGMC_ERR_INVALID, "a population needs at least one replica");
+    if (n > (size_t(1) << 31)) return fail(ISINGMC_ERR_INVALID, "populations above 2^31 replicas are not supported");
+    if (!energies || !src_out) return fail(ISINGMC_ERR_INVALID, "NULL argument");
+    if (!std::isfinite(dbeta)) return fail(ISINGMC_ERR_INVALID, "dbeta must be finite");
+    for (size_t r = 0; r < n; r++)
+        if (!std::isfinite(energies[r])) return fail(ISINGMC_ERR_INVALID, "energies must be finite");
+    const uint64_t S = pa_sources(seed, step, n, energies, dbeta, src_out, eref_out);
+    if (sum_out) *sum_out = S;
+    return ISINGMC_OK;
+}
+
 // adjacency order -> input-edge order: edge e is the next unfilled entry of both its ends' rows
 template <typename F>
 static void for_each_input_edge(const Adjacency &A, const uint64_t *ea, const uint64_t *eb, size_t n_edges, F &&f)

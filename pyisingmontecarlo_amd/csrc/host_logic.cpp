@@ -269,6 +269,38 @@ uint64_t pt_swap_round(uint64_t seed, uint64_t round, size_t n_rungs, const doub
     return swaps;
 }
 
+// ---- population annealing: the resampling rule ----------------------------------------------
+uint64_t pa_sources(uint64_t seed, uint64_t step, size_t n, const double *energies, double dbeta, uint32_t *src_out, double *eref_out)
+{
+    double eref = energies[0];
+    for (size_t r = 1; r < n; r++) eref = dbeta >= 0.0 ? std::min(eref, energies[r]) : std::max(eref, energies[r]);
+    std::vector<uint64_t> C(n);
+    uint64_t S = 0;
+    for (size_t r = 0; r < n; r++) {
+        // one subtraction, one multiplication, one negation, each rounded on its own (the volatile temporaries keep a
+        // compiler that contracts by default from fusing them: the device computes exactly these three operations)
+        volatile double d = energies[r] - eref;
+        volatile double m = dbeta * d;
+        const double x = -m;
+        S += uint64_t(std::ldexp(det_exp_host(x), 32)); // in [0, 2^32]
+        C[r] = S;
+    }
+    const uint32_t ctr[4] = {uint32_t(step), uint32_t(step >> 32), 0u, 0x50415253u /* "PARS" */};
+    uint32_t rnd[4];
+    philox4x32_10_host(ctr, uint32_t(seed), uint32_t(seed >> 32), rnd);
+    const uint64_t U = (uint64_t(rnd[1]) << 32) | rnd[0];
+    using u128 = unsigned __int128;
+    const uint64_t u = uint64_t((u128(U) * S) >> 64);
+    size_t r = 0;
+    for (size_t j = 0; j < n; j++) { // j S + u < n S = n C[n - 1]: r never runs past the end
+        const u128 t = u128(j) * S + u;
+        while (t >= u128(n) * C[r]) r++;
+        src_out[j] = uint32_t(r);
+    }
+    if (eref_out) *eref_out = eref;
+    return S;
+}
+
 // ---- replica-packed real-coupling path --------------------------------------------------------
 RjQuant rj_quantise(const Adjacency &A, size_t nvars, const double *biases)
 {

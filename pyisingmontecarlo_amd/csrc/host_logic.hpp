@@ -64,6 +64,12 @@ Colouring greedy_colouring(const Adjacency &A, size_t nvars);
 uint64_t pt_swap_round(uint64_t seed, uint64_t round, size_t n_rungs, const double *betas,
                        const double *slot_energy, uint32_t *perm);
 
+// The source table of one population-annealing resampling (device twin: pa_kernels.hip).  Weights
+// W[r] = floor(det_exp(-(dbeta (E[r] - E_ref))) 2^32) with E_ref = min E (dbeta >= 0) or max E, S = sum W, inclusive prefix sums C;
+// offset u = mulhi64(U, S) with U the low 64 bits of Philox4x32-10({step lo, step hi, 0, "PARS"}, seed); new slot j copies the
+// replica src[j] = the r with n C[r - 1] <= j S + u < n C[r] (systematic resampling; src is non-decreasing).  Returns S; n >= 1.
+uint64_t pa_sources(uint64_t seed, uint64_t step, size_t n, const double *energies, double dbeta, uint32_t *src_out, double *eref_out);
+
 // ---- replica-packed real-coupling path: host halves of the spec ---------------------------
 // Scales: F_i = |h_i| + sum_e |J_e|, Fmax = max F_i, med = the lower median nonzero |coupling or bias|;
 // k = ilogb(min(Fmax, 64 med)) + 1 - 30 is the graph's quantum; site i quantises what it sees at k_i = max(k, ilogb(F_i) + 1 - 30)

@@ -4,6 +4,7 @@
 //   isingmc.hip    replica containers, every sweep / measurement launch, the persistent strip kernel's host side
 //   sampling.hip   get_states and the double-buffered sampling pipeline
 //   tempering.hip  on-stream parallel tempering, the in-process ladder group (RCCL through dlopen)
+//   population.hip population annealing: the on-stream resampling step (isingmc_pa_*)
 //   debug.hip      shader-clock probe
 #pragma once
 #include <hip/hip_runtime.h>
@@ -33,6 +34,7 @@
 #include "packed_cluster_kernels.hpp"
 #include "packed_icm_kernels.hpp"
 #include "packed_kernels.hpp"
+#include "pa_kernels.hpp"
 #include "mc_types.hpp"
 #include "real_types.hpp"
 #include "spread_types.hpp"
@@ -40,6 +42,7 @@
 
 using namespace isingmc;
 
+static_assert(PA_PAD_SITE == PAD_SITE, "pa_kernels.hip tests PkGraphDev::site against the general path's padding mark");
 static_assert(PKC_PAD_SITE == PAD_SITE, "packed_cluster_kernels.hip tests PkGraphDev::site against the general path's padding mark");
 
 
@@ -206,6 +209,13 @@ struct isingmc_graph {
     }
 };
 
+// device tables of ONE beta for a run_steps call that must not upload any (step_presets_build)
+struct StepPreset {
+    const LatThr *thr = nullptr;       // checkerboard paths
+    const uint32_t *pk_tabs = nullptr; // bit-sliced packed path: PK_TAB_WORDS words
+    const RjBeta *rj = nullptr;        // real-coupling packed path
+};
+
 struct isingmc_states {
     isingmc_graph *g = nullptr;
     Options opt; // the environment's switches when the container was created (isingmc_states_set_option changes one)
@@ -301,6 +311,19 @@ struct isingmc_states {
     size_t icmb_cap = 0, icmb_pairs = 0;
     bool icmb_have_stats = false;
     hipEvent_t icmb_ev[2] = {nullptr, nullptr}; // the other container's stream has arrived / this container's launches are enqueued
+    // population annealing (isingmc_pa_*): everything below is allocated by the first resampling and stays
+    uint32_t *d_pa_state = nullptr; // the second state buffer the gathers write into: as large as d_state (pa_state_words words)
+    size_t pa_state_words = 0;
+    size_t pa_cap = 0;              // replicas the tables below hold
+    double *d_pa_energy = nullptr;          // [pa_cap]
+    unsigned long long *d_pa_cum = nullptr; // [pa_cap] weights, then their inclusive prefix sums; pa_scan_blocks(pa_cap) block sums follow
+    uint32_t *d_pa_src = nullptr;           // [pa_cap] source table of the last isingmc_pa_resample
+    uint32_t *d_pa_user_src = nullptr;      // [pa_cap] the caller's table of the last isingmc_pa_apply_sources
+    const StepPreset *step_preset = nullptr; // set around a run_steps call by isingmc_pa_run: the tables of its beta are on the device
+    uint32_t *d_pa_family = nullptr, *d_pa_family2 = nullptr; // [pa_cap] family of every slot, and the buffer its gather writes into
+    PaRecord *d_pa_record = nullptr;
+    bool pa_have_record = false;    // an isingmc_pa_resample has been enqueued
+    bool pa_families_set = false;   // d_pa_family holds the table (else: the identity)
 
     ~isingmc_states()
     {
@@ -322,6 +345,9 @@ struct isingmc_states {
         if (d_cl_stats) (void)cached_free(d_cl_stats);
         if (d_icm_stats) (void)cached_free(d_icm_stats);
         for (void *p : {(void *)d_icmb_work, (void *)d_icmb_slots, (void *)d_icmb_stats, (void *)d_icmb_inv})
+            if (p) (void)cached_free(p);
+        for (void *p : {(void *)d_pa_state, (void *)d_pa_energy, (void *)d_pa_cum, (void *)d_pa_src, (void *)d_pa_user_src, (void *)d_pa_family, (void *)d_pa_family2,
+                        (void *)d_pa_record})
             if (p) (void)cached_free(p);
         for (auto ev : icmb_ev) pooled_event_destroy(ev, true);
         for (int b = 0; b < 2; b++) {
@@ -418,6 +444,9 @@ IM_INTERNAL double lattice_energy(const isingmc_graph *g, unsigned long long sat
 IM_INTERNAL void pack_state(const isingmc_graph *g, const uint8_t *spins, uint32_t *words);
 IM_INTERNAL void unpack_state(const isingmc_graph *g, const uint32_t *words, uint8_t *spins);
 
+// ---- tempering.hip -----------------------------------------------------------------------------------------------------------
+IM_INTERNAL int energies_enqueue(isingmc_states *s, double *d_out); // checkerboard (periodic, no field) and both packed families
+
 // ---- isingmc.hip (replica containers and launches) ---------------------------------------------------------------------------
 constexpr size_t MAX_GRID_Y = 32768;
 constexpr int STRIP_TIMED_OUT = 1000; // internal status, never returned through the C ABI
@@ -429,6 +458,7 @@ struct StripPlan {
 };
 IM_INTERNAL int run_steps(isingmc_states *s, size_t timesteps, const double *betas, size_t beta_stride, double *energies_per_step,
                           float *device_ms, bool sync = true, double *final_energies = nullptr);
+IM_INTERNAL int step_presets_build(isingmc_states *s, const double *betas, size_t n, DeviceScratch &scratch, std::vector<StepPreset> &out);
 IM_INTERNAL int set_betas(isingmc_states *s, const double *beta_per_replica, bool all_equal);
 IM_INTERNAL int measure_enqueue(isingmc_states *s, unsigned long long *counts_slot, double *e_slot, long long *m_slot, bool want_up = true);
 IM_INTERNAL void lat_measure_enqueue(isingmc_states *s, unsigned long long *out, size_t out_stride); // lattice containers: the counting launches alone

@@ -489,6 +489,38 @@ static int pk_set_betas(isingmc_states *s)
     return ISINGMC_OK;
 }
 
+// The acceptance tables of n betas on the device, for calls that run a schedule without waiting on the host between its
+// temperatures (isingmc_pa_run): entry k serves run_steps through isingmc_states::step_preset.  Blocking uploads, before the
+// schedule is enqueued; the blocks belong to `scratch`.
+int step_presets_build(isingmc_states *s, const double *betas, size_t n, DeviceScratch &scratch, std::vector<StepPreset> &out)
+{
+    const isingmc_graph *g = s->g;
+    out.assign(n, StepPreset{});
+    if (s->packed && s->rj) {
+        std::vector<RjBeta> h(n);
+        for (size_t k = 0; k < n; k++) rj_beta(betas[k], g->rj_k, &h[k].shift, &h[k].mant);
+        RjBeta *d = nullptr;
+        TRY(scratch.alloc(&d, n));
+        HIP_TRY(hipMemcpy(d, h.data(), n * sizeof(RjBeta), hipMemcpyHostToDevice));
+        for (size_t k = 0; k < n; k++) out[k].rj = d + k;
+    } else if (s->packed) {
+        std::vector<uint32_t> h(n * PK_TAB_WORDS);
+        for (size_t k = 0; k < n; k++) pk_fill_table(h.data() + k * PK_TAB_WORDS, g->jabs, [&](uint32_t) { return betas[k]; });
+        uint32_t *d = nullptr;
+        TRY(scratch.alloc(&d, h.size()));
+        HIP_TRY(hipMemcpy(d, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        for (size_t k = 0; k < n; k++) out[k].pk_tabs = d + k * PK_TAB_WORDS;
+    } else {
+        std::vector<LatThr> h(n);
+        for (size_t k = 0; k < n; k++) h[k] = lattice_thresholds(betas[k], g->jabs);
+        LatThr *d = nullptr;
+        TRY(scratch.alloc(&d, n));
+        HIP_TRY(hipMemcpy(d, h.data(), n * sizeof(LatThr), hipMemcpyHostToDevice));
+        for (size_t k = 0; k < n; k++) out[k].thr = d + k;
+    }
+    return ISINGMC_OK;
+}
+
 // real-coupling path: one launch per colour class; a workgroup walks several 256-position blocks (it loads the log table once)
 static void rj_launch_timestep(isingmc_states *s, const RjBeta *betas, uint32_t beta_stride, size_t gb, size_t ge, hipStream_t stream)
 {
@@ -1213,7 +1245,7 @@ static double step_beta(const StepRun &c, size_t k) { return c.s->has_betas ? 0.
 
 static int upload_lat_thresholds(StepRun &c, size_t k0, size_t nk)
 {
-    if (c.s->has_betas) return ISINGMC_OK;
+    if (c.s->has_betas || c.s->step_preset) return ISINGMC_OK;
     fill_step_tables(c, k0, nk, c.h_thr, [&](double beta) { return lattice_thresholds(beta, c.s->g->jabs); });
     HIP_TRY(hipMemcpyAsync(c.d_thr, c.h_thr.data(), c.h_thr.size() * sizeof(LatThr), hipMemcpyHostToDevice, c.s->stream));
     return ISINGMC_OK;
@@ -1229,7 +1261,7 @@ static int run_packed(StepRun &c, size_t k0, size_t nk)
     const size_t philox_words = !s->rj && g->pk_uni_deg && !s->opt.disable_packed_uniform ? s->groups * pk_uni_philox_table_words() : 0;
     // one table per timestep of the chunk, or one for the call: written by the call's first Metropolis chunk, which is not
     // chunk 0 when the call begins with a cluster step
-    const bool new_step_tabs = !s->has_betas && (c.beta_stride || !c.pk_tabs_written);
+    const bool new_step_tabs = !s->has_betas && !s->step_preset && (c.beta_stride || !c.pk_tabs_written);
     const bool new_philox_rows = philox_words && !(s->pk_philox_steps && s->pk_philox_groups == s->groups && s->t >= s->pk_philox_t0 &&
                                                    s->t + nk <= s->pk_philox_t0 + s->pk_philox_steps);
     if (k0 > 0 && (new_step_tabs || new_philox_rows)) { // the chunk's tables are overwritten: every lane must have finished reading them
@@ -2063,10 +2095,17 @@ static int run_steps_impl(isingmc_states *s, size_t timesteps, const double *bet
     StepRun c{s, plan_steps(s, timesteps, energies_per_step != nullptr), betas, beta_stride, timesteps, energies_per_step, final_energies};
     const StepPlan &P = c.P;
     const size_t n_tabs = s->has_betas ? 0 : beta_stride ? P.chunk : 1;
-    if (n_tabs && (P.path == StepPath::LatResident || P.path == StepPath::LatStrip)) TRY(c.scratch.alloc(&c.d_thr, n_tabs));
+    if (s->step_preset) { // the caller's device tables of this call's ONE beta (a population-annealing schedule): nothing to upload
+        if (beta_stride || s->has_betas) return fail(ISINGMC_ERR_INVALID, "preset step tables serve one beta per call");
+        c.d_thr = const_cast<LatThr *>(s->step_preset->thr);
+        c.d_rj = const_cast<RjBeta *>(s->step_preset->rj);
+        c.d_pk_tabs = const_cast<uint32_t *>(s->step_preset->pk_tabs);
+    } else {
+        if (n_tabs && (P.path == StepPath::LatResident || P.path == StepPath::LatStrip)) TRY(c.scratch.alloc(&c.d_thr, n_tabs));
+        if (n_tabs && P.path == StepPath::Packed && s->rj) TRY(c.scratch.alloc(&c.d_rj, n_tabs));
+        if (n_tabs && P.path == StepPath::Packed && !s->rj) TRY(c.scratch.alloc(&c.d_pk_tabs, n_tabs * PK_TAB_WORDS));
+    }
     if (n_tabs && P.path == StepPath::GenResident) TRY(c.scratch.alloc(&c.d_betas, n_tabs));
-    if (n_tabs && P.path == StepPath::Packed && s->rj) TRY(c.scratch.alloc(&c.d_rj, n_tabs));
-    if (n_tabs && P.path == StepPath::Packed && !s->rj) TRY(c.scratch.alloc(&c.d_pk_tabs, n_tabs * PK_TAB_WORDS));
     const bool general = P.path == StepPath::GenResident || P.path == StepPath::GenCsr;
     if (energies_per_step && general) TRY(c.scratch.alloc(&c.d_energies, P.chunk * R));
     if (energies_per_step && P.path == StepPath::GenCsr) TRY(c.scratch.alloc(&c.d_mags, R));
@@ -2158,4 +2197,16 @@ extern "C" int isingmc_get_packed_states(isingmc_states *s, uint32_t *words_out)
     HIP_TRY(hipMemcpyAsync(words_out, s->d_state, s->R * s->g->state_words * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return ISINGMC_OK;
+}
+
+extern "C" int isingmc_get_raw_state(isingmc_states *s, uint32_t *words_out, size_t *n_words_out)
+{
+    if (!s) return fail(ISINGMC_ERR_INVALID, "NULL states");
+    const size_t n = s->packed ? s->groups * size_t(s->g->pk.n_pos) : s->R * s->g->state_words;
+    if (n_words_out) *n_words_out = n;
+    if (!words_out || n == 0) return ISINGMC_OK;
+    TRY(use_device(s->g->device));
+    HIP_TRY(hipMemcpyAsync(words_out, s->d_state, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return strip_error(strip_check(s));
 }

@@ -1,0 +1,212 @@
+// libisingmc.so: population annealing -- the resampling step on the container's stream (isingmc_pa_*).
+// The kernels live in pa_kernels.hip; the energies come from the measurement the tempering rounds use (energies_enqueue).
+#include "internal.hpp"
+
+// why this container cannot be resampled ("" when it can): no side effects
+static std::string pa_obstacle(const isingmc_states *s)
+{
+    const isingmc_graph *g = s->g;
+    if (!s->packed && g->kind != ISINGMC_KIND_LATTICE2D)
+        return "population annealing is not implemented for containers on the f64 CSR general-graph family (the replica-packed families "
+               "are chosen by size, by ISINGMC_FORCE_PACKED=1 or by ISINGMC_FLAG_STABLE_PATH at creation)";
+    if (!s->packed && g->mc_mode != MC_NONE)
+        return "population annealing needs the device-side energy array, which lattices with fields, open boundaries or anisotropic "
+               "couplings do not have";
+    if (s->pt_attached) return "a tempering ladder is attached to this container: a population shares one beta";
+    if (s->has_betas) return "per-replica betas are set for this container: a population shares one beta";
+    if (s->first != 0 || s->first + s->R < s->n_total) return "this container is a shard of a larger set of experiments: one population lives in one container";
+    if (s->R == 0) return "the container holds no replica";
+    if (s->R > PA_MAX_REPLICAS) return "populations above 2^31 replicas are not supported";
+    return "";
+}
+
+static size_t pa_state_size(const isingmc_states *s) { return s->packed ? s->groups * size_t(s->g->pk.n_pos) : s->cap * s->g->state_words; }
+
+// the second state buffer and the tables, sized for the container as it is now (it may have grown since the last call)
+static int pa_reserve(isingmc_states *s)
+{
+    const size_t words = pa_state_size(s);
+    if (s->d_pa_state && s->pa_state_words == words && s->pa_cap >= s->R) return ISINGMC_OK;
+    HIP_TRY(stream_quiesce(s->stream)); // recycled blocks: nothing enqueued may still use the old ones
+    std::vector<uint32_t> family(s->R);
+    for (size_t r = 0; r < s->R; r++) family[r] = uint32_t(r);
+    if (s->pa_families_set && s->pa_cap) // a container that grew keeps its families; the new slots found their own
+        HIP_TRY(hipMemcpy(family.data(), s->d_pa_family, std::min(s->pa_cap, s->R) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (void **p : {(void **)&s->d_pa_state, (void **)&s->d_pa_energy, (void **)&s->d_pa_cum, (void **)&s->d_pa_src, (void **)&s->d_pa_user_src, (void **)&s->d_pa_family,
+                     (void **)&s->d_pa_family2}) {
+        if (*p) (void)cached_free(*p);
+        *p = nullptr;
+    }
+    s->pa_cap = s->pa_state_words = 0;
+    s->pa_families_set = false;
+    TRY(dev_alloc(&s->d_pa_state, words));
+    TRY(dev_alloc(&s->d_pa_energy, s->R));
+    TRY(dev_alloc(&s->d_pa_cum, s->R + pa_scan_blocks(s->R)));
+    TRY(dev_alloc(&s->d_pa_src, s->R));
+    TRY(dev_alloc(&s->d_pa_user_src, s->R));
+    TRY(dev_alloc(&s->d_pa_family, s->R));
+    TRY(dev_alloc(&s->d_pa_family2, s->R));
+    if (!s->d_pa_record) TRY(dev_alloc(&s->d_pa_record, 1));
+    HIP_TRY(hipMemcpy(s->d_pa_family, family.data(), s->R * sizeof(uint32_t), hipMemcpyHostToDevice));
+    s->pa_state_words = words;
+    s->pa_cap = s->R;
+    s->pa_families_set = true;
+    return ISINGMC_OK;
+}
+
+// enqueue: new slot j <- old slot d_src[j], configurations and families; then nothing the container had cached about its
+// configurations holds any longer
+static int pa_gather(isingmc_states *s, const uint32_t *d_src)
+{
+    const isingmc_graph *g = s->g;
+    if (s->packed) // pk_bit0 == 0: a shard is refused
+        HIP_TRY(pa_launch_bit_gather(s->stream, s->d_state, s->d_pa_state, d_src, uint32_t(s->R), s->groups, g->pk.n_pos, g->pk.site));
+    else
+        HIP_TRY(pa_launch_row_gather(s->stream, s->d_state, s->d_pa_state, d_src, s->R, g->state_words));
+    HIP_TRY(pa_launch_gather_u32(s->stream, s->d_pa_family, d_src, uint32_t(s->R), s->d_pa_family2));
+    std::swap(s->d_state, s->d_pa_state); // every launch reads the pointer when it is enqueued: the stream orders the rest
+    std::swap(s->d_pa_family, s->d_pa_family2);
+    s->meas_fresh = false; // energies a strip launch left for the next tempering measurement
+    // (the strip path's snapshot is taken anew by every synchronous call: nothing to drop)
+    if (s->d_halo) { // halo rows the strips exchanged: the state a fresh allocation starts from
+        HIP_TRY(hipMemsetAsync(s->d_halo, 0, s->halo_cap * sizeof(unsigned long long), s->stream));
+        s->strip_epoch = 0;
+    }
+    return ISINGMC_OK;
+}
+
+// enqueue one resampling; its record goes to *d_rec (device)
+static int pa_resample_enqueue(isingmc_states *s, double dbeta, uint64_t seed, uint64_t step, PaRecord *d_rec)
+{
+    const uint32_t R = uint32_t(s->R);
+    TRY(energies_enqueue(s, s->d_pa_energy));
+    HIP_TRY(pa_launch_weights(s->stream, s->d_pa_energy, R, dbeta, seed, step, s->d_pa_cum, d_rec));
+    HIP_TRY(pa_launch_scan(s->stream, s->d_pa_cum, R, s->d_pa_cum + R));
+    HIP_TRY(pa_launch_sources(s->stream, s->d_pa_cum, R, d_rec, s->d_pa_src));
+    return pa_gather(s, s->d_pa_src);
+}
+
+extern "C" int isingmc_pa_resample(isingmc_states *s, double dbeta, uint64_t seed, uint64_t step)
+{
+    if (!s) return fail(ISINGMC_ERR_INVALID, "NULL states");
+    if (!std::isfinite(dbeta)) return fail(ISINGMC_ERR_INVALID, "dbeta must be finite");
+    {
+        const std::string why = pa_obstacle(s);
+        if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
+    }
+    TRY(use_device(s->g->device));
+    TRY(pa_reserve(s));
+    TRY(pa_resample_enqueue(s, dbeta, seed, step, s->d_pa_record));
+    s->pa_have_record = true;
+    return ISINGMC_OK;
+}
+
+// The whole schedule in one call: for k = 0 .. n - 1 { k > 0: resample for betas[k] - betas[k - 1] with step counter k;
+// sweeps_per_beta timesteps at betas[k] }, everything enqueued, ONE wait at the end.  The acceptance tables of every beta go to
+// the device before the first launch and every resampling writes its record into its own slot of a device log.  (With a
+// cluster period on, the cluster steps' workspace is per run of timesteps and the host waits once per beta to hand it back.)
+extern "C" int isingmc_pa_run(isingmc_states *s, const double *betas, size_t n_betas, size_t sweeps_per_beta, uint64_t seed, uint64_t *sum_out,
+                              double *eref_out, uint64_t *distinct_out, double *mean_energy_out)
+{
+    if (!s || !betas || n_betas == 0) return fail(ISINGMC_ERR_INVALID, "NULL argument / no betas");
+    for (size_t k = 0; k < n_betas; k++)
+        if (!std::isfinite(betas[k])) return fail(ISINGMC_ERR_INVALID, "beta must be finite");
+    {
+        const std::string why = pa_obstacle(s);
+        if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
+    }
+    TRY(use_device(s->g->device));
+    TRY(pa_reserve(s));
+    const size_t n_steps = n_betas - 1;
+    DeviceScratch scratch(s->stream); // the tables and the log: handed back after the final wait
+    std::vector<StepPreset> presets;
+    TRY(step_presets_build(s, betas, n_betas, scratch, presets));
+    PaRecord *d_log = nullptr;
+    TRY(scratch.alloc(&d_log, n_steps));
+    int rc = ISINGMC_OK;
+    for (size_t k = 0; k < n_betas && rc == ISINGMC_OK; k++) {
+        if (k > 0) rc = pa_resample_enqueue(s, betas[k] - betas[k - 1], seed, k, d_log + (k - 1));
+        if (rc != ISINGMC_OK) break;
+        s->step_preset = &presets[k];
+        rc = run_steps(s, sweeps_per_beta, &betas[k], 0, nullptr, nullptr, /*sync=*/false);
+        s->step_preset = nullptr;
+    }
+    if (rc == ISINGMC_OK && n_steps) {
+        HIP_TRY(hipMemcpyAsync(s->d_pa_record, d_log + (n_steps - 1), sizeof(PaRecord), hipMemcpyDeviceToDevice, s->stream));
+        s->pa_have_record = true;
+    }
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    TRY(strip_error(strip_check(s)));
+    if (rc != ISINGMC_OK) return strip_error(rc);
+    std::vector<PaRecord> log(n_steps);
+    if (n_steps) HIP_TRY(hipMemcpy(log.data(), d_log, n_steps * sizeof(PaRecord), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < n_steps; k++) {
+        if (sum_out) sum_out[k] = log[k].sum;
+        if (eref_out) eref_out[k] = log[k].eref;
+        if (distinct_out) distinct_out[k] = log[k].distinct;
+        if (mean_energy_out) mean_energy_out[k] = log[k].mean;
+    }
+    return ISINGMC_OK;
+}
+
+extern "C" int isingmc_pa_apply_sources(isingmc_states *s, const uint32_t *src)
+{
+    if (!s || !src) return fail(ISINGMC_ERR_INVALID, "NULL argument");
+    {
+        const std::string why = pa_obstacle(s);
+        if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
+    }
+    for (size_t j = 0; j < s->R; j++)
+        if (src[j] >= s->R) return fail(ISINGMC_ERR_INVALID, "source table entry " + std::to_string(j) + " is not a replica of this container");
+    TRY(use_device(s->g->device));
+    TRY(pa_reserve(s));
+    HIP_TRY(hipMemcpyAsync(s->d_pa_user_src, src, s->R * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+    TRY(pa_gather(s, s->d_pa_user_src));
+    HIP_TRY(hipStreamSynchronize(s->stream)); // the caller's table is free again
+    return strip_error(strip_check(s));
+}
+
+extern "C" int isingmc_pa_last(isingmc_states *s, uint32_t *src_out, uint64_t *sum_out, double *eref_out, uint64_t *distinct_out,
+                               double *mean_energy_out)
+{
+    if (!s) return fail(ISINGMC_ERR_INVALID, "NULL states");
+    if (!s->pa_have_record) return fail(ISINGMC_ERR_INVALID, "no resampling has been run on this container (isingmc_pa_resample)");
+    TRY(use_device(s->g->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    TRY(strip_error(strip_check(s)));
+    PaRecord rec;
+    HIP_TRY(hipMemcpy(&rec, s->d_pa_record, sizeof rec, hipMemcpyDeviceToHost));
+    if (src_out) HIP_TRY(hipMemcpy(src_out, s->d_pa_src, std::min(s->R, s->pa_cap) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (sum_out) *sum_out = rec.sum;
+    if (eref_out) *eref_out = rec.eref;
+    if (distinct_out) *distinct_out = rec.distinct;
+    if (mean_energy_out) *mean_energy_out = rec.mean;
+    return ISINGMC_OK;
+}
+
+extern "C" int isingmc_pa_families(isingmc_states *s, uint32_t *family_out)
+{
+    if (!s || !family_out) return fail(ISINGMC_ERR_INVALID, "NULL argument");
+    TRY(use_device(s->g->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    TRY(strip_error(strip_check(s)));
+    for (size_t r = 0; r < s->R; r++) family_out[r] = uint32_t(r); // slots no resampling has touched found their own family
+    if (s->pa_families_set) HIP_TRY(hipMemcpy(family_out, s->d_pa_family, std::min(s->R, s->pa_cap) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return ISINGMC_OK;
+}
+
+extern "C" int isingmc_pa_reset_families(isingmc_states *s)
+{
+    if (!s) return fail(ISINGMC_ERR_INVALID, "NULL states");
+    {
+        const std::string why = pa_obstacle(s);
+        if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
+    }
+    if (!s->pa_families_set) return ISINGMC_OK;
+    TRY(use_device(s->g->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    std::vector<uint32_t> family(s->pa_cap);
+    for (size_t r = 0; r < family.size(); r++) family[r] = uint32_t(r);
+    HIP_TRY(hipMemcpy(s->d_pa_family, family.data(), family.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return ISINGMC_OK;
+}

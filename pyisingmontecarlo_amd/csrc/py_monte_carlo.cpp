@@ -9,6 +9,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <cmath>
 #include <cstdlib>
 #include <memory>
 #include <limits>
@@ -371,6 +372,80 @@ public:
         return py::make_tuple(energies, states);
     }
 
+    // extension: population annealing.  `population` replicas are cooled through the non-decreasing `betas`:
+    // before the sweeps at betas[k], k > 0, the population is resampled on the device for the step betas[k] - betas[k - 1]
+    // (isingmc_pa_resample, step counter k, keyed by the LAST of make_seeds(population + 1); the first `population` seeds key the
+    // replicas); then sweeps_per_beta timesteps at betas[k] (cluster periods set on this object apply).  One library call
+    // (isingmc_pa_run) enqueues it all; nothing waits on the host until the end.
+    py::object run_population_annealing(const std::vector<double> &betas, size_t sweeps_per_beta, size_t population, bool return_states)
+    {
+        require_classical();
+        if (betas.empty()) throw py::value_error("betas must hold at least one inverse temperature");
+        for (size_t k = 0; k < betas.size(); k++)
+            if (!std::isfinite(betas[k]) || (k && betas[k] < betas[k - 1])) throw py::value_error("betas must be finite and non-decreasing");
+        if (population == 0) throw py::value_error("population must be positive");
+        if (sweeps_per_beta == 0) throw py::value_error("sweeps_per_beta must be positive");
+        if (devices_.size() != 1) throw py::value_error("population annealing runs on one device: one population lives in one container (set_device)");
+        const size_t R = population, N = E_->nvars, n = betas.size();
+        const std::vector<uint64_t> seeds = make_seeds(R + 1);
+        const std::shared_ptr<GraphHandle> gh = graph(0);
+        py::array_t<double> energies(std::vector<ssize_t>{ssize_t(R)});
+        py::array_t<bool> states(std::vector<ssize_t>{ssize_t(return_states ? R : 0), ssize_t(N)});
+        py::array_t<double> log_z(std::vector<ssize_t>{ssize_t(n)}), mean_e(std::vector<ssize_t>{ssize_t(n)});
+        py::array_t<int64_t> distinct(std::vector<ssize_t>{ssize_t(n - 1)});
+        py::array_t<uint32_t> families(std::vector<ssize_t>{ssize_t(R)});
+        double *e = energies.mutable_data(), *lz = log_z.mutable_data(), *me = mean_e.mutable_data();
+        int64_t *ds = distinct.mutable_data();
+        uint32_t *fam = families.mutable_data();
+        uint8_t *st = reinterpret_cast<uint8_t *>(states.mutable_data());
+        int rc = ISINGMC_OK;
+        std::string msg;
+        {
+            py::gil_scoped_release nogil;
+            StatesHandle h;
+            h.graph = gh;
+            const uint8_t *ini = initial_state_.empty() ? nullptr : initial_state_.data();
+            rc = isingmc_states_create(gh->g, R, seeds.data(), ini, &h.s);
+            if (rc == ISINGMC_OK && cluster_every_) rc = isingmc_states_set_cluster_every(h.s, cluster_every_);
+            if (rc == ISINGMC_OK && icm_every_) rc = isingmc_states_set_icm_every(h.s, icm_every_);
+            // the whole schedule is enqueued; the host waits once, at its end, and reads the step records
+            std::vector<uint64_t> sums(n - 1), nd(n - 1);
+            std::vector<double> erefs(n - 1);
+            if (rc == ISINGMC_OK) rc = isingmc_pa_run(h.s, betas.data(), n, sweeps_per_beta, seeds[R], sums.data(), erefs.data(), nd.data(), me);
+            lz[0] = 0.0;
+            for (size_t k = 1; k < n && rc == ISINGMC_OK; k++) {
+                // ln Q = ln(S / (R 2^32)) - dbeta E_ref estimates ln Z(betas[k]) - ln Z(betas[k - 1])
+                const double dbeta = betas[k] - betas[k - 1];
+                lz[k] = lz[k - 1] + (std::log(std::ldexp(double(sums[k - 1]), -32) / double(R)) - dbeta * erefs[k - 1]);
+                ds[k - 1] = int64_t(nd[k - 1]);
+            }
+            if (rc == ISINGMC_OK) rc = isingmc_get_energies(h.s, e);
+            if (rc == ISINGMC_OK && return_states) rc = isingmc_get_states(h.s, st, N);
+            if (rc == ISINGMC_OK) rc = isingmc_pa_families(h.s, fam);
+            if (rc != ISINGMC_OK) msg = isingmc_last_error();
+        }
+        if (rc == ISINGMC_ERR_INVALID) throw py::value_error(msg);
+        if (rc == ISINGMC_ERR_ALLOC) throw std::bad_alloc();
+        if (rc != ISINGMC_OK) throw std::runtime_error(msg);
+        double sum_e = 0.0, rho = 0.0;
+        for (size_t r = 0; r < R; r++) sum_e += e[r];
+        me[n - 1] = sum_e / double(R); // the final measurement
+        std::vector<uint32_t> count(R, 0u);
+        for (size_t r = 0; r < R; r++) count[fam[r]]++;
+        for (size_t f = 0; f < R; f++) rho += double(count[f]) * double(count[f]);
+        rho /= double(R); // rho_t = R sum_f (n_f / R)^2
+        py::dict d;
+        d["energies"] = energies;
+        d["states"] = return_states ? py::object(states) : py::object(py::none());
+        d["log_z_ratio"] = log_z;
+        d["mean_energy"] = mean_e;
+        d["distinct_sources"] = distinct;
+        d["families"] = families;
+        d["rho_t"] = rho;
+        d["betas"] = py::array_t<double>(ssize_t(n), betas.data());
+        return py::module_::import("types").attr("SimpleNamespace")(**d);
+    }
+
     Lattice clone() const { return *this; } // lattice.rs:1038-1040 (the immutable device graph is shared)
 
     static void sample_into(isingmc_states *s, double beta, size_t therm, size_t freq, size_t S, size_t, size_t,
@@ -679,6 +754,8 @@ PYBIND11_MODULE(_py_monte_carlo, m)
         .def("run_monte_carlo_annealing_and_get_energies", &Lattice::run_monte_carlo_annealing_and_get_energies,
              "betas"_a, "timesteps"_a, "num_experiments"_a, "only_basic_moves"_a = py::none(),
              "edge_move_importance_sampling"_a = py::none(), "replica_range"_a = py::none())
+        .def("run_population_annealing", &Lattice::run_population_annealing, "betas"_a, "sweeps_per_beta"_a, "population"_a,
+             py::kw_only(), "return_states"_a = true)
         .def("clone", &Lattice::clone);
     // the reference's quantum (SSE) entry points (lattice.rs:478-1036) live in the un-vendored qmc crate and are out of
     // scope: present by name, so a script written for the reference fails with a reason instead of an AttributeError

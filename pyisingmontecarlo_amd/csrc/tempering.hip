@@ -238,35 +238,39 @@ extern "C" int isingmc_pt_measure(isingmc_states *s)
 {
     if (!s || !s->pt_attached) return fail(ISINGMC_ERR_INVALID, "no ladder attached");
     TRY(use_device(s->g->device));
+    if (s->R == 0) return ISINGMC_OK;
+    if (s->g->kind == ISINGMC_KIND_LATTICE2D && s->meas_fresh) { // the last strip launch of isingmc_pt_time_steps has already written these energies
+        s->meas_fresh = false;
+        return ISINGMC_OK;
+    }
+    return energies_enqueue(s, s->pt_world == 1 ? s->d_pt_all + s->pt.slot_offset : s->d_pt_local);
+}
+
+// enqueue: the energies of the container's configurations -> d_out[R] (device), the f64 values of isingmc_get_energies
+int energies_enqueue(isingmc_states *s, double *d_out)
+{
     const isingmc_graph *g = s->g;
     const size_t R = s->R;
     if (R == 0) return ISINGMC_OK;
     if (g->kind == ISINGMC_KIND_LATTICE2D) {
         // three launches per round: the conversion kernel leaves the counters zeroed for the next round and, on
         // a single rank, writes straight into the gathered array (no memset, no device-to-device copy)
-        if (s->meas_fresh) { // the last strip launch of isingmc_pt_time_steps has already written these energies
-            s->meas_fresh = false;
-            return ISINGMC_OK;
-        }
         if (!s->meas_zero) HIP_TRY(hipMemsetAsync(s->d_meas, 0, 2 * R * sizeof(unsigned long long), s->stream));
         lat_measure_enqueue(s, s->d_meas, size_t(2));
         hipLaunchKernelGGL(lat_energy_from_counts_kernel, dim3(unsigned((R + 255) / 256)), dim3(256), 0, s->stream, s->d_meas,
-                           uint32_t(R), g->jabs, 2ll * (long long)g->nvars,
-                           s->pt_world == 1 ? s->d_pt_all + s->pt.slot_offset : s->d_pt_local);
+                           uint32_t(R), g->jabs, 2ll * (long long)g->nvars, d_out);
         s->meas_zero = true;
     } else if (s->packed && !s->rj) {
         TRY(measure_enqueue(s, s->d_meas, nullptr, nullptr, /*want_up=*/false));
         s->meas_zero = false;
         hipLaunchKernelGGL(pk_energy_from_counts_kernel, dim3(unsigned((R + 255) / 256)), dim3(256), 0, s->stream, s->d_meas, uint32_t(s->pk_bit0),
-                           uint32_t(R), g->jabs, double(int64_t(g->n_directed / 2)), g->self_energy,
-                           s->pt_world == 1 ? s->d_pt_all + s->pt.slot_offset : s->d_pt_local);
+                           uint32_t(R), g->jabs, double(int64_t(g->n_directed / 2)), g->self_energy, d_out);
     } else if (s->packed && s->rj) {
         TRY(measure_enqueue(s, s->d_meas, nullptr, nullptr, /*want_up=*/false));
         s->meas_zero = false;
-        HIP_TRY(rj_launch_energy_from_counts(s->stream, s->d_meas, uint32_t(s->pk_bit0), uint32_t(R), g->rj_k_energy, g->self_energy,
-                                             s->pt_world == 1 ? s->d_pt_all + s->pt.slot_offset : s->d_pt_local));
+        HIP_TRY(rj_launch_energy_from_counts(s->stream, s->d_meas, uint32_t(s->pk_bit0), uint32_t(R), g->rj_k_energy, g->self_energy, d_out));
     } else {
-        return fail(ISINGMC_ERR_INVALID, "on-stream tempering is implemented for the lattice path and the real-coupling path; use the host swap step");
+        return fail(ISINGMC_ERR_INVALID, "no device-side energy array for this container: it exists for periodic field-free lattices and for the replica-packed paths");
     }
     HIP_TRY(hipGetLastError());
     return ISINGMC_OK;
