@@ -45,10 +45,15 @@ static int init_random(isingmc_states *s, size_t first, size_t count)
 static int upload_state(isingmc_states *s, size_t first, size_t count, const uint8_t *spins)
 {
     s->meas_fresh = false;
-    std::vector<uint32_t> words(s->g->state_words);
+    const size_t sw = s->g->state_words;
+    std::vector<uint32_t> words(sw);
     pack_state(s->g, spins, words.data());
-    for (size_t r = first; r < first + count; r++)
-        HIP_TRY(hipMemcpyAsync(s->d_state + r * s->g->state_words, words.data(), words.size() * sizeof(uint32_t),
+    // the same row for every replica: one copy per batch of rows (a population of 2^20 small lattices took one copy per ROW)
+    const size_t batch = std::min(count, std::max<size_t>(1, (size_t(1) << 22) / sw)); // at most 16 MiB of host rows
+    std::vector<uint32_t> rows(batch * sw);
+    for (size_t k = 0; k < batch; k++) std::copy(words.begin(), words.end(), rows.begin() + k * sw);
+    for (size_t r = first; r < first + count; r += batch)
+        HIP_TRY(hipMemcpyAsync(s->d_state + r * sw, rows.data(), std::min(batch, first + count - r) * sw * sizeof(uint32_t),
                                hipMemcpyHostToDevice, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return ISINGMC_OK;

@@ -3,7 +3,8 @@
 Written from the S14 text alone: reference energy, the exponent as three separately rounded f64 operations, 2^32 fixed-point
 weights of the oracle's det_exp, exact integer sums, the offset from one Philox4x32-10 call, the source of slot j as the replica
 whose interval of R C holds j S + u, and the two gathers on arrays in the device layouts (rows of a checkerboard container,
-bits of the words of a replica-packed one).
+bits of the words of a replica-packed one).  sources() and bit_gather() are the definition, one Python step per slot;
+sources_fast() and bit_gather_fast() are their vectorised twins for the populations of tests/test_gpu_pa_large.py.
 """
 import math
 from fractions import Fraction
@@ -49,6 +50,36 @@ def sources(seed, step, energies, dbeta):
                 weights=W)
 
 
+def sources_fast(seed, step, energies, dbeta):
+    """The vectorised twin of sources() for populations up to 2^21 (sources() stays the definition; tests/test_pa_host.py holds the
+    two equal).  One det_exp per distinct exponent; the prefix sums in uint64 (S <= R 2^32 <= 2^53: exact); the quotient
+    q[j] = floor((j S + u) / R) from S = a R + b as j a + floor((j b + u) / R), every term below 2^64 (j, b < 2^21, u < 2^53,
+    a <= 2^32); the source of slot j is the smallest r with R C[r] > j S + u, that is the smallest r with C[r] > q[j].
+    Returns the keys of sources() (weights as uint64[R]), needs_high_words: R S >= 2^64, the populations at which the device's
+    128-bit compare has non-zero high words, and low_word_carries: the number of slots j at which the low word of j S overflows
+    when u is added (it can only happen once R S >= 2^64)."""
+    from oracle import oracle as O
+
+    e = np.asarray(energies, dtype=np.float64)
+    R = len(e)
+    assert 0 < R <= 1 << 21
+    eref = np.float64(e.min() if dbeta >= 0 else e.max())
+    x = -(np.float64(dbeta) * (e - eref))
+    distinct_x, inverse = np.unique(x, return_inverse=True)
+    W = np.array([int(math.floor(math.ldexp(O.det_exp(float(v)), 32))) for v in distinct_x], dtype=np.uint64)[inverse.ravel()]
+    C = np.cumsum(W, dtype=np.uint64)
+    S = int(C[-1])
+    assert S <= R << 32
+    u = offset(seed, step, S)
+    a, b = divmod(S, R)
+    j = np.arange(R, dtype=np.uint64)
+    q = j * np.uint64(a) + (j * np.uint64(b) + np.uint64(u)) // np.uint64(R)
+    src = np.searchsorted(C, q, side="right").astype(np.uint32)
+    low = j * np.uint64(S % (1 << 64))   # the low word of j S (uint64 arrays wrap)
+    return dict(src=src, sum=S, eref=float(eref), distinct=len(np.unique(src)), mean_energy=float(np.mean(e)), weights=W,
+                needs_high_words=R * S >= 1 << 64, low_word_carries=int((low + np.uint64(u) < low).sum()))
+
+
 def log_q(rec, R, dbeta):
     """ln Q of a step record: the estimate of ln Z(beta_to) - ln Z(beta_from)."""
     return math.log(Fraction(rec["sum"], R << 32)) - dbeta * rec["eref"]
@@ -71,6 +102,28 @@ def bit_gather(words, src, padding=None):
         bit = (words[sj // 32] >> np.uint32(sj % 32)) & np.uint32(1)
         new = (out[j // 32] & ~np.uint32(1 << (j % 32))) | (bit << np.uint32(j % 32))
         out[j // 32] = np.where(real, new, out[j // 32])
+    return out
+
+
+def bit_gather_fast(words, src, padding=None):
+    """The vectorised twin of bit_gather(): 32 passes, one per target bit, each over every target group at once."""
+    words = np.asarray(words, dtype=np.uint32)
+    src = np.asarray(src, dtype=np.int64)
+    groups, n_pos = words.shape
+    R = len(src)
+    owned = (R + 31) // 32   # groups with at least one slot below R
+    real = np.ones(n_pos, dtype=bool) if padding is None else ~np.asarray(padding, dtype=bool)
+    cols = np.nonzero(real)[0]
+    live = np.ascontiguousarray(words[:, cols])   # the real positions alone: padding keeps its words
+    acc = np.zeros((owned, len(cols)), dtype=np.uint32)
+    for b in range(32):
+        s = src[b::32]   # the sources of bit b of groups 0, 1, ...
+        acc[:len(s)] |= ((live[s >> 5] >> (s & 31).astype(np.uint32)[:, None]) & np.uint32(1)) << np.uint32(b)
+    mask = np.full(owned, 0xFFFFFFFF, dtype=np.uint32)
+    if R % 32:
+        mask[-1] = (1 << (R % 32)) - 1
+    out = words.copy()
+    out[:owned, cols] = (live[:owned] & ~mask[:, None]) | acc
     return out
 
 

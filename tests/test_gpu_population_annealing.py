@@ -33,8 +33,12 @@ class _Board:
         self.ref = [self.lat.init(s) for s in self.seeds]
         self.t = 0
 
-    def sweeps(self, n, beta):
-        self.st.do_time_steps(n, beta)
+    def sweeps(self, n, beta, per_step_energies=False):
+        out = self.st.do_time_steps(n, beta, per_step_energies=per_step_energies)
+        self.advance(n, beta)
+        return out
+
+    def advance(self, n, beta):
         if self.k:
             spins = [self.lat.unpack(w) for w in self.ref]
             spins, _, _ = ICM.run_replicas(self.W, self.H, self.jr, self.jd, list(self.seeds), spins, self.t, [beta] * n, self.k)
@@ -44,6 +48,10 @@ class _Board:
                 for t in range(self.t, self.t + n):
                     self.lat.sweep(w, s, t, beta)
         self.t += n
+
+    def energies(self):
+        """The energies of the restatement's configurations: no call into the library."""
+        return np.array([self.lat.energy_mag(w)[0] for w in self.ref])
 
     def snapshot(self):
         """The raw device words before a gather: gather() then checks the words after it against the restatement's row gather."""
@@ -79,11 +87,12 @@ class _Packed:
         self.e_ref = None
         self.t = 0
 
-    def sweeps(self, n, beta):
-        self.st.do_time_steps(n, beta)
+    def sweeps(self, n, beta, per_step_energies=False):
+        out = self.st.do_time_steps(n, beta, per_step_energies=per_step_energies)
         self.ref, e, _ = IR.run(self.G, self.seeds, n, self.k, betas=[beta] * n, states=self.ref, t0=self.t, biases=self.biases, real=self.real)
         self.e_ref = e[:, -1]
         self.t += n
+        return out
 
     def snapshot(self):
         """The raw device words u32[groups][n_pos] before a gather, padding positions and unowned bits included."""
@@ -109,6 +118,12 @@ class _Packed:
         assert np.array_equal(e, self.e_ref)
         assert self.st.timestep == self.t
         return e
+
+    def energies(self):
+        """The energies of the restatement's configurations: no call into the library."""
+        if self.e_ref is None:
+            self.e_ref = np.array([self.oracle_energy(self.ref[r]) for r in range(len(self.seeds))])
+        return self.e_ref
 
     def oracle_energy(self, spins):
         from oracle import oracle as O
@@ -431,3 +446,153 @@ def test_python_argument_checks(exact):
     lat.set_initial_state([True] * 256)
     r = lat.run_population_annealing([0.0], 1, 4)   # one beta: no resampling at all
     assert r.log_z_ratio.tolist() == [0.0] and r.distinct_sources.shape == (0,) and r.rho_t == 1.0
+
+
+# ---- heating, vanishing weights, call sequences without a host measurement, growth -----------------------------------------
+@pytest.mark.parametrize("case", FAMILIES, ids=_id)
+def test_heating_steps(capi, exact, monkeypatch, case):
+    """dbeta < 0: the reference energy is the MAXIMUM, the weights fall towards the low energies."""
+    kind, R = case
+    P = _make(capi, exact, monkeypatch, kind, R)
+    P.sweeps(3, BETA)
+    e = P.compare()
+    fam = np.arange(R, dtype=np.uint32)
+    want, fam = _resample_and_compare(P, e, -0.05, 1, fam)
+    assert want["eref"] == e.max() and want["eref"] > e.min()
+    assert want["weights"][int(np.argmax(e))] == 1 << 32 and want["weights"][int(np.argmin(e))] < 1 << 32
+    P.sweeps(2, BETA - 0.05)
+    e = P.compare()
+    want, fam = _resample_and_compare(P, e, -0.05, 2, fam)
+    assert want["eref"] == e.max() and want["eref"] > e.min()
+    P.sweeps(1, BETA - 0.1)
+    P.compare()
+
+
+def _all_up_at_slot_5(P):
+    n = P.st.graph.nvars
+    P.st.set_state(5, np.ones(n, dtype=np.uint8))
+    if isinstance(P, _Board):
+        P.ref[5] = P.lat.pack(np.ones(n, dtype=np.uint8))
+    else:
+        P.ref[5] = 1
+        P.e_ref = None
+
+
+@pytest.mark.parametrize("case", [(("board", 128, 64, False), 37, 0.05), (("cubic", 8, False), 70, 0.1)], ids=lambda c: _id(c[:2]))
+def test_weights_that_vanish(capi, exact, monkeypatch, case):
+    """One replica in the ground state of a ferromagnet among replicas near beta = 0.1: every other exponent is below -40, where
+    det_exp returns 0, so S = 2^32 exactly and one replica takes every slot; heated by the same step on a twin container, that
+    replica alone gets no copy."""
+    kind, R, dbeta = case
+    P = _make(capi, exact, monkeypatch, kind, R)
+    P.sweeps(2, 0.1)
+    _all_up_at_slot_5(P)
+    e = P.compare()
+    assert int(np.argmin(e)) == 5
+    for _ in range(4):   # the RESTATEMENT says whether the step is large enough
+        W = PA.sources(SEED, 1, e, dbeta)["weights"]
+        if W[5] == 1 << 32 and sum(W) == 1 << 32:
+            break
+        dbeta *= 2
+    else:
+        pytest.fail("no step leaves one weight")
+    assert -dbeta * (np.delete(e, 5).min() - e[5]) < -40.0
+    want, fam = _resample_and_compare(P, e, dbeta, 1, np.arange(R, dtype=np.uint32))
+    assert want["sum"] == 1 << 32 and want["distinct"] == 1 and (want["src"] == 5).all() and (fam == 5).all()
+    assert (P.st.pa_families() == 5).all() and P.st.pa_last()["sum"] == 1 << 32
+    P.sweeps(1, 0.1)
+    P.compare()
+    Q = _make(capi, exact, monkeypatch, kind, R)
+    Q.sweeps(2, 0.1)
+    _all_up_at_slot_5(Q)
+    e = Q.compare()
+    want, fam = _resample_and_compare(Q, e, -dbeta, 1, np.arange(R, dtype=np.uint32))
+    assert want["weights"][5] == 0 and 5 not in want["src"] and 5 not in fam and want["distinct"] > 1
+    Q.sweeps(1, 0.1)
+    Q.compare()
+
+
+SEQUENCE_CASES = [(("board", 64, 4, True), 37), (("strip",), 8), (("cubic", 6, True), 70), (("real",), 45)]
+
+
+@pytest.mark.parametrize("case", SEQUENCE_CASES, ids=_id)
+def test_two_resamplings_in_a_row(capi, exact, monkeypatch, case):
+    """No host measurement between the two: the second step weighs the energies e[src] of the gathered population."""
+    kind, R = case
+    P = _make(capi, exact, monkeypatch, kind, R)
+    P.sweeps(3, BETA)
+    e = P.compare()
+    first = PA.sources(SEED, 1, e, 0.05)
+    e1 = e[first["src"]]
+    second = PA.sources(SEED, 2, e1, 0.05)
+    P.snapshot()
+    P.st.pa_resample(0.05, SEED, 1)
+    P.st.pa_resample(0.05, SEED, 2)
+    got = P.st.pa_last()
+    assert np.array_equal(got["src"], second["src"])
+    assert got["sum"] == second["sum"] and got["eref"] == second["eref"] and got["distinct"] == second["distinct"]
+    assert abs(got["mean_energy"] - second["mean_energy"]) <= R * 2.0 ** -52 * np.abs(e1).mean()
+    both = first["src"][second["src"]]   # new[j] = old[first[second[j]]]
+    P.gather(both)
+    assert np.array_equal(P.st.pa_families(), both)
+    assert np.array_equal(P.compare(), e[both])
+    P.sweeps(1, BETA)
+    P.compare()
+
+
+@pytest.mark.parametrize("case", SEQUENCE_CASES, ids=_id)
+def test_resampling_straight_after_other_measurements(capi, exact, monkeypatch, case):
+    """pa_resample directly after a run that returned per-step energies, and directly after magnetisations(): the restatement is
+    fed with the energies of its own configurations, the library is not asked for them in between."""
+    kind, R = case
+    P = _make(capi, exact, monkeypatch, kind, R)
+    P.sweeps(2, BETA)
+    P.compare()
+    fam = np.arange(R, dtype=np.uint32)
+    per_step = P.sweeps(2, BETA, per_step_energies=True)
+    e = P.energies()
+    assert np.array_equal(per_step[:, -1], e)
+    _, fam = _resample_and_compare(P, e, 0.05, 1, fam)
+    P.sweeps(2, BETA + 0.05)
+    e = P.energies()
+    m = P.st.magnetisations()
+    assert m.shape == (R,)
+    _, fam = _resample_and_compare(P, e, 0.05, 2, fam)
+    m = P.st.magnetisations()   # ... and once more with nothing but a resampling since the last measurement
+    e = P.energies()
+    _, fam = _resample_and_compare(P, e, 0.05, 3, fam)
+    P.sweeps(1, BETA + 0.1)
+    P.compare()
+
+
+@pytest.mark.parametrize("case", [(("board", 64, 4, True), 37), (("cubic", 6, True), 64)], ids=_id)
+def test_growth_after_a_resampling(capi, exact, monkeypatch, case):
+    """append on a resampled container (on the cubic graph the 65th replica opens a group): the family table is kept, the new slot
+    founds its own family, and the next resampling runs on buffers of the new size."""
+    kind, R = case
+    P = _make(capi, exact, monkeypatch, kind, R)
+    P.sweeps(2, BETA)
+    e = P.compare()
+    _, fam = _resample_and_compare(P, e, 0.05, 1, np.arange(R, dtype=np.uint32))
+    assert len(set(fam.tolist())) < R
+    seed = capi.make_seeds(77, 1)[0]
+    P.st.append(seed)
+    P.seeds = np.append(P.seeds, seed)
+    if isinstance(P, _Board):
+        P.ref.append(P.lat.init(seed))
+    else:
+        start, _, _ = IR.run(P.G, np.array([seed], dtype=np.uint64), 0, 0, betas=[])   # a new group, keyed by its first seed
+        P.ref = np.concatenate([P.ref, start])
+        P.e_ref = None
+    fam = np.append(fam, np.uint32(R))
+    assert P.st.count == R + 1 and np.array_equal(P.st.pa_families(), fam)
+    P.compare()
+    P.sweeps(2, BETA + 0.05)
+    e = P.compare()
+    assert np.array_equal(P.st.pa_families(), fam)
+    want, fam = _resample_and_compare(P, e, 0.05, 2, fam)   # raw words, word for word, inside
+    assert len(want["src"]) == R + 1
+    P.sweeps(1, BETA + 0.1)
+    P.compare()
+    P.st.pa_reset_families()
+    assert np.array_equal(P.st.pa_families(), np.arange(R + 1))

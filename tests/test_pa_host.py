@@ -97,3 +97,71 @@ def test_gathers_of_the_restatement():
         want = bits(words, src[j]) if j < R else bits(words, j)
         assert np.array_equal(bits(out, j)[:60], want[:60])
         assert np.array_equal(bits(out, j)[60:], bits(words, j)[60:])
+
+
+# ---- the vectorised restatement (sources_fast, bit_gather_fast) and the host rule at the populations it makes affordable ---
+def _energies(kind, R):
+    rng = np.random.default_rng(R)
+    if kind == "equal":
+        return np.full(R, -123.5)
+    if kind == "binomial":
+        return -512.0 + 4.0 * rng.binomial(128, 0.3, R)
+    return -300.0 + 25.0 * rng.normal(size=R)   # not integers: the subtraction and the product round
+
+
+def _same_table(fast, slow):
+    for name in ("sum", "eref", "distinct", "mean_energy"):
+        assert fast[name] == slow[name], name
+    assert np.array_equal(fast["src"], slow["src"]) and fast["src"].dtype == slow["src"].dtype
+    assert fast["weights"].tolist() == slow["weights"]
+
+
+@pytest.mark.parametrize("R", [1, 2, 31, 32, 33, 64, 1000, 2000])
+@pytest.mark.parametrize("dbeta", [0.0, 0.05, 1.0, -0.05, -1.0])
+def test_fast_sources_equal_the_definition(oracle, R, dbeta):
+    for kind in ("equal", "binomial", "real"):
+        e = _energies(kind, R)
+        fast = PA.sources_fast(SEED, 5, e, dbeta)
+        _same_table(fast, PA.sources(SEED, 5, e, dbeta))
+        assert not fast["needs_high_words"] and fast["low_word_carries"] == 0
+
+
+@pytest.mark.parametrize("R", [32, 33, 63, 64, 65, 95, 1000, 2000])   # the last group owns R % 32 in {0, 1, 31, 8, 16} bits
+def test_fast_bit_gather_equals_the_definition(R):
+    rng = np.random.default_rng(R)
+    groups, n_pos = (R + 31) // 32, 24
+    words = rng.integers(0, 1 << 32, (groups, n_pos), dtype=np.uint64).astype(np.uint32)
+    pad = np.zeros(n_pos, dtype=bool)
+    pad[[3, 20, 23]] = True
+    for src in (rng.integers(0, R, R), np.sort(rng.integers(0, R, R)), np.arange(R)[::-1], (np.arange(R) * 2654435761) % R):
+        assert np.array_equal(PA.bit_gather_fast(words, src, pad), PA.bit_gather(words, src, pad))
+        assert np.array_equal(PA.bit_gather_fast(words, src), PA.bit_gather(words, src))
+    assert np.array_equal(PA.bit_gather_fast(words, np.arange(R), pad), words)
+
+
+LARGE = [(65535, "equal", 0.7), (65535, "binomial", -0.05), (65535, "real", 0.05),
+         (65536, "equal", 0.7), (65536, "equal", -0.7), (65536, "binomial", 0.05), (65536, "real", -0.05),
+         ((1 << 20) + 1025, "equal", -0.7), ((1 << 20) + 1025, "binomial", 0.05), ((1 << 20) + 1025, "binomial", -0.05),
+         ((1 << 20) + 1025, "real", 0.002), ((1 << 20) + 1025, "real", -0.002)]
+
+
+@pytest.mark.parametrize("R,kind,dbeta", LARGE)
+def test_host_rule_at_the_populations_with_high_words(capi, oracle, R, kind, dbeta):
+    """isingmc_host_pa_sources against sources_fast on both sides of R S = 2^64.  What the case reaches is certified by the
+    restatement: below R = 65 536 no product reaches 2^64; R = 65 536 reaches it with equal energies alone (S = R 2^32, the low
+    words of j S are multiples of 2^48 and never carry); at 2^20 + 1025 every case reaches it, and where the mean weight is large
+    (equal energies, |dbeta| = 0.002) the low word of j S + u carries at some slots."""
+    e = _energies(kind, R)
+    want = PA.sources_fast(SEED, 3, e, dbeta)
+    src, total, eref = capi.pa_sources(SEED, 3, e, dbeta)
+    assert total == want["sum"] and eref == want["eref"] and eref == (e.min() if dbeta >= 0 else e.max())
+    assert np.array_equal(src, want["src"])
+    print(f"R {R} {kind} dbeta {dbeta}: S / (R 2^32) = {want['sum'] / (R << 32):.5f}, distinct {want['distinct']}, "
+          f"high words {want['needs_high_words']}, low-word carries {want['low_word_carries']}")
+    assert want["needs_high_words"] == (R > 65536 or (R == 65536 and kind == "equal"))
+    if kind == "equal":
+        assert np.array_equal(src, np.arange(R)) and total == R << 32 and want["distinct"] == R
+    if R > 65536 and (kind == "equal" or abs(dbeta) == 0.002):
+        assert want["low_word_carries"] > 0
+    else:
+        assert R > 65536 or want["low_word_carries"] == 0
