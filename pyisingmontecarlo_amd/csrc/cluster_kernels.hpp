@@ -4,6 +4,7 @@
 // kernels).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <array>
 #include <cstddef>
 #include <cstdint>
 
@@ -26,7 +27,19 @@ struct ClusterWork {
     uint32_t *fliptab; // [n][N / 32]  flip bit of every possible root
 };
 
-constexpr size_t cluster_words_per_replica(uint64_t nvars) { return size_t(2 * nvars + nvars / 16 + nvars / 32); }
+// Words per replica of {labels, sizes, bonds, fliptab}.  The members lie in this order, one behind the other, in the block of a batch: its
+// size (cluster_words_per_replica) and its carving (cluster_carve) both follow from this one line.
+constexpr std::array<size_t, 4> cluster_member_words(uint64_t nvars) { return {{size_t(nvars), size_t(nvars), size_t(nvars / 16), size_t(nvars / 32)}}; }
+constexpr size_t cluster_words_per_replica(uint64_t nvars) { const std::array<size_t, 4> w = cluster_member_words(nvars); return w[0] + w[1] + w[2] + w[3]; }
+static_assert(cluster_words_per_replica(4096) == 2 * 4096 + 256 + 128, "labels N | sizes N | bonds N / 16 | fliptab N / 32");
+
+// the workspace of `batch` replicas in a block of batch * cluster_words_per_replica(nvars) words
+static inline ClusterWork cluster_carve(uint32_t *block, size_t batch, uint64_t nvars)
+{
+    const std::array<size_t, 4> w = cluster_member_words(nvars);
+    uint32_t *const sizes = block + batch * w[0], *const bonds = sizes + batch * w[1], *const fliptab = bonds + batch * w[2];
+    return ClusterWork{block, sizes, bonds, fliptab};
+}
 
 // One cluster step of replicas [0, n) at timestep t: state / keys / thr_per_replica / stats point at the first replica of the
 // batch.  thr_per_replica == nullptr: every replica uses thr.  stats: [n][2] = {clusters, largest cluster}, zero on entry.

@@ -470,4 +470,10 @@ void unpack_lattice(uint32_t W, uint32_t H, const uint32_t *words, uint8_t *spin
     else unpack_lattice_impl<false>(W, H, words, spins);
 }
 
+size_t nonlocal_batch(size_t items, size_t words_per_item, size_t workspace_bytes)
+{
+    const size_t fit = std::max<size_t>(1, workspace_bytes) / (words_per_item * sizeof(uint32_t));
+    return std::min({items, size_t(32768), std::max<size_t>(1, fit)});
+}
+
 } // namespace isingmc

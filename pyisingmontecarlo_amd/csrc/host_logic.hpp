@@ -92,6 +92,11 @@ void rj_beta(double beta, int k, uint32_t *shift_out, uint32_t *mant_out);
 // LT[i], i = 0 .. 2048: log2(1 + i/2048) in Q24, centred for linear interpolation (see oracle/ising_oracle.c engine E)
 void rj_log_table(uint32_t *out);
 
+// Items (replicas, pairs, replica groups, pair blocks) per batch of a non-local move whose labelling workspace takes
+// words_per_item 32-bit words per item: as many as workspace_bytes hold, at least one, at most `items` and at most 32768 (a batch
+// is the y dimension of one grid).  Internal to the library: not among its dynamic symbols.
+__attribute__((visibility("hidden"))) size_t nonlocal_batch(size_t items, size_t words_per_item, size_t workspace_bytes);
+
 // packed checkerboard planes of one replica -> W*H bytes in site order (16 bytes per SSE2 store)
 void unpack_lattice(uint32_t W, uint32_t H, const uint32_t *words, uint8_t *spins);
 

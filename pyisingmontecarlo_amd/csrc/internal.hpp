@@ -2,6 +2,7 @@
 //   core.hip       error state, device-block / pinned-block / stream / event caches, environment helpers
 //   graph.hip      edge-list checks, host-only C ABI helpers, lattice / general / packed / real-coupling graph construction
 //   isingmc.hip    replica containers, every sweep / measurement launch, the persistent strip kernel's host side
+//   nonlocal.hip   host side of the non-local moves: Swendsen-Wang steps, isoenergetic cluster moves inside and between containers
 //   sampling.hip   get_states and the double-buffered sampling pipeline
 //   tempering.hip  on-stream parallel tempering, the in-process ladder group (RCCL through dlopen)
 //   population.hip population annealing: the on-stream resampling step (isingmc_pa_*)
@@ -386,6 +387,30 @@ static int dev_alloc(T **out, size_t count)
     return ISINGMC_OK;
 }
 
+// A device block that a container owns takes another size: nothing enqueued on `stream` may still use the old block, which goes
+// back to the cache.  `count` elements, recorded as *cap = new_cap (the owner's unit); a failed allocation leaves {nullptr, 0}.
+template <typename T>
+static int dev_regrow(hipStream_t stream, T **block, size_t *cap, size_t count, size_t new_cap)
+{
+    HIP_TRY(stream_quiesce(stream));
+    if (*block) HIP_TRY(cached_free(*block));
+    *block = nullptr;
+    *cap = 0;
+    TRY(dev_alloc(block, count));
+    *cap = new_cap;
+    return ISINGMC_OK;
+}
+
+// device -> host on the container's stream, waited for
+template <typename T>
+static int read_back(isingmc_states *s, std::vector<T> &h, const T *d, size_t n)
+{
+    h.resize(n);
+    HIP_TRY(hipMemcpyAsync(h.data(), d, n * sizeof(T), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return ISINGMC_OK;
+}
+
 // device scratch of one API call: freed on every exit path, after the stream has drained
 struct DeviceScratch {
     hipStream_t stream;
@@ -460,6 +485,7 @@ IM_INTERNAL int run_steps(isingmc_states *s, size_t timesteps, const double *bet
                           float *device_ms, bool sync = true, double *final_energies = nullptr);
 IM_INTERNAL int step_presets_build(isingmc_states *s, const double *betas, size_t n, DeviceScratch &scratch, std::vector<StepPreset> &out);
 IM_INTERNAL int set_betas(isingmc_states *s, const double *beta_per_replica, bool all_equal);
+IM_INTERNAL int lanes_join(isingmc_states *s); // the main stream waits for the replica lanes of the current run_steps call
 IM_INTERNAL int measure_enqueue(isingmc_states *s, unsigned long long *counts_slot, double *e_slot, long long *m_slot, bool want_up = true);
 IM_INTERNAL void lat_measure_enqueue(isingmc_states *s, unsigned long long *out, size_t out_stride); // lattice containers: the counting launches alone
 IM_INTERNAL double pk_energy(const isingmc_graph *g, bool rj, unsigned long long c0, unsigned long long c1);
@@ -472,6 +498,26 @@ IM_INTERNAL int strip_error(int rc);
 IM_INTERNAL bool may_use_strips(const isingmc_states *s);
 IM_INTERNAL int snapshot_take(isingmc_states *s);
 IM_INTERNAL int snapshot_restore(isingmc_states *s);
+
+// ---- nonlocal.hip (Swendsen-Wang steps and isoenergetic cluster moves) -------------------------------------------------------
+// What the non-local steps of ONE run_steps call keep between them: filled by the call's first such step, the device blocks in the
+// call's DeviceScratch.  The host copies live as long as the call: they feed asynchronous copies.
+struct NonlocalRun {
+    ClusterWork cl{nullptr, nullptr, nullptr, nullptr};      // workspace of one batch: of replicas (cluster steps) or pairs (S9) of a lattice,
+    PkClusterWork pk_cl{nullptr, nullptr, nullptr, nullptr}; // of replica groups of a packed container (S11),
+    PkIcmWork pk_icm{nullptr, nullptr, nullptr};             // of replica groups for the isoenergetic move (S12)
+    size_t batch = 0;                                        // items of that batch (0: no workspace yet)
+    uint64_t *d_cl_thr = nullptr;                            // bond thresholds per counter slot (per-replica betas)
+    std::vector<uint64_t> h_cl_thr{};
+    uint32_t *d_icm_mask = nullptr;                          // packed containers: the moving pairs of every group
+    std::vector<uint32_t> h_icm_mask{};
+};
+IM_INTERNAL bool is_cluster_step(const isingmc_states *s); // is timestep s->t a Swendsen-Wang step / an isoenergetic cluster move?
+IM_INTERNAL bool is_icm_step(const isingmc_states *s);
+// timestep s->t as that move and s->t++, nothing else.  beta: the call's beta of this step (not read with per-replica betas)
+IM_INTERNAL int run_cluster_step(isingmc_states *s, NonlocalRun &n, DeviceScratch &scratch, double beta);
+IM_INTERNAL int run_icm_step(isingmc_states *s, NonlocalRun &n, DeviceScratch &scratch);
+IM_INTERNAL bool icm_unequal_pair_betas(const isingmc_states *s, const double *betas);
 
 // counter pairs of a measurement (measure_enqueue): one per (group, bit) slot of a packed container, one per replica otherwise
 static inline size_t counter_slots(const isingmc_states *s) { return s->packed ? s->pk_slots() : s->R; }

@@ -16,7 +16,6 @@ static dim3 lat_grid(const isingmc_graph *g, uint32_t quads, size_t replicas)
 
 static int lanes_reserve(isingmc_states *s, size_t n);
 static int lanes_fork(isingmc_states *s, size_t n);
-static int lanes_join(isingmc_states *s);
 
 // replica-packed general path (defined further down)
 static int choose_packed(const isingmc_states *s, size_t n_replicas);
@@ -235,14 +234,6 @@ extern "C" int isingmc_states_set_option(isingmc_states *s, const char *name, lo
 extern "C" int isingmc_states_set_betas(isingmc_states *s, const double *beta_per_replica)
 {
     return set_betas(s, beta_per_replica, false);
-}
-
-// the isoenergetic cluster move is valid between replicas at one temperature only
-static bool icm_unequal_pair_betas(const isingmc_states *s, const double *betas)
-{
-    for (size_t r = 0; r + 1 < s->R; r += 2)
-        if (betas[r] != betas[r + 1]) return true;
-    return false;
 }
 
 // all_equal: the caller passes one beta R times (run_sampling) -- then a shard that cuts a replica group is fine
@@ -720,7 +711,7 @@ static int lanes_fork(isingmc_states *s, size_t n)
     return ISINGMC_OK;
 }
 
-static int lanes_join(isingmc_states *s)
+int lanes_join(isingmc_states *s)
 {
     for (size_t i = 0; i < s->n_lanes && s->n_lanes > 1; i++) {
         HIP_TRY(hipEventRecord(s->lane_events[i], s->lanes[i]));
@@ -894,16 +885,6 @@ int measure_enqueue(isingmc_states *s, unsigned long long *counts_slot, double *
 void lat_measure_enqueue(isingmc_states *s, unsigned long long *out, size_t out_stride)
 {
     LAT_DISPATCH(launch_lat_measure, s, out, out_stride);
-}
-
-// device -> host, waited for
-template <typename T>
-static int read_back(isingmc_states *s, std::vector<T> &h, const T *d, size_t n)
-{
-    h.resize(n);
-    HIP_TRY(hipMemcpyAsync(h.data(), d, n * sizeof(T), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return ISINGMC_OK;
 }
 
 // energies / magnetisations of the current configurations into host arrays (either may be NULL)
@@ -1100,14 +1081,7 @@ static int run_steps_impl(isingmc_states *s, size_t timesteps, const double *bet
 int snapshot_take(isingmc_states *s)
 {
     const size_t words = s->R * s->g->state_words;
-    if (s->snapshot_cap < words) {
-        HIP_TRY(stream_quiesce(s->stream));
-        if (s->d_snapshot) HIP_TRY(cached_free(s->d_snapshot));
-        s->d_snapshot = nullptr;
-        s->snapshot_cap = 0;
-        TRY(dev_alloc(&s->d_snapshot, words));
-        s->snapshot_cap = words;
-    }
+    if (s->snapshot_cap < words) TRY(dev_regrow(s->stream, &s->d_snapshot, &s->snapshot_cap, words, words));
     HIP_TRY(hipMemcpyAsync(s->d_snapshot, s->d_state, words * sizeof(uint32_t), hipMemcpyDeviceToDevice, s->stream));
     return ISINGMC_OK;
 }
@@ -1226,16 +1200,8 @@ struct StepRun {
     std::vector<LatThr> h_thr{};
     std::vector<std::array<uint32_t, PK_TAB_WORDS>> h_pk_tabs{};
     std::vector<RjBeta> h_rj{};
-    // cluster steps: the workspace of one batch of replicas (allocated by the call's first cluster step), per-replica thresholds
-    ClusterWork cl{nullptr, nullptr, nullptr, nullptr};
-    PkClusterWork pk_cl{nullptr, nullptr, nullptr, nullptr}; // (packed containers: a batch of replica groups)
-    PkIcmWork pk_icm{nullptr, nullptr, nullptr};             // (isoenergetic moves on packed containers, S12)
-    uint32_t *d_icm_mask = nullptr;                          // the moving pairs of every group (written by the call's first move)
-    std::vector<uint32_t> h_icm_mask{};
-    size_t cl_batch = 0;
     bool pk_tabs_written = false; // run_packed has written the call's acceptance table (a call may begin with a cluster step)
-    uint64_t *d_cl_thr = nullptr;
-    std::vector<uint64_t> h_cl_thr{};
+    NonlocalRun nonlocal{};       // cluster steps and isoenergetic moves of the call (nonlocal.hip)
 };
 
 // the host's tables of the chunk [k0, k0 + nk)
@@ -1513,544 +1479,12 @@ static int run_gen_csr(StepRun &c, size_t k0, size_t nk)
     return ISINGMC_OK;
 }
 
-// ------------------------------------------------------------------------------------------------
-// Swendsen-Wang cluster steps (cluster_kernels.hip; S11 on replica-packed containers, packed_cluster_kernels.hip)
-// ------------------------------------------------------------------------------------------------
-
-// why this container cannot take cluster steps ("" when it can)
-static std::string cluster_obstacle(const isingmc_states *s)
+// the energy after a non-local timestep (a chunk of its own): into counter slot 0 of step 0 of the chunk
+static int measure_nonlocal_step(StepRun &c)
 {
-    const isingmc_graph *g = s->g;
-    if (s->packed) { // S11: any graph of the bit-sliced packed path, any sign pattern
-        if (s->rj) return "cluster updates are not implemented for the replica-packed real-coupling path (couplings of one size and no biases only)";
-        if (s->pt_attached) return "a tempering ladder is attached to this container (isingmc_pt_detach first)";
-        return "";
-    }
-    if (g->kind != ISINGMC_KIND_LATTICE2D)
-        return "cluster updates need a container on the checkerboard lattice path or on the replica-packed bit-sliced path; this graph runs on "
-               "the f64 CSR general-graph kernel family (cluster updates on general graphs need the replica-packed family: chosen by size, "
-               "or by ISINGMC_FORCE_PACKED=1 / the stable-path flag at creation)";
-    if (g->mc_mode == MC_FIELD || g->mc_mode == MC_FIELD_OPEN) return "cluster updates are not implemented for lattices with a field";
-    if (g->mc_mode == MC_OPEN) return "cluster updates are not implemented for open boundaries (periodic lattices only)";
-    if (g->mc_mode != MC_NONE) return "cluster updates are not implemented for anisotropic couplings (|Jx| != |Jy|)";
-    if (!g->uniform_sign) return "cluster updates are not implemented for +-J sign patterns (one coupling sign only)";
-    if (g->nvars >= 0xFFFFFFFFull) return "cluster updates label sites with 32 bits: W H must be below 2^32 - 1";
-    if (s->pt_attached) return "a tempering ladder is attached to this container (isingmc_pt_detach first)";
-    return "";
-}
-
-extern "C" int isingmc_states_set_cluster_every(isingmc_states *s, size_t k)
-{
-    if (!s) return fail(ISINGMC_ERR_INVALID, "NULL states");
-    if (k) {
-        const std::string why = cluster_obstacle(s);
-        if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
-        if (s->icm_every) return fail(ISINGMC_ERR_INVALID, "isoenergetic cluster moves are switched on for this container (isingmc_states_set_icm_every): one non-local move at a time");
-    }
-    s->cluster_every = k;
-    return ISINGMC_OK;
-}
-
-extern "C" int isingmc_states_cluster_every(const isingmc_states *s, size_t *k_out)
-{
-    if (!s || !k_out) return fail(ISINGMC_ERR_INVALID, "NULL argument");
-    *k_out = s->cluster_every;
-    return ISINGMC_OK;
-}
-
-extern "C" int isingmc_cluster_stats(isingmc_states *s, uint64_t *n_clusters_out, uint64_t *largest_out)
-{
-    if (!s || !n_clusters_out || !largest_out) return fail(ISINGMC_ERR_INVALID, "NULL argument");
-    if (!s->cl_have_stats || s->cl_stats_cap < counter_slots(s)) return fail(ISINGMC_ERR_INVALID, "no cluster step has run on these replicas yet");
-    TRY(use_device(s->g->device));
-    std::vector<uint32_t> h;
-    TRY(read_back(s, h, s->d_cl_stats, 2 * counter_slots(s)));
-    for (size_t r = 0; r < s->R; r++) { // (packed: one pair per (group, bit) slot)
-        n_clusters_out[r] = h[2 * counter_slot(s, r)];
-        largest_out[r] = h[2 * counter_slot(s, r) + 1];
-    }
-    return ISINGMC_OK;
-}
-
-// T = floor((1 - exp(-2 beta |J|)) 2^32) in f64 (expm1 of glibc, as the tests' restatement); 2^32 = always, 0 = never
-static uint64_t cluster_threshold(double beta, double jabs)
-{
-    if (!(beta > 0.0)) return 0;
-    return uint64_t(std::floor(std::ldexp(-std::expm1(-2.0 * beta * jabs), 32)));
-}
-
-static bool is_cluster_step(const isingmc_states *s) { return s->cluster_every && s->t % s->cluster_every == s->cluster_every - 1; }
-
-// the same on a replica-packed bit-sliced container: batches of whole replica groups; every bit of a group is
-// simulated, owned or not, as by the sweeps
-static int run_cluster_packed(StepRun &c, size_t k0)
-{
-    isingmc_states *s = c.s;
-    const isingmc_graph *g = s->g;
-    const size_t groups = s->groups, slots = s->pk_slots(), n_pos = g->pk.n_pos;
-    if (!c.pk_cl.labels) {
-        const size_t words = pk_cluster_words_per_group(n_pos);
-        c.cl_batch = std::min<size_t>({groups, size_t(32768), std::max<size_t>(1, size_t(std::max(1, s->opt.cluster_workspace_bytes)) / (words * sizeof(uint32_t)))});
-        uint32_t *block = nullptr;
-        TRY(c.scratch.alloc(&block, c.cl_batch * words));
-        c.pk_cl.labels = block;
-        c.pk_cl.sizes = c.pk_cl.labels + c.cl_batch * n_pos * 32;
-        c.pk_cl.bonds = c.pk_cl.sizes + c.cl_batch * n_pos * 32;
-        c.pk_cl.fliptab = c.pk_cl.bonds + c.cl_batch * n_pos * PK_MAX_DEG;
-    }
-    if (s->cl_stats_cap < slots) { // (the groups of a packed container are fixed for its life: allocated once)
-        HIP_TRY(stream_quiesce(s->stream));
-        if (s->d_cl_stats) HIP_TRY(cached_free(s->d_cl_stats));
-        s->d_cl_stats = nullptr;
-        s->cl_stats_cap = 0;
-        TRY(dev_alloc(&s->d_cl_stats, 2 * slots));
-        s->cl_stats_cap = slots;
-    }
-    uint64_t thr = 0;
-    if (!s->has_betas) thr = cluster_threshold(c.betas[k0 * c.beta_stride], g->jabs);
-    else if (!c.d_cl_thr) { // per-replica betas do not change inside a call; bits this shard does not own take the nearest owned replica's
-        c.h_cl_thr.resize(slots);
-        for (size_t sl = 0; sl < slots; sl++)
-            c.h_cl_thr[sl] = cluster_threshold(s->betas[sl < s->pk_bit0 ? 0 : std::min(s->R - 1, sl - s->pk_bit0)], g->jabs);
-        TRY(c.scratch.alloc(&c.d_cl_thr, slots));
-        HIP_TRY(hipMemcpyAsync(c.d_cl_thr, c.h_cl_thr.data(), slots * sizeof(uint64_t), hipMemcpyHostToDevice, s->stream));
-    }
-    HIP_TRY(hipMemsetAsync(s->d_cl_stats, 0, 2 * slots * sizeof(uint32_t), s->stream));
-    for (size_t g0 = 0; g0 < groups; g0 += c.cl_batch) {
-        const size_t n = std::min(c.cl_batch, groups - g0);
-        HIP_TRY(pk_cluster_launch_step(s->stream, s->d_state + g0 * n_pos, g->pk, s->t, s->d_keys + g0, thr, c.d_cl_thr ? c.d_cl_thr + 32 * g0 : nullptr,
-                                       c.pk_cl, uint32_t(n), s->d_cl_stats + 2 * 32 * g0));
-    }
-    s->cl_have_stats = true;
-    s->t++;
-    if (c.d_counts) TRY(measure_enqueue(s, c.d_counts, nullptr, nullptr, /*want_up=*/false)); // the energy after this timestep: step 0 of the chunk
-    return ISINGMC_OK;
-}
-
-// timestep s->t (= step k0 of the call) as a cluster step of every replica, batch by batch on the main stream
-static int run_cluster(StepRun &c, size_t k0)
-{
-    isingmc_states *s = c.s;
-    const isingmc_graph *g = s->g;
-    const size_t R = s->R;
-    if (s->n_lanes > 1) TRY(lanes_join(s)); // the Metropolis stretch before this step may have run on replica lanes
-    if (s->packed) return run_cluster_packed(c, k0);
-    if (!c.cl.labels) {
-        const size_t words = cluster_words_per_replica(g->nvars);
-        c.cl_batch = std::min<size_t>({R, size_t(32768), std::max<size_t>(1, size_t(std::max(1, s->opt.cluster_workspace_bytes)) / (words * sizeof(uint32_t)))});
-        uint32_t *block = nullptr;
-        TRY(c.scratch.alloc(&block, c.cl_batch * words));
-        c.cl.labels = block;
-        c.cl.sizes = c.cl.labels + c.cl_batch * g->nvars;
-        c.cl.bonds = c.cl.sizes + c.cl_batch * g->nvars;
-        c.cl.fliptab = c.cl.bonds + c.cl_batch * (g->nvars / 16);
-    }
-    if (s->cl_stats_cap < R) {
-        HIP_TRY(stream_quiesce(s->stream)); // the old block is recycled
-        if (s->d_cl_stats) HIP_TRY(cached_free(s->d_cl_stats));
-        s->d_cl_stats = nullptr;
-        s->cl_stats_cap = 0;
-        TRY(dev_alloc(&s->d_cl_stats, 2 * s->cap));
-        s->cl_stats_cap = s->cap;
-    }
-    uint64_t thr = 0;
-    if (!s->has_betas) thr = cluster_threshold(c.betas[k0 * c.beta_stride], g->jabs);
-    else if (!c.d_cl_thr) { // per-replica betas do not change inside a call
-        c.h_cl_thr.resize(R);
-        for (size_t r = 0; r < R; r++) c.h_cl_thr[r] = cluster_threshold(s->betas[r], g->jabs);
-        TRY(c.scratch.alloc(&c.d_cl_thr, R));
-        HIP_TRY(hipMemcpyAsync(c.d_cl_thr, c.h_cl_thr.data(), R * sizeof(uint64_t), hipMemcpyHostToDevice, s->stream));
-    }
-    HIP_TRY(hipMemsetAsync(s->d_cl_stats, 0, 2 * R * sizeof(uint32_t), s->stream));
-    for (size_t r0 = 0; r0 < R; r0 += c.cl_batch) {
-        const size_t n = std::min(c.cl_batch, R - r0);
-        HIP_TRY(cluster_launch_step(s->stream, s->d_state + r0 * g->state_words, g->geom, s->t, s->d_keys + r0, g->jneg_uniform, thr,
-                                    c.d_cl_thr ? c.d_cl_thr + r0 : nullptr, c.cl, uint32_t(n), s->d_cl_stats + 2 * r0));
-    }
-    s->cl_have_stats = true;
-    s->t++;
-    if (c.d_counts) lat_measure_enqueue(s, c.d_counts, 2 * c.P.step_slots); // the energy after this timestep: counter slot 0 of step 0 of the chunk
-    return ISINGMC_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Isoenergetic cluster moves between replica pairs (cluster_kernels.hip; S12 on replica-packed containers of both
-// families, packed_icm_kernels.hip)
-// ------------------------------------------------------------------------------------------------
-
-// why this container cannot take isoenergetic cluster moves ("" when it can)
-static std::string icm_obstacle(const isingmc_states *s)
-{
-    const isingmc_graph *g = s->g;
-    if (s->packed) { // S12: any graph of either packed family (the move reads no coupling and no bias)
-        if (s->cluster_every)
-            return "Swendsen-Wang cluster updates are switched on for this replica-packed general-graph container (isingmc_states_set_cluster_every): "
-                   "one non-local move at a time";
-    } else {
-        if (g->kind != ISINGMC_KIND_LATTICE2D)
-            return "isoenergetic cluster moves need a container on the checkerboard lattice path; this graph runs on a general-graph kernel family";
-        if (g->mc_mode == MC_FIELD || g->mc_mode == MC_FIELD_OPEN) return "isoenergetic cluster moves are not implemented for lattices with a field";
-        if (g->mc_mode == MC_OPEN) return "isoenergetic cluster moves are not implemented for open boundaries (periodic lattices only)";
-        if (g->mc_mode != MC_NONE) return "isoenergetic cluster moves are not implemented for anisotropic couplings (|Jx| != |Jy|)";
-        if (g->nvars >= 0xFFFFFFFFull) return "isoenergetic cluster moves label sites with 32 bits: W H must be below 2^32 - 1";
-    }
-    if (s->pt_attached) return "a tempering ladder is attached to this container (isingmc_pt_detach first)";
-    if (s->cluster_every) return "Swendsen-Wang cluster updates are switched on for this container (isingmc_states_set_cluster_every): one non-local move at a time";
-    // pairs are (2 p, 2 p + 1) of the GLOBAL experiment index: a shard must hold both replicas of every pair it touches
-    // (packed: the pair is then bits (2 j, 2 j + 1) of one state word, pk_bit0 = first % 32 being even)
-    if (s->first % 2) return "this shard starts at an odd experiment index: its first replica's partner lives on another shard";
-    if ((s->first + s->R) % 2 && s->first + s->R < s->n_total) return "this shard ends inside a pair: its last replica's partner lives on another shard";
-    if (s->has_betas && icm_unequal_pair_betas(s, s->betas.data()))
-        return "per-replica betas differ inside a pair: the two replicas of every pair (2 p, 2 p + 1) need equal betas";
-    return "";
-}
-
-extern "C" int isingmc_states_set_icm_every(isingmc_states *s, size_t k)
-{
-    if (!s) return fail(ISINGMC_ERR_INVALID, "NULL states");
-    if (k) {
-        const std::string why = icm_obstacle(s);
-        if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
-    }
-    s->icm_every = k;
-    return ISINGMC_OK;
-}
-
-extern "C" int isingmc_states_icm_every(const isingmc_states *s, size_t *k_out)
-{
-    if (!s || !k_out) return fail(ISINGMC_ERR_INVALID, "NULL argument");
-    *k_out = s->icm_every;
-    return ISINGMC_OK;
-}
-
-extern "C" int isingmc_icm_stats(isingmc_states *s, uint64_t *n_clusters_out, uint64_t *largest_out, uint64_t *minus_sites_out)
-{
-    if (!s || !n_clusters_out || !largest_out || !minus_sites_out) return fail(ISINGMC_ERR_INVALID, "NULL argument");
-    const size_t pairs = s->R / 2, slot0 = s->packed ? s->pk_bit0 / 2 : 0; // (packed: device slot 16 group + pair; pk_bit0 is even)
-    if (!s->icm_have_stats || s->icm_stats_cap < slot0 + pairs) return fail(ISINGMC_ERR_INVALID, "no isoenergetic cluster move has run on these replicas yet");
-    TRY(use_device(s->g->device));
-    std::vector<uint32_t> h;
-    TRY(read_back(s, h, s->d_icm_stats, 3 * s->icm_stats_cap));
-    for (size_t p = 0; p < pairs; p++) {
-        n_clusters_out[p] = h[2 * (slot0 + p)];
-        largest_out[p] = h[2 * (slot0 + p) + 1];
-        minus_sites_out[p] = h[2 * s->icm_stats_cap + slot0 + p];
-    }
-    return ISINGMC_OK;
-}
-
-static bool is_icm_step(const isingmc_states *s) { return s->icm_every && s->t % s->icm_every == s->icm_every - 1; }
-
-// the same on a replica-packed container of either family: batches of whole replica groups, 16 pairs each; pair j
-// of GLOBAL group G moves when both its experiments exist (32 G + 2 j + 1 < n_total), owned by this shard or not
-static int run_icm_packed(StepRun &c)
-{
-    isingmc_states *s = c.s;
-    const isingmc_graph *g = s->g;
-    const size_t groups = s->groups, pair_slots = 16 * groups, n_pos = g->pk.n_pos;
-    if (!c.pk_icm.labels) {
-        const size_t words = pk_icm_words_per_group(n_pos);
-        c.cl_batch = std::min<size_t>({groups, size_t(32768), std::max<size_t>(1, size_t(std::max(1, s->opt.cluster_workspace_bytes)) / (words * sizeof(uint32_t)))});
-        uint32_t *block = nullptr;
-        TRY(c.scratch.alloc(&block, c.cl_batch * words));
-        c.pk_icm.labels = block;
-        c.pk_icm.sizes = c.pk_icm.labels + c.cl_batch * n_pos * 16;
-        c.pk_icm.fliptab = c.pk_icm.sizes + c.cl_batch * n_pos * 16;
-        c.h_icm_mask.resize(groups);
-        const size_t G0 = s->first / 32;
-        for (size_t gi = 0; gi < groups; gi++) {
-            uint32_t m = 0;
-            for (size_t j = 0; j < 16; j++)
-                if (32 * (G0 + gi) + 2 * j + 1 < s->n_total) m |= 1u << (2 * j);
-            c.h_icm_mask[gi] = m;
-        }
-        TRY(c.scratch.alloc(&c.d_icm_mask, groups));
-        HIP_TRY(hipMemcpyAsync(c.d_icm_mask, c.h_icm_mask.data(), groups * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream)); // (h_icm_mask lives as long as the call)
-    }
-    if (s->icm_stats_cap < pair_slots) { // (the groups of a packed container are fixed for its life: allocated once)
-        HIP_TRY(stream_quiesce(s->stream));
-        if (s->d_icm_stats) HIP_TRY(cached_free(s->d_icm_stats));
-        s->d_icm_stats = nullptr;
-        s->icm_stats_cap = 0;
-        TRY(dev_alloc(&s->d_icm_stats, 3 * pair_slots));
-        s->icm_stats_cap = pair_slots;
-    }
-    HIP_TRY(hipMemsetAsync(s->d_icm_stats, 0, 3 * s->icm_stats_cap * sizeof(uint32_t), s->stream));
-    for (size_t g0 = 0; g0 < groups; g0 += c.cl_batch) {
-        const size_t n = std::min(c.cl_batch, groups - g0);
-        HIP_TRY(pk_icm_launch_step(s->stream, s->d_state + g0 * n_pos, g->pk, s->rj ? g->rj.nbr : nullptr, s->rj ? g->rj.slots : 0, s->t, s->d_keys + g0,
-                                   c.d_icm_mask + g0, c.pk_icm, uint32_t(n), s->d_icm_stats + 2 * 16 * g0, s->d_icm_stats + 2 * s->icm_stats_cap + 16 * g0));
-    }
-    s->icm_have_stats = true;
-    s->t++;
-    if (c.d_counts) TRY(measure_enqueue(s, c.d_counts, nullptr, nullptr, /*want_up=*/false)); // the energy after this timestep: step 0 of the chunk
-    return ISINGMC_OK;
-}
-
-// timestep s->t as an isoenergetic cluster move of every pair, batch by batch on the main stream; a last replica without a
-// partner stays as it is
-static int run_icm(StepRun &c)
-{
-    isingmc_states *s = c.s;
-    const isingmc_graph *g = s->g;
-    const size_t pairs = s->R / 2;
-    if (s->n_lanes > 1) TRY(lanes_join(s)); // the Metropolis stretch before this step may have run on replica lanes
-    if (s->packed) return run_icm_packed(c);
-    if (pairs && !c.cl.labels) { // one labelling problem per PAIR
-        const size_t words = cluster_words_per_replica(g->nvars);
-        c.cl_batch = std::min<size_t>({pairs, size_t(32768), std::max<size_t>(1, size_t(std::max(1, s->opt.cluster_workspace_bytes)) / (words * sizeof(uint32_t)))});
-        uint32_t *block = nullptr;
-        TRY(c.scratch.alloc(&block, c.cl_batch * words));
-        c.cl.labels = block;
-        c.cl.sizes = c.cl.labels + c.cl_batch * g->nvars;
-        c.cl.bonds = c.cl.sizes + c.cl_batch * g->nvars;
-        c.cl.fliptab = c.cl.bonds + c.cl_batch * (g->nvars / 16);
-    }
-    if (!s->d_icm_stats || s->icm_stats_cap < pairs) {
-        HIP_TRY(stream_quiesce(s->stream)); // the old block is recycled
-        if (s->d_icm_stats) HIP_TRY(cached_free(s->d_icm_stats));
-        s->d_icm_stats = nullptr;
-        s->icm_stats_cap = 0;
-        const size_t cap = std::max<size_t>(1, s->cap / 2);
-        TRY(dev_alloc(&s->d_icm_stats, 3 * cap));
-        s->icm_stats_cap = cap;
-    }
-    HIP_TRY(hipMemsetAsync(s->d_icm_stats, 0, 3 * s->icm_stats_cap * sizeof(uint32_t), s->stream));
-    for (size_t p0 = 0; p0 < pairs; p0 += c.cl_batch) {
-        const size_t n = std::min(c.cl_batch, pairs - p0);
-        HIP_TRY(icm_launch_step(s->stream, s->d_state + 2 * p0 * g->state_words, g->geom, s->t, s->d_keys + 2 * p0, c.cl, uint32_t(n),
-                                s->d_icm_stats + 2 * p0, s->d_icm_stats + 2 * s->icm_stats_cap + p0));
-    }
-    s->icm_have_stats = true;
-    s->t++;
-    if (c.d_counts) lat_measure_enqueue(s, c.d_counts, 2 * c.P.step_slots); // the energy after this timestep: counter slot 0 of step 0 of the chunk
-    return ISINGMC_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Isoenergetic cluster moves between two containers (cluster_kernels.hip): the move of S9 with pair p =
-// (slot slots_a[p] of a, slot slots_b[p] of b) -- what two tempering ladders over the same betas need, whose rung permutations
-// live on the device.  Two replica-packed containers of one family take the same call in the form of DESIGN.md S13
-// (packed_between_kernels.hip)
-// ------------------------------------------------------------------------------------------------
-
-// why these two containers cannot take a move between them ("" when they can): icm_obstacle without its ladder and shard clauses
-static std::string icm_between_obstacle(const isingmc_states *a, const isingmc_states *b)
-{
-    if (a == b) return "an isoenergetic cluster move between two containers needs two different containers";
-    if (a->g != b->g) return "the two containers belong to different graph handles: both must be replicas of one isingmc_graph";
-    const isingmc_graph *g = a->g; // (one graph handle: one device)
-    if (a->packed && b->packed) { // S13: any graph of either packed family, both containers on the same one
-        if (a->rj != b->rj)
-            return "the two containers run on different kernel families (one on the replica-packed bit-sliced family, the other on the "
-                   "replica-packed real-coupling family): a move between containers needs both on the same family";
-    } else {
-        if (g->kind != ISINGMC_KIND_LATTICE2D || a->packed || b->packed)
-            return "isoenergetic cluster moves need containers on the checkerboard lattice path; this graph runs on a general-graph kernel family";
-        if (g->mc_mode == MC_FIELD || g->mc_mode == MC_FIELD_OPEN) return "isoenergetic cluster moves are not implemented for lattices with a field";
-        if (g->mc_mode == MC_OPEN) return "isoenergetic cluster moves are not implemented for open boundaries (periodic lattices only)";
-        if (g->mc_mode != MC_NONE) return "isoenergetic cluster moves are not implemented for anisotropic couplings (|Jx| != |Jy|)";
-        if (g->nvars >= 0xFFFFFFFFull) return "isoenergetic cluster moves label sites with 32 bits: W H must be below 2^32 - 1";
-    }
-    for (const isingmc_states *s : {a, b}) {
-        if (s->cluster_every) return "Swendsen-Wang cluster updates are switched on for one of the containers (isingmc_states_set_cluster_every): one non-local move at a time";
-        if (s->icm_every) return "isoenergetic cluster moves inside one of the containers are switched on (isingmc_states_set_icm_every): one non-local move at a time";
-    }
-    if (a->t != b->t) return "the two containers stand at unequal timesteps: the move is timestep t of both";
-    return "";
-}
-
-// the move between two replica-packed containers of one family (packed_between_kernels.hip) behind the checks of
-// isingmc_icm_between: batches of whole pair blocks (32 pairs each) under a's cluster_workspace_bytes.  slots_a == nullptr: the
-// two ladders' permutations on the device.
-static int icm_between_packed(isingmc_states *a, isingmc_states *b, const uint32_t *slots_a, const uint32_t *slots_b, size_t n_pairs)
-{
-    const isingmc_graph *g = a->g;
-    const size_t n_pos = g->pk.n_pos, blocks = (n_pairs + 31) / 32;
-    // workspace, tables, statistics and events stay with `a`: nothing below waits for the device unless one of them grows
-    const size_t words = pk_between_words_per_block(n_pos);
-    const size_t batch = std::min<size_t>({blocks, size_t(32768), std::max<size_t>(1, size_t(std::max(1, a->opt.cluster_workspace_bytes)) / (words * sizeof(uint32_t)))});
-    if (!a->d_icmb_work || a->icmb_batch != batch) {
-        HIP_TRY(stream_quiesce(a->stream)); // the old block is recycled
-        if (a->d_icmb_work) HIP_TRY(cached_free(a->d_icmb_work));
-        a->d_icmb_work = nullptr;
-        a->icmb_batch = 0;
-        TRY(dev_alloc(&a->d_icmb_work, batch * words));
-        a->icmb_batch = batch;
-    }
-    const size_t inv_words = 32 * (a->groups + b->groups);
-    if (a->icmb_inv_cap < inv_words) {
-        HIP_TRY(stream_quiesce(a->stream));
-        if (a->d_icmb_inv) HIP_TRY(cached_free(a->d_icmb_inv));
-        a->d_icmb_inv = nullptr;
-        a->icmb_inv_cap = 0;
-        TRY(dev_alloc(&a->d_icmb_inv, inv_words));
-        a->icmb_inv_cap = inv_words;
-    }
-    if (a->icmb_cap < n_pairs) {
-        HIP_TRY(stream_quiesce(a->stream));
-        for (uint32_t **p : {&a->d_icmb_slots, &a->d_icmb_stats}) {
-            if (*p) HIP_TRY(cached_free(*p));
-            *p = nullptr;
-        }
-        a->icmb_cap = 0;
-        a->icmb_have_stats = false;
-        const size_t cap = std::max(n_pairs, a->cap);
-        TRY(dev_alloc(&a->d_icmb_slots, 2 * cap));
-        TRY(dev_alloc(&a->d_icmb_stats, 3 * cap));
-        a->icmb_cap = cap;
-    }
-    for (hipEvent_t &ev : a->icmb_ev)
-        if (!ev) HIP_TRY(pooled_event_create(&ev, true));
-    PkBetweenWork work;
-    work.labels = a->d_icmb_work;
-    work.sizes = work.labels + batch * n_pos * 32;
-    work.d = work.sizes + batch * n_pos * 32;
-    work.f = work.d + batch * n_pos;
-    work.fliptab = work.f + batch * n_pos;
-    const uint32_t *d_sa = a->d_pt_perm, *d_sb = b->d_pt_perm;
-    if (slots_a) {
-        HIP_TRY(hipMemcpyAsync(a->d_icmb_slots, slots_a, n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, a->stream));
-        HIP_TRY(hipMemcpyAsync(a->d_icmb_slots + a->icmb_cap, slots_b, n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, a->stream));
-        d_sa = a->d_icmb_slots;
-        d_sb = a->d_icmb_slots + a->icmb_cap;
-    }
-    const PkBetweenSide A{a->d_state, d_sa, a->d_icmb_inv, uint32_t(a->pk_bit0), uint32_t(a->R), uint32_t(a->groups)};
-    const PkBetweenSide B{b->d_state, d_sb, a->d_icmb_inv + 32 * a->groups, uint32_t(b->pk_bit0), uint32_t(b->R), uint32_t(b->groups)};
-    HIP_TRY(hipEventRecord(a->icmb_ev[0], b->stream)); // b's sweeps and exchange rounds so far ...
-    HIP_TRY(hipStreamWaitEvent(a->stream, a->icmb_ev[0], 0)); // ... before a's stream touches b's words and permutation
-    HIP_TRY(hipMemsetAsync(a->d_icmb_stats, 0, 3 * a->icmb_cap * sizeof(uint32_t), a->stream));
-    HIP_TRY(pk_between_launch_tables(a->stream, A, B, uint32_t(n_pairs)));
-    for (size_t b0 = 0; b0 < blocks; b0 += batch) {
-        const size_t n = std::min(batch, blocks - b0);
-        HIP_TRY(pk_between_launch_batch(a->stream, A, B, g->pk, a->rj ? g->rj.nbr : nullptr, a->rj ? g->rj.slots : 0, a->t, a->d_keys, work, uint32_t(b0),
-                                        uint32_t(n), uint32_t(n_pairs), a->d_icmb_stats, a->d_icmb_stats + 2 * a->icmb_cap));
-    }
-    HIP_TRY(hipEventRecord(a->icmb_ev[1], a->stream));
-    HIP_TRY(hipStreamWaitEvent(b->stream, a->icmb_ev[1], 0)); // b goes on with the new configurations
-    a->icmb_pairs = n_pairs;
-    a->icmb_have_stats = true;
-    for (isingmc_states *s : {a, b}) {
-        s->t++;
-        s->meas_fresh = false; // cached ladder energies belong to the configurations before the move
-    }
-    return ISINGMC_OK;
-}
-
-extern "C" int isingmc_icm_between(isingmc_states *a, isingmc_states *b, const uint32_t *slots_a, const uint32_t *slots_b, size_t n_pairs)
-{
-    if (!a || !b) return fail(ISINGMC_ERR_INVALID, "NULL states");
-    {
-        const std::string why = icm_between_obstacle(a, b);
-        if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
-    }
-    if ((slots_a == nullptr) != (slots_b == nullptr)) return fail(ISINGMC_ERR_INVALID, "give both slot tables or neither");
-    const isingmc_graph *g = a->g;
-    const bool ladders = slots_a == nullptr;
-    if (ladders) { // pair r = (a's rung r, b's rung r): the permutations are read on the device
-        if (!a->pt_attached || !b->pt_attached) return fail(ISINGMC_ERR_INVALID, "without slot tables both containers need an attached tempering ladder (isingmc_pt_attach)");
-        for (const isingmc_states *s : {a, b})
-            if (s->pt_world != 1 || s->pt.slot_offset != 0 || s->pt.n_rungs != s->R)
-                return fail(ISINGMC_ERR_INVALID, "without slot tables each ladder must live on its container alone (world size 1, one slot per rung): sharded ladders are not served");
-        if (a->pt.n_rungs != b->pt.n_rungs) return fail(ISINGMC_ERR_INVALID, "the two ladders differ in their number of rungs");
-        if (a->ladder_betas.size() != b->ladder_betas.size() ||
-            std::memcmp(a->ladder_betas.data(), b->ladder_betas.data(), a->ladder_betas.size() * sizeof(double)) != 0)
-            return fail(ISINGMC_ERR_INVALID, "the two ladders differ in their betas: the replicas of a pair need equal betas");
-        if (n_pairs != a->R) return fail(ISINGMC_ERR_INVALID, "without slot tables n_pairs must be the number of rungs");
-    } else {
-        if (n_pairs > a->R || n_pairs > b->R) return fail(ISINGMC_ERR_INVALID, "more pairs than replicas");
-        std::vector<uint8_t> seen_a(a->R, 0), seen_b(b->R, 0);
-        for (size_t p = 0; p < n_pairs; p++) {
-            if (slots_a[p] >= a->R || slots_b[p] >= b->R) return fail(ISINGMC_ERR_INVALID, "slot out of range");
-            if (seen_a[slots_a[p]]++ || seen_b[slots_b[p]]++) return fail(ISINGMC_ERR_INVALID, "a duplicate slot: every replica belongs to at most one pair");
-        }
-        // per-replica betas set by the host are known here; a ladder relabels them on the device (the caller pairs equal rungs)
-        if (a->has_betas != b->has_betas && !a->pt_attached && !b->pt_attached)
-            return fail(ISINGMC_ERR_INVALID, "per-replica betas are set on one container only: the replicas of a pair need equal betas");
-        if (a->has_betas && b->has_betas && !a->pt_attached && !b->pt_attached)
-            for (size_t p = 0; p < n_pairs; p++)
-                if (std::memcmp(&a->betas[slots_a[p]], &b->betas[slots_b[p]], sizeof(double)) != 0)
-                    return fail(ISINGMC_ERR_INVALID, "per-replica betas differ inside a pair: the two replicas of every pair need equal betas");
-    }
-    TRY(use_device(g->device));
-    if (n_pairs == 0) { // time passes all the same
-        a->t++;
-        b->t++;
-        return ISINGMC_OK;
-    }
-    for (isingmc_states *s : {a, b})
-        if (s->n_lanes > 1) TRY(lanes_join(s));
-    if (a->packed) return icm_between_packed(a, b, slots_a, slots_b, n_pairs);
-    // workspace, tables, statistics and events stay with `a`: nothing below waits for the device unless one of them grows
-    const size_t words = cluster_words_per_replica(g->nvars);
-    const size_t batch = std::min<size_t>({n_pairs, size_t(32768), std::max<size_t>(1, size_t(std::max(1, a->opt.cluster_workspace_bytes)) / (words * sizeof(uint32_t)))});
-    if (!a->d_icmb_work || a->icmb_batch != batch) {
-        HIP_TRY(stream_quiesce(a->stream)); // the old block is recycled
-        if (a->d_icmb_work) HIP_TRY(cached_free(a->d_icmb_work));
-        a->d_icmb_work = nullptr;
-        a->icmb_batch = 0;
-        TRY(dev_alloc(&a->d_icmb_work, batch * words));
-        a->icmb_batch = batch;
-    }
-    if (a->icmb_cap < n_pairs) {
-        HIP_TRY(stream_quiesce(a->stream));
-        for (uint32_t **p : {&a->d_icmb_slots, &a->d_icmb_stats}) {
-            if (*p) HIP_TRY(cached_free(*p));
-            *p = nullptr;
-        }
-        a->icmb_cap = 0;
-        a->icmb_have_stats = false;
-        const size_t cap = std::max(n_pairs, a->cap);
-        TRY(dev_alloc(&a->d_icmb_slots, 2 * cap));
-        TRY(dev_alloc(&a->d_icmb_stats, 3 * cap));
-        a->icmb_cap = cap;
-    }
-    for (hipEvent_t &ev : a->icmb_ev)
-        if (!ev) HIP_TRY(pooled_event_create(&ev, true));
-    ClusterWork cl;
-    cl.labels = a->d_icmb_work;
-    cl.sizes = cl.labels + batch * g->nvars;
-    cl.bonds = cl.sizes + batch * g->nvars;
-    cl.fliptab = cl.bonds + batch * (g->nvars / 16);
-    const uint32_t *d_sa = a->d_pt_perm, *d_sb = b->d_pt_perm;
-    if (!ladders) {
-        HIP_TRY(hipMemcpyAsync(a->d_icmb_slots, slots_a, n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, a->stream));
-        HIP_TRY(hipMemcpyAsync(a->d_icmb_slots + a->icmb_cap, slots_b, n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, a->stream));
-        d_sa = a->d_icmb_slots;
-        d_sb = a->d_icmb_slots + a->icmb_cap;
-    }
-    HIP_TRY(hipEventRecord(a->icmb_ev[0], b->stream)); // b's sweeps and exchange rounds so far ...
-    HIP_TRY(hipStreamWaitEvent(a->stream, a->icmb_ev[0], 0)); // ... before a's stream touches b's planes and permutation
-    HIP_TRY(hipMemsetAsync(a->d_icmb_stats, 0, 3 * a->icmb_cap * sizeof(uint32_t), a->stream));
-    for (size_t p0 = 0; p0 < n_pairs; p0 += batch) {
-        const size_t n = std::min(batch, n_pairs - p0);
-        HIP_TRY(icm_between_launch_step(a->stream, a->d_state, b->d_state, d_sa + p0, d_sb + p0, g->geom, a->t, a->d_keys, cl, uint32_t(n),
-                                        a->d_icmb_stats + 2 * p0, a->d_icmb_stats + 2 * a->icmb_cap + p0));
-    }
-    HIP_TRY(hipEventRecord(a->icmb_ev[1], a->stream));
-    HIP_TRY(hipStreamWaitEvent(b->stream, a->icmb_ev[1], 0)); // b goes on with the new configurations
-    a->icmb_pairs = n_pairs;
-    a->icmb_have_stats = true;
-    for (isingmc_states *s : {a, b}) {
-        s->t++;
-        s->meas_fresh = false; // energies a strip launch left behind belong to the configurations before the move
-    }
-    return ISINGMC_OK;
-}
-
-extern "C" int isingmc_icm_between_stats(isingmc_states *a, uint64_t *n_clusters_out, uint64_t *largest_out, uint64_t *minus_sites_out, size_t n_pairs)
-{
-    if (!a || !n_clusters_out || !largest_out || !minus_sites_out) return fail(ISINGMC_ERR_INVALID, "NULL argument");
-    if (!a->icmb_have_stats) return fail(ISINGMC_ERR_INVALID, "no isoenergetic cluster move between containers has been called on this container yet");
-    if (n_pairs != a->icmb_pairs) return fail(ISINGMC_ERR_INVALID, "n_pairs differs from the number of pairs of the last move");
-    TRY(use_device(a->g->device));
-    std::vector<uint32_t> h;
-    TRY(read_back(a, h, a->d_icmb_stats, 3 * a->icmb_cap));
-    for (size_t p = 0; p < n_pairs; p++) {
-        n_clusters_out[p] = h[2 * p];
-        largest_out[p] = h[2 * p + 1];
-        minus_sites_out[p] = h[2 * a->icmb_cap + p];
-    }
+    if (!c.d_counts) return ISINGMC_OK;
+    if (c.s->packed) return measure_enqueue(c.s, c.d_counts, nullptr, nullptr, /*want_up=*/false);
+    lat_measure_enqueue(c.s, c.d_counts, 2 * c.P.step_slots);
     return ISINGMC_OK;
 }
 
@@ -2136,8 +1570,8 @@ static int run_steps_impl(isingmc_states *s, size_t timesteps, const double *bet
         }
         if (c.d_counts && P.path != StepPath::Packed) // (measure_enqueue clears the packed counters itself)
             HIP_TRY(hipMemsetAsync(c.d_counts, 0, nk * R * P.step_slots * 2 * sizeof(unsigned long long), s->stream));
-        if (cluster) rc = run_cluster(c, k0);
-        else if (icm) rc = run_icm(c);
+        if (cluster) rc = run_cluster_step(s, c.nonlocal, c.scratch, step_beta(c, k0));
+        else if (icm) rc = run_icm_step(s, c.nonlocal, c.scratch);
         else switch (P.path) {
         case StepPath::Packed: rc = run_packed(c, k0, nk); break;
         case StepPath::LatResident: rc = run_lat_resident(c, k0, nk); break;
@@ -2148,6 +1582,7 @@ static int run_steps_impl(isingmc_states *s, size_t timesteps, const double *bet
         case StepPath::GenResident: rc = run_gen_resident(c, k0, nk); break;
         case StepPath::GenCsr: rc = run_gen_csr(c, k0, nk); break;
         }
+        if (rc == ISINGMC_OK && (cluster || icm)) rc = measure_nonlocal_step(c);
         if (rc == ISINGMC_OK && energies_per_step) rc = read_step_energies(c, k0, nk);
     }
     if (s->n_lanes > 1) { const int jrc = lanes_join(s); if (rc == ISINGMC_OK) rc = jrc; }

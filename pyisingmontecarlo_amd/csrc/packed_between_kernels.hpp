@@ -6,6 +6,7 @@
 // tuned sweep kernels).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <array>
 #include <cstddef>
 #include <cstdint>
 
@@ -25,7 +26,19 @@ struct PkBetweenWork {
     uint32_t *fliptab; // [n][32][n_pos / 32]  one flip bit per (pair lane, possible root position)
 };
 
-constexpr size_t pk_between_words_per_block(uint64_t n_pos) { return size_t(67 * n_pos); }
+// Words per block of {labels, sizes, d, f, fliptab}.  The members lie in this order, one behind the other, in the block of a batch: its
+// size (pk_between_words_per_block) and its carving (pk_between_carve) both follow from this one line.
+constexpr std::array<size_t, 5> pk_between_member_words(uint64_t n_pos) { return {{size_t(32 * n_pos), size_t(32 * n_pos), size_t(n_pos), size_t(n_pos), size_t(n_pos)}}; }
+constexpr size_t pk_between_words_per_block(uint64_t n_pos) { const std::array<size_t, 5> w = pk_between_member_words(n_pos); return w[0] + w[1] + w[2] + w[3] + w[4]; }
+static_assert(pk_between_words_per_block(256) == 67 * 256, "labels 32 n_pos | sizes 32 n_pos | d n_pos | f n_pos | fliptab n_pos");
+
+// the workspace of `batch` pair blocks in a block of batch * pk_between_words_per_block(n_pos) words
+static inline PkBetweenWork pk_between_carve(uint32_t *block, size_t batch, uint64_t n_pos)
+{
+    const std::array<size_t, 5> w = pk_between_member_words(n_pos);
+    uint32_t *const sizes = block + batch * w[0], *const d = sizes + batch * w[1], *const f = d + batch * w[2], *const fliptab = f + batch * w[3];
+    return PkBetweenWork{block, sizes, d, f, fliptab};
+}
 
 // one of the two containers as the kernels see it
 struct PkBetweenSide {

@@ -3,6 +3,7 @@
 // nothing here is instantiated beside the tuned sweep kernels).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <array>
 #include <cstddef>
 #include <cstdint>
 
@@ -24,7 +25,19 @@ struct PkClusterWork {
     uint32_t *fliptab; // [n][n_pos]             flip bits of the 32 replicas for every possible root
 };
 
-constexpr size_t pk_cluster_words_per_group(uint64_t n_pos) { return size_t((64 + PK_MAX_DEG + 1) * n_pos); }
+// Words per group of {labels, sizes, bonds, fliptab}.  The members lie in this order, one behind the other, in the block of a batch: its
+// size (pk_cluster_words_per_group) and its carving (pk_cluster_carve) both follow from this one line.
+constexpr std::array<size_t, 4> pk_cluster_member_words(uint64_t n_pos) { return {{size_t(32 * n_pos), size_t(32 * n_pos), size_t(PK_MAX_DEG * n_pos), size_t(n_pos)}}; }
+constexpr size_t pk_cluster_words_per_group(uint64_t n_pos) { const std::array<size_t, 4> w = pk_cluster_member_words(n_pos); return w[0] + w[1] + w[2] + w[3]; }
+static_assert(pk_cluster_words_per_group(256) == (64 + PK_MAX_DEG + 1) * 256, "labels 32 n_pos | sizes 32 n_pos | bonds PK_MAX_DEG n_pos | fliptab n_pos");
+
+// the workspace of `batch` groups in a block of batch * pk_cluster_words_per_group(n_pos) words
+static inline PkClusterWork pk_cluster_carve(uint32_t *block, size_t batch, uint64_t n_pos)
+{
+    const std::array<size_t, 4> w = pk_cluster_member_words(n_pos);
+    uint32_t *const sizes = block + batch * w[0], *const bonds = sizes + batch * w[1], *const fliptab = bonds + batch * w[2];
+    return PkClusterWork{block, sizes, bonds, fliptab};
+}
 
 // One cluster step of groups [0, n) at timestep t: state / group_keys / thr_per_slot / stats point at the first group of the
 // batch.  thr_per_slot == nullptr: every replica uses thr; else thr_per_slot[32 g + b].  stats: [32 n][2] = {clusters, largest

@@ -5,6 +5,7 @@
 // beside the tuned sweep kernels).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <array>
 #include <cstddef>
 #include <cstdint>
 
@@ -22,7 +23,19 @@ struct PkIcmWork {
     uint32_t *fliptab; // [n][n_pos / 2]  16 flip bits per possible root position: position r = half r & 1 of word r >> 1
 };
 
-constexpr size_t pk_icm_words_per_group(uint64_t n_pos) { return size_t(32 * n_pos + n_pos / 2); }
+// Words per group of {labels, sizes, fliptab}.  The members lie in this order, one behind the other, in the block of a batch: its
+// size (pk_icm_words_per_group) and its carving (pk_icm_carve) both follow from this one line.
+constexpr std::array<size_t, 3> pk_icm_member_words(uint64_t n_pos) { return {{size_t(16 * n_pos), size_t(16 * n_pos), size_t(n_pos / 2)}}; }
+constexpr size_t pk_icm_words_per_group(uint64_t n_pos) { const std::array<size_t, 3> w = pk_icm_member_words(n_pos); return w[0] + w[1] + w[2]; }
+static_assert(pk_icm_words_per_group(256) == 32 * 256 + 128, "labels 16 n_pos | sizes 16 n_pos | fliptab n_pos / 2");
+
+// the workspace of `batch` groups in a block of batch * pk_icm_words_per_group(n_pos) words
+static inline PkIcmWork pk_icm_carve(uint32_t *block, size_t batch, uint64_t n_pos)
+{
+    const std::array<size_t, 3> w = pk_icm_member_words(n_pos);
+    uint32_t *const sizes = block + batch * w[0], *const fliptab = sizes + batch * w[1];
+    return PkIcmWork{block, sizes, fliptab};
+}
 
 // One move of groups [0, n) at timestep t: state / group_keys / move_mask / stats / minus point at the first group of the batch.
 // move_mask[g]: bit 2 j set when pair j of group g moves.  nbr_rj == nullptr: the neighbours of G.nbr_ell (PK_MAX_DEG slots);

@@ -3,7 +3,7 @@
 // and run by tests/test_host_sanitizers.py (GPU AddressSanitizer is not available on the pool: the sanitizers run on
 // the CPU build only).  Every case also checks the invariants the device code relies on: a recognised lattice accounts
 // for every edge, the adjacency is symmetric and in range, the colouring is proper and its classes are whole
-// 256-position blocks, quantised couplings fit 31 bits per site, schedules are finite.
+// 256-position blocks, quantised couplings fit 31 bits per site, schedules are finite, a workspace batch fits its bytes.
 // usage: host_fuzz [cases] [seed]
 #include "host_logic.hpp"
 
@@ -335,6 +335,21 @@ void check_schedules(Rng &r, uint64_t case_no)
     for (size_t k = offset + size_t(W) * H; k < bytes.size(); k++) CHECK(bytes[k] == 0xEE);
 }
 
+// batch of a non-local move's labelling workspace: as many items as the bytes hold, within [1, min(items, 32768)]
+void check_batch(Rng &r, uint64_t case_no)
+{
+    const size_t items = 1 + size_t(r.below(r.coin() ? 64 : uint64_t(1) << 20));
+    const size_t words = 1 + size_t(r.below(r.coin() ? 4096 : uint64_t(1) << 26));
+    const size_t bytes = 1 + size_t(r.below(r.coin(0.2) ? 64 : (uint64_t(1) << 31) - 1)); // the option is a positive int
+    const size_t batch = nonlocal_batch(items, words, bytes);
+    const size_t most = std::min<size_t>(items, 32768);
+    CHECK(batch >= 1 && batch <= most);
+    CHECK(batch == 1 || batch * words * 4 <= bytes);
+    CHECK(batch == most || (batch + 1) * words * 4 > bytes); // the largest such value
+    // the expression every caller used to write out
+    CHECK(batch == std::min<size_t>({items, size_t(32768), std::max<size_t>(1, size_t(std::max(1, int(bytes))) / (words * sizeof(uint32_t)))}));
+}
+
 } // namespace
 
 int main(int argc, char **argv)
@@ -353,6 +368,7 @@ int main(int argc, char **argv)
             check_case(r, graph_case(r), false, false, case_no);
         }
         check_schedules(r, case_no);
+        check_batch(r, case_no);
     }
     uint32_t table[2049];
     rj_log_table(table);
