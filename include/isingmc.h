@@ -314,6 +314,31 @@ int isingmc_icm_between(isingmc_states *a, isingmc_states *b, const uint32_t *sl
  * uint64[n_pairs] each with n_pairs that of the call (synchronises) */
 int isingmc_icm_between_stats(isingmc_states *a, uint64_t *n_clusters_out, uint64_t *largest_out, uint64_t *minus_sites_out, size_t n_pairs);
 
+/* ---- Spin and link overlaps between replica pairs (no reference counterpart) ----
+ * Exact integers of the configurations as they are, counted on the device; for pair p of configurations (x, y) of one graph
+ *   spin_out[p] = sum_i s_i^x s_i^y                          over the nvars sites (sites in no edge count like any other)
+ *   link_out[p] = sum_e s_{a_e}^x s_{b_e}^x s_{a_e}^y s_{b_e}^y   one term per entry e of the edge list given at graph creation:
+ *     entries with zero coupling are included, duplicated entries are separate terms, and an entry with a_e == b_e (graph
+ *     creation accepts it and folds its J into a constant of the energy) is the constant term +1.
+ * The overlaps are q = spin / nvars and q_l = link / n_edges; no coupling and no bias is read.  int64[n_pairs] each;
+ * link_out == NULL skips all bond work, spin_out may not be NULL.
+ *   b == NULL or b == a: pairs inside one container.  Both tables NULL: the pairing of the isoenergetic moves -- the replicas with
+ *     GLOBAL experiment indices (2 p, 2 p + 1) form pair p, n_pairs must be count / 2, a last replica without a partner is left
+ *     out; a shard that starts at an odd experiment index is refused.
+ *   two containers, both tables NULL: pair p = (slot p of a, slot p of b), n_pairs <= the smaller count.
+ *   slots_a / slots_b: uint32[n_pairs] in host memory, pair p = (slot slots_a[p] of a, slot slots_b[p] of b); any slot below its
+ *     container's count, any number of times; a pair (r, r) is legal (spin = nvars, link = n_edges).
+ * The call synchronises.  It writes no configuration, consumes no random number and leaves the timestep counters alone; it asks
+ * for neither equal betas nor equal timesteps nor a cluster period, and works with a tempering ladder attached.  Workspace: 16
+ * bytes per pair; the tabled form on replica-packed containers also gathers 4 bytes per position and block of 32 pairs, batched
+ * under a's option "cluster_workspace_bytes".
+ * Served: checkerboard lattice containers with fast_path == 0 (periodic, no field, one |J|) of any sign pattern, and
+ * replica-packed containers of both families.  Refused with ISINGMC_ERR_INVALID and a message: the f64 CSR general-graph family;
+ * lattices with a field, open boundaries or anisotropic couplings; two containers of different graph handles or kernel families;
+ * a slot at or beyond its container's count; n_pairs == 0; one table without the other. */
+int isingmc_overlaps(isingmc_states *a, isingmc_states *b, const uint32_t *slots_a, const uint32_t *slots_b, size_t n_pairs,
+                     int64_t *spin_out, int64_t *link_out);
+
 /* replaces the whole sampling loop of lattice.rs:271-287 / classicising.rs:144-173:
  *   thermalization x do_time_step(beta);  n_samples x { sampling_freq x do_time_step(beta);
  *   states[r][k][:] = state_ref();  energies[r][k] = get_energy() }

@@ -77,6 +77,7 @@ _PROTOTYPES = {
     "isingmc_icm_stats": (C.c_int, [_vp, _vp, _vp, _vp]),
     "isingmc_icm_between": (C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t]),
     "isingmc_icm_between_stats": (C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t]),
+    "isingmc_overlaps": (C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
     "isingmc_run_sampling": (C.c_int, [_vp, C.c_double, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp]),
     "isingmc_pt_attach": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint64]),
     "isingmc_pt_can_attach": (C.c_int, [_vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_int)]),
@@ -469,6 +470,26 @@ class States:
         out = [np.zeros(n, dtype=np.uint64) for _ in range(3)]
         _check(lib().isingmc_icm_between_stats(self._h, _p(out[0]), _p(out[1]), _p(out[2]), n))
         return tuple(out)
+
+    def overlaps(self, other=None, slots_a=None, slots_b=None, link=True):
+        """(spin, link): int64[n_pairs] each, spin[p] = sum_i s_i s'_i and link[p] = sum over the edge-list entries of
+        s_a s_b s'_a s'_b for pair p; link is None when not asked for.  Without tables: the pairs (2p, 2p + 1) of
+        this container, or with `other` pair p = (slot p of self, slot p of other) up to the smaller count; with tables pair p =
+        (slot slots_a[p] of self, slot slots_b[p] of `other`, or of self without one).  Reads only; synchronises."""
+        if (slots_a is None) != (slots_b is None):
+            raise ValueError("give both slot tables or neither")
+        if slots_a is None:
+            sa, sb = None, None
+            n = self.count // 2 if other is None or other is self else min(self.count, other.count)
+        else:
+            sa, sb = _arr(slots_a, np.uint32), _arr(slots_b, np.uint32)
+            if sa.ndim != 1 or sa.shape != sb.shape:
+                raise ValueError("the slot tables must be two one-dimensional arrays of one length")
+            n = sa.size
+        spin = np.zeros(n, dtype=np.int64)
+        lnk = np.zeros(n, dtype=np.int64) if link else None
+        _check(lib().isingmc_overlaps(self._h, None if other is None else other._h, _p(sa), _p(sb), n, _p(spin), _p(lnk)))
+        return spin, lnk
 
     def do_time_steps(self, timesteps, beta=None, per_step_energies=False):
         """beta: float (constant), sequence of length timesteps, or None when per-replica betas are set."""

@@ -3,6 +3,7 @@
 //   graph.hip      edge-list checks, host-only C ABI helpers, lattice / general / packed / real-coupling graph construction
 //   isingmc.hip    replica containers, every sweep / measurement launch, the persistent strip kernel's host side
 //   nonlocal.hip   host side of the non-local moves: Swendsen-Wang steps, isoenergetic cluster moves inside and between containers
+//   overlaps.hip   spin and link overlaps between replica pairs (isingmc_overlaps)
 //   sampling.hip   get_states and the double-buffered sampling pipeline
 //   tempering.hip  on-stream parallel tempering, the in-process ladder group (RCCL through dlopen)
 //   population.hip population annealing: the on-stream resampling step (isingmc_pa_*)
@@ -37,6 +38,7 @@
 #include "packed_kernels.hpp"
 #include "pa_kernels.hpp"
 #include "mc_types.hpp"
+#include "overlap_kernels.hpp"
 #include "real_types.hpp"
 #include "spread_types.hpp"
 #include "strip_types.hpp"
@@ -518,6 +520,8 @@ IM_INTERNAL bool is_icm_step(const isingmc_states *s);
 IM_INTERNAL int run_cluster_step(isingmc_states *s, NonlocalRun &n, DeviceScratch &scratch, double beta);
 IM_INTERNAL int run_icm_step(isingmc_states *s, NonlocalRun &n, DeviceScratch &scratch);
 IM_INTERNAL bool icm_unequal_pair_betas(const isingmc_states *s, const double *betas);
+// the clauses every non-local move and measurement of a checkerboard lattice shares ("" when none applies)
+IM_INTERNAL std::string lattice_obstacle(const isingmc_graph *g, const std::string &what, bool any_sign, bool labels = true);
 
 // counter pairs of a measurement (measure_enqueue): one per (group, bit) slot of a packed container, one per replica otherwise
 static inline size_t counter_slots(const isingmc_states *s) { return s->packed ? s->pk_slots() : s->R; }

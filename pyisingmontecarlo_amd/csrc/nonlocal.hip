@@ -11,14 +11,15 @@ static size_t workspace_batch(const isingmc_states *s, size_t items, size_t word
 }
 
 // The clauses every non-local move of a checkerboard lattice shares ("" when none applies); `what` begins the message.
-// any_sign: the move reads no coupling (the isoenergetic moves), so +-J sign patterns are fine.
-static std::string lattice_obstacle(const isingmc_graph *g, const std::string &what, bool any_sign)
+// any_sign: the move reads no coupling (the isoenergetic moves), so +-J sign patterns are fine.  labels: it labels sites (the
+// overlap measurement of overlaps.hip does not).
+std::string lattice_obstacle(const isingmc_graph *g, const std::string &what, bool any_sign, bool labels)
 {
     if (g->mc_mode == MC_FIELD || g->mc_mode == MC_FIELD_OPEN) return what + " are not implemented for lattices with a field";
     if (g->mc_mode == MC_OPEN) return what + " are not implemented for open boundaries (periodic lattices only)";
     if (g->mc_mode != MC_NONE) return what + " are not implemented for anisotropic couplings (|Jx| != |Jy|)";
     if (!any_sign && !g->uniform_sign) return what + " are not implemented for +-J sign patterns (one coupling sign only)";
-    if (g->nvars >= 0xFFFFFFFFull) return what + " label sites with 32 bits: W H must be below 2^32 - 1";
+    if (labels && g->nvars >= 0xFFFFFFFFull) return what + " label sites with 32 bits: W H must be below 2^32 - 1";
     return "";
 }
 

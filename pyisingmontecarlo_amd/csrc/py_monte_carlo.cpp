@@ -377,7 +377,10 @@ public:
     // (isingmc_pa_resample, step counter k, keyed by the LAST of make_seeds(population + 1); the first `population` seeds key the
     // replicas); then sweeps_per_beta timesteps at betas[k] (cluster periods set on this object apply).  One library call
     // (isingmc_pa_run) enqueues it all; nothing waits on the host until the end.
-    py::object run_population_annealing(const std::vector<double> &betas, size_t sweeps_per_beta, size_t population, bool return_states)
+    // measure_overlaps: the result also carries the spin and link overlaps of the final population between the
+    // replicas (p, p + R / 2) (isingmc_overlaps); pairs of one family are the caller's to drop.
+    py::object run_population_annealing(const std::vector<double> &betas, size_t sweeps_per_beta, size_t population, bool return_states,
+                                        bool measure_overlaps)
     {
         require_classical();
         if (betas.empty()) throw py::value_error("betas must hold at least one inverse temperature");
@@ -398,6 +401,10 @@ public:
         int64_t *ds = distinct.mutable_data();
         uint32_t *fam = families.mutable_data();
         uint8_t *st = reinterpret_cast<uint8_t *>(states.mutable_data());
+        const size_t n_ovl = measure_overlaps ? R / 2 : 0;
+        py::array_t<int64_t> ovl_pairs(std::vector<ssize_t>{ssize_t(n_ovl), 2}), ovl_spin(std::vector<ssize_t>{ssize_t(n_ovl)}),
+            ovl_link(std::vector<ssize_t>{ssize_t(n_ovl)});
+        int64_t *op = ovl_pairs.mutable_data(), *os = ovl_spin.mutable_data(), *ol = ovl_link.mutable_data();
         int rc = ISINGMC_OK;
         std::string msg;
         {
@@ -422,6 +429,14 @@ public:
             if (rc == ISINGMC_OK) rc = isingmc_get_energies(h.s, e);
             if (rc == ISINGMC_OK && return_states) rc = isingmc_get_states(h.s, st, N);
             if (rc == ISINGMC_OK) rc = isingmc_pa_families(h.s, fam);
+            if (rc == ISINGMC_OK && n_ovl) {
+                std::vector<uint32_t> sa(n_ovl), sb(n_ovl);
+                for (size_t p = 0; p < n_ovl; p++) {
+                    op[2 * p] = int64_t(sa[p] = uint32_t(p));
+                    op[2 * p + 1] = int64_t(sb[p] = uint32_t(p + n_ovl));
+                }
+                rc = isingmc_overlaps(h.s, nullptr, sa.data(), sb.data(), n_ovl, os, ol);
+            }
             if (rc != ISINGMC_OK) msg = isingmc_last_error();
         }
         if (rc == ISINGMC_ERR_INVALID) throw py::value_error(msg);
@@ -443,6 +458,11 @@ public:
         d["families"] = families;
         d["rho_t"] = rho;
         d["betas"] = py::array_t<double>(ssize_t(n), betas.data());
+        if (measure_overlaps) {
+            d["overlap_pairs"] = ovl_pairs;
+            d["spin_overlaps"] = ovl_spin;
+            d["link_overlaps"] = ovl_link;
+        }
         return py::module_::import("types").attr("SimpleNamespace")(**d);
     }
 
@@ -667,6 +687,36 @@ public:
         return s;
     }
     size_t get_num_graphs() const { return isingmc_states_count(st_->s); }
+    // extension: spin and link overlaps between the persistent replicas, exact integers counted on the device.
+    // pairs: None = the replicas (2 p, 2 p + 1), or an integer [n, 2] array of graph indices.  Returns (spin, link) as int64[n]
+    // (link = None when not asked for); ValueError where isingmc_overlaps refuses.
+    py::tuple get_overlaps(const py::object &pairs, bool link)
+    {
+        std::vector<uint32_t> sa, sb;
+        size_t n = isingmc_states_count(st_->s) / 2;
+        if (!pairs.is_none()) {
+            const auto arr = py::array_t<int64_t, py::array::c_style | py::array::forcecast>::ensure(pairs);
+            if (!arr || arr.ndim() != 2 || arr.shape(1) != 2) throw py::value_error("pairs must be an integer array of shape [n, 2]");
+            n = size_t(arr.shape(0));
+            const size_t R = isingmc_states_count(st_->s);
+            const int64_t *v = arr.data();
+            sa.resize(n);
+            sb.resize(n);
+            for (size_t p = 0; p < n; p++) {
+                if (v[2 * p] < 0 || v[2 * p + 1] < 0 || size_t(v[2 * p]) >= R || size_t(v[2 * p + 1]) >= R)
+                    throw py::value_error("slot out of range: every graph index of `pairs` must be below get_num_graphs()");
+                sa[p] = uint32_t(v[2 * p]);
+                sb[p] = uint32_t(v[2 * p + 1]);
+            }
+        }
+        py::array_t<int64_t> spin(std::vector<ssize_t>{ssize_t(n)}), lnk(std::vector<ssize_t>{ssize_t(link ? n : 0)});
+        int64_t *s_out = spin.mutable_data(), *l_out = link ? lnk.mutable_data() : nullptr;
+        {
+            py::gil_scoped_release nogil;
+            check(isingmc_overlaps(st_->s, nullptr, pairs_ptr(sa), pairs_ptr(sb), n, s_out, l_out));
+        }
+        return py::make_tuple(spin, link ? py::object(lnk) : py::object(py::none()));
+    }
     // extension: Swendsen-Wang cluster steps on the persistent replicas (see Lattice.set_cluster_update_every); the graph is known
     // here, so one the cluster step does not serve raises ValueError at once
     void set_cluster_update_every(size_t k) { check(isingmc_states_set_cluster_every(st_->s, k)); }
@@ -674,6 +724,7 @@ public:
     void set_replica_cluster_update_every(size_t k) { check(isingmc_states_set_icm_every(st_->s, k)); }
 
 private:
+    static const uint32_t *pairs_ptr(const std::vector<uint32_t> &v) { return v.empty() ? nullptr : v.data(); }
     // nspinupdates = single-spin attempts per timestep (classicising.rs:88-110 hands it to do_time_step; crate default:
     // nvars).  The engine attempts every site once per sweep, in the colour order, so attempts are executed sweep by
     // sweep: `timesteps` timesteps of n attempts add timesteps x n attempts to a cursor that persists across calls,
@@ -755,7 +806,7 @@ PYBIND11_MODULE(_py_monte_carlo, m)
              "betas"_a, "timesteps"_a, "num_experiments"_a, "only_basic_moves"_a = py::none(),
              "edge_move_importance_sampling"_a = py::none(), "replica_range"_a = py::none())
         .def("run_population_annealing", &Lattice::run_population_annealing, "betas"_a, "sweeps_per_beta"_a, "population"_a,
-             py::kw_only(), "return_states"_a = true)
+             py::kw_only(), "return_states"_a = true, "measure_overlaps"_a = false)
         .def("clone", &Lattice::clone);
     // the reference's quantum (SSE) entry points (lattice.rs:478-1036) live in the un-vendored qmc crate and are out of
     // scope: present by name, so a script written for the reference fails with a reason instead of an AttributeError
@@ -786,6 +837,7 @@ PYBIND11_MODULE(_py_monte_carlo, m)
         .def("get_energies", &ClassicIsing::get_energies)
         .def("get_states", &ClassicIsing::get_states)
         .def("get_num_graphs", &ClassicIsing::get_num_graphs)
+        .def("get_overlaps", &ClassicIsing::get_overlaps, "pairs"_a = py::none(), "link"_a = true)
         .def("set_cluster_update_every", &ClassicIsing::set_cluster_update_every, "k"_a)
         .def("set_replica_cluster_update_every", &ClassicIsing::set_replica_cluster_update_every, "k"_a);
 }

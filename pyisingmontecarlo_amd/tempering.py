@@ -192,6 +192,21 @@ class ClassicalTempering:
             self._icm_pending = False
         return self._icm_stats
 
+    def get_overlaps(self, link=True):
+        """copies=2 only: (spin, link) between the two configurations currently at every rung, int64[G] each in the order of
+        get_betas() (link is None when not asked for): spin = sum_i s_i s'_i, link = sum over the edge-list entries
+        of s_a s_b s'_a s'_b.  Pair r is the pair _pair_icm moves: (copy 0's slot at rung r, copy 1's slot at rung r), with the
+        ladders' device permutations on the on-stream path and the host tables on the host swap path as slot tables.  Reads
+        only: no configuration, random number or timestep changes."""
+        if self._pair is None:
+            raise ValueError("overlaps need two configurations per temperature: build the ladder with copies=2")
+        self._materialise_pair()
+        a, b = self._pair
+        if not hasattr(a._states, "overlaps"):
+            raise ValueError("this engine has no overlap measurement between containers (overlaps)")
+        perm = self.get_permutation()
+        return a._states.overlaps(b._states, perm[0], perm[1], link=link)
+
     # -- copies=2: the two ladders, cut at exchange rounds and at cluster moves ------------------------------------------------
     def _materialise_pair(self):
         if self._states is not None:
