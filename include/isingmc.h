@@ -339,6 +339,38 @@ int isingmc_icm_between_stats(isingmc_states *a, uint64_t *n_clusters_out, uint6
 int isingmc_overlaps(isingmc_states *a, isingmc_states *b, const uint32_t *slots_a, const uint32_t *slots_b, size_t n_pairs,
                      int64_t *spin_out, int64_t *link_out);
 
+/* ---- each replica's lowest-energy configuration, kept on the device (no reference counterpart) ----
+ * A container may keep, per replica, the lowest energy its configuration has had at an UPDATE, the timestep of that update and
+ * the configuration itself.  An update measures the f64 energies of isingmc_get_energies on the device and, for every replica
+ * with e < record (strictly: ties keep the earliest update; records start at +inf), sets record = e, timestep = t and copies
+ * the replica's configuration into a second state buffer.  Nothing crosses the bus until isingmc_best_get.
+ * isingmc_states_set_track_best(states, every): every = 0 (the default) is off; every = k > 0: inside isingmc_do_time_steps*,
+ * the calls built on it (isingmc_pt_time_steps, isingmc_pa_run) and isingmc_run_sampling an update follows every timestep after
+ * which t % k == 0.  The calls are cut into stretches at those timesteps; no configuration, energy or timestep they produce
+ * changes.  While tracking is on, isingmc_pt_measure also serves the records from the energies it has just written (rounds
+ * that would run inside one persistent launch take one launch per round, as with the option pt_in_kernel = 0),
+ * isingmc_pa_resample does so before its gather, and isingmc_pa_run adds one update after its last sweeps.  Records belong to
+ * the SLOT: neither a ladder's permutation nor a resampling moves them.  isingmc_states_set_state leaves them alone.
+ * Memory: a second state buffer as large as the state plus 28 bytes per replica, allocated when tracking is first switched on
+ * (or by the first isingmc_best_update) and freed with the container.
+ * Served: checkerboard lattice containers with fast_path == 0 and both replica-packed families (the containers with a device-side
+ * energy array).  Refused with ISINGMC_ERR_INVALID and a message, the container unchanged: the f64 CSR general-graph family;
+ * lattices with a field, open boundaries or anisotropic couplings; isingmc_states_append while tracking is on. */
+int isingmc_states_set_track_best(isingmc_states *states, size_t every);
+int isingmc_states_track_best(const isingmc_states *states, size_t *every_out);
+/* enqueue only: one update at the container's current timestep, whatever the period */
+int isingmc_best_update(isingmc_states *states);
+/* synchronises.  energies_out: double[count] (+inf where no update has happened); states_out: one byte per spin as
+ * isingmc_get_states, taken from the second buffer (all zero where no update has happened); timesteps_out: uint64[count];
+ * *improvements_out: how often any record has been set since the last reset.  Any pointer may be NULL. */
+int isingmc_best_get(isingmc_states *states, double *energies_out, uint8_t *states_out, size_t replica_stride_bytes,
+                     uint64_t *timesteps_out, uint64_t *improvements_out);
+/* the second buffer's words as they lie in memory, as isingmc_get_raw_state (padding positions and the bits of a packed group
+ * this container does not own hold no defined value) */
+int isingmc_best_raw_state(isingmc_states *states, uint32_t *words_out, size_t *n_words_out);
+/* records back to +inf, timesteps and the improvement count to 0; the second buffer keeps its words */
+int isingmc_best_reset(isingmc_states *states);
+
 /* replaces the whole sampling loop of lattice.rs:271-287 / classicising.rs:144-173:
  *   thermalization x do_time_step(beta);  n_samples x { sampling_freq x do_time_step(beta);
  *   states[r][k][:] = state_ref();  energies[r][k] = get_energy() }

@@ -78,6 +78,12 @@ _PROTOTYPES = {
     "isingmc_icm_between": (C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t]),
     "isingmc_icm_between_stats": (C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t]),
     "isingmc_overlaps": (C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
+    "isingmc_states_set_track_best": (C.c_int, [_vp, C.c_size_t]),
+    "isingmc_states_track_best": (C.c_int, [_vp, C.POINTER(C.c_size_t)]),
+    "isingmc_best_update": (C.c_int, [_vp]),
+    "isingmc_best_get": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.POINTER(C.c_uint64)]),
+    "isingmc_best_raw_state": (C.c_int, [_vp, _vp, C.POINTER(C.c_size_t)]),
+    "isingmc_best_reset": (C.c_int, [_vp]),
     "isingmc_run_sampling": (C.c_int, [_vp, C.c_double, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp]),
     "isingmc_pt_attach": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint64]),
     "isingmc_pt_can_attach": (C.c_int, [_vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_int)]),
@@ -490,6 +496,42 @@ class States:
         lnk = np.zeros(n, dtype=np.int64) if link else None
         _check(lib().isingmc_overlaps(self._h, None if other is None else other._h, _p(sa), _p(sb), n, _p(spin), _p(lnk)))
         return spin, lnk
+
+    # ---- each replica's lowest-energy configuration
+    def set_track_best(self, k):
+        """An update of the records follows every timestep after which t % k == 0; 0 switches tracking off."""
+        _check(lib().isingmc_states_set_track_best(self._h, int(k)))
+
+    @property
+    def track_best(self):
+        k = C.c_size_t()
+        _check(lib().isingmc_states_track_best(self._h, C.byref(k)))
+        return int(k.value)
+
+    def best_update(self):
+        """One update at the current timestep, whatever the period; enqueue only."""
+        _check(lib().isingmc_best_update(self._h))
+
+    def best(self, states=True):
+        """(energies float64[R], states bool[R, nvars] or None, timesteps uint64[R], improvements): every replica's record, the
+        configuration it was set with and the timestep of that update; how often a record has been set.  Synchronises."""
+        R, N = self.count, self.graph.nvars
+        e, t = np.zeros(R, dtype=np.float64), np.zeros(R, dtype=np.uint64)
+        st = np.zeros((R, N), dtype=np.bool_) if states else None
+        n = C.c_uint64()
+        _check(lib().isingmc_best_get(self._h, _p(e), None if st is None else st.ctypes.data_as(_vp), N, _p(t), C.byref(n)))
+        return e, st, t, int(n.value)
+
+    def best_raw(self):
+        """The second state buffer's words as they lie in memory, uint32 (one-dimensional), as raw_state()."""
+        n = C.c_size_t()
+        _check(lib().isingmc_best_raw_state(self._h, None, C.byref(n)))
+        out = np.zeros(n.value, dtype=np.uint32)
+        _check(lib().isingmc_best_raw_state(self._h, _p(out), None))
+        return out
+
+    def best_reset(self):
+        _check(lib().isingmc_best_reset(self._h))
 
     def do_time_steps(self, timesteps, beta=None, per_step_energies=False):
         """beta: float (constant), sequence of length timesteps, or None when per-replica betas are set."""

@@ -4,6 +4,7 @@
 //   isingmc.hip    replica containers, every sweep / measurement launch, the persistent strip kernel's host side
 //   nonlocal.hip   host side of the non-local moves: Swendsen-Wang steps, isoenergetic cluster moves inside and between containers
 //   overlaps.hip   spin and link overlaps between replica pairs (isingmc_overlaps)
+//   best.hip       each replica's lowest-energy configuration, kept on the device (isingmc_best_*)
 //   sampling.hip   get_states and the double-buffered sampling pipeline
 //   tempering.hip  on-stream parallel tempering, the in-process ladder group (RCCL through dlopen)
 //   population.hip population annealing: the on-stream resampling step (isingmc_pa_*)
@@ -28,6 +29,7 @@
 #include <vector>
 
 #include "../../include/isingmc.h"
+#include "best_kernels.hpp"
 #include "cluster_kernels.hpp"
 #include "general_kernels.hpp"
 #include "host_logic.hpp"
@@ -327,6 +329,18 @@ struct isingmc_states {
     PaRecord *d_pa_record = nullptr;
     bool pa_have_record = false;    // an isingmc_pa_resample has been enqueued
     bool pa_families_set = false;   // d_pa_family holds the table (else: the identity)
+    // each replica's lowest-energy configuration (isingmc_best_*): allocated when tracking is switched on (or by the
+    // first isingmc_best_update) for the replicas the container holds then, and kept
+    size_t best_every = 0;            // an update follows every timestep after which t % best_every == 0; 0 = off
+    uint32_t *d_best_state = nullptr; // as large as d_state, same layout; padding positions and unowned bits of a packed container
+    size_t best_state_words = 0;      // hold no defined value (cleared once, so that the raw read-out is deterministic)
+    size_t best_cap = 0;              // replicas the records below hold
+    double *d_best_e = nullptr;                // [best_cap] records, +inf before the first update
+    unsigned long long *d_best_t = nullptr;    // [best_cap] the timestep each record was set at
+    double *d_best_energy = nullptr;           // [best_cap] the energies an update measures
+    uint32_t *d_best_flags = nullptr;          // a flag per replica (checkerboard) / an improvement mask per group (packed)
+    unsigned long long *d_best_count = nullptr; // improvements so far
+    bool strip_guard = false; // inside with_strip_retry: a strip launch is checked before an update may keep what it left
 
     ~isingmc_states()
     {
@@ -351,6 +365,8 @@ struct isingmc_states {
             if (p) (void)cached_free(p);
         for (void *p : {(void *)d_pa_state, (void *)d_pa_energy, (void *)d_pa_cum, (void *)d_pa_src, (void *)d_pa_user_src, (void *)d_pa_family, (void *)d_pa_family2,
                         (void *)d_pa_record})
+            if (p) (void)cached_free(p);
+        for (void *p : {(void *)d_best_state, (void *)d_best_e, (void *)d_best_t, (void *)d_best_energy, (void *)d_best_flags, (void *)d_best_count})
             if (p) (void)cached_free(p);
         for (auto ev : icmb_ev) pooled_event_destroy(ev, true);
         for (int b = 0; b < 2; b++) {
@@ -491,7 +507,8 @@ IM_INTERNAL int lanes_join(isingmc_states *s); // the main stream waits for the 
 IM_INTERNAL int measure_enqueue(isingmc_states *s, unsigned long long *counts_slot, double *e_slot, long long *m_slot, bool want_up = true);
 IM_INTERNAL void lat_measure_enqueue(isingmc_states *s, unsigned long long *out, size_t out_stride); // lattice containers: the counting launches alone
 IM_INTERNAL double pk_energy(const isingmc_graph *g, bool rj, unsigned long long c0, unsigned long long c1);
-IM_INTERNAL int pk_get_states(isingmc_states *s, uint8_t *states_out, size_t replica_stride_bytes, uint32_t *packed_out);
+IM_INTERNAL int pk_get_states(isingmc_states *s, uint8_t *states_out, size_t replica_stride_bytes, uint32_t *packed_out,
+                              const uint32_t *d_words = nullptr); // d_words: a buffer laid out as d_state (nullptr: d_state itself)
 IM_INTERNAL StripPlan strip_plan(const isingmc_states *s, size_t timesteps, bool ladder = false);
 IM_INTERNAL int launch_strip(isingmc_states *s, const StripPlan &P, size_t r0, size_t n, size_t nk, const LatThr *d_thr_steps, uint32_t thr_stride,
                              unsigned long long *steps_out, double *final_energies, const StripLadder *ladder = nullptr);
@@ -500,6 +517,15 @@ IM_INTERNAL int strip_error(int rc);
 IM_INTERNAL bool may_use_strips(const isingmc_states *s);
 IM_INTERNAL int snapshot_take(isingmc_states *s);
 IM_INTERNAL int snapshot_restore(isingmc_states *s);
+
+// ---- sampling.hip ------------------------------------------------------------------------------------------------------------
+// one byte per spin of every replica out of `d_words`, a buffer laid out as d_state (isingmc_get_states passes d_state)
+IM_INTERNAL int expand_states(isingmc_states *s, const uint32_t *d_words, uint8_t *states_out, size_t replica_stride_bytes);
+
+// ---- best.hip (each replica's lowest-energy configuration) -------------------------------------------------------------------
+// enqueue: decide + keep from d_energy[R], the energies of the CURRENT configurations, on the container's stream (lanes joined)
+IM_INTERNAL int best_from_energies(isingmc_states *s, const double *d_energy);
+IM_INTERNAL int best_update_enqueue(isingmc_states *s); // energies_enqueue into the container's own array, then the above
 
 // ---- nonlocal.hip (Swendsen-Wang steps and isoenergetic cluster moves) -------------------------------------------------------
 // What the non-local steps of ONE run_steps call keep between them: filled by the call's first such step, the device blocks in the
@@ -541,7 +567,9 @@ static int with_strip_retry(isingmc_states *s, bool may_strip, F &&call)
     TRY(use_device(s->g->device));
     const uint64_t t0 = s->t;
     TRY(snapshot_take(s));
+    s->strip_guard = true;
     const int rc = call();
+    s->strip_guard = false;
     if (rc != STRIP_TIMED_OUT) return rc;
     TRY(snapshot_restore(s));
     s->t = t0;

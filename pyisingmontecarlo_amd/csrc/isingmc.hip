@@ -165,6 +165,7 @@ extern "C" int isingmc_states_append(isingmc_states *s, uint64_t seed, const uin
 {
     if (!s) return fail(ISINGMC_ERR_INVALID, "NULL states");
     if (s->has_betas) return fail(ISINGMC_ERR_INVALID, "clear the per-replica betas before appending replicas");
+    if (s->best_every) return fail(ISINGMC_ERR_INVALID, "minimum tracking is switched on for this container (isingmc_states_set_track_best): its records are sized for the replicas it holds; switch tracking on after the graphs are added");
     TRY(use_device(s->g->device));
     if (s->packed) return pk_append(s, seed, initial_state);
     return add_replicas(s, 1, &seed, initial_state);
@@ -591,11 +592,11 @@ double pk_energy(const isingmc_graph *g, bool rj, unsigned long long c0, unsigne
 }
 
 // packed words -> one byte per spin, replica by replica
-int pk_get_states(isingmc_states *s, uint8_t *states_out, size_t replica_stride_bytes, uint32_t *packed_out)
+int pk_get_states(isingmc_states *s, uint8_t *states_out, size_t replica_stride_bytes, uint32_t *packed_out, const uint32_t *d_words)
 {
     const isingmc_graph *g = s->g;
     std::vector<uint32_t> words(s->groups * g->pk.n_pos);
-    HIP_TRY(hipMemcpyAsync(words.data(), s->d_state, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(words.data(), d_words ? d_words : s->d_state, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     parallel_for(s->R, [&](size_t r) {
         const uint32_t *w = words.data() + ((r + s->pk_bit0) / 32) * g->pk.n_pos;
@@ -1563,9 +1564,11 @@ static int run_steps_impl(isingmc_states *s, size_t timesteps, const double *bet
         // (Swendsen-Wang steps and isoenergetic cluster moves exclude each other: at most one period applies)
         const bool cluster = is_cluster_step(s), icm = is_icm_step(s);
         if (cluster || icm) nk = 1;
-        else if (const size_t every = s->cluster_every ? s->cluster_every : s->icm_every) {
-            nk = std::min<size_t>(nk, every - 1 - s->t % every);
-            // (joined by the cluster step before this stretch; the packed runner forks behind its table launches)
+        else {
+            if (const size_t every = s->cluster_every ? s->cluster_every : s->icm_every) nk = std::min<size_t>(nk, every - 1 - s->t % every);
+            // minimum tracking cuts the call too: a stretch ends with the timestep after which t % best_every == 0
+            if (s->best_every) nk = std::min<size_t>(nk, s->best_every - s->t % s->best_every);
+            // (joined by the cluster step or the update before this stretch; the packed runner forks behind its table launches)
             if (P.lanes > 1 && s->n_lanes <= 1 && P.path != StepPath::Packed) TRY(lanes_fork(s, P.lanes));
         }
         if (c.d_counts && P.path != StepPath::Packed) // (measure_enqueue clears the packed counters itself)
@@ -1584,6 +1587,15 @@ static int run_steps_impl(isingmc_states *s, size_t timesteps, const double *bet
         }
         if (rc == ISINGMC_OK && (cluster || icm)) rc = measure_nonlocal_step(c);
         if (rc == ISINGMC_OK && energies_per_step) rc = read_step_energies(c, k0, nk);
+        if (rc == ISINGMC_OK && s->best_every && s->t % s->best_every == 0) {
+            // a call that may be repeated after a strip launch gave up (with_strip_retry) keeps nothing such a launch left:
+            // the launch is waited for and checked first.  The repeat then finds the same records again and changes none
+            if (s->strip_guard && P.path == StepPath::LatStrip) {
+                HIP_TRY(hipStreamSynchronize(s->stream));
+                rc = strip_check(s);
+            }
+            if (rc == ISINGMC_OK) rc = best_update_enqueue(s);
+        }
     }
     if (s->n_lanes > 1) { const int jrc = lanes_join(s); if (rc == ISINGMC_OK) rc = jrc; }
     if (device_ms && rc == ISINGMC_OK) {

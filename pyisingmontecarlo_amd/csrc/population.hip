@@ -80,6 +80,8 @@ static int pa_resample_enqueue(isingmc_states *s, double dbeta, uint64_t seed, u
 {
     const uint32_t R = uint32_t(s->R);
     TRY(energies_enqueue(s, s->d_pa_energy));
+    // minimum tracking: the records see the population before the gather; they stay with the slots
+    if (s->best_every) TRY(best_from_energies(s, s->d_pa_energy));
     HIP_TRY(pa_launch_weights(s->stream, s->d_pa_energy, R, dbeta, seed, step, s->d_pa_cum, d_rec));
     HIP_TRY(pa_launch_scan(s->stream, s->d_pa_cum, R, s->d_pa_cum + R));
     HIP_TRY(pa_launch_sources(s->stream, s->d_pa_cum, R, d_rec, s->d_pa_src));
@@ -131,6 +133,7 @@ extern "C" int isingmc_pa_run(isingmc_states *s, const double *betas, size_t n_b
         rc = run_steps(s, sweeps_per_beta, &betas[k], 0, nullptr, nullptr, /*sync=*/false);
         s->step_preset = nullptr;
     }
+    if (rc == ISINGMC_OK && s->best_every) rc = best_update_enqueue(s); // the final population
     if (rc == ISINGMC_OK && n_steps) {
         HIP_TRY(hipMemcpyAsync(s->d_pa_record, d_log + (n_steps - 1), sizeof(PaRecord), hipMemcpyDeviceToDevice, s->stream));
         s->pa_have_record = true;

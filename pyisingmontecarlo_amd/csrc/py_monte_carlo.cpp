@@ -9,6 +9,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <memory>
@@ -372,6 +373,33 @@ public:
         return py::make_tuple(energies, states);
     }
 
+    // extension: the annealing run of run_monte_carlo_annealing with every experiment's lowest-energy configuration
+    // kept on the device: an update of the records follows every timestep after which t % every == 0 (isingmc_states_set_track_best).
+    // Returns (min_energies f64[R], min_states bool[R, N], min_timesteps uint64[R]); cluster periods set on this object apply.
+    // One device: the records live in one container.
+    py::tuple run_monte_carlo_annealing_and_get_minimum(const std::vector<std::pair<size_t, double>> &betas, size_t timesteps,
+                                                        size_t num_experiments, size_t every, std::optional<bool>)
+    {
+        require_classical();
+        if (every == 0) throw py::value_error("every must be positive: an update of the records follows every timestep after which t % every == 0");
+        if (devices_.size() != 1) throw py::value_error("minimum tracking runs on one device: the records live in one container (set_device)");
+        const std::vector<double> schedule = expand(betas, timesteps);
+        const size_t R = num_experiments, N = E_->nvars;
+        py::array_t<double> energies(std::vector<ssize_t>{ssize_t(R)});
+        py::array_t<bool> states(std::vector<ssize_t>{ssize_t(R), ssize_t(N)});
+        py::array_t<uint64_t> steps(std::vector<ssize_t>{ssize_t(R)});
+        double *e = energies.mutable_data();
+        uint8_t *st = reinterpret_cast<uint8_t *>(states.mutable_data());
+        uint64_t *ts = steps.mutable_data();
+        fan_out(num_experiments, 0, R, [&](isingmc_states *s, size_t) {
+            int rc = isingmc_states_set_track_best(s, every);
+            if (rc == ISINGMC_OK) rc = isingmc_do_time_steps(s, timesteps, schedule.data(), 1, nullptr);
+            if (rc == ISINGMC_OK) rc = isingmc_best_get(s, e, st, N, ts, nullptr);
+            return rc;
+        });
+        return py::make_tuple(energies, states, steps);
+    }
+
     // extension: population annealing.  `population` replicas are cooled through the non-decreasing `betas`:
     // before the sweeps at betas[k], k > 0, the population is resampled on the device for the step betas[k] - betas[k - 1]
     // (isingmc_pa_resample, step counter k, keyed by the LAST of make_seeds(population + 1); the first `population` seeds key the
@@ -379,8 +407,11 @@ public:
     // (isingmc_pa_run) enqueues it all; nothing waits on the host until the end.
     // measure_overlaps: the result also carries the spin and link overlaps of the final population between the
     // replicas (p, p + R / 2) (isingmc_overlaps); pairs of one family are the caller's to drop.
+    // track_minimum: every SLOT keeps the lowest-energy configuration that ever sat in it, seen before every
+    // resampling and after the last sweeps; the result carries the population's minimum over the slots as min_energy, min_state
+    // and min_beta_index (the index of the beta whose sweeps produced it).
     py::object run_population_annealing(const std::vector<double> &betas, size_t sweeps_per_beta, size_t population, bool return_states,
-                                        bool measure_overlaps)
+                                        bool measure_overlaps, bool track_minimum)
     {
         require_classical();
         if (betas.empty()) throw py::value_error("betas must hold at least one inverse temperature");
@@ -405,6 +436,10 @@ public:
         py::array_t<int64_t> ovl_pairs(std::vector<ssize_t>{ssize_t(n_ovl), 2}), ovl_spin(std::vector<ssize_t>{ssize_t(n_ovl)}),
             ovl_link(std::vector<ssize_t>{ssize_t(n_ovl)});
         int64_t *op = ovl_pairs.mutable_data(), *os = ovl_spin.mutable_data(), *ol = ovl_link.mutable_data();
+        py::array_t<bool> min_state(std::vector<ssize_t>{ssize_t(track_minimum ? N : 0)});
+        uint8_t *mst = reinterpret_cast<uint8_t *>(min_state.mutable_data());
+        double min_energy = std::numeric_limits<double>::infinity();
+        uint64_t min_t = 0;
         int rc = ISINGMC_OK;
         std::string msg;
         {
@@ -415,6 +450,8 @@ public:
             rc = isingmc_states_create(gh->g, R, seeds.data(), ini, &h.s);
             if (rc == ISINGMC_OK && cluster_every_) rc = isingmc_states_set_cluster_every(h.s, cluster_every_);
             if (rc == ISINGMC_OK && icm_every_) rc = isingmc_states_set_icm_every(h.s, icm_every_);
+            // the update points are the resamplings and the end of the run: a period no timestep reaches leaves the sweeps uncut
+            if (rc == ISINGMC_OK && track_minimum) rc = isingmc_states_set_track_best(h.s, size_t(1) << 62);
             // the whole schedule is enqueued; the host waits once, at its end, and reads the step records
             std::vector<uint64_t> sums(n - 1), nd(n - 1);
             std::vector<double> erefs(n - 1);
@@ -436,6 +473,20 @@ public:
                     op[2 * p + 1] = int64_t(sb[p] = uint32_t(p + n_ovl));
                 }
                 rc = isingmc_overlaps(h.s, nullptr, sa.data(), sb.data(), n_ovl, os, ol);
+            }
+            if (rc == ISINGMC_OK && track_minimum) { // the population's minimum: the first slot with the lowest record
+                std::vector<double> be(R);
+                std::vector<uint64_t> bt(R);
+                std::vector<uint8_t> bs(R * N);
+                rc = isingmc_best_get(h.s, be.data(), bs.data(), N, bt.data(), nullptr);
+                size_t arg = 0;
+                for (size_t r = 1; r < R && rc == ISINGMC_OK; r++)
+                    if (be[r] < be[arg]) arg = r;
+                if (rc == ISINGMC_OK) {
+                    min_energy = be[arg];
+                    min_t = bt[arg];
+                    std::copy(bs.begin() + arg * N, bs.begin() + (arg + 1) * N, mst);
+                }
             }
             if (rc != ISINGMC_OK) msg = isingmc_last_error();
         }
@@ -462,6 +513,13 @@ public:
             d["overlap_pairs"] = ovl_pairs;
             d["spin_overlaps"] = ovl_spin;
             d["link_overlaps"] = ovl_link;
+        }
+        if (track_minimum) {
+            d["min_energy"] = min_energy;
+            d["min_state"] = min_state;
+            // a record set at timestep t (t = k sweeps_per_beta at the resampling before beta k, n sweeps_per_beta at the end) was
+            // produced by the sweeps at beta ceil(t / sweeps_per_beta) - 1
+            d["min_beta_index"] = min_t ? (min_t + sweeps_per_beta - 1) / sweeps_per_beta - 1 : size_t(0);
         }
         return py::module_::import("types").attr("SimpleNamespace")(**d);
     }
@@ -717,6 +775,28 @@ public:
         }
         return py::make_tuple(spin, link ? py::object(lnk) : py::object(py::none()));
     }
+    // extension: every persistent replica's lowest-energy configuration, kept on the device.
+    // set_track_minimum(every): an update of the records follows every timestep after which t % every == 0 (0: off); add_graph is
+    // refused while it is on.  get_minimum() -> (energies f64[R], states bool[R, N], timesteps uint64[R], improvements);
+    // reset_minimum() sets the records back to +inf.  ValueError where isingmc_states_set_track_best refuses.
+    void set_track_minimum(size_t every) { check(isingmc_states_set_track_best(st_->s, every)); }
+    py::tuple get_minimum()
+    {
+        const size_t R = isingmc_states_count(st_->s), N = E_.nvars;
+        py::array_t<double> e(std::vector<ssize_t>{ssize_t(R)});
+        py::array_t<bool> s(std::vector<ssize_t>{ssize_t(R), ssize_t(N)});
+        py::array_t<uint64_t> t(std::vector<ssize_t>{ssize_t(R)});
+        uint64_t improvements = 0;
+        double *e_out = e.mutable_data();
+        uint8_t *s_out = reinterpret_cast<uint8_t *>(s.mutable_data());
+        uint64_t *t_out = t.mutable_data();
+        {
+            py::gil_scoped_release nogil;
+            check(isingmc_best_get(st_->s, e_out, s_out, N, t_out, &improvements));
+        }
+        return py::make_tuple(e, s, t, improvements);
+    }
+    void reset_minimum() { check(isingmc_best_reset(st_->s)); }
     // extension: Swendsen-Wang cluster steps on the persistent replicas (see Lattice.set_cluster_update_every); the graph is known
     // here, so one the cluster step does not serve raises ValueError at once
     void set_cluster_update_every(size_t k) { check(isingmc_states_set_cluster_every(st_->s, k)); }
@@ -806,7 +886,9 @@ PYBIND11_MODULE(_py_monte_carlo, m)
              "betas"_a, "timesteps"_a, "num_experiments"_a, "only_basic_moves"_a = py::none(),
              "edge_move_importance_sampling"_a = py::none(), "replica_range"_a = py::none())
         .def("run_population_annealing", &Lattice::run_population_annealing, "betas"_a, "sweeps_per_beta"_a, "population"_a,
-             py::kw_only(), "return_states"_a = true, "measure_overlaps"_a = false)
+             py::kw_only(), "return_states"_a = true, "measure_overlaps"_a = false, "track_minimum"_a = false)
+        .def("run_monte_carlo_annealing_and_get_minimum", &Lattice::run_monte_carlo_annealing_and_get_minimum, "betas"_a, "timesteps"_a,
+             "num_experiments"_a, "every"_a = 1, "only_basic_moves"_a = py::none())
         .def("clone", &Lattice::clone);
     // the reference's quantum (SSE) entry points (lattice.rs:478-1036) live in the un-vendored qmc crate and are out of
     // scope: present by name, so a script written for the reference fails with a reason instead of an AttributeError
@@ -838,6 +920,9 @@ PYBIND11_MODULE(_py_monte_carlo, m)
         .def("get_states", &ClassicIsing::get_states)
         .def("get_num_graphs", &ClassicIsing::get_num_graphs)
         .def("get_overlaps", &ClassicIsing::get_overlaps, "pairs"_a = py::none(), "link"_a = true)
+        .def("set_track_minimum", &ClassicIsing::set_track_minimum, "every"_a)
+        .def("get_minimum", &ClassicIsing::get_minimum)
+        .def("reset_minimum", &ClassicIsing::reset_minimum)
         .def("set_cluster_update_every", &ClassicIsing::set_cluster_update_every, "k"_a)
         .def("set_replica_cluster_update_every", &ClassicIsing::set_replica_cluster_update_every, "k"_a);
 }

@@ -10,8 +10,13 @@ extern "C" int isingmc_get_states(isingmc_states *s, uint8_t *states_out, size_t
     if (!s || !states_out) return fail(ISINGMC_ERR_INVALID, "NULL argument");
     if (replica_stride_bytes < s->g->nvars) return fail(ISINGMC_ERR_INVALID, "replica stride smaller than nvars");
     TRY(use_device(s->g->device));
+    return expand_states(s, s->d_state, states_out, replica_stride_bytes);
+}
+
+int expand_states(isingmc_states *s, const uint32_t *d_words, uint8_t *states_out, size_t replica_stride_bytes)
+{
     const isingmc_graph *g = s->g;
-    if (s->packed) return s->R ? pk_get_states(s, states_out, replica_stride_bytes, nullptr) : ISINGMC_OK;
+    if (s->packed) return s->R ? pk_get_states(s, states_out, replica_stride_bytes, nullptr, d_words) : ISINGMC_OK;
     // packed device words -> pinned host memory in slabs of replicas (<= 64 MiB), two in flight on the copy stream, expanded
     // to bytes by the host threads while the next slab crosses PCIe (the buffers of the sampling pipeline)
     if (s->R == 0) return ISINGMC_OK;
@@ -23,7 +28,7 @@ extern "C" int isingmc_get_states(isingmc_states *s, uint8_t *states_out, size_t
     HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->sample_ready[0], 0));
     const auto copy_slab = [&](size_t j) {
         const size_t r0 = j * slab, n = std::min(slab, s->R - r0);
-        HIP_TRY(hipMemcpyAsync(s->h_samples[j & 1], s->d_state + r0 * g->state_words, n * g->state_words * sizeof(uint32_t),
+        HIP_TRY(hipMemcpyAsync(s->h_samples[j & 1], d_words + r0 * g->state_words, n * g->state_words * sizeof(uint32_t),
                                hipMemcpyDeviceToHost, s->copy_stream));
         HIP_TRY(hipEventRecord(s->sample_copied[j & 1], s->copy_stream));
         return int(ISINGMC_OK);

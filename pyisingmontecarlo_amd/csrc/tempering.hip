@@ -196,7 +196,8 @@ extern "C" int isingmc_pt_run(isingmc_states *s, size_t timesteps, size_t swap_e
     const size_t rounds = timesteps / swap_every, tail = timesteps % swap_every;
     const StripPlan P = s->R ? strip_plan(s, rounds * swap_every, /*ladder=*/true) : StripPlan{};
     const bool in_kernel = P.use && P.replicas_per_pass >= s->R && rounds >= 2 && rounds * swap_every <= 65536 &&
-                           s->R == s->pt.n_rungs && s->opt.pt_in_kernel != 0;
+                           s->R == s->pt.n_rungs && s->opt.pt_in_kernel != 0 &&
+                           !s->best_every; // minimum tracking reads every round's energies: one launch per round
     if (in_kernel) {
         const size_t R = s->R, nk = rounds * swap_every;
         if (!s->d_pt_mail) {
@@ -239,11 +240,13 @@ extern "C" int isingmc_pt_measure(isingmc_states *s)
     if (!s || !s->pt_attached) return fail(ISINGMC_ERR_INVALID, "no ladder attached");
     TRY(use_device(s->g->device));
     if (s->R == 0) return ISINGMC_OK;
-    if (s->g->kind == ISINGMC_KIND_LATTICE2D && s->meas_fresh) { // the last strip launch of isingmc_pt_time_steps has already written these energies
+    double *d_out = s->pt_world == 1 ? s->d_pt_all + s->pt.slot_offset : s->d_pt_local;
+    if (s->g->kind == ISINGMC_KIND_LATTICE2D && s->meas_fresh) // the last strip launch of isingmc_pt_time_steps has already written these energies
         s->meas_fresh = false;
-        return ISINGMC_OK;
-    }
-    return energies_enqueue(s, s->pt_world == 1 ? s->d_pt_all + s->pt.slot_offset : s->d_pt_local);
+    else
+        TRY(energies_enqueue(s, d_out));
+    // minimum tracking: the round's energies serve the records too -- per slot, so the permutation does not enter
+    return s->best_every ? best_from_energies(s, d_out) : ISINGMC_OK;
 }
 
 // enqueue: the energies of the container's configurations -> d_out[R] (device), the f64 values of isingmc_get_energies

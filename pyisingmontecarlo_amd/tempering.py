@@ -50,6 +50,7 @@ def _split(edges):
     return ea, eb, ej
 
 
+TRACK_AT_ROUNDS = 1 << 62       # set_track_best period of a ladder: no timestep reaches it, the exchange rounds update the records
 COPY_SEED_XOR = 0x9E3779B97F4A7C15  # copy 1 of a copies=2 ladder is the ladder of seed ^ this
 
 
@@ -69,6 +70,7 @@ class ClassicalTempering:
             raise ValueError("copies must be 1 or 2")
         self._ncopies = int(copies)
         self._icm_every = 0
+        self._track_minimum = False
         self._pair = None
         self._devices = None if devices is None else [int(d) for d in devices]
         self._group_backend = int(group_backend)
@@ -206,6 +208,42 @@ class ClassicalTempering:
             raise ValueError("this engine has no overlap measurement between containers (overlaps)")
         perm = self.get_permutation()
         return a._states.overlaps(b._states, perm[0], perm[1], link=link)
+
+    # -- every slot's lowest-energy configuration ---------------------------------------------------------------
+    def set_track_minimum(self, on):
+        """Keep, on the device, the lowest-energy configuration every SLOT has held at an exchange round: the round's own energy
+        measurement serves the records too (one launch per round while it is on; rounds never run inside one persistent launch).
+        Records belong to the slot (the configuration), not to the rung.  copies 1 and 2, one process, one device."""
+        if self._devices is not None or self._world > 1:
+            raise ValueError("minimum tracking is for a ladder on one process and one device: not with devices=[...] or a "
+                             "torch.distributed group of several ranks")
+        self._track_minimum = bool(on)
+        if self._pair is not None:
+            for c in self._pair:
+                c.set_track_minimum(on)
+        elif self._states is not None:
+            self._apply_track_minimum()
+
+    def _apply_track_minimum(self):
+        if not hasattr(self._states, "set_track_best"):
+            raise ValueError("this engine keeps no minimum records (set_track_best)")
+        # the update points are the exchange rounds: a period no timestep reaches leaves the sweeps between them uncut
+        self._states.set_track_best(TRACK_AT_ROUNDS if self._track_minimum else 0)
+
+    def get_minimum(self):
+        """(energies float64[G], states bool[G, N], timesteps uint64[G], rungs int64[G]) per SLOT: the lowest energy the slot's
+        configuration had at an exchange round, that configuration, the timestep of that round, and the rung the slot holds now.
+        copies=2: one leading row per copy."""
+        if self._pair is not None:
+            self._materialise_pair()
+            return tuple(np.stack(x) for x in zip(*(c.get_minimum() for c in self._pair)))
+        self._materialise()
+        if not self._track_minimum:
+            raise ValueError("minimum tracking is off: call set_track_minimum(True) first")
+        e, st, t, _ = self._states.best()
+        rungs = np.empty(len(self._betas), dtype=np.int64)
+        rungs[self.get_permutation()] = np.arange(len(self._betas))
+        return e, st, t, rungs
 
     # -- copies=2: the two ladders, cut at exchange rounds and at cluster moves ------------------------------------------------
     def _materialise_pair(self):
@@ -365,6 +403,8 @@ class ClassicalTempering:
             self._pt_stream = self._states.pt_stream() if self._world > 1 else None
         else:
             self._push_betas()
+        if self._track_minimum:
+            self._apply_track_minimum()
 
     def _materialise_in_process(self, G):
         """One shard per device, the same ladder attached to each, an isingmc_pt_group between them."""
@@ -446,6 +486,8 @@ class ClassicalTempering:
                 self._perm = self._states.pt_state()[0]
             return
         local = self._states.energies() if self._hi > self._lo else np.zeros(0)
+        if self._track_minimum and self._hi > self._lo:
+            self._states.best_update()
         slot_e = self._slot_energies(local)
         self._total_swaps += _capi.pt_swap_round(self._seed, self._round, self._betas, slot_e, self._perm)
         self._round += 1
