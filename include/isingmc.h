@@ -144,6 +144,17 @@ int isingmc_host_pt_swap_round(uint64_t seed, uint64_t round, size_t n_rungs, co
 int isingmc_host_pa_sources(uint64_t seed, uint64_t step, size_t n, const double *energies, double dbeta, uint32_t *src_out,
                             uint64_t *sum_out, double *eref_out);
 
+/* The position lists of a class set on the replica-packed families, as isingmc_site_classes_create builds them
+ * for the device.  site[n_pos]: the site at every position of the packed layout, 0xFFFFFFFF on padding; cls[n_tables][nvars]: a
+ * class below n_classes or 0xFFFFFFFF (no class) per site.  Per table the classed, non-padding positions are sorted by class,
+ * ascending inside a class, into order_out; the sorted list is cut into segments of at most 1024 positions, four words
+ * {table, class, first, count} each in seg_out (`first` indexes order_out; a segment never mixes classes; an empty class has
+ * none); tables after one another.  Capacities the caller provides: order_out n_tables * n_pos words, seg_out
+ * 4 * n_tables * (n_classes + n_pos / 1024) words; *n_order_out / *n_seg_out: positions / segments written.
+ * sizes_out[n_tables][n_classes]: sites per class (may be NULL).  Refuses what isingmc_site_classes_create refuses. */
+int isingmc_host_class_segments(const uint32_t *site, size_t n_pos, const uint32_t *cls, size_t nvars, size_t n_tables, size_t n_classes,
+                                uint32_t *order_out, size_t *n_order_out, uint32_t *seg_out, size_t *n_seg_out, uint64_t *sizes_out);
+
 /* Host halves of the replica-packed REAL-COUPLING path -- what the device kernels are fed with, exposed
  * so that they can be checked without a GPU.  That path serves edge lists with couplings of several sizes
  * (lattice.rs:46-50 takes any f64) and arbitrary site biases (set_individual_bias / set_global_bias, lattice.rs:104-131)
@@ -338,6 +349,34 @@ int isingmc_icm_between_stats(isingmc_states *a, uint64_t *n_clusters_out, uint6
  * a slot at or beyond its container's count; n_pairs == 0; one table without the other. */
 int isingmc_overlaps(isingmc_states *a, isingmc_states *b, const uint32_t *slots_a, const uint32_t *slots_b, size_t n_pairs,
                      int64_t *spin_out, int64_t *link_out);
+
+/* ---- Spin overlaps resolved by a class label per site (no reference counterpart) ----
+ * A class table gives every site i < nvars a class cls[i] in 0 .. n_classes - 1, or ISINGMC_NO_CLASS ("counted nowhere"); a class
+ * set is n_tables such tables over one graph.  For pair p of configurations (x, y)
+ *   out[p][t][c] = sum over the sites i with cls[t][i] == c of s_i^x s_i^y          int64[n_pairs][n_tables][n_classes]
+ * exact integers, counted on the device.  Sites in no edge count like any other, an empty class gives 0, and for a table without
+ * ISINGMC_NO_CLASS the sum over c is spin_out[p] of isingmc_overlaps.  With the plane at coordinate x of a lattice as class x the
+ * result is the overlap profile Q_x whose Fourier transform gives the wave-vector-dependent spin-glass susceptibility along
+ * that axis (pyisingmontecarlo_amd/correlation.py); sublattices give staggered overlaps, a marked region a window overlap.
+ * isingmc_site_classes_create rearranges the tables into the layouts the kernels read and keeps them on the graph's device: a
+ * measurement is repeated thousands of times during a run.  cls: uint32[n_tables][nvars] in host memory, in the site numbering
+ * of the edge list.  Limits, each refused with ISINGMC_ERR_INVALID and a message: 1 <= n_tables <= 8; 1 <= n_classes <= 4096;
+ * n_tables * n_classes <= 8192 (the checkerboard kernel's histogram: 32 KiB of LDS); a class value >= n_classes that is not
+ * ISINGMC_NO_CLASS.  A handle serves the graph it was made for and is destroyed before it; destroy accepts NULL.
+ * isingmc_site_classes_sizes: the number of sites of every class, uint64[n_tables][n_classes] (the result of a pair (r, r)).
+ * isingmc_overlaps_by_class: a, b, slots_a, slots_b and n_pairs choose the pairs exactly as in isingmc_overlaps, with the same
+ * validation and messages, and the same containers are served and refused.  It also refuses a handle made for another graph and
+ * NULL classes or out.  The call synchronises.  It writes no configuration, consumes no random number and leaves the timestep
+ * counters alone.  Workspace: 8 bytes per (pair, table, class), and on replica-packed containers with slot tables the gather of
+ * isingmc_overlaps; the pairs are batched under a's option "cluster_workspace_bytes".  On replica-packed containers a class costs
+ * at least one workgroup per 32 replicas, however few sites it has. */
+#define ISINGMC_NO_CLASS 0xFFFFFFFFu
+typedef struct isingmc_site_classes isingmc_site_classes;
+int isingmc_site_classes_create(isingmc_graph *graph, const uint32_t *cls, size_t n_tables, size_t n_classes, isingmc_site_classes **out);
+int isingmc_site_classes_destroy(isingmc_site_classes *classes);
+int isingmc_site_classes_sizes(const isingmc_site_classes *classes, uint64_t *sizes_out);
+int isingmc_overlaps_by_class(isingmc_states *a, isingmc_states *b, const uint32_t *slots_a, const uint32_t *slots_b, size_t n_pairs,
+                              const isingmc_site_classes *classes, int64_t *out);
 
 /* ---- each replica's lowest-energy configuration, kept on the device (no reference counterpart) ----
  * A container may keep, per replica, the lowest energy its configuration has had at an UPDATE, the timestep of that update and

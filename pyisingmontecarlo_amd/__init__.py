@@ -3,6 +3,7 @@
   _capi            ctypes binding of the C ABI (include/isingmc.h, lib/libisingmc.so)
   _py_monte_carlo  C++ host shim with the reference's `py_monte_carlo` classes (Lattice, ClassicIsing)
   distributed      one-process-per-GPU replica sharding + parallel tempering over torch.distributed
+  correlation      numpy only: plane classes, chi_SG(k) and xi_L from the overlaps by site class
 
 The HIP library is mandatory: nothing in this package computes a spin flip on the CPU.
 """

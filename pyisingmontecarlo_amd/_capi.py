@@ -42,6 +42,8 @@ _PROTOTYPES = {
                                              C.POINTER(C.c_uint64)]),
     "isingmc_host_pa_sources": (C.c_int, [C.c_uint64, C.c_uint64, C.c_size_t, _vp, C.c_double, _vp, C.POINTER(C.c_uint64),
                                           C.POINTER(C.c_double)]),
+    "isingmc_host_class_segments": (C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, C.POINTER(C.c_size_t), _vp,
+                                              C.POINTER(C.c_size_t), _vp]),
     "isingmc_host_rj_quantise": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp, _vp, _vp, C.POINTER(C.c_int),
                                            C.POINTER(C.c_int)]),
     "isingmc_host_rj_energy_levels": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int)]),
@@ -78,6 +80,10 @@ _PROTOTYPES = {
     "isingmc_icm_between": (C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t]),
     "isingmc_icm_between_stats": (C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t]),
     "isingmc_overlaps": (C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
+    "isingmc_site_classes_create": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.POINTER(_vp)]),
+    "isingmc_site_classes_destroy": (C.c_int, [_vp]),
+    "isingmc_site_classes_sizes": (C.c_int, [_vp, _vp]),
+    "isingmc_overlaps_by_class": (C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
     "isingmc_states_set_track_best": (C.c_int, [_vp, C.c_size_t]),
     "isingmc_states_track_best": (C.c_int, [_vp, C.POINTER(C.c_size_t)]),
     "isingmc_best_update": (C.c_int, [_vp]),
@@ -273,6 +279,36 @@ def pa_sources(seed, step, energies, dbeta):
     return src, total.value, eref.value
 
 
+NO_CLASS = 0xFFFFFFFF
+
+
+def class_tables(tables, nvars, n_classes=None):
+    """(uint32[n_tables, nvars], n_classes) of one table or a stack of them; n_classes defaults to the largest class + 1, NO_CLASS
+    entries left aside."""
+    t = np.atleast_2d(_arr(tables, np.uint32))
+    if t.ndim != 2 or t.shape[1] != nvars:
+        raise ValueError("class tables must be one array of nvars entries, or a stack [n_tables, nvars] of them")
+    if n_classes is None:
+        classed = t[t != NO_CLASS]
+        n_classes = int(classed.max()) + 1 if classed.size else 1
+    return np.ascontiguousarray(t), int(n_classes)
+
+
+def class_segments(site, tables, n_classes):
+    """(order, seg[n_seg, 4] = {table, class, first, count}, sizes[n_tables, n_classes]): the position lists of a class set on the
+    replica-packed families from a position -> site table (0xFFFFFFFF on padding).  No device."""
+    site = _arr(site, np.uint32)
+    t = np.atleast_2d(_arr(tables, np.uint32))
+    n_tables, nvars = t.shape
+    order = np.zeros(max(n_tables * len(site), 1), dtype=np.uint32)
+    seg = np.zeros((max(n_tables * (max(int(n_classes), 0) + len(site) // 1024), 1), 4), dtype=np.uint32)
+    sizes = np.zeros((n_tables, max(int(n_classes), 0)), dtype=np.uint64)
+    n_order, n_seg = C.c_size_t(), C.c_size_t()
+    _check(lib().isingmc_host_class_segments(_p(site), len(site), _p(t), nvars, n_tables, int(n_classes), _p(order), C.byref(n_order),
+                                             _p(seg), C.byref(n_seg), _p(sizes)))
+    return order[:n_order.value], seg[:n_seg.value], sizes
+
+
 class PtGroup:
     """isingmc_pt_group: the shards of one ladder (States objects with the ladder attached, one per device) driven from this
     thread; the energies travel by RCCL (dlopen'd inside the library) or by device copies.  backend: 0 auto, 1 RCCL, 2 copies."""
@@ -348,6 +384,33 @@ class Graph:
                 if child is not None:
                     child.close()
             lib().isingmc_graph_destroy(self._h)
+            self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SiteClasses:
+    """isingmc_site_classes: class tables over one graph, rearranged once for the kernels and kept on its device.
+    tables: one table of nvars classes or a stack [n_tables, nvars], in the site numbering of the edge list; NO_CLASS = counted
+    nowhere.  .sizes: uint64[n_tables, n_classes], the sites of every class."""
+
+    def __init__(self, graph, tables, n_classes=None):
+        self.graph = graph  # keeps the graph alive
+        self._h = _vp()
+        t, n_classes = class_tables(tables, graph.nvars, n_classes)
+        self.n_tables, self.n_classes = t.shape[0], n_classes
+        _check(lib().isingmc_site_classes_create(graph._h, _p(t), self.n_tables, n_classes, C.byref(self._h)))
+        graph._children.append(weakref.ref(self))
+        self.sizes = np.zeros((self.n_tables, n_classes), dtype=np.uint64)
+        _check(lib().isingmc_site_classes_sizes(self._h, _p(self.sizes)))
+
+    def close(self):
+        if self._h:
+            lib().isingmc_site_classes_destroy(self._h)
             self._h = _vp()
 
     def __del__(self):
@@ -477,11 +540,8 @@ class States:
         _check(lib().isingmc_icm_between_stats(self._h, _p(out[0]), _p(out[1]), _p(out[2]), n))
         return tuple(out)
 
-    def overlaps(self, other=None, slots_a=None, slots_b=None, link=True):
-        """(spin, link): int64[n_pairs] each, spin[p] = sum_i s_i s'_i and link[p] = sum over the edge-list entries of
-        s_a s_b s'_a s'_b for pair p (DESIGN.md S15); link is None when not asked for.  Without tables: the pairs (2p, 2p + 1) of
-        this container, or with `other` pair p = (slot p of self, slot p of other) up to the smaller count; with tables pair p =
-        (slot slots_a[p] of self, slot slots_b[p] of `other`, or of self without one).  Reads only; synchronises."""
+    def _overlap_pairs(self, other, slots_a, slots_b):
+        """(slots_a, slots_b, n_pairs) as isingmc_overlaps and isingmc_overlaps_by_class take them."""
         if (slots_a is None) != (slots_b is None):
             raise ValueError("give both slot tables or neither")
         if slots_a is None:
@@ -492,10 +552,27 @@ class States:
             if sa.ndim != 1 or sa.shape != sb.shape:
                 raise ValueError("the slot tables must be two one-dimensional arrays of one length")
             n = sa.size
+        return sa, sb, n
+
+    def overlaps(self, other=None, slots_a=None, slots_b=None, link=True):
+        """(spin, link): int64[n_pairs] each, spin[p] = sum_i s_i s'_i and link[p] = sum over the edge-list entries of
+        s_a s_b s'_a s'_b for pair p (DESIGN.md S15); link is None when not asked for.  Without tables: the pairs (2p, 2p + 1) of
+        this container, or with `other` pair p = (slot p of self, slot p of other) up to the smaller count; with tables pair p =
+        (slot slots_a[p] of self, slot slots_b[p] of `other`, or of self without one).  Reads only; synchronises."""
+        sa, sb, n = self._overlap_pairs(other, slots_a, slots_b)
         spin = np.zeros(n, dtype=np.int64)
         lnk = np.zeros(n, dtype=np.int64) if link else None
         _check(lib().isingmc_overlaps(self._h, None if other is None else other._h, _p(sa), _p(sb), n, _p(spin), _p(lnk)))
         return spin, lnk
+
+    def overlaps_by_class(self, classes, other=None, slots_a=None, slots_b=None):
+        """int64[n_pairs, n_tables, n_classes]: out[p, t, c] = the sum of s_i s'_i over the sites i of class c of table t
+        (DESIGN.md S17), for the pairs overlaps() would take with the same arguments.  classes: a SiteClasses of this graph.
+        Reads only; synchronises."""
+        sa, sb, n = self._overlap_pairs(other, slots_a, slots_b)
+        out = np.zeros((n, classes.n_tables, classes.n_classes), dtype=np.int64)
+        _check(lib().isingmc_overlaps_by_class(self._h, None if other is None else other._h, _p(sa), _p(sb), n, classes._h, _p(out)))
+        return out
 
     # ---- each replica's lowest-energy configuration (DESIGN.md S16)
     def set_track_best(self, k):

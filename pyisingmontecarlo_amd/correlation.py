@@ -1,0 +1,34 @@
+"""From overlaps resolved by plane to the wave-vector-dependent spin-glass susceptibility and the second-moment
+correlation length -- numpy only, no device.
+
+For a wave vector k along a lattice axis,  sum_i q_i e^{i k x_i} = sum_x e^{i k x} Q_x  with Q_x the overlap q_i = s_i^a s_i^b summed
+over the plane at coordinate x: the device returns the L integers Q_x per pair and axis (States.overlaps_by_class with the tables
+of plane_classes), and the rest is a Fourier transform of L numbers.
+"""
+import numpy as np
+
+
+def plane_classes(shape):
+    """uint32[ndim, prod(shape)]: table a gives site i the class coords[a], its coordinate along axis a, where
+    i = np.ravel_multi_index(coords, shape) (C order: the LAST axis runs fastest).  The caller's site numbering must be this one:
+    a 2-d lattice with site y * W + x is shape (H, W) -- table 0 the rows y, table 1 the columns x -- and a cubic lattice with
+    site (z * L + y) * L + x is shape (L, L, L) with the tables z, y, x."""
+    shape = tuple(int(n) for n in shape)
+    return np.indices(shape, dtype=np.uint32).reshape(len(shape), -1)
+
+
+def chi_sg(planes, nvars):
+    """|fft(planes, axis=-1)|^2 / nvars: entry n is chi_SG at k_n = 2 pi n / L for ONE pair, planes[..., x] = Q_x the L plane
+    overlaps of one axis (leading axes, such as pairs, are kept).  Average it over pairs and samples before anything else."""
+    f = np.fft.fft(np.asarray(planes, dtype=np.float64), axis=-1)
+    return (f.real ** 2 + f.imag ** 2) / float(nvars)
+
+
+def correlation_length(chi0, chik, L, n=1):
+    """xi_L = sqrt(chi0 / chik - 1) / (2 sin(pi n / L)) from chi0 = chi_SG(0) and chik = chi_SG(k_n), k_n = 2 pi n / L.
+
+    Both arguments are AVERAGED susceptibilities: the average of chi_sg over the pairs of a sample (the thermal average) and over
+    the samples (the disorder average) comes BEFORE the ratio.  The ratio of one pair's values is not an estimate of anything: a
+    single |q_hat(k)|^2 is exponentially distributed and the mean of the ratios diverges."""
+    chi0, chik = np.asarray(chi0, dtype=np.float64), np.asarray(chik, dtype=np.float64)
+    return np.sqrt(chi0 / chik - 1.0) / (2.0 * np.sin(np.pi * n / L))

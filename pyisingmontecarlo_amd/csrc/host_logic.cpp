@@ -476,4 +476,28 @@ size_t nonlocal_batch(size_t items, size_t words_per_item, size_t workspace_byte
     return std::min({items, size_t(32768), std::max<size_t>(1, fit)});
 }
 
+ClassSegments class_segments(const uint32_t *site, size_t n_pos, const uint32_t *cls, size_t nvars, size_t n_tables, size_t n_classes)
+{
+    ClassSegments S;
+    S.sizes.assign(n_tables * n_classes, 0);
+    std::vector<uint32_t> start(n_classes + 1);
+    for (size_t t = 0; t < n_tables; t++) {
+        const uint32_t *c = cls + t * nvars;
+        uint64_t *size = S.sizes.data() + t * n_classes;
+        for (size_t p = 0; p < n_pos; p++)
+            if (site[p] != CLASS_PAD_SITE && c[site[p]] != CLASS_NONE) size[c[site[p]]]++;
+        // counting sort of the positions by class: ascending position inside a class
+        const size_t base = S.order.size();
+        start[0] = uint32_t(base);
+        for (size_t k = 0; k < n_classes; k++) start[k + 1] = start[k] + uint32_t(size[k]);
+        S.order.resize(start[n_classes]);
+        for (size_t k = 0; k < n_classes; k++)
+            for (uint32_t first = start[k]; first < start[k + 1]; first += CLASS_SEGMENT_MAX)
+                S.seg.insert(S.seg.end(), {uint32_t(t), uint32_t(k), first, std::min(CLASS_SEGMENT_MAX, start[k + 1] - first)});
+        for (size_t p = 0; p < n_pos; p++)
+            if (site[p] != CLASS_PAD_SITE && c[site[p]] != CLASS_NONE) S.order[start[c[site[p]]]++] = uint32_t(p);
+    }
+    return S;
+}
+
 } // namespace isingmc

@@ -97,6 +97,20 @@ void rj_log_table(uint32_t *out);
 // is the y dimension of one grid).  Internal to the library: not among its dynamic symbols.
 __attribute__((visibility("hidden"))) size_t nonlocal_batch(size_t items, size_t words_per_item, size_t workspace_bytes);
 
+// Site classes of the replica-packed families (device reader: overlap_class_kernels.hip).  site[n_pos]: the site of
+// every position, CLASS_PAD_SITE on padding; cls[n_tables][nvars]: a class below n_classes or CLASS_NONE per site.  Per table the
+// classed positions are sorted by class (ascending position inside a class) into `order`, and the sorted list is cut into
+// segments {table, class, first, count} -- `first` indexes `order`, count <= CLASS_SEGMENT_MAX, a segment never mixes classes or
+// tables; an empty class has no segment.  sizes[n_tables][n_classes]: sites per class.  The caller has checked the class values.
+constexpr uint32_t CLASS_NONE = 0xFFFFFFFFu, CLASS_PAD_SITE = 0xFFFFFFFFu;
+constexpr uint32_t CLASS_SEGMENT_MAX = 1024; // positions one workgroup of ovl_pk_class_kernel counts
+struct ClassSegments {
+    std::vector<uint32_t> order;
+    std::vector<uint32_t> seg; // four words per segment
+    std::vector<uint64_t> sizes;
+};
+ClassSegments class_segments(const uint32_t *site, size_t n_pos, const uint32_t *cls, size_t nvars, size_t n_tables, size_t n_classes);
+
 // packed checkerboard planes of one replica -> W*H bytes in site order (16 bytes per SSE2 store)
 void unpack_lattice(uint32_t W, uint32_t H, const uint32_t *words, uint8_t *spins);
 

@@ -3,7 +3,8 @@
 //   graph.hip      edge-list checks, host-only C ABI helpers, lattice / general / packed / real-coupling graph construction
 //   isingmc.hip    replica containers, every sweep / measurement launch, the persistent strip kernel's host side
 //   nonlocal.hip   host side of the non-local moves: Swendsen-Wang steps, isoenergetic cluster moves inside and between containers
-//   overlaps.hip   spin and link overlaps between replica pairs (isingmc_overlaps)
+//   overlaps.hip   spin and link overlaps between replica pairs (isingmc_overlaps), and the spin overlap by site class
+//                  (isingmc_site_classes_*, isingmc_overlaps_by_class)
 //   best.hip       each replica's lowest-energy configuration, kept on the device (isingmc_best_*)
 //   sampling.hip   get_states and the double-buffered sampling pipeline
 //   tempering.hip  on-stream parallel tempering, the in-process ladder group (RCCL through dlopen)
@@ -40,6 +41,7 @@
 #include "packed_kernels.hpp"
 #include "pa_kernels.hpp"
 #include "mc_types.hpp"
+#include "overlap_class_kernels.hpp"
 #include "overlap_kernels.hpp"
 #include "real_types.hpp"
 #include "spread_types.hpp"
@@ -48,6 +50,7 @@
 using namespace isingmc;
 
 static_assert(PA_PAD_SITE == PAD_SITE, "pa_kernels.hip tests PkGraphDev::site against the general path's padding mark");
+static_assert(CLASS_PAD_SITE == PAD_SITE, "host_logic.cpp class_segments tests the site table against the general path's padding mark");
 static_assert(PKC_PAD_SITE == PAD_SITE, "packed_cluster_kernels.hip tests PkGraphDev::site against the general path's padding mark");
 
 

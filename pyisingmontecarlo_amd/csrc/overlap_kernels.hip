@@ -22,34 +22,10 @@ namespace isingmc {
 namespace {
 
 constexpr uint32_t OVL_LAT_WORDS = 4;      // colour-0 words per thread of the checkerboard kernels (a workgroup covers 1024 words)
-constexpr uint32_t OVL_PK_ITER = 4;        // positions per thread of ovl_pk_count_kernel (a workgroup covers 1024 positions)
 constexpr uint32_t OVL_MAX_GRID_Y = 32768;
-constexpr int OVL_D_PLANES = 3;            // counts up to OVL_PK_ITER per thread and column
 constexpr int OVL_B_PLANES = 7;            // counts up to OVL_PK_ITER x 31 slots per thread and column
 static_assert(OVL_PK_ITER < (1u << OVL_D_PLANES) && OVL_PK_ITER * 31 < (1u << OVL_B_PLANES), "the bit-sliced counters must hold a thread's counts");
 static_assert(PK_MAX_DEG <= 31, "OVL_B_PLANES is sized for at most 31 adjacency slots");
-
-// c += x in every bit column (c: the planes of a bit-sliced counter, least significant first)
-template <int N>
-__device__ __forceinline__ void ovl_csa_add(uint32_t (&c)[N], uint32_t x)
-{
-#pragma unroll
-    for (int b = 0; b < N; b++) {
-        const uint32_t carry = c[b] & x;
-        c[b] ^= x;
-        x = carry;
-    }
-}
-
-// the wave's total of bit column `bit` of a bit-sliced counter (wave-uniform)
-template <int N>
-__device__ __forceinline__ uint32_t ovl_column_total(const uint32_t (&c)[N], uint32_t bit)
-{
-    uint32_t total = 0;
-#pragma unroll
-    for (int b = 0; b < N; b++) total += uint32_t(__popcll(__ballot((c[b] >> bit) & 1u))) << b;
-    return total;
-}
 
 // the body of both checkerboard kernels: sa / sb = the planes of the pair's two replicas, acc = the pair's two accumulators
 __device__ __forceinline__ void ovl_lat_body(const uint32_t *__restrict__ sa, const uint32_t *__restrict__ sb, const LatGeom &g,
@@ -228,12 +204,19 @@ hipError_t overlap_launch_packed_pairs(hipStream_t stream, const uint32_t *state
     return hipGetLastError();
 }
 
+hipError_t overlap_launch_packed_gather(hipStream_t stream, const OverlapSide &a, const OverlapSide &b, const PkGraphDev &G, uint32_t block0,
+                                        uint32_t n_blocks, uint32_t n_pairs, uint32_t *d)
+{
+    hipLaunchKernelGGL(ovl_pk_gather_kernel, dim3(G.n_pos / 8, n_blocks), dim3(256), 0, stream, a.state, b.state, a.slots, b.slots, a.bit0, b.bit0,
+                       a.n_slots, b.n_slots, G.n_pos, G.site, 32 * block0, n_pairs, d);
+    return hipGetLastError();
+}
+
 hipError_t overlap_launch_packed_tables(hipStream_t stream, const OverlapSide &a, const OverlapSide &b, const PkGraphDev &G,
                                         const uint32_t *nbr_rj, uint32_t rj_slots, bool link, uint32_t block0, uint32_t n_blocks,
                                         uint32_t n_pairs, uint32_t *d, unsigned long long *out)
 {
-    hipLaunchKernelGGL(ovl_pk_gather_kernel, dim3(G.n_pos / 8, n_blocks), dim3(256), 0, stream, a.state, b.state, a.slots, b.slots, a.bit0, b.bit0,
-                       a.n_slots, b.n_slots, G.n_pos, G.site, 32 * block0, n_pairs, d);
+    (void)overlap_launch_packed_gather(stream, a, b, G, block0, n_blocks, n_pairs, d);
     ovl_pk_launch_count<false>(stream, d, G, nbr_rj, rj_slots, link, n_blocks, out + 2 * 32 * size_t(block0));
     return hipGetLastError();
 }

@@ -17,6 +17,32 @@
 
 namespace isingmc {
 
+// ---- shared with overlap_class_kernels.hip --------------------------------------------------------------------
+constexpr uint32_t OVL_PK_ITER = 4; // positions per thread of the packed counting kernels (a workgroup covers 1024 positions)
+constexpr int OVL_D_PLANES = 3;     // counts up to OVL_PK_ITER per thread and column
+
+// c += x in every bit column (c: the planes of a bit-sliced counter, least significant first)
+template <int N>
+__device__ __forceinline__ void ovl_csa_add(uint32_t (&c)[N], uint32_t x)
+{
+#pragma unroll
+    for (int b = 0; b < N; b++) {
+        const uint32_t carry = c[b] & x;
+        c[b] ^= x;
+        x = carry;
+    }
+}
+
+// the wave's total of bit column `bit` of a bit-sliced counter (wave-uniform)
+template <int N>
+__device__ __forceinline__ uint32_t ovl_column_total(const uint32_t (&c)[N], uint32_t bit)
+{
+    uint32_t total = 0;
+#pragma unroll
+    for (int b = 0; b < N; b++) total += uint32_t(__popcll(__ballot((c[b] >> bit) & 1u))) << b;
+    return total;
+}
+
 // Checkerboard path (state u32[R][2 wpp]).  slots_a == nullptr: pair p = replicas (2 p, 2 p + 1) of state_a (state_b is not read);
 // else pair p = replica slots_a[p] of state_a and replica slots_b[p] of state_b (device tables; the two arrays may be one).
 // link = false: D alone, out[2 p + 1] stays zero.
@@ -37,6 +63,10 @@ struct OverlapSide {
     uint32_t bit0;         // slot s is bit (bit0 + s) & 31 of local group (bit0 + s) >> 5
     uint32_t n_slots;      // slots owned (a table entry at or beyond it reads nothing: the pair's overlap word bit stays 0)
 };
+
+// The gather alone (DESIGN.md S17 counts its words by class): d[n_blocks][n_pos] as below
+hipError_t overlap_launch_packed_gather(hipStream_t stream, const OverlapSide &a, const OverlapSide &b, const PkGraphDev &G, uint32_t block0,
+                                        uint32_t n_blocks, uint32_t n_pairs, uint32_t *d);
 
 // Arbitrary pairs: pair blocks [block0, block0 + n_blocks) of 32 pairs each (pair 32 B + i = bit i of block B) are gathered into
 // the overlap words d[n_blocks][n_pos] (bit i set where pair i differs; 0 on padding and on empty lanes) and counted into

@@ -18,11 +18,18 @@ static std::string overlaps_obstacle(const isingmc_states *a, const isingmc_stat
     return lattice_obstacle(g, "overlaps", true, false);
 }
 
-extern "C" int isingmc_overlaps(isingmc_states *a, isingmc_states *b, const uint32_t *slots_a, const uint32_t *slots_b, size_t n_pairs,
-                                int64_t *spin_out, int64_t *link_out)
+// The pairs of one call, validated: what isingmc_overlaps and isingmc_overlaps_by_class share.  On success b is never NULL and
+// either default_pairs holds (the pairing (2 p, 2 p + 1) inside one container, no tables) or slots_a / slots_b are host tables of
+// n_pairs entries below their containers' counts (`identity` backs them for two containers without tables).
+struct OverlapPairing {
+    isingmc_states *b = nullptr;
+    const uint32_t *slots_a = nullptr, *slots_b = nullptr;
+    bool default_pairs = false;
+    std::vector<uint32_t> identity;
+};
+
+static int overlap_pairing(isingmc_states *a, isingmc_states *b, const uint32_t *slots_a, const uint32_t *slots_b, size_t n_pairs, OverlapPairing &P)
 {
-    if (!a) return fail(ISINGMC_ERR_INVALID, "NULL states");
-    if (!spin_out) return fail(ISINGMC_ERR_INVALID, "NULL argument: spin_out (link_out alone may be NULL)");
     if (!b) b = a;
     {
         const std::string why = overlaps_obstacle(a, b);
@@ -30,21 +37,47 @@ extern "C" int isingmc_overlaps(isingmc_states *a, isingmc_states *b, const uint
     }
     if ((slots_a == nullptr) != (slots_b == nullptr)) return fail(ISINGMC_ERR_INVALID, "give both slot tables or neither");
     if (n_pairs == 0) return fail(ISINGMC_ERR_INVALID, "n_pairs is 0: nothing to measure");
-    const bool default_pairs = !slots_a && a == b; // (2 p, 2 p + 1) of the GLOBAL experiment index, as the isoenergetic moves pair them
-    std::vector<uint32_t> identity;
-    if (default_pairs) {
+    P.default_pairs = !slots_a && a == b; // (2 p, 2 p + 1) of the GLOBAL experiment index, as the isoenergetic moves pair them
+    if (P.default_pairs) {
         if (a->first % 2) return fail(ISINGMC_ERR_INVALID, "this shard starts at an odd experiment index: its first replica's partner lives on another shard");
         if (n_pairs != a->R / 2) return fail(ISINGMC_ERR_INVALID, "without slot tables n_pairs must be count / 2 (pair p = replicas (2 p, 2 p + 1))");
     } else if (!slots_a) { // two containers: pair p = (slot p of a, slot p of b)
         if (n_pairs > a->R || n_pairs > b->R) return fail(ISINGMC_ERR_INVALID, "without slot tables n_pairs must not exceed the smaller of the two counts");
-        identity.resize(n_pairs);
-        for (size_t p = 0; p < n_pairs; p++) identity[p] = uint32_t(p);
-        slots_a = slots_b = identity.data();
+        P.identity.resize(n_pairs);
+        for (size_t p = 0; p < n_pairs; p++) P.identity[p] = uint32_t(p);
+        slots_a = slots_b = P.identity.data();
     } else {
         if (n_pairs > 0xFFFFFFFFull - 32) return fail(ISINGMC_ERR_INVALID, "more than 2^32 - 33 pairs in one call");
         for (size_t p = 0; p < n_pairs; p++)
             if (slots_a[p] >= a->R || slots_b[p] >= b->R) return fail(ISINGMC_ERR_INVALID, "slot out of range: every table entry must be below its container's count");
     }
+    P.b = b;
+    P.slots_a = slots_a;
+    P.slots_b = slots_b;
+    return ISINGMC_OK;
+}
+
+// a's stream after b's sweeps and exchange rounds so far, before it reads b's configurations
+static int overlap_order_after(isingmc_states *a, isingmc_states *b)
+{
+    if (a == b) return ISINGMC_OK;
+    if (!a->icmb_ev[0]) HIP_TRY(pooled_event_create(&a->icmb_ev[0], true));
+    HIP_TRY(hipEventRecord(a->icmb_ev[0], b->stream));
+    HIP_TRY(hipStreamWaitEvent(a->stream, a->icmb_ev[0], 0));
+    return ISINGMC_OK;
+}
+
+extern "C" int isingmc_overlaps(isingmc_states *a, isingmc_states *b, const uint32_t *slots_a, const uint32_t *slots_b, size_t n_pairs,
+                                int64_t *spin_out, int64_t *link_out)
+{
+    if (!a) return fail(ISINGMC_ERR_INVALID, "NULL states");
+    if (!spin_out) return fail(ISINGMC_ERR_INVALID, "NULL argument: spin_out (link_out alone may be NULL)");
+    OverlapPairing P;
+    TRY(overlap_pairing(a, b, slots_a, slots_b, n_pairs, P));
+    b = P.b;
+    slots_a = P.slots_a;
+    slots_b = P.slots_b;
+    const bool default_pairs = P.default_pairs;
     const isingmc_graph *g = a->g;
     const bool link = link_out != nullptr;
     TRY(use_device(g->device));
@@ -65,11 +98,7 @@ extern "C" int isingmc_overlaps(isingmc_states *a, isingmc_states *b, const uint
         HIP_TRY(hipMemcpyAsync(d_sa, slots_a, n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, a->stream));
         HIP_TRY(hipMemcpyAsync(d_sb, slots_b, n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, a->stream));
     }
-    if (a != b) { // b's sweeps and exchange rounds so far, before a's stream reads b's configurations
-        if (!a->icmb_ev[0]) HIP_TRY(pooled_event_create(&a->icmb_ev[0], true));
-        HIP_TRY(hipEventRecord(a->icmb_ev[0], b->stream));
-        HIP_TRY(hipStreamWaitEvent(a->stream, a->icmb_ev[0], 0));
-    }
+    TRY(overlap_order_after(a, b));
     const uint32_t *nbr_rj = a->rj ? g->rj.nbr : nullptr;
     const uint32_t rj_slots = a->rj ? g->rj.slots : 0;
     if (!a->packed) {
@@ -90,6 +119,212 @@ extern "C" int isingmc_overlaps(isingmc_states *a, isingmc_states *b, const uint
     for (size_t p = 0; p < n_pairs; p++) {
         spin_out[p] = int64_t(g->nvars) - 2 * int64_t(h[2 * (acc0 + p)]);
         if (link) link_out[p] = int64_t(g->n_edges) - 2 * int64_t(h[2 * (acc0 + p) + 1]);
+    }
+    return ISINGMC_OK;
+}
+
+// ---- overlaps resolved by a class label per site ----------------------------------------------------------------
+// A class set as the kernels of overlap_class_kernels.hip read it: on a recognised lattice the tables in plane order with one
+// shared-class entry per word, on a graph with a replica-packed layout the positions sorted by class and cut into segments.  A
+// graph that only the f64 CSR family serves gets the sizes alone: the measurement refuses its containers.
+struct isingmc_site_classes {
+    const isingmc_graph *g = nullptr;
+    int device = 0;
+    size_t n_tables = 0, n_classes = 0;
+    std::vector<uint64_t> sizes; // [n_tables][n_classes]
+    bool has_lat = false, has_pk = false;
+    LatClassDev lat{};
+    PkClassDev pk{};
+    std::vector<void *> dev_allocs;
+};
+
+// the limits of a class set and the values of its tables ("" when they hold)
+static std::string class_set_obstacle(const uint32_t *cls, size_t nvars, size_t n_tables, size_t n_classes)
+{
+    if (n_tables < 1 || n_tables > 8) return "n_tables must be 1 .. 8";
+    if (n_classes < 1 || n_classes > 4096) return "n_classes must be 1 .. 4096";
+    if (n_tables * n_classes > OVC_MAX_BINS) return "n_tables * n_classes must not exceed 8192 (the histogram of the checkerboard kernel: 32 KiB of LDS)";
+    if (n_tables * nvars > 0xFFFFFFFFull) return "n_tables * nvars must stay below 2^32";
+    for (size_t i = 0; i < n_tables * nvars; i++)
+        if (cls[i] >= n_classes && cls[i] != ISINGMC_NO_CLASS)
+            return "class value out of range: table " + std::to_string(i / nvars) + " gives site " + std::to_string(i % nvars) + " the class " +
+                   std::to_string(cls[i]) + ", which is neither below n_classes = " + std::to_string(n_classes) + " nor ISINGMC_NO_CLASS";
+    return "";
+}
+
+extern "C" int isingmc_host_class_segments(const uint32_t *site, size_t n_pos, const uint32_t *cls, size_t nvars, size_t n_tables, size_t n_classes,
+                                           uint32_t *order_out, size_t *n_order_out, uint32_t *seg_out, size_t *n_seg_out, uint64_t *sizes_out)
+{
+    if (!site || !cls || !order_out || !n_order_out || !seg_out || !n_seg_out) return fail(ISINGMC_ERR_INVALID, "NULL argument (sizes_out alone may be NULL)");
+    {
+        const std::string why = class_set_obstacle(cls, nvars, n_tables, n_classes);
+        if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
+    }
+    for (size_t p = 0; p < n_pos; p++)
+        if (site[p] != CLASS_PAD_SITE && site[p] >= nvars) return fail(ISINGMC_ERR_INVALID, "site table entry out of range: a position holds a site below nvars or the padding mark");
+    const ClassSegments S = class_segments(site, n_pos, cls, nvars, n_tables, n_classes);
+    std::copy(S.order.begin(), S.order.end(), order_out);
+    std::copy(S.seg.begin(), S.seg.end(), seg_out);
+    if (sizes_out) std::copy(S.sizes.begin(), S.sizes.end(), sizes_out);
+    *n_order_out = S.order.size();
+    *n_seg_out = S.seg.size() / 4;
+    return ISINGMC_OK;
+}
+
+template <typename T>
+static int classes_upload(isingmc_site_classes *c, const T **dst, const T *src, size_t count)
+{
+    T *d = nullptr;
+    TRY(dev_alloc(&d, count));
+    c->dev_allocs.push_back(d);
+    if (count) HIP_TRY(hipMemcpy(d, src, count * sizeof(T), hipMemcpyHostToDevice));
+    *dst = d;
+    return ISINGMC_OK;
+}
+
+static int site_classes_fill(isingmc_site_classes *c, const uint32_t *cls)
+{
+    const isingmc_graph *g = c->g;
+    const size_t nvars = g->nvars, T = c->n_tables;
+    c->sizes.assign(T * c->n_classes, 0);
+    for (size_t t = 0; t < T; t++)
+        for (size_t i = 0; i < nvars; i++)
+            if (cls[t * nvars + i] != ISINGMC_NO_CLASS) c->sizes[t * c->n_classes + cls[t * nvars + i]]++;
+    if (g->kind == ISINGMC_KIND_LATTICE2D) { // plane order: site (x, y) is bit (x / 2) % 32 of word y wpr + x / 64 of plane (x + y) & 1
+        const LatGeom &L = g->geom;
+        const size_t words = 2 * size_t(L.wpp);
+        std::vector<uint32_t> perm(T * nvars), word_cls(T * words);
+        for (size_t t = 0; t < T; t++) {
+            for (uint32_t y = 0; y < L.H; y++)
+                for (uint32_t x = 0; x < L.W; x++) {
+                    const uint32_t plane = (x + y) & 1, i = x >> 1;
+                    perm[(t * words + size_t(plane) * L.wpp + size_t(y) * L.wpr + (i >> 5)) * 32 + (i & 31)] = cls[t * nvars + size_t(y) * L.W + x];
+                }
+            for (size_t w = 0; w < words; w++) {
+                const uint32_t *line = perm.data() + (t * words + w) * 32;
+                word_cls[t * words + w] = std::all_of(line, line + 32, [&](uint32_t v) { return v == line[0]; }) ? line[0] : OVC_MIXED;
+            }
+        }
+        TRY(classes_upload(c, &c->lat.cls, perm.data(), perm.size()));
+        TRY(classes_upload(c, &c->lat.word_cls, word_cls.data(), word_cls.size()));
+        c->lat.n_tables = uint32_t(T);
+        c->lat.n_classes = uint32_t(c->n_classes);
+        c->has_lat = true;
+    } else if (g->packed_ok || g->rj_ok) { // the content of PkGraphDev::site, from the host's site -> position table
+        const size_t n_pos = g->pk.n_pos;
+        std::vector<uint32_t> site(n_pos, PAD_SITE), order(T * n_pos), seg(4 * T * (c->n_classes + n_pos / CLASS_SEGMENT_MAX));
+        for (size_t i = 0; i < nvars; i++) site[g->pos[i]] = uint32_t(i);
+        size_t n_order = 0, n_seg = 0;
+        TRY(isingmc_host_class_segments(site.data(), n_pos, cls, nvars, T, c->n_classes, order.data(), &n_order, seg.data(), &n_seg, nullptr));
+        const uint32_t *d_seg = nullptr;
+        TRY(classes_upload(c, &c->pk.order, order.data(), n_order));
+        TRY(classes_upload(c, &d_seg, seg.data(), 4 * n_seg));
+        c->pk.seg = reinterpret_cast<const uint4 *>(d_seg);
+        c->pk.n_seg = uint32_t(n_seg);
+        c->pk.n_tables = uint32_t(T);
+        c->pk.n_classes = uint32_t(c->n_classes);
+        c->has_pk = true;
+    }
+    return ISINGMC_OK;
+}
+
+extern "C" int isingmc_site_classes_create(isingmc_graph *graph, const uint32_t *cls, size_t n_tables, size_t n_classes, isingmc_site_classes **out)
+{
+    if (!graph || !cls || !out) return fail(ISINGMC_ERR_INVALID, "NULL argument");
+    *out = nullptr;
+    {
+        const std::string why = class_set_obstacle(cls, graph->nvars, n_tables, n_classes);
+        if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
+    }
+    TRY(use_device(graph->device));
+    std::unique_ptr<isingmc_site_classes, int (*)(isingmc_site_classes *)> c(new isingmc_site_classes, isingmc_site_classes_destroy);
+    c->g = graph;
+    c->device = graph->device;
+    c->n_tables = n_tables;
+    c->n_classes = n_classes;
+    TRY(site_classes_fill(c.get(), cls));
+    *out = c.release();
+    return ISINGMC_OK;
+}
+
+extern "C" int isingmc_site_classes_destroy(isingmc_site_classes *classes)
+{
+    if (!classes) return ISINGMC_OK;
+    (void)hipSetDevice(classes->device); // (every measurement has waited for its kernels: nothing reads the blocks any more)
+    for (void *p : classes->dev_allocs) (void)cached_free(p);
+    delete classes;
+    return ISINGMC_OK;
+}
+
+extern "C" int isingmc_site_classes_sizes(const isingmc_site_classes *classes, uint64_t *sizes_out)
+{
+    if (!classes || !sizes_out) return fail(ISINGMC_ERR_INVALID, "NULL argument");
+    std::copy(classes->sizes.begin(), classes->sizes.end(), sizes_out);
+    return ISINGMC_OK;
+}
+
+extern "C" int isingmc_overlaps_by_class(isingmc_states *a, isingmc_states *b, const uint32_t *slots_a, const uint32_t *slots_b, size_t n_pairs,
+                                         const isingmc_site_classes *classes, int64_t *out)
+{
+    if (!a) return fail(ISINGMC_ERR_INVALID, "NULL states");
+    if (!classes || !out) return fail(ISINGMC_ERR_INVALID, "NULL argument: classes and out are both needed");
+    OverlapPairing P;
+    TRY(overlap_pairing(a, b, slots_a, slots_b, n_pairs, P));
+    b = P.b;
+    const isingmc_graph *g = a->g;
+    if (classes->g != g) return fail(ISINGMC_ERR_INVALID, "the class set was made for another graph handle: its tables follow that graph's layout");
+    if (a->packed ? !classes->has_pk : !classes->has_lat) return fail(ISINGMC_ERR_INVALID, "the class set holds no layout for this container's kernel family");
+    TRY(use_device(g->device));
+    for (isingmc_states *s : {a, b})
+        if (s->n_lanes > 1) TRY(lanes_join(s));
+    const size_t bins = classes->n_tables * classes->n_classes, workspace = size_t(std::max(1, a->opt.cluster_workspace_bytes));
+    DeviceScratch scratch(a->stream);
+    uint32_t *d_sa = nullptr, *d_sb = nullptr;
+    if (!P.default_pairs) { // (the host tables live as long as the call, which waits for the device before it returns)
+        TRY(scratch.alloc(&d_sa, 2 * n_pairs));
+        d_sb = d_sa + n_pairs;
+        HIP_TRY(hipMemcpyAsync(d_sa, P.slots_a, n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, a->stream));
+        HIP_TRY(hipMemcpyAsync(d_sb, P.slots_b, n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, a->stream));
+    }
+    TRY(overlap_order_after(a, b));
+    unsigned long long *d_acc = nullptr;
+    std::vector<unsigned long long> h;
+    // the accumulators of pair p as the p-th [n_tables][n_classes] block of the result
+    const auto store = [&](size_t p, const unsigned long long *D) {
+        for (size_t i = 0; i < bins; i++) out[p * bins + i] = int64_t(classes->sizes[i]) - 2 * int64_t(D[i]);
+    };
+    if (!a->packed) { // batches of pairs, two words per accumulator
+        const size_t batch = nonlocal_batch(n_pairs, 2 * bins, workspace), rw = 2 * size_t(g->geom.wpp);
+        TRY(scratch.alloc(&d_acc, batch * bins));
+        for (size_t p0 = 0; p0 < n_pairs; p0 += batch) {
+            const size_t n = std::min(batch, n_pairs - p0);
+            HIP_TRY(hipMemsetAsync(d_acc, 0, n * bins * sizeof(unsigned long long), a->stream));
+            HIP_TRY(overlap_class_launch_lattice(a->stream, P.default_pairs ? a->d_state + 2 * p0 * rw : a->d_state, b->d_state, d_sa ? d_sa + p0 : nullptr,
+                                                 d_sb ? d_sb + p0 : nullptr, g->geom, classes->lat, uint32_t(n), d_acc));
+            TRY(read_back(a, h, d_acc, n * bins));
+            for (size_t p = 0; p < n; p++) store(p0 + p, h.data() + p * bins);
+        }
+        return ISINGMC_OK;
+    }
+    // replica groups (16 pair columns, no workspace) or pair blocks of 32 pairs with their gathered overlap words
+    const size_t n_pos = g->pk.n_pos, cols = P.default_pairs ? 16 : 32, items = P.default_pairs ? a->groups : (n_pairs + 31) / 32;
+    const size_t col0 = P.default_pairs ? a->pk_bit0 / 2 : 0; // (column 16 group + pair of the first pair; pk_bit0 is even)
+    const size_t batch = nonlocal_batch(items, 2 * cols * bins + (P.default_pairs ? 0 : n_pos), workspace);
+    uint32_t *d_words = nullptr;
+    TRY(scratch.alloc(&d_acc, batch * cols * bins));
+    if (!P.default_pairs) TRY(scratch.alloc(&d_words, batch * n_pos));
+    const OverlapSide A{a->d_state, d_sa, uint32_t(a->pk_bit0), uint32_t(a->R)}, B{b->d_state, d_sb, uint32_t(b->pk_bit0), uint32_t(b->R)};
+    for (size_t i0 = 0; i0 < items; i0 += batch) {
+        const size_t n = std::min(batch, items - i0);
+        HIP_TRY(hipMemsetAsync(d_acc, 0, n * cols * bins * sizeof(unsigned long long), a->stream));
+        if (!P.default_pairs) HIP_TRY(overlap_launch_packed_gather(a->stream, A, B, g->pk, uint32_t(i0), uint32_t(n), uint32_t(n_pairs), d_words));
+        HIP_TRY(overlap_class_launch_packed(a->stream, P.default_pairs ? a->d_state + i0 * n_pos : d_words, uint32_t(n_pos), P.default_pairs,
+                                            classes->pk, uint32_t(n), d_acc));
+        TRY(read_back(a, h, d_acc, n * cols * bins));
+        for (size_t c = 0; c < n * cols; c++) {
+            const size_t column = i0 * cols + c;
+            if (column >= col0 && column - col0 < n_pairs) store(column - col0, h.data() + c * bins);
+        }
     }
     return ISINGMC_OK;
 }

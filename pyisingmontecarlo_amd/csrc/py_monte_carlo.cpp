@@ -91,6 +91,37 @@ struct StatesHandle {
     ~StatesHandle() { isingmc_states_destroy(s); }
 };
 
+// class tables as Python gives them: one integer array of nvars classes or a stack [n_tables, nvars]; n_classes
+// None = the largest class + 1, ISINGMC_NO_CLASS entries left aside
+struct ClassTables {
+    std::vector<uint32_t> cls;
+    size_t n_tables = 0, n_classes = 0;
+};
+
+ClassTables class_tables(const py::object &tables, const py::object &n_classes, size_t nvars)
+{
+    const auto arr = py::array_t<int64_t, py::array::c_style | py::array::forcecast>::ensure(tables);
+    if (!arr || arr.ndim() < 1 || arr.ndim() > 2 || size_t(arr.shape(arr.ndim() - 1)) != nvars)
+        throw py::value_error("class tables must be one integer array of nvars entries, or a stack [n_tables, nvars] of them");
+    ClassTables T;
+    T.n_tables = arr.ndim() == 2 ? size_t(arr.shape(0)) : 1;
+    T.cls.resize(size_t(arr.size()));
+    const int64_t *v = arr.data();
+    int64_t largest = -1;
+    for (size_t i = 0; i < T.cls.size(); i++) {
+        if (v[i] < 0 || v[i] > int64_t(ISINGMC_NO_CLASS)) throw py::value_error("class value out of range: a class is a non-negative integer or NO_CLASS (0xFFFFFFFF)");
+        T.cls[i] = uint32_t(v[i]);
+        if (T.cls[i] != ISINGMC_NO_CLASS) largest = std::max(largest, v[i]);
+    }
+    T.n_classes = n_classes.is_none() ? size_t(largest + 1 > 0 ? largest + 1 : 1) : n_classes.cast<size_t>();
+    return T;
+}
+
+struct ClassesHandle {
+    isingmc_site_classes *c = nullptr;
+    ~ClassesHandle() { isingmc_site_classes_destroy(c); }
+};
+
 struct EdgeArrays {
     std::vector<uint64_t> a, b;
     std::vector<double> j;
@@ -407,13 +438,18 @@ public:
     // (isingmc_pa_run) enqueues it all; nothing waits on the host until the end.
     // measure_overlaps: the result also carries the spin and link overlaps of the final population between the
     // replicas (p, p + R / 2) (isingmc_overlaps); pairs of one family are the caller's to drop.
+    // overlap_classes (needs measure_overlaps): class tables, one array of nvars classes or a stack of them; the
+    // result also carries overlaps_by_class, int64[R / 2, n_tables, n_classes] for the same pairs (isingmc_overlaps_by_class).
     // track_minimum: every SLOT keeps the lowest-energy configuration that ever sat in it, seen before every
     // resampling and after the last sweeps; the result carries the population's minimum over the slots as min_energy, min_state
     // and min_beta_index (the index of the beta whose sweeps produced it).
     py::object run_population_annealing(const std::vector<double> &betas, size_t sweeps_per_beta, size_t population, bool return_states,
-                                        bool measure_overlaps, bool track_minimum)
+                                        bool measure_overlaps, bool track_minimum, const py::object &overlap_classes)
     {
         require_classical();
+        if (!overlap_classes.is_none() && !measure_overlaps)
+            throw py::value_error("overlap_classes resolves the overlaps of measure_overlaps=True by site class: it needs measure_overlaps");
+        const ClassTables classes = overlap_classes.is_none() ? ClassTables{} : class_tables(overlap_classes, py::none(), E_->nvars);
         if (betas.empty()) throw py::value_error("betas must hold at least one inverse temperature");
         for (size_t k = 0; k < betas.size(); k++)
             if (!std::isfinite(betas[k]) || (k && betas[k] < betas[k - 1])) throw py::value_error("betas must be finite and non-decreasing");
@@ -436,6 +472,8 @@ public:
         py::array_t<int64_t> ovl_pairs(std::vector<ssize_t>{ssize_t(n_ovl), 2}), ovl_spin(std::vector<ssize_t>{ssize_t(n_ovl)}),
             ovl_link(std::vector<ssize_t>{ssize_t(n_ovl)});
         int64_t *op = ovl_pairs.mutable_data(), *os = ovl_spin.mutable_data(), *ol = ovl_link.mutable_data();
+        py::array_t<int64_t> ovl_class(std::vector<ssize_t>{ssize_t(classes.n_tables ? n_ovl : 0), ssize_t(classes.n_tables), ssize_t(classes.n_classes)});
+        int64_t *oc = ovl_class.mutable_data();
         py::array_t<bool> min_state(std::vector<ssize_t>{ssize_t(track_minimum ? N : 0)});
         uint8_t *mst = reinterpret_cast<uint8_t *>(min_state.mutable_data());
         double min_energy = std::numeric_limits<double>::infinity();
@@ -473,6 +511,12 @@ public:
                     op[2 * p + 1] = int64_t(sb[p] = uint32_t(p + n_ovl));
                 }
                 rc = isingmc_overlaps(h.s, nullptr, sa.data(), sb.data(), n_ovl, os, ol);
+                if (rc == ISINGMC_OK && classes.n_tables) {
+                    ClassesHandle ch;
+                    rc = isingmc_site_classes_create(gh->g, classes.cls.data(), classes.n_tables, classes.n_classes, &ch.c);
+                    if (rc == ISINGMC_OK) rc = isingmc_overlaps_by_class(h.s, nullptr, sa.data(), sb.data(), n_ovl, ch.c, oc);
+                    if (rc != ISINGMC_OK) msg = isingmc_last_error(); // (before the handle's destructor calls into the library again)
+                }
             }
             if (rc == ISINGMC_OK && track_minimum) { // the population's minimum: the first slot with the lowest record
                 std::vector<double> be(R);
@@ -488,7 +532,7 @@ public:
                     std::copy(bs.begin() + arg * N, bs.begin() + (arg + 1) * N, mst);
                 }
             }
-            if (rc != ISINGMC_OK) msg = isingmc_last_error();
+            if (rc != ISINGMC_OK && msg.empty()) msg = isingmc_last_error();
         }
         if (rc == ISINGMC_ERR_INVALID) throw py::value_error(msg);
         if (rc == ISINGMC_ERR_ALLOC) throw std::bad_alloc();
@@ -513,6 +557,7 @@ public:
             d["overlap_pairs"] = ovl_pairs;
             d["spin_overlaps"] = ovl_spin;
             d["link_overlaps"] = ovl_link;
+            if (classes.n_tables) d["overlaps_by_class"] = ovl_class;
         }
         if (track_minimum) {
             d["min_energy"] = min_energy;
@@ -751,22 +796,7 @@ public:
     py::tuple get_overlaps(const py::object &pairs, bool link)
     {
         std::vector<uint32_t> sa, sb;
-        size_t n = isingmc_states_count(st_->s) / 2;
-        if (!pairs.is_none()) {
-            const auto arr = py::array_t<int64_t, py::array::c_style | py::array::forcecast>::ensure(pairs);
-            if (!arr || arr.ndim() != 2 || arr.shape(1) != 2) throw py::value_error("pairs must be an integer array of shape [n, 2]");
-            n = size_t(arr.shape(0));
-            const size_t R = isingmc_states_count(st_->s);
-            const int64_t *v = arr.data();
-            sa.resize(n);
-            sb.resize(n);
-            for (size_t p = 0; p < n; p++) {
-                if (v[2 * p] < 0 || v[2 * p + 1] < 0 || size_t(v[2 * p]) >= R || size_t(v[2 * p + 1]) >= R)
-                    throw py::value_error("slot out of range: every graph index of `pairs` must be below get_num_graphs()");
-                sa[p] = uint32_t(v[2 * p]);
-                sb[p] = uint32_t(v[2 * p + 1]);
-            }
-        }
+        const size_t n = overlap_pairs(pairs, sa, sb);
         py::array_t<int64_t> spin(std::vector<ssize_t>{ssize_t(n)}), lnk(std::vector<ssize_t>{ssize_t(link ? n : 0)});
         int64_t *s_out = spin.mutable_data(), *l_out = link ? lnk.mutable_data() : nullptr;
         {
@@ -774,6 +804,24 @@ public:
             check(isingmc_overlaps(st_->s, nullptr, pairs_ptr(sa), pairs_ptr(sb), n, s_out, l_out));
         }
         return py::make_tuple(spin, link ? py::object(lnk) : py::object(py::none()));
+    }
+    // extension: the spin overlap between the persistent replicas resolved by site class.  classes: one integer
+    // array of nvars classes or a stack [n_tables, nvars] (NO_CLASS = 0xFFFFFFFF: counted nowhere); n_classes: None = the largest
+    // class + 1; pairs as get_overlaps takes them.  Returns int64[n, n_tables, n_classes]; ValueError where the library refuses.
+    py::array_t<int64_t> get_overlaps_by_class(const py::object &classes, const py::object &n_classes, const py::object &pairs)
+    {
+        const ClassTables T = class_tables(classes, n_classes, E_.nvars);
+        std::vector<uint32_t> sa, sb;
+        const size_t n = overlap_pairs(pairs, sa, sb);
+        py::array_t<int64_t> out(std::vector<ssize_t>{ssize_t(n), ssize_t(T.n_tables), ssize_t(T.n_classes)});
+        int64_t *o = out.mutable_data();
+        {
+            py::gil_scoped_release nogil;
+            ClassesHandle ch;
+            check(isingmc_site_classes_create(st_->graph->g, T.cls.data(), T.n_tables, T.n_classes, &ch.c));
+            check(isingmc_overlaps_by_class(st_->s, nullptr, pairs_ptr(sa), pairs_ptr(sb), n, ch.c, o));
+        }
+        return out;
     }
     // extension: every persistent replica's lowest-energy configuration, kept on the device.
     // set_track_minimum(every): an update of the records follows every timestep after which t % every == 0 (0: off); add_graph is
@@ -805,6 +853,25 @@ public:
 
 private:
     static const uint32_t *pairs_ptr(const std::vector<uint32_t> &v) { return v.empty() ? nullptr : v.data(); }
+    // `pairs` of get_overlaps / get_overlaps_by_class as two slot tables (left empty for None); returns the number of pairs
+    size_t overlap_pairs(const py::object &pairs, std::vector<uint32_t> &sa, std::vector<uint32_t> &sb) const
+    {
+        const size_t R = isingmc_states_count(st_->s);
+        if (pairs.is_none()) return R / 2;
+        const auto arr = py::array_t<int64_t, py::array::c_style | py::array::forcecast>::ensure(pairs);
+        if (!arr || arr.ndim() != 2 || arr.shape(1) != 2) throw py::value_error("pairs must be an integer array of shape [n, 2]");
+        const size_t n = size_t(arr.shape(0));
+        const int64_t *v = arr.data();
+        sa.resize(n);
+        sb.resize(n);
+        for (size_t p = 0; p < n; p++) {
+            if (v[2 * p] < 0 || v[2 * p + 1] < 0 || size_t(v[2 * p]) >= R || size_t(v[2 * p + 1]) >= R)
+                throw py::value_error("slot out of range: every graph index of `pairs` must be below get_num_graphs()");
+            sa[p] = uint32_t(v[2 * p]);
+            sb[p] = uint32_t(v[2 * p + 1]);
+        }
+        return n;
+    }
     // nspinupdates = single-spin attempts per timestep (classicising.rs:88-110 hands it to do_time_step; crate default:
     // nvars).  The engine attempts every site once per sweep, in the colour order, so attempts are executed sweep by
     // sweep: `timesteps` timesteps of n attempts add timesteps x n attempts to a cursor that persists across calls,
@@ -886,7 +953,8 @@ PYBIND11_MODULE(_py_monte_carlo, m)
              "betas"_a, "timesteps"_a, "num_experiments"_a, "only_basic_moves"_a = py::none(),
              "edge_move_importance_sampling"_a = py::none(), "replica_range"_a = py::none())
         .def("run_population_annealing", &Lattice::run_population_annealing, "betas"_a, "sweeps_per_beta"_a, "population"_a,
-             py::kw_only(), "return_states"_a = true, "measure_overlaps"_a = false, "track_minimum"_a = false)
+             py::kw_only(), "return_states"_a = true, "measure_overlaps"_a = false, "track_minimum"_a = false,
+             "overlap_classes"_a = py::none())
         .def("run_monte_carlo_annealing_and_get_minimum", &Lattice::run_monte_carlo_annealing_and_get_minimum, "betas"_a, "timesteps"_a,
              "num_experiments"_a, "every"_a = 1, "only_basic_moves"_a = py::none())
         .def("clone", &Lattice::clone);
@@ -920,6 +988,7 @@ PYBIND11_MODULE(_py_monte_carlo, m)
         .def("get_states", &ClassicIsing::get_states)
         .def("get_num_graphs", &ClassicIsing::get_num_graphs)
         .def("get_overlaps", &ClassicIsing::get_overlaps, "pairs"_a = py::none(), "link"_a = true)
+        .def("get_overlaps_by_class", &ClassicIsing::get_overlaps_by_class, "classes"_a, "n_classes"_a = py::none(), "pairs"_a = py::none())
         .def("set_track_minimum", &ClassicIsing::set_track_minimum, "every"_a)
         .def("get_minimum", &ClassicIsing::get_minimum)
         .def("reset_minimum", &ClassicIsing::reset_minimum)

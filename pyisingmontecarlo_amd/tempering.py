@@ -209,6 +209,34 @@ class ClassicalTempering:
         perm = self.get_permutation()
         return a._states.overlaps(b._states, perm[0], perm[1], link=link)
 
+    def site_classes(self, tables, n_classes=None):
+        """copies=2 only: the class tables (one array of nvars classes or a stack [n_tables, nvars]) as a device-resident class
+        set of the ladder's graph, for get_overlaps_by_class: built once, used at every measurement."""
+        if self._pair is None:
+            raise ValueError("overlaps need two configurations per temperature: build the ladder with copies=2")
+        self._materialise_pair()
+        states = self._pair[0]._states
+        if not hasattr(states, "overlaps_by_class"):
+            raise ValueError("this engine has no overlap measurement by site class (overlaps_by_class)")
+        return _capi.SiteClasses(states.graph, tables, n_classes)
+
+    def get_overlaps_by_class(self, classes, n_classes=None):
+        """copies=2 only: int64[G, n_tables, n_classes], entry r the spin overlap between the two configurations currently at
+        rung r resolved by site class: out[r, t, c] = sum of s_i s'_i over the sites of class c of table t, in the
+        order of get_betas() and for the pairs of get_overlaps().  classes: what site_classes() returned, or class tables (a
+        class set is then built for this one call).  Reads only."""
+        own = not isinstance(classes, _capi.SiteClasses)
+        if own:
+            classes = self.site_classes(classes, n_classes)
+        try:
+            self._materialise_pair()
+            a, b = self._pair
+            perm = self.get_permutation()
+            return a._states.overlaps_by_class(classes, b._states, perm[0], perm[1])
+        finally:
+            if own:
+                classes.close()
+
     # -- every slot's lowest-energy configuration (DESIGN.md S16) ---------------------------------------------------------------
     def set_track_minimum(self, on):
         """Keep, on the device, the lowest-energy configuration every SLOT has held at an exchange round: the round's own energy
