@@ -13,6 +13,7 @@
 // the same move between two containers, paired through slot tables in device memory.
 #include "cluster_kernels.hpp"
 #include "cluster_union.hpp"
+#include "philox.hpp"
 
 namespace isingmc {
 

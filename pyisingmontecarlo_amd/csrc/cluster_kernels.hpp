@@ -8,7 +8,7 @@
 #include <cstddef>
 #include <cstdint>
 
-#include "lattice_kernels.hpp"
+#include "lattice_types.hpp"
 
 namespace isingmc {
 

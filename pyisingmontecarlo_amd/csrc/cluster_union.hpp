@@ -1,7 +1,8 @@
 // Union-find on a label array that other threads link concurrently (LDS: workgroup scope, global: agent scope), shared by
-// cluster_kernels.hip (S8-S10) and packed_cluster_kernels.hip (S11).  Every union links a root to a SMALLER label with an
-// integer atomicMin, so the final root of a component is its smallest member whatever the order of execution, and every loop
-// walks strictly decreasing labels: it ends without waiting for any other thread.
+// cluster_kernels.hip (S8-S10) and, through packed_label.hpp, packed_cluster_kernels.hip (S11), packed_icm_kernels.hip (S12)
+// and packed_between_kernels.hip (S13).  Every union links a root to a SMALLER label with an integer atomicMin, so the final
+// root of a component is its smallest member whatever the order of execution, and every loop walks strictly decreasing labels:
+// it ends without waiting for any other thread.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

@@ -32,9 +32,9 @@
 #include "../../include/isingmc.h"
 #include "best_kernels.hpp"
 #include "cluster_kernels.hpp"
+#include "lattice_kernels.hpp" // (ahead of general_kernels.hpp: a code object lists its kernels in the order of their definitions)
 #include "general_kernels.hpp"
 #include "host_logic.hpp"
-#include "lattice_kernels.hpp"
 #include "packed_between_kernels.hpp"
 #include "packed_cluster_kernels.hpp"
 #include "packed_icm_kernels.hpp"

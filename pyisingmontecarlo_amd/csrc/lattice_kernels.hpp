@@ -13,28 +13,11 @@
 // The few spins whose prefix ties the threshold (2^-N_PLANES of them) are resolved with one 32-bit
 // Philox word each.  Everything is integer: the CPU oracle reproduces the configurations bit for bit.
 #pragma once
+#include "lattice_types.hpp"
 #include "philox.hpp"
 #include <type_traits>
 
 namespace isingmc {
-
-struct LatGeom {
-    uint32_t W, H;
-    uint32_t wpr;    // words per colour-row = W / 64
-    uint32_t wpp;    // words per plane = H * wpr
-    uint32_t nquads; // wpp / 4
-    int32_t cols_log2; // log2(quads per row) when the division-free, parity-uniform thread mapping applies, else -1
-};
-
-struct LatThr {
-    uint64_t T3, T4; // floor(exp(-beta dE) 2^THR_BITS) for k = 3, 4; 2^THR_BITS = always accept
-};
-
-#ifndef ISINGMC_N_PLANES
-#define ISINGMC_N_PLANES 7
-#endif
-constexpr int N_PLANES = ISINGMC_N_PLANES;
-constexpr int THR_BITS = N_PLANES + 32; // acceptance probabilities are fixed-point with this many bits
 
 __device__ __forceinline__ uint32_t sel4(uint4 v, uint32_t i)
 {

@@ -402,8 +402,8 @@ extern "C" int isingmc_icm_between(isingmc_states *a, isingmc_states *b, const u
     uint32_t *const stats = a->d_icmb_stats, *const minus = a->d_icmb_stats + 2 * a->icmb_cap;
     if (a->packed) {
         const PkBetweenWork work = pk_between_carve(a->d_icmb_work, batch, n_pos);
-        const PkBetweenSide A{a->d_state, d_sa, a->d_icmb_inv, uint32_t(a->pk_bit0), uint32_t(a->R), uint32_t(a->groups)};
-        const PkBetweenSide B{b->d_state, d_sb, a->d_icmb_inv + 32 * a->groups, uint32_t(b->pk_bit0), uint32_t(b->R), uint32_t(b->groups)};
+        const PkBetweenSide A{{a->d_state, d_sa, uint32_t(a->pk_bit0), uint32_t(a->R)}, a->d_icmb_inv, uint32_t(a->groups)};
+        const PkBetweenSide B{{b->d_state, d_sb, uint32_t(b->pk_bit0), uint32_t(b->R)}, a->d_icmb_inv + 32 * a->groups, uint32_t(b->groups)};
         HIP_TRY(pk_between_launch_tables(a->stream, A, B, uint32_t(n_pairs)));
         for (size_t b0 = 0; b0 < items; b0 += batch)
             HIP_TRY(pk_between_launch_batch(a->stream, A, B, g->pk, a->rj ? g->rj.nbr : nullptr, a->rj ? g->rj.slots : 0, a->t, a->d_keys, work, uint32_t(b0),

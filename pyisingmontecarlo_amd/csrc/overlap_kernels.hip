@@ -7,14 +7,15 @@
 //                      formed on the fly, 16 pair columns) or per pair block (the gathered words, 32 pair columns); one thread per
 //                      position and OVL_PK_ITER positions after one another: bit-sliced carry-save counters per column, then one
 //                      ballot per (column, counter plane)
-//   ovl_pk_gather_kernel                      one thread per (position, pair lane): the d member of pkb_gather_kernel
+//   ovl_pk_gather_kernel                      one thread per (position, pair lane): the overlap words of pair blocks, through the
+//                      gather that S13's pkb_gather_kernel uses (packed_label.hpp)
 // Every kernel reduces in the wavefront, across its four waves through LDS, and ends with one 64-bit atomic per counter and
 // workgroup.  Nothing is written but the accumulators and the gather's own workspace.
 #include "overlap_kernels.hpp"
 
 #include <algorithm>
 
-#include "packed_cluster_kernels.hpp"
+#include "packed_label.hpp"
 #include "packed_nbr.hpp"
 
 namespace isingmc {
@@ -142,24 +143,10 @@ __global__ __launch_bounds__(256) void ovl_pk_count_kernel(const uint32_t *__res
 }
 
 // grid: (n_pos / 8, n_blocks); a wave = two consecutive positions x 32 pair lanes.  pair0 = 32 x the batch's first block.
-__global__ __launch_bounds__(256) void ovl_pk_gather_kernel(const uint32_t *__restrict__ a_state, const uint32_t *__restrict__ b_state,
-                                                            const uint32_t *__restrict__ slots_a, const uint32_t *__restrict__ slots_b,
-                                                            const uint32_t bit0_a, const uint32_t bit0_b, const uint32_t n_slots_a,
-                                                            const uint32_t n_slots_b, const uint32_t n_pos, const uint32_t *__restrict__ site,
+__global__ __launch_bounds__(256) void ovl_pk_gather_kernel(const PkSide a, const PkSide b, const uint32_t n_pos, const uint32_t *__restrict__ site,
                                                             const uint32_t pair0, const uint32_t n_pairs, uint32_t *__restrict__ d)
 {
-    const uint32_t B = blockIdx.y, i = threadIdx.x & 31u, pl = threadIdx.x >> 5, p = blockIdx.x * 8 + pl;
-    const uint32_t n = pair0 + 32 * B + i;
-    uint32_t x = 0;
-    if (n < n_pairs && site[p] != PKC_PAD_SITE) {
-        const uint32_t sa = slots_a[n], sb = slots_b[n];
-        if (sa < n_slots_a && sb < n_slots_b) {
-            const uint32_t ca = bit0_a + sa, cb = bit0_b + sb;
-            x = ((a_state[size_t(ca >> 5) * n_pos + p] >> (ca & 31u)) ^ (b_state[size_t(cb >> 5) * n_pos + p] >> (cb & 31u))) & 1u;
-        }
-    }
-    const uint64_t differ = __ballot(x != 0); // lanes 0..31: this wave's even position-lane, 32..63: the odd one
-    if (i == 0) d[size_t(B) * n_pos + p] = uint32_t(differ >> (32 * (pl & 1u)));
+    pkl_gather_word(a, b, n_pos, site, pair0, n_pairs, d);
 }
 
 hipError_t overlap_launch_lattice(hipStream_t stream, const uint32_t *state_a, const uint32_t *state_b, const uint32_t *slots_a,
@@ -185,12 +172,10 @@ void ovl_pk_launch_count(hipStream_t stream, const uint32_t *words, const PkGrap
                          uint32_t items, unsigned long long *out)
 {
     const uint32_t n_pos = G.n_pos, blocks = (n_pos + 256 * OVL_PK_ITER - 1) / (256 * OVL_PK_ITER);
-    if (nbr_rj)
-        hipLaunchKernelGGL((ovl_pk_count_kernel<RjNbr, PAIRED>), dim3(blocks, items), dim3(256), 0, stream, words, RjNbr{nbr_rj, n_pos, rj_slots},
-                           link ? rj_slots : 0u, n_pos, G.site, out);
-    else
-        hipLaunchKernelGGL((ovl_pk_count_kernel<PkNbr, PAIRED>), dim3(blocks, items), dim3(256), 0, stream, words, PkNbr{G.nbr_ell, n_pos},
-                           link ? uint32_t(PK_MAX_DEG) : 0u, n_pos, G.site, out);
+    pk_nbr_dispatch(G, nbr_rj, rj_slots, [&](auto nbr) {
+        hipLaunchKernelGGL((ovl_pk_count_kernel<decltype(nbr), PAIRED>), dim3(blocks, items), dim3(256), 0, stream, words, nbr,
+                           link ? nbr.slots() : 0u, n_pos, G.site, out);
+    });
 }
 
 } // namespace
@@ -204,15 +189,14 @@ hipError_t overlap_launch_packed_pairs(hipStream_t stream, const uint32_t *state
     return hipGetLastError();
 }
 
-hipError_t overlap_launch_packed_gather(hipStream_t stream, const OverlapSide &a, const OverlapSide &b, const PkGraphDev &G, uint32_t block0,
+hipError_t overlap_launch_packed_gather(hipStream_t stream, const PkSide &a, const PkSide &b, const PkGraphDev &G, uint32_t block0,
                                         uint32_t n_blocks, uint32_t n_pairs, uint32_t *d)
 {
-    hipLaunchKernelGGL(ovl_pk_gather_kernel, dim3(G.n_pos / 8, n_blocks), dim3(256), 0, stream, a.state, b.state, a.slots, b.slots, a.bit0, b.bit0,
-                       a.n_slots, b.n_slots, G.n_pos, G.site, 32 * block0, n_pairs, d);
+    hipLaunchKernelGGL(ovl_pk_gather_kernel, dim3(G.n_pos / 8, n_blocks), dim3(256), 0, stream, a, b, G.n_pos, G.site, 32 * block0, n_pairs, d);
     return hipGetLastError();
 }
 
-hipError_t overlap_launch_packed_tables(hipStream_t stream, const OverlapSide &a, const OverlapSide &b, const PkGraphDev &G,
+hipError_t overlap_launch_packed_tables(hipStream_t stream, const PkSide &a, const PkSide &b, const PkGraphDev &G,
                                         const uint32_t *nbr_rj, uint32_t rj_slots, bool link, uint32_t block0, uint32_t n_blocks,
                                         uint32_t n_pairs, uint32_t *d, unsigned long long *out)
 {

@@ -56,22 +56,15 @@ hipError_t overlap_launch_lattice(hipStream_t stream, const uint32_t *state_a, c
 hipError_t overlap_launch_packed_pairs(hipStream_t stream, const uint32_t *state, const PkGraphDev &G, const uint32_t *nbr_rj,
                                        uint32_t rj_slots, bool link, size_t groups, unsigned long long *out);
 
-// one of the two containers of the arbitrary-pair form as the kernels see it (the two may be the same container)
-struct OverlapSide {
-    const uint32_t *state; // [groups][n_pos]
-    const uint32_t *slots; // [n_pairs] device table
-    uint32_t bit0;         // slot s is bit (bit0 + s) & 31 of local group (bit0 + s) >> 5
-    uint32_t n_slots;      // slots owned (a table entry at or beyond it reads nothing: the pair's overlap word bit stays 0)
-};
-
+// The arbitrary-pair form takes its two containers as PkSide (packed_types.hpp; the two may be the same container).
 // The gather alone (DESIGN.md S17 counts its words by class): d[n_blocks][n_pos] as below
-hipError_t overlap_launch_packed_gather(hipStream_t stream, const OverlapSide &a, const OverlapSide &b, const PkGraphDev &G, uint32_t block0,
+hipError_t overlap_launch_packed_gather(hipStream_t stream, const PkSide &a, const PkSide &b, const PkGraphDev &G, uint32_t block0,
                                         uint32_t n_blocks, uint32_t n_pairs, uint32_t *d);
 
 // Arbitrary pairs: pair blocks [block0, block0 + n_blocks) of 32 pairs each (pair 32 B + i = bit i of block B) are gathered into
 // the overlap words d[n_blocks][n_pos] (bit i set where pair i differs; 0 on padding and on empty lanes) and counted into
 // out[32 block0 ...].  n_blocks <= 32768.
-hipError_t overlap_launch_packed_tables(hipStream_t stream, const OverlapSide &a, const OverlapSide &b, const PkGraphDev &G,
+hipError_t overlap_launch_packed_tables(hipStream_t stream, const PkSide &a, const PkSide &b, const PkGraphDev &G,
                                         const uint32_t *nbr_rj, uint32_t rj_slots, bool link, uint32_t block0, uint32_t n_blocks,
                                         uint32_t n_pairs, uint32_t *d, unsigned long long *out);
 

@@ -109,7 +109,7 @@ extern "C" int isingmc_overlaps(isingmc_states *a, isingmc_states *b, const uint
         const size_t batch = nonlocal_batch(blocks, n_pos, size_t(std::max(1, a->opt.cluster_workspace_bytes)));
         uint32_t *d_words = nullptr;
         TRY(scratch.alloc(&d_words, batch * n_pos));
-        const OverlapSide A{a->d_state, d_sa, uint32_t(a->pk_bit0), uint32_t(a->R)}, B{b->d_state, d_sb, uint32_t(b->pk_bit0), uint32_t(b->R)};
+        const PkSide A{a->d_state, d_sa, uint32_t(a->pk_bit0), uint32_t(a->R)}, B{b->d_state, d_sb, uint32_t(b->pk_bit0), uint32_t(b->R)};
         for (size_t b0 = 0; b0 < blocks; b0 += batch)
             HIP_TRY(overlap_launch_packed_tables(a->stream, A, B, g->pk, nbr_rj, rj_slots, link, uint32_t(b0), uint32_t(std::min(batch, blocks - b0)),
                                                  uint32_t(n_pairs), d_words, d_acc));
@@ -313,7 +313,7 @@ extern "C" int isingmc_overlaps_by_class(isingmc_states *a, isingmc_states *b, c
     uint32_t *d_words = nullptr;
     TRY(scratch.alloc(&d_acc, batch * cols * bins));
     if (!P.default_pairs) TRY(scratch.alloc(&d_words, batch * n_pos));
-    const OverlapSide A{a->d_state, d_sa, uint32_t(a->pk_bit0), uint32_t(a->R)}, B{b->d_state, d_sb, uint32_t(b->pk_bit0), uint32_t(b->R)};
+    const PkSide A{a->d_state, d_sa, uint32_t(a->pk_bit0), uint32_t(a->R)}, B{b->d_state, d_sb, uint32_t(b->pk_bit0), uint32_t(b->R)};
     for (size_t i0 = 0; i0 < items; i0 += batch) {
         const size_t n = std::min(batch, items - i0);
         HIP_TRY(hipMemsetAsync(d_acc, 0, n * cols * bins * sizeof(unsigned long long), a->stream));

@@ -10,18 +10,19 @@
 //   pkb_flip_kernel    one thread per (position-lane, pair lane), eight positions after one another: d = 1 lanes chase to the root
 //                      and look the flip bit up, ballot -> the flip word f[B][p]; counts the d = 1 positions, the roots and the
 //                      positions per root
-//   pkc_max_kernel     (packed_cluster_kernels.hip, unchanged: the sizes have its layout) largest cluster
+//   pkl_max_kernel<32> (S11's instantiation, through pk_cluster_launch_max: the sizes have its layout) largest cluster
 //   pkb_apply_kernel   once per container, one thread per state word: XORs the flip bit of every owned bit that belongs to a pair
 //                      of the batch into the word, one plain store per changed word -- no atomics on spin words
 // Labels are laid out [block][position][pair lane]: a wave covers two consecutive positions x 32 pairs, so the first hop of a
 // chase is one coalesced 128-byte row per position.  No kernel waits for another workgroup; every loop walks strictly decreasing
 // labels (cluster_union.hpp).  Everything that depends on blockIdx alone (the inverse-table row of a group) is wave-uniform.
+// The gather of the overlap word, the owned-bond union loop, the counting of roots, d = 1 positions and positions per root and the
+// workgroup reduction are packed_label.hpp's, shared with S11, S12 and S15.
 #include "packed_between_kernels.hpp"
 
 #include <algorithm>
 
-#include "cluster_union.hpp"
-#include "packed_cluster_kernels.hpp"
+#include "packed_label.hpp"
 #include "packed_nbr.hpp"
 #include "philox.hpp"
 
@@ -31,17 +32,6 @@ namespace {
 
 constexpr uint32_t PKB_FLIP_POS = 64;          // positions per workgroup of pkb_flip_kernel (n_pos is a multiple of 256)
 constexpr uint32_t PKB_MAX_GRID_Y = 32768;
-constexpr int AGENT = __HIP_MEMORY_SCOPE_AGENT;
-
-// per-lane combination of the 8 position-lanes of a workgroup (lane = tid & 31 = pair lane) -> threads 0..31
-template <typename OP>
-__device__ __forceinline__ uint32_t pkb_reduce_lanes(uint32_t v, uint32_t (&red)[4][32], OP op)
-{
-    v = op(v, uint32_t(__shfl_xor(v, 32)));
-    if ((threadIdx.x & 63u) < 32) red[threadIdx.x >> 6][threadIdx.x & 31u] = v;
-    __syncthreads();
-    return threadIdx.x < 32 ? op(op(red[0][threadIdx.x], red[1][threadIdx.x]), op(red[2][threadIdx.x], red[3][threadIdx.x])) : 0u;
-}
 
 } // namespace
 
@@ -56,35 +46,22 @@ __global__ __launch_bounds__(256) void pkb_inverse_kernel(const uint32_t *__rest
 }
 
 // grid: (n_pos / 8, n_blocks); a wave = two consecutive positions x 32 pair lanes.  pair0 = 32 x the batch's first block.
-__global__ __launch_bounds__(256) void pkb_gather_kernel(const uint32_t *__restrict__ a_state, const uint32_t *__restrict__ b_state,
-                                                         const uint32_t *__restrict__ slots_a, const uint32_t *__restrict__ slots_b,
-                                                         const uint32_t bit0_a, const uint32_t bit0_b, const uint32_t n_slots_a,
-                                                         const uint32_t n_slots_b, const uint32_t n_pos, const uint32_t *__restrict__ site,
+__global__ __launch_bounds__(256) void pkb_gather_kernel(const PkSide a, const PkSide b, const uint32_t n_pos, const uint32_t *__restrict__ site,
                                                          const uint64_t t, const uint2 *__restrict__ a_keys, const uint32_t pair0,
                                                          const uint32_t n_pairs, uint32_t *__restrict__ labels, uint32_t *__restrict__ sizes,
                                                          uint32_t *__restrict__ d, uint32_t *__restrict__ fliptab)
 {
-    const uint32_t B = blockIdx.y, i = threadIdx.x & 31u, pl = threadIdx.x >> 5, p = blockIdx.x * 8 + pl;
-    const uint32_t n = pair0 + 32 * B + i;
-    uint32_t x = 0;
-    if (n < n_pairs && site[p] != PKC_PAD_SITE) {
-        const uint32_t sa = slots_a[n], sb = slots_b[n];
-        if (sa < n_slots_a && sb < n_slots_b) {
-            const uint32_t ca = bit0_a + sa, cb = bit0_b + sb;
-            x = ((a_state[size_t(ca >> 5) * n_pos + p] >> (ca & 31u)) ^ (b_state[size_t(cb >> 5) * n_pos + p] >> (cb & 31u))) & 1u;
-        }
-    }
-    const uint64_t differ = __ballot(x != 0); // lanes 0..31: this wave's even position-lane, 32..63: the odd one
-    if (i == 0) d[size_t(B) * n_pos + p] = uint32_t(differ >> (32 * (pl & 1u)));
+    const uint32_t B = blockIdx.y;
+    pkl_gather_word(a, b, n_pos, site, pair0, n_pairs, d);
     const size_t idx = size_t(blockIdx.x) * 256 + threadIdx.x, base = size_t(B) * n_pos * 32;
-    labels[base + idx] = p;
+    labels[base + idx] = uint32_t(idx >> 5);
     sizes[base + idx] = 0;
     if (idx < n_pos / 4) { // (whole waves: n_pos / 4 is a multiple of 64) call c of pair lane j: root positions 128 c .. 128 c + 127
         const uint32_t calls = n_pos >> 7, j = uint32_t(idx) / calls, c = uint32_t(idx) % calls, nj = pair0 + 32 * B + j;
         if (nj < n_pairs) {
-            const uint32_t sa = slots_a[nj];
-            if (sa < n_slots_a) {
-                const uint32_t ca = bit0_a + sa;
+            const uint32_t sa = a.slots[nj];
+            if (sa < a.n_slots) {
+                const uint32_t ca = a.bit0 + sa;
                 const uint4 v = philox4x32_10(make_uint4(uint32_t(t), c, DOM_PK_BETWEEN_FLIP, ctr2(t, ca & 31u, 0)), a_keys[ca >> 5]);
                 *reinterpret_cast<uint4 *>(fliptab + size_t(B) * n_pos + size_t(j) * (n_pos >> 5) + 4 * c) = v;
             }
@@ -101,12 +78,7 @@ __global__ __launch_bounds__(256) void pkb_union_kernel(const NBR nbr, const uin
     const uint32_t *dB = d + size_t(B) * n_pos;
     if (!((dB[p] >> i) & 1u)) return;
     uint32_t *lab = labels + size_t(B) * n_pos * 32 + i; // this pair's labels: lab[32 position]
-    const uint32_t n_slots = nbr.slots();
-    for (uint32_t k = 0; k < n_slots; k++) {
-        const uint32_t q = nbr(k, p);
-        if (q <= p) continue; // the end with the smaller position owns the bond
-        if ((dB[q] >> i) & 1u) cl_unite<AGENT, 32>(lab, p, q);
-    }
+    pkl_unite_owned<32>(lab, nbr, p, [&](uint32_t q) { return (dB[q] >> i) & 1u; });
 }
 
 // grid: (n_pos / PKB_FLIP_POS, n_blocks); thread (position-lane pl = tid / 32, pair lane i) visits positions base + 8 it + pl.
@@ -118,39 +90,23 @@ __global__ __launch_bounds__(256) void pkb_flip_kernel(const uint32_t n_pos, con
     __shared__ uint32_t red[4][32];
     const uint32_t B = blockIdx.y, i = threadIdx.x & 31u, pl = threadIdx.x >> 5;
     const uint32_t *lab = labels + size_t(B) * n_pos * 32 + i;
-    uint32_t *sz = sizes + size_t(B) * n_pos * 32 + i;
     const uint32_t *ft = fliptab + size_t(B) * n_pos + size_t(i) * (n_pos >> 5);
     const uint32_t *dB = d + size_t(B) * n_pos;
     uint32_t *fB = f + size_t(B) * n_pos;
-    // positions per root: consecutive positions of one root (a large cluster) add up in a register before they go out
-    uint32_t n_roots = 0, n_minus = 0, run_root = 0, run = 0;
+    PklCounts<32> counts{sizes + size_t(B) * n_pos * 32 + i};
     for (uint32_t it = 0; it < PKB_FLIP_POS / 8; it++) {
         const uint32_t p = blockIdx.x * PKB_FLIP_POS + 8 * it + pl;
         uint32_t flip = 0;
         if ((dB[p] >> i) & 1u) {
-            const uint32_t root = cl_find<AGENT, 32>(lab, p);
+            const uint32_t root = cl_find<PKL_AGENT, 32>(lab, p);
             flip = (ft[root >> 5] >> (root & 31u)) & 1u;
-            n_minus++;
-            n_roots += root == p;
-            if (run && root != run_root) {
-                atomicAdd(sz + size_t(32) * run_root, run);
-                run = 0;
-            }
-            run_root = root;
-            run++;
+            counts.account(p, root);
         }
         const uint64_t flips = __ballot(flip != 0); // lanes 0..31: this wave's even position-lane, 32..63: the odd one
         if (i == 0) fB[p] = uint32_t(flips >> (32 * (pl & 1u)));
     }
-    // the two position-lanes of a wave often end in the same root: one atomic for both
-    const uint32_t o_root = uint32_t(__shfl_xor(run_root, 32)), o_run = uint32_t(__shfl_xor(run, 32));
-    if (run && o_run && o_root == run_root) run = (pl & 1u) ? 0 : run + o_run;
-    if (run) atomicAdd(sz + size_t(32) * run_root, run);
-    const uint32_t roots = pkb_reduce_lanes(n_roots, red, [](uint32_t a, uint32_t c) { return a + c; });
-    if (threadIdx.x < 32 && roots) atomicAdd(stats + 2 * (32 * size_t(B) + threadIdx.x), roots);
-    __syncthreads(); // red is reused
-    const uint32_t total = pkb_reduce_lanes(n_minus, red, [](uint32_t a, uint32_t c) { return a + c; });
-    if (threadIdx.x < 32 && total) atomicAdd(minus + 32 * size_t(B) + threadIdx.x, total);
+    counts.flush();
+    counts.finish(red, B, stats, minus);
 }
 
 // grid: (n_pos / 256, groups); thread = the state word of (local group blockIdx.y, position).  The inverse-table row of the group
@@ -185,14 +141,11 @@ hipError_t pk_between_launch_batch(hipStream_t stream, const PkBetweenSide &a, c
                                    uint32_t n_pairs, uint32_t *stats, uint32_t *minus)
 {
     const uint32_t n_pos = G.n_pos, pair0 = 32 * block0;
-    hipLaunchKernelGGL(pkb_gather_kernel, dim3(n_pos / 8, n_blocks), dim3(256), 0, stream, a.state, b.state, a.slots, b.slots, a.bit0, b.bit0,
-                       a.n_slots, b.n_slots, n_pos, G.site, t, a_keys, pair0, n_pairs, work.labels, work.sizes, work.d, work.fliptab);
-    if (nbr_rj)
-        hipLaunchKernelGGL(pkb_union_kernel<RjNbr>, dim3(n_pos / 8, n_blocks), dim3(256), 0, stream, RjNbr{nbr_rj, n_pos, rj_slots}, n_pos, work.d,
-                           work.labels);
-    else
-        hipLaunchKernelGGL(pkb_union_kernel<PkNbr>, dim3(n_pos / 8, n_blocks), dim3(256), 0, stream, PkNbr{G.nbr_ell, n_pos}, n_pos, work.d,
-                           work.labels);
+    hipLaunchKernelGGL(pkb_gather_kernel, dim3(n_pos / 8, n_blocks), dim3(256), 0, stream, PkSide(a), PkSide(b), n_pos, G.site, t, a_keys, pair0,
+                       n_pairs, work.labels, work.sizes, work.d, work.fliptab);
+    pk_nbr_dispatch(G, nbr_rj, rj_slots, [&](auto nbr) {
+        hipLaunchKernelGGL(pkb_union_kernel<decltype(nbr)>, dim3(n_pos / 8, n_blocks), dim3(256), 0, stream, nbr, n_pos, work.d, work.labels);
+    });
     hipLaunchKernelGGL(pkb_flip_kernel, dim3(n_pos / PKB_FLIP_POS, n_blocks), dim3(256), 0, stream, n_pos, work.d, work.labels, work.fliptab,
                        work.sizes, work.f, stats + 2 * size_t(pair0), minus + pair0);
     hipError_t rc = pk_cluster_launch_max(stream, n_pos, work.sizes, n_blocks, stats + 2 * size_t(pair0));

@@ -40,13 +40,9 @@ static inline PkBetweenWork pk_between_carve(uint32_t *block, size_t batch, uint
     return PkBetweenWork{block, sizes, d, f, fliptab};
 }
 
-// one of the two containers as the kernels see it
-struct PkBetweenSide {
-    uint32_t *state;       // [groups][n_pos]
-    const uint32_t *slots; // [n_pairs] slot of every pair (a device table: the host's copy or a ladder's rung permutation)
+// one of the two containers as the kernels see it: PkSide (packed_types.hpp) and what the move writes back through
+struct PkBetweenSide : PkSide {
     uint32_t *inv;         // [groups][32] pair of every (local group, bit), PKB_NO_PAIR where none (pk_between_launch_tables)
-    uint32_t bit0;         // slot s is bit (bit0 + s) & 31 of local group (bit0 + s) >> 5
-    uint32_t n_slots;      // slots owned (a table entry at or beyond it names no pair: nothing is read or written for it)
     uint32_t groups;
 };
 

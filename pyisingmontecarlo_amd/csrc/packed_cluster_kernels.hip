@@ -8,14 +8,15 @@
 //   pkc_union_kernel   one thread per (position, replica bit): every active owned bond hooks the larger root below the smaller
 //   pkc_flip_kernel    one thread per (position, replica bit), eight positions after one another: chase to the root, look the flip
 //                      bit up, ballot -> XOR into the state word; counts the roots and the positions per root
-//   pkc_max_kernel     largest cluster
+//   pkl_max_kernel<32> largest cluster (packed_label.hpp; pk_cluster_launch_max launches it for S13 too)
 // Labels are laid out [group][position][replica bit]: lane = replica bit, so the first hop of a wave is one coalesced 128-byte
-// row per position.  Padding positions own no bonds, are never flipped and never counted.
+// row per position.  Padding positions own no bonds, are never flipped and never counted.  The counting of roots and of
+// positions per root, the workgroup reduction and the largest-cluster kernel are packed_label.hpp's, shared with S12 and S13.
 #include "packed_cluster_kernels.hpp"
 
 #include <algorithm>
 
-#include "cluster_union.hpp"
+#include "packed_label.hpp"
 #include "philox.hpp"
 
 namespace isingmc {
@@ -23,17 +24,6 @@ namespace isingmc {
 namespace {
 
 constexpr uint32_t PKC_FLIP_POS = 64;          // positions per workgroup of pkc_flip_kernel (n_pos is a multiple of 256)
-constexpr int AGENT = __HIP_MEMORY_SCOPE_AGENT;
-
-// per-lane counts of the 8 position-lanes of a workgroup (lane = tid & 31 = replica bit) -> threads 0..31
-template <typename OP>
-__device__ __forceinline__ uint32_t pkc_reduce_bits(uint32_t v, uint32_t (&red)[4][32], OP op)
-{
-    v = op(v, uint32_t(__shfl_xor(v, 32)));
-    if ((threadIdx.x & 63u) < 32) red[threadIdx.x >> 6][threadIdx.x & 31u] = v;
-    __syncthreads();
-    return threadIdx.x < 32 ? op(op(red[0][threadIdx.x], red[1][threadIdx.x]), op(red[2][threadIdx.x], red[3][threadIdx.x])) : 0u;
-}
 
 } // namespace
 
@@ -96,7 +86,7 @@ __global__ __launch_bounds__(256) void pkc_union_kernel(const PkGraphDev G, cons
 #pragma unroll
     for (uint32_t k = 0; k < uint32_t(PK_MAX_DEG); k++) {
         const uint32_t w = bonds[(size_t(g) * PK_MAX_DEG + k) * G.n_pos + p];
-        if ((w >> b) & 1u) cl_unite<AGENT, 32>(lab, p, G.nbr_ell[size_t(k) * G.n_pos + p] & 0x7FFFFFFFu);
+        if ((w >> b) & 1u) cl_unite<PKL_AGENT, 32>(lab, p, G.nbr_ell[size_t(k) * G.n_pos + p] & 0x7FFFFFFFu);
     }
 }
 
@@ -109,48 +99,24 @@ __global__ __launch_bounds__(256) void pkc_flip_kernel(uint32_t *__restrict__ st
     __shared__ uint32_t red[4][32];
     const uint32_t g = blockIdx.y, b = threadIdx.x & 31u, pl = threadIdx.x >> 5;
     const uint32_t *lab = labels + size_t(g) * G.n_pos * 32 + b;
-    uint32_t *sz = sizes + size_t(g) * G.n_pos * 32 + b;
     const uint32_t *ft = fliptab + size_t(g) * G.n_pos;
     uint32_t *st = state + size_t(g) * G.n_pos;
-    // positions per root: consecutive positions of one root (a large cluster) add up in a register before they go out
-    uint32_t n_roots = 0, run_root = 0, run = 0;
+    PklCounts<32> counts{sizes + size_t(g) * G.n_pos * 32 + b};
     for (uint32_t i = 0; i < PKC_FLIP_POS / 8; i++) {
         const uint32_t p = blockIdx.x * PKC_FLIP_POS + 8 * i + pl;
         const bool real = G.site[p] != PKC_PAD_SITE;
         uint32_t flip = 0;
         if (real) {
-            const uint32_t root = cl_find<AGENT, 32>(lab, p);
+            const uint32_t root = cl_find<PKL_AGENT, 32>(lab, p);
             flip = (ft[root] >> b) & 1u;
-            n_roots += root == p;
-            if (run && root != run_root) {
-                atomicAdd(sz + size_t(32) * run_root, run);
-                run = 0;
-            }
-            run_root = root;
-            run++;
+            counts.account(p, root);
         }
         const uint64_t flips = __ballot(flip != 0); // lanes 0..31: this wave's even position-lane, 32..63: the odd one
         const uint32_t word = uint32_t(flips >> (32 * (pl & 1u)));
         if (b == 0 && word) st[p] ^= word;
     }
-    // the two position-lanes of a wave often end in the same root: one atomic for both
-    const uint32_t o_root = uint32_t(__shfl_xor(run_root, 32)), o_run = uint32_t(__shfl_xor(run, 32));
-    if (run && o_run && o_root == run_root) run = (pl & 1u) ? 0 : run + o_run;
-    if (run) atomicAdd(sz + size_t(32) * run_root, run);
-    const uint32_t total = pkc_reduce_bits(n_roots, red, [](uint32_t a, uint32_t c) { return a + c; });
-    if (threadIdx.x < 32 && total) atomicAdd(stats + 2 * (32 * size_t(g) + threadIdx.x), total);
-}
-
-// grid: (min(n_pos / 8, 1024), n)
-__global__ __launch_bounds__(256) void pkc_max_kernel(const uint32_t n_pos, const uint32_t *__restrict__ sizes, uint32_t *__restrict__ stats)
-{
-    __shared__ uint32_t red[4][32];
-    const uint32_t g = blockIdx.y, b = threadIdx.x & 31u, pl = threadIdx.x >> 5;
-    const uint32_t *sz = sizes + size_t(g) * n_pos * 32 + b;
-    uint32_t m = 0;
-    for (uint32_t p = blockIdx.x * 8 + pl; p < n_pos; p += gridDim.x * 8) m = max(m, sz[size_t(32) * p]);
-    const uint32_t total = pkc_reduce_bits(m, red, [](uint32_t a, uint32_t c) { return max(a, c); });
-    if (threadIdx.x < 32 && total) atomicMax(stats + 2 * (32 * size_t(g) + threadIdx.x) + 1, total);
+    counts.flush();
+    counts.finish(red, g, stats);
 }
 
 hipError_t pk_cluster_launch_step(hipStream_t stream, uint32_t *state, const PkGraphDev &G, uint64_t t, const uint2 *group_keys, uint64_t thr,
@@ -162,13 +128,12 @@ hipError_t pk_cluster_launch_step(hipStream_t stream, uint32_t *state, const PkG
                        work.bonds);
     hipLaunchKernelGGL(pkc_union_kernel, dim3(n_pos / 8, n), dim3(256), 0, stream, G, work.bonds, work.labels);
     hipLaunchKernelGGL(pkc_flip_kernel, dim3(n_pos / PKC_FLIP_POS, n), dim3(256), 0, stream, state, G, work.labels, work.fliptab, work.sizes, stats);
-    hipLaunchKernelGGL(pkc_max_kernel, dim3(std::min(n_pos / 8, 1024u), n), dim3(256), 0, stream, n_pos, work.sizes, stats);
-    return hipGetLastError();
+    return pk_cluster_launch_max(stream, n_pos, work.sizes, n, stats);
 }
 
 hipError_t pk_cluster_launch_max(hipStream_t stream, uint32_t n_pos, const uint32_t *sizes, uint32_t n, uint32_t *stats)
 {
-    hipLaunchKernelGGL(pkc_max_kernel, dim3(std::min(n_pos / 8, 1024u), n), dim3(256), 0, stream, n_pos, sizes, stats);
+    hipLaunchKernelGGL(pkl_max_kernel<32>, dim3(std::min(n_pos / 8, 1024u), n), dim3(256), 0, stream, n_pos, sizes, stats);
     return hipGetLastError();
 }
 

@@ -5,7 +5,7 @@
 
 #include <cstdint>
 
-#include "lattice_kernels.hpp"
+#include "lattice_types.hpp"
 
 namespace isingmc {
 
@@ -33,6 +33,15 @@ struct PkGraphDev {
     const uint32_t *class_base; // n_colours + 1, multiples of 256
     uint32_t n_colours;
     uint32_t n_pos;             // multiple of 256
+};
+
+// One of the two containers of an arbitrary pairing as the kernels see it (S13's moves, S15's overlaps; the two may be the same
+// container): pair n is slot slots[n] of it.
+struct PkSide {
+    uint32_t *state;       // [groups][n_pos]
+    const uint32_t *slots; // [n_pairs] slot of every pair (a device table: the host's copy or a ladder's rung permutation)
+    uint32_t bit0;         // slot s is bit (bit0 + s) & 31 of local group (bit0 + s) >> 5
+    uint32_t n_slots;      // slots owned (a table entry at or beyond it names no pair: nothing is read or written for it)
 };
 
 // Block headers of the one-degree kernels (packed_uni_kernels.hpp), [n_pos / 64][PK_MAX_DEG] each:
