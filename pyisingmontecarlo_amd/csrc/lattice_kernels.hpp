@@ -181,9 +181,13 @@ __device__ __forceinline__ void bond_masks(const uint32_t own, const QuadNbr &n,
 }
 
 // Bit-sliced decision state of one quad: class masks (3 / 4 satisfied bonds), "prefix already smaller than
-// the threshold" and "prefix still equal to it" per spin.
+// the threshold" and "prefix still equal to it" per spin.  und0 = eq3 | eq4 stays as the class stage left it: the planes
+// whose threshold bit is set for both classes take it as their threshold word, and the final xor (quad_new_words) reads it.
+// The class-3 mask itself is not kept.  Only the spins of und0 matter from here on (und never leaves und0, and quad_new_words
+// ignores lt outside it), and among them "class 3" is "not class 4": the planes whose threshold bit is set for class 3 alone
+// read ~eq4 through their truth tables (BITOP_LT_NOT, BITOP_UND_NOT).  Four registers less through the Philox calls.
 struct QuadState {
-    uint32_t eq3[4], eq4[4], lt[4], und[4];
+    uint32_t eq4[4], lt[4], und[4], und0[4];
 };
 
 // the wave-uniform threshold data of a replica as the kernels consume it
@@ -247,6 +251,7 @@ template <bool PMJ>
 __device__ __forceinline__ void quad_classes(const uint32_t own[4], const QuadNbr &n, const ThrBits &tb, const QuadSigns &js,
                                              const uint32_t jneg_uniform, QuadState &st)
 {
+    uint32_t eq3[4];
     if constexpr (PMJ) {
 #pragma unroll
         for (int q = 0; q < 4; q++) { // jneg planes hold 1 where J < 0: satisfied = own ^ neighbour ^ jneg
@@ -254,7 +259,7 @@ __device__ __forceinline__ void quad_classes(const uint32_t own[4], const QuadNb
             const uint32_t a1 = own[q] ^ n.dn[q] ^ js.w[q][1];
             const uint32_t a2 = own[q] ^ n.ce[q] ^ js.w[q][2];
             const uint32_t a3 = own[q] ^ n.si[q] ^ js.w[q][3];
-            class_masks(a0 ^ a1, a0 & a1, a2 ^ a3, a2 & a3, st.eq3[q], st.eq4[q]);
+            class_masks(a0 ^ a1, a0 & a1, a2 ^ a3, a2 & a3, eq3[q], st.eq4[q]);
         }
     } else {
         // One sign for the whole graph (jneg_uniform is 0 or ~0, in an SGPR): the bond masks a_i = own ^ neighbour ^ sign are
@@ -277,20 +282,31 @@ __device__ __forceinline__ void quad_classes(const uint32_t own[4], const QuadNb
             }
         }
 #pragma unroll
-        for (int q = 0; q < 4; q++) class_masks(n.up[q] ^ n.dn[q], c01[q], n.ce[q] ^ n.si[q], c23[q], st.eq3[q], st.eq4[q]);
+        for (int q = 0; q < 4; q++) class_masks(n.up[q] ^ n.dn[q], c01[q], n.ce[q] ^ n.si[q], c23[q], eq3[q], st.eq4[q]);
     }
     if (tb.any_all) { // threshold 2^THR_BITS (beta = 0 ...): the class flips outright, like k <= 2; scalar branch, rarely taken
 #pragma unroll
         for (int q = 0; q < 4; q++) {
-            if (tb.all3) st.eq3[q] = 0;
+            if (tb.all3) eq3[q] = 0;
             if (tb.all4) st.eq4[q] = 0;
         }
     }
 #pragma unroll
     for (int q = 0; q < 4; q++) {
         st.lt[q] = 0;
-        st.und[q] = st.eq3[q] | st.eq4[q];
+        st.und0[q] = eq3[q] | st.eq4[q];
+        st.und[q] = st.und0[q];
     }
+}
+
+// The new words of a quad.  A spin flips iff it is in neither costly class, or its prefix is below the threshold, or it won its
+// tie (quad_ties records a win in lt): own ^ (~und0 | lt), ONE 3-input function per word -- truth table 0x4B for the operand
+// order (own, und0, lt); tests/test_sweep_fold_tables.py derives it.
+constexpr uint32_t BITOP_FLIP = 0x4B;
+__device__ __forceinline__ void quad_new_words(const uint32_t own[4], const QuadState &st, uint32_t neww[4])
+{
+#pragma unroll
+    for (int q = 0; q < 4; q++) neww[q] = __builtin_amdgcn_bitop3_b32(own[q], st.und0[q], st.lt[q], BITOP_FLIP);
 }
 
 // N_PLANES bit-planes of the uniform prefixes compared against the top N_PLANES threshold bits of each spin's
@@ -300,49 +316,92 @@ __device__ __forceinline__ void quad_classes(const uint32_t own[4], const QuadNb
 // sits in the OTHER non-multiplied word, so those two vector multiplies do not depend on it and are shared by
 // all calls of a quad (common subexpressions): 2 + 14 per call instead of 16.
 // The comparison runs from the LEAST significant plane up: with r the random bit and tb the threshold bit of a
-// spin, lt' = (~r & tb) | (~(r ^ tb) & lt) and eq' = eq & ~(r ^ tb) are both 3-input functions -- two
+// spin, lt' = (~r & tb) | (~(r ^ tb) & lt) and eq' = eq & ~(r ^ tb) are both 3-input functions -- at most two
 // v_bitop3_b32 per word and plane whatever the threshold bits (MSB first needs three, and a fourth register
 // copy on the planes whose threshold bits are both 0).  Plane p is Philox call p either way: same decisions.
 // NQ > 1 decides several quads together (the wave-uniform work is then issued once); measured, a two-quad
 // kernel built on it ran exactly as fast as the one-quad kernel (the kernel is bound by VALU cycles, which
 // are the same per quad, and the scalar unit runs beside it), so only NQ = 1 is instantiated.
+// All-zero planes: where the threshold bit of a plane is 0 for both classes, lt &= ~r and und &= ~r.  Two such planes that are
+// neighbours in processing order are applied together, x & ~(ra | rb) -- ONE 3-input function per word and mask for the pair
+// instead of two (truth table 0x10 for the operand order x, ra, rb).  The first plane of a pair is left "open": its words stay
+// in registers and the second plane applies both.  Thresholds are per replica, so the pairing is wave-uniform and is decided on
+// the scalar unit, greedily in processing order; an odd run of zero planes leaves its last plane on the single form.  Plane p
+// remains Philox call p and every call is made either way: same decisions.
+constexpr uint32_t BITOP_ZERO_PAIR = 0x10;
+// one plane with threshold word tb, operand orders (r, tb, lt) and (und, r, tb); the _NOT tables take ~tb in tb's place
+constexpr uint32_t BITOP_LT = 0x8E, BITOP_UND = 0x90, BITOP_LT_NOT = 0x2B, BITOP_UND_NOT = 0x60;
+constexpr uint32_t SEL_ZERO_PAIR = 4, SEL_ZERO_OPEN = 5; // selector values beside the threshold bits (bit of T3) | (bit of T4) << 1
+
+constexpr bool PLANE_MERGE = true; // the default of the MERGE parameters below
+
+// the wave-uniform selector of plane p; `open`: the plane before it in processing order (p + 1) was left open.
+// MERGE = false: every all-zero plane on the single form (the measuring kernel, which has no four registers to hold a plane's
+// words through the next call: it keeps the quad's neighbours for its bond count and spilled with the merge)
+template <bool MERGE>
+__device__ __forceinline__ uint32_t plane_selector(const ThrBits &tb, const int p, const bool open)
+{
+    const uint32_t i = N_PLANES - 1 - p; // planes run from the least significant bit up: step i looks at threshold bit i
+    uint32_t sel = ((tb.hi3 >> i) & 1u) | (((tb.hi4 >> i) & 1u) << 1);
+    if constexpr (MERGE) {
+        if (open) sel = SEL_ZERO_PAIR;
+        else if (sel == 0 && p > 0 && (((tb.hi3 | tb.hi4) >> (i + 1)) & 1u) == 0) sel = SEL_ZERO_OPEN;
+    }
+    // (the scalar unit runs beside the vector ALU; as nested bool tests the compiler parked a bool in a VGPR: a v_cndmask and
+    // a v_cmp per plane)
+    return __builtin_amdgcn_readfirstlane(sel);
+}
+
 // one plane of the comparison for the four words rr[] of a quad (plane p = Philox call p): what quad_planes does per
 // plane, for callers that hold the random words already (kept apart from quad_planes: routing the streaming kernels
-// through it cost lat_sweep_loop_kernel two registers, 66 instead of 64 = a wave per SIMD)
-__device__ __forceinline__ void plane_step(QuadState &st, const uint32_t rr[4], const int p, const ThrBits &tb)
+// through it cost lat_sweep_loop_kernel two registers, 66 instead of 64 = a wave per SIMD).  prev[] = the words of plane p + 1
+// (read only when that plane was left open); returns whether THIS plane is left open.
+__device__ __forceinline__ bool plane_step(QuadState &st, const uint32_t rr[4], const uint32_t prev[4], const int p, const ThrBits &tb,
+                                           const bool open)
 {
     // threshold bit of this plane for class 3 / class 4: wave-uniform, so the per-spin threshold word is
-    // one of {0, eq3, eq4, eq3|eq4} -- scalar branches pick the register
+    // one of {0, eq3, eq4, eq3|eq4} -- scalar branches pick the register (eq3: ~eq4 inside the truth table)
     const auto step = [&](int q, uint32_t tbw) {
-        st.lt[q] = __builtin_amdgcn_bitop3_b32(rr[q], tbw, st.lt[q], 0x8E);   // (~r & tb) | (~(r ^ tb) & lt)
-        st.und[q] = __builtin_amdgcn_bitop3_b32(st.und[q], rr[q], tbw, 0x90); // eq & ~(r ^ tb)
+        st.lt[q] = __builtin_amdgcn_bitop3_b32(rr[q], tbw, st.lt[q], BITOP_LT);    // (~r & tb) | (~(r ^ tb) & lt)
+        st.und[q] = __builtin_amdgcn_bitop3_b32(st.und[q], rr[q], tbw, BITOP_UND); // eq & ~(r ^ tb)
     };
-    // one scalar selector per plane (the scalar unit runs beside the vector ALU; as two nested bool tests the
-    // compiler parked the second bool in a VGPR: a v_cndmask and a v_cmp per plane)
-    const uint32_t sel = __builtin_amdgcn_readfirstlane(((tb.hi3 >> (N_PLANES - 1 - p)) & 1u) | (((tb.hi4 >> (N_PLANES - 1 - p)) & 1u) << 1));
+    const auto step_not = [&](int q, uint32_t ntbw) { // the same with tb = ~ntbw
+        st.lt[q] = __builtin_amdgcn_bitop3_b32(rr[q], ntbw, st.lt[q], BITOP_LT_NOT);
+        st.und[q] = __builtin_amdgcn_bitop3_b32(st.und[q], rr[q], ntbw, BITOP_UND_NOT);
+    };
+    const uint32_t sel = plane_selector<PLANE_MERGE>(tb, p, open);
     if (sel == 3) {
 #pragma unroll
-        for (int q = 0; q < 4; q++) step(q, st.eq3[q] | st.eq4[q]);
+        for (int q = 0; q < 4; q++) step(q, st.und0[q]);
     } else if (sel == 1) {
 #pragma unroll
-        for (int q = 0; q < 4; q++) step(q, st.eq3[q]);
+        for (int q = 0; q < 4; q++) step_not(q, st.eq4[q]);
     } else if (sel == 2) {
 #pragma unroll
         for (int q = 0; q < 4; q++) step(q, st.eq4[q]);
-    } else {
+    } else if (PLANE_MERGE && sel == SEL_ZERO_PAIR) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            st.lt[q] = __builtin_amdgcn_bitop3_b32(st.lt[q], prev[q], rr[q], BITOP_ZERO_PAIR);
+            st.und[q] = __builtin_amdgcn_bitop3_b32(st.und[q], prev[q], rr[q], BITOP_ZERO_PAIR);
+        }
+    } else if (sel == 0) {
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             st.lt[q] &= ~rr[q];
             st.und[q] &= ~rr[q];
         }
     }
+    return PLANE_MERGE && sel == SEL_ZERO_OPEN;
 }
 
-template <int NQ>
+template <int NQ, bool MERGE = PLANE_MERGE>
 __device__ __forceinline__ void quad_planes(QuadState (&st)[NQ], const uint32_t (&Q)[NQ], const uint32_t colour, const uint64_t t,
                                             const uint2 key, const PhiloxVKeys &vk, const ThrBits &tb)
 {
     const uint32_t c0 = uint32_t(t);
+    uint32_t prev[NQ][4]; // the words of the plane before: read only behind a plane that was left open
+    bool open = false;
 #pragma unroll
     for (int p = N_PLANES - 1; p >= 0; p--) {
         uint32_t rr[NQ][4];
@@ -352,30 +411,40 @@ __device__ __forceinline__ void quad_planes(QuadState (&st)[NQ], const uint32_t 
             rr[j][0] = rnd.x; rr[j][1] = rnd.y; rr[j][2] = rnd.z; rr[j][3] = rnd.w;
         }
         // threshold bit of this plane for class 3 / class 4: wave-uniform, so the per-spin threshold word is
-        // one of {0, eq3, eq4, eq3|eq4} -- scalar branches pick the register
+        // one of {0, eq3, eq4, eq3|eq4} -- scalar branches pick the register (eq3: ~eq4 inside the truth table)
         auto step = [&](int j, int q, uint32_t tbw) {
-            st[j].lt[q] = __builtin_amdgcn_bitop3_b32(rr[j][q], tbw, st[j].lt[q], 0x8E);   // (~r & tb) | (~(r ^ tb) & lt)
-            st[j].und[q] = __builtin_amdgcn_bitop3_b32(st[j].und[q], rr[j][q], tbw, 0x90); // eq & ~(r ^ tb)
+            st[j].lt[q] = __builtin_amdgcn_bitop3_b32(rr[j][q], tbw, st[j].lt[q], BITOP_LT);    // (~r & tb) | (~(r ^ tb) & lt)
+            st[j].und[q] = __builtin_amdgcn_bitop3_b32(st[j].und[q], rr[j][q], tbw, BITOP_UND); // eq & ~(r ^ tb)
         };
-        // one scalar selector per plane (the scalar unit runs beside the vector ALU; as two nested bool tests the
-        // compiler parked the second bool in a VGPR: a v_cndmask and a v_cmp per plane)
-        const uint32_t sel = __builtin_amdgcn_readfirstlane(((tb.hi3 >> (N_PLANES - 1 - p)) & 1u) | (((tb.hi4 >> (N_PLANES - 1 - p)) & 1u) << 1));
+        auto step_not = [&](int j, int q, uint32_t ntbw) { // the same with tb = ~ntbw
+            st[j].lt[q] = __builtin_amdgcn_bitop3_b32(rr[j][q], ntbw, st[j].lt[q], BITOP_LT_NOT);
+            st[j].und[q] = __builtin_amdgcn_bitop3_b32(st[j].und[q], rr[j][q], ntbw, BITOP_UND_NOT);
+        };
+        const uint32_t sel = plane_selector<MERGE>(tb, p, open);
         if (sel == 3) {
 #pragma unroll
             for (int j = 0; j < NQ; j++)
 #pragma unroll
-                for (int q = 0; q < 4; q++) step(j, q, st[j].eq3[q] | st[j].eq4[q]);
+                for (int q = 0; q < 4; q++) step(j, q, st[j].und0[q]);
         } else if (sel == 1) {
 #pragma unroll
             for (int j = 0; j < NQ; j++)
 #pragma unroll
-                for (int q = 0; q < 4; q++) step(j, q, st[j].eq3[q]);
+                for (int q = 0; q < 4; q++) step_not(j, q, st[j].eq4[q]);
         } else if (sel == 2) {
 #pragma unroll
             for (int j = 0; j < NQ; j++)
 #pragma unroll
                 for (int q = 0; q < 4; q++) step(j, q, st[j].eq4[q]);
-        } else {
+        } else if (MERGE && p < N_PLANES - 1 && sel == SEL_ZERO_PAIR) { // (the first plane has none before it: prev[] is not read there)
+#pragma unroll
+            for (int j = 0; j < NQ; j++)
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    st[j].lt[q] = __builtin_amdgcn_bitop3_b32(st[j].lt[q], prev[j][q], rr[j][q], BITOP_ZERO_PAIR);
+                    st[j].und[q] = __builtin_amdgcn_bitop3_b32(st[j].und[q], prev[j][q], rr[j][q], BITOP_ZERO_PAIR);
+                }
+        } else if (sel == 0) {
 #pragma unroll
             for (int j = 0; j < NQ; j++)
 #pragma unroll
@@ -383,7 +452,20 @@ __device__ __forceinline__ void quad_planes(QuadState (&st)[NQ], const uint32_t 
                     st[j].lt[q] &= ~rr[j][q];
                     st[j].und[q] &= ~rr[j][q];
                 }
+        } else if (MERGE) {
+            // left open.  Nothing is issued, but the masks count as rewritten in place, as on every other path: with a path that
+            // leaves them alone the compiler copied all eight to fresh registers in front of EVERY plane's branches
+            // (+32 vector instructions per quad on the device's counters)
+#pragma unroll
+            for (int j = 0; j < NQ; j++)
+#pragma unroll
+                for (int q = 0; q < 4; q++) asm volatile("" : "+v"(st[j].lt[q]), "+v"(st[j].und[q]));
         }
+        open = MERGE && sel == SEL_ZERO_OPEN;
+#pragma unroll
+        for (int j = 0; j < NQ; j++)
+#pragma unroll
+            for (int q = 0; q < 4; q++) prev[j][q] = rr[j][q];
     }
 }
 
@@ -408,14 +490,13 @@ __device__ __forceinline__ void quad_random(QuadRandom &R, const uint32_t Q, con
     R.tie = philox4x32_10(make_uint4(c0, Q, DOM_LAT_SWEEP, ctr2(t, colour, N_PLANES)), key, vk);
 }
 
-// residual stage: spins whose prefix equals the threshold's top bits (ties) draw 32 more bits; acc = flips
-__device__ __forceinline__ void quad_ties(const QuadState &st, const uint32_t Q, const uint32_t colour, const uint64_t t,
-                                          const uint2 key, const PhiloxVKeys &vk, const ThrBits &tb, uint32_t acc[4],
+// residual stage: spins whose prefix equals the threshold's top bits (ties) draw 32 more bits; a tie that is won is recorded
+// in st.lt ("below the threshold"), which quad_new_words folds into the new words
+__device__ __forceinline__ void quad_ties(QuadState &st, const uint32_t Q, const uint32_t colour, const uint64_t t,
+                                          const uint2 key, const PhiloxVKeys &vk, const ThrBits &tb,
                                           const uint4 *first_call = nullptr)
 {
     const uint32_t c0 = uint32_t(t), c1 = Q;
-#pragma unroll
-    for (int q = 0; q < 4; q++) acc[q] = __builtin_amdgcn_bitop3_b32(st.eq3[q], st.eq4[q], st.lt[q], 0xAB); // ~(eq3|eq4) | lt
 #ifdef ISINGMC_TIMING_ONLY_NO_TIES // diagnostic build: what the tie stage costs (results are wrong without it)
     if (false) {
 #else
@@ -429,7 +510,7 @@ __device__ __forceinline__ void quad_ties(const QuadState &st, const uint32_t Q,
         {
             const uint32_t rr4[4] = {rnd.x, rnd.y, rnd.z, rnd.w};
 #pragma unroll
-            for (int q = 0; q < 4; q++) acc[q] |= st.und[q] & (0u - uint32_t(rr4[q] < ((st.und[q] & st.eq4[q]) ? tb.lo4 : tb.lo3)));
+            for (int q = 0; q < 4; q++) st.lt[q] |= st.und[q] & (0u - uint32_t(rr4[q] < ((st.und[q] & st.eq4[q]) ? tb.lo4 : tb.lo3)));
             return;
         }
 #endif
@@ -451,7 +532,7 @@ __device__ __forceinline__ void quad_ties(const QuadState &st, const uint32_t Q,
                     const uint32_t bit = m & (0u - m);
                     m ^= bit;
                     const uint32_t lo = (bit & st.eq4[q]) ? lo4v : lo3v;
-                    if (r0 < lo) acc[q] |= bit;
+                    if (r0 < lo) st.lt[q] |= bit;
                     r0 = r1; r1 = r2; r2 = r3;
                 }
             }
@@ -467,7 +548,7 @@ __device__ __forceinline__ void quad_ties(const QuadState &st, const uint32_t Q,
                     if (nres != 0 && (nres & 3u) == 0)
                         w = philox4x32_10(make_uint4(c0, c1, DOM_LAT_SWEEP, ctr2(t, colour, N_PLANES + (nres >> 2))), key, vk);
                     const uint32_t lo = ((st.eq4[q] >> b) & 1u) ? tb.lo4 : tb.lo3;
-                    if (sel4(w, nres & 3u) < lo) acc[q] |= 1u << b;
+                    if (sel4(w, nres & 3u) < lo) st.lt[q] |= 1u << b;
                     nres++;
                 }
             }
@@ -475,19 +556,20 @@ __device__ __forceinline__ void quad_ties(const QuadState &st, const uint32_t Q,
     }
 }
 
-// The 128 flip decisions of quad Q from its loaded words: acc[q] bit b = 1 where the spin flips.
-template <bool PMJ>
+// The 128 flip decisions of quad Q from its loaded words, applied: neww[q] = own[q] with the bits of the flipping spins inverted.
+template <bool PMJ, bool MERGE = PLANE_MERGE>
 __device__ __forceinline__ void quad_flips(const uint32_t own[4], const QuadNbr &n, const uint32_t colour, const uint64_t t,
                                            const uint2 key, const PhiloxVKeys &vk,
                                            const LatThr thr, const QuadSigns &js, const uint32_t jneg_uniform,
-                                           const uint32_t Q, uint32_t acc[4])
+                                           const uint32_t Q, uint32_t neww[4])
 {
     const ThrBits tb = thr_bits(thr);
     QuadState st[1];
     const uint32_t Qs[1] = {Q};
     quad_classes<PMJ>(own, n, tb, js, jneg_uniform, st[0]);
-    quad_planes<1>(st, Qs, colour, t, key, vk, tb);
-    quad_ties(st[0], Q, colour, t, key, vk, tb, acc);
+    quad_planes<1, MERGE>(st, Qs, colour, t, key, vk, tb);
+    quad_ties(st[0], Q, colour, t, key, vk, tb);
+    quad_new_words(own, st[0], neww);
 }
 
 // the same decisions from random words drawn earlier (quad_random)
@@ -495,14 +577,16 @@ template <bool PMJ>
 __device__ __forceinline__ void quad_flips_pre(const uint32_t own[4], const QuadNbr &n, const uint32_t colour, const uint64_t t,
                                                const uint2 key, const PhiloxVKeys &vk,
                                                const LatThr thr, const QuadSigns &js, const uint32_t jneg_uniform, const uint32_t Q,
-                                               const QuadRandom &R, uint32_t acc[4])
+                                               const QuadRandom &R, uint32_t neww[4])
 {
     const ThrBits tb = thr_bits(thr);
     QuadState st;
     quad_classes<PMJ>(own, n, tb, js, jneg_uniform, st);
+    bool open = false;
 #pragma unroll
-    for (int p = N_PLANES - 1; p >= 0; p--) plane_step(st, R.rr[p], p, tb);
-    quad_ties(st, Q, colour, t, key, vk, tb, acc, &R.tie);
+    for (int p = N_PLANES - 1; p >= 0; p--) open = plane_step(st, R.rr[p], R.rr[p < N_PLANES - 1 ? p + 1 : p], p, tb, open);
+    quad_ties(st, Q, colour, t, key, vk, tb, &R.tie);
+    quad_new_words(own, st, neww);
 }
 
 // One Metropolis update of the 128 spins of a quad (thread index gid -> quad via thread_to_quad) of the
@@ -616,45 +700,44 @@ __device__ __forceinline__ void update_quad(const Mem &mem, const LatGeom &g, co
 {
     if constexpr (VEC && UNI && std::is_same<Mem, BufPlanes>::value) {
         typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-        uint32_t Q, vQ, own[4], acc[4];
+        uint32_t Q, vQ, own[4], neww[4];
         QuadNbr n;
         QuadSigns js;
         load_quad_uni(mem, g, colour, gid, Q, vQ, own, n);
         load_signs<PMJ>(jn, g, Q, js);
-        quad_flips<PMJ>(own, n, colour, t, key, vk, thr, js, jneg_uniform, Q, acc);
+        quad_flips<PMJ, PLANE_MERGE && !MEASURE>(own, n, colour, t, key, vk, thr, js, jneg_uniform, Q, neww);
         if constexpr (MEASURE) {
             // NOT stored here: the vector store (buffer_store_dwordx4 with a register offset) reads its four data registers
             // some cycles after it issues, the compiler's hazard model inserts no wait state for that form, and the counting
             // below would overwrite them at once -- on a loaded chip a word of the quad then arrived in memory as a bit
             // count (wrong spins from ~1500 workgroups per launch on; round 3).  The kernel stores as its last instruction.
 #pragma unroll
-            for (int q = 0; q < 4; q++) { pending->w[q] = own[q] ^ acc[q]; pending->widx[q] = 4 * Q + q; }
+            for (int q = 0; q < 4; q++) { pending->w[q] = neww[q]; pending->widx[q] = 4 * Q + q; }
             quad_measure<PMJ>(pending->w, n, js, jneg_uniform, *sat, *up);
         } else {
-            __builtin_amdgcn_raw_buffer_store_b128(u32x4{own[0] ^ acc[0], own[1] ^ acc[1], own[2] ^ acc[2], own[3] ^ acc[3]}, mem.rsrc,
-                                                   vQ, mem.own_off, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(u32x4{neww[0], neww[1], neww[2], neww[3]}, mem.rsrc, vQ, mem.own_off, 0);
         }
         return;
     }
     uint32_t Q, qy, qxw;
     thread_to_quad<UNI>(g, gid, Q, qy, qxw);
 
-    uint32_t own[4], widx[4], acc[4];
+    uint32_t own[4], widx[4], neww[4];
     QuadNbr n;
     QuadSigns js;
     load_signs<PMJ>(jn, g, Q, js);
     load_quad<VEC, UNI>(mem, g, colour, Q, qy, qxw, own, n, widx);
-    quad_flips<PMJ>(own, n, colour, t, key, vk, thr, js, jneg_uniform, Q, acc);
+    quad_flips<PMJ, PLANE_MERGE && !MEASURE>(own, n, colour, t, key, vk, thr, js, jneg_uniform, Q, neww);
 
     if constexpr (MEASURE) { // stored by the kernel at its end, as above
 #pragma unroll
-        for (int q = 0; q < 4; q++) { pending->w[q] = own[q] ^ acc[q]; pending->widx[q] = widx[q]; }
+        for (int q = 0; q < 4; q++) { pending->w[q] = neww[q]; pending->widx[q] = widx[q]; }
         quad_measure<PMJ>(pending->w, n, js, jneg_uniform, *sat, *up);
     } else if constexpr (VEC) {
-        mem.store4(widx[0], make_uint4(own[0] ^ acc[0], own[1] ^ acc[1], own[2] ^ acc[2], own[3] ^ acc[3]));
+        mem.store4(widx[0], make_uint4(neww[0], neww[1], neww[2], neww[3]));
     } else {
 #pragma unroll
-        for (int q = 0; q < 4; q++) mem.store1(widx[q], own[q] ^ acc[q]);
+        for (int q = 0; q < 4; q++) mem.store1(widx[q], neww[q]);
     }
 }
 
@@ -796,7 +879,7 @@ __global__ __launch_bounds__(256) void lat_sweep_loop_kernel(
         const u32x4 u4 = __builtin_amdgcn_raw_buffer_load_b128(mem.rsrc, vU, s_ud, 0);
         const u32x4 d4 = __builtin_amdgcn_raw_buffer_load_b128(mem.rsrc, vD, s_ud, 0);
         const uint32_t sw = __builtin_amdgcn_raw_buffer_load_b32(mem.rsrc, vS, mem.oth_off + walked, 0);
-        uint32_t own[4] = {o4.x, o4.y, o4.z, o4.w}, acc[4];
+        uint32_t own[4] = {o4.x, o4.y, o4.z, o4.w}, neww[4];
         QuadNbr n;
         n.ce[0] = c4.x; n.ce[1] = c4.y; n.ce[2] = c4.z; n.ce[3] = c4.w;
         n.up[0] = u4.x; n.up[1] = u4.y; n.up[2] = u4.z; n.up[3] = u4.w;
@@ -809,9 +892,9 @@ __global__ __launch_bounds__(256) void lat_sweep_loop_kernel(
         const uint32_t Qs[1] = {Q};
         quad_classes<PMJ>(own, n, tb, js, jneg_uniform, st[0]);
         quad_planes<1>(st, Qs, colour, t, key, vk, tb);
-        quad_ties(st[0], Q, colour, t, key, vk, tb, acc);
-        __builtin_amdgcn_raw_buffer_store_b128(u32x4{own[0] ^ acc[0], own[1] ^ acc[1], own[2] ^ acc[2], own[3] ^ acc[3]}, mem.rsrc, vQ,
-                                               mem.own_off + walked, 0);
+        quad_ties(st[0], Q, colour, t, key, vk, tb);
+        quad_new_words(own, st[0], neww);
+        __builtin_amdgcn_raw_buffer_store_b128(u32x4{neww[0], neww[1], neww[2], neww[3]}, mem.rsrc, vQ, mem.own_off + walked, 0);
         Q += stride;
         ys += row_step;
         walked += byte_step;

@@ -51,18 +51,18 @@ __global__ __launch_bounds__(1024) void lat_resident_spread_kernel(
                 }
                 R.tie = s_rand[8 * tid + N_PLANES];
                 const PtrPlanes mem{planes + colour * g.wpp, planes + (1 - colour) * g.wpp};
-                uint32_t Q, qy, qxw, own[4], widx[4], acc[4];
+                uint32_t Q, qy, qxw, own[4], widx[4], neww[4];
                 thread_to_quad<false>(g, tid, Q, qy, qxw);
                 QuadNbr n;
                 QuadSigns js;
                 load_signs<PMJ>(PMJ ? jneg + size_t(colour) * 4 * g.wpp : nullptr, g, Q, js);
                 load_quad<VEC, false>(mem, g, colour, Q, qy, qxw, own, n, widx);
-                quad_flips_pre<PMJ>(own, n, colour, t, key, vk, thr, js, jneg_uniform, Q, R, acc);
+                quad_flips_pre<PMJ>(own, n, colour, t, key, vk, thr, js, jneg_uniform, Q, R, neww);
                 if constexpr (VEC) {
-                    mem.store4(widx[0], make_uint4(own[0] ^ acc[0], own[1] ^ acc[1], own[2] ^ acc[2], own[3] ^ acc[3]));
+                    mem.store4(widx[0], make_uint4(neww[0], neww[1], neww[2], neww[3]));
                 } else {
 #pragma unroll
-                    for (int q = 0; q < 4; q++) mem.store1(widx[q], own[q] ^ acc[q]);
+                    for (int q = 0; q < 4; q++) mem.store1(widx[q], neww[q]);
                 }
             }
             __syncthreads();

@@ -103,19 +103,17 @@ __device__ __forceinline__ void strip_update_quad(uint32_t *lds, const uint32_t 
     const uint32_t sx = odd ? (xw + 4 == wpr ? 0 : xw + 4) : (xw == 0 ? wpr : xw) - 1;
     QuadNbr n;
     n.si[0] = othp[yl * wpr + sx];
-    uint32_t own[4] = {o4.x, o4.y, o4.z, o4.w}, acc[4];
+    const uint32_t own[4] = {o4.x, o4.y, o4.z, o4.w};
     n.ce[0] = c4.x; n.ce[1] = c4.y; n.ce[2] = c4.z; n.ce[3] = c4.w;
     n.up[0] = u4.x; n.up[1] = u4.y; n.up[2] = u4.z; n.up[3] = u4.w;
     n.dn[0] = d4.x; n.dn[1] = d4.y; n.dn[2] = d4.z; n.dn[3] = d4.w;
     side_words(n, odd);
 #ifdef ISINGMC_STRIP_NO_PRECOMPUTE // A/B build: the random words drawn after the wait, as in the streaming kernels
     (void)R;
-    quad_flips<PMJ>(own, n, colour, t, key, vk, thr, js, jneg_uniform, Q, acc);
+    quad_flips<PMJ>(own, n, colour, t, key, vk, thr, js, jneg_uniform, Q, new_words);
 #else
-    quad_flips_pre<PMJ>(own, n, colour, t, key, vk, thr, js, jneg_uniform, Q, R, acc);
+    quad_flips_pre<PMJ>(own, n, colour, t, key, vk, thr, js, jneg_uniform, Q, R, new_words);
 #endif
-#pragma unroll
-    for (int q = 0; q < 4; q++) new_words[q] = own[q] ^ acc[q];
     *reinterpret_cast<uint4 *>(ownp + w0) = make_uint4(new_words[0], new_words[1], new_words[2], new_words[3]);
     if (measure) quad_measure<PMJ>(new_words, n, js, jneg_uniform, sat, up); // wave-uniform
 }
