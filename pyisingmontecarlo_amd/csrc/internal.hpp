@@ -110,6 +110,7 @@ struct Options {
     int streams = 0, pk_streams = 0;                                            // replica lanes: 0 = the measured rule
     int sweep_iters = 0, debug_sweep_lds = 0;
     int resident_spread = 1, resident_lpq = 0, gen_stage = -1;
+    int gen_rb = 0; // replicas per thread of the streaming CSR kernel: 0 = the rule of launch_gen_timestep, 1 / 2 / 4 / 8 forces
     int sample_slab_bytes = 64 << 20, pt_in_kernel = 1, real_target_wgs = 3072;
     int cluster_workspace_bytes = 1 << 30; // labels, cluster sizes and bond planes of one batch of replicas
 
@@ -133,6 +134,7 @@ struct Options {
         o.resident_spread = env_int("ISINGMC_RESIDENT_SPREAD", 1);
         o.resident_lpq = env_int("ISINGMC_RESIDENT_LPQ", 0);
         o.gen_stage = env_int("ISINGMC_GEN_STAGE", -1);
+        o.gen_rb = env_int("ISINGMC_GEN_RB_FORCE", 0);
         o.sample_slab_bytes = std::max(1, env_int("ISINGMC_SAMPLE_SLAB_BYTES", 64 << 20));
         o.pt_in_kernel = env_int("ISINGMC_PT_IN_KERNEL", 1);
         o.real_target_wgs = std::max(256, env_int("ISINGMC_REAL_TARGET_WGS", 3072));
@@ -149,7 +151,7 @@ struct Options {
             {"disable_packed_uniform", &disable_packed_uniform}, {"disable_resident", &disable_resident}, {"strip", &strip},
             {"strip_nw", &strip_nw}, {"strip_max_wg", &strip_max_wg}, {"strip_test_fail_once", &strip_test_fail_once},
             {"streams", &streams}, {"pk_streams", &pk_streams}, {"sweep_iters", &sweep_iters}, {"debug_sweep_lds", &debug_sweep_lds},
-            {"resident_spread", &resident_spread}, {"resident_lpq", &resident_lpq}, {"gen_stage", &gen_stage},
+            {"resident_spread", &resident_spread}, {"resident_lpq", &resident_lpq}, {"gen_stage", &gen_stage}, {"gen_rb", &gen_rb},
             {"sample_slab_bytes", &sample_slab_bytes}, {"pt_in_kernel", &pt_in_kernel}, {"real_target_wgs", &real_target_wgs},
             {"cluster_workspace_bytes", &cluster_workspace_bytes}};
         for (const auto &e : table)

@@ -802,6 +802,8 @@ static void launch_gen_timestep(isingmc_states *s, double beta)
         size_t rb = GEN_RB;
         const size_t blocks = (e - b + 255) / 256;
         while (rb > 1 && (s->R < rb || blocks * ((s->R + rb - 1) / rb) < 2048)) rb /= 2;
+        // ISINGMC_GEN_RB_FORCE=1 / 2 / 4 / 8 (option gen_rb) forces, up to the compiled GEN_RB (tests, A/B runs): same results
+        if (const int f = s->opt.gen_rb; f == 1 || f == 2 || f == 4 || f == 8) rb = std::min<size_t>(size_t(f), GEN_RB);
         const auto launch = [&](auto wt) {
             using WT = decltype(wt);
             if (rb >= 8) launch_gen_class<WT, 8>(s, b, e, beta);

@@ -277,7 +277,8 @@ def test_set_option_names(capi, exact):
     g = capi.Graph(*exact.square_lattice_edges(64, 8, -1.0))
     st = capi.States(g, TC.seeds_for(LATS[0], 1))
     for name in ("disable_packed_uniform", "DISABLE_PACKED_UNIFORM", "ISINGMC_DISABLE_PACKED_UNIFORM", "isingmc_disable_resident",
-                 "strip", "sweep_iters", "resident_spread", "streams", "pk_streams", "cluster_workspace_bytes"):
+                 "strip", "sweep_iters", "resident_spread", "streams", "pk_streams", "cluster_workspace_bytes", "gen_stage", "gen_rb",
+                 "GEN_RB"):
         st.set_option(name, 1)
     for name in ("force_real", "disable_real", "force_packed", "disable_packed", "ISINGMC_DISABLE_PACKED", "Force_Packed"):
         with pytest.raises(ValueError, match="fixed when it is created"):
