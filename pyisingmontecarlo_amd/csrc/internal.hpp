@@ -112,6 +112,7 @@ struct Options {
     int resident_spread = 1, resident_lpq = 0, gen_stage = -1;
     int gen_rb = 0; // replicas per thread of the streaming CSR kernel: 0 = the rule of launch_gen_timestep, 1 / 2 / 4 / 8 forces
     int sample_slab_bytes = 64 << 20, pt_in_kernel = 1, real_target_wgs = 3072;
+    int real_measure_wgs = 0; // workgroups the real-coupling measurement shares among its groups: 0 = the occupancy figure (measure_enqueue)
     int cluster_workspace_bytes = 1 << 30; // labels, cluster sizes and bond planes of one batch of replicas
 
     static Options from_env()
@@ -138,6 +139,7 @@ struct Options {
         o.sample_slab_bytes = std::max(1, env_int("ISINGMC_SAMPLE_SLAB_BYTES", 64 << 20));
         o.pt_in_kernel = env_int("ISINGMC_PT_IN_KERNEL", 1);
         o.real_target_wgs = std::max(256, env_int("ISINGMC_REAL_TARGET_WGS", 3072));
+        o.real_measure_wgs = env_int("ISINGMC_REAL_MEASURE_WGS", 0);
         o.cluster_workspace_bytes = std::max(1, env_int("ISINGMC_CLUSTER_WORKSPACE_BYTES", 1 << 30));
         return o;
     }
@@ -153,6 +155,7 @@ struct Options {
             {"streams", &streams}, {"pk_streams", &pk_streams}, {"sweep_iters", &sweep_iters}, {"debug_sweep_lds", &debug_sweep_lds},
             {"resident_spread", &resident_spread}, {"resident_lpq", &resident_lpq}, {"gen_stage", &gen_stage}, {"gen_rb", &gen_rb},
             {"sample_slab_bytes", &sample_slab_bytes}, {"pt_in_kernel", &pt_in_kernel}, {"real_target_wgs", &real_target_wgs},
+            {"real_measure_wgs", &real_measure_wgs},
             {"cluster_workspace_bytes", &cluster_workspace_bytes}};
         for (const auto &e : table)
             if (n == e.first) { *e.second = int(value); return true; }

@@ -837,7 +837,8 @@ int measure_enqueue(isingmc_states *s, unsigned long long *counts_slot, double *
                 if (slot == 0) slot = std::max(1, rj_measure_blocks_per_cu(g->rj.slots, bip, want_up));
                 pc = slot;
             }
-            const size_t resident = size_t(pc) * size_t(std::max(g->n_cu, 1));
+            // ISINGMC_REAL_MEASURE_WGS=<n> (option real_measure_wgs) replaces the figure (tests, A/B runs): exact integer sums, same results
+            const size_t resident = s->opt.real_measure_wgs > 0 ? size_t(s->opt.real_measure_wgs) : size_t(pc) * size_t(std::max(g->n_cu, 1));
             // two colour classes: the bonds from class 0 alone; class 1 is visited only for its bias terms or the up spins
             const uint32_t class0_end = bip ? uint32_t(g->class_base[1]) : 0u;
             const uint32_t scan_end = bip && !g->has_bias && !want_up ? class0_end : g->pk.n_pos;

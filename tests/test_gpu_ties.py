@@ -278,7 +278,7 @@ def test_set_option_names(capi, exact):
     st = capi.States(g, TC.seeds_for(LATS[0], 1))
     for name in ("disable_packed_uniform", "DISABLE_PACKED_UNIFORM", "ISINGMC_DISABLE_PACKED_UNIFORM", "isingmc_disable_resident",
                  "strip", "sweep_iters", "resident_spread", "streams", "pk_streams", "cluster_workspace_bytes", "gen_stage", "gen_rb",
-                 "GEN_RB"):
+                 "GEN_RB", "real_measure_wgs", "ISINGMC_REAL_MEASURE_WGS"):
         st.set_option(name, 1)
     for name in ("force_real", "disable_real", "force_packed", "disable_packed", "ISINGMC_DISABLE_PACKED", "Force_Packed"):
         with pytest.raises(ValueError, match="fixed when it is created"):
