@@ -8,23 +8,10 @@
 // the flip mask of a wave is its __ballot, written by lane 0 -- no atomics.
 #pragma once
 #include "det_exp.hpp"
+#include "general_types.hpp"
 #include "philox.hpp"
 
 namespace isingmc {
-
-constexpr uint32_t PAD_SITE = 0xFFFFFFFFu;
-
-struct GenGraphDev {
-    const uint32_t *rowptr;  // n_pos + 1
-    const uint32_t *nbr;     // neighbour POSITIONS
-    const void *w;           // couplings, float (when lossless) or double
-    const double *bias;      // per position, or nullptr (all zero)
-    const uint32_t *site;    // original site id per position, PAD_SITE on padding
-    const uint32_t *class_base; // n_colours + 1 positions (device copy of the colour-class boundaries)
-    uint32_t n_colours;
-    uint32_t n_pos;          // multiple of 64
-    uint32_t n_words;        // n_pos / 32
-};
 
 constexpr int GEN_ROW_BATCH = 8; // directed edges of a CSR row fetched together
 
@@ -130,10 +117,8 @@ __global__ __launch_bounds__(256) void gen_sweep_kernel(
 }
 
 // random start: packed word w = Philox(key, (0, w>>2, 0, "GENI"))[w&3], padding bits cleared
-__attribute__((unused)) static __global__ __launch_bounds__(256) void gen_init_kernel(uint32_t *__restrict__ state,
-                                                       const GenGraphDev G,
-                                                       const uint2 *__restrict__ keys,
-                                                       const uint32_t first_replica)
+__global__ __launch_bounds__(256) void gen_init_kernel(uint32_t *__restrict__ state, const GenGraphDev G,
+                                                       const uint2 *__restrict__ keys, const uint32_t first_replica)
 {
     const uint32_t r = first_replica + blockIdx.y;
     const uint32_t w = blockIdx.x * 256 + threadIdx.x;
@@ -181,11 +166,9 @@ __global__ __launch_bounds__(256) void gen_measure_kernel(const uint32_t *__rest
 }
 
 // fixed-order tree sum of one replica's partials: out_e[r], out_m[r]
-__attribute__((unused)) static __global__ __launch_bounds__(256) void gen_reduce_kernel(const double *__restrict__ partial_e,
-                                                         const long long *__restrict__ partial_m,
-                                                         const uint32_t n_partials,
-                                                         double *__restrict__ out_e,
-                                                         long long *__restrict__ out_m)
+__global__ __launch_bounds__(256) void gen_reduce_kernel(const double *__restrict__ partial_e,
+                                                         const long long *__restrict__ partial_m, const uint32_t n_partials,
+                                                         double *__restrict__ out_e, long long *__restrict__ out_m)
 {
     __shared__ double se[256];
     __shared__ long long sm[256];
@@ -213,22 +196,6 @@ __attribute__((unused)) static __global__ __launch_bounds__(256) void gen_reduce
 // arithmetic and Philox counters as gen_sweep_kernel => same configurations.
 // energies_out (optional): E after every timestep, [replica][timesteps], reduced in a fixed order.
 // ------------------------------------------------------------------------------------------------
-constexpr uint32_t GEN_RESIDENT_MAX_BYTES = 32 * 1024;
-
-// LDS words the staged variant needs behind the state words (see gen_resident_kernel STAGE); edges2 = directed edges
-// stage: 1 = everything, 2 = the topology only (row pointers, site ids, neighbour positions: the links of the dependent chain;
-// couplings and biases stay in global memory, their addresses do not depend on loaded data)
-__host__ __device__ inline uint32_t gen_stage_words(uint32_t n_pos, uint32_t edges2, bool has_bias, uint32_t w_bytes, int stage)
-{
-    uint32_t off = ((n_pos / 32) + 1u) & ~1u;             // state words, then 8-byte alignment
-    if (stage == 1) {
-        if (has_bias) off += 2 * n_pos;                    // f64 bias per position
-        off += edges2 * (w_bytes / 4);                     // couplings (f32 or f64)
-        off = (off + 1u) & ~1u;
-    }
-    return off + (n_pos + 1) + n_pos + edges2;             // rowptr, site, nbr
-}
-
 // STAGE: the graph itself (row pointers, neighbour positions, couplings, biases, site ids) is copied into LDS once per launch.
 // A timestep of a small graph is a chain of DEPENDENT loads per colour class -- site -> row pointer -> neighbour -> spin word --
 // and from global memory each link costs an L2 round trip although nothing but the spins ever changes: 2.2 us per timestep for
@@ -329,59 +296,6 @@ __global__ __launch_bounds__(1024) void gen_resident_kernel(
         }
     }
     for (uint32_t i = tid; i < G.n_words; i += nthreads) mine[i] = st[i];
-}
-
-// ------------------------------------------------------------------------------------------------
-// Parallel-tempering exchange round ON THE STREAM (host twin: pt_swap_round in
-// host_logic.cpp -- same Philox counters, same det_exp, hence the same decisions).  One workgroup:
-// the pairs (i, i+1) of the round's parity are disjoint, so one thread per pair swaps perm entries in
-// place; then every rung relabels its slot's beta / thresholds if the slot is local.  No host sync.
-// ------------------------------------------------------------------------------------------------
-struct PtDev {
-    const double *ladder;        // beta per rung
-    const uint64_t *ladder_thr;  // per rung, host-computed: lattice {T3, T4} (exp of glibc); real-coupling path: one word = its RjBeta; else nullptr
-    uint32_t thr_words;          // 64-bit words of ladder_thr per rung (2 / 1)
-    uint32_t *perm;              // rung -> global slot
-    const double *slot_energy;   // all slots (gathered)
-    unsigned long long *counters; // [0] = round, [1] = total swaps
-    uint32_t n_rungs, slot_offset, n_local;
-    uint32_t seed_lo, seed_hi;
-};
-
-__attribute__((unused)) static __global__ __launch_bounds__(1024) void pt_swap_kernel(const PtDev P, uint64_t *__restrict__ thr_local /*thr_words words per local slot*/,
-                                                       double *__restrict__ beta_local, const uint32_t apply_only)
-{
-    const unsigned long long round = P.counters[0];
-    __syncthreads(); // everyone has read the round before thread 0 bumps it
-    unsigned swaps = 0;
-    for (uint32_t i = uint32_t(round & 1) + 2 * threadIdx.x; !apply_only && i + 1 < P.n_rungs; i += 2 * blockDim.x) {
-        const uint32_t sa = P.perm[i], sb = P.perm[i + 1];
-        const double d = (P.ladder[i] - P.ladder[i + 1]) * (P.slot_energy[sa] - P.slot_energy[sb]);
-        bool accept = d >= 0.0;
-        if (!accept) {
-            const uint4 rnd = philox4x32_10(make_uint4(i, uint32_t(round), uint32_t(round >> 32), 0x50545357u),
-                                            make_uint2(P.seed_lo, P.seed_hi));
-            const uint64_t x = (uint64_t(rnd.y) << 32) | rnd.x;
-            accept = double(x >> 11) * (1.0 / 9007199254740992.0) < det_exp(d);
-        }
-        if (accept) {
-            P.perm[i] = sb;
-            P.perm[i + 1] = sa;
-            swaps++;
-        }
-    }
-    if (swaps) atomicAdd(&P.counters[1], (unsigned long long)swaps);
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < P.n_rungs; i += blockDim.x) {
-        const uint32_t slot = P.perm[i];
-        if (slot >= P.slot_offset && slot < P.slot_offset + P.n_local) {
-            const uint32_t r = slot - P.slot_offset;
-            if (beta_local) beta_local[r] = P.ladder[i];
-            if (P.ladder_thr)
-                for (uint32_t k = 0; k < P.thr_words; k++) thr_local[size_t(P.thr_words) * r + k] = P.ladder_thr[size_t(P.thr_words) * i + k];
-        }
-    }
-    if (threadIdx.x == 0 && !apply_only) P.counters[0] = round + 1;
 }
 
 } // namespace isingmc

@@ -485,7 +485,7 @@ ClassSegments class_segments(const uint32_t *site, size_t n_pos, const uint32_t 
         const uint32_t *c = cls + t * nvars;
         uint64_t *size = S.sizes.data() + t * n_classes;
         for (size_t p = 0; p < n_pos; p++)
-            if (site[p] != CLASS_PAD_SITE && c[site[p]] != CLASS_NONE) size[c[site[p]]]++;
+            if (site[p] != PAD_SITE && c[site[p]] != CLASS_NONE) size[c[site[p]]]++;
         // counting sort of the positions by class: ascending position inside a class
         const size_t base = S.order.size();
         start[0] = uint32_t(base);
@@ -495,7 +495,7 @@ ClassSegments class_segments(const uint32_t *site, size_t n_pos, const uint32_t 
             for (uint32_t first = start[k]; first < start[k + 1]; first += CLASS_SEGMENT_MAX)
                 S.seg.insert(S.seg.end(), {uint32_t(t), uint32_t(k), first, std::min(CLASS_SEGMENT_MAX, start[k + 1] - first)});
         for (size_t p = 0; p < n_pos; p++)
-            if (site[p] != CLASS_PAD_SITE && c[site[p]] != CLASS_NONE) S.order[start[c[site[p]]]++] = uint32_t(p);
+            if (site[p] != PAD_SITE && c[site[p]] != CLASS_NONE) S.order[start[c[site[p]]]++] = uint32_t(p);
     }
     return S;
 }

@@ -6,6 +6,8 @@
 #include <string>
 #include <vector>
 
+#include "general_types.hpp"
+
 namespace isingmc {
 
 // xoshiro256++ seeded by SplitMix64: rand 0.8 SmallRng::seed_from_u64 on 64-bit targets
@@ -98,11 +100,11 @@ void rj_log_table(uint32_t *out);
 __attribute__((visibility("hidden"))) size_t nonlocal_batch(size_t items, size_t words_per_item, size_t workspace_bytes);
 
 // Site classes of the replica-packed families (device reader: overlap_class_kernels.hip).  site[n_pos]: the site of
-// every position, CLASS_PAD_SITE on padding; cls[n_tables][nvars]: a class below n_classes or CLASS_NONE per site.  Per table the
+// every position, PAD_SITE on padding; cls[n_tables][nvars]: a class below n_classes or CLASS_NONE per site.  Per table the
 // classed positions are sorted by class (ascending position inside a class) into `order`, and the sorted list is cut into
 // segments {table, class, first, count} -- `first` indexes `order`, count <= CLASS_SEGMENT_MAX, a segment never mixes classes or
 // tables; an empty class has no segment.  sizes[n_tables][n_classes]: sites per class.  The caller has checked the class values.
-constexpr uint32_t CLASS_NONE = 0xFFFFFFFFu, CLASS_PAD_SITE = 0xFFFFFFFFu;
+constexpr uint32_t CLASS_NONE = 0xFFFFFFFFu;
 constexpr uint32_t CLASS_SEGMENT_MAX = 1024; // positions one workgroup of ovl_pk_class_kernel counts
 struct ClassSegments {
     std::vector<uint32_t> order;

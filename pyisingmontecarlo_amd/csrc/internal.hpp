@@ -1,7 +1,7 @@
 // Internal declarations shared by the host translation units of libisingmc.so (not installed, not part of the C ABI):
 //   core.hip       error state, device-block / pinned-block / stream / event caches, environment helpers
 //   graph.hip      edge-list checks, host-only C ABI helpers, lattice / general / packed / real-coupling graph construction
-//   isingmc.hip    replica containers, every sweep / measurement launch, the persistent strip kernel's host side
+//   isingmc.hip    replica containers, the policy of every sweep / measurement launch, the persistent strip kernel's host side
 //   nonlocal.hip   host side of the non-local moves: Swendsen-Wang steps, isoenergetic cluster moves inside and between containers
 //   overlaps.hip   spin and link overlaps between replica pairs (isingmc_overlaps), and the spin overlap by site class
 //                  (isingmc_site_classes_*, isingmc_overlaps_by_class)
@@ -10,6 +10,8 @@
 //   tempering.hip  on-stream parallel tempering, the in-process ladder group (RCCL through dlopen)
 //   population.hip population annealing: the on-stream resampling step (isingmc_pa_*)
 //   debug.hip      shader-clock probe
+// Every kernel but the probe's is defined in a *_kernels.hip unit of its own and launched through the plain C++ launchers that the
+// headers below declare; none of them defines a kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <sys/mman.h>
@@ -32,13 +34,13 @@
 #include "../../include/isingmc.h"
 #include "best_kernels.hpp"
 #include "cluster_kernels.hpp"
-#include "lattice_kernels.hpp" // (ahead of general_kernels.hpp: a code object lists its kernels in the order of their definitions)
-#include "general_kernels.hpp"
+#include "general_launch.hpp"
 #include "host_logic.hpp"
+#include "lattice_types.hpp"
 #include "packed_between_kernels.hpp"
 #include "packed_cluster_kernels.hpp"
 #include "packed_icm_kernels.hpp"
-#include "packed_kernels.hpp"
+#include "packed_types.hpp"
 #include "pa_kernels.hpp"
 #include "mc_types.hpp"
 #include "overlap_class_kernels.hpp"
@@ -46,12 +48,9 @@
 #include "real_types.hpp"
 #include "spread_types.hpp"
 #include "strip_types.hpp"
+#include "tempering_types.hpp"
 
 using namespace isingmc;
-
-static_assert(PA_PAD_SITE == PAD_SITE, "pa_kernels.hip tests PkGraphDev::site against the general path's padding mark");
-static_assert(CLASS_PAD_SITE == PAD_SITE, "host_logic.cpp class_segments tests the site table against the general path's padding mark");
-static_assert(PKC_PAD_SITE == PAD_SITE, "packed_cluster_kernels.hip tests PkGraphDev::site against the general path's padding mark");
 
 
 #define IM_INTERNAL __attribute__((visibility("hidden")))

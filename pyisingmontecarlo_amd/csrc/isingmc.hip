@@ -1,18 +1,12 @@
 // libisingmc.so: replica containers and every Monte-Carlo launch of the C ABI of include/isingmc.h (gfx950 only).
-// Host orchestration only -- every Monte-Carlo operation runs in the kernels of lattice_kernels.hpp / general_kernels.hpp /
-// packed_kernels.hpp (+ the strip, spread, multi-class, one-degree and real-coupling translation units).  There is no CPU fallback.
+// Host orchestration only -- every Monte-Carlo operation runs in the kernels of the lattice, general, packed, strip, spread,
+// multi-class, one-degree and real-coupling translation units, behind their launchers.  There is no CPU fallback.
 // (internal.hpp: how the host side is cut into translation units.)
 #include "internal.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // states
 // ------------------------------------------------------------------------------------------------
-static dim3 lat_grid(const isingmc_graph *g, uint32_t quads, size_t replicas)
-{
-    (void)g;
-    return dim3((quads + 255) / 256, unsigned(replicas), 1);
-}
-
 
 static int lanes_reserve(isingmc_states *s, size_t n);
 static int lanes_fork(isingmc_states *s, size_t n);
@@ -30,13 +24,8 @@ static int init_random(isingmc_states *s, size_t first, size_t count)
     const isingmc_graph *g = s->g;
     for (size_t r0 = first; r0 < first + count; r0 += MAX_GRID_Y) {
         const size_t n = std::min(MAX_GRID_Y, first + count - r0);
-        if (g->kind == ISINGMC_KIND_LATTICE2D)
-            hipLaunchKernelGGL(lat_init_kernel, lat_grid(g, 2 * g->geom.nquads, n), dim3(256), 0, s->stream,
-                               s->d_state, g->geom, s->d_keys, uint32_t(r0));
-        else
-            hipLaunchKernelGGL(gen_init_kernel, dim3((g->gdev.n_words + 255) / 256, unsigned(n)), dim3(256), 0,
-                               s->stream, s->d_state, g->gdev, s->d_keys, uint32_t(r0));
-        HIP_TRY(hipGetLastError());
+        if (g->kind == ISINGMC_KIND_LATTICE2D) HIP_TRY(lat_launch_init(s->stream, s->d_state, g->geom, s->d_keys, uint32_t(r0), uint32_t(n)));
+        else HIP_TRY(gen_launch_init(s->stream, s->d_state, g->gdev, s->d_keys, uint32_t(r0), uint32_t(n)));
     }
     return ISINGMC_OK;
 }
@@ -383,10 +372,8 @@ static int pk_create(isingmc_states *s, const uint64_t *all_seeds, size_t first,
     } else {
         for (size_t g0 = 0; g0 < s->groups; g0 += MAX_GRID_Y) {
             const size_t ng = std::min(MAX_GRID_Y, s->groups - g0);
-            hipLaunchKernelGGL(pk_init_kernel, dim3((g->pk.n_pos + 255) / 256, unsigned(ng)), dim3(256), 0, s->stream, s->d_state,
-                               g->pk, s->d_keys, uint32_t(g0));
+            HIP_TRY(pk_launch_init(s->stream, s->d_state, g->pk, s->d_keys, uint32_t(g0), uint32_t(ng)));
         }
-        HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(s->stream));
     }
     return ISINGMC_OK;
@@ -427,9 +414,7 @@ static int pk_append(isingmc_states *s, uint64_t seed, const uint8_t *initial_st
         if (s->d_tab) { (void)cached_free(s->d_tab); s->d_tab = nullptr; }             // per-group tables: rebuilt by the next set_betas
         if (s->d_pk_philox) { (void)cached_free(s->d_pk_philox); s->d_pk_philox = nullptr; s->pk_philox_steps = 0; } // rows per group count
         if (s->d_rj_betas) { (void)cached_free(s->d_rj_betas); s->d_rj_betas = nullptr; }
-        hipLaunchKernelGGL(pk_init_kernel, dim3((g->pk.n_pos + 255) / 256, 1), dim3(256), 0, s->stream, s->d_state, g->pk, s->d_keys,
-                           uint32_t(s->groups));
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(pk_launch_init(s->stream, s->d_state, g->pk, s->d_keys, uint32_t(s->groups), 1));
         HIP_TRY(hipStreamSynchronize(s->stream));
         s->groups = groups;
     }
@@ -438,9 +423,7 @@ static int pk_append(isingmc_states *s, uint64_t seed, const uint8_t *initial_st
     else if (slot % 32 != 0) {
         // (real-coupling path: the bits of a group this container does not own are not simulated at all, rj_sweep_kernel PARTIAL,
         //  so the column holds whatever it held)
-        hipLaunchKernelGGL(pk_init_replica_kernel, dim3((g->pk.n_pos + 255) / 256), dim3(256), 0, s->stream, s->d_state, g->pk, s->d_keys,
-                           uint32_t(slot / 32), uint32_t(slot % 32));
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(pk_launch_init_replica(s->stream, s->d_state, g->pk, s->d_keys, uint32_t(slot / 32), uint32_t(slot % 32)));
         HIP_TRY(hipStreamSynchronize(s->stream));
     }
     return ISINGMC_OK;
@@ -456,9 +439,8 @@ static int pk_set_state(isingmc_states *s, size_t replica, const uint8_t *spins)
     uint32_t *d_bits = nullptr;
     TRY(scratch.alloc(&d_bits, bits.size()));
     HIP_TRY(hipMemcpy(d_bits, bits.data(), bits.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(pk_set_replica_kernel, dim3((g->pk.n_pos + 255) / 256), dim3(256), 0, s->stream, s->d_state,
-                       g->pk.n_pos, d_bits, uint32_t((replica + s->pk_bit0) / 32), uint32_t((replica + s->pk_bit0) % 32));
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(pk_launch_set_replica(s->stream, s->d_state, g->pk.n_pos, d_bits, uint32_t((replica + s->pk_bit0) / 32),
+                                  uint32_t((replica + s->pk_bit0) % 32)));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return ISINGMC_OK;
 }
@@ -553,7 +535,7 @@ static void rj_launch_timestep(isingmc_states *s, const RjBeta *betas, uint32_t 
     }
 }
 
-static void pk_launch_timestep(isingmc_states *s, const uint32_t *tabs, uint32_t tab_stride, const uint32_t *philox_tab, size_t gb, size_t ge,
+static int pk_launch_timestep(isingmc_states *s, const uint32_t *tabs, uint32_t tab_stride, const uint32_t *philox_tab, size_t gb, size_t ge,
                                hipStream_t stream)
 {
     const isingmc_graph *g = s->g;
@@ -572,11 +554,11 @@ static void pk_launch_timestep(isingmc_states *s, const uint32_t *tabs, uint32_t
                                           tabs + (tab_stride ? g0 * tab_stride : 0), tab_stride,
                                           philox_tab + g0 * pk_uni_philox_table_words(), g->pk_class_table[c] != 0);
             if (e > mid)
-                hipLaunchKernelGGL(pk_sweep_kernel, dim3((e - mid) / 1024 + ((e - mid) % 1024 != 0), unsigned(ng)), dim3(256), 0, stream,
-                                   s->d_state + g0 * g->pk.n_pos, g->pk, mid, e, s->t, s->d_keys + g0,
-                                   tabs + (tab_stride ? g0 * tab_stride : 0), tab_stride);
+                HIP_TRY(pk_launch_sweep(uint32_t(ng), stream, s->d_state + g0 * g->pk.n_pos, g->pk, mid, e, s->t, s->d_keys + g0,
+                                        tabs + (tab_stride ? g0 * tab_stride : 0), tab_stride));
         }
     }
+    return ISINGMC_OK;
 }
 
 
@@ -631,24 +613,19 @@ int pk_get_states(isingmc_states *s, uint8_t *states_out, size_t replica_stride_
 //  - else two quads per thread while that leaves >= 8 workgroups per CU (measured before the rule above existed: 2 quads +4 %,
 //    4 +2.7 %, 8 +1.3 % on uniform J; +-J: 2 quads +2.6 %).  Workgroups of 128 or 64 threads: no gain.
 // ISINGMC_SWEEP_ITERS=1|2|4|8|16|32 forces the choice (measurement and tests).
-template <bool PMJ>
 static uint32_t sweep_loop_iters(isingmc_states *s, size_t n, unsigned lds_bytes)
 {
     const LatGeom &geom = s->g->geom;
+    const bool pmj = !s->g->uniform_sign;
     const auto fits = [&](uint32_t k) { return geom.nquads % (256 * k) == 0 && geom.H % (2 * k) == 0; };
     const int forced = s->opt.sweep_iters;
     if (forced) return forced > 1 && forced <= 32 && (forced & (forced - 1)) == 0 && fits(uint32_t(forced)) ? uint32_t(forced) : 1u;
-    if (s->sweep_resident_wgs[PMJ] < 0 || s->sweep_resident_lds != lds_bytes) {
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lat_sweep_loop_kernel<PMJ>, 256, lds_bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            per_cu = 0;
-        }
-        s->sweep_resident_wgs[!PMJ] = -1; // a container runs one of the two instantiations
-        s->sweep_resident_wgs[PMJ] = per_cu * s->g->n_cu;
+    if (s->sweep_resident_wgs[pmj] < 0 || s->sweep_resident_lds != lds_bytes) {
+        s->sweep_resident_wgs[!pmj] = -1; // a container runs one of the two instantiations
+        s->sweep_resident_wgs[pmj] = lat_sweep_loop_blocks_per_cu(pmj, lds_bytes) * s->g->n_cu;
         s->sweep_resident_lds = lds_bytes;
     }
-    const size_t resident = size_t(s->sweep_resident_wgs[PMJ]);
+    const size_t resident = size_t(s->sweep_resident_wgs[pmj]);
     for (uint32_t k = 16; resident > 0 && k > 1; k >>= 1) {
         if (!fits(k)) continue;
         const size_t wgs = size_t(geom.nquads / (256 * k)) * s->R;
@@ -657,10 +634,10 @@ static uint32_t sweep_loop_iters(isingmc_states *s, size_t n, unsigned lds_bytes
     return fits(2) && size_t(geom.nquads / 512) * n >= size_t(8) * 256 ? 2u : 1u;
 }
 
-template <bool VEC, bool PMJ>
-static void launch_lat_sweep(isingmc_states *s, uint32_t colour, const LatThr &thr, uint64_t t_arg)
+static int launch_lat_sweep(isingmc_states *s, uint32_t colour, const LatThr &thr, uint64_t t_arg)
 {
     const isingmc_graph *g = s->g;
+    const bool uni = g->vec && g->geom.cols_log2 >= 0; // the division-free mapping: what the looping kernel needs
     // replicas are independent: with n_lanes > 1 the replica blocks go to different streams, so that the
     // launch gap / ramp / tail of one block's half-sweep overlaps the other blocks' work
     const size_t per_lane = (s->R + s->n_lanes - 1) / s->n_lanes;
@@ -671,21 +648,12 @@ static void launch_lat_sweep(isingmc_states *s, uint32_t colour, const LatThr &t
             const size_t n = std::min(MAX_GRID_Y, hi - r0);
             // diagnostic: ISINGMC_DEBUG_SWEEP_LDS=<bytes> of unused LDS per workgroup lowers the occupancy
             const unsigned dbg_lds = unsigned(std::max(0, s->opt.debug_sweep_lds));
-            const auto launch = [&](auto kernel) {
-                hipLaunchKernelGGL(kernel, lat_grid(g, g->geom.nquads, n), dim3(256), dbg_lds, stream,
-                                   s->d_state + r0 * g->state_words, g->geom, colour, t_arg, s->d_keys + r0, thr,
-                                   s->has_betas ? s->d_thr + r0 : nullptr, g->d_jneg, g->jneg_uniform);
-            };
-            uint32_t iters = 1;
-            if (VEC && g->geom.cols_log2 >= 0) iters = sweep_loop_iters<PMJ>(s, n, dbg_lds);
-            if (iters > 1)
-                hipLaunchKernelGGL(lat_sweep_loop_kernel<PMJ>, dim3(g->geom.nquads / (256 * iters), unsigned(n), 1), dim3(256), dbg_lds, stream,
-                                   s->d_state + r0 * g->state_words, g->geom, colour, t_arg, s->d_keys + r0, thr,
-                                   s->has_betas ? s->d_thr + r0 : nullptr, g->d_jneg, g->jneg_uniform, iters);
-            else if (VEC && g->geom.cols_log2 >= 0) launch(lat_sweep_kernel<VEC, PMJ, VEC>); // division-free mapping
-            else launch(lat_sweep_kernel<VEC, PMJ, false>);
+            const uint32_t iters = uni ? sweep_loop_iters(s, n, dbg_lds) : 1;
+            HIP_TRY(lat_launch_sweep(g->vec, !g->uniform_sign, iters, uint32_t(n), dbg_lds, stream, s->d_state + r0 * g->state_words, g->geom,
+                                     colour, t_arg, s->d_keys + r0, thr, s->has_betas ? s->d_thr + r0 : nullptr, g->d_jneg, g->jneg_uniform));
         }
     }
+    return ISINGMC_OK;
 }
 
 // fork: the lanes wait for everything queued on the main stream; join: the main stream waits for the lanes
@@ -722,75 +690,45 @@ int lanes_join(isingmc_states *s)
     return ISINGMC_OK;
 }
 
-template <bool VEC, bool PMJ>
-static void launch_lat_measure(isingmc_states *s, unsigned long long *out, size_t out_stride)
+void lat_measure_enqueue(isingmc_states *s, unsigned long long *out, size_t out_stride)
 {
     const isingmc_graph *g = s->g;
+    const bool pmj = !g->uniform_sign;
     for (size_t r0 = 0; r0 < s->R; r0 += MAX_GRID_Y) {
         const size_t n = std::min(MAX_GRID_Y, s->R - r0);
         const uint32_t blocks = (g->geom.nquads + 256 * MEASURE_QUADS_PER_THREAD - 1) / (256 * MEASURE_QUADS_PER_THREAD);
         if (g->mc_mode == MC_ANISO) { // the two directions' bonds carry different |J|: counted apart
-            (void)mc_launch_measure_aniso(PMJ, dim3(blocks, unsigned(n)), s->stream, s->d_state + r0 * g->state_words, g->geom, g->d_jneg,
+            (void)mc_launch_measure_aniso(pmj, dim3(blocks, unsigned(n)), s->stream, s->d_state + r0 * g->state_words, g->geom, g->d_jneg,
                                           g->jneg_uniform, out + r0 * out_stride, out_stride);
             continue;
         }
         if (g->mc_mode == MC_OPEN || g->mc_mode == MC_FIELD_OPEN || g->d_fneg) {
             // the bonds across an open boundary do not exist: they must not count as satisfied; with field-sign planes the
             // spins along their site's field are counted too
-            (void)mc_launch_measure_open(PMJ, dim3(blocks, unsigned(n)), s->stream, s->d_state + r0 * g->state_words, g->geom, g->d_jneg,
+            (void)mc_launch_measure_open(pmj, dim3(blocks, unsigned(n)), s->stream, s->d_state + r0 * g->state_words, g->geom, g->d_jneg,
                                          g->jneg_uniform, g->open, g->d_fneg, out + r0 * out_stride, out_stride);
             continue;
         }
-        hipLaunchKernelGGL((lat_measure_kernel<VEC, PMJ>), dim3(blocks, unsigned(n)), dim3(256), 0, s->stream,
-                           s->d_state + r0 * g->state_words, g->geom, g->d_jneg, g->jneg_uniform,
-                           out + r0 * out_stride, out_stride);
+        (void)lat_launch_measure(g->vec, pmj, uint32_t(n), s->stream, s->d_state + r0 * g->state_words, g->geom, g->d_jneg, g->jneg_uniform,
+                                 out + r0 * out_stride, out_stride);
     }
 }
 
 // colour-1 half-sweep fused with the measurement of the finished timestep (single stream: the per-step energy
 // mode does not use replica lanes)
-template <bool VEC, bool PMJ>
-static void launch_lat_sweep_measure(isingmc_states *s, const LatThr &thr, uint64_t t_arg, unsigned long long *out, size_t out_stride)
+static int launch_lat_sweep_measure(isingmc_states *s, const LatThr &thr, uint64_t t_arg, unsigned long long *out, size_t out_stride)
 {
     const isingmc_graph *g = s->g;
     for (size_t r0 = 0; r0 < s->R; r0 += MAX_GRID_Y) {
         const size_t n = std::min(MAX_GRID_Y, s->R - r0);
-        const auto launch = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, lat_grid(g, g->geom.nquads, n), dim3(256), 0, s->stream, s->d_state + r0 * g->state_words,
-                               g->geom, t_arg, s->d_keys + r0, thr, s->has_betas ? s->d_thr + r0 : nullptr, g->d_jneg,
-                               g->jneg_uniform, out + r0 * out_stride, out_stride);
-        };
-        if (VEC && g->geom.cols_log2 >= 0) launch(lat_sweep_measure_kernel<VEC, PMJ, VEC>);
-        else launch(lat_sweep_measure_kernel<VEC, PMJ, false>);
+        HIP_TRY(lat_launch_sweep_measure(g->vec, !g->uniform_sign, uint32_t(n), s->stream, s->d_state + r0 * g->state_words, g->geom, t_arg,
+                                         s->d_keys + r0, thr, s->has_betas ? s->d_thr + r0 : nullptr, g->d_jneg, g->jneg_uniform,
+                                         out + r0 * out_stride, out_stride));
     }
+    return ISINGMC_OK;
 }
 
-#define LAT_DISPATCH(fn, ...)                                                                       \
-    do {                                                                                            \
-        const bool pmj__ = !s->g->uniform_sign;                                                     \
-        if (s->g->vec) { if (pmj__) fn<true, true>(__VA_ARGS__); else fn<true, false>(__VA_ARGS__); } \
-        else { if (pmj__) fn<false, true>(__VA_ARGS__); else fn<false, false>(__VA_ARGS__); }       \
-    } while (0)
-
-#ifndef ISINGMC_GEN_RB
-#define ISINGMC_GEN_RB 8
-#endif
-constexpr int GEN_RB = ISINGMC_GEN_RB; // replicas per thread on the general path (amortises the CSR stream)
-
-template <typename WT, int RB>
-static void launch_gen_class(isingmc_states *s, uint32_t b, uint32_t e, double beta)
-{
-    const isingmc_graph *g = s->g;
-    const size_t chunk = MAX_GRID_Y * RB;
-    for (size_t r0 = 0; r0 < s->R; r0 += chunk) {
-        const size_t n = std::min(chunk, s->R - r0);
-        const dim3 grid((e - b + 255) / 256, unsigned((n + RB - 1) / RB));
-        hipLaunchKernelGGL((gen_sweep_kernel<WT, RB>), grid, dim3(256), 0, s->stream, s->d_state + r0 * g->state_words,
-                           g->gdev, b, e, s->t, s->d_keys + r0, beta, s->has_betas ? s->d_beta + r0 : nullptr, uint32_t(n));
-    }
-}
-
-static void launch_gen_timestep(isingmc_states *s, double beta)
+static int launch_gen_timestep(isingmc_states *s, double beta)
 {
     const isingmc_graph *g = s->g;
     for (uint32_t c = 0; c < g->n_colours; c++) {
@@ -804,15 +742,14 @@ static void launch_gen_timestep(isingmc_states *s, double beta)
         while (rb > 1 && (s->R < rb || blocks * ((s->R + rb - 1) / rb) < 2048)) rb /= 2;
         // ISINGMC_GEN_RB_FORCE=1 / 2 / 4 / 8 (option gen_rb) forces, up to the compiled GEN_RB (tests, A/B runs): same results
         if (const int f = s->opt.gen_rb; f == 1 || f == 2 || f == 4 || f == 8) rb = std::min<size_t>(size_t(f), GEN_RB);
-        const auto launch = [&](auto wt) {
-            using WT = decltype(wt);
-            if (rb >= 8) launch_gen_class<WT, 8>(s, b, e, beta);
-            else if (rb == 4) launch_gen_class<WT, 4>(s, b, e, beta);
-            else if (rb == 2) launch_gen_class<WT, 2>(s, b, e, beta);
-            else launch_gen_class<WT, 1>(s, b, e, beta);
-        };
-        if (g->w_is_float) launch(float(0)); else launch(double(0));
+        const size_t chunk = MAX_GRID_Y * rb;
+        for (size_t r0 = 0; r0 < s->R; r0 += chunk) {
+            const size_t n = std::min(chunk, s->R - r0);
+            HIP_TRY(gen_launch_sweep(g->w_is_float, int(rb), uint32_t(n), s->stream, s->d_state + r0 * g->state_words, g->gdev, b, e, s->t,
+                                     s->d_keys + r0, beta, s->has_betas ? s->d_beta + r0 : nullptr));
+        }
     }
+    return ISINGMC_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -861,34 +798,22 @@ int measure_enqueue(isingmc_states *s, unsigned long long *counts_slot, double *
         const unsigned blocks = unsigned(std::max<uint32_t>(1, std::min<uint32_t>(2048, (g->pk.n_pos + 256 * ppt - 1) / (256 * ppt))));
         for (size_t g0 = 0; g0 < s->groups; g0 += MAX_GRID_Y) {
             const size_t ng = std::min(MAX_GRID_Y, s->groups - g0);
-            hipLaunchKernelGGL(pk_measure_kernel, dim3(blocks, unsigned(ng)), dim3(256), 0, s->stream,
-                               s->d_state + g0 * g->pk.n_pos, g->pk, counts_slot + 2 * 32 * g0, uint32_t(32 * ng), ppt,
-                               g->n_colours == 2 ? uint32_t(g->class_base[1]) : g->pk.n_pos, g->n_colours == 2 ? 2u : 1u);
+            HIP_TRY(pk_launch_measure(blocks, uint32_t(ng), s->stream, s->d_state + g0 * g->pk.n_pos, g->pk, counts_slot + 2 * 32 * g0, ppt,
+                                      g->n_colours == 2 ? uint32_t(g->class_base[1]) : g->pk.n_pos, g->n_colours == 2 ? 2u : 1u));
         }
     } else if (g->kind == ISINGMC_KIND_LATTICE2D) {
         HIP_TRY(hipMemsetAsync(counts_slot, 0, 2 * R * sizeof(unsigned long long), s->stream));
-        LAT_DISPATCH(launch_lat_measure, s, counts_slot, size_t(2));
+        lat_measure_enqueue(s, counts_slot, 2);
     } else {
         for (size_t r0 = 0; r0 < R; r0 += MAX_GRID_Y) {
             const size_t n = std::min(MAX_GRID_Y, R - r0);
-            const dim3 grid(s->n_partials, unsigned(n));
-            if (g->w_is_float)
-                hipLaunchKernelGGL(gen_measure_kernel<float>, grid, dim3(256), 0, s->stream, s->d_state + r0 * g->state_words,
-                                   g->gdev, s->d_pe + r0 * s->n_partials, s->d_pm + r0 * s->n_partials);
-            else
-                hipLaunchKernelGGL(gen_measure_kernel<double>, grid, dim3(256), 0, s->stream, s->d_state + r0 * g->state_words,
-                                   g->gdev, s->d_pe + r0 * s->n_partials, s->d_pm + r0 * s->n_partials);
+            HIP_TRY(gen_launch_measure(g->w_is_float, uint32_t(n), s->n_partials, s->stream, s->d_state + r0 * g->state_words, g->gdev,
+                                       s->d_pe + r0 * s->n_partials, s->d_pm + r0 * s->n_partials));
         }
-        hipLaunchKernelGGL(gen_reduce_kernel, dim3(unsigned(R)), dim3(256), 0, s->stream, s->d_pe, s->d_pm, s->n_partials,
-                           e_slot, m_slot);
+        HIP_TRY(gen_launch_reduce(s->stream, s->d_pe, s->d_pm, s->n_partials, uint32_t(R), e_slot, m_slot));
     }
     HIP_TRY(hipGetLastError());
     return ISINGMC_OK;
-}
-
-void lat_measure_enqueue(isingmc_states *s, unsigned long long *out, size_t out_stride)
-{
-    LAT_DISPATCH(launch_lat_measure, s, out, out_stride);
 }
 
 // energies / magnetisations of the current configurations into host arrays (either may be NULL)
@@ -1278,8 +1203,8 @@ static int run_packed(StepRun &c, size_t k0, size_t nk)
                 else rj_launch_timestep(s, c.d_rj + (c.beta_stride ? k : 0), 0, gb, ge, st);
             } else {
                 const uint32_t *rows = philox_words ? s->d_pk_philox + size_t(s->t - s->pk_philox_t0) * philox_words : nullptr; // timestep s->t's
-                if (s->has_betas) pk_launch_timestep(s, s->d_tab, PK_TAB_WORDS, rows, gb, ge, st);
-                else pk_launch_timestep(s, c.d_pk_tabs + (c.beta_stride ? k * PK_TAB_WORDS : 0), 0, rows, gb, ge, st);
+                if (s->has_betas) TRY(pk_launch_timestep(s, s->d_tab, PK_TAB_WORDS, rows, gb, ge, st));
+                else TRY(pk_launch_timestep(s, c.d_pk_tabs + (c.beta_stride ? k * PK_TAB_WORDS : 0), 0, rows, gb, ge, st));
             }
         }
         s->t++;
@@ -1313,17 +1238,15 @@ static int run_lat_resident(StepRun &c, size_t k0, size_t nk)
     }
     const unsigned threads = spread ? spread_threads : unsigned(std::min<size_t>(1024, (g->geom.nquads + 63) / 64 * 64));
     const size_t lds = spread ? spread_lds : g->state_words * sizeof(uint32_t);
-    const auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(unsigned(R)), dim3(threads), lds, s->stream,
-                           s->d_state, g->geom, s->t, uint32_t(nk), s->d_keys, c.d_thr, uint32_t(c.beta_stride ? 1 : 0),
-                           s->has_betas ? s->d_thr : nullptr, g->d_jneg, g->jneg_uniform, c.d_counts, uint32_t(R));
-    };
     if (spread) {
         HIP_TRY(spread_launch(g->vec, !g->uniform_sign, lpq, unsigned(R), threads, lds, s->stream, s->d_state, g->geom, s->t, uint32_t(nk), s->d_keys,
                               c.d_thr, uint32_t(c.beta_stride ? 1 : 0), s->has_betas ? s->d_thr : nullptr, g->d_jneg, g->jneg_uniform,
                               c.d_counts, uint32_t(R)));
-    } else if (g->vec) { if (g->uniform_sign) launch(lat_resident_kernel<true, false>); else launch(lat_resident_kernel<true, true>); }
-    else { if (g->uniform_sign) launch(lat_resident_kernel<false, false>); else launch(lat_resident_kernel<false, true>); }
+    } else {
+        HIP_TRY(lat_launch_resident(g->vec, !g->uniform_sign, unsigned(R), threads, lds, s->stream, s->d_state, g->geom, s->t, uint32_t(nk),
+                                    s->d_keys, c.d_thr, uint32_t(c.beta_stride ? 1 : 0), s->has_betas ? s->d_thr : nullptr, g->d_jneg,
+                                    g->jneg_uniform, c.d_counts));
+    }
     s->t += nk;
     if (k0 + nk < c.timesteps && !c.d_counts) HIP_TRY(hipStreamSynchronize(s->stream)); // h_thr is reused by the next chunk
     return ISINGMC_OK;
@@ -1412,18 +1335,9 @@ static int run_gen_resident(StepRun &c, size_t k0, size_t nk)
         else if (resident[2]) stage = 2;
         stage_bytes = bytes[stage];
     }
-    const auto launch = [&](auto kernel) {
-        if (stage_bytes > 64 * 1024) // beyond the default limit of dynamic LDS
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(stage_bytes));
-        hipLaunchKernelGGL(kernel, dim3(unsigned(R)), dim3(threads), stage ? stage_bytes : g->state_words * sizeof(uint32_t), s->stream,
-                           s->d_state, g->gdev, s->t, uint32_t(nk), s->d_keys, c.d_betas, uint32_t(c.beta_stride ? 1 : 0),
-                           s->has_betas ? s->d_beta : nullptr, c.d_energies, g->self_energy, g->gen_edges2);
-    };
-    if (g->w_is_float) {
-        if (stage == 1) launch(gen_resident_kernel<float, 1>); else if (stage == 2) launch(gen_resident_kernel<float, 2>); else launch(gen_resident_kernel<float, 0>);
-    } else {
-        if (stage == 1) launch(gen_resident_kernel<double, 1>); else if (stage == 2) launch(gen_resident_kernel<double, 2>); else launch(gen_resident_kernel<double, 0>);
-    }
+    HIP_TRY(gen_launch_resident(g->w_is_float, stage, unsigned(R), threads, stage ? stage_bytes : g->state_words * sizeof(uint32_t), s->stream,
+                                s->d_state, g->gdev, s->t, uint32_t(nk), s->d_keys, c.d_betas, uint32_t(c.beta_stride ? 1 : 0),
+                                s->has_betas ? s->d_beta : nullptr, c.d_energies, g->self_energy, g->gen_edges2));
     s->t += nk;
     if (!c.d_energies && k0 + nk < c.timesteps) HIP_TRY(hipStreamSynchronize(s->stream));
     return ISINGMC_OK;
@@ -1436,9 +1350,9 @@ static int run_lat_stream(StepRun &c, size_t k0, size_t nk)
     const size_t R = s->R, SS = c.P.step_slots;
     for (size_t k = k0; k < k0 + nk; k++) {
         const LatThr thr = lattice_thresholds(step_beta(c, k), s->g->jabs);
-        LAT_DISPATCH(launch_lat_sweep, s, 0u, thr, s->t);
-        if (c.d_counts) LAT_DISPATCH(launch_lat_sweep_measure, s, thr, s->t, c.d_counts + (k - k0) * R * 2 * SS, 2 * SS);
-        else LAT_DISPATCH(launch_lat_sweep, s, 1u, thr, s->t);
+        TRY(launch_lat_sweep(s, 0u, thr, s->t));
+        if (c.d_counts) TRY(launch_lat_sweep_measure(s, thr, s->t, c.d_counts + (k - k0) * R * 2 * SS, 2 * SS));
+        else TRY(launch_lat_sweep(s, 1u, thr, s->t));
         s->t++;
     }
     return ISINGMC_OK;
@@ -1459,7 +1373,7 @@ static int run_mc_stream(StepRun &c, size_t k0, size_t nk)
                 hipStream_t stream = s->n_lanes > 1 ? s->lanes[lane] : s->stream;
                 for (size_t r0 = lo; r0 < hi; r0 += MAX_GRID_Y) {
                     const size_t n = std::min(MAX_GRID_Y, hi - r0);
-                    HIP_TRY(mc_launch_sweep(g->mc_mode, !g->uniform_sign, lat_grid(g, g->geom.nquads, n), stream,
+                    HIP_TRY(mc_launch_sweep(g->mc_mode, !g->uniform_sign, dim3((g->geom.nquads + 255) / 256, unsigned(n)), stream,
                                             s->d_state + r0 * g->state_words, g->geom, colour, s->t, s->d_keys + r0, thr,
                                             s->has_betas ? s->d_thr_mc + r0 : nullptr, g->d_jneg, g->jneg_uniform, g->open, g->d_fneg));
                 }
@@ -1476,7 +1390,7 @@ static int run_gen_csr(StepRun &c, size_t k0, size_t nk)
 {
     isingmc_states *s = c.s;
     for (size_t k = k0; k < k0 + nk; k++) {
-        launch_gen_timestep(s, step_beta(c, k));
+        TRY(launch_gen_timestep(s, step_beta(c, k)));
         s->t++;
         if (c.d_energies) TRY(measure_enqueue(s, nullptr, c.d_energies + (k - k0) * s->R, c.d_mags));
     }

@@ -741,7 +741,6 @@ __device__ __forceinline__ void update_quad(const Mem &mem, const LatGeom &g, co
     }
 }
 
-constexpr uint32_t MEASURE_SLOTS = 16;
 #ifndef ISINGMC_MEASURE_WAVES
 #define ISINGMC_MEASURE_WAVES 7 // waves per SIMD the measuring kernel is compiled for (<= 72 VGPRs; it wanted 74-80 and ran at 6)
 #endif
@@ -901,24 +900,9 @@ __global__ __launch_bounds__(256) void lat_sweep_loop_kernel(
     }
 }
 
-// Random initial configuration: word w of plane c = Philox(key, (0, w>>2, c<<8, "LATI"))[w&3].
-__attribute__((unused)) static __global__ __launch_bounds__(256) void lat_init_kernel(uint32_t *__restrict__ state, const LatGeom g,
-                                                       const uint2 *__restrict__ keys,
-                                                       const uint32_t first_replica)
-{
-    const uint32_t r = first_replica + blockIdx.y;
-    const uint32_t Q = blockIdx.x * 256 + threadIdx.x;
-    if (Q >= 2 * g.nquads) return;
-    const uint32_t c = Q >= g.nquads, q = Q - c * g.nquads;
-    const uint4 rnd = philox4x32_10(make_uint4(0, q, ctr2(0, c, 0), DOM_LAT_INIT), keys[r]);
-    *reinterpret_cast<uint4 *>(state + size_t(r) * 2 * g.wpp + size_t(c) * g.wpp + 4 * size_t(q)) = rnd;
-}
-
 // Full recomputation of the satisfied-bond count and the up-spin count of every replica
 // (get_energy, lattice.rs:208): every bond joins a colour-0 site to a colour-1 site, so the four
 // bonds of the colour-0 sites cover each bond once.  out[2r] += satisfied, out[2r+1] += up spins.
-constexpr uint32_t MEASURE_QUADS_PER_THREAD = 16;
-
 template <bool VEC, bool PMJ>
 __global__ __launch_bounds__(256) void lat_measure_kernel(
     const uint32_t *__restrict__ state, const LatGeom g, const uint32_t *__restrict__ jneg,
@@ -971,8 +955,6 @@ __global__ __launch_bounds__(256) void lat_measure_kernel(
 // configurations are bit-identical to the per-colour launches of lat_sweep_kernel.
 // steps_out (optional): satisfied bonds / up spins after every timestep, [step][replica][2].
 // ------------------------------------------------------------------------------------------------
-constexpr uint32_t LDS_RESIDENT_MAX_BYTES = 64 * 1024;
-
 template <bool VEC, bool PMJ>
 __global__ __launch_bounds__(1024) void lat_resident_kernel(
     uint32_t *__restrict__ state, const LatGeom g, const uint64_t t0, const uint32_t timesteps,
@@ -1031,18 +1013,6 @@ __global__ __launch_bounds__(1024) void lat_resident_kernel(
     }
     for (uint32_t i = tid; i < g.wpp / 2; i += nthreads)
         reinterpret_cast<uint4 *>(mine)[i] = reinterpret_cast<const uint4 *>(planes)[i];
-}
-
-// lattice energies from the satisfied-bond counters: E = |J| (n_bonds - 2 sat)  (exact in f64)
-__attribute__((unused)) static __global__ void lat_energy_from_counts_kernel(unsigned long long *__restrict__ meas, const uint32_t n,
-                                              const double jabs, const long long n_bonds, double *__restrict__ out)
-{
-    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < n) {
-        out[r] = jabs * double(n_bonds - 2 * (long long)meas[2 * size_t(r)]);
-        meas[2 * size_t(r)] = 0; // the counters are left zeroed for the next measurement (no memset per round)
-        meas[2 * size_t(r) + 1] = 0;
-    }
 }
 
 } // namespace isingmc

@@ -111,7 +111,7 @@ __global__ __launch_bounds__(256) void ovl_pk_count_kernel(const uint32_t *__res
     for (uint32_t it = 0; it < OVL_PK_ITER; it++) {
         const uint32_t p = (blockIdx.x * OVL_PK_ITER + it) * 256 + threadIdx.x;
         if (p >= n_pos) break;
-        if (site[p] == PKC_PAD_SITE) continue;
+        if (site[p] == PAD_SITE) continue;
         const uint32_t xp = overlap_word(p);
         ovl_csa_add(cd, xp);
         for (uint32_t k = 0; k < n_slots; k++) {

@@ -161,7 +161,7 @@ extern "C" int isingmc_host_class_segments(const uint32_t *site, size_t n_pos, c
         if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
     }
     for (size_t p = 0; p < n_pos; p++)
-        if (site[p] != CLASS_PAD_SITE && site[p] >= nvars) return fail(ISINGMC_ERR_INVALID, "site table entry out of range: a position holds a site below nvars or the padding mark");
+        if (site[p] != PAD_SITE && site[p] >= nvars) return fail(ISINGMC_ERR_INVALID, "site table entry out of range: a position holds a site below nvars or the padding mark");
     const ClassSegments S = class_segments(site, n_pos, cls, nvars, n_tables, n_classes);
     std::copy(S.order.begin(), S.order.end(), order_out);
     std::copy(S.seg.begin(), S.seg.end(), seg_out);

@@ -204,7 +204,7 @@ __global__ __launch_bounds__(256) void pa_bit_gather_kernel(const uint32_t *__re
     const size_t own = size_t(tg) * n_pos + p;
     const uint32_t old = in[own];
     uint32_t word = old;
-    if (site[p] != PA_PAD_SITE) {
+    if (site[p] != PAD_SITE) {
         const uint32_t nb = min(32u, R - 32u * tg); // slots of this group the container owns
         uint32_t cur_g = 0xFFFFFFFFu, cur_w = 0u, acc = 0u;
         for (uint32_t b = 0; b < nb; b++) {

@@ -14,11 +14,12 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "general_types.hpp"
+
 namespace isingmc {
 
 constexpr uint32_t DOM_PA_RESAMPLE = 0x50415253u; // "PARS"
 constexpr uint32_t PA_SCAN_BLOCK = 1024;          // elements per workgroup of the scan's first and third pass
-constexpr uint32_t PA_PAD_SITE = 0xFFFFFFFFu;     // padding mark of PkGraphDev::site (checked against PAD_SITE in population.hip)
 constexpr uint64_t PA_MAX_REPLICAS = uint64_t(1) << 31;
 
 // the record of one resampling, as the device leaves it
@@ -44,7 +45,7 @@ hipError_t pa_launch_gather_u32(hipStream_t stream, const uint32_t *in, const ui
 // checkerboard containers: out[j][:] = in[src[j]][:], rows of state_words words
 hipError_t pa_launch_row_gather(hipStream_t stream, const uint32_t *in, uint32_t *out, const uint32_t *src, size_t R, size_t state_words);
 // replica-packed containers, u32[groups][n_pos]: bit s % 32 of group s / 32 of `out` = that of slot src[s] of `in` for s < R at
-// the real positions; every other bit (slots >= R, padding positions: site[p] == PA_PAD_SITE) is copied from its own place
+// the real positions; every other bit (slots >= R, padding positions: site[p] == PAD_SITE) is copied from its own place
 hipError_t pa_launch_bit_gather(hipStream_t stream, const uint32_t *in, uint32_t *out, const uint32_t *src, uint32_t R, size_t groups,
                                 uint32_t n_pos, const uint32_t *site);
 

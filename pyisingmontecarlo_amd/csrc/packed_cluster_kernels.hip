@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256) void pkc_flip_kernel(uint32_t *__restrict__ st
     PklCounts<32> counts{sizes + size_t(g) * G.n_pos * 32 + b};
     for (uint32_t i = 0; i < PKC_FLIP_POS / 8; i++) {
         const uint32_t p = blockIdx.x * PKC_FLIP_POS + 8 * i + pl;
-        const bool real = G.site[p] != PKC_PAD_SITE;
+        const bool real = G.site[p] != PAD_SITE;
         uint32_t flip = 0;
         if (real) {
             const uint32_t root = cl_find<PKL_AGENT, 32>(lab, p);

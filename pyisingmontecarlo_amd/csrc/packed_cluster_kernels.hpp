@@ -13,9 +13,6 @@ namespace isingmc {
 
 constexpr uint32_t DOM_PK_CL_BOND = 0x504B4244u; // "PKBD"
 constexpr uint32_t DOM_PK_CL_FLIP = 0x504B464Cu; // "PKFL"
-// PkGraphDev::site on padding; general_kernels.hpp (PAD_SITE) is not included here because it would instantiate its kernels in
-// this translation unit: internal.hpp, which sees both, asserts that the two agree
-constexpr uint32_t PKC_PAD_SITE = 0xFFFFFFFFu;
 
 // workspace of one batch of n replica groups (n_pos positions each)
 struct PkClusterWork {

@@ -88,7 +88,7 @@ __global__ __launch_bounds__(256) void pki_flip_kernel(uint32_t *__restrict__ st
     for (uint32_t i = 0; i < PKI_FLIP_POS / 16; i++) {
         const uint32_t p = blockIdx.x * PKI_FLIP_POS + 16 * i + pl;
         const uint32_t w = st[p];
-        const uint32_t d = site[p] != PKC_PAD_SITE ? (w ^ (w >> 1)) & mask : 0u;
+        const uint32_t d = site[p] != PAD_SITE ? (w ^ (w >> 1)) & mask : 0u;
         uint32_t flip = 0;
         if ((d >> (2 * j)) & 1u) {
             const uint32_t root = cl_find<PKL_AGENT, 16>(lab, p);

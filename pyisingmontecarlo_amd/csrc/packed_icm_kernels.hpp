@@ -39,7 +39,7 @@ static inline PkIcmWork pk_icm_carve(uint32_t *block, size_t batch, uint64_t n_p
 
 // One move of groups [0, n) at timestep t: state / group_keys / move_mask / stats / minus point at the first group of the batch.
 // move_mask[g]: bit 2 j set when pair j of group g moves.  nbr_rj == nullptr: the neighbours of G.nbr_ell (PK_MAX_DEG slots);
-// else nbr_rj[slot][n_pos] with rj_slots slots (the own position in unused slots).  `site` marks the padding (PKC_PAD_SITE).
+// else nbr_rj[slot][n_pos] with rj_slots slots (the own position in unused slots).  `site` marks the padding (PAD_SITE).
 // stats: [16 n][2] = {clusters, largest cluster}, minus: [16 n] = positions where the pair differs, per (group, pair); zero on
 // entry.  n <= 32768.
 hipError_t pk_icm_launch_step(hipStream_t stream, uint32_t *state, const PkGraphDev &G, const uint32_t *nbr_rj, uint32_t rj_slots, uint64_t t,

@@ -51,10 +51,10 @@ __device__ __forceinline__ uint32_t pk_match(uint32_t c0, uint32_t c1, uint32_t 
 }
 
 // one colour class of one timestep; blockIdx.y = replica group
-__attribute__((unused)) static __global__ __launch_bounds__(256, 8) void pk_sweep_kernel(uint32_t *__restrict__ state, const PkGraphDev G,
-                                                       const uint32_t class_begin, const uint32_t class_end,
-                                                       const uint64_t t, const uint2 *__restrict__ group_keys,
-                                                       const uint32_t *__restrict__ tabs, const uint32_t tab_stride)
+__global__ __launch_bounds__(256, 8) void pk_sweep_kernel(uint32_t *__restrict__ state, const PkGraphDev G,
+                                                          const uint32_t class_begin, const uint32_t class_end,
+                                                          const uint64_t t, const uint2 *__restrict__ group_keys,
+                                                          const uint32_t *__restrict__ tabs, const uint32_t tab_stride)
 {
     const uint32_t g = blockIdx.y;
     const uint32_t tid = blockIdx.x * 256 + threadIdx.x; // wave w of the class owns positions [256w, 256w+256)
@@ -183,7 +183,7 @@ __attribute__((unused)) static __global__ __launch_bounds__(256, 8) void pk_swee
 
 // random start: position p is word q = (p & 255) >> 6 of its quad (leader p - 64 q):
 // word = Philox(group key, (0, leader, 0, "PKIN"))[q]; padding positions 0
-__attribute__((unused)) static __global__ __launch_bounds__(256) void pk_init_kernel(uint32_t *__restrict__ state, const PkGraphDev G,
+__global__ __launch_bounds__(256) void pk_init_kernel(uint32_t *__restrict__ state, const PkGraphDev G,
                                                       const uint2 *__restrict__ group_keys, const uint32_t first_group)
 {
     const uint32_t g = first_group + blockIdx.y;
@@ -196,7 +196,7 @@ __attribute__((unused)) static __global__ __launch_bounds__(256) void pk_init_ke
 
 // the random start of ONE replica bit of a group (real-coupling path: a replica appended to a partly used group starts from
 // its random start -- the bits a container does not own are not simulated there, see rj_sweep_kernel PARTIAL)
-__attribute__((unused)) static __global__ __launch_bounds__(256) void pk_init_replica_kernel(uint32_t *__restrict__ state, const PkGraphDev G,
+__global__ __launch_bounds__(256) void pk_init_replica_kernel(uint32_t *__restrict__ state, const PkGraphDev G,
                                                               const uint2 *__restrict__ group_keys, const uint32_t g, const uint32_t bit)
 {
     const uint32_t p = blockIdx.x * 256 + threadIdx.x;
@@ -215,7 +215,6 @@ __attribute__((unused)) static __global__ __launch_bounds__(256) void pk_init_re
 // for every plane and replica bit one ballot + scalar popcount over the wavefront (the scalar unit is idle
 // anyway).  ~1 vector instruction per position and 32 replicas; the previous version spent a lane per
 // (position, replica) pair and took 7.3 ms for 256^3 x 64 replicas, 20x a sweep.
-constexpr uint32_t PK_MEASURE_POS_PER_THREAD = 32; // 6 x 32 = 192 < 2^8 satisfied bonds, 32 < 2^6 up spins per thread
 constexpr uint32_t PK_MEASURE_CHUNK = 256 * PK_MEASURE_POS_PER_THREAD;
 
 // bit-sliced add of the K2-plane number x into the K-plane accumulator S (per bit lane), K2 <= K
@@ -236,7 +235,7 @@ __device__ __forceinline__ void bs_add(uint32_t (&S)[K], const uint32_t (&x)[K2]
 // sat_end / sat_scale: on a 2-coloured (bipartite) graph every bond joins class 0 to class 1, so the bonds are counted from
 // the class-0 positions only (sat_end = the end of class 0) and doubled (sat_scale = 2) into the same directed total -- half
 // the neighbour gathers; otherwise sat_end = n_pos, sat_scale = 1.
-__attribute__((unused)) static __global__ __launch_bounds__(256) void pk_measure_kernel(const uint32_t *__restrict__ state, const PkGraphDev G,
+__global__ __launch_bounds__(256) void pk_measure_kernel(const uint32_t *__restrict__ state, const PkGraphDev G,
                                                          unsigned long long *__restrict__ out, const uint32_t n_replicas,
                                                          const uint32_t pos_per_thread, const uint32_t sat_end, const uint32_t sat_scale)
 {
@@ -302,7 +301,7 @@ __attribute__((unused)) static __global__ __launch_bounds__(256) void pk_measure
 }
 
 // write one replica's spins (bits[] packed by position, 32 positions per word) into bit `bit` of group g
-__attribute__((unused)) static __global__ __launch_bounds__(256) void pk_set_replica_kernel(uint32_t *__restrict__ state, const uint32_t n_pos,
+__global__ __launch_bounds__(256) void pk_set_replica_kernel(uint32_t *__restrict__ state, const uint32_t n_pos,
                                                              const uint32_t *__restrict__ bits, const uint32_t g,
                                                              const uint32_t bit)
 {
@@ -311,39 +310,6 @@ __attribute__((unused)) static __global__ __launch_bounds__(256) void pk_set_rep
     uint32_t *w = state + size_t(g) * n_pos + p;
     const uint32_t v = (bits[p >> 5] >> (p & 31u)) & 1u;
     *w = (*w & ~(1u << bit)) | (v << bit);
-}
-
-// ---- tempering on the stream (isingmc_pt_* on a packed container) -------------------------------------------------------
-// Energies of the local slots from the measurement counters: E = |J| (undirected bonds - directed satisfied count) + self loops --
-// the arithmetic of the host's pk_energy, hence the same bits.
-__attribute__((unused)) static __global__ void pk_energy_from_counts_kernel(const unsigned long long *__restrict__ meas, const uint32_t first_slot,
-                                                                            const uint32_t n, const double jabs, const double half_directed,
-                                                                            const double self_energy, double *__restrict__ out)
-{
-    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < n) out[r] = jabs * (half_directed - double((long long)meas[2 * size_t(first_slot + r)])) + self_energy;
-}
-
-// Threshold tables of every group from per-slot thresholds (slot_thr[slot][m - 1] = T_m(beta of the slot), written by the exchange
-// kernel): what pk_fill_table builds on the host for isingmc_states_set_betas, bit for bit.  One wavefront per group; lane r < 32 =
-// replica bit r; slots at or beyond n_owned take the last owned slot's thresholds (as the host does).
-__attribute__((unused)) static __global__ void pk_tables_from_slots_kernel(const unsigned long long *__restrict__ slot_thr, const uint32_t n_owned,
-                                                                           uint32_t *__restrict__ tabs)
-{
-    const uint32_t g = blockIdx.x, lane = threadIdx.x; // 64 threads
-    uint32_t *tab = tabs + size_t(g) * PK_TAB_WORDS;
-    const uint32_t slot = min(32u * g + (lane & 31u), n_owned - 1u);
-    for (uint32_t m = 0; m < uint32_t(PK_MAX_DEG); m++) {
-        const unsigned long long T = lane < 32 ? slot_thr[size_t(slot) * PK_MAX_DEG + m] : 0ull;
-        const uint32_t all = uint32_t(__ballot(lane < 32 && (T >> THR_BITS) != 0));
-        if (lane == 0) tab[PK_TAB_ALL + m] = all;
-        const uint32_t hi = uint32_t(T >> 32) & ((1u << N_PLANES) - 1);
-        for (int p = 0; p < N_PLANES; p++) {
-            const uint32_t w = uint32_t(__ballot(lane < 32 && ((hi >> (N_PLANES - 1 - p)) & 1u)));
-            if (lane == 0) tab[PK_TAB_TBW + m * N_PLANES + p] = w;
-        }
-        if (lane < 32) tab[PK_TAB_LO + m * 32 + lane] = uint32_t(T);
-    }
 }
 
 } // namespace isingmc

@@ -110,7 +110,7 @@ __device__ __forceinline__ void pkl_gather_word(const PkSide &a, const PkSide &b
     const uint32_t B = blockIdx.y, i = threadIdx.x & 31u, pl = threadIdx.x >> 5, p = blockIdx.x * 8 + pl;
     const uint32_t n = pair0 + 32 * B + i;
     uint32_t x = 0;
-    if (n < n_pairs && site[p] != PKC_PAD_SITE) {
+    if (n < n_pairs && site[p] != PAD_SITE) {
         const uint32_t sa = a.slots[n], sb = b.slots[n];
         if (sa < a.n_slots && sb < b.n_slots) {
             const uint32_t ca = a.bit0 + sa, cb = b.bit0 + sb;

@@ -5,6 +5,7 @@
 
 #include <cstdint>
 
+#include "general_types.hpp"
 #include "lattice_types.hpp"
 
 namespace isingmc {
@@ -34,6 +35,21 @@ struct PkGraphDev {
     uint32_t n_colours;
     uint32_t n_pos;             // multiple of 256
 };
+
+// ---- launchers of packed_kernels.hip (every graph of the path).  n_groups replica groups, whose words, keys and tables begin at
+// the pointers passed
+hipError_t pk_launch_init(hipStream_t stream, uint32_t *state, const PkGraphDev &G, const uint2 *group_keys, uint32_t first_group, uint32_t n_groups);
+// the random start of replica bit `bit` of group g alone / that bit from bits[] (packed by position, 32 positions per word)
+hipError_t pk_launch_init_replica(hipStream_t stream, uint32_t *state, const PkGraphDev &G, const uint2 *group_keys, uint32_t g, uint32_t bit);
+hipError_t pk_launch_set_replica(hipStream_t stream, uint32_t *state, uint32_t n_pos, const uint32_t *bits, uint32_t g, uint32_t bit);
+// positions [class_begin, class_end) of one colour class, one timestep; tab_stride == 0: one threshold table for every group
+hipError_t pk_launch_sweep(uint32_t n_groups, hipStream_t stream, uint32_t *state, const PkGraphDev &G, uint32_t class_begin, uint32_t class_end,
+                           uint64_t t, const uint2 *group_keys, const uint32_t *tabs, uint32_t tab_stride);
+// out[2 slot] += directed satisfied bonds, out[2 slot + 1] += up spins of slot = 32 g + b; `blocks` workgroups per group walk
+// pos_per_thread <= PK_MEASURE_POS_PER_THREAD positions per thread at a time; sat_end / sat_scale: see pk_measure_kernel
+constexpr uint32_t PK_MEASURE_POS_PER_THREAD = 32; // 6 x 32 = 192 < 2^8 satisfied bonds, 32 < 2^6 up spins per thread
+hipError_t pk_launch_measure(unsigned blocks, uint32_t n_groups, hipStream_t stream, const uint32_t *state, const PkGraphDev &G,
+                             unsigned long long *out, uint32_t pos_per_thread, uint32_t sat_end, uint32_t sat_scale);
 
 // One of the two containers of an arbitrary pairing as the kernels see it (S13's moves, S15's overlaps; the two may be the same
 // container): pair n is slot slots[n] of it.

@@ -14,12 +14,11 @@
 //      integer test  max(X >> shift, 0) <= (Lambda_q * mant) >> 32  -- no exp, no f64, no 53-bit uniform per attempt.
 // The CPU oracle (engine E, oracle/ising_oracle.c) takes the same decisions spin by spin from a direct integer field sum.
 #pragma once
+#include "general_types.hpp"
 #include "philox.hpp"
 #include "real_types.hpp"
 
 namespace isingmc {
-
-constexpr uint32_t RJ_PAD_SITE = 0xFFFFFFFFu; // == PAD_SITE (general_kernels.hpp)
 
 // One step of the transposition: swap the high sub-blocks (bits m << s) of x with the low sub-blocks (bits m) of y.
 __device__ __forceinline__ void rj_delta_swap(uint32_t &x, uint32_t &y, const uint32_t m, const int s)
@@ -277,7 +276,7 @@ __global__ __launch_bounds__(RjShape<SLOTS>::THREADS) void rj_measure_kernel(con
     for (int b = 0; b < (UP ? 32 : 1); b++) up[b] = 0;
     for (uint32_t base = blockIdx.x * RjShape<SLOTS>::THREADS; base < scan_end; base += gridDim.x * RjShape<SLOTS>::THREADS) { // base: wave-uniform
         const uint32_t p = base + tid;
-        if (site[p] == RJ_PAD_SITE) continue;
+        if (site[p] == PAD_SITE) continue;
         uint32_t own, w[RjShape<SLOTS>::WORDS];
         int32_t jq[SLOTS], hq;
         // class boundaries are multiples of 256: uniform per workgroup.  Class 1 of a two-class graph: only the bias term

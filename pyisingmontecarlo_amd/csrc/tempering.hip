@@ -33,8 +33,7 @@ static uint64_t *pt_thr_local(isingmc_states *s)
 static int pt_after_swap(isingmc_states *s)
 {
     if (s->packed && !s->rj && s->R) {
-        hipLaunchKernelGGL(pk_tables_from_slots_kernel, dim3(unsigned(s->groups)), dim3(64), 0, s->stream, s->d_pk_slot_thr, uint32_t(s->R), s->d_tab);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(pk_launch_tables_from_slots(s->stream, s->d_pk_slot_thr, uint32_t(s->R), uint32_t(s->groups), s->d_tab));
     }
     return ISINGMC_OK;
 }
@@ -157,8 +156,7 @@ extern "C" int isingmc_pt_attach(isingmc_states *s, const double *ladder_betas, 
     s->betas.assign(s->R, 0.0);
     s->has_betas = true;
     s->pt_attached = true;
-    hipLaunchKernelGGL(pt_swap_kernel, dim3(1), dim3(1024), 0, s->stream, s->pt, pt_thr_local(s), s->packed ? nullptr : s->d_beta, 1u);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(pt_launch_swap(s->stream, s->pt, pt_thr_local(s), s->packed ? nullptr : s->d_beta, /*apply_only=*/true));
     TRY(pt_after_swap(s));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return ISINGMC_OK;
@@ -260,14 +258,13 @@ int energies_enqueue(isingmc_states *s, double *d_out)
         // a single rank, writes straight into the gathered array (no memset, no device-to-device copy)
         if (!s->meas_zero) HIP_TRY(hipMemsetAsync(s->d_meas, 0, 2 * R * sizeof(unsigned long long), s->stream));
         lat_measure_enqueue(s, s->d_meas, size_t(2));
-        hipLaunchKernelGGL(lat_energy_from_counts_kernel, dim3(unsigned((R + 255) / 256)), dim3(256), 0, s->stream, s->d_meas,
-                           uint32_t(R), g->jabs, 2ll * (long long)g->nvars, d_out);
+        HIP_TRY(lat_launch_energy_from_counts(s->stream, s->d_meas, uint32_t(R), g->jabs, 2ll * (long long)g->nvars, d_out));
         s->meas_zero = true;
     } else if (s->packed && !s->rj) {
         TRY(measure_enqueue(s, s->d_meas, nullptr, nullptr, /*want_up=*/false));
         s->meas_zero = false;
-        hipLaunchKernelGGL(pk_energy_from_counts_kernel, dim3(unsigned((R + 255) / 256)), dim3(256), 0, s->stream, s->d_meas, uint32_t(s->pk_bit0),
-                           uint32_t(R), g->jabs, double(int64_t(g->n_directed / 2)), g->self_energy, d_out);
+        HIP_TRY(pk_launch_energy_from_counts(s->stream, s->d_meas, uint32_t(s->pk_bit0), uint32_t(R), g->jabs, double(int64_t(g->n_directed / 2)),
+                                             g->self_energy, d_out));
     } else if (s->packed && s->rj) {
         TRY(measure_enqueue(s, s->d_meas, nullptr, nullptr, /*want_up=*/false));
         s->meas_zero = false;
@@ -284,8 +281,7 @@ extern "C" int isingmc_pt_swap(isingmc_states *s)
 {
     if (!s || !s->pt_attached) return fail(ISINGMC_ERR_INVALID, "no ladder attached");
     TRY(use_device(s->g->device));
-    hipLaunchKernelGGL(pt_swap_kernel, dim3(1), dim3(1024), 0, s->stream, s->pt, pt_thr_local(s), s->packed ? nullptr : s->d_beta, 0u);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(pt_launch_swap(s->stream, s->pt, pt_thr_local(s), s->packed ? nullptr : s->d_beta, /*apply_only=*/false));
     return pt_after_swap(s);
 }
 

@@ -86,7 +86,7 @@ def n_positions(oracle, g):
 
 
 def gen_stage_words(n_pos, edges2, has_bias, w_bytes, stage):
-    """general_kernels.hpp gen_stage_words: 32-bit LDS words of the resident kernel's STAGE 1 / 2"""
+    """general_types.hpp gen_stage_words: 32-bit LDS words of the resident kernel's STAGE 1 / 2"""
     off = (n_pos // 32 + 1) & ~1
     if stage == 1:
         if has_bias:

@@ -20,13 +20,23 @@ ASM_FLAGS = HIP_CODEGEN_FLAGS + ["-S", "--cuda-device-only"]
 
 
 @pytest.fixture(scope="module")
-def device_asm(tmp_path_factory):
+def unit_asm(tmp_path_factory):
+    """the device assembly of every translation unit of the library that may hold device code, compiled with the library's own flags"""
     if not (os.path.exists(HIPCC) or shutil.which(HIPCC)):
         pytest.skip("hipcc not available")
-    out = tmp_path_factory.mktemp("asm") / "isingmc.s"
-    src = os.path.join(ROOT, "pyisingmontecarlo_amd", "csrc", "isingmc.hip")
-    subprocess.check_call([HIPCC] + ASM_FLAGS + ["-o", str(out), src], stderr=subprocess.DEVNULL)
-    return out.read_text()
+    tmp = tmp_path_factory.mktemp("asm")
+    procs = []
+    for name in HIP_SOURCES:
+        if not name.endswith(".hip"):
+            continue
+        out = tmp / (name + ".s")
+        procs.append((name, out, subprocess.Popen([HIPCC] + ASM_FLAGS + ["-o", str(out), os.path.join(ROOT, "pyisingmontecarlo_amd", "csrc", name)],
+                                                  stderr=subprocess.DEVNULL)))
+    texts = {}
+    for name, out, proc in procs:
+        assert proc.wait() == 0, name
+        texts[name] = out.read_text()
+    return texts
 
 
 def _kernel_meta(asm, mangled_prefix):
@@ -42,8 +52,8 @@ def _kernel_meta(asm, mangled_prefix):
 
 
 @pytest.mark.parametrize("prefix", ["_ZN7isingmc21lat_sweep_loop_kernel", "_ZN7isingmc16lat_sweep_kernel"])
-def test_sweep_kernels_keep_eight_waves_per_simd(device_asm, prefix):
-    metas = _kernel_meta(device_asm, prefix)
+def test_sweep_kernels_keep_eight_waves_per_simd(unit_asm, prefix):
+    metas = _kernel_meta(unit_asm["lattice_kernels.hip"], prefix)
     assert metas, "kernel not found in the device assembly"
     for name, vgpr, spill, scratch in metas:
         if prefix.endswith("loop_kernel") and "ILb1E" in name:
@@ -52,21 +62,18 @@ def test_sweep_kernels_keep_eight_waves_per_simd(device_asm, prefix):
         assert spill == 0 and scratch == 0, f"{name}: spills to scratch"
 
 
-def test_packed_sweep_kernel_keeps_eight_waves(device_asm):
+def test_packed_sweep_kernel_keeps_eight_waves(unit_asm):
     """Capped at 64 VGPRs with __launch_bounds__(256, 8): three spilled registers cost less than the eighth wave
     gains (the kernel is bound by the latency of its dependent memory phases): +2 % on 256^3 x 64."""
-    for name, vgpr, spill, scratch in _kernel_meta(device_asm, "_ZN7isingmc15pk_sweep_kernel"):
+    metas = _kernel_meta(unit_asm["packed_kernels.hip"], "_ZN7isingmc15pk_sweep_kernel")
+    assert metas, "kernel not found in the device assembly"
+    for name, vgpr, spill, scratch in metas:
         assert vgpr <= 64 and spill <= 4 and scratch <= 32, f"{name}: {vgpr} VGPRs, {spill} spills, {scratch} B scratch"
 
 
-def test_packed_uniform_degree_kernels_keep_eight_waves(tmp_path):
+def test_packed_uniform_degree_kernels_keep_eight_waves(unit_asm):
     """pk_sweep_uni_kernel<D, UB, PMJ, TABLE>: at most a few spilled registers at __launch_bounds__(256, 8)."""
-    if not (os.path.exists(HIPCC) or shutil.which(HIPCC)):
-        pytest.skip("hipcc not available")
-    out = tmp_path / "pku.s"
-    src = os.path.join(ROOT, "pyisingmontecarlo_amd", "csrc", "packed_uni_kernels.hip")
-    subprocess.check_call([HIPCC] + ASM_FLAGS + ["-o", str(out), src], stderr=subprocess.DEVNULL)
-    metas = _kernel_meta(out.read_text(), "_ZN7isingmc19pk_sweep_uni_kernel")
+    metas = _kernel_meta(unit_asm["packed_uni_kernels.hip"], "_ZN7isingmc19pk_sweep_uni_kernel")
     assert len(metas) == 32
     for name, vgpr, spill, scratch in metas:
         assert vgpr <= 64 and spill <= 4 and scratch <= 32, f"{name}: {vgpr} VGPRs, {spill} spills, {scratch} B scratch"
@@ -74,16 +81,11 @@ def test_packed_uniform_degree_kernels_keep_eight_waves(tmp_path):
             assert spill == 0 and scratch == 0, f"{name}: spills"
 
 
-def test_multi_class_kernels_keep_their_occupancy(tmp_path):
+def test_multi_class_kernels_keep_their_occupancy(unit_asm):
     """lat_mc_sweep_kernel: the uniform-field instantiation the field benchmark runs (<FIELD, uniform sign, 2^k mapping, no
     sign planes>) stays at 7 waves per SIMD (<= 72 VGPRs; a runtime branch on the sign-plane pointer once made it 97), the
     open-boundary ones at 8 (<= 64), and nothing spills."""
-    if not (os.path.exists(HIPCC) or shutil.which(HIPCC)):
-        pytest.skip("hipcc not available")
-    out = tmp_path / "mc.s"
-    src = os.path.join(ROOT, "pyisingmontecarlo_amd", "csrc", "mc_kernels.hip")
-    subprocess.check_call([HIPCC] + ASM_FLAGS + ["-o", str(out), src], stderr=subprocess.DEVNULL)
-    metas = _kernel_meta(out.read_text(), "_ZN7isingmc19lat_mc_sweep_kernel")
+    metas = _kernel_meta(unit_asm["mc_kernels.hip"], "_ZN7isingmc19lat_mc_sweep_kernel")
     assert len(metas) == 24
     for name, vgpr, spill, scratch in metas:
         assert spill == 0 and scratch == 0, f"{name}: spills"
@@ -93,7 +95,7 @@ def test_multi_class_kernels_keep_their_occupancy(tmp_path):
             assert vgpr <= 65, f"{name}: {vgpr} VGPRs"
 
 
-def test_no_vector_store_data_is_overwritten_right_behind_the_store(device_asm, tmp_path):
+def test_no_vector_store_data_is_overwritten_right_behind_the_store(unit_asm):
     """A buffer_store_dwordx3/x4 reads its data registers some cycles after it issues.  The compiler's hazard model
     (GCNHazardRecognizer::createsVALUHazard) inserts wait states only when the store's soffset is an immediate; with a REGISTER
     soffset it inserts none -- and on a loaded MI355X the fused sweep+measure kernel, whose bit counts overwrote the data
@@ -103,17 +105,7 @@ def test_no_vector_store_data_is_overwritten_right_behind_the_store(device_asm, 
     registers within 8 instructions of it: ANY instruction whose destination overlaps them counts (vector ALU, LDS reads, memory
     loads, accumulator moves), and a branch inside the window is followed on BOTH paths (fall-through: one slot; taken: four slots,
     the instruction fetch is redirected); a branch to a label the scan cannot find fails the test."""
-    texts = {"isingmc.hip": device_asm}
-    procs = []
-    for name in HIP_SOURCES:   # every other translation unit that may hold device code
-        if name == "isingmc.hip" or not name.endswith(".hip"):
-            continue
-        out = tmp_path / (name + ".s")
-        procs.append((name, out, subprocess.Popen([HIPCC] + ASM_FLAGS + ["-o", str(out), os.path.join(ROOT, "pyisingmontecarlo_amd", "csrc", name)],
-                                                  stderr=subprocess.DEVNULL)))
-    for name, out, proc in procs:
-        assert proc.wait() == 0, name
-        texts[name] = out.read_text()
+    texts = unit_asm
     store = re.compile(r"\s(buffer_store_dwordx[34])\s+v\[(\d+):(\d+)\],\s*\S+,\s*s\[\d+:\d+\],\s*(\S+)")
     dest = re.compile(r"^(\w+)\s+(?:v(\d+)\b|v\[(\d+):(\d+)\]|a(\d+)\b|a\[(\d+):(\d+)\])")   # first operand = destination
     no_dest = ("buffer_store", "global_store", "flat_store", "ds_write", "ds_add", "ds_sub", "ds_max", "ds_min", "ds_and", "ds_or", "ds_xor",
@@ -162,3 +154,28 @@ def test_no_vector_store_data_is_overwritten_right_behind_the_store(device_asm, 
 
             scan(i + 1, 8, set())
     assert stores >= 4, "no register-offset vector stores found: has the pattern of this test gone stale?"
+
+
+HOST_UNITS = ["core.hip", "graph.hip", "isingmc.hip", "nonlocal.hip", "overlaps.hip", "best.hip", "sampling.hip", "tempering.hip", "population.hip"]
+
+
+def test_every_kernel_is_compiled_in_exactly_one_unit(unit_asm):
+    """Kernels live in *_kernels.hip units behind plain launchers.  A header that defines a kernel and reaches a second unit (through
+    internal.hpp, say) compiles a copy of that kernel into the unit's code object: dead device code, and one more place where the
+    register allocation of a tuned kernel could drift unseen.  Across the library every kernel symbol occurs in exactly one unit, the
+    host units hold none, and debug.hip holds its clock probe alone."""
+    where = {}
+    for name, text in unit_asm.items():
+        for sym in re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", text, re.M):
+            where.setdefault(sym, []).append(name)
+    for kernel, unit in (("lat_sweep_loop_kernel", "lattice_kernels.hip"), ("gen_sweep_kernel", "general_kernels.hip"),
+                         ("pk_sweep_kernel", "packed_kernels.hip"), ("pt_swap_kernel", "tempering_kernels.hip")):
+        assert any(kernel in sym and units == [unit] for sym, units in where.items()), f"{kernel} not found in {unit}: has the pattern of this test gone stale?"
+    twice = {sym: units for sym, units in where.items() if len(units) != 1}
+    assert not twice, twice
+    for name in HOST_UNITS:
+        assert name in unit_asm, name
+        held = [sym for sym, units in where.items() if name in units]
+        assert not held, f"{name} compiles device code: {held}"
+    probe = [sym for sym, units in where.items() if "debug.hip" in units]
+    assert len(probe) == 1 and "clock_probe_kernel" in probe[0], probe

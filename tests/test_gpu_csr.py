@@ -190,7 +190,7 @@ def test_rb_rule(capi, oracle, shape, R, replicas):
 
 
 def test_grid_cut(capi, oracle):
-    """32768 + 5 replicas at RB = 1: launch_gen_class and the measurement cut the replica range at 32768 grid rows and offset
+    """32768 + 5 replicas at RB = 1: launch_gen_timestep and the measurement cut the replica range at 32768 grid rows and offset
     keys, betas, states and partial sums; per-replica betas.  Every replica equals the RB = 8 run (one launch)."""
     g = CR.one_block_graph()
     R = 32768 + 5
