@@ -512,6 +512,13 @@ int isingmc_pa_reset_families(isingmc_states *states);
 int isingmc_debug_shader_clock(isingmc_states *states, size_t timesteps, double beta, double probe_ms,
                                double *ghz_out);
 
+/* ---- test hook (no reference counterpart) -------------------------------------------------------------
+ * The device blocks and pinned host blocks that graphs, containers and running calls of this process hold
+ * at the moment, taken from the library's block caches (idle blocks do not count; with
+ * ISINGMC_NO_ALLOC_CACHE=1 nothing is tracked and both are 0).  Equal counts before an object is created
+ * and after it is destroyed: every block it took has come back. */
+int isingmc_debug_live_blocks(size_t *device_blocks_out, size_t *pinned_blocks_out);
+
 #ifdef __cplusplus
 }
 #endif

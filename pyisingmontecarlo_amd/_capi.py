@@ -115,6 +115,7 @@ _PROTOTYPES = {
     "isingmc_states_stream": (C.c_int, [_vp, C.POINTER(_vp)]),
     "isingmc_synchronize": (C.c_int, [_vp]),
     "isingmc_debug_shader_clock": (C.c_int, [_vp, C.c_size_t, C.c_double, C.c_double, C.POINTER(C.c_double)]),
+    "isingmc_debug_live_blocks": (C.c_int, [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
 
@@ -349,6 +350,13 @@ class PtGroup:
 def release_cached_resources():
     """Hand the library's idle device blocks, pinned host blocks, streams and events back to the runtime; bytes released."""
     return int(lib().isingmc_release_cached_resources())
+
+
+def debug_live_blocks():
+    """(device blocks, pinned host blocks) that owners inside the library hold right now (the caches' idle blocks not counted)."""
+    dev, pinned = C.c_size_t(), C.c_size_t()
+    _check(lib().isingmc_debug_live_blocks(C.byref(dev), C.byref(pinned)))
+    return dev.value, pinned.value
 
 
 class Graph:

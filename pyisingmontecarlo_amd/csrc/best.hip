@@ -38,20 +38,17 @@ static int best_reserve(isingmc_states *s)
     const size_t words = best_state_size(s);
     if (s->d_best_state && s->best_state_words == words && s->best_cap == s->R) return ISINGMC_OK;
     HIP_TRY(stream_quiesce(s->stream)); // recycled blocks: nothing enqueued may still use the old ones
-    for (void **p : {(void **)&s->d_best_state, (void **)&s->d_best_e, (void **)&s->d_best_t, (void **)&s->d_best_energy, (void **)&s->d_best_flags,
-                     (void **)&s->d_best_count}) {
-        if (*p) (void)cached_free(*p);
-        *p = nullptr;
-    }
+    s->d_best_state.reset(); s->d_best_e.reset(); s->d_best_t.reset();
+    s->d_best_energy.reset(); s->d_best_flags.reset(); s->d_best_count.reset();
     s->best_cap = s->best_state_words = 0;
     // Padding positions and the bits of a packed group this container does not own take whatever the copies bring along: they
     // have no defined value.  The buffer is cleared once, so that isingmc_best_raw_state is deterministic.
-    TRY(dev_alloc(&s->d_best_state, words));
-    TRY(dev_alloc(&s->d_best_e, s->R));
-    TRY(dev_alloc(&s->d_best_t, s->R));
-    TRY(dev_alloc(&s->d_best_energy, s->R));
-    TRY(dev_alloc(&s->d_best_flags, s->packed ? s->groups : s->R));
-    TRY(dev_alloc(&s->d_best_count, 1));
+    TRY(dev_alloc(s->d_best_state, words));
+    TRY(dev_alloc(s->d_best_e, s->R));
+    TRY(dev_alloc(s->d_best_t, s->R));
+    TRY(dev_alloc(s->d_best_energy, s->R));
+    TRY(dev_alloc(s->d_best_flags, s->packed ? s->groups : s->R));
+    TRY(dev_alloc(s->d_best_count, 1));
     HIP_TRY(hipMemsetAsync(s->d_best_state, 0, words * sizeof(uint32_t), s->stream));
     s->best_state_words = words;
     s->best_cap = s->R;

@@ -80,9 +80,9 @@ hipError_t cached_malloc(void **out, size_t bytes)
     return err;
 }
 
-hipError_t cached_free(void *p)
+void cached_free(void *p)
 {
-    if (!p) return hipSuccess;
+    if (!p) return;
     DevCache &c = dev_cache();
     {
         std::lock_guard<std::mutex> lock(c.mu);
@@ -94,11 +94,11 @@ hipError_t cached_free(void *p)
                 c.idle.size() < DevCache::MAX_COUNT) {
                 c.idle.emplace(key, p);
                 c.idle_bytes += key.second;
-                return hipSuccess;
+                return;
             }
         }
     }
-    return hipFree(p);
+    (void)hipFree(p);
 }
 
 // ... and pinned host blocks (the staging buffers of get_states / the sampling pipeline: pinning and unpinning cost ~150 us each)
@@ -138,9 +138,9 @@ hipError_t cached_host_malloc(void **out, size_t bytes)
     return err;
 }
 
-hipError_t cached_host_free(void *p)
+void cached_host_free(void *p)
 {
-    if (!p) return hipSuccess;
+    if (!p) return;
     HostCache &c = host_cache();
     {
         std::lock_guard<std::mutex> lock(c.mu);
@@ -151,11 +151,11 @@ hipError_t cached_host_free(void *p)
             if (!dev_cache_off() && bytes <= (size_t(64) << 20) && c.idle_bytes + bytes <= (size_t(256) << 20) && c.idle.size() < 64) {
                 c.idle.emplace(bytes, p);
                 c.idle_bytes += bytes;
-                return hipSuccess;
+                return;
             }
         }
     }
-    return hipHostFree(p);
+    (void)hipHostFree(p);
 }
 
 // Streams are recycled the same way (creating and destroying the three streams of a replica container took ~1.5 ms of that
@@ -335,6 +335,20 @@ extern "C" size_t isingmc_release_cached_resources(void)
     for (hipEvent_t ev : events) (void)hipEventDestroy(ev);
     (void)hipGetLastError();
     return bytes;
+}
+
+extern "C" int isingmc_debug_live_blocks(size_t *device_blocks_out, size_t *pinned_blocks_out)
+{
+    if (!device_blocks_out || !pinned_blocks_out) return fail(ISINGMC_ERR_INVALID, "NULL argument");
+    {
+        DevCache &c = dev_cache();
+        std::lock_guard<std::mutex> lock(c.mu);
+        *device_blocks_out = c.live.size();
+    }
+    HostCache &c = host_cache();
+    std::lock_guard<std::mutex> lock(c.mu);
+    *pinned_blocks_out = c.live.size();
+    return ISINGMC_OK;
 }
 
 extern "C" int isingmc_device_count(int *count)

@@ -10,6 +10,7 @@
 //   tempering.hip  on-stream parallel tempering, the in-process ladder group (RCCL through dlopen)
 //   population.hip population annealing: the on-stream resampling step (isingmc_pa_*)
 //   debug.hip      shader-clock probe
+// Device and pinned blocks are held in the handles of owned_block.hpp, which free them: no unit frees a block by hand.
 // Every kernel but the probe's is defined in a *_kernels.hip unit of its own and launched through the plain C++ launchers that the
 // headers below declare; none of them defines a kernel.
 #pragma once
@@ -45,6 +46,7 @@
 #include "mc_types.hpp"
 #include "overlap_class_kernels.hpp"
 #include "overlap_kernels.hpp"
+#include "owned_block.hpp"
 #include "real_types.hpp"
 #include "spread_types.hpp"
 #include "strip_types.hpp"
@@ -73,11 +75,9 @@ IM_INTERNAL int fail(int code, const std::string &msg); // sets the calling thre
 
 
 // ---- caches (core.hip): device blocks, pinned host blocks, streams, events are recycled; every owner drains its streams before
-// it hands a block back (hipFree used to synchronise the device)
+// it hands a block back (hipFree used to synchronise the device).  Blocks are held in the handles of owned_block.hpp, which free them.
 IM_INTERNAL hipError_t cached_malloc(void **out, size_t bytes);
-IM_INTERNAL hipError_t cached_free(void *p);
 IM_INTERNAL hipError_t cached_host_malloc(void **out, size_t bytes);
-IM_INTERNAL hipError_t cached_host_free(void *p);
 IM_INTERNAL hipError_t pooled_stream_create(hipStream_t *out);
 IM_INTERNAL hipError_t stream_quiesce(hipStream_t st); // a query when everything has completed, else a synchronisation
 IM_INTERNAL void pooled_stream_destroy(hipStream_t st);
@@ -211,13 +211,12 @@ struct isingmc_graph {
     Options opt;                          // the environment's switches when the graph was created
     std::vector<uint32_t> class_real_end; // per colour class: end of its real sites (the padding follows)
     int n_cu = 256;                       // compute units of the device (queried once, at creation)
-    std::vector<void *> dev_allocs;
+    std::vector<DevBlock<unsigned char>> dev_allocs;
 
     ~isingmc_graph()
     {
         (void)hipSetDevice(device);
-        (void)hipDeviceSynchronize(); // the blocks are recycled (cached_free): no kernel may still be reading the graph
-        for (void *p : dev_allocs) (void)cached_free(p);
+        (void)hipDeviceSynchronize(); // the blocks are recycled when dev_allocs goes: no kernel may still be reading the graph
     }
 };
 
@@ -232,8 +231,8 @@ struct isingmc_states {
     isingmc_graph *g = nullptr;
     Options opt; // the environment's switches when the container was created (isingmc_states_set_option changes one)
     size_t R = 0, cap = 0;
-    uint32_t *d_state = nullptr;
-    uint2 *d_keys = nullptr;
+    DevBlock<uint32_t> d_state;
+    DevBlock<uint2> d_keys;
     uint64_t t = 0; // absolute timestep = Philox counter
     hipStream_t stream = nullptr;
     std::vector<hipStream_t> lanes; // sweep launches of disjoint replica blocks alternate over these (see run_steps)
@@ -247,154 +246,126 @@ struct isingmc_states {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool has_betas = false;
     std::vector<double> betas;
-    LatThr *d_thr = nullptr;
-    LatThrMC *d_thr_mc = nullptr; // per-replica thresholds of the multi-class kernels (has_betas on a field / open lattice)
-    double *d_beta = nullptr;
+    DevBlock<LatThr> d_thr;
+    DevBlock<LatThrMC> d_thr_mc; // per-replica thresholds of the multi-class kernels (has_betas on a field / open lattice)
+    DevBlock<double> d_beta;
     // measurement scratch
-    unsigned long long *d_meas = nullptr; // lattice: [R][2]
+    DevBlock<unsigned long long> d_meas; // lattice: [R][2]
     bool meas_zero = false;               // d_meas is known to be all zero (left so by the tempering measurement)
-    double *d_pe = nullptr, *d_oe = nullptr;
-    long long *d_pm = nullptr, *d_om = nullptr;
+    DevBlock<double> d_pe, d_oe;
+    DevBlock<long long> d_pm, d_om;
     uint32_t n_partials = 0;
     // replica-packed general path: one word per position = 32 replicas of a group
     bool packed = false;
     size_t groups = 0;
     size_t pk_bit0 = 0; // replica r of this shard is bit (r + pk_bit0) % 32 of group (r + pk_bit0) / 32 (shards cut GLOBAL groups)
     size_t pk_slots() const { return 32 * groups; } // counter slots: one per (group, bit), owned or not
-    uint32_t *d_tab = nullptr; // threshold tables [groups or steps][PK_TAB_WORDS]
+    DevBlock<uint32_t> d_tab; // threshold tables [groups or steps][PK_TAB_WORDS]
     // one-degree packed kernels: the wave-uniform halves of the Philox calls of timesteps [pk_philox_t0, + pk_philox_steps) for
     // pk_philox_groups groups (packed_types.hpp); kept across calls -- a tempering round of ten timesteps does not pay a table launch
-    uint32_t *d_pk_philox = nullptr;
+    DevBlock<uint32_t> d_pk_philox;
     uint64_t pk_philox_t0 = 0;
     size_t pk_philox_steps = 0, pk_philox_groups = 0;
     bool rj = false;           // packed container on the real-coupling path (real_kernels.hpp) instead of the bit-sliced one
-    RjBeta *d_rj_betas = nullptr; // per-replica acceptance scales [32 groups] (has_betas)
-    unsigned long long *d_pk_slot_thr = nullptr; // on-stream tempering on the bit-sliced packed path: T_m per slot [32 groups][PK_MAX_DEG]
+    DevBlock<RjBeta> d_rj_betas; // per-replica acceptance scales [32 groups] (has_betas)
+    DevBlock<unsigned long long> d_pk_slot_thr; // on-stream tempering on the bit-sliced packed path: T_m per slot [32 groups][PK_MAX_DEG]
     size_t n_total = 0, first = 0; // this container is the shard [first, first + R) of n_total experiments
     // persistent strip kernel (strip_kernels.hpp): halo granules, error word, tag epoch
-    unsigned long long *d_halo = nullptr;
+    DevBlock<unsigned long long> d_halo;
     size_t halo_cap = 0; // granules allocated
-    uint32_t *d_strip_err = nullptr;
+    DevBlock<uint32_t> d_strip_err;
     uint32_t strip_epoch = 0;
-    unsigned long long *d_pt_mail = nullptr, *d_pt_round_counts = nullptr; // in-kernel exchange rounds (StripLadder)
-    uint32_t *d_pt_perm2 = nullptr;
-    unsigned long long *d_strip_fin = nullptr; // [cap] final-measurement counters of the strip kernel (zero between launches)
+    DevBlock<unsigned long long> d_pt_mail, d_pt_round_counts; // in-kernel exchange rounds (StripLadder)
+    DevBlock<uint32_t> d_pt_perm2;
+    DevBlock<unsigned long long> d_strip_fin; // [cap] final-measurement counters of the strip kernel (zero between launches)
     bool strip_test_failed = false; // ISINGMC_STRIP_TEST_FAIL_ONCE has fired for this object
     bool strip_disabled = false;    // a strip launch of this object timed out once: the per-colour launches serve it from then on
-    uint32_t *d_snapshot = nullptr; // the planes a synchronous call started from (restored when a strip launch gives up)
+    DevBlock<uint32_t> d_snapshot; // the planes a synchronous call started from (restored when a strip launch gives up)
     size_t snapshot_cap = 0;
     bool meas_fresh = false; // the tempering send buffer holds the energies of the CURRENT configurations (written by the last strip launch)
     // sampling pipeline (isingmc_run_sampling): two slabs of samples in flight
     hipStream_t copy_stream = nullptr;
     hipEvent_t sample_ready[2] = {nullptr, nullptr}, sample_copied[2] = {nullptr, nullptr};
-    uint32_t *d_samples[2] = {nullptr, nullptr}, *h_samples[2] = {nullptr, nullptr}; // h_*: pinned
-    unsigned long long *d_sample_counts[2] = {nullptr, nullptr}, *h_counts[2] = {nullptr, nullptr};
-    double *d_sample_e[2] = {nullptr, nullptr}, *h_e[2] = {nullptr, nullptr};
-    long long *d_sample_m = nullptr;
+    DevBlock<uint32_t> d_samples[2];
+    PinnedBlock<uint32_t> h_samples[2];
+    DevBlock<unsigned long long> d_sample_counts[2];
+    PinnedBlock<unsigned long long> h_counts[2];
+    DevBlock<double> d_sample_e[2];
+    PinnedBlock<double> h_e[2];
+    DevBlock<long long> d_sample_m;
     size_t sample_cap_words = 0, sample_cap_counts = 0, sample_cap_e = 0;
     // on-stream parallel tempering (isingmc_pt_*)
     bool pt_attached = false;
     PtDev pt{};
-    double *d_pt_ladder = nullptr, *d_pt_local = nullptr, *d_pt_all = nullptr;
-    uint64_t *d_pt_ladder_thr = nullptr;
-    uint32_t *d_pt_perm = nullptr;
-    unsigned long long *d_pt_counters = nullptr;
+    DevBlock<double> d_pt_ladder, d_pt_local, d_pt_all;
+    DevBlock<uint64_t> d_pt_ladder_thr;
+    DevBlock<uint32_t> d_pt_perm;
+    DevBlock<unsigned long long> d_pt_counters;
     size_t pt_per = 0, pt_world = 1;
     std::vector<double> ladder_betas; // host copy of d_pt_ladder (two ladders are compared without a device read)
     // Swendsen-Wang cluster steps (cluster_kernels.hpp): timestep t is one when cluster_every > 0 and t % cluster_every == cluster_every - 1
     size_t cluster_every = 0;
-    uint32_t *d_cl_stats = nullptr; // [cl_stats_cap][2]: clusters, largest cluster of the last cluster step (packed: per counter slot)
+    DevBlock<uint32_t> d_cl_stats; // [cl_stats_cap][2]: clusters, largest cluster of the last cluster step (packed: per counter slot)
     size_t cl_stats_cap = 0;
     bool cl_have_stats = false;
     // isoenergetic cluster moves between the replicas (2 p, 2 p + 1): timestep t is one when icm_every > 0 and
     // t % icm_every == icm_every - 1; never on together with cluster_every
     size_t icm_every = 0;
-    uint32_t *d_icm_stats = nullptr; // [icm_stats_cap][2] clusters, largest cluster, then [icm_stats_cap] q = -1 sites: the last ICM step of every pair
+    DevBlock<uint32_t> d_icm_stats; // [icm_stats_cap][2] clusters, largest cluster, then [icm_stats_cap] q = -1 sites: the last ICM step of every pair
     size_t icm_stats_cap = 0;
     bool icm_have_stats = false;
     // isoenergetic cluster moves between this container and another one (isingmc_icm_between): everything below
     // belongs to the FIRST container of the call and stays with it, so that a call only enqueues
-    uint32_t *d_icmb_work = nullptr;  // labelling workspace of icmb_batch pairs (cluster_words_per_replica each); packed containers
+    DevBlock<uint32_t> d_icmb_work; // labelling workspace of icmb_batch pairs (cluster_words_per_replica each); packed containers
     size_t icmb_batch = 0;            // (DESIGN.md S13): of icmb_batch pair BLOCKS (pk_between_words_per_block each)
-    uint32_t *d_icmb_inv = nullptr;   // packed containers: (local group, bit) -> pair of the call, this container's groups first,
+    DevBlock<uint32_t> d_icmb_inv;  // packed containers: (local group, bit) -> pair of the call, this container's groups first,
     size_t icmb_inv_cap = 0;          // then the other one's (words)
-    uint32_t *d_icmb_slots = nullptr; // [2][icmb_cap] slot tables of the host-table form
-    uint32_t *d_icmb_stats = nullptr; // [icmb_cap][2] clusters, largest cluster, then [icmb_cap] q = -1 sites: the last call
+    DevBlock<uint32_t> d_icmb_slots; // [2][icmb_cap] slot tables of the host-table form
+    DevBlock<uint32_t> d_icmb_stats; // [icmb_cap][2] clusters, largest cluster, then [icmb_cap] q = -1 sites: the last call
     size_t icmb_cap = 0, icmb_pairs = 0;
     bool icmb_have_stats = false;
     hipEvent_t icmb_ev[2] = {nullptr, nullptr}; // the other container's stream has arrived / this container's launches are enqueued
     // population annealing (isingmc_pa_*): everything below is allocated by the first resampling and stays
-    uint32_t *d_pa_state = nullptr; // the second state buffer the gathers write into: as large as d_state (pa_state_words words)
+    DevBlock<uint32_t> d_pa_state; // the second state buffer the gathers write into: as large as d_state (pa_state_words words)
     size_t pa_state_words = 0;
     size_t pa_cap = 0;              // replicas the tables below hold
-    double *d_pa_energy = nullptr;          // [pa_cap]
-    unsigned long long *d_pa_cum = nullptr; // [pa_cap] weights, then their inclusive prefix sums; pa_scan_blocks(pa_cap) block sums follow
-    uint32_t *d_pa_src = nullptr;           // [pa_cap] source table of the last isingmc_pa_resample
-    uint32_t *d_pa_user_src = nullptr;      // [pa_cap] the caller's table of the last isingmc_pa_apply_sources
+    DevBlock<double> d_pa_energy;          // [pa_cap]
+    DevBlock<unsigned long long> d_pa_cum; // [pa_cap] weights, then their inclusive prefix sums; pa_scan_blocks(pa_cap) block sums follow
+    DevBlock<uint32_t> d_pa_src;           // [pa_cap] source table of the last isingmc_pa_resample
+    DevBlock<uint32_t> d_pa_user_src;      // [pa_cap] the caller's table of the last isingmc_pa_apply_sources
     const StepPreset *step_preset = nullptr; // set around a run_steps call by isingmc_pa_run: the tables of its beta are on the device
-    uint32_t *d_pa_family = nullptr, *d_pa_family2 = nullptr; // [pa_cap] family of every slot, and the buffer its gather writes into
-    PaRecord *d_pa_record = nullptr;
+    DevBlock<uint32_t> d_pa_family, d_pa_family2; // [pa_cap] family of every slot, and the buffer its gather writes into
+    DevBlock<PaRecord> d_pa_record;
     bool pa_have_record = false;    // an isingmc_pa_resample has been enqueued
     bool pa_families_set = false;   // d_pa_family holds the table (else: the identity)
     // each replica's lowest-energy configuration (isingmc_best_*): allocated when tracking is switched on (or by the
     // first isingmc_best_update) for the replicas the container holds then, and kept
     size_t best_every = 0;            // an update follows every timestep after which t % best_every == 0; 0 = off
-    uint32_t *d_best_state = nullptr; // as large as d_state, same layout; padding positions and unowned bits of a packed container
+    DevBlock<uint32_t> d_best_state; // as large as d_state, same layout; padding positions and unowned bits of a packed container
     size_t best_state_words = 0;      // hold no defined value (cleared once, so that the raw read-out is deterministic)
     size_t best_cap = 0;              // replicas the records below hold
-    double *d_best_e = nullptr;                // [best_cap] records, +inf before the first update
-    unsigned long long *d_best_t = nullptr;    // [best_cap] the timestep each record was set at
-    double *d_best_energy = nullptr;           // [best_cap] the energies an update measures
-    uint32_t *d_best_flags = nullptr;          // a flag per replica (checkerboard) / an improvement mask per group (packed)
-    unsigned long long *d_best_count = nullptr; // improvements so far
+    DevBlock<double> d_best_e;                // [best_cap] records, +inf before the first update
+    DevBlock<unsigned long long> d_best_t;    // [best_cap] the timestep each record was set at
+    DevBlock<double> d_best_energy;           // [best_cap] the energies an update measures
+    DevBlock<uint32_t> d_best_flags;          // a flag per replica (checkerboard) / an improvement mask per group (packed)
+    DevBlock<unsigned long long> d_best_count; // improvements so far
     bool strip_guard = false; // inside with_strip_retry: a strip launch is checked before an update may keep what it left
 
     ~isingmc_states()
     {
         if (!g) return;
         (void)hipSetDevice(g->device);
-        // the blocks below go back to the cache, where the next request may pick them up at once: nothing of this object may
-        // still be running (hipFree used to wait for the whole device)
+        // the members' blocks go back to the cache after this body, where the next request may pick them up at once: nothing of
+        // this object may still be running (hipFree used to wait for the whole device)
         if (stream) (void)stream_quiesce(stream);
         for (auto st : lanes) (void)stream_quiesce(st);
         if (copy_stream) (void)stream_quiesce(copy_stream);
-        for (void *p : {(void *)d_state, (void *)d_keys, (void *)d_thr, (void *)d_beta, (void *)d_meas,
-                        (void *)d_pe, (void *)d_oe, (void *)d_pm, (void *)d_om})
-            if (p) (void)cached_free(p);
-        if (d_tab) (void)cached_free(d_tab);
-        if (d_pk_philox) (void)cached_free(d_pk_philox);
-        if (d_rj_betas) (void)cached_free(d_rj_betas);
-        if (d_pk_slot_thr) (void)cached_free(d_pk_slot_thr);
-        if (d_thr_mc) (void)cached_free(d_thr_mc);
-        if (d_cl_stats) (void)cached_free(d_cl_stats);
-        if (d_icm_stats) (void)cached_free(d_icm_stats);
-        for (void *p : {(void *)d_icmb_work, (void *)d_icmb_slots, (void *)d_icmb_stats, (void *)d_icmb_inv})
-            if (p) (void)cached_free(p);
-        for (void *p : {(void *)d_pa_state, (void *)d_pa_energy, (void *)d_pa_cum, (void *)d_pa_src, (void *)d_pa_user_src, (void *)d_pa_family, (void *)d_pa_family2,
-                        (void *)d_pa_record})
-            if (p) (void)cached_free(p);
-        for (void *p : {(void *)d_best_state, (void *)d_best_e, (void *)d_best_t, (void *)d_best_energy, (void *)d_best_flags, (void *)d_best_count})
-            if (p) (void)cached_free(p);
         for (auto ev : icmb_ev) pooled_event_destroy(ev, true);
         for (int b = 0; b < 2; b++) {
-            for (void *p : {(void *)d_samples[b], (void *)d_sample_counts[b], (void *)d_sample_e[b]})
-                if (p) (void)cached_free(p);
-            for (void *p : {(void *)h_samples[b], (void *)h_counts[b], (void *)h_e[b]})
-                if (p) (void)cached_host_free(p);
             pooled_event_destroy(sample_ready[b], true);
             pooled_event_destroy(sample_copied[b], true);
         }
-        if (d_sample_m) (void)cached_free(d_sample_m);
         pooled_stream_destroy(copy_stream);
-        if (d_halo) (void)cached_free(d_halo);
-        if (d_strip_err) (void)cached_free(d_strip_err);
-        if (d_strip_fin) (void)cached_free(d_strip_fin);
-        if (d_snapshot) (void)cached_free(d_snapshot);
-        for (void *p : {(void *)d_pt_mail, (void *)d_pt_round_counts, (void *)d_pt_perm2})
-            if (p) (void)cached_free(p);
-        for (void *p : {(void *)d_pt_ladder, (void *)d_pt_local, (void *)d_pt_all, (void *)d_pt_ladder_thr, (void *)d_pt_perm,
-                        (void *)d_pt_counters})
-            if (p) (void)cached_free(p);
         for (auto st : lanes) pooled_stream_destroy(st);
         for (auto ev : lane_events) pooled_event_destroy(ev, true);
         pooled_event_destroy(fork_event, true);
@@ -404,22 +375,37 @@ struct isingmc_states {
     }
 };
 
+// `count` elements into `out`; whatever `out` held is freed, but only once the new block is there.  The caller has made sure that
+// nothing enqueued reads the old block.
 template <typename T>
-static int dev_alloc(T **out, size_t count)
+static int dev_alloc(DevBlock<T> &out, size_t count)
+{
+    void *p = nullptr;
+    HIP_TRY(cached_malloc(&p, std::max<size_t>(count, 1) * sizeof(T)));
+    out = DevBlock<T>(static_cast<T *>(p));
+    return ISINGMC_OK;
+}
+
+// ... `count` elements of any type that `owner` keeps until it goes (a graph's tables, the scratch of one call)
+using DevBlocks = std::vector<DevBlock<unsigned char>>;
+template <typename T>
+static int dev_alloc(DevBlocks &owner, T **out, size_t count)
 {
     *out = nullptr;
-    HIP_TRY(cached_malloc(reinterpret_cast<void **>(out), std::max<size_t>(count, 1) * sizeof(T)));
+    DevBlock<unsigned char> b;
+    TRY(dev_alloc(b, std::max<size_t>(count, 1) * sizeof(T)));
+    *out = reinterpret_cast<T *>(b.get());
+    owner.push_back(std::move(b));
     return ISINGMC_OK;
 }
 
 // A device block that a container owns takes another size: nothing enqueued on `stream` may still use the old block, which goes
 // back to the cache.  `count` elements, recorded as *cap = new_cap (the owner's unit); a failed allocation leaves {nullptr, 0}.
 template <typename T>
-static int dev_regrow(hipStream_t stream, T **block, size_t *cap, size_t count, size_t new_cap)
+static int dev_regrow(hipStream_t stream, DevBlock<T> &block, size_t *cap, size_t count, size_t new_cap)
 {
     HIP_TRY(stream_quiesce(stream));
-    if (*block) HIP_TRY(cached_free(*block));
-    *block = nullptr;
+    block.reset();
     *cap = 0;
     TRY(dev_alloc(block, count));
     *cap = new_cap;
@@ -439,30 +425,19 @@ static int read_back(isingmc_states *s, std::vector<T> &h, const T *d, size_t n)
 // device scratch of one API call: freed on every exit path, after the stream has drained
 struct DeviceScratch {
     hipStream_t stream;
-    std::vector<void *> ptrs;
+    DevBlocks blocks;
     explicit DeviceScratch(hipStream_t st) : stream(st) {}
     DeviceScratch(const DeviceScratch &) = delete;
-    ~DeviceScratch()
-    {
-        if (ptrs.empty()) return;
-        (void)hipStreamSynchronize(stream);
-        for (void *p : ptrs) (void)cached_free(p);
-    }
+    ~DeviceScratch() { if (!blocks.empty()) (void)hipStreamSynchronize(stream); }
     template <typename T>
-    int alloc(T **out, size_t count)
-    {
-        TRY(dev_alloc(out, count));
-        ptrs.push_back(*out);
-        return ISINGMC_OK;
-    }
+    int alloc(T **out, size_t count) { return dev_alloc(blocks, out, count); }
 };
 
 template <typename T>
 static int graph_upload(isingmc_graph *g, const T **dst, const std::vector<T> &src)
 {
     T *d = nullptr;
-    TRY(dev_alloc(&d, src.size()));
-    g->dev_allocs.push_back(d);
+    TRY(dev_alloc(g->dev_allocs, &d, src.size()));
     if (!src.empty()) HIP_TRY(hipMemcpy(d, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
     *dst = d;
     return ISINGMC_OK;

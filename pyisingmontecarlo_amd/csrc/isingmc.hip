@@ -51,16 +51,10 @@ static int reserve(isingmc_states *s, size_t cap)
 {
     if (cap <= s->cap) return ISINGMC_OK;
     const isingmc_graph *g = s->g;
-    uint32_t *d_state = nullptr;
-    uint2 *d_keys = nullptr;
-    struct Undo { // a failure below must not leak the new buffers
-        uint32_t **a;
-        uint2 **b;
-        bool armed = true;
-        ~Undo() { if (armed) { if (*a) (void)cached_free(*a); if (*b) (void)cached_free(*b); } }
-    } undo{&d_state, &d_keys};
-    TRY(dev_alloc(&d_state, cap * g->state_words));
-    TRY(dev_alloc(&d_keys, cap));
+    DevBlock<uint32_t> d_state; // a failure below frees the new buffers
+    DevBlock<uint2> d_keys;
+    TRY(dev_alloc(d_state, cap * g->state_words));
+    TRY(dev_alloc(d_keys, cap));
     // enqueue-only calls (isingmc_pt_*, the sampling loop) may still be running on the engine's non-blocking stream, which the
     // null-stream copies below are NOT ordered against; and the old blocks go back to the cache at the end
     HIP_TRY(stream_quiesce(s->stream));
@@ -71,25 +65,22 @@ static int reserve(isingmc_states *s, size_t cap)
         HIP_TRY(hipMemcpy(d_keys, s->d_keys, s->R * sizeof(uint2), hipMemcpyDeviceToDevice));
         HIP_TRY(hipDeviceSynchronize()); // device-to-device copies may still run when hipMemcpy returns; the old blocks are recycled below
     }
-    undo.armed = false;
-    for (void *p : {(void *)s->d_state, (void *)s->d_keys, (void *)s->d_thr, (void *)s->d_beta, (void *)s->d_meas,
-                    (void *)s->d_pe, (void *)s->d_oe, (void *)s->d_pm, (void *)s->d_om})
-        if (p) (void)cached_free(p);
-    s->d_state = d_state;
-    s->d_keys = d_keys;
-    s->d_thr = nullptr; s->d_beta = nullptr; s->d_meas = nullptr;
-    s->d_pe = nullptr; s->d_oe = nullptr; s->d_pm = nullptr; s->d_om = nullptr;
-    TRY(dev_alloc(&s->d_thr, cap));
-    TRY(dev_alloc(&s->d_beta, cap));
+    s->d_state = std::move(d_state);
+    s->d_keys = std::move(d_keys);
+    s->d_thr.reset(); s->d_beta.reset(); s->d_meas.reset(); // the old sizes go before the new ones come
+    s->d_pe.reset(); s->d_oe.reset(); s->d_pm.reset(); s->d_om.reset();
+    s->d_strip_fin.reset(); // [cap] too: launch_strip allocates it again
+    TRY(dev_alloc(s->d_thr, cap));
+    TRY(dev_alloc(s->d_beta, cap));
     if (g->kind == ISINGMC_KIND_LATTICE2D) {
-        TRY(dev_alloc(&s->d_meas, 2 * cap));
+        TRY(dev_alloc(s->d_meas, 2 * cap));
         s->meas_zero = false;
     } else {
         s->n_partials = (g->gdev.n_pos + 255) / 256;
-        TRY(dev_alloc(&s->d_pe, cap * s->n_partials));
-        TRY(dev_alloc(&s->d_pm, cap * s->n_partials));
-        TRY(dev_alloc(&s->d_oe, cap));
-        TRY(dev_alloc(&s->d_om, cap));
+        TRY(dev_alloc(s->d_pe, cap * s->n_partials));
+        TRY(dev_alloc(s->d_pm, cap * s->n_partials));
+        TRY(dev_alloc(s->d_oe, cap));
+        TRY(dev_alloc(s->d_om, cap));
     }
     s->cap = cap;
     return ISINGMC_OK;
@@ -258,9 +249,8 @@ int set_betas(isingmc_states *s, const double *beta_per_replica, bool all_equal)
         std::vector<LatThrMC> thr(s->R);
         for (size_t r = 0; r < s->R; r++) thr[r] = lattice_thresholds_mc(s->g, s->betas[r]);
         HIP_TRY(stream_quiesce(s->stream)); // the old table may still be read by enqueued timesteps; its block is recycled
-        if (s->d_thr_mc) HIP_TRY(cached_free(s->d_thr_mc));
-        s->d_thr_mc = nullptr;
-        TRY(dev_alloc(&s->d_thr_mc, s->cap));
+        s->d_thr_mc.reset();
+        TRY(dev_alloc(s->d_thr_mc, s->cap));
         if (s->R) HIP_TRY(hipMemcpyAsync(s->d_thr_mc, thr.data(), s->R * sizeof(LatThrMC), hipMemcpyHostToDevice, s->stream));
     } else if (s->g->kind == ISINGMC_KIND_LATTICE2D) {
         std::vector<LatThr> thr(s->R);
@@ -354,9 +344,9 @@ static int pk_create(isingmc_states *s, const uint64_t *all_seeds, size_t first,
     s->pk_bit0 = first % 32;
     s->groups = (s->pk_bit0 + n + 31) / 32;
     s->R = s->cap = n;
-    TRY(dev_alloc(&s->d_state, s->groups * g->pk.n_pos));
-    TRY(dev_alloc(&s->d_keys, s->groups));
-    TRY(dev_alloc(&s->d_meas, 2 * s->pk_slots()));
+    TRY(dev_alloc(s->d_state, s->groups * g->pk.n_pos));
+    TRY(dev_alloc(s->d_keys, s->groups));
+    TRY(dev_alloc(s->d_meas, 2 * s->pk_slots()));
     s->meas_zero = false;
     std::vector<uint2> keys(s->groups);
     for (size_t k = 0; k < s->groups; k++) { // a group is keyed by the seed of its first GLOBAL replica
@@ -393,27 +383,26 @@ static int pk_append(isingmc_states *s, uint64_t seed, const uint8_t *initial_st
     const size_t slot = s->R;
     if (slot % 32 == 0) { // a new group
         const size_t groups = s->groups + 1;
-        uint32_t *d_state = nullptr;
-        uint2 *d_keys = nullptr;
-        unsigned long long *d_meas = nullptr;
-        TRY(dev_alloc(&d_state, groups * g->pk.n_pos));
-        struct Undo { void *a, **b, **c; bool armed = true; ~Undo() { if (armed) { (void)cached_free(a); if (*b) (void)cached_free(*b); if (*c) (void)cached_free(*c); } } }
-            undo{d_state, reinterpret_cast<void **>(&d_keys), reinterpret_cast<void **>(&d_meas)};
-        TRY(dev_alloc(&d_keys, groups));
-        TRY(dev_alloc(&d_meas, 2 * 32 * groups));
+        DevBlock<uint32_t> d_state; // a failure below frees the new buffers
+        DevBlock<uint2> d_keys;
+        DevBlock<unsigned long long> d_meas;
+        TRY(dev_alloc(d_state, groups * g->pk.n_pos));
+        TRY(dev_alloc(d_keys, groups));
+        TRY(dev_alloc(d_meas, 2 * 32 * groups));
         HIP_TRY(hipStreamSynchronize(s->stream));
         HIP_TRY(hipMemcpy(d_state, s->d_state, s->groups * g->pk.n_pos * sizeof(uint32_t), hipMemcpyDeviceToDevice));
         HIP_TRY(hipMemcpy(d_keys, s->d_keys, s->groups * sizeof(uint2), hipMemcpyDeviceToDevice));
         HIP_TRY(hipDeviceSynchronize()); // as in reserve(): the old blocks go back to the cache below
         const uint2 key = make_uint2(uint32_t(seed), uint32_t(seed >> 32));
         HIP_TRY(hipMemcpy(d_keys + s->groups, &key, sizeof key, hipMemcpyHostToDevice));
-        undo.armed = false;
-        (void)cached_free(s->d_state); (void)cached_free(s->d_keys); (void)cached_free(s->d_meas);
-        s->d_state = d_state; s->d_keys = d_keys; s->d_meas = d_meas;
+        s->d_state = std::move(d_state);
+        s->d_keys = std::move(d_keys);
+        s->d_meas = std::move(d_meas);
         s->meas_zero = false;
-        if (s->d_tab) { (void)cached_free(s->d_tab); s->d_tab = nullptr; }             // per-group tables: rebuilt by the next set_betas
-        if (s->d_pk_philox) { (void)cached_free(s->d_pk_philox); s->d_pk_philox = nullptr; s->pk_philox_steps = 0; } // rows per group count
-        if (s->d_rj_betas) { (void)cached_free(s->d_rj_betas); s->d_rj_betas = nullptr; }
+        s->d_tab.reset(); // per-group tables: rebuilt by the next set_betas
+        s->d_pk_philox.reset(); // rows per group count
+        s->pk_philox_steps = 0;
+        s->d_rj_betas.reset();
         HIP_TRY(pk_launch_init(s->stream, s->d_state, g->pk, s->d_keys, uint32_t(s->groups), 1));
         HIP_TRY(hipStreamSynchronize(s->stream));
         s->groups = groups;
@@ -453,7 +442,7 @@ static int pk_set_betas(isingmc_states *s)
             const size_t r = sl < s->pk_bit0 ? 0 : std::min(s->R - 1, sl - s->pk_bit0);
             rj_beta(s->betas[r], s->g->rj_k, &tab[sl].shift, &tab[sl].mant);
         }
-        if (!s->d_rj_betas) TRY(dev_alloc(&s->d_rj_betas, tab.size()));
+        if (!s->d_rj_betas) TRY(dev_alloc(s->d_rj_betas, tab.size()));
         HIP_TRY(hipStreamSynchronize(s->stream)); // no launch may still be reading the old scales
         HIP_TRY(hipMemcpy(s->d_rj_betas, tab.data(), tab.size() * sizeof(RjBeta), hipMemcpyHostToDevice));
         return ISINGMC_OK;
@@ -462,7 +451,7 @@ static int pk_set_betas(isingmc_states *s)
     for (size_t k = 0; k < s->groups; k++)
         pk_fill_table(tabs.data() + k * PK_TAB_WORDS, s->g->jabs,
                       [&](uint32_t r) { return s->betas[std::min(s->R - 1, 32 * k + r)]; }); // pk_bit0 == 0 (checked by the caller)
-    if (!s->d_tab) TRY(dev_alloc(&s->d_tab, tabs.size())); // groups is fixed for the life of a packed container (no append): allocated once
+    if (!s->d_tab) TRY(dev_alloc(s->d_tab, tabs.size())); // groups is fixed for the life of a packed container (no append): allocated once
     HIP_TRY(hipStreamSynchronize(s->stream)); // no launch may still be reading the old tables
     HIP_TRY(hipMemcpy(s->d_tab, tabs.data(), tabs.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     return ISINGMC_OK;
@@ -830,7 +819,7 @@ static int measure(isingmc_states *s, double *energies, int64_t *mags)
         TRY(measure_enqueue(s, s->d_meas, nullptr, nullptr, /*want_up=*/mags != nullptr));
         s->meas_zero = false;
         std::vector<unsigned long long> h;
-        TRY(read_back(s, h, s->d_meas, 2 * counter_slots(s)));
+        TRY(read_back(s, h, s->d_meas.get(), 2 * counter_slots(s)));
         for (size_t r = 0; r < R; r++) {
             const size_t sl = counter_slot(s, r);
             if (energies) energies[r] = counters_energy(s, h[2 * sl], h[2 * sl + 1]);
@@ -921,23 +910,18 @@ int launch_strip(isingmc_states *s, const StripPlan &P, size_t r0, size_t n, siz
     const isingmc_graph *g = s->g;
     const size_t granules = s->cap * size_t(P.a.n_strips) * 4 * g->geom.wpr;
     if (s->halo_cap < granules) {
-        HIP_TRY(stream_quiesce(s->stream)); // recycled blocks: nothing enqueued may still use the old one
-        if (s->d_halo) HIP_TRY(cached_free(s->d_halo));
-        s->d_halo = nullptr;
-        s->halo_cap = 0;
-        TRY(dev_alloc(&s->d_halo, granules));
+        TRY(dev_regrow(s->stream, s->d_halo, &s->halo_cap, granules, granules));
         HIP_TRY(hipMemsetAsync(s->d_halo, 0, granules * sizeof(unsigned long long), s->stream));
-        s->halo_cap = granules;
         s->strip_epoch = 0;
     }
     if (!s->d_strip_err) {
-        TRY(dev_alloc(&s->d_strip_err, 4));
+        TRY(dev_alloc(s->d_strip_err, 4));
         HIP_TRY(hipMemsetAsync(s->d_strip_err, 0, 4 * sizeof(uint32_t), s->stream));
     }
     StripFinal fin{nullptr, nullptr, 0.0, 0};
     if (final_energies) {
         if (!s->d_strip_fin) {
-            TRY(dev_alloc(&s->d_strip_fin, s->cap));
+            TRY(dev_alloc(s->d_strip_fin, s->cap));
             HIP_TRY(hipMemsetAsync(s->d_strip_fin, 0, s->cap * sizeof(unsigned long long), s->stream));
         }
         fin = StripFinal{s->d_strip_fin + r0, final_energies + r0, g->jabs, 2ll * (long long)g->nvars};
@@ -1010,7 +994,7 @@ static int run_steps_impl(isingmc_states *s, size_t timesteps, const double *bet
 int snapshot_take(isingmc_states *s)
 {
     const size_t words = s->R * s->g->state_words;
-    if (s->snapshot_cap < words) TRY(dev_regrow(s->stream, &s->d_snapshot, &s->snapshot_cap, words, words));
+    if (s->snapshot_cap < words) TRY(dev_regrow(s->stream, s->d_snapshot, &s->snapshot_cap, words, words));
     HIP_TRY(hipMemcpyAsync(s->d_snapshot, s->d_state, words * sizeof(uint32_t), hipMemcpyDeviceToDevice, s->stream));
     return ISINGMC_OK;
 }
@@ -1185,7 +1169,7 @@ static int run_packed(StepRun &c, size_t k0, size_t nk)
     }
     if (new_step_tabs) c.pk_tabs_written = true;
     if (new_philox_rows) { // (on the main stream, the lanes joined: in order with every sweep that read the old rows)
-        if (!s->d_pk_philox) TRY(dev_alloc(&s->d_pk_philox, PK_PHILOX_STEPS * philox_words));
+        if (!s->d_pk_philox) TRY(dev_alloc(s->d_pk_philox, PK_PHILOX_STEPS * philox_words));
         HIP_TRY(pk_uni_launch_philox_table(s->stream, s->d_pk_philox, s->d_keys, uint32_t(s->groups), s->t, uint32_t(PK_PHILOX_STEPS)));
         s->pk_philox_t0 = s->t;
         s->pk_philox_steps = PK_PHILOX_STEPS;

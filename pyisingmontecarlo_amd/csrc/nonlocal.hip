@@ -85,7 +85,7 @@ extern "C" int isingmc_cluster_stats(isingmc_states *s, uint64_t *n_clusters_out
     if (!s->cl_have_stats || s->cl_stats_cap < counter_slots(s)) return fail(ISINGMC_ERR_INVALID, "no cluster step has run on these replicas yet");
     TRY(use_device(s->g->device));
     std::vector<uint32_t> h;
-    TRY(read_back(s, h, s->d_cl_stats, 2 * counter_slots(s)));
+    TRY(read_back(s, h, s->d_cl_stats.get(), 2 * counter_slots(s)));
     for (size_t r = 0; r < s->R; r++) { // (packed: one pair per (group, bit) slot)
         n_clusters_out[r] = h[2 * counter_slot(s, r)];
         largest_out[r] = h[2 * counter_slot(s, r) + 1];
@@ -121,7 +121,7 @@ int run_cluster_step(isingmc_states *s, NonlocalRun &n, DeviceScratch &scratch, 
     }
     if (s->cl_stats_cap < slots) { // a lattice container may grow; the groups of a packed one are fixed for its life: allocated once
         const size_t cap = s->packed ? slots : s->cap;
-        TRY(dev_regrow(s->stream, &s->d_cl_stats, &s->cl_stats_cap, 2 * cap, cap));
+        TRY(dev_regrow(s->stream, s->d_cl_stats, &s->cl_stats_cap, 2 * cap, cap));
     }
     uint64_t thr = 0;
     if (!s->has_betas) thr = cluster_threshold(beta, g->jabs);
@@ -249,7 +249,7 @@ int run_icm_step(isingmc_states *s, NonlocalRun &n, DeviceScratch &scratch)
     //  and its groups are fixed for its life: allocated once)
     if (!s->d_icm_stats || s->icm_stats_cap < pair_slots) {
         const size_t cap = s->packed ? pair_slots : std::max<size_t>(1, s->cap / 2);
-        TRY(dev_regrow(s->stream, &s->d_icm_stats, &s->icm_stats_cap, 3 * cap, cap));
+        TRY(dev_regrow(s->stream, s->d_icm_stats, &s->icm_stats_cap, 3 * cap, cap));
     }
     uint32_t *const minus = s->d_icm_stats + 2 * s->icm_stats_cap;
     HIP_TRY(hipMemsetAsync(s->d_icm_stats, 0, 3 * s->icm_stats_cap * sizeof(uint32_t), s->stream));
@@ -306,15 +306,13 @@ static int between_prepare(isingmc_states *a, isingmc_states *b, const uint32_t 
 {
     if (a->icmb_cap < n_pairs) {
         HIP_TRY(stream_quiesce(a->stream));
-        for (uint32_t **p : {&a->d_icmb_slots, &a->d_icmb_stats}) {
-            if (*p) HIP_TRY(cached_free(*p));
-            *p = nullptr;
-        }
+        a->d_icmb_slots.reset();
+        a->d_icmb_stats.reset();
         a->icmb_cap = 0;
         a->icmb_have_stats = false;
         const size_t cap = std::max(n_pairs, a->cap);
-        TRY(dev_alloc(&a->d_icmb_slots, 2 * cap));
-        TRY(dev_alloc(&a->d_icmb_stats, 3 * cap));
+        TRY(dev_alloc(a->d_icmb_slots, 2 * cap));
+        TRY(dev_alloc(a->d_icmb_stats, 3 * cap));
         a->icmb_cap = cap;
     }
     for (hipEvent_t &ev : a->icmb_ev)
@@ -394,9 +392,9 @@ extern "C" int isingmc_icm_between(isingmc_states *a, isingmc_states *b, const u
     const size_t n_pos = g->pk.n_pos, items = a->packed ? (n_pairs + 31) / 32 : n_pairs;
     const size_t words = a->packed ? pk_between_words_per_block(n_pos) : cluster_words_per_replica(g->nvars);
     const size_t batch = workspace_batch(a, items, words);
-    if (!a->d_icmb_work || a->icmb_batch != batch) TRY(dev_regrow(a->stream, &a->d_icmb_work, &a->icmb_batch, batch * words, batch));
+    if (!a->d_icmb_work || a->icmb_batch != batch) TRY(dev_regrow(a->stream, a->d_icmb_work, &a->icmb_batch, batch * words, batch));
     const size_t inv_words = 32 * (a->groups + b->groups); // packed: (local group, bit) -> pair, a's groups first
-    if (a->packed && a->icmb_inv_cap < inv_words) TRY(dev_regrow(a->stream, &a->d_icmb_inv, &a->icmb_inv_cap, inv_words, inv_words));
+    if (a->packed && a->icmb_inv_cap < inv_words) TRY(dev_regrow(a->stream, a->d_icmb_inv, &a->icmb_inv_cap, inv_words, inv_words));
     const uint32_t *d_sa = nullptr, *d_sb = nullptr;
     TRY(between_prepare(a, b, slots_a, slots_b, n_pairs, &d_sa, &d_sb));
     uint32_t *const stats = a->d_icmb_stats, *const minus = a->d_icmb_stats + 2 * a->icmb_cap;

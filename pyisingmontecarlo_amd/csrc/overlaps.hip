@@ -135,7 +135,7 @@ struct isingmc_site_classes {
     bool has_lat = false, has_pk = false;
     LatClassDev lat{};
     PkClassDev pk{};
-    std::vector<void *> dev_allocs;
+    DevBlocks dev_allocs;
 };
 
 // the limits of a class set and the values of its tables ("" when they hold)
@@ -175,8 +175,7 @@ template <typename T>
 static int classes_upload(isingmc_site_classes *c, const T **dst, const T *src, size_t count)
 {
     T *d = nullptr;
-    TRY(dev_alloc(&d, count));
-    c->dev_allocs.push_back(d);
+    TRY(dev_alloc(c->dev_allocs, &d, count));
     if (count) HIP_TRY(hipMemcpy(d, src, count * sizeof(T), hipMemcpyHostToDevice));
     *dst = d;
     return ISINGMC_OK;
@@ -251,7 +250,6 @@ extern "C" int isingmc_site_classes_destroy(isingmc_site_classes *classes)
 {
     if (!classes) return ISINGMC_OK;
     (void)hipSetDevice(classes->device); // (every measurement has waited for its kernels: nothing reads the blocks any more)
-    for (void *p : classes->dev_allocs) (void)cached_free(p);
     delete classes;
     return ISINGMC_OK;
 }

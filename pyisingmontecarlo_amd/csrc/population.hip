@@ -32,21 +32,18 @@ static int pa_reserve(isingmc_states *s)
     for (size_t r = 0; r < s->R; r++) family[r] = uint32_t(r);
     if (s->pa_families_set && s->pa_cap) // a container that grew keeps its families; the new slots found their own
         HIP_TRY(hipMemcpy(family.data(), s->d_pa_family, std::min(s->pa_cap, s->R) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    for (void **p : {(void **)&s->d_pa_state, (void **)&s->d_pa_energy, (void **)&s->d_pa_cum, (void **)&s->d_pa_src, (void **)&s->d_pa_user_src, (void **)&s->d_pa_family,
-                     (void **)&s->d_pa_family2}) {
-        if (*p) (void)cached_free(*p);
-        *p = nullptr;
-    }
+    s->d_pa_state.reset(); s->d_pa_energy.reset(); s->d_pa_cum.reset(); s->d_pa_src.reset();
+    s->d_pa_user_src.reset(); s->d_pa_family.reset(); s->d_pa_family2.reset();
     s->pa_cap = s->pa_state_words = 0;
     s->pa_families_set = false;
-    TRY(dev_alloc(&s->d_pa_state, words));
-    TRY(dev_alloc(&s->d_pa_energy, s->R));
-    TRY(dev_alloc(&s->d_pa_cum, s->R + pa_scan_blocks(s->R)));
-    TRY(dev_alloc(&s->d_pa_src, s->R));
-    TRY(dev_alloc(&s->d_pa_user_src, s->R));
-    TRY(dev_alloc(&s->d_pa_family, s->R));
-    TRY(dev_alloc(&s->d_pa_family2, s->R));
-    if (!s->d_pa_record) TRY(dev_alloc(&s->d_pa_record, 1));
+    TRY(dev_alloc(s->d_pa_state, words));
+    TRY(dev_alloc(s->d_pa_energy, s->R));
+    TRY(dev_alloc(s->d_pa_cum, s->R + pa_scan_blocks(s->R)));
+    TRY(dev_alloc(s->d_pa_src, s->R));
+    TRY(dev_alloc(s->d_pa_user_src, s->R));
+    TRY(dev_alloc(s->d_pa_family, s->R));
+    TRY(dev_alloc(s->d_pa_family2, s->R));
+    if (!s->d_pa_record) TRY(dev_alloc(s->d_pa_record, 1));
     HIP_TRY(hipMemcpy(s->d_pa_family, family.data(), s->R * sizeof(uint32_t), hipMemcpyHostToDevice));
     s->pa_state_words = words;
     s->pa_cap = s->R;

@@ -52,14 +52,14 @@ int expand_states(isingmc_states *s, const uint32_t *d_words, uint8_t *states_ou
 // ------------------------------------------------------------------------------------------------
 // buffers of the sampling pipeline, grown on demand and kept for the next call (pinning host memory is slow)
 template <typename T>
-static int regrow(T **dev, T **host, size_t count)
+static int regrow(DevBlock<T> &dev, PinnedBlock<T> &host, size_t count)
 {
-    if (*dev) HIP_TRY(cached_free(*dev));
-    if (*host) HIP_TRY(cached_host_free(*host));
-    *dev = nullptr;
-    *host = nullptr;
+    dev.reset();
+    host.reset();
     TRY(dev_alloc(dev, count));
-    HIP_TRY(cached_host_malloc(reinterpret_cast<void **>(host), std::max<size_t>(count, 1) * sizeof(T)));
+    void *p = nullptr;
+    HIP_TRY(cached_host_malloc(&p, std::max<size_t>(count, 1) * sizeof(T)));
+    host = PinnedBlock<T>(static_cast<T *>(p));
     return ISINGMC_OK;
 }
 
@@ -75,20 +75,19 @@ static int sampling_reserve(isingmc_states *s, size_t words, size_t counts, size
     HIP_TRY(hipStreamSynchronize(s->copy_stream));
     if (words > s->sample_cap_words) {
         s->sample_cap_words = 0;
-        for (int b = 0; b < 2; b++) TRY(regrow(&s->d_samples[b], &s->h_samples[b], words));
+        for (int b = 0; b < 2; b++) TRY(regrow(s->d_samples[b], s->h_samples[b], words));
         s->sample_cap_words = words;
     }
     if (counts > s->sample_cap_counts) {
         s->sample_cap_counts = 0;
-        for (int b = 0; b < 2; b++) TRY(regrow(&s->d_sample_counts[b], &s->h_counts[b], counts));
+        for (int b = 0; b < 2; b++) TRY(regrow(s->d_sample_counts[b], s->h_counts[b], counts));
         s->sample_cap_counts = counts;
     }
     if (energies > s->sample_cap_e) {
         s->sample_cap_e = 0;
-        for (int b = 0; b < 2; b++) TRY(regrow(&s->d_sample_e[b], &s->h_e[b], energies));
-        if (s->d_sample_m) HIP_TRY(cached_free(s->d_sample_m));
-        s->d_sample_m = nullptr;
-        TRY(dev_alloc(&s->d_sample_m, energies));
+        for (int b = 0; b < 2; b++) TRY(regrow(s->d_sample_e[b], s->h_e[b], energies));
+        s->d_sample_m.reset();
+        TRY(dev_alloc(s->d_sample_m, energies));
         s->sample_cap_e = energies;
     }
     return ISINGMC_OK;

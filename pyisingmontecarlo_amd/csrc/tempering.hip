@@ -25,8 +25,8 @@ extern "C" int isingmc_synchronize(isingmc_states *s)
 static uint64_t *pt_thr_local(isingmc_states *s)
 {
     if (s->packed && s->rj) return reinterpret_cast<uint64_t *>(s->d_rj_betas + s->pk_bit0);
-    if (s->packed) return reinterpret_cast<uint64_t *>(s->d_pk_slot_thr); // pk_bit0 == 0 (checked at attach)
-    return reinterpret_cast<uint64_t *>(s->d_thr);
+    if (s->packed) return reinterpret_cast<uint64_t *>(s->d_pk_slot_thr.get()); // pk_bit0 == 0 (checked at attach)
+    return reinterpret_cast<uint64_t *>(s->d_thr.get());
 }
 
 // bit-sliced packed path: the groups' threshold tables follow the slots' new thresholds (enqueue only)
@@ -74,12 +74,8 @@ extern "C" int isingmc_pt_detach(isingmc_states *s)
     TRY(use_device(s->g->device));
     HIP_TRY(hipStreamSynchronize(s->stream)); // enqueued rounds may still read the ladder
     TRY(strip_error(strip_check(s)));
-    for (void **p : {(void **)&s->d_pt_ladder, (void **)&s->d_pt_local, (void **)&s->d_pt_all, (void **)&s->d_pt_ladder_thr,
-                     (void **)&s->d_pt_perm, (void **)&s->d_pt_counters, (void **)&s->d_pt_mail, (void **)&s->d_pt_round_counts,
-                     (void **)&s->d_pt_perm2}) {
-        if (*p) (void)cached_free(*p);
-        *p = nullptr;
-    }
+    s->d_pt_ladder.reset(); s->d_pt_local.reset(); s->d_pt_all.reset(); s->d_pt_ladder_thr.reset(); s->d_pt_perm.reset();
+    s->d_pt_counters.reset(); s->d_pt_mail.reset(); s->d_pt_round_counts.reset(); s->d_pt_perm2.reset();
     s->pt = PtDev{};
     s->pt_attached = false;
     s->has_betas = false;
@@ -103,11 +99,11 @@ extern "C" int isingmc_pt_attach(isingmc_states *s, const double *ladder_betas, 
     TRY(use_device(s->g->device));
     const isingmc_graph *g = s->g;
     const bool lattice = g->kind == ISINGMC_KIND_LATTICE2D;
-    TRY(dev_alloc(&s->d_pt_ladder, n_rungs));
-    TRY(dev_alloc(&s->d_pt_perm, n_rungs));
-    TRY(dev_alloc(&s->d_pt_local, slots_per_rank));
-    TRY(dev_alloc(&s->d_pt_all, slots_per_rank * world_size));
-    TRY(dev_alloc(&s->d_pt_counters, 2));
+    TRY(dev_alloc(s->d_pt_ladder, n_rungs));
+    TRY(dev_alloc(s->d_pt_perm, n_rungs));
+    TRY(dev_alloc(s->d_pt_local, slots_per_rank));
+    TRY(dev_alloc(s->d_pt_all, slots_per_rank * world_size));
+    TRY(dev_alloc(s->d_pt_counters, 2));
     std::vector<uint32_t> perm(n_rungs);
     for (size_t i = 0; i < n_rungs; i++) perm[i] = uint32_t(i);
     HIP_TRY(hipMemcpy(s->d_pt_ladder, ladder_betas, n_rungs * sizeof(double), hipMemcpyHostToDevice));
@@ -122,9 +118,9 @@ extern "C" int isingmc_pt_attach(isingmc_states *s, const double *ladder_betas, 
             rj_beta(ladder_betas[i], g->rj_k, &b.shift, &b.mant);
             std::memcpy(&thr[i], &b, sizeof b);
         }
-        TRY(dev_alloc(&s->d_pt_ladder_thr, n_rungs));
+        TRY(dev_alloc(s->d_pt_ladder_thr, n_rungs));
         HIP_TRY(hipMemcpy(s->d_pt_ladder_thr, thr.data(), thr.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-        if (!s->d_rj_betas) TRY(dev_alloc(&s->d_rj_betas, 32 * s->groups));
+        if (!s->d_rj_betas) TRY(dev_alloc(s->d_rj_betas, 32 * s->groups));
         std::vector<RjBeta> init(32 * s->groups, RjBeta{31u, 0xFFFFFFFFu}); // bits this shard does not own: accept-all, nobody reads them
         HIP_TRY(hipMemcpy(s->d_rj_betas, init.data(), init.size() * sizeof(RjBeta), hipMemcpyHostToDevice));
     }
@@ -132,11 +128,11 @@ extern "C" int isingmc_pt_attach(isingmc_states *s, const double *ladder_betas, 
         std::vector<uint64_t> thr(size_t(PK_MAX_DEG) * n_rungs);
         for (size_t i = 0; i < n_rungs; i++)
             for (uint32_t m = 1; m <= uint32_t(PK_MAX_DEG); m++) thr[i * PK_MAX_DEG + m - 1] = threshold_fixed(ladder_betas[i], 2.0 * g->jabs * double(m));
-        TRY(dev_alloc(&s->d_pt_ladder_thr, thr.size()));
+        TRY(dev_alloc(s->d_pt_ladder_thr, thr.size()));
         HIP_TRY(hipMemcpy(s->d_pt_ladder_thr, thr.data(), thr.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-        if (!s->d_pk_slot_thr) TRY(dev_alloc(&s->d_pk_slot_thr, size_t(32) * s->groups * PK_MAX_DEG));
+        if (!s->d_pk_slot_thr) TRY(dev_alloc(s->d_pk_slot_thr, size_t(32) * s->groups * PK_MAX_DEG));
         HIP_TRY(hipMemset(s->d_pk_slot_thr, 0, size_t(32) * s->groups * PK_MAX_DEG * sizeof(unsigned long long)));
-        if (!s->d_tab) TRY(dev_alloc(&s->d_tab, s->groups * PK_TAB_WORDS));
+        if (!s->d_tab) TRY(dev_alloc(s->d_tab, s->groups * PK_TAB_WORDS));
     }
     if (lattice) { // thresholds per rung from the host's exp: bit-identical to isingmc_states_set_betas
         std::vector<uint64_t> thr(2 * n_rungs);
@@ -145,7 +141,7 @@ extern "C" int isingmc_pt_attach(isingmc_states *s, const double *ladder_betas, 
             thr[2 * i] = t.T3;
             thr[2 * i + 1] = t.T4;
         }
-        TRY(dev_alloc(&s->d_pt_ladder_thr, 2 * n_rungs));
+        TRY(dev_alloc(s->d_pt_ladder_thr, 2 * n_rungs));
         HIP_TRY(hipMemcpy(s->d_pt_ladder_thr, thr.data(), thr.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
     }
     s->pt = PtDev{s->d_pt_ladder, s->d_pt_ladder_thr, rj_ladder ? 1u : pk_ladder ? uint32_t(PK_MAX_DEG) : 2u, s->d_pt_perm, s->d_pt_all, s->d_pt_counters, uint32_t(n_rungs),
@@ -199,9 +195,9 @@ extern "C" int isingmc_pt_run(isingmc_states *s, size_t timesteps, size_t swap_e
     if (in_kernel) {
         const size_t R = s->R, nk = rounds * swap_every;
         if (!s->d_pt_mail) {
-            TRY(dev_alloc(&s->d_pt_mail, 4 * R));
-            TRY(dev_alloc(&s->d_pt_round_counts, 2 * R));
-            TRY(dev_alloc(&s->d_pt_perm2, R));
+            TRY(dev_alloc(s->d_pt_mail, 4 * R));
+            TRY(dev_alloc(s->d_pt_round_counts, 2 * R));
+            TRY(dev_alloc(s->d_pt_perm2, R));
             HIP_TRY(hipMemsetAsync(s->d_pt_mail, 0, 4 * R * sizeof(unsigned long long), s->stream));
             HIP_TRY(hipMemsetAsync(s->d_pt_round_counts, 0, 2 * R * sizeof(unsigned long long), s->stream));
         }
@@ -209,7 +205,7 @@ extern "C" int isingmc_pt_run(isingmc_states *s, size_t timesteps, size_t swap_e
         unsigned long long c[2];
         HIP_TRY(hipStreamSynchronize(s->stream));
         HIP_TRY(hipMemcpy(c, s->d_pt_counters, sizeof c, hipMemcpyDeviceToHost));
-        const StripLadder lad{s->d_pt_ladder, reinterpret_cast<const unsigned long long *>(s->d_pt_ladder_thr), s->d_pt_perm, s->d_pt_perm2,
+        const StripLadder lad{s->d_pt_ladder, reinterpret_cast<const unsigned long long *>(s->d_pt_ladder_thr.get()), s->d_pt_perm, s->d_pt_perm2,
                               s->d_pt_mail, s->d_pt_round_counts, s->d_pt_counters, c[0], uint32_t(R), uint32_t(swap_every), s->pt.seed_lo,
                               s->pt.seed_hi, g->jabs, 2ll * (long long)g->nvars};
         s->meas_fresh = false;
