@@ -410,6 +410,51 @@ int isingmc_best_raw_state(isingmc_states *states, uint32_t *words_out, size_t *
 /* records back to +inf, timesteps and the improvement count to 0; the second buffer keeps its words */
 int isingmc_best_reset(isingmc_states *states);
 
+/* ---- per-site spin sums and per-bond sums over the samples of a run (the classical counterpart of
+ * run_quantum_monte_carlo_and_measure_spins) ----
+ * Thermal averages resolved per site without a configuration leaving the device: the local magnetisations <s_i> and the bond
+ * correlations <s_a s_b> as exact integer sums, True = +1 as in isingmc_get_states.  n = the samples taken so far.
+ *   summed mode (flags 0):         site[i] = sum over samples and over the container's replicas of s_i, int64[nvars]; with
+ *                                  ISINGMC_MOMENTS_BONDS also bond[e] = that sum of s_a s_b for entry e of the edge list given at
+ *                                  graph creation, int64[n_edges], by the conventions of link_out of isingmc_overlaps: zero
+ *                                  couplings count, duplicated entries are separate, an entry a_e == b_e adds +1 per sample and replica
+ *   ISINGMC_MOMENTS_PER_REPLICA:   site[r][i] = sum over the samples of replica r of s_i, int64[count][nvars]; no bond sums
+ * Sites in no edge count like any other; padding positions of a packed container, the bits of a packed group the container does
+ * not own and replicas beyond count never count.
+ * every > 0 records t0 = the current timestep; from then on, inside isingmc_do_time_steps* and isingmc_run_sampling, a sample of
+ * all replicas follows every timestep t > t0 with (t - t0) % every == 0, whatever kind of timestep it is (sweep, Swendsen-Wang
+ * step, isoenergetic move): the stretch of Metropolis sweeps is cut there and the sample is enqueued behind it.  No
+ * configuration, energy, random number or timestep of the run changes.  every == 0 (the default) switches accumulation off and
+ * keeps the sums; switching it on again with the same flags goes on counting, with other flags (or another replica count, or
+ * another value of the option moments_planes) the sums start from zero.  isingmc_states_set_timestep while it is on re-bases t0.
+ * Memory: summed mode 256 bytes per state word (768 with bonds) on a lattice, 8 bytes per position and 16 per edge entry on a packed
+ * container.  Per-replica mode keeps K time planes of the state's own size (the option moments_planes, 1 .. 16, default 8; one
+ * sample adds the state into them, and every 2^K - 1 samples they are flushed) plus 32-bit totals of 32 times the state's size, so a
+ * replica holds at most 2^32 - 1 samples.  The option moments_bytes (default 4 GiB) bounds all of it.
+ * Served: exactly the containers isingmc_overlaps serves -- periodic field-free checkerboard lattices of any sign pattern and
+ * both replica-packed families.  Refused with ISINGMC_ERR_INVALID and a message, the container unchanged: the f64 CSR family;
+ * a tempering ladder attached (and isingmc_pt_attach while accumulation is on: a slot changes its temperature); isingmc_pa_run,
+ * isingmc_pa_resample and isingmc_states_append while it is on; ISINGMC_MOMENTS_BONDS together with ISINGMC_MOMENTS_PER_REPLICA;
+ * sums larger than moments_bytes. */
+#define ISINGMC_MOMENTS_PER_REPLICA 1u
+#define ISINGMC_MOMENTS_BONDS 2u
+int isingmc_states_set_moments_every(isingmc_states *states, size_t every, unsigned flags);
+int isingmc_states_moments_every(const isingmc_states *states, size_t *every_out, unsigned *flags_out);
+/* enqueue only: one sample at the container's current timestep, whatever the period (never switched on: summed mode, sites alone) */
+int isingmc_moments_accumulate(isingmc_states *states);
+/* synchronises and flushes the time planes.  *n_samples_out = n; site_out / bond_out as above, in the site numbering and edge
+ * order of graph creation.  Any pointer may be NULL; bond_out needs ISINGMC_MOMENTS_BONDS. */
+int isingmc_moments_get(isingmc_states *states, uint64_t *n_samples_out, int64_t *site_out, int64_t *bond_out);
+/* sums and n back to zero; the setting stays */
+int isingmc_moments_reset(isingmc_states *states);
+/* The loop of isingmc_run_sampling with the samples summed instead of copied out: the sums are zeroed, then
+ *   thermalization x do_time_step(beta);  n_samples x { sampling_freq x do_time_step(beta);  one sample }
+ * is enqueued back to back and the host waits once, for energies_out: double[count], the energies of the final configurations
+ * (NULL allowed).  Accumulation is off on entry and off again on return; isingmc_moments_get reads the sums.  beta is ignored
+ * while per-replica betas are set.  Same trajectory and same samples as isingmc_run_sampling with these arguments. */
+int isingmc_run_sampling_moments(isingmc_states *states, double beta, size_t thermalization, size_t sampling_freq,
+                                 size_t n_samples, unsigned flags, double *energies_out);
+
 /* replaces the whole sampling loop of lattice.rs:271-287 / classicising.rs:144-173:
  *   thermalization x do_time_step(beta);  n_samples x { sampling_freq x do_time_step(beta);
  *   states[r][k][:] = state_ref();  energies[r][k] = get_energy() }

@@ -13,6 +13,8 @@ OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_ALLOC = range(5)
 KIND_GENERAL, KIND_LATTICE2D = 0, 1
 FLAG_FORCE_GENERAL = 1
 FLAG_STABLE_PATH = 2
+MOMENTS_PER_REPLICA = 1  # ISINGMC_MOMENTS_*
+MOMENTS_BONDS = 2
 FAMILIES = ("checkerboard", "csr_f64", "packed_bitsliced", "packed_real")
 
 
@@ -90,6 +92,12 @@ _PROTOTYPES = {
     "isingmc_best_get": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, C.POINTER(C.c_uint64)]),
     "isingmc_best_raw_state": (C.c_int, [_vp, _vp, C.POINTER(C.c_size_t)]),
     "isingmc_best_reset": (C.c_int, [_vp]),
+    "isingmc_states_set_moments_every": (C.c_int, [_vp, C.c_size_t, C.c_uint]),
+    "isingmc_states_moments_every": (C.c_int, [_vp, C.POINTER(C.c_size_t), C.POINTER(C.c_uint)]),
+    "isingmc_moments_accumulate": (C.c_int, [_vp]),
+    "isingmc_moments_get": (C.c_int, [_vp, C.POINTER(C.c_uint64), _vp, _vp]),
+    "isingmc_moments_reset": (C.c_int, [_vp]),
+    "isingmc_run_sampling_moments": (C.c_int, [_vp, C.c_double, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint, _vp]),
     "isingmc_run_sampling": (C.c_int, [_vp, C.c_double, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp]),
     "isingmc_pt_attach": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint64]),
     "isingmc_pt_can_attach": (C.c_int, [_vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_int)]),
@@ -376,6 +384,7 @@ class Graph:
         _check(lib().isingmc_graph_info(self._h, C.byref(info)))
         self.info = info
         self.nvars = int(info.nvars)
+        self.n_edges = int(info.n_edges)
         self.kind = int(info.kind)
         self.state_words = int(info.state_words)
 
@@ -617,6 +626,46 @@ class States:
 
     def best_reset(self):
         _check(lib().isingmc_best_reset(self._h))
+
+    # ---- per-site spin sums and per-bond sums over the samples of a run
+    def set_moments_every(self, every, per_replica=False, bonds=False):
+        """A sample of all replicas follows every timestep t > t0 (now) with (t - t0) % every == 0; 0 switches accumulation off and
+        keeps the sums.  per_replica: sums per replica instead of over all of them; bonds: the sums of s_a s_b per edge-list entry too."""
+        flags = (MOMENTS_PER_REPLICA if per_replica else 0) | (MOMENTS_BONDS if bonds else 0)
+        _check(lib().isingmc_states_set_moments_every(self._h, int(every), flags))
+
+    @property
+    def moments_every(self):
+        """(every, per_replica, bonds) as set."""
+        k, f = C.c_size_t(), C.c_uint()
+        _check(lib().isingmc_states_moments_every(self._h, C.byref(k), C.byref(f)))
+        return int(k.value), bool(f.value & MOMENTS_PER_REPLICA), bool(f.value & MOMENTS_BONDS)
+
+    def accumulate_moments(self):
+        """One sample at the current timestep, whatever the period; enqueue only."""
+        _check(lib().isingmc_moments_accumulate(self._h))
+
+    def moments(self):
+        """(n, site, bond or None): the samples taken and the exact integer sums, True = +1 -- site int64[nvars] (int64[R, nvars] per
+        replica), bond int64[n_edges] in the order of the edge list when bond sums are held.  Synchronises."""
+        _, per_replica, bonds = self.moments_every
+        N = self.graph.nvars
+        site = np.zeros((self.count, N) if per_replica else N, dtype=np.int64)
+        bond = np.zeros(self.graph.n_edges, dtype=np.int64) if bonds else None
+        n = C.c_uint64()
+        _check(lib().isingmc_moments_get(self._h, C.byref(n), _p(site), _p(bond)))
+        return int(n.value), site, bond
+
+    def reset_moments(self):
+        _check(lib().isingmc_moments_reset(self._h))
+
+    def run_sampling_moments(self, beta, thermalization, sampling_freq, n_samples, per_replica=False, bonds=False):
+        """The loop of run_sampling with the samples summed on the device: the final energies float64[R]; moments() reads the sums."""
+        flags = (MOMENTS_PER_REPLICA if per_replica else 0) | (MOMENTS_BONDS if bonds else 0)
+        energies = np.zeros(self.count, dtype=np.float64)
+        _check(lib().isingmc_run_sampling_moments(self._h, float(0.0 if beta is None else beta), thermalization, sampling_freq, n_samples,
+                                                  flags, _p(energies)))
+        return energies
 
     def do_time_steps(self, timesteps, beta=None, per_step_energies=False):
         """beta: float (constant), sequence of length timesteps, or None when per-replica betas are set."""

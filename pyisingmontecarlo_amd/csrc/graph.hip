@@ -579,6 +579,34 @@ static int build_general(isingmc_graph *g, const uint64_t *ea, const uint64_t *e
     return ISINGMC_OK;
 }
 
+// which entry of the edge list is which bond (isingmc_graph::edge_ends / edge_slots: results per entry)
+static void keep_edge_order(isingmc_graph *g, const uint64_t *ea, const uint64_t *eb, size_t n_edges)
+{
+    if (g->kind != ISINGMC_KIND_LATTICE2D) { // (sites of the general path are below 2^32)
+        g->edge_ends.resize(2 * n_edges);
+        for (size_t k = 0; k < n_edges; k++) {
+            g->edge_ends[2 * k] = uint32_t(ea[k]);
+            g->edge_ends[2 * k + 1] = uint32_t(eb[k]);
+        }
+        return;
+    }
+    // the slots of recognise_lattice2d, which has seen every entry take one of these four forms
+    const uint64_t W = g->geom.W, N = g->nvars;
+    const auto slot_of = [&](size_t k) {
+        const uint64_t lo = std::min(ea[k], eb[k]), hi = std::max(ea[k], eb[k]), d = hi - lo;
+        if (d == 1 && lo % W != W - 1) return 2 * lo;
+        if (d == W - 1 && lo % W == 0) return 2 * hi;
+        if (d == W) return 2 * lo + 1;
+        return 2 * hi + 1;
+    };
+    size_t k = 0;
+    while (k < n_edges && slot_of(k) == k) k++;
+    if (k == n_edges) return; // entry e is slot e
+    if (2 * N > 0xFFFFFFFFull) { g->edge_order_kept = false; return; }
+    g->edge_slots.resize(n_edges);
+    for (k = 0; k < n_edges; k++) g->edge_slots[k] = uint32_t(slot_of(k));
+}
+
 extern "C" int isingmc_graph_create(const uint64_t *ea, const uint64_t *eb, const double *ej, size_t n_edges,
                                     size_t nvars, const double *biases, int device, unsigned flags,
                                     isingmc_graph **graph_out)
@@ -607,6 +635,7 @@ extern "C" int isingmc_graph_create(const uint64_t *ea, const uint64_t *eb, cons
     if (!(flags & ISINGMC_FLAG_FORCE_GENERAL) && !std::isnan(h)) L = recognise_lattice2d(ea, eb, ej, n_edges, nvars);
     if (lattice_fast_path_ok(L, h, field_signs)) TRY(build_lattice(g.get(), L, h, biases, field_signs));
     else TRY(build_general(g.get(), ea, eb, ej, n_edges, nvars, biases));
+    keep_edge_order(g.get(), ea, eb, n_edges);
     *graph_out = g.release();
     return ISINGMC_OK;
 }

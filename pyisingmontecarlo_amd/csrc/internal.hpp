@@ -6,6 +6,7 @@
 //   overlaps.hip   spin and link overlaps between replica pairs (isingmc_overlaps), and the spin overlap by site class
 //                  (isingmc_site_classes_*, isingmc_overlaps_by_class)
 //   best.hip       each replica's lowest-energy configuration, kept on the device (isingmc_best_*)
+//   moments.hip    per-site spin sums and per-bond sums over the samples of a run (isingmc_moments_*)
 //   sampling.hip   get_states and the double-buffered sampling pipeline
 //   tempering.hip  on-stream parallel tempering, the in-process ladder group (RCCL through dlopen)
 //   population.hip population annealing: the on-stream resampling step (isingmc_pa_*)
@@ -44,6 +45,7 @@
 #include "packed_types.hpp"
 #include "pa_kernels.hpp"
 #include "mc_types.hpp"
+#include "moments_kernels.hpp"
 #include "overlap_class_kernels.hpp"
 #include "overlap_kernels.hpp"
 #include "owned_block.hpp"
@@ -113,6 +115,8 @@ struct Options {
     int sample_slab_bytes = 64 << 20, pt_in_kernel = 1, real_target_wgs = 3072;
     int real_measure_wgs = 0; // workgroups the real-coupling measurement shares among its groups: 0 = the occupancy figure (measure_enqueue)
     int cluster_workspace_bytes = 1 << 30; // labels, cluster sizes and bond planes of one batch of replicas
+    int moments_planes = 8;               // time planes of the per-replica moment sums: a flush every 2^K - 1 samples
+    long long moments_bytes = 4ll << 30;   // the most device memory the moment sums of one container may take (64 bits: beyond an int)
 
     static Options from_env()
     {
@@ -140,6 +144,8 @@ struct Options {
         o.real_target_wgs = std::max(256, env_int("ISINGMC_REAL_TARGET_WGS", 3072));
         o.real_measure_wgs = env_int("ISINGMC_REAL_MEASURE_WGS", 0);
         o.cluster_workspace_bytes = std::max(1, env_int("ISINGMC_CLUSTER_WORKSPACE_BYTES", 1 << 30));
+        o.moments_planes = env_int("ISINGMC_MOMENTS_PLANES", o.moments_planes);
+        if (const char *v = std::getenv("ISINGMC_MOMENTS_BYTES")) o.moments_bytes = std::atoll(v);
         return o;
     }
 
@@ -147,6 +153,7 @@ struct Options {
     bool set(const std::string &name_in, long value)
     {
         const std::string n = option_bare_name(name_in);
+        if (n == "moments_bytes") { moments_bytes = value; return true; }
         const std::pair<const char *, int *> table[] = {
             {"force_real", &force_real}, {"disable_real", &disable_real}, {"force_packed", &force_packed}, {"disable_packed", &disable_packed},
             {"disable_packed_uniform", &disable_packed_uniform}, {"disable_resident", &disable_resident}, {"strip", &strip},
@@ -155,7 +162,7 @@ struct Options {
             {"resident_spread", &resident_spread}, {"resident_lpq", &resident_lpq}, {"gen_stage", &gen_stage}, {"gen_rb", &gen_rb},
             {"sample_slab_bytes", &sample_slab_bytes}, {"pt_in_kernel", &pt_in_kernel}, {"real_target_wgs", &real_target_wgs},
             {"real_measure_wgs", &real_measure_wgs},
-            {"cluster_workspace_bytes", &cluster_workspace_bytes}};
+            {"cluster_workspace_bytes", &cluster_workspace_bytes}, {"moments_planes", &moments_planes}};
         for (const auto &e : table)
             if (n == e.first) { *e.second = int(value); return true; }
         return false;
@@ -211,6 +218,11 @@ struct isingmc_graph {
     Options opt;                          // the environment's switches when the graph was created
     std::vector<uint32_t> class_real_end; // per colour class: end of its real sites (the padding follows)
     int n_cu = 256;                       // compute units of the device (queried once, at creation)
+    // The order of the edge list, for results per entry.  General graphs: the two sites of every entry.  Recognised
+    // lattices: the bond slot 2 site + direction (0 right, 1 down) of every entry -- empty when entry e is slot e, the order the
+    // usual generators emit.  edge_order_kept = false: a lattice too large for 32-bit slots in another order (bond sums refused).
+    std::vector<uint32_t> edge_ends, edge_slots;
+    bool edge_order_kept = true;
     std::vector<DevBlock<unsigned char>> dev_allocs;
 
     ~isingmc_graph()
@@ -349,6 +361,22 @@ struct isingmc_states {
     DevBlock<double> d_best_energy;           // [best_cap] the energies an update measures
     DevBlock<uint32_t> d_best_flags;          // a flag per replica (checkerboard) / an improvement mask per group (packed)
     DevBlock<unsigned long long> d_best_count; // improvements so far
+    // per-site and per-bond sums over the samples of a run (isingmc_moments_*): allocated when accumulation is
+    // switched on (or by the first isingmc_moments_accumulate) for the replicas the container holds then, and kept
+    size_t mom_every = 0;        // a sample follows every timestep t > mom_t0 with (t - mom_t0) % mom_every == 0; 0 = off
+    unsigned mom_flags = 0;      // ISINGMC_MOMENTS_* of the sums held
+    uint64_t mom_t0 = 0;
+    uint64_t mom_n = 0;          // samples in the sums
+    bool mom_have = false;       // the blocks below are allocated, for mom_R replicas
+    size_t mom_R = 0;
+    DevBlock<unsigned long long> d_mom_site, d_mom_bond; // summed mode: set-bit counts in the layouts of moments_kernels.hpp
+    DevBlock<uint2> d_mom_edges;                          // packed containers with bond sums: the two positions of every edge entry
+    DevBlock<uint32_t> d_mom_planes, d_mom_totals;        // per-replica mode: mom_k time planes of the state's shape, 32-bit totals
+    int mom_k = 0;
+    uint32_t mom_pending = 0;    // samples in the time planes since the last flush (< 2^mom_k)
+    // a call repeated after a strip launch gave up (with_strip_retry) takes no sample twice: the samples up to mom_replay_to were
+    // taken by the attempt that is repeated (mom_last_t: the timestep of the last sample the step loop took)
+    uint64_t mom_last_t = 0, mom_replay_to = 0;
     bool strip_guard = false; // inside with_strip_retry: a strip launch is checked before an update may keep what it left
 
     ~isingmc_states()
@@ -509,6 +537,9 @@ IM_INTERNAL int expand_states(isingmc_states *s, const uint32_t *d_words, uint8_
 IM_INTERNAL int best_from_energies(isingmc_states *s, const double *d_energy);
 IM_INTERNAL int best_update_enqueue(isingmc_states *s); // energies_enqueue into the container's own array, then the above
 
+// ---- moments.hip (per-site and per-bond sums over the samples of a run) -------------------------------------------------------
+IM_INTERNAL int moments_sample_enqueue(isingmc_states *s); // enqueue: one sample of all replicas into the sums (joins the lanes)
+
 // ---- nonlocal.hip (Swendsen-Wang steps and isoenergetic cluster moves) -------------------------------------------------------
 // What the non-local steps of ONE run_steps call keep between them: filled by the call's first such step, the device blocks in the
 // call's DeviceScratch.  The host copies live as long as the call: they feed asynchronous copies.
@@ -554,6 +585,9 @@ static int with_strip_retry(isingmc_states *s, bool may_strip, F &&call)
     s->strip_guard = false;
     if (rc != STRIP_TIMED_OUT) return rc;
     TRY(snapshot_restore(s));
+    s->mom_replay_to = s->mom_every && s->mom_last_t > t0 ? s->mom_last_t : 0; // (the repeat skips the samples already in the sums)
     s->t = t0;
-    return strip_error(call());
+    const int rc2 = strip_error(call());
+    s->mom_replay_to = 0;
+    return rc2;
 }

@@ -146,6 +146,7 @@ extern "C" int isingmc_states_append(isingmc_states *s, uint64_t seed, const uin
     if (!s) return fail(ISINGMC_ERR_INVALID, "NULL states");
     if (s->has_betas) return fail(ISINGMC_ERR_INVALID, "clear the per-replica betas before appending replicas");
     if (s->best_every) return fail(ISINGMC_ERR_INVALID, "minimum tracking is switched on for this container (isingmc_states_set_track_best): its records are sized for the replicas it holds; switch tracking on after the graphs are added");
+    if (s->mom_every) return fail(ISINGMC_ERR_INVALID, "moment sums are switched on for this container (isingmc_states_set_moments_every): they are sized for the replicas it holds; switch accumulation on after the graphs are added");
     TRY(use_device(s->g->device));
     if (s->packed) return pk_append(s, seed, initial_state);
     return add_replicas(s, 1, &seed, initial_state);
@@ -194,6 +195,8 @@ extern "C" int isingmc_states_set_timestep(isingmc_states *s, uint64_t t)
     TRY(use_device(s->g->device));
     HIP_TRY(hipStreamSynchronize(s->stream));
     s->t = t;
+    s->mom_t0 = t; // the sample points of the moment sums are counted from here
+    s->mom_last_t = 0;
     return ISINGMC_OK;
 }
 
@@ -1469,6 +1472,8 @@ static int run_steps_impl(isingmc_states *s, size_t timesteps, const double *bet
             if (const size_t every = s->cluster_every ? s->cluster_every : s->icm_every) nk = std::min<size_t>(nk, every - 1 - s->t % every);
             // minimum tracking cuts the call too: a stretch ends with the timestep after which t % best_every == 0
             if (s->best_every) nk = std::min<size_t>(nk, s->best_every - s->t % s->best_every);
+            // ... and the moment sums (S18): a stretch ends with the timestep after which (t - t0) % mom_every == 0
+            if (s->mom_every) nk = std::min<size_t>(nk, s->mom_every - (s->t - s->mom_t0) % s->mom_every);
             // (joined by the cluster step or the update before this stretch; the packed runner forks behind its table launches)
             if (P.lanes > 1 && s->n_lanes <= 1 && P.path != StepPath::Packed) TRY(lanes_fork(s, P.lanes));
         }
@@ -1496,6 +1501,16 @@ static int run_steps_impl(isingmc_states *s, size_t timesteps, const double *bet
                 rc = strip_check(s);
             }
             if (rc == ISINGMC_OK) rc = best_update_enqueue(s);
+        }
+        // a sample of the moment sums, unless the attempt this call repeats has taken it already (with_strip_retry).  A sample
+        // cannot be taken back: what a strip launch left is checked first, as above
+        if (rc == ISINGMC_OK && s->mom_every && (s->t - s->mom_t0) % s->mom_every == 0 && s->t > s->mom_replay_to) {
+            if (s->strip_guard && P.path == StepPath::LatStrip) {
+                HIP_TRY(hipStreamSynchronize(s->stream));
+                rc = strip_check(s);
+            }
+            if (rc == ISINGMC_OK) rc = moments_sample_enqueue(s);
+            if (rc == ISINGMC_OK) s->mom_last_t = s->t;
         }
     }
     if (s->n_lanes > 1) { const int jrc = lanes_join(s); if (rc == ISINGMC_OK) rc = jrc; }

@@ -93,6 +93,7 @@ extern "C" int isingmc_pa_resample(isingmc_states *s, double dbeta, uint64_t see
         const std::string why = pa_obstacle(s);
         if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
     }
+    if (s->mom_every) return fail(ISINGMC_ERR_INVALID, "moment sums are switched on for this container (isingmc_states_set_moments_every): a resampling replaces the replicas whose samples they hold; switch accumulation off first");
     TRY(use_device(s->g->device));
     TRY(pa_reserve(s));
     TRY(pa_resample_enqueue(s, dbeta, seed, step, s->d_pa_record));
@@ -114,6 +115,7 @@ extern "C" int isingmc_pa_run(isingmc_states *s, const double *betas, size_t n_b
         const std::string why = pa_obstacle(s);
         if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
     }
+    if (s->mom_every) return fail(ISINGMC_ERR_INVALID, "moment sums are switched on for this container (isingmc_states_set_moments_every): a resampling replaces the replicas whose samples they hold; switch accumulation off first");
     TRY(use_device(s->g->device));
     TRY(pa_reserve(s));
     const size_t n_steps = n_betas - 1;

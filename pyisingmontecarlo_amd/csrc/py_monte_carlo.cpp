@@ -361,6 +361,40 @@ public:
         return py::make_tuple(energies, states);
     }
 
+    // extension: the classical counterpart of run_quantum_monte_carlo_and_measure_spins.  The bookkeeping of
+    // run_monte_carlo_sampling -- thermalise, then timesteps sweeps with a sample every sampling_freq -- with the samples summed on
+    // the device: no configuration crosses the bus.  Returns (energies f64[R] of the final configurations, mean_spins f64[R, N], or
+    // f64[N] when per_experiment is false), plus mean_bonds f64[n_edges] (the average of s_a s_b per edge-list entry) when bonds is
+    // set, which needs per_experiment=False.  Means are the exact integer sums over their counts, True = +1; NaN without a sample.
+    // One device: the sums live in one container.  Cluster periods set on this object apply.
+    py::tuple run_monte_carlo_and_measure_spins(double beta, size_t timesteps, size_t num_experiments, std::optional<size_t> thermalization_time,
+                                                std::optional<size_t> sampling_freq, bool per_experiment, bool bonds)
+    {
+        require_classical();
+        const size_t therm = thermalization_time.value_or(0), freq = sampling_freq.value_or(1);
+        if (freq == 0) throw py::value_error("sampling_freq must be positive");
+        if (bonds && per_experiment) throw py::value_error("bond sums per experiment are not offered: bonds=True needs per_experiment=False");
+        if (devices_.size() != 1) throw py::value_error("spin measurement runs on one device: the sums live in one container (set_device)");
+        const size_t S = timesteps / freq, R = num_experiments, N = E_->nvars, NE = E_->a.size();
+        const unsigned flags = (per_experiment ? ISINGMC_MOMENTS_PER_REPLICA : 0u) | (bonds ? ISINGMC_MOMENTS_BONDS : 0u);
+        py::array_t<double> energies(std::vector<ssize_t>{ssize_t(R)});
+        py::array_t<double> spins(per_experiment ? std::vector<ssize_t>{ssize_t(R), ssize_t(N)} : std::vector<ssize_t>{ssize_t(N)});
+        py::array_t<double> bond_means(std::vector<ssize_t>{ssize_t(bonds ? NE : 0)});
+        double *e = energies.mutable_data(), *sp = spins.mutable_data(), *bm = bond_means.mutable_data();
+        std::vector<int64_t> site(per_experiment ? R * N : N), bond(bonds ? NE : 0);
+        uint64_t n = 0;
+        fan_out(num_experiments, 0, R, [&](isingmc_states *s, size_t) {
+            int rc = isingmc_run_sampling_moments(s, beta, therm, freq, S, flags, e);
+            if (rc == ISINGMC_OK) rc = isingmc_moments_get(s, &n, site.data(), bonds ? bond.data() : nullptr);
+            return rc;
+        });
+        const double per_site = double(n) * (per_experiment ? 1.0 : double(R));
+        for (size_t i = 0; i < site.size(); i++) sp[i] = double(site[i]) / per_site;
+        for (size_t k = 0; k < bond.size(); k++) bm[k] = double(bond[k]) / (double(n) * double(R));
+        if (bonds) return py::make_tuple(energies, spins, bond_means);
+        return py::make_tuple(energies, spins);
+    }
+
     // lattice.rs:309-385
     py::tuple run_monte_carlo_annealing(const std::vector<std::pair<size_t, double>> &betas, size_t timesteps,
                                         size_t num_experiments, std::optional<bool>, std::optional<bool>,
@@ -845,6 +879,32 @@ public:
         return py::make_tuple(e, s, t, improvements);
     }
     void reset_minimum() { check(isingmc_best_reset(st_->s)); }
+    // extension: per-site spin sums (and per-bond sums) over the samples of the persistent replicas' runs.
+    // set_measure_spins_every(k): a sample of all replicas follows every k-th timestep from now on (0: off, the sums stay); add_graph
+    // is refused while it is on.  get_measured_spins() -> (n, spins int64[N] or int64[R, N], bonds int64[n_edges] or None): the raw
+    // integer sums, True = +1, and the number of samples in them.  ValueError where isingmc_states_set_moments_every refuses.
+    void set_measure_spins_every(size_t k, bool per_experiment, bool bonds)
+    {
+        check(isingmc_states_set_moments_every(st_->s, k, (per_experiment ? ISINGMC_MOMENTS_PER_REPLICA : 0u) | (bonds ? ISINGMC_MOMENTS_BONDS : 0u)));
+    }
+    py::tuple get_measured_spins()
+    {
+        size_t every = 0;
+        unsigned flags = 0;
+        check(isingmc_states_moments_every(st_->s, &every, &flags));
+        const bool per = flags & ISINGMC_MOMENTS_PER_REPLICA, bonds = flags & ISINGMC_MOMENTS_BONDS;
+        const size_t R = isingmc_states_count(st_->s), N = E_.nvars;
+        py::array_t<int64_t> site(per ? std::vector<ssize_t>{ssize_t(R), ssize_t(N)} : std::vector<ssize_t>{ssize_t(N)});
+        py::array_t<int64_t> bond(std::vector<ssize_t>{ssize_t(bonds ? E_.a.size() : 0)});
+        int64_t *s_out = site.mutable_data(), *b_out = bonds ? bond.mutable_data() : nullptr;
+        uint64_t n = 0;
+        {
+            py::gil_scoped_release nogil;
+            check(isingmc_moments_get(st_->s, &n, s_out, b_out));
+        }
+        return py::make_tuple(n, site, bonds ? py::object(bond) : py::object(py::none()));
+    }
+    void reset_measured_spins() { check(isingmc_moments_reset(st_->s)); }
     // extension: Swendsen-Wang cluster steps on the persistent replicas (see Lattice.set_cluster_update_every); the graph is known
     // here, so one the cluster step does not serve raises ValueError at once
     void set_cluster_update_every(size_t k) { check(isingmc_states_set_cluster_every(st_->s, k)); }
@@ -946,6 +1006,9 @@ PYBIND11_MODULE(_py_monte_carlo, m)
              "num_experiments"_a, "only_basic_moves"_a = py::none(), "thermalization_time"_a = py::none(),
              "sampling_freq"_a = py::none(), "edge_move_importance_sampling"_a = py::none(),
              "replica_range"_a = py::none())
+        .def("run_monte_carlo_and_measure_spins", &Lattice::run_monte_carlo_and_measure_spins, "beta"_a, "timesteps"_a,
+             "num_experiments"_a, "thermalization_time"_a = py::none(), "sampling_freq"_a = py::none(),
+             "per_experiment"_a = true, "bonds"_a = false)
         .def("run_monte_carlo_annealing", &Lattice::run_monte_carlo_annealing, "betas"_a, "timesteps"_a,
              "num_experiments"_a, "only_basic_moves"_a = py::none(), "edge_move_importance_sampling"_a = py::none(),
              "replica_range"_a = py::none())
@@ -992,6 +1055,9 @@ PYBIND11_MODULE(_py_monte_carlo, m)
         .def("set_track_minimum", &ClassicIsing::set_track_minimum, "every"_a)
         .def("get_minimum", &ClassicIsing::get_minimum)
         .def("reset_minimum", &ClassicIsing::reset_minimum)
+        .def("set_measure_spins_every", &ClassicIsing::set_measure_spins_every, "k"_a, "per_experiment"_a = false, "bonds"_a = false)
+        .def("get_measured_spins", &ClassicIsing::get_measured_spins)
+        .def("reset_measured_spins", &ClassicIsing::reset_measured_spins)
         .def("set_cluster_update_every", &ClassicIsing::set_cluster_update_every, "k"_a)
         .def("set_replica_cluster_update_every", &ClassicIsing::set_replica_cluster_update_every, "k"_a);
 }
