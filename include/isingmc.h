@@ -419,6 +419,16 @@ int isingmc_best_reset(isingmc_states *states);
  *                                  graph creation, int64[n_edges], by the conventions of link_out of isingmc_overlaps: zero
  *                                  couplings count, duplicated entries are separate, an entry a_e == b_e adds +1 per sample and replica
  *   ISINGMC_MOMENTS_PER_REPLICA:   site[r][i] = sum over the samples of replica r of s_i, int64[count][nvars]; no bond sums
+ *   ISINGMC_MOMENTS_PER_RUNG:       a container with a tempering ladder attached: site[i][v] = sum over the samples of
+ *                                  s_v of the configuration that held rung i when the sample was taken, int64[n_rungs][nvars], i in
+ *                                  ladder order; no bond sums.  A sample uses the permutation as it stands on the stream behind its
+ *                                  timestep, before any exchange round that follows: a configuration counts at the beta it was just
+ *                                  swept at.  The kernel reads the permutation on the device; nothing waits on the host.  Samples are
+ *                                  taken inside isingmc_pt_time_steps, isingmc_pt_run (one launch per round while it is on, with the
+ *                                  same decisions and results), isingmc_do_time_steps* and isingmc_icm_between (the move is timestep
+ *                                  t of both containers; each one with this mode on takes its sample behind it).  Memory and limits
+ *                                  are those of the per-replica mode.  Accepted only with the whole ladder on the container (world
+ *                                  size 1, count == n_rungs, slot_offset 0); the order is isingmc_pt_attach, then this.
  * Sites in no edge count like any other; padding positions of a packed container, the bits of a packed group the container does
  * not own and replicas beyond count never count.
  * every > 0 records t0 = the current timestep; from then on, inside isingmc_do_time_steps* and isingmc_run_sampling, a sample of
@@ -433,11 +443,14 @@ int isingmc_best_reset(isingmc_states *states);
  * replica holds at most 2^32 - 1 samples.  The option moments_bytes (default 4 GiB) bounds all of it.
  * Served: exactly the containers isingmc_overlaps serves -- periodic field-free checkerboard lattices of any sign pattern and
  * both replica-packed families.  Refused with ISINGMC_ERR_INVALID and a message, the container unchanged: the f64 CSR family;
- * a tempering ladder attached (and isingmc_pt_attach while accumulation is on: a slot changes its temperature); isingmc_pa_run,
- * isingmc_pa_resample and isingmc_states_append while it is on; ISINGMC_MOMENTS_BONDS together with ISINGMC_MOMENTS_PER_REPLICA;
- * sums larger than moments_bytes. */
+ * a tempering ladder attached unless the sums are per rung (and isingmc_pt_attach while accumulation is on: a slot changes its
+ * temperature); isingmc_pa_run, isingmc_pa_resample and isingmc_states_append while it is on; ISINGMC_MOMENTS_BONDS together with
+ * ISINGMC_MOMENTS_PER_REPLICA; sums larger than moments_bytes; ISINGMC_MOMENTS_PER_RUNG without a ladder attached, on a shard of a
+ * larger ladder, together with either other flag, or in isingmc_run_sampling_moments (it runs no exchange rounds); isingmc_pt_detach
+ * while sums per rung are switched on. */
 #define ISINGMC_MOMENTS_PER_REPLICA 1u
 #define ISINGMC_MOMENTS_BONDS 2u
+#define ISINGMC_MOMENTS_PER_RUNG 4u
 int isingmc_states_set_moments_every(isingmc_states *states, size_t every, unsigned flags);
 int isingmc_states_moments_every(const isingmc_states *states, size_t *every_out, unsigned *flags_out);
 /* enqueue only: one sample at the container's current timestep, whatever the period (never switched on: summed mode, sites alone) */

@@ -15,6 +15,7 @@ FLAG_FORCE_GENERAL = 1
 FLAG_STABLE_PATH = 2
 MOMENTS_PER_REPLICA = 1  # ISINGMC_MOMENTS_*
 MOMENTS_BONDS = 2
+MOMENTS_PER_RUNG = 4
 FAMILIES = ("checkerboard", "csr_f64", "packed_bitsliced", "packed_real")
 
 
@@ -628,10 +629,11 @@ class States:
         _check(lib().isingmc_best_reset(self._h))
 
     # ---- per-site spin sums and per-bond sums over the samples of a run
-    def set_moments_every(self, every, per_replica=False, bonds=False):
+    def set_moments_every(self, every, per_replica=False, bonds=False, per_rung=False):
         """A sample of all replicas follows every timestep t > t0 (now) with (t - t0) % every == 0; 0 switches accumulation off and
-        keeps the sums.  per_replica: sums per replica instead of over all of them; bonds: the sums of s_a s_b per edge-list entry too."""
-        flags = (MOMENTS_PER_REPLICA if per_replica else 0) | (MOMENTS_BONDS if bonds else 0)
+        keeps the sums.  per_replica: sums per replica instead of over all of them; bonds: the sums of s_a s_b per edge-list entry too.
+        per_rung: a container with a whole tempering ladder attached -- sums per rung, whichever slot holds it."""
+        flags = (MOMENTS_PER_REPLICA if per_replica else 0) | (MOMENTS_BONDS if bonds else 0) | (MOMENTS_PER_RUNG if per_rung else 0)
         _check(lib().isingmc_states_set_moments_every(self._h, int(every), flags))
 
     @property
@@ -641,16 +643,24 @@ class States:
         _check(lib().isingmc_states_moments_every(self._h, C.byref(k), C.byref(f)))
         return int(k.value), bool(f.value & MOMENTS_PER_REPLICA), bool(f.value & MOMENTS_BONDS)
 
+    @property
+    def moments_per_rung(self):
+        """Are the sums held (or last set) the sums per rung of a tempering ladder?"""
+        f = C.c_uint()
+        _check(lib().isingmc_states_moments_every(self._h, None, C.byref(f)))
+        return bool(f.value & MOMENTS_PER_RUNG)
+
     def accumulate_moments(self):
         """One sample at the current timestep, whatever the period; enqueue only."""
         _check(lib().isingmc_moments_accumulate(self._h))
 
     def moments(self):
         """(n, site, bond or None): the samples taken and the exact integer sums, True = +1 -- site int64[nvars] (int64[R, nvars] per
-        replica), bond int64[n_edges] in the order of the edge list when bond sums are held.  Synchronises."""
+        replica, int64[n_rungs, nvars] in ladder order per rung), bond int64[n_edges] in the order of the edge list when bond sums are
+        held.  Synchronises."""
         _, per_replica, bonds = self.moments_every
         N = self.graph.nvars
-        site = np.zeros((self.count, N) if per_replica else N, dtype=np.int64)
+        site = np.zeros((self.count, N) if per_replica or self.moments_per_rung else N, dtype=np.int64)
         bond = np.zeros(self.graph.n_edges, dtype=np.int64) if bonds else None
         n = C.c_uint64()
         _check(lib().isingmc_moments_get(self._h, C.byref(n), _p(site), _p(bond)))

@@ -1,4 +1,4 @@
-// libisingmc.so: per-site spin sums and per-bond sums over the samples of a run, kept on the device (DESIGN.md S18,
+// libisingmc.so: per-site spin sums and per-bond sums over the samples of a run, kept on the device (by rung of a tempering ladder S19;
 // isingmc_moments_* and isingmc_states_set_moments_every) -- which containers are served, the totals and their byte budget, the
 // sample enqueued behind a timestep, the read-out in the site numbering and edge order of graph creation.  Nothing here is a
 // kernel: they are in moments_kernels.hip, whose header states what is counted and where.
@@ -6,13 +6,16 @@
 
 static bool mom_per_replica(unsigned flags) { return (flags & ISINGMC_MOMENTS_PER_REPLICA) != 0; }
 static bool mom_bonds(unsigned flags) { return (flags & ISINGMC_MOMENTS_BONDS) != 0; }
+static bool mom_per_rung(unsigned flags) { return (flags & ISINGMC_MOMENTS_PER_RUNG) != 0; }
+// the per-replica and the per-rung sums share time planes and 32-bit totals of the state's shape: their rows are slots or rungs
+static bool mom_rows(unsigned flags) { return mom_per_replica(flags) || mom_per_rung(flags); }
 static size_t mom_state_words(const isingmc_states *s) { return s->packed ? s->groups * size_t(s->g->pk.n_pos) : s->R * s->g->state_words; }
 
 // device bytes of the sums of this container as it is now
 static unsigned long long mom_bytes(const isingmc_states *s, unsigned flags, int k)
 {
     const isingmc_graph *g = s->g;
-    if (mom_per_replica(flags)) return (unsigned long long)(k + 32) * mom_state_words(s) * sizeof(uint32_t);
+    if (mom_rows(flags)) return (unsigned long long)(k + 32) * mom_state_words(s) * sizeof(uint32_t);
     if (!s->packed) return (mom_bonds(flags) ? 3ull : 1ull) * 32 * g->state_words * sizeof(unsigned long long);
     return g->pk.n_pos * sizeof(unsigned long long) + (mom_bonds(flags) ? g->n_edges * (sizeof(unsigned long long) + sizeof(uint2)) : 0ull);
 }
@@ -21,7 +24,11 @@ static unsigned long long mom_bytes(const isingmc_states *s, unsigned flags, int
 static std::string mom_obstacle(const isingmc_states *s, unsigned flags)
 {
     const isingmc_graph *g = s->g;
-    if (flags & ~unsigned(ISINGMC_MOMENTS_PER_REPLICA | ISINGMC_MOMENTS_BONDS)) return "unknown flag: ISINGMC_MOMENTS_PER_REPLICA and ISINGMC_MOMENTS_BONDS are the flags of the moment sums";
+    if (flags & ~unsigned(ISINGMC_MOMENTS_PER_REPLICA | ISINGMC_MOMENTS_BONDS | ISINGMC_MOMENTS_PER_RUNG))
+        return "unknown flag: ISINGMC_MOMENTS_PER_REPLICA, ISINGMC_MOMENTS_BONDS and ISINGMC_MOMENTS_PER_RUNG are the flags of the moment sums";
+    if (mom_per_rung(flags) && (mom_per_replica(flags) || mom_bonds(flags)))
+        return "sums per rung go alone: ISINGMC_MOMENTS_PER_RUNG takes neither ISINGMC_MOMENTS_PER_REPLICA (a rung is held by one slot at a time) "
+               "nor ISINGMC_MOMENTS_BONDS (bond sums per rung are not offered)";
     if (mom_per_replica(flags) && mom_bonds(flags))
         return "bond sums per replica are not offered: ISINGMC_MOMENTS_BONDS goes with the sums over all replicas only";
     if (!s->packed) {
@@ -32,26 +39,30 @@ static std::string mom_obstacle(const isingmc_states *s, unsigned flags)
         const std::string why = lattice_obstacle(g, "moment sums", true, false);
         if (!why.empty()) return why;
     }
-    if (s->pt_attached)
-        return "a tempering ladder is attached: a slot changes its temperature at every exchange, and sums per rung are not implemented "
-               "(isingmc_pt_detach first)";
+    if (s->pt_attached && !mom_per_rung(flags))
+        return "a tempering ladder is attached: a slot changes its temperature at every exchange, so sums per slot or over all slots mix the "
+               "temperatures (ISINGMC_MOMENTS_PER_RUNG sums by rung; or isingmc_pt_detach first)";
+    if (mom_per_rung(flags) && !s->pt_attached)
+        return "sums per rung need a tempering ladder: none is attached to this container (isingmc_pt_attach first, then switch the sums on)";
+    if (mom_per_rung(flags) && (s->pt_world != 1 || s->pt.slot_offset != 0 || s->pt.n_rungs != s->R))
+        return "sums per rung need the whole ladder on this container (world size 1, one slot per rung): a shard of a larger ladder is not served";
     if (mom_bonds(flags) && !g->edge_order_kept)
         return "this lattice is too large for bond sums in the order of its edge list (2 W H must stay below 2^32 unless entry e is bond e)";
     if (mom_bonds(flags) && s->packed && (g->n_edges >> 32)) return "bond sums serve at most 2^32 - 1 edge-list entries";
     if (s->R >> 31) return "moment sums serve at most 2^31 - 1 replicas";
     const int k = s->opt.moments_planes;
-    if (mom_per_replica(flags) && (k < 1 || k > MOM_MAX_TIME_PLANES)) return "the option moments_planes must be 1 .. 16";
+    if (mom_rows(flags) && (k < 1 || k > MOM_MAX_TIME_PLANES)) return "the option moments_planes must be 1 .. 16";
     const unsigned long long need = mom_bytes(s, flags, k), budget = (unsigned long long)std::max(0ll, s->opt.moments_bytes);
     if (need > budget)
         return "the moment sums of this container take " + std::to_string(need) + " bytes of device memory, more than the option moments_bytes = " +
-               std::to_string(budget) + " allows (per-replica totals are 32 times the state; isingmc_states_set_option raises the budget)";
+               std::to_string(budget) + " allows (per-replica and per-rung totals are 32 times the state; isingmc_states_set_option raises the budget)";
     return "";
 }
 
 static int mom_zero_enqueue(isingmc_states *s)
 {
     const unsigned flags = s->mom_flags;
-    if (mom_per_replica(flags)) {
+    if (mom_rows(flags)) {
         const size_t words = mom_state_words(s);
         HIP_TRY(hipMemsetAsync(s->d_mom_planes, 0, size_t(s->mom_k) * words * sizeof(uint32_t), s->stream));
         HIP_TRY(hipMemsetAsync(s->d_mom_totals, 0, 32 * words * sizeof(uint32_t), s->stream));
@@ -71,12 +82,12 @@ static int mom_zero_enqueue(isingmc_states *s)
 static int mom_reserve(isingmc_states *s, unsigned flags)
 {
     const isingmc_graph *g = s->g;
-    const int k = mom_per_replica(flags) ? s->opt.moments_planes : 0;
+    const int k = mom_rows(flags) ? s->opt.moments_planes : 0;
     if (s->mom_have && s->mom_flags == flags && s->mom_R == s->R && s->mom_k == k) return ISINGMC_OK;
     HIP_TRY(stream_quiesce(s->stream)); // recycled blocks: nothing enqueued may still use the old ones
     s->d_mom_site.reset(); s->d_mom_bond.reset(); s->d_mom_edges.reset(); s->d_mom_planes.reset(); s->d_mom_totals.reset();
     s->mom_have = false;
-    if (mom_per_replica(flags)) {
+    if (mom_rows(flags)) {
         const size_t words = mom_state_words(s);
         TRY(dev_alloc(s->d_mom_planes, size_t(k) * words));
         TRY(dev_alloc(s->d_mom_totals, 32 * words));
@@ -137,9 +148,16 @@ int moments_sample_enqueue(isingmc_states *s)
     if (s->n_lanes > 1) TRY(lanes_join(s)); // the sweeps before this sample may have run on replica lanes
     const isingmc_graph *g = s->g;
     const unsigned flags = s->mom_flags;
-    if (mom_per_replica(flags)) {
-        if (s->mom_n >= 0xFFFFFFFFull) return fail(ISINGMC_ERR_INVALID, "the per-replica totals are 32-bit counts: 2^32 - 1 samples are in them (isingmc_moments_reset)");
-        HIP_TRY(moments_launch_add(s->stream, s->d_state, mom_state_words(s), s->mom_k, s->d_mom_planes));
+    if (mom_rows(flags)) {
+        if (s->mom_n >= 0xFFFFFFFFull) return fail(ISINGMC_ERR_INVALID, "the per-replica and per-rung totals are 32-bit counts: 2^32 - 1 samples are in them (isingmc_moments_reset)");
+        if (!mom_per_rung(flags))
+            HIP_TRY(moments_launch_add(s->stream, s->d_state, mom_state_words(s), s->mom_k, s->d_mom_planes));
+        // per rung: the permutation is read by the kernel, as the exchange rounds enqueued so far leave it
+        else if (!s->packed)
+            HIP_TRY(moments_launch_add_by_rung(s->stream, s->d_state, s->d_pt_perm, s->R, g->state_words, s->mom_k, s->d_mom_planes));
+        else
+            HIP_TRY(moments_launch_packed_add_by_rung(s->stream, s->d_state, s->d_pt_perm, s->R, g->pk.n_pos, uint32_t(s->pk_bit0), mom_state_words(s),
+                                                      s->mom_k, s->d_mom_planes));
         if (++s->mom_pending == (1u << s->mom_k) - 1) TRY(mom_flush_enqueue(s));
     } else if (!s->packed) {
         HIP_TRY(moments_launch_lattice_sum(s->stream, s->d_state, g->geom, s->R, mom_bonds(flags), s->d_mom_site));
@@ -206,6 +224,9 @@ extern "C" int isingmc_run_sampling_moments(isingmc_states *s, double beta, size
     if (!s) return fail(ISINGMC_ERR_INVALID, "NULL states");
     if (sampling_freq == 0) return fail(ISINGMC_ERR_INVALID, "sampling_freq must be positive");
     if (!s->has_betas && !std::isfinite(beta)) return fail(ISINGMC_ERR_INVALID, "beta must be finite");
+    if (mom_per_rung(flags))
+        return fail(ISINGMC_ERR_INVALID, "the sampling run takes no ISINGMC_MOMENTS_PER_RUNG: it runs no exchange rounds; a ladder runs through isingmc_pt_run / "
+                                         "isingmc_pt_time_steps with the sums switched on (isingmc_states_set_moments_every)");
     if (s->mom_every) return fail(ISINGMC_ERR_INVALID, "moment sums are switched on for this container already: the sampling run sets its own period (switch accumulation off first)");
     {
         const std::string why = mom_obstacle(s, flags);
@@ -217,7 +238,7 @@ extern "C" int isingmc_run_sampling_moments(isingmc_states *s, double beta, size
     s->mom_last_t = 0;
     const bool may_strip = may_use_strips(s) && (strip_plan(s, thermalization).use || strip_plan(s, n_samples * sampling_freq).use);
     TRY(with_strip_retry(s, may_strip, [&] { return run_sampling_moments_impl(s, beta, thermalization, sampling_freq, n_samples); }));
-    if (mom_per_replica(s->mom_flags)) TRY(mom_flush_enqueue(s));
+    if (mom_rows(s->mom_flags)) TRY(mom_flush_enqueue(s));
     if (energies_out) return isingmc_get_energies(s, energies_out); // waits
     HIP_TRY(hipStreamSynchronize(s->stream));
     return strip_error(strip_check(s));
@@ -232,23 +253,24 @@ extern "C" int isingmc_moments_get(isingmc_states *s, uint64_t *n_samples_out, i
     if (bond_out && !mom_bonds(flags)) return fail(ISINGMC_ERR_INVALID, "no bond sums are held: switch accumulation on with ISINGMC_MOMENTS_BONDS (bond_out may be NULL)");
     TRY(use_device(s->g->device));
     const isingmc_graph *g = s->g;
-    if (mom_per_replica(flags)) TRY(mom_flush_enqueue(s));
+    if (mom_rows(flags)) TRY(mom_flush_enqueue(s));
     HIP_TRY(hipStreamSynchronize(s->stream));
     TRY(strip_error(strip_check(s)));
     if (n_samples_out) *n_samples_out = s->mom_n;
     const int64_t n = int64_t(s->mom_n), nR = n * int64_t(s->R);
     const size_t N = g->nvars;
-    if (mom_per_replica(flags)) {
+    if (mom_rows(flags)) { // row r: replica r's slot, or rung r itself
+        const bool by_rung = mom_per_rung(flags);
         if (!site_out || s->R == 0) return ISINGMC_OK;
         std::vector<uint32_t> h;
         TRY(read_back(s, h, s->d_mom_totals.get(), 32 * mom_state_words(s)));
-        if (s->packed) { // totals[slot][n_pos]
+        if (s->packed) { // totals[slot or rung][n_pos]
             const size_t n_pos = g->pk.n_pos;
             parallel_for(s->R, [&](size_t r) {
-                const uint32_t *row = h.data() + counter_slot(s, r) * n_pos;
+                const uint32_t *row = h.data() + (by_rung ? r : counter_slot(s, r)) * n_pos;
                 for (size_t i = 0; i < N; i++) site_out[r * N + i] = 2 * int64_t(row[g->pos[i]]) - n;
             }, N * 8);
-        } else { // totals[replica][32][state words]
+        } else { // totals[replica or rung][32][state words]
             const LatGeom &L = g->geom;
             const size_t sw = g->state_words;
             parallel_for(s->R, [&](size_t r) {

@@ -6,6 +6,10 @@
 //   mom_pk_bond_kernel     ... one thread per edge-list entry, popcount of the agreement of its two positions' words
 //   mom_add_kernel         per replica: one thread per state word, the word into the K time planes in global memory
 //   mom_flush_kernel       per replica: one thread per state word, its K planes expanded into 32 32-bit totals and cleared
+//   mom_add_by_rung_kernel     per rung of a tempering ladder, checkerboard path: mom_add_kernel with the source row
+//                              routed through the ladder's permutation, one rung per blockIdx.y
+//   mom_pk_add_by_rung_kernel  ... packed paths: one thread per position of a destination group, which gathers its word bit by bit
+//                              from the slots that hold the group's 32 rungs
 // One owner per total: no atomics, no reductions.
 #include "moments_kernels.hpp"
 
@@ -18,6 +22,7 @@ namespace isingmc {
 namespace {
 
 constexpr uint32_t MOM_MAX_BLOCKS = 1u << 20; // grid-stride beyond this many workgroups
+constexpr uint32_t MOM_MAX_GRID_Y = 65535;    // ... and beyond this many rungs or destination groups on blockIdx.y
 
 // the slots of group g that the container owns: [32 g, 32 g + 32) cut with [bit0, bit0 + n_owned)
 __device__ __forceinline__ uint32_t mom_owned_mask(uint32_t g, uint32_t bit0, uint32_t n_owned)
@@ -125,6 +130,75 @@ __global__ __launch_bounds__(256) void mom_flush_kernel(uint32_t *__restrict__ p
     }
 }
 
+// grid: (word blocks, rungs): the rung is uniform per workgroup, so perm[rung] is one scalar load and both rows are streamed
+__global__ __launch_bounds__(256) void mom_add_by_rung_kernel(const uint32_t *__restrict__ state, const uint32_t *__restrict__ perm,
+                                                              const uint32_t n_rungs, const uint32_t row_words, const int k,
+                                                              uint32_t *__restrict__ planes)
+{
+    const size_t n_words = size_t(n_rungs) * row_words;
+    for (uint32_t rung = blockIdx.y; rung < n_rungs; rung += gridDim.y) {
+        const uint32_t slot = perm[rung];
+        if (slot >= n_rungs) continue; // (a permutation of the rungs: never taken)
+        const uint32_t *src = state + size_t(slot) * row_words;
+        uint32_t *dst = planes + size_t(rung) * row_words;
+        for (uint32_t w = blockIdx.x * 256 + threadIdx.x; w < row_words; w += gridDim.x * 256) vc_add_strided(dst + w, n_words, k, src[w]);
+    }
+}
+
+// grid: (position blocks, destination groups).  Destination word (G, p) takes bit b from the slot that holds rung 32 G + b: bit
+// q & 31 of state word (q >> 5, p), q = bit0 + slot.  The 32 sources of the group are resolved once per workgroup into LDS -- bit
+// position, source group, and the set of rungs that share that source group -- and read back wave-uniformly, so the loop below
+// is scalar control flow around loads in which the lanes of a wave read consecutive positions of ONE source group: each source
+// word is loaded once however many of the group's rungs it feeds.
+__global__ __launch_bounds__(256) void mom_pk_add_by_rung_kernel(const uint32_t *__restrict__ state, const uint32_t *__restrict__ perm,
+                                                                 const uint32_t n_rungs, const uint32_t n_pos, const uint32_t bit0,
+                                                                 const uint32_t dst_groups, const size_t n_words, const int k,
+                                                                 uint32_t *__restrict__ planes)
+{
+    __shared__ uint32_t src[32];  // bit0 + slot of rung 32 G + b; ~0u: no such rung
+    __shared__ uint32_t same[32]; // the rungs b' of this group whose source lies in the same state group as b's
+    __shared__ uint32_t valid;
+    for (uint32_t G = blockIdx.y; G < dst_groups; G += gridDim.y) {
+        if (threadIdx.x < 32) {
+            const uint32_t rung = 32 * G + threadIdx.x;
+            uint32_t q = ~0u;
+            if (rung < n_rungs) {
+                const uint32_t slot = perm[rung];
+                if (slot < n_rungs) q = bit0 + slot; // (a permutation of the rungs: always)
+            }
+            src[threadIdx.x] = q;
+        }
+        __syncthreads();
+        if (threadIdx.x < 32) {
+            const uint32_t mine = src[threadIdx.x];
+            uint32_t m = 0, v = 0;
+            for (uint32_t b = 0; b < 32; b++) {
+                const uint32_t q = src[b];
+                if (q != ~0u) v |= 1u << b;
+                if (q != ~0u && mine != ~0u && (q >> 5) == (mine >> 5)) m |= 1u << b;
+            }
+            same[threadIdx.x] = m;
+            if (threadIdx.x == 0) valid = v;
+        }
+        __syncthreads();
+        for (uint32_t p = blockIdx.x * 256 + threadIdx.x; p < n_pos; p += gridDim.x * 256) {
+            uint32_t word = 0;
+            for (uint32_t todo = __builtin_amdgcn_readfirstlane(valid); todo;) {
+                const uint32_t b0 = __builtin_ctz(todo);
+                uint32_t m = __builtin_amdgcn_readfirstlane(same[b0]);
+                todo &= ~m;
+                const uint32_t w = state[size_t(__builtin_amdgcn_readfirstlane(src[b0]) >> 5) * n_pos + p];
+                for (; m; m &= m - 1) {
+                    const uint32_t b = __builtin_ctz(m);
+                    word |= ((w >> (__builtin_amdgcn_readfirstlane(src[b]) & 31u)) & 1u) << b;
+                }
+            }
+            vc_add_strided(planes + size_t(G) * n_pos + p, n_words, k, word);
+        }
+        __syncthreads(); // the tables are rewritten for the next group
+    }
+}
+
 namespace {
 
 uint32_t mom_blocks(size_t items) { return uint32_t(std::min<size_t>((items + 255) / 256, MOM_MAX_BLOCKS)); }
@@ -162,6 +236,25 @@ hipError_t moments_launch_flush(hipStream_t stream, uint32_t *planes, size_t n_r
 {
     if (n_rows * row_words == 0) return hipSuccess;
     hipLaunchKernelGGL(mom_flush_kernel, dim3(mom_blocks(n_rows * row_words)), dim3(256), 0, stream, planes, n_rows, row_words, k, totals);
+    return hipGetLastError();
+}
+
+hipError_t moments_launch_add_by_rung(hipStream_t stream, const uint32_t *state, const uint32_t *perm, size_t n_rungs, size_t row_words, int k,
+                                      uint32_t *planes)
+{
+    if (n_rungs * row_words == 0) return hipSuccess;
+    hipLaunchKernelGGL(mom_add_by_rung_kernel, dim3(mom_blocks(row_words), uint32_t(std::min<size_t>(n_rungs, MOM_MAX_GRID_Y))), dim3(256), 0, stream,
+                       state, perm, uint32_t(n_rungs), uint32_t(row_words), k, planes);
+    return hipGetLastError();
+}
+
+hipError_t moments_launch_packed_add_by_rung(hipStream_t stream, const uint32_t *state, const uint32_t *perm, size_t n_rungs, uint32_t n_pos,
+                                             uint32_t bit0, size_t n_words, int k, uint32_t *planes)
+{
+    const size_t dst_groups = (n_rungs + 31) / 32;
+    if (dst_groups * n_pos == 0) return hipSuccess;
+    hipLaunchKernelGGL(mom_pk_add_by_rung_kernel, dim3(mom_blocks(n_pos), uint32_t(std::min<size_t>(dst_groups, MOM_MAX_GRID_Y))), dim3(256), 0,
+                       stream, state, perm, uint32_t(n_rungs), n_pos, bit0, uint32_t(dst_groups), n_words, k, planes);
     return hipGetLastError();
 }
 

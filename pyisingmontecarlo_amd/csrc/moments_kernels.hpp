@@ -39,4 +39,15 @@ hipError_t moments_launch_add(hipStream_t stream, const uint32_t *state, size_t 
 // goes to totals[(32 r + b) row_words + w].  Checkerboard: a row is a replica; packed: a row is a group, 32 r + b its replica slots.
 hipError_t moments_launch_flush(hipStream_t stream, uint32_t *planes, size_t n_rows, size_t row_words, int k, uint32_t *totals);
 
+// ---- per rung of a tempering ladder: the same planes and totals, their rows rungs instead of slots ------------------
+// perm u32[n_rungs] (device): rung -> the slot that holds it, read by the kernel where the exchange rounds leave it.
+// Checkerboard path: planes u32[k][n_rungs row_words], row i += state row perm[i] (state u32[n_rungs][row_words]).
+hipError_t moments_launch_add_by_rung(hipStream_t stream, const uint32_t *state, const uint32_t *perm, size_t n_rungs, size_t row_words, int k,
+                                      uint32_t *planes);
+// Packed paths: planes u32[k][n_words] of which the first ceil(n_rungs / 32) n_pos words are used; bit b of destination word (G, p) +=
+// bit q & 31 of state word (q >> 5, p), q = bit0 + perm[32 G + b]; rungs from n_rungs on add nothing.  The state must hold the groups
+// up to (bit0 + n_rungs - 1) >> 5.  Padding positions are counted like any other; the host reads none of them.
+hipError_t moments_launch_packed_add_by_rung(hipStream_t stream, const uint32_t *state, const uint32_t *perm, size_t n_rungs, uint32_t n_pos,
+                                             uint32_t bit0, size_t n_words, int k, uint32_t *planes);
+
 } // namespace isingmc

@@ -331,6 +331,18 @@ static int between_prepare(isingmc_states *a, isingmc_states *b, const uint32_t 
     return ISINGMC_OK;
 }
 
+// Sums per rung: the move has been a timestep of both containers, and whichever of them has its period fall on it
+// takes its sample, each on its own stream (b's waits for the move).  The other modes of S18 take no sample here, as before.
+static int between_sample(isingmc_states *a, isingmc_states *b)
+{
+    for (isingmc_states *s : {a, b})
+        if (s->mom_every && (s->mom_flags & ISINGMC_MOMENTS_PER_RUNG) && (s->t - s->mom_t0) % s->mom_every == 0) {
+            TRY(moments_sample_enqueue(s));
+            s->mom_last_t = s->t;
+        }
+    return ISINGMC_OK;
+}
+
 // behind the launches: b goes on with the new configurations, and the move has been timestep t of both containers
 static int between_finish(isingmc_states *a, isingmc_states *b, size_t n_pairs)
 {
@@ -342,7 +354,7 @@ static int between_finish(isingmc_states *a, isingmc_states *b, size_t n_pairs)
         s->t++;
         s->meas_fresh = false; // cached ladder energies (and those a strip launch left behind) belong to the configurations before the move
     }
-    return ISINGMC_OK;
+    return between_sample(a, b);
 }
 
 extern "C" int isingmc_icm_between(isingmc_states *a, isingmc_states *b, const uint32_t *slots_a, const uint32_t *slots_b, size_t n_pairs)
@@ -383,7 +395,7 @@ extern "C" int isingmc_icm_between(isingmc_states *a, isingmc_states *b, const u
     if (n_pairs == 0) { // time passes all the same
         a->t++;
         b->t++;
-        return ISINGMC_OK;
+        return between_sample(a, b);
     }
     for (isingmc_states *s : {a, b})
         if (s->n_lanes > 1) TRY(lanes_join(s));

@@ -273,6 +273,52 @@ class ClassicalTempering:
         rungs[self.get_permutation()] = np.arange(len(self._betas))
         return e, st, t, rungs
 
+    # -- thermal averages <s_i> at every rung, summed on the device ------------------------------------------------
+    def _measured_spins_states(self):
+        """The container(s) that hold the sums per rung, one per copy; ValueError where the ladder cannot have them."""
+        if self._devices is not None:
+            raise ValueError("spin sums per rung are for a ladder on one device: not with devices=[...] (a shard holds part of the ladder)")
+        if self._world > 1:
+            raise ValueError("spin sums per rung are for a ladder on one process: not inside a torch.distributed group of several ranks")
+        self._materialise()
+        copies = self._pair if self._pair is not None else [self]
+        for c in copies:
+            if not hasattr(c._states, "set_moments_every"):
+                raise ValueError("this engine keeps no spin sums (set_moments_every)")
+            if not c._on_stream:
+                raise ValueError("spin sums per rung need the ladder on the device's stream: this ladder takes the host swap step "
+                                 "(ISINGMC_PT_HOST=1, or a container that pt_can_attach refuses)")
+        return [c._states for c in copies]
+
+    def set_measure_spins_every(self, k):
+        """A sample of every rung follows each k-th timestep from now on (0: off, the sums stay): rung i adds the configuration that
+        holds beta i at that moment, before any exchange round that follows the timestep.  Before or after the first timestep (the
+        ladder is built here if it is not yet); no configuration, energy, random number or exchange decision changes."""
+        if int(k) < 0:
+            raise ValueError("k must not be negative")
+        for st in self._measured_spins_states():
+            st.set_moments_every(int(k), per_rung=True)
+
+    def get_measured_spins(self):
+        """(n_samples, means float64[G, N]): the thermal average of every spin at every rung over the samples taken, True = +1, in
+        the order of get_betas() (zeros before the first sample).  copies=2: float64[2, G, N], one leading row per copy."""
+        out = []
+        for st in self._measured_spins_states():
+            if not st.moments_per_rung:
+                raise ValueError("no spin sums per rung are held: call set_measure_spins_every(k) first")
+            n, site, _ = st.moments()
+            out.append((n, site / float(max(n, 1))))
+        if self._pair is None:
+            return out[0]
+        if out[0][0] != out[1][0]:   # (both copies stand at one timestep with one period)
+            raise RuntimeError("the two copies of the ladder hold different numbers of samples")
+        return out[0][0], np.stack([m for _, m in out])
+
+    def reset_measured_spins(self):
+        """Sums and sample count back to zero; the period stays."""
+        for st in self._measured_spins_states():
+            st.reset_moments()
+
     # -- copies=2: the two ladders, cut at exchange rounds and at cluster moves ------------------------------------------------
     def _materialise_pair(self):
         if self._states is not None:
