@@ -132,6 +132,16 @@ int isingmc_host_colour_graph(const uint64_t *edge_a, const uint64_t *edge_b, si
 int isingmc_host_pt_swap_round(uint64_t seed, uint64_t round, size_t n_rungs, const double *betas,
                                const double *slot_energy, uint32_t *perm, uint64_t *swaps_out);
 
+/* The ladder statistics of one exchange round (the rule is stated at isingmc_pt_set_statistics), the host twin of
+ * what the exchange kernels keep on the device: called after isingmc_host_pt_swap_round with the round's number, the permutation
+ * before and after it and the energies it decided from, on caller-held arrays: attempts / accepts uint64[n_rungs - 1] (may be
+ * NULL for n_rungs < 2), n_up / n_down uint64[n_rungs], sum_e / sum_e2 double[n_rungs], round_trips uint64[n_rungs] and labels
+ * uint8[n_rungs] by slot, *rounds. */
+int isingmc_host_pt_statistics_round(uint64_t round, size_t n_rungs, const uint32_t *perm_before, const uint32_t *perm_after,
+                                     const double *slot_energy, uint64_t *attempts, uint64_t *accepts, uint64_t *n_up,
+                                     uint64_t *n_down, double *sum_e, double *sum_e2, uint64_t *round_trips, uint8_t *labels,
+                                     uint64_t *rounds);
+
 /* The source table of one population-annealing resampling, the host twin of what isingmc_pa_resample computes
  * on the device.  energies[n] are the replicas' energies (the f64 values of isingmc_get_energies), dbeta = beta_to - beta_from of
  * either sign.  E_ref = min E for dbeta >= 0, else max E; x[r] = -(dbeta * (E[r] - E_ref)), three separately rounded f64
@@ -495,7 +505,8 @@ int isingmc_pt_attach(isingmc_states *states, const double *ladder_betas, size_t
  * isingmc_last_error() says why): the ranks of a sharded ladder agree on the answer BEFORE any of them attaches */
 int isingmc_pt_can_attach(const isingmc_states *states, size_t n_rungs, size_t slot_offset, size_t slots_per_rank,
                           size_t world_size, int *ok_out);
-/* release the ladder (synchronises); configurations and timestep stay, the per-replica betas are cleared */
+/* release the ladder (synchronises); configurations and timestep stay, the per-replica betas are cleared; the ladder's
+ * statistics (below) are discarded with it: the next ladder starts without any, switched off */
 int isingmc_pt_detach(isingmc_states *states);
 /* device pointers: local = double[slots_per_rank] (send buffer), all = double[world_size*slots_per_rank] */
 int isingmc_pt_buffers(isingmc_states *states, void **d_local_out, void **d_all_out, size_t *per_rank_out);
@@ -507,6 +518,37 @@ int isingmc_pt_run(isingmc_states *states, size_t timesteps, size_t swap_every);
 int isingmc_pt_swap(isingmc_states *states);                         /* enqueue only */
 /* synchronises; perm_out = uint32[n_rungs] (rung -> slot), exchange rounds done, accepted swaps */
 int isingmc_pt_state(isingmc_states *states, uint32_t *perm_out, uint64_t *round_out, uint64_t *swaps_out);
+
+/* ---- ladder statistics (no reference counterpart): what choosing the betas needs, kept on the device ----
+ * While they are on, every exchange round -- isingmc_pt_swap, and the rounds that the strips of isingmc_pt_run's persistent
+ * launch decide among themselves: statistics do NOT put that call on one launch per round -- updates, with `round` the
+ * round's number, p / p' the permutation rung -> slot before / after it and E[slot] the energies it decides from:
+ *   1. every rung i: sum_e[i] += E[p[i]], sum_e2[i] += E[p[i]] * E[p[i]] (f64; the product and both additions rounded
+ *      separately, one addition per rung and round in round order: numpy reproduces the sums bit for bit).  A configuration
+ *      counts at the beta it was just swept at.
+ *   2. every pair (i, i + 1) with i = round (mod 2), i + 1 < n_rungs: attempts[i] += 1, accepts[i] += 1 if it was exchanged.
+ *   3. n_rungs >= 2, with one label per slot (0 = none, the start; 1 = up; 2 = down): the slot s = p'[0] gains a round trip if
+ *      its label is down, and becomes up; the slot p'[n_rungs - 1] becomes down; then every rung i adds (label[p'[i]] == up)
+ *      to n_up[i] and (label[p'[i]] == down) to n_down[i].  n_up / (n_up + n_down) is the flow fraction of feedback-optimised
+ *      ladders (Katzgraber, Trebst, Huse and Troyer 2006).
+ *   4. rounds += 1.
+ * The relabelling launch of isingmc_pt_attach updates nothing.  Decisions, configurations, energies and random numbers do not
+ * change.  A shard of a larger ladder is accepted: every rank's exchange kernel sees the whole permutation and all gathered
+ * energies, so every rank holds the statistics of the whole ladder, identical, without communication.
+ *
+ * set_statistics: the first switch-on allocates one device block (2 (n - 1) + 2 n uint64 counters, 2 n f64 sums, n uint64 round
+ * trips, n label bytes, the round count) and zeroes it on the stream; on = 0 stops counting and keeps the values.
+ * statistics_get (synchronises): attempts / accepts uint64[n_rungs - 1]; n_up / n_down uint64[n_rungs] and sum_e / sum_e2
+ * double[n_rungs] by rung; round_trips uint64[n_rungs] and labels uint8[n_rungs] by GLOBAL slot; *in_kernel_rounds_out = how many
+ * of the counted rounds were decided inside persistent launches (a host count).  Any pointer may be NULL.
+ * statistics_reset (enqueue only): everything back to zero, the labels to none; the setting stays.
+ * Refused with ISINGMC_ERR_INVALID, container unchanged: no ladder attached; get or reset before the first switch-on. */
+int isingmc_pt_set_statistics(isingmc_states *states, int on);
+int isingmc_pt_statistics_get(isingmc_states *states, uint64_t *rounds_out, uint64_t *in_kernel_rounds_out, uint64_t *attempts_out,
+                              uint64_t *accepts_out, uint64_t *n_up_out, uint64_t *n_down_out, double *sum_e_out, double *sum_e2_out,
+                              uint64_t *round_trips_out, uint8_t *labels_out);
+int isingmc_pt_statistics_reset(isingmc_states *states);
+
 /* the engine's hipStream_t (for enqueuing the collective) and a host-side wait for it */
 int isingmc_states_stream(isingmc_states *states, void **stream_out);
 int isingmc_synchronize(isingmc_states *states);

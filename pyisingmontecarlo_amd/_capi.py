@@ -43,6 +43,7 @@ _PROTOTYPES = {
     "isingmc_host_colour_graph": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, _vp, C.POINTER(C.c_uint32)]),
     "isingmc_host_pt_swap_round": (C.c_int, [C.c_uint64, C.c_uint64, C.c_size_t, _vp, _vp, _vp,
                                              C.POINTER(C.c_uint64)]),
+    "isingmc_host_pt_statistics_round": (C.c_int, [C.c_uint64, C.c_size_t] + [_vp] * 11 + [C.POINTER(C.c_uint64)]),
     "isingmc_host_pa_sources": (C.c_int, [C.c_uint64, C.c_uint64, C.c_size_t, _vp, C.c_double, _vp, C.POINTER(C.c_uint64),
                                           C.POINTER(C.c_double)]),
     "isingmc_host_class_segments": (C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, C.POINTER(C.c_size_t), _vp,
@@ -115,6 +116,9 @@ _PROTOTYPES = {
     "isingmc_pt_run": (C.c_int, [_vp, C.c_size_t, C.c_size_t]),
     "isingmc_pt_swap": (C.c_int, [_vp]),
     "isingmc_pt_state": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "isingmc_pt_set_statistics": (C.c_int, [_vp, C.c_int]),
+    "isingmc_pt_statistics_get": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)] + [_vp] * 8),
+    "isingmc_pt_statistics_reset": (C.c_int, [_vp]),
     "isingmc_pa_resample": (C.c_int, [_vp, C.c_double, C.c_uint64, C.c_uint64]),
     "isingmc_pa_apply_sources": (C.c_int, [_vp, _vp]),
     "isingmc_pa_run": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_uint64, _vp, _vp, _vp, _vp]),
@@ -277,6 +281,34 @@ def pt_swap_round(seed, rnd, betas, slot_energy, perm):
     _check(lib().isingmc_host_pt_swap_round(C.c_uint64(int(seed)), C.c_uint64(int(rnd)), len(betas), _p(betas),
                                             _p(slot_energy), _p(perm), C.byref(swaps)))
     return swaps.value
+
+
+def pt_statistics_zeros(n_rungs):
+    """The raw ladder statistics of a ladder of n_rungs before its first round: what States.pt_statistics()
+    returns, as caller-held arrays for pt_statistics_round."""
+    n = int(n_rungs)
+    out = {k: np.zeros(max(n - 1, 0), dtype=np.uint64) for k in ("attempts", "accepts")}
+    out.update({k: np.zeros(n, dtype=np.uint64) for k in ("n_up", "n_down", "round_trips")})
+    out.update({k: np.zeros(n, dtype=np.float64) for k in ("sum_e", "sum_e2")})
+    out["labels"] = np.zeros(n, dtype=np.uint8)
+    out["rounds"], out["in_kernel_rounds"] = 0, 0
+    return out
+
+
+def pt_statistics_round(stats, rnd, perm_before, perm_after, slot_energy):
+    """One exchange round's update of `stats` (pt_statistics_zeros) in place, after pt_swap_round: the host twin of the kernels."""
+    pb, pa, e = _arr(perm_before, np.uint32), _arr(perm_after, np.uint32), _arr(slot_energy, np.float64)
+    n = len(stats["labels"])
+    if not (len(pb) == len(pa) == n and len(e) >= n):
+        raise ValueError("permutations and energies must cover the ladder's rungs")
+    for k, dt in (("attempts", np.uint64), ("accepts", np.uint64), ("n_up", np.uint64), ("n_down", np.uint64), ("sum_e", np.float64),
+                  ("sum_e2", np.float64), ("round_trips", np.uint64), ("labels", np.uint8)):
+        assert stats[k].dtype == dt and stats[k].flags.c_contiguous
+    rounds = C.c_uint64(int(stats["rounds"]))
+    _check(lib().isingmc_host_pt_statistics_round(C.c_uint64(int(rnd)), n, _p(pb), _p(pa), _p(e), _p(stats["attempts"]),
+                                                  _p(stats["accepts"]), _p(stats["n_up"]), _p(stats["n_down"]), _p(stats["sum_e"]),
+                                                  _p(stats["sum_e2"]), _p(stats["round_trips"]), _p(stats["labels"]), C.byref(rounds)))
+    stats["rounds"] = rounds.value
 
 
 def pa_sources(seed, step, energies, dbeta):
@@ -788,6 +820,23 @@ class States:
         rnd, swaps = C.c_uint64(), C.c_uint64()
         _check(lib().isingmc_pt_state(self._h, _p(perm), C.byref(rnd), C.byref(swaps)))
         return perm, rnd.value, swaps.value
+
+    # ---- ladder statistics
+    def pt_set_statistics(self, on=True):
+        _check(lib().isingmc_pt_set_statistics(self._h, int(bool(on))))
+
+    def pt_statistics(self):
+        """The raw statistics (synchronises): dict(rounds, in_kernel_rounds, attempts, accepts, n_up, n_down, sum_e, sum_e2 by rung /
+        pair, round_trips, labels by global slot)."""
+        out = pt_statistics_zeros(getattr(self, "_pt_rungs", 0))
+        rounds, inside = C.c_uint64(), C.c_uint64()
+        _check(lib().isingmc_pt_statistics_get(self._h, C.byref(rounds), C.byref(inside), *(_p(out[k]) for k in (
+            "attempts", "accepts", "n_up", "n_down", "sum_e", "sum_e2", "round_trips", "labels"))))
+        out["rounds"], out["in_kernel_rounds"] = rounds.value, inside.value
+        return out
+
+    def pt_reset_statistics(self):
+        _check(lib().isingmc_pt_statistics_reset(self._h))
 
     def raw_state(self):
         """The device words as they lie in memory, uint32 (one-dimensional): padding and unowned bits of a packed container included."""

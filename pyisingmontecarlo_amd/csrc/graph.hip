@@ -167,6 +167,22 @@ extern "C" int isingmc_host_pt_swap_round(uint64_t seed, uint64_t round, size_t 
     return ISINGMC_OK;
 }
 
+extern "C" int isingmc_host_pt_statistics_round(uint64_t round, size_t n_rungs, const uint32_t *perm_before, const uint32_t *perm_after,
+                                                const double *slot_energy, uint64_t *attempts, uint64_t *accepts, uint64_t *n_up,
+                                                uint64_t *n_down, double *sum_e, double *sum_e2, uint64_t *round_trips, uint8_t *labels,
+                                                uint64_t *rounds)
+{
+    if (!rounds) return fail(ISINGMC_ERR_INVALID, "NULL argument");
+    if (n_rungs && (!perm_before || !perm_after || !slot_energy || !n_up || !n_down || !sum_e || !sum_e2 || !round_trips || !labels))
+        return fail(ISINGMC_ERR_INVALID, "NULL argument");
+    if (n_rungs >= 2 && (!attempts || !accepts)) return fail(ISINGMC_ERR_INVALID, "NULL argument");
+    for (size_t i = 0; i < n_rungs; i++)
+        if (perm_before[i] >= n_rungs || perm_after[i] >= n_rungs) return fail(ISINGMC_ERR_INVALID, "perm is not a permutation of the rungs");
+    pt_statistics_round(round, n_rungs, perm_before, perm_after, slot_energy, attempts, accepts, n_up, n_down, sum_e, sum_e2, round_trips,
+                        labels, rounds);
+    return ISINGMC_OK;
+}
+
 extern "C" int isingmc_host_pa_sources(uint64_t seed, uint64_t step, size_t n, const double *energies, double dbeta, uint32_t *src_out,
                                        uint64_t *sum_out, double *eref_out)
 {

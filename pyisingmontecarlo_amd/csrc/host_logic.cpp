@@ -269,6 +269,36 @@ uint64_t pt_swap_round(uint64_t seed, uint64_t round, size_t n_rungs, const doub
     return swaps;
 }
 
+void pt_statistics_round(uint64_t round, size_t n_rungs, const uint32_t *perm_before, const uint32_t *perm_after, const double *slot_energy,
+                         uint64_t *attempts, uint64_t *accepts, uint64_t *n_up, uint64_t *n_down, double *sum_e, double *sum_e2,
+                         uint64_t *round_trips, uint8_t *labels, uint64_t *rounds)
+{
+    for (size_t i = 0; i < n_rungs; i++) {
+        // (the volatile temporaries keep a compiler that contracts by default from fusing the product into the second sum)
+        const double e = slot_energy[perm_before[i]];
+        volatile double sq = e * e;
+        volatile double s = sum_e[i] + e;
+        volatile double s2 = sum_e2[i] + sq;
+        sum_e[i] = s;
+        sum_e2[i] = s2;
+    }
+    for (size_t i = round & 1; i + 1 < n_rungs; i += 2) {
+        attempts[i] += 1;
+        if (perm_after[i] != perm_before[i]) accepts[i] += 1;
+    }
+    if (n_rungs >= 2) {
+        const uint32_t cold = perm_after[0], hot = perm_after[n_rungs - 1];
+        if (labels[cold] == 2) round_trips[cold] += 1;
+        labels[cold] = 1;
+        labels[hot] = 2;
+        for (size_t i = 0; i < n_rungs; i++) {
+            n_up[i] += labels[perm_after[i]] == 1;
+            n_down[i] += labels[perm_after[i]] == 2;
+        }
+    }
+    *rounds += 1;
+}
+
 // ---- population annealing: the resampling rule ----------------------------------------------
 uint64_t pa_sources(uint64_t seed, uint64_t step, size_t n, const double *energies, double dbeta, uint32_t *src_out, double *eref_out)
 {

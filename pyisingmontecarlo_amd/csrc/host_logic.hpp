@@ -66,6 +66,16 @@ Colouring greedy_colouring(const Adjacency &A, size_t nvars);
 uint64_t pt_swap_round(uint64_t seed, uint64_t round, size_t n_rungs, const double *betas,
                        const double *slot_energy, uint32_t *perm);
 
+// The ladder statistics of one exchange round (device twins: pt_swap_kernel and the exchange rounds of the strip
+// kernel), called after pt_swap_round with the permutation before and after it and the energies it decided from.  Per rung:
+// sum_e += E, sum_e2 += E * E of the slot that held it before the round (product and additions rounded separately); per pair of
+// the round's parity: attempts, and accepts where the entries changed; n_rungs >= 2: the slot now at rung 0 completes a round trip
+// if it was labelled DOWN (2) and becomes UP (1), the slot now at the last rung becomes DOWN, then every rung counts the label
+// of the slot it now holds; *rounds += 1.  round_trips and labels are indexed by slot, the other arrays by rung (pairs: lower rung).
+void pt_statistics_round(uint64_t round, size_t n_rungs, const uint32_t *perm_before, const uint32_t *perm_after, const double *slot_energy,
+                         uint64_t *attempts, uint64_t *accepts, uint64_t *n_up, uint64_t *n_down, double *sum_e, double *sum_e2,
+                         uint64_t *round_trips, uint8_t *labels, uint64_t *rounds);
+
 // The source table of one population-annealing resampling (device twin: pa_kernels.hip).  Weights
 // W[r] = floor(det_exp(-(dbeta (E[r] - E_ref))) 2^32) with E_ref = min E (dbeta >= 0) or max E, S = sum W, inclusive prefix sums C;
 // offset u = mulhi64(U, S) with U the low 64 bits of Philox4x32-10({step lo, step hi, 0, "PARS"}, seed); new slot j copies the

@@ -315,6 +315,9 @@ struct isingmc_states {
     DevBlock<unsigned long long> d_pt_counters;
     size_t pt_per = 0, pt_world = 1;
     std::vector<double> ladder_betas; // host copy of d_pt_ladder (two ladders are compared without a device read)
+    DevBlock<unsigned long long> d_pt_stats; // ladder statistics: the block of PtStats, from the first switch-on to the detach
+    bool pt_stats_on = false;                // s->pt.stats == d_pt_stats while on, nullptr while off
+    uint64_t pt_in_kernel_rounds = 0;        // rounds counted inside persistent strip launches (host count: which path a run took)
     // Swendsen-Wang cluster steps (cluster_kernels.hpp): timestep t is one when cluster_every > 0 and t % cluster_every == cluster_every - 1
     size_t cluster_every = 0;
     DevBlock<uint32_t> d_cl_stats; // [cl_stats_cap][2]: clusters, largest cluster of the last cluster step (packed: per counter slot)

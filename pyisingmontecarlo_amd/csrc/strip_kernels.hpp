@@ -26,6 +26,7 @@
 #pragma once
 #include "lattice_kernels.hpp"
 #include "strip_types.hpp"
+#include "tempering_types.hpp"
 
 namespace isingmc {
 
@@ -75,6 +76,38 @@ __device__ __forceinline__ bool strip_wait_granule(const unsigned long long *p, 
             return false;
         }
     }
+}
+
+// Ladder statistics of the rounds inside the launch, one lane's work per replica and round.
+// Step 1, by the strip that posts the replica's total, BEFORE the release store of the post: the one addition of this round to
+// sum_e / sum_e2 of the replica's rung.  Whoever holds the rung in the next round held it in this one or was this holder's
+// partner: every one of its strips has read this post behind an agent-scope acquire before its own poster adds.  The words
+// go through agent-scope atomic loads and stores, so that no cache of another XCD serves an older value.
+__device__ __forceinline__ void strip_stats_energy(const StripLadder &lad, const uint32_t rung, const unsigned long long total)
+{
+    const PtStats S = pt_stats_view(lad.stats, lad.n_rungs);
+    const strip_gu64 pe = (strip_gu64)(S.sum_e + rung), pe2 = (strip_gu64)(S.sum_e2 + rung);
+    double sum_e = __longlong_as_double((long long)__hip_atomic_load(pe, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    double sum_e2 = __longlong_as_double((long long)__hip_atomic_load(pe2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    pt_stats_add_energy(sum_e, sum_e2, lad.jabs * double(lad.n_bonds - 2 * (long long)total));
+    __hip_atomic_store(pe, (unsigned long long)__double_as_longlong(sum_e), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(pe2, (unsigned long long)__double_as_longlong(sum_e2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Step 3, by strip 0 of replica (= slot) r, which holds `rung` after the round: label and round-trip count are the slot's own
+// (no other workgroup touches them during the launch); the rung's counts are served by another workgroup in another round: atomics.
+__device__ __forceinline__ void strip_stats_flow(const StripLadder &lad, const uint32_t r, const uint32_t rung)
+{
+    const PtStats S = pt_stats_view(lad.stats, lad.n_rungs);
+    uint8_t label = S.labels[r];
+    if (rung == 0) {
+        if (label == PT_LABEL_DOWN) S.round_trips[r] += 1;
+        S.labels[r] = label = PT_LABEL_UP;
+    } else if (rung + 1 == lad.n_rungs) {
+        S.labels[r] = label = PT_LABEL_DOWN;
+    }
+    if (label == PT_LABEL_UP) atomicAdd(S.n_up + rung, 1ull);
+    if (label == PT_LABEL_DOWN) atomicAdd(S.n_down + rung, 1ull);
 }
 
 // granules of one replica: [strip][plane][side: 0 = its top row, 1 = its bottom row][wpr]
@@ -301,6 +334,7 @@ __global__ __launch_bounds__(64 * NW, 4) void lat_strip_kernel(
                         // first: the reset is ordered before the post (release) and the readers' later adds after their read of the
                         // post (acquire fence in the exchange below) -- once per replica and round, so the ordering costs nothing
                         __hip_atomic_store((strip_gu64)cnt, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        if (lad.stats) strip_stats_energy(lad, my_rung, total); // ordered as the reset: before the post
                         __hip_atomic_store((strip_gu64)(lad.mail + size_t(round & 3) * lad.n_rungs + my_rung),
                                            ((unsigned long long)(uint32_t(round) + 1u) << 32) | total, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
                     }
@@ -354,7 +388,13 @@ __global__ __launch_bounds__(64 * NW, 4) void lat_strip_kernel(
                         new_rung = partner;
                         if (strip == 0 && my_rung < partner) atomicAdd(lad.counters + 1, 1ull); // once per accepted pair
                     }
+                    if (lad.stats && strip == 0 && my_rung < partner) { // the pair's counts belong to its lower rung
+                        const PtStats S = pt_stats_view(lad.stats, lad.n_rungs);
+                        atomicAdd(S.attempts + lo, 1ull);
+                        if (accept) atomicAdd(S.accepts + lo, 1ull);
+                    }
                 }
+                if (lad.stats && !bail && strip == 0 && lad.n_rungs >= 2) strip_stats_flow(lad, r, new_rung);
             }
             if constexpr (NW > 1) {
                 if (tid == 0) { red[9] = new_rung; if (bail) red[8] = 1; }
@@ -370,7 +410,10 @@ __global__ __launch_bounds__(64 * NW, 4) void lat_strip_kernel(
     }
     if (LAD && strip == 0 && tid == 0) { // the ladder as this launch leaves it
         lad.perm_out[my_rung] = r;
-        if (r == 0) lad.counters[0] = lad.round0 + (timesteps - 1) / lad.swap_every;
+        if (r == 0) {
+            lad.counters[0] = lad.round0 + (timesteps - 1) / lad.swap_every;
+            if (lad.stats) *pt_stats_view(lad.stats, lad.n_rungs).rounds += (timesteps - 1) / lad.swap_every;
+        }
     }
     if constexpr (NW > 1) __syncthreads();
 #pragma unroll

@@ -54,6 +54,7 @@ struct StripLadder {
     uint32_t n_rungs, swap_every, seed_lo, seed_hi;
     double jabs;
     long long n_bonds;
+    unsigned long long *stats;             // ladder statistics: the block of PtStats; nullptr: off (tested at run time)
 };
 
 // one launch: `blocks` strips of `nw` waves (1 or 4) each; arguments as lat_strip_kernel

@@ -80,6 +80,9 @@ extern "C" int isingmc_pt_detach(isingmc_states *s)
     TRY(strip_error(strip_check(s)));
     s->d_pt_ladder.reset(); s->d_pt_local.reset(); s->d_pt_all.reset(); s->d_pt_ladder_thr.reset(); s->d_pt_perm.reset();
     s->d_pt_counters.reset(); s->d_pt_mail.reset(); s->d_pt_round_counts.reset(); s->d_pt_perm2.reset();
+    s->d_pt_stats.reset(); // the ladder statistics go with the ladder: the next one starts clean and switched off
+    s->pt_stats_on = false;
+    s->pt_in_kernel_rounds = 0;
     s->pt = PtDev{};
     s->pt_attached = false;
     s->has_betas = false;
@@ -149,7 +152,7 @@ extern "C" int isingmc_pt_attach(isingmc_states *s, const double *ladder_betas, 
         HIP_TRY(hipMemcpy(s->d_pt_ladder_thr, thr.data(), thr.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
     }
     s->pt = PtDev{s->d_pt_ladder, s->d_pt_ladder_thr, rj_ladder ? 1u : pk_ladder ? uint32_t(PK_MAX_DEG) : 2u, s->d_pt_perm, s->d_pt_all, s->d_pt_counters, uint32_t(n_rungs),
-                  uint32_t(slot_offset), uint32_t(s->R), uint32_t(seed), uint32_t(seed >> 32)};
+                  uint32_t(slot_offset), uint32_t(s->R), uint32_t(seed), uint32_t(seed >> 32), /*stats=*/nullptr};
     s->pt_per = slots_per_rank;
     s->pt_world = world_size;
     s->ladder_betas.assign(ladder_betas, ladder_betas + n_rungs);
@@ -212,9 +215,10 @@ extern "C" int isingmc_pt_run(isingmc_states *s, size_t timesteps, size_t swap_e
         HIP_TRY(hipMemcpy(c, s->d_pt_counters, sizeof c, hipMemcpyDeviceToHost));
         const StripLadder lad{s->d_pt_ladder, reinterpret_cast<const unsigned long long *>(s->d_pt_ladder_thr.get()), s->d_pt_perm, s->d_pt_perm2,
                               s->d_pt_mail, s->d_pt_round_counts, s->d_pt_counters, c[0], uint32_t(R), uint32_t(swap_every), s->pt.seed_lo,
-                              s->pt.seed_hi, g->jabs, 2ll * (long long)g->nvars};
+                              s->pt.seed_hi, g->jabs, 2ll * (long long)g->nvars, s->pt.stats};
         s->meas_fresh = false;
         TRY(launch_strip(s, P, 0, R, nk, nullptr, 0, nullptr, s->d_pt_all + s->pt.slot_offset, &lad));
+        if (s->pt_stats_on) s->pt_in_kernel_rounds += rounds - 1; //  the launch's strips count these rounds themselves
         s->strip_epoch += uint32_t(2 * nk);
         s->t += nk;
         s->meas_fresh = true; // the launch wrote the final energies
@@ -284,6 +288,64 @@ extern "C" int isingmc_pt_swap(isingmc_states *s)
     TRY(use_device(s->g->device));
     HIP_TRY(pt_launch_swap(s->stream, s->pt, pt_thr_local(s), s->packed ? nullptr : s->d_beta, /*apply_only=*/false));
     return pt_after_swap(s);
+}
+
+// ------------------------------------------------------------------------------------------------
+// ladder statistics: pair acceptance, replica flow and energy sums per rung, kept by the exchange kernels themselves
+// ------------------------------------------------------------------------------------------------
+static int pt_stats_zero(isingmc_states *s)
+{
+    HIP_TRY(hipMemsetAsync(s->d_pt_stats, 0, pt_stats_bytes(s->pt.n_rungs), s->stream));
+    s->pt_in_kernel_rounds = 0;
+    return ISINGMC_OK;
+}
+
+extern "C" int isingmc_pt_set_statistics(isingmc_states *s, int on)
+{
+    if (!s || !s->pt_attached) return fail(ISINGMC_ERR_INVALID, "no ladder attached");
+    TRY(use_device(s->g->device));
+    if (on && !s->d_pt_stats) {
+        TRY(dev_alloc(s->d_pt_stats, pt_stats_bytes(s->pt.n_rungs) / sizeof(unsigned long long)));
+        TRY(pt_stats_zero(s));
+    }
+    s->pt_stats_on = on != 0;
+    s->pt.stats = on ? s->d_pt_stats.get() : nullptr; // a kernel argument: launches already enqueued keep what they were given
+    return ISINGMC_OK;
+}
+
+extern "C" int isingmc_pt_statistics_get(isingmc_states *s, uint64_t *rounds_out, uint64_t *in_kernel_rounds_out, uint64_t *attempts_out,
+                                         uint64_t *accepts_out, uint64_t *n_up_out, uint64_t *n_down_out, double *sum_e_out,
+                                         double *sum_e2_out, uint64_t *round_trips_out, uint8_t *labels_out)
+{
+    if (!s || !s->pt_attached) return fail(ISINGMC_ERR_INVALID, "no ladder attached");
+    if (!s->d_pt_stats) return fail(ISINGMC_ERR_INVALID, "this ladder holds no statistics: switch them on first (isingmc_pt_set_statistics)");
+    TRY(use_device(s->g->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    TRY(strip_error(strip_check(s)));
+    const uint32_t n = s->pt.n_rungs;
+    std::vector<unsigned long long> h(pt_stats_bytes(n) / sizeof(unsigned long long));
+    HIP_TRY(hipMemcpy(h.data(), s->d_pt_stats, pt_stats_bytes(n), hipMemcpyDeviceToHost));
+    const PtStats S = pt_stats_view(h.data(), n);
+    const size_t pairs = n ? n - 1 : 0;
+    if (rounds_out) *rounds_out = *S.rounds;
+    if (in_kernel_rounds_out) *in_kernel_rounds_out = s->pt_in_kernel_rounds;
+    if (attempts_out) std::copy(S.attempts, S.attempts + pairs, attempts_out);
+    if (accepts_out) std::copy(S.accepts, S.accepts + pairs, accepts_out);
+    if (n_up_out) std::copy(S.n_up, S.n_up + n, n_up_out);
+    if (n_down_out) std::copy(S.n_down, S.n_down + n, n_down_out);
+    if (sum_e_out) std::copy(S.sum_e, S.sum_e + n, sum_e_out);
+    if (sum_e2_out) std::copy(S.sum_e2, S.sum_e2 + n, sum_e2_out);
+    if (round_trips_out) std::copy(S.round_trips, S.round_trips + n, round_trips_out);
+    if (labels_out) std::copy(S.labels, S.labels + n, labels_out);
+    return ISINGMC_OK;
+}
+
+extern "C" int isingmc_pt_statistics_reset(isingmc_states *s)
+{
+    if (!s || !s->pt_attached) return fail(ISINGMC_ERR_INVALID, "no ladder attached");
+    if (!s->d_pt_stats) return fail(ISINGMC_ERR_INVALID, "this ladder holds no statistics: switch them on first (isingmc_pt_set_statistics)");
+    TRY(use_device(s->g->device));
+    return pt_stats_zero(s); // on the stream: behind the rounds already enqueued
 }
 
 // synchronises; perm_out: uint32[n_rungs] (rung -> slot)

@@ -19,6 +19,15 @@ __global__ __launch_bounds__(1024) void pt_swap_kernel(const PtDev P, uint64_t *
 {
     const unsigned long long round = P.counters[0];
     __syncthreads(); // everyone has read the round before thread 0 bumps it
+    // ladder statistics: off costs this one uniform branch
+    const bool stats = P.stats != nullptr && !apply_only;
+    PtStats S{};
+    if (stats) {
+        S = pt_stats_view(P.stats, P.n_rungs);
+        for (uint32_t i = threadIdx.x; i < P.n_rungs; i += blockDim.x) // a configuration counts at the beta it was just swept at
+            pt_stats_add_energy(S.sum_e[i], S.sum_e2[i], P.slot_energy[P.perm[i]]);
+        __syncthreads(); // the permutation before the round has been read
+    }
     unsigned swaps = 0;
     for (uint32_t i = uint32_t(round & 1) + 2 * threadIdx.x; !apply_only && i + 1 < P.n_rungs; i += 2 * blockDim.x) {
         const uint32_t sa = P.perm[i], sb = P.perm[i + 1];
@@ -35,9 +44,28 @@ __global__ __launch_bounds__(1024) void pt_swap_kernel(const PtDev P, uint64_t *
             P.perm[i + 1] = sa;
             swaps++;
         }
+        if (stats) { // the deciding thread is the pair's only writer
+            S.attempts[i] += 1;
+            if (accept) S.accepts[i] += 1;
+        }
     }
     if (swaps) atomicAdd(&P.counters[1], (unsigned long long)swaps);
     __syncthreads();
+    if (stats && P.n_rungs >= 2) { // replica flow, from the permutation after the round
+        if (threadIdx.x == 0) {
+            const uint32_t cold = P.perm[0], hot = P.perm[P.n_rungs - 1];
+            if (S.labels[cold] == PT_LABEL_DOWN) S.round_trips[cold] += 1;
+            S.labels[cold] = PT_LABEL_UP;
+            S.labels[hot] = PT_LABEL_DOWN;
+        }
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < P.n_rungs; i += blockDim.x) {
+            const uint8_t label = S.labels[P.perm[i]];
+            if (label == PT_LABEL_UP) S.n_up[i] += 1;
+            if (label == PT_LABEL_DOWN) S.n_down[i] += 1;
+        }
+    }
+    if (stats && threadIdx.x == 0) *S.rounds += 1;
     for (uint32_t i = threadIdx.x; i < P.n_rungs; i += blockDim.x) {
         const uint32_t slot = P.perm[i];
         if (slot >= P.slot_offset && slot < P.slot_offset + P.n_local) {

@@ -50,7 +50,34 @@ def _split(edges):
     return ea, eb, ej
 
 
-TRACK_AT_ROUNDS = 1 << 62       # set_track_best period of a ladder: no timestep reaches it, the exchange rounds update the records
+def betas_from_flow(betas, n_up, n_down, n_rungs=None):
+    """A new ladder from the measured replica flow (get_ladder_statistics()["n_up"], ["n_down"]), by the feedback idea of Katzgraber,
+    Trebst, Huse and Troyer (2006): in a ladder that wastes no rung the flow fraction f = n_up / (n_up + n_down) falls linearly
+    with the rung index from 1 at rung 0 to 0 at the last rung.  The method: (1) f per rung, with f = 1 at rung 0 and f = 0 at
+    the last rung by definition, rungs without a labelled visit taking the linear interpolation in the rung index between their
+    measured neighbours; (2) f made monotone by a running maximum from the last rung (the end where f = 0) towards rung 0;
+    (3) the piecewise-linear f(beta) through the measured points inverted at the n_rungs (default: as many as before) equidistant
+    values 1, ..., 0; (4) the two end betas kept as they are.  Pure numpy, no device.  A heuristic: it moves rungs towards
+    the bottlenecks of the measured flow, it needs enough round trips for f to mean anything, and it wants iterating."""
+    betas = np.asarray(betas, dtype=np.float64)
+    up, down = np.asarray(n_up, dtype=np.float64), np.asarray(n_down, dtype=np.float64)
+    n = len(betas)
+    m = n if n_rungs is None else int(n_rungs)
+    if n < 2 or m < 2 or up.shape != (n,) or down.shape != (n,):
+        raise ValueError("betas, n_up and n_down must have one entry per rung of a ladder of at least two rungs")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        f = np.where(up + down > 0, up / (up + down), np.nan)
+    f[0], f[-1] = 1.0, 0.0
+    known = ~np.isnan(f)
+    f = np.interp(np.arange(n), np.flatnonzero(known), f[known])
+    f = np.maximum.accumulate(f[::-1])            # from the last rung on: non-decreasing, 0 ... 1
+    target = (m - 1 - np.arange(m)) / float(m - 1)
+    out = np.interp(target, f, betas[::-1])
+    out[0], out[-1] = betas[0], betas[-1]
+    return out
+
+
+TRACK_AT_ROUNDS = 1 << 62      # set_track_best period of a ladder: no timestep reaches it, the exchange rounds update the records
 COPY_SEED_XOR = 0x9E3779B97F4A7C15  # copy 1 of a copies=2 ladder is the ladder of seed ^ this (DESIGN.md S10)
 
 
@@ -115,6 +142,8 @@ class ClassicalTempering:
         self._round = 0
         self._total_swaps = 0
         self._on_stream = False
+        self._stats_on, self._stats_seen = False, False   # ladder statistics: counting now / switched on at least once
+        self._host_stats = None                           # host swap path: the arrays of _capi.pt_statistics_zeros
 
     def _default_device(self):
         import os
@@ -319,6 +348,82 @@ class ClassicalTempering:
         for st in self._measured_spins_states():
             st.reset_moments()
 
+    # -- what choosing the ladder needs: pair acceptance, replica flow, energy sums, kept by the exchange rounds ------
+    def set_ladder_statistics(self, on=True):
+        """From now on every exchange round counts (on=False: stops, the values stay): per pair of neighbouring rungs the attempts
+        and accepted exchanges, per rung the energy sums of the configuration that was swept at it and how often the configuration
+        it holds last visited rung 0 (up) or the last rung (down), per slot the completed round trips rung 0 -> last rung -> rung 0.
+        Before or after the first timestep.  On the device's stream the exchange kernels keep them (rounds inside a persistent
+        launch included: nothing waits on the host); on the host swap path this class keeps the same numbers through the
+        library's host twin; with devices=[...] and in a torch.distributed group every shard holds the whole ladder's, identical.
+        No configuration, energy, random number or exchange decision changes."""
+        if self._pair is not None:
+            for c in self._pair:
+                c.set_ladder_statistics(on)
+            return
+        self._stats_on = bool(on)
+        self._stats_seen = self._stats_seen or self._stats_on
+        if self._states is not None:
+            self._apply_ladder_statistics()
+
+    def _apply_ladder_statistics(self):
+        """(the ladder exists and set_ladder_statistics(True) has been called at least once: the statistics exist from here on)"""
+        if self._pgroup is not None or self._on_stream:
+            for st in (self._shards if self._pgroup is not None else [self._states]):
+                st.pt_set_statistics(True)   # the first switch-on allocates; switched on and off again before any round: zeros
+                if not self._stats_on:
+                    st.pt_set_statistics(False)
+        elif self._host_stats is None:
+            self._host_stats = _capi.pt_statistics_zeros(len(self._betas))
+
+    def _raw_ladder_statistics(self):
+        if not self._stats_seen:
+            raise ValueError("this ladder holds no statistics: call set_ladder_statistics() first")
+        self._materialise()
+        if self._pgroup is not None or self._on_stream:
+            return self._states.pt_statistics()   # (devices=[...]: shard 0's block; every shard's is the same)
+        return {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in self._host_stats.items()}
+
+    def get_ladder_statistics(self):
+        """dict: rounds, in_kernel_rounds (of them, decided inside persistent launches); attempts, accepts uint64[G - 1] and
+        acceptance float64[G - 1] = accepts / attempts per pair (i, i + 1), NaN where a pair has no attempt; n_up, n_down uint64[G] and
+        flow float64[G] = n_up / (n_up + n_down), NaN where a rung has no labelled visit; mean_energy, var_energy float64[G] from
+        the energy sums over the rounds (NaN before the first round) -- all in the order of get_betas(); round_trips uint64[G] and
+        labels uint8[G] (0 none, 1 up, 2 down) per replica SLOT, slot s being the configuration that started at rung s (where it is
+        now: get_permutation()).  copies=2: every entry has a leading axis of 2, one row per copy."""
+        if self._pair is not None:
+            both = [c.get_ladder_statistics() for c in self._pair]
+            return {k: np.stack([np.asarray(d[k]) for d in both]) for k in both[0]}
+        raw = self._raw_ladder_statistics()
+        out = {k: raw[k] for k in ("rounds", "in_kernel_rounds", "attempts", "accepts")}
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["acceptance"] = np.where(raw["attempts"] > 0, raw["accepts"] / raw["attempts"].astype(np.float64), np.nan)
+            visits = (raw["n_up"] + raw["n_down"]).astype(np.float64)
+            out["n_up"], out["n_down"] = raw["n_up"], raw["n_down"]
+            out["flow"] = np.where(visits > 0, raw["n_up"] / visits, np.nan)
+            rounds = float(raw["rounds"]) if raw["rounds"] else np.nan
+            out["mean_energy"] = raw["sum_e"] / rounds
+            out["var_energy"] = raw["sum_e2"] / rounds - out["mean_energy"] ** 2
+        out["round_trips"], out["labels"] = raw["round_trips"], raw["labels"]
+        return out
+
+    def reset_ladder_statistics(self):
+        """Every count and sum back to zero, the labels to none; the setting stays."""
+        if self._pair is not None:
+            for c in self._pair:
+                c.reset_ladder_statistics()
+            return
+        if not self._stats_seen:
+            raise ValueError("this ladder holds no statistics: call set_ladder_statistics() first")
+        self._materialise()
+        if self._pgroup is not None:
+            for st in self._shards:
+                st.pt_reset_statistics()
+        elif self._on_stream:
+            self._states.pt_reset_statistics()
+        else:
+            self._host_stats = _capi.pt_statistics_zeros(len(self._betas))
+
     # -- copies=2: the two ladders, cut at exchange rounds and at cluster moves ------------------------------------------------
     def _materialise_pair(self):
         if self._states is not None:
@@ -479,6 +584,8 @@ class ClassicalTempering:
             self._push_betas()
         if self._track_minimum:
             self._apply_track_minimum()
+        if self._stats_seen:
+            self._apply_ladder_statistics()
 
     def _materialise_in_process(self, G):
         """One shard per device, the same ladder attached to each, an isingmc_pt_group between them."""
@@ -506,6 +613,8 @@ class ClassicalTempering:
         self._lo, self._hi = 0, G
         self._perm = np.arange(G, dtype=np.uint32)
         self._on_stream = True
+        if self._stats_seen:
+            self._apply_ladder_statistics()
 
     def group_backend(self):
         """'rccl' or 'copy' for an in-process ladder (devices=[...]), else None."""
@@ -563,7 +672,10 @@ class ClassicalTempering:
         if self._track_minimum and self._hi > self._lo:
             self._states.best_update()
         slot_e = self._slot_energies(local)
+        before = self._perm.copy() if self._stats_on else None
         self._total_swaps += _capi.pt_swap_round(self._seed, self._round, self._betas, slot_e, self._perm)
+        if self._stats_on:   # the host twin of what the exchange kernels keep; every rank computes the same
+            _capi.pt_statistics_round(self._host_stats, self._round, before, self._perm, slot_e)
         self._round += 1
         self._push_betas()
 
