@@ -388,6 +388,47 @@ int isingmc_site_classes_sizes(const isingmc_site_classes *classes, uint64_t *si
 int isingmc_overlaps_by_class(isingmc_states *a, isingmc_states *b, const uint32_t *slots_a, const uint32_t *slots_b, size_t n_pairs,
                               const isingmc_site_classes *classes, int64_t *out);
 
+/* ---- The overlap series: overlaps per sample, logged on the device (no reference counterpart) ----
+ * A device-resident log with one row per sample.  A record appends a row without the host waiting for anything; the log is read
+ * once, afterwards.  A row is int64[n_pairs][1 + link + n_tables * n_classes]: for pair p the spin overlap, with
+ * ISINGMC_SERIES_LINK the link overlap, and with a class set out[p][t][c] -- the exact integers spin_out, link_out and out of
+ * isingmc_overlaps and isingmc_overlaps_by_class, by their conventions (zero couplings, duplicated entries and entries a_e == b_e
+ * included).  The log holds `capacity` rows in one device block of the series, at most the option "overlap_series_bytes" of `a`
+ * (isingmc_states_set_option; ISINGMC_OVERLAP_SERIES_BYTES, default 1 GiB); the host keeps the timestep of every row (a's counter
+ * when the record was enqueued) and the row count.
+ * isingmc_overlap_series_create: the containers served and refused are those of isingmc_overlaps, with its messages; b == NULL:
+ *   pairs inside `a`.  classes may be NULL.  With ISINGMC_SERIES_BY_RUNG both containers carry a whole tempering ladder over
+ *   bitwise equal betas (the condition of the table-free form of isingmc_icm_between), n_pairs is the number of rungs and pair r =
+ *   (a's slot at rung r, b's slot at rung r), the permutations read on the device when the record runs.
+ * isingmc_overlap_series_record: one row for the configurations as they are, enqueue only.  slots_a / slots_b choose the pairs as
+ *   in isingmc_overlaps (both NULL: the pairs (2 p, 2 p + 1) of one container, (slot p, slot p) of two; n_pairs as given at
+ *   creation); a BY_RUNG series takes no tables.  The tables are copied before the call returns.  a's stream waits for what b's
+ *   stream holds, and b's stream for the record.  A full log refuses with ISINGMC_ERR_INVALID: nothing is enqueued, the rows stay.
+ * isingmc_overlap_series_set_every: every > 0: from now on (t0 = a's timestep) a record without tables follows every timestep t
+ *   with (t - t0) % every == 0, whatever kind of timestep it is, inside isingmc_do_time_steps*, isingmc_run_sampling and
+ *   isingmc_run_sampling_moments; 0 switches it off and keeps the rows.  Only for a series inside one container (b == NULL,
+ *   n_pairs = count / 2, no ISINGMC_SERIES_BY_RUNG), one such series per container.  isingmc_states_set_timestep re-bases t0;
+ *   a run call whose rows would not fit fails before it enqueues anything; isingmc_states_append, isingmc_pa_run and
+ *   isingmc_pa_resample are refused while it is on.
+ * isingmc_overlap_series_count: rows held and the capacity (either pointer may be NULL).
+ * isingmc_overlap_series_get: waits for a's stream, then copies the rows [first, first + n): timesteps_out[n],
+ *   spin_out[n][n_pairs], link_out[n][n_pairs], class_out[n][n_pairs][n_tables][n_classes]; any pointer may be NULL.  Changes nothing.
+ * isingmc_overlap_series_reset: the row count back to 0 (enqueue only); the period stays.
+ * A series is destroyed before its containers and its class set; isingmc_pt_detach is refused on a container with a live BY_RUNG
+ * series. */
+typedef struct isingmc_overlap_series isingmc_overlap_series;
+#define ISINGMC_SERIES_LINK 1u    /* also the link overlap */
+#define ISINGMC_SERIES_BY_RUNG 2u /* pair r = (a's slot at rung r, b's slot at rung r), permutations read on the device */
+int isingmc_overlap_series_create(isingmc_states *a, isingmc_states *b, size_t n_pairs, const isingmc_site_classes *classes,
+                                  unsigned flags, size_t capacity, isingmc_overlap_series **out);
+int isingmc_overlap_series_record(isingmc_overlap_series *s, const uint32_t *slots_a, const uint32_t *slots_b);
+int isingmc_overlap_series_set_every(isingmc_overlap_series *s, size_t every);
+int isingmc_overlap_series_count(const isingmc_overlap_series *s, size_t *n_out, size_t *capacity_out);
+int isingmc_overlap_series_get(isingmc_overlap_series *s, size_t first, size_t n, uint64_t *timesteps_out,
+                               int64_t *spin_out, int64_t *link_out, int64_t *class_out);
+int isingmc_overlap_series_reset(isingmc_overlap_series *s);
+int isingmc_overlap_series_destroy(isingmc_overlap_series *s);
+
 /* ---- each replica's lowest-energy configuration, kept on the device (no reference counterpart) ----
  * A container may keep, per replica, the lowest energy its configuration has had at an UPDATE, the timestep of that update and
  * the configuration itself.  An update measures the f64 energies of isingmc_get_energies on the device and, for every replica

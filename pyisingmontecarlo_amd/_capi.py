@@ -16,6 +16,8 @@ FLAG_STABLE_PATH = 2
 MOMENTS_PER_REPLICA = 1  # ISINGMC_MOMENTS_*
 MOMENTS_BONDS = 2
 MOMENTS_PER_RUNG = 4
+SERIES_LINK = 1  # ISINGMC_SERIES_*
+SERIES_BY_RUNG = 2
 FAMILIES = ("checkerboard", "csr_f64", "packed_bitsliced", "packed_real")
 
 
@@ -88,6 +90,13 @@ _PROTOTYPES = {
     "isingmc_site_classes_destroy": (C.c_int, [_vp]),
     "isingmc_site_classes_sizes": (C.c_int, [_vp, _vp]),
     "isingmc_overlaps_by_class": (C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
+    "isingmc_overlap_series_create": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_uint, C.c_size_t, C.POINTER(_vp)]),
+    "isingmc_overlap_series_record": (C.c_int, [_vp, _vp, _vp]),
+    "isingmc_overlap_series_set_every": (C.c_int, [_vp, C.c_size_t]),
+    "isingmc_overlap_series_count": (C.c_int, [_vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "isingmc_overlap_series_get": (C.c_int, [_vp, C.c_size_t, C.c_size_t, _vp, _vp, _vp, _vp]),
+    "isingmc_overlap_series_reset": (C.c_int, [_vp]),
+    "isingmc_overlap_series_destroy": (C.c_int, [_vp]),
     "isingmc_states_set_track_best": (C.c_int, [_vp, C.c_size_t]),
     "isingmc_states_track_best": (C.c_int, [_vp, C.POINTER(C.c_size_t)]),
     "isingmc_best_update": (C.c_int, [_vp]),
@@ -460,8 +469,103 @@ class SiteClasses:
 
     def close(self):
         if self._h:
+            _close_series(self)
             lib().isingmc_site_classes_destroy(self._h)
             self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _SeriesHandle:
+    """The handle of an overlap series, shared by the OverlapSeries and by everything it reads (its containers, its class set):
+    whichever of them goes first destroys the series.  (Not a weak reference to the OverlapSeries: the garbage collector clears
+    those before it finalises a cycle, and the series must go before what it reads in whatever order that happens.)"""
+
+    def __init__(self):
+        self.h = _vp()
+
+    def close(self):
+        if self.h:
+            lib().isingmc_overlap_series_destroy(self.h)
+            self.h = _vp()
+
+
+def _close_series(owner):
+    """The overlap series that read `owner` (a container or a class set) go before it does."""
+    for handle in owner.__dict__.pop("_series", []):
+        handle.close()
+
+
+class OverlapSeries:
+    """isingmc_overlap_series: a device-resident log with one row of overlaps per sample.  record() and the
+    periodic records inside the step loop only enqueue; get() reads the log, once, afterwards.  Made by States.overlap_series."""
+
+    def __init__(self, a, other=None, n_pairs=None, classes=None, link=True, by_rung=False, capacity=4096):
+        self._a, self._b, self._classes = a, other, classes  # keeps them alive
+        self._handle = _SeriesHandle()
+        if n_pairs is None:
+            n_pairs = a.count if by_rung else a.count // 2 if other is None or other is a else min(a.count, other.count)
+        self.n_pairs, self.link, self.by_rung = int(n_pairs), bool(link), bool(by_rung)
+        self.n_tables, self.n_classes = (classes.n_tables, classes.n_classes) if classes is not None else (0, 0)
+        flags = (SERIES_LINK if link else 0) | (SERIES_BY_RUNG if by_rung else 0)
+        _check(lib().isingmc_overlap_series_create(a._h, None if other is None else other._h, self.n_pairs,
+                                                   None if classes is None else classes._h, flags, int(capacity), C.byref(self._handle.h)))
+        for owner in (a, other, classes):
+            if owner is not None:
+                owner.__dict__["_series"] = [h for h in owner.__dict__.get("_series", []) if h.h] + [self._handle]
+
+    @property
+    def _h(self):
+        return self._handle.h
+
+    def record(self, slots_a=None, slots_b=None):
+        """One row for the configurations as they are; pairs as States.overlaps takes them.  Enqueue only."""
+        if (slots_a is None) != (slots_b is None):
+            raise ValueError("give both slot tables or neither")
+        sa, sb = _arr(slots_a, np.uint32), _arr(slots_b, np.uint32)
+        if sa is not None and (sa.ndim != 1 or sa.shape != sb.shape or sa.size != self.n_pairs):
+            raise ValueError("the slot tables must be two one-dimensional arrays of n_pairs entries")
+        _check(lib().isingmc_overlap_series_record(self._h, _p(sa), _p(sb)))
+
+    def set_every(self, k):
+        """A record follows every timestep t > t0 (now) with (t - t0) % k == 0, inside the run calls; 0: off, the rows stay."""
+        _check(lib().isingmc_overlap_series_set_every(self._h, int(k)))
+
+    @property
+    def count(self):
+        n = C.c_size_t()
+        _check(lib().isingmc_overlap_series_count(self._h, C.byref(n), None))
+        return int(n.value)
+
+    @property
+    def capacity(self):
+        n = C.c_size_t()
+        _check(lib().isingmc_overlap_series_count(self._h, None, C.byref(n)))
+        return int(n.value)
+
+    def get(self, first=0, n=None):
+        """(timesteps uint64[n], spin int64[n, P], link int64[n, P] or None, by_class int64[n, P, T, C] or None) of the rows
+        [first, first + n) (n=None: all from `first` on).  Synchronises; changes nothing."""
+        first = int(first)
+        n = max(self.count - first, 0) if n is None else int(n)
+        P = self.n_pairs
+        t = np.zeros(n, dtype=np.uint64)
+        spin = np.zeros((n, P), dtype=np.int64)
+        lnk = np.zeros((n, P), dtype=np.int64) if self.link else None
+        cls = np.zeros((n, P, self.n_tables, self.n_classes), dtype=np.int64) if self.n_tables else None
+        _check(lib().isingmc_overlap_series_get(self._h, first, n, _p(t), _p(spin), _p(lnk), _p(cls)))
+        return t, spin, lnk, cls
+
+    def reset(self):
+        """The row count back to 0 (enqueue only); the period stays."""
+        _check(lib().isingmc_overlap_series_reset(self._h))
+
+    def close(self):
+        self._handle.close()
 
     def __del__(self):
         try:
@@ -623,6 +727,12 @@ class States:
         out = np.zeros((n, classes.n_tables, classes.n_classes), dtype=np.int64)
         _check(lib().isingmc_overlaps_by_class(self._h, None if other is None else other._h, _p(sa), _p(sb), n, classes._h, _p(out)))
         return out
+
+    def overlap_series(self, other=None, n_pairs=None, classes=None, link=True, by_rung=False, capacity=4096):
+        """An OverlapSeries over the pairs overlaps() would take: one row per record, kept on the device.
+        n_pairs=None: count // 2 inside this container, the smaller count between two, the number of rungs with by_rung (both
+        containers carry a whole ladder over equal betas; pair r = the two replicas at rung r, read on the device)."""
+        return OverlapSeries(self, other, n_pairs, classes, link, by_rung, capacity)
 
     # ---- each replica's lowest-energy configuration (DESIGN.md S16)
     def set_track_best(self, k):
@@ -895,6 +1005,7 @@ class States:
         if self._h:
             for grp in getattr(self, "_groups", []):
                 grp.close()
+            _close_series(self)
             lib().isingmc_states_destroy(self._h)
             self._h = _vp()
 

@@ -4,6 +4,10 @@ correlation length -- numpy only, no device.
 For a wave vector k along a lattice axis,  sum_i q_i e^{i k x_i} = sum_x e^{i k x} Q_x  with Q_x the overlap q_i = s_i^a s_i^b summed
 over the plane at coordinate x: the device returns the L integers Q_x per pair and axis (States.overlaps_by_class with the tables
 of plane_classes), and the rest is a Fourier transform of L numbers.
+
+The rows of an overlap series (OverlapSeries.get, ClassicalTempering.get_measured_overlaps) feed both directly:
+overlap_moments takes `spin` [n, P], and chi_sg / correlation_length take by_class[..., t, :] -- [n, P, L] for axis t -- as they
+come, the sample and pair axes being leading axes like any other.
 """
 import numpy as np
 
@@ -22,6 +26,17 @@ def chi_sg(planes, nvars):
     overlaps of one axis (leading axes, such as pairs, are kept).  Average it over pairs and samples before anything else."""
     f = np.fft.fft(np.asarray(planes, dtype=np.float64), axis=-1)
     return (f.real ** 2 + f.imag ** 2) / float(nvars)
+
+
+def overlap_moments(spin, nvars):
+    """(<q>, <q^2>, <q^4>, binder) per column of spin[n, ...]: q = spin / nvars averaged over the n samples of axis 0 (the rows of
+    an overlap series), and the Binder ratio (3 - <q^4> / <q^2>^2) / 2 -- 1 when every sample has |q| = 1, 0 for a Gaussian q.  A
+    column whose <q^2> is 0 has no ratio: NaN.  Average over disorder realisations BEFORE the ratio, as with correlation_length."""
+    q = np.asarray(spin, dtype=np.float64) / float(nvars)
+    q1, q2, q4 = q.mean(axis=0), (q ** 2).mean(axis=0), (q ** 4).mean(axis=0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        binder = np.where(q2 > 0, (3.0 - q4 / q2 ** 2) / 2.0, np.nan)
+    return q1, q2, q4, binder
 
 
 def correlation_length(chi0, chik, L, n=1):

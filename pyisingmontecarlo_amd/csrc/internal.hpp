@@ -5,6 +5,7 @@
 //   nonlocal.hip   host side of the non-local moves: Swendsen-Wang steps, isoenergetic cluster moves inside and between containers
 //   overlaps.hip   spin and link overlaps between replica pairs (isingmc_overlaps), and the spin overlap by site class
 //                  (isingmc_site_classes_*, isingmc_overlaps_by_class)
+//   overlap_series.hip  the device-resident log of overlap measurements, one row per sample (isingmc_overlap_series_*)
 //   best.hip       each replica's lowest-energy configuration, kept on the device (isingmc_best_*)
 //   moments.hip    per-site spin sums and per-bond sums over the samples of a run (isingmc_moments_*)
 //   sampling.hip   get_states and the double-buffered sampling pipeline
@@ -48,6 +49,7 @@
 #include "moments_kernels.hpp"
 #include "overlap_class_kernels.hpp"
 #include "overlap_kernels.hpp"
+#include "overlap_series_kernels.hpp"
 #include "owned_block.hpp"
 #include "real_types.hpp"
 #include "spread_types.hpp"
@@ -117,6 +119,7 @@ struct Options {
     int cluster_workspace_bytes = 1 << 30; // labels, cluster sizes and bond planes of one batch of replicas
     int moments_planes = 8;               // time planes of the per-replica moment sums: a flush every 2^K - 1 samples
     long long moments_bytes = 4ll << 30;   // the most device memory the moment sums of one container may take (64 bits: beyond an int)
+    long long overlap_series_bytes = 1ll << 30; // the most device memory the log of one overlap series may take
 
     static Options from_env()
     {
@@ -146,6 +149,7 @@ struct Options {
         o.cluster_workspace_bytes = std::max(1, env_int("ISINGMC_CLUSTER_WORKSPACE_BYTES", 1 << 30));
         o.moments_planes = env_int("ISINGMC_MOMENTS_PLANES", o.moments_planes);
         if (const char *v = std::getenv("ISINGMC_MOMENTS_BYTES")) o.moments_bytes = std::atoll(v);
+        if (const char *v = std::getenv("ISINGMC_OVERLAP_SERIES_BYTES")) o.overlap_series_bytes = std::atoll(v);
         return o;
     }
 
@@ -154,6 +158,7 @@ struct Options {
     {
         const std::string n = option_bare_name(name_in);
         if (n == "moments_bytes") { moments_bytes = value; return true; }
+        if (n == "overlap_series_bytes") { overlap_series_bytes = value; return true; }
         const std::pair<const char *, int *> table[] = {
             {"force_real", &force_real}, {"disable_real", &disable_real}, {"force_packed", &force_packed}, {"disable_packed", &disable_packed},
             {"disable_packed_uniform", &disable_packed_uniform}, {"disable_resident", &disable_resident}, {"strip", &strip},
@@ -380,6 +385,12 @@ struct isingmc_states {
     // a call repeated after a strip launch gave up (with_strip_retry) takes no sample twice: the samples up to mom_replay_to were
     // taken by the attempt that is repeated (mom_last_t: the timestep of the last sample the step loop took)
     uint64_t mom_last_t = 0, mom_replay_to = 0;
+    // the overlap series of this container that records on a period (isingmc_overlap_series_set_every): a row
+    // follows every timestep t > osr_t0 with (t - osr_t0) % osr_every == 0; the replay guard is the one of the moment sums
+    isingmc_overlap_series *osr = nullptr;
+    size_t osr_every = 0;
+    uint64_t osr_t0 = 0, osr_last_t = 0, osr_replay_to = 0;
+    size_t osr_by_rung_live = 0; // live series that read this container's ladder permutation on the device: no isingmc_pt_detach
     bool strip_guard = false; // inside with_strip_retry: a strip launch is checked before an update may keep what it left
 
     ~isingmc_states()
@@ -543,6 +554,39 @@ IM_INTERNAL int best_update_enqueue(isingmc_states *s); // energies_enqueue into
 // ---- moments.hip (per-site and per-bond sums over the samples of a run) -------------------------------------------------------
 IM_INTERNAL int moments_sample_enqueue(isingmc_states *s); // enqueue: one sample of all replicas into the sums (joins the lanes)
 
+// ---- overlaps.hip (which containers and pairings an overlap measurement serves) --------------------------------------------------
+// A class set as the kernels of overlap_class_kernels.hip read it: on a recognised lattice the tables in plane order with one
+// shared-class entry per word, on a graph with a replica-packed layout the positions sorted by class and cut into segments.  A
+// graph that only the f64 CSR family serves gets the sizes alone: the measurement refuses its containers.
+struct isingmc_site_classes {
+    const isingmc_graph *g = nullptr;
+    int device = 0;
+    size_t n_tables = 0, n_classes = 0;
+    std::vector<uint64_t> sizes; // [n_tables][n_classes]
+    bool has_lat = false, has_pk = false;
+    LatClassDev lat{};
+    PkClassDev pk{};
+    DevBlocks dev_allocs;
+};
+
+// The pairs of one call, validated: what isingmc_overlaps, isingmc_overlaps_by_class and the overlap series share.  On success b is
+// never NULL and either default_pairs holds (the pairing (2 p, 2 p + 1) inside one container, no tables) or slots_a / slots_b are
+// host tables of n_pairs entries below their containers' counts (`identity` backs them for two containers without tables).
+struct OverlapPairing {
+    isingmc_states *b = nullptr;
+    const uint32_t *slots_a = nullptr, *slots_b = nullptr;
+    bool default_pairs = false;
+    std::vector<uint32_t> identity;
+};
+// why these containers cannot be measured against each other ("" when they can; a == b: pairs inside one container)
+IM_INTERNAL std::string overlaps_obstacle(const isingmc_states *a, const isingmc_states *b);
+IM_INTERNAL int overlap_pairing(isingmc_states *a, isingmc_states *b, const uint32_t *slots_a, const uint32_t *slots_b, size_t n_pairs, OverlapPairing &P);
+
+// ---- overlap_series.hip (the device-resident log of overlap measurements) ----------------------------------------------------
+// why a run of `timesteps` timesteps cannot start ("" when it can): the periodic series of the container would run full in it
+IM_INTERNAL std::string osr_run_obstacle(const isingmc_states *s, size_t timesteps);
+IM_INTERNAL int osr_sample_enqueue(isingmc_states *s); // enqueue: one row of the container's periodic series at timestep s->t
+
 // ---- nonlocal.hip (Swendsen-Wang steps and isoenergetic cluster moves) -------------------------------------------------------
 // What the non-local steps of ONE run_steps call keep between them: filled by the call's first such step, the device blocks in the
 // call's DeviceScratch.  The host copies live as long as the call: they feed asynchronous copies.
@@ -589,8 +633,10 @@ static int with_strip_retry(isingmc_states *s, bool may_strip, F &&call)
     if (rc != STRIP_TIMED_OUT) return rc;
     TRY(snapshot_restore(s));
     s->mom_replay_to = s->mom_every && s->mom_last_t > t0 ? s->mom_last_t : 0; // (the repeat skips the samples already in the sums)
+    s->osr_replay_to = s->osr_every && s->osr_last_t > t0 ? s->osr_last_t : 0;  // (... and the rows already in the overlap series)
     s->t = t0;
     const int rc2 = strip_error(call());
     s->mom_replay_to = 0;
+    s->osr_replay_to = 0;
     return rc2;
 }

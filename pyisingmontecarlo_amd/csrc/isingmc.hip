@@ -147,6 +147,7 @@ extern "C" int isingmc_states_append(isingmc_states *s, uint64_t seed, const uin
     if (s->has_betas) return fail(ISINGMC_ERR_INVALID, "clear the per-replica betas before appending replicas");
     if (s->best_every) return fail(ISINGMC_ERR_INVALID, "minimum tracking is switched on for this container (isingmc_states_set_track_best): its records are sized for the replicas it holds; switch tracking on after the graphs are added");
     if (s->mom_every) return fail(ISINGMC_ERR_INVALID, "moment sums are switched on for this container (isingmc_states_set_moments_every): they are sized for the replicas it holds; switch accumulation on after the graphs are added");
+    if (s->osr_every) return fail(ISINGMC_ERR_INVALID, "an overlap series records on a period for this container (isingmc_overlap_series_set_every): its pairs are those of the replicas it holds; switch the period on after the graphs are added");
     TRY(use_device(s->g->device));
     if (s->packed) return pk_append(s, seed, initial_state);
     return add_replicas(s, 1, &seed, initial_state);
@@ -197,6 +198,8 @@ extern "C" int isingmc_states_set_timestep(isingmc_states *s, uint64_t t)
     s->t = t;
     s->mom_t0 = t; // the sample points of the moment sums are counted from here
     s->mom_last_t = 0;
+    s->osr_t0 = t; // ... and those of a periodic overlap series (S21)
+    s->osr_last_t = 0;
     return ISINGMC_OK;
 }
 
@@ -1017,6 +1020,10 @@ bool may_use_strips(const isingmc_states *s)
 int run_steps(isingmc_states *s, size_t timesteps, const double *betas, size_t beta_stride,
               double *energies_per_step, float *device_ms, bool sync, double *final_energies)
 {
+    if (s && s->osr_every) { // a periodic overlap series that would run full: nothing is enqueued
+        const std::string why = osr_run_obstacle(s, timesteps);
+        if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
+    }
     const bool may_strip = sync && timesteps >= 2 && may_use_strips(s) && strip_plan(s, timesteps).use;
     return with_strip_retry(s, may_strip, [&] {
         return run_steps_impl(s, timesteps, betas, beta_stride, energies_per_step, device_ms, sync, final_energies);
@@ -1474,6 +1481,8 @@ static int run_steps_impl(isingmc_states *s, size_t timesteps, const double *bet
             if (s->best_every) nk = std::min<size_t>(nk, s->best_every - s->t % s->best_every);
             // ... and the moment sums (S18): a stretch ends with the timestep after which (t - t0) % mom_every == 0
             if (s->mom_every) nk = std::min<size_t>(nk, s->mom_every - (s->t - s->mom_t0) % s->mom_every);
+            // ... and a periodic overlap series (S21), by the same rule
+            if (s->osr_every) nk = std::min<size_t>(nk, s->osr_every - (s->t - s->osr_t0) % s->osr_every);
             // (joined by the cluster step or the update before this stretch; the packed runner forks behind its table launches)
             if (P.lanes > 1 && s->n_lanes <= 1 && P.path != StepPath::Packed) TRY(lanes_fork(s, P.lanes));
         }
@@ -1511,6 +1520,15 @@ static int run_steps_impl(isingmc_states *s, size_t timesteps, const double *bet
             }
             if (rc == ISINGMC_OK) rc = moments_sample_enqueue(s);
             if (rc == ISINGMC_OK) s->mom_last_t = s->t;
+        }
+        // a row of the periodic overlap series (S21), by the rule of the moment sums: not twice, and behind a checked strip launch
+        if (rc == ISINGMC_OK && s->osr_every && (s->t - s->osr_t0) % s->osr_every == 0 && s->t > s->osr_replay_to) {
+            if (s->strip_guard && P.path == StepPath::LatStrip) {
+                HIP_TRY(hipStreamSynchronize(s->stream));
+                rc = strip_check(s);
+            }
+            if (rc == ISINGMC_OK) rc = osr_sample_enqueue(s);
+            if (rc == ISINGMC_OK) s->osr_last_t = s->t;
         }
     }
     if (s->n_lanes > 1) { const int jrc = lanes_join(s); if (rc == ISINGMC_OK) rc = jrc; }

@@ -232,6 +232,10 @@ extern "C" int isingmc_run_sampling_moments(isingmc_states *s, double beta, size
         const std::string why = mom_obstacle(s, flags);
         if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
     }
+    if (s->osr_every) { // a periodic overlap series that would run full: nothing is enqueued
+        const std::string full = osr_run_obstacle(s, thermalization + sampling_freq * n_samples);
+        if (!full.empty()) return fail(ISINGMC_ERR_INVALID, full);
+    }
     TRY(use_device(s->g->device));
     TRY(mom_reserve(s, flags));
     TRY(mom_zero_enqueue(s));

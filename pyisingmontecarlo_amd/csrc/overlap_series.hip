@@ -1,0 +1,339 @@
+// libisingmc.so: host side of the overlap series (isingmc_overlap_series_*) -- a device-resident log with one row of
+// overlaps per sample.  A record enqueues the launches of isingmc_overlaps / isingmc_overlaps_by_class into accumulators the
+// series owns, and behind each batch the store kernel of overlap_series_kernels.hip, which writes the row entries; nothing comes
+// back to the host before isingmc_overlap_series_get.  Nothing here is a kernel.
+#include "internal.hpp"
+
+struct isingmc_overlap_series {
+    isingmc_states *a = nullptr, *b = nullptr; // b == a: pairs inside one container
+    const isingmc_site_classes *classes = nullptr;
+    unsigned flags = 0;
+    size_t n_pairs = 0, capacity = 0;
+    size_t bins = 0, entries = 0; // n_tables * n_classes; entries of one pair: 1 + link + bins
+    DevBlock<long long> d_log;             // [capacity][n_pairs][entries]
+    DevBlock<unsigned long long> d_sizes;  // {nvars, n_edges, sizes[n_tables][n_classes]}: what the store kernel subtracts from
+    DevBlock<uint32_t> d_slots;            // [2][n_pairs] the slot tables of the record being enqueued
+    // workspace of one record; it grows only behind stream_quiesce of a's stream
+    DevBlock<unsigned long long> d_acc, d_cacc; // {D, B} per pair column; the class bins of one batch
+    DevBlock<uint32_t> d_words;                 // packed containers with tables: the gathered overlap words of one batch
+    size_t acc_cap = 0, cacc_cap = 0, words_cap = 0;
+    std::vector<uint64_t> timesteps;            // of the rows: its size is the row count
+    std::vector<std::vector<uint32_t>> uploads; // host tables that an enqueued copy may still read
+    hipEvent_t ev[2] = {nullptr, nullptr};      // b's stream has arrived / the record is enqueued
+};
+
+static bool osr_link(const isingmc_overlap_series *S) { return (S->flags & ISINGMC_SERIES_LINK) != 0; }
+static bool osr_by_rung(const isingmc_overlap_series *S) { return (S->flags & ISINGMC_SERIES_BY_RUNG) != 0; }
+
+// what the table-free form of isingmc_icm_between asks of two ladders ("" when they serve), in its words
+static std::string osr_ladders_obstacle(const isingmc_states *a, const isingmc_states *b, size_t n_pairs)
+{
+    if (!b || a == b) return "ISINGMC_SERIES_BY_RUNG pairs the rungs of two ladders: it needs two different containers";
+    if (!a->pt_attached || !b->pt_attached) return "without slot tables both containers need an attached tempering ladder (isingmc_pt_attach)";
+    for (const isingmc_states *s : {a, b})
+        if (s->pt_world != 1 || s->pt.slot_offset != 0 || s->pt.n_rungs != s->R)
+            return "without slot tables each ladder must live on its container alone (world size 1, one slot per rung): sharded ladders are not served";
+    if (a->pt.n_rungs != b->pt.n_rungs) return "the two ladders differ in their number of rungs";
+    if (a->ladder_betas.size() != b->ladder_betas.size() ||
+        std::memcmp(a->ladder_betas.data(), b->ladder_betas.data(), a->ladder_betas.size() * sizeof(double)) != 0)
+        return "the two ladders differ in their betas: the replicas of a pair need equal betas";
+    if (n_pairs != a->R) return "without slot tables n_pairs must be the number of rungs";
+    return "";
+}
+
+extern "C" int isingmc_overlap_series_create(isingmc_states *a, isingmc_states *b, size_t n_pairs, const isingmc_site_classes *classes,
+                                             unsigned flags, size_t capacity, isingmc_overlap_series **out)
+{
+    if (!a || !out) return fail(ISINGMC_ERR_INVALID, "NULL argument");
+    *out = nullptr;
+    if (flags & ~unsigned(ISINGMC_SERIES_LINK | ISINGMC_SERIES_BY_RUNG))
+        return fail(ISINGMC_ERR_INVALID, "unknown flag: ISINGMC_SERIES_LINK and ISINGMC_SERIES_BY_RUNG are the flags of an overlap series");
+    {
+        const std::string why = overlaps_obstacle(a, b ? b : a);
+        if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
+    }
+    const isingmc_graph *g = a->g;
+    if (n_pairs == 0) return fail(ISINGMC_ERR_INVALID, "n_pairs is 0: nothing to measure");
+    if (n_pairs > 0xFFFFFFFFull - 32) return fail(ISINGMC_ERR_INVALID, "more than 2^32 - 33 pairs in one call");
+    if (capacity == 0) return fail(ISINGMC_ERR_INVALID, "capacity is 0: the log holds no row");
+    if (flags & ISINGMC_SERIES_BY_RUNG) {
+        const std::string why = osr_ladders_obstacle(a, b, n_pairs);
+        if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
+    }
+    if (classes) {
+        if (classes->g != g) return fail(ISINGMC_ERR_INVALID, "the class set was made for another graph handle: its tables follow that graph's layout");
+        if (a->packed ? !classes->has_pk : !classes->has_lat) return fail(ISINGMC_ERR_INVALID, "the class set holds no layout for this container's kernel family");
+    }
+    const size_t bins = classes ? classes->n_tables * classes->n_classes : 0;
+    const size_t entries = 1 + ((flags & ISINGMC_SERIES_LINK) ? 1 : 0) + bins;
+    const unsigned long long budget = (unsigned long long)std::max(0ll, a->opt.overlap_series_bytes);
+    const unsigned long long row_bytes = (unsigned long long)n_pairs * entries * sizeof(long long); // (< 2^32 x 8194 x 8: no overflow)
+    if (row_bytes > budget || capacity > budget / row_bytes)
+        return fail(ISINGMC_ERR_INVALID, "a log of " + std::to_string(capacity) + " rows of " + std::to_string(row_bytes) +
+                                             " bytes is larger than the option overlap_series_bytes = " + std::to_string(budget) +
+                                             " allows (isingmc_states_set_option raises the budget)");
+    TRY(use_device(g->device));
+    std::unique_ptr<isingmc_overlap_series> S(new isingmc_overlap_series);
+    S->a = a;
+    S->b = b ? b : a;
+    S->classes = classes;
+    S->flags = flags;
+    S->n_pairs = n_pairs;
+    S->capacity = capacity;
+    S->bins = bins;
+    S->entries = entries;
+    TRY(dev_alloc(S->d_log, capacity * n_pairs * entries));
+    TRY(dev_alloc(S->d_slots, 2 * n_pairs));
+    std::vector<unsigned long long> sizes{(unsigned long long)g->nvars, (unsigned long long)g->n_edges};
+    if (classes) sizes.insert(sizes.end(), classes->sizes.begin(), classes->sizes.end());
+    TRY(dev_alloc(S->d_sizes, sizes.size()));
+    HIP_TRY(hipMemcpy(S->d_sizes, sizes.data(), sizes.size() * sizeof(unsigned long long), hipMemcpyHostToDevice)); // once: waited for here
+    for (hipEvent_t &ev : S->ev) HIP_TRY(pooled_event_create(&ev, true));
+    if (osr_by_rung(S.get()))
+        for (isingmc_states *s : {S->a, S->b}) s->osr_by_rung_live++;
+    *out = S.release();
+    return ISINGMC_OK;
+}
+
+extern "C" int isingmc_overlap_series_destroy(isingmc_overlap_series *S)
+{
+    if (!S) return ISINGMC_OK;
+    isingmc_states *a = S->a;
+    (void)hipSetDevice(a->g->device);
+    (void)stream_quiesce(a->stream); // the blocks go back to the cache: no record may still be running
+    if (a->osr == S) {
+        a->osr = nullptr;
+        a->osr_every = 0;
+    }
+    if (osr_by_rung(S))
+        for (isingmc_states *s : {S->a, S->b}) s->osr_by_rung_live--;
+    for (hipEvent_t ev : S->ev) pooled_event_destroy(ev, true);
+    delete S;
+    return ISINGMC_OK;
+}
+
+template <typename T>
+static int osr_ensure(isingmc_overlap_series *S, DevBlock<T> &block, size_t *cap, size_t need)
+{
+    if (need <= *cap) return ISINGMC_OK;
+    return dev_regrow(S->a->stream, block, cap, need, need);
+}
+
+// the batches of one record under a's cluster_workspace_bytes, as isingmc_overlaps and isingmc_overlaps_by_class cut them
+struct OsrPlan {
+    size_t acc_pairs = 0, acc0 = 0; // accumulator columns of the spin / link launches and the column of pair 0
+    size_t blocks = 0, batch = 0;   // packed containers with tables: pair blocks of 32 pairs and those of one batch
+    size_t cols = 1, items = 0, col0 = 0, cbatch = 0; // by class: pair columns per item, items, the column of pair 0, items per batch
+};
+
+static OsrPlan osr_plan(const isingmc_overlap_series *S, bool default_pairs)
+{
+    const isingmc_states *a = S->a;
+    const size_t n_pos = a->g->pk.n_pos, n_pairs = S->n_pairs, bins = S->bins;
+    const size_t workspace = size_t(std::max(1, a->opt.cluster_workspace_bytes));
+    OsrPlan P;
+    P.blocks = (n_pairs + 31) / 32;
+    P.acc_pairs = !a->packed ? n_pairs : default_pairs ? 16 * a->groups : 32 * P.blocks;
+    P.acc0 = a->packed && default_pairs ? a->pk_bit0 / 2 : 0; // (device slot 16 group + pair; pk_bit0 is even)
+    if (a->packed && !default_pairs) P.batch = nonlocal_batch(P.blocks, n_pos, workspace);
+    if (!bins) return P;
+    if (!a->packed) {
+        P.items = n_pairs;
+        P.cbatch = nonlocal_batch(n_pairs, 2 * bins, workspace);
+    } else {
+        P.cols = default_pairs ? 16 : 32;
+        P.items = default_pairs ? a->groups : P.blocks;
+        P.col0 = P.acc0;
+        P.cbatch = nonlocal_batch(P.items, 2 * P.cols * bins + (default_pairs ? 0 : n_pos), workspace);
+    }
+    return P;
+}
+
+// One row for the configurations as they are.  d_sa / d_sb: device slot tables, nullptr for the pairs (2 p, 2 p + 1) of one
+// container.  Enqueue only, unless the workspace has to grow.
+static int osr_enqueue(isingmc_overlap_series *S, const uint32_t *d_sa, const uint32_t *d_sb)
+{
+    isingmc_states *a = S->a, *b = S->b;
+    const isingmc_graph *g = a->g;
+    const bool link = osr_link(S), default_pairs = d_sa == nullptr;
+    const size_t n_pairs = S->n_pairs, bins = S->bins, n_pos = g->pk.n_pos;
+    const OsrPlan P = osr_plan(S, default_pairs);
+    TRY(osr_ensure(S, S->d_acc, &S->acc_cap, 2 * P.acc_pairs));
+    TRY(osr_ensure(S, S->d_cacc, &S->cacc_cap, P.cbatch * P.cols * bins));
+    TRY(osr_ensure(S, S->d_words, &S->words_cap, (a->packed && !default_pairs ? std::max(P.batch, bins ? P.cbatch : 0) : 0) * n_pos));
+    for (isingmc_states *s : {a, b})
+        if (s->n_lanes > 1) TRY(lanes_join(s));
+    if (a != b) { // b's sweeps and exchange rounds so far, before a's stream reads b's configurations and permutation
+        HIP_TRY(hipEventRecord(S->ev[0], b->stream));
+        HIP_TRY(hipStreamWaitEvent(a->stream, S->ev[0], 0));
+    }
+    long long *const row = S->d_log + S->timesteps.size() * n_pairs * S->entries;
+    unsigned long long *const d_acc = S->d_acc;
+    const uint32_t *nbr_rj = a->rj ? g->rj.nbr : nullptr;
+    const uint32_t rj_slots = a->rj ? g->rj.slots : 0;
+    const PkSide A{a->d_state, d_sa, uint32_t(a->pk_bit0), uint32_t(a->R)}, B{b->d_state, d_sb, uint32_t(b->pk_bit0), uint32_t(b->R)};
+    // spin and link overlap: entries 0 and 1 of every pair
+    HIP_TRY(hipMemsetAsync(d_acc, 0, 2 * P.acc_pairs * sizeof(unsigned long long), a->stream));
+    if (!a->packed) {
+        HIP_TRY(overlap_launch_lattice(a->stream, a->d_state, b->d_state, d_sa, d_sb, g->geom, link, n_pairs, d_acc));
+    } else if (default_pairs) {
+        HIP_TRY(overlap_launch_packed_pairs(a->stream, a->d_state, g->pk, nbr_rj, rj_slots, link, a->groups, d_acc));
+    } else {
+        for (size_t b0 = 0; b0 < P.blocks; b0 += P.batch)
+            HIP_TRY(overlap_launch_packed_tables(a->stream, A, B, g->pk, nbr_rj, rj_slots, link, uint32_t(b0), uint32_t(std::min(P.batch, P.blocks - b0)),
+                                                 uint32_t(n_pairs), S->d_words, d_acc));
+    }
+    HIP_TRY(osr_launch_store(a->stream, OsrStore{d_acc, S->d_sizes, row, 0, P.acc0, P.acc_pairs, n_pairs, 2, link ? 2u : 1u, uint32_t(S->entries), 0}));
+    // by class: the entries behind them, batch by batch
+    if (bins) {
+        const isingmc_site_classes *C = S->classes;
+        unsigned long long *const d_cacc = S->d_cacc;
+        const uint32_t offset = link ? 2 : 1;
+        const size_t rw = 2 * size_t(g->geom.wpp);
+        for (size_t i0 = 0; i0 < P.items; i0 += P.cbatch) {
+            const size_t n = std::min(P.cbatch, P.items - i0);
+            HIP_TRY(hipMemsetAsync(d_cacc, 0, n * P.cols * bins * sizeof(unsigned long long), a->stream));
+            if (!a->packed) {
+                HIP_TRY(overlap_class_launch_lattice(a->stream, default_pairs ? a->d_state + 2 * i0 * rw : a->d_state.get(), b->d_state,
+                                                     d_sa ? d_sa + i0 : nullptr, d_sb ? d_sb + i0 : nullptr, g->geom, C->lat, uint32_t(n), d_cacc));
+            } else {
+                if (!default_pairs) HIP_TRY(overlap_launch_packed_gather(a->stream, A, B, g->pk, uint32_t(i0), uint32_t(n), uint32_t(n_pairs), S->d_words));
+                HIP_TRY(overlap_class_launch_packed(a->stream, default_pairs ? a->d_state + i0 * n_pos : S->d_words.get(), uint32_t(n_pos), default_pairs,
+                                                    C->pk, uint32_t(n), d_cacc));
+            }
+            HIP_TRY(osr_launch_store(a->stream, OsrStore{d_cacc, S->d_sizes + 2, row, i0 * P.cols, P.col0, n * P.cols, n_pairs, uint32_t(bins), uint32_t(bins),
+                                                         uint32_t(S->entries), offset}));
+        }
+    }
+    if (a != b) { // b's next sweeps must not run under a's reads
+        HIP_TRY(hipEventRecord(S->ev[1], a->stream));
+        HIP_TRY(hipStreamWaitEvent(b->stream, S->ev[1], 0));
+    }
+    S->timesteps.push_back(a->t);
+    return ISINGMC_OK;
+}
+
+static int osr_full(const isingmc_overlap_series *S)
+{
+    return fail(ISINGMC_ERR_INVALID, "the overlap series is full: it holds " + std::to_string(S->capacity) +
+                                         " rows, its capacity (isingmc_overlap_series_get, then isingmc_overlap_series_reset)");
+}
+
+extern "C" int isingmc_overlap_series_record(isingmc_overlap_series *S, const uint32_t *slots_a, const uint32_t *slots_b)
+{
+    if (!S) return fail(ISINGMC_ERR_INVALID, "NULL series");
+    isingmc_states *a = S->a, *b = S->b;
+    const size_t n_pairs = S->n_pairs;
+    const uint32_t *d_sa = nullptr, *d_sb = nullptr;
+    OverlapPairing P;
+    if (osr_by_rung(S)) {
+        if (slots_a || slots_b) return fail(ISINGMC_ERR_INVALID, "a series made with ISINGMC_SERIES_BY_RUNG takes no slot tables: its pairs are the rungs of the two ladders");
+        const std::string why = osr_ladders_obstacle(a, b, n_pairs); // (a ladder may have been detached and attached again since)
+        if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
+        d_sa = a->d_pt_perm;
+        d_sb = b->d_pt_perm;
+    } else {
+        TRY(overlap_pairing(a, b, slots_a, slots_b, n_pairs, P));
+    }
+    if (S->timesteps.size() >= S->capacity) return osr_full(S);
+    TRY(use_device(a->g->device));
+    if (!osr_by_rung(S) && !P.default_pairs) {
+        // the tables go into a block of the series; the host copy lives until a's stream has passed the upload
+        if (!S->uploads.empty() && hipStreamQuery(a->stream) == hipSuccess) S->uploads.clear();
+        S->uploads.emplace_back(2 * n_pairs);
+        uint32_t *h = S->uploads.back().data();
+        std::copy(P.slots_a, P.slots_a + n_pairs, h);
+        std::copy(P.slots_b, P.slots_b + n_pairs, h + n_pairs);
+        HIP_TRY(hipMemcpyAsync(S->d_slots, h, 2 * n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, a->stream));
+        d_sa = S->d_slots;
+        d_sb = S->d_slots + n_pairs;
+    }
+    return osr_enqueue(S, d_sa, d_sb);
+}
+
+extern "C" int isingmc_overlap_series_set_every(isingmc_overlap_series *S, size_t every)
+{
+    if (!S) return fail(ISINGMC_ERR_INVALID, "NULL series");
+    isingmc_states *a = S->a;
+    if (every == 0) { // off: the rows stay
+        if (a->osr == S) {
+            a->osr = nullptr;
+            a->osr_every = 0;
+        }
+        return ISINGMC_OK;
+    }
+    if (S->b != a || osr_by_rung(S))
+        return fail(ISINGMC_ERR_INVALID, "a period is for a series inside one container (b == NULL, no ISINGMC_SERIES_BY_RUNG): between two containers "
+                                         "there is no common step loop; record explicitly, as with isingmc_icm_between");
+    if (a->osr && a->osr != S) return fail(ISINGMC_ERR_INVALID, "another overlap series of this container records on a period already: one periodic series per container");
+    OverlapPairing P;
+    TRY(overlap_pairing(a, a, nullptr, nullptr, S->n_pairs, P)); // a periodic record takes no tables: the pairs (2 p, 2 p + 1)
+    a->osr = S;
+    a->osr_every = every;
+    a->osr_t0 = a->t;
+    a->osr_last_t = 0;
+    return ISINGMC_OK;
+}
+
+std::string osr_run_obstacle(const isingmc_states *s, size_t timesteps)
+{
+    if (!s->osr_every || !s->osr) return "";
+    const uint64_t done = s->t - s->osr_t0; // sample points: t0 + every, t0 + 2 every, ...
+    const uint64_t samples = (done + timesteps) / s->osr_every - done / s->osr_every;
+    const size_t have = s->osr->timesteps.size();
+    if (samples <= s->osr->capacity - have) return "";
+    return "the overlap series of this container would run full: the call takes " + std::to_string(samples) + " samples and the log has room for " +
+           std::to_string(s->osr->capacity - have) + " of its " + std::to_string(s->osr->capacity) +
+           " rows (isingmc_overlap_series_get, then isingmc_overlap_series_reset; or switch the period off)";
+}
+
+int osr_sample_enqueue(isingmc_states *s)
+{
+    isingmc_overlap_series *S = s->osr;
+    if (S->timesteps.size() >= S->capacity) return osr_full(S);
+    return osr_enqueue(S, nullptr, nullptr);
+}
+
+extern "C" int isingmc_overlap_series_count(const isingmc_overlap_series *S, size_t *n_out, size_t *capacity_out)
+{
+    if (!S) return fail(ISINGMC_ERR_INVALID, "NULL series");
+    if (n_out) *n_out = S->timesteps.size();
+    if (capacity_out) *capacity_out = S->capacity;
+    return ISINGMC_OK;
+}
+
+extern "C" int isingmc_overlap_series_get(isingmc_overlap_series *S, size_t first, size_t n, uint64_t *timesteps_out, int64_t *spin_out,
+                                          int64_t *link_out, int64_t *class_out)
+{
+    if (!S) return fail(ISINGMC_ERR_INVALID, "NULL series");
+    const size_t have = S->timesteps.size();
+    if (first > have || n > have - first) return fail(ISINGMC_ERR_INVALID, "rows out of range: the series holds " + std::to_string(have) + " rows");
+    if (link_out && !osr_link(S)) return fail(ISINGMC_ERR_INVALID, "no link overlaps are held: make the series with ISINGMC_SERIES_LINK (link_out may be NULL)");
+    if (class_out && !S->bins) return fail(ISINGMC_ERR_INVALID, "no overlaps by class are held: make the series with a class set (class_out may be NULL)");
+    isingmc_states *a = S->a;
+    TRY(use_device(a->g->device));
+    HIP_TRY(hipStreamSynchronize(a->stream));
+    S->uploads.clear();
+    TRY(strip_error(strip_check(a)));
+    if (timesteps_out) std::copy(S->timesteps.begin() + first, S->timesteps.begin() + first + n, timesteps_out);
+    if (n == 0 || (!spin_out && !link_out && !class_out)) return ISINGMC_OK;
+    const size_t E = S->entries, row = S->n_pairs * E, bins = S->bins, off = osr_link(S) ? 2 : 1;
+    std::vector<long long> h;
+    TRY(read_back(a, h, S->d_log.get() + first * row, n * row));
+    for (size_t i = 0; i < n * S->n_pairs; i++) { // (row, pair)
+        const long long *e = h.data() + i * E;
+        if (spin_out) spin_out[i] = e[0];
+        if (link_out) link_out[i] = e[1];
+        if (class_out) std::copy(e + off, e + off + bins, class_out + i * bins);
+    }
+    return ISINGMC_OK;
+}
+
+extern "C" int isingmc_overlap_series_reset(isingmc_overlap_series *S)
+{
+    if (!S) return fail(ISINGMC_ERR_INVALID, "NULL series");
+    // rows enqueued so far still land in the log, ahead on a's stream of whatever overwrites them: nothing to wait for
+    S->timesteps.clear();
+    if (S->a->osr == S) S->a->osr_last_t = 0;
+    return ISINGMC_OK;
+}

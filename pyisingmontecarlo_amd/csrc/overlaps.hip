@@ -4,7 +4,7 @@
 #include "internal.hpp"
 
 // why these containers cannot be measured against each other ("" when they can; a == b: pairs inside one container)
-static std::string overlaps_obstacle(const isingmc_states *a, const isingmc_states *b)
+std::string overlaps_obstacle(const isingmc_states *a, const isingmc_states *b)
 {
     if (a->g != b->g) return "the two containers belong to different graph handles: both must be replicas of one isingmc_graph";
     const isingmc_graph *g = a->g; // (one graph handle: one device)
@@ -18,17 +18,8 @@ static std::string overlaps_obstacle(const isingmc_states *a, const isingmc_stat
     return lattice_obstacle(g, "overlaps", true, false);
 }
 
-// The pairs of one call, validated: what isingmc_overlaps and isingmc_overlaps_by_class share.  On success b is never NULL and
-// either default_pairs holds (the pairing (2 p, 2 p + 1) inside one container, no tables) or slots_a / slots_b are host tables of
-// n_pairs entries below their containers' counts (`identity` backs them for two containers without tables).
-struct OverlapPairing {
-    isingmc_states *b = nullptr;
-    const uint32_t *slots_a = nullptr, *slots_b = nullptr;
-    bool default_pairs = false;
-    std::vector<uint32_t> identity;
-};
-
-static int overlap_pairing(isingmc_states *a, isingmc_states *b, const uint32_t *slots_a, const uint32_t *slots_b, size_t n_pairs, OverlapPairing &P)
+// the pairs of one call, validated (OverlapPairing, internal.hpp)
+int overlap_pairing(isingmc_states *a, isingmc_states *b, const uint32_t *slots_a, const uint32_t *slots_b, size_t n_pairs, OverlapPairing &P)
 {
     if (!b) b = a;
     {
@@ -124,19 +115,7 @@ extern "C" int isingmc_overlaps(isingmc_states *a, isingmc_states *b, const uint
 }
 
 // ---- overlaps resolved by a class label per site ----------------------------------------------------------------
-// A class set as the kernels of overlap_class_kernels.hip read it: on a recognised lattice the tables in plane order with one
-// shared-class entry per word, on a graph with a replica-packed layout the positions sorted by class and cut into segments.  A
-// graph that only the f64 CSR family serves gets the sizes alone: the measurement refuses its containers.
-struct isingmc_site_classes {
-    const isingmc_graph *g = nullptr;
-    int device = 0;
-    size_t n_tables = 0, n_classes = 0;
-    std::vector<uint64_t> sizes; // [n_tables][n_classes]
-    bool has_lat = false, has_pk = false;
-    LatClassDev lat{};
-    PkClassDev pk{};
-    DevBlocks dev_allocs;
-};
+// (the class set itself, isingmc_site_classes, is in internal.hpp: the overlap series reads it too)
 
 // the limits of a class set and the values of its tables ("" when they hold)
 static std::string class_set_obstacle(const uint32_t *cls, size_t nvars, size_t n_tables, size_t n_classes)

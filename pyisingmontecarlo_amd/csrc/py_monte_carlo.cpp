@@ -122,6 +122,15 @@ struct ClassesHandle {
     ~ClassesHandle() { isingmc_site_classes_destroy(c); }
 };
 
+// an overlap series with the class set it reads: the series goes first, and both before their container
+struct SeriesHandle {
+    isingmc_overlap_series *s = nullptr;
+    ClassesHandle classes;
+    bool link = false;
+    size_t n_pairs = 0, n_tables = 0, n_classes = 0;
+    ~SeriesHandle() { isingmc_overlap_series_destroy(s); }
+};
+
 struct EdgeArrays {
     std::vector<uint64_t> a, b;
     std::vector<double> j;
@@ -905,6 +914,54 @@ public:
         return py::make_tuple(n, site, bonds ? py::object(bond) : py::object(py::none()));
     }
     void reset_measured_spins() { check(isingmc_moments_reset(st_->s)); }
+    // extension: the overlaps between the persistent replicas (2 p, 2 p + 1), logged on the device once per sample.
+    // set_measure_overlaps_every(k, link, classes, capacity): a row follows every k-th timestep from now on, without the host
+    // waiting (0: off, the rows stay); a call with k > 0 starts a new log of `capacity` rows.  classes: class tables as
+    // get_overlaps_by_class takes them, or None.  get_measured_overlaps() -> (timesteps uint64[n], spin int64[n, P], link int64[n, P]
+    // or None, by_class int64[n, P, T, C] or None); reset_measured_overlaps() empties the log and keeps the period.  add_graph is
+    // refused while it is on.  ValueError where isingmc_overlap_series_create / _set_every refuse.
+    void set_measure_overlaps_every(size_t k, bool link, const py::object &classes, size_t capacity)
+    {
+        if (k == 0) {
+            if (series_) check(isingmc_overlap_series_set_every(series_->s, 0));
+            return;
+        }
+        auto h = std::make_unique<SeriesHandle>();
+        if (!classes.is_none()) {
+            const ClassTables T = class_tables(classes, py::none(), E_.nvars);
+            check(isingmc_site_classes_create(st_->graph->g, T.cls.data(), T.n_tables, T.n_classes, &h->classes.c));
+            h->n_tables = T.n_tables;
+            h->n_classes = T.n_classes;
+        }
+        h->link = link;
+        h->n_pairs = isingmc_states_count(st_->s) / 2;
+        check(isingmc_overlap_series_create(st_->s, nullptr, h->n_pairs, h->classes.c, link ? ISINGMC_SERIES_LINK : 0u, capacity, &h->s));
+        series_.reset(); // (the old log goes, and its period with it, before the new one takes the container's one period)
+        check(isingmc_overlap_series_set_every(h->s, k));
+        series_ = std::move(h);
+    }
+    py::tuple get_measured_overlaps()
+    {
+        if (!series_) throw py::value_error("no overlaps are logged: call set_measure_overlaps_every(k) first");
+        const SeriesHandle &h = *series_;
+        size_t n = 0;
+        check(isingmc_overlap_series_count(h.s, &n, nullptr));
+        const ssize_t N = ssize_t(n), P = ssize_t(h.n_pairs);
+        py::array_t<uint64_t> t(std::vector<ssize_t>{N});
+        py::array_t<int64_t> spin(std::vector<ssize_t>{N, P}), lnk(std::vector<ssize_t>{h.link ? N : 0, P});
+        py::array_t<int64_t> cls(std::vector<ssize_t>{h.n_tables ? N : 0, P, ssize_t(h.n_tables), ssize_t(h.n_classes)});
+        uint64_t *t_out = t.mutable_data();
+        int64_t *s_out = spin.mutable_data(), *l_out = h.link ? lnk.mutable_data() : nullptr, *c_out = h.n_tables ? cls.mutable_data() : nullptr;
+        {
+            py::gil_scoped_release nogil;
+            check(isingmc_overlap_series_get(h.s, 0, n, t_out, s_out, l_out, c_out));
+        }
+        return py::make_tuple(t, spin, h.link ? py::object(lnk) : py::object(py::none()), h.n_tables ? py::object(cls) : py::object(py::none()));
+    }
+    void reset_measured_overlaps()
+    {
+        if (series_) check(isingmc_overlap_series_reset(series_->s));
+    }
     // extension: Swendsen-Wang cluster steps on the persistent replicas (see Lattice.set_cluster_update_every); the graph is known
     // here, so one the cluster step does not serve raises ValueError at once
     void set_cluster_update_every(size_t k) { check(isingmc_states_set_cluster_every(st_->s, k)); }
@@ -970,6 +1027,7 @@ private:
     std::vector<uint64_t> drawn_;
     std::shared_ptr<GraphHandle> graph_;
     std::shared_ptr<StatesHandle> st_;
+    std::unique_ptr<SeriesHandle> series_; // (declared last: destroyed before the container it reads)
 };
 
 } // namespace
@@ -1052,6 +1110,10 @@ PYBIND11_MODULE(_py_monte_carlo, m)
         .def("get_num_graphs", &ClassicIsing::get_num_graphs)
         .def("get_overlaps", &ClassicIsing::get_overlaps, "pairs"_a = py::none(), "link"_a = true)
         .def("get_overlaps_by_class", &ClassicIsing::get_overlaps_by_class, "classes"_a, "n_classes"_a = py::none(), "pairs"_a = py::none())
+        .def("set_measure_overlaps_every", &ClassicIsing::set_measure_overlaps_every, "k"_a, "link"_a = true, "classes"_a = py::none(),
+             "capacity"_a = 4096)
+        .def("get_measured_overlaps", &ClassicIsing::get_measured_overlaps)
+        .def("reset_measured_overlaps", &ClassicIsing::reset_measured_overlaps)
         .def("set_track_minimum", &ClassicIsing::set_track_minimum, "every"_a)
         .def("get_minimum", &ClassicIsing::get_minimum)
         .def("reset_minimum", &ClassicIsing::reset_minimum)

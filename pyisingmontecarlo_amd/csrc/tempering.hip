@@ -75,6 +75,9 @@ extern "C" int isingmc_pt_detach(isingmc_states *s)
     if (s->mom_every)
         return fail(ISINGMC_ERR_INVALID, "sums per rung are switched on for this container (isingmc_states_set_moments_every): their samples read the ladder's "
                                          "permutation; switch accumulation off first");
+    if (s->osr_by_rung_live)
+        return fail(ISINGMC_ERR_INVALID, "an overlap series made with ISINGMC_SERIES_BY_RUNG reads this ladder's permutation on the device "
+                                         "(isingmc_overlap_series_destroy first)");
     TRY(use_device(s->g->device));
     HIP_TRY(hipStreamSynchronize(s->stream)); // enqueued rounds may still read the ladder
     TRY(strip_error(strip_check(s)));
@@ -199,7 +202,8 @@ extern "C" int isingmc_pt_run(isingmc_states *s, size_t timesteps, size_t swap_e
     const bool in_kernel = P.use && P.replicas_per_pass >= s->R && rounds >= 2 && rounds * swap_every <= 65536 &&
                            s->R == s->pt.n_rungs && s->opt.pt_in_kernel != 0 &&
                            !s->best_every && // minimum tracking reads every round's energies: one launch per round
-                           !s->mom_every;    // sums per rung (S19) read the configurations and the permutation between the rounds: the same
+                           !s->mom_every &&  // sums per rung (S19) read the configurations and the permutation between the rounds: the same
+                           !s->osr_every;    // ... and so does a periodic overlap series (S21)
     if (in_kernel) {
         const size_t R = s->R, nk = rounds * swap_every;
         if (!s->d_pt_mail) {

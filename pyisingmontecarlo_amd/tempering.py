@@ -131,6 +131,7 @@ class ClassicalTempering:
                           for s in (self._seed, self._seed ^ COPY_SEED_XOR)]
             self._t = 0               # absolute timestep, the same on both copies
             self._icm_stats, self._icm_pending = None, False
+        self._ovl_series, self._ovl_every, self._ovl_t0, self._ovl_classes = None, 0, 0, None   # overlap series
         self._betas = []
         self._slot_seeds = []
         self._n_drawn = 0
@@ -265,6 +266,64 @@ class ClassicalTempering:
         finally:
             if own:
                 classes.close()
+
+    # -- the overlaps at every rung, logged on the device once per sample -----------------------------------------
+    def set_measure_overlaps_every(self, k, link=True, classes=None, capacity=4096):
+        """copies=2 only: from now on a row of overlaps between the two configurations at every rung follows each k-th timestep,
+        logged on the device without the host waiting (0: off, the rows stay; a call with k > 0 starts a new log of `capacity`
+        rows).  Where several things fall on one boundary the order is the timestep (a sweep or a cluster move), the sample, the
+        exchange round: a configuration counts at the beta it was just swept at.  classes: what site_classes() returned, class
+        tables, or None.  On the device's stream the pairs are read from the ladders' permutations on the device; on the host
+        swap path the host permutations go with every record.  No configuration, random number or exchange decision changes."""
+        if int(k) < 0:
+            raise ValueError("k must not be negative")
+        if self._pair is None:
+            raise ValueError("overlaps need two configurations per temperature: build the ladder with copies=2")
+        if self._devices is not None or self._world > 1:   # (copies=2 refuses both at construction: kept for the message)
+            raise ValueError("the overlap series is for a ladder on one process and one device: not with devices=[...] or a "
+                             "torch.distributed group of several ranks")
+        if int(k) == 0:
+            self._ovl_every = 0
+            return
+        self._materialise_pair()
+        a, b = self._pair
+        if not hasattr(a._states, "overlap_series"):
+            raise ValueError("this engine has no overlap series (overlap_series)")
+        if classes is not None and not isinstance(classes, _capi.SiteClasses):
+            classes = self.site_classes(classes)
+        series = a._states.overlap_series(b._states, len(self._betas), classes, link=link, by_rung=self._on_stream, capacity=capacity)
+        if self._ovl_series is not None:
+            self._ovl_series.close()
+        self._ovl_series, self._ovl_classes = series, classes
+        self._ovl_every, self._ovl_t0 = int(k), self._t
+
+    def get_measured_overlaps(self):
+        """(timesteps uint64[n], spin int64[n, G], link int64[n, G] or None, by_class int64[n, G, T, C] or None): the rows logged
+        so far in the order of get_betas(), the exact integers of get_overlaps() / get_overlaps_by_class().  Synchronises."""
+        if self._ovl_series is None:
+            raise ValueError("no overlaps are logged: call set_measure_overlaps_every(k) first")
+        return self._ovl_series.get()
+
+    def reset_measured_overlaps(self):
+        """The log back to no rows; the period stays."""
+        if self._ovl_series is None:
+            raise ValueError("no overlaps are logged: call set_measure_overlaps_every(k) first")
+        self._ovl_series.reset()
+
+    def _until_sample(self):
+        """Timesteps up to and including the one the next sample follows (None: no sample is due)."""
+        k = self._ovl_every
+        return (k - (self._t - self._ovl_t0) % k) if k else None
+
+    def _pair_sample(self):
+        """The sample behind timestep self._t - 1, if one falls there: before any exchange round on the same boundary."""
+        k = self._ovl_every
+        if not k or (self._t - self._ovl_t0) % k:
+            return
+        if self._on_stream:
+            self._ovl_series.record()   # the rung permutations are read on the device
+        else:
+            self._ovl_series.record(self._pair[0]._perm, self._pair[1]._perm)
 
     # -- every slot's lowest-energy configuration (DESIGN.md S16) ---------------------------------------------------------------
     def set_track_minimum(self, on):
@@ -471,16 +530,20 @@ class ClassicalTempering:
         while done < t:
             m = self._until_icm()
             if m == 0:
-                self._pair_icm()   # a timestep; a round that falls on the same boundary comes after it
+                self._pair_icm()   # a timestep; a sample, then a round, that fall on the same boundary come after it
                 done += 1
+                self._pair_sample()
                 if f and done % f == 0:
                     for c in self._pair:
                         c._swap_step()
                 continue
             n = t - done if m is None else min(m, t - done)
             while n > 0:
-                if f and done % f == 0 and n >= f and self._on_stream:
-                    whole = n // f * f     # rounds inside the stretch: one library call (in-kernel rounds on strip shapes)
+                u = self._until_sample()
+                whole = n // f * f if f else 0   # rounds inside the stretch: one library call (in-kernel rounds on strip shapes)
+                if u is not None:                # ... which ends before the next sample: that one goes between a timestep and its round
+                    whole = min(whole, (u - 1) // f * f) if f else 0
+                if f and done % f == 0 and whole >= f and self._on_stream:
                     for c in self._pair:
                         c._states.pt_run(whole, f)
                     self._t += whole
@@ -488,9 +551,11 @@ class ClassicalTempering:
                     n -= whole
                     continue
                 b = min(n, f - done % f) if f else n
+                b = b if u is None else min(b, u)
                 self._pair_sweeps(b)
                 done += b
                 n -= b
+                self._pair_sample()
                 if f and done % f == 0:
                     for c in self._pair:
                         c._swap_step()
