@@ -4,7 +4,7 @@
 //   isingmc.hip    replica containers, the policy of every sweep / measurement launch, the persistent strip kernel's host side
 //   nonlocal.hip   host side of the non-local moves: Swendsen-Wang steps, isoenergetic cluster moves inside and between containers
 //   overlaps.hip   spin and link overlaps between replica pairs (isingmc_overlaps), and the spin overlap by site class
-//                  (isingmc_site_classes_*, isingmc_overlaps_by_class)
+//                  (isingmc_site_classes_*, isingmc_overlaps_by_class); the overlap core they share with the series
 //   overlap_series.hip  the device-resident log of overlap measurements, one row per sample (isingmc_overlap_series_*)
 //   best.hip       each replica's lowest-energy configuration, kept on the device (isingmc_best_*)
 //   moments.hip    per-site spin sums and per-bond sums over the samples of a run (isingmc_moments_*)
@@ -244,6 +244,22 @@ struct StepPreset {
     const RjBeta *rj = nullptr;        // real-coupling packed path
 };
 
+// A measurement the step loop takes on a period: a sample follows every timestep t > t0 with (t - t0) % every == 0.  A call
+// repeated after a strip launch gave up (with_strip_retry) takes no sample twice: the samples up to replay_to were taken by the
+// attempt that is repeated (last_t: the timestep of the last sample the step loop took).
+struct Periodic {
+    size_t every = 0; // 0 = off
+    uint64_t t0 = 0, last_t = 0, replay_to = 0;
+    uint64_t phase(uint64_t t) const { return (t - t0) % every; }
+    // timesteps from t up to and including the next sample point (no bound while off)
+    size_t stretch(uint64_t t) const { return every ? size_t(every - phase(t)) : std::numeric_limits<size_t>::max(); }
+    bool due(uint64_t t) const { return every && phase(t) == 0 && t > replay_to; }
+    uint64_t points(uint64_t t, uint64_t n) const { return (t - t0 + n) / every - (t - t0) / every; } // sample points in (t, t + n]
+    void restart(uint64_t t) { t0 = t; last_t = 0; } // the sample points are counted from t
+    // around the repeat of a call that started at timestep t: it skips the samples already taken
+    void replay_since(uint64_t t) { replay_to = every && last_t > t ? last_t : 0; }
+};
+
 struct isingmc_states {
     isingmc_graph *g = nullptr;
     Options opt; // the environment's switches when the container was created (isingmc_states_set_option changes one)
@@ -360,7 +376,8 @@ struct isingmc_states {
     bool pa_families_set = false;   // d_pa_family holds the table (else: the identity)
     // each replica's lowest-energy configuration (isingmc_best_*): allocated when tracking is switched on (or by the
     // first isingmc_best_update) for the replicas the container holds then, and kept
-    size_t best_every = 0;            // an update follows every timestep after which t % best_every == 0; 0 = off
+    Periodic best_at;                 // an update follows every timestep after which t % every == 0 (t0 stays 0, no replay guard:
+                                      // a repeated call finds the same records again and changes none)
     DevBlock<uint32_t> d_best_state; // as large as d_state, same layout; padding positions and unowned bits of a packed container
     size_t best_state_words = 0;      // hold no defined value (cleared once, so that the raw read-out is deterministic)
     size_t best_cap = 0;              // replicas the records below hold
@@ -371,9 +388,8 @@ struct isingmc_states {
     DevBlock<unsigned long long> d_best_count; // improvements so far
     // per-site and per-bond sums over the samples of a run (isingmc_moments_*): allocated when accumulation is
     // switched on (or by the first isingmc_moments_accumulate) for the replicas the container holds then, and kept
-    size_t mom_every = 0;        // a sample follows every timestep t > mom_t0 with (t - mom_t0) % mom_every == 0; 0 = off
+    Periodic mom_at;             // the sample points of the step loop
     unsigned mom_flags = 0;      // ISINGMC_MOMENTS_* of the sums held
-    uint64_t mom_t0 = 0;
     uint64_t mom_n = 0;          // samples in the sums
     bool mom_have = false;       // the blocks below are allocated, for mom_R replicas
     size_t mom_R = 0;
@@ -382,14 +398,10 @@ struct isingmc_states {
     DevBlock<uint32_t> d_mom_planes, d_mom_totals;        // per-replica mode: mom_k time planes of the state's shape, 32-bit totals
     int mom_k = 0;
     uint32_t mom_pending = 0;    // samples in the time planes since the last flush (< 2^mom_k)
-    // a call repeated after a strip launch gave up (with_strip_retry) takes no sample twice: the samples up to mom_replay_to were
-    // taken by the attempt that is repeated (mom_last_t: the timestep of the last sample the step loop took)
-    uint64_t mom_last_t = 0, mom_replay_to = 0;
-    // the overlap series of this container that records on a period (isingmc_overlap_series_set_every): a row
-    // follows every timestep t > osr_t0 with (t - osr_t0) % osr_every == 0; the replay guard is the one of the moment sums
+    // the overlap series of this container that records on a period (isingmc_overlap_series_set_every): a row at
+    // every sample point of osr_at
     isingmc_overlap_series *osr = nullptr;
-    size_t osr_every = 0;
-    uint64_t osr_t0 = 0, osr_last_t = 0, osr_replay_to = 0;
+    Periodic osr_at;
     size_t osr_by_rung_live = 0; // live series that read this container's ladder permutation on the device: no isingmc_pt_detach
     bool strip_guard = false; // inside with_strip_retry: a strip launch is checked before an update may keep what it left
 
@@ -461,6 +473,15 @@ static int read_back(isingmc_states *s, std::vector<T> &h, const T *d, size_t n)
     h.resize(n);
     HIP_TRY(hipMemcpyAsync(h.data(), d, n * sizeof(T), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
+    return ISINGMC_OK;
+}
+
+// `waiter` goes on behind what `ahead` holds so far.  ev: an event of the caller's -- which one it owns is part of its lifetime
+// rules (a container's icmb_ev for the between move and the synchronising overlap calls, a series' own for its records)
+static inline int stream_wait_for(hipStream_t waiter, hipStream_t ahead, hipEvent_t ev)
+{
+    HIP_TRY(hipEventRecord(ev, ahead));
+    HIP_TRY(hipStreamWaitEvent(waiter, ev, 0));
     return ISINGMC_OK;
 }
 
@@ -581,10 +602,56 @@ struct OverlapPairing {
 // why these containers cannot be measured against each other ("" when they can; a == b: pairs inside one container)
 IM_INTERNAL std::string overlaps_obstacle(const isingmc_states *a, const isingmc_states *b);
 IM_INTERNAL int overlap_pairing(isingmc_states *a, isingmc_states *b, const uint32_t *slots_a, const uint32_t *slots_b, size_t n_pairs, OverlapPairing &P);
+// why this class set cannot resolve the overlaps of a's replicas ("" when it can)
+IM_INTERNAL std::string classes_obstacle(const isingmc_site_classes *classes, const isingmc_states *a);
+
+// The overlap core: isingmc_overlaps, isingmc_overlaps_by_class and the records of the overlap series are one measurement, cut
+// into the same batches and enqueued by the same two functions; they differ in where the workspace lives and in what becomes of
+// the accumulators.
+// One measurement: device slot tables, or nullptr for the pairs (2 p, 2 p + 1) of one container
+struct OverlapJob {
+    isingmc_states *a, *b; // b == a: pairs inside one container
+    const uint32_t *d_sa, *d_sb;
+    size_t n_pairs;
+    bool link;                           // (the spin / link pass)
+    const isingmc_site_classes *classes; // (the class pass; nullptr when there is none)
+    bool default_pairs() const { return d_sa == nullptr; }
+    size_t bins() const { return classes ? classes->n_tables * classes->n_classes : 0; }
+};
+// Its batches under a's cluster_workspace_bytes
+struct OverlapPlan {
+    size_t acc_pairs = 0, acc0 = 0; // accumulator columns of the spin / link launches and the column of pair 0
+    size_t blocks = 0, batch = 0;   // packed containers with tables: pair blocks of 32 pairs and those of one batch (else batch = 0)
+    size_t cols = 1, items = 0, col0 = 0, cbatch = 0; // by class: pair columns per item, items, the column of pair 0, items per batch
+};
+IM_INTERNAL OverlapPlan overlap_plan(const isingmc_states *a, size_t n_pairs, bool default_pairs, size_t bins);
+// Its workspace: acc[2 acc_pairs] for the spin / link pass, cacc[cbatch cols bins] for the class pass, and where batch != 0 the
+// gathered overlap words of one batch of either pass, words[batch n_pos] / words[cbatch n_pos]
+struct OverlapWork {
+    unsigned long long *acc, *cacc;
+    uint32_t *words;
+};
+// What becomes of a finished batch of accumulators -- (accumulators, first column of the batch, columns in the batch) -- by
+// reference to the caller's callable, which outlives the call it is passed to.  (No std::function: a record of the series
+// must not allocate per batch.)
+class OverlapSink {
+    void *f;
+    int (*call)(void *, const unsigned long long *, size_t, size_t);
+
+public:
+    template <typename F>
+    OverlapSink(F &fn) : f(&fn), call([](void *p, const unsigned long long *acc, size_t c0, size_t n) { return (*static_cast<F *>(p))(acc, c0, n); }) {}
+    int operator()(const unsigned long long *acc, size_t c0, size_t n) const { return call(f, acc, c0, n); }
+};
+// Enqueue on a's stream; the caller has joined the lanes and put a's stream behind b's.  The spin / link pass clears acc, counts
+// into it and hands all acc_pairs columns to the sink once; the class pass does so batch by batch with cacc.
+IM_INTERNAL int overlap_enqueue(const OverlapJob &J, const OverlapPlan &P, const OverlapWork &W, OverlapSink sink);
+IM_INTERNAL int overlap_class_enqueue(const OverlapJob &J, const OverlapPlan &P, const OverlapWork &W, OverlapSink sink);
+IM_INTERNAL int overlap_lanes_join(isingmc_states *a, isingmc_states *b); // both containers' sweeps so far on their main streams
 
 // ---- overlap_series.hip (the device-resident log of overlap measurements) ----------------------------------------------------
-// why a run of `timesteps` timesteps cannot start ("" when it can): the periodic series of the container would run full in it
-IM_INTERNAL std::string osr_run_obstacle(const isingmc_states *s, size_t timesteps);
+// before a run of `timesteps` timesteps enqueues anything: fails when the periodic series of the container would run full in it
+IM_INTERNAL int osr_room_or_fail(const isingmc_states *s, size_t timesteps);
 IM_INTERNAL int osr_sample_enqueue(isingmc_states *s); // enqueue: one row of the container's periodic series at timestep s->t
 
 // ---- nonlocal.hip (Swendsen-Wang steps and isoenergetic cluster moves) -------------------------------------------------------
@@ -632,11 +699,10 @@ static int with_strip_retry(isingmc_states *s, bool may_strip, F &&call)
     s->strip_guard = false;
     if (rc != STRIP_TIMED_OUT) return rc;
     TRY(snapshot_restore(s));
-    s->mom_replay_to = s->mom_every && s->mom_last_t > t0 ? s->mom_last_t : 0; // (the repeat skips the samples already in the sums)
-    s->osr_replay_to = s->osr_every && s->osr_last_t > t0 ? s->osr_last_t : 0;  // (... and the rows already in the overlap series)
+    s->mom_at.replay_since(t0); // (the repeat skips the samples already in the sums
+    s->osr_at.replay_since(t0); // ... and the rows already in the overlap series)
     s->t = t0;
     const int rc2 = strip_error(call());
-    s->mom_replay_to = 0;
-    s->osr_replay_to = 0;
+    s->mom_at.replay_to = s->osr_at.replay_to = 0;
     return rc2;
 }

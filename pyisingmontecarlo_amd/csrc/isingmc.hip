@@ -145,9 +145,9 @@ extern "C" int isingmc_states_append(isingmc_states *s, uint64_t seed, const uin
 {
     if (!s) return fail(ISINGMC_ERR_INVALID, "NULL states");
     if (s->has_betas) return fail(ISINGMC_ERR_INVALID, "clear the per-replica betas before appending replicas");
-    if (s->best_every) return fail(ISINGMC_ERR_INVALID, "minimum tracking is switched on for this container (isingmc_states_set_track_best): its records are sized for the replicas it holds; switch tracking on after the graphs are added");
-    if (s->mom_every) return fail(ISINGMC_ERR_INVALID, "moment sums are switched on for this container (isingmc_states_set_moments_every): they are sized for the replicas it holds; switch accumulation on after the graphs are added");
-    if (s->osr_every) return fail(ISINGMC_ERR_INVALID, "an overlap series records on a period for this container (isingmc_overlap_series_set_every): its pairs are those of the replicas it holds; switch the period on after the graphs are added");
+    if (s->best_at.every) return fail(ISINGMC_ERR_INVALID, "minimum tracking is switched on for this container (isingmc_states_set_track_best): its records are sized for the replicas it holds; switch tracking on after the graphs are added");
+    if (s->mom_at.every) return fail(ISINGMC_ERR_INVALID, "moment sums are switched on for this container (isingmc_states_set_moments_every): they are sized for the replicas it holds; switch accumulation on after the graphs are added");
+    if (s->osr_at.every) return fail(ISINGMC_ERR_INVALID, "an overlap series records on a period for this container (isingmc_overlap_series_set_every): its pairs are those of the replicas it holds; switch the period on after the graphs are added");
     TRY(use_device(s->g->device));
     if (s->packed) return pk_append(s, seed, initial_state);
     return add_replicas(s, 1, &seed, initial_state);
@@ -196,10 +196,8 @@ extern "C" int isingmc_states_set_timestep(isingmc_states *s, uint64_t t)
     TRY(use_device(s->g->device));
     HIP_TRY(hipStreamSynchronize(s->stream));
     s->t = t;
-    s->mom_t0 = t; // the sample points of the moment sums are counted from here
-    s->mom_last_t = 0;
-    s->osr_t0 = t; // ... and those of a periodic overlap series (S21)
-    s->osr_last_t = 0;
+    s->mom_at.restart(t); // the sample points of the moment sums are counted from here
+    s->osr_at.restart(t); // ... and those of a periodic overlap series (S21)
     return ISINGMC_OK;
 }
 
@@ -1020,10 +1018,7 @@ bool may_use_strips(const isingmc_states *s)
 int run_steps(isingmc_states *s, size_t timesteps, const double *betas, size_t beta_stride,
               double *energies_per_step, float *device_ms, bool sync, double *final_energies)
 {
-    if (s && s->osr_every) { // a periodic overlap series that would run full: nothing is enqueued
-        const std::string why = osr_run_obstacle(s, timesteps);
-        if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
-    }
+    if (s) TRY(osr_room_or_fail(s, timesteps));
     const bool may_strip = sync && timesteps >= 2 && may_use_strips(s) && strip_plan(s, timesteps).use;
     return with_strip_retry(s, may_strip, [&] {
         return run_steps_impl(s, timesteps, betas, beta_stride, energies_per_step, device_ms, sync, final_energies);
@@ -1469,6 +1464,19 @@ static int run_steps_impl(isingmc_states *s, size_t timesteps, const double *bet
     } lane_join{s};
     if (P.lanes > 1 && P.path != StepPath::Packed) TRY(lanes_fork(s, P.lanes)); // (the packed runner forks behind its table launches)
     int rc = ISINGMC_OK;
+    // A periodic update whose sample point is timestep s->t, unless the attempt this call repeats has taken it already
+    // (with_strip_retry).  A call that may be repeated after a strip launch gave up keeps nothing such a launch left: the launch is
+    // waited for and checked first.  (The status returned is the wait's alone; everything else goes into rc.)
+    const auto sample = [&](Periodic &p, int (*enqueue)(isingmc_states *)) -> int {
+        if (rc != ISINGMC_OK || !p.due(s->t)) return ISINGMC_OK;
+        if (s->strip_guard && P.path == StepPath::LatStrip) {
+            HIP_TRY(hipStreamSynchronize(s->stream));
+            rc = strip_check(s);
+        }
+        if (rc == ISINGMC_OK) rc = enqueue(s);
+        if (rc == ISINGMC_OK) p.last_t = s->t;
+        return ISINGMC_OK;
+    };
     for (size_t k0 = 0, nk = 0; k0 < timesteps && rc == ISINGMC_OK; k0 += nk) {
         nk = std::min(P.chunk, timesteps - k0);
         // cluster steps cut the call: a chunk is one cluster step, or a Metropolis stretch that ends before the next one
@@ -1477,12 +1485,9 @@ static int run_steps_impl(isingmc_states *s, size_t timesteps, const double *bet
         if (cluster || icm) nk = 1;
         else {
             if (const size_t every = s->cluster_every ? s->cluster_every : s->icm_every) nk = std::min<size_t>(nk, every - 1 - s->t % every);
-            // minimum tracking cuts the call too: a stretch ends with the timestep after which t % best_every == 0
-            if (s->best_every) nk = std::min<size_t>(nk, s->best_every - s->t % s->best_every);
-            // ... and the moment sums (S18): a stretch ends with the timestep after which (t - t0) % mom_every == 0
-            if (s->mom_every) nk = std::min<size_t>(nk, s->mom_every - (s->t - s->mom_t0) % s->mom_every);
-            // ... and a periodic overlap series (S21), by the same rule
-            if (s->osr_every) nk = std::min<size_t>(nk, s->osr_every - (s->t - s->osr_t0) % s->osr_every);
+            // minimum tracking, the moment sums (S18) and a periodic overlap series (S21) cut the call too: a
+            // stretch ends with their next sample point
+            nk = std::min({nk, s->best_at.stretch(s->t), s->mom_at.stretch(s->t), s->osr_at.stretch(s->t)});
             // (joined by the cluster step or the update before this stretch; the packed runner forks behind its table launches)
             if (P.lanes > 1 && s->n_lanes <= 1 && P.path != StepPath::Packed) TRY(lanes_fork(s, P.lanes));
         }
@@ -1502,34 +1507,11 @@ static int run_steps_impl(isingmc_states *s, size_t timesteps, const double *bet
         }
         if (rc == ISINGMC_OK && (cluster || icm)) rc = measure_nonlocal_step(c);
         if (rc == ISINGMC_OK && energies_per_step) rc = read_step_energies(c, k0, nk);
-        if (rc == ISINGMC_OK && s->best_every && s->t % s->best_every == 0) {
-            // a call that may be repeated after a strip launch gave up (with_strip_retry) keeps nothing such a launch left:
-            // the launch is waited for and checked first.  The repeat then finds the same records again and changes none
-            if (s->strip_guard && P.path == StepPath::LatStrip) {
-                HIP_TRY(hipStreamSynchronize(s->stream));
-                rc = strip_check(s);
-            }
-            if (rc == ISINGMC_OK) rc = best_update_enqueue(s);
-        }
-        // a sample of the moment sums, unless the attempt this call repeats has taken it already (with_strip_retry).  A sample
-        // cannot be taken back: what a strip launch left is checked first, as above
-        if (rc == ISINGMC_OK && s->mom_every && (s->t - s->mom_t0) % s->mom_every == 0 && s->t > s->mom_replay_to) {
-            if (s->strip_guard && P.path == StepPath::LatStrip) {
-                HIP_TRY(hipStreamSynchronize(s->stream));
-                rc = strip_check(s);
-            }
-            if (rc == ISINGMC_OK) rc = moments_sample_enqueue(s);
-            if (rc == ISINGMC_OK) s->mom_last_t = s->t;
-        }
-        // a row of the periodic overlap series (S21), by the rule of the moment sums: not twice, and behind a checked strip launch
-        if (rc == ISINGMC_OK && s->osr_every && (s->t - s->osr_t0) % s->osr_every == 0 && s->t > s->osr_replay_to) {
-            if (s->strip_guard && P.path == StepPath::LatStrip) {
-                HIP_TRY(hipStreamSynchronize(s->stream));
-                rc = strip_check(s);
-            }
-            if (rc == ISINGMC_OK) rc = osr_sample_enqueue(s);
-            if (rc == ISINGMC_OK) s->osr_last_t = s->t;
-        }
+        // the records of minimum tracking: the repeat of a call finds the same records again and changes none
+        TRY(sample(s->best_at, best_update_enqueue));
+        // a sample of the moment sums and a row of the periodic overlap series (S21): neither can be taken back
+        TRY(sample(s->mom_at, moments_sample_enqueue));
+        TRY(sample(s->osr_at, osr_sample_enqueue));
     }
     if (s->n_lanes > 1) { const int jrc = lanes_join(s); if (rc == ISINGMC_OK) rc = jrc; }
     if (device_ms && rc == ISINGMC_OK) {

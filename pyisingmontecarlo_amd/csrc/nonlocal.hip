@@ -325,8 +325,7 @@ static int between_prepare(isingmc_states *a, isingmc_states *b, const uint32_t 
         *d_sa = a->d_icmb_slots;
         *d_sb = a->d_icmb_slots + a->icmb_cap;
     }
-    HIP_TRY(hipEventRecord(a->icmb_ev[0], b->stream)); // b's sweeps and exchange rounds so far ...
-    HIP_TRY(hipStreamWaitEvent(a->stream, a->icmb_ev[0], 0)); // ... before a's stream touches b's configurations and permutation
+    TRY(stream_wait_for(a->stream, b->stream, a->icmb_ev[0])); // b's sweeps and exchange rounds so far, before a's stream touches b's configurations and permutation
     HIP_TRY(hipMemsetAsync(a->d_icmb_stats, 0, 3 * a->icmb_cap * sizeof(uint32_t), a->stream));
     return ISINGMC_OK;
 }
@@ -336,9 +335,9 @@ static int between_prepare(isingmc_states *a, isingmc_states *b, const uint32_t 
 static int between_sample(isingmc_states *a, isingmc_states *b)
 {
     for (isingmc_states *s : {a, b})
-        if (s->mom_every && (s->mom_flags & ISINGMC_MOMENTS_PER_RUNG) && (s->t - s->mom_t0) % s->mom_every == 0) {
+        if ((s->mom_flags & ISINGMC_MOMENTS_PER_RUNG) && s->mom_at.due(s->t)) { // (no repeat is under way here: replay_to is 0)
             TRY(moments_sample_enqueue(s));
-            s->mom_last_t = s->t;
+            s->mom_at.last_t = s->t;
         }
     return ISINGMC_OK;
 }
@@ -346,8 +345,7 @@ static int between_sample(isingmc_states *a, isingmc_states *b)
 // behind the launches: b goes on with the new configurations, and the move has been timestep t of both containers
 static int between_finish(isingmc_states *a, isingmc_states *b, size_t n_pairs)
 {
-    HIP_TRY(hipEventRecord(a->icmb_ev[1], a->stream));
-    HIP_TRY(hipStreamWaitEvent(b->stream, a->icmb_ev[1], 0));
+    TRY(stream_wait_for(b->stream, a->stream, a->icmb_ev[1]));
     a->icmb_pairs = n_pairs;
     a->icmb_have_stats = true;
     for (isingmc_states *s : {a, b}) {

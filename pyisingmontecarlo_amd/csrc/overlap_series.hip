@@ -1,7 +1,8 @@
 // libisingmc.so: host side of the overlap series (isingmc_overlap_series_*) -- a device-resident log with one row of
-// overlaps per sample.  A record enqueues the launches of isingmc_overlaps / isingmc_overlaps_by_class into accumulators the
-// series owns, and behind each batch the store kernel of overlap_series_kernels.hip, which writes the row entries; nothing comes
-// back to the host before isingmc_overlap_series_get.  Nothing here is a kernel.
+// overlaps per sample.  A record runs the two passes of the overlap core (overlaps.hip), as isingmc_overlaps and
+// isingmc_overlaps_by_class do, in a workspace the series owns, and behind each batch the store kernel of
+// overlap_series_kernels.hip, which writes the row entries; nothing comes back to the host before isingmc_overlap_series_get.
+// Nothing here is a kernel.
 #include "internal.hpp"
 
 struct isingmc_overlap_series {
@@ -61,8 +62,8 @@ extern "C" int isingmc_overlap_series_create(isingmc_states *a, isingmc_states *
         if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
     }
     if (classes) {
-        if (classes->g != g) return fail(ISINGMC_ERR_INVALID, "the class set was made for another graph handle: its tables follow that graph's layout");
-        if (a->packed ? !classes->has_pk : !classes->has_lat) return fail(ISINGMC_ERR_INVALID, "the class set holds no layout for this container's kernel family");
+        const std::string why = classes_obstacle(classes, a);
+        if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
     }
     const size_t bins = classes ? classes->n_tables * classes->n_classes : 0;
     const size_t entries = 1 + ((flags & ISINGMC_SERIES_LINK) ? 1 : 0) + bins;
@@ -103,7 +104,7 @@ extern "C" int isingmc_overlap_series_destroy(isingmc_overlap_series *S)
     (void)stream_quiesce(a->stream); // the blocks go back to the cache: no record may still be running
     if (a->osr == S) {
         a->osr = nullptr;
-        a->osr_every = 0;
+        a->osr_at.every = 0;
     }
     if (osr_by_rung(S))
         for (isingmc_states *s : {S->a, S->b}) s->osr_by_rung_live--;
@@ -119,96 +120,36 @@ static int osr_ensure(isingmc_overlap_series *S, DevBlock<T> &block, size_t *cap
     return dev_regrow(S->a->stream, block, cap, need, need);
 }
 
-// the batches of one record under a's cluster_workspace_bytes, as isingmc_overlaps and isingmc_overlaps_by_class cut them
-struct OsrPlan {
-    size_t acc_pairs = 0, acc0 = 0; // accumulator columns of the spin / link launches and the column of pair 0
-    size_t blocks = 0, batch = 0;   // packed containers with tables: pair blocks of 32 pairs and those of one batch
-    size_t cols = 1, items = 0, col0 = 0, cbatch = 0; // by class: pair columns per item, items, the column of pair 0, items per batch
-};
-
-static OsrPlan osr_plan(const isingmc_overlap_series *S, bool default_pairs)
-{
-    const isingmc_states *a = S->a;
-    const size_t n_pos = a->g->pk.n_pos, n_pairs = S->n_pairs, bins = S->bins;
-    const size_t workspace = size_t(std::max(1, a->opt.cluster_workspace_bytes));
-    OsrPlan P;
-    P.blocks = (n_pairs + 31) / 32;
-    P.acc_pairs = !a->packed ? n_pairs : default_pairs ? 16 * a->groups : 32 * P.blocks;
-    P.acc0 = a->packed && default_pairs ? a->pk_bit0 / 2 : 0; // (device slot 16 group + pair; pk_bit0 is even)
-    if (a->packed && !default_pairs) P.batch = nonlocal_batch(P.blocks, n_pos, workspace);
-    if (!bins) return P;
-    if (!a->packed) {
-        P.items = n_pairs;
-        P.cbatch = nonlocal_batch(n_pairs, 2 * bins, workspace);
-    } else {
-        P.cols = default_pairs ? 16 : 32;
-        P.items = default_pairs ? a->groups : P.blocks;
-        P.col0 = P.acc0;
-        P.cbatch = nonlocal_batch(P.items, 2 * P.cols * bins + (default_pairs ? 0 : n_pos), workspace);
-    }
-    return P;
-}
-
-// One row for the configurations as they are.  d_sa / d_sb: device slot tables, nullptr for the pairs (2 p, 2 p + 1) of one
-// container.  Enqueue only, unless the workspace has to grow.
+// One row for the configurations as they are: the measurement of the overlap core (overlaps.hip) in the workspace of the series,
+// with the store kernel behind every batch of accumulators.  d_sa / d_sb: device slot tables, nullptr for the pairs (2 p, 2 p + 1)
+// of one container.  Enqueue only, unless the workspace has to grow.
 static int osr_enqueue(isingmc_overlap_series *S, const uint32_t *d_sa, const uint32_t *d_sb)
 {
     isingmc_states *a = S->a, *b = S->b;
-    const isingmc_graph *g = a->g;
-    const bool link = osr_link(S), default_pairs = d_sa == nullptr;
-    const size_t n_pairs = S->n_pairs, bins = S->bins, n_pos = g->pk.n_pos;
-    const OsrPlan P = osr_plan(S, default_pairs);
+    const OverlapJob J{a, b, d_sa, d_sb, S->n_pairs, osr_link(S), S->classes};
+    const OverlapPlan P = overlap_plan(a, S->n_pairs, J.default_pairs(), S->bins);
     TRY(osr_ensure(S, S->d_acc, &S->acc_cap, 2 * P.acc_pairs));
-    TRY(osr_ensure(S, S->d_cacc, &S->cacc_cap, P.cbatch * P.cols * bins));
-    TRY(osr_ensure(S, S->d_words, &S->words_cap, (a->packed && !default_pairs ? std::max(P.batch, bins ? P.cbatch : 0) : 0) * n_pos));
-    for (isingmc_states *s : {a, b})
-        if (s->n_lanes > 1) TRY(lanes_join(s));
-    if (a != b) { // b's sweeps and exchange rounds so far, before a's stream reads b's configurations and permutation
-        HIP_TRY(hipEventRecord(S->ev[0], b->stream));
-        HIP_TRY(hipStreamWaitEvent(a->stream, S->ev[0], 0));
-    }
-    long long *const row = S->d_log + S->timesteps.size() * n_pairs * S->entries;
-    unsigned long long *const d_acc = S->d_acc;
-    const uint32_t *nbr_rj = a->rj ? g->rj.nbr : nullptr;
-    const uint32_t rj_slots = a->rj ? g->rj.slots : 0;
-    const PkSide A{a->d_state, d_sa, uint32_t(a->pk_bit0), uint32_t(a->R)}, B{b->d_state, d_sb, uint32_t(b->pk_bit0), uint32_t(b->R)};
+    TRY(osr_ensure(S, S->d_cacc, &S->cacc_cap, P.cbatch * P.cols * S->bins));
+    TRY(osr_ensure(S, S->d_words, &S->words_cap, (P.batch ? std::max(P.batch, P.cbatch) : 0) * a->g->pk.n_pos));
+    const OverlapWork W{S->d_acc, S->d_cacc, S->d_words};
+    TRY(overlap_lanes_join(a, b));
+    // b's sweeps and exchange rounds so far, before a's stream reads b's configurations and permutation
+    if (a != b) TRY(stream_wait_for(a->stream, b->stream, S->ev[0]));
+    long long *const row = S->d_log + S->timesteps.size() * S->n_pairs * S->entries;
+    const uint32_t entries = uint32_t(S->entries), n_spin = J.link ? 2 : 1, bins = uint32_t(S->bins);
     // spin and link overlap: entries 0 and 1 of every pair
-    HIP_TRY(hipMemsetAsync(d_acc, 0, 2 * P.acc_pairs * sizeof(unsigned long long), a->stream));
-    if (!a->packed) {
-        HIP_TRY(overlap_launch_lattice(a->stream, a->d_state, b->d_state, d_sa, d_sb, g->geom, link, n_pairs, d_acc));
-    } else if (default_pairs) {
-        HIP_TRY(overlap_launch_packed_pairs(a->stream, a->d_state, g->pk, nbr_rj, rj_slots, link, a->groups, d_acc));
-    } else {
-        for (size_t b0 = 0; b0 < P.blocks; b0 += P.batch)
-            HIP_TRY(overlap_launch_packed_tables(a->stream, A, B, g->pk, nbr_rj, rj_slots, link, uint32_t(b0), uint32_t(std::min(P.batch, P.blocks - b0)),
-                                                 uint32_t(n_pairs), S->d_words, d_acc));
-    }
-    HIP_TRY(osr_launch_store(a->stream, OsrStore{d_acc, S->d_sizes, row, 0, P.acc0, P.acc_pairs, n_pairs, 2, link ? 2u : 1u, uint32_t(S->entries), 0}));
+    auto store = [&](const unsigned long long *acc, size_t c0, size_t n) -> int {
+        HIP_TRY(osr_launch_store(a->stream, OsrStore{acc, S->d_sizes, row, c0, P.acc0, n, S->n_pairs, 2, n_spin, entries, 0}));
+        return ISINGMC_OK;
+    };
+    TRY(overlap_enqueue(J, P, W, store));
     // by class: the entries behind them, batch by batch
-    if (bins) {
-        const isingmc_site_classes *C = S->classes;
-        unsigned long long *const d_cacc = S->d_cacc;
-        const uint32_t offset = link ? 2 : 1;
-        const size_t rw = 2 * size_t(g->geom.wpp);
-        for (size_t i0 = 0; i0 < P.items; i0 += P.cbatch) {
-            const size_t n = std::min(P.cbatch, P.items - i0);
-            HIP_TRY(hipMemsetAsync(d_cacc, 0, n * P.cols * bins * sizeof(unsigned long long), a->stream));
-            if (!a->packed) {
-                HIP_TRY(overlap_class_launch_lattice(a->stream, default_pairs ? a->d_state + 2 * i0 * rw : a->d_state.get(), b->d_state,
-                                                     d_sa ? d_sa + i0 : nullptr, d_sb ? d_sb + i0 : nullptr, g->geom, C->lat, uint32_t(n), d_cacc));
-            } else {
-                if (!default_pairs) HIP_TRY(overlap_launch_packed_gather(a->stream, A, B, g->pk, uint32_t(i0), uint32_t(n), uint32_t(n_pairs), S->d_words));
-                HIP_TRY(overlap_class_launch_packed(a->stream, default_pairs ? a->d_state + i0 * n_pos : S->d_words.get(), uint32_t(n_pos), default_pairs,
-                                                    C->pk, uint32_t(n), d_cacc));
-            }
-            HIP_TRY(osr_launch_store(a->stream, OsrStore{d_cacc, S->d_sizes + 2, row, i0 * P.cols, P.col0, n * P.cols, n_pairs, uint32_t(bins), uint32_t(bins),
-                                                         uint32_t(S->entries), offset}));
-        }
-    }
-    if (a != b) { // b's next sweeps must not run under a's reads
-        HIP_TRY(hipEventRecord(S->ev[1], a->stream));
-        HIP_TRY(hipStreamWaitEvent(b->stream, S->ev[1], 0));
-    }
+    auto store_classes = [&](const unsigned long long *acc, size_t c0, size_t n) -> int {
+        HIP_TRY(osr_launch_store(a->stream, OsrStore{acc, S->d_sizes + 2, row, c0, P.col0, n, S->n_pairs, bins, bins, entries, n_spin}));
+        return ISINGMC_OK;
+    };
+    if (bins) TRY(overlap_class_enqueue(J, P, W, store_classes));
+    if (a != b) TRY(stream_wait_for(b->stream, a->stream, S->ev[1])); // b's next sweeps must not run under a's reads
     S->timesteps.push_back(a->t);
     return ISINGMC_OK;
 }
@@ -258,7 +199,7 @@ extern "C" int isingmc_overlap_series_set_every(isingmc_overlap_series *S, size_
     if (every == 0) { // off: the rows stay
         if (a->osr == S) {
             a->osr = nullptr;
-            a->osr_every = 0;
+            a->osr_at.every = 0;
         }
         return ISINGMC_OK;
     }
@@ -269,22 +210,22 @@ extern "C" int isingmc_overlap_series_set_every(isingmc_overlap_series *S, size_
     OverlapPairing P;
     TRY(overlap_pairing(a, a, nullptr, nullptr, S->n_pairs, P)); // a periodic record takes no tables: the pairs (2 p, 2 p + 1)
     a->osr = S;
-    a->osr_every = every;
-    a->osr_t0 = a->t;
-    a->osr_last_t = 0;
+    a->osr_at.every = every;
+    a->osr_at.restart(a->t);
     return ISINGMC_OK;
 }
 
-std::string osr_run_obstacle(const isingmc_states *s, size_t timesteps)
+int osr_room_or_fail(const isingmc_states *s, size_t timesteps)
 {
-    if (!s->osr_every || !s->osr) return "";
-    const uint64_t done = s->t - s->osr_t0; // sample points: t0 + every, t0 + 2 every, ...
-    const uint64_t samples = (done + timesteps) / s->osr_every - done / s->osr_every;
+    if (!s->osr_at.every || !s->osr) return ISINGMC_OK;
+    const uint64_t samples = s->osr_at.points(s->t, timesteps); // sample points: t0 + every, t0 + 2 every, ...
     const size_t have = s->osr->timesteps.size();
-    if (samples <= s->osr->capacity - have) return "";
-    return "the overlap series of this container would run full: the call takes " + std::to_string(samples) + " samples and the log has room for " +
-           std::to_string(s->osr->capacity - have) + " of its " + std::to_string(s->osr->capacity) +
-           " rows (isingmc_overlap_series_get, then isingmc_overlap_series_reset; or switch the period off)";
+    if (samples <= s->osr->capacity - have) return ISINGMC_OK;
+    // a periodic series that would run full: nothing is enqueued
+    return fail(ISINGMC_ERR_INVALID, "the overlap series of this container would run full: the call takes " + std::to_string(samples) +
+                                         " samples and the log has room for " + std::to_string(s->osr->capacity - have) + " of its " +
+                                         std::to_string(s->osr->capacity) +
+                                         " rows (isingmc_overlap_series_get, then isingmc_overlap_series_reset; or switch the period off)");
 }
 
 int osr_sample_enqueue(isingmc_states *s)
@@ -334,6 +275,6 @@ extern "C" int isingmc_overlap_series_reset(isingmc_overlap_series *S)
     if (!S) return fail(ISINGMC_ERR_INVALID, "NULL series");
     // rows enqueued so far still land in the log, ahead on a's stream of whatever overwrites them: nothing to wait for
     S->timesteps.clear();
-    if (S->a->osr == S) S->a->osr_last_t = 0;
+    if (S->a->osr == S) S->a->osr_at.last_t = 0;
     return ISINGMC_OK;
 }

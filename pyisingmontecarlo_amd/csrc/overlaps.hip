@@ -1,5 +1,6 @@
 // libisingmc.so: host side of the overlap measurement (isingmc_overlaps) -- which containers and pairings it
-// serves, the accumulators and slot tables of one call, the batches of the arbitrary-pair form on replica-packed containers.
+// serves, and the overlap core: the one plan of a measurement's batches and the two launch sequences that the synchronising
+// calls here and the records of overlap_series.hip share.
 // Nothing here is a kernel: they are in overlap_kernels.hip, whose header states what is counted.
 #include "internal.hpp"
 
@@ -48,13 +49,121 @@ int overlap_pairing(isingmc_states *a, isingmc_states *b, const uint32_t *slots_
     return ISINGMC_OK;
 }
 
-// a's stream after b's sweeps and exchange rounds so far, before it reads b's configurations
+int overlap_lanes_join(isingmc_states *a, isingmc_states *b)
+{
+    for (isingmc_states *s : {a, b})
+        if (s->n_lanes > 1) TRY(lanes_join(s));
+    return ISINGMC_OK;
+}
+
+std::string classes_obstacle(const isingmc_site_classes *classes, const isingmc_states *a)
+{
+    if (classes->g != a->g) return "the class set was made for another graph handle: its tables follow that graph's layout";
+    if (a->packed ? !classes->has_pk : !classes->has_lat) return "the class set holds no layout for this container's kernel family";
+    return "";
+}
+
+// ---- the overlap core (internal.hpp): one plan and one launch sequence per pass -------------------------------------------------
+
+OverlapPlan overlap_plan(const isingmc_states *a, size_t n_pairs, bool default_pairs, size_t bins)
+{
+    const size_t n_pos = a->g->pk.n_pos, workspace = size_t(std::max(1, a->opt.cluster_workspace_bytes));
+    OverlapPlan P;
+    // accumulators {D, B} per pair; the packed kernels write whole groups (16 pairs) or pair blocks (32 pairs)
+    P.blocks = (n_pairs + 31) / 32;
+    P.acc_pairs = !a->packed ? n_pairs : default_pairs ? 16 * a->groups : 32 * P.blocks;
+    P.acc0 = a->packed && default_pairs ? a->pk_bit0 / 2 : 0; // (device slot 16 group + pair; pk_bit0 is even)
+    if (a->packed && !default_pairs) P.batch = nonlocal_batch(P.blocks, n_pos, workspace);
+    if (!bins) return P;
+    if (!a->packed) { // batches of pairs, two words per accumulator
+        P.items = n_pairs;
+        P.cbatch = nonlocal_batch(n_pairs, 2 * bins, workspace);
+    } else { // replica groups (16 pair columns, no workspace) or pair blocks of 32 pairs with their gathered overlap words
+        P.cols = default_pairs ? 16 : 32;
+        P.items = default_pairs ? a->groups : P.blocks;
+        P.col0 = P.acc0;
+        P.cbatch = nonlocal_batch(P.items, 2 * P.cols * bins + (default_pairs ? 0 : n_pos), workspace);
+    }
+    return P;
+}
+
+// what the packed kernels read of a job: its two containers as PkSide, and the neighbour table of the real-coupling family
+struct OverlapSides {
+    PkSide A, B;
+    const uint32_t *nbr_rj;
+    uint32_t rj_slots;
+};
+static OverlapSides overlap_sides(const OverlapJob &J)
+{
+    const isingmc_states *a = J.a, *b = J.b;
+    return {{a->d_state, J.d_sa, uint32_t(a->pk_bit0), uint32_t(a->R)},
+            {b->d_state, J.d_sb, uint32_t(b->pk_bit0), uint32_t(b->R)},
+            a->rj ? a->g->rj.nbr : nullptr,
+            a->rj ? a->g->rj.slots : 0};
+}
+
+int overlap_enqueue(const OverlapJob &J, const OverlapPlan &P, const OverlapWork &W, OverlapSink sink)
+{
+    const isingmc_states *a = J.a, *b = J.b;
+    const isingmc_graph *g = a->g;
+    const OverlapSides S = overlap_sides(J);
+    HIP_TRY(hipMemsetAsync(W.acc, 0, 2 * P.acc_pairs * sizeof(unsigned long long), a->stream));
+    if (!a->packed) {
+        HIP_TRY(overlap_launch_lattice(a->stream, a->d_state, b->d_state, J.d_sa, J.d_sb, g->geom, J.link, J.n_pairs, W.acc));
+    } else if (J.default_pairs()) {
+        HIP_TRY(overlap_launch_packed_pairs(a->stream, a->d_state, g->pk, S.nbr_rj, S.rj_slots, J.link, a->groups, W.acc));
+    } else { // pair blocks of 32 pairs, their overlap words batched under a's cluster_workspace_bytes
+        for (size_t b0 = 0; b0 < P.blocks; b0 += P.batch)
+            HIP_TRY(overlap_launch_packed_tables(a->stream, S.A, S.B, g->pk, S.nbr_rj, S.rj_slots, J.link, uint32_t(b0),
+                                                 uint32_t(std::min(P.batch, P.blocks - b0)), uint32_t(J.n_pairs), W.words, W.acc));
+    }
+    return sink(W.acc, 0, P.acc_pairs);
+}
+
+int overlap_class_enqueue(const OverlapJob &J, const OverlapPlan &P, const OverlapWork &W, OverlapSink sink)
+{
+    const isingmc_states *a = J.a, *b = J.b;
+    const isingmc_graph *g = a->g;
+    const isingmc_site_classes *C = J.classes;
+    const bool default_pairs = J.default_pairs();
+    const size_t bins = J.bins(), n_pos = g->pk.n_pos, rw = 2 * size_t(g->geom.wpp);
+    const OverlapSides S = overlap_sides(J);
+    for (size_t i0 = 0; i0 < P.items; i0 += P.cbatch) {
+        const size_t n = std::min(P.cbatch, P.items - i0);
+        HIP_TRY(hipMemsetAsync(W.cacc, 0, n * P.cols * bins * sizeof(unsigned long long), a->stream));
+        if (!a->packed) {
+            HIP_TRY(overlap_class_launch_lattice(a->stream, default_pairs ? a->d_state + 2 * i0 * rw : a->d_state.get(), b->d_state,
+                                                 J.d_sa ? J.d_sa + i0 : nullptr, J.d_sb ? J.d_sb + i0 : nullptr, g->geom, C->lat, uint32_t(n), W.cacc));
+        } else {
+            if (!default_pairs) HIP_TRY(overlap_launch_packed_gather(a->stream, S.A, S.B, g->pk, uint32_t(i0), uint32_t(n), uint32_t(J.n_pairs), W.words));
+            HIP_TRY(overlap_class_launch_packed(a->stream, default_pairs ? a->d_state + i0 * n_pos : W.words, uint32_t(n_pos), default_pairs, C->pk,
+                                                uint32_t(n), W.cacc));
+        }
+        TRY(sink(W.cacc, i0 * P.cols, n * P.cols));
+    }
+    return ISINGMC_OK;
+}
+
+// ---- the synchronising calls: workspace from the call's DeviceScratch, accumulators read back ------------------------------------
+
+// a's stream after b's sweeps and exchange rounds so far, before it reads b's configurations (the event is the between move's)
 static int overlap_order_after(isingmc_states *a, isingmc_states *b)
 {
     if (a == b) return ISINGMC_OK;
     if (!a->icmb_ev[0]) HIP_TRY(pooled_event_create(&a->icmb_ev[0], true));
-    HIP_TRY(hipEventRecord(a->icmb_ev[0], b->stream));
-    HIP_TRY(hipStreamWaitEvent(a->stream, a->icmb_ev[0], 0));
+    return stream_wait_for(a->stream, b->stream, a->icmb_ev[0]);
+}
+
+// the host tables of the pairing as the job's device tables (they live as long as the call, which waits for the device before it returns)
+static int overlap_upload(DeviceScratch &scratch, const OverlapPairing &P, OverlapJob &J)
+{
+    if (P.default_pairs) return ISINGMC_OK;
+    uint32_t *d = nullptr;
+    TRY(scratch.alloc(&d, 2 * J.n_pairs));
+    HIP_TRY(hipMemcpyAsync(d, P.slots_a, J.n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, J.a->stream));
+    HIP_TRY(hipMemcpyAsync(d + J.n_pairs, P.slots_b, J.n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, J.a->stream));
+    J.d_sa = d;
+    J.d_sb = d + J.n_pairs;
     return ISINGMC_OK;
 }
 
@@ -66,50 +175,23 @@ extern "C" int isingmc_overlaps(isingmc_states *a, isingmc_states *b, const uint
     OverlapPairing P;
     TRY(overlap_pairing(a, b, slots_a, slots_b, n_pairs, P));
     b = P.b;
-    slots_a = P.slots_a;
-    slots_b = P.slots_b;
-    const bool default_pairs = P.default_pairs;
     const isingmc_graph *g = a->g;
-    const bool link = link_out != nullptr;
     TRY(use_device(g->device));
-    for (isingmc_states *s : {a, b})
-        if (s->n_lanes > 1) TRY(lanes_join(s));
-    // accumulators {D, B} per pair; the packed kernels write whole groups (16 pairs) or pair blocks (32 pairs)
-    const size_t n_pos = g->pk.n_pos, blocks = (n_pairs + 31) / 32;
-    const size_t acc_pairs = !a->packed ? n_pairs : default_pairs ? 16 * a->groups : 32 * blocks;
-    const size_t acc0 = a->packed && default_pairs ? a->pk_bit0 / 2 : 0; // (device slot 16 group + pair; pk_bit0 is even)
+    TRY(overlap_lanes_join(a, b));
+    const OverlapPlan L = overlap_plan(a, n_pairs, P.default_pairs, 0);
+    OverlapJob J{a, b, nullptr, nullptr, n_pairs, link_out != nullptr, nullptr};
+    OverlapWork W{nullptr, nullptr, nullptr};
     DeviceScratch scratch(a->stream);
-    unsigned long long *d_acc = nullptr;
-    TRY(scratch.alloc(&d_acc, 2 * acc_pairs));
-    HIP_TRY(hipMemsetAsync(d_acc, 0, 2 * acc_pairs * sizeof(unsigned long long), a->stream));
-    uint32_t *d_sa = nullptr, *d_sb = nullptr;
-    if (!default_pairs) { // (the host tables live as long as the call, which waits for the device before it returns)
-        TRY(scratch.alloc(&d_sa, 2 * n_pairs));
-        d_sb = d_sa + n_pairs;
-        HIP_TRY(hipMemcpyAsync(d_sa, slots_a, n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, a->stream));
-        HIP_TRY(hipMemcpyAsync(d_sb, slots_b, n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, a->stream));
-    }
+    TRY(scratch.alloc(&W.acc, 2 * L.acc_pairs));
+    TRY(overlap_upload(scratch, P, J));
+    if (L.batch) TRY(scratch.alloc(&W.words, L.batch * g->pk.n_pos));
     TRY(overlap_order_after(a, b));
-    const uint32_t *nbr_rj = a->rj ? g->rj.nbr : nullptr;
-    const uint32_t rj_slots = a->rj ? g->rj.slots : 0;
-    if (!a->packed) {
-        HIP_TRY(overlap_launch_lattice(a->stream, a->d_state, b->d_state, d_sa, d_sb, g->geom, link, n_pairs, d_acc));
-    } else if (default_pairs) {
-        HIP_TRY(overlap_launch_packed_pairs(a->stream, a->d_state, g->pk, nbr_rj, rj_slots, link, a->groups, d_acc));
-    } else { // pair blocks of 32 pairs, their overlap words batched under a's cluster_workspace_bytes
-        const size_t batch = nonlocal_batch(blocks, n_pos, size_t(std::max(1, a->opt.cluster_workspace_bytes)));
-        uint32_t *d_words = nullptr;
-        TRY(scratch.alloc(&d_words, batch * n_pos));
-        const PkSide A{a->d_state, d_sa, uint32_t(a->pk_bit0), uint32_t(a->R)}, B{b->d_state, d_sb, uint32_t(b->pk_bit0), uint32_t(b->R)};
-        for (size_t b0 = 0; b0 < blocks; b0 += batch)
-            HIP_TRY(overlap_launch_packed_tables(a->stream, A, B, g->pk, nbr_rj, rj_slots, link, uint32_t(b0), uint32_t(std::min(batch, blocks - b0)),
-                                                 uint32_t(n_pairs), d_words, d_acc));
-    }
     std::vector<unsigned long long> h;
-    TRY(read_back(a, h, d_acc, 2 * acc_pairs)); // waits: b may go on as soon as the call returns
+    auto sink = [&](const unsigned long long *acc, size_t, size_t n) { return read_back(a, h, acc, 2 * n); }; // waits: b may go on as soon as the call returns
+    TRY(overlap_enqueue(J, L, W, sink));
     for (size_t p = 0; p < n_pairs; p++) {
-        spin_out[p] = int64_t(g->nvars) - 2 * int64_t(h[2 * (acc0 + p)]);
-        if (link) link_out[p] = int64_t(g->n_edges) - 2 * int64_t(h[2 * (acc0 + p) + 1]);
+        spin_out[p] = int64_t(g->nvars) - 2 * int64_t(h[2 * (L.acc0 + p)]);
+        if (J.link) link_out[p] = int64_t(g->n_edges) - 2 * int64_t(h[2 * (L.acc0 + p) + 1]);
     }
     return ISINGMC_OK;
 }
@@ -248,60 +330,36 @@ extern "C" int isingmc_overlaps_by_class(isingmc_states *a, isingmc_states *b, c
     OverlapPairing P;
     TRY(overlap_pairing(a, b, slots_a, slots_b, n_pairs, P));
     b = P.b;
-    const isingmc_graph *g = a->g;
-    if (classes->g != g) return fail(ISINGMC_ERR_INVALID, "the class set was made for another graph handle: its tables follow that graph's layout");
-    if (a->packed ? !classes->has_pk : !classes->has_lat) return fail(ISINGMC_ERR_INVALID, "the class set holds no layout for this container's kernel family");
-    TRY(use_device(g->device));
-    for (isingmc_states *s : {a, b})
-        if (s->n_lanes > 1) TRY(lanes_join(s));
-    const size_t bins = classes->n_tables * classes->n_classes, workspace = size_t(std::max(1, a->opt.cluster_workspace_bytes));
-    DeviceScratch scratch(a->stream);
-    uint32_t *d_sa = nullptr, *d_sb = nullptr;
-    if (!P.default_pairs) { // (the host tables live as long as the call, which waits for the device before it returns)
-        TRY(scratch.alloc(&d_sa, 2 * n_pairs));
-        d_sb = d_sa + n_pairs;
-        HIP_TRY(hipMemcpyAsync(d_sa, P.slots_a, n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, a->stream));
-        HIP_TRY(hipMemcpyAsync(d_sb, P.slots_b, n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, a->stream));
+    {
+        const std::string why = classes_obstacle(classes, a);
+        if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
     }
+    TRY(use_device(a->g->device));
+    TRY(overlap_lanes_join(a, b));
+    const size_t bins = classes->n_tables * classes->n_classes;
+    const OverlapPlan L = overlap_plan(a, n_pairs, P.default_pairs, bins);
+    OverlapJob J{a, b, nullptr, nullptr, n_pairs, false, classes};
+    OverlapWork W{nullptr, nullptr, nullptr};
+    DeviceScratch scratch(a->stream);
+    TRY(overlap_upload(scratch, P, J));
     TRY(overlap_order_after(a, b));
-    unsigned long long *d_acc = nullptr;
+    TRY(scratch.alloc(&W.cacc, L.cbatch * L.cols * bins));
+    if (L.batch) TRY(scratch.alloc(&W.words, L.cbatch * a->g->pk.n_pos));
     std::vector<unsigned long long> h;
-    // the accumulators of pair p as the p-th [n_tables][n_classes] block of the result
-    const auto store = [&](size_t p, const unsigned long long *D) {
-        for (size_t i = 0; i < bins; i++) out[p * bins + i] = int64_t(classes->sizes[i]) - 2 * int64_t(D[i]);
-    };
-    if (!a->packed) { // batches of pairs, two words per accumulator
-        const size_t batch = nonlocal_batch(n_pairs, 2 * bins, workspace), rw = 2 * size_t(g->geom.wpp);
-        TRY(scratch.alloc(&d_acc, batch * bins));
-        for (size_t p0 = 0; p0 < n_pairs; p0 += batch) {
-            const size_t n = std::min(batch, n_pairs - p0);
-            HIP_TRY(hipMemsetAsync(d_acc, 0, n * bins * sizeof(unsigned long long), a->stream));
-            HIP_TRY(overlap_class_launch_lattice(a->stream, P.default_pairs ? a->d_state + 2 * p0 * rw : a->d_state, b->d_state, d_sa ? d_sa + p0 : nullptr,
-                                                 d_sb ? d_sb + p0 : nullptr, g->geom, classes->lat, uint32_t(n), d_acc));
-            TRY(read_back(a, h, d_acc, n * bins));
-            for (size_t p = 0; p < n; p++) store(p0 + p, h.data() + p * bins);
+    // the accumulators of pair p as the p-th [n_tables][n_classes] block of the result; columns that hold no pair of the call are passed over
+    auto sink = [&](const unsigned long long *acc, size_t c0, size_t n) -> int {
+        TRY(read_back(a, h, acc, n * bins));
+        // (locals: through the captures every term of the inner loop would be loaded again behind each store)
+        const size_t nb = bins, col0 = L.col0;
+        const uint64_t *const sizes = classes->sizes.data();
+        for (size_t c = 0; c < n; c++) {
+            const size_t column = c0 + c, p = column - col0;
+            if (column < col0 || p >= n_pairs) continue;
+            const unsigned long long *const D = h.data() + c * nb;
+            int64_t *const o = out + p * nb;
+            for (size_t i = 0; i < nb; i++) o[i] = int64_t(sizes[i]) - 2 * int64_t(D[i]);
         }
         return ISINGMC_OK;
-    }
-    // replica groups (16 pair columns, no workspace) or pair blocks of 32 pairs with their gathered overlap words
-    const size_t n_pos = g->pk.n_pos, cols = P.default_pairs ? 16 : 32, items = P.default_pairs ? a->groups : (n_pairs + 31) / 32;
-    const size_t col0 = P.default_pairs ? a->pk_bit0 / 2 : 0; // (column 16 group + pair of the first pair; pk_bit0 is even)
-    const size_t batch = nonlocal_batch(items, 2 * cols * bins + (P.default_pairs ? 0 : n_pos), workspace);
-    uint32_t *d_words = nullptr;
-    TRY(scratch.alloc(&d_acc, batch * cols * bins));
-    if (!P.default_pairs) TRY(scratch.alloc(&d_words, batch * n_pos));
-    const PkSide A{a->d_state, d_sa, uint32_t(a->pk_bit0), uint32_t(a->R)}, B{b->d_state, d_sb, uint32_t(b->pk_bit0), uint32_t(b->R)};
-    for (size_t i0 = 0; i0 < items; i0 += batch) {
-        const size_t n = std::min(batch, items - i0);
-        HIP_TRY(hipMemsetAsync(d_acc, 0, n * cols * bins * sizeof(unsigned long long), a->stream));
-        if (!P.default_pairs) HIP_TRY(overlap_launch_packed_gather(a->stream, A, B, g->pk, uint32_t(i0), uint32_t(n), uint32_t(n_pairs), d_words));
-        HIP_TRY(overlap_class_launch_packed(a->stream, P.default_pairs ? a->d_state + i0 * n_pos : d_words, uint32_t(n_pos), P.default_pairs,
-                                            classes->pk, uint32_t(n), d_acc));
-        TRY(read_back(a, h, d_acc, n * cols * bins));
-        for (size_t c = 0; c < n * cols; c++) {
-            const size_t column = i0 * cols + c;
-            if (column >= col0 && column - col0 < n_pairs) store(column - col0, h.data() + c * bins);
-        }
-    }
-    return ISINGMC_OK;
+    };
+    return overlap_class_enqueue(J, L, W, sink);
 }

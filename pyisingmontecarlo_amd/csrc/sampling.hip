@@ -110,10 +110,7 @@ extern "C" int isingmc_run_sampling(isingmc_states *s, double beta, size_t therm
                                     size_t n_samples, double *energies_out, uint8_t *states_out)
 {
     if (!s) return fail(ISINGMC_ERR_INVALID, "NULL states");
-    if (s->osr_every) { // a periodic overlap series that would run full: nothing is enqueued
-        const std::string why = osr_run_obstacle(s, thermalization + sampling_freq * n_samples);
-        if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
-    }
+    TRY(osr_room_or_fail(s, thermalization + sampling_freq * n_samples));
     const bool may_strip = may_use_strips(s) && (strip_plan(s, thermalization).use || strip_plan(s, sampling_freq).use);
     return with_strip_retry(s, may_strip, [&] {
         return run_sampling_impl(s, beta, thermalization, sampling_freq, n_samples, energies_out, states_out);

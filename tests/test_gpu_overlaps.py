@@ -219,6 +219,33 @@ def test_real_coupling_degree_15_zero_couplings_and_a_duplicate(capi):
     _check_tables(shard, ea, eb, len(ea), rng, other=st)
 
 
+# ---- the arbitrary-pair form of both packed families in batches ---------------------------------------------------------------
+@pytest.mark.parametrize("family", ["packed_bitsliced", "packed_real"])
+def test_packed_tables_in_batches(capi, exact, force_packed, family):
+    """70 pairs = three pair blocks, the last partly filled, inside one container and between two (40 and 37 replicas) of the 6^3
+    cube: cluster_workspace_bytes = 1 cuts one block per batch, 1 << 30 takes all three in one.  Both against the numpy rule --
+    the one anchor of the batches that shares no plan with the library (the series and the class form compare with this call)."""
+    if family == "packed_bitsliced":
+        ea, eb, ej = IR.cubic_glass(exact, 6)
+        g = capi.Graph(ea, eb, ej, nvars=216, force_general=True)
+    else:   # Gaussian couplings: the neighbour table of the real-coupling family
+        ea, eb, _ = exact.cubic_lattice_edges(6, 1.0)
+        g = capi.Graph(ea, eb, np.random.default_rng(2024).normal(size=len(ea)), nvars=216, stable_path=True)
+    a, b = capi.States(g, capi.make_seeds(220, 40)), capi.States(g, capi.make_seeds(221, 37))
+    assert a.family == family
+    a.do_time_steps(3, 0.5)
+    b.do_time_steps(2, 0.5)
+    rng = np.random.default_rng(70)
+    for other in (None, b):
+        sa, sb = _tables(rng, 70, 40, 40 if other is None else 37)
+        assert sa[2] == sa[1]   # a slot used twice
+        got = []
+        for workspace in (1, 1 << 30):
+            a.set_option("cluster_workspace_bytes", workspace)
+            got.append(_check(a, ea, eb, other, sa, sb))
+        assert np.array_equal(got[0][0], got[1][0]) and np.array_equal(got[0][1], got[1][1])
+
+
 # ---- 6. cross-checks against code that exists ------------------------------------------------------------------------------
 def _three_paths(capi, exact, monkeypatch):
     """(graph, ea, eb) on the checkerboard path, then -- under ISINGMC_FORCE_PACKED=1 -- on the bit-sliced and the real-coupling
