@@ -10,6 +10,8 @@ step exchanges TEMPERATURES, never configurations: every rank all-gathers one fl
 (RCCL over xGMI with backend nccl), evaluates the same Philox-keyed decisions in libisingmc's host code
 (isingmc_host_pt_swap_round) and re-labels its own slots' betas.  No spin ever crosses a link.
 """
+import os
+
 import numpy as np
 
 from . import _capi
@@ -80,6 +82,266 @@ def betas_from_flow(betas, n_up, n_down, n_rungs=None):
 TRACK_AT_ROUNDS = 1 << 62      # set_track_best period of a ladder: no timestep reaches it, the exchange rounds update the records
 COPY_SEED_XOR = 0x9E3779B97F4A7C15  # copy 1 of a copies=2 ladder is the ladder of seed ^ this
 
+SWEEPS, MOVE, FUSED = 0, 1, 2               # a stretch of schedule(): Metropolis sweeps, one cluster move, sweeps with their rounds inside
+NO_FUSE, FUSE_ROUNDS, FUSE_CALL = 0, 1, 2   # what a ladder takes as one FUSED library call: nothing, whole rounds, the call's partial last block too
+
+
+def schedule(t, T, f=0, k=0, every=0, origin=0, sample=0, fuse=NO_FUSE):
+    """Where a call of T timesteps that starts at absolute timestep t is cut: the countdown of tempering.rs:172-212 and the order
+    rule of DESIGN.md S21, for every loop of this file.  Pure: integers in, integers out.  f: an exchange round after every f-th
+    timestep of the CALL (<= 0: none; a partial last block gets none); k: absolute timestep u is a cluster move iff u % k == k - 1
+    (0: none); every, origin: an overlap sample follows timestep u iff (u + 1 - origin) % every == 0 (0: none); sample: a state
+    sample follows every sample-th timestep of the call (0: none).  Yields (n, kind, overlap_due, round_due, sample_due) per
+    stretch: n timesteps of one kind -- SWEEPS, MOVE (n == 1) or, where `fuse` allows, FUSED: sweeps with their rounds inside one
+    library call, starting on a round boundary and ending before the next sample or move -- and what follows the stretch's last
+    timestep, in this order: the overlap sample, the exchange round, the state sample."""
+    f, done = max(int(f), 0), 0
+    if fuse == FUSE_CALL and f and T > 0 and not (k or every or sample):   # nothing cuts the call: the closed form, no loop to set up
+        yield T, FUSED, False, False, False
+        return
+    while done < T:
+        kind, n = SWEEPS, T - done
+        if k and t % k == k - 1:
+            kind, n = MOVE, 1
+        else:
+            if k:
+                n = min(n, k - 1 - t % k)   # Metropolis timesteps before the next cluster move
+            u = every - (t - origin) % every if every else None   # timesteps up to and including the one the next sample follows
+            if sample and (u is None or sample - done % sample < u):
+                u = sample - done % sample
+            fused = 0
+            if f and fuse and done % f == 0:
+                fused = (n if u is None else min(n, u - 1)) // f * f   # the sample goes between its timestep and that timestep's round
+                if fuse == FUSE_CALL and u is None and n == T - done:
+                    fused = n
+            if fused:
+                kind, n = FUSED, fused
+            else:
+                n = min(n, f - done % f) if f else n
+                n = n if u is None else min(n, u)
+        t, done = t + n, done + n
+        yield (n, kind, bool(every) and (t - origin) % every == 0, kind != FUSED and f > 0 and done % f == 0,
+               bool(sample) and done % sample == 0)
+
+
+def _frequencies(replica_swap_freq, sampling_freq):
+    """(exchange period, sampling period) of timesteps_sample: both default to 1 (tempering.rs:163-164), <= 0 exchanges never."""
+    sampling_freq = 1 if sampling_freq is None else int(sampling_freq)
+    if sampling_freq <= 0:
+        raise ValueError("sampling_freq must be positive")
+    return max(1 if replica_swap_freq is None else int(replica_swap_freq), 0), sampling_freq
+
+
+def _inverse(perm):
+    """slot -> rung from rung -> slot."""
+    inv = np.empty(len(perm), dtype=np.int64)
+    inv[perm] = np.arange(len(perm))
+    return inv
+
+
+def _by_rung(states, rungs):
+    """bool[C, G, S, N] by slot and the rung every slot held at every sample, int64[C, G, S] -> the states by rung."""
+    out = np.empty_like(states)
+    for c in range(states.shape[0]):
+        for s in range(states.shape[2]):
+            out[c, rungs[c, :, s], s, :] = states[c, :, s, :]
+    return out
+
+
+class _HostLadder:
+    """What the loops of ClassicalTempering need of a ladder -- sweep, plain, exchange, slot_sums, read_states, perm, total_swaps,
+    synchronize, the three statistics calls; `fuse` and, where it is not NO_FUSE, run -- chosen once when the ladder is built.
+    This one is the host swap step, on any number of ranks: one float64 per slot gathered over the ranks, the decisions in the
+    library's host code, the betas pushed back into the container.  Permutation, round and swap counts live on the owner."""
+    fuse, backend = NO_FUSE, None
+
+    def __init__(self, owner):
+        self.o, self.st, self.local = owner, owner._states, owner._hi > owner._lo
+        self.stats = None   # the arrays of _capi.pt_statistics_zeros
+        self.push_betas()
+
+    def push_betas(self):
+        o = self.o
+        beta_of_slot = np.empty(len(o._betas), dtype=np.float64)
+        beta_of_slot[o._perm] = o._betas
+        if self.local:
+            self.st.set_betas(beta_of_slot[o._lo:o._hi])
+
+    def sweep(self, n):
+        if self.local:
+            self.st.do_time_steps(n)
+
+    plain = sweep   # timesteps(t) without a period; on the device's stream too it stays do_time_steps and does not wait
+
+    def gather(self, local):
+        """float64[G] in slot order on every rank, from every rank's block: the swap step's all-gather."""
+        o, G = self.o, len(self.o._betas)
+        gathered = D.all_gather_f64(local, o._per, o._group)
+        out = np.empty(G, dtype=np.float64)
+        for r in range(o._world):
+            lo, hi = D.shard_bounds(G, o._world, r)
+            out[lo:hi] = gathered[r * o._per:r * o._per + (hi - lo)]
+        return out
+
+    def slot_sums(self, n):
+        """n timesteps; every slot's energy summed over them, float64[G] on every rank."""
+        return self.gather(self.st.do_time_steps(n, per_step_energies=True).sum(axis=1) if self.local else np.zeros(0))
+
+    def exchange(self):
+        o = self.o
+        local = self.st.energies() if self.local else np.zeros(0)
+        if o._track_minimum and self.local:
+            self.st.best_update()
+        slot_e = self.gather(local)
+        before = o._perm.copy() if o._stats_on else None
+        o._total_swaps += _capi.pt_swap_round(o._seed, o._round, o._betas, slot_e, o._perm)
+        if o._stats_on:   # the host twin of what the exchange kernels keep (DESIGN.md S20); every rank computes the same
+            _capi.pt_statistics_round(self.stats, o._round, before, o._perm, slot_e)
+        o._round += 1
+        self.push_betas()
+
+    def read_states(self, out):
+        if self.local:
+            self.st.states(out=out)
+
+    def perm(self):
+        return self.o._perm
+
+    def total_swaps(self):
+        return self.o._total_swaps
+
+    def synchronize(self):
+        pass
+
+    def set_statistics(self, on):
+        if self.stats is None:
+            self.stats = _capi.pt_statistics_zeros(len(self.o._betas))
+
+    def raw_statistics(self):
+        return {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in self.stats.items()}
+
+    def reset_statistics(self):
+        self.stats = _capi.pt_statistics_zeros(len(self.o._betas))
+
+
+class _StreamLadder(_HostLadder):
+    """The ladder on the engine's HIP stream, alone or as a rank of a torch group (every rank then holds slots): sweeps,
+    measurement, exchange decisions and beta relabelling are enqueued, the device owns permutation and counts.  plain, gather,
+    slot_sums and read_states are the host ladder's."""
+
+    def __init__(self, owner):
+        self.o, self.st, self.local, self.shards = owner, owner._states, True, [owner._states]
+        self.st.pt_attach(owner._betas, owner._lo, owner._per, owner._world, owner._seed)
+        self.local_e, self.all_e = self.st.pt_buffers()
+        self.stream = self.st.pt_stream() if owner._world > 1 else None
+        self.fuse = FUSE_CALL if owner._world == 1 else NO_FUSE   # single rank: a whole call is one library call (one persistent launch on mid-size lattices)
+
+    def sweep(self, n):
+        for st in self.shards:
+            st.pt_time_steps(n)
+
+    def run(self, n, f):
+        self.st.pt_run(n, f)
+
+    def exchange(self):
+        # measure -> [RCCL all-gather on the engine's stream] -> exchange kernel: nothing waits on the host
+        self.st.pt_measure()
+        if self.o._world > 1:
+            import torch
+            import torch.distributed as dist
+            group, world, per = self.o._group, self.o._world, self.o._per
+            if dist.get_backend(group) == "nccl":
+                with torch.cuda.stream(self.stream):
+                    dist.all_gather_into_tensor(self.all_e, self.local_e, group=group)
+            else:
+                # gloo (several ranks rehearsing on one GPU): the same exchange through the host -- wait for the
+                # measurement, gather on the CPU, put the result where the exchange kernel reads it
+                self.st.synchronize()
+                send = self.local_e.cpu()
+                recv = torch.empty(world * per, dtype=torch.float64)
+                dist.all_gather_into_tensor(recv, send, group=group)
+                self.all_e.copy_(recv)
+                torch.cuda.synchronize()
+        self.st.pt_swap()
+
+    def perm(self):
+        self.o._perm = self.st.pt_state()[0]
+        return self.o._perm
+
+    def total_swaps(self):
+        return int(self.st.pt_state()[2])
+
+    def synchronize(self):
+        self.st.synchronize()
+
+    def set_statistics(self, on):
+        for st in self.shards:
+            st.pt_set_statistics(True)   # the first switch-on allocates; switched on and off again before any round: zeros
+            if not on:
+                st.pt_set_statistics(False)
+
+    def raw_statistics(self):
+        return self.st.pt_statistics()   # (devices=[...]: shard 0's block; every shard's is the same)
+
+    def reset_statistics(self):
+        for st in self.shards:
+            st.pt_reset_statistics()
+
+
+class _GroupLadder(_StreamLadder):
+    """The in-process ladder of devices=[...]: one shard per device, the same ladder attached to each, an isingmc_pt_group
+    between them.  Shard 0 answers for the ladder's state (perm, total_swaps, raw_statistics: every shard's is the same)."""
+    fuse = FUSE_CALL
+
+    def __init__(self, owner, G):
+        n = len(owner._devices)
+        if n == 0:
+            raise ValueError("devices must name at least one GPU")
+        owner._per = D.block_size(G, n)
+        seeds = np.array(owner._slot_seeds, dtype=np.uint64)
+        self.bounds = [D.shard_bounds(G, n, k) for k in range(n)]
+        if any(hi <= lo for lo, hi in self.bounds):
+            raise ValueError("more devices than blocks of rungs: every device needs at least one slot")
+        self.shards = []
+        for k, dev in enumerate(owner._devices):
+            engine = HipEngine(owner._ea, owner._eb, owner._ej, owner.nvars, device=dev)
+            st = engine.make_states(seeds, self.bounds[k])
+            if not (engine.supports_on_stream_pt and st.pt_can_attach(G, self.bounds[k][0], owner._per, n)):
+                raise ValueError("the in-process ladder needs on-stream tempering on every shard (a periodic field-free lattice or "
+                                 "a replica-packed graph; on the bit-sliced path shards of whole 32-slot groups): " + _capi.last_error())
+            self.shards.append(st)
+        for k, st in enumerate(self.shards):
+            st.pt_attach(owner._betas, self.bounds[k][0], owner._per, n, owner._seed)
+        self.group = _capi.PtGroup(self.shards, owner._group_backend)
+        self.o, self.st = owner, self.shards[0]
+        owner._shards, owner._states, owner._lo, owner._hi, owner._on_stream = self.shards, self.shards[0], 0, G, True
+
+    backend = property(lambda self: self.group.backend)
+
+    def plain(self, n):
+        self.sweep(n)
+        self.synchronize()
+
+    def run(self, n, f):
+        self.group.run(n, f)
+
+    def exchange(self):
+        for st in self.shards:
+            st.pt_measure()
+        self.group.allgather()
+        for st in self.shards:
+            st.pt_swap()
+
+    def slot_sums(self, n):
+        return np.concatenate([st.do_time_steps(n, per_step_energies=True).sum(axis=1) for st in self.shards])
+
+    def read_states(self, out):
+        for (lo, hi), st in zip(self.bounds, self.shards):
+            st.states(out=out[lo:hi])
+
+    def synchronize(self):
+        self.group.synchronize()
+
 
 class ClassicalTempering:
     def __init__(self, edges, seed=None, *, group=None, device=None, engine_factory=None, devices=None, group_backend=0, copies=1):
@@ -101,7 +363,9 @@ class ClassicalTempering:
         self._pair = None
         self._devices = None if devices is None else [int(d) for d in devices]
         self._group_backend = int(group_backend)
-        self._shards, self._pgroup = None, None
+        self._shards = None    # devices=[...]: the containers, one per device
+        self._lads = None      # the _HostLadder / _StreamLadder / _GroupLadder behind the loops, one per copy: chosen by _materialise
+        self._t = 0            # absolute timestep of the ladder the calls are made on (a pair drives its copies: theirs stays 0)
         if self._devices is not None and (group is not None or D.world_rank(group)[0] > 1):
             raise ValueError("devices=[...] is the in-process ladder: not inside a torch.distributed job")
         self.nvars = int(max(self._ea.max(), self._eb.max())) + 1  # tempering.rs:44-49
@@ -129,7 +393,6 @@ class ClassicalTempering:
 
             self._pair = [ClassicalTempering((self._ea, self._eb, self._ej), s, device=device, engine_factory=factory)
                           for s in (self._seed, self._seed ^ COPY_SEED_XOR)]
-            self._t = 0               # absolute timestep, the same on both copies
             self._icm_stats, self._icm_pending = None, False
         self._ovl_series, self._ovl_every, self._ovl_t0, self._ovl_classes = None, 0, 0, None   # overlap series
         self._betas = []
@@ -144,10 +407,8 @@ class ClassicalTempering:
         self._total_swaps = 0
         self._on_stream = False
         self._stats_on, self._stats_seen = False, False   # ladder statistics: counting now / switched on at least once
-        self._host_stats = None                           # host swap path: the arrays of _capi.pt_statistics_zeros
 
     def _default_device(self):
-        import os
         if self._device is not None:
             return self._device
         return int(os.environ.get("ISINGMC_DEVICE", os.environ.get("LOCAL_RANK", "0")))
@@ -175,13 +436,7 @@ class ClassicalTempering:
         return len(self._betas)
 
     def get_total_swaps(self):  # tempering.rs:297-299
-        if self._pair is not None:
-            return sum(c.get_total_swaps() for c in self._pair)
-        if self._pgroup is not None:
-            return int(self._shards[0].pt_state()[2])
-        if self._on_stream:
-            return int(self._states.pt_state()[2]) if self._hi > self._lo else self._total_swaps
-        return self._total_swaps
+        return sum(lad.total_swaps() for lad in self._lads or [])
 
     def get_betas(self):
         return np.array(self._betas)
@@ -191,11 +446,7 @@ class ClassicalTempering:
         if self._pair is not None:
             return np.stack([c.get_permutation() for c in self._pair])
         self._materialise()
-        if self._pgroup is not None:
-            self._perm = self._shards[0].pt_state()[0]
-        elif self._on_stream and self._hi > self._lo:
-            self._perm = self._states.pt_state()[0]
-        return self._perm.copy()
+        return self._lads[0].perm().copy()
 
     # -------------------------------------------------------------------------------------------
     def set_replica_cluster_update_every(self, k):
@@ -232,7 +483,7 @@ class ClassicalTempering:
         only: no configuration, random number or timestep changes."""
         if self._pair is None:
             raise ValueError("overlaps need two configurations per temperature: build the ladder with copies=2")
-        self._materialise_pair()
+        self._materialise()
         a, b = self._pair
         if not hasattr(a._states, "overlaps"):
             raise ValueError("this engine has no overlap measurement between containers (overlaps)")
@@ -244,7 +495,7 @@ class ClassicalTempering:
         set of the ladder's graph, for get_overlaps_by_class: built once, used at every measurement."""
         if self._pair is None:
             raise ValueError("overlaps need two configurations per temperature: build the ladder with copies=2")
-        self._materialise_pair()
+        self._materialise()
         states = self._pair[0]._states
         if not hasattr(states, "overlaps_by_class"):
             raise ValueError("this engine has no overlap measurement by site class (overlaps_by_class)")
@@ -259,7 +510,7 @@ class ClassicalTempering:
         if own:
             classes = self.site_classes(classes, n_classes)
         try:
-            self._materialise_pair()
+            self._materialise()
             a, b = self._pair
             perm = self.get_permutation()
             return a._states.overlaps_by_class(classes, b._states, perm[0], perm[1])
@@ -285,7 +536,7 @@ class ClassicalTempering:
         if int(k) == 0:
             self._ovl_every = 0
             return
-        self._materialise_pair()
+        self._materialise()
         a, b = self._pair
         if not hasattr(a._states, "overlap_series"):
             raise ValueError("this engine has no overlap series (overlap_series)")
@@ -310,16 +561,8 @@ class ClassicalTempering:
             raise ValueError("no overlaps are logged: call set_measure_overlaps_every(k) first")
         self._ovl_series.reset()
 
-    def _until_sample(self):
-        """Timesteps up to and including the one the next sample follows (None: no sample is due)."""
-        k = self._ovl_every
-        return (k - (self._t - self._ovl_t0) % k) if k else None
-
     def _pair_sample(self):
-        """The sample behind timestep self._t - 1, if one falls there: before any exchange round on the same boundary."""
-        k = self._ovl_every
-        if not k or (self._t - self._ovl_t0) % k:
-            return
+        """The sample behind timestep self._t - 1: before any exchange round on the same boundary."""
         if self._on_stream:
             self._ovl_series.record()   # the rung permutations are read on the device
         else:
@@ -351,7 +594,7 @@ class ClassicalTempering:
         configuration had at an exchange round, that configuration, the timestep of that round, and the rung the slot holds now.
         copies=2: one leading row per copy."""
         if self._pair is not None:
-            self._materialise_pair()
+            self._materialise()
             return tuple(np.stack(x) for x in zip(*(c.get_minimum() for c in self._pair)))
         self._materialise()
         if not self._track_minimum:
@@ -423,25 +666,13 @@ class ClassicalTempering:
         self._stats_on = bool(on)
         self._stats_seen = self._stats_seen or self._stats_on
         if self._states is not None:
-            self._apply_ladder_statistics()
+            self._lads[0].set_statistics(self._stats_on)
 
-    def _apply_ladder_statistics(self):
-        """(the ladder exists and set_ladder_statistics(True) has been called at least once: the statistics exist from here on)"""
-        if self._pgroup is not None or self._on_stream:
-            for st in (self._shards if self._pgroup is not None else [self._states]):
-                st.pt_set_statistics(True)   # the first switch-on allocates; switched on and off again before any round: zeros
-                if not self._stats_on:
-                    st.pt_set_statistics(False)
-        elif self._host_stats is None:
-            self._host_stats = _capi.pt_statistics_zeros(len(self._betas))
-
-    def _raw_ladder_statistics(self):
+    def _statistics_ladder(self):
         if not self._stats_seen:
             raise ValueError("this ladder holds no statistics: call set_ladder_statistics() first")
         self._materialise()
-        if self._pgroup is not None or self._on_stream:
-            return self._states.pt_statistics()   # (devices=[...]: shard 0's block; every shard's is the same)
-        return {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in self._host_stats.items()}
+        return self._lads[0]
 
     def get_ladder_statistics(self):
         """dict: rounds, in_kernel_rounds (of them, decided inside persistent launches); attempts, accepts uint64[G - 1] and
@@ -453,7 +684,7 @@ class ClassicalTempering:
         if self._pair is not None:
             both = [c.get_ladder_statistics() for c in self._pair]
             return {k: np.stack([np.asarray(d[k]) for d in both]) for k in both[0]}
-        raw = self._raw_ladder_statistics()
+        raw = self._statistics_ladder().raw_statistics()
         out = {k: raw[k] for k in ("rounds", "in_kernel_rounds", "attempts", "accepts")}
         with np.errstate(divide="ignore", invalid="ignore"):
             out["acceptance"] = np.where(raw["attempts"] > 0, raw["accepts"] / raw["attempts"].astype(np.float64), np.nan)
@@ -472,23 +703,42 @@ class ClassicalTempering:
             for c in self._pair:
                 c.reset_ladder_statistics()
             return
-        if not self._stats_seen:
-            raise ValueError("this ladder holds no statistics: call set_ladder_statistics() first")
-        self._materialise()
-        if self._pgroup is not None:
-            for st in self._shards:
-                st.pt_reset_statistics()
-        elif self._on_stream:
-            self._states.pt_reset_statistics()
-        else:
-            self._host_stats = _capi.pt_statistics_zeros(len(self._betas))
+        self._statistics_ladder().reset_statistics()
 
-    # -- copies=2: the two ladders, cut at exchange rounds and at cluster moves ------------------------------------------------
-    def _materialise_pair(self):
+    # -- building the ladder: which of the three kinds it is gets decided here, once ----------------------------------------------
+    def _materialise(self):
         if self._states is not None:
             return
-        if not self._betas:
+        G = len(self._betas)
+        if G == 0:
             raise ValueError("no graphs: call add_graph(beta) first")
+        if self._pair is not None:
+            return self._materialise_pair()
+        self._perm = np.arange(G, dtype=np.uint32)
+        if self._devices is not None:
+            self._lads = [_GroupLadder(self, G)]
+        else:
+            self._per = D.block_size(G, self._world)
+            self._lo, self._hi = D.shard_bounds(G, self._world, self._rank)
+            self._engine = self._engine_factory()
+            self._states = self._engine.make_states(np.array(self._slot_seeds, dtype=np.uint64), (self._lo, self._hi))
+            self._on_stream = (bool(getattr(self._engine, "supports_on_stream_pt", False)) and self._hi > self._lo and
+                               os.environ.get("ISINGMC_PT_HOST", "0") in ("", "0"))  # ISINGMC_PT_HOST=1: the host swap step (A/B runs)
+            # eligibility first, WITHOUT side effects (e.g. a real-coupling graph too small for the packed kernels, a bit-sliced shard
+            # that cuts a replica group: the host swap step serves those) ...
+            if self._on_stream:
+                self._on_stream = self._states.pt_can_attach(G, self._lo, self._per, self._world)
+            if self._world > 1:  # ... then every rank must take the same path (the collective differs) ...
+                flags = D.all_gather_f64(np.array([float(self._on_stream)]), 1, self._group)  # (a rank without slots has no buffers to gather into: host path for all)
+                self._on_stream = bool(flags.min() > 0)
+            self._lads = [_StreamLadder(self) if self._on_stream else _HostLadder(self)]   # ... and only then does anyone attach
+            if self._track_minimum:
+                self._apply_track_minimum()
+        if self._stats_seen:   # (set_ladder_statistics(True) has been called at least once: the statistics exist from here on)
+            self._lads[0].set_statistics(self._stats_on)
+
+    def _materialise_pair(self):
+        """copies=2: two copies=1 ladders on one engine; the loops below walk both and add the cuts at cluster moves and samples."""
         a, b = self._pair
         a._materialise()
         b._materialise()
@@ -496,9 +746,18 @@ class ClassicalTempering:
             raise RuntimeError("the two copies of the ladder took different exchange paths")
         if self._icm_every and not hasattr(a._states, "icm_between"):
             raise ValueError("this engine has no isoenergetic cluster move between containers (icm_between)")
-        self._states = a._states
-        self._on_stream = a._on_stream
+        self._states, self._on_stream, self._lads = a._states, a._on_stream, a._lads + b._lads
+        self._lo, self._hi = a._lo, a._hi
         self._icm_pending = False
+
+    def group_backend(self):
+        """'rccl' or 'copy' for an in-process ladder (devices=[...]), else None."""
+        self._materialise()
+        return self._lads[0].backend
+
+    def _swap_step(self):
+        """One exchange round of a copies=1 ladder that has been built."""
+        self._lads[0].exchange()
 
     def _pair_icm(self):
         """Timestep self._t of both copies as a cluster move between the configurations at equal rungs."""
@@ -508,282 +767,37 @@ class ClassicalTempering:
         else:
             a._states.icm_between(b._states, a._perm, b._perm)
         self._icm_stats, self._icm_pending = None, True
-        self._t += 1
 
-    def _pair_sweeps(self, n):
-        for c in self._pair:
-            if c._on_stream:
-                c._states.pt_time_steps(n)
-            else:
-                c._states.do_time_steps(n)
-        self._t += n
-
-    def _until_icm(self):
-        """Metropolis timesteps before the next cluster move (None: there is none)."""
-        k = self._icm_every
-        return (k - 1 - self._t % k) if k else None
-
-    def _pair_timesteps(self, t, f):
-        self._materialise_pair()
-        t, f = int(t), int(f or 0)
-        done = 0
-        while done < t:
-            m = self._until_icm()
-            if m == 0:
-                self._pair_icm()   # a timestep; a sample, then a round, that fall on the same boundary come after it
-                done += 1
-                self._pair_sample()
-                if f and done % f == 0:
-                    for c in self._pair:
-                        c._swap_step()
-                continue
-            n = t - done if m is None else min(m, t - done)
-            while n > 0:
-                u = self._until_sample()
-                whole = n // f * f if f else 0   # rounds inside the stretch: one library call (in-kernel rounds on strip shapes)
-                if u is not None:                # ... which ends before the next sample: that one goes between a timestep and its round
-                    whole = min(whole, (u - 1) // f * f) if f else 0
-                if f and done % f == 0 and whole >= f and self._on_stream:
-                    for c in self._pair:
-                        c._states.pt_run(whole, f)
-                    self._t += whole
-                    done += whole
-                    n -= whole
-                    continue
-                b = min(n, f - done % f) if f else n
-                b = b if u is None else min(b, u)
-                self._pair_sweeps(b)
-                done += b
-                n -= b
-                self._pair_sample()
-                if f and done % f == 0:
-                    for c in self._pair:
-                        c._swap_step()
-        if self._on_stream:
-            for c in self._pair:
-                c._states.synchronize()
-
-    def _pair_timesteps_sample(self, timesteps, replica_swap_freq, sampling_freq):
-        """The countdown scheduler of timesteps_sample over both copies, cut at cluster moves as well: states bool[2, G, S, N]
-        by rung, energies float64[2, G]."""
-        self._materialise_pair()
-        sampling_freq = 1 if sampling_freq is None else int(sampling_freq)
-        replica_swap_freq = 1 if replica_swap_freq is None else int(replica_swap_freq)
-        if sampling_freq <= 0:
-            raise ValueError("sampling_freq must be positive")
-        G, N = len(self._betas), self.nvars
-        S = timesteps // sampling_freq
-        for c in self._pair:
-            if c._on_stream:
-                c._perm = c._states.pt_state()[0]
-        states = np.zeros((2, G, S, N), dtype=np.bool_)   # by slot first
-        rungs = np.zeros((2, G, S), dtype=np.int64)
-        energy_acc = np.zeros((2, G), dtype=np.float64)
-        remaining, to_swap, to_sample, k = timesteps, replica_swap_freq, sampling_freq, 0
-        while remaining > 0:
-            t = min(to_sample, remaining) if replica_swap_freq <= 0 else min(to_sample, to_swap, remaining)
-            m = self._until_icm()
-            if m == 0:
-                t = 1
-                self._pair_icm()
-                for i, c in enumerate(self._pair):   # the energy after the move counts as this timestep's energy
-                    energy_acc[i] += c._states.energies()[c._perm]
-            else:
-                t = t if m is None else min(t, m)
-                for i, c in enumerate(self._pair):
-                    energy_acc[i] += c._states.do_time_steps(t, per_step_energies=True).sum(axis=1)[c._perm]
-                self._t += t
-            to_sample -= t
-            to_swap -= t
-            remaining -= t
-            if to_swap == 0 and replica_swap_freq > 0:
-                for c in self._pair:
-                    c._swap_step(need_perm=True)
-                to_swap = replica_swap_freq
-            if to_sample == 0:
-                if k < S:
-                    for i, c in enumerate(self._pair):
-                        c._states.states(out=states[i, :, k, :])
-                        inv = np.empty(G, dtype=np.int64)
-                        inv[c._perm] = np.arange(G)
-                        rungs[i, :, k] = inv
-                k += 1
-                to_sample = sampling_freq
-        by_rung = np.empty_like(states)
-        for i in range(2):
-            for s in range(S):
-                by_rung[i, rungs[i, :, s], s, :] = states[i, :, s, :]
-        return by_rung, energy_acc / max(timesteps, 1)
-
-    def _materialise(self):
-        if self._pair is not None:
-            return self._materialise_pair()
-        if self._states is not None:
-            return
-        G = len(self._betas)
-        if G == 0:
-            raise ValueError("no graphs: call add_graph(beta) first")
-        if self._devices is not None:
-            return self._materialise_in_process(G)
-        self._per = D.block_size(G, self._world)
-        self._lo, self._hi = D.shard_bounds(G, self._world, self._rank)
-        self._engine = self._engine_factory()
-        self._states = self._engine.make_states(np.array(self._slot_seeds, dtype=np.uint64), (self._lo, self._hi))
-        self._perm = np.arange(G, dtype=np.uint32)
-        import os
-        self._on_stream = (bool(getattr(self._engine, "supports_on_stream_pt", False)) and self._hi > self._lo and
-                           os.environ.get("ISINGMC_PT_HOST", "0") in ("", "0"))  # ISINGMC_PT_HOST=1: the host swap step (A/B runs)
-        # eligibility first, WITHOUT side effects (e.g. a real-coupling graph too small for the packed kernels, a bit-sliced shard
-        # that cuts a replica group: the host swap step serves those) ...
-        if self._on_stream:
-            self._on_stream = self._states.pt_can_attach(G, self._lo, self._per, self._world)
-        if self._world > 1:  # ... then every rank must take the same path (the collective differs) ...
-            flags = D.all_gather_f64(np.array([float(self._on_stream)]), 1, self._group)  # (a rank without slots has no buffers to gather into: host path for all)
-            self._on_stream = bool(flags.min() > 0)
-        if self._on_stream:  # ... and only then does anyone attach
-            self._states.pt_attach(self._betas, self._lo, self._per, self._world, self._seed)
-        if self._on_stream:
-            self._pt_local, self._pt_all = self._states.pt_buffers()
-            self._pt_stream = self._states.pt_stream() if self._world > 1 else None
-        else:
-            self._push_betas()
-        if self._track_minimum:
-            self._apply_track_minimum()
-        if self._stats_seen:
-            self._apply_ladder_statistics()
-
-    def _materialise_in_process(self, G):
-        """One shard per device, the same ladder attached to each, an isingmc_pt_group between them."""
-        n = len(self._devices)
-        if n == 0:
-            raise ValueError("devices must name at least one GPU")
-        self._per = D.block_size(G, n)
-        seeds = np.array(self._slot_seeds, dtype=np.uint64)
-        self._bounds = [D.shard_bounds(G, n, k) for k in range(n)]
-        if any(hi <= lo for lo, hi in self._bounds):
-            raise ValueError("more devices than blocks of rungs: every device needs at least one slot")
-        shards = []
-        for k, dev in enumerate(self._devices):
-            engine = HipEngine(self._ea, self._eb, self._ej, self.nvars, device=dev)
-            st = engine.make_states(seeds, self._bounds[k])
-            if not (engine.supports_on_stream_pt and st.pt_can_attach(G, self._bounds[k][0], self._per, n)):
-                raise ValueError("the in-process ladder needs on-stream tempering on every shard (a periodic field-free lattice or "
-                                 "a replica-packed graph; on the bit-sliced path shards of whole 32-slot groups): " + _capi.last_error())
-            shards.append(st)
-        for k, st in enumerate(shards):
-            st.pt_attach(self._betas, self._bounds[k][0], self._per, n, self._seed)
-        self._shards = shards
-        self._pgroup = _capi.PtGroup(shards, self._group_backend)
-        self._states = shards[0]
-        self._lo, self._hi = 0, G
-        self._perm = np.arange(G, dtype=np.uint32)
-        self._on_stream = True
-        if self._stats_seen:
-            self._apply_ladder_statistics()
-
-    def group_backend(self):
-        """'rccl' or 'copy' for an in-process ladder (devices=[...]), else None."""
-        self._materialise()
-        return None if self._pgroup is None else self._pgroup.backend
-
-    def _in_process_swap_round(self):
-        for st in self._shards:
-            st.pt_measure()
-        self._pgroup.allgather()
-        for st in self._shards:
-            st.pt_swap()
-
-    def _push_betas(self):
-        G = len(self._betas)
-        beta_of_slot = np.empty(G, dtype=np.float64)
-        beta_of_slot[self._perm] = self._betas
-        if self._hi > self._lo:
-            self._states.set_betas(beta_of_slot[self._lo:self._hi])
-
-    def _slot_energies(self, local):
-        """float64[G] in slot order on every rank: the swap step's all-gather."""
-        G = len(self._betas)
-        gathered = D.all_gather_f64(local, self._per, self._group)
-        out = np.empty(G, dtype=np.float64)
-        for r in range(self._world):
-            lo, hi = D.shard_bounds(G, self._world, r)
-            out[lo:hi] = gathered[r * self._per:r * self._per + (hi - lo)]
-        return out
-
-    def _swap_step(self, need_perm=False):
-        if self._on_stream:
-            # measure -> [RCCL all-gather on the engine's stream] -> exchange kernel: nothing waits on the host
-            self._states.pt_measure()
-            if self._world > 1:
-                import torch
-                import torch.distributed as dist
-                if dist.get_backend(self._group) == "nccl":
-                    with torch.cuda.stream(self._pt_stream):
-                        dist.all_gather_into_tensor(self._pt_all, self._pt_local, group=self._group)
-                else:
-                    # gloo (several ranks rehearsing on one GPU): the same exchange through the host -- wait for the
-                    # measurement, gather on the CPU, put the result where the exchange kernel reads it
-                    self._states.synchronize()
-                    send = self._pt_local.cpu()
-                    recv = torch.empty(self._world * self._per, dtype=torch.float64)
-                    dist.all_gather_into_tensor(recv, send, group=self._group)
-                    self._pt_all.copy_(recv)
-                    torch.cuda.synchronize()
-            self._states.pt_swap()
-            if need_perm:
-                self._perm = self._states.pt_state()[0]
-            return
-        local = self._states.energies() if self._hi > self._lo else np.zeros(0)
-        if self._track_minimum and self._hi > self._lo:
-            self._states.best_update()
-        slot_e = self._slot_energies(local)
-        before = self._perm.copy() if self._stats_on else None
-        self._total_swaps += _capi.pt_swap_round(self._seed, self._round, self._betas, slot_e, self._perm)
-        if self._stats_on:   # the host twin of what the exchange kernels keep (DESIGN.md S20); every rank computes the same
-            _capi.pt_statistics_round(self._host_stats, self._round, before, self._perm, slot_e)
-        self._round += 1
-        self._push_betas()
-
+    # -- the two loops: both walk schedule(), which holds the order "timestep, overlap sample, exchange round, state sample" ----------
     def timesteps(self, t, replica_swap_freq=None):
         """tempering.rs:150-152 (parallel_timesteps): t sweeps on every rung.  replica_swap_freq (extension):
         an exchange round after every `replica_swap_freq` sweeps, as in the loop of tempering.rs:177-194."""
-        if self._pair is not None:
-            if t > 0:
-                self._pair_timesteps(t, replica_swap_freq)
-            return
-        self._materialise()
+        if self._pair is None or t > 0:   # (a call without timesteps does not build a copies=2 ladder)
+            self._materialise()
         if t <= 0:
             return
-        if self._pgroup is not None:
-            if not replica_swap_freq:
-                for st in self._shards:
-                    st.pt_time_steps(int(t))
-            else:
-                self._pgroup.run(int(t), int(replica_swap_freq))
-            self._pgroup.synchronize()
-            return
-        if not replica_swap_freq:
-            if self._hi > self._lo:
-                self._states.do_time_steps(t)
-            return
-        if self._on_stream and self._world == 1 and self._hi > self._lo:
-            # single rank: the whole loop is one library call (one persistent launch on mid-size lattices)
-            self._states.pt_run(int(t), int(replica_swap_freq))
-            self._states.synchronize()
-            return
-        done = 0
-        while done < t:
-            b = min(int(replica_swap_freq), t - done)
-            if self._hi > self._lo:
-                if self._on_stream:
-                    self._states.pt_time_steps(b)
-                else:
-                    self._states.do_time_steps(b)
-            done += b
-            if b == replica_swap_freq:
-                self._swap_step()
-        if self._on_stream:
-            self._states.synchronize()
+        t, f, lads = int(t), int(replica_swap_freq or 0), self._lads
+        if not f and self._pair is None:
+            self._t += t
+            return lads[0].plain(t)
+        # a copies=1 ladder hands the library whole calls where it can, a pair whole rounds: its copies meet at moves and samples
+        fuse = lads[0].fuse if self._pair is None else min(lads[0].fuse, FUSE_ROUNDS)
+        for n, kind, overlap_due, round_due, _ in schedule(self._t, t, f, self._icm_every, self._ovl_every, self._ovl_t0, 0, fuse):
+            for lad in lads:
+                if kind == FUSED:
+                    lad.run(n, f)
+                elif kind == SWEEPS:
+                    lad.sweep(n)
+            if kind == MOVE:
+                self._pair_icm()
+            self._t += n
+            if overlap_due:
+                self._pair_sample()
+            if round_due:
+                for lad in lads:
+                    lad.exchange()
+        for lad in lads:
+            lad.synchronize()
 
     def timesteps_sample(self, timesteps, replica_swap_freq=None, sampling_freq=None):
         """tempering.rs:156-222: countdown scheduler of run / swap / sample.
@@ -794,90 +808,34 @@ class ClassicalTempering:
         held at each sample (configurations never leave their GPU).  copies=2: states bool[2, G, S, N] by rung and
         energies float64[2, G], one row per copy.
         """
-        if self._pair is not None:
-            return self._pair_timesteps_sample(timesteps, replica_swap_freq, sampling_freq)
         self._materialise()
-        if self._pgroup is not None:
-            return self._timesteps_sample_in_process(timesteps, replica_swap_freq, sampling_freq)
-        if self._on_stream and self._hi > self._lo:
-            self._perm = self._states.pt_state()[0]  # the device owns the ladder state
-        sampling_freq = 1 if sampling_freq is None else int(sampling_freq)
-        replica_swap_freq = 1 if replica_swap_freq is None else int(replica_swap_freq)
-        if sampling_freq <= 0:
-            raise ValueError("sampling_freq must be positive")
-        G, N = len(self._betas), self.nvars
-        n_local = self._hi - self._lo
-        S = timesteps // sampling_freq
-        states = np.zeros((n_local, S, N), dtype=np.bool_)
-        rungs = np.zeros((n_local, S), dtype=np.int64)
-        energy_acc = np.zeros(G, dtype=np.float64)
-
-        remaining, to_swap, to_sample, k = timesteps, replica_swap_freq, sampling_freq, 0
-        while remaining > 0:
-            t = min(to_sample, remaining) if replica_swap_freq <= 0 else min(to_sample, to_swap, remaining)
-            local_sum = np.zeros(n_local)
-            if n_local:
-                local_sum = self._states.do_time_steps(t, per_step_energies=True).sum(axis=1)
-            # energy_acc[rung] += te * t  (tempering.rs:185), te = mean energy over the block
-            energy_acc += self._slot_energies(local_sum)[self._perm]
-            to_sample -= t
-            to_swap -= t
-            remaining -= t
-            if to_swap == 0 and replica_swap_freq > 0:
-                self._swap_step(need_perm=True)
-                to_swap = replica_swap_freq
-            if to_sample == 0:
-                if n_local and k < S:
-                    self._states.states(out=states[:, k, :])
-                    inv = np.empty(G, dtype=np.int64)
-                    inv[self._perm] = np.arange(G)
-                    rungs[:, k] = inv[self._lo:self._hi]
-                k += 1
-                to_sample = sampling_freq
-        energies = energy_acc / max(timesteps, 1)
-        if self._world == 1:
-            by_rung = np.empty_like(states)
-            for s in range(S):
-                by_rung[rungs[:, s], s, :] = states[:, s, :]
-            return by_rung, energies
-        return states, energies, rungs
-
-    def _timesteps_sample_in_process(self, timesteps, replica_swap_freq, sampling_freq):
-        """The countdown scheduler of tempering.rs:156-222 over the shards of an in-process ladder: (states bool[G, S, N] by
-        rung, energies float64[G])."""
-        sampling_freq = 1 if sampling_freq is None else int(sampling_freq)
-        replica_swap_freq = 1 if replica_swap_freq is None else int(replica_swap_freq)
-        if sampling_freq <= 0:
-            raise ValueError("sampling_freq must be positive")
-        G, N = len(self._betas), self.nvars
-        S = timesteps // sampling_freq
-        perm = self._shards[0].pt_state()[0]
-        states = np.zeros((G, S, N), dtype=np.bool_)           # by slot first
-        rungs = np.zeros((G, S), dtype=np.int64)
-        energy_acc = np.zeros(G, dtype=np.float64)
-        remaining, to_swap, to_sample, k = timesteps, replica_swap_freq, sampling_freq, 0
-        while remaining > 0:
-            t = min(to_sample, remaining) if replica_swap_freq <= 0 else min(to_sample, to_swap, remaining)
-            slot_sum = np.concatenate([st.do_time_steps(t, per_step_energies=True).sum(axis=1) for st in self._shards])
-            energy_acc += slot_sum[perm]                         # energy_acc[rung] += te * t (tempering.rs:185)
-            to_sample -= t
-            to_swap -= t
-            remaining -= t
-            if to_swap == 0 and replica_swap_freq > 0:
-                self._in_process_swap_round()
-                perm = self._shards[0].pt_state()[0]
-                to_swap = replica_swap_freq
-            if to_sample == 0:
+        f, sampling_freq = _frequencies(replica_swap_freq, sampling_freq)
+        lads, G, S = self._lads, len(self._betas), timesteps // sampling_freq
+        perms = [lad.perm() for lad in lads]   # (on the device's stream the device owns the ladder state)
+        states = np.zeros((len(lads), self._hi - self._lo, S, self.nvars), dtype=np.bool_)   # by slot first
+        rungs = np.zeros(states.shape[:3], dtype=np.int64)
+        energy_acc = np.zeros((len(lads), G), dtype=np.float64)
+        k = 0
+        for n, kind, _, round_due, sample_due in schedule(self._t, timesteps, f, self._icm_every, sample=sampling_freq):
+            if kind == MOVE:
+                self._pair_icm()
+            for i, lad in enumerate(lads):
+                # energy_acc[rung] += te * t (tempering.rs:185), te = mean energy over the block; the energy after a move counts as
+                # that timestep's energy
+                energy_acc[i] += (lad.st.energies() if kind == MOVE else lad.slot_sums(n))[perms[i]]
+            self._t += n
+            if round_due:
+                for i, lad in enumerate(lads):
+                    lad.exchange()
+                    perms[i] = lad.perm()
+            if sample_due:
                 if k < S:
-                    for (lo, hi), st in zip(self._bounds, self._shards):
-                        st.states(out=states[lo:hi, k, :])
-                    inv = np.empty(G, dtype=np.int64)
-                    inv[perm] = np.arange(G)
-                    rungs[:, k] = inv
+                    for i, lad in enumerate(lads):
+                        lad.read_states(states[i, :, k, :])
+                        rungs[i, :, k] = _inverse(perms[i])[self._lo:self._hi]
                 k += 1
-                to_sample = sampling_freq
-        self._perm = perm
-        by_rung = np.empty_like(states)
-        for s in range(S):
-            by_rung[rungs[:, s], s, :] = states[:, s, :]
-        return by_rung, energy_acc / max(timesteps, 1)
+        energies = energy_acc / max(timesteps, 1)
+        if self._world > 1:
+            return states[0], energies[0], rungs[0]
+        by_rung = _by_rung(states, rungs)
+        return (by_rung, energies) if self._pair is not None else (by_rung[0], energies[0])
