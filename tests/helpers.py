@@ -44,8 +44,9 @@ class OracleLatStates:
 
 
 class OracleLatEngine:
-    def __init__(self, W, H, jabs=1.0, jpos=0):
-        self.lat = O.Lat(W, H, jabs, jpos)
+    def __init__(self, W, H, jabs=1.0, jpos=0, jright=None, jdown=None):
+        """jright / jdown: uint8[H * W] sign planes of a +-J lattice (1 where the bond is +|J|), passed on to oracle.Lat"""
+        self.lat = O.Lat(W, H, jabs, jpos, jright, jdown)
         self.nvars = W * H
 
     def make_states(self, seeds, replica_range=None):
