@@ -429,6 +429,59 @@ int isingmc_overlap_series_get(isingmc_overlap_series *s, size_t first, size_t n
 int isingmc_overlap_series_reset(isingmc_overlap_series *s);
 int isingmc_overlap_series_destroy(isingmc_overlap_series *s);
 
+/* ---- The observable series: energy and magnetisation per sample, logged on the device (no reference counterpart) ----
+ * The sibling of the overlap series for the observables of ONE container `a`: a device-resident log with one row per sample.  A
+ * record appends a row without the host waiting for anything; the log is read once, afterwards.  A series has n_columns = count
+ * columns: the replicas in slot order, or with ISINGMC_OBS_BY_RUNG the rungs in ladder order -- column i is then the slot that holds
+ * rung i when the record runs; the permutation is read on the device, behind the timestep and before any exchange round that follows.
+ * A row holds, per column,
+ *   energy         f64, bit for bit the value isingmc_get_energies would return for that configuration at that moment
+ *   magnetisation  int64, sum_i s_i, as isingmc_get_magnetisations
+ *   by_class[t][c] with a class set: int64, the sum of s_i over the sites of class c of table t.  ISINGMC_NO_CLASS sites count
+ *                  nowhere, an empty class gives 0, a table without ISINGMC_NO_CLASS adds up to the magnetisation; padding positions,
+ *                  bits a packed group does not own and replicas beyond count never count.
+ * A record consumes no random number and writes no configuration; it counts into a block the series owns and leaves the timestep
+ * counters, the container's measurement scratch and whatever the ladder's next exchange round decides from exactly as they were: an
+ * exchange round that follows a record takes the same decisions as without it.  The log holds `capacity` rows in one device block of
+ * the series, at most the option "observable_series_bytes" of `a` (isingmc_states_set_option; ISINGMC_OBSERVABLE_SERIES_BYTES,
+ * default 1 GiB); the host keeps the timestep of every row (a's counter when the record was enqueued) and the row count.
+ * isingmc_observable_series_create: served are exactly the containers with a device-side energy array -- periodic, field-free,
+ *   isotropic checkerboard lattices (fast_path == 0) and both replica-packed families, shards of a larger set of experiments
+ *   included.  ISINGMC_ERR_INVALID, the container unchanged: the f64 CSR family; lattices with field, open boundary or anisotropy;
+ *   unknown flags; neither ISINGMC_OBS_ENERGY nor ISINGMC_OBS_MAGNETISATION nor a class set; capacity == 0; a class set of another
+ *   graph; a log beyond the byte budget.  ISINGMC_OBS_BY_RUNG needs the whole ladder on the container (world size 1, count ==
+ *   n_rungs, slot offset 0); without it an attached ladder is allowed and the columns are slots.
+ * isingmc_observable_series_record: one row for the configurations as they are, enqueue only.  A full log refuses with
+ *   ISINGMC_ERR_INVALID: nothing is enqueued, the rows stay.
+ * isingmc_observable_series_set_every: every > 0: from now on (t0 = a's timestep) a record follows every timestep t with
+ *   (t - t0) % every == 0, whatever kind of timestep it is, inside isingmc_do_time_steps*, isingmc_run_sampling,
+ *   isingmc_run_sampling_moments and therefore isingmc_pt_time_steps; isingmc_pt_run takes one launch per round while the period is
+ *   on (same decisions, same results), and a series by rung takes its row behind an isingmc_icm_between move whose timestep is a
+ *   sample point.  0 switches it off and keeps the rows.  One such series per container.  isingmc_states_set_timestep re-bases t0; a
+ *   run call whose rows would not fit fails before it enqueues anything -- isingmc_pt_run counts the rows of its whole call before
+ *   its first round, and isingmc_icm_between the row behind the move before its launches; isingmc_states_append, isingmc_pa_run
+ *   and isingmc_pa_resample are refused while it is on.
+ * isingmc_observable_series_count: rows held and the capacity (either pointer may be NULL).
+ * isingmc_observable_series_get: waits once for a's stream, then copies the rows [first, first + n): timesteps_out[n],
+ *   energy_out[n][n_columns], magnetisation_out[n][n_columns], class_out[n][n_columns][n_tables][n_classes]; any pointer may be NULL;
+ *   asking for a part the series does not hold is refused.  Changes nothing.
+ * isingmc_observable_series_reset: the row count back to 0 (enqueue only); the period stays.
+ * A series is destroyed before its container and its class set; isingmc_pt_detach is refused on a container with a live BY_RUNG
+ * series. */
+typedef struct isingmc_observable_series isingmc_observable_series;
+#define ISINGMC_OBS_ENERGY 1u        /* the energy of every column */
+#define ISINGMC_OBS_MAGNETISATION 2u /* the magnetisation of every column */
+#define ISINGMC_OBS_BY_RUNG 4u       /* column i = the slot at rung i, the permutation read on the device */
+int isingmc_observable_series_create(isingmc_states *a, const isingmc_site_classes *classes, unsigned flags, size_t capacity,
+                                     isingmc_observable_series **out);
+int isingmc_observable_series_record(isingmc_observable_series *s);
+int isingmc_observable_series_set_every(isingmc_observable_series *s, size_t every);
+int isingmc_observable_series_count(const isingmc_observable_series *s, size_t *n_out, size_t *capacity_out);
+int isingmc_observable_series_get(isingmc_observable_series *s, size_t first, size_t n, uint64_t *timesteps_out, double *energy_out,
+                                  int64_t *magnetisation_out, int64_t *class_out);
+int isingmc_observable_series_reset(isingmc_observable_series *s);
+int isingmc_observable_series_destroy(isingmc_observable_series *s);
+
 /* ---- each replica's lowest-energy configuration, kept on the device (no reference counterpart) ----
  * A container may keep, per replica, the lowest energy its configuration has had at an UPDATE, the timestep of that update and
  * the configuration itself.  An update measures the f64 energies of isingmc_get_energies on the device and, for every replica

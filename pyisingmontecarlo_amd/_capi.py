@@ -18,6 +18,9 @@ MOMENTS_BONDS = 2
 MOMENTS_PER_RUNG = 4
 SERIES_LINK = 1  # ISINGMC_SERIES_*
 SERIES_BY_RUNG = 2
+OBS_ENERGY = 1  # ISINGMC_OBS_*
+OBS_MAGNETISATION = 2
+OBS_BY_RUNG = 4
 FAMILIES = ("checkerboard", "csr_f64", "packed_bitsliced", "packed_real")
 
 
@@ -97,6 +100,13 @@ _PROTOTYPES = {
     "isingmc_overlap_series_get": (C.c_int, [_vp, C.c_size_t, C.c_size_t, _vp, _vp, _vp, _vp]),
     "isingmc_overlap_series_reset": (C.c_int, [_vp]),
     "isingmc_overlap_series_destroy": (C.c_int, [_vp]),
+    "isingmc_observable_series_create": (C.c_int, [_vp, _vp, C.c_uint, C.c_size_t, C.POINTER(_vp)]),
+    "isingmc_observable_series_record": (C.c_int, [_vp]),
+    "isingmc_observable_series_set_every": (C.c_int, [_vp, C.c_size_t]),
+    "isingmc_observable_series_count": (C.c_int, [_vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "isingmc_observable_series_get": (C.c_int, [_vp, C.c_size_t, C.c_size_t, _vp, _vp, _vp, _vp]),
+    "isingmc_observable_series_reset": (C.c_int, [_vp]),
+    "isingmc_observable_series_destroy": (C.c_int, [_vp]),
     "isingmc_states_set_track_best": (C.c_int, [_vp, C.c_size_t]),
     "isingmc_states_track_best": (C.c_int, [_vp, C.POINTER(C.c_size_t)]),
     "isingmc_best_update": (C.c_int, [_vp]),
@@ -485,17 +495,25 @@ class _SeriesHandle:
     whichever of them goes first destroys the series.  (Not a weak reference to the OverlapSeries: the garbage collector clears
     those before it finalises a cycle, and the series must go before what it reads in whatever order that happens.)"""
 
+    destroy = "isingmc_overlap_series_destroy"
+
     def __init__(self):
         self.h = _vp()
 
     def close(self):
         if self.h:
-            lib().isingmc_overlap_series_destroy(self.h)
+            getattr(lib(), self.destroy)(self.h)
             self.h = _vp()
 
 
+class _ObservableSeriesHandle(_SeriesHandle):
+    """... and the handle of an observable series, by the same rule."""
+
+    destroy = "isingmc_observable_series_destroy"
+
+
 def _close_series(owner):
-    """The overlap series that read `owner` (a container or a class set) go before it does."""
+    """The overlap and observable series that read `owner` (a container or a class set) go before it does."""
     for handle in owner.__dict__.pop("_series", []):
         handle.close()
 
@@ -563,6 +581,75 @@ class OverlapSeries:
     def reset(self):
         """The row count back to 0 (enqueue only); the period stays."""
         _check(lib().isingmc_overlap_series_reset(self._h))
+
+    def close(self):
+        self._handle.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ObservableSeries:
+    """isingmc_observable_series: a device-resident log with one row per sample -- per column (replica slot, or rung with by_rung)
+    the energy, the magnetisation and the magnetisation by site class.  record() and the periodic records inside
+    the step loop only enqueue; get() reads the log, once, afterwards.  Made by States.observable_series."""
+
+    def __init__(self, a, classes=None, energy=True, magnetisation=True, by_rung=False, capacity=4096):
+        self._a, self._classes = a, classes  # keeps them alive
+        self._handle = _ObservableSeriesHandle()
+        self.energy, self.magnetisation, self.by_rung = bool(energy), bool(magnetisation), bool(by_rung)
+        self.n_columns = a.count
+        self.n_tables, self.n_classes = (classes.n_tables, classes.n_classes) if classes is not None else (0, 0)
+        flags = (OBS_ENERGY if energy else 0) | (OBS_MAGNETISATION if magnetisation else 0) | (OBS_BY_RUNG if by_rung else 0)
+        _check(lib().isingmc_observable_series_create(a._h, None if classes is None else classes._h, flags, int(capacity),
+                                                      C.byref(self._handle.h)))
+        for owner in (a, classes):
+            if owner is not None:
+                owner.__dict__["_series"] = [h for h in owner.__dict__.get("_series", []) if h.h] + [self._handle]
+
+    @property
+    def _h(self):
+        return self._handle.h
+
+    def record(self):
+        """One row for the configurations as they are.  Enqueue only."""
+        _check(lib().isingmc_observable_series_record(self._h))
+
+    def set_every(self, k):
+        """A record follows every timestep t > t0 (now) with (t - t0) % k == 0, inside the run calls; 0: off, the rows stay."""
+        _check(lib().isingmc_observable_series_set_every(self._h, int(k)))
+
+    @property
+    def count(self):
+        n = C.c_size_t()
+        _check(lib().isingmc_observable_series_count(self._h, C.byref(n), None))
+        return int(n.value)
+
+    @property
+    def capacity(self):
+        n = C.c_size_t()
+        _check(lib().isingmc_observable_series_count(self._h, None, C.byref(n)))
+        return int(n.value)
+
+    def get(self, first=0, n=None):
+        """(timesteps uint64[n], energy float64[n, C] or None, magnetisation int64[n, C] or None, by_class int64[n, C, T, K] or
+        None) of the rows [first, first + n) (n=None: all from `first` on).  Synchronises once; changes nothing."""
+        first = int(first)
+        n = max(self.count - first, 0) if n is None else int(n)
+        cols = self.n_columns
+        t = np.zeros(n, dtype=np.uint64)
+        e = np.zeros((n, cols), dtype=np.float64) if self.energy else None
+        m = np.zeros((n, cols), dtype=np.int64) if self.magnetisation else None
+        cls = np.zeros((n, cols, self.n_tables, self.n_classes), dtype=np.int64) if self.n_tables else None
+        _check(lib().isingmc_observable_series_get(self._h, first, n, _p(t), _p(e), _p(m), _p(cls)))
+        return t, e, m, cls
+
+    def reset(self):
+        """The row count back to 0 (enqueue only); the period stays."""
+        _check(lib().isingmc_observable_series_reset(self._h))
 
     def close(self):
         self._handle.close()
@@ -727,6 +814,11 @@ class States:
         out = np.zeros((n, classes.n_tables, classes.n_classes), dtype=np.int64)
         _check(lib().isingmc_overlaps_by_class(self._h, None if other is None else other._h, _p(sa), _p(sb), n, classes._h, _p(out)))
         return out
+
+    def observable_series(self, classes=None, energy=True, magnetisation=True, by_rung=False, capacity=4096):
+        """An ObservableSeries: energy, magnetisation and magnetisation by class of every replica (by_rung: of
+        every rung of the attached ladder), one row per record, kept on the device."""
+        return ObservableSeries(self, classes, energy, magnetisation, by_rung, capacity)
 
     def overlap_series(self, other=None, n_pairs=None, classes=None, link=True, by_rung=False, capacity=4096):
         """An OverlapSeries over the pairs overlaps() would take: one row per record, kept on the device.

@@ -8,6 +8,10 @@ of plane_classes), and the rest is a Fourier transform of L numbers.
 The rows of an overlap series (OverlapSeries.get, ClassicalTempering.get_measured_overlaps) feed both directly:
 overlap_moments takes `spin` [n, P], and chi_sg / correlation_length take by_class[..., t, :] -- [n, P, L] for axis t -- as they
 come, the sample and pair axes being leading axes like any other.
+
+The rows of an observable series (ObservableSeries.get) do the same for the magnetisation of a ferromagnet:
+magnetisation_moments takes `magnetisation` [n, C], and structure_factor takes by_class[..., t, :] -- the plane magnetisations M_x of
+axis t -- as they come; its rows, averaged over samples, feed correlation_length unchanged.
 """
 import numpy as np
 
@@ -37,6 +41,25 @@ def overlap_moments(spin, nvars):
     with np.errstate(divide="ignore", invalid="ignore"):
         binder = np.where(q2 > 0, (3.0 - q4 / q2 ** 2) / 2.0, np.nan)
     return q1, q2, q4, binder
+
+
+def magnetisation_moments(mag, nvars):
+    """(<m>, <|m|>, <m^2>, <m^4>, U4) per column of mag[n, ...]: m = mag / nvars averaged over the n samples of axis 0 (the rows of
+    an observable series), and the Binder cumulant U4 = 1 - <m^4> / (3 <m^2>^2) -- 2/3 when every sample has |m| = 1, 0 for a
+    Gaussian m.  A column whose <m^2> is 0 has no cumulant: NaN.  The susceptibility is beta N (<m^2> - <|m|>^2)."""
+    m = np.asarray(mag, dtype=np.float64) / float(nvars)
+    m1, ma, m2, m4 = m.mean(axis=0), np.abs(m).mean(axis=0), (m ** 2).mean(axis=0), (m ** 4).mean(axis=0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        u4 = np.where(m2 > 0, (3.0 * m2 ** 2 - m4) / (3.0 * m2 ** 2), np.nan)  # (one rounding: exactly 2/3 for |m| = 1)
+    return m1, ma, m2, m4, u4
+
+
+def structure_factor(planes, nvars):
+    """|sum_x e^{i k x} M_x|^2 / nvars per row and wave number: entry n is S(k_n) at k_n = 2 pi n / L for ONE configuration,
+    planes[..., x] = M_x the L plane magnetisations of one axis (the by_class rows of plane_classes; leading axes, such as samples
+    and replicas, are kept).  Average it over samples before correlation_length takes the ratio."""
+    f = np.fft.fft(np.asarray(planes, dtype=np.float64), axis=-1)
+    return (f.real ** 2 + f.imag ** 2) / float(nvars)
 
 
 def correlation_length(chi0, chik, L, n=1):

@@ -6,6 +6,7 @@
 //   overlaps.hip   spin and link overlaps between replica pairs (isingmc_overlaps), and the spin overlap by site class
 //                  (isingmc_site_classes_*, isingmc_overlaps_by_class); the overlap core they share with the series
 //   overlap_series.hip  the device-resident log of overlap measurements, one row per sample (isingmc_overlap_series_*)
+//   observable_series.hip  the device-resident log of energy and magnetisation per sample (isingmc_observable_series_*)
 //   best.hip       each replica's lowest-energy configuration, kept on the device (isingmc_best_*)
 //   moments.hip    per-site spin sums and per-bond sums over the samples of a run (isingmc_moments_*)
 //   sampling.hip   get_states and the double-buffered sampling pipeline
@@ -47,6 +48,7 @@
 #include "pa_kernels.hpp"
 #include "mc_types.hpp"
 #include "moments_kernels.hpp"
+#include "observable_series_kernels.hpp"
 #include "overlap_class_kernels.hpp"
 #include "overlap_kernels.hpp"
 #include "overlap_series_kernels.hpp"
@@ -120,6 +122,7 @@ struct Options {
     int moments_planes = 8;               // time planes of the per-replica moment sums: a flush every 2^K - 1 samples
     long long moments_bytes = 4ll << 30;   // the most device memory the moment sums of one container may take (64 bits: beyond an int)
     long long overlap_series_bytes = 1ll << 30; // the most device memory the log of one overlap series may take
+    long long observable_series_bytes = 1ll << 30; // ... and the log of one observable series
 
     static Options from_env()
     {
@@ -150,6 +153,7 @@ struct Options {
         o.moments_planes = env_int("ISINGMC_MOMENTS_PLANES", o.moments_planes);
         if (const char *v = std::getenv("ISINGMC_MOMENTS_BYTES")) o.moments_bytes = std::atoll(v);
         if (const char *v = std::getenv("ISINGMC_OVERLAP_SERIES_BYTES")) o.overlap_series_bytes = std::atoll(v);
+        if (const char *v = std::getenv("ISINGMC_OBSERVABLE_SERIES_BYTES")) o.observable_series_bytes = std::atoll(v);
         return o;
     }
 
@@ -159,6 +163,7 @@ struct Options {
         const std::string n = option_bare_name(name_in);
         if (n == "moments_bytes") { moments_bytes = value; return true; }
         if (n == "overlap_series_bytes") { overlap_series_bytes = value; return true; }
+        if (n == "observable_series_bytes") { observable_series_bytes = value; return true; }
         const std::pair<const char *, int *> table[] = {
             {"force_real", &force_real}, {"disable_real", &disable_real}, {"force_packed", &force_packed}, {"disable_packed", &disable_packed},
             {"disable_packed_uniform", &disable_packed_uniform}, {"disable_resident", &disable_resident}, {"strip", &strip},
@@ -403,6 +408,11 @@ struct isingmc_states {
     isingmc_overlap_series *osr = nullptr;
     Periodic osr_at;
     size_t osr_by_rung_live = 0; // live series that read this container's ladder permutation on the device: no isingmc_pt_detach
+    // the observable series of this container that records on a period (isingmc_observable_series_set_every): a row
+    // at every sample point of obs_at
+    isingmc_observable_series *obs = nullptr;
+    Periodic obs_at;
+    size_t obs_by_rung_live = 0; // live observable series that read the ladder permutation on the device: no isingmc_pt_detach
     bool strip_guard = false; // inside with_strip_retry: a strip launch is checked before an update may keep what it left
 
     ~isingmc_states()
@@ -654,6 +664,12 @@ IM_INTERNAL int overlap_lanes_join(isingmc_states *a, isingmc_states *b); // bot
 IM_INTERNAL int osr_room_or_fail(const isingmc_states *s, size_t timesteps);
 IM_INTERNAL int osr_sample_enqueue(isingmc_states *s); // enqueue: one row of the container's periodic series at timestep s->t
 
+// ---- observable_series.hip (the device-resident log of energy and magnetisation per sample) ---------------------------------
+// before a run of `timesteps` timesteps enqueues anything: fails when the periodic series of the container would run full in it
+IM_INTERNAL int obs_room_or_fail(const isingmc_states *s, size_t timesteps);
+IM_INTERNAL int obs_sample_enqueue(isingmc_states *s); // enqueue: one row of the container's periodic series at timestep s->t
+IM_INTERNAL bool obs_sample_by_rung(const isingmc_states *s); // the container's periodic series is one by rung
+
 // ---- nonlocal.hip (Swendsen-Wang steps and isoenergetic cluster moves) -------------------------------------------------------
 // What the non-local steps of ONE run_steps call keep between them: filled by the call's first such step, the device blocks in the
 // call's DeviceScratch.  The host copies live as long as the call: they feed asynchronous copies.
@@ -700,9 +716,10 @@ static int with_strip_retry(isingmc_states *s, bool may_strip, F &&call)
     if (rc != STRIP_TIMED_OUT) return rc;
     TRY(snapshot_restore(s));
     s->mom_at.replay_since(t0); // (the repeat skips the samples already in the sums
-    s->osr_at.replay_since(t0); // ... and the rows already in the overlap series)
+    s->osr_at.replay_since(t0); // ... and the rows already in the overlap series
+    s->obs_at.replay_since(t0); // ... and in the observable series)
     s->t = t0;
     const int rc2 = strip_error(call());
-    s->mom_at.replay_to = s->osr_at.replay_to = 0;
+    s->mom_at.replay_to = s->osr_at.replay_to = s->obs_at.replay_to = 0;
     return rc2;
 }

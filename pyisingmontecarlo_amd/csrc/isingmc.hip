@@ -148,6 +148,7 @@ extern "C" int isingmc_states_append(isingmc_states *s, uint64_t seed, const uin
     if (s->best_at.every) return fail(ISINGMC_ERR_INVALID, "minimum tracking is switched on for this container (isingmc_states_set_track_best): its records are sized for the replicas it holds; switch tracking on after the graphs are added");
     if (s->mom_at.every) return fail(ISINGMC_ERR_INVALID, "moment sums are switched on for this container (isingmc_states_set_moments_every): they are sized for the replicas it holds; switch accumulation on after the graphs are added");
     if (s->osr_at.every) return fail(ISINGMC_ERR_INVALID, "an overlap series records on a period for this container (isingmc_overlap_series_set_every): its pairs are those of the replicas it holds; switch the period on after the graphs are added");
+    if (s->obs_at.every) return fail(ISINGMC_ERR_INVALID, "an observable series records on a period for this container (isingmc_observable_series_set_every): its columns are the replicas it holds; switch the period on after the graphs are added");
     TRY(use_device(s->g->device));
     if (s->packed) return pk_append(s, seed, initial_state);
     return add_replicas(s, 1, &seed, initial_state);
@@ -198,6 +199,7 @@ extern "C" int isingmc_states_set_timestep(isingmc_states *s, uint64_t t)
     s->t = t;
     s->mom_at.restart(t); // the sample points of the moment sums are counted from here
     s->osr_at.restart(t); // ... and those of a periodic overlap series (S21)
+    s->obs_at.restart(t); // ... and of a periodic observable series (S22)
     return ISINGMC_OK;
 }
 
@@ -1019,6 +1021,7 @@ int run_steps(isingmc_states *s, size_t timesteps, const double *betas, size_t b
               double *energies_per_step, float *device_ms, bool sync, double *final_energies)
 {
     if (s) TRY(osr_room_or_fail(s, timesteps));
+    if (s) TRY(obs_room_or_fail(s, timesteps));
     const bool may_strip = sync && timesteps >= 2 && may_use_strips(s) && strip_plan(s, timesteps).use;
     return with_strip_retry(s, may_strip, [&] {
         return run_steps_impl(s, timesteps, betas, beta_stride, energies_per_step, device_ms, sync, final_energies);
@@ -1485,9 +1488,9 @@ static int run_steps_impl(isingmc_states *s, size_t timesteps, const double *bet
         if (cluster || icm) nk = 1;
         else {
             if (const size_t every = s->cluster_every ? s->cluster_every : s->icm_every) nk = std::min<size_t>(nk, every - 1 - s->t % every);
-            // minimum tracking, the moment sums (S18) and a periodic overlap series (S21) cut the call too: a
-            // stretch ends with their next sample point
-            nk = std::min({nk, s->best_at.stretch(s->t), s->mom_at.stretch(s->t), s->osr_at.stretch(s->t)});
+            // minimum tracking, the moment sums (S18), a periodic overlap series (S21) and a periodic observable
+            // series (S22) cut the call too: a stretch ends with their next sample point
+            nk = std::min({nk, s->best_at.stretch(s->t), s->mom_at.stretch(s->t), s->osr_at.stretch(s->t), s->obs_at.stretch(s->t)});
             // (joined by the cluster step or the update before this stretch; the packed runner forks behind its table launches)
             if (P.lanes > 1 && s->n_lanes <= 1 && P.path != StepPath::Packed) TRY(lanes_fork(s, P.lanes));
         }
@@ -1512,6 +1515,7 @@ static int run_steps_impl(isingmc_states *s, size_t timesteps, const double *bet
         // a sample of the moment sums and a row of the periodic overlap series (S21): neither can be taken back
         TRY(sample(s->mom_at, moments_sample_enqueue));
         TRY(sample(s->osr_at, osr_sample_enqueue));
+        TRY(sample(s->obs_at, obs_sample_enqueue)); // ... nor can a row of the periodic observable series (S22)
     }
     if (s->n_lanes > 1) { const int jrc = lanes_join(s); if (rc == ISINGMC_OK) rc = jrc; }
     if (device_ms && rc == ISINGMC_OK) {

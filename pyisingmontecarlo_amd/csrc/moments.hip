@@ -232,6 +232,7 @@ extern "C" int isingmc_run_sampling_moments(isingmc_states *s, double beta, size
         if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
     }
     TRY(osr_room_or_fail(s, thermalization + sampling_freq * n_samples));
+    TRY(obs_room_or_fail(s, thermalization + sampling_freq * n_samples));
     TRY(use_device(s->g->device));
     TRY(mom_reserve(s, flags));
     TRY(mom_zero_enqueue(s));

@@ -339,6 +339,12 @@ static int between_sample(isingmc_states *a, isingmc_states *b)
             TRY(moments_sample_enqueue(s));
             s->mom_at.last_t = s->t;
         }
+    // ... and a periodic observable series by rung (S22) takes its row, by the same rule
+    for (isingmc_states *s : {a, b})
+        if (obs_sample_by_rung(s) && s->obs_at.due(s->t)) {
+            TRY(obs_sample_enqueue(s));
+            s->obs_at.last_t = s->t;
+        }
     return ISINGMC_OK;
 }
 
@@ -389,6 +395,9 @@ extern "C" int isingmc_icm_between(isingmc_states *a, isingmc_states *b, const u
                 if (std::memcmp(&a->betas[slots_a[p]], &b->betas[slots_b[p]], sizeof(double)) != 0)
                     return fail(ISINGMC_ERR_INVALID, "per-replica betas differ inside a pair: the two replicas of every pair need equal betas");
     }
+    // a periodic observable series by rung whose log has no room for the row behind this move: nothing is enqueued
+    for (const isingmc_states *s : {a, b})
+        if (obs_sample_by_rung(s)) TRY(obs_room_or_fail(s, 1));
     TRY(use_device(g->device));
     if (n_pairs == 0) { // time passes all the same
         a->t++;

@@ -12,58 +12,26 @@
 #include <algorithm>
 
 #include "host_logic.hpp"
+#include "lat_class_count.hpp"
 
 namespace isingmc {
 
 namespace {
 
-constexpr uint32_t OVC_LAT_WORDS = 4; // words of each plane per thread of the checkerboard kernels (a workgroup covers 1024 words)
-// a histogram bin counts at most the sites of both planes' words of one workgroup
-static_assert(uint64_t(256) * OVC_LAT_WORDS * 32 * 2 <= 0xFFFFFFFFull, "the LDS histogram's bins are 32 bits wide");
 static_assert(CLASS_SEGMENT_MAX == 256 * OVL_PK_ITER, "a segment is what one workgroup of ovl_pk_class_kernel counts");
 static_assert(CLASS_NONE == OVC_NO_CLASS, "host_logic.cpp class_segments drops the positions without a class");
 
-// the body of both checkerboard kernels: sa / sb = the planes of the pair's two replicas, acc = the pair's [n_tables][n_classes]
+// the body of both checkerboard kernels: sa / sb = the planes of the pair's two replicas, acc = the pair's [n_tables][n_classes];
+// the counting itself is lat_class_count (lat_class_count.hpp) over d = sa ^ sb, once per word
 __device__ __forceinline__ void ovl_lat_class_body(const uint32_t *__restrict__ sa, const uint32_t *__restrict__ sb, const LatGeom &g,
                                                    const LatClassDev &C, unsigned long long *__restrict__ acc)
 {
-    extern __shared__ __attribute__((aligned(16))) uint32_t hist[]; // [n_tables][n_classes]
-    const uint32_t bins = C.n_tables * C.n_classes;
-    for (uint32_t i = threadIdx.x; i < bins; i += 256) hist[i] = 0;
-    __syncthreads();
-    for (uint32_t i = 0; i < OVC_LAT_WORDS; i++) {
-        const uint32_t w = (blockIdx.x * OVC_LAT_WORDS + i) * 256 + threadIdx.x;
-        if (w >= g.wpp) break;
-        for (uint32_t plane = 0; plane < 2; plane++) {
-            const uint32_t pw = plane * g.wpp + w; // word of the replica, and of a table's layout
-            const uint32_t d = sa[pw] ^ sb[pw];
-            if (!d) continue;
-            for (uint32_t t = 0; t < C.n_tables; t++) {
-                const size_t tw = size_t(t) * 2 * g.wpp + pw;
-                uint32_t *h = hist + t * C.n_classes;
-                const uint32_t shared = C.word_cls[tw];
-                if (shared != OVC_MIXED) {
-                    if (shared != OVC_NO_CLASS) atomicAdd(h + shared, uint32_t(__popc(d)));
-                    continue;
-                }
-                const uint32_t *line = C.cls + tw * 32;
-                for (uint32_t rest = d; rest; rest &= rest - 1) {
-                    const uint32_t c = line[__ffs(rest) - 1];
-                    if (c != OVC_NO_CLASS) atomicAdd(h + c, 1u);
-                }
-            }
-        }
-    }
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < bins; i += 256) {
-        const uint32_t total = hist[i];
-        if (total) atomicAdd(acc + i, (unsigned long long)total);
-    }
+    lat_class_count([&](uint32_t pw) { return sa[pw] ^ sb[pw]; }, g, C, acc);
 }
 
 } // namespace
 
-// grid: (ceil(wpp / (256 OVC_LAT_WORDS)), n_pairs); pair p = replicas 2 p and 2 p + 1 of `state`; dynamic LDS: 4 bytes per bin
+// grid: (lat_class_blocks, n_pairs); pair p = replicas 2 p and 2 p + 1 of `state`; dynamic LDS: 4 bytes per bin
 __global__ __launch_bounds__(256) void ovl_lat_class_kernel(const uint32_t *__restrict__ state, const LatGeom g, const LatClassDev C,
                                                             unsigned long long *__restrict__ out)
 {
@@ -121,7 +89,7 @@ hipError_t overlap_class_launch_lattice(hipStream_t stream, const uint32_t *stat
                                         const uint32_t *slots_b, const LatGeom &g, const LatClassDev &C, uint32_t n_pairs,
                                         unsigned long long *out)
 {
-    const uint32_t blocks = (g.wpp + 256 * OVC_LAT_WORDS - 1) / (256 * OVC_LAT_WORDS);
+    const uint32_t blocks = lat_class_blocks(g);
     const uint32_t lds = C.n_tables * C.n_classes * uint32_t(sizeof(uint32_t));
     if (slots_a)
         hipLaunchKernelGGL(ovl_lat_class_between_kernel, dim3(blocks, n_pairs), dim3(256), lds, stream, state_a, state_b, slots_a, slots_b, g, C, out);

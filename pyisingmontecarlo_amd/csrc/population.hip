@@ -95,6 +95,7 @@ extern "C" int isingmc_pa_resample(isingmc_states *s, double dbeta, uint64_t see
     }
     if (s->mom_at.every) return fail(ISINGMC_ERR_INVALID, "moment sums are switched on for this container (isingmc_states_set_moments_every): a resampling replaces the replicas whose samples they hold; switch accumulation off first");
     if (s->osr_at.every) return fail(ISINGMC_ERR_INVALID, "an overlap series records on a period for this container (isingmc_overlap_series_set_every): a resampling replaces the replicas whose pairs it follows; switch the period off first");
+    if (s->obs_at.every) return fail(ISINGMC_ERR_INVALID, "an observable series records on a period for this container (isingmc_observable_series_set_every): a resampling replaces the replicas whose columns it follows; switch the period off first");
     TRY(use_device(s->g->device));
     TRY(pa_reserve(s));
     TRY(pa_resample_enqueue(s, dbeta, seed, step, s->d_pa_record));
@@ -118,6 +119,7 @@ extern "C" int isingmc_pa_run(isingmc_states *s, const double *betas, size_t n_b
     }
     if (s->mom_at.every) return fail(ISINGMC_ERR_INVALID, "moment sums are switched on for this container (isingmc_states_set_moments_every): a resampling replaces the replicas whose samples they hold; switch accumulation off first");
     if (s->osr_at.every) return fail(ISINGMC_ERR_INVALID, "an overlap series records on a period for this container (isingmc_overlap_series_set_every): a resampling replaces the replicas whose pairs it follows; switch the period off first");
+    if (s->obs_at.every) return fail(ISINGMC_ERR_INVALID, "an observable series records on a period for this container (isingmc_observable_series_set_every): a resampling replaces the replicas whose columns it follows; switch the period off first");
     TRY(use_device(s->g->device));
     TRY(pa_reserve(s));
     const size_t n_steps = n_betas - 1;

@@ -131,6 +131,14 @@ struct SeriesHandle {
     ~SeriesHandle() { isingmc_overlap_series_destroy(s); }
 };
 
+// an observable series with the class set it reads: the same order
+struct ObsSeriesHandle {
+    isingmc_observable_series *s = nullptr;
+    ClassesHandle classes;
+    size_t n_columns = 0, n_tables = 0, n_classes = 0;
+    ~ObsSeriesHandle() { isingmc_observable_series_destroy(s); }
+};
+
 struct EdgeArrays {
     std::vector<uint64_t> a, b;
     std::vector<double> j;
@@ -402,6 +410,55 @@ public:
         for (size_t k = 0; k < bond.size(); k++) bm[k] = double(bond[k]) / (double(n) * double(R));
         if (bonds) return py::make_tuple(energies, spins, bond_means);
         return py::make_tuple(energies, spins);
+    }
+
+    // extension: the sibling of run_monte_carlo_and_measure_spins for the two observables every study starts from.
+    // The trajectory and the bookkeeping of run_monte_carlo_sampling with these arguments -- thermalise, then timesteps sweeps with a
+    // sample every sampling_freq -- with the energy and the magnetisation of every sample logged on the device: nothing waits per
+    // sample and no configuration crosses the bus.  The host waits where the two isingmc_do_time_steps calls end (the thermalisation,
+    // then the run: the C ABI has no enqueue-only plain run to put the period's origin behind the thermalisation) and reads the log
+    // once.  Returns (energies f64[R, S], magnetisations
+    // int64[R, S]), plus by_class int64[R, S, T, K] with class tables as get_overlaps_by_class takes them.  One device: the log
+    // lives in one container.  Cluster periods set on this object apply.
+    py::tuple run_monte_carlo_and_measure_observables(double beta, size_t timesteps, size_t num_experiments, std::optional<size_t> thermalization_time,
+                                                      std::optional<size_t> sampling_freq, const py::object &classes)
+    {
+        require_classical();
+        const size_t therm = thermalization_time.value_or(0), freq = sampling_freq.value_or(1);
+        if (freq == 0) throw py::value_error("sampling_freq must be positive");
+        if (devices_.size() != 1) throw py::value_error("observable measurement runs on one device: the log lives in one container (set_device)");
+        const size_t S = timesteps / freq, R = num_experiments;
+        const ClassTables T = classes.is_none() ? ClassTables{} : class_tables(classes, py::none(), E_->nvars);
+        const size_t bins = T.n_tables * T.n_classes;
+        const std::shared_ptr<GraphHandle> gh = graph(0);
+        py::array_t<double> energies(std::vector<ssize_t>{ssize_t(R), ssize_t(S)});
+        py::array_t<int64_t> mags(std::vector<ssize_t>{ssize_t(R), ssize_t(S)});
+        py::array_t<int64_t> by_class(std::vector<ssize_t>{ssize_t(bins ? R : 0), ssize_t(S), ssize_t(T.n_tables), ssize_t(T.n_classes)});
+        double *e = energies.mutable_data();
+        int64_t *m = mags.mutable_data(), *c = by_class.mutable_data();
+        fan_out(num_experiments, 0, R, [&](isingmc_states *s, size_t) {
+            if (S == 0 || R == 0) return isingmc_do_time_steps(s, therm, &beta, 0, nullptr);
+            ObsSeriesHandle h; // (the series goes before the class set, and both before the container fan_out destroys)
+            int rc = ISINGMC_OK;
+            if (bins) rc = isingmc_site_classes_create(gh->g, T.cls.data(), T.n_tables, T.n_classes, &h.classes.c);
+            if (rc == ISINGMC_OK) rc = isingmc_observable_series_create(s, h.classes.c, ISINGMC_OBS_ENERGY | ISINGMC_OBS_MAGNETISATION, S, &h.s);
+            if (rc == ISINGMC_OK && therm) rc = isingmc_do_time_steps(s, therm, &beta, 0, nullptr);
+            if (rc == ISINGMC_OK) rc = isingmc_observable_series_set_every(h.s, freq); // the sample points are counted from here
+            if (rc == ISINGMC_OK) rc = isingmc_do_time_steps(s, S * freq, &beta, 0, nullptr);
+            std::vector<double> he(S * R);
+            std::vector<int64_t> hm(S * R), hc(S * R * bins);
+            if (rc == ISINGMC_OK) rc = isingmc_observable_series_get(h.s, 0, S, nullptr, he.data(), hm.data(), bins ? hc.data() : nullptr);
+            if (rc != ISINGMC_OK) return rc;
+            for (size_t k = 0; k < S; k++) // rows [S][R] -> [R][S]
+                for (size_t r = 0; r < R; r++) {
+                    e[r * S + k] = he[k * R + r];
+                    m[r * S + k] = hm[k * R + r];
+                    if (bins) std::copy(hc.begin() + (k * R + r) * bins, hc.begin() + (k * R + r + 1) * bins, c + (r * S + k) * bins);
+                }
+            return int(ISINGMC_OK);
+        });
+        if (bins) return py::make_tuple(energies, mags, by_class);
+        return py::make_tuple(energies, mags);
     }
 
     // lattice.rs:309-385
@@ -962,6 +1019,55 @@ public:
     {
         if (series_) check(isingmc_overlap_series_reset(series_->s));
     }
+    // extension: energy, magnetisation and magnetisation by class of every persistent replica, logged on the device
+    // once per sample.  set_measure_observables_every(k, classes, capacity): a row follows every k-th timestep from now on, without
+    // the host waiting (0: off, the rows stay); a call with k > 0 starts a new log of `capacity` rows.  classes: class tables as
+    // get_overlaps_by_class takes them, or None.  get_measured_observables() -> (timesteps uint64[n], energies f64[n, R],
+    // magnetisations int64[n, R], by_class int64[n, R, T, K] or None); reset_measured_observables() empties the log and keeps the
+    // period.  add_graph is refused while it is on.  ValueError where isingmc_observable_series_create / _set_every refuse.
+    void set_measure_observables_every(size_t k, const py::object &classes, size_t capacity)
+    {
+        if (k == 0) {
+            if (obs_series_) check(isingmc_observable_series_set_every(obs_series_->s, 0));
+            return;
+        }
+        auto h = std::make_unique<ObsSeriesHandle>();
+        if (!classes.is_none()) {
+            const ClassTables T = class_tables(classes, py::none(), E_.nvars);
+            check(isingmc_site_classes_create(st_->graph->g, T.cls.data(), T.n_tables, T.n_classes, &h->classes.c));
+            h->n_tables = T.n_tables;
+            h->n_classes = T.n_classes;
+        }
+        h->n_columns = isingmc_states_count(st_->s);
+        check(isingmc_observable_series_create(st_->s, h->classes.c, ISINGMC_OBS_ENERGY | ISINGMC_OBS_MAGNETISATION, capacity, &h->s));
+        obs_series_.reset(); // (the old log goes, and its period with it, before the new one takes the container's one period)
+        check(isingmc_observable_series_set_every(h->s, k));
+        obs_series_ = std::move(h);
+    }
+    py::tuple get_measured_observables()
+    {
+        if (!obs_series_) throw py::value_error("no observables are logged: call set_measure_observables_every(k) first");
+        const ObsSeriesHandle &h = *obs_series_;
+        size_t n = 0;
+        check(isingmc_observable_series_count(h.s, &n, nullptr));
+        const ssize_t N = ssize_t(n), R = ssize_t(h.n_columns);
+        py::array_t<uint64_t> t(std::vector<ssize_t>{N});
+        py::array_t<double> e(std::vector<ssize_t>{N, R});
+        py::array_t<int64_t> m(std::vector<ssize_t>{N, R});
+        py::array_t<int64_t> cls(std::vector<ssize_t>{h.n_tables ? N : 0, R, ssize_t(h.n_tables), ssize_t(h.n_classes)});
+        uint64_t *t_out = t.mutable_data();
+        double *e_out = e.mutable_data();
+        int64_t *m_out = m.mutable_data(), *c_out = h.n_tables ? cls.mutable_data() : nullptr;
+        {
+            py::gil_scoped_release nogil;
+            check(isingmc_observable_series_get(h.s, 0, n, t_out, e_out, m_out, c_out));
+        }
+        return py::make_tuple(t, e, m, h.n_tables ? py::object(cls) : py::object(py::none()));
+    }
+    void reset_measured_observables()
+    {
+        if (obs_series_) check(isingmc_observable_series_reset(obs_series_->s));
+    }
     // extension: Swendsen-Wang cluster steps on the persistent replicas (see Lattice.set_cluster_update_every); the graph is known
     // here, so one the cluster step does not serve raises ValueError at once
     void set_cluster_update_every(size_t k) { check(isingmc_states_set_cluster_every(st_->s, k)); }
@@ -1028,6 +1134,7 @@ private:
     std::shared_ptr<GraphHandle> graph_;
     std::shared_ptr<StatesHandle> st_;
     std::unique_ptr<SeriesHandle> series_; // (declared last: destroyed before the container it reads)
+    std::unique_ptr<ObsSeriesHandle> obs_series_; // (the same)
 };
 
 } // namespace
@@ -1067,6 +1174,8 @@ PYBIND11_MODULE(_py_monte_carlo, m)
         .def("run_monte_carlo_and_measure_spins", &Lattice::run_monte_carlo_and_measure_spins, "beta"_a, "timesteps"_a,
              "num_experiments"_a, "thermalization_time"_a = py::none(), "sampling_freq"_a = py::none(),
              "per_experiment"_a = true, "bonds"_a = false)
+        .def("run_monte_carlo_and_measure_observables", &Lattice::run_monte_carlo_and_measure_observables, "beta"_a, "timesteps"_a,
+             "num_experiments"_a, "thermalization_time"_a = py::none(), "sampling_freq"_a = py::none(), "classes"_a = py::none())
         .def("run_monte_carlo_annealing", &Lattice::run_monte_carlo_annealing, "betas"_a, "timesteps"_a,
              "num_experiments"_a, "only_basic_moves"_a = py::none(), "edge_move_importance_sampling"_a = py::none(),
              "replica_range"_a = py::none())
@@ -1114,6 +1223,9 @@ PYBIND11_MODULE(_py_monte_carlo, m)
              "capacity"_a = 4096)
         .def("get_measured_overlaps", &ClassicIsing::get_measured_overlaps)
         .def("reset_measured_overlaps", &ClassicIsing::reset_measured_overlaps)
+        .def("set_measure_observables_every", &ClassicIsing::set_measure_observables_every, "k"_a, "classes"_a = py::none(), "capacity"_a = 4096)
+        .def("get_measured_observables", &ClassicIsing::get_measured_observables)
+        .def("reset_measured_observables", &ClassicIsing::reset_measured_observables)
         .def("set_track_minimum", &ClassicIsing::set_track_minimum, "every"_a)
         .def("get_minimum", &ClassicIsing::get_minimum)
         .def("reset_minimum", &ClassicIsing::reset_minimum)

@@ -14,6 +14,7 @@
 //      integer test  max(X >> shift, 0) <= (Lambda_q * mant) >> 32  -- no exp, no f64, no 53-bit uniform per attempt.
 // The CPU oracle (engine E, oracle/ising_oracle.c) takes the same decisions spin by spin from a direct integer field sum.
 #pragma once
+#include "energy_from_counts.hpp"
 #include "general_types.hpp"
 #include "philox.hpp"
 #include "real_types.hpp"
@@ -342,8 +343,7 @@ __attribute__((unused)) static __global__ void rj_energy_from_counts_kernel(unsi
 {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r < n) {
-        const long long hi = (long long)meas[2 * size_t(first_slot + r)], lo = (long long)meas[2 * size_t(first_slot + r) + 1];
-        out[r] = (ldexp(double(-(hi / 2)), k_energy) + ldexp(double(-(lo / 2)), k_energy - 24)) + self_energy;
+        out[r] = rj_energy_of_counts(k_energy, self_energy, meas[2 * size_t(first_slot + r)], meas[2 * size_t(first_slot + r) + 1]);
     }
 }
 

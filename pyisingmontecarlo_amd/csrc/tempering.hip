@@ -78,6 +78,9 @@ extern "C" int isingmc_pt_detach(isingmc_states *s)
     if (s->osr_by_rung_live)
         return fail(ISINGMC_ERR_INVALID, "an overlap series made with ISINGMC_SERIES_BY_RUNG reads this ladder's permutation on the device "
                                          "(isingmc_overlap_series_destroy first)");
+    if (s->obs_by_rung_live)
+        return fail(ISINGMC_ERR_INVALID, "an observable series made with ISINGMC_OBS_BY_RUNG reads this ladder's permutation on the device "
+                                         "(isingmc_observable_series_destroy first)");
     TRY(use_device(s->g->device));
     HIP_TRY(hipStreamSynchronize(s->stream)); // enqueued rounds may still read the ladder
     TRY(strip_error(strip_check(s)));
@@ -195,6 +198,7 @@ extern "C" int isingmc_pt_run(isingmc_states *s, size_t timesteps, size_t swap_e
     if (!s || !s->pt_attached) return fail(ISINGMC_ERR_INVALID, "no ladder attached");
     if (swap_every == 0) return fail(ISINGMC_ERR_INVALID, "swap_every must be positive");
     if (s->pt_world != 1) return fail(ISINGMC_ERR_INVALID, "isingmc_pt_run is for a single rank: the all-gather of a sharded ladder sits between measure and swap");
+    TRY(obs_room_or_fail(s, timesteps)); // a periodic observable series that would run full in the WHOLE call: no round is enqueued
     TRY(use_device(s->g->device));
     const isingmc_graph *g = s->g;
     const size_t rounds = timesteps / swap_every, tail = timesteps % swap_every;
@@ -203,7 +207,8 @@ extern "C" int isingmc_pt_run(isingmc_states *s, size_t timesteps, size_t swap_e
                            s->R == s->pt.n_rungs && s->opt.pt_in_kernel != 0 &&
                            !s->best_at.every && // minimum tracking reads every round's energies: one launch per round
                            !s->mom_at.every &&  // sums per rung (S19) read the configurations and the permutation between the rounds: the same
-                           !s->osr_at.every;    // ... and so does a periodic overlap series (S21)
+                           !s->osr_at.every &&  // ... and so does a periodic overlap series (S21)
+                           !s->obs_at.every;    // ... and a periodic observable series (S22)
     if (in_kernel) {
         const size_t R = s->R, nk = rounds * swap_every;
         if (!s->d_pt_mail) {

@@ -3,6 +3,7 @@
 #include "tempering_types.hpp"
 
 #include "det_exp.hpp"
+#include "energy_from_counts.hpp"
 #include "packed_types.hpp"
 #include "philox.hpp"
 
@@ -84,7 +85,7 @@ __global__ void lat_energy_from_counts_kernel(unsigned long long *__restrict__ m
 {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r < n) {
-        out[r] = jabs * double(n_bonds - 2 * (long long)meas[2 * size_t(r)]);
+        out[r] = lat_energy_of_counts(jabs, n_bonds, meas[2 * size_t(r)]);
         meas[2 * size_t(r)] = 0; // the counters are left zeroed for the next measurement (no memset per round)
         meas[2 * size_t(r) + 1] = 0;
     }
@@ -97,7 +98,7 @@ __global__ void pk_energy_from_counts_kernel(const unsigned long long *__restric
                                              const double self_energy, double *__restrict__ out)
 {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < n) out[r] = jabs * (half_directed - double((long long)meas[2 * size_t(first_slot + r)])) + self_energy;
+    if (r < n) out[r] = pk_energy_of_counts(jabs, half_directed, self_energy, meas[2 * size_t(first_slot + r)]);
 }
 
 // Threshold tables of every group from per-slot thresholds (slot_thr[slot][m - 1] = T_m(beta of the slot), written by the exchange

@@ -395,6 +395,7 @@ class ClassicalTempering:
                           for s in (self._seed, self._seed ^ COPY_SEED_XOR)]
             self._icm_stats, self._icm_pending = None, False
         self._ovl_series, self._ovl_every, self._ovl_t0, self._ovl_classes = None, 0, 0, None   # overlap series
+        self._obs_series, self._obs_every, self._obs_t0 = None, 0, 0   # the observable series by rung, one per copy
         self._betas = []
         self._slot_seeds = []
         self._n_drawn = 0
@@ -605,19 +606,20 @@ class ClassicalTempering:
         return e, st, t, rungs
 
     # -- thermal averages <s_i> at every rung, summed on the device ------------------------------------------------
-    def _measured_spins_states(self):
-        """The container(s) that hold the sums per rung, one per copy; ValueError where the ladder cannot have them."""
+    def _per_rung_states(self, what="spin sums per rung", needs="set_moments_every", keeps="spin sums"):
+        """The container(s) that hold the sums (or the observable series) per rung, one per copy; ValueError where the ladder cannot
+        have them."""
         if self._devices is not None:
-            raise ValueError("spin sums per rung are for a ladder on one device: not with devices=[...] (a shard holds part of the ladder)")
+            raise ValueError(what + " are for a ladder on one device: not with devices=[...] (a shard holds part of the ladder)")
         if self._world > 1:
-            raise ValueError("spin sums per rung are for a ladder on one process: not inside a torch.distributed group of several ranks")
+            raise ValueError(what + " are for a ladder on one process: not inside a torch.distributed group of several ranks")
         self._materialise()
         copies = self._pair if self._pair is not None else [self]
         for c in copies:
-            if not hasattr(c._states, "set_moments_every"):
-                raise ValueError("this engine keeps no spin sums (set_moments_every)")
+            if not hasattr(c._states, needs):
+                raise ValueError("this engine keeps no %s (%s)" % (keeps, needs))
             if not c._on_stream:
-                raise ValueError("spin sums per rung need the ladder on the device's stream: this ladder takes the host swap step "
+                raise ValueError(what + " need the ladder on the device's stream: this ladder takes the host swap step "
                                  "(ISINGMC_PT_HOST=1, or a container that pt_can_attach refuses)")
         return [c._states for c in copies]
 
@@ -627,14 +629,14 @@ class ClassicalTempering:
         ladder is built here if it is not yet); no configuration, energy, random number or exchange decision changes."""
         if int(k) < 0:
             raise ValueError("k must not be negative")
-        for st in self._measured_spins_states():
+        for st in self._per_rung_states():
             st.set_moments_every(int(k), per_rung=True)
 
     def get_measured_spins(self):
         """(n_samples, means float64[G, N]): the thermal average of every spin at every rung over the samples taken, True = +1, in
         the order of get_betas() (zeros before the first sample).  copies=2: float64[2, G, N], one leading row per copy."""
         out = []
-        for st in self._measured_spins_states():
+        for st in self._per_rung_states():
             if not st.moments_per_rung:
                 raise ValueError("no spin sums per rung are held: call set_measure_spins_every(k) first")
             n, site, _ = st.moments()
@@ -647,8 +649,70 @@ class ClassicalTempering:
 
     def reset_measured_spins(self):
         """Sums and sample count back to zero; the period stays."""
-        for st in self._measured_spins_states():
+        for st in self._per_rung_states():
             st.reset_moments()
+
+    # -- energy and magnetisation of every rung per sample, logged on the device (DESIGN.md S22) --------------------------------------
+    def _obs_states(self):
+        return self._per_rung_states("observables per rung", "observable_series", "observable series")
+
+    def set_measure_observables_every(self, k, classes=None, capacity=4096):
+        """A row of the observable series follows each k-th timestep from now on (0: off, the rows stay): per rung the energy, the
+        magnetisation and, with class tables (as site_classes takes them), the magnetisation by class of the configuration that
+        holds that rung at that moment, before any exchange round that follows the timestep.  The period lives in the library, one
+        series by rung per copy; a call with k > 0 starts a new log of `capacity` rows.  No configuration, energy, random number or
+        exchange decision changes."""
+        if int(k) < 0:
+            raise ValueError("k must not be negative")
+        if int(k) == 0:
+            for series in self._obs_series or []:
+                series.set_every(0)
+            self._obs_every = 0
+            return
+        states = self._obs_states()
+        for series in self._obs_series or []:
+            series.close()   # (the old logs go, and their periods with them, before the new ones take the containers' periods)
+        self._obs_series = None
+        made = []
+        for st in states:
+            cls = classes if classes is None or isinstance(classes, _capi.SiteClasses) else _capi.SiteClasses(st.graph, classes)
+            series = st.observable_series(classes=cls, by_rung=True, capacity=int(capacity))
+            series.set_every(int(k))
+            made.append(series)
+        self._obs_series, self._obs_every, self._obs_t0 = made, int(k), self._t
+
+    def _obs_room(self, T):
+        """Before a call of T timesteps moves anything: ValueError when the rows of the call would not fit the logs.  (The library
+        refuses each of its calls by the same count; a call of this class is several of them, on two copies.)"""
+        if not self._obs_every or not self._obs_series:
+            return
+        k, since = self._obs_every, self._t - self._obs_t0
+        samples = (since + int(T)) // k - since // k
+        for series in self._obs_series:
+            room = series.capacity - series.count
+            if samples > room:
+                raise ValueError("the observable series of this ladder would run full: the call takes %d samples and the log has room "
+                                 "for %d of its %d rows (get_measured_observables, then reset_measured_observables; or switch the "
+                                 "period off)" % (samples, room, series.capacity))
+
+    def get_measured_observables(self):
+        """(timesteps uint64[n], energy float64[n, G], magnetisation int64[n, G], by_class int64[n, G, T, K] or None), the columns
+        in the order of get_betas().  copies=2: the three arrays get a leading axis of 2, one entry per copy.  One wait per copy."""
+        if not self._obs_series:
+            raise ValueError("no observables are logged: call set_measure_observables_every(k) first")
+        out = [series.get() for series in self._obs_series]
+        if self._pair is None:
+            return out[0]
+        if not np.array_equal(out[0][0], out[1][0]):   # (both copies stand at one timestep with one period)
+            raise RuntimeError("the two copies of the ladder hold rows of different timesteps")
+        return (out[0][0],) + tuple(None if a is None else np.stack([a, b]) for a, b in zip(out[0][1:], out[1][1:]))
+
+    def reset_measured_observables(self):
+        """The row count back to zero; the period stays."""
+        if not self._obs_series:
+            raise ValueError("no observables are logged: call set_measure_observables_every(k) first")
+        for series in self._obs_series:
+            series.reset()
 
     # -- what choosing the ladder needs: pair acceptance, replica flow, energy sums, kept by the exchange rounds (DESIGN.md S20) ------
     def set_ladder_statistics(self, on=True):
@@ -776,6 +840,7 @@ class ClassicalTempering:
             self._materialise()
         if t <= 0:
             return
+        self._obs_room(t)
         t, f, lads = int(t), int(replica_swap_freq or 0), self._lads
         if not f and self._pair is None:
             self._t += t
@@ -809,6 +874,7 @@ class ClassicalTempering:
         energies float64[2, G], one row per copy.
         """
         self._materialise()
+        self._obs_room(timesteps)
         f, sampling_freq = _frequencies(replica_swap_freq, sampling_freq)
         lads, G, S = self._lads, len(self._betas), timesteps // sampling_freq
         perms = [lad.perm() for lad in lads]   # (on the device's stream the device owns the ladder state)
