@@ -491,25 +491,17 @@ class SiteClasses:
 
 
 class _SeriesHandle:
-    """The handle of an overlap series, shared by the OverlapSeries and by everything it reads (its containers, its class set):
-    whichever of them goes first destroys the series.  (Not a weak reference to the OverlapSeries: the garbage collector clears
-    those before it finalises a cycle, and the series must go before what it reads in whatever order that happens.)"""
+    """The handle of an overlap or observable series, shared by the series object and by everything it reads (its containers, its
+    class set): whichever of them goes first destroys the series.  (Not a weak reference to the series object: the garbage collector
+    clears those before it finalises a cycle, and the series must go before what it reads in whatever order that happens.)"""
 
-    destroy = "isingmc_overlap_series_destroy"
-
-    def __init__(self):
-        self.h = _vp()
+    def __init__(self, destroy):
+        self.h, self.destroy = _vp(), destroy
 
     def close(self):
         if self.h:
             getattr(lib(), self.destroy)(self.h)
             self.h = _vp()
-
-
-class _ObservableSeriesHandle(_SeriesHandle):
-    """... and the handle of an observable series, by the same rule."""
-
-    destroy = "isingmc_observable_series_destroy"
 
 
 def _close_series(owner):
@@ -518,27 +510,74 @@ def _close_series(owner):
         handle.close()
 
 
-class OverlapSeries:
+class _DeviceSeries:
+    """What the two device-resident logs share: the handle and its registration with the objects the series reads, the period, the
+    row count and the capacity.  _PREFIX names the entry points of the subclass."""
+
+    def _create(self, owners, *args):
+        """isingmc_<kind>_series_create(*args, &handle); the owners given (None: absent) destroy the series when they go first."""
+        self._handle = _SeriesHandle(self._PREFIX + "destroy")
+        _check(self._call("create", *args, C.byref(self._handle.h)))
+        for owner in owners:
+            if owner is not None:
+                owner.__dict__["_series"] = [h for h in owner.__dict__.get("_series", []) if h.h] + [self._handle]
+
+    def _call(self, name, *args):
+        return getattr(lib(), self._PREFIX + name)(*args)
+
+    @property
+    def _h(self):
+        return self._handle.h
+
+    def set_every(self, k):
+        """A record follows every timestep t > t0 (now) with (t - t0) % k == 0, inside the run calls; 0: off, the rows stay."""
+        _check(self._call("set_every", self._h, int(k)))
+
+    @property
+    def count(self):
+        n = C.c_size_t()
+        _check(self._call("count", self._h, C.byref(n), None))
+        return int(n.value)
+
+    @property
+    def capacity(self):
+        n = C.c_size_t()
+        _check(self._call("count", self._h, None, C.byref(n)))
+        return int(n.value)
+
+    def _rows(self, first, n):
+        first = int(first)
+        return first, max(self.count - first, 0) if n is None else int(n)
+
+    def reset(self):
+        """The row count back to 0 (enqueue only); the period stays."""
+        _check(self._call("reset", self._h))
+
+    def close(self):
+        self._handle.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class OverlapSeries(_DeviceSeries):
     """isingmc_overlap_series: a device-resident log with one row of overlaps per sample.  record() and the
     periodic records inside the step loop only enqueue; get() reads the log, once, afterwards.  Made by States.overlap_series."""
 
+    _PREFIX = "isingmc_overlap_series_"
+
     def __init__(self, a, other=None, n_pairs=None, classes=None, link=True, by_rung=False, capacity=4096):
         self._a, self._b, self._classes = a, other, classes  # keeps them alive
-        self._handle = _SeriesHandle()
         if n_pairs is None:
             n_pairs = a.count if by_rung else a.count // 2 if other is None or other is a else min(a.count, other.count)
         self.n_pairs, self.link, self.by_rung = int(n_pairs), bool(link), bool(by_rung)
         self.n_tables, self.n_classes = (classes.n_tables, classes.n_classes) if classes is not None else (0, 0)
         flags = (SERIES_LINK if link else 0) | (SERIES_BY_RUNG if by_rung else 0)
-        _check(lib().isingmc_overlap_series_create(a._h, None if other is None else other._h, self.n_pairs,
-                                                   None if classes is None else classes._h, flags, int(capacity), C.byref(self._handle.h)))
-        for owner in (a, other, classes):
-            if owner is not None:
-                owner.__dict__["_series"] = [h for h in owner.__dict__.get("_series", []) if h.h] + [self._handle]
-
-    @property
-    def _h(self):
-        return self._handle.h
+        self._create((a, other, classes), a._h, None if other is None else other._h, self.n_pairs,
+                     None if classes is None else classes._h, flags, int(capacity))
 
     def record(self, slots_a=None, slots_b=None):
         """One row for the configurations as they are; pairs as States.overlaps takes them.  Enqueue only."""
@@ -547,118 +586,51 @@ class OverlapSeries:
         sa, sb = _arr(slots_a, np.uint32), _arr(slots_b, np.uint32)
         if sa is not None and (sa.ndim != 1 or sa.shape != sb.shape or sa.size != self.n_pairs):
             raise ValueError("the slot tables must be two one-dimensional arrays of n_pairs entries")
-        _check(lib().isingmc_overlap_series_record(self._h, _p(sa), _p(sb)))
-
-    def set_every(self, k):
-        """A record follows every timestep t > t0 (now) with (t - t0) % k == 0, inside the run calls; 0: off, the rows stay."""
-        _check(lib().isingmc_overlap_series_set_every(self._h, int(k)))
-
-    @property
-    def count(self):
-        n = C.c_size_t()
-        _check(lib().isingmc_overlap_series_count(self._h, C.byref(n), None))
-        return int(n.value)
-
-    @property
-    def capacity(self):
-        n = C.c_size_t()
-        _check(lib().isingmc_overlap_series_count(self._h, None, C.byref(n)))
-        return int(n.value)
+        _check(self._call("record", self._h, _p(sa), _p(sb)))
 
     def get(self, first=0, n=None):
         """(timesteps uint64[n], spin int64[n, P], link int64[n, P] or None, by_class int64[n, P, T, C] or None) of the rows
         [first, first + n) (n=None: all from `first` on).  Synchronises; changes nothing."""
-        first = int(first)
-        n = max(self.count - first, 0) if n is None else int(n)
+        first, n = self._rows(first, n)
         P = self.n_pairs
         t = np.zeros(n, dtype=np.uint64)
         spin = np.zeros((n, P), dtype=np.int64)
         lnk = np.zeros((n, P), dtype=np.int64) if self.link else None
         cls = np.zeros((n, P, self.n_tables, self.n_classes), dtype=np.int64) if self.n_tables else None
-        _check(lib().isingmc_overlap_series_get(self._h, first, n, _p(t), _p(spin), _p(lnk), _p(cls)))
+        _check(self._call("get", self._h, first, n, _p(t), _p(spin), _p(lnk), _p(cls)))
         return t, spin, lnk, cls
 
-    def reset(self):
-        """The row count back to 0 (enqueue only); the period stays."""
-        _check(lib().isingmc_overlap_series_reset(self._h))
 
-    def close(self):
-        self._handle.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class ObservableSeries:
+class ObservableSeries(_DeviceSeries):
     """isingmc_observable_series: a device-resident log with one row per sample -- per column (replica slot, or rung with by_rung)
     the energy, the magnetisation and the magnetisation by site class.  record() and the periodic records inside
     the step loop only enqueue; get() reads the log, once, afterwards.  Made by States.observable_series."""
 
+    _PREFIX = "isingmc_observable_series_"
+
     def __init__(self, a, classes=None, energy=True, magnetisation=True, by_rung=False, capacity=4096):
         self._a, self._classes = a, classes  # keeps them alive
-        self._handle = _ObservableSeriesHandle()
         self.energy, self.magnetisation, self.by_rung = bool(energy), bool(magnetisation), bool(by_rung)
         self.n_columns = a.count
         self.n_tables, self.n_classes = (classes.n_tables, classes.n_classes) if classes is not None else (0, 0)
         flags = (OBS_ENERGY if energy else 0) | (OBS_MAGNETISATION if magnetisation else 0) | (OBS_BY_RUNG if by_rung else 0)
-        _check(lib().isingmc_observable_series_create(a._h, None if classes is None else classes._h, flags, int(capacity),
-                                                      C.byref(self._handle.h)))
-        for owner in (a, classes):
-            if owner is not None:
-                owner.__dict__["_series"] = [h for h in owner.__dict__.get("_series", []) if h.h] + [self._handle]
-
-    @property
-    def _h(self):
-        return self._handle.h
+        self._create((a, classes), a._h, None if classes is None else classes._h, flags, int(capacity))
 
     def record(self):
         """One row for the configurations as they are.  Enqueue only."""
-        _check(lib().isingmc_observable_series_record(self._h))
-
-    def set_every(self, k):
-        """A record follows every timestep t > t0 (now) with (t - t0) % k == 0, inside the run calls; 0: off, the rows stay."""
-        _check(lib().isingmc_observable_series_set_every(self._h, int(k)))
-
-    @property
-    def count(self):
-        n = C.c_size_t()
-        _check(lib().isingmc_observable_series_count(self._h, C.byref(n), None))
-        return int(n.value)
-
-    @property
-    def capacity(self):
-        n = C.c_size_t()
-        _check(lib().isingmc_observable_series_count(self._h, None, C.byref(n)))
-        return int(n.value)
+        _check(self._call("record", self._h))
 
     def get(self, first=0, n=None):
         """(timesteps uint64[n], energy float64[n, C] or None, magnetisation int64[n, C] or None, by_class int64[n, C, T, K] or
         None) of the rows [first, first + n) (n=None: all from `first` on).  Synchronises once; changes nothing."""
-        first = int(first)
-        n = max(self.count - first, 0) if n is None else int(n)
+        first, n = self._rows(first, n)
         cols = self.n_columns
         t = np.zeros(n, dtype=np.uint64)
         e = np.zeros((n, cols), dtype=np.float64) if self.energy else None
         m = np.zeros((n, cols), dtype=np.int64) if self.magnetisation else None
         cls = np.zeros((n, cols, self.n_tables, self.n_classes), dtype=np.int64) if self.n_tables else None
-        _check(lib().isingmc_observable_series_get(self._h, first, n, _p(t), _p(e), _p(m), _p(cls)))
+        _check(self._call("get", self._h, first, n, _p(t), _p(e), _p(m), _p(cls)))
         return t, e, m, cls
-
-    def reset(self):
-        """The row count back to 0 (enqueue only); the period stays."""
-        _check(lib().isingmc_observable_series_reset(self._h))
-
-    def close(self):
-        self._handle.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class States:

@@ -64,14 +64,14 @@ extern "C" int isingmc_states_set_track_best(isingmc_states *s, size_t every)
         TRY(use_device(s->g->device));
         TRY(best_reserve(s));
     }
-    s->best_at.every = every;
+    s->rec[REC_BEST].every = every;
     return ISINGMC_OK;
 }
 
 extern "C" int isingmc_states_track_best(const isingmc_states *s, size_t *every_out)
 {
     if (!s || !every_out) return fail(ISINGMC_ERR_INVALID, "NULL argument");
-    *every_out = s->best_at.every;
+    *every_out = s->rec[REC_BEST].every;
     return ISINGMC_OK;
 }
 

@@ -3,6 +3,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -122,6 +123,23 @@ struct ClassSegments {
     std::vector<uint64_t> sizes;
 };
 ClassSegments class_segments(const uint32_t *site, size_t n_pos, const uint32_t *cls, size_t nvars, size_t n_tables, size_t n_classes);
+
+// The sample points of a measurement the step loop takes on a period (the recorder table of recorders.hip).
+// A sample follows every timestep t > t0 with (t - t0) % every == 0.  A call repeated after a strip launch gave up
+// (with_strip_retry) takes no sample twice: the samples up to replay_to were taken by the attempt that is repeated (last_t: the
+// timestep of the last sample the step loop took).
+struct Periodic {
+    size_t every = 0; // 0 = off
+    uint64_t t0 = 0, last_t = 0, replay_to = 0;
+    uint64_t phase(uint64_t t) const { return (t - t0) % every; }
+    // timesteps from t up to and including the next sample point (no bound while off)
+    size_t stretch(uint64_t t) const { return every ? size_t(every - phase(t)) : std::numeric_limits<size_t>::max(); }
+    bool due(uint64_t t) const { return every && phase(t) == 0 && t > replay_to; }
+    uint64_t points(uint64_t t, uint64_t n) const { return (t - t0 + n) / every - (t - t0) / every; } // sample points in (t, t + n]
+    void restart(uint64_t t) { t0 = t; last_t = 0; } // the sample points are counted from t
+    // around the repeat of a call that started at timestep t: it skips the samples already taken
+    void replay_since(uint64_t t) { replay_to = every && last_t > t ? last_t : 0; }
+};
 
 // packed checkerboard planes of one replica -> W*H bytes in site order (16 bytes per SSE2 store)
 void unpack_lattice(uint32_t W, uint32_t H, const uint32_t *words, uint8_t *spins);

@@ -7,6 +7,7 @@
 //                  (isingmc_site_classes_*, isingmc_overlaps_by_class); the overlap core they share with the series
 //   overlap_series.hip  the device-resident log of overlap measurements, one row per sample (isingmc_overlap_series_*)
 //   observable_series.hip  the device-resident log of energy and magnetisation per sample (isingmc_observable_series_*)
+//   recorders.hip  the table of the measurements the step loop takes on a period, and the log core of the two series
 //   best.hip       each replica's lowest-energy configuration, kept on the device (isingmc_best_*)
 //   moments.hip    per-site spin sums and per-bond sums over the samples of a run (isingmc_moments_*)
 //   sampling.hip   get_states and the double-buffered sampling pipeline
@@ -249,21 +250,9 @@ struct StepPreset {
     const RjBeta *rj = nullptr;        // real-coupling packed path
 };
 
-// A measurement the step loop takes on a period: a sample follows every timestep t > t0 with (t - t0) % every == 0.  A call
-// repeated after a strip launch gave up (with_strip_retry) takes no sample twice: the samples up to replay_to were taken by the
-// attempt that is repeated (last_t: the timestep of the last sample the step loop took).
-struct Periodic {
-    size_t every = 0; // 0 = off
-    uint64_t t0 = 0, last_t = 0, replay_to = 0;
-    uint64_t phase(uint64_t t) const { return (t - t0) % every; }
-    // timesteps from t up to and including the next sample point (no bound while off)
-    size_t stretch(uint64_t t) const { return every ? size_t(every - phase(t)) : std::numeric_limits<size_t>::max(); }
-    bool due(uint64_t t) const { return every && phase(t) == 0 && t > replay_to; }
-    uint64_t points(uint64_t t, uint64_t n) const { return (t - t0 + n) / every - (t - t0) / every; } // sample points in (t, t + n]
-    void restart(uint64_t t) { t0 = t; last_t = 0; } // the sample points are counted from t
-    // around the repeat of a call that started at timestep t: it skips the samples already taken
-    void replay_since(uint64_t t) { replay_to = every && last_t > t ? last_t : 0; }
-};
+// The measurements the step loop takes on a period (recorders.hip holds their table), in the order it samples them
+enum Recorder { REC_BEST, REC_MOMENTS, REC_OVERLAPS, REC_OBSERVABLES, REC_COUNT };
+struct SeriesLog;
 
 struct isingmc_states {
     isingmc_graph *g = nullptr;
@@ -381,8 +370,6 @@ struct isingmc_states {
     bool pa_families_set = false;   // d_pa_family holds the table (else: the identity)
     // each replica's lowest-energy configuration (isingmc_best_*): allocated when tracking is switched on (or by the
     // first isingmc_best_update) for the replicas the container holds then, and kept
-    Periodic best_at;                 // an update follows every timestep after which t % every == 0 (t0 stays 0, no replay guard:
-                                      // a repeated call finds the same records again and changes none)
     DevBlock<uint32_t> d_best_state; // as large as d_state, same layout; padding positions and unowned bits of a packed container
     size_t best_state_words = 0;      // hold no defined value (cleared once, so that the raw read-out is deterministic)
     size_t best_cap = 0;              // replicas the records below hold
@@ -393,7 +380,6 @@ struct isingmc_states {
     DevBlock<unsigned long long> d_best_count; // improvements so far
     // per-site and per-bond sums over the samples of a run (isingmc_moments_*): allocated when accumulation is
     // switched on (or by the first isingmc_moments_accumulate) for the replicas the container holds then, and kept
-    Periodic mom_at;             // the sample points of the step loop
     unsigned mom_flags = 0;      // ISINGMC_MOMENTS_* of the sums held
     uint64_t mom_n = 0;          // samples in the sums
     bool mom_have = false;       // the blocks below are allocated, for mom_R replicas
@@ -403,16 +389,12 @@ struct isingmc_states {
     DevBlock<uint32_t> d_mom_planes, d_mom_totals;        // per-replica mode: mom_k time planes of the state's shape, 32-bit totals
     int mom_k = 0;
     uint32_t mom_pending = 0;    // samples in the time planes since the last flush (< 2^mom_k)
-    // the overlap series of this container that records on a period (isingmc_overlap_series_set_every): a row at
-    // every sample point of osr_at
-    isingmc_overlap_series *osr = nullptr;
-    Periodic osr_at;
-    size_t osr_by_rung_live = 0; // live series that read this container's ladder permutation on the device: no isingmc_pt_detach
-    // the observable series of this container that records on a period (isingmc_observable_series_set_every): a row
-    // at every sample point of obs_at
-    isingmc_observable_series *obs = nullptr;
-    Periodic obs_at;
-    size_t obs_by_rung_live = 0; // live observable series that read the ladder permutation on the device: no isingmc_pt_detach
+    // the sample points of the periodic recorders.  REC_BEST: an update follows every timestep after which t % every == 0 (t0 stays
+    // 0).  REC_OVERLAPS / REC_OBSERVABLES: a row of series[...], the one series of its kind that records on a period
+    Periodic rec[REC_COUNT];
+    SeriesLog *series[REC_COUNT] = {};
+    size_t osr_by_rung_live = 0; // live overlap series that read this container's ladder permutation on the device: no isingmc_pt_detach
+    size_t obs_by_rung_live = 0; // ... and live observable series that do
     bool strip_guard = false; // inside with_strip_retry: a strip launch is checked before an update may keep what it left
 
     ~isingmc_states()
@@ -659,16 +641,54 @@ IM_INTERNAL int overlap_enqueue(const OverlapJob &J, const OverlapPlan &P, const
 IM_INTERNAL int overlap_class_enqueue(const OverlapJob &J, const OverlapPlan &P, const OverlapWork &W, OverlapSink sink);
 IM_INTERNAL int overlap_lanes_join(isingmc_states *a, isingmc_states *b); // both containers' sweeps so far on their main streams
 
-// ---- overlap_series.hip (the device-resident log of overlap measurements) ----------------------------------------------------
-// before a run of `timesteps` timesteps enqueues anything: fails when the periodic series of the container would run full in it
-IM_INTERNAL int osr_room_or_fail(const isingmc_states *s, size_t timesteps);
-IM_INTERNAL int osr_sample_enqueue(isingmc_states *s); // enqueue: one row of the container's periodic series at timestep s->t
+// ---- recorders.hip (the periodic recorders as one table; the log core of the two series) -----------------------------------------
+// Every recorder due at timestep s->t takes its sample, unless the attempt this call repeats took it already (with_strip_retry).
+// after_strip: a call that may be repeated first waits for the strip launch before and checks it.  The status returned is that wait's
+// alone; everything else goes into rc, and an error in rc ends the sampling.
+IM_INTERNAL int recorders_sample(isingmc_states *s, bool after_strip, int &rc);
+IM_INTERNAL int recorder_sample_now(isingmc_states *s, Recorder which); // that one recorder, if timestep s->t is its sample point
+IM_INTERNAL int recorders_room_or_fail(const isingmc_states *s, size_t timesteps); // before a run enqueues anything: would a series run full in it?
+IM_INTERNAL void recorders_restart(isingmc_states *s, uint64_t t);       // isingmc_states_set_timestep: the sample points are counted from t
+IM_INTERNAL void recorders_replay_since(isingmc_states *s, uint64_t t0); // around the repeat of a call that started at t0
+enum class RecorderRefusal { Append, Resample };
+IM_INTERNAL const char *recorders_refusal(const isingmc_states *s, RecorderRefusal what); // the sentence of the first recorder that is on and objects, or nullptr
+static inline size_t recorders_stretch(const isingmc_states *s) // timesteps from s->t up to and including the next sample point
+{
+    size_t n = std::numeric_limits<size_t>::max();
+    for (const Periodic &p : s->rec) n = std::min(n, p.stretch(s->t));
+    return n;
+}
+static inline bool recorders_any_on(const isingmc_states *s) { return recorders_stretch(s) != std::numeric_limits<size_t>::max(); } // (a sample point is ahead)
 
-// ---- observable_series.hip (the device-resident log of energy and magnetisation per sample) ---------------------------------
-// before a run of `timesteps` timesteps enqueues anything: fails when the periodic series of the container would run full in it
-IM_INTERNAL int obs_room_or_fail(const isingmc_states *s, size_t timesteps);
-IM_INTERNAL int obs_sample_enqueue(isingmc_states *s); // enqueue: one row of the container's periodic series at timestep s->t
-IM_INTERNAL bool obs_sample_by_rung(const isingmc_states *s); // the container's periodic series is one by rung
+// The log of a series: `capacity` rows of `row` 8-byte entries on the device and the timestep of every row held.  Both series derive
+// from it; `noun` ("overlap" / "observable") names them in the sentences, a->series[which] is the one that records on a period.
+struct SeriesLog {
+    isingmc_states *const a;
+    const Recorder which;
+    const char *const noun;
+    size_t capacity = 0, row = 0;
+    DevBlock<unsigned long long> d_log; // [capacity][row]
+    std::vector<uint64_t> timesteps;    // of the rows: its size is the row count
+    SeriesLog(isingmc_states *a_, Recorder which_, const char *noun_) : a(a_), which(which_), noun(noun_) {}
+    unsigned long long *next_row() const { return d_log.get() + timesteps.size() * row; }
+    bool periodic() const { return a->series[which] == this; }
+    int period_off() { if (periodic()) { a->series[which] = nullptr; a->rec[which].every = 0; } return ISINGMC_OK; } // the rows stay
+    int period_on(size_t every) { a->series[which] = this; a->rec[which].every = every; a->rec[which].restart(a->t); return ISINGMC_OK; }
+};
+IM_INTERNAL int series_budget_or_fail(const char *noun, long long budget_option, size_t capacity, unsigned long long row_bytes);
+IM_INTERNAL int series_full_or_ok(const SeriesLog *L);          // fails when the log holds `capacity` rows
+IM_INTERNAL int series_room_or_fail(const isingmc_states *s, Recorder which, size_t timesteps);
+IM_INTERNAL int series_period_free_or_fail(const SeriesLog *L); // fails when another series of the kind holds the container's period
+IM_INTERNAL int series_count(const SeriesLog *L, size_t *n_out, size_t *capacity_out);
+IM_INTERNAL int series_reset(SeriesLog *L);
+// get: rows in range, `refusal` (the caller's own, or nullptr), the wait for a's stream, the strip check; then the timesteps and rows
+IM_INTERNAL int series_read(SeriesLog *L, size_t first, size_t n, const char *refusal, uint64_t *timesteps_out, bool want_rows, std::vector<unsigned long long> &rows);
+IM_INTERNAL void series_unregister(SeriesLog *L); // destroy: drains a's stream and gives the period up
+
+// ---- overlap_series.hip / observable_series.hip (the device-resident logs, one row per sample) ----------------------------------
+IM_INTERNAL int osr_sample_enqueue(isingmc_states *s); // enqueue: one row of the container's periodic series at timestep s->t
+IM_INTERNAL int obs_sample_enqueue(isingmc_states *s);
+IM_INTERNAL bool obs_sample_by_rung(const isingmc_states *s); // the container's periodic observable series is one by rung
 
 // ---- nonlocal.hip (Swendsen-Wang steps and isoenergetic cluster moves) -------------------------------------------------------
 // What the non-local steps of ONE run_steps call keep between them: filled by the call's first such step, the device blocks in the
@@ -715,11 +735,9 @@ static int with_strip_retry(isingmc_states *s, bool may_strip, F &&call)
     s->strip_guard = false;
     if (rc != STRIP_TIMED_OUT) return rc;
     TRY(snapshot_restore(s));
-    s->mom_at.replay_since(t0); // (the repeat skips the samples already in the sums
-    s->osr_at.replay_since(t0); // ... and the rows already in the overlap series
-    s->obs_at.replay_since(t0); // ... and in the observable series)
+    recorders_replay_since(s, t0); // (the repeat skips the samples already in the sums and the rows already in the two series)
     s->t = t0;
     const int rc2 = strip_error(call());
-    s->mom_at.replay_to = s->osr_at.replay_to = s->obs_at.replay_to = 0;
+    for (Periodic &p : s->rec) p.replay_to = 0;
     return rc2;
 }

@@ -145,10 +145,7 @@ extern "C" int isingmc_states_append(isingmc_states *s, uint64_t seed, const uin
 {
     if (!s) return fail(ISINGMC_ERR_INVALID, "NULL states");
     if (s->has_betas) return fail(ISINGMC_ERR_INVALID, "clear the per-replica betas before appending replicas");
-    if (s->best_at.every) return fail(ISINGMC_ERR_INVALID, "minimum tracking is switched on for this container (isingmc_states_set_track_best): its records are sized for the replicas it holds; switch tracking on after the graphs are added");
-    if (s->mom_at.every) return fail(ISINGMC_ERR_INVALID, "moment sums are switched on for this container (isingmc_states_set_moments_every): they are sized for the replicas it holds; switch accumulation on after the graphs are added");
-    if (s->osr_at.every) return fail(ISINGMC_ERR_INVALID, "an overlap series records on a period for this container (isingmc_overlap_series_set_every): its pairs are those of the replicas it holds; switch the period on after the graphs are added");
-    if (s->obs_at.every) return fail(ISINGMC_ERR_INVALID, "an observable series records on a period for this container (isingmc_observable_series_set_every): its columns are the replicas it holds; switch the period on after the graphs are added");
+    if (const char *why = recorders_refusal(s, RecorderRefusal::Append)) return fail(ISINGMC_ERR_INVALID, why);
     TRY(use_device(s->g->device));
     if (s->packed) return pk_append(s, seed, initial_state);
     return add_replicas(s, 1, &seed, initial_state);
@@ -197,9 +194,7 @@ extern "C" int isingmc_states_set_timestep(isingmc_states *s, uint64_t t)
     TRY(use_device(s->g->device));
     HIP_TRY(hipStreamSynchronize(s->stream));
     s->t = t;
-    s->mom_at.restart(t); // the sample points of the moment sums are counted from here
-    s->osr_at.restart(t); // ... and those of a periodic overlap series (S21)
-    s->obs_at.restart(t); // ... and of a periodic observable series (S22)
+    recorders_restart(s, t); // the sample points of the moment sums and of the periodic series (S21, S22) are counted from here
     return ISINGMC_OK;
 }
 
@@ -1020,8 +1015,7 @@ bool may_use_strips(const isingmc_states *s)
 int run_steps(isingmc_states *s, size_t timesteps, const double *betas, size_t beta_stride,
               double *energies_per_step, float *device_ms, bool sync, double *final_energies)
 {
-    if (s) TRY(osr_room_or_fail(s, timesteps));
-    if (s) TRY(obs_room_or_fail(s, timesteps));
+    if (s) TRY(recorders_room_or_fail(s, timesteps));
     const bool may_strip = sync && timesteps >= 2 && may_use_strips(s) && strip_plan(s, timesteps).use;
     return with_strip_retry(s, may_strip, [&] {
         return run_steps_impl(s, timesteps, betas, beta_stride, energies_per_step, device_ms, sync, final_energies);
@@ -1467,19 +1461,6 @@ static int run_steps_impl(isingmc_states *s, size_t timesteps, const double *bet
     } lane_join{s};
     if (P.lanes > 1 && P.path != StepPath::Packed) TRY(lanes_fork(s, P.lanes)); // (the packed runner forks behind its table launches)
     int rc = ISINGMC_OK;
-    // A periodic update whose sample point is timestep s->t, unless the attempt this call repeats has taken it already
-    // (with_strip_retry).  A call that may be repeated after a strip launch gave up keeps nothing such a launch left: the launch is
-    // waited for and checked first.  (The status returned is the wait's alone; everything else goes into rc.)
-    const auto sample = [&](Periodic &p, int (*enqueue)(isingmc_states *)) -> int {
-        if (rc != ISINGMC_OK || !p.due(s->t)) return ISINGMC_OK;
-        if (s->strip_guard && P.path == StepPath::LatStrip) {
-            HIP_TRY(hipStreamSynchronize(s->stream));
-            rc = strip_check(s);
-        }
-        if (rc == ISINGMC_OK) rc = enqueue(s);
-        if (rc == ISINGMC_OK) p.last_t = s->t;
-        return ISINGMC_OK;
-    };
     for (size_t k0 = 0, nk = 0; k0 < timesteps && rc == ISINGMC_OK; k0 += nk) {
         nk = std::min(P.chunk, timesteps - k0);
         // cluster steps cut the call: a chunk is one cluster step, or a Metropolis stretch that ends before the next one
@@ -1488,9 +1469,8 @@ static int run_steps_impl(isingmc_states *s, size_t timesteps, const double *bet
         if (cluster || icm) nk = 1;
         else {
             if (const size_t every = s->cluster_every ? s->cluster_every : s->icm_every) nk = std::min<size_t>(nk, every - 1 - s->t % every);
-            // minimum tracking, the moment sums (S18), a periodic overlap series (S21) and a periodic observable
-            // series (S22) cut the call too: a stretch ends with their next sample point
-            nk = std::min({nk, s->best_at.stretch(s->t), s->mom_at.stretch(s->t), s->osr_at.stretch(s->t), s->obs_at.stretch(s->t)});
+            // the periodic recorders cut the call too: a stretch ends with their next sample point
+            nk = std::min(nk, recorders_stretch(s));
             // (joined by the cluster step or the update before this stretch; the packed runner forks behind its table launches)
             if (P.lanes > 1 && s->n_lanes <= 1 && P.path != StepPath::Packed) TRY(lanes_fork(s, P.lanes));
         }
@@ -1510,12 +1490,7 @@ static int run_steps_impl(isingmc_states *s, size_t timesteps, const double *bet
         }
         if (rc == ISINGMC_OK && (cluster || icm)) rc = measure_nonlocal_step(c);
         if (rc == ISINGMC_OK && energies_per_step) rc = read_step_energies(c, k0, nk);
-        // the records of minimum tracking: the repeat of a call finds the same records again and changes none
-        TRY(sample(s->best_at, best_update_enqueue));
-        // a sample of the moment sums and a row of the periodic overlap series (S21): neither can be taken back
-        TRY(sample(s->mom_at, moments_sample_enqueue));
-        TRY(sample(s->osr_at, osr_sample_enqueue));
-        TRY(sample(s->obs_at, obs_sample_enqueue)); // ... nor can a row of the periodic observable series (S22)
+        TRY(recorders_sample(s, P.path == StepPath::LatStrip, rc)); // (the status is the strip wait's alone; the samples' goes into rc)
     }
     if (s->n_lanes > 1) { const int jrc = lanes_join(s); if (rc == ISINGMC_OK) rc = jrc; }
     if (device_ms && rc == ISINGMC_OK) {

@@ -118,16 +118,16 @@ extern "C" int isingmc_states_set_moments_every(isingmc_states *s, size_t every,
         if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
         TRY(use_device(s->g->device));
         TRY(mom_reserve(s, flags));
-        s->mom_at.restart(s->t);
+        s->rec[REC_MOMENTS].restart(s->t);
     }
-    s->mom_at.every = every;
+    s->rec[REC_MOMENTS].every = every;
     return ISINGMC_OK;
 }
 
 extern "C" int isingmc_states_moments_every(const isingmc_states *s, size_t *every_out, unsigned *flags_out)
 {
     if (!s) return fail(ISINGMC_ERR_INVALID, "NULL states");
-    if (every_out) *every_out = s->mom_at.every;
+    if (every_out) *every_out = s->rec[REC_MOMENTS].every;
     if (flags_out) *flags_out = s->mom_flags;
     return ISINGMC_OK;
 }
@@ -205,12 +205,12 @@ static int run_sampling_moments_impl(isingmc_states *s, double beta, size_t ther
     }
     struct Off {
         isingmc_states *s;
-        ~Off() { s->mom_at.every = 0; }
+        ~Off() { s->rec[REC_MOMENTS].every = 0; }
     } off{s};
-    s->mom_at.every = 0;
+    s->rec[REC_MOMENTS].every = 0;
     TRY(run_steps(s, thermalization, nullptr, 0, nullptr, nullptr, /*sync=*/false));
-    s->mom_at.every = sampling_freq;
-    s->mom_at.t0 = s->t;
+    s->rec[REC_MOMENTS].every = sampling_freq;
+    s->rec[REC_MOMENTS].t0 = s->t;
     TRY(run_steps(s, n_samples * sampling_freq, nullptr, 0, nullptr, nullptr, /*sync=*/false));
     if (!s->strip_guard) return ISINGMC_OK;
     HIP_TRY(hipStreamSynchronize(s->stream)); // (a call that may be repeated: what the last strip launch left is checked here)
@@ -226,17 +226,16 @@ extern "C" int isingmc_run_sampling_moments(isingmc_states *s, double beta, size
     if (mom_per_rung(flags))
         return fail(ISINGMC_ERR_INVALID, "the sampling run takes no ISINGMC_MOMENTS_PER_RUNG: it runs no exchange rounds; a ladder runs through isingmc_pt_run / "
                                          "isingmc_pt_time_steps with the sums switched on (isingmc_states_set_moments_every)");
-    if (s->mom_at.every) return fail(ISINGMC_ERR_INVALID, "moment sums are switched on for this container already: the sampling run sets its own period (switch accumulation off first)");
+    if (s->rec[REC_MOMENTS].every) return fail(ISINGMC_ERR_INVALID, "moment sums are switched on for this container already: the sampling run sets its own period (switch accumulation off first)");
     {
         const std::string why = mom_obstacle(s, flags);
         if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
     }
-    TRY(osr_room_or_fail(s, thermalization + sampling_freq * n_samples));
-    TRY(obs_room_or_fail(s, thermalization + sampling_freq * n_samples));
+    TRY(recorders_room_or_fail(s, thermalization + sampling_freq * n_samples));
     TRY(use_device(s->g->device));
     TRY(mom_reserve(s, flags));
     TRY(mom_zero_enqueue(s));
-    s->mom_at.last_t = 0;
+    s->rec[REC_MOMENTS].last_t = 0;
     const bool may_strip = may_use_strips(s) && (strip_plan(s, thermalization).use || strip_plan(s, n_samples * sampling_freq).use);
     TRY(with_strip_retry(s, may_strip, [&] { return run_sampling_moments_impl(s, beta, thermalization, sampling_freq, n_samples); }));
     if (mom_rows(s->mom_flags)) TRY(mom_flush_enqueue(s));

@@ -335,16 +335,10 @@ static int between_prepare(isingmc_states *a, isingmc_states *b, const uint32_t 
 static int between_sample(isingmc_states *a, isingmc_states *b)
 {
     for (isingmc_states *s : {a, b})
-        if ((s->mom_flags & ISINGMC_MOMENTS_PER_RUNG) && s->mom_at.due(s->t)) { // (no repeat is under way here: replay_to is 0)
-            TRY(moments_sample_enqueue(s));
-            s->mom_at.last_t = s->t;
-        }
+        if (s->mom_flags & ISINGMC_MOMENTS_PER_RUNG) TRY(recorder_sample_now(s, REC_MOMENTS)); // (no repeat is under way here: replay_to is 0)
     // ... and a periodic observable series by rung (S22) takes its row, by the same rule
     for (isingmc_states *s : {a, b})
-        if (obs_sample_by_rung(s) && s->obs_at.due(s->t)) {
-            TRY(obs_sample_enqueue(s));
-            s->obs_at.last_t = s->t;
-        }
+        if (obs_sample_by_rung(s)) TRY(recorder_sample_now(s, REC_OBSERVABLES));
     return ISINGMC_OK;
 }
 
@@ -397,7 +391,7 @@ extern "C" int isingmc_icm_between(isingmc_states *a, isingmc_states *b, const u
     }
     // a periodic observable series by rung whose log has no room for the row behind this move: nothing is enqueued
     for (const isingmc_states *s : {a, b})
-        if (obs_sample_by_rung(s)) TRY(obs_room_or_fail(s, 1));
+        if (obs_sample_by_rung(s)) TRY(series_room_or_fail(s, REC_OBSERVABLES, 1));
     TRY(use_device(g->device));
     if (n_pairs == 0) { // time passes all the same
         a->t++;

@@ -6,20 +6,18 @@
 // Nothing here is a kernel.
 #include "internal.hpp"
 
-struct isingmc_observable_series {
-    isingmc_states *a = nullptr;
+// rows of {energy f64[n_columns]} {magnetisation i64[n_columns]} {by class i64[n_columns][bins]}, the parts held
+struct isingmc_observable_series : SeriesLog {
+    explicit isingmc_observable_series(isingmc_states *a_) : SeriesLog(a_, REC_OBSERVABLES, "observable") {}
     const isingmc_site_classes *classes = nullptr;
     unsigned flags = 0;
-    size_t n_columns = 0, capacity = 0;
+    size_t n_columns = 0;
     size_t bins = 0, entries = 0; // n_tables * n_classes; 8-byte entries of one column: energy + magnetisation + bins
-    // [capacity] rows of {energy f64[n_columns]} {magnetisation i64[n_columns]} {by class i64[n_columns][bins]}, the parts held
-    DevBlock<unsigned long long> d_log;
     DevBlock<unsigned long long> d_sizes; // sizes[n_tables][n_classes]: what the class store subtracts
     DevBlock<unsigned long long> d_cnt;   // [2][counter slots][2]: the counters of one record (the second block: the real-coupling
                                           // family's up spins, whose launch shares its counter with the lo level of the energy)
     DevBlock<unsigned long long> d_cacc;  // the class counters of one batch; grows only behind stream_quiesce of a's stream
     size_t cacc_cap = 0;
-    std::vector<uint64_t> timesteps;      // of the rows: its size is the row count
 };
 
 static bool obs_energy(const isingmc_observable_series *S) { return (S->flags & ISINGMC_OBS_ENERGY) != 0; }
@@ -74,22 +72,17 @@ extern "C" int isingmc_observable_series_create(isingmc_states *a, const isingmc
     const isingmc_graph *g = a->g;
     const size_t bins = classes ? classes->n_tables * classes->n_classes : 0;
     const size_t entries = ((flags & ISINGMC_OBS_ENERGY) ? 1 : 0) + ((flags & ISINGMC_OBS_MAGNETISATION) ? 1 : 0) + bins;
-    const unsigned long long budget = (unsigned long long)std::max(0ll, a->opt.observable_series_bytes);
-    const unsigned long long row_bytes = (unsigned long long)a->R * entries * 8; // (< 2^32 x 8194 x 8: no overflow)
-    if (row_bytes > budget || capacity > budget / row_bytes)
-        return fail(ISINGMC_ERR_INVALID, "a log of " + std::to_string(capacity) + " rows of " + std::to_string(row_bytes) +
-                                             " bytes is larger than the option observable_series_bytes = " + std::to_string(budget) +
-                                             " allows (isingmc_states_set_option raises the budget)");
+    TRY(series_budget_or_fail("observable", a->opt.observable_series_bytes, capacity, (unsigned long long)a->R * entries * 8));
     TRY(use_device(g->device));
-    std::unique_ptr<isingmc_observable_series> S(new isingmc_observable_series);
-    S->a = a;
+    std::unique_ptr<isingmc_observable_series> S(new isingmc_observable_series(a));
     S->classes = classes;
     S->flags = flags;
     S->n_columns = a->R;
     S->capacity = capacity;
+    S->row = a->R * entries;
     S->bins = bins;
     S->entries = entries;
-    TRY(dev_alloc(S->d_log, capacity * a->R * entries));
+    TRY(dev_alloc(S->d_log, capacity * S->row));
     TRY(dev_alloc(S->d_cnt, 2 * 2 * counter_slots(a)));
     if (bins) {
         std::vector<unsigned long long> sizes(classes->sizes.begin(), classes->sizes.end());
@@ -104,14 +97,8 @@ extern "C" int isingmc_observable_series_create(isingmc_states *a, const isingmc
 extern "C" int isingmc_observable_series_destroy(isingmc_observable_series *S)
 {
     if (!S) return ISINGMC_OK;
-    isingmc_states *a = S->a;
-    (void)hipSetDevice(a->g->device);
-    (void)stream_quiesce(a->stream); // the blocks go back to the cache: no record may still be running
-    if (a->obs == S) {
-        a->obs = nullptr;
-        a->obs_at.every = 0;
-    }
-    if (obs_by_rung(S)) a->obs_by_rung_live--;
+    series_unregister(S);
+    if (obs_by_rung(S)) S->a->obs_by_rung_live--;
     delete S;
     return ISINGMC_OK;
 }
@@ -159,7 +146,7 @@ static int obs_enqueue(isingmc_observable_series *S)
     }
     if (a->n_lanes > 1) TRY(lanes_join(a)); // the sweeps before this record may have run on replica lanes
     const size_t C = S->n_columns, slots = counter_slots(a);
-    unsigned long long *const row = S->d_log + S->timesteps.size() * C * S->entries;
+    unsigned long long *const row = S->next_row();
     double *row_e = obs_energy(S) ? reinterpret_cast<double *>(row) : nullptr;
     long long *row_m = obs_mag(S) ? reinterpret_cast<long long *>(row) + (obs_energy(S) ? C : 0) : nullptr;
     long long *row_c = reinterpret_cast<long long *>(row) + ((obs_energy(S) ? C : 0) + (obs_mag(S) ? C : 0));
@@ -197,16 +184,10 @@ static int obs_enqueue(isingmc_observable_series *S)
     return ISINGMC_OK;
 }
 
-static int obs_full(const isingmc_observable_series *S)
-{
-    return fail(ISINGMC_ERR_INVALID, "the observable series is full: it holds " + std::to_string(S->capacity) +
-                                         " rows, its capacity (isingmc_observable_series_get, then isingmc_observable_series_reset)");
-}
-
 extern "C" int isingmc_observable_series_record(isingmc_observable_series *S)
 {
     if (!S) return fail(ISINGMC_ERR_INVALID, "NULL series");
-    if (S->timesteps.size() >= S->capacity) return obs_full(S);
+    TRY(series_full_or_ok(S));
     TRY(use_device(S->a->g->device));
     return obs_enqueue(S);
 }
@@ -214,71 +195,38 @@ extern "C" int isingmc_observable_series_record(isingmc_observable_series *S)
 extern "C" int isingmc_observable_series_set_every(isingmc_observable_series *S, size_t every)
 {
     if (!S) return fail(ISINGMC_ERR_INVALID, "NULL series");
-    isingmc_states *a = S->a;
-    if (every == 0) { // off: the rows stay
-        if (a->obs == S) {
-            a->obs = nullptr;
-            a->obs_at.every = 0;
-        }
-        return ISINGMC_OK;
-    }
-    if (a->obs && a->obs != S) return fail(ISINGMC_ERR_INVALID, "another observable series of this container records on a period already: one periodic series per container");
-    a->obs = S;
-    a->obs_at.every = every;
-    a->obs_at.restart(a->t);
-    return ISINGMC_OK;
-}
-
-int obs_room_or_fail(const isingmc_states *s, size_t timesteps)
-{
-    if (!s->obs_at.every || !s->obs) return ISINGMC_OK;
-    const uint64_t samples = s->obs_at.points(s->t, timesteps); // sample points: t0 + every, t0 + 2 every, ...
-    const size_t have = s->obs->timesteps.size();
-    if (samples <= s->obs->capacity - have) return ISINGMC_OK;
-    // a periodic series that would run full: nothing is enqueued
-    return fail(ISINGMC_ERR_INVALID, "the observable series of this container would run full: the call takes " + std::to_string(samples) +
-                                         " samples and the log has room for " + std::to_string(s->obs->capacity - have) + " of its " +
-                                         std::to_string(s->obs->capacity) +
-                                         " rows (isingmc_observable_series_get, then isingmc_observable_series_reset; or switch the period off)");
+    if (every == 0) return S->period_off(); // off: the rows stay
+    TRY(series_period_free_or_fail(S));
+    return S->period_on(every);
 }
 
 int obs_sample_enqueue(isingmc_states *s)
 {
-    isingmc_observable_series *S = s->obs;
-    if (S->timesteps.size() >= S->capacity) return obs_full(S);
+    isingmc_observable_series *S = static_cast<isingmc_observable_series *>(s->series[REC_OBSERVABLES]);
+    TRY(series_full_or_ok(S));
     return obs_enqueue(S);
 }
 
-bool obs_sample_by_rung(const isingmc_states *s) { return s->obs && obs_by_rung(s->obs); }
-
-extern "C" int isingmc_observable_series_count(const isingmc_observable_series *S, size_t *n_out, size_t *capacity_out)
+bool obs_sample_by_rung(const isingmc_states *s)
 {
-    if (!S) return fail(ISINGMC_ERR_INVALID, "NULL series");
-    if (n_out) *n_out = S->timesteps.size();
-    if (capacity_out) *capacity_out = S->capacity;
-    return ISINGMC_OK;
+    const auto *S = static_cast<const isingmc_observable_series *>(s->series[REC_OBSERVABLES]);
+    return S && obs_by_rung(S);
 }
+
+extern "C" int isingmc_observable_series_count(const isingmc_observable_series *S, size_t *n, size_t *capacity) { return series_count(S, n, capacity); }
 
 extern "C" int isingmc_observable_series_get(isingmc_observable_series *S, size_t first, size_t n, uint64_t *timesteps_out, double *energy_out,
                                              int64_t *magnetisation_out, int64_t *class_out)
 {
     if (!S) return fail(ISINGMC_ERR_INVALID, "NULL series");
-    const size_t have = S->timesteps.size();
-    if (first > have || n > have - first) return fail(ISINGMC_ERR_INVALID, "rows out of range: the series holds " + std::to_string(have) + " rows");
-    if (energy_out && !obs_energy(S)) return fail(ISINGMC_ERR_INVALID, "no energies are held: make the series with ISINGMC_OBS_ENERGY (energy_out may be NULL)");
-    if (magnetisation_out && !obs_mag(S)) return fail(ISINGMC_ERR_INVALID, "no magnetisations are held: make the series with ISINGMC_OBS_MAGNETISATION (magnetisation_out may be NULL)");
-    if (class_out && !S->bins) return fail(ISINGMC_ERR_INVALID, "no magnetisations by class are held: make the series with a class set (class_out may be NULL)");
-    isingmc_states *a = S->a;
-    TRY(use_device(a->g->device));
-    HIP_TRY(hipStreamSynchronize(a->stream));
-    TRY(strip_error(strip_check(a)));
-    if (timesteps_out) std::copy(S->timesteps.begin() + first, S->timesteps.begin() + first + n, timesteps_out);
-    if (n == 0 || (!energy_out && !magnetisation_out && !class_out)) return ISINGMC_OK;
-    const size_t C = S->n_columns, row = C * S->entries;
+    const char *why = energy_out && !obs_energy(S) ? "no energies are held: make the series with ISINGMC_OBS_ENERGY (energy_out may be NULL)"
+                      : magnetisation_out && !obs_mag(S) ? "no magnetisations are held: make the series with ISINGMC_OBS_MAGNETISATION (magnetisation_out may be NULL)"
+                      : class_out && !S->bins ? "no magnetisations by class are held: make the series with a class set (class_out may be NULL)" : nullptr;
     std::vector<unsigned long long> h;
-    TRY(read_back(a, h, S->d_log.get() + first * row, n * row));
+    TRY(series_read(S, first, n, why, timesteps_out, energy_out || magnetisation_out || class_out, h));
+    const size_t C = S->n_columns, row = S->row;
     const size_t off_m = obs_energy(S) ? C : 0, off_c = off_m + (obs_mag(S) ? C : 0);
-    for (size_t i = 0; i < n; i++) {
+    for (size_t i = 0; i < h.size() / row; i++) {
         const unsigned long long *r = h.data() + i * row;
         if (energy_out) std::memcpy(energy_out + i * C, r, C * sizeof(double));
         if (magnetisation_out) std::memcpy(magnetisation_out + i * C, r + off_m, C * sizeof(int64_t));
@@ -287,11 +235,4 @@ extern "C" int isingmc_observable_series_get(isingmc_observable_series *S, size_
     return ISINGMC_OK;
 }
 
-extern "C" int isingmc_observable_series_reset(isingmc_observable_series *S)
-{
-    if (!S) return fail(ISINGMC_ERR_INVALID, "NULL series");
-    // rows enqueued so far still land in the log, ahead on a's stream of whatever overwrites them: nothing to wait for
-    S->timesteps.clear();
-    if (S->a->obs == S) S->a->obs_at.last_t = 0;
-    return ISINGMC_OK;
-}
+extern "C" int isingmc_observable_series_reset(isingmc_observable_series *S) { return series_reset(S); }

@@ -5,20 +5,19 @@
 // Nothing here is a kernel.
 #include "internal.hpp"
 
-struct isingmc_overlap_series {
-    isingmc_states *a = nullptr, *b = nullptr; // b == a: pairs inside one container
+struct isingmc_overlap_series : SeriesLog { // rows of [n_pairs][entries], read as long long
+    isingmc_states *b = nullptr; // b == a: pairs inside one container
+    explicit isingmc_overlap_series(isingmc_states *a_) : SeriesLog(a_, REC_OVERLAPS, "overlap") {}
     const isingmc_site_classes *classes = nullptr;
     unsigned flags = 0;
-    size_t n_pairs = 0, capacity = 0;
+    size_t n_pairs = 0;
     size_t bins = 0, entries = 0; // n_tables * n_classes; entries of one pair: 1 + link + bins
-    DevBlock<long long> d_log;             // [capacity][n_pairs][entries]
     DevBlock<unsigned long long> d_sizes;  // {nvars, n_edges, sizes[n_tables][n_classes]}: what the store kernel subtracts from
     DevBlock<uint32_t> d_slots;            // [2][n_pairs] the slot tables of the record being enqueued
     // workspace of one record; it grows only behind stream_quiesce of a's stream
     DevBlock<unsigned long long> d_acc, d_cacc; // {D, B} per pair column; the class bins of one batch
     DevBlock<uint32_t> d_words;                 // packed containers with tables: the gathered overlap words of one batch
     size_t acc_cap = 0, cacc_cap = 0, words_cap = 0;
-    std::vector<uint64_t> timesteps;            // of the rows: its size is the row count
     std::vector<std::vector<uint32_t>> uploads; // host tables that an enqueued copy may still read
     hipEvent_t ev[2] = {nullptr, nullptr};      // b's stream has arrived / the record is enqueued
 };
@@ -67,23 +66,18 @@ extern "C" int isingmc_overlap_series_create(isingmc_states *a, isingmc_states *
     }
     const size_t bins = classes ? classes->n_tables * classes->n_classes : 0;
     const size_t entries = 1 + ((flags & ISINGMC_SERIES_LINK) ? 1 : 0) + bins;
-    const unsigned long long budget = (unsigned long long)std::max(0ll, a->opt.overlap_series_bytes);
-    const unsigned long long row_bytes = (unsigned long long)n_pairs * entries * sizeof(long long); // (< 2^32 x 8194 x 8: no overflow)
-    if (row_bytes > budget || capacity > budget / row_bytes)
-        return fail(ISINGMC_ERR_INVALID, "a log of " + std::to_string(capacity) + " rows of " + std::to_string(row_bytes) +
-                                             " bytes is larger than the option overlap_series_bytes = " + std::to_string(budget) +
-                                             " allows (isingmc_states_set_option raises the budget)");
+    TRY(series_budget_or_fail("overlap", a->opt.overlap_series_bytes, capacity, (unsigned long long)n_pairs * entries * sizeof(long long)));
     TRY(use_device(g->device));
-    std::unique_ptr<isingmc_overlap_series> S(new isingmc_overlap_series);
-    S->a = a;
+    std::unique_ptr<isingmc_overlap_series> S(new isingmc_overlap_series(a));
     S->b = b ? b : a;
     S->classes = classes;
     S->flags = flags;
     S->n_pairs = n_pairs;
     S->capacity = capacity;
+    S->row = n_pairs * entries;
     S->bins = bins;
     S->entries = entries;
-    TRY(dev_alloc(S->d_log, capacity * n_pairs * entries));
+    TRY(dev_alloc(S->d_log, capacity * S->row));
     TRY(dev_alloc(S->d_slots, 2 * n_pairs));
     std::vector<unsigned long long> sizes{(unsigned long long)g->nvars, (unsigned long long)g->n_edges};
     if (classes) sizes.insert(sizes.end(), classes->sizes.begin(), classes->sizes.end());
@@ -99,13 +93,7 @@ extern "C" int isingmc_overlap_series_create(isingmc_states *a, isingmc_states *
 extern "C" int isingmc_overlap_series_destroy(isingmc_overlap_series *S)
 {
     if (!S) return ISINGMC_OK;
-    isingmc_states *a = S->a;
-    (void)hipSetDevice(a->g->device);
-    (void)stream_quiesce(a->stream); // the blocks go back to the cache: no record may still be running
-    if (a->osr == S) {
-        a->osr = nullptr;
-        a->osr_at.every = 0;
-    }
+    series_unregister(S);
     if (osr_by_rung(S))
         for (isingmc_states *s : {S->a, S->b}) s->osr_by_rung_live--;
     for (hipEvent_t ev : S->ev) pooled_event_destroy(ev, true);
@@ -135,7 +123,7 @@ static int osr_enqueue(isingmc_overlap_series *S, const uint32_t *d_sa, const ui
     TRY(overlap_lanes_join(a, b));
     // b's sweeps and exchange rounds so far, before a's stream reads b's configurations and permutation
     if (a != b) TRY(stream_wait_for(a->stream, b->stream, S->ev[0]));
-    long long *const row = S->d_log + S->timesteps.size() * S->n_pairs * S->entries;
+    long long *const row = reinterpret_cast<long long *>(S->next_row());
     const uint32_t entries = uint32_t(S->entries), n_spin = J.link ? 2 : 1, bins = uint32_t(S->bins);
     // spin and link overlap: entries 0 and 1 of every pair
     auto store = [&](const unsigned long long *acc, size_t c0, size_t n) -> int {
@@ -154,12 +142,6 @@ static int osr_enqueue(isingmc_overlap_series *S, const uint32_t *d_sa, const ui
     return ISINGMC_OK;
 }
 
-static int osr_full(const isingmc_overlap_series *S)
-{
-    return fail(ISINGMC_ERR_INVALID, "the overlap series is full: it holds " + std::to_string(S->capacity) +
-                                         " rows, its capacity (isingmc_overlap_series_get, then isingmc_overlap_series_reset)");
-}
-
 extern "C" int isingmc_overlap_series_record(isingmc_overlap_series *S, const uint32_t *slots_a, const uint32_t *slots_b)
 {
     if (!S) return fail(ISINGMC_ERR_INVALID, "NULL series");
@@ -176,7 +158,7 @@ extern "C" int isingmc_overlap_series_record(isingmc_overlap_series *S, const ui
     } else {
         TRY(overlap_pairing(a, b, slots_a, slots_b, n_pairs, P));
     }
-    if (S->timesteps.size() >= S->capacity) return osr_full(S);
+    TRY(series_full_or_ok(S));
     TRY(use_device(a->g->device));
     if (!osr_by_rung(S) && !P.default_pairs) {
         // the tables go into a block of the series; the host copy lives until a's stream has passed the upload
@@ -196,73 +178,37 @@ extern "C" int isingmc_overlap_series_set_every(isingmc_overlap_series *S, size_
 {
     if (!S) return fail(ISINGMC_ERR_INVALID, "NULL series");
     isingmc_states *a = S->a;
-    if (every == 0) { // off: the rows stay
-        if (a->osr == S) {
-            a->osr = nullptr;
-            a->osr_at.every = 0;
-        }
-        return ISINGMC_OK;
-    }
+    if (every == 0) return S->period_off(); // off: the rows stay
     if (S->b != a || osr_by_rung(S))
         return fail(ISINGMC_ERR_INVALID, "a period is for a series inside one container (b == NULL, no ISINGMC_SERIES_BY_RUNG): between two containers "
                                          "there is no common step loop; record explicitly, as with isingmc_icm_between");
-    if (a->osr && a->osr != S) return fail(ISINGMC_ERR_INVALID, "another overlap series of this container records on a period already: one periodic series per container");
+    TRY(series_period_free_or_fail(S));
     OverlapPairing P;
     TRY(overlap_pairing(a, a, nullptr, nullptr, S->n_pairs, P)); // a periodic record takes no tables: the pairs (2 p, 2 p + 1)
-    a->osr = S;
-    a->osr_at.every = every;
-    a->osr_at.restart(a->t);
-    return ISINGMC_OK;
-}
-
-int osr_room_or_fail(const isingmc_states *s, size_t timesteps)
-{
-    if (!s->osr_at.every || !s->osr) return ISINGMC_OK;
-    const uint64_t samples = s->osr_at.points(s->t, timesteps); // sample points: t0 + every, t0 + 2 every, ...
-    const size_t have = s->osr->timesteps.size();
-    if (samples <= s->osr->capacity - have) return ISINGMC_OK;
-    // a periodic series that would run full: nothing is enqueued
-    return fail(ISINGMC_ERR_INVALID, "the overlap series of this container would run full: the call takes " + std::to_string(samples) +
-                                         " samples and the log has room for " + std::to_string(s->osr->capacity - have) + " of its " +
-                                         std::to_string(s->osr->capacity) +
-                                         " rows (isingmc_overlap_series_get, then isingmc_overlap_series_reset; or switch the period off)");
+    return S->period_on(every);
 }
 
 int osr_sample_enqueue(isingmc_states *s)
 {
-    isingmc_overlap_series *S = s->osr;
-    if (S->timesteps.size() >= S->capacity) return osr_full(S);
+    isingmc_overlap_series *S = static_cast<isingmc_overlap_series *>(s->series[REC_OVERLAPS]);
+    TRY(series_full_or_ok(S));
     return osr_enqueue(S, nullptr, nullptr);
 }
 
-extern "C" int isingmc_overlap_series_count(const isingmc_overlap_series *S, size_t *n_out, size_t *capacity_out)
-{
-    if (!S) return fail(ISINGMC_ERR_INVALID, "NULL series");
-    if (n_out) *n_out = S->timesteps.size();
-    if (capacity_out) *capacity_out = S->capacity;
-    return ISINGMC_OK;
-}
+extern "C" int isingmc_overlap_series_count(const isingmc_overlap_series *S, size_t *n, size_t *capacity) { return series_count(S, n, capacity); }
 
 extern "C" int isingmc_overlap_series_get(isingmc_overlap_series *S, size_t first, size_t n, uint64_t *timesteps_out, int64_t *spin_out,
                                           int64_t *link_out, int64_t *class_out)
 {
     if (!S) return fail(ISINGMC_ERR_INVALID, "NULL series");
-    const size_t have = S->timesteps.size();
-    if (first > have || n > have - first) return fail(ISINGMC_ERR_INVALID, "rows out of range: the series holds " + std::to_string(have) + " rows");
-    if (link_out && !osr_link(S)) return fail(ISINGMC_ERR_INVALID, "no link overlaps are held: make the series with ISINGMC_SERIES_LINK (link_out may be NULL)");
-    if (class_out && !S->bins) return fail(ISINGMC_ERR_INVALID, "no overlaps by class are held: make the series with a class set (class_out may be NULL)");
-    isingmc_states *a = S->a;
-    TRY(use_device(a->g->device));
-    HIP_TRY(hipStreamSynchronize(a->stream));
-    S->uploads.clear();
-    TRY(strip_error(strip_check(a)));
-    if (timesteps_out) std::copy(S->timesteps.begin() + first, S->timesteps.begin() + first + n, timesteps_out);
-    if (n == 0 || (!spin_out && !link_out && !class_out)) return ISINGMC_OK;
-    const size_t E = S->entries, row = S->n_pairs * E, bins = S->bins, off = osr_link(S) ? 2 : 1;
-    std::vector<long long> h;
-    TRY(read_back(a, h, S->d_log.get() + first * row, n * row));
-    for (size_t i = 0; i < n * S->n_pairs; i++) { // (row, pair)
-        const long long *e = h.data() + i * E;
+    const char *why = link_out && !osr_link(S) ? "no link overlaps are held: make the series with ISINGMC_SERIES_LINK (link_out may be NULL)"
+                      : class_out && !S->bins ? "no overlaps by class are held: make the series with a class set (class_out may be NULL)" : nullptr;
+    std::vector<unsigned long long> h;
+    TRY(series_read(S, first, n, why, timesteps_out, spin_out || link_out || class_out, h));
+    S->uploads.clear(); // (a's stream has drained)
+    const size_t E = S->entries, bins = S->bins, off = osr_link(S) ? 2 : 1;
+    for (size_t i = 0; i < h.size() / E; i++) { // (row, pair)
+        const long long *e = reinterpret_cast<const long long *>(h.data()) + i * E;
         if (spin_out) spin_out[i] = e[0];
         if (link_out) link_out[i] = e[1];
         if (class_out) std::copy(e + off, e + off + bins, class_out + i * bins);
@@ -270,11 +216,4 @@ extern "C" int isingmc_overlap_series_get(isingmc_overlap_series *S, size_t firs
     return ISINGMC_OK;
 }
 
-extern "C" int isingmc_overlap_series_reset(isingmc_overlap_series *S)
-{
-    if (!S) return fail(ISINGMC_ERR_INVALID, "NULL series");
-    // rows enqueued so far still land in the log, ahead on a's stream of whatever overwrites them: nothing to wait for
-    S->timesteps.clear();
-    if (S->a->osr == S) S->a->osr_at.last_t = 0;
-    return ISINGMC_OK;
-}
+extern "C" int isingmc_overlap_series_reset(isingmc_overlap_series *S) { return series_reset(S); }

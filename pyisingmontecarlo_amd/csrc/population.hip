@@ -78,7 +78,7 @@ static int pa_resample_enqueue(isingmc_states *s, double dbeta, uint64_t seed, u
     const uint32_t R = uint32_t(s->R);
     TRY(energies_enqueue(s, s->d_pa_energy));
     // minimum tracking: the records see the population before the gather; they stay with the slots
-    if (s->best_at.every) TRY(best_from_energies(s, s->d_pa_energy));
+    if (s->rec[REC_BEST].every) TRY(best_from_energies(s, s->d_pa_energy));
     HIP_TRY(pa_launch_weights(s->stream, s->d_pa_energy, R, dbeta, seed, step, s->d_pa_cum, d_rec));
     HIP_TRY(pa_launch_scan(s->stream, s->d_pa_cum, R, s->d_pa_cum + R));
     HIP_TRY(pa_launch_sources(s->stream, s->d_pa_cum, R, d_rec, s->d_pa_src));
@@ -93,9 +93,7 @@ extern "C" int isingmc_pa_resample(isingmc_states *s, double dbeta, uint64_t see
         const std::string why = pa_obstacle(s);
         if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
     }
-    if (s->mom_at.every) return fail(ISINGMC_ERR_INVALID, "moment sums are switched on for this container (isingmc_states_set_moments_every): a resampling replaces the replicas whose samples they hold; switch accumulation off first");
-    if (s->osr_at.every) return fail(ISINGMC_ERR_INVALID, "an overlap series records on a period for this container (isingmc_overlap_series_set_every): a resampling replaces the replicas whose pairs it follows; switch the period off first");
-    if (s->obs_at.every) return fail(ISINGMC_ERR_INVALID, "an observable series records on a period for this container (isingmc_observable_series_set_every): a resampling replaces the replicas whose columns it follows; switch the period off first");
+    if (const char *why = recorders_refusal(s, RecorderRefusal::Resample)) return fail(ISINGMC_ERR_INVALID, why);
     TRY(use_device(s->g->device));
     TRY(pa_reserve(s));
     TRY(pa_resample_enqueue(s, dbeta, seed, step, s->d_pa_record));
@@ -117,9 +115,7 @@ extern "C" int isingmc_pa_run(isingmc_states *s, const double *betas, size_t n_b
         const std::string why = pa_obstacle(s);
         if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
     }
-    if (s->mom_at.every) return fail(ISINGMC_ERR_INVALID, "moment sums are switched on for this container (isingmc_states_set_moments_every): a resampling replaces the replicas whose samples they hold; switch accumulation off first");
-    if (s->osr_at.every) return fail(ISINGMC_ERR_INVALID, "an overlap series records on a period for this container (isingmc_overlap_series_set_every): a resampling replaces the replicas whose pairs it follows; switch the period off first");
-    if (s->obs_at.every) return fail(ISINGMC_ERR_INVALID, "an observable series records on a period for this container (isingmc_observable_series_set_every): a resampling replaces the replicas whose columns it follows; switch the period off first");
+    if (const char *why = recorders_refusal(s, RecorderRefusal::Resample)) return fail(ISINGMC_ERR_INVALID, why);
     TRY(use_device(s->g->device));
     TRY(pa_reserve(s));
     const size_t n_steps = n_betas - 1;
@@ -136,7 +132,7 @@ extern "C" int isingmc_pa_run(isingmc_states *s, const double *betas, size_t n_b
         rc = run_steps(s, sweeps_per_beta, &betas[k], 0, nullptr, nullptr, /*sync=*/false);
         s->step_preset = nullptr;
     }
-    if (rc == ISINGMC_OK && s->best_at.every) rc = best_update_enqueue(s); // the final population
+    if (rc == ISINGMC_OK && s->rec[REC_BEST].every) rc = best_update_enqueue(s); // the final population
     if (rc == ISINGMC_OK && n_steps) {
         HIP_TRY(hipMemcpyAsync(s->d_pa_record, d_log + (n_steps - 1), sizeof(PaRecord), hipMemcpyDeviceToDevice, s->stream));
         s->pa_have_record = true;

@@ -122,22 +122,18 @@ struct ClassesHandle {
     ~ClassesHandle() { isingmc_site_classes_destroy(c); }
 };
 
-// an overlap series with the class set it reads: the series goes first, and both before their container
-struct SeriesHandle {
-    isingmc_overlap_series *s = nullptr;
+// a device series with the class set it reads: the series goes first, and both before their container.
+// columns: the pairs of an overlap series, the replicas of an observable series
+template <typename Series, int (*Destroy)(Series *)>
+struct SeriesHandleOf {
+    Series *s = nullptr;
     ClassesHandle classes;
     bool link = false;
-    size_t n_pairs = 0, n_tables = 0, n_classes = 0;
-    ~SeriesHandle() { isingmc_overlap_series_destroy(s); }
+    size_t columns = 0, n_tables = 0, n_classes = 0;
+    ~SeriesHandleOf() { Destroy(s); }
 };
-
-// an observable series with the class set it reads: the same order
-struct ObsSeriesHandle {
-    isingmc_observable_series *s = nullptr;
-    ClassesHandle classes;
-    size_t n_columns = 0, n_tables = 0, n_classes = 0;
-    ~ObsSeriesHandle() { isingmc_observable_series_destroy(s); }
-};
+using SeriesHandle = SeriesHandleOf<isingmc_overlap_series, isingmc_overlap_series_destroy>;
+using ObsSeriesHandle = SeriesHandleOf<isingmc_observable_series, isingmc_observable_series_destroy>;
 
 struct EdgeArrays {
     std::vector<uint64_t> a, b;
@@ -971,6 +967,19 @@ public:
         return py::make_tuple(n, site, bonds ? py::object(bond) : py::object(py::none()));
     }
     void reset_measured_spins() { check(isingmc_moments_reset(st_->s)); }
+    // the handle of a new series over `columns` columns, with the class set made from the caller's tables (None: no class set)
+    template <typename H>
+    std::unique_ptr<H> series_handle(const py::object &classes, size_t columns)
+    {
+        auto h = std::make_unique<H>();
+        h->columns = columns;
+        if (classes.is_none()) return h;
+        const ClassTables T = class_tables(classes, py::none(), E_.nvars);
+        check(isingmc_site_classes_create(st_->graph->g, T.cls.data(), T.n_tables, T.n_classes, &h->classes.c));
+        h->n_tables = T.n_tables;
+        h->n_classes = T.n_classes;
+        return h;
+    }
     // extension: the overlaps between the persistent replicas (2 p, 2 p + 1), logged on the device once per sample.
     // set_measure_overlaps_every(k, link, classes, capacity): a row follows every k-th timestep from now on, without the host
     // waiting (0: off, the rows stay); a call with k > 0 starts a new log of `capacity` rows.  classes: class tables as
@@ -983,16 +992,9 @@ public:
             if (series_) check(isingmc_overlap_series_set_every(series_->s, 0));
             return;
         }
-        auto h = std::make_unique<SeriesHandle>();
-        if (!classes.is_none()) {
-            const ClassTables T = class_tables(classes, py::none(), E_.nvars);
-            check(isingmc_site_classes_create(st_->graph->g, T.cls.data(), T.n_tables, T.n_classes, &h->classes.c));
-            h->n_tables = T.n_tables;
-            h->n_classes = T.n_classes;
-        }
+        auto h = series_handle<SeriesHandle>(classes, isingmc_states_count(st_->s) / 2);
         h->link = link;
-        h->n_pairs = isingmc_states_count(st_->s) / 2;
-        check(isingmc_overlap_series_create(st_->s, nullptr, h->n_pairs, h->classes.c, link ? ISINGMC_SERIES_LINK : 0u, capacity, &h->s));
+        check(isingmc_overlap_series_create(st_->s, nullptr, h->columns, h->classes.c, link ? ISINGMC_SERIES_LINK : 0u, capacity, &h->s));
         series_.reset(); // (the old log goes, and its period with it, before the new one takes the container's one period)
         check(isingmc_overlap_series_set_every(h->s, k));
         series_ = std::move(h);
@@ -1003,7 +1005,7 @@ public:
         const SeriesHandle &h = *series_;
         size_t n = 0;
         check(isingmc_overlap_series_count(h.s, &n, nullptr));
-        const ssize_t N = ssize_t(n), P = ssize_t(h.n_pairs);
+        const ssize_t N = ssize_t(n), P = ssize_t(h.columns);
         py::array_t<uint64_t> t(std::vector<ssize_t>{N});
         py::array_t<int64_t> spin(std::vector<ssize_t>{N, P}), lnk(std::vector<ssize_t>{h.link ? N : 0, P});
         py::array_t<int64_t> cls(std::vector<ssize_t>{h.n_tables ? N : 0, P, ssize_t(h.n_tables), ssize_t(h.n_classes)});
@@ -1015,10 +1017,7 @@ public:
         }
         return py::make_tuple(t, spin, h.link ? py::object(lnk) : py::object(py::none()), h.n_tables ? py::object(cls) : py::object(py::none()));
     }
-    void reset_measured_overlaps()
-    {
-        if (series_) check(isingmc_overlap_series_reset(series_->s));
-    }
+    void reset_measured_overlaps() { if (series_) check(isingmc_overlap_series_reset(series_->s)); }
     // extension: energy, magnetisation and magnetisation by class of every persistent replica, logged on the device
     // once per sample.  set_measure_observables_every(k, classes, capacity): a row follows every k-th timestep from now on, without
     // the host waiting (0: off, the rows stay); a call with k > 0 starts a new log of `capacity` rows.  classes: class tables as
@@ -1031,14 +1030,7 @@ public:
             if (obs_series_) check(isingmc_observable_series_set_every(obs_series_->s, 0));
             return;
         }
-        auto h = std::make_unique<ObsSeriesHandle>();
-        if (!classes.is_none()) {
-            const ClassTables T = class_tables(classes, py::none(), E_.nvars);
-            check(isingmc_site_classes_create(st_->graph->g, T.cls.data(), T.n_tables, T.n_classes, &h->classes.c));
-            h->n_tables = T.n_tables;
-            h->n_classes = T.n_classes;
-        }
-        h->n_columns = isingmc_states_count(st_->s);
+        auto h = series_handle<ObsSeriesHandle>(classes, isingmc_states_count(st_->s));
         check(isingmc_observable_series_create(st_->s, h->classes.c, ISINGMC_OBS_ENERGY | ISINGMC_OBS_MAGNETISATION, capacity, &h->s));
         obs_series_.reset(); // (the old log goes, and its period with it, before the new one takes the container's one period)
         check(isingmc_observable_series_set_every(h->s, k));
@@ -1050,7 +1042,7 @@ public:
         const ObsSeriesHandle &h = *obs_series_;
         size_t n = 0;
         check(isingmc_observable_series_count(h.s, &n, nullptr));
-        const ssize_t N = ssize_t(n), R = ssize_t(h.n_columns);
+        const ssize_t N = ssize_t(n), R = ssize_t(h.columns);
         py::array_t<uint64_t> t(std::vector<ssize_t>{N});
         py::array_t<double> e(std::vector<ssize_t>{N, R});
         py::array_t<int64_t> m(std::vector<ssize_t>{N, R});
@@ -1064,10 +1056,7 @@ public:
         }
         return py::make_tuple(t, e, m, h.n_tables ? py::object(cls) : py::object(py::none()));
     }
-    void reset_measured_observables()
-    {
-        if (obs_series_) check(isingmc_observable_series_reset(obs_series_->s));
-    }
+    void reset_measured_observables() { if (obs_series_) check(isingmc_observable_series_reset(obs_series_->s)); }
     // extension: Swendsen-Wang cluster steps on the persistent replicas (see Lattice.set_cluster_update_every); the graph is known
     // here, so one the cluster step does not serve raises ValueError at once
     void set_cluster_update_every(size_t k) { check(isingmc_states_set_cluster_every(st_->s, k)); }

@@ -110,8 +110,7 @@ extern "C" int isingmc_run_sampling(isingmc_states *s, double beta, size_t therm
                                     size_t n_samples, double *energies_out, uint8_t *states_out)
 {
     if (!s) return fail(ISINGMC_ERR_INVALID, "NULL states");
-    TRY(osr_room_or_fail(s, thermalization + sampling_freq * n_samples));
-    TRY(obs_room_or_fail(s, thermalization + sampling_freq * n_samples));
+    TRY(recorders_room_or_fail(s, thermalization + sampling_freq * n_samples));
     const bool may_strip = may_use_strips(s) && (strip_plan(s, thermalization).use || strip_plan(s, sampling_freq).use);
     return with_strip_retry(s, may_strip, [&] {
         return run_sampling_impl(s, beta, thermalization, sampling_freq, n_samples, energies_out, states_out);

@@ -44,7 +44,7 @@ static std::string pt_attach_obstacle(const isingmc_states *s, size_t n_rungs, s
     if (s->pt_attached) return "a ladder is already attached";
     if (s->cluster_every) return "cluster updates are switched on for this container (isingmc_states_set_cluster_every): a tempering round has no cluster steps";
     if (s->icm_every) return "isoenergetic cluster moves are switched on for this container (isingmc_states_set_icm_every): inside a ladder the pairs would have to follow the rung permutation";
-    if (s->mom_at.every) return "moment sums are switched on for this container (isingmc_states_set_moments_every): inside a ladder a slot changes its temperature; attach the ladder first, then switch the sums per rung on (ISINGMC_MOMENTS_PER_RUNG)";
+    if (s->rec[REC_MOMENTS].every) return "moment sums are switched on for this container (isingmc_states_set_moments_every): inside a ladder a slot changes its temperature; attach the ladder first, then switch the sums per rung on (ISINGMC_MOMENTS_PER_RUNG)";
     const bool pk_ladder = s->packed && !s->rj;
     if (!s->packed && (s->g->kind != ISINGMC_KIND_LATTICE2D || s->g->mc_mode != MC_NONE))
         return "on-stream tempering is implemented for periodic, field-free lattices and for the replica-packed "
@@ -72,7 +72,7 @@ extern "C" int isingmc_pt_detach(isingmc_states *s)
 {
     if (!s) return fail(ISINGMC_ERR_INVALID, "NULL states");
     if (!s->pt_attached) return ISINGMC_OK;
-    if (s->mom_at.every)
+    if (s->rec[REC_MOMENTS].every)
         return fail(ISINGMC_ERR_INVALID, "sums per rung are switched on for this container (isingmc_states_set_moments_every): their samples read the ladder's "
                                          "permutation; switch accumulation off first");
     if (s->osr_by_rung_live)
@@ -198,17 +198,16 @@ extern "C" int isingmc_pt_run(isingmc_states *s, size_t timesteps, size_t swap_e
     if (!s || !s->pt_attached) return fail(ISINGMC_ERR_INVALID, "no ladder attached");
     if (swap_every == 0) return fail(ISINGMC_ERR_INVALID, "swap_every must be positive");
     if (s->pt_world != 1) return fail(ISINGMC_ERR_INVALID, "isingmc_pt_run is for a single rank: the all-gather of a sharded ladder sits between measure and swap");
-    TRY(obs_room_or_fail(s, timesteps)); // a periodic observable series that would run full in the WHOLE call: no round is enqueued
+    TRY(recorders_room_or_fail(s, timesteps)); // a periodic series that would run full in the WHOLE call: no round is enqueued
     TRY(use_device(s->g->device));
     const isingmc_graph *g = s->g;
     const size_t rounds = timesteps / swap_every, tail = timesteps % swap_every;
     const StripPlan P = s->R ? strip_plan(s, rounds * swap_every, /*ladder=*/true) : StripPlan{};
     const bool in_kernel = P.use && P.replicas_per_pass >= s->R && rounds >= 2 && rounds * swap_every <= 65536 &&
                            s->R == s->pt.n_rungs && s->opt.pt_in_kernel != 0 &&
-                           !s->best_at.every && // minimum tracking reads every round's energies: one launch per round
-                           !s->mom_at.every &&  // sums per rung (S19) read the configurations and the permutation between the rounds: the same
-                           !s->osr_at.every &&  // ... and so does a periodic overlap series (S21)
-                           !s->obs_at.every;    // ... and a periodic observable series (S22)
+                           // minimum tracking reads every round's energies, sums per rung (S19) and the periodic series
+                           // (S21, S22) the configurations and the permutation between the rounds: one launch per round
+                           !recorders_any_on(s);
     if (in_kernel) {
         const size_t R = s->R, nk = rounds * swap_every;
         if (!s->d_pt_mail) {
@@ -258,7 +257,7 @@ extern "C" int isingmc_pt_measure(isingmc_states *s)
     else
         TRY(energies_enqueue(s, d_out));
     // minimum tracking: the round's energies serve the records too -- per slot, so the permutation does not enter
-    return s->best_at.every ? best_from_energies(s, d_out) : ISINGMC_OK;
+    return s->rec[REC_BEST].every ? best_from_energies(s, d_out) : ISINGMC_OK;
 }
 
 // enqueue: the energies of the container's configurations -> d_out[R] (device), the f64 values of isingmc_get_energies
