@@ -230,6 +230,18 @@ void isingmc_states_destroy(isingmc_states *states);
  * environment once, when a graph / a container is created -- never at call time -- so two containers of one process can differ.
  * The kernel FAMILY (force_real, disable_real, force_packed, disable_packed) is fixed at creation and cannot be changed here. */
 int isingmc_states_set_option(isingmc_states *states, const char *name, long value);
+/* The option "philox_rounds" (ISINGMC_PHILOX_ROUNDS, default 10) is the one switch that selects another trajectory: the rounds of
+ * Philox4x32 in the draws of the Metropolis sweeps, 10 or 7.  It serves the periodic, field-free, one-|J| checkerboard lattices
+ * (family 0 without a field, open boundaries or a second |J|) and there only the sweeps' plane and tie calls: initial
+ * configurations, exchange decisions, Swendsen-Wang bonds, isoenergetic cluster moves and population-annealing offsets draw with
+ * ten rounds whatever it says, so a container starts from the same configurations and a ladder decides its exchanges from the
+ * same words at either value.  ISINGMC_ERR_INVALID, the value left as it was, for any value but 7 and 10 and for 7 on a container
+ * of another family.  The generator keeps no state: the option may change between calls and holds for the calls planned after it.
+ * From the environment, 7 is the default of the containers it serves and the others keep 10; a value that is no round count fails
+ * the creation.  Philox4x32-7 is the fewest rounds with no reported BigCrush failure (Salmon et al., SC'11); 10 stays the default. */
+int isingmc_states_philox_rounds(const isingmc_states *states, int *rounds_out); /* the rounds the container's sweeps draw with */
+/* ... and the rounds a container created NOW on this graph would start with (the environment as it is; 10 where 7 is not served) */
+int isingmc_graph_philox_rounds(const isingmc_graph *graph, int *rounds_out);
 
 /* Per-replica inverse temperatures (parallel-tempering ladder; shaped after
  * LatticeTempering.add_graph(beta), tempering.rs:70-113).  NULL clears them.  While set, the

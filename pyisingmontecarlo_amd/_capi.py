@@ -70,6 +70,8 @@ _PROTOTYPES = {
     "isingmc_graph_family_for": (C.c_int, [_vp, C.c_size_t, C.POINTER(C.c_int)]),
     "isingmc_states_family": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "isingmc_states_set_option": (C.c_int, [_vp, C.c_char_p, C.c_long]),
+    "isingmc_states_philox_rounds": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "isingmc_graph_philox_rounds": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "isingmc_states_set_betas": (C.c_int, [_vp, _vp]),
     "isingmc_do_time_steps": (C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t, _vp]),
     "isingmc_do_time_steps_timed": (C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(C.c_float)]),
@@ -688,6 +690,14 @@ class States:
     def set_option(self, name, value):
         """One of the path / tuning switches of this container (the ISINGMC_* variable's name without the prefix)."""
         _check(lib().isingmc_states_set_option(self._h, name.encode(), int(value)))
+
+    @property
+    def philox_rounds(self):
+        """Rounds of Philox4x32 in the draws of this container's sweeps: 10, or 7 after set_option("philox_rounds", 7) /
+        ISINGMC_PHILOX_ROUNDS=7 on a periodic, field-free, one-|J| checkerboard lattice."""
+        r = C.c_int()
+        _check(lib().isingmc_states_philox_rounds(self._h, C.byref(r)))
+        return r.value
 
     def set_betas(self, betas):
         b = _arr(betas, np.float64)

@@ -124,6 +124,9 @@ struct Options {
     long long moments_bytes = 4ll << 30;   // the most device memory the moment sums of one container may take (64 bits: beyond an int)
     long long overlap_series_bytes = 1ll << 30; // the most device memory the log of one overlap series may take
     long long observable_series_bytes = 1ll << 30; // ... and the log of one observable series
+    // Rounds of the sweeps' Philox calls, 10 or 7: the one switch here that selects another trajectory.  Written
+    // only through philox_rounds_set (isingmc.hip), which checks the value and the container; read wherever a call is planned
+    int philox_rounds = 10;
 
     static Options from_env()
     {
@@ -155,6 +158,7 @@ struct Options {
         if (const char *v = std::getenv("ISINGMC_MOMENTS_BYTES")) o.moments_bytes = std::atoll(v);
         if (const char *v = std::getenv("ISINGMC_OVERLAP_SERIES_BYTES")) o.overlap_series_bytes = std::atoll(v);
         if (const char *v = std::getenv("ISINGMC_OBSERVABLE_SERIES_BYTES")) o.observable_series_bytes = std::atoll(v);
+        o.philox_rounds = env_int("ISINGMC_PHILOX_ROUNDS", 10);
         return o;
     }
 
@@ -270,6 +274,7 @@ struct isingmc_states {
     // (occupancy query x CUs, asked once; -1 = not asked yet)
     int sweep_resident_wgs[2] = {-1, -1};
     unsigned sweep_resident_lds = 0;
+    int sweep_resident_rounds = 10; // ... and of which round count (Options::philox_rounds)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool has_betas = false;
     std::vector<double> betas;
@@ -552,6 +557,8 @@ IM_INTERNAL int launch_strip(isingmc_states *s, const StripPlan &P, size_t r0, s
 IM_INTERNAL int strip_check(isingmc_states *s);
 IM_INTERNAL int strip_error(int rc);
 IM_INTERNAL bool may_use_strips(const isingmc_states *s);
+// Philox4x32-7 for the sweeps: the periodic, field-free, one-|J| checkerboard lattices alone
+IM_INTERNAL bool philox_rounds_served_by(const isingmc_states *s);
 IM_INTERNAL int snapshot_take(isingmc_states *s);
 IM_INTERNAL int snapshot_restore(isingmc_states *s);
 

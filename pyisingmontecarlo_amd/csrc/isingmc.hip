@@ -131,6 +131,11 @@ extern "C" int isingmc_states_create_range(isingmc_graph *g, size_t n_total, con
         TRY(reserve(s.get(), std::max<size_t>(count, 1)));
         TRY(add_replicas(s.get(), count, all_seeds + first, initial_state));
     }
+    // ISINGMC_PHILOX_ROUNDS is the process's default for the containers the option serves; the others draw with ten rounds
+    // whatever it says (isingmc_states_philox_rounds tells).  A value that is no round count fails the creation.
+    if (s->opt.philox_rounds != 7 && s->opt.philox_rounds != 10)
+        return fail(ISINGMC_ERR_INVALID, "ISINGMC_PHILOX_ROUNDS=" + std::to_string(s->opt.philox_rounds) + ": the sweeps draw with 7 or 10 Philox rounds");
+    if (!philox_rounds_served_by(s.get())) s->opt.philox_rounds = 10;
     *states_out = s.release();
     return ISINGMC_OK;
 }
@@ -200,6 +205,28 @@ extern "C" int isingmc_states_set_timestep(isingmc_states *s, uint64_t t)
 
 extern "C" void isingmc_states_destroy(isingmc_states *s) { delete s; }
 
+bool philox_rounds_served_by(const isingmc_states *s)
+{
+    return !s->packed && s->g->kind == ISINGMC_KIND_LATTICE2D && s->g->mc_mode == MC_NONE;
+}
+
+// the option "philox_rounds": a refusal leaves the value as it was
+static int philox_rounds_set(isingmc_states *s, long value)
+{
+    if (value != 7 && value != 10)
+        return fail(ISINGMC_ERR_INVALID, "philox_rounds = " + std::to_string(value) + ": the sweeps draw with 7 or 10 Philox rounds");
+    if (value == 7 && !philox_rounds_served_by(s)) {
+        const isingmc_graph *g = s->g;
+        const std::string family = s->packed ? (s->rj ? "the replica-packed real-coupling family" : "the replica-packed bit-sliced family")
+                                   : g->kind != ISINGMC_KIND_LATTICE2D ? "the f64 CSR family"
+                                   : "the multi-class checkerboard kernels (a field, open boundaries or two |J|)";
+        return fail(ISINGMC_ERR_INVALID, "philox_rounds = 7 serves the periodic, field-free, one-|J| checkerboard lattices alone; this container runs on " +
+                                             family + ", which draws with ten rounds");
+    }
+    s->opt.philox_rounds = int(value);
+    return ISINGMC_OK;
+}
+
 extern "C" int isingmc_states_set_option(isingmc_states *s, const char *name, long value)
 {
     if (!s || !name) return fail(ISINGMC_ERR_INVALID, "NULL argument");
@@ -209,7 +236,23 @@ extern "C" int isingmc_states_set_option(isingmc_states *s, const char *name, lo
         if (bare == family) // (the whole name: "disable_packed_uniform" is a switch of its own, eight characters longer)
             return fail(ISINGMC_ERR_INVALID, "the kernel family of a container is fixed when it is created (set ISINGMC_" + std::string(family) +
                                                  " in the environment before isingmc_states_create)");
+    if (bare == "philox_rounds") return philox_rounds_set(s, value);
     if (!s->opt.set(n, value)) return fail(ISINGMC_ERR_INVALID, "unknown option '" + n + "'");
+    return ISINGMC_OK;
+}
+
+extern "C" int isingmc_graph_philox_rounds(const isingmc_graph *g, int *rounds_out)
+{
+    if (!g || !rounds_out) return fail(ISINGMC_ERR_INVALID, "NULL argument");
+    const int env = Options::from_env().philox_rounds; // (a value that is no round count fails the creation itself)
+    *rounds_out = env == 7 && g->kind == ISINGMC_KIND_LATTICE2D && g->mc_mode == MC_NONE ? 7 : 10; // a recognised lattice never runs packed
+    return ISINGMC_OK;
+}
+
+extern "C" int isingmc_states_philox_rounds(const isingmc_states *s, int *rounds_out)
+{
+    if (!s || !rounds_out) return fail(ISINGMC_ERR_INVALID, "NULL argument");
+    *rounds_out = s->opt.philox_rounds;
     return ISINGMC_OK;
 }
 
@@ -610,10 +653,11 @@ static uint32_t sweep_loop_iters(isingmc_states *s, size_t n, unsigned lds_bytes
     const auto fits = [&](uint32_t k) { return geom.nquads % (256 * k) == 0 && geom.H % (2 * k) == 0; };
     const int forced = s->opt.sweep_iters;
     if (forced) return forced > 1 && forced <= 32 && (forced & (forced - 1)) == 0 && fits(uint32_t(forced)) ? uint32_t(forced) : 1u;
-    if (s->sweep_resident_wgs[pmj] < 0 || s->sweep_resident_lds != lds_bytes) {
+    if (s->sweep_resident_wgs[pmj] < 0 || s->sweep_resident_lds != lds_bytes || s->sweep_resident_rounds != s->opt.philox_rounds) {
         s->sweep_resident_wgs[!pmj] = -1; // a container runs one of the two instantiations
-        s->sweep_resident_wgs[pmj] = lat_sweep_loop_blocks_per_cu(pmj, lds_bytes) * s->g->n_cu;
+        s->sweep_resident_wgs[pmj] = lat_sweep_loop_blocks_per_cu(pmj, lds_bytes, s->opt.philox_rounds) * s->g->n_cu;
         s->sweep_resident_lds = lds_bytes;
+        s->sweep_resident_rounds = s->opt.philox_rounds;
     }
     const size_t resident = size_t(s->sweep_resident_wgs[pmj]);
     for (uint32_t k = 16; resident > 0 && k > 1; k >>= 1) {
@@ -640,7 +684,8 @@ static int launch_lat_sweep(isingmc_states *s, uint32_t colour, const LatThr &th
             const unsigned dbg_lds = unsigned(std::max(0, s->opt.debug_sweep_lds));
             const uint32_t iters = uni ? sweep_loop_iters(s, n, dbg_lds) : 1;
             HIP_TRY(lat_launch_sweep(g->vec, !g->uniform_sign, iters, uint32_t(n), dbg_lds, stream, s->d_state + r0 * g->state_words, g->geom,
-                                     colour, t_arg, s->d_keys + r0, thr, s->has_betas ? s->d_thr + r0 : nullptr, g->d_jneg, g->jneg_uniform));
+                                     colour, t_arg, s->d_keys + r0, thr, s->has_betas ? s->d_thr + r0 : nullptr, g->d_jneg, g->jneg_uniform,
+                                     s->opt.philox_rounds));
         }
     }
     return ISINGMC_OK;
@@ -713,7 +758,7 @@ static int launch_lat_sweep_measure(isingmc_states *s, const LatThr &thr, uint64
         const size_t n = std::min(MAX_GRID_Y, s->R - r0);
         HIP_TRY(lat_launch_sweep_measure(g->vec, !g->uniform_sign, uint32_t(n), s->stream, s->d_state + r0 * g->state_words, g->geom, t_arg,
                                          s->d_keys + r0, thr, s->has_betas ? s->d_thr + r0 : nullptr, g->d_jneg, g->jneg_uniform,
-                                         out + r0 * out_stride, out_stride));
+                                         out + r0 * out_stride, out_stride, s->opt.philox_rounds));
     }
     return ISINGMC_OK;
 }
@@ -852,15 +897,15 @@ static bool resident_disabled(const isingmc_states *s) { return s->opt.disable_r
 // between dependent launches to matter (<= ISINGMC_STRIP_MAX_WG workgroups in all, default the resident limit), the geometry must cut into strips of 256 quads with at least two strips per replica, and the poll of a
 // half-sweep must fit one workgroup (2 rows of <= 128 words).  ISINGMC_STRIP=0 disables, =1 forces (tests, A/B runs).
 // resident workgroups per CU, cached per instantiation and LDS size (the occupancy query is a runtime call)
-static int strip_resident_blocks_per_cu(bool pmj, int nw, bool ladder, size_t lds)
+static int strip_resident_blocks_per_cu(bool pmj, int nw, bool ladder, size_t lds, int rounds)
 {
     static std::mutex mu;
     static std::vector<std::pair<uint64_t, int>> cache;
-    const uint64_t key = (uint64_t(lds) << 8) | (uint64_t(pmj) << 2) | (uint64_t(ladder) << 1) | uint64_t(nw == 1);
+    const uint64_t key = (uint64_t(lds) << 8) | (uint64_t(rounds == 7) << 3) | (uint64_t(pmj) << 2) | (uint64_t(ladder) << 1) | uint64_t(nw == 1);
     std::lock_guard<std::mutex> lock(mu);
     for (const auto &e : cache)
         if (e.first == key) return e.second;
-    const int n = strip_blocks_per_cu(pmj, nw, ladder, lds);
+    const int n = strip_blocks_per_cu(pmj, nw, ladder, lds, rounds);
     cache.emplace_back(key, n);
     return n;
 }
@@ -880,7 +925,7 @@ StripPlan strip_plan(const isingmc_states *s, size_t timesteps, bool ladder)
     // instantiation with its dynamic LDS (registers, LDS, wave slots), and never more than the policy bound of
     // STRIP_MAX_WAVES_PER_CU waves (beyond it the per-colour launches are faster anyway).
     const size_t lds = (size_t(2) * (S + 2) * g->geom.wpr + 16) * sizeof(uint32_t);
-    const int by_occupancy = strip_resident_blocks_per_cu(!g->uniform_sign, P.nw, ladder, lds);
+    const int by_occupancy = strip_resident_blocks_per_cu(!g->uniform_sign, P.nw, ladder, lds, s->opt.philox_rounds);
     const size_t per_cu = std::min<size_t>(size_t(STRIP_MAX_WAVES_PER_CU) / size_t(P.nw), size_t(std::max(by_occupancy, 0)));
     const size_t limit = per_cu * size_t(std::max(g->n_cu, 1)); // workgroups resident at once
     const size_t n_strips = g->geom.H / S, total = s->R * n_strips;
@@ -952,7 +997,7 @@ int launch_strip(isingmc_states *s, const StripPlan &P, size_t r0, size_t n, siz
         HIP_TRY(strip_launch(!g->uniform_sign, P.nw, unsigned(n * a.n_strips), lds, s->stream, s->d_state + r0 * g->state_words, g->geom, a, s->t,
                              uint32_t(nk), s->d_keys + r0, d_thr_steps, thr_stride, s->has_betas ? s->d_thr + r0 : nullptr, g->d_jneg,
                              g->jneg_uniform, s->d_halo + r0 * size_t(a.n_strips) * 4 * g->geom.wpr, steps_out, fin,
-                             ladder ? *ladder : StripLadder{}, uint32_t(s->R), s->d_strip_err));
+                             ladder ? *ladder : StripLadder{}, uint32_t(s->R), s->d_strip_err, s->opt.philox_rounds));
         HIP_TRY(hipEventRecord(ev, s->stream));
     }
     return ISINGMC_OK;
@@ -1219,7 +1264,7 @@ static int run_lat_resident(StepRun &c, size_t k0, size_t nk)
     const unsigned spread_threads = unsigned((size_t(g->geom.nquads) * size_t(lpq) + 63) / 64 * 64);
     const size_t spread_lds = g->state_words * sizeof(uint32_t) + size_t(g->geom.nquads) * 8 * sizeof(uint4);
     if (spread && spread_mode != 2) {
-        const int per_cu = spread_blocks_per_cu(g->vec, !g->uniform_sign, lpq, spread_threads, spread_lds);
+        const int per_cu = spread_blocks_per_cu(g->vec, !g->uniform_sign, lpq, spread_threads, spread_lds, s->opt.philox_rounds);
         spread = per_cu > 0 && R <= size_t(g->n_cu) * size_t(per_cu);
     }
     const unsigned threads = spread ? spread_threads : unsigned(std::min<size_t>(1024, (g->geom.nquads + 63) / 64 * 64));
@@ -1227,11 +1272,11 @@ static int run_lat_resident(StepRun &c, size_t k0, size_t nk)
     if (spread) {
         HIP_TRY(spread_launch(g->vec, !g->uniform_sign, lpq, unsigned(R), threads, lds, s->stream, s->d_state, g->geom, s->t, uint32_t(nk), s->d_keys,
                               c.d_thr, uint32_t(c.beta_stride ? 1 : 0), s->has_betas ? s->d_thr : nullptr, g->d_jneg, g->jneg_uniform,
-                              c.d_counts, uint32_t(R)));
+                              c.d_counts, uint32_t(R), s->opt.philox_rounds));
     } else {
         HIP_TRY(lat_launch_resident(g->vec, !g->uniform_sign, unsigned(R), threads, lds, s->stream, s->d_state, g->geom, s->t, uint32_t(nk),
                                     s->d_keys, c.d_thr, uint32_t(c.beta_stride ? 1 : 0), s->has_betas ? s->d_thr : nullptr, g->d_jneg,
-                                    g->jneg_uniform, c.d_counts));
+                                    g->jneg_uniform, c.d_counts, s->opt.philox_rounds));
     }
     s->t += nk;
     if (k0 + nk < c.timesteps && !c.d_counts) HIP_TRY(hipStreamSynchronize(s->stream)); // h_thr is reused by the next chunk

@@ -395,9 +395,9 @@ __device__ __forceinline__ bool plane_step(QuadState &st, const uint32_t rr[4], 
     return PLANE_MERGE && sel == SEL_ZERO_OPEN;
 }
 
-template <int NQ, bool MERGE = PLANE_MERGE>
+template <int NQ, bool MERGE = PLANE_MERGE, int R>
 __device__ __forceinline__ void quad_planes(QuadState (&st)[NQ], const uint32_t (&Q)[NQ], const uint32_t colour, const uint64_t t,
-                                            const uint2 key, const PhiloxVKeys &vk, const ThrBits &tb)
+                                            const uint2 key, const PhiloxVKeysR<R> &vk, const ThrBits &tb)
 {
     const uint32_t c0 = uint32_t(t);
     uint32_t prev[NQ][4]; // the words of the plane before: read only behind a plane that was left open
@@ -407,7 +407,7 @@ __device__ __forceinline__ void quad_planes(QuadState (&st)[NQ], const uint32_t 
         uint32_t rr[NQ][4];
 #pragma unroll
         for (int j = 0; j < NQ; j++) {
-            const uint4 rnd = philox4x32_10(make_uint4(c0, Q[j], DOM_LAT_SWEEP, ctr2(t, colour, p)), key, vk);
+            const uint4 rnd = philox4x32(make_uint4(c0, Q[j], DOM_LAT_SWEEP, ctr2(t, colour, p)), key, vk);
             rr[j][0] = rnd.x; rr[j][1] = rnd.y; rr[j][2] = rnd.z; rr[j][3] = rnd.w;
         }
         // threshold bit of this plane for class 3 / class 4: wave-uniform, so the per-spin threshold word is
@@ -478,22 +478,24 @@ struct QuadRandom {
     uint4 tie;
 };
 
+template <int ROUNDS>
 __device__ __forceinline__ void quad_random(QuadRandom &R, const uint32_t Q, const uint32_t colour, const uint64_t t, const uint2 key,
-                                            const PhiloxVKeys &vk)
+                                            const PhiloxVKeysR<ROUNDS> &vk)
 {
     const uint32_t c0 = uint32_t(t);
 #pragma unroll
     for (int p = 0; p < N_PLANES; p++) {
-        const uint4 rnd = philox4x32_10(make_uint4(c0, Q, DOM_LAT_SWEEP, ctr2(t, colour, p)), key, vk);
+        const uint4 rnd = philox4x32(make_uint4(c0, Q, DOM_LAT_SWEEP, ctr2(t, colour, p)), key, vk);
         R.rr[p][0] = rnd.x; R.rr[p][1] = rnd.y; R.rr[p][2] = rnd.z; R.rr[p][3] = rnd.w;
     }
-    R.tie = philox4x32_10(make_uint4(c0, Q, DOM_LAT_SWEEP, ctr2(t, colour, N_PLANES)), key, vk);
+    R.tie = philox4x32(make_uint4(c0, Q, DOM_LAT_SWEEP, ctr2(t, colour, N_PLANES)), key, vk);
 }
 
 // residual stage: spins whose prefix equals the threshold's top bits (ties) draw 32 more bits; a tie that is won is recorded
 // in st.lt ("below the threshold"), which quad_new_words folds into the new words
+template <int R>
 __device__ __forceinline__ void quad_ties(QuadState &st, const uint32_t Q, const uint32_t colour, const uint64_t t,
-                                          const uint2 key, const PhiloxVKeys &vk, const ThrBits &tb,
+                                          const uint2 key, const PhiloxVKeysR<R> &vk, const ThrBits &tb,
                                           const uint4 *first_call = nullptr)
 {
     const uint32_t c0 = uint32_t(t), c1 = Q;
@@ -504,7 +506,7 @@ __device__ __forceinline__ void quad_ties(QuadState &st, const uint32_t Q, const
 #endif
         // the first residual call is hoisted: inside the divergent per-word loops below it would be
         // issued once per loop (up to 4x per wave) instead of once
-        const uint4 rnd = first_call ? *first_call : philox4x32_10(make_uint4(c0, c1, DOM_LAT_SWEEP, ctr2(t, colour, N_PLANES)), key, vk);
+        const uint4 rnd = first_call ? *first_call : philox4x32(make_uint4(c0, c1, DOM_LAT_SWEEP, ctr2(t, colour, N_PLANES)), key, vk);
 #ifdef ISINGMC_TIMING_ONLY_NO_TIE_LOOPS // diagnostic build (results are wrong): the residual call kept, the per-tie loops replaced
         // by ONE compare per word -- the floor of any reorganisation of the loops (wave-level compaction included)
         {
@@ -546,7 +548,7 @@ __device__ __forceinline__ void quad_ties(QuadState &st, const uint32_t Q, const
                     const uint32_t b = __ffs(m) - 1;
                     m &= m - 1;
                     if (nres != 0 && (nres & 3u) == 0)
-                        w = philox4x32_10(make_uint4(c0, c1, DOM_LAT_SWEEP, ctr2(t, colour, N_PLANES + (nres >> 2))), key, vk);
+                        w = philox4x32(make_uint4(c0, c1, DOM_LAT_SWEEP, ctr2(t, colour, N_PLANES + (nres >> 2))), key, vk);
                     const uint32_t lo = ((st.eq4[q] >> b) & 1u) ? tb.lo4 : tb.lo3;
                     if (sel4(w, nres & 3u) < lo) st.lt[q] |= 1u << b;
                     nres++;
@@ -557,9 +559,9 @@ __device__ __forceinline__ void quad_ties(QuadState &st, const uint32_t Q, const
 }
 
 // The 128 flip decisions of quad Q from its loaded words, applied: neww[q] = own[q] with the bits of the flipping spins inverted.
-template <bool PMJ, bool MERGE = PLANE_MERGE>
+template <bool PMJ, bool MERGE = PLANE_MERGE, int R>
 __device__ __forceinline__ void quad_flips(const uint32_t own[4], const QuadNbr &n, const uint32_t colour, const uint64_t t,
-                                           const uint2 key, const PhiloxVKeys &vk,
+                                           const uint2 key, const PhiloxVKeysR<R> &vk,
                                            const LatThr thr, const QuadSigns &js, const uint32_t jneg_uniform,
                                            const uint32_t Q, uint32_t neww[4])
 {
@@ -573,9 +575,9 @@ __device__ __forceinline__ void quad_flips(const uint32_t own[4], const QuadNbr 
 }
 
 // the same decisions from random words drawn earlier (quad_random)
-template <bool PMJ>
+template <bool PMJ, int ROUNDS>
 __device__ __forceinline__ void quad_flips_pre(const uint32_t own[4], const QuadNbr &n, const uint32_t colour, const uint64_t t,
-                                               const uint2 key, const PhiloxVKeys &vk,
+                                               const uint2 key, const PhiloxVKeysR<ROUNDS> &vk,
                                                const LatThr thr, const QuadSigns &js, const uint32_t jneg_uniform, const uint32_t Q,
                                                const QuadRandom &R, uint32_t neww[4])
 {
@@ -692,9 +694,9 @@ __device__ __forceinline__ void store_pending(const Mem &mem, const PendingQuad 
     }
 }
 
-template <bool VEC, bool PMJ, bool UNI, typename Mem, bool MEASURE = false>
+template <bool VEC, bool PMJ, bool UNI, typename Mem, bool MEASURE = false, int R>
 __device__ __forceinline__ void update_quad(const Mem &mem, const LatGeom &g, const uint32_t colour, const uint64_t t, const uint2 key,
-                                            const PhiloxVKeys &vk, const LatThr thr, const uint32_t *__restrict__ jn,
+                                            const PhiloxVKeysR<R> &vk, const LatThr thr, const uint32_t *__restrict__ jn,
                                             const uint32_t jneg_uniform, const uint32_t gid, uint32_t *sat = nullptr,
                                             uint32_t *up = nullptr, PendingQuad *pending = nullptr)
 {
@@ -748,7 +750,7 @@ __device__ __forceinline__ void update_quad(const Mem &mem, const LatGeom &g, co
 // Colour-1 half-sweep that also measures (energies after every timestep, lattice.rs:445-455): out[r * stride] +=
 // satisfied bonds, out[r * stride + 1] += up spins of replica r after this timestep -- what lat_measure_kernel
 // would count in a second pass over the planes.
-template <bool VEC, bool PMJ, bool UNI>
+template <bool VEC, bool PMJ, bool UNI, int ROUNDS = 10>
 __global__ __launch_bounds__(256, ISINGMC_MEASURE_WAVES) void lat_sweep_measure_kernel(
     uint32_t *__restrict__ state, const LatGeom g, const uint64_t t, const uint2 *__restrict__ keys, const LatThr thr_uniform,
     const LatThr *__restrict__ thr_replica, const uint32_t *__restrict__ jneg, const uint32_t jneg_uniform,
@@ -768,7 +770,7 @@ __global__ __launch_bounds__(256, ISINGMC_MEASURE_WAVES) void lat_sweep_measure_
     PendingQuad pending;
     if (gid < g.nquads) {
         const uint2 key = keys[r];
-        update_quad<VEC, PMJ, UNI, BufPlanes, true>(mem, g, colour, t, key, philox_vkeys(key), thr_replica ? thr_replica[r] : thr_uniform,
+        update_quad<VEC, PMJ, UNI, BufPlanes, true>(mem, g, colour, t, key, philox_vkeys<ROUNDS>(key), thr_replica ? thr_replica[r] : thr_uniform,
                                                     PMJ ? jneg + size_t(colour) * 4 * g.wpp : nullptr, jneg_uniform, gid, &sat, &up, &pending);
     }
 #pragma unroll
@@ -784,7 +786,7 @@ __global__ __launch_bounds__(256, ISINGMC_MEASURE_WAVES) void lat_sweep_measure_
     if (gid < g.nquads) store_pending<VEC>(mem, pending);
 }
 
-template <bool VEC, bool PMJ, bool UNI>
+template <bool VEC, bool PMJ, bool UNI, int ROUNDS = 10>
 __global__ __launch_bounds__(256) void lat_sweep_kernel(
     uint32_t *__restrict__ state, const LatGeom g, const uint32_t colour, const uint64_t t,
     const uint2 *__restrict__ keys, const LatThr thr_uniform, const LatThr *__restrict__ thr_replica,
@@ -798,7 +800,7 @@ __global__ __launch_bounds__(256) void lat_sweep_kernel(
     mem.own_off = colour * g.wpp * 4u;
     mem.oth_off = (1 - colour) * g.wpp * 4u;
     const uint2 key = keys[r];
-    update_quad<VEC, PMJ, UNI>(mem, g, colour, t, key, philox_vkeys(key), thr_replica ? thr_replica[r] : thr_uniform,
+    update_quad<VEC, PMJ, UNI>(mem, g, colour, t, key, philox_vkeys<ROUNDS>(key), thr_replica ? thr_replica[r] : thr_uniform,
                                PMJ ? jneg + size_t(colour) * 4 * g.wpp : nullptr, jneg_uniform, gid);
 }
 
@@ -816,7 +818,7 @@ __global__ __launch_bounds__(256) void lat_sweep_kernel(
 // and the quad index (Philox counter word 1) takes one add.  The wave's first row is carried on the scalar
 // unit: the iteration in which the wave holds row H-1 wraps its rows per lane, as load_quad_uni does; so does, in all
 // its iterations, the wave that starts in row 0.
-template <bool PMJ>
+template <bool PMJ, int ROUNDS = 10>
 __global__ __launch_bounds__(256) void lat_sweep_loop_kernel(
     uint32_t *__restrict__ state, const LatGeom g, const uint32_t colour, const uint64_t t,
     const uint2 *__restrict__ keys, const LatThr thr_uniform, const LatThr *__restrict__ thr_replica,
@@ -831,7 +833,7 @@ __global__ __launch_bounds__(256) void lat_sweep_loop_kernel(
     mem.own_off = colour * g.wpp * 4u;
     mem.oth_off = (1 - colour) * g.wpp * 4u;
     const uint2 key = keys[r];
-    const PhiloxVKeys vk = philox_vkeys(key);
+    const PhiloxVKeysR<ROUNDS> vk = philox_vkeys<ROUNDS>(key);
     const ThrBits tb = thr_bits(thr_replica ? thr_replica[r] : thr_uniform);
     const uint32_t *jn = PMJ ? jneg + size_t(colour) * 4 * g.wpp : nullptr;
 
@@ -955,7 +957,7 @@ __global__ __launch_bounds__(256) void lat_measure_kernel(
 // configurations are bit-identical to the per-colour launches of lat_sweep_kernel.
 // steps_out (optional): satisfied bonds / up spins after every timestep, [step][replica][2].
 // ------------------------------------------------------------------------------------------------
-template <bool VEC, bool PMJ>
+template <bool VEC, bool PMJ, int ROUNDS = 10>
 __global__ __launch_bounds__(1024) void lat_resident_kernel(
     uint32_t *__restrict__ state, const LatGeom g, const uint64_t t0, const uint32_t timesteps,
     const uint2 *__restrict__ keys, const LatThr *__restrict__ thr_steps, const uint32_t thr_stride,
@@ -969,7 +971,7 @@ __global__ __launch_bounds__(1024) void lat_resident_kernel(
     for (uint32_t i = tid; i < g.wpp / 2; i += nthreads) // 2*wpp words = wpp/2 uint4
         reinterpret_cast<uint4 *>(planes)[i] = reinterpret_cast<const uint4 *>(mine)[i];
     const uint2 key = keys[r];
-    const PhiloxVKeys vk = philox_vkeys(key);
+    const PhiloxVKeysR<ROUNDS> vk = philox_vkeys<ROUNDS>(key);
     __syncthreads();
     for (uint32_t k = 0; k < timesteps; k++) {
         const LatThr thr = thr_replica ? thr_replica[r] : thr_steps[size_t(k) * thr_stride];

@@ -29,19 +29,20 @@ constexpr uint32_t MEASURE_QUADS_PER_THREAD = 16; // quads a thread of lat_measu
 constexpr uint32_t LDS_RESIDENT_MAX_BYTES = 64 * 1024; // both planes of a replica of the LDS-resident kernels
 
 // ---- launchers (lattice_kernels.hip).  vec / pmj: quads inside one row (wpr % 4 == 0) / couplings of both signs; grid.y or
-// grid.x = n_replicas, whose planes, keys and thr_replica entries (nullptr: thr for all) begin at the pointers passed
+// grid.x = n_replicas, whose planes, keys and thr_replica entries (nullptr: thr for all) begin at the pointers passed.
+// rounds: of the sweeps' Philox calls, 10 or 7 (anything else is hipErrorInvalidValue) -- the launcher picks the instantiation
 hipError_t lat_launch_init(hipStream_t stream, uint32_t *state, const LatGeom &g, const uint2 *keys, uint32_t first_replica, uint32_t n_replicas);
 // one colour of one timestep.  iters quads per thread: 1 = lat_sweep_kernel (with the division-free mapping when vec and
 // g.cols_log2 >= 0), else lat_sweep_loop_kernel -- that mapping only, iters * 256 divides g.nquads and 2 * iters divides g.H
 hipError_t lat_launch_sweep(bool vec, bool pmj, uint32_t iters, uint32_t n_replicas, unsigned lds_bytes, hipStream_t stream, uint32_t *state,
                             const LatGeom &g, uint32_t colour, uint64_t t, const uint2 *keys, const LatThr &thr, const LatThr *thr_replica,
-                            const uint32_t *jneg, uint32_t jneg_uniform);
-// workgroups of lat_sweep_loop_kernel<pmj> one compute unit holds at once with lds_bytes of LDS each; 0 when the query fails
-int lat_sweep_loop_blocks_per_cu(bool pmj, unsigned lds_bytes);
+                            const uint32_t *jneg, uint32_t jneg_uniform, int rounds = 10);
+// workgroups of lat_sweep_loop_kernel<pmj, rounds> one compute unit holds at once with lds_bytes of LDS each; 0 when the query fails
+int lat_sweep_loop_blocks_per_cu(bool pmj, unsigned lds_bytes, int rounds = 10);
 // the colour-1 half-sweep fused with the measurement: out[r * out_stride + 2 slot] += satisfied bonds, MEASURE_SLOTS slots
 hipError_t lat_launch_sweep_measure(bool vec, bool pmj, uint32_t n_replicas, hipStream_t stream, uint32_t *state, const LatGeom &g, uint64_t t,
                                     const uint2 *keys, const LatThr &thr, const LatThr *thr_replica, const uint32_t *jneg,
-                                    uint32_t jneg_uniform, unsigned long long *out, size_t out_stride);
+                                    uint32_t jneg_uniform, unsigned long long *out, size_t out_stride, int rounds = 10);
 // out[r * out_stride] += satisfied bonds, out[r * out_stride + 1] += up spins
 hipError_t lat_launch_measure(bool vec, bool pmj, uint32_t n_replicas, hipStream_t stream, const uint32_t *state, const LatGeom &g,
                               const uint32_t *jneg, uint32_t jneg_uniform, unsigned long long *out, size_t out_stride);
@@ -49,6 +50,6 @@ hipError_t lat_launch_measure(bool vec, bool pmj, uint32_t n_replicas, hipStream
 hipError_t lat_launch_resident(bool vec, bool pmj, unsigned n_replicas, unsigned threads, size_t lds_bytes, hipStream_t stream, uint32_t *state,
                                const LatGeom &g, uint64_t t0, uint32_t timesteps, const uint2 *keys, const LatThr *thr_steps,
                                uint32_t thr_stride, const LatThr *thr_replica, const uint32_t *jneg, uint32_t jneg_uniform,
-                               unsigned long long *steps_out);
+                               unsigned long long *steps_out, int rounds = 10);
 
 } // namespace isingmc

@@ -1,6 +1,8 @@
 // Philox4x32-10 counter-based RNG for gfx950 device code (Salmon et al., SC'11).
 // One call = 10 rounds of two 32x32->64 multiplies (v_mad_u64_u32 / v_mul_hi_u32) + xors; the key
 // schedule is wave-uniform (the key is per replica) and stays on the scalar unit.
+// The sweeps of the periodic, field-free checkerboard lattices may ask for Philox4x32-7 instead: the forms below
+// exist for R = 10 and R = 7 rounds, R a compile-time constant.  Rounds 1-3 are the same code for both; R counts the late rounds only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -34,8 +36,12 @@ __device__ __forceinline__ void philox_round(uint4 &c, uint2 &k)
 // and 3 have one uniform multiply each.  Those rounds are written with plain xors so that hipcc keeps
 // their uniform halves on the scalar unit (s_mul_hi_u32 / s_mul_i32 / s_xor); from round 4 on everything
 // varies and the xors are v_bitop3.
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k)
+constexpr bool philox_rounds_served(int R) { return R == 7 || R == 10; }
+
+template <int R>
+__device__ __forceinline__ uint4 philox4x32(uint4 c, uint2 k)
 {
+    static_assert(philox_rounds_served(R), "Philox4x32-R: R = 7 or 10");
 #ifdef ISINGMC_TIMING_ONLY_CHEAP_RNG // diagnostic build: what everything except Philox costs (results are wrong)
     return make_uint4(c.x ^ k.x ^ c.y, c.y * 3u + c.w, c.z ^ k.y ^ (c.y >> 3), c.w + c.y);
 #endif
@@ -43,9 +49,11 @@ __device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k)
     philox_round<false>(c, k);
     philox_round<false>(c, k);
 #pragma unroll
-    for (int r = 3; r < 10; r++) philox_round<true>(c, k);
+    for (int r = 3; r < R; r++) philox_round<true>(c, k);
     return c;
 }
+
+__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) { return philox4x32<10>(c, k); }
 
 // ---- calls that differ only in counter word 3 (and whose word 1 is the only lane-varying input) ----------------------------
 // Rounds 1-3 of such calls, spelled out (M0, M1 the multipliers; W0, W1 the key increments; c = (c0, c1, c2, c3), key (kx, ky)):
@@ -88,34 +96,47 @@ __device__ __forceinline__ PhiloxShared philox_shared(uint32_t c1, uint32_t c2, 
     return PhiloxShared{uint32_t(P), uint32_t(V >> 32), uint32_t(V)};
 }
 
-// rounds 4-10 of the call whose uniform words are (s1, s2, s3)
-__device__ __forceinline__ uint4 philox4x32_10_late(const PhiloxShared &sh, uint32_t s1, uint32_t s2, uint32_t s3, uint2 key)
+// rounds 4-R of the call whose uniform words are (s1, s2, s3)
+template <int R>
+__device__ __forceinline__ uint4 philox4x32_late(const PhiloxShared &sh, uint32_t s1, uint32_t s2, uint32_t s3, uint2 key)
 {
+    static_assert(philox_rounds_served(R), "Philox4x32-R: R = 7 or 10");
     uint4 c = make_uint4(sh.v_hi ^ s1, sh.v_lo, sh.p_lo ^ s2, s3);
 #ifdef ISINGMC_TIMING_ONLY_CHEAP_RNG
     return c;
 #endif
     uint2 k = make_uint2(key.x + 3u * PHILOX_W0, key.y + 3u * PHILOX_W1);
 #pragma unroll
-    for (int r = 3; r < 10; r++) philox_round<true>(c, k);
+    for (int r = 3; r < R; r++) philox_round<true>(c, k);
     return c;
 }
 
-// The round keys of rounds 4-10 in VECTOR registers.  Measured on gfx950 (tools/ubench/valu_forms.hip): a VALU
+__device__ __forceinline__ uint4 philox4x32_10_late(const PhiloxShared &sh, uint32_t s1, uint32_t s2, uint32_t s3, uint2 key)
+{
+    return philox4x32_late<10>(sh, s1, s2, s3, key);
+}
+
+// The round keys of rounds 4-R in VECTOR registers.  Measured on gfx950 (tools/ubench/valu_forms.hip): a VALU
 // instruction with an SGPR source issues in 4.3 cycles per wave, the same instruction on VGPRs only in 2.5
 // (v_xor, v_and, v_add, v_bitop3, shifts; everything else -- multiplies, v_and_or, v_alignbit, v_cndmask -- is
-// 4.2 either way).  The xor3 of a Philox round has the (wave-uniform) round key as one source: 14 per call.
+// 4.2 either way).  The xor3 of a Philox round has the (wave-uniform) round key as one source: 14 per call at R = 10.
 // Holding those 14 keys in VGPRs, written once per thread, takes 26 cycles off every call (150 -> 124).
 // The v_mov is inline asm so that the compiler cannot fold the SGPR back into the uses.
-struct PhiloxVKeys {
-    uint32_t kx[7], ky[7];
+// R = 7: four late rounds, four key pairs.
+template <int R>
+struct PhiloxVKeysR {
+    static_assert(philox_rounds_served(R), "Philox4x32-R: R = 7 or 10");
+    static constexpr int late_rounds = R - 3;
+    uint32_t kx[late_rounds], ky[late_rounds];
 };
+using PhiloxVKeys = PhiloxVKeysR<10>;
 
-__device__ __forceinline__ PhiloxVKeys philox_vkeys(uint2 k)
+template <int R = 10>
+__device__ __forceinline__ PhiloxVKeysR<R> philox_vkeys(uint2 k)
 {
-    PhiloxVKeys v;
+    PhiloxVKeysR<R> v;
 #pragma unroll
-    for (int r = 0; r < 7; r++) {
+    for (int r = 0; r < R - 3; r++) {
         const uint32_t x = k.x + uint32_t(r + 3) * 0x9E3779B9u, y = k.y + uint32_t(r + 3) * 0xBB67AE85u;
 #ifdef ISINGMC_AB_SCALAR_KEYS // A/B build: the keys stay SGPR operands
         v.kx[r] = x;
@@ -128,7 +149,9 @@ __device__ __forceinline__ PhiloxVKeys philox_vkeys(uint2 k)
     return v;
 }
 
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k, const PhiloxVKeys &vk)
+// the round count comes with the keys: a kernel picks it once, where it makes them
+template <int R>
+__device__ __forceinline__ uint4 philox4x32(uint4 c, uint2 k, const PhiloxVKeysR<R> &vk)
 {
 #ifdef ISINGMC_TIMING_ONLY_CHEAP_RNG
     return make_uint4(c.x ^ k.x ^ c.y, c.y * 3u + c.w, c.z ^ k.y ^ (c.y >> 3), c.w + c.y);
@@ -136,13 +159,8 @@ __device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k, const PhiloxVKe
     philox_round<false>(c, k);
     philox_round<false>(c, k);
     philox_round<false>(c, k);
-#ifdef ISINGMC_TIMING_ONLY_PHILOX_ROUNDS // diagnostic build (another generator: results differ): Philox4x32-R for R = 7 .. 10
-    constexpr int late_rounds = ISINGMC_TIMING_ONLY_PHILOX_ROUNDS - 3;
-#else
-    constexpr int late_rounds = 7;
-#endif
 #pragma unroll
-    for (int r = 0; r < late_rounds; r++) {
+    for (int r = 0; r < R - 3; r++) {
         const uint64_t p0 = uint64_t(0xD2511F53u) * c.x;
         const uint64_t p1 = uint64_t(0xCD9E8D57u) * c.z;
         c = make_uint4(__builtin_amdgcn_bitop3_b32(uint32_t(p1 >> 32), c.y, vk.kx[r], 0x96), uint32_t(p1),
@@ -150,6 +168,8 @@ __device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k, const PhiloxVKe
     }
     return c;
 }
+
+__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k, const PhiloxVKeys &vk) { return philox4x32(c, k, vk); }
 
 // counter word 2: (t >> 32) in the top 16 bits, colour in bits 8..15, call index in bits 0..7
 __device__ __forceinline__ uint32_t ctr2(uint64_t t, uint32_t colour, uint32_t call)

@@ -300,6 +300,16 @@ public:
     // (isingmc_states_set_icm_every; 0 = off, the default): the non-local move for +-J glasses.  Applied to every container the
     // run_* methods create; the device blocks then hold whole pairs.
     void set_replica_cluster_update_every(size_t k) { icm_every_ = k; }
+    // extension: the rounds of Philox4x32 in the draws of the Metropolis sweeps, 10 or 7 (option "philox_rounds").
+    // Applied to every container the run_* methods create; a graph whose containers run on a family that 7 does not serve raises
+    // ValueError there -- never a run with ten rounds instead.
+    void set_rng_rounds(int rounds)
+    {
+        if (rounds != 7 && rounds != 10) throw py::value_error("rng_rounds must be 7 or 10 (rounds of Philox4x32 in the sweeps' draws)");
+        rng_rounds_ = rounds;
+    }
+    // the option on a container just created (nothing when set_rng_rounds was never called: the environment's default stays)
+    int apply_rng_rounds(isingmc_states *s) const { return rng_rounds_ ? isingmc_states_set_option(s, "philox_rounds", *rng_rounds_) : ISINGMC_OK; }
     py::dict engine_info(std::optional<size_t> num_experiments)
     {
         isingmc_graph_info_t info;
@@ -308,6 +318,9 @@ public:
         d["stable_path"] = bool(info.stable_path);
         d["cluster_update_every"] = cluster_every_;
         d["replica_cluster_update_every"] = icm_every_;
+        int rounds = 10; // what set_rng_rounds asked for, else what a container created now would start with
+        check(isingmc_graph_philox_rounds(graph()->g, &rounds));
+        d["rng_rounds"] = rng_rounds_.value_or(rounds);
         if (num_experiments) { // the kernel family a call with that many experiments runs on
             int family = 0;
             check(isingmc_graph_family_for(graph()->g, *num_experiments, &family));
@@ -582,6 +595,7 @@ public:
             h.graph = gh;
             const uint8_t *ini = initial_state_.empty() ? nullptr : initial_state_.data();
             rc = isingmc_states_create(gh->g, R, seeds.data(), ini, &h.s);
+            if (rc == ISINGMC_OK) rc = apply_rng_rounds(h.s);
             if (rc == ISINGMC_OK && cluster_every_) rc = isingmc_states_set_cluster_every(h.s, cluster_every_);
             if (rc == ISINGMC_OK && icm_every_) rc = isingmc_states_set_icm_every(h.s, icm_every_);
             // the update points are the resamplings and the end of the run: a period no timestep reaches leaves the sweeps uncut
@@ -733,6 +747,7 @@ private:
         const auto run_block = [&](Block &blk) {
             isingmc_states *st = nullptr;
             blk.rc = isingmc_states_create_range(graphs_[blk.slot]->g, num_experiments, seeds.data(), blk.lo, blk.hi - blk.lo, ini, &st);
+            if (blk.rc == ISINGMC_OK) blk.rc = apply_rng_rounds(st);
             if (blk.rc == ISINGMC_OK && cluster_every_) blk.rc = isingmc_states_set_cluster_every(st, cluster_every_);
             if (blk.rc == ISINGMC_OK && icm_every_) blk.rc = isingmc_states_set_icm_every(st, icm_every_);
             if (blk.rc == ISINGMC_OK) blk.rc = body(st, blk.lo - lo);
@@ -777,6 +792,7 @@ private:
     std::vector<int> devices_;  // one block of experiments per entry (ISINGMC_DEVICES; an ordinal may repeat)
     bool force_general_ = false, stable_path_ = false;
     size_t cluster_every_ = 0, icm_every_ = 0;
+    std::optional<int> rng_rounds_; // set_rng_rounds
     std::vector<std::shared_ptr<GraphHandle>> graphs_;
 };
 
@@ -886,6 +902,15 @@ public:
         return s;
     }
     size_t get_num_graphs() const { return isingmc_states_count(st_->s); }
+    // extension: the rounds of Philox4x32 in the sweeps' draws of the persistent replicas, 10 or 7, from the next call
+    // on; ValueError where the option "philox_rounds" refuses (another value, or 7 on a family it does not serve)
+    void set_rng_rounds(int rounds) { check(isingmc_states_set_option(st_->s, "philox_rounds", rounds)); }
+    int get_rng_rounds() const
+    {
+        int rounds = 10;
+        check(isingmc_states_philox_rounds(st_->s, &rounds));
+        return rounds;
+    }
     // extension: spin and link overlaps between the persistent replicas, exact integers counted on the device.
     // pairs: None = the replicas (2 p, 2 p + 1), or an integer [n, 2] array of graph indices.  Returns (spin, link) as int64[n]
     // (link = None when not asked for); ValueError where isingmc_overlaps refuses.
@@ -1152,6 +1177,7 @@ PYBIND11_MODULE(_py_monte_carlo, m)
         .def("set_stable_path", &Lattice::set_stable_path, "stable"_a)
         .def("set_cluster_update_every", &Lattice::set_cluster_update_every, "k"_a)
         .def("set_replica_cluster_update_every", &Lattice::set_replica_cluster_update_every, "k"_a)
+        .def("set_rng_rounds", [](py::object self, int rounds) { self.cast<Lattice &>().set_rng_rounds(rounds); return self; }, "rounds"_a)
         .def("engine_info", &Lattice::engine_info, "num_experiments"_a = py::none())
         .def("run_monte_carlo", &Lattice::run_monte_carlo, "beta"_a, "timesteps"_a, "num_experiments"_a,
              "only_basic_moves"_a = py::none(), "edge_move_importance_sampling"_a = py::none(),
@@ -1206,6 +1232,8 @@ PYBIND11_MODULE(_py_monte_carlo, m)
         .def("get_energies", &ClassicIsing::get_energies)
         .def("get_states", &ClassicIsing::get_states)
         .def("get_num_graphs", &ClassicIsing::get_num_graphs)
+        .def("set_rng_rounds", [](py::object self, int rounds) { self.cast<ClassicIsing &>().set_rng_rounds(rounds); return self; }, "rounds"_a)
+        .def("get_rng_rounds", &ClassicIsing::get_rng_rounds)
         .def("get_overlaps", &ClassicIsing::get_overlaps, "pairs"_a = py::none(), "link"_a = true)
         .def("get_overlaps_by_class", &ClassicIsing::get_overlaps_by_class, "classes"_a, "n_classes"_a = py::none(), "pairs"_a = py::none())
         .def("set_measure_overlaps_every", &ClassicIsing::set_measure_overlaps_every, "k"_a, "link"_a = true, "classes"_a = py::none(),

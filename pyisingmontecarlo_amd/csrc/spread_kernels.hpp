@@ -14,7 +14,7 @@ namespace isingmc {
 // exactly as quad_flips_pre does from pre-drawn words.  Same counters, same decisions: bit-identical to that kernel.
 static_assert(N_PLANES == 7, "lat_resident_spread_kernel: eight lanes per quad = 7 bit planes + the first residual call");
 // LPQ = lanes per quad: 8 (one call each), 4 or 2 (two / four calls each) -- whatever lets 1024 threads cover the colour
-template <bool VEC, bool PMJ, int LPQ>
+template <bool VEC, bool PMJ, int LPQ, int ROUNDS = 10>
 __global__ __launch_bounds__(1024) void lat_resident_spread_kernel(
     uint32_t *__restrict__ state, const LatGeom g, const uint64_t t0, const uint32_t timesteps,
     const uint2 *__restrict__ keys, const LatThr *__restrict__ thr_steps, const uint32_t thr_stride,
@@ -29,7 +29,7 @@ __global__ __launch_bounds__(1024) void lat_resident_spread_kernel(
     for (uint32_t i = tid; i < g.wpp / 2; i += nthreads)
         reinterpret_cast<uint4 *>(planes)[i] = reinterpret_cast<const uint4 *>(mine)[i];
     const uint2 key = keys[r];
-    const PhiloxVKeys vk = philox_vkeys(key);
+    const PhiloxVKeysR<ROUNDS> vk = philox_vkeys<ROUNDS>(key);
     const uint32_t quad = tid / LPQ, call = tid % LPQ; // blockDim.x >= LPQ * nquads (host)
     __syncthreads();
     for (uint32_t k = 0; k < timesteps; k++) {
@@ -39,7 +39,7 @@ __global__ __launch_bounds__(1024) void lat_resident_spread_kernel(
             if (quad < g.nquads) { // Q == the quad's index under the row-major mapping (thread_to_quad<false>)
 #pragma unroll
                 for (uint32_t c = 0; c < 8 / LPQ; c++)
-                    s_rand[8 * quad + call + LPQ * c] = philox4x32_10(make_uint4(uint32_t(t), quad, DOM_LAT_SWEEP, ctr2(t, colour, call + LPQ * c)), key, vk);
+                    s_rand[8 * quad + call + LPQ * c] = philox4x32(make_uint4(uint32_t(t), quad, DOM_LAT_SWEEP, ctr2(t, colour, call + LPQ * c)), key, vk);
             }
             __syncthreads();
             if (tid < g.nquads) { // the deciding lanes are the FIRST nquads threads: whole waves, not every eighth lane of all of them

@@ -116,10 +116,10 @@ __device__ __forceinline__ size_t strip_granule(const LatGeom &g, uint32_t strip
     return ((size_t(strip) * 2 + plane) * 2 + side) * g.wpr;
 }
 
-template <bool PMJ>
+template <bool PMJ, int ROUNDS>
 __device__ __forceinline__ void strip_update_quad(uint32_t *lds, const uint32_t PL, const LatGeom &g, const uint32_t colour,
                                                   const uint32_t yl, const uint32_t col, const uint32_t Q, const bool odd, const uint64_t t,
-                                                  const uint2 key, const PhiloxVKeys &vk, const LatThr thr,
+                                                  const uint2 key, const PhiloxVKeysR<ROUNDS> &vk, const LatThr thr,
                                                   const uint32_t *__restrict__ jn, const uint32_t jneg_uniform, const QuadRandom &R,
                                                   uint32_t new_words[4], const bool measure, uint32_t &sat, uint32_t &up)
 {
@@ -156,7 +156,8 @@ __device__ __forceinline__ void strip_update_quad(uint32_t *lds, const uint32_t 
 // after every timestep, [step][replica][2], zeroed by the host (the strips of a replica add into it).
 // fin (optional): energies of the final configurations, see StripFinal.
 // LAD: exchange rounds inside the launch (StripLadder); a separate instantiation, so that launches without them pay nothing
-template <bool PMJ, int NW, bool LAD>
+// ROUNDS: of the sweeps' Philox calls; the exchange decisions of the rounds inside the launch draw with ten whatever it is
+template <bool PMJ, int NW, bool LAD, int ROUNDS = 10>
 __global__ __launch_bounds__(64 * NW, 4) void lat_strip_kernel(
     uint32_t *__restrict__ state, const LatGeom g, const StripArgs a, const uint64_t t0, const uint32_t timesteps,
     const uint2 *__restrict__ keys, const LatThr *__restrict__ thr_steps, const uint32_t thr_stride,
@@ -205,7 +206,7 @@ __global__ __launch_bounds__(64 * NW, 4) void lat_strip_kernel(
         my_rung = __builtin_amdgcn_readfirstlane(red[9]);
     }
     const uint2 key = keys[r];
-    const PhiloxVKeys vk = philox_vkeys(key);
+    const PhiloxVKeysR<ROUNDS> vk = philox_vkeys<ROUNDS>(key);
 
     // thread -> quad of the strip.  NW = 4: a pair of waves shares 2 * rpw consecutive rows, wave 0 the even ones, wave 1
     // the odd ones (rpw = 64 / quads per row), so the row parity is uniform per wavefront (as thread_to_quad<true>).

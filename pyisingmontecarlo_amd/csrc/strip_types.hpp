@@ -57,14 +57,15 @@ struct StripLadder {
     unsigned long long *stats;             // ladder statistics: the block of PtStats; nullptr: off (tested at run time)
 };
 
-// one launch: `blocks` strips of `nw` waves (1 or 4) each; arguments as lat_strip_kernel
+// one launch: `blocks` strips of `nw` waves (1 or 4) each; arguments as lat_strip_kernel.  rounds: of the sweeps' Philox calls,
+// 10 or 7 (anything else is hipErrorInvalidValue); the exchange decisions of a ladder's rounds inside the launch draw with ten
 hipError_t strip_launch(bool pmj, int nw, unsigned blocks, size_t lds_bytes, hipStream_t stream, uint32_t *state, const LatGeom &g,
                         const StripArgs &a, uint64_t t0, uint32_t timesteps, const uint2 *keys, const LatThr *thr_steps,
                         uint32_t thr_stride, const LatThr *thr_replica, const uint32_t *jneg, uint32_t jneg_uniform,
                         unsigned long long *halo, unsigned long long *steps_out, const StripFinal &fin, const StripLadder &lad,
-                        uint32_t n_replicas, uint32_t *err);
+                        uint32_t n_replicas, uint32_t *err, int rounds = 10);
 
-// resident workgroups per CU of the instantiation (pmj, nw, ladder) at `lds_bytes` of dynamic LDS: hipOccupancyMaxActiveBlocksPerMultiprocessor
-int strip_blocks_per_cu(bool pmj, int nw, bool ladder, size_t lds_bytes);
+// resident workgroups per CU of the instantiation (pmj, nw, ladder, rounds) at `lds_bytes` of dynamic LDS: hipOccupancyMaxActiveBlocksPerMultiprocessor
+int strip_blocks_per_cu(bool pmj, int nw, bool ladder, size_t lds_bytes, int rounds = 10);
 
 } // namespace isingmc

@@ -344,7 +344,7 @@ class _GroupLadder(_StreamLadder):
 
 
 class ClassicalTempering:
-    def __init__(self, edges, seed=None, *, group=None, device=None, engine_factory=None, devices=None, group_backend=0, copies=1):
+    def __init__(self, edges, seed=None, *, group=None, device=None, engine_factory=None, devices=None, group_backend=0, copies=1, rng_rounds=None):
         """devices: HIP ordinals of an IN-PROCESS ladder -- shard k of the slots lives on devices[k] and the exchange step runs
         through the library's RCCL group (group_backend 0: RCCL when the devices are distinct, else device copies; 1: RCCL;
         2: copies).  Mutually exclusive with a torch.distributed `group`.
@@ -353,10 +353,18 @@ class ClassicalTempering:
         configurations at every rung (set_replica_cluster_update_every).  Copy 0 is the ladder copies=1 would build; copy 1 is
         the ladder of the seed `seed ^ COPY_SEED_XOR`.  Single process, single device only.  Served: periodic field-free 2-D
         lattices, and every graph whose containers run on a replica-packed family -- with ISINGMC_FORCE_PACKED=1,
-        the stable-path flag or a large enough graph that is the 3-d +-J glass and every Gaussian glass."""
+        the stable-path flag or a large enough graph that is the 3-d +-J glass and every Gaussian glass.
+
+        rng_rounds: rounds of Philox4x32 in the draws of the Metropolis sweeps, 10 or 7; None leaves the containers'
+        default (10 unless ISINGMC_PHILOX_ROUNDS says 7).  The exchange decisions draw with ten rounds either way.  copies 1 and 2,
+        one process, one device: with devices=[...] or a torch.distributed group of several ranks 7 is refused.  ValueError at the
+        first timestep when the graph's containers run on a family that 7 does not serve."""
         self._ea, self._eb, self._ej = _split(edges)
         if copies not in (1, 2):
             raise ValueError("copies must be 1 or 2")
+        if rng_rounds not in (None, 7, 10):
+            raise ValueError("rng_rounds must be 7 or 10")
+        self._rng_rounds = None if rng_rounds is None else int(rng_rounds)
         self._ncopies = int(copies)
         self._icm_every = 0
         self._track_minimum = False
@@ -371,6 +379,9 @@ class ClassicalTempering:
         self.nvars = int(max(self._ea.max(), self._eb.max())) + 1  # tempering.rs:44-49
         self._group = group
         self._world, self._rank = D.world_rank(group)
+        if self._rng_rounds == 7 and (self._devices is not None or self._world > 1):
+            raise ValueError("rng_rounds=7 is for a ladder on one process and one device: not with devices=[...] or a "
+                             "torch.distributed group of several ranks")
         if seed is None:
             if self._world > 1:
                 raise ValueError("a seed is required when the ladder is sharded over several ranks")
@@ -391,7 +402,7 @@ class ClassicalTempering:
                                                                          device=self._default_device())))())
                 return shared[0]
 
-            self._pair = [ClassicalTempering((self._ea, self._eb, self._ej), s, device=device, engine_factory=factory)
+            self._pair = [ClassicalTempering((self._ea, self._eb, self._ej), s, device=device, engine_factory=factory, rng_rounds=rng_rounds)
                           for s in (self._seed, self._seed ^ COPY_SEED_XOR)]
             self._icm_stats, self._icm_pending = None, False
         self._ovl_series, self._ovl_every, self._ovl_t0, self._ovl_classes = None, 0, 0, None   # overlap series
@@ -786,6 +797,10 @@ class ClassicalTempering:
             self._lo, self._hi = D.shard_bounds(G, self._world, self._rank)
             self._engine = self._engine_factory()
             self._states = self._engine.make_states(np.array(self._slot_seeds, dtype=np.uint64), (self._lo, self._hi))
+            if self._rng_rounds is not None and self._world == 1:
+                if not hasattr(self._states, "set_option"):
+                    raise ValueError("this engine's containers have no option 'philox_rounds' (rng_rounds)")
+                self._states.set_option("philox_rounds", self._rng_rounds)
             self._on_stream = (bool(getattr(self._engine, "supports_on_stream_pt", False)) and self._hi > self._lo and
                                os.environ.get("ISINGMC_PT_HOST", "0") in ("", "0"))  # ISINGMC_PT_HOST=1: the host swap step (A/B runs)
             # eligibility first, WITHOUT side effects (e.g. a real-coupling graph too small for the packed kernels, a bit-sliced shard
