@@ -11,6 +11,8 @@
 
 #include <algorithm>
 
+#include "kernel_pick.hpp"
+
 namespace isingmc {
 
 namespace {
@@ -88,10 +90,10 @@ hipError_t best_launch_decide(hipStream_t stream, bool packed, const double *ene
     const uint32_t n_slots = packed ? 32u * n_groups : n;
     if (n_slots == 0) return hipSuccess;
     const dim3 grid((n_slots + 255) / 256);
-    if (packed)
-        hipLaunchKernelGGL(best_decide_kernel<true>, grid, dim3(256), 0, stream, energy, n, bit0, n_slots, (unsigned long long)t, best_e, best_t, out, improved);
-    else
-        hipLaunchKernelGGL(best_decide_kernel<false>, grid, dim3(256), 0, stream, energy, n, 0u, n_slots, (unsigned long long)t, best_e, best_t, out, improved);
+    pick(packed, [&](auto PACKED) { // (replica slots, not bits of a group: no first bit)
+        hipLaunchKernelGGL(best_decide_kernel<PACKED.value>, grid, dim3(256), 0, stream, energy, n, PACKED.value ? bit0 : 0u, n_slots,
+                           (unsigned long long)t, best_e, best_t, out, improved);
+    });
     return hipGetLastError();
 }
 

@@ -1,6 +1,8 @@
 // Translation unit of the checkerboard kernels (lattice_kernels.hpp): their instantiations and launchers (lattice_types.hpp).
 #include "lattice_kernels.hpp"
 
+#include "kernel_pick.hpp"
+
 namespace isingmc {
 
 // Random initial configuration: word w of plane c = Philox(key, (0, w>>2, c<<8, "LATI"))[w&3].
@@ -18,22 +20,14 @@ __global__ __launch_bounds__(256) void lat_init_kernel(uint32_t *__restrict__ st
 
 static dim3 lat_grid(uint32_t quads, uint32_t n_replicas) { return dim3((quads + 255) / 256, n_replicas, 1); }
 
-// f(VEC, PMJ) with the two flags as compile-time constants
-template <typename F>
-static void lat_pick(bool vec, bool pmj, F &&f)
-{
-    if (vec) { if (pmj) f(std::true_type{}, std::true_type{}); else f(std::true_type{}, std::false_type{}); }
-    else { if (pmj) f(std::false_type{}, std::true_type{}); else f(std::false_type{}, std::false_type{}); }
-}
+// the Philox round count as a template argument; rounds is 7 or 10 (the launchers have checked)
+using LatRounds = or_last<7, 10>;
 
-// f(VEC, PMJ, ROUNDS) for the kernels that draw the sweeps' random words; rounds is 7 or 10 (the launchers have checked)
+// f(kernel): the instantiation of the looping kernel for (pmj, rounds), for its launch and its occupancy query alike
 template <typename F>
-static void lat_pick_rounds(bool vec, bool pmj, int rounds, F &&f)
+static void lat_pick_sweep_loop(bool pmj, int rounds, F &&f)
 {
-    lat_pick(vec, pmj, [&](auto V, auto P) {
-        if (rounds == 7) f(V, P, std::integral_constant<int, 7>{});
-        else f(V, P, std::integral_constant<int, 10>{});
-    });
+    pick(pmj, LatRounds{rounds}, [&](auto P, auto N) { f(lat_sweep_loop_kernel<P.value, N.value>); });
 }
 
 hipError_t lat_launch_init(hipStream_t stream, uint32_t *state, const LatGeom &g, const uint2 *keys, uint32_t first_replica, uint32_t n_replicas)
@@ -49,33 +43,27 @@ hipError_t lat_launch_sweep(bool vec, bool pmj, uint32_t iters, uint32_t n_repli
     const bool uni = vec && g.cols_log2 >= 0;
     if (iters > 1 && (!uni || g.nquads % (256 * iters) != 0)) return hipErrorInvalidValue;
     if (!philox_rounds_served(rounds)) return hipErrorInvalidValue;
-    lat_pick_rounds(vec, pmj, rounds, [&](auto V, auto P, auto N) {
-        constexpr bool VEC = decltype(V)::value, PMJ = decltype(P)::value;
-        constexpr int R = decltype(N)::value;
-        const auto launch = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, lat_grid(g.nquads, n_replicas), dim3(256), lds_bytes, stream, state, g, colour, t, keys, thr, thr_replica,
-                               jneg, jneg_uniform);
-        };
-        if (iters > 1)
-            hipLaunchKernelGGL((lat_sweep_loop_kernel<PMJ, R>), dim3(g.nquads / (256 * iters), n_replicas, 1), dim3(256), lds_bytes, stream, state, g,
-                               colour, t, keys, thr, thr_replica, jneg, jneg_uniform, iters);
-        else if (uni) launch(lat_sweep_kernel<VEC, PMJ, VEC, R>); // division-free mapping
-        else launch(lat_sweep_kernel<VEC, PMJ, false, R>);
-    });
+    if (iters > 1)
+        lat_pick_sweep_loop(pmj, rounds, [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(g.nquads / (256 * iters), n_replicas, 1), dim3(256), lds_bytes, stream, state, g, colour, t, keys, thr,
+                               thr_replica, jneg, jneg_uniform, iters);
+        });
+    else
+        pick(vec, pmj, uni, LatRounds{rounds}, [&](auto V, auto P, auto U, auto N) {
+            if constexpr (V.value || !U.value) // UNI, the division-free mapping, only together with VEC
+                hipLaunchKernelGGL((lat_sweep_kernel<V.value, P.value, U.value, N.value>), lat_grid(g.nquads, n_replicas), dim3(256), lds_bytes, stream,
+                                   state, g, colour, t, keys, thr, thr_replica, jneg, jneg_uniform);
+        });
     return hipGetLastError();
 }
 
 int lat_sweep_loop_blocks_per_cu(bool pmj, unsigned lds_bytes, int rounds)
 {
     int n = 0;
-    hipError_t err = hipErrorInvalidValue;
-    if (rounds == 10)
-        err = pmj ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, lat_sweep_loop_kernel<true>, 256, lds_bytes)
-                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, lat_sweep_loop_kernel<false>, 256, lds_bytes);
-    else if (rounds == 7)
-        err = pmj ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, lat_sweep_loop_kernel<true, 7>, 256, lds_bytes)
-                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, lat_sweep_loop_kernel<false, 7>, 256, lds_bytes);
-    if (err != hipSuccess) n = 0;
+    if (philox_rounds_served(rounds))
+        lat_pick_sweep_loop(pmj, rounds, [&](auto kernel) {
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, 256, lds_bytes) != hipSuccess) n = 0;
+        });
     (void)hipGetLastError();
     return n;
 }
@@ -85,15 +73,10 @@ hipError_t lat_launch_sweep_measure(bool vec, bool pmj, uint32_t n_replicas, hip
                                     uint32_t jneg_uniform, unsigned long long *out, size_t out_stride, int rounds)
 {
     if (!philox_rounds_served(rounds)) return hipErrorInvalidValue;
-    lat_pick_rounds(vec, pmj, rounds, [&](auto V, auto P, auto N) {
-        constexpr bool VEC = decltype(V)::value, PMJ = decltype(P)::value;
-        constexpr int R = decltype(N)::value;
-        const auto launch = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, lat_grid(g.nquads, n_replicas), dim3(256), 0, stream, state, g, t, keys, thr, thr_replica, jneg,
-                               jneg_uniform, out, out_stride);
-        };
-        if (VEC && g.cols_log2 >= 0) launch(lat_sweep_measure_kernel<VEC, PMJ, VEC, R>);
-        else launch(lat_sweep_measure_kernel<VEC, PMJ, false, R>);
+    pick(vec, pmj, vec && g.cols_log2 >= 0, LatRounds{rounds}, [&](auto V, auto P, auto U, auto N) {
+        if constexpr (V.value || !U.value) // as in lat_launch_sweep
+            hipLaunchKernelGGL((lat_sweep_measure_kernel<V.value, P.value, U.value, N.value>), lat_grid(g.nquads, n_replicas), dim3(256), 0, stream,
+                               state, g, t, keys, thr, thr_replica, jneg, jneg_uniform, out, out_stride);
     });
     return hipGetLastError();
 }
@@ -102,9 +85,9 @@ hipError_t lat_launch_measure(bool vec, bool pmj, uint32_t n_replicas, hipStream
                               const uint32_t *jneg, uint32_t jneg_uniform, unsigned long long *out, size_t out_stride)
 {
     const uint32_t blocks = (g.nquads + 256 * MEASURE_QUADS_PER_THREAD - 1) / (256 * MEASURE_QUADS_PER_THREAD);
-    lat_pick(vec, pmj, [&](auto V, auto P) {
-        hipLaunchKernelGGL((lat_measure_kernel<decltype(V)::value, decltype(P)::value>), dim3(blocks, n_replicas), dim3(256), 0, stream, state, g,
-                           jneg, jneg_uniform, out, out_stride);
+    pick(vec, pmj, [&](auto V, auto P) {
+        hipLaunchKernelGGL((lat_measure_kernel<V.value, P.value>), dim3(blocks, n_replicas), dim3(256), 0, stream, state, g, jneg, jneg_uniform, out,
+                           out_stride);
     });
     return hipGetLastError();
 }
@@ -115,9 +98,9 @@ hipError_t lat_launch_resident(bool vec, bool pmj, unsigned n_replicas, unsigned
                                unsigned long long *steps_out, int rounds)
 {
     if (!philox_rounds_served(rounds)) return hipErrorInvalidValue;
-    lat_pick_rounds(vec, pmj, rounds, [&](auto V, auto P, auto N) {
-        hipLaunchKernelGGL((lat_resident_kernel<decltype(V)::value, decltype(P)::value, decltype(N)::value>), dim3(n_replicas), dim3(threads), lds_bytes, stream, state,
-                           g, t0, timesteps, keys, thr_steps, thr_stride, thr_replica, jneg, jneg_uniform, steps_out, uint32_t(n_replicas));
+    pick(vec, pmj, LatRounds{rounds}, [&](auto V, auto P, auto N) {
+        hipLaunchKernelGGL((lat_resident_kernel<V.value, P.value, N.value>), dim3(n_replicas), dim3(threads), lds_bytes, stream, state, g, t0, timesteps,
+                           keys, thr_steps, thr_stride, thr_replica, jneg, jneg_uniform, steps_out, uint32_t(n_replicas));
     });
     return hipGetLastError();
 }

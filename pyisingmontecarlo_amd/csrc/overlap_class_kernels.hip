@@ -12,6 +12,7 @@
 #include <algorithm>
 
 #include "host_logic.hpp"
+#include "kernel_pick.hpp"
 #include "lat_class_count.hpp"
 
 namespace isingmc {
@@ -102,8 +103,9 @@ hipError_t overlap_class_launch_packed(hipStream_t stream, const uint32_t *words
                                        uint32_t items, unsigned long long *out)
 {
     if (C.n_seg == 0) return hipSuccess; // every site without a class: the accumulators stay zero
-    if (paired) hipLaunchKernelGGL(ovl_pk_class_kernel<true>, dim3(C.n_seg, items), dim3(256), 0, stream, words, n_pos, C, out);
-    else hipLaunchKernelGGL(ovl_pk_class_kernel<false>, dim3(C.n_seg, items), dim3(256), 0, stream, words, n_pos, C, out);
+    pick(paired, [&](auto PAIRED) {
+        hipLaunchKernelGGL(ovl_pk_class_kernel<PAIRED.value>, dim3(C.n_seg, items), dim3(256), 0, stream, words, n_pos, C, out);
+    });
     return hipGetLastError();
 }
 

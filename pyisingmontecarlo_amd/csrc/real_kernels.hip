@@ -1,61 +1,38 @@
 // Translation unit of the replica-packed real-coupling kernels (see real_types.hpp for why it is apart from isingmc.hip).
 #include "real_kernels.hpp"
 
-#include <type_traits>
+#include "kernel_pick.hpp"
 
 namespace isingmc {
 
-template <typename F>
-static void rj_with_slots(uint32_t slots, F &&f)
-{
-    if (slots == 4) f(std::integral_constant<int, 4>{});
-    else if (slots == 7) f(std::integral_constant<int, 7>{});
-    else if (slots == 11) f(std::integral_constant<int, 11>{});
-    else if (slots == 15) f(std::integral_constant<int, 15>{});
-    else if (slots == 23) f(std::integral_constant<int, 23>{});
-    else f(std::integral_constant<int, 31>{});
-}
+static or_last<4, 7, 11, 15, 23, 31> rj_slots(uint32_t slots) { return {int(slots)}; } // the slot counts with an RjShape
 
 uint32_t rj_threads(uint32_t slots)
 {
     uint32_t n = 256;
-    rj_with_slots(slots, [&](auto s_c) { n = uint32_t(RjShape<decltype(s_c)::value>::THREADS); });
+    pick(rj_slots(slots), [&](auto S) { n = uint32_t(RjShape<S.value>::THREADS); });
     return n;
 }
 
 hipError_t rj_launch_sweep(dim3 grid, hipStream_t stream, uint32_t *state, const RjGraphDev &G, uint32_t class_begin, uint32_t real_end,
                            uint64_t t, const uint2 *group_keys, const RjBeta *betas, uint32_t beta_stride, uint32_t q_lo, uint32_t q_hi)
 {
-    rj_with_slots(G.slots, [&](auto s_c) {
-        constexpr int S = decltype(s_c)::value;
-        const auto launch = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, grid, dim3(RjShape<S>::THREADS), 0, stream, state, G, class_begin, real_end, t, group_keys, betas,
-                               q_lo, q_hi);
-        };
-        const bool whole = q_lo == 0 && q_hi >= 8; // every replica bit of the groups of this launch is decided
-        const bool heavy = G.dshift != nullptr;
-        // (partly owned groups of graphs WITHOUT heavy sites have their own instantiations: carrying the heavy-site shift cost the
-        //  few-replica runs 9 % -- 2048^2 Gaussian x 8: 4.98 -> 4.54e11 -- when round 4 first folded them into the heavy ones)
-        const auto pick = [&](auto ub_c) {
-            constexpr bool UB = decltype(ub_c)::value;
-            if (!whole) { if (heavy) launch(rj_sweep_kernel<S, UB, true, true>); else launch(rj_sweep_kernel<S, UB, true, false>); }
-            else if (heavy) launch(rj_sweep_kernel<S, UB, false, true>);
-            else launch(rj_sweep_kernel<S, UB, false, false>);
-        };
-        if (beta_stride == 0) pick(std::true_type{});
-        else pick(std::false_type{});
+    const bool whole = q_lo == 0 && q_hi >= 8; // every replica bit of the groups of this launch is decided
+    const bool heavy = G.dshift != nullptr;
+    // (partly owned groups of graphs WITHOUT heavy sites have their own instantiations: carrying the heavy-site shift cost the
+    //  few-replica runs 9 % -- 2048^2 Gaussian x 8: 4.98 -> 4.54e11 -- when round 4 first folded them into the heavy ones)
+    pick(rj_slots(G.slots), beta_stride == 0, !whole, heavy, [&](auto S, auto UB, auto PARTIAL, auto HEAVY) {
+        hipLaunchKernelGGL((rj_sweep_kernel<S.value, UB.value, PARTIAL.value, HEAVY.value>), grid, dim3(RjShape<S.value>::THREADS), 0, stream, state, G,
+                           class_begin, real_end, t, group_keys, betas, q_lo, q_hi);
     });
     return hipGetLastError();
 }
 
+// f(kernel, threads): the instantiation for (slots, bipartite, count_up) and its workgroup size, for its launch and its occupancy query alike
 template <typename F>
 static void rj_pick_measure(uint32_t slots, bool bip, bool up, F &&f)
 {
-    rj_with_slots(slots, [&](auto s_c) {
-        constexpr int S = decltype(s_c)::value;
-        if (bip) { if (up) f(rj_measure_kernel<S, true, true>, RjShape<S>::THREADS); else f(rj_measure_kernel<S, true, false>, RjShape<S>::THREADS); }
-        else { if (up) f(rj_measure_kernel<S, false, true>, RjShape<S>::THREADS); else f(rj_measure_kernel<S, false, false>, RjShape<S>::THREADS); }
-    });
+    pick(rj_slots(slots), bip, up, [&](auto S, auto BIP, auto UP) { f(rj_measure_kernel<S.value, BIP.value, UP.value>, RjShape<S.value>::THREADS); });
 }
 
 hipError_t rj_launch_measure(dim3 grid, hipStream_t stream, const uint32_t *state, const RjGraphDev &G, const uint32_t *site,

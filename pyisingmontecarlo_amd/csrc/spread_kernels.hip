@@ -1,28 +1,16 @@
 // Translation unit of the lane-parallel resident lattice kernel (see spread_kernels.hpp for why it is apart from isingmc.hip).
 #include "spread_kernels.hpp"
 
+#include "kernel_pick.hpp"
+
 namespace isingmc {
 
-template <int LPQ, int R, typename F>
-static void spread_pick_lpq(bool vec, bool pmj, F &&f)
-{
-    if (vec) { if (pmj) f(lat_resident_spread_kernel<true, true, LPQ, R>); else f(lat_resident_spread_kernel<true, false, LPQ, R>); }
-    else { if (pmj) f(lat_resident_spread_kernel<false, true, LPQ, R>); else f(lat_resident_spread_kernel<false, false, LPQ, R>); }
-}
-
-template <int R, typename F>
-static void spread_pick_rounds(bool vec, bool pmj, int lanes_per_quad, F &&f)
-{
-    if (lanes_per_quad == 8) spread_pick_lpq<8, R>(vec, pmj, f);
-    else if (lanes_per_quad == 4) spread_pick_lpq<4, R>(vec, pmj, f);
-    else spread_pick_lpq<2, R>(vec, pmj, f);
-}
-
+// f(kernel): the instantiation for one launch shape, for its launch and its occupancy query alike
 template <typename F>
 static void spread_pick(bool vec, bool pmj, int lanes_per_quad, int rounds, F &&f) // rounds is 7 or 10 (the callers have checked)
 {
-    if (rounds == 7) spread_pick_rounds<7>(vec, pmj, lanes_per_quad, f);
-    else spread_pick_rounds<10>(vec, pmj, lanes_per_quad, f);
+    pick(vec, pmj, or_last<8, 4, 2>{lanes_per_quad}, or_last<7, 10>{rounds},
+         [&](auto V, auto P, auto L, auto N) { f(lat_resident_spread_kernel<V.value, P.value, L.value, N.value>); });
 }
 
 hipError_t spread_launch(bool vec, bool pmj, int lanes_per_quad, unsigned blocks, unsigned threads, size_t lds_bytes, hipStream_t stream, uint32_t *state,

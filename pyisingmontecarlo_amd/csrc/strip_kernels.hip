@@ -1,7 +1,18 @@
 // Translation unit of the persistent strip kernel (see strip_types.hpp for why it is apart from isingmc.hip).
 #include "strip_kernels.hpp"
 
+#include "kernel_pick.hpp"
+
 namespace isingmc {
+
+// f(kernel, threads): the instantiation for (pmj, nw, ladder, rounds) and its workgroup size.  The plan sizes the persistent grid by the
+// occupancy of the very kernel the launch runs (its workgroups wait on their neighbours' halos): both go through here.
+template <typename F>
+static void strip_pick(bool pmj, int nw, bool ladder, int rounds, F &&f) // rounds is 7 or 10 (the callers have checked)
+{
+    pick(pmj, or_last<1, 4>{nw}, ladder, or_last<7, 10>{rounds},
+         [&](auto P, auto N, auto L, auto R) { f(lat_strip_kernel<P.value, N.value, L.value, R.value>, 64 * N.value); });
+}
 
 hipError_t strip_launch(bool pmj, int nw, unsigned blocks, size_t lds_bytes, hipStream_t stream, uint32_t *state, const LatGeom &g,
                         const StripArgs &a, uint64_t t0, uint32_t timesteps, const uint2 *keys, const LatThr *thr_steps,
@@ -10,22 +21,10 @@ hipError_t strip_launch(bool pmj, int nw, unsigned blocks, size_t lds_bytes, hip
                         uint32_t n_replicas, uint32_t *err, int rounds)
 {
     if (!philox_rounds_served(rounds)) return hipErrorInvalidValue;
-    const auto launch = [&](auto kernel, unsigned threads) {
+    strip_pick(pmj, nw, lad.ladder != nullptr, rounds, [&](auto kernel, int threads) {
         hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), lds_bytes, stream, state, g, a, t0, timesteps, keys, thr_steps, thr_stride,
                            thr_replica, jneg, jneg_uniform, halo, steps_out, fin, lad, n_replicas, err);
-    };
-    const bool ladder = lad.ladder != nullptr;
-    const auto pick = [&](auto pmj_c, auto nw_c) {
-        constexpr bool P = decltype(pmj_c)::value;
-        constexpr int N = decltype(nw_c)::value;
-        if (rounds == 7) {
-            if (ladder) launch(lat_strip_kernel<P, N, true, 7>, 64u * N);
-            else launch(lat_strip_kernel<P, N, false, 7>, 64u * N);
-        } else if (ladder) launch(lat_strip_kernel<P, N, true>, 64u * N);
-        else launch(lat_strip_kernel<P, N, false>, 64u * N);
-    };
-    if (nw == 1) { if (pmj) pick(std::true_type{}, std::integral_constant<int, 1>{}); else pick(std::false_type{}, std::integral_constant<int, 1>{}); }
-    else { if (pmj) pick(std::true_type{}, std::integral_constant<int, 4>{}); else pick(std::false_type{}, std::integral_constant<int, 4>{}); }
+    });
     return hipGetLastError();
 }
 
@@ -35,20 +34,9 @@ int strip_blocks_per_cu(bool pmj, int nw, bool ladder, size_t lds_bytes, int rou
 {
     int n = 0;
     if (!philox_rounds_served(rounds)) return 0;
-    const auto ask = [&](auto kernel, int threads) {
+    strip_pick(pmj, nw, ladder, rounds, [&](auto kernel, int threads) {
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, threads, lds_bytes) != hipSuccess) n = 0;
-    };
-    const auto pick = [&](auto pmj_c, auto nw_c) {
-        constexpr bool P = decltype(pmj_c)::value;
-        constexpr int N = decltype(nw_c)::value;
-        if (rounds == 7) {
-            if (ladder) ask(lat_strip_kernel<P, N, true, 7>, 64 * N);
-            else ask(lat_strip_kernel<P, N, false, 7>, 64 * N);
-        } else if (ladder) ask(lat_strip_kernel<P, N, true>, 64 * N);
-        else ask(lat_strip_kernel<P, N, false>, 64 * N);
-    };
-    if (nw == 1) { if (pmj) pick(std::true_type{}, std::integral_constant<int, 1>{}); else pick(std::false_type{}, std::integral_constant<int, 1>{}); }
-    else { if (pmj) pick(std::true_type{}, std::integral_constant<int, 4>{}); else pick(std::false_type{}, std::integral_constant<int, 4>{}); }
+    });
     (void)hipGetLastError();
     return n;
 }

@@ -124,7 +124,7 @@ def vec(W, H):
 
 
 def uni(W, H):
-    """lattice_kernels.hip, lat_launch_sweep_measure:  if (VEC && g.cols_log2 >= 0) launch(lat_sweep_measure_kernel<VEC, PMJ, VEC>);"""
+    """lattice_kernels.hip, lat_launch_sweep_measure:  pick(vec, pmj, vec && g.cols_log2 >= 0, ...) -> lat_sweep_measure_kernel<VEC, PMJ, UNI>"""
     return vec(W, H) and cols_log2(W, H) >= 0
 
 

@@ -211,7 +211,7 @@ def _b(flag):
 
 
 def sweep_kernel(case, shape, R=3):
-    """the instantiation one timestep of the case runs on the shape (mc_kernels.hip: launch_mode, launch_resident_mode)"""
+    """the instantiation one timestep of the case runs on the shape (mc_kernels.hip: mc_launch_sweep, mc_launch_resident)"""
     mode = mc_mode(case)
     if resident_fits(shape.W, shape.H, shape.options):
         spread, _ = resident_launch(shape.W, shape.H, R, shape.options)

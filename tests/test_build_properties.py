@@ -156,6 +156,35 @@ def test_no_vector_store_data_is_overwritten_right_behind_the_store(unit_asm):
     assert stores >= 4, "no register-offset vector stores found: has the pattern of this test gone stale?"
 
 
+# kernels per name in the units whose launchers turn runtime values into template arguments (csrc/kernel_pick.hpp)
+KERNEL_CENSUS = {
+    "lattice_kernels.hip": {"lat_init": 1, "lat_measure": 4, "lat_resident": 8, "lat_sweep": 12, "lat_sweep_loop": 4, "lat_sweep_measure": 12},
+    "spread_kernels.hip": {"lat_resident_spread": 24},
+    "strip_kernels.hip": {"lat_strip": 16},
+    "mc_kernels.hip": {"lat_mc_sweep": 24, "lat_mc_resident": 24, "lat_mc_measure_aniso": 2, "lat_mc_measure_open": 2},
+    "packed_uni_kernels.hip": {"pk_sweep_uni": 32, "pk_philox_table": 1},
+    "real_kernels.hip": {"rj_sweep": 48, "rj_measure": 24, "rj_energy_from_counts": 1},
+    "general_kernels.hip": {"gen_init": 1, "gen_sweep": 8, "gen_measure": 2, "gen_reduce": 1, "gen_resident": 6},
+    "best_kernels.hip": {"best_decide": 2, "best_keep_rows": 1, "best_keep_bits": 1},
+    "overlap_class_kernels.hip": {"ovl_lat_class": 1, "ovl_lat_class_between": 1, "ovl_pk_class": 2},
+}
+
+
+def test_the_launcher_units_hold_exactly_their_instantiations(unit_asm):
+    """The launchers select an instantiation per choice, and a choice that depends on another one is decided inside the selection
+    (UNI only together with VEC, sign planes only for the modes with a field, ...): a Cartesian selection would compile kernels nothing
+    launches, a dropped branch would leave a launch without its kernel.  Neither shows in any result; the count per kernel name does."""
+    for unit, expected in KERNEL_CENSUS.items():
+        census = {}
+        for sym in re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", unit_asm[unit], re.M):
+            m = re.match(r"_ZN7isingmc(?:12_GLOBAL__N_1|L)?(\d+)", sym)  # (in an unnamed namespace, or static)
+            assert m, f"{unit}: {sym}"
+            name = sym[m.end():m.end() + int(m.group(1))]
+            assert name.endswith("_kernel"), f"{unit}: {sym}"
+            census[name[:-len("_kernel")]] = census.get(name[:-len("_kernel")], 0) + 1
+        assert census == expected, unit
+
+
 HOST_UNITS = ["core.hip", "graph.hip", "isingmc.hip", "nonlocal.hip", "overlaps.hip", "best.hip", "sampling.hip", "tempering.hip", "population.hip"]
 
 
