@@ -494,6 +494,11 @@ int isingmc_observable_series_get(isingmc_observable_series *s, size_t first, si
 int isingmc_observable_series_reset(isingmc_observable_series *s);
 int isingmc_observable_series_destroy(isingmc_observable_series *s);
 
+/* ---- The cluster series: declared in isingmc_cluster_series.h, which the end of this header includes ---- */
+/* The counting rule of the room check, without a device: *steps_out = the timesteps t in [t0, t0 + timesteps) with t % k == k - 1
+ * (0 when k == 0). */
+int isingmc_host_nonlocal_steps(uint64_t t0, size_t timesteps, size_t k, uint64_t *steps_out);
+
 /* ---- each replica's lowest-energy configuration, kept on the device (no reference counterpart) ----
  * A container may keep, per replica, the lowest energy its configuration has had at an UPDATE, the timestep of that update and
  * the configuration itself.  An update measures the f64 energies of isingmc_get_energies on the device and, for every replica
@@ -728,4 +733,5 @@ int isingmc_debug_live_blocks(size_t *device_blocks_out, size_t *pinned_blocks_o
 #ifdef __cplusplus
 }
 #endif
+#include "isingmc_cluster_series.h"
 #endif /* ISINGMC_H */

@@ -109,6 +109,7 @@ _PROTOTYPES = {
     "isingmc_observable_series_get": (C.c_int, [_vp, C.c_size_t, C.c_size_t, _vp, _vp, _vp, _vp]),
     "isingmc_observable_series_reset": (C.c_int, [_vp]),
     "isingmc_observable_series_destroy": (C.c_int, [_vp]),
+    "isingmc_host_nonlocal_steps": (C.c_int, [C.c_uint64, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64)]),
     "isingmc_states_set_track_best": (C.c_int, [_vp, C.c_size_t]),
     "isingmc_states_track_best": (C.c_int, [_vp, C.POINTER(C.c_size_t)]),
     "isingmc_best_update": (C.c_int, [_vp]),
@@ -152,6 +153,15 @@ _PROTOTYPES = {
     "isingmc_debug_live_blocks": (C.c_int, [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
+# include/isingmc_cluster_series.h: the header isingmc.h includes at its end, bound with the table above
+_CLUSTER_SERIES_PROTOTYPES = {
+    "isingmc_cluster_series_create": (C.c_int, [_vp, C.c_int, C.c_size_t, C.POINTER(_vp)]),
+    "isingmc_cluster_series_count": (C.c_int, [_vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "isingmc_cluster_series_get": (C.c_int, [_vp, C.c_size_t, C.c_size_t, _vp, _vp]),
+    "isingmc_cluster_series_reset": (C.c_int, [_vp]),
+    "isingmc_cluster_series_destroy": (C.c_int, [_vp]),
+}
+CLUSTER_SERIES_SYMBOLS = tuple(_CLUSTER_SERIES_PROTOTYPES)
 
 _lib = None
 _hip_preloaded = False
@@ -189,7 +199,7 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -m pyisingmontecarlo_amd.build` "
                 "(there is no CPU fallback)")
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in _PROTOTYPES.items():
+        for name, (res, args) in list(_PROTOTYPES.items()) + list(_CLUSTER_SERIES_PROTOTYPES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -635,6 +645,47 @@ class ObservableSeries(_DeviceSeries):
         return t, e, m, cls
 
 
+CLUSTER_SERIES_KINDS = {"sw": 0, "icm": 1}  # ISINGMC_CLUSTER_SERIES_*
+
+
+class ClusterSeries(_DeviceSeries):
+    """isingmc_cluster_series: a device-resident log with one row per non-local step of its container -- per column (replica of a
+    Swendsen-Wang step, pair of an isoenergetic cluster move) the number of clusters, the largest, and the sums of s, s^2 and s^4
+    over the cluster sizes.  The steps append the rows themselves, enqueue only; get() reads the log, once,
+    afterwards.  Made by States.cluster_series."""
+
+    _PREFIX = "isingmc_cluster_series_"
+
+    def __init__(self, a, kind="sw", capacity=4096):
+        if kind not in CLUSTER_SERIES_KINDS:
+            raise ValueError("kind must be 'sw' (Swendsen-Wang steps) or 'icm' (isoenergetic cluster moves)")
+        self._a = a  # keeps it alive
+        self.kind = kind
+        self.n_columns = a.count if kind == "sw" else a.count // 2
+        self._create((a,), a._h, CLUSTER_SERIES_KINDS[kind], int(capacity))
+
+    def set_every(self, k):
+        """A cluster series has no period of its own: its rows are the container's non-local steps (States.set_cluster_every /
+        set_icm_every)."""
+        raise TypeError("a cluster series has no period of its own: its rows follow set_cluster_every / set_icm_every of the container")
+
+    def get(self, first=0, n=None):
+        """(timesteps uint64[n], n_clusters, largest, sites, s2, s4_lo, s4_hi: uint64[n, C] each) of the rows [first, first + n)
+        (n=None: all from `first` on); sum s^4 = s4_hi 2^64 + s4_lo.  Synchronises once; changes nothing."""
+        first, n = self._rows(first, n)
+        t = np.zeros(n, dtype=np.uint64)
+        rows = np.zeros((n, self.n_columns, 6), dtype=np.uint64)
+        _check(self._call("get", self._h, first, n, _p(t), _p(rows)))
+        return (t,) + tuple(np.ascontiguousarray(rows[:, :, i]) for i in range(6))
+
+
+def nonlocal_steps(t0, timesteps, k):
+    """The timesteps t in [t0, t0 + timesteps) with t % k == k - 1 (0 when k == 0): the rows a run call appends to a cluster series."""
+    out = C.c_uint64()
+    _check(lib().isingmc_host_nonlocal_steps(C.c_uint64(int(t0)), int(timesteps), int(k), C.byref(out)))
+    return int(out.value)
+
+
 class States:
     """isingmc_states: R replicas of the graph's spins on the device."""
 
@@ -801,6 +852,12 @@ class States:
         """An ObservableSeries: energy, magnetisation and magnetisation by class of every replica (by_rung: of
         every rung of the attached ladder), one row per record, kept on the device."""
         return ObservableSeries(self, classes, energy, magnetisation, by_rung, capacity)
+
+    def cluster_series(self, kind="sw", capacity=4096):
+        """A ClusterSeries: the cluster-size moments of every Swendsen-Wang step (kind="sw", a column per replica)
+        or isoenergetic cluster move (kind="icm", a column per pair (2p, 2p + 1)) of this container, one row per step, kept on the
+        device.  One live cluster series per container."""
+        return ClusterSeries(self, kind, capacity)
 
     def overlap_series(self, other=None, n_pairs=None, classes=None, link=True, by_rung=False, capacity=4096):
         """An OverlapSeries over the pairs overlaps() would take: one row per record, kept on the device.

@@ -54,6 +54,23 @@ def magnetisation_moments(mag, nvars):
     return m1, ma, m2, m4, u4
 
 
+def cluster_estimators(s2, s4_lo, s4_hi, nvars):
+    """(chi, <m^2>, <m^4>, U4) per column from the rows of a cluster series of Swendsen-Wang steps (DESIGN.md S24:
+    ClusterSeries.get), s2[n, ...] = sum s^2 and s4 = s4_hi 2^64 + s4_lo = sum s^4 over the cluster sizes of each step.  Given the
+    bonds of a step the clusters take their signs independently, so E[M^2 | bonds] = S2 and E[M^4 | bonds] = 3 S2^2 - 2 S4:
+    chi = <S2> / N, <m^2> = <S2> / N^2, <m^4> = <3 S2^2 - 2 S4> / N^4 and U4 = 1 - <m^4> / (3 <m^2>^2), averaged over the n rows of
+    axis 0 in float64.  S4 <= S2^2, so 3 S2^2 - 2 S4 >= S2^2: the difference loses no digits.  On an antiferromagnet m is the
+    staggered magnetisation."""
+    n = float(nvars)
+    S2 = np.asarray(s2, dtype=np.uint64).astype(np.float64)
+    S4 = np.asarray(s4_hi, dtype=np.uint64).astype(np.float64) * 2.0 ** 64 + np.asarray(s4_lo, dtype=np.uint64).astype(np.float64)
+    m2 = S2.mean(axis=0) / n ** 2
+    m4 = (3.0 * S2 ** 2 - 2.0 * S4).mean(axis=0) / n ** 4
+    with np.errstate(divide="ignore", invalid="ignore"):
+        u4 = np.where(m2 > 0, (3.0 * m2 ** 2 - m4) / (3.0 * m2 ** 2), np.nan)
+    return m2 * n, m2, m4, u4
+
+
 def structure_factor(planes, nvars):
     """|sum_x e^{i k x} M_x|^2 / nvars per row and wave number: entry n is S(k_n) at k_n = 2 pi n / L for ONE configuration,
     planes[..., x] = M_x the L plane magnetisations of one axis (the by_class rows of plane_classes; leading axes, such as samples

@@ -5,7 +5,8 @@
 //   cl_merge_kernel   one thread per bond that leaves a tile (both periodic wraps included): union in global memory
 //   cl_flip_kernel    one wave per 64 consecutive sites of a row: chase to the root, look the flip bit up, ballot -> the two
 //                     32-spin words of the row segment; counts the roots and the sites per root
-//   cl_max_kernel     largest cluster
+//   cl_max_kernel     largest cluster (cl_max_moments_kernel while a cluster series is live, DESIGN.md S24: the same pass also
+//                     sums s^2 and s^4 over the cluster sizes into the series' row)
 // Every union links a root to a SMALLER site id with an integer atomicMin, so the final root of a component is its smallest
 // site id whatever the order of execution, and every loop below walks strictly decreasing labels: it ends after at most
 // W H steps without waiting for any other thread.
@@ -186,6 +187,66 @@ __global__ __launch_bounds__(256) void cl_max_kernel(const uint32_t *__restrict_
     if ((threadIdx.x & 63u) == 0 && m) atomicMax(stats + 2 * r + 1, m);
 }
 
+// cl_max_kernel with the cluster-size moments of DESIGN.md S24, launched in its place while a cluster series is live: the same
+// grid, the same uint4 loads, the same atomicMax.  Each thread holds S2 in 64 bits and S4 in 128 (cluster_moments.hpp); the wave
+// adds up by shuffles and lane 0 adds into the row's column of replica / pair r of the batch: three 64-bit atomics per wave that
+// saw a root.  Bounded by the read of `sizes`, 4 bytes per site, as the kernel it replaces.
+__global__ __launch_bounds__(256) void cl_max_moments_kernel(const uint32_t *__restrict__ sizes, const uint32_t quads, uint32_t *__restrict__ stats,
+                                                             const ClusterMomentsOut out)
+{
+    const uint32_t r = blockIdx.y, q = blockIdx.x * 256 + threadIdx.x;
+    uint32_t m = 0;
+    ClusterMoments sum;
+    if (q < quads) {
+        const uint4 v = reinterpret_cast<const uint4 *>(sizes + size_t(r) * 4 * quads)[q];
+        m = max(max(v.x, v.y), max(v.z, v.w));
+        if (m) { // (most sites are no roots)
+            sum.add_size(v.x);
+            sum.add_size(v.y);
+            sum.add_size(v.z);
+            sum.add_size(v.w);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = max(m, uint32_t(__shfl_xor(m, o)));
+    if (!m) return; // (the whole wave: no root among its 256 sites)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum.add_lane_xor(o);
+    if ((threadIdx.x & 63u) != 0) return;
+    atomicMax(stats + 2 * r + 1, m);
+    const uint32_t col = out.slot0 + r - out.first_slot;
+    if (col < out.n_cols) sum.add_to(out.row + size_t(CLS_ROW) * col);
+}
+
+// one thread per column of the row
+__global__ __launch_bounds__(256) void cls_store_kernel(const uint32_t *__restrict__ stats, const uint32_t *__restrict__ minus,
+                                                        const unsigned long long nvars, const uint32_t first_slot, const uint32_t n_cols,
+                                                        unsigned long long *__restrict__ row)
+{
+    const uint32_t c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= n_cols) return;
+    const size_t slot = size_t(first_slot) + c;
+    unsigned long long *col = row + size_t(CLS_ROW) * c;
+    col[CLS_N_CLUSTERS] = stats[2 * slot];
+    col[CLS_LARGEST] = stats[2 * slot + 1];
+    col[CLS_SITES] = minus ? minus[slot] : nvars;
+}
+
+hipError_t cluster_series_launch_store(hipStream_t stream, const uint32_t *stats, const uint32_t *minus, unsigned long long nvars,
+                                       uint32_t first_slot, uint32_t n_cols, unsigned long long *row)
+{
+    if (n_cols == 0) return hipSuccess;
+    hipLaunchKernelGGL(cls_store_kernel, dim3((n_cols + 255) / 256), dim3(256), 0, stream, stats, minus, nvars, first_slot, n_cols, row);
+    return hipGetLastError();
+}
+
+// the last launch of a step on a lattice: the largest cluster of every labelling problem, with the moments while a series is live
+static void cl_launch_max(hipStream_t stream, const uint32_t *sizes, uint32_t quads, uint32_t n, uint32_t *stats, const ClusterMomentsOut &out)
+{
+    if (out.row) hipLaunchKernelGGL(cl_max_moments_kernel, dim3((quads + 255) / 256, n), dim3(256), 0, stream, sizes, quads, stats, out);
+    else hipLaunchKernelGGL(cl_max_kernel, dim3((quads + 255) / 256, n), dim3(256), 0, stream, sizes, quads, stats);
+}
+
 // ---- isoenergetic cluster move between the replicas of a pair ------------------------------------------------
 // Four launches of their own around the unchanged labelling: icm_bonds_kernel -> cl_tile_kernel -> cl_merge_kernel ->
 // icm_flip_kernel -> cl_max_kernel, with n = number of pairs.  Pair p = replicas 2 p and 2 p + 1 of `state`; q = spins of the
@@ -318,7 +379,8 @@ __global__ __launch_bounds__(256) void icm_flip_between_kernel(uint32_t *__restr
 }
 
 hipError_t cluster_launch_step(hipStream_t stream, uint32_t *state, const LatGeom &g, uint64_t t, const uint2 *keys, uint32_t jneg_uniform,
-                               uint64_t thr, const uint64_t *thr_per_replica, const ClusterWork &work, uint32_t n, uint32_t *stats)
+                               uint64_t thr, const uint64_t *thr_per_replica, const ClusterWork &work, uint32_t n, uint32_t *stats,
+                               const ClusterMomentsOut &moments)
 {
     const uint32_t wpp = g.wpp, tile_rows = (g.H + CL_TILE_ROWS - 1) / CL_TILE_ROWS;
     const uint32_t border = g.H * g.wpr + tile_rows * g.W, quads = g.W * g.H / 4;
@@ -327,12 +389,12 @@ hipError_t cluster_launch_step(hipStream_t stream, uint32_t *state, const LatGeo
     hipLaunchKernelGGL(cl_tile_kernel, dim3(g.wpr, tile_rows, n), dim3(256), 0, stream, g, work.bonds, work.labels, work.sizes);
     hipLaunchKernelGGL(cl_merge_kernel, dim3((border + 255) / 256, n), dim3(256), 0, stream, g, work.bonds, work.labels);
     hipLaunchKernelGGL(cl_flip_kernel, dim3((wpp + 3) / 4, n), dim3(256), 0, stream, state, g, work.labels, work.fliptab, work.sizes, stats);
-    hipLaunchKernelGGL(cl_max_kernel, dim3((quads + 255) / 256, n), dim3(256), 0, stream, work.sizes, quads, stats);
+    cl_launch_max(stream, work.sizes, quads, n, stats, moments);
     return hipGetLastError();
 }
 
 hipError_t icm_launch_step(hipStream_t stream, uint32_t *state, const LatGeom &g, uint64_t t, const uint2 *keys, const ClusterWork &work,
-                           uint32_t n_pairs, uint32_t *stats, uint32_t *minus_sites)
+                           uint32_t n_pairs, uint32_t *stats, uint32_t *minus_sites, const ClusterMomentsOut &moments)
 {
     const uint32_t wpp = g.wpp, tile_rows = (g.H + CL_TILE_ROWS - 1) / CL_TILE_ROWS;
     const uint32_t border = g.H * g.wpr + tile_rows * g.W, quads = g.W * g.H / 4;
@@ -341,7 +403,7 @@ hipError_t icm_launch_step(hipStream_t stream, uint32_t *state, const LatGeom &g
     hipLaunchKernelGGL(cl_tile_kernel, dim3(g.wpr, tile_rows, n_pairs), dim3(256), 0, stream, g, work.bonds, work.labels, work.sizes);
     hipLaunchKernelGGL(cl_merge_kernel, dim3((border + 255) / 256, n_pairs), dim3(256), 0, stream, g, work.bonds, work.labels);
     hipLaunchKernelGGL(icm_flip_kernel, dim3((wpp + 3) / 4, n_pairs), dim3(256), 0, stream, state, g, work.labels, work.fliptab, work.sizes, stats);
-    hipLaunchKernelGGL(cl_max_kernel, dim3((quads + 255) / 256, n_pairs), dim3(256), 0, stream, work.sizes, quads, stats);
+    cl_launch_max(stream, work.sizes, quads, n_pairs, stats, moments);
     return hipGetLastError();
 }
 

@@ -8,6 +8,7 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "cluster_moments.hpp"
 #include "lattice_types.hpp"
 
 namespace isingmc {
@@ -43,15 +44,17 @@ static inline ClusterWork cluster_carve(uint32_t *block, size_t batch, uint64_t 
 
 // One cluster step of replicas [0, n) at timestep t: state / keys / thr_per_replica / stats point at the first replica of the
 // batch.  thr_per_replica == nullptr: every replica uses thr.  stats: [n][2] = {clusters, largest cluster}, zero on entry.
+// moments: with a row, the last launch also adds the cluster-size moments of replica r into column slot0 + r (cluster_moments.hpp).
 hipError_t cluster_launch_step(hipStream_t stream, uint32_t *state, const LatGeom &g, uint64_t t, const uint2 *keys, uint32_t jneg_uniform,
-                               uint64_t thr, const uint64_t *thr_per_replica, const ClusterWork &work, uint32_t n, uint32_t *stats);
+                               uint64_t thr, const uint64_t *thr_per_replica, const ClusterWork &work, uint32_t n, uint32_t *stats,
+                               const ClusterMomentsOut &moments = {});
 
 // One isoenergetic cluster move of pairs [0, n_pairs) at timestep t: pair p = replicas 2 p and 2 p + 1 behind
 // `state` / `keys` (the key of replica 2 p draws the flip bits); the workspace holds n_pairs labelling problems.
 // stats: [n_pairs][2] = {q = -1 clusters, largest one} in the layout cl_max_kernel writes; minus_sites: [n_pairs] q = -1 sites;
-// both zero on entry.
+// both zero on entry.  moments: as above, pair p into column slot0 + p.
 hipError_t icm_launch_step(hipStream_t stream, uint32_t *state, const LatGeom &g, uint64_t t, const uint2 *keys, const ClusterWork &work,
-                           uint32_t n_pairs, uint32_t *stats, uint32_t *minus_sites);
+                           uint32_t n_pairs, uint32_t *stats, uint32_t *minus_sites, const ClusterMomentsOut &moments = {});
 
 // The same move between two containers: pair p = replica slots_a[p] behind state_a and replica slots_b[p] behind
 // state_b, both tables in DEVICE memory ([n_pairs], every slot at most once); keys_a: the keys of state_a's replicas from slot 0

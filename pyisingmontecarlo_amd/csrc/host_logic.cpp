@@ -506,6 +506,11 @@ size_t nonlocal_batch(size_t items, size_t words_per_item, size_t workspace_byte
     return std::min({items, size_t(32768), std::max<size_t>(1, fit)});
 }
 
+uint64_t nonlocal_steps_in(uint64_t t0, uint64_t timesteps, uint64_t k)
+{
+    return k ? (t0 + timesteps) / k - t0 / k : 0; // multiples of k among t + 1 for t in [t0, t0 + timesteps)
+}
+
 ClassSegments class_segments(const uint32_t *site, size_t n_pos, const uint32_t *cls, size_t nvars, size_t n_tables, size_t n_classes)
 {
     ClassSegments S;

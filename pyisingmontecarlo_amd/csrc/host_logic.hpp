@@ -110,6 +110,10 @@ void rj_log_table(uint32_t *out);
 // is the y dimension of one grid).  Internal to the library: not among its dynamic symbols.
 __attribute__((visibility("hidden"))) size_t nonlocal_batch(size_t items, size_t words_per_item, size_t workspace_bytes);
 
+// Non-local steps of a run call: the timesteps t in [t0, t0 + timesteps) with t % k == k - 1; none when k == 0.
+// What a cluster series (S24) needs room for before the call enqueues anything.
+uint64_t nonlocal_steps_in(uint64_t t0, uint64_t timesteps, uint64_t k);
+
 // Site classes of the replica-packed families (device reader: overlap_class_kernels.hip).  site[n_pos]: the site of
 // every position, PAD_SITE on padding; cls[n_tables][nvars]: a class below n_classes or CLASS_NONE per site.  Per table the
 // classed positions are sorted by class (ascending position inside a class) into `order`, and the sorted list is cut into

@@ -7,7 +7,8 @@
 //                  (isingmc_site_classes_*, isingmc_overlaps_by_class); the overlap core they share with the series
 //   overlap_series.hip  the device-resident log of overlap measurements, one row per sample (isingmc_overlap_series_*)
 //   observable_series.hip  the device-resident log of energy and magnetisation per sample (isingmc_observable_series_*)
-//   recorders.hip  the table of the measurements the step loop takes on a period, and the log core of the two series
+//   cluster_series.hip  the device-resident log of cluster-size moments, one row per non-local step (isingmc_cluster_series_*)
+//   recorders.hip  the table of the measurements the step loop takes on a period, and the log core of the series
 //   best.hip       each replica's lowest-energy configuration, kept on the device (isingmc_best_*)
 //   moments.hip    per-site spin sums and per-bond sums over the samples of a run (isingmc_moments_*)
 //   sampling.hip   get_states and the double-buffered sampling pipeline
@@ -124,6 +125,7 @@ struct Options {
     long long moments_bytes = 4ll << 30;   // the most device memory the moment sums of one container may take (64 bits: beyond an int)
     long long overlap_series_bytes = 1ll << 30; // the most device memory the log of one overlap series may take
     long long observable_series_bytes = 1ll << 30; // ... and the log of one observable series
+    long long cluster_series_bytes = 1ll << 30;    // ... and the log of one cluster series
     // Rounds of the sweeps' Philox calls, 10 or 7: the one switch here that selects another trajectory.  Written
     // only through philox_rounds_set (isingmc.hip), which checks the value and the container; read wherever a call is planned
     int philox_rounds = 10;
@@ -158,6 +160,7 @@ struct Options {
         if (const char *v = std::getenv("ISINGMC_MOMENTS_BYTES")) o.moments_bytes = std::atoll(v);
         if (const char *v = std::getenv("ISINGMC_OVERLAP_SERIES_BYTES")) o.overlap_series_bytes = std::atoll(v);
         if (const char *v = std::getenv("ISINGMC_OBSERVABLE_SERIES_BYTES")) o.observable_series_bytes = std::atoll(v);
+        if (const char *v = std::getenv("ISINGMC_CLUSTER_SERIES_BYTES")) o.cluster_series_bytes = std::atoll(v);
         o.philox_rounds = env_int("ISINGMC_PHILOX_ROUNDS", 10);
         return o;
     }
@@ -169,6 +172,7 @@ struct Options {
         if (n == "moments_bytes") { moments_bytes = value; return true; }
         if (n == "overlap_series_bytes") { overlap_series_bytes = value; return true; }
         if (n == "observable_series_bytes") { observable_series_bytes = value; return true; }
+        if (n == "cluster_series_bytes") { cluster_series_bytes = value; return true; }
         const std::pair<const char *, int *> table[] = {
             {"force_real", &force_real}, {"disable_real", &disable_real}, {"force_packed", &force_packed}, {"disable_packed", &disable_packed},
             {"disable_packed_uniform", &disable_packed_uniform}, {"disable_resident", &disable_resident}, {"strip", &strip},
@@ -254,8 +258,9 @@ struct StepPreset {
     const RjBeta *rj = nullptr;        // real-coupling packed path
 };
 
-// The measurements the step loop takes on a period (recorders.hip holds their table), in the order it samples them
-enum Recorder { REC_BEST, REC_MOMENTS, REC_OVERLAPS, REC_OBSERVABLES, REC_COUNT };
+// The measurements the step loop takes on a period (recorders.hip holds their table), in the order it samples them.  REC_CLUSTERS
+// has no period of its own (its `every` stays 0): the non-local steps themselves append its rows
+enum Recorder { REC_BEST, REC_MOMENTS, REC_OVERLAPS, REC_OBSERVABLES, REC_CLUSTERS, REC_COUNT };
 struct SeriesLog;
 
 struct isingmc_states {
@@ -395,7 +400,8 @@ struct isingmc_states {
     int mom_k = 0;
     uint32_t mom_pending = 0;    // samples in the time planes since the last flush (< 2^mom_k)
     // the sample points of the periodic recorders.  REC_BEST: an update follows every timestep after which t % every == 0 (t0 stays
-    // 0).  REC_OVERLAPS / REC_OBSERVABLES: a row of series[...], the one series of its kind that records on a period
+    // 0).  REC_OVERLAPS / REC_OBSERVABLES: a row of series[...], the one series of its kind that records on a period.
+    // REC_CLUSTERS: series[...] is the container's one live cluster series (S24)
     Periodic rec[REC_COUNT];
     SeriesLog *series[REC_COUNT] = {};
     size_t osr_by_rung_live = 0; // live overlap series that read this container's ladder permutation on the device: no isingmc_pt_detach
@@ -697,6 +703,19 @@ IM_INTERNAL int osr_sample_enqueue(isingmc_states *s); // enqueue: one row of th
 IM_INTERNAL int obs_sample_enqueue(isingmc_states *s);
 IM_INTERNAL bool obs_sample_by_rung(const isingmc_states *s); // the container's periodic observable series is one by rung
 
+// ---- cluster_series.hip (the device-resident log of cluster-size moments, one row per non-local step) -----------------------------
+// Around the batches of the non-local step at timestep s->t, of kind ISINGMC_CLUSTER_SERIES_SW / _ICM.  begin: with a live series
+// of that kind, the next row cleared and *out pointing at it (first_slot, n_cols; the step sets slot0 per batch); else out->row
+// stays nullptr and the step runs as without a series.  end (only behind a begin that gave a row): n_clusters, largest and sites
+// out of the step's statistics -- stats[slot][2], minus[slot] or nullptr -- and the row counts.  Enqueue only.
+IM_INTERNAL int cluster_series_begin(isingmc_states *s, int kind, ClusterMomentsOut *out);
+IM_INTERNAL int cluster_series_end(isingmc_states *s, const ClusterMomentsOut &out, const uint32_t *stats, const uint32_t *minus);
+IM_INTERNAL int cluster_series_room_or_fail(const isingmc_states *s, size_t timesteps); // before a run enqueues anything
+IM_INTERNAL void cluster_series_replay_since(isingmc_states *s, uint64_t t0); // the repeat of a call that started at t0 writes its rows again
+// why this container cannot take Swendsen-Wang steps / isoenergetic cluster moves ("" when it can) (nonlocal.hip)
+IM_INTERNAL std::string cluster_obstacle(const isingmc_states *s);
+IM_INTERNAL std::string icm_obstacle(const isingmc_states *s);
+
 // ---- nonlocal.hip (Swendsen-Wang steps and isoenergetic cluster moves) -------------------------------------------------------
 // What the non-local steps of ONE run_steps call keep between them: filled by the call's first such step, the device blocks in the
 // call's DeviceScratch.  The host copies live as long as the call: they feed asynchronous copies.
@@ -742,7 +761,8 @@ static int with_strip_retry(isingmc_states *s, bool may_strip, F &&call)
     s->strip_guard = false;
     if (rc != STRIP_TIMED_OUT) return rc;
     TRY(snapshot_restore(s));
-    recorders_replay_since(s, t0); // (the repeat skips the samples already in the sums and the rows already in the two series)
+    recorders_replay_since(s, t0); // (the repeat skips the samples already in the sums and the rows already in the two series,
+                                   //  and writes the rows of the cluster series again)
     s->t = t0;
     const int rc2 = strip_error(call());
     for (Periodic &p : s->rec) p.replay_to = 0;

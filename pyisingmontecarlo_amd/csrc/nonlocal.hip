@@ -43,7 +43,7 @@ static int read_pair_stats(isingmc_states *s, const uint32_t *d_stats, size_t ca
 // ------------------------------------------------------------------------------------------------
 
 // why this container cannot take cluster steps ("" when it can)
-static std::string cluster_obstacle(const isingmc_states *s)
+std::string cluster_obstacle(const isingmc_states *s)
 {
     const isingmc_graph *g = s->g;
     if (s->packed) { // S11: any graph of the bit-sliced packed path, any sign pattern
@@ -133,15 +133,19 @@ int run_cluster_step(isingmc_states *s, NonlocalRun &n, DeviceScratch &scratch, 
         HIP_TRY(hipMemcpyAsync(n.d_cl_thr, n.h_cl_thr.data(), slots * sizeof(uint64_t), hipMemcpyHostToDevice, s->stream));
     }
     HIP_TRY(hipMemsetAsync(s->d_cl_stats, 0, 2 * slots * sizeof(uint32_t), s->stream));
+    ClusterMomentsOut row; // a live cluster series: every batch adds its columns' moments into the same row
+    TRY(cluster_series_begin(s, ISINGMC_CLUSTER_SERIES_SW, &row));
     for (size_t i0 = 0; i0 < items; i0 += n.batch) {
         const uint32_t ni = uint32_t(std::min(n.batch, items - i0));
+        row.slot0 = uint32_t(s->packed ? 32 * i0 : i0);
         if (s->packed)
             HIP_TRY(pk_cluster_launch_step(s->stream, s->d_state + i0 * n_pos, g->pk, s->t, s->d_keys + i0, thr, n.d_cl_thr ? n.d_cl_thr + 32 * i0 : nullptr,
-                                           n.pk_cl, ni, s->d_cl_stats + 2 * 32 * i0));
+                                           n.pk_cl, ni, s->d_cl_stats + 2 * 32 * i0, row));
         else
             HIP_TRY(cluster_launch_step(s->stream, s->d_state + i0 * g->state_words, g->geom, s->t, s->d_keys + i0, g->jneg_uniform, thr,
-                                        n.d_cl_thr ? n.d_cl_thr + i0 : nullptr, n.cl, ni, s->d_cl_stats + 2 * i0));
+                                        n.d_cl_thr ? n.d_cl_thr + i0 : nullptr, n.cl, ni, s->d_cl_stats + 2 * i0, row));
     }
+    if (row.row) TRY(cluster_series_end(s, row, s->d_cl_stats, nullptr));
     s->cl_have_stats = true;
     s->t++;
     return ISINGMC_OK;
@@ -161,7 +165,7 @@ bool icm_unequal_pair_betas(const isingmc_states *s, const double *betas)
 }
 
 // why this container cannot take isoenergetic cluster moves ("" when it can)
-static std::string icm_obstacle(const isingmc_states *s)
+std::string icm_obstacle(const isingmc_states *s)
 {
     const isingmc_graph *g = s->g;
     if (s->packed) { // S12: any graph of either packed family (the move reads no coupling and no bias)
@@ -253,15 +257,19 @@ int run_icm_step(isingmc_states *s, NonlocalRun &n, DeviceScratch &scratch)
     }
     uint32_t *const minus = s->d_icm_stats + 2 * s->icm_stats_cap;
     HIP_TRY(hipMemsetAsync(s->d_icm_stats, 0, 3 * s->icm_stats_cap * sizeof(uint32_t), s->stream));
+    ClusterMomentsOut row; // a live cluster series: every batch adds its pairs' moments into the same row
+    TRY(cluster_series_begin(s, ISINGMC_CLUSTER_SERIES_ICM, &row));
     for (size_t i0 = 0; i0 < items; i0 += n.batch) {
         const uint32_t ni = uint32_t(std::min(n.batch, items - i0));
+        row.slot0 = uint32_t(s->packed ? 16 * i0 : i0);
         if (s->packed)
             HIP_TRY(pk_icm_launch_step(s->stream, s->d_state + i0 * n_pos, g->pk, s->rj ? g->rj.nbr : nullptr, s->rj ? g->rj.slots : 0, s->t, s->d_keys + i0,
-                                       n.d_icm_mask + i0, n.pk_icm, ni, s->d_icm_stats + 2 * 16 * i0, minus + 16 * i0));
+                                       n.d_icm_mask + i0, n.pk_icm, ni, s->d_icm_stats + 2 * 16 * i0, minus + 16 * i0, row));
         else
             HIP_TRY(icm_launch_step(s->stream, s->d_state + 2 * i0 * g->state_words, g->geom, s->t, s->d_keys + 2 * i0, n.cl, ni, s->d_icm_stats + 2 * i0,
-                                    minus + i0));
+                                    minus + i0, row));
     }
+    if (row.row) TRY(cluster_series_end(s, row, s->d_icm_stats, minus));
     s->icm_have_stats = true;
     s->t++;
     return ISINGMC_OK;

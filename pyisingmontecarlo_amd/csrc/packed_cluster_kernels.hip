@@ -8,7 +8,8 @@
 //   pkc_union_kernel   one thread per (position, replica bit): every active owned bond hooks the larger root below the smaller
 //   pkc_flip_kernel    one thread per (position, replica bit), eight positions after one another: chase to the root, look the flip
 //                      bit up, ballot -> XOR into the state word; counts the roots and the positions per root
-//   pkl_max_kernel<32> largest cluster (packed_label.hpp; pk_cluster_launch_max launches it for S13 too)
+//   pkl_max_kernel<32> largest cluster (packed_label.hpp; pk_cluster_launch_max launches it for S13 too); while a cluster series
+//                      is live pkl_max_moments_kernel<32> in its place
 // Labels are laid out [group][position][replica bit]: lane = replica bit, so the first hop of a wave is one coalesced 128-byte
 // row per position.  Padding positions own no bonds, are never flipped and never counted.  The counting of roots and of
 // positions per root, the workgroup reduction and the largest-cluster kernel are packed_label.hpp's, shared with S12 and S13.
@@ -120,7 +121,8 @@ __global__ __launch_bounds__(256) void pkc_flip_kernel(uint32_t *__restrict__ st
 }
 
 hipError_t pk_cluster_launch_step(hipStream_t stream, uint32_t *state, const PkGraphDev &G, uint64_t t, const uint2 *group_keys, uint64_t thr,
-                                  const uint64_t *thr_per_slot, const PkClusterWork &work, uint32_t n, uint32_t *stats)
+                                  const uint64_t *thr_per_slot, const PkClusterWork &work, uint32_t n, uint32_t *stats,
+                                  const ClusterMomentsOut &moments)
 {
     const uint32_t n_pos = G.n_pos;
     hipLaunchKernelGGL(pkc_init_kernel, dim3(n_pos / 8, n), dim3(256), 0, stream, n_pos, t, group_keys, work.labels, work.sizes, work.fliptab);
@@ -128,7 +130,8 @@ hipError_t pk_cluster_launch_step(hipStream_t stream, uint32_t *state, const PkG
                        work.bonds);
     hipLaunchKernelGGL(pkc_union_kernel, dim3(n_pos / 8, n), dim3(256), 0, stream, G, work.bonds, work.labels);
     hipLaunchKernelGGL(pkc_flip_kernel, dim3(n_pos / PKC_FLIP_POS, n), dim3(256), 0, stream, state, G, work.labels, work.fliptab, work.sizes, stats);
-    return pk_cluster_launch_max(stream, n_pos, work.sizes, n, stats);
+    pkl_launch_max<32>(stream, n_pos, work.sizes, n, stats, moments);
+    return hipGetLastError();
 }
 
 hipError_t pk_cluster_launch_max(hipStream_t stream, uint32_t n_pos, const uint32_t *sizes, uint32_t n, uint32_t *stats)

@@ -7,6 +7,7 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "cluster_moments.hpp"
 #include "packed_types.hpp"
 
 namespace isingmc {
@@ -38,9 +39,11 @@ static inline PkClusterWork pk_cluster_carve(uint32_t *block, size_t batch, uint
 
 // One cluster step of groups [0, n) at timestep t: state / group_keys / thr_per_slot / stats point at the first group of the
 // batch.  thr_per_slot == nullptr: every replica uses thr; else thr_per_slot[32 g + b].  stats: [32 n][2] = {clusters, largest
-// cluster} per (group, replica bit), zero on entry.  n <= 32768.
+// cluster} per (group, replica bit), zero on entry.  n <= 32768.  moments: with a row, the last launch also adds the cluster-size
+// moments of bit b of group g into the column of counter slot slot0 + 32 g + b (cluster_moments.hpp).
 hipError_t pk_cluster_launch_step(hipStream_t stream, uint32_t *state, const PkGraphDev &G, uint64_t t, const uint2 *group_keys, uint64_t thr,
-                                  const uint64_t *thr_per_slot, const PkClusterWork &work, uint32_t n, uint32_t *stats);
+                                  const uint64_t *thr_per_slot, const PkClusterWork &work, uint32_t n, uint32_t *stats,
+                                  const ClusterMomentsOut &moments = {});
 
 // The last launch of the step on its own, for any sizes[n][n_pos][32] (S13's pair blocks have this layout): stats[2 (32 g + b) + 1]
 // = max over p of sizes[g][p][b]; entries whose maximum is 0 are not written.

@@ -9,7 +9,8 @@
 //   pki_flip_kernel    one thread per (position-lane, pair), eight positions after one another: d = 1 lanes chase to the root and
 //                      look the flip bit up, ballot -> one lane XORs both bits of every flipped pair into the state word; counts
 //                      the d = 1 positions, the roots and the positions per root
-//   pkl_max_kernel<16> largest cluster (packed_label.hpp)
+//   pkl_max_kernel<16> largest cluster (packed_label.hpp); while a cluster series is live pkl_max_moments_kernel<16> in its place
+//                      
 // Labels are laid out [group][position][pair]: a wave covers four consecutive positions x 16 pairs, so the first hop of a chase
 // is one coalesced 64-byte row per position.  No kernel waits for another workgroup; every loop walks strictly decreasing
 // labels (cluster_union.hpp).  The owned-bond union loop, the counting of roots, d = 1 positions and positions per root, the
@@ -108,7 +109,7 @@ __global__ __launch_bounds__(256) void pki_flip_kernel(uint32_t *__restrict__ st
 
 hipError_t pk_icm_launch_step(hipStream_t stream, uint32_t *state, const PkGraphDev &G, const uint32_t *nbr_rj, uint32_t rj_slots, uint64_t t,
                               const uint2 *group_keys, const uint32_t *move_mask, const PkIcmWork &work, uint32_t n, uint32_t *stats,
-                              uint32_t *minus)
+                              uint32_t *minus, const ClusterMomentsOut &moments)
 {
     const uint32_t n_pos = G.n_pos;
     hipLaunchKernelGGL(pki_init_kernel, dim3(n_pos / 16, n), dim3(256), 0, stream, n_pos, t, group_keys, work.labels, work.sizes, work.fliptab);
@@ -117,7 +118,7 @@ hipError_t pk_icm_launch_step(hipStream_t stream, uint32_t *state, const PkGraph
     });
     hipLaunchKernelGGL(pki_flip_kernel, dim3(n_pos / PKI_FLIP_POS, n), dim3(256), 0, stream, state, n_pos, G.site, move_mask, work.labels,
                        work.fliptab, work.sizes, stats, minus);
-    hipLaunchKernelGGL(pkl_max_kernel<16>, dim3(std::min(n_pos / 16, 1024u), n), dim3(256), 0, stream, n_pos, work.sizes, stats);
+    pkl_launch_max<16>(stream, n_pos, work.sizes, n, stats, moments);
     return hipGetLastError();
 }
 

@@ -9,6 +9,7 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "cluster_moments.hpp"
 #include "packed_types.hpp"
 #include "real_types.hpp"
 
@@ -41,9 +42,10 @@ static inline PkIcmWork pk_icm_carve(uint32_t *block, size_t batch, uint64_t n_p
 // move_mask[g]: bit 2 j set when pair j of group g moves.  nbr_rj == nullptr: the neighbours of G.nbr_ell (PK_MAX_DEG slots);
 // else nbr_rj[slot][n_pos] with rj_slots slots (the own position in unused slots).  `site` marks the padding (PAD_SITE).
 // stats: [16 n][2] = {clusters, largest cluster}, minus: [16 n] = positions where the pair differs, per (group, pair); zero on
-// entry.  n <= 32768.
+// entry.  n <= 32768.  moments: with a row, the last launch also adds the cluster-size moments of pair j of group g into the column
+// of pair slot slot0 + 16 g + j (cluster_moments.hpp).
 hipError_t pk_icm_launch_step(hipStream_t stream, uint32_t *state, const PkGraphDev &G, const uint32_t *nbr_rj, uint32_t rj_slots, uint64_t t,
                               const uint2 *group_keys, const uint32_t *move_mask, const PkIcmWork &work, uint32_t n, uint32_t *stats,
-                              uint32_t *minus);
+                              uint32_t *minus, const ClusterMomentsOut &moments = {});
 
 } // namespace isingmc

@@ -101,6 +101,45 @@ __global__ __launch_bounds__(256) void pkl_max_kernel(const uint32_t n_pos, cons
     if (threadIdx.x < LANES && total) atomicMax(stats + 2 * (LANES * size_t(g) + threadIdx.x) + 1, total);
 }
 
+// pkl_max_kernel with the cluster-size moments of DESIGN.md S24, launched in its place while a cluster series is live: the same
+// grid and the same walk over sizes[g][p][column].  The flip kernels count real positions (d = 1 positions) alone and the init
+// kernels clear every entry, so padding positions and the columns of pairs that do not move read 0 and add nothing; a column
+// whose counter slot out.slot0 + LANES g + c lies outside the row -- a bit the shard does not own -- is summed and dropped.
+// Each thread holds S2 in 64 bits and S4 in 128 (cluster_moments.hpp); the position-lanes of a wave add up by shuffles and the
+// wave's first LANES lanes add into their columns.  Bounded by the read of `sizes`, as the kernel it replaces.
+template <uint32_t LANES>
+__global__ __launch_bounds__(256) void pkl_max_moments_kernel(const uint32_t n_pos, const uint32_t *__restrict__ sizes, uint32_t *__restrict__ stats,
+                                                              const ClusterMomentsOut out)
+{
+    __shared__ uint32_t red[4][LANES];
+    const uint32_t g = blockIdx.y, c = threadIdx.x & (LANES - 1), pl = threadIdx.x / LANES;
+    const uint32_t *sz = sizes + size_t(g) * n_pos * LANES + c;
+    uint32_t m = 0;
+    ClusterMoments sum;
+    for (uint32_t p = blockIdx.x * (256 / LANES) + pl; p < n_pos; p += gridDim.x * (256 / LANES)) {
+        const uint32_t s = sz[size_t(LANES) * p];
+        if (s) { // (most positions are no roots)
+            m = max(m, s);
+            sum.add_size(s);
+        }
+    }
+#pragma unroll
+    for (uint32_t sh = LANES; sh <= 32; sh *= 2) sum.add_lane_xor(int(sh));
+    const uint32_t col = out.slot0 + LANES * g + c - out.first_slot;
+    if ((threadIdx.x & 63u) < LANES && col < out.n_cols) sum.add_to(out.row + size_t(CLS_ROW) * col);
+    const uint32_t total = pkl_reduce(m, red, [](uint32_t a, uint32_t b) { return max(a, b); });
+    if (threadIdx.x < LANES && total) atomicMax(stats + 2 * (LANES * size_t(g) + threadIdx.x) + 1, total);
+}
+
+// the last launch of a step on the packed layouts: pkl_max_kernel, or its moments form while a series is live (out.row)
+template <uint32_t LANES>
+inline void pkl_launch_max(hipStream_t stream, uint32_t n_pos, const uint32_t *sizes, uint32_t n, uint32_t *stats, const ClusterMomentsOut &out)
+{
+    const dim3 grid(n_pos / (256 / LANES) < 1024u ? n_pos / (256 / LANES) : 1024u, n);
+    if (out.row) hipLaunchKernelGGL(pkl_max_moments_kernel<LANES>, grid, dim3(256), 0, stream, n_pos, sizes, stats, out);
+    else hipLaunchKernelGGL(pkl_max_kernel<LANES>, grid, dim3(256), 0, stream, n_pos, sizes, stats);
+}
+
 // The overlap word of a pair block, in a grid of (n_pos / 8, n_blocks) with 32 pair lanes: bit i of d[B][p] is set where the two
 // replicas of pair pair0 + 32 B + i -- slot a.slots[pair] of a, slot b.slots[pair] of b -- differ at position p; 0 on padding
 // and on empty lanes.

@@ -134,6 +134,29 @@ struct SeriesHandleOf {
 };
 using SeriesHandle = SeriesHandleOf<isingmc_overlap_series, isingmc_overlap_series_destroy>;
 using ObsSeriesHandle = SeriesHandleOf<isingmc_observable_series, isingmc_observable_series_destroy>;
+using ClusterSeriesHandle = SeriesHandleOf<isingmc_cluster_series, isingmc_cluster_series_destroy>; // (no class set; columns: replicas or pairs)
+
+// the rows of a cluster series, t[n] and rows[n][columns][6] as isingmc_cluster_series_get hands them out, as (timesteps uint64[m],
+// n_clusters, largest, sites, s2, s4_lo, s4_hi: uint64[m, C] each): the m rows of timesteps >= from_t
+py::tuple cluster_series_rows(const std::vector<uint64_t> &t, const std::vector<uint64_t> &rows, size_t columns, uint64_t from_t)
+{
+    const size_t n = t.size();
+    size_t skip = 0;
+    while (skip < n && t[skip] < from_t) skip++;
+    const ssize_t N = ssize_t(n - skip), C = ssize_t(columns);
+    py::array_t<uint64_t> ts(std::vector<ssize_t>{N});
+    std::copy(t.begin() + skip, t.end(), ts.mutable_data());
+    py::tuple out(7);
+    out[0] = ts;
+    for (size_t e = 0; e < 6; e++) {
+        py::array_t<uint64_t> a(std::vector<ssize_t>{N, C});
+        uint64_t *d = a.mutable_data();
+        for (size_t k = skip; k < n; k++)
+            for (size_t c = 0; c < columns; c++) d[(k - skip) * columns + c] = rows[(k * columns + c) * 6 + e];
+        out[e + 1] = a;
+    }
+    return out;
+}
 
 struct EdgeArrays {
     std::vector<uint64_t> a, b;
@@ -468,6 +491,33 @@ public:
         });
         if (bins) return py::make_tuple(energies, mags, by_class);
         return py::make_tuple(energies, mags);
+    }
+
+    // extension: the improved estimators' raw material.  thermalization_time + timesteps timesteps at beta with the
+    // cluster period set on this object (set_cluster_update_every: a column per experiment; set_replica_cluster_update_every: a
+    // column per pair), the cluster-size moments of every non-local step logged on the device: one run, one read.  Returns
+    // (timesteps uint64[n], n_clusters, largest, sites, s2, s4_lo, s4_hi: uint64[n, C] each) for the steps at timesteps >=
+    // thermalization_time.  One device: the log lives in one container.  ValueError with neither period on.
+    py::tuple run_monte_carlo_and_measure_clusters(double beta, size_t timesteps, size_t num_experiments, std::optional<size_t> thermalization_time)
+    {
+        require_classical();
+        if (!cluster_every_ && !icm_every_)
+            throw py::value_error("no cluster period is on: set_cluster_update_every(k) or set_replica_cluster_update_every(k) first (neither is set)");
+        if (devices_.size() != 1) throw py::value_error("cluster measurement runs on one device: the log lives in one container (set_device)");
+        const size_t therm = thermalization_time.value_or(0), total = therm + timesteps, k = cluster_every_ ? cluster_every_ : icm_every_;
+        const int kind = cluster_every_ ? ISINGMC_CLUSTER_SERIES_SW : ISINGMC_CLUSTER_SERIES_ICM;
+        const size_t columns = cluster_every_ ? num_experiments : num_experiments / 2;
+        uint64_t steps = 0;
+        check(isingmc_host_nonlocal_steps(0, total, k, &steps));
+        std::vector<uint64_t> t(steps), rows(size_t(steps) * columns * 6);
+        fan_out(num_experiments, 0, num_experiments, [&](isingmc_states *s, size_t) {
+            ClusterSeriesHandle h; // (the series goes before the container fan_out destroys)
+            int rc = isingmc_cluster_series_create(s, kind, std::max<size_t>(1, size_t(steps)), &h.s);
+            if (rc == ISINGMC_OK) rc = isingmc_do_time_steps(s, total, &beta, 0, nullptr);
+            if (rc == ISINGMC_OK) rc = isingmc_cluster_series_get(h.s, 0, size_t(steps), t.data(), rows.data());
+            return rc;
+        });
+        return cluster_series_rows(t, rows, columns, therm);
     }
 
     // lattice.rs:309-385
@@ -1082,6 +1132,36 @@ public:
         return py::make_tuple(t, e, m, h.n_tables ? py::object(cls) : py::object(py::none()));
     }
     void reset_measured_observables() { if (obs_series_) check(isingmc_observable_series_reset(obs_series_->s)); }
+    // extension: the cluster-size moments of every non-local step of the persistent replicas, logged on the device.
+    // set_measure_clusters(capacity): a new log of `capacity` rows; its kind follows whichever period is on -- Swendsen-Wang steps
+    // (set_cluster_update_every: a column per replica) or isoenergetic moves (set_replica_cluster_update_every: a column per pair);
+    // ValueError if neither is.  get_measured_clusters() -> (timesteps uint64[n], n_clusters, largest, sites, s2, s4_lo, s4_hi:
+    // uint64[n, C] each); reset_measured_clusters() empties the log.  add_graph is refused while the log lives.
+    void set_measure_clusters(size_t capacity)
+    {
+        size_t sw = 0, icm = 0;
+        check(isingmc_states_cluster_every(st_->s, &sw));
+        check(isingmc_states_icm_every(st_->s, &icm));
+        if (!sw && !icm) throw py::value_error("neither cluster period is on: set_cluster_update_every(k) or set_replica_cluster_update_every(k) first");
+        cluster_series_.reset(); // (the old log goes before the new one takes the container's one slot)
+        auto h = std::make_unique<ClusterSeriesHandle>();
+        h->columns = sw ? isingmc_states_count(st_->s) : isingmc_states_count(st_->s) / 2;
+        check(isingmc_cluster_series_create(st_->s, sw ? ISINGMC_CLUSTER_SERIES_SW : ISINGMC_CLUSTER_SERIES_ICM, capacity, &h->s));
+        cluster_series_ = std::move(h);
+    }
+    py::tuple get_measured_clusters()
+    {
+        if (!cluster_series_) throw py::value_error("no clusters are logged: call set_measure_clusters() first");
+        size_t n = 0;
+        check(isingmc_cluster_series_count(cluster_series_->s, &n, nullptr));
+        std::vector<uint64_t> t(n), rows(n * cluster_series_->columns * 6);
+        {
+            py::gil_scoped_release nogil;
+            check(isingmc_cluster_series_get(cluster_series_->s, 0, n, t.data(), rows.data()));
+        }
+        return cluster_series_rows(t, rows, cluster_series_->columns, 0);
+    }
+    void reset_measured_clusters() { if (cluster_series_) check(isingmc_cluster_series_reset(cluster_series_->s)); }
     // extension: Swendsen-Wang cluster steps on the persistent replicas (see Lattice.set_cluster_update_every); the graph is known
     // here, so one the cluster step does not serve raises ValueError at once
     void set_cluster_update_every(size_t k) { check(isingmc_states_set_cluster_every(st_->s, k)); }
@@ -1149,6 +1229,7 @@ private:
     std::shared_ptr<StatesHandle> st_;
     std::unique_ptr<SeriesHandle> series_; // (declared last: destroyed before the container it reads)
     std::unique_ptr<ObsSeriesHandle> obs_series_; // (the same)
+    std::unique_ptr<ClusterSeriesHandle> cluster_series_; // (the same)
 };
 
 } // namespace
@@ -1191,6 +1272,8 @@ PYBIND11_MODULE(_py_monte_carlo, m)
              "per_experiment"_a = true, "bonds"_a = false)
         .def("run_monte_carlo_and_measure_observables", &Lattice::run_monte_carlo_and_measure_observables, "beta"_a, "timesteps"_a,
              "num_experiments"_a, "thermalization_time"_a = py::none(), "sampling_freq"_a = py::none(), "classes"_a = py::none())
+        .def("run_monte_carlo_and_measure_clusters", &Lattice::run_monte_carlo_and_measure_clusters, "beta"_a, "timesteps"_a,
+             "num_experiments"_a, "thermalization_time"_a = py::none())
         .def("run_monte_carlo_annealing", &Lattice::run_monte_carlo_annealing, "betas"_a, "timesteps"_a,
              "num_experiments"_a, "only_basic_moves"_a = py::none(), "edge_move_importance_sampling"_a = py::none(),
              "replica_range"_a = py::none())
@@ -1243,6 +1326,9 @@ PYBIND11_MODULE(_py_monte_carlo, m)
         .def("set_measure_observables_every", &ClassicIsing::set_measure_observables_every, "k"_a, "classes"_a = py::none(), "capacity"_a = 4096)
         .def("get_measured_observables", &ClassicIsing::get_measured_observables)
         .def("reset_measured_observables", &ClassicIsing::reset_measured_observables)
+        .def("set_measure_clusters", &ClassicIsing::set_measure_clusters, "capacity"_a = 4096)
+        .def("get_measured_clusters", &ClassicIsing::get_measured_clusters)
+        .def("reset_measured_clusters", &ClassicIsing::reset_measured_clusters)
         .def("set_track_minimum", &ClassicIsing::set_track_minimum, "every"_a)
         .def("get_minimum", &ClassicIsing::get_minimum)
         .def("reset_minimum", &ClassicIsing::reset_minimum)

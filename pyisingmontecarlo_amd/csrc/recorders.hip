@@ -1,6 +1,8 @@
 // libisingmc.so: the measurements the step loop takes on a period -- minimum tracking, the moment sums (S18), the
 // overlap series (S21), the observable series (S22) -- as one table with the functions over it that serve every place which has to
-// know all recorders (a new recorder is a row), and the log core the two series share.  Nothing here is a kernel.
+// know all recorders (a new recorder is a row), and the log core the series share.  The cluster series (S24) is a row too: it has
+// no period, the non-local steps append its rows, but it can run full and it objects to what the others object to.  Nothing here is
+// a kernel.
 #include "internal.hpp"
 
 // Plain function pointers in a constant table (as OverlapSink argues in internal.hpp: nothing on the sampling path allocates).
@@ -24,6 +26,9 @@ static const RecorderRow RECORDERS[REC_COUNT] = {
     {obs_sample_enqueue, [](const isingmc_states *s, size_t n) { return series_room_or_fail(s, REC_OBSERVABLES, n); }, true, true,
      "an observable series records on a period for this container (isingmc_observable_series_set_every): its columns are the replicas it holds; switch the period on after the graphs are added",
      "an observable series records on a period for this container (isingmc_observable_series_set_every): a resampling replaces the replicas whose columns it follows; switch the period off first"},
+    {nullptr, cluster_series_room_or_fail, false, false, // (never due: the rows are the non-local steps'; a repeat writes them again, below)
+     "a cluster series is live on this container (isingmc_cluster_series_create): its columns are the replicas it holds; make the series after the graphs are added",
+     "a cluster series is live on this container (isingmc_cluster_series_create): a resampling replaces the replicas whose columns it follows; destroy the series first"},
 };
 
 int recorders_sample(isingmc_states *s, bool after_strip, int &rc)
@@ -66,13 +71,14 @@ void recorders_replay_since(isingmc_states *s, uint64_t t0)
 {
     for (int i = 0; i < REC_COUNT; i++)
         if (RECORDERS[i].replay_guard) s->rec[i].replay_since(t0);
+    cluster_series_replay_since(s, t0);
 }
 
 const char *recorders_refusal(const isingmc_states *s, RecorderRefusal what)
 {
     for (int i = 0; i < REC_COUNT; i++) {
         const char *why = what == RecorderRefusal::Append ? RECORDERS[i].refuse_append : RECORDERS[i].refuse_resample;
-        if (s->rec[i].every && why) return why;
+        if ((s->rec[i].every || s->series[i]) && why) return why; // (on: a period, or the series that holds the container's slot)
     }
     return nullptr;
 }
