@@ -154,6 +154,20 @@ int isingmc_host_pt_statistics_round(uint64_t round, size_t n_rungs, const uint3
 int isingmc_host_pa_sources(uint64_t seed, uint64_t step, size_t n, const double *energies, double dbeta, uint32_t *src_out,
                             uint64_t *sum_out, double *eref_out);
 
+/* The temperature step of a population-annealing schedule, chosen from the population itself, the host twin of
+ * what isingmc_pa_choose_step computes on the device.  energies[n] as for isingmc_host_pa_sources; dbeta_max > 0 and finite; target
+ * in (0, 1], taken as t32 = ceil(target 2^32).  Candidates k = 1 .. 65536 with dbeta_k = double(k) * (dbeta_max 2^-16), one rounded
+ * multiplication.  Per candidate: W[r](k) = the weights of isingmc_host_pa_sources for dbeta_k (E_ref = min E), S(k) = sum W,
+ * N(k) = sum_r min(S, n W[r]) as a 128-bit integer; the candidate HOLDS when N(k) 2^32 >= t32 n S(k) (128-bit compare), that is
+ * when the overlap (1/n) sum_r min(1, tau_r) of the energy histograms at the two temperatures -- tau_r = n W[r] / S, the expected
+ * number of copies of replica r -- is at least the target.  The search is fixed (the result is defined even where rounding makes
+ * the predicate non-monotone): lo = 0, width = 65536; four rounds with step = width / 16 evaluate lo + j step for j = 1 .. 16
+ * (first round) or 1 .. 15, j* = the number of leading candidates that hold, lo += j* step, width = step; j* = 16 in the first round
+ * ends the search with k = 65536.  Result: k = max(lo, 1), dbeta_k, S(k) and N(k) = *num_hi_out 2^64 + *num_lo_out (any output may
+ * be NULL).  A population of equal energies takes the whole dbeta_max; k >= 1 guarantees progress. */
+int isingmc_host_pa_choose_step(size_t n, const double *energies, double dbeta_max, double target, uint32_t *k_out, double *dbeta_out,
+                                uint64_t *sum_out, uint64_t *num_lo_out, uint64_t *num_hi_out);
+
 /* The position lists of a class set on the replica-packed families, as isingmc_site_classes_create builds them
  * for the device.  site[n_pos]: the site at every position of the packed layout, 0xFFFFFFFF on padding; cls[n_tables][nvars]: a
  * class below n_classes or 0xFFFFFFFF (no class) per site.  Per table the classed, non-padding positions are sorted by class,
@@ -692,7 +706,8 @@ void isingmc_pt_group_destroy(isingmc_pt_group *group);
  * Served: checkerboard containers with fast_path == 0 and both replica-packed families.  Refused with ISINGMC_ERR_INVALID and a
  * message by every entry point of this block, the container untouched: the f64 CSR family; lattices with fields, open boundaries or anisotropic couplings (they
  * have no device-side energy array); a tempering ladder attached; per-replica betas set; a shard of a larger set of experiments;
- * an empty container; more than 2^31 replicas; a non-finite dbeta. */
+ * an empty container; more than 2^31 replicas; a non-finite dbeta.  The steps may be given (isingmc_pa_run) or chosen from the
+ * population as the schedule runs (isingmc_pa_choose_step, isingmc_pa_run_adaptive). */
 /* enqueue only: measure, weights, prefix sum, source table, gather.  dbeta = beta_to - beta_from; (seed, step) key the offset. */
 int isingmc_pa_resample(isingmc_states *states, double dbeta, uint64_t seed, uint64_t step);
 /* the gather alone with the caller's table src[count] in host memory: new slot j <- old replica src[j]; any table with entries
@@ -706,6 +721,28 @@ int isingmc_pa_apply_sources(isingmc_states *states, const uint32_t *src);
  * isingmc_pa_resample and isingmc_do_time_steps. */
 int isingmc_pa_run(isingmc_states *states, const double *betas, size_t n_betas, size_t sweeps_per_beta, uint64_t seed,
                    uint64_t *sum_out, double *eref_out, uint64_t *distinct_out, double *mean_energy_out);
+/* The step chooser: measures the energies as isingmc_pa_resample would, runs the rule of
+ * isingmc_host_pa_choose_step on the device (grid-wide integer reductions, stream-ordered launches) and synchronises to return
+ * the decision.  It READS only: configurations, random numbers, the timestep, the families and the record of isingmc_pa_last stay
+ * as they are.  An isingmc_pa_resample(*dbeta_out) that follows forms exactly the weights the choice was made with: its record's sum
+ * equals *sum_out.  Refused like the other entry points of this block (and like isingmc_pa_resample while a recorder objects), and for
+ * a dbeta_max that is not finite and positive or a target outside (0, 1]; the container untouched. */
+int isingmc_pa_choose_step(isingmc_states *states, double dbeta_max, double target, uint32_t *k_out, double *dbeta_out, uint64_t *sum_out,
+                           uint64_t *num_lo_out, uint64_t *num_hi_out);
+/* A schedule from beta_start up to beta_end whose steps are chosen as it runs: sweeps_per_beta timesteps at beta_start, then
+ * { isingmc_pa_choose_step with dbeta_max = min(dbeta_cap, beta_end - beta); beta += dbeta -- or, when k = 65536 and that
+ * dbeta_max reaches beta_end, beta = beta_end exactly; the resampling for dbeta keyed by (seed, step index 1, 2, ..);
+ * sweeps_per_beta timesteps } until beta = beta_end.  dbeta_cap > 0 (infinity: no cap).  Same results as that loop of
+ * isingmc_pa_choose_step, isingmc_pa_resample and isingmc_do_time_steps.  The host waits once per temperature, for the decision
+ * (it builds the acceptance tables from the beta); the search is enqueued behind the sweeps.  betas_out[max_steps + 1] receives the
+ * schedule, *n_betas_out its length; sum_out / eref_out / distinct_out / mean_energy_out[max_steps] (any may be NULL) the step
+ * records as isingmc_pa_run reports them.  If max_steps steps do not reach beta_end: ISINGMC_ERR_INVALID, the container at the last
+ * completed temperature betas_out[*n_betas_out - 1], the outputs filled that far.  isingmc_pa_run on betas_out repeats the run
+ * wherever betas[k] - betas[k-1] gives back every chosen dbeta exactly (always for the last step; for all steps when beta_start,
+ * beta_end and dbeta_cap are dyadic, as multiples of 2^-20 below 1 are); elsewhere the two differ by the rounding of that difference. */
+int isingmc_pa_run_adaptive(isingmc_states *states, double beta_start, double beta_end, size_t sweeps_per_beta, uint64_t seed,
+                            double target, double dbeta_cap, size_t max_steps, double *betas_out, size_t *n_betas_out,
+                            uint64_t *sum_out, double *eref_out, uint64_t *distinct_out, double *mean_energy_out);
 /* synchronises; the record of the last resampling (isingmc_pa_resample, or the last step of isingmc_pa_run): src_out[count]
  * (NULL allowed; that resampling's own table -- a later isingmc_pa_apply_sources does not touch it), S, E_ref, the number of distinct sources and the population's mean energy before the resampling.
  * ISINGMC_ERR_INVALID before the first resampling. */

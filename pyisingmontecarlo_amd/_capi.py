@@ -51,6 +51,8 @@ _PROTOTYPES = {
     "isingmc_host_pt_statistics_round": (C.c_int, [C.c_uint64, C.c_size_t] + [_vp] * 11 + [C.POINTER(C.c_uint64)]),
     "isingmc_host_pa_sources": (C.c_int, [C.c_uint64, C.c_uint64, C.c_size_t, _vp, C.c_double, _vp, C.POINTER(C.c_uint64),
                                           C.POINTER(C.c_double)]),
+    "isingmc_host_pa_choose_step": (C.c_int, [C.c_size_t, _vp, C.c_double, C.c_double, C.POINTER(C.c_uint32), C.POINTER(C.c_double),
+                                              C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "isingmc_host_class_segments": (C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, C.POINTER(C.c_size_t), _vp,
                                               C.POINTER(C.c_size_t), _vp]),
     "isingmc_host_rj_quantise": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_size_t, _vp, _vp, _vp, _vp, C.POINTER(C.c_int),
@@ -144,6 +146,10 @@ _PROTOTYPES = {
     "isingmc_pa_resample": (C.c_int, [_vp, C.c_double, C.c_uint64, C.c_uint64]),
     "isingmc_pa_apply_sources": (C.c_int, [_vp, _vp]),
     "isingmc_pa_run": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "isingmc_pa_choose_step": (C.c_int, [_vp, C.c_double, C.c_double, C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_uint64),
+                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "isingmc_pa_run_adaptive": (C.c_int, [_vp, C.c_double, C.c_double, C.c_size_t, C.c_uint64, C.c_double, C.c_double, C.c_size_t, _vp,
+                                          C.POINTER(C.c_size_t), _vp, _vp, _vp, _vp]),
     "isingmc_pa_last": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "isingmc_pa_families": (C.c_int, [_vp, _vp]),
     "isingmc_pa_reset_families": (C.c_int, [_vp]),
@@ -350,6 +356,19 @@ def pa_sources(seed, step, energies, dbeta):
     _check(lib().isingmc_host_pa_sources(C.c_uint64(int(seed)), C.c_uint64(int(step)), len(e), _p(e), float(dbeta), _p(src),
                                          C.byref(total), C.byref(eref)))
     return src, total.value, eref.value
+
+
+def _pa_choice(call):
+    """dict(k, dbeta, sum, num): the outputs of one of the two step choosers (num = N as a Python integer)."""
+    k, dbeta, total, lo, hi = C.c_uint32(), C.c_double(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+    _check(call(C.byref(k), C.byref(dbeta), C.byref(total), C.byref(lo), C.byref(hi)))
+    return dict(k=k.value, dbeta=dbeta.value, sum=total.value, num=(hi.value << 64) | lo.value)
+
+
+def pa_choose_step(energies, dbeta_max, target):
+    """The temperature step of a population-annealing schedule from the energies, on the host."""
+    e = _arr(energies, np.float64)
+    return _pa_choice(lambda *out: lib().isingmc_host_pa_choose_step(len(e), _p(e), float(dbeta_max), float(target), *out))
 
 
 NO_CLASS = 0xFFFFFFFF
@@ -1096,6 +1115,28 @@ class States:
         eref, mean = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.float64)
         _check(lib().isingmc_pa_run(self._h, _p(b), len(b), int(sweeps_per_beta), C.c_uint64(int(seed)), _p(total), _p(eref), _p(distinct), _p(mean)))
         return dict(sum=total, eref=eref, distinct=distinct, mean_energy=mean)
+
+    def pa_choose_step(self, dbeta_max, target):
+        """dict(k, dbeta, sum, num) of the step chosen for the population as it stands; reads only, synchronises."""
+        return _pa_choice(lambda *out: lib().isingmc_pa_choose_step(self._h, float(dbeta_max), float(target), *out))
+
+    def pa_run_adaptive(self, beta_start, beta_end, sweeps_per_beta, seed, target, dbeta_cap=None, max_steps=10000):
+        """A schedule whose steps are chosen as it runs: dict(betas, sum, eref, distinct, mean_energy), one record per step.  A
+        ValueError for a max_steps that does not reach beta_end carries what was completed as its attribute `partial`."""
+        betas, n = np.zeros(max_steps + 1, dtype=np.float64), C.c_size_t()
+        total, distinct = np.zeros(max_steps, dtype=np.uint64), np.zeros(max_steps, dtype=np.uint64)
+        eref, mean = np.zeros(max_steps, dtype=np.float64), np.zeros(max_steps, dtype=np.float64)
+        cap = float("inf") if dbeta_cap is None else float(dbeta_cap)
+        rc = lib().isingmc_pa_run_adaptive(self._h, float(beta_start), float(beta_end), int(sweeps_per_beta), C.c_uint64(int(seed)), float(target),
+                                           cap, int(max_steps), _p(betas), C.byref(n), _p(total), _p(eref), _p(distinct), _p(mean))
+        m = max(n.value, 1) - 1
+        out = dict(betas=betas[:n.value].copy(), sum=total[:m].copy(), eref=eref[:m].copy(), distinct=distinct[:m].copy(), mean_energy=mean[:m].copy())
+        try:
+            _check(rc)
+        except ValueError as e:
+            e.partial = out
+            raise
+        return out
 
     def pa_resample(self, dbeta, seed, step):
         """Resample the population for the step dbeta = beta_to - beta_from; enqueue only."""

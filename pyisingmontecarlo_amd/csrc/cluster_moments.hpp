@@ -9,6 +9,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "sum128.hpp"
+
 namespace isingmc {
 
 constexpr uint32_t CLS_ROW = 6;
@@ -24,34 +26,27 @@ struct ClusterMomentsOut {
 
 // the sums of one thread, then of one wave
 struct ClusterMoments {
-    unsigned long long s2 = 0, s4_lo = 0, s4_hi = 0;
+    unsigned long long s2 = 0;
+    Sum128 s4;
 
-    __device__ __forceinline__ void add128(unsigned long long lo, unsigned long long hi)
-    {
-        s4_lo += lo;
-        s4_hi += hi + (s4_lo < lo ? 1ull : 0ull);
-    }
     __device__ __forceinline__ void add_size(uint32_t s)
     {
         const unsigned long long q = (unsigned long long)s * s;
         s2 += q;
-        add128(q * q, __umul64hi(q, q));
+        s4.add(q * q, __umul64hi(q, q));
     }
     // this lane's sums + those of lane (lane ^ mask)
     __device__ __forceinline__ void add_lane_xor(int mask)
     {
-        const unsigned long long o2 = __shfl_xor(s2, mask), olo = __shfl_xor(s4_lo, mask), ohi = __shfl_xor(s4_hi, mask);
-        s2 += o2;
-        add128(olo, ohi);
+        s2 += __shfl_xor(s2, mask);
+        s4.add_lane_xor(mask);
     }
-    // into the column at `col`: one 64-bit atomic per word; the add that makes the low word wrap carries one into the high word
+    // into the column at `col`: one 64-bit atomic per word (the carry of the low word of S4: Sum128::atomic_add_to)
     __device__ __forceinline__ void add_to(unsigned long long *col) const
     {
         if (!s2) return; // (no cluster among the sizes this sum saw)
         atomicAdd(col + CLS_S2, s2);
-        const unsigned long long old = atomicAdd(col + CLS_S4_LO, s4_lo);
-        const unsigned long long hi = s4_hi + (old + s4_lo < old ? 1ull : 0ull);
-        if (hi) atomicAdd(col + CLS_S4_HI, hi);
+        s4.atomic_add_to(col + CLS_S4_LO, col + CLS_S4_HI);
     }
 };
 

@@ -183,6 +183,24 @@ extern "C" int isingmc_host_pt_statistics_round(uint64_t round, size_t n_rungs, 
     return ISINGMC_OK;
 }
 
+extern "C" int isingmc_host_pa_choose_step(size_t n, const double *energies, double dbeta_max, double target, uint32_t *k_out, double *dbeta_out,
+                                           uint64_t *sum_out, uint64_t *num_lo_out, uint64_t *num_hi_out)
+{
+    if (n == 0) return fail(ISINGMC_ERR_INVALID, "a population needs at least one replica");
+    if (n > (size_t(1) << 31)) return fail(ISINGMC_ERR_INVALID, "populations above 2^31 replicas are not supported");
+    if (!energies) return fail(ISINGMC_ERR_INVALID, "NULL argument");
+    if (const char *why = pa_choose_refusal(dbeta_max, target)) return fail(ISINGMC_ERR_INVALID, why);
+    for (size_t r = 0; r < n; r++)
+        if (!std::isfinite(energies[r])) return fail(ISINGMC_ERR_INVALID, "energies must be finite");
+    const PaChoice c = pa_choose_step(n, energies, dbeta_max, pa_target32(target));
+    if (k_out) *k_out = c.k;
+    if (dbeta_out) *dbeta_out = c.dbeta;
+    if (sum_out) *sum_out = c.sum;
+    if (num_lo_out) *num_lo_out = c.num_lo;
+    if (num_hi_out) *num_hi_out = c.num_hi;
+    return ISINGMC_OK;
+}
+
 extern "C" int isingmc_host_pa_sources(uint64_t seed, uint64_t step, size_t n, const double *energies, double dbeta, uint32_t *src_out,
                                        uint64_t *sum_out, double *eref_out)
 {

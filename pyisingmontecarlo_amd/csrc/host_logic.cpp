@@ -331,6 +331,56 @@ uint64_t pa_sources(uint64_t seed, uint64_t step, size_t n, const double *energi
     return S;
 }
 
+// ---- population annealing: the step chooser ---------------------------------------------------
+uint64_t pa_target32(double target) { return uint64_t(std::ceil(std::ldexp(target, 32))); }
+
+const char *pa_choose_refusal(double dbeta_max, double target)
+{
+    if (!std::isfinite(dbeta_max) || !(dbeta_max > 0.0)) return "dbeta_max must be finite and positive (heating steps are not chosen)";
+    if (!(target > 0.0) || !(target <= 1.0)) return "the target overlap must lie in (0, 1]";
+    return nullptr;
+}
+
+PaChoice pa_choose_step(size_t n, const double *energies, double dbeta_max, uint64_t t32)
+{
+    using u128 = unsigned __int128;
+    const double eref = *std::min_element(energies, energies + n);
+    const double unit = std::ldexp(dbeta_max, -16);
+    std::vector<double> d(n);
+    for (size_t r = 0; r < n; r++) d[r] = energies[r] - eref;
+    std::vector<uint64_t> W(n);
+    PaChoice kept{};
+    // candidate k: (holds, S, N)
+    const auto evaluate = [&](uint32_t k, PaChoice *out) {
+        volatile double dbeta = double(k) * unit; // (rounded on their own, like the exponent below: see pa_sources)
+        uint64_t S = 0;
+        for (size_t r = 0; r < n; r++) {
+            volatile double m = dbeta * d[r];
+            const double x = -m;
+            S += W[r] = uint64_t(std::ldexp(det_exp_host(x), 32));
+        }
+        u128 N = 0;
+        for (size_t r = 0; r < n; r++) N += std::min<uint64_t>(S, uint64_t(n) * W[r]);
+        *out = PaChoice{k, dbeta, S, uint64_t(N), uint64_t(N >> 64)};
+        return (N << 32) >= u128(t32 * uint64_t(n)) * S;
+    };
+    uint32_t lo = 0, width = 65536;
+    for (int round = 1; round <= 4; round++) {
+        const uint32_t step = width / 16, nc = round == 1 ? 16 : 15;
+        uint32_t jstar = 0;
+        PaChoice c{};
+        while (jstar < nc && evaluate(lo + (jstar + 1) * step, &c)) {
+            kept = c;
+            jstar++;
+        }
+        if (round == 4 && lo == 0 && jstar == 0) kept = c; // k = 1: the candidate that has just failed
+        lo += jstar * step;
+        width = step;
+        if (round == 1 && jstar == 16) break;
+    }
+    return kept; // k = max(lo, 1)
+}
+
 // ---- replica-packed real-coupling path --------------------------------------------------------
 RjQuant rj_quantise(const Adjacency &A, size_t nvars, const double *biases)
 {

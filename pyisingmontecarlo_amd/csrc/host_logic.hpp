@@ -83,6 +83,20 @@ void pt_statistics_round(uint64_t round, size_t n_rungs, const uint32_t *perm_be
 // replica src[j] = the r with n C[r - 1] <= j S + u < n C[r] (systematic resampling; src is non-decreasing).  Returns S; n >= 1.
 uint64_t pa_sources(uint64_t seed, uint64_t step, size_t n, const double *energies, double dbeta, uint32_t *src_out, double *eref_out);
 
+// The step chooser of population annealing (device twin: the pa_choose_* kernels of pa_kernels.hip): the largest
+// step k / 65536 of dbeta_max, k = 1 .. 65536, that a fixed 16-ary search finds with N(k) 2^32 >= t32 n S(k), where the weights are
+// those of pa_sources for dbeta_k = double(k) * (dbeta_max 2^-16), E_ref = min E, S = sum W and N = sum min(S, n W) in 128 bits.
+// Four rounds: the candidates lo + j width / 16, j = 1 .. 16 (15 after the first round), the leading ones that hold move lo; all 16
+// of the first round: k = 65536.  k = max(lo, 1).  n in 1 .. 2^31, dbeta_max > 0, t32 in 1 .. 2^32, everything finite.
+struct PaChoice {
+    uint32_t k;
+    double dbeta;
+    uint64_t sum, num_lo, num_hi;
+};
+uint64_t pa_target32(double target); // ceil(target 2^32): the smallest 2^-32 fixed-point number that is not below target
+PaChoice pa_choose_step(size_t n, const double *energies, double dbeta_max, uint64_t t32);
+const char *pa_choose_refusal(double dbeta_max, double target); // why these arguments are refused, or nullptr
+
 // ---- replica-packed real-coupling path: host halves of the spec ---------------------------
 // Scales: F_i = |h_i| + sum_e |J_e|, Fmax = max F_i, med = the lower median nonzero |coupling or bias|;
 // k = ilogb(min(Fmax, 64 med)) + 1 - 30 is the graph's quantum; site i quantises what it sees at k_i = max(k, ilogb(F_i) + 1 - 30)

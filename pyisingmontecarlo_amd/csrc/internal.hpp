@@ -378,6 +378,10 @@ struct isingmc_states {
     DevBlock<PaRecord> d_pa_record;
     bool pa_have_record = false;    // an isingmc_pa_resample has been enqueued
     bool pa_families_set = false;   // d_pa_family holds the table (else: the identity)
+    // the step chooser (isingmc_pa_choose_step): blocks of its own, so that a choice touches nothing a resampling keeps
+    DevBlock<double> d_pac_energy;  // [pac_cap]
+    size_t pac_cap = 0;
+    DevBlock<PaChoose> d_pac;
     // each replica's lowest-energy configuration (isingmc_best_*): allocated when tracking is switched on (or by the
     // first isingmc_best_update) for the replicas the container holds then, and kept
     DevBlock<uint32_t> d_best_state; // as large as d_state, same layout; padding positions and unowned bits of a packed container

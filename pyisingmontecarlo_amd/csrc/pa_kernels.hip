@@ -8,6 +8,7 @@
 
 #include "det_exp.hpp"
 #include "philox.hpp"
+#include "sum128.hpp"
 
 namespace isingmc {
 
@@ -221,7 +222,199 @@ __global__ __launch_bounds__(256) void pa_bit_gather_kernel(const uint32_t *__re
     out[own] = word;
 }
 
+// ---- step chooser ------------------------------------------------------------------------------------------
+// Grid-wide passes over E[R], 256 threads per workgroup, grid-stride; every workgroup reduces what it saw and adds it to the
+// record with one atomic per word.  Integer sums and an integer maximum: no result depends on the order of the workgroups.
+constexpr uint32_t PAC_THREADS = 256, PAC_WAVES = PAC_THREADS / 64, PAC_MAX_BLOCKS = 2048;
+
+// f64 -> u64 that orders like the values (the bits of a finite double; -0 sorts below +0, which no decision sees)
+__device__ __forceinline__ unsigned long long pac_key(double v)
+{
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    return b >> 63 ? ~b : b | 0x8000000000000000ull;
+}
+__device__ __forceinline__ double pac_key_value(unsigned long long key)
+{
+    return __longlong_as_double((long long)(key >> 63 ? key & 0x7FFFFFFFFFFFFFFFull : ~key));
+}
+
+__device__ __forceinline__ unsigned long long pac_weight(double dbeta, double d)
+{
+    const double x = -__dmul_rn(dbeta, d);
+    return (unsigned long long)(det_exp(x) * 4294967296.0); // in [0, 2^32]: the weight of pa_weights_kernel
+}
+
+// E_ref = min E: rec->eref_key = max of ~key
+__global__ __launch_bounds__(PAC_THREADS) void pa_choose_min_kernel(const double *__restrict__ energies, uint32_t R, PaChoose *rec)
+{
+    __shared__ unsigned long long s_k[PAC_WAVES];
+    unsigned long long best = 0;
+    for (size_t r = size_t(blockIdx.x) * PAC_THREADS + threadIdx.x; r < R; r += size_t(gridDim.x) * PAC_THREADS) {
+        const unsigned long long k = ~pac_key(energies[r]);
+        best = k > best ? k : best;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long other = __shfl_xor(best, o);
+        best = other > best ? other : best;
+    }
+    if ((threadIdx.x & 63u) == 0) s_k[threadIdx.x >> 6] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (uint32_t w = 1; w < PAC_WAVES; w++) best = s_k[w] > best ? s_k[w] : best;
+        atomicMax(&rec->eref_key, best);
+    }
+}
+
+// sum pass: S[j] += W_r(candidate j), NC candidates (16 in the first round, 15 afterwards), the running sums in registers
+template <int NC>
+__global__ __launch_bounds__(PAC_THREADS) void pa_choose_sum_kernel(const double *__restrict__ energies, uint32_t R, PaChoose *rec)
+{
+    __shared__ unsigned long long s_part[PAC_WAVES][PA_CHOOSE_CANDIDATES];
+    if (rec->done) return; // (uniform)
+    const double eref = pac_key_value(~rec->eref_key);
+    double dbeta[NC];
+    unsigned long long acc[NC];
+#pragma unroll
+    for (int j = 0; j < NC; j++) {
+        dbeta[j] = rec->dbeta[j];
+        acc[j] = 0;
+    }
+    for (size_t r = size_t(blockIdx.x) * PAC_THREADS + threadIdx.x; r < R; r += size_t(gridDim.x) * PAC_THREADS) {
+        const double d = __dsub_rn(energies[r], eref);
+#pragma unroll
+        for (int j = 0; j < NC; j++) acc[j] += pac_weight(dbeta[j], d);
+    }
+#pragma unroll
+    for (int j = 0; j < NC; j++) {
+        for (int o = 32; o > 0; o >>= 1) acc[j] += __shfl_xor(acc[j], o);
+        if ((threadIdx.x & 63u) == 0) s_part[threadIdx.x >> 6][j] = acc[j];
+    }
+    __syncthreads();
+    if (threadIdx.x < uint32_t(NC)) {
+        unsigned long long v = 0;
+        for (uint32_t w = 0; w < PAC_WAVES; w++) v += s_part[w][threadIdx.x];
+        if (v) atomicAdd(&rec->sum[threadIdx.x], v);
+    }
+}
+
+// overlap pass: N[j] += min(S[j], R W_r(candidate j)), 128-bit sums (every term is at most 2^63: W <= 2^32, R <= 2^31, S <= R 2^32)
+template <int NC>
+__global__ __launch_bounds__(PAC_THREADS) void pa_choose_overlap_kernel(const double *__restrict__ energies, uint32_t R, PaChoose *rec)
+{
+    __shared__ unsigned long long s_lo[PAC_WAVES][PA_CHOOSE_CANDIDATES], s_hi[PAC_WAVES][PA_CHOOSE_CANDIDATES];
+    if (rec->done) return; // (uniform)
+    const double eref = pac_key_value(~rec->eref_key);
+    double dbeta[NC];
+    unsigned long long S[NC];
+    Sum128 acc[NC];
+#pragma unroll
+    for (int j = 0; j < NC; j++) {
+        dbeta[j] = rec->dbeta[j];
+        S[j] = rec->sum[j];
+    }
+    for (size_t r = size_t(blockIdx.x) * PAC_THREADS + threadIdx.x; r < R; r += size_t(gridDim.x) * PAC_THREADS) {
+        const double d = __dsub_rn(energies[r], eref);
+#pragma unroll
+        for (int j = 0; j < NC; j++) {
+            const unsigned long long rw = (unsigned long long)R * pac_weight(dbeta[j], d);
+            acc[j].add(rw < S[j] ? rw : S[j], 0ull);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NC; j++) {
+        for (int o = 32; o > 0; o >>= 1) acc[j].add_lane_xor(o);
+        if ((threadIdx.x & 63u) == 0) {
+            s_lo[threadIdx.x >> 6][j] = acc[j].lo;
+            s_hi[threadIdx.x >> 6][j] = acc[j].hi;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < uint32_t(NC)) {
+        Sum128 v;
+        for (uint32_t w = 0; w < PAC_WAVES; w++) v.add(s_lo[w][threadIdx.x], s_hi[w][threadIdx.x]);
+        if (v.lo | v.hi) v.atomic_add_to(&rec->num_lo[threadIdx.x], &rec->num_hi[threadIdx.x]);
+    }
+}
+
+// One wave.  round 0 opens the search; round 1 .. 4 counts the leading candidates whose predicate N 2^32 >= t32 R S holds
+// (128-bit compare), moves (lo, width), keeps S and N of the candidate that becomes lo, clears the accumulators and writes the
+// next round's candidates -- or, behind the last round, the result.
+__global__ __launch_bounds__(64) void pa_choose_decide_kernel(PaChoose *rec, uint32_t R, double unit, unsigned long long t32, uint32_t round)
+{
+    const uint32_t j = threadIdx.x;
+    if (rec->done) return; // (uniform)
+    uint32_t lo = 0, width = PA_CHOOSE_GRID;
+    if (round > 0) {
+        lo = rec->lo;
+        width = rec->width;
+        const uint32_t step = width / PA_CHOOSE_CANDIDATES, nc = round == 1 ? PA_CHOOSE_CANDIDATES : PA_CHOOSE_CANDIDATES - 1;
+        bool holds = false;
+        unsigned long long S = 0, n_lo = 0, n_hi = 0;
+        if (j < nc) {
+            S = rec->sum[j];
+            n_lo = rec->num_lo[j];
+            n_hi = rec->num_hi[j];
+            const unsigned long long l_hi = (n_hi << 32) | (n_lo >> 32), l_lo = n_lo << 32; // N < 2^94
+            const unsigned long long a = t32 * R;                                            // <= 2^63
+            const unsigned long long r_hi = __umul64hi(a, S), r_lo = a * S;
+            holds = l_hi > r_hi || (l_hi == r_hi && l_lo >= r_lo);
+        }
+        const unsigned long long fails = ~__ballot(holds);           // (the lanes from nc on fail)
+        const uint32_t jstar = uint32_t(__ffsll((long long)fails)) - 1u; // the leading candidates that hold: 0 .. nc
+        const bool last = round == PA_CHOOSE_ROUNDS;
+        // the candidate that becomes lo -- or k = 1, which the last round evaluates first when lo stays 0
+        const uint32_t keep = jstar ? jstar - 1u : (last && lo == 0 ? 0u : 0xFFFFFFFFu);
+        __syncthreads(); // (every lane has read its accumulators)
+        if (j == keep) {
+            rec->sum_k = S;
+            rec->num_lo_k = n_lo;
+            rec->num_hi_k = n_hi;
+        }
+        lo += jstar * step;
+        width = step;
+        if (j == 0) {
+            const bool all = round == 1 && jstar == PA_CHOOSE_CANDIDATES;
+            if (all || last) {
+                const uint32_t k = lo ? lo : 1u;
+                rec->k = k;
+                rec->dbeta_k = __dmul_rn(double(k), unit);
+                rec->done = all ? 1u : 0u;
+            }
+        }
+    }
+    if (j == 0) {
+        rec->lo = lo;
+        rec->width = width;
+    }
+    if (j < PA_CHOOSE_CANDIDATES) {
+        rec->sum[j] = 0;
+        rec->num_lo[j] = 0;
+        rec->num_hi[j] = 0;
+        rec->dbeta[j] = __dmul_rn(double(lo + (j + 1u) * (width / PA_CHOOSE_CANDIDATES)), unit);
+    }
+}
+
 } // namespace
+
+hipError_t pa_launch_choose(hipStream_t stream, const double *energies, uint32_t R, double unit, unsigned long long t32, PaChoose *rec)
+{
+    const unsigned blocks = unsigned(std::min<size_t>((size_t(R) + PAC_THREADS - 1) / PAC_THREADS, PAC_MAX_BLOCKS));
+    hipError_t err = hipMemsetAsync(rec, 0, sizeof(PaChoose), stream);
+    if (err != hipSuccess) return err;
+    hipLaunchKernelGGL(pa_choose_min_kernel, dim3(blocks), dim3(PAC_THREADS), 0, stream, energies, R, rec);
+    hipLaunchKernelGGL(pa_choose_decide_kernel, dim3(1), dim3(64), 0, stream, rec, R, unit, t32, 0u);
+    for (uint32_t round = 1; round <= PA_CHOOSE_ROUNDS; round++) {
+        if (round == 1) {
+            hipLaunchKernelGGL(pa_choose_sum_kernel<16>, dim3(blocks), dim3(PAC_THREADS), 0, stream, energies, R, rec);
+            hipLaunchKernelGGL(pa_choose_overlap_kernel<16>, dim3(blocks), dim3(PAC_THREADS), 0, stream, energies, R, rec);
+        } else {
+            hipLaunchKernelGGL(pa_choose_sum_kernel<15>, dim3(blocks), dim3(PAC_THREADS), 0, stream, energies, R, rec);
+            hipLaunchKernelGGL(pa_choose_overlap_kernel<15>, dim3(blocks), dim3(PAC_THREADS), 0, stream, energies, R, rec);
+        }
+        hipLaunchKernelGGL(pa_choose_decide_kernel, dim3(1), dim3(64), 0, stream, rec, R, unit, t32, round);
+    }
+    return hipGetLastError();
+}
 
 hipError_t pa_launch_weights(hipStream_t stream, const double *energies, uint32_t R, double dbeta, uint64_t seed, uint64_t step,
                              unsigned long long *weights, PaRecord *rec)

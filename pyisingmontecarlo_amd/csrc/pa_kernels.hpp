@@ -31,6 +31,23 @@ struct PaRecord {
     unsigned long long u;        // the offset in [0, S)
 };
 
+// The step chooser: the device record of one search.  Zero before the search (hipMemsetAsync); the accumulators
+// are zero again behind every decision.
+constexpr uint32_t PA_CHOOSE_CANDIDATES = 16; // per round
+constexpr uint32_t PA_CHOOSE_ROUNDS = 4;
+constexpr uint32_t PA_CHOOSE_GRID = 65536;    // the candidates are k / 65536 of dbeta_max, k = 1 .. 65536
+struct PaChoose {
+    unsigned long long sum[PA_CHOOSE_CANDIDATES];                                   // S of the round's candidates
+    unsigned long long num_lo[PA_CHOOSE_CANDIDATES], num_hi[PA_CHOOSE_CANDIDATES]; // N of the round's candidates, 128 bits
+    double dbeta[PA_CHOOSE_CANDIDATES];                                             // the round's candidates
+    unsigned long long eref_key; // ~(the ordered key of min E): grown with atomicMax from zero
+    uint32_t lo, width;          // the search: the answer is in (lo, lo + width), or lo
+    uint32_t done;               // the first round held at all 16 candidates: k = 65536, the later rounds do nothing
+    uint32_t k;                  // the result, behind the last decision: k, dbeta_k, S(k), N(k)
+    double dbeta_k;
+    unsigned long long sum_k, num_lo_k, num_hi_k;
+};
+
 constexpr size_t pa_scan_blocks(size_t R) { return (R + PA_SCAN_BLOCK - 1) / PA_SCAN_BLOCK; }
 
 // energies[R] -> weights[R] and *rec (distinct = 0); one workgroup
@@ -48,5 +65,9 @@ hipError_t pa_launch_row_gather(hipStream_t stream, const uint32_t *in, uint32_t
 // the real positions; every other bit (slots >= R, padding positions: site[p] == PAD_SITE) is copied from its own place
 hipError_t pa_launch_bit_gather(hipStream_t stream, const uint32_t *in, uint32_t *out, const uint32_t *src, uint32_t R, size_t groups,
                                 uint32_t n_pos, const uint32_t *site);
+// The whole search of the step chooser from energies[R], enqueue only: *rec is cleared, E_ref found, then four
+// rounds of { sum pass, overlap pass, decision }: 15 stream-ordered launches, no workgroup waits for another one.
+// unit = dbeta_max 2^-16; t32 = ceil(target 2^32) in 1 .. 2^32.  The result is in rec->k, dbeta_k, sum_k, num_lo_k, num_hi_k.
+hipError_t pa_launch_choose(hipStream_t stream, const double *energies, uint32_t R, double unit, unsigned long long t32, PaChoose *rec);
 
 } // namespace isingmc

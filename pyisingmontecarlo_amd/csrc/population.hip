@@ -151,6 +151,117 @@ extern "C" int isingmc_pa_run(isingmc_states *s, const double *betas, size_t n_b
     return ISINGMC_OK;
 }
 
+// ---- the step chooser ----------------------------------------------------------------------------------------
+// measure into the chooser's own array, search, wait for the decision: nothing a resampling or a sweep keeps is written
+static int pa_choose(isingmc_states *s, double dbeta_max, double target, PaChoose *out)
+{
+    if (!s->d_pac) TRY(dev_alloc(s->d_pac, 1));
+    if (s->pac_cap < s->R) TRY(dev_regrow(s->stream, s->d_pac_energy, &s->pac_cap, s->R, s->R));
+    TRY(energies_enqueue(s, s->d_pac_energy));
+    HIP_TRY(pa_launch_choose(s->stream, s->d_pac_energy, uint32_t(s->R), std::ldexp(dbeta_max, -16), pa_target32(target), s->d_pac));
+    HIP_TRY(hipMemcpyAsync(out, s->d_pac, sizeof(PaChoose), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return strip_error(strip_check(s));
+}
+
+// what every entry point of the chooser refuses before it touches the container
+static int pa_choose_admit(const isingmc_states *s, double dbeta_max, double target)
+{
+    if (!s) return fail(ISINGMC_ERR_INVALID, "NULL states");
+    if (const char *why = pa_choose_refusal(dbeta_max, target)) return fail(ISINGMC_ERR_INVALID, why);
+    const std::string why = pa_obstacle(s);
+    if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
+    if (const char *rec = recorders_refusal(s, RecorderRefusal::Resample)) return fail(ISINGMC_ERR_INVALID, rec);
+    return ISINGMC_OK;
+}
+
+extern "C" int isingmc_pa_choose_step(isingmc_states *s, double dbeta_max, double target, uint32_t *k_out, double *dbeta_out, uint64_t *sum_out,
+                                      uint64_t *num_lo_out, uint64_t *num_hi_out)
+{
+    TRY(pa_choose_admit(s, dbeta_max, target));
+    TRY(use_device(s->g->device));
+    PaChoose c;
+    TRY(pa_choose(s, dbeta_max, target, &c));
+    if (k_out) *k_out = c.k;
+    if (dbeta_out) *dbeta_out = c.dbeta_k;
+    if (sum_out) *sum_out = c.sum_k;
+    if (num_lo_out) *num_lo_out = c.num_lo_k;
+    if (num_hi_out) *num_hi_out = c.num_hi_k;
+    return ISINGMC_OK;
+}
+
+// The schedule is made as it runs: sweeps at beta_start, then { choose; resample with the chosen step, keyed by (seed, step index);
+// sweeps } until beta_end.  The host waits once per temperature, for the decision: it needs the beta to build the acceptance tables,
+// which go to the device while the resampling runs.  The sweeps of a temperature are in flight while the next search is enqueued.
+extern "C" int isingmc_pa_run_adaptive(isingmc_states *s, double beta_start, double beta_end, size_t sweeps_per_beta, uint64_t seed, double target,
+                                       double dbeta_cap, size_t max_steps, double *betas_out, size_t *n_betas_out, uint64_t *sum_out,
+                                       double *eref_out, uint64_t *distinct_out, double *mean_energy_out)
+{
+    if (n_betas_out) *n_betas_out = 0;
+    if (!betas_out || !n_betas_out) return fail(ISINGMC_ERR_INVALID, "NULL argument");
+    if (!std::isfinite(beta_start) || !std::isfinite(beta_end) || beta_end < beta_start)
+        return fail(ISINGMC_ERR_INVALID, "beta_start and beta_end must be finite with beta_start <= beta_end (heating schedules are not chosen)");
+    if (!(dbeta_cap > 0.0)) return fail(ISINGMC_ERR_INVALID, "dbeta_cap must be positive (infinity: no cap)");
+    TRY(pa_choose_admit(s, 1.0, target));
+    TRY(use_device(s->g->device));
+    TRY(pa_reserve(s));
+    std::unique_ptr<DeviceScratch> tables; // the acceptance tables of the temperature whose sweeps are in flight
+    const auto sweep = [&](double beta) {
+        tables = std::make_unique<DeviceScratch>(s->stream);
+        std::vector<StepPreset> preset;
+        TRY(step_presets_build(s, &beta, 1, *tables, preset));
+        s->step_preset = &preset[0];
+        const int rc = run_steps(s, sweeps_per_beta, &beta, 0, nullptr, nullptr, /*sync=*/false);
+        s->step_preset = nullptr;
+        return rc;
+    };
+    // the record of the resampling before the sweeps in flight: read when the stream has drained
+    const auto read_record = [&](size_t step) {
+        PaRecord rec;
+        HIP_TRY(hipMemcpy(&rec, s->d_pa_record, sizeof rec, hipMemcpyDeviceToHost));
+        if (sum_out) sum_out[step] = rec.sum;
+        if (eref_out) eref_out[step] = rec.eref;
+        if (distinct_out) distinct_out[step] = rec.distinct;
+        if (mean_energy_out) mean_energy_out[step] = rec.mean;
+        return int(ISINGMC_OK);
+    };
+    double beta = beta_start;
+    size_t steps = 0;
+    betas_out[0] = beta;
+    int rc = sweep(beta);
+    while (rc == ISINGMC_OK && beta < beta_end && steps < max_steps) {
+        const double dbeta_max = std::min(dbeta_cap, beta_end - beta);
+        PaChoose c;
+        rc = pa_choose(s, dbeta_max, target, &c); // (waits: the sweeps before are done)
+        if (rc != ISINGMC_OK) break;
+        tables.reset();
+        if (steps) rc = read_record(steps - 1);
+        if (rc != ISINGMC_OK) break;
+        *n_betas_out = steps + 1; // the temperatures completed
+        const double dbeta = c.dbeta_k;
+        // the whole of a dbeta_max that reaches beta_end -- the rest of the way (whatever its rounding), or a cap beyond it -- ends the schedule
+        const bool reaches = !(dbeta_cap < beta_end - beta) || beta + dbeta_max >= beta_end;
+        beta = c.k == PA_CHOOSE_GRID && reaches ? beta_end : beta + dbeta;
+        steps++;
+        rc = pa_resample_enqueue(s, dbeta, seed, steps, s->d_pa_record);
+        if (rc != ISINGMC_OK) break;
+        s->pa_have_record = true;
+        betas_out[steps] = beta;
+        rc = sweep(beta);
+    }
+    if (rc == ISINGMC_OK && s->rec[REC_BEST].every) rc = best_update_enqueue(s); // the final population
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    tables.reset();
+    TRY(strip_error(strip_check(s)));
+    if (rc != ISINGMC_OK) return strip_error(rc);
+    if (steps) TRY(read_record(steps - 1));
+    *n_betas_out = steps + 1;
+    if (beta < beta_end)
+        return fail(ISINGMC_ERR_INVALID, "max_steps = " + std::to_string(max_steps) + " temperature steps did not reach beta_end: the population stands at beta " +
+                                             std::to_string(beta) + " (n_betas_out temperatures completed)");
+    return ISINGMC_OK;
+}
+
 extern "C" int isingmc_pa_apply_sources(isingmc_states *s, const uint32_t *src)
 {
     if (!s || !src) return fail(ISINGMC_ERR_INVALID, "NULL argument");

@@ -590,41 +590,35 @@ public:
         return py::make_tuple(energies, states, steps);
     }
 
-    // extension (DESIGN.md S14): population annealing.  `population` replicas are cooled through the non-decreasing `betas`:
-    // before the sweeps at betas[k], k > 0, the population is resampled on the device for the step betas[k] - betas[k - 1]
-    // (isingmc_pa_resample, step counter k, keyed by the LAST of make_seeds(population + 1); the first `population` seeds key the
-    // replicas); then sweeps_per_beta timesteps at betas[k] (cluster periods set on this object apply).  One library call
-    // (isingmc_pa_run) enqueues it all; nothing waits on the host until the end.
-    // measure_overlaps (DESIGN.md S15): the result also carries the spin and link overlaps of the final population between the
-    // replicas (p, p + R / 2) (isingmc_overlaps); pairs of one family are the caller's to drop.
-    // overlap_classes (DESIGN.md S17; needs measure_overlaps): class tables, one array of nvars classes or a stack of them; the
-    // result also carries overlaps_by_class, int64[R / 2, n_tables, n_classes] for the same pairs (isingmc_overlaps_by_class).
-    // track_minimum (DESIGN.md S16): every SLOT keeps the lowest-energy configuration that ever sat in it, seen before every
-    // resampling and after the last sweeps; the result carries the population's minimum over the slots as min_energy, min_state
-    // and min_beta_index (the index of the beta whose sweeps produced it).
-    py::object run_population_annealing(const std::vector<double> &betas, size_t sweeps_per_beta, size_t population, bool return_states,
-                                        bool measure_overlaps, bool track_minimum, const py::object &overlap_classes)
+    // the schedule of a population-annealing run as it was taken, with the record of every resampling (one fewer than betas)
+    struct PaLog {
+        std::vector<double> betas, erefs, mean;
+        std::vector<uint64_t> sums, distinct;
+    };
+
+    // What the two population-annealing entry points share: the refusals (check_schedule: those of the caller's own arguments, in
+    // their place among them), the container, the schedule `run` drives on it (keyed by the last of make_seeds(population + 1))
+    // and the read-out of the final population.
+    template <typename Check, typename Run>
+    py::object population_annealing(const Check &check_schedule, const Run &run, size_t sweeps_per_beta, size_t population, bool return_states, bool measure_overlaps,
+                                    bool track_minimum, const py::object &overlap_classes)
     {
         require_classical();
         if (!overlap_classes.is_none() && !measure_overlaps)
             throw py::value_error("overlap_classes resolves the overlaps of measure_overlaps=True by site class: it needs measure_overlaps");
         const ClassTables classes = overlap_classes.is_none() ? ClassTables{} : class_tables(overlap_classes, py::none(), E_->nvars);
-        if (betas.empty()) throw py::value_error("betas must hold at least one inverse temperature");
-        for (size_t k = 0; k < betas.size(); k++)
-            if (!std::isfinite(betas[k]) || (k && betas[k] < betas[k - 1])) throw py::value_error("betas must be finite and non-decreasing");
+        check_schedule();
         if (population == 0) throw py::value_error("population must be positive");
         if (sweeps_per_beta == 0) throw py::value_error("sweeps_per_beta must be positive");
         if (devices_.size() != 1) throw py::value_error("population annealing runs on one device: one population lives in one container (set_device)");
-        const size_t R = population, N = E_->nvars, n = betas.size();
+        const size_t R = population, N = E_->nvars;
         const std::vector<uint64_t> seeds = make_seeds(R + 1);
         const std::shared_ptr<GraphHandle> gh = graph(0);
         py::array_t<double> energies(std::vector<ssize_t>{ssize_t(R)});
         py::array_t<bool> states(std::vector<ssize_t>{ssize_t(return_states ? R : 0), ssize_t(N)});
-        py::array_t<double> log_z(std::vector<ssize_t>{ssize_t(n)}), mean_e(std::vector<ssize_t>{ssize_t(n)});
-        py::array_t<int64_t> distinct(std::vector<ssize_t>{ssize_t(n - 1)});
+        PaLog log;
         py::array_t<uint32_t> families(std::vector<ssize_t>{ssize_t(R)});
-        double *e = energies.mutable_data(), *lz = log_z.mutable_data(), *me = mean_e.mutable_data();
-        int64_t *ds = distinct.mutable_data();
+        double *e = energies.mutable_data();
         uint32_t *fam = families.mutable_data();
         uint8_t *st = reinterpret_cast<uint8_t *>(states.mutable_data());
         const size_t n_ovl = measure_overlaps ? R / 2 : 0;
@@ -650,17 +644,7 @@ public:
             if (rc == ISINGMC_OK && icm_every_) rc = isingmc_states_set_icm_every(h.s, icm_every_);
             // the update points are the resamplings and the end of the run: a period no timestep reaches leaves the sweeps uncut
             if (rc == ISINGMC_OK && track_minimum) rc = isingmc_states_set_track_best(h.s, size_t(1) << 62);
-            // the whole schedule is enqueued; the host waits once, at its end, and reads the step records
-            std::vector<uint64_t> sums(n - 1), nd(n - 1);
-            std::vector<double> erefs(n - 1);
-            if (rc == ISINGMC_OK) rc = isingmc_pa_run(h.s, betas.data(), n, sweeps_per_beta, seeds[R], sums.data(), erefs.data(), nd.data(), me);
-            lz[0] = 0.0;
-            for (size_t k = 1; k < n && rc == ISINGMC_OK; k++) {
-                // ln Q = ln(S / (R 2^32)) - dbeta E_ref estimates ln Z(betas[k]) - ln Z(betas[k - 1])
-                const double dbeta = betas[k] - betas[k - 1];
-                lz[k] = lz[k - 1] + (std::log(std::ldexp(double(sums[k - 1]), -32) / double(R)) - dbeta * erefs[k - 1]);
-                ds[k - 1] = int64_t(nd[k - 1]);
-            }
+            if (rc == ISINGMC_OK) rc = run(h.s, seeds[R], log);
             if (rc == ISINGMC_OK) rc = isingmc_get_energies(h.s, e);
             if (rc == ISINGMC_OK && return_states) rc = isingmc_get_states(h.s, st, N);
             if (rc == ISINGMC_OK) rc = isingmc_pa_families(h.s, fam);
@@ -697,6 +681,20 @@ public:
         if (rc == ISINGMC_ERR_INVALID) throw py::value_error(msg);
         if (rc == ISINGMC_ERR_ALLOC) throw std::bad_alloc();
         if (rc != ISINGMC_OK) throw std::runtime_error(msg);
+        const std::vector<double> &betas = log.betas;
+        const size_t n = betas.size();
+        py::array_t<double> log_z(std::vector<ssize_t>{ssize_t(n)}), mean_e(std::vector<ssize_t>{ssize_t(n)});
+        py::array_t<int64_t> distinct(std::vector<ssize_t>{ssize_t(n - 1)});
+        double *lz = log_z.mutable_data(), *me = mean_e.mutable_data();
+        int64_t *ds = distinct.mutable_data();
+        lz[0] = 0.0;
+        for (size_t k = 1; k < n; k++) {
+            // ln Q = ln(S / (R 2^32)) - dbeta E_ref estimates ln Z(betas[k]) - ln Z(betas[k - 1])
+            const double dbeta = betas[k] - betas[k - 1];
+            lz[k] = lz[k - 1] + (std::log(std::ldexp(double(log.sums[k - 1]), -32) / double(R)) - dbeta * log.erefs[k - 1]);
+            ds[k - 1] = int64_t(log.distinct[k - 1]);
+            me[k - 1] = log.mean[k - 1];
+        }
         double sum_e = 0.0, rho = 0.0;
         for (size_t r = 0; r < R; r++) sum_e += e[r];
         me[n - 1] = sum_e / double(R); // the final measurement
@@ -727,6 +725,66 @@ public:
             d["min_beta_index"] = min_t ? (min_t + sweeps_per_beta - 1) / sweeps_per_beta - 1 : size_t(0);
         }
         return py::module_::import("types").attr("SimpleNamespace")(**d);
+    }
+
+    // extension (DESIGN.md S14): population annealing.  `population` replicas are cooled through the non-decreasing `betas`:
+    // before the sweeps at betas[k], k > 0, the population is resampled on the device for the step betas[k] - betas[k - 1]
+    // (isingmc_pa_resample, step counter k, keyed by the LAST of make_seeds(population + 1); the first `population` seeds key the
+    // replicas); then sweeps_per_beta timesteps at betas[k] (cluster periods set on this object apply).  One library call
+    // (isingmc_pa_run) enqueues it all; nothing waits on the host until the end.
+    // measure_overlaps (DESIGN.md S15): the result also carries the spin and link overlaps of the final population between the
+    // replicas (p, p + R / 2) (isingmc_overlaps); pairs of one family are the caller's to drop.
+    // overlap_classes (DESIGN.md S17; needs measure_overlaps): class tables, one array of nvars classes or a stack of them; the
+    // result also carries overlaps_by_class, int64[R / 2, n_tables, n_classes] for the same pairs (isingmc_overlaps_by_class).
+    // track_minimum (DESIGN.md S16): every SLOT keeps the lowest-energy configuration that ever sat in it, seen before every
+    // resampling and after the last sweeps; the result carries the population's minimum over the slots as min_energy, min_state
+    // and min_beta_index (the index of the beta whose sweeps produced it).
+    py::object run_population_annealing(const std::vector<double> &betas, size_t sweeps_per_beta, size_t population, bool return_states,
+                                        bool measure_overlaps, bool track_minimum, const py::object &overlap_classes)
+    {
+        const auto check = [&] {
+            if (betas.empty()) throw py::value_error("betas must hold at least one inverse temperature");
+            for (size_t k = 0; k < betas.size(); k++)
+                if (!std::isfinite(betas[k]) || (k && betas[k] < betas[k - 1])) throw py::value_error("betas must be finite and non-decreasing");
+        };
+        // the whole schedule is enqueued; the host waits once, at its end, and reads the step records
+        const auto run = [&](isingmc_states *s, uint64_t seed, PaLog &log) {
+            const size_t n = betas.size();
+            log.betas = betas;
+            log.sums.resize(n - 1); log.erefs.resize(n - 1); log.distinct.resize(n - 1); log.mean.resize(n - 1);
+            return isingmc_pa_run(s, betas.data(), n, sweeps_per_beta, seed, log.sums.data(), log.erefs.data(), log.distinct.data(), log.mean.data());
+        };
+        return population_annealing(check, run, sweeps_per_beta, population, return_states, measure_overlaps, track_minimum, overlap_classes);
+    }
+
+    // extension: population annealing from beta_start up to beta_end with the temperature steps chosen on the device
+    // from the population itself (isingmc_pa_run_adaptive): the largest step, of at most max_dbeta (None: no cap), at which the
+    // energy histograms of the two temperatures still overlap by target_overlap.  0.85 is the value customary in the literature, a
+    // default and not a measured optimum.  The result is that of run_population_annealing; its `betas` is the schedule that was
+    // taken, which log_z_ratio, mean_energy and distinct_sources are indexed by.  The host waits once per temperature.  ValueError
+    // if max_steps steps do not reach beta_end.
+    py::object run_population_annealing_adaptive(double beta_start, double beta_end, size_t sweeps_per_beta, size_t population, double target_overlap,
+                                                 std::optional<double> max_dbeta, size_t max_steps, bool return_states, bool measure_overlaps,
+                                                 bool track_minimum, const py::object &overlap_classes)
+    {
+        const auto check = [&] {
+            if (!std::isfinite(beta_start) || !std::isfinite(beta_end) || beta_end < beta_start)
+                throw py::value_error("beta_start and beta_end must be finite with beta_start <= beta_end");
+            if (max_steps >= (size_t(1) << 32)) throw py::value_error("max_steps must be below 2^32");
+        };
+        const auto run = [&](isingmc_states *s, uint64_t seed, PaLog &log) {
+            log.betas.resize(max_steps + 1);
+            log.sums.resize(max_steps); log.erefs.resize(max_steps); log.distinct.resize(max_steps); log.mean.resize(max_steps);
+            size_t n = 0;
+            const int rc = isingmc_pa_run_adaptive(s, beta_start, beta_end, sweeps_per_beta, seed, target_overlap,
+                                                   max_dbeta ? *max_dbeta : std::numeric_limits<double>::infinity(), max_steps, log.betas.data(), &n,
+                                                   log.sums.data(), log.erefs.data(), log.distinct.data(), log.mean.data());
+            n = std::max<size_t>(n, 1);
+            log.betas.resize(n);
+            log.sums.resize(n - 1); log.erefs.resize(n - 1); log.distinct.resize(n - 1); log.mean.resize(n - 1);
+            return rc;
+        };
+        return population_annealing(check, run, sweeps_per_beta, population, return_states, measure_overlaps, track_minimum, overlap_classes);
     }
 
     Lattice clone() const { return *this; } // lattice.rs:1038-1040 (the immutable device graph is shared)
@@ -1282,6 +1340,10 @@ PYBIND11_MODULE(_py_monte_carlo, m)
              "edge_move_importance_sampling"_a = py::none(), "replica_range"_a = py::none())
         .def("run_population_annealing", &Lattice::run_population_annealing, "betas"_a, "sweeps_per_beta"_a, "population"_a,
              py::kw_only(), "return_states"_a = true, "measure_overlaps"_a = false, "track_minimum"_a = false,
+             "overlap_classes"_a = py::none())
+        .def("run_population_annealing_adaptive", &Lattice::run_population_annealing_adaptive, "beta_start"_a, "beta_end"_a,
+             "sweeps_per_beta"_a, "population"_a, py::kw_only(), "target_overlap"_a = 0.85, "max_dbeta"_a = py::none(),
+             "max_steps"_a = 10000, "return_states"_a = true, "measure_overlaps"_a = false, "track_minimum"_a = false,
              "overlap_classes"_a = py::none())
         .def("run_monte_carlo_annealing_and_get_minimum", &Lattice::run_monte_carlo_annealing_and_get_minimum, "betas"_a, "timesteps"_a,
              "num_experiments"_a, "every"_a = 1, "only_basic_moves"_a = py::none())
