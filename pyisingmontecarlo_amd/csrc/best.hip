@@ -23,10 +23,10 @@ static size_t best_state_size(const isingmc_states *s) { return s->packed ? s->g
 
 static int best_reset_enqueue(isingmc_states *s)
 {
-    const std::vector<double> inf(s->best_cap, std::numeric_limits<double>::infinity());
-    HIP_TRY(hipMemcpyAsync(s->d_best_e, inf.data(), inf.size() * sizeof(double), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemsetAsync(s->d_best_t, 0, s->best_cap * sizeof(unsigned long long), s->stream));
-    HIP_TRY(hipMemsetAsync(s->d_best_count, 0, sizeof(unsigned long long), s->stream));
+    const std::vector<double> inf(s->best.cap, std::numeric_limits<double>::infinity());
+    HIP_TRY(hipMemcpyAsync(s->best.d_e, inf.data(), inf.size() * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemsetAsync(s->best.d_t, 0, s->best.cap * sizeof(unsigned long long), s->stream));
+    HIP_TRY(hipMemsetAsync(s->best.d_count, 0, sizeof(unsigned long long), s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream)); // (the host vector above)
     return ISINGMC_OK;
 }
@@ -36,22 +36,20 @@ static int best_reset_enqueue(isingmc_states *s)
 static int best_reserve(isingmc_states *s)
 {
     const size_t words = best_state_size(s);
-    if (s->d_best_state && s->best_state_words == words && s->best_cap == s->R) return ISINGMC_OK;
+    if (s->best.d_state && s->best.state_words == words && s->best.cap == s->R) return ISINGMC_OK;
     HIP_TRY(stream_quiesce(s->stream)); // recycled blocks: nothing enqueued may still use the old ones
-    s->d_best_state.reset(); s->d_best_e.reset(); s->d_best_t.reset();
-    s->d_best_energy.reset(); s->d_best_flags.reset(); s->d_best_count.reset();
-    s->best_cap = s->best_state_words = 0;
+    s->best = BestState{}; // (every member: the blocks go back, the sizes are 0)
     // Padding positions and the bits of a packed group this container does not own take whatever the copies bring along: they
     // have no defined value.  The buffer is cleared once, so that isingmc_best_raw_state is deterministic.
-    TRY(dev_alloc(s->d_best_state, words));
-    TRY(dev_alloc(s->d_best_e, s->R));
-    TRY(dev_alloc(s->d_best_t, s->R));
-    TRY(dev_alloc(s->d_best_energy, s->R));
-    TRY(dev_alloc(s->d_best_flags, s->packed ? s->groups : s->R));
-    TRY(dev_alloc(s->d_best_count, 1));
-    HIP_TRY(hipMemsetAsync(s->d_best_state, 0, words * sizeof(uint32_t), s->stream));
-    s->best_state_words = words;
-    s->best_cap = s->R;
+    TRY(dev_alloc(s->best.d_state, words));
+    TRY(dev_alloc(s->best.d_e, s->R));
+    TRY(dev_alloc(s->best.d_t, s->R));
+    TRY(dev_alloc(s->best.d_energy, s->R));
+    TRY(dev_alloc(s->best.d_flags, s->packed ? s->groups : s->R));
+    TRY(dev_alloc(s->best.d_count, 1));
+    HIP_TRY(hipMemsetAsync(s->best.d_state, 0, words * sizeof(uint32_t), s->stream));
+    s->best.state_words = words;
+    s->best.cap = s->R;
     return best_reset_enqueue(s);
 }
 
@@ -80,12 +78,12 @@ int best_from_energies(isingmc_states *s, const double *d_energy)
     if (s->R == 0) return ISINGMC_OK;
     if (s->n_lanes > 1) TRY(lanes_join(s)); // the sweeps before this update may have run on replica lanes
     const isingmc_graph *g = s->g;
-    HIP_TRY(best_launch_decide(s->stream, s->packed, d_energy, uint32_t(s->R), uint32_t(s->pk_bit0), uint32_t(s->groups), s->t, s->d_best_e, s->d_best_t,
-                               s->d_best_flags, s->d_best_count));
+    HIP_TRY(best_launch_decide(s->stream, s->packed, d_energy, uint32_t(s->R), uint32_t(s->pk_bit0), uint32_t(s->groups), s->t, s->best.d_e, s->best.d_t,
+                               s->best.d_flags, s->best.d_count));
     if (s->packed)
-        HIP_TRY(best_launch_keep_bits(s->stream, s->d_state, s->d_best_state, s->d_best_flags, uint32_t(s->R), uint32_t(s->pk_bit0), s->groups, g->pk.n_pos));
+        HIP_TRY(best_launch_keep_bits(s->stream, s->d_state, s->best.d_state, s->best.d_flags, uint32_t(s->R), uint32_t(s->pk_bit0), s->groups, g->pk.n_pos));
     else
-        HIP_TRY(best_launch_keep_rows(s->stream, s->d_state, s->d_best_state, s->d_best_flags, s->R, g->state_words));
+        HIP_TRY(best_launch_keep_rows(s->stream, s->d_state, s->best.d_state, s->best.d_flags, s->R, g->state_words));
     return ISINGMC_OK;
 }
 
@@ -93,8 +91,8 @@ int best_update_enqueue(isingmc_states *s)
 {
     if (s->R == 0) return ISINGMC_OK;
     if (s->n_lanes > 1) TRY(lanes_join(s));
-    TRY(energies_enqueue(s, s->d_best_energy));
-    return best_from_energies(s, s->d_best_energy);
+    TRY(energies_enqueue(s, s->best.d_energy));
+    return best_from_energies(s, s->best.d_energy);
 }
 
 extern "C" int isingmc_best_update(isingmc_states *s)
@@ -112,7 +110,7 @@ extern "C" int isingmc_best_update(isingmc_states *s)
 static int best_ready(isingmc_states *s)
 {
     if (!s) return fail(ISINGMC_ERR_INVALID, "NULL states");
-    if (!s->d_best_state || s->best_cap != s->R)
+    if (!s->best.d_state || s->best.cap != s->R)
         return fail(ISINGMC_ERR_INVALID, "this container keeps no records: switch tracking on (isingmc_states_set_track_best) or call isingmc_best_update first");
     TRY(use_device(s->g->device));
     HIP_TRY(hipStreamSynchronize(s->stream));
@@ -125,10 +123,10 @@ extern "C" int isingmc_best_get(isingmc_states *s, double *energies_out, uint8_t
     TRY(best_ready(s));
     if (states_out && replica_stride_bytes < s->g->nvars) return fail(ISINGMC_ERR_INVALID, "replica stride smaller than nvars");
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the timestep records are read out as they lie");
-    if (energies_out && s->R) HIP_TRY(hipMemcpy(energies_out, s->d_best_e, s->R * sizeof(double), hipMemcpyDeviceToHost));
-    if (timesteps_out && s->R) HIP_TRY(hipMemcpy(timesteps_out, s->d_best_t, s->R * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (improvements_out) HIP_TRY(hipMemcpy(improvements_out, s->d_best_count, sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (states_out) TRY(expand_states(s, s->d_best_state, states_out, replica_stride_bytes));
+    if (energies_out && s->R) HIP_TRY(hipMemcpy(energies_out, s->best.d_e, s->R * sizeof(double), hipMemcpyDeviceToHost));
+    if (timesteps_out && s->R) HIP_TRY(hipMemcpy(timesteps_out, s->best.d_t, s->R * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (improvements_out) HIP_TRY(hipMemcpy(improvements_out, s->best.d_count, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (states_out) TRY(expand_states(s, s->best.d_state, states_out, replica_stride_bytes));
     return ISINGMC_OK;
 }
 
@@ -139,14 +137,14 @@ extern "C" int isingmc_best_raw_state(isingmc_states *s, uint32_t *words_out, si
     if (n_words_out) *n_words_out = n;
     if (!words_out || n == 0) return ISINGMC_OK;
     TRY(best_ready(s));
-    HIP_TRY(hipMemcpy(words_out, s->d_best_state, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(words_out, s->best.d_state, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return ISINGMC_OK;
 }
 
 extern "C" int isingmc_best_reset(isingmc_states *s)
 {
     if (!s) return fail(ISINGMC_ERR_INVALID, "NULL states");
-    if (!s->d_best_state) return ISINGMC_OK; // nothing recorded yet: the records start at +inf anyway
+    if (!s->best.d_state) return ISINGMC_OK; // nothing recorded yet: the records start at +inf anyway
     TRY(use_device(s->g->device));
     return best_reset_enqueue(s);
 }

@@ -24,7 +24,7 @@ extern "C" int isingmc_cluster_series_create(isingmc_states *a, int kind, size_t
     if (kind == ISINGMC_CLUSTER_SERIES_SW) {
         const std::string why = cluster_obstacle(a);
         if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
-        if (a->icm_every) return fail(ISINGMC_ERR_INVALID, "isoenergetic cluster moves are switched on for this container (isingmc_states_set_icm_every): one non-local move at a time");
+        if (a->icm.every) return fail(ISINGMC_ERR_INVALID, "isoenergetic cluster moves are switched on for this container (isingmc_states_set_icm_every): one non-local move at a time");
     } else {
         const std::string why = icm_obstacle(a);
         if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
@@ -79,7 +79,7 @@ extern "C" int isingmc_host_nonlocal_steps(uint64_t t0, size_t timesteps, size_t
 // the period whose steps append rows to S
 static size_t series_every(const isingmc_states *s, const isingmc_cluster_series *S)
 {
-    return S->kind == ISINGMC_CLUSTER_SERIES_SW ? s->cluster_every : s->icm_every;
+    return S->kind == ISINGMC_CLUSTER_SERIES_SW ? s->cl.every : s->icm.every;
 }
 
 int cluster_series_room_or_fail(const isingmc_states *s, size_t timesteps)

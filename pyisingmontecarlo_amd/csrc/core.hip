@@ -172,7 +172,7 @@ StreamPool &stream_pool()
 }
 } // namespace
 
-hipError_t pooled_stream_create(hipStream_t *out)
+static hipError_t pooled_stream_create(hipStream_t *out)
 {
     int dev = 0;
     hipError_t err = hipGetDevice(&dev);
@@ -226,7 +226,7 @@ EventPool &event_pool()
 }
 } // namespace
 
-hipError_t pooled_event_create(hipEvent_t *out, bool disable_timing)
+static hipError_t pooled_event_create(hipEvent_t *out, bool disable_timing)
 {
     int dev = 0;
     if (!dev_cache_off() && hipGetDevice(&dev) == hipSuccess) {
@@ -258,6 +258,31 @@ void pooled_event_destroy(hipEvent_t ev, bool disable_timing)
     (void)hipEventDestroy(ev);
 }
 
+// One helper per kind fills a handle (as dev_alloc fills a block): what `out` held goes back, but only once the new one is there
+int stream_create(PooledStream &out)
+{
+    hipStream_t st = nullptr;
+    HIP_TRY(pooled_stream_create(&st));
+    out = PooledStream(st);
+    return ISINGMC_OK;
+}
+
+int event_create(PooledEvent &out)
+{
+    hipEvent_t ev = nullptr;
+    HIP_TRY(pooled_event_create(&ev, true));
+    out = PooledEvent(ev);
+    return ISINGMC_OK;
+}
+
+int event_create(TimedEvent &out)
+{
+    hipEvent_t ev = nullptr;
+    HIP_TRY(pooled_event_create(&ev, false));
+    out = TimedEvent(ev);
+    return ISINGMC_OK;
+}
+
 int use_device(int device)
 {
     int count = 0;
@@ -274,18 +299,6 @@ int use_device(int device)
     // clear what others left behind so that the hipGetLastError() checks after our launches see only ours
     (void)hipGetLastError();
     return ISINGMC_OK;
-}
-
-bool env_flag(const char *name)
-{
-    const char *e = std::getenv(name);
-    return e && e[0] && e[0] != '0';
-}
-
-int env_int(const char *name, int dflt)
-{
-    const char *e = std::getenv(name);
-    return e && e[0] ? std::atoi(e) : dflt;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -15,7 +15,8 @@
 //   tempering.hip  on-stream parallel tempering, the in-process ladder group (RCCL through dlopen)
 //   population.hip population annealing: the on-stream resampling step (isingmc_pa_*)
 //   debug.hip      shader-clock probe
-// Device and pinned blocks are held in the handles of owned_block.hpp, which free them: no unit frees a block by hand.
+// Device and pinned blocks, pooled streams and events are held in the handles of owned_block.hpp, which hand them back: no unit
+// frees one by hand.  The path / tuning switches of a graph or a container are options.hpp.
 // Every kernel but the probe's is defined in a *_kernels.hip unit of its own and launched through the plain C++ launchers that the
 // headers below declare; none of them defines a kernel.
 #pragma once
@@ -54,6 +55,7 @@
 #include "overlap_class_kernels.hpp"
 #include "overlap_kernels.hpp"
 #include "overlap_series_kernels.hpp"
+#include "options.hpp"
 #include "owned_block.hpp"
 #include "real_types.hpp"
 #include "spread_types.hpp"
@@ -86,107 +88,14 @@ IM_INTERNAL int fail(int code, const std::string &msg); // sets the calling thre
 // it hands a block back (hipFree used to synchronise the device).  Blocks are held in the handles of owned_block.hpp, which free them.
 IM_INTERNAL hipError_t cached_malloc(void **out, size_t bytes);
 IM_INTERNAL hipError_t cached_host_malloc(void **out, size_t bytes);
-IM_INTERNAL hipError_t pooled_stream_create(hipStream_t *out);
 IM_INTERNAL hipError_t stream_quiesce(hipStream_t st); // a query when everything has completed, else a synchronisation
-IM_INTERNAL void pooled_stream_destroy(hipStream_t st);
-IM_INTERNAL hipError_t pooled_event_create(hipEvent_t *out, bool disable_timing);
-IM_INTERNAL void pooled_event_destroy(hipEvent_t ev, bool disable_timing);
+// Pooled streams and events are held in the handles of owned_block.hpp, which hand them back; these fill one (as dev_alloc a block)
+IM_INTERNAL int stream_create(PooledStream &out);
+IM_INTERNAL int event_create(PooledEvent &out); // no timing: ordering between streams
+IM_INTERNAL int event_create(TimedEvent &out);  // with timing: the *_timed entry point
 IM_INTERNAL int use_device(int device);
-IM_INTERNAL bool env_flag(const char *name);
-IM_INTERNAL int env_int(const char *name, int dflt);
 
-// ------------------------------------------------------------------------------------------------
-// Path / tuning switches.  They are read from the environment ONCE, when a graph or a replica container is created, into an
-// options block of that handle; isingmc_states_set_option changes one of them on one container.  Nothing below *_create calls
-// getenv: two containers of one process can run different paths, and a test that sets a variable must do so before it creates
-// the object it wants to steer.  (Measurement / A-B switches and test hooks; none of them changes a result, only which kernel
-// produces it -- except FORCE / DISABLE of a kernel FAMILY, which select another spec: DESIGN.md section 2.)
-// ------------------------------------------------------------------------------------------------
-// an option's name as the table below holds it: lower case, without the ISINGMC_ prefix
-inline std::string option_bare_name(const std::string &name)
-{
-    std::string n;
-    for (char c : name) n += char(std::tolower(static_cast<unsigned char>(c)));
-    return n.rfind("isingmc_", 0) == 0 ? n.substr(8) : n;
-}
-
-struct Options {
-    int force_real = 0, disable_real = 0, force_packed = 0, disable_packed = 0; // kernel family (decided at creation)
-    int disable_packed_uniform = 0, disable_resident = 0;
-    int strip = -1, strip_nw = 4, strip_max_wg = -1, strip_test_fail_once = 0; // persistent strip kernel: -1 auto / 0 off / 1 force
-    int streams = 0, pk_streams = 0;                                            // replica lanes: 0 = the measured rule
-    int sweep_iters = 0, debug_sweep_lds = 0;
-    int resident_spread = 1, resident_lpq = 0, gen_stage = -1;
-    int gen_rb = 0; // replicas per thread of the streaming CSR kernel: 0 = the rule of launch_gen_timestep, 1 / 2 / 4 / 8 forces
-    int sample_slab_bytes = 64 << 20, pt_in_kernel = 1, real_target_wgs = 3072;
-    int real_measure_wgs = 0; // workgroups the real-coupling measurement shares among its groups: 0 = the occupancy figure (measure_enqueue)
-    int cluster_workspace_bytes = 1 << 30; // labels, cluster sizes and bond planes of one batch of replicas
-    int moments_planes = 8;               // time planes of the per-replica moment sums: a flush every 2^K - 1 samples
-    long long moments_bytes = 4ll << 30;   // the most device memory the moment sums of one container may take (64 bits: beyond an int)
-    long long overlap_series_bytes = 1ll << 30; // the most device memory the log of one overlap series may take
-    long long observable_series_bytes = 1ll << 30; // ... and the log of one observable series
-    long long cluster_series_bytes = 1ll << 30;    // ... and the log of one cluster series
-    // Rounds of the sweeps' Philox calls, 10 or 7: the one switch here that selects another trajectory.  Written
-    // only through philox_rounds_set (isingmc.hip), which checks the value and the container; read wherever a call is planned
-    int philox_rounds = 10;
-
-    static Options from_env()
-    {
-        Options o;
-        o.force_real = env_flag("ISINGMC_FORCE_REAL");
-        o.disable_real = env_flag("ISINGMC_DISABLE_REAL");
-        o.force_packed = env_flag("ISINGMC_FORCE_PACKED");
-        o.disable_packed = env_flag("ISINGMC_DISABLE_PACKED");
-        o.disable_packed_uniform = env_flag("ISINGMC_DISABLE_PACKED_UNIFORM");
-        o.disable_resident = env_flag("ISINGMC_DISABLE_RESIDENT");
-        o.strip = env_int("ISINGMC_STRIP", -1);
-        o.strip_nw = env_int("ISINGMC_STRIP_NW", 4);
-        o.strip_max_wg = env_int("ISINGMC_STRIP_MAX_WG", -1);
-        o.strip_test_fail_once = env_flag("ISINGMC_STRIP_TEST_FAIL_ONCE");
-        o.streams = env_int("ISINGMC_STREAMS", 0);
-        o.pk_streams = env_int("ISINGMC_PK_STREAMS", 0);
-        o.sweep_iters = env_int("ISINGMC_SWEEP_ITERS", 0);
-        o.debug_sweep_lds = env_int("ISINGMC_DEBUG_SWEEP_LDS", 0);
-        o.resident_spread = env_int("ISINGMC_RESIDENT_SPREAD", 1);
-        o.resident_lpq = env_int("ISINGMC_RESIDENT_LPQ", 0);
-        o.gen_stage = env_int("ISINGMC_GEN_STAGE", -1);
-        o.gen_rb = env_int("ISINGMC_GEN_RB_FORCE", 0);
-        o.sample_slab_bytes = std::max(1, env_int("ISINGMC_SAMPLE_SLAB_BYTES", 64 << 20));
-        o.pt_in_kernel = env_int("ISINGMC_PT_IN_KERNEL", 1);
-        o.real_target_wgs = std::max(256, env_int("ISINGMC_REAL_TARGET_WGS", 3072));
-        o.real_measure_wgs = env_int("ISINGMC_REAL_MEASURE_WGS", 0);
-        o.cluster_workspace_bytes = std::max(1, env_int("ISINGMC_CLUSTER_WORKSPACE_BYTES", 1 << 30));
-        o.moments_planes = env_int("ISINGMC_MOMENTS_PLANES", o.moments_planes);
-        if (const char *v = std::getenv("ISINGMC_MOMENTS_BYTES")) o.moments_bytes = std::atoll(v);
-        if (const char *v = std::getenv("ISINGMC_OVERLAP_SERIES_BYTES")) o.overlap_series_bytes = std::atoll(v);
-        if (const char *v = std::getenv("ISINGMC_OBSERVABLE_SERIES_BYTES")) o.observable_series_bytes = std::atoll(v);
-        if (const char *v = std::getenv("ISINGMC_CLUSTER_SERIES_BYTES")) o.cluster_series_bytes = std::atoll(v);
-        o.philox_rounds = env_int("ISINGMC_PHILOX_ROUNDS", 10);
-        return o;
-    }
-
-    // name: the environment variable's name without the ISINGMC_ prefix, lower or upper case
-    bool set(const std::string &name_in, long value)
-    {
-        const std::string n = option_bare_name(name_in);
-        if (n == "moments_bytes") { moments_bytes = value; return true; }
-        if (n == "overlap_series_bytes") { overlap_series_bytes = value; return true; }
-        if (n == "observable_series_bytes") { observable_series_bytes = value; return true; }
-        if (n == "cluster_series_bytes") { cluster_series_bytes = value; return true; }
-        const std::pair<const char *, int *> table[] = {
-            {"force_real", &force_real}, {"disable_real", &disable_real}, {"force_packed", &force_packed}, {"disable_packed", &disable_packed},
-            {"disable_packed_uniform", &disable_packed_uniform}, {"disable_resident", &disable_resident}, {"strip", &strip},
-            {"strip_nw", &strip_nw}, {"strip_max_wg", &strip_max_wg}, {"strip_test_fail_once", &strip_test_fail_once},
-            {"streams", &streams}, {"pk_streams", &pk_streams}, {"sweep_iters", &sweep_iters}, {"debug_sweep_lds", &debug_sweep_lds},
-            {"resident_spread", &resident_spread}, {"resident_lpq", &resident_lpq}, {"gen_stage", &gen_stage}, {"gen_rb", &gen_rb},
-            {"sample_slab_bytes", &sample_slab_bytes}, {"pt_in_kernel", &pt_in_kernel}, {"real_target_wgs", &real_target_wgs},
-            {"real_measure_wgs", &real_measure_wgs},
-            {"cluster_workspace_bytes", &cluster_workspace_bytes}, {"moments_planes", &moments_planes}};
-        for (const auto &e : table)
-            if (n == e.first) { *e.second = int(value); return true; }
-        return false;
-    }
-};
+// ---- options.hpp: struct Options, the path / tuning switches of a graph or a container, and the environment helpers ----------
 
 struct isingmc_graph {
     int device = 0;
@@ -263,6 +172,134 @@ struct StepPreset {
 enum Recorder { REC_BEST, REC_MOMENTS, REC_OVERLAPS, REC_OBSERVABLES, REC_CLUSTERS, REC_COUNT };
 struct SeriesLog;
 
+// The state of a container that ONE unit owns, a struct per unit; isingmc_states holds one of each.  Other units read them (a
+// refusal, a join before a launch); the owner alone allocates, grows and resets.
+
+// ---- isingmc.hip (the persistent strip kernel's host side, strip_kernels.hpp) -------------------------------------------------
+struct StripState {
+    DevBlock<unsigned long long> d_halo; // halo granules
+    size_t halo_cap = 0;                 // granules allocated
+    DevBlock<uint32_t> d_err;            // error word
+    uint32_t epoch = 0;                  // tag epoch
+    DevBlock<unsigned long long> d_pt_mail, d_pt_round_counts; // in-kernel exchange rounds (StripLadder)
+    DevBlock<uint32_t> d_pt_perm2;
+    DevBlock<unsigned long long> d_fin; // [cap] final-measurement counters of the strip kernel (zero between launches)
+    bool test_failed = false; // ISINGMC_STRIP_TEST_FAIL_ONCE has fired for this object
+    bool disabled = false;    // a strip launch of this object timed out once: the per-colour launches serve it from then on
+    DevBlock<uint32_t> d_snapshot; // the planes a synchronous call started from (restored when a strip launch gives up)
+    size_t snapshot_cap = 0;
+    bool guard = false; // inside with_strip_retry: a strip launch is checked before an update may keep what it left
+};
+
+// ---- sampling.hip (isingmc_run_sampling: two slabs of samples in flight) ------------------------------------------------------
+struct SamplingState {
+    PooledStream copy_stream;
+    PooledEvent ready[2], copied[2];
+    DevBlock<uint32_t> d_samples[2];
+    PinnedBlock<uint32_t> h_samples[2];
+    DevBlock<unsigned long long> d_counts[2];
+    PinnedBlock<unsigned long long> h_counts[2];
+    DevBlock<double> d_e[2];
+    PinnedBlock<double> h_e[2];
+    DevBlock<long long> d_m;
+    size_t cap_words = 0, cap_counts = 0, cap_e = 0;
+};
+
+// ---- tempering.hip (on-stream parallel tempering, isingmc_pt_*): the host side of the ladder; PtDev is what the kernels read ----
+struct TemperingState {
+    bool attached = false;
+    DevBlock<double> d_ladder, d_local, d_all;
+    DevBlock<uint64_t> d_ladder_thr;
+    DevBlock<uint32_t> d_perm;
+    DevBlock<unsigned long long> d_counters;
+    size_t per = 0, world = 1;
+    std::vector<double> ladder_betas; // host copy of d_ladder (two ladders are compared without a device read)
+    DevBlock<unsigned long long> d_stats; // ladder statistics: the block of PtStats, from the first switch-on to the detach
+    bool stats_on = false;                // the container's pt.stats == d_stats while on, nullptr while off
+    uint64_t in_kernel_rounds = 0;        // rounds counted inside persistent strip launches (host count: which path a run took)
+};
+
+// ---- nonlocal.hip -------------------------------------------------------------------------------------------------------------
+// Swendsen-Wang cluster steps (cluster_kernels.hpp): timestep t is one when every > 0 and t % every == every - 1
+struct ClusterState {
+    size_t every = 0;
+    DevBlock<uint32_t> d_stats; // [stats_cap][2]: clusters, largest cluster of the last cluster step (packed: per counter slot)
+    size_t stats_cap = 0;
+    bool have_stats = false;
+};
+// isoenergetic cluster moves between the replicas (2 p, 2 p + 1): timestep t is one when every > 0 and
+// t % every == every - 1; never on together with the cluster steps
+struct IcmState {
+    size_t every = 0;
+    DevBlock<uint32_t> d_stats; // [stats_cap][2] clusters, largest cluster, then [stats_cap] q = -1 sites: the last ICM step of every pair
+    size_t stats_cap = 0;
+    bool have_stats = false;
+};
+// isoenergetic cluster moves between this container and another one (isingmc_icm_between): everything here
+// belongs to the FIRST container of the call and stays with it, so that a call only enqueues
+struct IcmBetweenState {
+    DevBlock<uint32_t> d_work; // labelling workspace of `batch` pairs (cluster_words_per_replica each); packed containers
+    size_t batch = 0;          // (DESIGN.md S13): of `batch` pair BLOCKS (pk_between_words_per_block each)
+    DevBlock<uint32_t> d_inv;  // packed containers: (local group, bit) -> pair of the call, this container's groups first,
+    size_t inv_cap = 0;        // then the other one's (words)
+    DevBlock<uint32_t> d_slots; // [2][cap] slot tables of the host-table form
+    DevBlock<uint32_t> d_stats; // [cap][2] clusters, largest cluster, then [cap] q = -1 sites: the last call
+    size_t cap = 0, pairs = 0;
+    bool have_stats = false;
+    PooledEvent ev[2]; // the other container's stream has arrived / this container's launches are enqueued
+};
+
+// ---- population.hip -----------------------------------------------------------------------------------------------------------
+// population annealing (isingmc_pa_*): everything here is allocated by the first resampling and stays
+struct PaState {
+    DevBlock<uint32_t> d_state; // the second state buffer the gathers write into: as large as the container's d_state (state_words words)
+    size_t state_words = 0;
+    size_t cap = 0;              // replicas the tables below hold
+    DevBlock<double> d_energy;          // [cap]
+    DevBlock<unsigned long long> d_cum; // [cap] weights, then their inclusive prefix sums; pa_scan_blocks(cap) block sums follow
+    DevBlock<uint32_t> d_src;           // [cap] source table of the last isingmc_pa_resample
+    DevBlock<uint32_t> d_user_src;      // [cap] the caller's table of the last isingmc_pa_apply_sources
+    DevBlock<uint32_t> d_family, d_family2; // [cap] family of every slot, and the buffer its gather writes into
+    DevBlock<PaRecord> d_record;
+    bool have_record = false;    // an isingmc_pa_resample has been enqueued
+    bool families_set = false;   // d_family holds the table (else: the identity)
+};
+// the step chooser (isingmc_pa_choose_step): blocks of its own, so that a choice touches nothing a resampling keeps
+struct PaChooseState {
+    DevBlock<double> d_energy;  // [cap]
+    size_t cap = 0;
+    DevBlock<PaChoose> d_choose;
+};
+
+// ---- best.hip -----------------------------------------------------------------------------------------------------------------
+// each replica's lowest-energy configuration (isingmc_best_*): allocated when tracking is switched on (or by the
+// first isingmc_best_update) for the replicas the container holds then, and kept
+struct BestState {
+    DevBlock<uint32_t> d_state; // as large as the container's d_state, same layout; padding positions and unowned bits of a packed
+    size_t state_words = 0;      // container hold no defined value (cleared once, so that the raw read-out is deterministic)
+    size_t cap = 0;              // replicas the records below hold
+    DevBlock<double> d_e;                // [cap] records, +inf before the first update
+    DevBlock<unsigned long long> d_t;    // [cap] the timestep each record was set at
+    DevBlock<double> d_energy;           // [cap] the energies an update measures
+    DevBlock<uint32_t> d_flags;          // a flag per replica (checkerboard) / an improvement mask per group (packed)
+    DevBlock<unsigned long long> d_count; // improvements so far
+};
+
+// ---- moments.hip --------------------------------------------------------------------------------------------------------------
+// per-site and per-bond sums over the samples of a run (isingmc_moments_*): allocated when accumulation is
+// switched on (or by the first isingmc_moments_accumulate) for the replicas the container holds then, and kept
+struct MomentsState {
+    unsigned flags = 0;      // ISINGMC_MOMENTS_* of the sums held
+    uint64_t n = 0;          // samples in the sums
+    bool have = false;       // the blocks below are allocated, for R replicas
+    size_t R = 0;
+    DevBlock<unsigned long long> d_site, d_bond; // summed mode: set-bit counts in the layouts of moments_kernels.hpp
+    DevBlock<uint2> d_edges;                      // packed containers with bond sums: the two positions of every edge entry
+    DevBlock<uint32_t> d_planes, d_totals;        // per-replica mode: k time planes of the state's shape, 32-bit totals
+    int k = 0;
+    uint32_t pending = 0;    // samples in the time planes since the last flush (< 2^k)
+};
+
 struct isingmc_states {
     isingmc_graph *g = nullptr;
     Options opt; // the environment's switches when the container was created (isingmc_states_set_option changes one)
@@ -270,25 +307,27 @@ struct isingmc_states {
     DevBlock<uint32_t> d_state;
     DevBlock<uint2> d_keys;
     uint64_t t = 0; // absolute timestep = Philox counter
-    hipStream_t stream = nullptr;
-    std::vector<hipStream_t> lanes; // sweep launches of disjoint replica blocks alternate over these (see run_steps)
-    std::vector<hipEvent_t> lane_events;
-    hipEvent_t fork_event = nullptr;
+    PooledStream stream;
+    std::vector<PooledStream> lanes; // sweep launches of disjoint replica blocks alternate over these (see run_steps)
+    std::vector<PooledEvent> lane_events;
+    PooledEvent fork_event;
     size_t n_lanes = 1; // lanes in use by the current run_steps call
     // workgroups of lat_sweep_loop_kernel<uniform J / +-J> the device holds at once with sweep_resident_lds bytes of LDS each
     // (occupancy query x CUs, asked once; -1 = not asked yet)
     int sweep_resident_wgs[2] = {-1, -1};
     unsigned sweep_resident_lds = 0;
     int sweep_resident_rounds = 10; // ... and of which round count (Options::philox_rounds)
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    TimedEvent ev0, ev1;
     bool has_betas = false;
     std::vector<double> betas;
     DevBlock<LatThr> d_thr;
     DevBlock<LatThrMC> d_thr_mc; // per-replica thresholds of the multi-class kernels (has_betas on a field / open lattice)
     DevBlock<double> d_beta;
+    const StepPreset *step_preset = nullptr; // set around a run_steps call by isingmc_pa_run: the tables of its beta are on the device
     // measurement scratch
     DevBlock<unsigned long long> d_meas; // lattice: [R][2]
     bool meas_zero = false;               // d_meas is known to be all zero (left so by the tempering measurement)
+    bool meas_fresh = false; // the tempering send buffer holds the energies of the CURRENT configurations (written by the last strip launch)
     DevBlock<double> d_pe, d_oe;
     DevBlock<long long> d_pm, d_om;
     uint32_t n_partials = 0;
@@ -307,102 +346,6 @@ struct isingmc_states {
     DevBlock<RjBeta> d_rj_betas; // per-replica acceptance scales [32 groups] (has_betas)
     DevBlock<unsigned long long> d_pk_slot_thr; // on-stream tempering on the bit-sliced packed path: T_m per slot [32 groups][PK_MAX_DEG]
     size_t n_total = 0, first = 0; // this container is the shard [first, first + R) of n_total experiments
-    // persistent strip kernel (strip_kernels.hpp): halo granules, error word, tag epoch
-    DevBlock<unsigned long long> d_halo;
-    size_t halo_cap = 0; // granules allocated
-    DevBlock<uint32_t> d_strip_err;
-    uint32_t strip_epoch = 0;
-    DevBlock<unsigned long long> d_pt_mail, d_pt_round_counts; // in-kernel exchange rounds (StripLadder)
-    DevBlock<uint32_t> d_pt_perm2;
-    DevBlock<unsigned long long> d_strip_fin; // [cap] final-measurement counters of the strip kernel (zero between launches)
-    bool strip_test_failed = false; // ISINGMC_STRIP_TEST_FAIL_ONCE has fired for this object
-    bool strip_disabled = false;    // a strip launch of this object timed out once: the per-colour launches serve it from then on
-    DevBlock<uint32_t> d_snapshot; // the planes a synchronous call started from (restored when a strip launch gives up)
-    size_t snapshot_cap = 0;
-    bool meas_fresh = false; // the tempering send buffer holds the energies of the CURRENT configurations (written by the last strip launch)
-    // sampling pipeline (isingmc_run_sampling): two slabs of samples in flight
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t sample_ready[2] = {nullptr, nullptr}, sample_copied[2] = {nullptr, nullptr};
-    DevBlock<uint32_t> d_samples[2];
-    PinnedBlock<uint32_t> h_samples[2];
-    DevBlock<unsigned long long> d_sample_counts[2];
-    PinnedBlock<unsigned long long> h_counts[2];
-    DevBlock<double> d_sample_e[2];
-    PinnedBlock<double> h_e[2];
-    DevBlock<long long> d_sample_m;
-    size_t sample_cap_words = 0, sample_cap_counts = 0, sample_cap_e = 0;
-    // on-stream parallel tempering (isingmc_pt_*)
-    bool pt_attached = false;
-    PtDev pt{};
-    DevBlock<double> d_pt_ladder, d_pt_local, d_pt_all;
-    DevBlock<uint64_t> d_pt_ladder_thr;
-    DevBlock<uint32_t> d_pt_perm;
-    DevBlock<unsigned long long> d_pt_counters;
-    size_t pt_per = 0, pt_world = 1;
-    std::vector<double> ladder_betas; // host copy of d_pt_ladder (two ladders are compared without a device read)
-    DevBlock<unsigned long long> d_pt_stats; // ladder statistics: the block of PtStats, from the first switch-on to the detach
-    bool pt_stats_on = false;                // s->pt.stats == d_pt_stats while on, nullptr while off
-    uint64_t pt_in_kernel_rounds = 0;        // rounds counted inside persistent strip launches (host count: which path a run took)
-    // Swendsen-Wang cluster steps (cluster_kernels.hpp): timestep t is one when cluster_every > 0 and t % cluster_every == cluster_every - 1
-    size_t cluster_every = 0;
-    DevBlock<uint32_t> d_cl_stats; // [cl_stats_cap][2]: clusters, largest cluster of the last cluster step (packed: per counter slot)
-    size_t cl_stats_cap = 0;
-    bool cl_have_stats = false;
-    // isoenergetic cluster moves between the replicas (2 p, 2 p + 1): timestep t is one when icm_every > 0 and
-    // t % icm_every == icm_every - 1; never on together with cluster_every
-    size_t icm_every = 0;
-    DevBlock<uint32_t> d_icm_stats; // [icm_stats_cap][2] clusters, largest cluster, then [icm_stats_cap] q = -1 sites: the last ICM step of every pair
-    size_t icm_stats_cap = 0;
-    bool icm_have_stats = false;
-    // isoenergetic cluster moves between this container and another one (isingmc_icm_between): everything below
-    // belongs to the FIRST container of the call and stays with it, so that a call only enqueues
-    DevBlock<uint32_t> d_icmb_work; // labelling workspace of icmb_batch pairs (cluster_words_per_replica each); packed containers
-    size_t icmb_batch = 0;            // (DESIGN.md S13): of icmb_batch pair BLOCKS (pk_between_words_per_block each)
-    DevBlock<uint32_t> d_icmb_inv;  // packed containers: (local group, bit) -> pair of the call, this container's groups first,
-    size_t icmb_inv_cap = 0;          // then the other one's (words)
-    DevBlock<uint32_t> d_icmb_slots; // [2][icmb_cap] slot tables of the host-table form
-    DevBlock<uint32_t> d_icmb_stats; // [icmb_cap][2] clusters, largest cluster, then [icmb_cap] q = -1 sites: the last call
-    size_t icmb_cap = 0, icmb_pairs = 0;
-    bool icmb_have_stats = false;
-    hipEvent_t icmb_ev[2] = {nullptr, nullptr}; // the other container's stream has arrived / this container's launches are enqueued
-    // population annealing (isingmc_pa_*): everything below is allocated by the first resampling and stays
-    DevBlock<uint32_t> d_pa_state; // the second state buffer the gathers write into: as large as d_state (pa_state_words words)
-    size_t pa_state_words = 0;
-    size_t pa_cap = 0;              // replicas the tables below hold
-    DevBlock<double> d_pa_energy;          // [pa_cap]
-    DevBlock<unsigned long long> d_pa_cum; // [pa_cap] weights, then their inclusive prefix sums; pa_scan_blocks(pa_cap) block sums follow
-    DevBlock<uint32_t> d_pa_src;           // [pa_cap] source table of the last isingmc_pa_resample
-    DevBlock<uint32_t> d_pa_user_src;      // [pa_cap] the caller's table of the last isingmc_pa_apply_sources
-    const StepPreset *step_preset = nullptr; // set around a run_steps call by isingmc_pa_run: the tables of its beta are on the device
-    DevBlock<uint32_t> d_pa_family, d_pa_family2; // [pa_cap] family of every slot, and the buffer its gather writes into
-    DevBlock<PaRecord> d_pa_record;
-    bool pa_have_record = false;    // an isingmc_pa_resample has been enqueued
-    bool pa_families_set = false;   // d_pa_family holds the table (else: the identity)
-    // the step chooser (isingmc_pa_choose_step): blocks of its own, so that a choice touches nothing a resampling keeps
-    DevBlock<double> d_pac_energy;  // [pac_cap]
-    size_t pac_cap = 0;
-    DevBlock<PaChoose> d_pac;
-    // each replica's lowest-energy configuration (isingmc_best_*): allocated when tracking is switched on (or by the
-    // first isingmc_best_update) for the replicas the container holds then, and kept
-    DevBlock<uint32_t> d_best_state; // as large as d_state, same layout; padding positions and unowned bits of a packed container
-    size_t best_state_words = 0;      // hold no defined value (cleared once, so that the raw read-out is deterministic)
-    size_t best_cap = 0;              // replicas the records below hold
-    DevBlock<double> d_best_e;                // [best_cap] records, +inf before the first update
-    DevBlock<unsigned long long> d_best_t;    // [best_cap] the timestep each record was set at
-    DevBlock<double> d_best_energy;           // [best_cap] the energies an update measures
-    DevBlock<uint32_t> d_best_flags;          // a flag per replica (checkerboard) / an improvement mask per group (packed)
-    DevBlock<unsigned long long> d_best_count; // improvements so far
-    // per-site and per-bond sums over the samples of a run (isingmc_moments_*): allocated when accumulation is
-    // switched on (or by the first isingmc_moments_accumulate) for the replicas the container holds then, and kept
-    unsigned mom_flags = 0;      // ISINGMC_MOMENTS_* of the sums held
-    uint64_t mom_n = 0;          // samples in the sums
-    bool mom_have = false;       // the blocks below are allocated, for mom_R replicas
-    size_t mom_R = 0;
-    DevBlock<unsigned long long> d_mom_site, d_mom_bond; // summed mode: set-bit counts in the layouts of moments_kernels.hpp
-    DevBlock<uint2> d_mom_edges;                          // packed containers with bond sums: the two positions of every edge entry
-    DevBlock<uint32_t> d_mom_planes, d_mom_totals;        // per-replica mode: mom_k time planes of the state's shape, 32-bit totals
-    int mom_k = 0;
-    uint32_t mom_pending = 0;    // samples in the time planes since the last flush (< 2^mom_k)
     // the sample points of the periodic recorders.  REC_BEST: an update follows every timestep after which t % every == 0 (t0 stays
     // 0).  REC_OVERLAPS / REC_OBSERVABLES: a row of series[...], the one series of its kind that records on a period.
     // REC_CLUSTERS: series[...] is the container's one live cluster series (S24)
@@ -410,29 +353,29 @@ struct isingmc_states {
     SeriesLog *series[REC_COUNT] = {};
     size_t osr_by_rung_live = 0; // live overlap series that read this container's ladder permutation on the device: no isingmc_pt_detach
     size_t obs_by_rung_live = 0; // ... and live observable series that do
-    bool strip_guard = false; // inside with_strip_retry: a strip launch is checked before an update may keep what it left
+    // what one unit owns (the structs above)
+    StripState strip;
+    SamplingState sampling;
+    PtDev pt{};
+    TemperingState tempering;
+    ClusterState cl;
+    IcmState icm;
+    IcmBetweenState icmb;
+    PaState pa;
+    PaChooseState pac;
+    BestState best;
+    MomentsState mom;
 
+    // The body runs before any member goes: with the device current, nothing of this object may still be running when the
+    // members' blocks, streams and events go back to their caches, where the next request may pick them up at once (hipFree used
+    // to wait for the whole device).  The handles release; nothing is released by hand.
     ~isingmc_states()
     {
         if (!g) return;
         (void)hipSetDevice(g->device);
-        // the members' blocks go back to the cache after this body, where the next request may pick them up at once: nothing of
-        // this object may still be running (hipFree used to wait for the whole device)
         if (stream) (void)stream_quiesce(stream);
-        for (auto st : lanes) (void)stream_quiesce(st);
-        if (copy_stream) (void)stream_quiesce(copy_stream);
-        for (auto ev : icmb_ev) pooled_event_destroy(ev, true);
-        for (int b = 0; b < 2; b++) {
-            pooled_event_destroy(sample_ready[b], true);
-            pooled_event_destroy(sample_copied[b], true);
-        }
-        pooled_stream_destroy(copy_stream);
-        for (auto st : lanes) pooled_stream_destroy(st);
-        for (auto ev : lane_events) pooled_event_destroy(ev, true);
-        pooled_event_destroy(fork_event, true);
-        pooled_event_destroy(ev0, false);
-        pooled_event_destroy(ev1, false);
-        pooled_stream_destroy(stream);
+        for (hipStream_t st : lanes) (void)stream_quiesce(st);
+        if (sampling.copy_stream) (void)stream_quiesce(sampling.copy_stream);
     }
 };
 
@@ -484,7 +427,7 @@ static int read_back(isingmc_states *s, std::vector<T> &h, const T *d, size_t n)
 }
 
 // `waiter` goes on behind what `ahead` holds so far.  ev: an event of the caller's -- which one it owns is part of its lifetime
-// rules (a container's icmb_ev for the between move and the synchronising overlap calls, a series' own for its records)
+// rules (a container's icmb.ev for the between move and the synchronising overlap calls, a series' own for its records)
 static inline int stream_wait_for(hipStream_t waiter, hipStream_t ahead, hipEvent_t ev)
 {
     HIP_TRY(hipEventRecord(ev, ahead));
@@ -760,9 +703,9 @@ static int with_strip_retry(isingmc_states *s, bool may_strip, F &&call)
     TRY(use_device(s->g->device));
     const uint64_t t0 = s->t;
     TRY(snapshot_take(s));
-    s->strip_guard = true;
+    s->strip.guard = true;
     const int rc = call();
-    s->strip_guard = false;
+    s->strip.guard = false;
     if (rc != STRIP_TIMED_OUT) return rc;
     TRY(snapshot_restore(s));
     recorders_replay_since(s, t0); // (the repeat skips the samples already in the sums and the rows already in the two series,

@@ -58,8 +58,8 @@ static int reserve(isingmc_states *s, size_t cap)
     // enqueue-only calls (isingmc_pt_*, the sampling loop) may still be running on the engine's non-blocking stream, which the
     // null-stream copies below are NOT ordered against; and the old blocks go back to the cache at the end
     HIP_TRY(stream_quiesce(s->stream));
-    for (auto st : s->lanes) HIP_TRY(stream_quiesce(st));
-    if (s->copy_stream) HIP_TRY(stream_quiesce(s->copy_stream));
+    for (hipStream_t st : s->lanes) HIP_TRY(stream_quiesce(st));
+    if (s->sampling.copy_stream) HIP_TRY(stream_quiesce(s->sampling.copy_stream));
     if (s->R) {
         HIP_TRY(hipMemcpy(d_state, s->d_state, s->R * g->state_words * sizeof(uint32_t), hipMemcpyDeviceToDevice));
         HIP_TRY(hipMemcpy(d_keys, s->d_keys, s->R * sizeof(uint2), hipMemcpyDeviceToDevice));
@@ -69,7 +69,7 @@ static int reserve(isingmc_states *s, size_t cap)
     s->d_keys = std::move(d_keys);
     s->d_thr.reset(); s->d_beta.reset(); s->d_meas.reset(); // the old sizes go before the new ones come
     s->d_pe.reset(); s->d_oe.reset(); s->d_pm.reset(); s->d_om.reset();
-    s->d_strip_fin.reset(); // [cap] too: launch_strip allocates it again
+    s->strip.d_fin.reset(); // [cap] too: launch_strip allocates it again
     TRY(dev_alloc(s->d_thr, cap));
     TRY(dev_alloc(s->d_beta, cap));
     if (g->kind == ISINGMC_KIND_LATTICE2D) {
@@ -117,9 +117,9 @@ extern "C" int isingmc_states_create_range(isingmc_graph *g, size_t n_total, con
     TRY(use_device(g->device));
     auto s = std::make_unique<isingmc_states>();
     s->g = g;
-    HIP_TRY(pooled_stream_create(&s->stream));
-    HIP_TRY(pooled_event_create(&s->ev0, false));
-    HIP_TRY(pooled_event_create(&s->ev1, false));
+    TRY(stream_create(s->stream));
+    TRY(event_create(s->ev0));
+    TRY(event_create(s->ev1));
     TRY(lanes_reserve(s.get(), 2)); // created up front: the first multi-lane run must not pay for stream creation
     s->n_total = n_total;
     s->first = first;
@@ -272,7 +272,7 @@ int set_betas(isingmc_states *s, const double *beta_per_replica, bool all_equal)
     }
     for (size_t r = 0; r < s->R; r++)
         if (!std::isfinite(beta_per_replica[r])) return fail(ISINGMC_ERR_INVALID, "beta must be finite");
-    if (s->icm_every && icm_unequal_pair_betas(s, beta_per_replica))
+    if (s->icm.every && icm_unequal_pair_betas(s, beta_per_replica))
         return fail(ISINGMC_ERR_INVALID, "isoenergetic cluster moves are switched on: the two replicas of every pair (2 p, 2 p + 1) need equal betas");
     TRY(use_device(s->g->device));
     if (!all_equal) { // one beta R times is as good as a uniform beta: any cut of a group is fine then
@@ -695,14 +695,14 @@ static int launch_lat_sweep(isingmc_states *s, uint32_t colour, const LatThr &th
 static int lanes_reserve(isingmc_states *s, size_t n)
 {
     while (s->lanes.size() < n) {
-        hipStream_t st;
-        hipEvent_t ev;
-        HIP_TRY(pooled_stream_create(&st));
-        HIP_TRY(pooled_event_create(&ev, true));
-        s->lanes.push_back(st);
-        s->lane_events.push_back(ev);
+        PooledStream st;
+        PooledEvent ev;
+        TRY(stream_create(st));
+        TRY(event_create(ev));
+        s->lanes.push_back(std::move(st));
+        s->lane_events.push_back(std::move(ev));
     }
-    if (!s->fork_event) HIP_TRY(pooled_event_create(&s->fork_event, true));
+    if (!s->fork_event) TRY(event_create(s->fork_event));
     return ISINGMC_OK;
 }
 
@@ -915,7 +915,7 @@ StripPlan strip_plan(const isingmc_states *s, size_t timesteps, bool ladder)
     StripPlan P;
     const isingmc_graph *g = s->g;
     const int mode = s->opt.strip;
-    if (mode == 0 || s->strip_disabled || g->kind != ISINGMC_KIND_LATTICE2D || !g->vec || timesteps < 2) return P;
+    if (mode == 0 || s->strip.disabled || g->kind != ISINGMC_KIND_LATTICE2D || !g->vec || timesteps < 2) return P;
     const uint32_t qpr = g->geom.wpr / 4;
     if ((qpr & (qpr - 1)) != 0 || qpr > 32) return P; // power of two, at least two rows per wave
     P.nw = s->opt.strip_nw == 1 ? 1 : 4; // measured on 1024^2 x 64 (round 4, with wave priorities): 8.4 (4) / 8.6 (1) us per timestep; with exchange rounds 10.4 (4) / 12.0 (1)
@@ -955,38 +955,38 @@ int launch_strip(isingmc_states *s, const StripPlan &P, size_t r0, size_t n, siz
 {
     const isingmc_graph *g = s->g;
     const size_t granules = s->cap * size_t(P.a.n_strips) * 4 * g->geom.wpr;
-    if (s->halo_cap < granules) {
-        TRY(dev_regrow(s->stream, s->d_halo, &s->halo_cap, granules, granules));
-        HIP_TRY(hipMemsetAsync(s->d_halo, 0, granules * sizeof(unsigned long long), s->stream));
-        s->strip_epoch = 0;
+    if (s->strip.halo_cap < granules) {
+        TRY(dev_regrow(s->stream, s->strip.d_halo, &s->strip.halo_cap, granules, granules));
+        HIP_TRY(hipMemsetAsync(s->strip.d_halo, 0, granules * sizeof(unsigned long long), s->stream));
+        s->strip.epoch = 0;
     }
-    if (!s->d_strip_err) {
-        TRY(dev_alloc(s->d_strip_err, 4));
-        HIP_TRY(hipMemsetAsync(s->d_strip_err, 0, 4 * sizeof(uint32_t), s->stream));
+    if (!s->strip.d_err) {
+        TRY(dev_alloc(s->strip.d_err, 4));
+        HIP_TRY(hipMemsetAsync(s->strip.d_err, 0, 4 * sizeof(uint32_t), s->stream));
     }
     StripFinal fin{nullptr, nullptr, 0.0, 0};
     if (final_energies) {
-        if (!s->d_strip_fin) {
-            TRY(dev_alloc(s->d_strip_fin, s->cap));
-            HIP_TRY(hipMemsetAsync(s->d_strip_fin, 0, s->cap * sizeof(unsigned long long), s->stream));
+        if (!s->strip.d_fin) {
+            TRY(dev_alloc(s->strip.d_fin, s->cap));
+            HIP_TRY(hipMemsetAsync(s->strip.d_fin, 0, s->cap * sizeof(unsigned long long), s->stream));
         }
-        fin = StripFinal{s->d_strip_fin + r0, final_energies + r0, g->jabs, 2ll * (long long)g->nvars};
+        fin = StripFinal{s->strip.d_fin + r0, final_energies + r0, g->jabs, 2ll * (long long)g->nvars};
     }
-    if (uint64_t(s->strip_epoch) + 2 * nk + 2 >= 0xFFFFFFF0ull) { // tags are unique per states object: restart them
-        HIP_TRY(hipMemsetAsync(s->d_halo, 0, s->halo_cap * sizeof(unsigned long long), s->stream));
-        s->strip_epoch = 0;
+    if (uint64_t(s->strip.epoch) + 2 * nk + 2 >= 0xFFFFFFF0ull) { // tags are unique per states object: restart them
+        HIP_TRY(hipMemsetAsync(s->strip.d_halo, 0, s->strip.halo_cap * sizeof(unsigned long long), s->stream));
+        s->strip.epoch = 0;
     }
     // test hook (tests/test_gpu_strip.py): the first strip launch of this object runs with the error word already raised,
     // as if a workgroup had timed out -- in-order dispatch makes a real timeout need a co-tenant or a replica of more strips
     // than the chip holds -- so that the host's recovery (restore the planes, repeat on the per-colour launches) is exercised
-    if (!s->strip_test_failed && s->opt.strip_test_fail_once) {
+    if (!s->strip.test_failed && s->opt.strip_test_fail_once) {
         const uint32_t one = STRIP_ERR_TIMEOUT;
-        HIP_TRY(hipMemcpyAsync(s->d_strip_err, &one, sizeof one, hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipMemcpyAsync(s->strip.d_err, &one, sizeof one, hipMemcpyHostToDevice, s->stream));
         HIP_TRY(hipStreamSynchronize(s->stream));
-        s->strip_test_failed = true;
+        s->strip.test_failed = true;
     }
     StripArgs a = P.a;
-    a.epoch = s->strip_epoch;
+    a.epoch = s->strip.epoch;
     a.xcd_remap = n % 8 == 0;
     const size_t lds = (size_t(2) * (a.S + 2) * g->geom.wpr + 16) * sizeof(uint32_t);
     {
@@ -996,8 +996,8 @@ int launch_strip(isingmc_states *s, const StripPlan &P, size_t r0, size_t n, siz
         else HIP_TRY(hipStreamWaitEvent(s->stream, ev, 0));
         HIP_TRY(strip_launch(!g->uniform_sign, P.nw, unsigned(n * a.n_strips), lds, s->stream, s->d_state + r0 * g->state_words, g->geom, a, s->t,
                              uint32_t(nk), s->d_keys + r0, d_thr_steps, thr_stride, s->has_betas ? s->d_thr + r0 : nullptr, g->d_jneg,
-                             g->jneg_uniform, s->d_halo + r0 * size_t(a.n_strips) * 4 * g->geom.wpr, steps_out, fin,
-                             ladder ? *ladder : StripLadder{}, uint32_t(s->R), s->d_strip_err, s->opt.philox_rounds));
+                             g->jneg_uniform, s->strip.d_halo + r0 * size_t(a.n_strips) * 4 * g->geom.wpr, steps_out, fin,
+                             ladder ? *ladder : StripLadder{}, uint32_t(s->R), s->strip.d_err, s->opt.philox_rounds));
         HIP_TRY(hipEventRecord(ev, s->stream));
     }
     return ISINGMC_OK;
@@ -1008,18 +1008,18 @@ int launch_strip(isingmc_states *s, const StripPlan &P, size_t r0, size_t n, siz
 // the planes they started from (run_steps, isingmc_run_sampling) repeat their work; the others report the error.
 int strip_check(isingmc_states *s)
 {
-    if (!s->d_strip_err) return ISINGMC_OK;
+    if (!s->strip.d_err) return ISINGMC_OK;
     uint32_t h = 0;
-    HIP_TRY(hipMemcpy(&h, s->d_strip_err, sizeof h, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&h, s->strip.d_err, sizeof h, hipMemcpyDeviceToHost));
     if (h == 0) return ISINGMC_OK;
-    (void)hipMemset(s->d_strip_err, 0, sizeof h);
-    if (s->d_strip_fin) (void)hipMemset(s->d_strip_fin, 0, s->cap * sizeof(unsigned long long));
-    if (s->d_pt_round_counts) (void)hipMemset(s->d_pt_round_counts, 0, 2 * s->R * sizeof(unsigned long long));
-    if (s->d_pt_mail) (void)hipMemset(s->d_pt_mail, 0, 4 * s->R * sizeof(unsigned long long));
-    if (s->d_halo) (void)hipMemset(s->d_halo, 0, s->halo_cap * sizeof(unsigned long long));
-    s->strip_epoch = 0;
+    (void)hipMemset(s->strip.d_err, 0, sizeof h);
+    if (s->strip.d_fin) (void)hipMemset(s->strip.d_fin, 0, s->cap * sizeof(unsigned long long));
+    if (s->strip.d_pt_round_counts) (void)hipMemset(s->strip.d_pt_round_counts, 0, 2 * s->R * sizeof(unsigned long long));
+    if (s->strip.d_pt_mail) (void)hipMemset(s->strip.d_pt_mail, 0, 4 * s->R * sizeof(unsigned long long));
+    if (s->strip.d_halo) (void)hipMemset(s->strip.d_halo, 0, s->strip.halo_cap * sizeof(unsigned long long));
+    s->strip.epoch = 0;
     s->meas_fresh = false;
-    s->strip_disabled = true;
+    s->strip.disabled = true;
     return STRIP_TIMED_OUT;
 }
 
@@ -1040,20 +1040,20 @@ static int run_steps_impl(isingmc_states *s, size_t timesteps, const double *bet
 int snapshot_take(isingmc_states *s)
 {
     const size_t words = s->R * s->g->state_words;
-    if (s->snapshot_cap < words) TRY(dev_regrow(s->stream, s->d_snapshot, &s->snapshot_cap, words, words));
-    HIP_TRY(hipMemcpyAsync(s->d_snapshot, s->d_state, words * sizeof(uint32_t), hipMemcpyDeviceToDevice, s->stream));
+    if (s->strip.snapshot_cap < words) TRY(dev_regrow(s->stream, s->strip.d_snapshot, &s->strip.snapshot_cap, words, words));
+    HIP_TRY(hipMemcpyAsync(s->strip.d_snapshot, s->d_state, words * sizeof(uint32_t), hipMemcpyDeviceToDevice, s->stream));
     return ISINGMC_OK;
 }
 
 int snapshot_restore(isingmc_states *s)
 {
-    HIP_TRY(hipMemcpyAsync(s->d_state, s->d_snapshot, s->R * s->g->state_words * sizeof(uint32_t), hipMemcpyDeviceToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->d_state, s->strip.d_snapshot, s->R * s->g->state_words * sizeof(uint32_t), hipMemcpyDeviceToDevice, s->stream));
     return ISINGMC_OK;
 }
 
 bool may_use_strips(const isingmc_states *s)
 {
-    return s && s->R && !s->packed && !s->strip_disabled && s->g->kind == ISINGMC_KIND_LATTICE2D && s->g->mc_mode == MC_NONE &&
+    return s && s->R && !s->packed && !s->strip.disabled && s->g->kind == ISINGMC_KIND_LATTICE2D && s->g->mc_mode == MC_NONE &&
            s->opt.strip != 0;
 }
 
@@ -1294,7 +1294,7 @@ static int run_lat_strip(StepRun &c, size_t k0, size_t nk)
     for (size_t r0 = 0; r0 < R; r0 += c.P.strip.replicas_per_pass)
         TRY(launch_strip(s, c.P.strip, r0, std::min(c.P.strip.replicas_per_pass, R - r0), nk, c.d_thr, uint32_t(c.beta_stride ? 1 : 0),
                          c.d_counts ? c.d_counts + 2 * r0 : nullptr, last ? c.final_energies : nullptr));
-    s->strip_epoch += uint32_t(2 * nk);
+    s->strip.epoch += uint32_t(2 * nk);
     s->t += nk;
     if (c.final_energies && last) s->meas_fresh = true;
     if (k0 + nk < c.timesteps && !c.d_counts) HIP_TRY(hipStreamSynchronize(s->stream)); // h_thr is reused by the next chunk
@@ -1513,7 +1513,7 @@ static int run_steps_impl(isingmc_states *s, size_t timesteps, const double *bet
         const bool cluster = is_cluster_step(s), icm = is_icm_step(s);
         if (cluster || icm) nk = 1;
         else {
-            if (const size_t every = s->cluster_every ? s->cluster_every : s->icm_every) nk = std::min<size_t>(nk, every - 1 - s->t % every);
+            if (const size_t every = s->cl.every ? s->cl.every : s->icm.every) nk = std::min<size_t>(nk, every - 1 - s->t % every);
             // the periodic recorders cut the call too: a stretch ends with their next sample point
             nk = std::min(nk, recorders_stretch(s));
             // (joined by the cluster step or the update before this stretch; the packed runner forks behind its table launches)

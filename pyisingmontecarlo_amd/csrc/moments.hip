@@ -39,12 +39,12 @@ static std::string mom_obstacle(const isingmc_states *s, unsigned flags)
         const std::string why = lattice_obstacle(g, "moment sums", true, false);
         if (!why.empty()) return why;
     }
-    if (s->pt_attached && !mom_per_rung(flags))
+    if (s->tempering.attached && !mom_per_rung(flags))
         return "a tempering ladder is attached: a slot changes its temperature at every exchange, so sums per slot or over all slots mix the "
                "temperatures (ISINGMC_MOMENTS_PER_RUNG sums by rung; or isingmc_pt_detach first)";
-    if (mom_per_rung(flags) && !s->pt_attached)
+    if (mom_per_rung(flags) && !s->tempering.attached)
         return "sums per rung need a tempering ladder: none is attached to this container (isingmc_pt_attach first, then switch the sums on)";
-    if (mom_per_rung(flags) && (s->pt_world != 1 || s->pt.slot_offset != 0 || s->pt.n_rungs != s->R))
+    if (mom_per_rung(flags) && (s->tempering.world != 1 || s->pt.slot_offset != 0 || s->pt.n_rungs != s->R))
         return "sums per rung need the whole ladder on this container (world size 1, one slot per rung): a shard of a larger ladder is not served";
     if (mom_bonds(flags) && !g->edge_order_kept)
         return "this lattice is too large for bond sums in the order of its edge list (2 W H must stay below 2^32 unless entry e is bond e)";
@@ -61,19 +61,19 @@ static std::string mom_obstacle(const isingmc_states *s, unsigned flags)
 
 static int mom_zero_enqueue(isingmc_states *s)
 {
-    const unsigned flags = s->mom_flags;
+    const unsigned flags = s->mom.flags;
     if (mom_rows(flags)) {
         const size_t words = mom_state_words(s);
-        HIP_TRY(hipMemsetAsync(s->d_mom_planes, 0, size_t(s->mom_k) * words * sizeof(uint32_t), s->stream));
-        HIP_TRY(hipMemsetAsync(s->d_mom_totals, 0, 32 * words * sizeof(uint32_t), s->stream));
+        HIP_TRY(hipMemsetAsync(s->mom.d_planes, 0, size_t(s->mom.k) * words * sizeof(uint32_t), s->stream));
+        HIP_TRY(hipMemsetAsync(s->mom.d_totals, 0, 32 * words * sizeof(uint32_t), s->stream));
     } else if (!s->packed) {
-        HIP_TRY(hipMemsetAsync(s->d_mom_site, 0, (mom_bonds(flags) ? 3 : 1) * 32 * s->g->state_words * sizeof(unsigned long long), s->stream));
+        HIP_TRY(hipMemsetAsync(s->mom.d_site, 0, (mom_bonds(flags) ? 3 : 1) * 32 * s->g->state_words * sizeof(unsigned long long), s->stream));
     } else {
-        HIP_TRY(hipMemsetAsync(s->d_mom_site, 0, s->g->pk.n_pos * sizeof(unsigned long long), s->stream));
-        if (mom_bonds(flags)) HIP_TRY(hipMemsetAsync(s->d_mom_bond, 0, std::max<size_t>(s->g->n_edges, 1) * sizeof(unsigned long long), s->stream));
+        HIP_TRY(hipMemsetAsync(s->mom.d_site, 0, s->g->pk.n_pos * sizeof(unsigned long long), s->stream));
+        if (mom_bonds(flags)) HIP_TRY(hipMemsetAsync(s->mom.d_bond, 0, std::max<size_t>(s->g->n_edges, 1) * sizeof(unsigned long long), s->stream));
     }
-    s->mom_n = 0;
-    s->mom_pending = 0;
+    s->mom.n = 0;
+    s->mom.pending = 0;
     return ISINGMC_OK;
 }
 
@@ -83,30 +83,30 @@ static int mom_reserve(isingmc_states *s, unsigned flags)
 {
     const isingmc_graph *g = s->g;
     const int k = mom_rows(flags) ? s->opt.moments_planes : 0;
-    if (s->mom_have && s->mom_flags == flags && s->mom_R == s->R && s->mom_k == k) return ISINGMC_OK;
+    if (s->mom.have && s->mom.flags == flags && s->mom.R == s->R && s->mom.k == k) return ISINGMC_OK;
     HIP_TRY(stream_quiesce(s->stream)); // recycled blocks: nothing enqueued may still use the old ones
-    s->d_mom_site.reset(); s->d_mom_bond.reset(); s->d_mom_edges.reset(); s->d_mom_planes.reset(); s->d_mom_totals.reset();
-    s->mom_have = false;
+    s->mom.d_site.reset(); s->mom.d_bond.reset(); s->mom.d_edges.reset(); s->mom.d_planes.reset(); s->mom.d_totals.reset();
+    s->mom.have = false;
     if (mom_rows(flags)) {
         const size_t words = mom_state_words(s);
-        TRY(dev_alloc(s->d_mom_planes, size_t(k) * words));
-        TRY(dev_alloc(s->d_mom_totals, 32 * words));
+        TRY(dev_alloc(s->mom.d_planes, size_t(k) * words));
+        TRY(dev_alloc(s->mom.d_totals, 32 * words));
     } else if (!s->packed) {
-        TRY(dev_alloc(s->d_mom_site, (mom_bonds(flags) ? 3 : 1) * 32 * g->state_words));
+        TRY(dev_alloc(s->mom.d_site, (mom_bonds(flags) ? 3 : 1) * 32 * g->state_words));
     } else {
-        TRY(dev_alloc(s->d_mom_site, g->pk.n_pos));
+        TRY(dev_alloc(s->mom.d_site, g->pk.n_pos));
         if (mom_bonds(flags)) {
             std::vector<uint2> ends(g->n_edges);
             for (size_t e = 0; e < g->n_edges; e++) ends[e] = make_uint2(uint32_t(g->pos[g->edge_ends[2 * e]]), uint32_t(g->pos[g->edge_ends[2 * e + 1]]));
-            TRY(dev_alloc(s->d_mom_bond, g->n_edges));
-            TRY(dev_alloc(s->d_mom_edges, g->n_edges));
-            if (g->n_edges) HIP_TRY(hipMemcpy(s->d_mom_edges, ends.data(), ends.size() * sizeof(uint2), hipMemcpyHostToDevice));
+            TRY(dev_alloc(s->mom.d_bond, g->n_edges));
+            TRY(dev_alloc(s->mom.d_edges, g->n_edges));
+            if (g->n_edges) HIP_TRY(hipMemcpy(s->mom.d_edges, ends.data(), ends.size() * sizeof(uint2), hipMemcpyHostToDevice));
         }
     }
-    s->mom_flags = flags;
-    s->mom_R = s->R;
-    s->mom_k = k;
-    s->mom_have = true;
+    s->mom.flags = flags;
+    s->mom.R = s->R;
+    s->mom.k = k;
+    s->mom.have = true;
     return mom_zero_enqueue(s);
 }
 
@@ -128,16 +128,16 @@ extern "C" int isingmc_states_moments_every(const isingmc_states *s, size_t *eve
 {
     if (!s) return fail(ISINGMC_ERR_INVALID, "NULL states");
     if (every_out) *every_out = s->rec[REC_MOMENTS].every;
-    if (flags_out) *flags_out = s->mom_flags;
+    if (flags_out) *flags_out = s->mom.flags;
     return ISINGMC_OK;
 }
 
 static int mom_flush_enqueue(isingmc_states *s)
 {
-    if (!s->mom_pending) return ISINGMC_OK;
+    if (!s->mom.pending) return ISINGMC_OK;
     const size_t rows = s->packed ? s->groups : s->R, row_words = s->packed ? size_t(s->g->pk.n_pos) : size_t(s->g->state_words);
-    HIP_TRY(moments_launch_flush(s->stream, s->d_mom_planes, rows, row_words, s->mom_k, s->d_mom_totals));
-    s->mom_pending = 0;
+    HIP_TRY(moments_launch_flush(s->stream, s->mom.d_planes, rows, row_words, s->mom.k, s->mom.d_totals));
+    s->mom.pending = 0;
     return ISINGMC_OK;
 }
 
@@ -146,32 +146,32 @@ int moments_sample_enqueue(isingmc_states *s)
     if (s->R == 0) return ISINGMC_OK;
     if (s->n_lanes > 1) TRY(lanes_join(s)); // the sweeps before this sample may have run on replica lanes
     const isingmc_graph *g = s->g;
-    const unsigned flags = s->mom_flags;
+    const unsigned flags = s->mom.flags;
     if (mom_rows(flags)) {
-        if (s->mom_n >= 0xFFFFFFFFull) return fail(ISINGMC_ERR_INVALID, "the per-replica and per-rung totals are 32-bit counts: 2^32 - 1 samples are in them (isingmc_moments_reset)");
+        if (s->mom.n >= 0xFFFFFFFFull) return fail(ISINGMC_ERR_INVALID, "the per-replica and per-rung totals are 32-bit counts: 2^32 - 1 samples are in them (isingmc_moments_reset)");
         if (!mom_per_rung(flags))
-            HIP_TRY(moments_launch_add(s->stream, s->d_state, mom_state_words(s), s->mom_k, s->d_mom_planes));
+            HIP_TRY(moments_launch_add(s->stream, s->d_state, mom_state_words(s), s->mom.k, s->mom.d_planes));
         // per rung: the permutation is read by the kernel, as the exchange rounds enqueued so far leave it
         else if (!s->packed)
-            HIP_TRY(moments_launch_add_by_rung(s->stream, s->d_state, s->d_pt_perm, s->R, g->state_words, s->mom_k, s->d_mom_planes));
+            HIP_TRY(moments_launch_add_by_rung(s->stream, s->d_state, s->tempering.d_perm, s->R, g->state_words, s->mom.k, s->mom.d_planes));
         else
-            HIP_TRY(moments_launch_packed_add_by_rung(s->stream, s->d_state, s->d_pt_perm, s->R, g->pk.n_pos, uint32_t(s->pk_bit0), mom_state_words(s),
-                                                      s->mom_k, s->d_mom_planes));
-        if (++s->mom_pending == (1u << s->mom_k) - 1) TRY(mom_flush_enqueue(s));
+            HIP_TRY(moments_launch_packed_add_by_rung(s->stream, s->d_state, s->tempering.d_perm, s->R, g->pk.n_pos, uint32_t(s->pk_bit0), mom_state_words(s),
+                                                      s->mom.k, s->mom.d_planes));
+        if (++s->mom.pending == (1u << s->mom.k) - 1) TRY(mom_flush_enqueue(s));
     } else if (!s->packed) {
-        HIP_TRY(moments_launch_lattice_sum(s->stream, s->d_state, g->geom, s->R, mom_bonds(flags), s->d_mom_site));
+        HIP_TRY(moments_launch_lattice_sum(s->stream, s->d_state, g->geom, s->R, mom_bonds(flags), s->mom.d_site));
     } else {
-        HIP_TRY(moments_launch_packed_sum(s->stream, s->d_state, g->pk.n_pos, s->groups, uint32_t(s->pk_bit0), uint32_t(s->R), s->d_mom_site,
-                                          s->d_mom_edges, mom_bonds(flags) ? size_t(g->n_edges) : 0, s->d_mom_bond));
+        HIP_TRY(moments_launch_packed_sum(s->stream, s->d_state, g->pk.n_pos, s->groups, uint32_t(s->pk_bit0), uint32_t(s->R), s->mom.d_site,
+                                          s->mom.d_edges, mom_bonds(flags) ? size_t(g->n_edges) : 0, s->mom.d_bond));
     }
-    s->mom_n++;
+    s->mom.n++;
     return ISINGMC_OK;
 }
 
 extern "C" int isingmc_moments_accumulate(isingmc_states *s)
 {
     if (!s) return fail(ISINGMC_ERR_INVALID, "NULL states");
-    const unsigned flags = s->mom_have ? s->mom_flags : 0u; // never switched on: the sums over all replicas, sites alone
+    const unsigned flags = s->mom.have ? s->mom.flags : 0u; // never switched on: the sums over all replicas, sites alone
     {
         const std::string why = mom_obstacle(s, flags);
         if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
@@ -184,7 +184,7 @@ extern "C" int isingmc_moments_accumulate(isingmc_states *s)
 extern "C" int isingmc_moments_reset(isingmc_states *s)
 {
     if (!s) return fail(ISINGMC_ERR_INVALID, "NULL states");
-    if (!s->mom_have) return ISINGMC_OK; // nothing counted yet
+    if (!s->mom.have) return ISINGMC_OK; // nothing counted yet
     TRY(use_device(s->g->device));
     return mom_zero_enqueue(s);
 }
@@ -212,7 +212,7 @@ static int run_sampling_moments_impl(isingmc_states *s, double beta, size_t ther
     s->rec[REC_MOMENTS].every = sampling_freq;
     s->rec[REC_MOMENTS].t0 = s->t;
     TRY(run_steps(s, n_samples * sampling_freq, nullptr, 0, nullptr, nullptr, /*sync=*/false));
-    if (!s->strip_guard) return ISINGMC_OK;
+    if (!s->strip.guard) return ISINGMC_OK;
     HIP_TRY(hipStreamSynchronize(s->stream)); // (a call that may be repeated: what the last strip launch left is checked here)
     return strip_check(s);
 }
@@ -238,7 +238,7 @@ extern "C" int isingmc_run_sampling_moments(isingmc_states *s, double beta, size
     s->rec[REC_MOMENTS].last_t = 0;
     const bool may_strip = may_use_strips(s) && (strip_plan(s, thermalization).use || strip_plan(s, n_samples * sampling_freq).use);
     TRY(with_strip_retry(s, may_strip, [&] { return run_sampling_moments_impl(s, beta, thermalization, sampling_freq, n_samples); }));
-    if (mom_rows(s->mom_flags)) TRY(mom_flush_enqueue(s));
+    if (mom_rows(s->mom.flags)) TRY(mom_flush_enqueue(s));
     if (energies_out) return isingmc_get_energies(s, energies_out); // waits
     HIP_TRY(hipStreamSynchronize(s->stream));
     return strip_error(strip_check(s));
@@ -247,23 +247,23 @@ extern "C" int isingmc_run_sampling_moments(isingmc_states *s, double beta, size
 extern "C" int isingmc_moments_get(isingmc_states *s, uint64_t *n_samples_out, int64_t *site_out, int64_t *bond_out)
 {
     if (!s) return fail(ISINGMC_ERR_INVALID, "NULL states");
-    if (!s->mom_have || s->mom_R != s->R)
+    if (!s->mom.have || s->mom.R != s->R)
         return fail(ISINGMC_ERR_INVALID, "this container holds no moment sums: switch accumulation on (isingmc_states_set_moments_every) or call isingmc_moments_accumulate first");
-    const unsigned flags = s->mom_flags;
+    const unsigned flags = s->mom.flags;
     if (bond_out && !mom_bonds(flags)) return fail(ISINGMC_ERR_INVALID, "no bond sums are held: switch accumulation on with ISINGMC_MOMENTS_BONDS (bond_out may be NULL)");
     TRY(use_device(s->g->device));
     const isingmc_graph *g = s->g;
     if (mom_rows(flags)) TRY(mom_flush_enqueue(s));
     HIP_TRY(hipStreamSynchronize(s->stream));
     TRY(strip_error(strip_check(s)));
-    if (n_samples_out) *n_samples_out = s->mom_n;
-    const int64_t n = int64_t(s->mom_n), nR = n * int64_t(s->R);
+    if (n_samples_out) *n_samples_out = s->mom.n;
+    const int64_t n = int64_t(s->mom.n), nR = n * int64_t(s->R);
     const size_t N = g->nvars;
     if (mom_rows(flags)) { // row r: replica r's slot, or rung r itself
         const bool by_rung = mom_per_rung(flags);
         if (!site_out || s->R == 0) return ISINGMC_OK;
         std::vector<uint32_t> h;
-        TRY(read_back(s, h, s->d_mom_totals.get(), 32 * mom_state_words(s)));
+        TRY(read_back(s, h, s->mom.d_totals.get(), 32 * mom_state_words(s)));
         if (s->packed) { // totals[slot or rung][n_pos]
             const size_t n_pos = g->pk.n_pos;
             parallel_for(s->R, [&](size_t r) {
@@ -291,7 +291,7 @@ extern "C" int isingmc_moments_get(isingmc_states *s, uint64_t *n_samples_out, i
         const size_t sw = g->state_words;
         const bool bonds = bond_out && mom_bonds(flags);
         if (!site_out && !bonds) return ISINGMC_OK;
-        TRY(read_back(s, h, s->d_mom_site.get(), (mom_bonds(flags) ? 3 : 1) * 32 * sw));
+        TRY(read_back(s, h, s->mom.d_site.get(), (mom_bonds(flags) ? 3 : 1) * 32 * sw));
         const auto total = [&](uint32_t kind, size_t site) {
             const uint32_t y = uint32_t(site / L.W), x = uint32_t(site - size_t(y) * L.W), i = x >> 1;
             const size_t w = size_t((x + y) & 1) * L.wpp + size_t(y) * L.wpr + (i >> 5);
@@ -307,11 +307,11 @@ extern "C" int isingmc_moments_get(isingmc_states *s, uint64_t *n_samples_out, i
         return ISINGMC_OK;
     }
     if (site_out) {
-        TRY(read_back(s, h, s->d_mom_site.get(), size_t(g->pk.n_pos)));
+        TRY(read_back(s, h, s->mom.d_site.get(), size_t(g->pk.n_pos)));
         for (size_t i = 0; i < N; i++) site_out[i] = 2 * int64_t(h[g->pos[i]]) - nR;
     }
     if (bond_out && g->n_edges) {
-        TRY(read_back(s, h, s->d_mom_bond.get(), size_t(g->n_edges)));
+        TRY(read_back(s, h, s->mom.d_bond.get(), size_t(g->n_edges)));
         for (size_t e = 0; e < g->n_edges; e++) bond_out[e] = 2 * int64_t(h[e]) - nR;
     }
     return ISINGMC_OK;

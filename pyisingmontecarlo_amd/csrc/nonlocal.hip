@@ -56,7 +56,7 @@ std::string cluster_obstacle(const isingmc_states *s)
         const std::string why = lattice_obstacle(g, "cluster updates", false);
         if (!why.empty()) return why;
     }
-    if (s->pt_attached) return "a tempering ladder is attached to this container (isingmc_pt_detach first)";
+    if (s->tempering.attached) return "a tempering ladder is attached to this container (isingmc_pt_detach first)";
     return "";
 }
 
@@ -66,26 +66,26 @@ extern "C" int isingmc_states_set_cluster_every(isingmc_states *s, size_t k)
     if (k) {
         const std::string why = cluster_obstacle(s);
         if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
-        if (s->icm_every) return fail(ISINGMC_ERR_INVALID, "isoenergetic cluster moves are switched on for this container (isingmc_states_set_icm_every): one non-local move at a time");
+        if (s->icm.every) return fail(ISINGMC_ERR_INVALID, "isoenergetic cluster moves are switched on for this container (isingmc_states_set_icm_every): one non-local move at a time");
     }
-    s->cluster_every = k;
+    s->cl.every = k;
     return ISINGMC_OK;
 }
 
 extern "C" int isingmc_states_cluster_every(const isingmc_states *s, size_t *k_out)
 {
     if (!s || !k_out) return fail(ISINGMC_ERR_INVALID, "NULL argument");
-    *k_out = s->cluster_every;
+    *k_out = s->cl.every;
     return ISINGMC_OK;
 }
 
 extern "C" int isingmc_cluster_stats(isingmc_states *s, uint64_t *n_clusters_out, uint64_t *largest_out)
 {
     if (!s || !n_clusters_out || !largest_out) return fail(ISINGMC_ERR_INVALID, "NULL argument");
-    if (!s->cl_have_stats || s->cl_stats_cap < counter_slots(s)) return fail(ISINGMC_ERR_INVALID, "no cluster step has run on these replicas yet");
+    if (!s->cl.have_stats || s->cl.stats_cap < counter_slots(s)) return fail(ISINGMC_ERR_INVALID, "no cluster step has run on these replicas yet");
     TRY(use_device(s->g->device));
     std::vector<uint32_t> h;
-    TRY(read_back(s, h, s->d_cl_stats.get(), 2 * counter_slots(s)));
+    TRY(read_back(s, h, s->cl.d_stats.get(), 2 * counter_slots(s)));
     for (size_t r = 0; r < s->R; r++) { // (packed: one pair per (group, bit) slot)
         n_clusters_out[r] = h[2 * counter_slot(s, r)];
         largest_out[r] = h[2 * counter_slot(s, r) + 1];
@@ -100,7 +100,7 @@ static uint64_t cluster_threshold(double beta, double jabs)
     return uint64_t(std::floor(std::ldexp(-std::expm1(-2.0 * beta * jabs), 32)));
 }
 
-bool is_cluster_step(const isingmc_states *s) { return s->cluster_every && s->t % s->cluster_every == s->cluster_every - 1; }
+bool is_cluster_step(const isingmc_states *s) { return s->cl.every && s->t % s->cl.every == s->cl.every - 1; }
 
 // Timestep s->t as a cluster step of every replica, batch by batch on the main stream.  A lattice container works in batches of
 // replicas; a replica-packed bit-sliced one in batches of whole replica groups, every bit of a group simulated,
@@ -119,9 +119,9 @@ int run_cluster_step(isingmc_states *s, NonlocalRun &n, DeviceScratch &scratch, 
         else n.cl = cluster_carve(block, batch, g->nvars);
         n.batch = batch;
     }
-    if (s->cl_stats_cap < slots) { // a lattice container may grow; the groups of a packed one are fixed for its life: allocated once
+    if (s->cl.stats_cap < slots) { // a lattice container may grow; the groups of a packed one are fixed for its life: allocated once
         const size_t cap = s->packed ? slots : s->cap;
-        TRY(dev_regrow(s->stream, s->d_cl_stats, &s->cl_stats_cap, 2 * cap, cap));
+        TRY(dev_regrow(s->stream, s->cl.d_stats, &s->cl.stats_cap, 2 * cap, cap));
     }
     uint64_t thr = 0;
     if (!s->has_betas) thr = cluster_threshold(beta, g->jabs);
@@ -132,7 +132,7 @@ int run_cluster_step(isingmc_states *s, NonlocalRun &n, DeviceScratch &scratch, 
         TRY(scratch.alloc(&n.d_cl_thr, slots));
         HIP_TRY(hipMemcpyAsync(n.d_cl_thr, n.h_cl_thr.data(), slots * sizeof(uint64_t), hipMemcpyHostToDevice, s->stream));
     }
-    HIP_TRY(hipMemsetAsync(s->d_cl_stats, 0, 2 * slots * sizeof(uint32_t), s->stream));
+    HIP_TRY(hipMemsetAsync(s->cl.d_stats, 0, 2 * slots * sizeof(uint32_t), s->stream));
     ClusterMomentsOut row; // a live cluster series: every batch adds its columns' moments into the same row
     TRY(cluster_series_begin(s, ISINGMC_CLUSTER_SERIES_SW, &row));
     for (size_t i0 = 0; i0 < items; i0 += n.batch) {
@@ -140,13 +140,13 @@ int run_cluster_step(isingmc_states *s, NonlocalRun &n, DeviceScratch &scratch, 
         row.slot0 = uint32_t(s->packed ? 32 * i0 : i0);
         if (s->packed)
             HIP_TRY(pk_cluster_launch_step(s->stream, s->d_state + i0 * n_pos, g->pk, s->t, s->d_keys + i0, thr, n.d_cl_thr ? n.d_cl_thr + 32 * i0 : nullptr,
-                                           n.pk_cl, ni, s->d_cl_stats + 2 * 32 * i0, row));
+                                           n.pk_cl, ni, s->cl.d_stats + 2 * 32 * i0, row));
         else
             HIP_TRY(cluster_launch_step(s->stream, s->d_state + i0 * g->state_words, g->geom, s->t, s->d_keys + i0, g->jneg_uniform, thr,
-                                        n.d_cl_thr ? n.d_cl_thr + i0 : nullptr, n.cl, ni, s->d_cl_stats + 2 * i0, row));
+                                        n.d_cl_thr ? n.d_cl_thr + i0 : nullptr, n.cl, ni, s->cl.d_stats + 2 * i0, row));
     }
-    if (row.row) TRY(cluster_series_end(s, row, s->d_cl_stats, nullptr));
-    s->cl_have_stats = true;
+    if (row.row) TRY(cluster_series_end(s, row, s->cl.d_stats, nullptr));
+    s->cl.have_stats = true;
     s->t++;
     return ISINGMC_OK;
 }
@@ -169,7 +169,7 @@ std::string icm_obstacle(const isingmc_states *s)
 {
     const isingmc_graph *g = s->g;
     if (s->packed) { // S12: any graph of either packed family (the move reads no coupling and no bias)
-        if (s->cluster_every)
+        if (s->cl.every)
             return "Swendsen-Wang cluster updates are switched on for this replica-packed general-graph container (isingmc_states_set_cluster_every): "
                    "one non-local move at a time";
     } else {
@@ -178,8 +178,8 @@ std::string icm_obstacle(const isingmc_states *s)
         const std::string why = lattice_obstacle(g, "isoenergetic cluster moves", true);
         if (!why.empty()) return why;
     }
-    if (s->pt_attached) return "a tempering ladder is attached to this container (isingmc_pt_detach first)";
-    if (s->cluster_every) return "Swendsen-Wang cluster updates are switched on for this container (isingmc_states_set_cluster_every): one non-local move at a time";
+    if (s->tempering.attached) return "a tempering ladder is attached to this container (isingmc_pt_detach first)";
+    if (s->cl.every) return "Swendsen-Wang cluster updates are switched on for this container (isingmc_states_set_cluster_every): one non-local move at a time";
     // pairs are (2 p, 2 p + 1) of the GLOBAL experiment index: a shard must hold both replicas of every pair it touches
     // (packed: the pair is then bits (2 j, 2 j + 1) of one state word, pk_bit0 = first % 32 being even)
     if (s->first % 2) return "this shard starts at an odd experiment index: its first replica's partner lives on another shard";
@@ -196,14 +196,14 @@ extern "C" int isingmc_states_set_icm_every(isingmc_states *s, size_t k)
         const std::string why = icm_obstacle(s);
         if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
     }
-    s->icm_every = k;
+    s->icm.every = k;
     return ISINGMC_OK;
 }
 
 extern "C" int isingmc_states_icm_every(const isingmc_states *s, size_t *k_out)
 {
     if (!s || !k_out) return fail(ISINGMC_ERR_INVALID, "NULL argument");
-    *k_out = s->icm_every;
+    *k_out = s->icm.every;
     return ISINGMC_OK;
 }
 
@@ -211,12 +211,12 @@ extern "C" int isingmc_icm_stats(isingmc_states *s, uint64_t *n_clusters_out, ui
 {
     if (!s || !n_clusters_out || !largest_out || !minus_sites_out) return fail(ISINGMC_ERR_INVALID, "NULL argument");
     const size_t pairs = s->R / 2, slot0 = s->packed ? s->pk_bit0 / 2 : 0; // (packed: device slot 16 group + pair; pk_bit0 is even)
-    if (!s->icm_have_stats || s->icm_stats_cap < slot0 + pairs) return fail(ISINGMC_ERR_INVALID, "no isoenergetic cluster move has run on these replicas yet");
+    if (!s->icm.have_stats || s->icm.stats_cap < slot0 + pairs) return fail(ISINGMC_ERR_INVALID, "no isoenergetic cluster move has run on these replicas yet");
     TRY(use_device(s->g->device));
-    return read_pair_stats(s, s->d_icm_stats, s->icm_stats_cap, slot0, pairs, n_clusters_out, largest_out, minus_sites_out);
+    return read_pair_stats(s, s->icm.d_stats, s->icm.stats_cap, slot0, pairs, n_clusters_out, largest_out, minus_sites_out);
 }
 
-bool is_icm_step(const isingmc_states *s) { return s->icm_every && s->t % s->icm_every == s->icm_every - 1; }
+bool is_icm_step(const isingmc_states *s) { return s->icm.every && s->t % s->icm.every == s->icm.every - 1; }
 
 // Timestep s->t as an isoenergetic cluster move of every pair, batch by batch on the main stream.  A lattice container works in
 // batches of pairs (one labelling problem per PAIR; a last replica without a partner stays as it is).  A replica-packed one of
@@ -251,12 +251,12 @@ int run_icm_step(isingmc_states *s, NonlocalRun &n, DeviceScratch &scratch)
     }
     // (a lattice container of one replica has no pair and still gets its block; a packed one has 16 slots per group from the start,
     //  and its groups are fixed for its life: allocated once)
-    if (!s->d_icm_stats || s->icm_stats_cap < pair_slots) {
+    if (!s->icm.d_stats || s->icm.stats_cap < pair_slots) {
         const size_t cap = s->packed ? pair_slots : std::max<size_t>(1, s->cap / 2);
-        TRY(dev_regrow(s->stream, s->d_icm_stats, &s->icm_stats_cap, 3 * cap, cap));
+        TRY(dev_regrow(s->stream, s->icm.d_stats, &s->icm.stats_cap, 3 * cap, cap));
     }
-    uint32_t *const minus = s->d_icm_stats + 2 * s->icm_stats_cap;
-    HIP_TRY(hipMemsetAsync(s->d_icm_stats, 0, 3 * s->icm_stats_cap * sizeof(uint32_t), s->stream));
+    uint32_t *const minus = s->icm.d_stats + 2 * s->icm.stats_cap;
+    HIP_TRY(hipMemsetAsync(s->icm.d_stats, 0, 3 * s->icm.stats_cap * sizeof(uint32_t), s->stream));
     ClusterMomentsOut row; // a live cluster series: every batch adds its pairs' moments into the same row
     TRY(cluster_series_begin(s, ISINGMC_CLUSTER_SERIES_ICM, &row));
     for (size_t i0 = 0; i0 < items; i0 += n.batch) {
@@ -264,13 +264,13 @@ int run_icm_step(isingmc_states *s, NonlocalRun &n, DeviceScratch &scratch)
         row.slot0 = uint32_t(s->packed ? 16 * i0 : i0);
         if (s->packed)
             HIP_TRY(pk_icm_launch_step(s->stream, s->d_state + i0 * n_pos, g->pk, s->rj ? g->rj.nbr : nullptr, s->rj ? g->rj.slots : 0, s->t, s->d_keys + i0,
-                                       n.d_icm_mask + i0, n.pk_icm, ni, s->d_icm_stats + 2 * 16 * i0, minus + 16 * i0, row));
+                                       n.d_icm_mask + i0, n.pk_icm, ni, s->icm.d_stats + 2 * 16 * i0, minus + 16 * i0, row));
         else
-            HIP_TRY(icm_launch_step(s->stream, s->d_state + 2 * i0 * g->state_words, g->geom, s->t, s->d_keys + 2 * i0, n.cl, ni, s->d_icm_stats + 2 * i0,
+            HIP_TRY(icm_launch_step(s->stream, s->d_state + 2 * i0 * g->state_words, g->geom, s->t, s->d_keys + 2 * i0, n.cl, ni, s->icm.d_stats + 2 * i0,
                                     minus + i0, row));
     }
-    if (row.row) TRY(cluster_series_end(s, row, s->d_icm_stats, minus));
-    s->icm_have_stats = true;
+    if (row.row) TRY(cluster_series_end(s, row, s->icm.d_stats, minus));
+    s->icm.have_stats = true;
     s->t++;
     return ISINGMC_OK;
 }
@@ -299,8 +299,8 @@ static std::string icm_between_obstacle(const isingmc_states *a, const isingmc_s
         if (!why.empty()) return why;
     }
     for (const isingmc_states *s : {a, b}) {
-        if (s->cluster_every) return "Swendsen-Wang cluster updates are switched on for one of the containers (isingmc_states_set_cluster_every): one non-local move at a time";
-        if (s->icm_every) return "isoenergetic cluster moves inside one of the containers are switched on (isingmc_states_set_icm_every): one non-local move at a time";
+        if (s->cl.every) return "Swendsen-Wang cluster updates are switched on for one of the containers (isingmc_states_set_cluster_every): one non-local move at a time";
+        if (s->icm.every) return "isoenergetic cluster moves inside one of the containers are switched on (isingmc_states_set_icm_every): one non-local move at a time";
     }
     if (a->t != b->t) return "the two containers stand at unequal timesteps: the move is timestep t of both";
     return "";
@@ -312,29 +312,29 @@ static std::string icm_between_obstacle(const isingmc_states *a, const isingmc_s
 static int between_prepare(isingmc_states *a, isingmc_states *b, const uint32_t *slots_a, const uint32_t *slots_b, size_t n_pairs,
                            const uint32_t **d_sa, const uint32_t **d_sb)
 {
-    if (a->icmb_cap < n_pairs) {
+    if (a->icmb.cap < n_pairs) {
         HIP_TRY(stream_quiesce(a->stream));
-        a->d_icmb_slots.reset();
-        a->d_icmb_stats.reset();
-        a->icmb_cap = 0;
-        a->icmb_have_stats = false;
+        a->icmb.d_slots.reset();
+        a->icmb.d_stats.reset();
+        a->icmb.cap = 0;
+        a->icmb.have_stats = false;
         const size_t cap = std::max(n_pairs, a->cap);
-        TRY(dev_alloc(a->d_icmb_slots, 2 * cap));
-        TRY(dev_alloc(a->d_icmb_stats, 3 * cap));
-        a->icmb_cap = cap;
+        TRY(dev_alloc(a->icmb.d_slots, 2 * cap));
+        TRY(dev_alloc(a->icmb.d_stats, 3 * cap));
+        a->icmb.cap = cap;
     }
-    for (hipEvent_t &ev : a->icmb_ev)
-        if (!ev) HIP_TRY(pooled_event_create(&ev, true));
-    *d_sa = a->d_pt_perm;
-    *d_sb = b->d_pt_perm;
+    for (PooledEvent &ev : a->icmb.ev)
+        if (!ev) TRY(event_create(ev));
+    *d_sa = a->tempering.d_perm;
+    *d_sb = b->tempering.d_perm;
     if (slots_a) {
-        HIP_TRY(hipMemcpyAsync(a->d_icmb_slots, slots_a, n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, a->stream));
-        HIP_TRY(hipMemcpyAsync(a->d_icmb_slots + a->icmb_cap, slots_b, n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, a->stream));
-        *d_sa = a->d_icmb_slots;
-        *d_sb = a->d_icmb_slots + a->icmb_cap;
+        HIP_TRY(hipMemcpyAsync(a->icmb.d_slots, slots_a, n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, a->stream));
+        HIP_TRY(hipMemcpyAsync(a->icmb.d_slots + a->icmb.cap, slots_b, n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, a->stream));
+        *d_sa = a->icmb.d_slots;
+        *d_sb = a->icmb.d_slots + a->icmb.cap;
     }
-    TRY(stream_wait_for(a->stream, b->stream, a->icmb_ev[0])); // b's sweeps and exchange rounds so far, before a's stream touches b's configurations and permutation
-    HIP_TRY(hipMemsetAsync(a->d_icmb_stats, 0, 3 * a->icmb_cap * sizeof(uint32_t), a->stream));
+    TRY(stream_wait_for(a->stream, b->stream, a->icmb.ev[0])); // b's sweeps and exchange rounds so far, before a's stream touches b's configurations and permutation
+    HIP_TRY(hipMemsetAsync(a->icmb.d_stats, 0, 3 * a->icmb.cap * sizeof(uint32_t), a->stream));
     return ISINGMC_OK;
 }
 
@@ -343,7 +343,7 @@ static int between_prepare(isingmc_states *a, isingmc_states *b, const uint32_t 
 static int between_sample(isingmc_states *a, isingmc_states *b)
 {
     for (isingmc_states *s : {a, b})
-        if (s->mom_flags & ISINGMC_MOMENTS_PER_RUNG) TRY(recorder_sample_now(s, REC_MOMENTS)); // (no repeat is under way here: replay_to is 0)
+        if (s->mom.flags & ISINGMC_MOMENTS_PER_RUNG) TRY(recorder_sample_now(s, REC_MOMENTS)); // (no repeat is under way here: replay_to is 0)
     // ... and a periodic observable series by rung (S22) takes its row, by the same rule
     for (isingmc_states *s : {a, b})
         if (obs_sample_by_rung(s)) TRY(recorder_sample_now(s, REC_OBSERVABLES));
@@ -353,9 +353,9 @@ static int between_sample(isingmc_states *a, isingmc_states *b)
 // behind the launches: b goes on with the new configurations, and the move has been timestep t of both containers
 static int between_finish(isingmc_states *a, isingmc_states *b, size_t n_pairs)
 {
-    TRY(stream_wait_for(b->stream, a->stream, a->icmb_ev[1]));
-    a->icmb_pairs = n_pairs;
-    a->icmb_have_stats = true;
+    TRY(stream_wait_for(b->stream, a->stream, a->icmb.ev[1]));
+    a->icmb.pairs = n_pairs;
+    a->icmb.have_stats = true;
     for (isingmc_states *s : {a, b}) {
         s->t++;
         s->meas_fresh = false; // cached ladder energies (and those a strip launch left behind) belong to the configurations before the move
@@ -373,13 +373,13 @@ extern "C" int isingmc_icm_between(isingmc_states *a, isingmc_states *b, const u
     if ((slots_a == nullptr) != (slots_b == nullptr)) return fail(ISINGMC_ERR_INVALID, "give both slot tables or neither");
     const isingmc_graph *g = a->g;
     if (!slots_a) { // pair r = (a's rung r, b's rung r): the permutations are read on the device
-        if (!a->pt_attached || !b->pt_attached) return fail(ISINGMC_ERR_INVALID, "without slot tables both containers need an attached tempering ladder (isingmc_pt_attach)");
+        if (!a->tempering.attached || !b->tempering.attached) return fail(ISINGMC_ERR_INVALID, "without slot tables both containers need an attached tempering ladder (isingmc_pt_attach)");
         for (const isingmc_states *s : {a, b})
-            if (s->pt_world != 1 || s->pt.slot_offset != 0 || s->pt.n_rungs != s->R)
+            if (s->tempering.world != 1 || s->pt.slot_offset != 0 || s->pt.n_rungs != s->R)
                 return fail(ISINGMC_ERR_INVALID, "without slot tables each ladder must live on its container alone (world size 1, one slot per rung): sharded ladders are not served");
         if (a->pt.n_rungs != b->pt.n_rungs) return fail(ISINGMC_ERR_INVALID, "the two ladders differ in their number of rungs");
-        if (a->ladder_betas.size() != b->ladder_betas.size() ||
-            std::memcmp(a->ladder_betas.data(), b->ladder_betas.data(), a->ladder_betas.size() * sizeof(double)) != 0)
+        if (a->tempering.ladder_betas.size() != b->tempering.ladder_betas.size() ||
+            std::memcmp(a->tempering.ladder_betas.data(), b->tempering.ladder_betas.data(), a->tempering.ladder_betas.size() * sizeof(double)) != 0)
             return fail(ISINGMC_ERR_INVALID, "the two ladders differ in their betas: the replicas of a pair need equal betas");
         if (n_pairs != a->R) return fail(ISINGMC_ERR_INVALID, "without slot tables n_pairs must be the number of rungs");
     } else {
@@ -390,9 +390,9 @@ extern "C" int isingmc_icm_between(isingmc_states *a, isingmc_states *b, const u
             if (seen_a[slots_a[p]]++ || seen_b[slots_b[p]]++) return fail(ISINGMC_ERR_INVALID, "a duplicate slot: every replica belongs to at most one pair");
         }
         // per-replica betas set by the host are known here; a ladder relabels them on the device (the caller pairs equal rungs)
-        if (a->has_betas != b->has_betas && !a->pt_attached && !b->pt_attached)
+        if (a->has_betas != b->has_betas && !a->tempering.attached && !b->tempering.attached)
             return fail(ISINGMC_ERR_INVALID, "per-replica betas are set on one container only: the replicas of a pair need equal betas");
-        if (a->has_betas && b->has_betas && !a->pt_attached && !b->pt_attached)
+        if (a->has_betas && b->has_betas && !a->tempering.attached && !b->tempering.attached)
             for (size_t p = 0; p < n_pairs; p++)
                 if (std::memcmp(&a->betas[slots_a[p]], &b->betas[slots_b[p]], sizeof(double)) != 0)
                     return fail(ISINGMC_ERR_INVALID, "per-replica betas differ inside a pair: the two replicas of every pair need equal betas");
@@ -413,22 +413,22 @@ extern "C" int isingmc_icm_between(isingmc_states *a, isingmc_states *b, const u
     const size_t n_pos = g->pk.n_pos, items = a->packed ? (n_pairs + 31) / 32 : n_pairs;
     const size_t words = a->packed ? pk_between_words_per_block(n_pos) : cluster_words_per_replica(g->nvars);
     const size_t batch = workspace_batch(a, items, words);
-    if (!a->d_icmb_work || a->icmb_batch != batch) TRY(dev_regrow(a->stream, a->d_icmb_work, &a->icmb_batch, batch * words, batch));
+    if (!a->icmb.d_work || a->icmb.batch != batch) TRY(dev_regrow(a->stream, a->icmb.d_work, &a->icmb.batch, batch * words, batch));
     const size_t inv_words = 32 * (a->groups + b->groups); // packed: (local group, bit) -> pair, a's groups first
-    if (a->packed && a->icmb_inv_cap < inv_words) TRY(dev_regrow(a->stream, a->d_icmb_inv, &a->icmb_inv_cap, inv_words, inv_words));
+    if (a->packed && a->icmb.inv_cap < inv_words) TRY(dev_regrow(a->stream, a->icmb.d_inv, &a->icmb.inv_cap, inv_words, inv_words));
     const uint32_t *d_sa = nullptr, *d_sb = nullptr;
     TRY(between_prepare(a, b, slots_a, slots_b, n_pairs, &d_sa, &d_sb));
-    uint32_t *const stats = a->d_icmb_stats, *const minus = a->d_icmb_stats + 2 * a->icmb_cap;
+    uint32_t *const stats = a->icmb.d_stats, *const minus = a->icmb.d_stats + 2 * a->icmb.cap;
     if (a->packed) {
-        const PkBetweenWork work = pk_between_carve(a->d_icmb_work, batch, n_pos);
-        const PkBetweenSide A{{a->d_state, d_sa, uint32_t(a->pk_bit0), uint32_t(a->R)}, a->d_icmb_inv, uint32_t(a->groups)};
-        const PkBetweenSide B{{b->d_state, d_sb, uint32_t(b->pk_bit0), uint32_t(b->R)}, a->d_icmb_inv + 32 * a->groups, uint32_t(b->groups)};
+        const PkBetweenWork work = pk_between_carve(a->icmb.d_work, batch, n_pos);
+        const PkBetweenSide A{{a->d_state, d_sa, uint32_t(a->pk_bit0), uint32_t(a->R)}, a->icmb.d_inv, uint32_t(a->groups)};
+        const PkBetweenSide B{{b->d_state, d_sb, uint32_t(b->pk_bit0), uint32_t(b->R)}, a->icmb.d_inv + 32 * a->groups, uint32_t(b->groups)};
         HIP_TRY(pk_between_launch_tables(a->stream, A, B, uint32_t(n_pairs)));
         for (size_t b0 = 0; b0 < items; b0 += batch)
             HIP_TRY(pk_between_launch_batch(a->stream, A, B, g->pk, a->rj ? g->rj.nbr : nullptr, a->rj ? g->rj.slots : 0, a->t, a->d_keys, work, uint32_t(b0),
                                             uint32_t(std::min(batch, items - b0)), uint32_t(n_pairs), stats, minus));
     } else {
-        const ClusterWork cl = cluster_carve(a->d_icmb_work, batch, g->nvars);
+        const ClusterWork cl = cluster_carve(a->icmb.d_work, batch, g->nvars);
         for (size_t p0 = 0; p0 < items; p0 += batch)
             HIP_TRY(icm_between_launch_step(a->stream, a->d_state, b->d_state, d_sa + p0, d_sb + p0, g->geom, a->t, a->d_keys, cl,
                                             uint32_t(std::min(batch, items - p0)), stats + 2 * p0, minus + p0));
@@ -439,8 +439,8 @@ extern "C" int isingmc_icm_between(isingmc_states *a, isingmc_states *b, const u
 extern "C" int isingmc_icm_between_stats(isingmc_states *a, uint64_t *n_clusters_out, uint64_t *largest_out, uint64_t *minus_sites_out, size_t n_pairs)
 {
     if (!a || !n_clusters_out || !largest_out || !minus_sites_out) return fail(ISINGMC_ERR_INVALID, "NULL argument");
-    if (!a->icmb_have_stats) return fail(ISINGMC_ERR_INVALID, "no isoenergetic cluster move between containers has been called on this container yet");
-    if (n_pairs != a->icmb_pairs) return fail(ISINGMC_ERR_INVALID, "n_pairs differs from the number of pairs of the last move");
+    if (!a->icmb.have_stats) return fail(ISINGMC_ERR_INVALID, "no isoenergetic cluster move between containers has been called on this container yet");
+    if (n_pairs != a->icmb.pairs) return fail(ISINGMC_ERR_INVALID, "n_pairs differs from the number of pairs of the last move");
     TRY(use_device(a->g->device));
-    return read_pair_stats(a, a->d_icmb_stats, a->icmb_cap, 0, n_pairs, n_clusters_out, largest_out, minus_sites_out);
+    return read_pair_stats(a, a->icmb.d_stats, a->icmb.cap, 0, n_pairs, n_clusters_out, largest_out, minus_sites_out);
 }

@@ -39,9 +39,9 @@ static std::string obs_obstacle(const isingmc_states *a)
 // what ISINGMC_OBS_BY_RUNG asks of the container's ladder ("" when it serves), in the words of ISINGMC_MOMENTS_PER_RUNG
 static std::string obs_ladder_obstacle(const isingmc_states *a)
 {
-    if (!a->pt_attached)
+    if (!a->tempering.attached)
         return "a series by rung needs a tempering ladder: none is attached to this container (isingmc_pt_attach first, then make the series)";
-    if (a->pt_world != 1 || a->pt.slot_offset != 0 || a->pt.n_rungs != a->R)
+    if (a->tempering.world != 1 || a->pt.slot_offset != 0 || a->pt.n_rungs != a->R)
         return "a series by rung needs the whole ladder on this container (world size 1, one slot per rung): a shard of a larger ladder is not served";
     return "";
 }
@@ -142,7 +142,7 @@ static int obs_enqueue(isingmc_observable_series *S)
     if (obs_by_rung(S)) {
         const std::string why = obs_ladder_obstacle(a); // (the ladder may have been detached and attached again since)
         if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
-        d_perm = a->d_pt_perm;
+        d_perm = a->tempering.d_perm;
     }
     if (a->n_lanes > 1) TRY(lanes_join(a)); // the sweeps before this record may have run on replica lanes
     const size_t C = S->n_columns, slots = counter_slots(a);

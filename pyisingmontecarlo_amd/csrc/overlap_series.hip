@@ -19,7 +19,7 @@ struct isingmc_overlap_series : SeriesLog { // rows of [n_pairs][entries], read 
     DevBlock<uint32_t> d_words;                 // packed containers with tables: the gathered overlap words of one batch
     size_t acc_cap = 0, cacc_cap = 0, words_cap = 0;
     std::vector<std::vector<uint32_t>> uploads; // host tables that an enqueued copy may still read
-    hipEvent_t ev[2] = {nullptr, nullptr};      // b's stream has arrived / the record is enqueued
+    PooledEvent ev[2];                          // b's stream has arrived / the record is enqueued
 };
 
 static bool osr_link(const isingmc_overlap_series *S) { return (S->flags & ISINGMC_SERIES_LINK) != 0; }
@@ -29,13 +29,13 @@ static bool osr_by_rung(const isingmc_overlap_series *S) { return (S->flags & IS
 static std::string osr_ladders_obstacle(const isingmc_states *a, const isingmc_states *b, size_t n_pairs)
 {
     if (!b || a == b) return "ISINGMC_SERIES_BY_RUNG pairs the rungs of two ladders: it needs two different containers";
-    if (!a->pt_attached || !b->pt_attached) return "without slot tables both containers need an attached tempering ladder (isingmc_pt_attach)";
+    if (!a->tempering.attached || !b->tempering.attached) return "without slot tables both containers need an attached tempering ladder (isingmc_pt_attach)";
     for (const isingmc_states *s : {a, b})
-        if (s->pt_world != 1 || s->pt.slot_offset != 0 || s->pt.n_rungs != s->R)
+        if (s->tempering.world != 1 || s->pt.slot_offset != 0 || s->pt.n_rungs != s->R)
             return "without slot tables each ladder must live on its container alone (world size 1, one slot per rung): sharded ladders are not served";
     if (a->pt.n_rungs != b->pt.n_rungs) return "the two ladders differ in their number of rungs";
-    if (a->ladder_betas.size() != b->ladder_betas.size() ||
-        std::memcmp(a->ladder_betas.data(), b->ladder_betas.data(), a->ladder_betas.size() * sizeof(double)) != 0)
+    if (a->tempering.ladder_betas.size() != b->tempering.ladder_betas.size() ||
+        std::memcmp(a->tempering.ladder_betas.data(), b->tempering.ladder_betas.data(), a->tempering.ladder_betas.size() * sizeof(double)) != 0)
         return "the two ladders differ in their betas: the replicas of a pair need equal betas";
     if (n_pairs != a->R) return "without slot tables n_pairs must be the number of rungs";
     return "";
@@ -83,7 +83,7 @@ extern "C" int isingmc_overlap_series_create(isingmc_states *a, isingmc_states *
     if (classes) sizes.insert(sizes.end(), classes->sizes.begin(), classes->sizes.end());
     TRY(dev_alloc(S->d_sizes, sizes.size()));
     HIP_TRY(hipMemcpy(S->d_sizes, sizes.data(), sizes.size() * sizeof(unsigned long long), hipMemcpyHostToDevice)); // once: waited for here
-    for (hipEvent_t &ev : S->ev) HIP_TRY(pooled_event_create(&ev, true));
+    for (PooledEvent &ev : S->ev) TRY(event_create(ev));
     if (osr_by_rung(S.get()))
         for (isingmc_states *s : {S->a, S->b}) s->osr_by_rung_live++;
     *out = S.release();
@@ -96,7 +96,6 @@ extern "C" int isingmc_overlap_series_destroy(isingmc_overlap_series *S)
     series_unregister(S);
     if (osr_by_rung(S))
         for (isingmc_states *s : {S->a, S->b}) s->osr_by_rung_live--;
-    for (hipEvent_t ev : S->ev) pooled_event_destroy(ev, true);
     delete S;
     return ISINGMC_OK;
 }
@@ -153,8 +152,8 @@ extern "C" int isingmc_overlap_series_record(isingmc_overlap_series *S, const ui
         if (slots_a || slots_b) return fail(ISINGMC_ERR_INVALID, "a series made with ISINGMC_SERIES_BY_RUNG takes no slot tables: its pairs are the rungs of the two ladders");
         const std::string why = osr_ladders_obstacle(a, b, n_pairs); // (a ladder may have been detached and attached again since)
         if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
-        d_sa = a->d_pt_perm;
-        d_sb = b->d_pt_perm;
+        d_sa = a->tempering.d_perm;
+        d_sb = b->tempering.d_perm;
     } else {
         TRY(overlap_pairing(a, b, slots_a, slots_b, n_pairs, P));
     }

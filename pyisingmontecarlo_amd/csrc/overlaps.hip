@@ -150,8 +150,8 @@ int overlap_class_enqueue(const OverlapJob &J, const OverlapPlan &P, const Overl
 static int overlap_order_after(isingmc_states *a, isingmc_states *b)
 {
     if (a == b) return ISINGMC_OK;
-    if (!a->icmb_ev[0]) HIP_TRY(pooled_event_create(&a->icmb_ev[0], true));
-    return stream_wait_for(a->stream, b->stream, a->icmb_ev[0]);
+    if (!a->icmb.ev[0]) TRY(event_create(a->icmb.ev[0]));
+    return stream_wait_for(a->stream, b->stream, a->icmb.ev[0]);
 }
 
 // the host tables of the pairing as the job's device tables (they live as long as the call, which waits for the device before it returns)

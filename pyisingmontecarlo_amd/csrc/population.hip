@@ -12,7 +12,7 @@ static std::string pa_obstacle(const isingmc_states *s)
     if (!s->packed && g->mc_mode != MC_NONE)
         return "population annealing needs the device-side energy array, which lattices with fields, open boundaries or anisotropic "
                "couplings do not have";
-    if (s->pt_attached) return "a tempering ladder is attached to this container: a population shares one beta";
+    if (s->tempering.attached) return "a tempering ladder is attached to this container: a population shares one beta";
     if (s->has_betas) return "per-replica betas are set for this container: a population shares one beta";
     if (s->first != 0 || s->first + s->R < s->n_total) return "this container is a shard of a larger set of experiments: one population lives in one container";
     if (s->R == 0) return "the container holds no replica";
@@ -26,28 +26,28 @@ static size_t pa_state_size(const isingmc_states *s) { return s->packed ? s->gro
 static int pa_reserve(isingmc_states *s)
 {
     const size_t words = pa_state_size(s);
-    if (s->d_pa_state && s->pa_state_words == words && s->pa_cap >= s->R) return ISINGMC_OK;
+    if (s->pa.d_state && s->pa.state_words == words && s->pa.cap >= s->R) return ISINGMC_OK;
     HIP_TRY(stream_quiesce(s->stream)); // recycled blocks: nothing enqueued may still use the old ones
     std::vector<uint32_t> family(s->R);
     for (size_t r = 0; r < s->R; r++) family[r] = uint32_t(r);
-    if (s->pa_families_set && s->pa_cap) // a container that grew keeps its families; the new slots found their own
-        HIP_TRY(hipMemcpy(family.data(), s->d_pa_family, std::min(s->pa_cap, s->R) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    s->d_pa_state.reset(); s->d_pa_energy.reset(); s->d_pa_cum.reset(); s->d_pa_src.reset();
-    s->d_pa_user_src.reset(); s->d_pa_family.reset(); s->d_pa_family2.reset();
-    s->pa_cap = s->pa_state_words = 0;
-    s->pa_families_set = false;
-    TRY(dev_alloc(s->d_pa_state, words));
-    TRY(dev_alloc(s->d_pa_energy, s->R));
-    TRY(dev_alloc(s->d_pa_cum, s->R + pa_scan_blocks(s->R)));
-    TRY(dev_alloc(s->d_pa_src, s->R));
-    TRY(dev_alloc(s->d_pa_user_src, s->R));
-    TRY(dev_alloc(s->d_pa_family, s->R));
-    TRY(dev_alloc(s->d_pa_family2, s->R));
-    if (!s->d_pa_record) TRY(dev_alloc(s->d_pa_record, 1));
-    HIP_TRY(hipMemcpy(s->d_pa_family, family.data(), s->R * sizeof(uint32_t), hipMemcpyHostToDevice));
-    s->pa_state_words = words;
-    s->pa_cap = s->R;
-    s->pa_families_set = true;
+    if (s->pa.families_set && s->pa.cap) // a container that grew keeps its families; the new slots found their own
+        HIP_TRY(hipMemcpy(family.data(), s->pa.d_family, std::min(s->pa.cap, s->R) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    s->pa.d_state.reset(); s->pa.d_energy.reset(); s->pa.d_cum.reset(); s->pa.d_src.reset();
+    s->pa.d_user_src.reset(); s->pa.d_family.reset(); s->pa.d_family2.reset();
+    s->pa.cap = s->pa.state_words = 0;
+    s->pa.families_set = false;
+    TRY(dev_alloc(s->pa.d_state, words));
+    TRY(dev_alloc(s->pa.d_energy, s->R));
+    TRY(dev_alloc(s->pa.d_cum, s->R + pa_scan_blocks(s->R)));
+    TRY(dev_alloc(s->pa.d_src, s->R));
+    TRY(dev_alloc(s->pa.d_user_src, s->R));
+    TRY(dev_alloc(s->pa.d_family, s->R));
+    TRY(dev_alloc(s->pa.d_family2, s->R));
+    if (!s->pa.d_record) TRY(dev_alloc(s->pa.d_record, 1));
+    HIP_TRY(hipMemcpy(s->pa.d_family, family.data(), s->R * sizeof(uint32_t), hipMemcpyHostToDevice));
+    s->pa.state_words = words;
+    s->pa.cap = s->R;
+    s->pa.families_set = true;
     return ISINGMC_OK;
 }
 
@@ -57,17 +57,17 @@ static int pa_gather(isingmc_states *s, const uint32_t *d_src)
 {
     const isingmc_graph *g = s->g;
     if (s->packed) // pk_bit0 == 0: a shard is refused
-        HIP_TRY(pa_launch_bit_gather(s->stream, s->d_state, s->d_pa_state, d_src, uint32_t(s->R), s->groups, g->pk.n_pos, g->pk.site));
+        HIP_TRY(pa_launch_bit_gather(s->stream, s->d_state, s->pa.d_state, d_src, uint32_t(s->R), s->groups, g->pk.n_pos, g->pk.site));
     else
-        HIP_TRY(pa_launch_row_gather(s->stream, s->d_state, s->d_pa_state, d_src, s->R, g->state_words));
-    HIP_TRY(pa_launch_gather_u32(s->stream, s->d_pa_family, d_src, uint32_t(s->R), s->d_pa_family2));
-    std::swap(s->d_state, s->d_pa_state); // every launch reads the pointer when it is enqueued: the stream orders the rest
-    std::swap(s->d_pa_family, s->d_pa_family2);
+        HIP_TRY(pa_launch_row_gather(s->stream, s->d_state, s->pa.d_state, d_src, s->R, g->state_words));
+    HIP_TRY(pa_launch_gather_u32(s->stream, s->pa.d_family, d_src, uint32_t(s->R), s->pa.d_family2));
+    std::swap(s->d_state, s->pa.d_state); // every launch reads the pointer when it is enqueued: the stream orders the rest
+    std::swap(s->pa.d_family, s->pa.d_family2);
     s->meas_fresh = false; // energies a strip launch left for the next tempering measurement
     // (the strip path's snapshot is taken anew by every synchronous call: nothing to drop)
-    if (s->d_halo) { // halo rows the strips exchanged: the state a fresh allocation starts from
-        HIP_TRY(hipMemsetAsync(s->d_halo, 0, s->halo_cap * sizeof(unsigned long long), s->stream));
-        s->strip_epoch = 0;
+    if (s->strip.d_halo) { // halo rows the strips exchanged: the state a fresh allocation starts from
+        HIP_TRY(hipMemsetAsync(s->strip.d_halo, 0, s->strip.halo_cap * sizeof(unsigned long long), s->stream));
+        s->strip.epoch = 0;
     }
     return ISINGMC_OK;
 }
@@ -76,13 +76,13 @@ static int pa_gather(isingmc_states *s, const uint32_t *d_src)
 static int pa_resample_enqueue(isingmc_states *s, double dbeta, uint64_t seed, uint64_t step, PaRecord *d_rec)
 {
     const uint32_t R = uint32_t(s->R);
-    TRY(energies_enqueue(s, s->d_pa_energy));
+    TRY(energies_enqueue(s, s->pa.d_energy));
     // minimum tracking: the records see the population before the gather; they stay with the slots
-    if (s->rec[REC_BEST].every) TRY(best_from_energies(s, s->d_pa_energy));
-    HIP_TRY(pa_launch_weights(s->stream, s->d_pa_energy, R, dbeta, seed, step, s->d_pa_cum, d_rec));
-    HIP_TRY(pa_launch_scan(s->stream, s->d_pa_cum, R, s->d_pa_cum + R));
-    HIP_TRY(pa_launch_sources(s->stream, s->d_pa_cum, R, d_rec, s->d_pa_src));
-    return pa_gather(s, s->d_pa_src);
+    if (s->rec[REC_BEST].every) TRY(best_from_energies(s, s->pa.d_energy));
+    HIP_TRY(pa_launch_weights(s->stream, s->pa.d_energy, R, dbeta, seed, step, s->pa.d_cum, d_rec));
+    HIP_TRY(pa_launch_scan(s->stream, s->pa.d_cum, R, s->pa.d_cum + R));
+    HIP_TRY(pa_launch_sources(s->stream, s->pa.d_cum, R, d_rec, s->pa.d_src));
+    return pa_gather(s, s->pa.d_src);
 }
 
 extern "C" int isingmc_pa_resample(isingmc_states *s, double dbeta, uint64_t seed, uint64_t step)
@@ -96,8 +96,8 @@ extern "C" int isingmc_pa_resample(isingmc_states *s, double dbeta, uint64_t see
     if (const char *why = recorders_refusal(s, RecorderRefusal::Resample)) return fail(ISINGMC_ERR_INVALID, why);
     TRY(use_device(s->g->device));
     TRY(pa_reserve(s));
-    TRY(pa_resample_enqueue(s, dbeta, seed, step, s->d_pa_record));
-    s->pa_have_record = true;
+    TRY(pa_resample_enqueue(s, dbeta, seed, step, s->pa.d_record));
+    s->pa.have_record = true;
     return ISINGMC_OK;
 }
 
@@ -134,8 +134,8 @@ extern "C" int isingmc_pa_run(isingmc_states *s, const double *betas, size_t n_b
     }
     if (rc == ISINGMC_OK && s->rec[REC_BEST].every) rc = best_update_enqueue(s); // the final population
     if (rc == ISINGMC_OK && n_steps) {
-        HIP_TRY(hipMemcpyAsync(s->d_pa_record, d_log + (n_steps - 1), sizeof(PaRecord), hipMemcpyDeviceToDevice, s->stream));
-        s->pa_have_record = true;
+        HIP_TRY(hipMemcpyAsync(s->pa.d_record, d_log + (n_steps - 1), sizeof(PaRecord), hipMemcpyDeviceToDevice, s->stream));
+        s->pa.have_record = true;
     }
     HIP_TRY(hipStreamSynchronize(s->stream));
     TRY(strip_error(strip_check(s)));
@@ -155,11 +155,11 @@ extern "C" int isingmc_pa_run(isingmc_states *s, const double *betas, size_t n_b
 // measure into the chooser's own array, search, wait for the decision: nothing a resampling or a sweep keeps is written
 static int pa_choose(isingmc_states *s, double dbeta_max, double target, PaChoose *out)
 {
-    if (!s->d_pac) TRY(dev_alloc(s->d_pac, 1));
-    if (s->pac_cap < s->R) TRY(dev_regrow(s->stream, s->d_pac_energy, &s->pac_cap, s->R, s->R));
-    TRY(energies_enqueue(s, s->d_pac_energy));
-    HIP_TRY(pa_launch_choose(s->stream, s->d_pac_energy, uint32_t(s->R), std::ldexp(dbeta_max, -16), pa_target32(target), s->d_pac));
-    HIP_TRY(hipMemcpyAsync(out, s->d_pac, sizeof(PaChoose), hipMemcpyDeviceToHost, s->stream));
+    if (!s->pac.d_choose) TRY(dev_alloc(s->pac.d_choose, 1));
+    if (s->pac.cap < s->R) TRY(dev_regrow(s->stream, s->pac.d_energy, &s->pac.cap, s->R, s->R));
+    TRY(energies_enqueue(s, s->pac.d_energy));
+    HIP_TRY(pa_launch_choose(s->stream, s->pac.d_energy, uint32_t(s->R), std::ldexp(dbeta_max, -16), pa_target32(target), s->pac.d_choose));
+    HIP_TRY(hipMemcpyAsync(out, s->pac.d_choose, sizeof(PaChoose), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return strip_error(strip_check(s));
 }
@@ -218,7 +218,7 @@ extern "C" int isingmc_pa_run_adaptive(isingmc_states *s, double beta_start, dou
     // the record of the resampling before the sweeps in flight: read when the stream has drained
     const auto read_record = [&](size_t step) {
         PaRecord rec;
-        HIP_TRY(hipMemcpy(&rec, s->d_pa_record, sizeof rec, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&rec, s->pa.d_record, sizeof rec, hipMemcpyDeviceToHost));
         if (sum_out) sum_out[step] = rec.sum;
         if (eref_out) eref_out[step] = rec.eref;
         if (distinct_out) distinct_out[step] = rec.distinct;
@@ -243,9 +243,9 @@ extern "C" int isingmc_pa_run_adaptive(isingmc_states *s, double beta_start, dou
         const bool reaches = !(dbeta_cap < beta_end - beta) || beta + dbeta_max >= beta_end;
         beta = c.k == PA_CHOOSE_GRID && reaches ? beta_end : beta + dbeta;
         steps++;
-        rc = pa_resample_enqueue(s, dbeta, seed, steps, s->d_pa_record);
+        rc = pa_resample_enqueue(s, dbeta, seed, steps, s->pa.d_record);
         if (rc != ISINGMC_OK) break;
-        s->pa_have_record = true;
+        s->pa.have_record = true;
         betas_out[steps] = beta;
         rc = sweep(beta);
     }
@@ -273,8 +273,8 @@ extern "C" int isingmc_pa_apply_sources(isingmc_states *s, const uint32_t *src)
         if (src[j] >= s->R) return fail(ISINGMC_ERR_INVALID, "source table entry " + std::to_string(j) + " is not a replica of this container");
     TRY(use_device(s->g->device));
     TRY(pa_reserve(s));
-    HIP_TRY(hipMemcpyAsync(s->d_pa_user_src, src, s->R * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
-    TRY(pa_gather(s, s->d_pa_user_src));
+    HIP_TRY(hipMemcpyAsync(s->pa.d_user_src, src, s->R * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+    TRY(pa_gather(s, s->pa.d_user_src));
     HIP_TRY(hipStreamSynchronize(s->stream)); // the caller's table is free again
     return strip_error(strip_check(s));
 }
@@ -283,13 +283,13 @@ extern "C" int isingmc_pa_last(isingmc_states *s, uint32_t *src_out, uint64_t *s
                                double *mean_energy_out)
 {
     if (!s) return fail(ISINGMC_ERR_INVALID, "NULL states");
-    if (!s->pa_have_record) return fail(ISINGMC_ERR_INVALID, "no resampling has been run on this container (isingmc_pa_resample)");
+    if (!s->pa.have_record) return fail(ISINGMC_ERR_INVALID, "no resampling has been run on this container (isingmc_pa_resample)");
     TRY(use_device(s->g->device));
     HIP_TRY(hipStreamSynchronize(s->stream));
     TRY(strip_error(strip_check(s)));
     PaRecord rec;
-    HIP_TRY(hipMemcpy(&rec, s->d_pa_record, sizeof rec, hipMemcpyDeviceToHost));
-    if (src_out) HIP_TRY(hipMemcpy(src_out, s->d_pa_src, std::min(s->R, s->pa_cap) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&rec, s->pa.d_record, sizeof rec, hipMemcpyDeviceToHost));
+    if (src_out) HIP_TRY(hipMemcpy(src_out, s->pa.d_src, std::min(s->R, s->pa.cap) * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (sum_out) *sum_out = rec.sum;
     if (eref_out) *eref_out = rec.eref;
     if (distinct_out) *distinct_out = rec.distinct;
@@ -304,7 +304,7 @@ extern "C" int isingmc_pa_families(isingmc_states *s, uint32_t *family_out)
     HIP_TRY(hipStreamSynchronize(s->stream));
     TRY(strip_error(strip_check(s)));
     for (size_t r = 0; r < s->R; r++) family_out[r] = uint32_t(r); // slots no resampling has touched found their own family
-    if (s->pa_families_set) HIP_TRY(hipMemcpy(family_out, s->d_pa_family, std::min(s->R, s->pa_cap) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (s->pa.families_set) HIP_TRY(hipMemcpy(family_out, s->pa.d_family, std::min(s->R, s->pa.cap) * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return ISINGMC_OK;
 }
 
@@ -315,11 +315,11 @@ extern "C" int isingmc_pa_reset_families(isingmc_states *s)
         const std::string why = pa_obstacle(s);
         if (!why.empty()) return fail(ISINGMC_ERR_INVALID, why);
     }
-    if (!s->pa_families_set) return ISINGMC_OK;
+    if (!s->pa.families_set) return ISINGMC_OK;
     TRY(use_device(s->g->device));
     HIP_TRY(hipStreamSynchronize(s->stream));
-    std::vector<uint32_t> family(s->pa_cap);
+    std::vector<uint32_t> family(s->pa.cap);
     for (size_t r = 0; r < family.size(); r++) family[r] = uint32_t(r);
-    HIP_TRY(hipMemcpy(s->d_pa_family, family.data(), family.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->pa.d_family, family.data(), family.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     return ISINGMC_OK;
 }

@@ -36,7 +36,7 @@ int recorders_sample(isingmc_states *s, bool after_strip, int &rc)
     for (int i = 0; i < REC_COUNT; i++) {
         Periodic &p = s->rec[i];
         if (rc != ISINGMC_OK || !p.due(s->t)) continue;
-        if (s->strip_guard && after_strip) {
+        if (s->strip.guard && after_strip) {
             HIP_TRY(hipStreamSynchronize(s->stream));
             rc = strip_check(s);
         }

@@ -24,21 +24,21 @@ int expand_states(isingmc_states *s, const uint32_t *d_words, uint8_t *states_ou
     const size_t n_slabs = (s->R + slab - 1) / slab;
     TRY(sampling_reserve(s, slab * g->state_words, 0, 0));
     madvise_hugepages(states_out, s->R * replica_stride_bytes);
-    HIP_TRY(hipEventRecord(s->sample_ready[0], s->stream)); // everything queued on the engine's stream comes first
-    HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->sample_ready[0], 0));
+    HIP_TRY(hipEventRecord(s->sampling.ready[0], s->stream)); // everything queued on the engine's stream comes first
+    HIP_TRY(hipStreamWaitEvent(s->sampling.copy_stream, s->sampling.ready[0], 0));
     const auto copy_slab = [&](size_t j) {
         const size_t r0 = j * slab, n = std::min(slab, s->R - r0);
-        HIP_TRY(hipMemcpyAsync(s->h_samples[j & 1], d_words + r0 * g->state_words, n * g->state_words * sizeof(uint32_t),
-                               hipMemcpyDeviceToHost, s->copy_stream));
-        HIP_TRY(hipEventRecord(s->sample_copied[j & 1], s->copy_stream));
+        HIP_TRY(hipMemcpyAsync(s->sampling.h_samples[j & 1], d_words + r0 * g->state_words, n * g->state_words * sizeof(uint32_t),
+                               hipMemcpyDeviceToHost, s->sampling.copy_stream));
+        HIP_TRY(hipEventRecord(s->sampling.copied[j & 1], s->sampling.copy_stream));
         return int(ISINGMC_OK);
     };
     TRY(copy_slab(0));
     for (size_t j = 0; j < n_slabs; j++) {
-        HIP_TRY(hipEventSynchronize(s->sample_copied[j & 1]));
+        HIP_TRY(hipEventSynchronize(s->sampling.copied[j & 1]));
         if (j + 1 < n_slabs) TRY(copy_slab(j + 1)); // into the other buffer, which slab j-1's expansion has released
         const size_t r0 = j * slab, n = std::min(slab, s->R - r0);
-        const uint32_t *words = s->h_samples[j & 1];
+        const uint32_t *words = s->sampling.h_samples[j & 1];
         parallel_for(n, [&](size_t i) { unpack_state(g, words + i * g->state_words, states_out + (r0 + i) * replica_stride_bytes); }, g->nvars);
     }
     return ISINGMC_OK;
@@ -65,30 +65,30 @@ static int regrow(DevBlock<T> &dev, PinnedBlock<T> &host, size_t count)
 
 static int sampling_reserve(isingmc_states *s, size_t words, size_t counts, size_t energies)
 {
-    if (!s->copy_stream) HIP_TRY(pooled_stream_create(&s->copy_stream));
+    if (!s->sampling.copy_stream) TRY(stream_create(s->sampling.copy_stream));
     HIP_TRY(stream_quiesce(s->stream)); // buffers regrown below go through the block caches
-    HIP_TRY(stream_quiesce(s->copy_stream));
+    HIP_TRY(stream_quiesce(s->sampling.copy_stream));
     for (int b = 0; b < 2; b++) {
-        if (!s->sample_ready[b]) HIP_TRY(pooled_event_create(&s->sample_ready[b], true));
-        if (!s->sample_copied[b]) HIP_TRY(pooled_event_create(&s->sample_copied[b], true));
+        if (!s->sampling.ready[b]) TRY(event_create(s->sampling.ready[b]));
+        if (!s->sampling.copied[b]) TRY(event_create(s->sampling.copied[b]));
     }
-    HIP_TRY(hipStreamSynchronize(s->copy_stream));
-    if (words > s->sample_cap_words) {
-        s->sample_cap_words = 0;
-        for (int b = 0; b < 2; b++) TRY(regrow(s->d_samples[b], s->h_samples[b], words));
-        s->sample_cap_words = words;
+    HIP_TRY(hipStreamSynchronize(s->sampling.copy_stream));
+    if (words > s->sampling.cap_words) {
+        s->sampling.cap_words = 0;
+        for (int b = 0; b < 2; b++) TRY(regrow(s->sampling.d_samples[b], s->sampling.h_samples[b], words));
+        s->sampling.cap_words = words;
     }
-    if (counts > s->sample_cap_counts) {
-        s->sample_cap_counts = 0;
-        for (int b = 0; b < 2; b++) TRY(regrow(s->d_sample_counts[b], s->h_counts[b], counts));
-        s->sample_cap_counts = counts;
+    if (counts > s->sampling.cap_counts) {
+        s->sampling.cap_counts = 0;
+        for (int b = 0; b < 2; b++) TRY(regrow(s->sampling.d_counts[b], s->sampling.h_counts[b], counts));
+        s->sampling.cap_counts = counts;
     }
-    if (energies > s->sample_cap_e) {
-        s->sample_cap_e = 0;
-        for (int b = 0; b < 2; b++) TRY(regrow(s->d_sample_e[b], s->h_e[b], energies));
-        s->d_sample_m.reset();
-        TRY(dev_alloc(s->d_sample_m, energies));
-        s->sample_cap_e = energies;
+    if (energies > s->sampling.cap_e) {
+        s->sampling.cap_e = 0;
+        for (int b = 0; b < 2; b++) TRY(regrow(s->sampling.d_e[b], s->sampling.h_e[b], energies));
+        s->sampling.d_m.reset();
+        TRY(dev_alloc(s->sampling.d_m, energies));
+        s->sampling.cap_e = energies;
     }
     return ISINGMC_OK;
 }
@@ -160,9 +160,9 @@ static int run_sampling_impl(isingmc_states *s, double beta, size_t thermalizati
     madvise_hugepages(states_out, R * S * N);
     const auto unpack_slab = [&](size_t j) {
         const size_t k0 = j * slab, nk = std::min(slab, S - k0), b = j & 1;
-        const uint32_t *h_samples = s->h_samples[b];
-        const unsigned long long *h_counts = s->h_counts[b];
-        const double *h_e = s->h_e[b];
+        const uint32_t *h_samples = s->sampling.h_samples[b];
+        const unsigned long long *h_counts = s->sampling.h_counts[b];
+        const double *h_e = s->sampling.h_e[b];
         parallel_for(nk * R, [&](size_t idx) {
             const size_t k = idx / R, r = idx % R;
             uint8_t *out = states_out + (r * S + k0 + k) * N;
@@ -183,22 +183,22 @@ static int run_sampling_impl(isingmc_states *s, double beta, size_t thermalizati
         // device slab b is free: its copy-out (slab j-2) was awaited before slab j-2 was expanded, in iteration j-1
         for (size_t k = 0; k < nk; k++) {
             TRY(run_steps(s, sampling_freq, nullptr, 0, nullptr, nullptr, /*sync=*/false));
-            HIP_TRY(hipMemcpyAsync(s->d_samples[b] + k * words, s->d_state, words * sizeof(uint32_t), hipMemcpyDeviceToDevice, s->stream));
-            TRY(measure_enqueue(s, counts ? s->d_sample_counts[b] + k * CS * 2 : nullptr, counts ? nullptr : s->d_sample_e[b] + k * R,
-                                counts ? nullptr : s->d_sample_m, /*want_up=*/false));
+            HIP_TRY(hipMemcpyAsync(s->sampling.d_samples[b] + k * words, s->d_state, words * sizeof(uint32_t), hipMemcpyDeviceToDevice, s->stream));
+            TRY(measure_enqueue(s, counts ? s->sampling.d_counts[b] + k * CS * 2 : nullptr, counts ? nullptr : s->sampling.d_e[b] + k * R,
+                                counts ? nullptr : s->sampling.d_m, /*want_up=*/false));
         }
-        HIP_TRY(hipEventRecord(s->sample_ready[b], s->stream));
-        HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->sample_ready[b], 0));
-        HIP_TRY(hipMemcpyAsync(s->h_samples[b], s->d_samples[b], nk * words * sizeof(uint32_t), hipMemcpyDeviceToHost, s->copy_stream));
-        if (counts) HIP_TRY(hipMemcpyAsync(s->h_counts[b], s->d_sample_counts[b], nk * CS * 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->copy_stream));
-        else HIP_TRY(hipMemcpyAsync(s->h_e[b], s->d_sample_e[b], nk * R * sizeof(double), hipMemcpyDeviceToHost, s->copy_stream));
-        HIP_TRY(hipEventRecord(s->sample_copied[b], s->copy_stream));
+        HIP_TRY(hipEventRecord(s->sampling.ready[b], s->stream));
+        HIP_TRY(hipStreamWaitEvent(s->sampling.copy_stream, s->sampling.ready[b], 0));
+        HIP_TRY(hipMemcpyAsync(s->sampling.h_samples[b], s->sampling.d_samples[b], nk * words * sizeof(uint32_t), hipMemcpyDeviceToHost, s->sampling.copy_stream));
+        if (counts) HIP_TRY(hipMemcpyAsync(s->sampling.h_counts[b], s->sampling.d_counts[b], nk * CS * 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->sampling.copy_stream));
+        else HIP_TRY(hipMemcpyAsync(s->sampling.h_e[b], s->sampling.d_e[b], nk * R * sizeof(double), hipMemcpyDeviceToHost, s->sampling.copy_stream));
+        HIP_TRY(hipEventRecord(s->sampling.copied[b], s->sampling.copy_stream));
         if (j >= 1) { // expand the previous slab while the device works on this one
-            HIP_TRY(hipEventSynchronize(s->sample_copied[1 - b]));
+            HIP_TRY(hipEventSynchronize(s->sampling.copied[1 - b]));
             unpack_slab(j - 1);
         }
     }
-    HIP_TRY(hipEventSynchronize(s->sample_copied[(n_slabs - 1) & 1]));
+    HIP_TRY(hipEventSynchronize(s->sampling.copied[(n_slabs - 1) & 1]));
     unpack_slab(n_slabs - 1);
     HIP_TRY(hipStreamSynchronize(s->stream));
     TRY(strip_check(s));

@@ -41,9 +41,9 @@ static int pt_after_swap(isingmc_states *s)
 // why this container cannot take an on-stream ladder of that geometry ("" when it can): no side effects
 static std::string pt_attach_obstacle(const isingmc_states *s, size_t n_rungs, size_t slot_offset, size_t slots_per_rank, size_t world_size)
 {
-    if (s->pt_attached) return "a ladder is already attached";
-    if (s->cluster_every) return "cluster updates are switched on for this container (isingmc_states_set_cluster_every): a tempering round has no cluster steps";
-    if (s->icm_every) return "isoenergetic cluster moves are switched on for this container (isingmc_states_set_icm_every): inside a ladder the pairs would have to follow the rung permutation";
+    if (s->tempering.attached) return "a ladder is already attached";
+    if (s->cl.every) return "cluster updates are switched on for this container (isingmc_states_set_cluster_every): a tempering round has no cluster steps";
+    if (s->icm.every) return "isoenergetic cluster moves are switched on for this container (isingmc_states_set_icm_every): inside a ladder the pairs would have to follow the rung permutation";
     if (s->series[REC_CLUSTERS]) return "a cluster series is live on this container (isingmc_cluster_series_create): a tempering round has no non-local steps of the container's own; destroy the series first";
     if (s->rec[REC_MOMENTS].every) return "moment sums are switched on for this container (isingmc_states_set_moments_every): inside a ladder a slot changes its temperature; attach the ladder first, then switch the sums per rung on (ISINGMC_MOMENTS_PER_RUNG)";
     const bool pk_ladder = s->packed && !s->rj;
@@ -72,7 +72,7 @@ extern "C" int isingmc_pt_can_attach(const isingmc_states *s, size_t n_rungs, si
 extern "C" int isingmc_pt_detach(isingmc_states *s)
 {
     if (!s) return fail(ISINGMC_ERR_INVALID, "NULL states");
-    if (!s->pt_attached) return ISINGMC_OK;
+    if (!s->tempering.attached) return ISINGMC_OK;
     if (s->rec[REC_MOMENTS].every)
         return fail(ISINGMC_ERR_INVALID, "sums per rung are switched on for this container (isingmc_states_set_moments_every): their samples read the ladder's "
                                          "permutation; switch accumulation off first");
@@ -85,16 +85,16 @@ extern "C" int isingmc_pt_detach(isingmc_states *s)
     TRY(use_device(s->g->device));
     HIP_TRY(hipStreamSynchronize(s->stream)); // enqueued rounds may still read the ladder
     TRY(strip_error(strip_check(s)));
-    s->d_pt_ladder.reset(); s->d_pt_local.reset(); s->d_pt_all.reset(); s->d_pt_ladder_thr.reset(); s->d_pt_perm.reset();
-    s->d_pt_counters.reset(); s->d_pt_mail.reset(); s->d_pt_round_counts.reset(); s->d_pt_perm2.reset();
-    s->d_pt_stats.reset(); // the ladder statistics go with the ladder: the next one starts clean and switched off
-    s->pt_stats_on = false;
-    s->pt_in_kernel_rounds = 0;
+    s->tempering.d_ladder.reset(); s->tempering.d_local.reset(); s->tempering.d_all.reset(); s->tempering.d_ladder_thr.reset(); s->tempering.d_perm.reset();
+    s->tempering.d_counters.reset(); s->strip.d_pt_mail.reset(); s->strip.d_pt_round_counts.reset(); s->strip.d_pt_perm2.reset();
+    s->tempering.d_stats.reset(); // the ladder statistics go with the ladder: the next one starts clean and switched off
+    s->tempering.stats_on = false;
+    s->tempering.in_kernel_rounds = 0;
     s->pt = PtDev{};
-    s->pt_attached = false;
+    s->tempering.attached = false;
     s->has_betas = false;
     s->betas.clear();
-    s->ladder_betas.clear();
+    s->tempering.ladder_betas.clear();
     s->meas_fresh = false;
     return ISINGMC_OK;
 }
@@ -113,18 +113,18 @@ extern "C" int isingmc_pt_attach(isingmc_states *s, const double *ladder_betas, 
     TRY(use_device(s->g->device));
     const isingmc_graph *g = s->g;
     const bool lattice = g->kind == ISINGMC_KIND_LATTICE2D;
-    TRY(dev_alloc(s->d_pt_ladder, n_rungs));
-    TRY(dev_alloc(s->d_pt_perm, n_rungs));
-    TRY(dev_alloc(s->d_pt_local, slots_per_rank));
-    TRY(dev_alloc(s->d_pt_all, slots_per_rank * world_size));
-    TRY(dev_alloc(s->d_pt_counters, 2));
+    TRY(dev_alloc(s->tempering.d_ladder, n_rungs));
+    TRY(dev_alloc(s->tempering.d_perm, n_rungs));
+    TRY(dev_alloc(s->tempering.d_local, slots_per_rank));
+    TRY(dev_alloc(s->tempering.d_all, slots_per_rank * world_size));
+    TRY(dev_alloc(s->tempering.d_counters, 2));
     std::vector<uint32_t> perm(n_rungs);
     for (size_t i = 0; i < n_rungs; i++) perm[i] = uint32_t(i);
-    HIP_TRY(hipMemcpy(s->d_pt_ladder, ladder_betas, n_rungs * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(s->d_pt_perm, perm.data(), n_rungs * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(s->d_pt_counters, 0, 2 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(s->d_pt_local, 0, slots_per_rank * sizeof(double)));
-    HIP_TRY(hipMemset(s->d_pt_all, 0, slots_per_rank * world_size * sizeof(double)));
+    HIP_TRY(hipMemcpy(s->tempering.d_ladder, ladder_betas, n_rungs * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->tempering.d_perm, perm.data(), n_rungs * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(s->tempering.d_counters, 0, 2 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemset(s->tempering.d_local, 0, slots_per_rank * sizeof(double)));
+    HIP_TRY(hipMemset(s->tempering.d_all, 0, slots_per_rank * world_size * sizeof(double)));
     if (rj_ladder) { // acceptance scales per rung (host arithmetic: the bits of isingmc_states_set_betas)
         std::vector<uint64_t> thr(n_rungs);
         for (size_t i = 0; i < n_rungs; i++) {
@@ -132,8 +132,8 @@ extern "C" int isingmc_pt_attach(isingmc_states *s, const double *ladder_betas, 
             rj_beta(ladder_betas[i], g->rj_k, &b.shift, &b.mant);
             std::memcpy(&thr[i], &b, sizeof b);
         }
-        TRY(dev_alloc(s->d_pt_ladder_thr, n_rungs));
-        HIP_TRY(hipMemcpy(s->d_pt_ladder_thr, thr.data(), thr.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+        TRY(dev_alloc(s->tempering.d_ladder_thr, n_rungs));
+        HIP_TRY(hipMemcpy(s->tempering.d_ladder_thr, thr.data(), thr.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
         if (!s->d_rj_betas) TRY(dev_alloc(s->d_rj_betas, 32 * s->groups));
         std::vector<RjBeta> init(32 * s->groups, RjBeta{31u, 0xFFFFFFFFu}); // bits this shard does not own: accept-all, nobody reads them
         HIP_TRY(hipMemcpy(s->d_rj_betas, init.data(), init.size() * sizeof(RjBeta), hipMemcpyHostToDevice));
@@ -142,8 +142,8 @@ extern "C" int isingmc_pt_attach(isingmc_states *s, const double *ladder_betas, 
         std::vector<uint64_t> thr(size_t(PK_MAX_DEG) * n_rungs);
         for (size_t i = 0; i < n_rungs; i++)
             for (uint32_t m = 1; m <= uint32_t(PK_MAX_DEG); m++) thr[i * PK_MAX_DEG + m - 1] = threshold_fixed(ladder_betas[i], 2.0 * g->jabs * double(m));
-        TRY(dev_alloc(s->d_pt_ladder_thr, thr.size()));
-        HIP_TRY(hipMemcpy(s->d_pt_ladder_thr, thr.data(), thr.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+        TRY(dev_alloc(s->tempering.d_ladder_thr, thr.size()));
+        HIP_TRY(hipMemcpy(s->tempering.d_ladder_thr, thr.data(), thr.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
         if (!s->d_pk_slot_thr) TRY(dev_alloc(s->d_pk_slot_thr, size_t(32) * s->groups * PK_MAX_DEG));
         HIP_TRY(hipMemset(s->d_pk_slot_thr, 0, size_t(32) * s->groups * PK_MAX_DEG * sizeof(unsigned long long)));
         if (!s->d_tab) TRY(dev_alloc(s->d_tab, s->groups * PK_TAB_WORDS));
@@ -155,17 +155,17 @@ extern "C" int isingmc_pt_attach(isingmc_states *s, const double *ladder_betas, 
             thr[2 * i] = t.T3;
             thr[2 * i + 1] = t.T4;
         }
-        TRY(dev_alloc(s->d_pt_ladder_thr, 2 * n_rungs));
-        HIP_TRY(hipMemcpy(s->d_pt_ladder_thr, thr.data(), thr.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+        TRY(dev_alloc(s->tempering.d_ladder_thr, 2 * n_rungs));
+        HIP_TRY(hipMemcpy(s->tempering.d_ladder_thr, thr.data(), thr.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
     }
-    s->pt = PtDev{s->d_pt_ladder, s->d_pt_ladder_thr, rj_ladder ? 1u : pk_ladder ? uint32_t(PK_MAX_DEG) : 2u, s->d_pt_perm, s->d_pt_all, s->d_pt_counters, uint32_t(n_rungs),
+    s->pt = PtDev{s->tempering.d_ladder, s->tempering.d_ladder_thr, rj_ladder ? 1u : pk_ladder ? uint32_t(PK_MAX_DEG) : 2u, s->tempering.d_perm, s->tempering.d_all, s->tempering.d_counters, uint32_t(n_rungs),
                   uint32_t(slot_offset), uint32_t(s->R), uint32_t(seed), uint32_t(seed >> 32), /*stats=*/nullptr};
-    s->pt_per = slots_per_rank;
-    s->pt_world = world_size;
-    s->ladder_betas.assign(ladder_betas, ladder_betas + n_rungs);
+    s->tempering.per = slots_per_rank;
+    s->tempering.world = world_size;
+    s->tempering.ladder_betas.assign(ladder_betas, ladder_betas + n_rungs);
     s->betas.assign(s->R, 0.0);
     s->has_betas = true;
-    s->pt_attached = true;
+    s->tempering.attached = true;
     HIP_TRY(pt_launch_swap(s->stream, s->pt, pt_thr_local(s), s->packed ? nullptr : s->d_beta, /*apply_only=*/true));
     TRY(pt_after_swap(s));
     HIP_TRY(hipStreamSynchronize(s->stream));
@@ -174,19 +174,19 @@ extern "C" int isingmc_pt_attach(isingmc_states *s, const double *ladder_betas, 
 
 extern "C" int isingmc_pt_buffers(isingmc_states *s, void **d_local_out, void **d_all_out, size_t *per_rank_out)
 {
-    if (!s || !s->pt_attached) return fail(ISINGMC_ERR_INVALID, "no ladder attached");
-    if (d_local_out) *d_local_out = s->d_pt_local;
-    if (d_all_out) *d_all_out = s->d_pt_all;
-    if (per_rank_out) *per_rank_out = s->pt_per;
+    if (!s || !s->tempering.attached) return fail(ISINGMC_ERR_INVALID, "no ladder attached");
+    if (d_local_out) *d_local_out = s->tempering.d_local;
+    if (d_all_out) *d_all_out = s->tempering.d_all;
+    if (per_rank_out) *per_rank_out = s->tempering.per;
     return ISINGMC_OK;
 }
 
 extern "C" int isingmc_pt_time_steps(isingmc_states *s, size_t timesteps)
 {
-    if (!s || !s->pt_attached) return fail(ISINGMC_ERR_INVALID, "no ladder attached");
+    if (!s || !s->tempering.attached) return fail(ISINGMC_ERR_INVALID, "no ladder attached");
     // the strip kernel measures the final configurations itself: isingmc_pt_measure then needs no pass over the planes
     return run_steps(s, timesteps, nullptr, 0, nullptr, nullptr, /*sync=*/false,
-                     /*final_energies=*/s->pt_world == 1 ? s->d_pt_all + s->pt.slot_offset : s->d_pt_local);
+                     /*final_energies=*/s->tempering.world == 1 ? s->tempering.d_all + s->pt.slot_offset : s->tempering.d_local);
 }
 
 // The loop of tempering.rs:177-194 { timesteps(swap_every); parallel_tempering_step } for `timesteps` sweeps in ONE library
@@ -196,9 +196,9 @@ extern "C" int isingmc_pt_time_steps(isingmc_states *s, size_t timesteps)
 // all-gather and therefore keep calling isingmc_pt_time_steps / _measure / _swap themselves.
 extern "C" int isingmc_pt_run(isingmc_states *s, size_t timesteps, size_t swap_every)
 {
-    if (!s || !s->pt_attached) return fail(ISINGMC_ERR_INVALID, "no ladder attached");
+    if (!s || !s->tempering.attached) return fail(ISINGMC_ERR_INVALID, "no ladder attached");
     if (swap_every == 0) return fail(ISINGMC_ERR_INVALID, "swap_every must be positive");
-    if (s->pt_world != 1) return fail(ISINGMC_ERR_INVALID, "isingmc_pt_run is for a single rank: the all-gather of a sharded ladder sits between measure and swap");
+    if (s->tempering.world != 1) return fail(ISINGMC_ERR_INVALID, "isingmc_pt_run is for a single rank: the all-gather of a sharded ladder sits between measure and swap");
     TRY(recorders_room_or_fail(s, timesteps)); // a periodic series that would run full in the WHOLE call: no round is enqueued
     TRY(use_device(s->g->device));
     const isingmc_graph *g = s->g;
@@ -211,27 +211,27 @@ extern "C" int isingmc_pt_run(isingmc_states *s, size_t timesteps, size_t swap_e
                            !recorders_any_on(s);
     if (in_kernel) {
         const size_t R = s->R, nk = rounds * swap_every;
-        if (!s->d_pt_mail) {
-            TRY(dev_alloc(s->d_pt_mail, 4 * R));
-            TRY(dev_alloc(s->d_pt_round_counts, 2 * R));
-            TRY(dev_alloc(s->d_pt_perm2, R));
-            HIP_TRY(hipMemsetAsync(s->d_pt_mail, 0, 4 * R * sizeof(unsigned long long), s->stream));
-            HIP_TRY(hipMemsetAsync(s->d_pt_round_counts, 0, 2 * R * sizeof(unsigned long long), s->stream));
+        if (!s->strip.d_pt_mail) {
+            TRY(dev_alloc(s->strip.d_pt_mail, 4 * R));
+            TRY(dev_alloc(s->strip.d_pt_round_counts, 2 * R));
+            TRY(dev_alloc(s->strip.d_pt_perm2, R));
+            HIP_TRY(hipMemsetAsync(s->strip.d_pt_mail, 0, 4 * R * sizeof(unsigned long long), s->stream));
+            HIP_TRY(hipMemsetAsync(s->strip.d_pt_round_counts, 0, 2 * R * sizeof(unsigned long long), s->stream));
         }
         // the number of the first round is on the device (exchange rounds never synchronise with the host): read it once here
         unsigned long long c[2];
         HIP_TRY(hipStreamSynchronize(s->stream));
-        HIP_TRY(hipMemcpy(c, s->d_pt_counters, sizeof c, hipMemcpyDeviceToHost));
-        const StripLadder lad{s->d_pt_ladder, reinterpret_cast<const unsigned long long *>(s->d_pt_ladder_thr.get()), s->d_pt_perm, s->d_pt_perm2,
-                              s->d_pt_mail, s->d_pt_round_counts, s->d_pt_counters, c[0], uint32_t(R), uint32_t(swap_every), s->pt.seed_lo,
+        HIP_TRY(hipMemcpy(c, s->tempering.d_counters, sizeof c, hipMemcpyDeviceToHost));
+        const StripLadder lad{s->tempering.d_ladder, reinterpret_cast<const unsigned long long *>(s->tempering.d_ladder_thr.get()), s->tempering.d_perm, s->strip.d_pt_perm2,
+                              s->strip.d_pt_mail, s->strip.d_pt_round_counts, s->tempering.d_counters, c[0], uint32_t(R), uint32_t(swap_every), s->pt.seed_lo,
                               s->pt.seed_hi, g->jabs, 2ll * (long long)g->nvars, s->pt.stats};
         s->meas_fresh = false;
-        TRY(launch_strip(s, P, 0, R, nk, nullptr, 0, nullptr, s->d_pt_all + s->pt.slot_offset, &lad));
-        if (s->pt_stats_on) s->pt_in_kernel_rounds += rounds - 1; //  the launch's strips count these rounds themselves
-        s->strip_epoch += uint32_t(2 * nk);
+        TRY(launch_strip(s, P, 0, R, nk, nullptr, 0, nullptr, s->tempering.d_all + s->pt.slot_offset, &lad));
+        if (s->tempering.stats_on) s->tempering.in_kernel_rounds += rounds - 1; //  the launch's strips count these rounds themselves
+        s->strip.epoch += uint32_t(2 * nk);
         s->t += nk;
         s->meas_fresh = true; // the launch wrote the final energies
-        HIP_TRY(hipMemcpyAsync(s->d_pt_perm, s->d_pt_perm2, R * sizeof(uint32_t), hipMemcpyDeviceToDevice, s->stream));
+        HIP_TRY(hipMemcpyAsync(s->tempering.d_perm, s->strip.d_pt_perm2, R * sizeof(uint32_t), hipMemcpyDeviceToDevice, s->stream));
         TRY(isingmc_pt_measure(s));
         TRY(isingmc_pt_swap(s)); // the last round of the block, at the kernel boundary (it also relabels d_thr / d_beta)
     } else {
@@ -249,10 +249,10 @@ extern "C" int isingmc_pt_run(isingmc_states *s, size_t timesteps, size_t swap_e
 // buffer when there is a single rank)
 extern "C" int isingmc_pt_measure(isingmc_states *s)
 {
-    if (!s || !s->pt_attached) return fail(ISINGMC_ERR_INVALID, "no ladder attached");
+    if (!s || !s->tempering.attached) return fail(ISINGMC_ERR_INVALID, "no ladder attached");
     TRY(use_device(s->g->device));
     if (s->R == 0) return ISINGMC_OK;
-    double *d_out = s->pt_world == 1 ? s->d_pt_all + s->pt.slot_offset : s->d_pt_local;
+    double *d_out = s->tempering.world == 1 ? s->tempering.d_all + s->pt.slot_offset : s->tempering.d_local;
     if (s->g->kind == ISINGMC_KIND_LATTICE2D && s->meas_fresh) // the last strip launch of isingmc_pt_time_steps has already written these energies
         s->meas_fresh = false;
     else
@@ -293,7 +293,7 @@ int energies_enqueue(isingmc_states *s, double *d_out)
 // enqueue: one exchange round from the gathered energies; relabels the local slots
 extern "C" int isingmc_pt_swap(isingmc_states *s)
 {
-    if (!s || !s->pt_attached) return fail(ISINGMC_ERR_INVALID, "no ladder attached");
+    if (!s || !s->tempering.attached) return fail(ISINGMC_ERR_INVALID, "no ladder attached");
     TRY(use_device(s->g->device));
     HIP_TRY(pt_launch_swap(s->stream, s->pt, pt_thr_local(s), s->packed ? nullptr : s->d_beta, /*apply_only=*/false));
     return pt_after_swap(s);
@@ -304,21 +304,21 @@ extern "C" int isingmc_pt_swap(isingmc_states *s)
 // ------------------------------------------------------------------------------------------------
 static int pt_stats_zero(isingmc_states *s)
 {
-    HIP_TRY(hipMemsetAsync(s->d_pt_stats, 0, pt_stats_bytes(s->pt.n_rungs), s->stream));
-    s->pt_in_kernel_rounds = 0;
+    HIP_TRY(hipMemsetAsync(s->tempering.d_stats, 0, pt_stats_bytes(s->pt.n_rungs), s->stream));
+    s->tempering.in_kernel_rounds = 0;
     return ISINGMC_OK;
 }
 
 extern "C" int isingmc_pt_set_statistics(isingmc_states *s, int on)
 {
-    if (!s || !s->pt_attached) return fail(ISINGMC_ERR_INVALID, "no ladder attached");
+    if (!s || !s->tempering.attached) return fail(ISINGMC_ERR_INVALID, "no ladder attached");
     TRY(use_device(s->g->device));
-    if (on && !s->d_pt_stats) {
-        TRY(dev_alloc(s->d_pt_stats, pt_stats_bytes(s->pt.n_rungs) / sizeof(unsigned long long)));
+    if (on && !s->tempering.d_stats) {
+        TRY(dev_alloc(s->tempering.d_stats, pt_stats_bytes(s->pt.n_rungs) / sizeof(unsigned long long)));
         TRY(pt_stats_zero(s));
     }
-    s->pt_stats_on = on != 0;
-    s->pt.stats = on ? s->d_pt_stats.get() : nullptr; // a kernel argument: launches already enqueued keep what they were given
+    s->tempering.stats_on = on != 0;
+    s->pt.stats = on ? s->tempering.d_stats.get() : nullptr; // a kernel argument: launches already enqueued keep what they were given
     return ISINGMC_OK;
 }
 
@@ -326,18 +326,18 @@ extern "C" int isingmc_pt_statistics_get(isingmc_states *s, uint64_t *rounds_out
                                          uint64_t *accepts_out, uint64_t *n_up_out, uint64_t *n_down_out, double *sum_e_out,
                                          double *sum_e2_out, uint64_t *round_trips_out, uint8_t *labels_out)
 {
-    if (!s || !s->pt_attached) return fail(ISINGMC_ERR_INVALID, "no ladder attached");
-    if (!s->d_pt_stats) return fail(ISINGMC_ERR_INVALID, "this ladder holds no statistics: switch them on first (isingmc_pt_set_statistics)");
+    if (!s || !s->tempering.attached) return fail(ISINGMC_ERR_INVALID, "no ladder attached");
+    if (!s->tempering.d_stats) return fail(ISINGMC_ERR_INVALID, "this ladder holds no statistics: switch them on first (isingmc_pt_set_statistics)");
     TRY(use_device(s->g->device));
     HIP_TRY(hipStreamSynchronize(s->stream));
     TRY(strip_error(strip_check(s)));
     const uint32_t n = s->pt.n_rungs;
     std::vector<unsigned long long> h(pt_stats_bytes(n) / sizeof(unsigned long long));
-    HIP_TRY(hipMemcpy(h.data(), s->d_pt_stats, pt_stats_bytes(n), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h.data(), s->tempering.d_stats, pt_stats_bytes(n), hipMemcpyDeviceToHost));
     const PtStats S = pt_stats_view(h.data(), n);
     const size_t pairs = n ? n - 1 : 0;
     if (rounds_out) *rounds_out = *S.rounds;
-    if (in_kernel_rounds_out) *in_kernel_rounds_out = s->pt_in_kernel_rounds;
+    if (in_kernel_rounds_out) *in_kernel_rounds_out = s->tempering.in_kernel_rounds;
     if (attempts_out) std::copy(S.attempts, S.attempts + pairs, attempts_out);
     if (accepts_out) std::copy(S.accepts, S.accepts + pairs, accepts_out);
     if (n_up_out) std::copy(S.n_up, S.n_up + n, n_up_out);
@@ -351,8 +351,8 @@ extern "C" int isingmc_pt_statistics_get(isingmc_states *s, uint64_t *rounds_out
 
 extern "C" int isingmc_pt_statistics_reset(isingmc_states *s)
 {
-    if (!s || !s->pt_attached) return fail(ISINGMC_ERR_INVALID, "no ladder attached");
-    if (!s->d_pt_stats) return fail(ISINGMC_ERR_INVALID, "this ladder holds no statistics: switch them on first (isingmc_pt_set_statistics)");
+    if (!s || !s->tempering.attached) return fail(ISINGMC_ERR_INVALID, "no ladder attached");
+    if (!s->tempering.d_stats) return fail(ISINGMC_ERR_INVALID, "this ladder holds no statistics: switch them on first (isingmc_pt_set_statistics)");
     TRY(use_device(s->g->device));
     return pt_stats_zero(s); // on the stream: behind the rounds already enqueued
 }
@@ -360,13 +360,13 @@ extern "C" int isingmc_pt_statistics_reset(isingmc_states *s)
 // synchronises; perm_out: uint32[n_rungs] (rung -> slot)
 extern "C" int isingmc_pt_state(isingmc_states *s, uint32_t *perm_out, uint64_t *round_out, uint64_t *swaps_out)
 {
-    if (!s || !s->pt_attached) return fail(ISINGMC_ERR_INVALID, "no ladder attached");
+    if (!s || !s->tempering.attached) return fail(ISINGMC_ERR_INVALID, "no ladder attached");
     TRY(use_device(s->g->device));
     HIP_TRY(hipStreamSynchronize(s->stream));
     TRY(strip_error(strip_check(s)));
     unsigned long long c[2];
-    HIP_TRY(hipMemcpy(c, s->d_pt_counters, sizeof c, hipMemcpyDeviceToHost));
-    if (perm_out) HIP_TRY(hipMemcpy(perm_out, s->d_pt_perm, s->pt.n_rungs * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(c, s->tempering.d_counters, sizeof c, hipMemcpyDeviceToHost));
+    if (perm_out) HIP_TRY(hipMemcpy(perm_out, s->tempering.d_perm, s->pt.n_rungs * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (round_out) *round_out = c[0];
     if (swaps_out) *swaps_out = c[1];
     return ISINGMC_OK;
@@ -452,11 +452,11 @@ extern "C" int isingmc_pt_group_create(isingmc_states **shards, size_t n_shards,
     bool distinct = true;
     for (size_t k = 0; k < n_shards; k++) {
         const isingmc_states *s = shards[k];
-        if (!s || !s->pt_attached) return fail(ISINGMC_ERR_INVALID, "every shard needs an attached ladder (isingmc_pt_attach)");
-        if (s->pt_world != n_shards || s->pt_per != shards[0]->pt_per || s->pt.n_rungs != shards[0]->pt.n_rungs ||
+        if (!s || !s->tempering.attached) return fail(ISINGMC_ERR_INVALID, "every shard needs an attached ladder (isingmc_pt_attach)");
+        if (s->tempering.world != n_shards || s->tempering.per != shards[0]->tempering.per || s->pt.n_rungs != shards[0]->pt.n_rungs ||
             s->pt.seed_lo != shards[0]->pt.seed_lo || s->pt.seed_hi != shards[0]->pt.seed_hi)
             return fail(ISINGMC_ERR_INVALID, "the shards are not attached to one ladder (world size, slots per rank, rungs, seed)");
-        if (s->pt.slot_offset != offset || s->pt.slot_offset != k * s->pt_per)
+        if (s->pt.slot_offset != offset || s->pt.slot_offset != k * s->tempering.per)
             return fail(ISINGMC_ERR_INVALID, "shard k must own the slots from k * slots_per_rank on, in rank order");
         offset += s->R;
         for (int d : devices) distinct &= d != s->g->device;
@@ -465,7 +465,7 @@ extern "C" int isingmc_pt_group_create(isingmc_states **shards, size_t n_shards,
     if (offset != shards[0]->pt.n_rungs) return fail(ISINGMC_ERR_INVALID, "the shards do not cover the ladder");
     auto grp = std::make_unique<isingmc_pt_group>();
     grp->shards.assign(shards, shards + n_shards);
-    grp->per = shards[0]->pt_per;
+    grp->per = shards[0]->tempering.per;
     grp->measured.assign(n_shards, nullptr);
     for (size_t k = 0; k < n_shards; k++) {
         TRY(use_device(devices[k]));
@@ -504,7 +504,7 @@ extern "C" int isingmc_pt_group_allgather(isingmc_pt_group *grp)
                   // the collective below -- a real communicator of one rank: what a one-GPU box can execute of RCCL -- moves the same bytes
         isingmc_states *s = grp->shards[0];
         TRY(use_device(s->g->device));
-        HIP_TRY(hipMemcpyAsync(s->d_pt_local, s->d_pt_all, grp->per * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
+        HIP_TRY(hipMemcpyAsync(s->tempering.d_local, s->tempering.d_all, grp->per * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
     }
     if (!grp->comms.empty()) {
         int rc = rccl().GroupStart();
@@ -512,7 +512,7 @@ extern "C" int isingmc_pt_group_allgather(isingmc_pt_group *grp)
         for (size_t k = 0; k < n && rc == 0; k++) {
             isingmc_states *s = grp->shards[k];
             (void)hipSetDevice(s->g->device); // (the stream belongs to this communicator's device)
-            rc = rccl().AllGather(s->d_pt_local, s->d_pt_all, grp->per, RCCL_FLOAT64, grp->comms[k], s->stream);
+            rc = rccl().AllGather(s->tempering.d_local, s->tempering.d_all, grp->per, RCCL_FLOAT64, grp->comms[k], s->stream);
         }
         const int rc2 = rccl().GroupEnd();
         if (rc != 0) return rccl_fail(rc, "ncclAllGather");
@@ -529,7 +529,7 @@ extern "C" int isingmc_pt_group_allgather(isingmc_pt_group *grp)
         for (size_t j = 0; j < n; j++) {
             const isingmc_states *src = grp->shards[j];
             if (j != k) HIP_TRY(hipStreamWaitEvent(s->stream, grp->measured[j], 0));
-            HIP_TRY(hipMemcpyPeerAsync(s->d_pt_all + j * grp->per, s->g->device, src->d_pt_local, src->g->device, grp->per * sizeof(double), s->stream));
+            HIP_TRY(hipMemcpyPeerAsync(s->tempering.d_all + j * grp->per, s->g->device, src->tempering.d_local, src->g->device, grp->per * sizeof(double), s->stream));
         }
     }
     // a shard's `local` buffer is overwritten by its next measurement: that must wait for the copies the OTHER shards made of it

@@ -1,5 +1,5 @@
-// Stand-alone check of csrc/owned_block.hpp with a counting free function in place of the block caches (built with ASan + UBSan
-// by tests/test_owned_block_host.py).  The free function only counts, so that no address comes round twice; main deletes every
+// Stand-alone check of csrc/owned_block.hpp with counting free functions in place of the block caches and of the stream and
+// event pools (built with ASan + UBSan by tests/test_owned_block_host.py).  The free function only counts, so that no address comes round twice; main deletes every
 // block at the end: one that was never handed back is then the leak checker's finding as well.
 #include <cstdio>
 #include <map>
@@ -19,6 +19,29 @@ static void counting_free(void *p)
 using Block = OwnedBlock<int, counting_free>;
 static_assert(!std::is_copy_constructible<Block>::value && !std::is_copy_assignable<Block>::value, "move-only");
 static_assert(sizeof(Block) == sizeof(int *), "a handle is its pointer");
+
+// The pooled handles: this program is the pool.  A stream or an event is an opaque value here, the address of a tag that is
+// never read through; every release is counted per value and, for events, per kind.
+static std::map<const void *, int> g_released; // handle value -> times released
+static int g_stream_releases = 0, g_event_releases[2] = {0, 0}; // events: [timing disabled?]
+void pooled_stream_destroy(ihipStream_t *st)
+{
+    g_released[st]++;
+    g_stream_releases++;
+}
+void pooled_event_destroy(ihipEvent_t *ev, bool disable_timing)
+{
+    g_released[ev]++;
+    g_event_releases[disable_timing ? 1 : 0]++;
+}
+static char g_tags[16];
+static ihipStream_t *stream_value(int i) { return reinterpret_cast<ihipStream_t *>(&g_tags[i]); }
+static ihipEvent_t *event_value(int i) { return reinterpret_cast<ihipEvent_t *>(&g_tags[i]); }
+static_assert(!std::is_copy_constructible<PooledStream>::value && !std::is_copy_assignable<PooledStream>::value, "move-only");
+static_assert(!std::is_copy_constructible<PooledEvent>::value && !std::is_copy_assignable<TimedEvent>::value, "move-only");
+static_assert(!std::is_same<PooledEvent, TimedEvent>::value && !std::is_convertible<PooledEvent, TimedEvent>::value &&
+                  !std::is_assignable<TimedEvent &, PooledEvent>::value, "an event's kind is part of its type");
+static_assert(sizeof(PooledStream) == sizeof(void *) && sizeof(TimedEvent) == sizeof(void *), "a handle is its value");
 
 static int g_failures = 0;
 #define CHECK(cond)                                                                    \
@@ -42,6 +65,90 @@ static bool alloc_into(Block &out, int tag, bool succeed)
     if (!succeed) return false;
     out = Block(fresh(tag));
     return true;
+}
+
+static void pooled_handles()
+{
+    { // a default-constructed handle releases nothing, on destruction, on reset or when it is moved from
+        PooledStream s;
+        PooledEvent e;
+        TimedEvent t;
+        CHECK(s.get() == nullptr && !s && !e && !t);
+        s.reset();
+        PooledStream s2(std::move(s));
+        PooledEvent arr[2]; // as the members ev[2] of a container
+        CHECK(!arr[0] && !arr[1] && !s2);
+    }
+    CHECK(g_stream_releases == 0 && g_event_releases[0] == 0 && g_event_releases[1] == 0);
+
+    { // destruction releases once; the conversion reads as the raw handle does
+        PooledStream s(stream_value(0));
+        ihipStream_t *raw = s;
+        CHECK(raw == stream_value(0) && s.get() == raw && s == stream_value(0) && s);
+        CHECK(g_stream_releases == 0);
+    }
+    CHECK(g_stream_releases == 1 && g_released[stream_value(0)] == 1);
+
+    { // move construction: one release for the two handles
+        PooledStream src(stream_value(1));
+        PooledStream dst(std::move(src));
+        CHECK(!src && dst.get() == stream_value(1) && g_stream_releases == 1);
+    }
+    CHECK(g_stream_releases == 2 && g_released[stream_value(1)] == 1);
+
+    { // move assignment over a held value releases that value exactly once, at once, and empties the source
+        PooledStream src(stream_value(2)), dst(stream_value(3));
+        dst = std::move(src);
+        CHECK(g_stream_releases == 3 && g_released[stream_value(3)] == 1 && g_released.count(stream_value(2)) == 0);
+        CHECK(!src && dst.get() == stream_value(2));
+        PooledStream &self = dst;
+        dst = std::move(self); // onto itself: nothing happens
+        CHECK(dst.get() == stream_value(2) && g_stream_releases == 3);
+    }
+    CHECK(g_stream_releases == 4 && g_released[stream_value(2)] == 1 && g_released[stream_value(3)] == 1);
+
+    { // reset() twice releases once
+        PooledStream s(stream_value(4));
+        s.reset();
+        CHECK(g_stream_releases == 5 && !s);
+        s.reset();
+        CHECK(g_stream_releases == 5);
+    }
+    CHECK(g_stream_releases == 5 && g_released[stream_value(4)] == 1);
+
+    { // what the creation helpers do: the new value into a temporary, assigned over whatever the handle held
+        PooledEvent e;
+        e = PooledEvent(event_value(5));
+        CHECK(g_event_releases[1] == 0);
+        e = PooledEvent(event_value(6));
+        CHECK(g_event_releases[1] == 1 && g_released[event_value(5)] == 1 && e.get() == event_value(6));
+    }
+    CHECK(g_event_releases[1] == 2 && g_event_releases[0] == 0 && g_released[event_value(6)] == 1);
+
+    { // each kind of event reaches its own release: no timing event ends up in the other pool
+        TimedEvent t(event_value(7));
+        CHECK(g_event_releases[0] == 0);
+    }
+    CHECK(g_event_releases[0] == 1 && g_event_releases[1] == 2 && g_released[event_value(7)] == 1);
+    {
+        PooledEvent e(event_value(8));
+        TimedEvent t0(event_value(9)), t1(event_value(10));
+    }
+    CHECK(g_event_releases[0] == 3 && g_event_releases[1] == 3 && g_stream_releases == 5);
+
+    { // the lanes of a container: a vector of handles releases each element once, across its reallocations
+        std::vector<PooledStream> lanes;
+        for (int i = 11; i < 16; i++) {
+            PooledStream st(stream_value(i));
+            lanes.push_back(std::move(st));
+        }
+        CHECK(g_stream_releases == 5);
+        int seen = 0;
+        for (ihipStream_t *st : lanes) seen += st == stream_value(11 + seen) ? 1 : 0; // iterating by value copies no handle
+        CHECK(seen == 5 && g_stream_releases == 5);
+    }
+    CHECK(g_stream_releases == 10);
+    for (const auto &kv : g_released) CHECK(kv.second == 1);
 }
 
 int main()
@@ -137,6 +244,8 @@ int main()
         CHECK(kv.second == 1);
         delete[] static_cast<int *>(kv.first);
     }
+
+    pooled_handles();
 
     if (g_failures) return 1;
     std::printf("owned_block_host: ok, %d blocks freed once each\n", g_frees);

@@ -1,5 +1,5 @@
-"""The one owner of device and pinned blocks (csrc/owned_block.hpp), without a device: `tests/owned_block_host.cpp` drives the
-handle with a counting free function under AddressSanitizer + UndefinedBehaviorSanitizer, as an executable of its own; and the
+"""The one owner of device and pinned blocks, and of pooled streams and events (csrc/owned_block.hpp), without a device:
+`tests/owned_block_host.cpp` drives the handles with counting free functions under AddressSanitizer + UndefinedBehaviorSanitizer, as an executable of its own; and the
 host sources are read to see that nothing but the handle and the caches themselves hands a block back."""
 import os
 import re
@@ -39,6 +39,10 @@ def test_only_the_handle_frees_blocks():
     sources = dict(_host_sources())
     assert {"core.hip", "owned_block.hpp", "internal.hpp", "isingmc.hip", "tempering.hip"} <= set(sources)
     for call in ("cached_free(", "cached_host_free("):
+        users = {name for name, text in sources.items() if call in text}
+        assert users == {"core.hip", "owned_block.hpp"}, (call, sorted(users))
+    # ... and pooled streams and events go back through their handle alone
+    for call in ("pooled_stream_destroy(", "pooled_event_destroy("):
         users = {name for name, text in sources.items() if call in text}
         assert users == {"core.hip", "owned_block.hpp"}, (call, sorted(users))
     for name, text in sources.items():
