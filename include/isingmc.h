@@ -603,6 +603,54 @@ int isingmc_moments_reset(isingmc_states *states);
 int isingmc_run_sampling_moments(isingmc_states *states, double beta, size_t thermalization, size_t sampling_freq,
                                  size_t n_samples, unsigned flags, double *energies_out);
 
+/* ---- spin autocorrelation over time lags, measured on the device ("the lag ring"; the classical counterpart of
+ * lattice.rs:628 run_quantum_monte_carlo_and_measure_variable_autocorrelation) ----
+ * A lag ring of a container holds L = n_lags snapshots of its configurations in the state buffer's own layout and R x (L + 1) 64-bit
+ * sums.  Samples are numbered j = 0, 1, ... since creation or the last reset.  Sample j adds, for every replica r and every lag
+ * l = 1 .. min(j, L), D_r(l) = #{sites i : s_i(now) != s_i(at sample j - l)} to diff[r][l], and then stores the current
+ * configuration as snapshot j mod L (the slot that held lag L, the oldest).  diff[r][0] stays 0; lag l has
+ * counts[l] = max(0, samples - l) terms, and C_r(l) = 1 - 2 diff[r][l] / (nvars counts[l]).  Exact integers, independent of the
+ * order of execution; only real sites of owned replicas count.  A sample is ONE launch on the container's stream: nothing is waited
+ * for, no random number is consumed, no configuration, energy or timestep changes.
+ * isingmc_autocorr_create: served are the containers isingmc_overlaps serves -- periodic, field-free checkerboard lattices (any sign
+ *   pattern) and both replica-packed families, shards included.  Refused with ISINGMC_ERR_INVALID before anything is allocated: the
+ *   f64 CSR family; fields, open boundaries, anisotropy; a tempering ladder attached (and isingmc_pt_attach while a ring lives: a slot
+ *   changes its temperature); n_lags outside 1 .. 256; flags != 0; a second ring on one container; a ring (snapshots + sums) larger
+ *   than the option "autocorr_bytes" (isingmc_states_set_option; ISINGMC_AUTOCORR_BYTES, default 4 GiB).  While a ring lives,
+ *   isingmc_states_append, isingmc_pa_run and isingmc_pa_resample are refused.
+ * isingmc_autocorr_set_every: every > 0: from now on (t0 = the container's timestep) a sample follows every timestep t with
+ *   (t - t0) % every == 0, whatever kind of timestep it is (Metropolis sweep, Swendsen-Wang step, isoenergetic move), inside
+ *   isingmc_do_time_steps*, isingmc_run_sampling and isingmc_run_sampling_moments; 0 switches the period off, ring and sums stay.
+ *   isingmc_states_set_timestep re-bases t0; the sample number goes on.
+ * isingmc_autocorr_sample: one sample now, enqueue only.
+ * isingmc_autocorr_count: samples taken since creation or the last reset, and L (either pointer may be NULL); no device access.
+ * isingmc_autocorr_get: waits once for the container's stream; counts_out: uint64[L + 1], diff_out: uint64[R][L + 1] (either may
+ *   be NULL).  Changes nothing.
+ * isingmc_autocorr_reset: sums and sample number to 0 (enqueue only); the period stays.
+ * isingmc_autocorr_destroy: waits for the container's stream and frees the ring; the container takes a new one afterwards.  The
+ *   ring must be destroyed before its container.
+ * isingmc_run_sampling_autocorr: the loop of isingmc_run_sampling with the samples taken by the ring instead of copied out: the ring
+ *   is reset, then  thermalization x do_time_step(beta);  n_samples x { sampling_freq x do_time_step(beta);  one sample }  is enqueued
+ *   back to back and the host waits once, for energies_out: double[count] (NULL allowed).  site_sums != 0: the per-replica site sums
+ *   (ISINGMC_MOMENTS_PER_REPLICA, zeroed first) take the same samples; isingmc_moments_get reads them, and sums beyond the option
+ *   moments_bytes refuse the call.  The ring's period (and with site_sums the sums') must be off on entry and is off on return.
+ * isingmc_host_autocorr_plan: the ring's bookkeeping without a device, as the launch of sample number samples_taken uses it:
+ *   slot_of_lag_out: uint32[L + 1] -- [0] = the slot the sample is stored in, [l] = the slot of the snapshot l samples back for
+ *   l = 1 .. *live_lags_out = min(samples_taken, L), 0xFFFFFFFF beyond; *write_slot_out = samples_taken mod L; counts_out:
+ *   uint64[L + 1] = max(0, samples_taken - l), the terms in lag l after samples_taken samples.  Any pointer may be NULL. */
+typedef struct isingmc_autocorr isingmc_autocorr;
+int isingmc_autocorr_create(isingmc_states *states, size_t n_lags, unsigned flags, isingmc_autocorr **out);
+int isingmc_autocorr_set_every(isingmc_autocorr *ac, size_t every);
+int isingmc_autocorr_sample(isingmc_autocorr *ac);
+int isingmc_autocorr_count(const isingmc_autocorr *ac, uint64_t *samples_out, size_t *n_lags_out);
+int isingmc_autocorr_get(isingmc_autocorr *ac, uint64_t *counts_out, uint64_t *diff_out);
+int isingmc_autocorr_reset(isingmc_autocorr *ac);
+int isingmc_autocorr_destroy(isingmc_autocorr *ac);
+int isingmc_run_sampling_autocorr(isingmc_autocorr *ac, double beta, size_t thermalization, size_t sampling_freq, size_t n_samples,
+                                  int site_sums, double *energies_out);
+int isingmc_host_autocorr_plan(uint64_t samples_taken, size_t n_lags, uint32_t *slot_of_lag_out, uint32_t *live_lags_out,
+                               uint32_t *write_slot_out, uint64_t *counts_out);
+
 /* replaces the whole sampling loop of lattice.rs:271-287 / classicising.rs:144-173:
  *   thermalization x do_time_step(beta);  n_samples x { sampling_freq x do_time_step(beta);
  *   states[r][k][:] = state_ref();  energies[r][k] = get_energy() }

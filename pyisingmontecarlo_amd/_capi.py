@@ -124,6 +124,15 @@ _PROTOTYPES = {
     "isingmc_moments_get": (C.c_int, [_vp, C.POINTER(C.c_uint64), _vp, _vp]),
     "isingmc_moments_reset": (C.c_int, [_vp]),
     "isingmc_run_sampling_moments": (C.c_int, [_vp, C.c_double, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint, _vp]),
+    "isingmc_autocorr_create": (C.c_int, [_vp, C.c_size_t, C.c_uint, C.POINTER(_vp)]),
+    "isingmc_autocorr_set_every": (C.c_int, [_vp, C.c_size_t]),
+    "isingmc_autocorr_sample": (C.c_int, [_vp]),
+    "isingmc_autocorr_count": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_size_t)]),
+    "isingmc_autocorr_get": (C.c_int, [_vp, _vp, _vp]),
+    "isingmc_autocorr_reset": (C.c_int, [_vp]),
+    "isingmc_autocorr_destroy": (C.c_int, [_vp]),
+    "isingmc_run_sampling_autocorr": (C.c_int, [_vp, C.c_double, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, _vp]),
+    "isingmc_host_autocorr_plan": (C.c_int, [C.c_uint64, C.c_size_t, _vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _vp]),
     "isingmc_run_sampling": (C.c_int, [_vp, C.c_double, C.c_size_t, C.c_size_t, C.c_size_t, _vp, _vp]),
     "isingmc_pt_attach": (C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint64]),
     "isingmc_pt_can_attach": (C.c_int, [_vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_int)]),
@@ -698,6 +707,84 @@ class ClusterSeries(_DeviceSeries):
         return (t,) + tuple(np.ascontiguousarray(rows[:, :, i]) for i in range(6))
 
 
+def autocorr_plan(samples_taken, n_lags):
+    """(slot_of_lag uint32[L + 1], live_lags, write_slot, counts uint64[L + 1]): the bookkeeping of a lag ring of L = n_lags snapshots
+    when samples_taken samples are in it, as the launch of the next sample uses it.  No device."""
+    L = int(n_lags)
+    slots, counts = np.zeros(max(L, 0) + 1, dtype=np.uint32), np.zeros(max(L, 0) + 1, dtype=np.uint64)
+    live, write = C.c_uint32(), C.c_uint32()
+    _check(lib().isingmc_host_autocorr_plan(C.c_uint64(int(samples_taken)), L, _p(slots), C.byref(live), C.byref(write), _p(counts)))
+    return slots, int(live.value), int(write.value), counts
+
+
+class Autocorrelation:
+    """isingmc_autocorr: the lag ring of a container -- L snapshots of its configurations on the device and, per
+    replica and lag l = 1 .. L, the number of sites that differ between a sample and the sample l samples before it, summed over
+    the samples.  sample() and the periodic samples inside the step loop only enqueue one launch; get() reads the sums, once,
+    afterwards.  Made by States.autocorrelation; one ring per container."""
+
+    def __init__(self, a, n_lags):
+        self._a = a  # keeps it alive
+        self._handle = _SeriesHandle("isingmc_autocorr_destroy")
+        _check(lib().isingmc_autocorr_create(a._h, int(n_lags), 0, C.byref(self._handle.h)))
+        a.__dict__["_series"] = [h for h in a.__dict__.get("_series", []) if h.h] + [self._handle]  # (the ring goes before its container)
+
+    @property
+    def _h(self):
+        return self._handle.h
+
+    def set_every(self, k):
+        """A sample follows every timestep t > t0 (now) with (t - t0) % k == 0, whatever kind of timestep it is, inside the run
+        calls; 0: off, ring and sums stay."""
+        _check(lib().isingmc_autocorr_set_every(self._h, int(k)))
+
+    def sample(self):
+        """One sample of the configurations as they are.  Enqueue only."""
+        _check(lib().isingmc_autocorr_sample(self._h))
+
+    @property
+    def samples(self):
+        """Samples taken since creation or the last reset."""
+        n = C.c_uint64()
+        _check(lib().isingmc_autocorr_count(self._h, C.byref(n), None))
+        return int(n.value)
+
+    @property
+    def n_lags(self):
+        n = C.c_size_t()
+        _check(lib().isingmc_autocorr_count(self._h, None, C.byref(n)))
+        return int(n.value)
+
+    def get(self):
+        """(counts uint64[L + 1], diff uint64[R, L + 1]): the terms in every lag, max(0, samples - l), and per replica the sum over
+        them of the sites that differ; diff[:, 0] is 0.  correlation.autocorrelation turns them into C.  Synchronises once; changes nothing."""
+        L = self.n_lags
+        counts, diff = np.zeros(L + 1, dtype=np.uint64), np.zeros((self._a.count, L + 1), dtype=np.uint64)
+        _check(lib().isingmc_autocorr_get(self._h, _p(counts), _p(diff)))
+        return counts, diff
+
+    def reset(self):
+        """Sums and sample number back to 0 (enqueue only); the period stays."""
+        _check(lib().isingmc_autocorr_reset(self._h))
+
+    def run_sampling(self, beta, thermalization, sampling_freq, n_samples, site_sums=False):
+        """The loop of States.run_sampling with the samples taken by the ring (reset first) instead of copied out: the final
+        energies float64[R], one wait.  site_sums: the per-replica site sums (States.moments) take the same samples."""
+        energies = np.zeros(self._a.count, dtype=np.float64)
+        _check(lib().isingmc_run_sampling_autocorr(self._h, float(0.0 if beta is None else beta), int(thermalization), int(sampling_freq),
+                                                   int(n_samples), int(bool(site_sums)), _p(energies)))
+        return energies
+
+    def close(self):
+        self._handle.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def nonlocal_steps(t0, timesteps, k):
     """The timesteps t in [t0, t0 + timesteps) with t % k == k - 1 (0 when k == 0): the rows a run call appends to a cluster series."""
     out = C.c_uint64()
@@ -883,6 +970,11 @@ class States:
         n_pairs=None: count // 2 inside this container, the smaller count between two, the number of rungs with by_rung (both
         containers carry a whole ladder over equal betas; pair r = the two replicas at rung r, read on the device)."""
         return OverlapSeries(self, other, n_pairs, classes, link, by_rung, capacity)
+
+    def autocorrelation(self, n_lags):
+        """An Autocorrelation: the lag ring of this container, n_lags = 1 .. 256 snapshots kept on the device.  One
+        ring per container; ValueError where isingmc_autocorr_create refuses."""
+        return Autocorrelation(self, n_lags)
 
     # ---- each replica's lowest-energy configuration (DESIGN.md S16)
     def set_track_best(self, k):

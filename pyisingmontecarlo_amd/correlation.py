@@ -87,3 +87,29 @@ def correlation_length(chi0, chik, L, n=1):
     single |q_hat(k)|^2 is exponentially distributed and the mean of the ratios diverges."""
     chi0, chik = np.asarray(chi0, dtype=np.float64), np.asarray(chik, dtype=np.float64)
     return np.sqrt(chi0 / chik - 1.0) / (2.0 * np.sin(np.pi * n / L))
+
+
+def autocorrelation(diff, counts, nvars):
+    """C[..., l] = 1 - 2 diff[..., l] / (nvars counts[l]) from the sums of a lag ring (Autocorrelation.get): diff[R, L + 1]
+    the differing sites summed over the counts[l] terms of lag l.  A lag without a term (counts[l] == 0) has no value: NaN.  Units
+    of the lag axis: samples."""
+    d = np.asarray(diff, dtype=np.uint64).astype(np.float64)
+    n = np.asarray(counts, dtype=np.uint64).astype(np.float64) * float(nvars)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(n > 0, 1.0 - 2.0 * d / n, np.nan)
+
+
+def integrated_time(corr, c=6.0):
+    """(tau_int float64[...], window int64[...]) per row of corr[..., l], l = 0 .. L, with Sokal's automatic window:
+    tau(W) = 1/2 + sum_{l=1..W} C(l), summed in the order of l, and the smallest W >= 1 with W >= c tau(W).  A row without such a W
+    within the measured lags returns tau(L) and window = -1: the run or the ring is too short for that row.  Units: samples."""
+    corr = np.asarray(corr, dtype=np.float64)
+    L = corr.shape[-1] - 1
+    if L < 1:  # lag 0 alone: tau(0) = 1/2, no window
+        return np.full(corr.shape[:-1], 0.5), np.full(corr.shape[:-1], -1, dtype=np.int64)
+    tau = 0.5 + np.cumsum(corr[..., 1:], axis=-1)              # tau[..., W - 1] = tau(W)
+    ok = np.arange(1, L + 1, dtype=np.float64) >= c * tau       # (a NaN compares false)
+    found = ok.any(axis=-1)
+    first = np.where(found, ok.argmax(axis=-1), L - 1)
+    tau_int = np.take_along_axis(tau, np.asarray(first)[..., None], axis=-1)[..., 0]
+    return tau_int, np.where(found, first + 1, -1).astype(np.int64)

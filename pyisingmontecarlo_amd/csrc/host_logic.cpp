@@ -561,6 +561,16 @@ uint64_t nonlocal_steps_in(uint64_t t0, uint64_t timesteps, uint64_t k)
     return k ? (t0 + timesteps) / k - t0 / k : 0; // multiples of k among t + 1 for t in [t0, t0 + timesteps)
 }
 
+AutocorrPlan autocorr_plan(uint64_t samples_taken, uint32_t n_lags)
+{
+    AutocorrPlan P;
+    P.samples_taken = samples_taken;
+    P.n_lags = n_lags;
+    P.live = uint32_t(std::min<uint64_t>(samples_taken, n_lags));
+    P.write_slot = uint32_t(samples_taken % n_lags);
+    return P;
+}
+
 ClassSegments class_segments(const uint32_t *site, size_t n_pos, const uint32_t *cls, size_t nvars, size_t n_tables, size_t n_classes)
 {
     ClassSegments S;

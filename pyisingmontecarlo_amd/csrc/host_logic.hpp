@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "autocorr_ring.hpp"
 #include "general_types.hpp"
 
 namespace isingmc {
@@ -158,6 +159,20 @@ struct Periodic {
     // around the repeat of a call that started at timestep t: it skips the samples already taken
     void replay_since(uint64_t t) { replay_to = every && last_t > t ? last_t : 0; }
 };
+
+// The bookkeeping of the lag ring when samples_taken samples are in it, 1 <= n_lags: what the launch of sample number
+// samples_taken is given, and what a read-out divides by.  live = min(samples_taken, n_lags) lags have a snapshot; the sample goes
+// into write_slot = samples_taken mod n_lags.  slot_of_lag(0) = write_slot (where lag 0, the current configuration, goes),
+// slot_of_lag(l) = the slot of the snapshot l samples back (autocorr_ring.hpp) for 1 <= l <= live, AUTOCORR_NO_SLOT beyond.
+// count(l): the terms summed into lag l by the samples so far, max(0, samples_taken - l).  Nothing is allocated.
+constexpr uint32_t AUTOCORR_NO_SLOT = 0xFFFFFFFFu;
+struct AutocorrPlan {
+    uint64_t samples_taken = 0;
+    uint32_t n_lags = 1, live = 0, write_slot = 0;
+    uint32_t slot_of_lag(uint32_t l) const { return l == 0 ? write_slot : l <= live ? acr_slot_of_lag(write_slot, l, n_lags) : AUTOCORR_NO_SLOT; }
+    uint64_t count(uint32_t l) const { return samples_taken > l ? samples_taken - l : 0; }
+};
+AutocorrPlan autocorr_plan(uint64_t samples_taken, uint32_t n_lags);
 
 // packed checkerboard planes of one replica -> W*H bytes in site order (16 bytes per SSE2 store)
 void unpack_lattice(uint32_t W, uint32_t H, const uint32_t *words, uint8_t *spins);

@@ -11,6 +11,7 @@
 //   recorders.hip  the table of the measurements the step loop takes on a period, and the log core of the series
 //   best.hip       each replica's lowest-energy configuration, kept on the device (isingmc_best_*)
 //   moments.hip    per-site spin sums and per-bond sums over the samples of a run (isingmc_moments_*)
+//   autocorr.hip   the lag ring: spin autocorrelation over time lags against stored snapshots (isingmc_autocorr_*)
 //   sampling.hip   get_states and the double-buffered sampling pipeline
 //   tempering.hip  on-stream parallel tempering, the in-process ladder group (RCCL through dlopen)
 //   population.hip population annealing: the on-stream resampling step (isingmc_pa_*)
@@ -39,6 +40,7 @@
 #include <vector>
 
 #include "../../include/isingmc.h"
+#include "autocorr_kernels.hpp"
 #include "best_kernels.hpp"
 #include "cluster_kernels.hpp"
 #include "general_launch.hpp"
@@ -169,7 +171,7 @@ struct StepPreset {
 
 // The measurements the step loop takes on a period (recorders.hip holds their table), in the order it samples them.  REC_CLUSTERS
 // has no period of its own (its `every` stays 0): the non-local steps themselves append its rows
-enum Recorder { REC_BEST, REC_MOMENTS, REC_OVERLAPS, REC_OBSERVABLES, REC_CLUSTERS, REC_COUNT };
+enum Recorder { REC_BEST, REC_MOMENTS, REC_OVERLAPS, REC_OBSERVABLES, REC_AUTOCORR, REC_CLUSTERS, REC_COUNT };
 struct SeriesLog;
 
 // The state of a container that ONE unit owns, a struct per unit; isingmc_states holds one of each.  Other units read them (a
@@ -300,6 +302,19 @@ struct MomentsState {
     uint32_t pending = 0;    // samples in the time planes since the last flush (< 2^k)
 };
 
+// ---- autocorr.hip -------------------------------------------------------------------------------------------------------------
+// the lag ring (isingmc_autocorr_*): allocated by isingmc_autocorr_create for the replicas the container holds
+// then, gone with isingmc_autocorr_destroy; one ring per container
+struct AutocorrState {
+    bool live = false;   // a ring exists (its handle is out)
+    uint32_t n_lags = 0; // L
+    uint64_t samples = 0; // samples enqueued since creation or the last reset: the next one is sample number `samples`
+    size_t R = 0;         // replicas the sums hold
+    size_t slot_words = 0; // words of one snapshot: the state buffer's
+    DevBlock<uint32_t> d_ring;           // [L][slot_words]
+    DevBlock<unsigned long long> d_sums; // [counter slots][L + 1]
+};
+
 struct isingmc_states {
     isingmc_graph *g = nullptr;
     Options opt; // the environment's switches when the container was created (isingmc_states_set_option changes one)
@@ -348,7 +363,8 @@ struct isingmc_states {
     size_t n_total = 0, first = 0; // this container is the shard [first, first + R) of n_total experiments
     // the sample points of the periodic recorders.  REC_BEST: an update follows every timestep after which t % every == 0 (t0 stays
     // 0).  REC_OVERLAPS / REC_OBSERVABLES: a row of series[...], the one series of its kind that records on a period.
-    // REC_CLUSTERS: series[...] is the container's one live cluster series (S24)
+    // REC_AUTOCORR: the lag ring's samples (S26; its state is acr below, not a series).  REC_CLUSTERS: series[...] is the container's
+    // one live cluster series (S24)
     Periodic rec[REC_COUNT];
     SeriesLog *series[REC_COUNT] = {};
     size_t osr_by_rung_live = 0; // live overlap series that read this container's ladder permutation on the device: no isingmc_pt_detach
@@ -365,6 +381,7 @@ struct isingmc_states {
     PaChooseState pac;
     BestState best;
     MomentsState mom;
+    AutocorrState acr;
 
     // The body runs before any member goes: with the device current, nothing of this object may still be running when the
     // members' blocks, streams and events go back to their caches, where the next request may pick them up at once (hipFree used
@@ -526,6 +543,9 @@ IM_INTERNAL int best_update_enqueue(isingmc_states *s); // energies_enqueue into
 
 // ---- moments.hip (per-site and per-bond sums over the samples of a run) -------------------------------------------------------
 IM_INTERNAL int moments_sample_enqueue(isingmc_states *s); // enqueue: one sample of all replicas into the sums (joins the lanes)
+
+// ---- autocorr.hip (the lag ring) ----------------------------------------------------------------------------------------------
+IM_INTERNAL int autocorr_sample_enqueue(isingmc_states *s); // enqueue: one sample of all replicas against the ring (joins the lanes)
 
 // ---- overlaps.hip (which containers and pairings an overlap measurement serves) --------------------------------------------------
 // A class set as the kernels of overlap_class_kernels.hip read it: on a recognised lattice the tables in plane order with one

@@ -237,6 +237,7 @@ extern "C" int isingmc_states_set_option(isingmc_states *s, const char *name, lo
             return fail(ISINGMC_ERR_INVALID, "the kernel family of a container is fixed when it is created (set ISINGMC_" + std::string(family) +
                                                  " in the environment before isingmc_states_create)");
     if (bare == "philox_rounds") return philox_rounds_set(s, value);
+    if (bare == "autocorr_bytes") { s->opt.autocorr_bytes = value; return ISINGMC_OK; } // (outside Options::table(), as options.hpp says)
     if (!s->opt.set(n, value)) return fail(ISINGMC_ERR_INVALID, "unknown option '" + n + "'");
     return ISINGMC_OK;
 }

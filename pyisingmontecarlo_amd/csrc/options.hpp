@@ -52,6 +52,10 @@ struct Options {
     // only through philox_rounds_set (isingmc.hip), which checks the value and the container; read wherever a call is planned.
     // Not in the table: set() does not reach it
     int philox_rounds = 10;
+    // The most device memory the snapshots and sums of a container's lag ring may take (next to moments_bytes in
+    // meaning, 64 bits).  Not in the table either -- tests/options_host.cpp pins the table's names and count: the environment is read
+    // below, and isingmc_states_set_option assigns it by name (isingmc.hip)
+    long long autocorr_bytes = 4ll << 30;
 
     // FLAG: set or not in the environment (anything but "" and "0..." is on; every flag is off by default).  INT: atoi, the
     // default when unset or empty.  INT64: atoll when set.  set() assigns the value as it comes, whatever the kind.
@@ -104,6 +108,7 @@ struct Options {
         o.real_target_wgs = std::max(256, o.real_target_wgs);
         o.cluster_workspace_bytes = std::max(1, o.cluster_workspace_bytes);
         o.philox_rounds = env_int("ISINGMC_PHILOX_ROUNDS", o.philox_rounds);
+        if (const char *v = std::getenv("ISINGMC_AUTOCORR_BYTES")) o.autocorr_bytes = std::atoll(v);
         return o;
     }
 

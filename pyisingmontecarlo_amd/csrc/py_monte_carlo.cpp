@@ -136,6 +136,24 @@ using SeriesHandle = SeriesHandleOf<isingmc_overlap_series, isingmc_overlap_seri
 using ObsSeriesHandle = SeriesHandleOf<isingmc_observable_series, isingmc_observable_series_destroy>;
 using ClusterSeriesHandle = SeriesHandleOf<isingmc_cluster_series, isingmc_cluster_series_destroy>; // (no class set; columns: replicas or pairs)
 
+// the lag ring of a container: it goes before the container
+struct AutocorrHandle {
+    isingmc_autocorr *ac = nullptr;
+    size_t every = 0, n_lags = 0;
+    ~AutocorrHandle() { isingmc_autocorr_destroy(ac); }
+};
+
+// C[r][l] = 1 - 2 diff[r][l] / (N counts[l]) as float64[R, cols] for the lags 0 .. cols - 1 of sums laid out [R][row]; NaN where a lag has no term
+py::array_t<double> autocorr_array(const std::vector<uint64_t> &counts, const std::vector<uint64_t> &diff, size_t R, size_t row, size_t cols, size_t nvars)
+{
+    py::array_t<double> corr(std::vector<ssize_t>{ssize_t(R), ssize_t(cols)});
+    double *c = corr.mutable_data();
+    for (size_t r = 0; r < R; r++)
+        for (size_t l = 0; l < cols; l++)
+            c[r * cols + l] = counts[l] ? 1.0 - 2.0 * double(diff[r * row + l]) / (double(nvars) * double(counts[l])) : std::numeric_limits<double>::quiet_NaN();
+    return corr;
+}
+
 // the rows of a cluster series, t[n] and rows[n][columns][6] as isingmc_cluster_series_get hands them out, as (timesteps uint64[m],
 // n_clusters, largest, sites, s2, s4_lo, s4_hi: uint64[m, C] each): the m rows of timesteps >= from_t
 py::tuple cluster_series_rows(const std::vector<uint64_t> &t, const std::vector<uint64_t> &rows, size_t columns, uint64_t from_t)
@@ -442,6 +460,57 @@ public:
         for (size_t k = 0; k < bond.size(); k++) bm[k] = double(bond[k]) / (double(n) * double(R));
         if (bonds) return py::make_tuple(energies, spins, bond_means);
         return py::make_tuple(energies, spins);
+    }
+
+    // extension: the classical counterpart of run_quantum_monte_carlo_and_measure_variable_autocorrelation
+    // (lattice.rs:628), the variable being the spin.  The trajectory and the bookkeeping of run_monte_carlo_sampling with the same
+    // seeds -- sampling_wait_buffer timesteps of thermalisation, then timesteps sweeps with a sample every sampling_freq, S =
+    // timesteps / sampling_freq samples -- with every sample compared on the device against the max_lag samples before it: one
+    // enqueue-only run and one wait for it (the reads of the sums that follow find the stream idle), no configuration crosses the bus.  Returns C float64[R, L + 1], L = min(max_lag, S - 1),
+    // C[r, l] = 1 - 2 diff[r, l] / (N (S - l)) = the average over the S - l sample pairs l samples apart of (1/N) sum_i s_i s_i';
+    // lag axis in samples.  connected=True: the per-replica site sums of S18 take the same samples and (1/N) sum_i <s_i>_r^2 is
+    // subtracted from every lag but not renormalised, <s_i>_r the mean over the S samples.  That estimate of the squared mean is
+    // biased upwards by about tau_int / S per site (the variance of a mean of S correlated samples), so at runs of a few tau the
+    // connected function comes out too low by that much at every lag; C(0) is then 1 - (1/N) sum <s_i>^2, not 1.  Sums beyond the
+    // option moments_bytes raise that option's error.  One device: the ring lives in one container.  Cluster periods set on this
+    // object apply.
+    py::array_t<double> run_monte_carlo_and_measure_variable_autocorrelation(double beta, size_t timesteps, size_t num_experiments,
+                                                                             std::optional<size_t> sampling_wait_buffer, std::optional<size_t> sampling_freq,
+                                                                             size_t max_lag, bool connected)
+    {
+        require_classical();
+        const size_t therm = sampling_wait_buffer.value_or(0), freq = sampling_freq.value_or(1);
+        if (freq == 0) throw py::value_error("sampling_freq must be positive");
+        if (max_lag < 1 || max_lag > 256) throw py::value_error("max_lag must be 1 .. 256 (the lags a ring holds)");
+        if (devices_.size() != 1) throw py::value_error("autocorrelation measurement runs on one device: the ring lives in one container (set_device)");
+        const size_t S = timesteps / freq, R = num_experiments, N = E_->nvars;
+        if (S < 2) throw py::value_error("an autocorrelation needs at least two samples: timesteps / sampling_freq is below 2");
+        const size_t L = std::min(max_lag, S - 1), row = L + 1;
+        std::vector<uint64_t> counts(row), diff(R * row);
+        std::vector<int64_t> site(connected ? R * N : 0);
+        uint64_t n = 0;
+        fan_out(num_experiments, 0, R, [&](isingmc_states *s, size_t) {
+            AutocorrHandle h; // (the ring goes before the container fan_out destroys)
+            int rc = isingmc_autocorr_create(s, L, 0, &h.ac);
+            if (rc == ISINGMC_OK) rc = isingmc_run_sampling_autocorr(h.ac, beta, therm, freq, S, connected ? 1 : 0, nullptr);
+            if (rc == ISINGMC_OK) rc = isingmc_autocorr_get(h.ac, counts.data(), diff.data());
+            if (rc == ISINGMC_OK && connected) rc = isingmc_moments_get(s, &n, site.data(), nullptr);
+            return rc;
+        });
+        py::array_t<double> corr = autocorr_array(counts, diff, R, row, row, N);
+        if (connected) {
+            double *c = corr.mutable_data();
+            for (size_t r = 0; r < R; r++) {
+                double m2 = 0.0; // (1/N) sum_i <s_i>_r^2, summed in site order
+                for (size_t i = 0; i < N; i++) {
+                    const double m = double(site[r * N + i]) / double(n);
+                    m2 += m * m;
+                }
+                m2 /= double(N);
+                for (size_t l = 0; l < row; l++) c[r * row + l] -= m2;
+            }
+        }
+        return corr;
     }
 
     // extension: the sibling of run_monte_carlo_and_measure_spins for the two observables every study starts from.
@@ -1220,6 +1289,50 @@ public:
         return cluster_series_rows(t, rows, cluster_series_->columns, 0);
     }
     void reset_measured_clusters() { if (cluster_series_) check(isingmc_cluster_series_reset(cluster_series_->s)); }
+    // extension: the spin autocorrelation of every persistent replica over time lags, measured on the device.
+    // set_measure_autocorrelation_every(k, max_lag): a sample follows every k-th timestep from now on, whatever kind of timestep it
+    // is, without the host waiting (0: off, ring and sums stay); a call with k > 0 starts a new ring of max_lag = 1 .. 256 snapshots.
+    // get_measured_autocorrelation() -> (lags_in_timesteps int64[L + 1] = l k, counts uint64[L + 1], corr float64[R, L + 1]):
+    // corr[:, 0] is 1 once a sample is in, a lag without a term is NaN.  reset_measured_autocorrelation() zeroes sums and sample
+    // number and keeps the period.  add_graph is refused while the ring lives.  ValueError where isingmc_autocorr_create refuses.
+    void set_measure_autocorrelation_every(size_t k, size_t max_lag)
+    {
+        if (k == 0) {
+            if (autocorr_) check(isingmc_autocorr_set_every(autocorr_->ac, 0));
+            return;
+        }
+        // The old ring has to go before the new one takes the container's one slot.  A lag count out of range is refused before that;
+        // what only the library can refuse -- a ring beyond autocorr_bytes -- comes after, and its ValueError says that the old ring
+        // has gone (the container's family, the other reason, cannot have changed since the old ring was made)
+        if (max_lag < 1 || max_lag > 256) throw py::value_error("max_lag must be 1 .. 256 (the lags a ring holds)");
+        const bool had_ring = bool(autocorr_);
+        autocorr_.reset();
+        auto h = std::make_unique<AutocorrHandle>();
+        if (isingmc_autocorr_create(st_->s, max_lag, 0, &h->ac) != ISINGMC_OK)
+            throw py::value_error(std::string(isingmc_last_error()) + (had_ring ? " (the ring measured so far has been destroyed)" : ""));
+        check(isingmc_autocorr_set_every(h->ac, k));
+        h->every = k;
+        h->n_lags = max_lag;
+        autocorr_ = std::move(h);
+    }
+    py::tuple get_measured_autocorrelation()
+    {
+        if (!autocorr_) throw py::value_error("no autocorrelation is measured: call set_measure_autocorrelation_every(k) first");
+        const size_t R = isingmc_states_count(st_->s), row = autocorr_->n_lags + 1;
+        std::vector<uint64_t> counts(row), diff(R * row);
+        {
+            py::gil_scoped_release nogil;
+            check(isingmc_autocorr_get(autocorr_->ac, counts.data(), diff.data()));
+        }
+        py::array_t<int64_t> lags(std::vector<ssize_t>{ssize_t(row)});
+        py::array_t<uint64_t> cnt(std::vector<ssize_t>{ssize_t(row)});
+        for (size_t l = 0; l < row; l++) {
+            lags.mutable_data()[l] = int64_t(l * autocorr_->every);
+            cnt.mutable_data()[l] = counts[l];
+        }
+        return py::make_tuple(lags, cnt, autocorr_array(counts, diff, R, row, row, E_.nvars));
+    }
+    void reset_measured_autocorrelation() { if (autocorr_) check(isingmc_autocorr_reset(autocorr_->ac)); }
     // extension: Swendsen-Wang cluster steps on the persistent replicas (see Lattice.set_cluster_update_every); the graph is known
     // here, so one the cluster step does not serve raises ValueError at once
     void set_cluster_update_every(size_t k) { check(isingmc_states_set_cluster_every(st_->s, k)); }
@@ -1288,6 +1401,7 @@ private:
     std::unique_ptr<SeriesHandle> series_; // (declared last: destroyed before the container it reads)
     std::unique_ptr<ObsSeriesHandle> obs_series_; // (the same)
     std::unique_ptr<ClusterSeriesHandle> cluster_series_; // (the same)
+    std::unique_ptr<AutocorrHandle> autocorr_; // (the same)
 };
 
 } // namespace
@@ -1330,6 +1444,9 @@ PYBIND11_MODULE(_py_monte_carlo, m)
              "per_experiment"_a = true, "bonds"_a = false)
         .def("run_monte_carlo_and_measure_observables", &Lattice::run_monte_carlo_and_measure_observables, "beta"_a, "timesteps"_a,
              "num_experiments"_a, "thermalization_time"_a = py::none(), "sampling_freq"_a = py::none(), "classes"_a = py::none())
+        .def("run_monte_carlo_and_measure_variable_autocorrelation", &Lattice::run_monte_carlo_and_measure_variable_autocorrelation, "beta"_a,
+             "timesteps"_a, "num_experiments"_a, "sampling_wait_buffer"_a = py::none(), "sampling_freq"_a = py::none(), "max_lag"_a = 32,
+             "connected"_a = false)
         .def("run_monte_carlo_and_measure_clusters", &Lattice::run_monte_carlo_and_measure_clusters, "beta"_a, "timesteps"_a,
              "num_experiments"_a, "thermalization_time"_a = py::none())
         .def("run_monte_carlo_annealing", &Lattice::run_monte_carlo_annealing, "betas"_a, "timesteps"_a,
@@ -1391,6 +1508,9 @@ PYBIND11_MODULE(_py_monte_carlo, m)
         .def("set_measure_clusters", &ClassicIsing::set_measure_clusters, "capacity"_a = 4096)
         .def("get_measured_clusters", &ClassicIsing::get_measured_clusters)
         .def("reset_measured_clusters", &ClassicIsing::reset_measured_clusters)
+        .def("set_measure_autocorrelation_every", &ClassicIsing::set_measure_autocorrelation_every, "k"_a, "max_lag"_a = 32)
+        .def("get_measured_autocorrelation", &ClassicIsing::get_measured_autocorrelation)
+        .def("reset_measured_autocorrelation", &ClassicIsing::reset_measured_autocorrelation)
         .def("set_track_minimum", &ClassicIsing::set_track_minimum, "every"_a)
         .def("get_minimum", &ClassicIsing::get_minimum)
         .def("reset_minimum", &ClassicIsing::reset_minimum)

@@ -1,5 +1,5 @@
 // libisingmc.so: the measurements the step loop takes on a period -- minimum tracking, the moment sums (S18), the
-// overlap series (S21), the observable series (S22) -- as one table with the functions over it that serve every place which has to
+// overlap series (S21), the observable series (S22), the lag ring (S26) -- as one table with the functions over it that serve every place which has to
 // know all recorders (a new recorder is a row), and the log core the series share.  The cluster series (S24) is a row too: it has
 // no period, the non-local steps append its rows, but it can run full and it objects to what the others object to.  Nothing here is
 // a kernel.
@@ -12,6 +12,7 @@ struct RecorderRow {
     bool replay_guard; // the repeat of a call skips the samples its first attempt took (minimum tracking: it finds the same records again)
     bool restarts;     // isingmc_states_set_timestep counts the sample points from the new timestep (minimum tracking: t0 stays 0)
     const char *refuse_append, *refuse_resample; // why replicas cannot be added / resampled while it is on (nullptr: they can)
+    bool (*live)(const isingmc_states *) = nullptr; // on without a period or a series in the container's slot (nullptr: never)
 };
 
 static const RecorderRow RECORDERS[REC_COUNT] = {
@@ -26,6 +27,10 @@ static const RecorderRow RECORDERS[REC_COUNT] = {
     {obs_sample_enqueue, [](const isingmc_states *s, size_t n) { return series_room_or_fail(s, REC_OBSERVABLES, n); }, true, true,
      "an observable series records on a period for this container (isingmc_observable_series_set_every): its columns are the replicas it holds; switch the period on after the graphs are added",
      "an observable series records on a period for this container (isingmc_observable_series_set_every): a resampling replaces the replicas whose columns it follows; switch the period off first"},
+    {autocorr_sample_enqueue, nullptr, true, true,
+     "a lag ring is live on this container (isingmc_autocorr_create): its snapshots and sums are sized for the replicas it holds; make the ring after the graphs are added",
+     "a lag ring is live on this container (isingmc_autocorr_create): a resampling replaces the replicas whose snapshots it holds; destroy the ring first",
+     [](const isingmc_states *s) { return s->acr.live; }},
     {nullptr, cluster_series_room_or_fail, false, false, // (never due: the rows are the non-local steps'; a repeat writes them again, below)
      "a cluster series is live on this container (isingmc_cluster_series_create): its columns are the replicas it holds; make the series after the graphs are added",
      "a cluster series is live on this container (isingmc_cluster_series_create): a resampling replaces the replicas whose columns it follows; destroy the series first"},
@@ -78,7 +83,8 @@ const char *recorders_refusal(const isingmc_states *s, RecorderRefusal what)
 {
     for (int i = 0; i < REC_COUNT; i++) {
         const char *why = what == RecorderRefusal::Append ? RECORDERS[i].refuse_append : RECORDERS[i].refuse_resample;
-        if ((s->rec[i].every || s->series[i]) && why) return why; // (on: a period, or the series that holds the container's slot)
+        const bool on = s->rec[i].every || s->series[i] || (RECORDERS[i].live && RECORDERS[i].live(s)); // a period, the series in the container's slot, a row's own state
+        if (on && why) return why;
     }
     return nullptr;
 }

@@ -45,6 +45,7 @@ static std::string pt_attach_obstacle(const isingmc_states *s, size_t n_rungs, s
     if (s->cl.every) return "cluster updates are switched on for this container (isingmc_states_set_cluster_every): a tempering round has no cluster steps";
     if (s->icm.every) return "isoenergetic cluster moves are switched on for this container (isingmc_states_set_icm_every): inside a ladder the pairs would have to follow the rung permutation";
     if (s->series[REC_CLUSTERS]) return "a cluster series is live on this container (isingmc_cluster_series_create): a tempering round has no non-local steps of the container's own; destroy the series first";
+    if (s->acr.live) return "a lag ring is live on this container (isingmc_autocorr_create): inside a ladder a slot changes its temperature, so its lags would mix the temperatures; destroy the ring first";
     if (s->rec[REC_MOMENTS].every) return "moment sums are switched on for this container (isingmc_states_set_moments_every): inside a ladder a slot changes its temperature; attach the ladder first, then switch the sums per rung on (ISINGMC_MOMENTS_PER_RUNG)";
     const bool pk_ladder = s->packed && !s->rj;
     if (!s->packed && (s->g->kind != ISINGMC_KIND_LATTICE2D || s->g->mc_mode != MC_NONE))
