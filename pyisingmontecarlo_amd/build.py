@@ -16,7 +16,7 @@ LIB = os.path.join(LIBDIR, "libisingmc.so")
 EXT = os.path.join(HERE, "_py_monte_carlo" + (sysconfig.get_config_var("EXT_SUFFIX") or ".so"))
 
 HIP_SOURCES = ["core.hip", "graph.hip", "isingmc.hip", "nonlocal.hip", "overlaps.hip", "overlap_series.hip", "observable_series.hip", "cluster_series.hip", "recorders.hip", "best.hip", "moments.hip", "autocorr.hip", "sampling.hip", "tempering.hip", "debug.hip", "lattice_kernels.hip", "general_kernels.hip", "packed_kernels.hip", "tempering_kernels.hip", "strip_kernels.hip", "spread_kernels.hip", "mc_kernels.hip", "packed_uni_kernels.hip", "real_kernels.hip", "cluster_kernels.hip", "packed_cluster_kernels.hip", "packed_icm_kernels.hip", "packed_between_kernels.hip", "overlap_kernels.hip", "overlap_class_kernels.hip", "overlap_series_kernels.hip", "observable_series_kernels.hip", "best_kernels.hip", "moments_kernels.hip", "autocorr_kernels.hip", "pa_kernels.hip", "population.hip", "host_logic.cpp"]
-HIP_DEPS = HIP_SOURCES + ["internal.hpp", "philox.hpp", "lattice_kernels.hpp", "lattice_types.hpp", "strip_kernels.hpp", "strip_types.hpp", "spread_kernels.hpp", "spread_types.hpp", "mc_kernels.hpp", "mc_quad_body.inc", "mc_types.hpp", "general_kernels.hpp", "general_types.hpp", "general_launch.hpp", "packed_kernels.hpp", "packed_types.hpp", "tempering_types.hpp", "packed_uni_kernels.hpp", "real_kernels.hpp", "real_types.hpp", "cluster_kernels.hpp", "cluster_moments.hpp", "sum128.hpp", "cluster_union.hpp", "packed_cluster_kernels.hpp", "packed_icm_kernels.hpp", "packed_between_kernels.hpp", "overlap_kernels.hpp", "overlap_class_kernels.hpp", "overlap_series_kernels.hpp", "observable_series_kernels.hpp", "energy_from_counts.hpp", "lat_class_count.hpp", "best_kernels.hpp", "moments_kernels.hpp", "autocorr_kernels.hpp", "autocorr_ring.hpp", "vertical_counter.hpp", "packed_nbr.hpp", "packed_label.hpp", "pa_kernels.hpp", "det_exp.hpp", "host_logic.hpp", "owned_block.hpp", "options.hpp", "kernel_pick.hpp",
+HIP_DEPS = HIP_SOURCES + ["internal.hpp", "philox.hpp", "lattice_kernels.hpp", "lattice_types.hpp", "strip_kernels.hpp", "strip_types.hpp", "spread_kernels.hpp", "spread_types.hpp", "mc_kernels.hpp", "mc_quad_body.inc", "mc_types.hpp", "general_kernels.hpp", "general_types.hpp", "general_launch.hpp", "packed_kernels.hpp", "packed_types.hpp", "tempering_types.hpp", "packed_uni_kernels.hpp", "real_kernels.hpp", "real_types.hpp", "cluster_kernels.hpp", "cluster_moments.hpp", "sum128.hpp", "cluster_union.hpp", "packed_cluster_kernels.hpp", "packed_icm_kernels.hpp", "packed_between_kernels.hpp", "overlap_kernels.hpp", "overlap_class_kernels.hpp", "overlap_series_kernels.hpp", "observable_series_kernels.hpp", "energy_from_counts.hpp", "lat_class_count.hpp", "best_kernels.hpp", "moments_kernels.hpp", "autocorr_kernels.hpp", "autocorr_ring.hpp", "vertical_counter.hpp", "packed_nbr.hpp", "packed_label.hpp", "pa_kernels.hpp", "det_exp.hpp", "host_logic.hpp", "owned_block.hpp", "options.hpp", "kernel_pick.hpp", "step_policy.hpp",
                           os.path.join(ROOT, "include", "isingmc.h"), os.path.join(ROOT, "include", "isingmc_cluster_series.h")]
 EXT_SOURCES = ["py_monte_carlo.cpp"]
 

@@ -302,6 +302,60 @@ int use_device(int device)
 }
 
 // ------------------------------------------------------------------------------------------------
+// The runtime's occupancy answers (workgroups per compute unit), asked once per query: the key is everything a query depends on
+// -- which kernel, its template arguments, dynamic LDS bytes, Philox rounds, block size.  The device fan-out asks from several
+// host threads; a query is a runtime call, a hit a scan of a handful of entries.
+// ------------------------------------------------------------------------------------------------
+namespace {
+enum OccupancyKernel : uint32_t { OCC_SWEEP_LOOP, OCC_RJ_MEASURE, OCC_STRIP, OCC_SPREAD };
+struct OccupancyKey {
+    uint32_t kernel, targs; // targs: the template arguments, packed by the caller below
+    uint64_t lds_bytes;
+    int rounds;
+    unsigned threads; // where the block size is the caller's choice (0: the instantiation fixes it)
+    bool operator==(const OccupancyKey &o) const
+    {
+        return kernel == o.kernel && targs == o.targs && lds_bytes == o.lds_bytes && rounds == o.rounds && threads == o.threads;
+    }
+};
+template <typename Query>
+int occupancy_cached(const OccupancyKey &key, Query &&query)
+{
+    static std::mutex mu;
+    static std::vector<std::pair<OccupancyKey, int>> cache;
+    std::lock_guard<std::mutex> lock(mu);
+    for (const auto &e : cache)
+        if (e.first == key) return e.second;
+    const int n = query();
+    cache.emplace_back(key, n);
+    return n;
+}
+} // namespace
+
+int cached_lat_sweep_loop_blocks_per_cu(bool pmj, unsigned lds_bytes, int rounds)
+{
+    return occupancy_cached({OCC_SWEEP_LOOP, uint32_t(pmj), lds_bytes, rounds, 0}, [&] { return lat_sweep_loop_blocks_per_cu(pmj, lds_bytes, rounds); });
+}
+
+int cached_rj_measure_blocks_per_cu(uint32_t slots, bool bipartite, bool count_up)
+{
+    return occupancy_cached({OCC_RJ_MEASURE, slots << 2 | uint32_t(bipartite) << 1 | uint32_t(count_up), 0, 10, 0},
+                            [&] { return rj_measure_blocks_per_cu(slots, bipartite, count_up); });
+}
+
+int cached_strip_blocks_per_cu(bool pmj, int nw, bool ladder, size_t lds_bytes, int rounds)
+{
+    return occupancy_cached({OCC_STRIP, uint32_t(pmj) << 2 | uint32_t(ladder) << 1 | uint32_t(nw == 1), lds_bytes, rounds, 0},
+                            [&] { return strip_blocks_per_cu(pmj, nw, ladder, lds_bytes, rounds); });
+}
+
+int cached_spread_blocks_per_cu(bool vec, bool pmj, int lanes_per_quad, unsigned threads, size_t lds_bytes, int rounds)
+{
+    return occupancy_cached({OCC_SPREAD, uint32_t(lanes_per_quad) << 2 | uint32_t(vec) << 1 | uint32_t(pmj), lds_bytes, rounds, threads},
+                            [&] { return spread_blocks_per_cu(vec, pmj, lanes_per_quad, threads, lds_bytes, rounds); });
+}
+
+// ------------------------------------------------------------------------------------------------
 // C ABI: misc + host-only helpers
 // ------------------------------------------------------------------------------------------------
 extern "C" const char *isingmc_last_error(void) { return g_last_error.c_str(); }

@@ -1,7 +1,7 @@
 // Internal declarations shared by the host translation units of libisingmc.so (not installed, not part of the C ABI):
 //   core.hip       error state, device-block / pinned-block / stream / event caches, environment helpers
 //   graph.hip      edge-list checks, host-only C ABI helpers, lattice / general / packed / real-coupling graph construction
-//   isingmc.hip    replica containers, the policy of every sweep / measurement launch, the persistent strip kernel's host side
+//   isingmc.hip    replica containers, every sweep / measurement launch (their policy: step_policy.hpp), the persistent strip kernel's host side
 //   nonlocal.hip   host side of the non-local moves: Swendsen-Wang steps, isoenergetic cluster moves inside and between containers
 //   overlaps.hip   spin and link overlaps between replica pairs (isingmc_overlaps), and the spin overlap by site class
 //                  (isingmc_site_classes_*, isingmc_overlaps_by_class); the overlap core they share with the series
@@ -61,6 +61,7 @@
 #include "owned_block.hpp"
 #include "real_types.hpp"
 #include "spread_types.hpp"
+#include "step_policy.hpp"
 #include "strip_types.hpp"
 #include "tempering_types.hpp"
 
@@ -96,6 +97,11 @@ IM_INTERNAL int stream_create(PooledStream &out);
 IM_INTERNAL int event_create(PooledEvent &out); // no timing: ordering between streams
 IM_INTERNAL int event_create(TimedEvent &out);  // with timing: the *_timed entry point
 IM_INTERNAL int use_device(int device);
+// the runtime's occupancy answers (workgroups per compute unit) behind one cache: each query is asked once per process
+IM_INTERNAL int cached_lat_sweep_loop_blocks_per_cu(bool pmj, unsigned lds_bytes, int rounds);
+IM_INTERNAL int cached_rj_measure_blocks_per_cu(uint32_t slots, bool bipartite, bool count_up);
+IM_INTERNAL int cached_strip_blocks_per_cu(bool pmj, int nw, bool ladder, size_t lds_bytes, int rounds);
+IM_INTERNAL int cached_spread_blocks_per_cu(bool vec, bool pmj, int lanes_per_quad, unsigned threads, size_t lds_bytes, int rounds);
 
 // ---- options.hpp: struct Options, the path / tuning switches of a graph or a container, and the environment helpers ----------
 
@@ -327,11 +333,6 @@ struct isingmc_states {
     std::vector<PooledEvent> lane_events;
     PooledEvent fork_event;
     size_t n_lanes = 1; // lanes in use by the current run_steps call
-    // workgroups of lat_sweep_loop_kernel<uniform J / +-J> the device holds at once with sweep_resident_lds bytes of LDS each
-    // (occupancy query x CUs, asked once; -1 = not asked yet)
-    int sweep_resident_wgs[2] = {-1, -1};
-    unsigned sweep_resident_lds = 0;
-    int sweep_resident_rounds = 10; // ... and of which round count (Options::philox_rounds)
     TimedEvent ev0, ev1;
     bool has_betas = false;
     std::vector<double> betas;
@@ -521,7 +522,8 @@ IM_INTERNAL void lat_measure_enqueue(isingmc_states *s, unsigned long long *out,
 IM_INTERNAL double pk_energy(const isingmc_graph *g, bool rj, unsigned long long c0, unsigned long long c1);
 IM_INTERNAL int pk_get_states(isingmc_states *s, uint8_t *states_out, size_t replica_stride_bytes, uint32_t *packed_out,
                               const uint32_t *d_words = nullptr); // d_words: a buffer laid out as d_state (nullptr: d_state itself)
-IM_INTERNAL StripPlan strip_plan(const isingmc_states *s, size_t timesteps, bool ladder = false);
+IM_INTERNAL step_policy::GraphFacts graph_facts(const isingmc_graph *g); // what step_policy.hpp reads of a graph
+IM_INTERNAL StripPlan strip_plan(const isingmc_states *s, size_t timesteps, bool ladder = false); // step_policy::strip_plan for this container
 IM_INTERNAL int launch_strip(isingmc_states *s, const StripPlan &P, size_t r0, size_t n, size_t nk, const LatThr *d_thr_steps, uint32_t thr_stride,
                              unsigned long long *steps_out, double *final_energies, const StripLadder *ladder = nullptr);
 IM_INTERNAL int strip_check(isingmc_states *s);

@@ -11,8 +11,45 @@
 static int lanes_reserve(isingmc_states *s, size_t n);
 static int lanes_fork(isingmc_states *s, size_t n);
 
+using step_policy::Family;
+using step_policy::StepPath;
+using step_policy::StepPlan;
+
+// the kernel headers' bounds as the policy header states them
+static_assert(step_policy::GEN_RESIDENT_BYTES == GEN_RESIDENT_MAX_BYTES && step_policy::LAT_RESIDENT_BYTES == LDS_RESIDENT_MAX_BYTES &&
+              step_policy::LAT_MEASURE_SLOTS == MEASURE_SLOTS && step_policy::PACKED_MAX_DEG == PK_MAX_DEG &&
+              step_policy::PACKED_MEASURE_POS == PK_MEASURE_POS_PER_THREAD && step_policy::STRIP_WAVES_PER_CU == STRIP_MAX_WAVES_PER_CU &&
+              step_policy::MC_MODE_NONE == MC_NONE, "step_policy.hpp restates a bound of a kernel header with another value");
+
+step_policy::GraphFacts graph_facts(const isingmc_graph *g)
+{
+    step_policy::GraphFacts f;
+    const bool lattice = g->kind == ISINGMC_KIND_LATTICE2D;
+    f.kind = lattice ? step_policy::GraphKind::Lattice2D : step_policy::GraphKind::General;
+    f.mc_mode = g->mc_mode;
+    f.nvars = g->nvars;
+    f.state_words = g->state_words;
+    f.wpr = g->geom.wpr; f.wpp = g->geom.wpp; f.H = g->geom.H; f.nquads = g->geom.nquads; f.cols_log2 = g->geom.cols_log2;
+    f.vec = g->vec;
+    f.uniform_sign = g->uniform_sign;
+    f.n_colours = g->n_colours;
+    for (size_t c = 0; c + 1 < g->class_base.size(); c++) f.largest_class = std::max<uint64_t>(f.largest_class, g->class_base[c + 1] - g->class_base[c]);
+    f.n_pos = g->pk.n_pos;
+    f.packed_ok = g->packed_ok;
+    f.rj_ok = g->rj_ok;
+    f.rj_slots = g->rj.slots;
+    f.pk_uni_deg = g->pk_uni_deg;
+    f.stable_path = g->stable_path;
+    f.n_cu = g->n_cu;
+    if (!lattice)
+        for (int mode = 1; mode <= 2; mode++)
+            f.gen_stage_words[mode] = gen_stage_words(g->gdev.n_pos, g->gen_edges2, g->gdev.bias != nullptr, g->w_is_float ? 4 : 8, mode);
+    return f;
+}
+
+static step_policy::ContainerFacts container_facts(const isingmc_states *s) { return {s->R, s->groups, s->packed, s->rj, s->strip.disabled}; }
+
 // replica-packed general path (defined further down)
-static int choose_packed(const isingmc_states *s, size_t n_replicas);
 static int pk_create(isingmc_states *s, const uint64_t *all_seeds, size_t first, size_t n, const uint8_t *initial_state);
 static int pk_set_state(isingmc_states *s, size_t replica, const uint8_t *spins);
 static int pk_set_betas(isingmc_states *s);
@@ -124,8 +161,9 @@ extern "C" int isingmc_states_create_range(isingmc_graph *g, size_t n_total, con
     s->n_total = n_total;
     s->first = first;
     s->opt = Options::from_env();
-    if (const int mode = count ? choose_packed(s.get(), n_total) : 0) {
-        s->rj = mode == 2;
+    const Family family = step_policy::choose_family(graph_facts(g), s->opt, count ? n_total : 0); // (an empty shard: one replica per word set)
+    if (family == Family::PackedBits || family == Family::PackedReal) {
+        s->rj = family == Family::PackedReal;
         TRY(pk_create(s.get(), all_seeds, first, count, initial_state));
     } else {
         TRY(reserve(s.get(), std::max<size_t>(count, 1)));
@@ -177,13 +215,7 @@ extern "C" int isingmc_states_family(const isingmc_states *s, int *family_out)
 extern "C" int isingmc_graph_family_for(const isingmc_graph *g, size_t n_experiments, int *family_out)
 {
     if (!g || !family_out) return fail(ISINGMC_ERR_INVALID, "NULL argument");
-    if (g->kind == ISINGMC_KIND_LATTICE2D) { *family_out = 0; return ISINGMC_OK; }
-    isingmc_states probe;
-    probe.g = const_cast<isingmc_graph *>(g);
-    probe.opt = Options::from_env();
-    const int mode = n_experiments ? choose_packed(&probe, n_experiments) : 0;
-    probe.g = nullptr; // (the probe owns nothing: its destructor must not touch the device)
-    *family_out = mode == 0 ? 1 : mode == 1 ? 2 : 3;
+    *family_out = int(step_policy::choose_family(graph_facts(g), Options::from_env(), n_experiments));
     return ISINGMC_OK;
 }
 
@@ -313,54 +345,6 @@ int set_betas(isingmc_states *s, const double *beta_per_replica, bool all_equal)
 // replica-packed general path (packed_kernels.hpp): state = uint32[groups][n_pos], group g = replicas
 // 32g .. 32g+31, keyed by the seed of its first replica
 // ------------------------------------------------------------------------------------------------
-
-// worth it from 16 replicas on and when the graph is too big for the LDS-resident per-replica kernel
-// LDS-resident kernel for small graphs only: one workgroup walks a whole replica, ~13 us + 2.8..5 ns per site
-// and timestep whatever the replica count, against ~5 us per colour class for the per-colour launches --
-// measured crossover ~8 000 sites at 4 replicas, ~14 000 at 64 (profiles/r01_resident_threshold.txt); a
-// 200 000-site graph ran 13x slower resident than streamed.
-static bool gen_resident_fits(const isingmc_graph *g, size_t n_replicas)
-{
-    return g->state_words * sizeof(uint32_t) <= GEN_RESIDENT_MAX_BYTES && g->nvars <= (n_replicas < 16 ? 8000u : 12000u);
-}
-
-// Packed or per-replica?  The packed kernels launch once per colour class and timestep; the LDS-resident CSR kernel runs a whole
-// call in one launch with one workgroup per replica, which wins on small graphs (they are bound by parallelism, and a word of 32
-// replicas concentrates them on few compute units).  Measured (profiles/r03_real_small.txt, r03_few_replicas.txt,
-// r03_packed_resident_experiment.txt; attempts/s of the packed path over the per-replica one):
-//  * real-coupling path, graphs the resident CSR kernel takes: 8 000 sites 1.7x at 16 replicas, 4 096 sites 1.0x at 64 and 1.5x at
-//    256, 1 728 sites 0.7x at 256 and 2.6x at 1 024, never at 1 024 sites; big graphs: 0.9x at 4 replicas, 1.5x at 8, 2.7x at 15;
-//  * bit-sliced path (a thread decides FOUR positions: a quarter of the threads): resident-size graphs 0.8x at 4 096 sites x 256,
-//    3.0x x 1 024; 0.67x at 8 000 x 256, 2.6x x 1 024; 13 824 sites 0.7x at 16 replicas, 1.2x at 64; 128^3: 1.4x at ONE replica.
-static bool packed_worth_it(const isingmc_graph *g, size_t n_replicas, bool real_path)
-{
-    const uint64_t work = uint64_t(g->nvars) * n_replicas; // attempts per timestep
-    const bool csr_resident = gen_resident_fits(g, n_replicas); // (the A/B switch ISINGMC_DISABLE_RESIDENT changes kernels, never the family)
-    if (real_path) {
-        // partial groups draw only their own replicas' Philox calls: 1.09x the CSR launches at ONE experiment (2048^2 Gaussian glass,
-        // profiles/r03_few_replicas.txt; re-measured in profiles/r04_real_eligibility.txt), 1.4x at 2, 2.0x at 4, 2.9x at 8
-        if (!csr_resident) return n_replicas >= 1;
-        return n_replicas >= 16 && (g->nvars >= 8000 || (g->nvars >= 1500 && work >= (uint64_t(3) << 19))); // 1.5 x 2^20: re-measured with the graph staged in LDS
-    }
-    return work >= (uint64_t(1) << (csr_resident ? 22 : 19));
-}
-
-// 0: one replica per word set (CSR kernels); 1: replica-packed bit-sliced path (S6); 2: replica-packed real-coupling path (S7)
-static int choose_packed(const isingmc_states *s, size_t n_replicas)
-{
-    const isingmc_graph *g = s->g;
-    const Options &o = s->opt;
-    if (g->rj_ok && !o.disable_real && (!g->packed_ok || o.force_real)) {
-        // (stable_path: the family follows from the graph alone -- experiment k must not change when the call asks for more of them)
-        if (o.force_real || g->stable_path) return n_replicas > 0 ? 2 : 0;
-        return packed_worth_it(g, n_replicas, true) ? 2 : 0;
-    }
-    if (!g->packed_ok || o.disable_packed) return 0;
-    // pk_sweep_kernel addresses the ELL table through one buffer descriptor with 32-bit byte offsets
-    if (uint64_t(g->pk.n_pos) * PK_MAX_DEG * sizeof(uint32_t) >= (uint64_t(1) << 31)) return 0;
-    if (o.force_packed || g->stable_path) return n_replicas > 0 ? 1 : 0;
-    return packed_worth_it(g, n_replicas, false) ? 1 : 0;
-}
 
 // threshold table of one group for per-replica betas (beta_of(r) for r = 0..31)
 template <typename F>
@@ -634,45 +618,13 @@ int pk_get_states(isingmc_states *s, uint8_t *states_out, size_t replica_stride_
 // ------------------------------------------------------------------------------------------------
 // sweeps
 // ------------------------------------------------------------------------------------------------
-// Quads per thread of a streaming half-sweep (1 = the one-quad kernel, else lat_sweep_loop_kernel), for a dispatch of `n`
-// replicas of the container's s->R.  A looping thread walks `iters` quads nquads / iters apart: that distance must be a whole,
-// even number of rows (the kernel carries the row parity and the column across its iterations), i.e. 2 * iters divides H.
-//  - resident-sized launch: the largest power of two <= 16 at which the workgroups of ALL lanes of the half-sweep together
-//    are a whole multiple, and at least twice, of the workgroups the device holds at once (occupancy query x CUs): every
-//    wave slot is refilled by the wave's own next quad, all workgroups are equally long and the rounds are whole, so there
-//    is no tail to quantise; the second round lets the CUs that ran ahead take more than their share.  4096^2 x 256 on 256
-//    CUs: 65536 one-quad workgroups, 2048 resident => 16 quads per thread, two rounds.  Measured there, same box, against
-//    two quads per thread: 16 quads +3.0 %, 8 quads +2.7 %, 32 quads (ONE round) +1.3 %; one lane instead of two: -7 % at
-//    16, -11 % at 32 (profiles/2026-10-17_resident_sweep_ab.txt);
-//  - else two quads per thread while that leaves >= 8 workgroups per CU (measured before the rule above existed: 2 quads +4 %,
-//    4 +2.7 %, 8 +1.3 % on uniform J; +-J: 2 quads +2.6 %).  Workgroups of 128 or 64 threads: no gain.
-// ISINGMC_SWEEP_ITERS=1|2|4|8|16|32 forces the choice (measurement and tests).
-static uint32_t sweep_loop_iters(isingmc_states *s, size_t n, unsigned lds_bytes)
-{
-    const LatGeom &geom = s->g->geom;
-    const bool pmj = !s->g->uniform_sign;
-    const auto fits = [&](uint32_t k) { return geom.nquads % (256 * k) == 0 && geom.H % (2 * k) == 0; };
-    const int forced = s->opt.sweep_iters;
-    if (forced) return forced > 1 && forced <= 32 && (forced & (forced - 1)) == 0 && fits(uint32_t(forced)) ? uint32_t(forced) : 1u;
-    if (s->sweep_resident_wgs[pmj] < 0 || s->sweep_resident_lds != lds_bytes || s->sweep_resident_rounds != s->opt.philox_rounds) {
-        s->sweep_resident_wgs[!pmj] = -1; // a container runs one of the two instantiations
-        s->sweep_resident_wgs[pmj] = lat_sweep_loop_blocks_per_cu(pmj, lds_bytes, s->opt.philox_rounds) * s->g->n_cu;
-        s->sweep_resident_lds = lds_bytes;
-        s->sweep_resident_rounds = s->opt.philox_rounds;
-    }
-    const size_t resident = size_t(s->sweep_resident_wgs[pmj]);
-    for (uint32_t k = 16; resident > 0 && k > 1; k >>= 1) {
-        if (!fits(k)) continue;
-        const size_t wgs = size_t(geom.nquads / (256 * k)) * s->R;
-        if (wgs >= 2 * resident && wgs % resident == 0) return k;
-    }
-    return fits(2) && size_t(geom.nquads / 512) * n >= size_t(8) * 256 ? 2u : 1u;
-}
-
-static int launch_lat_sweep(isingmc_states *s, uint32_t colour, const LatThr &thr, uint64_t t_arg)
+// resident_wgs: workgroups of the looping kernel the device holds at once (sweep_resident_wgs, once per run call)
+static int launch_lat_sweep(isingmc_states *s, const step_policy::GraphFacts &G, int resident_wgs, uint32_t colour, const LatThr &thr, uint64_t t_arg)
 {
     const isingmc_graph *g = s->g;
-    const bool uni = g->vec && g->geom.cols_log2 >= 0; // the division-free mapping: what the looping kernel needs
+    // diagnostic: ISINGMC_DEBUG_SWEEP_LDS=<bytes> of unused LDS per workgroup lowers the occupancy
+    const unsigned dbg_lds = unsigned(std::max(0, s->opt.debug_sweep_lds));
+    const bool uni = step_policy::uniform_mapping(G); // what the looping kernel needs
     // replicas are independent: with n_lanes > 1 the replica blocks go to different streams, so that the
     // launch gap / ramp / tail of one block's half-sweep overlaps the other blocks' work
     const size_t per_lane = (s->R + s->n_lanes - 1) / s->n_lanes;
@@ -681,9 +633,7 @@ static int launch_lat_sweep(isingmc_states *s, uint32_t colour, const LatThr &th
         hipStream_t stream = s->n_lanes > 1 ? s->lanes[lane] : s->stream;
         for (size_t r0 = lo; r0 < hi; r0 += MAX_GRID_Y) {
             const size_t n = std::min(MAX_GRID_Y, hi - r0);
-            // diagnostic: ISINGMC_DEBUG_SWEEP_LDS=<bytes> of unused LDS per workgroup lowers the occupancy
-            const unsigned dbg_lds = unsigned(std::max(0, s->opt.debug_sweep_lds));
-            const uint32_t iters = uni ? sweep_loop_iters(s, n, dbg_lds) : 1;
+            const uint32_t iters = uni ? step_policy::sweep_iters(G, s->opt, s->R, n, resident_wgs) : 1;
             HIP_TRY(lat_launch_sweep(g->vec, !g->uniform_sign, iters, uint32_t(n), dbg_lds, stream, s->d_state + r0 * g->state_words, g->geom,
                                      colour, t_arg, s->d_keys + r0, thr, s->has_betas ? s->d_thr + r0 : nullptr, g->d_jneg, g->jneg_uniform,
                                      s->opt.philox_rounds));
@@ -764,20 +714,14 @@ static int launch_lat_sweep_measure(isingmc_states *s, const LatThr &thr, uint64
     return ISINGMC_OK;
 }
 
+// one launch per colour class, step_policy::gen_replicas_per_thread replicas per thread
 static int launch_gen_timestep(isingmc_states *s, double beta)
 {
     const isingmc_graph *g = s->g;
     for (uint32_t c = 0; c < g->n_colours; c++) {
         const uint32_t b = uint32_t(g->class_base[c]), e = uint32_t(g->class_base[c + 1]);
         if (e == b) continue;
-        // replicas per thread: GEN_RB amortises the CSR stream of a big class; a class that would leave the chip
-        // short of workgroups (< 8 per CU) halves it until the grid is large enough
-        // (200 000 sites x 64 replicas: 56 us per launch at 8 replicas per thread)
-        size_t rb = GEN_RB;
-        const size_t blocks = (e - b + 255) / 256;
-        while (rb > 1 && (s->R < rb || blocks * ((s->R + rb - 1) / rb) < 2048)) rb /= 2;
-        // ISINGMC_GEN_RB_FORCE=1 / 2 / 4 / 8 (option gen_rb) forces, up to the compiled GEN_RB (tests, A/B runs): same results
-        if (const int f = s->opt.gen_rb; f == 1 || f == 2 || f == 4 || f == 8) rb = std::min<size_t>(size_t(f), GEN_RB);
+        const size_t rb = step_policy::gen_replicas_per_thread((e - b + 255) / 256, s->R, s->opt, GEN_RB);
         const size_t chunk = MAX_GRID_Y * rb;
         for (size_t r0 = 0; r0 < s->R; r0 += chunk) {
             const size_t n = std::min(chunk, s->R - r0);
@@ -799,42 +743,27 @@ int measure_enqueue(isingmc_states *s, unsigned long long *counts_slot, double *
         HIP_TRY(hipMemsetAsync(counts_slot, 0, 2 * s->pk_slots() * sizeof(unsigned long long), s->stream));
         if (s->rj) {
             const bool bip = g->n_colours == 2;
-            // all workgroups resident at once (the runtime's occupancy figure for this instantiation), every one walks its
-            // share of the blocks; a grid one round and a bit long would run its tail at a fraction of the chip
-            static std::mutex per_cu_mutex; // (the device fan-out measures from several host threads)
-            static int per_cu[6][2][2] = {};
-            int pc;
-            {
-                std::lock_guard<std::mutex> lock(per_cu_mutex);
-                int &slot = per_cu[g->rj.slots == 4 ? 0 : g->rj.slots == 7 ? 1 : g->rj.slots == 11 ? 2 : g->rj.slots == 15 ? 3 : g->rj.slots == 23 ? 4 : 5][bip][want_up];
-                if (slot == 0) slot = std::max(1, rj_measure_blocks_per_cu(g->rj.slots, bip, want_up));
-                pc = slot;
-            }
-            // ISINGMC_REAL_MEASURE_WGS=<n> (option real_measure_wgs) replaces the figure (tests, A/B runs): exact integer sums, same results
-            const size_t resident = s->opt.real_measure_wgs > 0 ? size_t(s->opt.real_measure_wgs) : size_t(pc) * size_t(std::max(g->n_cu, 1));
+            const int per_cu = std::max(1, cached_rj_measure_blocks_per_cu(g->rj.slots, bip, want_up));
             // two colour classes: the bonds from class 0 alone; class 1 is visited only for its bias terms or the up spins
             const uint32_t class0_end = bip ? uint32_t(g->class_base[1]) : 0u;
             const uint32_t scan_end = bip && !g->has_bias && !want_up ? class0_end : g->pk.n_pos;
             const size_t scan_blocks = scan_end / rj_threads(g->rj.slots);
             for (size_t g0 = 0; g0 < s->groups; g0 += MAX_GRID_Y) {
                 const size_t ng = std::min(MAX_GRID_Y, s->groups - g0);
-                const size_t gx = std::min(scan_blocks, std::max<size_t>(1, resident / ng));
+                const size_t gx = step_policy::rj_measure_grid_x(g->n_cu, s->opt, per_cu, scan_blocks, ng);
                 // hi level (+ the up spins when wanted) into the first counter of a slot, lo level into the second
-                HIP_TRY(rj_launch_measure(dim3(unsigned(std::max<size_t>(gx, 1)), unsigned(ng)), s->stream, s->d_state + g0 * g->pk.n_pos, g->rj_hi,
+                HIP_TRY(rj_launch_measure(dim3(unsigned(gx), unsigned(ng)), s->stream, s->d_state + g0 * g->pk.n_pos, g->rj_hi,
                                           g->pk.site, class0_end, scan_end, want_up, counts_slot + 2 * 32 * g0));
                 if (!want_up)
-                    HIP_TRY(rj_launch_measure(dim3(unsigned(std::max<size_t>(gx, 1)), unsigned(ng)), s->stream, s->d_state + g0 * g->pk.n_pos, g->rj_lo,
+                    HIP_TRY(rj_launch_measure(dim3(unsigned(gx), unsigned(ng)), s->stream, s->d_state + g0 * g->pk.n_pos, g->rj_lo,
                                               g->pk.site, class0_end, scan_end, false, counts_slot + 2 * 32 * g0 + 1));
             }
             return ISINGMC_OK;
         }
-        uint32_t ppt = PK_MEASURE_POS_PER_THREAD; // halved until the launch has >= 1024 workgroups (not below 8: the transpose
-                                                  // at the end of a chunk costs as much as ~16 positions)
-        while (ppt > 8 && size_t((g->pk.n_pos + 256 * ppt - 1) / (256 * ppt)) * s->groups < 1024) ppt /= 2;
-        const unsigned blocks = unsigned(std::max<uint32_t>(1, std::min<uint32_t>(2048, (g->pk.n_pos + 256 * ppt - 1) / (256 * ppt))));
+        const step_policy::PkMeasureGrid grid = step_policy::pk_measure_grid(g->pk.n_pos, s->groups);
         for (size_t g0 = 0; g0 < s->groups; g0 += MAX_GRID_Y) {
             const size_t ng = std::min(MAX_GRID_Y, s->groups - g0);
-            HIP_TRY(pk_launch_measure(blocks, uint32_t(ng), s->stream, s->d_state + g0 * g->pk.n_pos, g->pk, counts_slot + 2 * 32 * g0, ppt,
+            HIP_TRY(pk_launch_measure(grid.blocks, uint32_t(ng), s->stream, s->d_state + g0 * g->pk.n_pos, g->pk, counts_slot + 2 * 32 * g0, grid.pos_per_thread,
                                       g->n_colours == 2 ? uint32_t(g->class_base[1]) : g->pk.n_pos, g->n_colours == 2 ? 2u : 1u));
         }
     } else if (g->kind == ISINGMC_KIND_LATTICE2D) {
@@ -887,63 +816,30 @@ static int measure(isingmc_states *s, double *energies, int64_t *mags)
     return ISINGMC_OK;
 }
 
-// ISINGMC_DISABLE_RESIDENT=1 (at creation): always use the per-colour launches (A/B runs, parity tests of both paths)
-static bool resident_disabled(const isingmc_states *s) { return s->opt.disable_resident != 0; }
-
 // ------------------------------------------------------------------------------------------------
-// persistent strip kernel (strip_kernels.hpp): when and how
+// persistent strip kernel (strip_kernels.hpp): when and how is step_policy::strip_plan; here its host side
 // ------------------------------------------------------------------------------------------------
-
-// Mid-size lattices only: a per-colour launch of the streaming kernel must be short enough for the ~5 us it loses
-// between dependent launches to matter (<= ISINGMC_STRIP_MAX_WG workgroups in all, default the resident limit), the geometry must cut into strips of 256 quads with at least two strips per replica, and the poll of a
-// half-sweep must fit one workgroup (2 rows of <= 128 words).  ISINGMC_STRIP=0 disables, =1 forces (tests, A/B runs).
-// resident workgroups per CU, cached per instantiation and LDS size (the occupancy query is a runtime call)
-static int strip_resident_blocks_per_cu(bool pmj, int nw, bool ladder, size_t lds, int rounds)
+static StripPlan to_strip_plan(const step_policy::StripChoice &c)
 {
-    static std::mutex mu;
-    static std::vector<std::pair<uint64_t, int>> cache;
-    const uint64_t key = (uint64_t(lds) << 8) | (uint64_t(rounds == 7) << 3) | (uint64_t(pmj) << 2) | (uint64_t(ladder) << 1) | uint64_t(nw == 1);
-    std::lock_guard<std::mutex> lock(mu);
-    for (const auto &e : cache)
-        if (e.first == key) return e.second;
-    const int n = strip_blocks_per_cu(pmj, nw, ladder, lds, rounds);
-    cache.emplace_back(key, n);
-    return n;
+    StripPlan P;
+    P.use = c.use;
+    P.nw = c.nw;
+    P.a.S = c.S;
+    P.a.n_strips = c.n_strips;
+    P.a.qpr_log2 = c.qpr_log2;
+    P.replicas_per_pass = c.replicas_per_pass;
+    return P;
+}
+
+// the occupancy figure of the strip instantiation this container would launch
+static auto strip_occupancy(const isingmc_states *s, bool ladder)
+{
+    return [s, ladder](int nw, size_t lds) { return cached_strip_blocks_per_cu(!s->g->uniform_sign, nw, ladder, lds, s->opt.philox_rounds); };
 }
 
 StripPlan strip_plan(const isingmc_states *s, size_t timesteps, bool ladder)
 {
-    StripPlan P;
-    const isingmc_graph *g = s->g;
-    const int mode = s->opt.strip;
-    if (mode == 0 || s->strip.disabled || g->kind != ISINGMC_KIND_LATTICE2D || !g->vec || timesteps < 2) return P;
-    const uint32_t qpr = g->geom.wpr / 4;
-    if ((qpr & (qpr - 1)) != 0 || qpr > 32) return P; // power of two, at least two rows per wave
-    P.nw = s->opt.strip_nw == 1 ? 1 : 4; // measured on 1024^2 x 64 (round 4, with wave priorities): 8.4 (4) / 8.6 (1) us per timestep; with exchange rounds 10.4 (4) / 12.0 (1)
-    const uint32_t S = 64 * uint32_t(P.nw) / qpr;
-    if (g->geom.H % S != 0 || g->geom.H / S < 2) return P;
-    // Every workgroup of a launch must be resident at once.  Per CU: what the runtime's occupancy calculation grants this
-    // instantiation with its dynamic LDS (registers, LDS, wave slots), and never more than the policy bound of
-    // STRIP_MAX_WAVES_PER_CU waves (beyond it the per-colour launches are faster anyway).
-    const size_t lds = (size_t(2) * (S + 2) * g->geom.wpr + 16) * sizeof(uint32_t);
-    const int by_occupancy = strip_resident_blocks_per_cu(!g->uniform_sign, P.nw, ladder, lds, s->opt.philox_rounds);
-    const size_t per_cu = std::min<size_t>(size_t(STRIP_MAX_WAVES_PER_CU) / size_t(P.nw), size_t(std::max(by_occupancy, 0)));
-    const size_t limit = per_cu * size_t(std::max(g->n_cu, 1)); // workgroups resident at once
-    const size_t n_strips = g->geom.H / S, total = s->R * n_strips;
-    if (limit == 0 || n_strips > limit) return P;
-    // one pass only by default: with twice the replicas (1024^2 x 128) the per-colour launches are long enough to win (16.7 vs 18.6 us)
-    if (mode != 1 && total > size_t(s->opt.strip_max_wg >= 0 ? s->opt.strip_max_wg : int(limit))) return P;
-    const size_t passes = (total + limit - 1) / limit;
-    P.replicas_per_pass = (s->R + passes - 1) / passes;
-    while (P.replicas_per_pass * n_strips > limit) P.replicas_per_pass--;
-    if (P.replicas_per_pass == 0) return P;
-    P.a.S = S;
-    P.a.n_strips = uint32_t(n_strips);
-    uint32_t ql = 0;
-    while ((1u << ql) < qpr) ql++;
-    P.a.qpr_log2 = ql;
-    P.use = true;
-    return P;
+    return to_strip_plan(step_policy::strip_plan(graph_facts(s->g), s->opt, s->R, s->strip.disabled, timesteps, strip_occupancy(s, ladder)));
 }
 
 // strip launches of one process on one device never overlap: each needs all its workgroups resident at once
@@ -989,7 +885,7 @@ int launch_strip(isingmc_states *s, const StripPlan &P, size_t r0, size_t n, siz
     StripArgs a = P.a;
     a.epoch = s->strip.epoch;
     a.xcd_remap = n % 8 == 0;
-    const size_t lds = (size_t(2) * (a.S + 2) * g->geom.wpr + 16) * sizeof(uint32_t);
+    const size_t lds = step_policy::strip_lds_bytes(a.S, g->geom.wpr);
     {
         std::lock_guard<std::mutex> lock(g_strip_mutex);
         hipEvent_t &ev = g_strip_done[g->device & 63];
@@ -1069,85 +965,18 @@ int run_steps(isingmc_states *s, size_t timesteps, const double *betas, size_t b
 }
 
 // ------------------------------------------------------------------------------------------------
-// run_steps: one plan per call (kernel path, chunk of timesteps, replica lanes), one runner per path for each chunk
+// run_steps: one plan per call (step_policy::plan_steps: kernel path, chunk of timesteps, replica lanes), one runner per path for each chunk
 // ------------------------------------------------------------------------------------------------
-enum class StepPath { Packed, LatResident, LatStrip, LatStream, McResident, McStream, GenResident, GenCsr };
-
-struct StepPlan {
-    StepPath path = StepPath::GenCsr;
-    size_t chunk = 0;      // timesteps per runner call (per-step energies are read back chunk by chunk)
-    size_t step_slots = 1; // per-step counter slots per replica: the streaming kernels measure into MEASURE_SLOTS partial counters
-    size_t lanes = 1;      // replica lanes (streams)
-    StripPlan strip;
-};
-
-// small lattices: one LDS-resident launch per chunk of timesteps instead of two launches per timestep (up to 1024 quads per
-// colour: beyond that one workgroup per replica is slower than the launches it saves); the multi-class kernels' bound too
-static bool lat_resident_fits(const isingmc_states *s)
-{
-    const isingmc_graph *g = s->g;
-    return g->state_words * sizeof(uint32_t) <= LDS_RESIDENT_MAX_BYTES && g->geom.nquads <= 1024 && !resident_disabled(s);
-}
-
-static StepPlan plan_steps(const isingmc_states *s, size_t timesteps, bool energies_per_step)
-{
-    const isingmc_graph *g = s->g;
-    const size_t R = s->R;
-    StepPlan P;
-    if (s->packed) {
-        P.path = StepPath::Packed;
-        P.chunk = std::min<size_t>(timesteps, 2048);
-        // The replica groups are independent: mid-size launches (a few waves per SIMD: the 64^3 glass x 64 replicas puts ONE wave on a
-        // SIMD per colour-class launch) leave the chip idle around every kernel boundary, so the groups go to several streams and one
-        // lane's launch gap / ramp / tail overlaps the other lanes' work (as the lattice path's replica lanes).  ISINGMC_PK_STREAMS=<n> forces.
-        if (!energies_per_step && s->groups >= 2) {
-            uint64_t biggest = 0;
-            for (uint32_t c = 0; c < g->n_colours; c++) biggest = std::max<uint64_t>(biggest, g->class_base[c + 1] - g->class_base[c]);
-            const uint64_t waves_per_launch = s->groups * biggest / (s->rj ? 64 : 256); // a thread decides 1 (real) / 4 (bit-sliced) positions
-            const int forced = s->opt.pk_streams;
-            if (forced > 0) P.lanes = size_t(forced);
-            // measured (tools/pk_lanes_ab.py, profiles/r03_pk_lanes_ab.txt): two lanes +7 % (2048^2 x 256) to +43 % (512^2 x 64) from ~2 000 waves per
-            // launch on, -3..-13 % below (32^3 x 64: the launches are too short for the fork / join); four lanes: worse than two almost everywhere
-            // Short calls (the 10-timestep blocks between tempering rounds) double their launch count with lanes and run into the host's
-            // launch rate sooner: 64^3 x 64 rungs went from 24.5 to 31 us per timestep; they take lanes only for long launches
-            else if (timesteps >= 64 ? waves_per_launch >= 2048 : timesteps >= 4 && waves_per_launch >= 16384) P.lanes = 2;
-            P.lanes = std::min(P.lanes, s->groups);
-        }
-        return P;
-    }
-    if (g->kind != ISINGMC_KIND_LATTICE2D) P.path = gen_resident_fits(g, R) && !resident_disabled(s) ? StepPath::GenResident : StepPath::GenCsr;
-    // lattices with a field or open boundaries: the multi-class kernels
-    else if (g->mc_mode != MC_NONE) P.path = lat_resident_fits(s) ? StepPath::McResident : StepPath::McStream;
-    else if (lat_resident_fits(s)) P.path = StepPath::LatResident;
-    else {
-        P.strip = strip_plan(s, timesteps);
-        P.path = P.strip.use ? StepPath::LatStrip : StepPath::LatStream;
-    }
-    if (energies_per_step && P.path == StepPath::LatStream) P.step_slots = MEASURE_SLOTS;
-    // per-step counters: 16 B per (step, replica) and counter slot, at most 32 MiB per chunk on each side of the bus
-    P.chunk = energies_per_step ? std::max<size_t>(1, std::min<size_t>(timesteps, (size_t(32) << 20) / (16 * R * P.step_slots))) : timesteps;
-    if (P.path == StepPath::LatResident || P.path == StepPath::LatStrip || P.path == StepPath::McResident || P.path == StepPath::GenResident)
-        P.chunk = std::min<size_t>(P.chunk, 65536);
-    // mid-size launches (a few waves per SIMD) leave the GPU idle around every kernel boundary: run the
-    // replica blocks on several streams.  Large launches (c2) keep the chip full on one stream.
-    if ((P.path == StepPath::LatStream || P.path == StepPath::McStream) && !energies_per_step) {
-        const size_t waves_per_launch = R * ((g->geom.nquads + 255) / 256) * 4;
-        if (s->opt.streams > 0) P.lanes = size_t(s->opt.streams);
-        // < 64 waves per SIMD per launch: +17..33 % with 2 lanes (4 go host-bound); short calls lose it to fork/join.
-        // Large launches: +2.8 % (one block's drain overlaps the other's ramp); the fork/join is ~45 us per call
-        else if (waves_per_launch < 64 * 1024 ? timesteps >= 64 : timesteps >= 8) P.lanes = 2;
-        P.lanes = std::min(P.lanes, R);
-    }
-    return P;
-}
-
 // one run_steps call: its arguments, its plan and its scratch (freed on every exit path, after the stream has drained)
 struct StepRun {
     isingmc_states *s;
+    step_policy::GraphFacts G; // what the plan and the runners' launch shapes are decided from
     StepPlan P;
     const double *betas;
     size_t beta_stride, timesteps;
     double *energies_per_step, *final_energies;
+    StripPlan strip = to_strip_plan(P.strip);
+    int sweep_resident_wgs = 0; // streaming sweeps: workgroups of lat_sweep_loop_kernel the device holds at once (occupancy x CUs)
     DeviceScratch scratch{s->stream};
     unsigned long long *d_counts = nullptr; // per-step counters [chunk][counter slots][step_slots][2] (lattice and packed paths)
     double *d_energies = nullptr;           // per-step energies [chunk x R] (general paths)
@@ -1252,30 +1081,15 @@ static int run_lat_resident(StepRun &c, size_t k0, size_t nk)
     const isingmc_graph *g = s->g;
     const size_t R = s->R;
     TRY(upload_lat_thresholds(c, k0, nk));
-    // small lattices: eight (four, two) lanes per quad, one (two, four) Philox calls each (lat_resident_spread_kernel)
-    // ... while every replica of the call is resident at once: beyond that the one-lane-per-quad kernel's small workgroups fill
-    // the chip better (measured, tools/small_lattice_spread_ab.py: 64^2 x 2048 4.1 against 5.9 us, x 4096 10.5 against 9.1;
-    // 128^2 x 512 4.4 against 5.4, x 1024 8.7 against 5.3).  ISINGMC_RESIDENT_SPREAD=0 / 2: never / whenever the lattice allows
-    const int spread_mode = s->opt.resident_spread;
-    // eight lanes per quad only: with four or two (256 / 512 quads per colour, 1024 threads) the barriers of a 16-wave workgroup
-    // cost more than the shorter chain saves (256^2 x 64: 5.7 against 5.1 us; ISINGMC_RESIDENT_LPQ=4 / 2 for A/B runs)
-    const int lpq_forced = s->opt.resident_lpq;
-    const int lpq = lpq_forced == 4 || lpq_forced == 2 ? lpq_forced : 8;
-    bool spread = spread_mode != 0 && size_t(g->geom.nquads) * size_t(lpq) <= 1024;
-    const unsigned spread_threads = unsigned((size_t(g->geom.nquads) * size_t(lpq) + 63) / 64 * 64);
-    const size_t spread_lds = g->state_words * sizeof(uint32_t) + size_t(g->geom.nquads) * 8 * sizeof(uint4);
-    if (spread && spread_mode != 2) {
-        const int per_cu = spread_blocks_per_cu(g->vec, !g->uniform_sign, lpq, spread_threads, spread_lds, s->opt.philox_rounds);
-        spread = per_cu > 0 && R <= size_t(g->n_cu) * size_t(per_cu);
-    }
-    const unsigned threads = spread ? spread_threads : unsigned(std::min<size_t>(1024, (g->geom.nquads + 63) / 64 * 64));
-    const size_t lds = spread ? spread_lds : g->state_words * sizeof(uint32_t);
-    if (spread) {
-        HIP_TRY(spread_launch(g->vec, !g->uniform_sign, lpq, unsigned(R), threads, lds, s->stream, s->d_state, g->geom, s->t, uint32_t(nk), s->d_keys,
+    const step_policy::LatResidentLaunch L = step_policy::lat_resident_launch(c.G, s->opt, R, [&](int lpq, unsigned threads, size_t lds) {
+        return cached_spread_blocks_per_cu(g->vec, !g->uniform_sign, lpq, threads, lds, s->opt.philox_rounds);
+    });
+    if (L.spread) {
+        HIP_TRY(spread_launch(g->vec, !g->uniform_sign, L.lpq, unsigned(R), L.threads, L.lds_bytes, s->stream, s->d_state, g->geom, s->t, uint32_t(nk), s->d_keys,
                               c.d_thr, uint32_t(c.beta_stride ? 1 : 0), s->has_betas ? s->d_thr : nullptr, g->d_jneg, g->jneg_uniform,
                               c.d_counts, uint32_t(R), s->opt.philox_rounds));
     } else {
-        HIP_TRY(lat_launch_resident(g->vec, !g->uniform_sign, unsigned(R), threads, lds, s->stream, s->d_state, g->geom, s->t, uint32_t(nk),
+        HIP_TRY(lat_launch_resident(g->vec, !g->uniform_sign, unsigned(R), L.threads, L.lds_bytes, s->stream, s->d_state, g->geom, s->t, uint32_t(nk),
                                     s->d_keys, c.d_thr, uint32_t(c.beta_stride ? 1 : 0), s->has_betas ? s->d_thr : nullptr, g->d_jneg,
                                     g->jneg_uniform, c.d_counts, s->opt.philox_rounds));
     }
@@ -1292,8 +1106,8 @@ static int run_lat_strip(StepRun &c, size_t k0, size_t nk)
     TRY(upload_lat_thresholds(c, k0, nk));
     // final_energies (device, [R]): the energies of the final configurations come with the last launch (tempering rounds)
     const bool last = k0 + nk == c.timesteps;
-    for (size_t r0 = 0; r0 < R; r0 += c.P.strip.replicas_per_pass)
-        TRY(launch_strip(s, c.P.strip, r0, std::min(c.P.strip.replicas_per_pass, R - r0), nk, c.d_thr, uint32_t(c.beta_stride ? 1 : 0),
+    for (size_t r0 = 0; r0 < R; r0 += c.strip.replicas_per_pass)
+        TRY(launch_strip(s, c.strip, r0, std::min(c.strip.replicas_per_pass, R - r0), nk, c.d_thr, uint32_t(c.beta_stride ? 1 : 0),
                          c.d_counts ? c.d_counts + 2 * r0 : nullptr, last ? c.final_energies : nullptr));
     s->strip.epoch += uint32_t(2 * nk);
     s->t += nk;
@@ -1315,17 +1129,10 @@ static int run_mc_resident(StepRun &c, size_t k0, size_t nk)
         TRY(thr_scratch.alloc(&d_thr_mc_steps, h.size()));
         HIP_TRY(hipMemcpy(d_thr_mc_steps, h.data(), h.size() * sizeof(LatThrMC), hipMemcpyHostToDevice));
     }
-    // small lattices, few enough replicas to be resident at once: eight lanes per quad (lat_mc_resident_kernel SPREAD; the
-    // kernel takes the spread form when the launch's LDS holds the random words too).  ISINGMC_RESIDENT_SPREAD=0: off
-    const int mc_spread_mode = s->opt.resident_spread;
-    const size_t spread_threads = (size_t(g->geom.nquads) * 8 + 63) / 64 * 64;
-    const bool mc_spread = mc_spread_mode != 0 && spread_threads <= 1024 &&
-                           (mc_spread_mode == 2 || R <= size_t(g->n_cu) * std::max<size_t>(1, 1024 / spread_threads));
-    const unsigned threads = mc_spread ? unsigned(spread_threads) : unsigned(std::min<size_t>(1024, (g->geom.nquads + 63) / 64 * 64));
-    const size_t mc_lds = g->state_words * sizeof(uint32_t) + (mc_spread ? size_t(g->geom.nquads) * 8 * sizeof(uint4) : 0);
+    const step_policy::LatResidentLaunch L = step_policy::mc_resident_launch(c.G, s->opt, R);
     for (size_t r0 = 0; r0 < R; r0 += 65535) {
         const size_t n = std::min<size_t>(65535, R - r0);
-        HIP_TRY(mc_launch_resident(g->mc_mode, !g->uniform_sign, unsigned(n), threads, mc_lds,
+        HIP_TRY(mc_launch_resident(g->mc_mode, !g->uniform_sign, unsigned(n), L.threads, L.lds_bytes,
                                    s->stream, s->d_state + r0 * g->state_words, g->geom, s->t, uint32_t(nk), s->d_keys + r0,
                                    d_thr_mc_steps, uint32_t(c.beta_stride ? 1 : 0),
                                    s->has_betas ? s->d_thr_mc + r0 : nullptr, g->d_jneg, g->jneg_uniform, g->open, g->d_fneg,
@@ -1342,32 +1149,8 @@ static int run_gen_resident(StepRun &c, size_t k0, size_t nk)
     const size_t R = s->R;
     const size_t nb = c.beta_stride ? nk : 1;
     if (!s->has_betas) HIP_TRY(hipMemcpyAsync(c.d_betas, c.betas + k0 * c.beta_stride, nb * sizeof(double), hipMemcpyHostToDevice, s->stream));
-    unsigned threads = 64;
-    for (uint32_t col = 0; col < g->n_colours; col++)
-        threads = std::max<unsigned>(threads, unsigned(std::min<uint64_t>(1024, g->class_base[col + 1] - g->class_base[col])));
-    // the graph in LDS too (gen_resident_kernel STAGE) while every replica of the call can still be resident at once (160 KB
-    // of LDS per compute unit): small graphs, where a timestep is a chain of dependent loads.  Everything when that fits,
-    // else the topology alone (the links of the chain); ISINGMC_GEN_STAGE=0 / 1 / 2 forces none / all / topology (A/B runs)
-    const int stage_mode = s->opt.gen_stage;
-    const size_t lds_cu = 160 * 1024, lds_max = 150 * 1024; // (a few KB stay free for the kernel's static LDS)
-    size_t stage_bytes = 0;
-    int stage = 0;
-    {
-        size_t bytes[3] = {0, 0, 0}, resident[3] = {0, 0, 0};
-        for (int mode = 1; mode <= 2; mode++) {
-            bytes[mode] = size_t(gen_stage_words(g->gdev.n_pos, g->gen_edges2, g->gdev.bias != nullptr, g->w_is_float ? 4 : 8, mode)) * 4;
-            if (bytes[mode] <= lds_max) resident[mode] = std::min<size_t>(2048 / threads, lds_cu / (bytes[mode] + 1024)); // workgroups per compute unit
-        }
-        if (stage_mode == 0) stage = 0;
-        else if (stage_mode == 1 || stage_mode == 2) stage = resident[stage_mode] ? stage_mode : 0;
-        else if (resident[1] && (R <= size_t(g->n_cu) * resident[1] || threads > 512 || resident[2] <= resident[1])) stage = 1;
-        // (measured, tools/small_graph_stage_ab.py: workgroups of <= 512 threads gain from running side by side, so when
-        //  the full copy would keep some of the call's replicas waiting the smaller one wins: 32^2 x 1024 5.7 against
-        //  6.2 us, 8^3 x 1024 3.5 against 4.4; 1024-thread workgroups do not: 12^3 x 512 6.6 against 9.4)
-        else if (resident[2]) stage = 2;
-        stage_bytes = bytes[stage];
-    }
-    HIP_TRY(gen_launch_resident(g->w_is_float, stage, unsigned(R), threads, stage ? stage_bytes : g->state_words * sizeof(uint32_t), s->stream,
+    const step_policy::GenResidentLaunch L = step_policy::gen_resident_launch(c.G, s->opt, R);
+    HIP_TRY(gen_launch_resident(g->w_is_float, L.stage, unsigned(R), L.threads, L.lds_bytes, s->stream,
                                 s->d_state, g->gdev, s->t, uint32_t(nk), s->d_keys, c.d_betas, uint32_t(c.beta_stride ? 1 : 0),
                                 s->has_betas ? s->d_beta : nullptr, c.d_energies, g->self_energy, g->gen_edges2));
     s->t += nk;
@@ -1382,9 +1165,9 @@ static int run_lat_stream(StepRun &c, size_t k0, size_t nk)
     const size_t R = s->R, SS = c.P.step_slots;
     for (size_t k = k0; k < k0 + nk; k++) {
         const LatThr thr = lattice_thresholds(step_beta(c, k), s->g->jabs);
-        TRY(launch_lat_sweep(s, 0u, thr, s->t));
+        TRY(launch_lat_sweep(s, c.G, c.sweep_resident_wgs, 0u, thr, s->t));
         if (c.d_counts) TRY(launch_lat_sweep_measure(s, thr, s->t, c.d_counts + (k - k0) * R * 2 * SS, 2 * SS));
-        else TRY(launch_lat_sweep(s, 1u, thr, s->t));
+        else TRY(launch_lat_sweep(s, c.G, c.sweep_resident_wgs, 1u, thr, s->t));
         s->t++;
     }
     return ISINGMC_OK;
@@ -1481,8 +1264,12 @@ static int run_steps_impl(isingmc_states *s, size_t timesteps, const double *bet
     if (R == 0) s->t += timesteps; // time passes for an empty container too (replicas appended later start here)
     if (R == 0 || timesteps == 0) return ISINGMC_OK;
     s->meas_fresh = false;
-    StepRun c{s, plan_steps(s, timesteps, energies_per_step != nullptr), betas, beta_stride, timesteps, energies_per_step, final_energies};
+    const step_policy::GraphFacts G = graph_facts(s->g);
+    StepRun c{s, G, step_policy::plan_steps(G, s->opt, container_facts(s), timesteps, energies_per_step != nullptr, strip_occupancy(s, false)),
+              betas, beta_stride, timesteps, energies_per_step, final_energies};
     const StepPlan &P = c.P;
+    if (P.path == StepPath::LatStream && step_policy::sweep_iters_reads_residency(G, s->opt))
+        c.sweep_resident_wgs = cached_lat_sweep_loop_blocks_per_cu(!s->g->uniform_sign, unsigned(std::max(0, s->opt.debug_sweep_lds)), s->opt.philox_rounds) * s->g->n_cu;
     const size_t n_tabs = s->has_betas ? 0 : beta_stride ? P.chunk : 1;
     if (s->step_preset) { // the caller's device tables of this call's ONE beta (a population-annealing schedule): nothing to upload
         if (beta_stride || s->has_betas) return fail(ISINGMC_ERR_INVALID, "preset step tables serve one beta per call");

@@ -205,12 +205,8 @@ extern "C" int isingmc_pt_run(isingmc_states *s, size_t timesteps, size_t swap_e
     const isingmc_graph *g = s->g;
     const size_t rounds = timesteps / swap_every, tail = timesteps % swap_every;
     const StripPlan P = s->R ? strip_plan(s, rounds * swap_every, /*ladder=*/true) : StripPlan{};
-    const bool in_kernel = P.use && P.replicas_per_pass >= s->R && rounds >= 2 && rounds * swap_every <= 65536 &&
-                           s->R == s->pt.n_rungs && s->opt.pt_in_kernel != 0 &&
-                           // minimum tracking reads every round's energies, sums per rung (S19) and the periodic series
-                           // (S21, S22) the configurations and the permutation between the rounds: one launch per round
-                           !recorders_any_on(s);
-    if (in_kernel) {
+    const size_t inside = step_policy::pt_rounds_in_kernel(P.use, P.replicas_per_pass, s->opt, s->R, s->pt.n_rungs, rounds, swap_every, recorders_any_on(s));
+    if (inside) {
         const size_t R = s->R, nk = rounds * swap_every;
         if (!s->strip.d_pt_mail) {
             TRY(dev_alloc(s->strip.d_pt_mail, 4 * R));
@@ -228,7 +224,7 @@ extern "C" int isingmc_pt_run(isingmc_states *s, size_t timesteps, size_t swap_e
                               s->pt.seed_hi, g->jabs, 2ll * (long long)g->nvars, s->pt.stats};
         s->meas_fresh = false;
         TRY(launch_strip(s, P, 0, R, nk, nullptr, 0, nullptr, s->tempering.d_all + s->pt.slot_offset, &lad));
-        if (s->tempering.stats_on) s->tempering.in_kernel_rounds += rounds - 1; //  the launch's strips count these rounds themselves
+        if (s->tempering.stats_on) s->tempering.in_kernel_rounds += inside; //  the launch's strips count these rounds themselves
         s->strip.epoch += uint32_t(2 * nk);
         s->t += nk;
         s->meas_fresh = true; // the launch wrote the final energies

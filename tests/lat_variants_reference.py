@@ -21,7 +21,7 @@ from mc_variants_reference import cols_log2, edge_lines, exact_energy_mag, geome
 
 MEASURE_SLOTS = 16                        # lattice_types.hpp
 MEASURE_QUADS_PER_THREAD = 16             # lattice_types.hpp
-RESIDENT_CHUNK = 65536                    # isingmc.hip, plan_steps: P.chunk = std::min<size_t>(P.chunk, 65536) on the resident paths
+RESIDENT_CHUNK = 65536                    # step_policy.hpp, plan_steps: P.chunk = std::min<size_t>(P.chunk, 65536) on the resident paths
 LDS_PER_CU = 160 * 1024                   # gfx950
 
 # beta 0 and a negative beta: every spin of both classes flips outright; 0.4407: both classes are costly; 3.0: the top threshold
@@ -118,7 +118,7 @@ def oracle_lat(O, case):
 
 # ---- the library's selection rules, restated ---------------------------------------------------------------------------------------
 def vec(W, H):
-    """graph.hip, build_lattice:  g->vec = G.wpr % 4 == 0;   (`cols_log2` is only looked for `if (g->vec)`: MV.cols_log2 divides
+    """step_policy.hpp, lattice_shape (which graph.hip builds the lattice from):  G.vec = G.wpr % 4 == 0;   (`cols_log2` is only looked for `if (g->vec)`: MV.cols_log2 divides
     wpr by four first, so it is asked behind `vec` here too)"""
     return geometry(W, H)[0] % 4 == 0
 
@@ -136,14 +136,15 @@ def fast_path_ok(W, H):
 
 
 def resident_launch(W, H, options):
-    """(spread, lpq, threads, lds_bytes) of isingmc.hip, run_lat_resident (lpq = 0 without the spread form):
+    """(spread, lpq, threads, lds_bytes) of step_policy.hpp, lat_resident_launch (lpq = 0 without the spread form;
+    tests/test_step_policy_host.py holds this restatement against it):
         const int lpq = lpq_forced == 4 || lpq_forced == 2 ? lpq_forced : 8;
-        bool spread = spread_mode != 0 && size_t(g->geom.nquads) * size_t(lpq) <= 1024;
-        const unsigned spread_threads = unsigned((size_t(g->geom.nquads) * size_t(lpq) + 63) / 64 * 64);
-        const size_t spread_lds = g->state_words * sizeof(uint32_t) + size_t(g->geom.nquads) * 8 * sizeof(uint4);
+        bool spread = spread_mode != 0 && size_t(g.nquads) * size_t(lpq) <= 1024;
+        const unsigned spread_threads = unsigned((size_t(g.nquads) * size_t(lpq) + 63) / 64 * 64);
+        const size_t spread_lds = g.state_words * sizeof(uint32_t) + size_t(g.nquads) * 8 * 16;
         if (spread && spread_mode != 2) { ... the occupancy query: not restated, the tests force mode 0 or 2 ... }
-        const unsigned threads = spread ? spread_threads : unsigned(std::min<size_t>(1024, (g->geom.nquads + 63) / 64 * 64));
-        const size_t lds = spread ? spread_lds : g->state_words * sizeof(uint32_t);"""
+        const unsigned threads = spread ? spread_threads : unsigned(std::min<size_t>(1024, (g.nquads + 63) / 64 * 64));
+        const size_t lds = spread ? spread_lds : g.state_words * sizeof(uint32_t);"""
     _, wpp, nquads = geometry(W, H)
     mode, forced = options.get("resident_spread", 1), options.get("resident_lpq", 0)
     assert mode in (0, 2), "mode 1 asks the runtime's occupancy calculation"

@@ -59,6 +59,14 @@ SHAPES = [
     Shape("resident-768x4", 768, 4, {}, "resident", False, True),
 ]
 SHAPE = {s.name: s for s in SHAPES}
+# the shapes beside the table that tests/test_mc_variants_host.py asks `resident_launch` about, and tests/test_step_policy_host.py
+# the library's rule: ((W, H, R, options), expected (spread, threads))
+LAUNCH_CASES = (((256, 136, 3, {}), (False, 192)), ((768, 44, 3, {}), (False, 192)),     # more than 128 quads: every thread has at most one
+                ((256, 1024, 3, {}), (False, 1024)),                                     # 1024 quads: no resident thread loops
+                ((256, 8, 3, {"resident_spread": 0}), (False, 64)), ((256, 8, 3, {}), (True, 64)), ((768, 4, 3, {}), (True, 128)),
+                ((256, 128, 3, {}), (True, 1024)), ((256, 132, 3, {}), (False, 192)),
+                # a container too large for every replica to be resident at once leaves the spread form: n_cu * (1024 / threads) replicas
+                ((256, 128, 256, {}), (True, 1024)), ((256, 128, 257, {}), (False, 128)), ((256, 128, 257, {"resident_spread": 2}), (True, 1024)))
 
 # ---- lattices ---------------------------------------------------------------------------------------------------------------------
 # name: (h, field signs, open_x, open_y, |Jx|, |Jy|); |h| <= 2|J| periodic, <= |J| on an open lattice (lattice_fast_path_ok).
@@ -155,7 +163,7 @@ def mc_mode(case):
 
 
 def geometry(W, H):
-    """graph.hip, build_lattice:  G.wpr = L.W / 64;  G.wpp = G.H * G.wpr;  G.nquads = G.wpp / 4;"""
+    """step_policy.hpp, lattice_shape (which graph.hip builds the lattice from):  G.wpr = W / 64;  G.wpp = H * G.wpr;  G.nquads = G.wpp / 4;"""
     wpr = W // 64
     return wpr, H * wpr, H * wpr // 4
 
@@ -168,13 +176,13 @@ def fast_path_ok(W, H):
 
 
 def cols_log2(W, H):
-    """graph.hip, build_lattice:
+    """step_policy.hpp, lattice_shape (tests/test_step_policy_host.py holds this restatement against it):
         const uint32_t cols = G.wpr / 4;
         if ((cols & (cols - 1)) == 0) {
             int cl = 0;
             while ((1u << cl) < cols) cl++;
             const uint32_t rows_per_pair = cl >= 6 ? 1 : 2 * (64u >> cl);
-            if (G.H % rows_per_pair == 0 && G.nquads % 64 == 0) G.cols_log2 = cl;
+            if (H % rows_per_pair == 0 && G.nquads % 64 == 0) G.cols_log2 = cl;
         }
     -1 otherwise; mc_kernels.hip, mc_launch_sweep:  const bool uni = g.cols_log2 >= 0;"""
     wpr, _, nquads = geometry(W, H)
@@ -187,18 +195,18 @@ def cols_log2(W, H):
 
 
 def resident_fits(W, H, options):
-    """isingmc.hip, lat_resident_fits:
-        return g->state_words * sizeof(uint32_t) <= LDS_RESIDENT_MAX_BYTES && g->geom.nquads <= 1024 && !resident_disabled(s);"""
+    """step_policy.hpp, lat_resident_fits (tests/test_step_policy_host.py holds this restatement against it):
+        return g.state_words * sizeof(uint32_t) <= LAT_RESIDENT_BYTES && g.nquads <= 1024 && o.disable_resident == 0;"""
     _, wpp, nquads = geometry(W, H)
     return 2 * wpp * 4 <= LDS_RESIDENT_MAX_BYTES and nquads <= 1024 and not options.get("disable_resident", 0)
 
 
 def resident_launch(W, H, R, options):
-    """(spread, threads) of isingmc.hip, run_mc_resident:
-        const size_t spread_threads = (size_t(g->geom.nquads) * 8 + 63) / 64 * 64;
+    """(spread, threads) of step_policy.hpp, mc_resident_launch (tests/test_step_policy_host.py holds this restatement against it):
+        const size_t spread_threads = (size_t(g.nquads) * 8 + 63) / 64 * 64;
         const bool mc_spread = mc_spread_mode != 0 && spread_threads <= 1024 &&
-                               (mc_spread_mode == 2 || R <= size_t(g->n_cu) * std::max<size_t>(1, 1024 / spread_threads));
-        const unsigned threads = mc_spread ? unsigned(spread_threads) : unsigned(std::min<size_t>(1024, (g->geom.nquads + 63) / 64 * 64));"""
+                               (mc_spread_mode == 2 || R <= size_t(g.n_cu) * std::max<size_t>(1, 1024 / spread_threads));
+        const unsigned threads = mc_spread ? unsigned(spread_threads) : unsigned(std::min<size_t>(1024, (g.nquads + 63) / 64 * 64));"""
     nquads = geometry(W, H)[2]
     mode = options.get("resident_spread", 1)
     spread_threads = (nquads * 8 + 63) // 64 * 64

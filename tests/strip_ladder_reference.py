@@ -1,8 +1,8 @@
 """The cases of the strip-ladder census (tests/test_gpu_strip_ladder.py) and everything they need that is not the kernel -- TEST
 INFRASTRUCTURE, no GPU.  lat_strip_kernel<PMJ, NW, LAD = true> (csrc/strip_kernels.hpp) holds the exchange rounds of a
 tempering ladder inside one persistent launch; which instantiation a ladder runs on follows from the couplings' signs (PMJ) and
-the strip_nw option (NW).  Here: the two selection rules restated (strip_plan of csrc/isingmc.hip, the in_kernel condition of
-isingmc_pt_run in csrc/tempering.hip), the smallest shapes of every geometry branch, the couplings, the ladders with their call
+the strip_nw option (NW).  Here: the two selection rules restated (strip_plan and pt_rounds_in_kernel of csrc/step_policy.hpp, which
+isingmc_pt_run of csrc/tempering.hip asks; tests/test_step_policy_host.py holds the restatements against them), the smallest shapes of every geometry branch, the couplings, the ladders with their call
 sequences, and the host twin: ClassicalTempering on the host swap step over the CPU oracle engine, driven one round at a time, its
 rounds recorded through the numpy rule of ladder_statistics_reference.py.  tests/test_strip_ladder_host.py proves without a GPU that
 the cases select what they claim and that the twin's rounds are not vacuous."""
@@ -17,7 +17,7 @@ from helpers import OracleLatEngine
 from oracle import exact as X
 
 
-# ---- strip_plan (csrc/isingmc.hip) restated ---------------------------------------------------------------------------------------
+# ---- strip_plan (csrc/step_policy.hpp) restated -----------------------------------------------------------------------------------
 def strip_plan(W, H, nw):
     """(qpr, S, strips) of a W x H lattice cut into strips of nw wavefronts, None where the strip kernel does not serve it: a row
     holds qpr = W / 256 quads (4 words of 32 spins of one colour), a power of two <= 32; a strip is S = 64 nw / qpr rows; the
@@ -33,7 +33,7 @@ def strip_plan(W, H, nw):
     return qpr, S, H // S
 
 
-# ---- the in_kernel condition of isingmc_pt_run (csrc/tempering.hip) restated ------------------------------------------------------
+# ---- pt_rounds_in_kernel (csrc/step_policy.hpp), the in_kernel condition of isingmc_pt_run, restated ------------------------------
 def rounds_inside_the_launch(n_slots, n_rungs, timesteps, swap_every, passes=1, tracking=False):
     """Exchange rounds that pt_run(timesteps, swap_every) decides inside one persistent launch, 0 where it takes one launch per
     round: at least two rounds, the container holds the whole ladder, rounds * swap_every <= 65536 timesteps, every replica in one
@@ -43,6 +43,19 @@ def rounds_inside_the_launch(n_slots, n_rungs, timesteps, swap_every, passes=1, 
         return 0
     return rounds - 1
 
+
+# what tests/test_strip_ladder_host.py asserts of the two restatements beside the shapes table, and tests/test_step_policy_host.py of
+# the library's rules: ((W, H, nw), expected strip_plan) and ((n_slots, n_rungs, timesteps, swap_every[, passes, tracking]), expected)
+STRIP_PLAN_CASES = (((768, 256, 4), None), ((16384, 16, 4), None),                      # qpr = 3; qpr = 64
+                    ((256, 128, 4), None), ((256, 128, 1), (1, 64, 2)),                 # the same lattice, cut by NW
+                    ((8192, 4, 4), None), ((1024, 48, 4), None))                        # the NW = 1 shapes exist for NW = 1 only
+IN_KERNEL_CASES = (((8, 8, 26, 4), 5), ((8, 8, 9, 3), 2), ((8, 8, 7, 1), 6),            # (the first two: test_inside_the_persistent_launch)
+                   ((8, 8, 3, 3), 0), ((8, 8, 5, 3), 0),                                # one round: at the kernel boundary
+                   ((4, 8, 26, 4), 0),                                                  # a shard of the ladder
+                   ((8, 8, 65536, 1), 65535), ((8, 8, 65537, 1), 0), ((8, 8, 65540, 2), 0),
+                   ((8, 8, 65537, 3), 21844),                                           # 21845 rounds = 65535 timesteps: the tail does not count
+                   ((8, 8, 26, 4, 2), 0), ((8, 8, 26, 4, 1, True), 0),                  # two passes; tracking
+                   ((1, 1, 8, 1), 7))                                                   # a ladder of one rung still runs its rounds inside
 
 # ---- shapes: the smallest at which each geometry branch of the kernel exists -------------------------------------------------------
 #        NW: ((W, H), qpr, S, strips)

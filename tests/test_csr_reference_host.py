@@ -106,7 +106,8 @@ def test_class_sizes(oracle):
 
 
 def rb_rule(blocks, R):
-    """launch_gen_timestep's rule for the replicas per thread of one class"""
+    """the rule for the replicas per thread of one class (step_policy.hpp, gen_replicas_per_thread; tests/test_step_policy_host.py
+    holds this restatement against it)"""
     rb = 8
     while rb > 1 and (R < rb or blocks * ((R + rb - 1) // rb) < 2048):
         rb //= 2

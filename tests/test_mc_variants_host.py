@@ -39,7 +39,8 @@ def test_shapes_select_what_they_are_named_for():
     assert MV.cols_log2(16384, 4) == 6 and MV.cols_log2(2048, 16) == 3 and MV.cols_log2(2048, 2048) == 3
     # resident without the spread form by the shape: more than 128 quads; 192 threads, so every thread has at most one quad
     assert MV.geometry(256, 136)[2] == 136 and MV.geometry(768, 44)[2] == 132
-    assert MV.resident_launch(256, 136, 3, {}) == (False, 192) and MV.resident_launch(768, 44, 3, {}) == (False, 192)
+    for args, want in MV.LAUNCH_CASES:
+        assert MV.resident_launch(*args) == want, args
     # lat_resident_fits admits at most 1024 quads and run_mc_resident gives every 64 quads a wave: no resident thread loops
     assert MV.resident_launch(256, 1024, 3, {}) == (False, 1024) and not MV.resident_fits(256, 1028, {})
     assert MV.resident_launch(256, 8, 3, by["resident-256x8-nospread"].options) == (False, 64)

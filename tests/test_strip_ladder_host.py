@@ -19,20 +19,14 @@ def test_strip_plan_restated():
             assert S * qpr == 64 * nw and S * strips == H   # a strip is 64 nw quads per colour; the strips tile the lattice
             assert R.strip_plan(W, S, nw) is None           # one strip
             assert R.strip_plan(W, H + 1, nw) is None       # strips that do not divide the rows
-    assert R.strip_plan(768, 256, 4) is None and R.strip_plan(16384, 16, 4) is None   # qpr = 3; qpr = 64
-    assert R.strip_plan(256, 128, 4) is None and R.strip_plan(256, 128, 1) == (1, 64, 2)   # the same lattice, cut by NW
-    assert R.strip_plan(8192, 4, 4) is None and R.strip_plan(1024, 48, 4) is None   # the NW = 1 shapes exist for NW = 1 only
+    for args, want in R.STRIP_PLAN_CASES:
+        assert R.strip_plan(*args) == want, args
 
 
 def test_in_kernel_condition_restated():
-    f = R.rounds_inside_the_launch
-    assert f(8, 8, 26, 4) == 5 and f(8, 8, 9, 3) == 2 and f(8, 8, 7, 1) == 6   # (the first two: test_inside_the_persistent_launch)
-    assert f(8, 8, 3, 3) == 0 and f(8, 8, 5, 3) == 0           # one round: at the kernel boundary
-    assert f(4, 8, 26, 4) == 0                                 # a shard of the ladder
-    assert f(8, 8, 65536, 1) == 65535 and f(8, 8, 65537, 1) == 0 and f(8, 8, 65540, 2) == 0
-    assert f(8, 8, 65537, 3) == 21844                          # 21845 rounds = 65535 timesteps: the tail does not count
-    assert f(8, 8, 26, 4, passes=2) == 0 and f(8, 8, 26, 4, tracking=True) == 0
-    assert f(1, 1, 8, 1) == 7                                  # a ladder of one rung still runs its rounds inside
+    assert len(R.IN_KERNEL_CASES) == 13
+    for args, want in R.IN_KERNEL_CASES:
+        assert R.rounds_inside_the_launch(*args) == want, args
 
 
 # ---- every case selects what it claims ----------------------------------------------------------------------------------------------
